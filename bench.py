@@ -3,8 +3,13 @@
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1 it is launched by
 torch.distributed.run, one rank per GPU (RCCL).  Rank 0 prints ONE JSON line on stdout: the COMPACT record
-(< 6 KB: the contract's fields, roofline incl. the N*d*4 leg, cpu_baseline, parity, one brief object per leg); the full record
-with every leg's roofline / notes goes to gpurun_out/bench_full.json (--full-out).
+(< 6 KB: the contract's fields, the roofline of the timed steps; with --full also the N*d*4 leg, cpu_baseline, parity and one brief
+object per leg).  A plain run sets up, warms up, times exactly K steps, writes the last step's outputs (--dump-outputs DIR) and
+prints that line, nothing else.  `--full` adds everything else the benchmark measures or checks, and writes the full record with
+every leg's roofline / notes to bench_out/bench_full.json (--full-out).
+
+--dump-outputs DIR: what the timed path returned in its last step, as DIR/indices.npy (float64), DIR/distances.npy (float32) and
+DIR/counts.npy (float64); inputs come from fixed seeds, so two builds run with the same arguments can be compared output for output.
 
 Headline workload (BASELINE.json configs[1] / configs[4]): corpus N=1,000,000 x 960 f32, L2Sqr, k=10, one step = one
 batch of nq=1000 queries (the size of data/gist_test.bin) through FlatIndex::knn semantics.  Gist1M is not
@@ -19,7 +24,7 @@ taken inside the library on its own stream during the timed steps.  `cpu_baselin
 oracle (a C restatement of the reference's Rust path, kind "port") timed on rank 0 at N=1 on a bounded
 query sample of the same corpus, and doubles as a parity check of the GPU results.
 
-At N=1 (default flags) the same run also reports, under "legs", every other item SURVEY.md 8(d) asks for:
+At N=1 with --full (default size) the same run also reports, under "legs", every other item SURVEY.md 8(d) asks for:
   flat_f32_operands  the same 1000-query step with the fp16 first pass switched off: the split-bf16 kernel streams the
                      4-B/element rows mirror, so ITS roofline is on N*d*4 bytes per corpus pass -- the figure the
                      ">= 70 % of HBM roofline" target is defined on
@@ -32,7 +37,7 @@ At N=1 (default flags) the same run also reports, under "legs", every other item
   hnsw               HNSW (M=16, efc=200, ef=128) on the first --hnsw-rows rows of that corpus (default: all 1M)
   hnsw_pq            the same graph walked with ADC distances + cached-form re-sort (HNSWIndex::knn_pq)
 each with its own roofline / cpu_baseline / parity, plus `attainable_peak_GBps` from a streaming-read probe in this run.
-`--legs none` prints the headline only (what N>1 runs always do).
+`--full --legs none` adds the CPU baseline and probes to the headline but no legs (N>1 runs never have legs).
 """
 from __future__ import annotations
 
@@ -362,7 +367,7 @@ def main():
     ap.add_argument("--nq", type=int, default=1000)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--cpu-queries", type=int, default=512,
-                    help="queries timed on the CPU oracle and parity-checked (0 = skip); 512 = ~12 s on 16 cores")
+                    help="--full: queries timed on the CPU oracle and parity-checked (0 = skip); 512 = ~12 s on 16 cores")
     ap.add_argument("--workload", choices=["flat", "pq_flat", "hnsw", "hnsw_pq", "ivf"], default="flat",
                     help="flat = the headline (BASELINE metric); pq_flat / hnsw = the other SURVEY 8d configs")
     ap.add_argument("--ef", type=int, default=0, help="pq_flat: ADC shortlist (default 100); hnsw: search ef (default 128); ivf: n_probes (default 4)")
@@ -380,10 +385,19 @@ def main():
     ap.add_argument("--half-kmul", type=int, default=0, help="flat: shortlist of the fp16 pass = max(64, kmul*k) (0: library default)")
     ap.add_argument("--param", action="append", default=[], metavar="NAME=VALUE",
                     help="developer tuning switch passed to vdb_set_param before the first step (A/B runs; results never depend on them)")
-    ap.add_argument("--full-out", type=str, default="", help="file of the full record (default gpurun_out/bench_full.json); stdout gets the compact line")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run everything else the benchmark measures or checks: the streaming-read probe, the CPU "
+                         "baseline + parity (--cpu-queries), the legs (--legs), the 8-bit filter's work statistics, the one-step-in-flight "
+                         "region of pipelined runs, the matrix-pipe probe, and the full record file (--full-out)")
+    ap.add_argument("--full-out", type=str, default="",
+                    help="file of the full record (with --full, default bench_out/bench_full.json; given explicitly, also written by a plain run); "
+                         "stdout gets the compact line")
     ap.add_argument("--dump", type=str, default="", help="rank 0 saves the last step's results to this .npz (tests)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="rank 0 writes the last timed step's outputs to DIR/indices.npy (float64), DIR/distances.npy (float32) and "
+                         "DIR/counts.npy (float64); above 64 MB in all, a fixed seeded sample of query rows (DIR/query_rows.npy)")
     ap.add_argument("--legs", choices=["auto", "all", "none"], default="auto",
-                    help="the SURVEY 8(d) report items beside the headline (N=1, flat): auto = all when the headline runs at its "
+                    help="--full: the SURVEY 8(d) report items beside the headline (N=1, flat): auto = all when the headline runs at its "
                          "default size, none = headline only")
     ap.add_argument("--hnsw-rows", type=int, default=1_000_000,
                     help="rows of the hnsw leg (BASELINE config 3 names Gist1M); the build -- batches of 1024 points as "
@@ -411,6 +425,8 @@ def main():
     # shares stdout) and exit with the child's code.  Under a launcher (WORLD_SIZE set) the flag must agree with it.
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         import socket
         import subprocess
@@ -467,13 +483,13 @@ def main():
                  if from_file else {"gistlike": "synthetic", "lowrank": "synthetic (low-rank gist-like)",
                                     "clustered": f"synthetic (1024 gist-like clusters, spread {args.cluster_spread} sigma)",
                                     "neardup": "synthetic (gist-like, 1 % near-duplicate rows in groups of 20)"}[args.data])
-    legs_on = world == 1 and wl == "flat" and (args.legs == "all" or (args.legs == "auto" and default_size))
+    legs_on = args.full and world == 1 and wl == "flat" and (args.legs == "all" or (args.legs == "auto" and default_size))
     ef = args.ef or {"pq_flat": 100, "hnsw": 128, "hnsw_pq": 128, "ivf": 4}.get(wl, 0)
     n, dim, nq, k = args.rows, args.dim, args.nq, args.k
     threads = min(len(os.sched_getaffinity(0)), 16)  # the GPU box's CPU share for one GPU
 
     attainable = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         from lab_1806_vec_db_amd.index import stream_probe
 
         attainable = round(stream_probe(local_rank, 3_840_000_000, 5), 1)  # before the corpus exists: 3.84 GB of its own
@@ -505,7 +521,7 @@ def main():
         pn, _, pval = pv.partition("=")
         ix.set_param(pn, int(pval))
     host_base = None
-    if rank == 0 and world == 1 and args.cpu_queries > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_queries > 0:
         host_base = base.cpu().numpy()
     build_s = 0.0
     if wl in ("pq_flat", "hnsw_pq"):
@@ -641,6 +657,8 @@ def main():
 
     elapsed, res = timed(ix, step, args.steps, args.warmup, drain if depth > 1 else None)
     head_steps = step_stats()
+    # the last timed step's answer as a caller receives it, copied to the host before anything else runs on the buffers
+    last_out = tuple(t.cpu().numpy() for t in res[:3]) if rank == 0 and (args.dump or args.dump_outputs) else None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -653,7 +671,7 @@ def main():
         if roofline and depth > 1:
             roofline["overlap_note"] = (f"{depth} steps in flight: the HIP-event duration of a corpus pass includes the CUs it waited for while the "
                                         "neighbouring steps' exact stage / query preparation ran beside it (passes themselves take turns)")
-            if world == 1:
+            if world == 1 and args.full:
                 # the same kernel with nothing beside it: a short region of synchronous calls right after the timed one
                 el1, _ = timed(ix, lambda: ix.flat_knn_device(queries.data_ptr(), nq, k, o_idx.data_ptr(), o_dist.data_ptr(), o_cnt.data_ptr()),
                                min(args.steps, 10), 2)
@@ -704,7 +722,7 @@ def main():
                                            "default and non-temporal loads (the non-temporal forms reach ~7.0 TB/s on this chip, the default ones ~6.2)")
 
     filter_work = None
-    if wl == "flat" and world == 1 and roofline and roofline.get("kernel") == "flat_i8":
+    if args.full and wl == "flat" and world == 1 and roofline and roofline.get("kernel") == "flat_i8":
         # what the 8-bit pass's exact stage had to do on THIS data: one more step with per-query statistics (after the timed region)
         if depth > 1:
             drain()
@@ -723,7 +741,9 @@ def main():
         return
 
     if args.dump:
-        np.savez(args.dump, idx=res[0].cpu().numpy(), dist=res[1].cpu().numpy(), cnt=res[2].cpu().numpy())
+        np.savez(args.dump, idx=last_out[0], dist=last_out[1], cnt=last_out[2])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out)
     qps = nq * args.steps / elapsed
     dname = "L2Sqr" if args.dist == "l2sqr" else "Cosine"
     names = {"flat": ("Flat brute force", "flat_knn_gist1m"), "pq_flat": (f"PQ-Flat {args.pq_bits}-bit m={dim // 3}, ADC ef={ef}", "pq_flat_knn_gist1m" + ("_8bit" if args.pq_bits == 8 else "")),
@@ -827,7 +847,7 @@ def main():
                                         "row-major fp16 image of the walks / IVF scan and IVF's 8-bit image are built on first use)")
         out["legs"] = legs
     mp = (out.get("roofline") or {}).get("matrix_pipe")
-    if mp is not None and world == 1 and mp.get("instruction", "").endswith(("f16", "i8")):
+    if args.full and mp is not None and world == 1 and mp.get("instruction", "").endswith(("f16", "i8")):
         # the matrix pipe's rate under sustained load on this box (the chip is power-limited well below the nominal peaks);
         # measured AFTER every timed region: half a second of nothing but MFMAs is not what a timed step should start behind
         from lab_1806_vec_db_amd.index import mfma_probe
@@ -840,18 +860,41 @@ def main():
                    "note": "sustained peak = vdb_mfma_probe(_i8) at the end of this run: the same instruction back to back on every SIMD, "
                            "best of 1 / 2 / 4 waves per SIMD; the chip lowers its clock under that load"})
     # the full record goes to a side file (and stays out of stdout); the FINAL stdout line is the compact one the driver parses
-    full_path = args.full_out or os.path.join(ROOT, "gpurun_out", "bench_full.json")
-    try:
-        os.makedirs(os.path.dirname(os.path.abspath(full_path)), exist_ok=True)
-        with open(full_path, "w") as fh:
-            json.dump(out, fh)
-            fh.write("\n")
-        shown = os.path.relpath(full_path, ROOT)
-    except OSError:
-        shown = None
+    shown = None
+    if args.full or args.full_out:
+        full_path = args.full_out or os.path.join(ROOT, "bench_out", "bench_full.json")
+        try:
+            os.makedirs(os.path.dirname(os.path.abspath(full_path)), exist_ok=True)
+            with open(full_path, "w") as fh:
+                json.dump(out, fh)
+                fh.write("\n")
+            shown = os.path.relpath(full_path, ROOT)
+        except OSError:
+            shown = None
     print(compact_line(out, shown), flush=True)
     if world > 1 or force_x:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the last timed step's (indices, distances, counts) as float64 / float32 / float64 .npy files.  Integers below
+    2**53 are exact in float64.  When the three exceed DUMP_LIMIT, the same fixed seeded sample of query rows is kept of each and its
+    row numbers go to query_rows.npy."""
+    idx, dist, cnt = (np.asarray(a) for a in arrays)
+    out = {"indices": idx.astype(np.float64), "distances": dist.astype(np.float32), "counts": cnt.astype(np.float64)}
+    rows = idx.shape[0]
+    per_row = sum(a.nbytes for a in out.values()) / max(rows, 1)
+    if rows and per_row * rows > DUMP_LIMIT:
+        keep = int((DUMP_LIMIT - 4096) // (per_row + 8))  # (4 KB: room for the .npy headers)
+        sel = np.sort(np.random.default_rng(1806).choice(rows, size=keep, replace=False))
+        out = {nm: a[sel] for nm, a in out.items()}
+        out["query_rows"] = sel.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for nm, a in out.items():
+        np.save(os.path.join(out_dir, nm + ".npy"), a)
 
 
 def cpu_and_parity(O, wl, ix, host_base, queries, res, gt, ncpu, k, ef, okind, threads, n, dim, nq):

@@ -64,3 +64,29 @@ def test_compact_line_of_a_multi_rank_record():
     full["n_gpus"] = 8
     c = json.loads(bench.compact_line(full, None))
     assert c["n_gpus"] == 8 and c["cpu_baseline"] is None and "legs" not in c and "full_record" not in c
+
+
+def test_dump_outputs_types_and_limit(tmp_path, monkeypatch):
+    """--dump-outputs writes float64 indices / counts and float32 distances; above the limit a fixed seeded sample of query rows,
+    the same for every array and every run, with its row numbers"""
+    import numpy as np
+
+    rng = np.random.default_rng(0)
+    idx = rng.integers(0, 1 << 40, size=(500, 10))
+    dist = rng.random((500, 10), dtype=np.float32)
+    cnt = np.full(500, 10, dtype=np.int64)
+    bench.dump_outputs(str(tmp_path / "a"), (idx, dist, cnt))
+    got = {nm: np.load(tmp_path / "a" / f"{nm}.npy") for nm in ("indices", "distances", "counts")}
+    assert got["indices"].dtype == np.float64 and got["distances"].dtype == np.float32 and got["counts"].dtype == np.float64
+    assert np.array_equal(got["indices"], idx.astype(np.float64)) and np.array_equal(got["distances"], dist)
+    assert not (tmp_path / "a" / "query_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 20000)
+    for run in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / run), (idx, dist, cnt))
+    rows = np.load(tmp_path / "b" / "query_rows.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "query_rows.npy"))
+    assert 0 < len(rows) < 500 and np.all(np.diff(rows) > 0)
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 20000
+    assert np.array_equal(np.load(tmp_path / "b" / "indices.npy"), idx[rows].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "b" / "distances.npy"), dist[rows])

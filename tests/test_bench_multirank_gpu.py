@@ -114,10 +114,10 @@ def test_pipelined_steps_with_the_rccl_exchange_and_self_launch(tmp_path):
 
 def test_bench_reads_raw_f32_files(tmp_path):
     """--base-file / --query-file: raw row-major f32 without header, the layout src/bin/convert_fvecs.rs:29-31 writes -- here the
-    reference's own gist_1000.bin / gist_test.bin; rows come from the file size, `data` names the files, parity against the oracle."""
+    reference's own gist_1000.bin / gist_test.bin; rows come from the file size, `data` names the files, parity against the oracle (--full)."""
     g = os.path.join(ROOT, "tests", "golden")
     args = ["--base-file", os.path.join(g, "gist_1000.bin"), "--query-file", os.path.join(g, "gist_test.bin"), "--steps", "2", "--warmup", "1",
-            "--legs", "none", "--cpu-queries", "48", "--nq", "200", "--dump", str(tmp_path / "f.npz")]
+            "--full", "--full-out", str(tmp_path / "full.json"), "--legs", "none", "--cpu-queries", "48", "--nq", "200", "--dump", str(tmp_path / "f.npz")]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -127,3 +127,21 @@ def test_bench_reads_raw_f32_files(tmp_path):
     assert d["idx"][0].tolist()[:3] == [918, 467, 725]  # query 0 of gist_test against gist_1000
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--base-file", os.path.join(g, "gist_1000.bin")], capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0 and "go together" in (bad.stderr + bad.stdout)
+
+
+def test_dump_outputs_are_the_last_steps_results(tmp_path):
+    """--dump-outputs DIR: the last timed step's indices / distances / counts as float64 / float32 / float64 .npy files, equal to what
+    --dump saves; a plain run (no --full) times exactly --steps steps, reports ms_per_step, and has no CPU baseline, parity or legs"""
+    d = tmp_path / "outs"
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "60000", "--nq", "96", "--dump", str(tmp_path / "p.npz"),
+            "--dump-outputs", str(d)]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and abs(line["value"] - 96 * 1e3 / line["ms_per_step"]) / line["value"] < 0.01
+    assert line["cpu_baseline"] is None and line["parity"] is None and "legs" not in line and "full_record" not in line
+    a = np.load(tmp_path / "p.npz")
+    idx, dist, cnt = np.load(d / "indices.npy"), np.load(d / "distances.npy"), np.load(d / "counts.npy")
+    assert idx.dtype == np.float64 and dist.dtype == np.float32 and cnt.dtype == np.float64
+    assert np.array_equal(idx, a["idx"].astype(np.float64)) and np.array_equal(dist, a["dist"]) and np.array_equal(cnt, a["cnt"].astype(np.float64))
+    assert idx.shape == (96, 10) and (cnt == 10).all()
