@@ -605,7 +605,7 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
     else if (n == "flat_half_redo")
         *out = idx->ix.half_redo.load();
     else if (n == "flat_half_valid")
-        *out = idx->ix.half_valid ? 1 : 0;
+        *out = idx->ix.half_m.valid ? 1 : 0;
     else if (n == "flat_gemm_coop_sets")  // the same of the fp16 / split-bf16 filter kernel
         *out = gemm_last_coop();
     else if (n == "flat_gemm8_coop_sets")  // workgroups per cooperative set of the most recent 8-bit filter launch of the process (0: none)
@@ -615,7 +615,7 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
     else if (n == "flat_i8_redo")
         *out = idx->ix.i8_redo.load();
     else if (n == "flat_i8_valid")
-        *out = idx->ix.i8_valid.load() ? 1 : 0;
+        *out = idx->ix.i8_m.valid ? 1 : 0;
     else if (n.rfind("flat_i8_rounds_", 0) == 0 && n.size() == 16 && n[15] >= '0' && n[15] <= '8')  // queries whose exact stage walked N rounds (8: 8 or more)
         *out = idx->ix.i8_rounds_hist[n[15] - '0'].load();
     else if (n == "mirror_alloc_failures")  // mirrors of this index whose allocation failed (the tier was left to the next one)

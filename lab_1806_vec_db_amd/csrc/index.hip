@@ -67,20 +67,11 @@ void Index::add_rows(const void *rows, uint64_t count, bool on_device) {
     d_sq.grow((n + count + 128) * sizeof(float), n * sizeof(float), s);  // +128: kernels may read a few entries past n
     char *dst = d_rows.as<char>() + n * row_bytes;
     VDB_HIP(hipMemcpyAsync(dst, rows, count * row_bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    bool mirror = mfma_supported((uint32_t)dim) && tiled_built;
-    uint64_t tiles_new = ((n + count + 15) / 16 + 11) / 12 * 12;  // whole 64-row items (k_flat_mfma) and whole 2/3-tile units (k_flat_gemm)
-    uint64_t tiles_old = n / 16;                                // the partially filled tile is rewritten
-    if (mirror) {
-        uint64_t tile_bytes = 16 * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float);
-        try {
-            d_tiled.grow(tiles_new * tile_bytes, tiles_old * tile_bytes, s);
-        } catch (const AllocError &) {  // the rows went in; the mirror is dropped and rebuilt (or not) by the search that wants it
-            d_tiled.release();
-            tiled_built = false;
-            mirror = false;
-            mirror_alloc_failures += 1;
-        }
-    }
+    const uint64_t tiles_new = mirror_tiles(n + count), tiles_old = n / 16;  // (the partially filled tile is rewritten)
+    const uint64_t tile_bytes = 16 * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float);
+    // a built split-bf16 mirror is extended; one that cannot grow is dropped and rebuilt (or not) by the search that wants it
+    const bool mirror = mfma_supported((uint32_t)dim) && tiled_m.valid &&
+                        tiled_m.attempt([&] { d_tiled.grow(tiles_new * tile_bytes, tiles_old * tile_bytes, s); });
     // row norms of the new rows and the fragment-ordered mirror of every 16-row tile that received rows (a u8 index feeds
     // these f32 build kernels widened chunks; the rows themselves stay at one byte per element)
     for_tile_chunks(*ws, tiles_old, tiles_new, n + count, [&](const float *v, uint64_t ta, uint64_t tb, uint64_t ra, uint64_t rb) {
@@ -96,19 +87,10 @@ void Index::add_rows(const void *rows, uint64_t count, bool on_device) {
         if (v > 0.0f && v < xsq_min_pos) xsq_min_pos = v;
     }
     h_sq.insert(h_sq.end(), sq.begin(), sq.end());
-    if (i8_defers_half() && half_n == n) {
-        // the 8-bit pass is this index's first tier: the fp16 mirror waits for its first use (ensure_half)
-    } else if (half_n == n) {
-        try {
-            half_refresh(*ws, n, n + count);  // needs the new xsq_max
-            half_n = n + count;
-        } catch (const AllocError &) {  // (as above: ensure_half decides at the next search)
-            d_tiled_h.release();
-            half_valid = false;
-            half_n = 0;
-            mirror_alloc_failures += 1;
-        }
-    }  // (else: already behind -- ensure_half catches up)
+    if (mirror) tiled_m.rows = n + count;
+    // an fp16 mirror in step is extended (needs the new xsq_max) unless the 8-bit pass is this index's first tier: then it waits for its
+    // first use, as does one already behind (ensure_half catches up); one that cannot grow is dropped (as above)
+    if (half_m.rows == n && !i8_defers_half() && half_m.attempt([&] { half_refresh(*ws, n, n + count); })) half_m.rows = n + count;
     {
         std::lock_guard<std::mutex> g(host_mu);
         if (on_device || elem_u8) {
@@ -136,28 +118,27 @@ void Index::swap_remove(uint64_t i) {
     if (mfma_supported((uint32_t)dim)) {  // rewrite the tiles of the moved row and of the removed last row
         for (uint64_t t : {i / 16, last / 16})
             for_tile_chunks(*ws, t, t + 1, last, [&](const float *v, uint64_t ta, uint64_t tb, uint64_t, uint64_t) {
-                if (tiled_built) launch_tile_rows(v, last, (uint32_t)dim, ta, tb, d_tiled.as<float>(), s);
+                if (tiled_m.valid) launch_tile_rows(v, last, (uint32_t)dim, ta, tb, d_tiled.as<float>(), s);
                 // same scale; the moved row's rounding error is already part of half_dx_*
-                if (half_valid && half_n == n) launch_tile_rows_h(v, last, (uint32_t)dim, ta, tb, half_sx(), d_tiled_h.p, s);
+                if (half_m.covers(n)) launch_tile_rows_h(v, last, (uint32_t)dim, ta, tb, half_sx(), d_tiled_h.p, s);
             });
     }
-    if (half_n == n) {
-        half_n = last;
-    } else {  // the mirror was behind the table: rebuilt in full by its next use (the moved row's error was never measured)
-        half_valid = false;
-        half_n = 0;
+    if (tiled_m.valid) tiled_m.rows = last;
+    // an fp16 mirror behind the table is rebuilt in full by its next use (the moved row's error was never measured)
+    if (half_m.rows == n)
+        half_m.rows = last;
+    else
+        half_m.invalidate();
+    if (i8_m.covers(n)) {  // (f32 rows only) the moved row's and the removed row's tiles, codes and constants
+        for (uint64_t t : {i / 16, last / 16})
+            launch_tile_rows_i8(d_rows.as<float>(), last, (uint32_t)dim, t, t + 1, d_mu_i8.as<float>(), i8_l1, i8_l2, d_tiled_i8.p,
+                                d_rowc_i8.as<float>(), s, dist == 1 ? d_sq.as<float>() : nullptr);  // (d_sq[i] already holds the moved row's)
+        i8_m.rows = last;
+    } else {
+        i8_m.invalidate();  // rows were added since the last search: rebuilt by the next one
     }
-    if (i8_valid) {  // (f32 rows only) the moved row's and the removed row's tiles, codes and constants
-        if (i8_n == n) {
-            for (uint64_t t : {i / 16, last / 16})
-                launch_tile_rows_i8(d_rows.as<float>(), last, (uint32_t)dim, t, t + 1, d_mu_i8.as<float>(), i8_l1, i8_l2, d_tiled_i8.p,
-                                    d_rowc_i8.as<float>(), s, dist == 1 ? d_sq.as<float>() : nullptr);  // (d_sq[i] already holds the moved row's)
-            i8_n = last;
-        } else {
-            i8_valid = false;  // rows were added since the last search: rebuilt by the next one
-            i8_n = 0;
-        }
-    }
+    rows_h_m.invalidate();  // (rebuilt by the next walk / scan that uses them)
+    rows_q8_m.invalidate();
     VDB_SYNC(s);
     {
         std::lock_guard<std::mutex> g(host_mu);
@@ -169,44 +150,53 @@ void Index::swap_remove(uint64_t i) {
     if (i < last) h_sq[i] = h_sq[last];
     h_sq.resize(last);
     n = last;
-    rows_h_n = 0;  // (rebuilt by the next walk that uses it)
-    rows_q8_n = 0;
     // xsq_max stays an upper bound (certification only needs a bound)
 }
 
-// ---- split-bf16 mirror, on first need ----------------------------------------------------------------
-// A mirror that cannot be allocated is not an error of the search that wanted it: the tier is left to the next one (8-bit -> fp16 ->
-// split-bf16 -> exact scan over the rows themselves) and the allocation is not tried again until the table changes.
-bool Index::ensure_tiled(Workspace &ws) {
-    std::lock_guard<std::mutex> g(tiled_mu);
-    if (tiled_built || n == 0) return true;
-    if (tiled_failed_n == n) return false;
-    const uint64_t tiles = ((n + 15) / 16 + 11) / 12 * 12;  // whole 64-row items (k_flat_mfma) and whole 2/3-tile units (k_flat_gemm)
-    const uint64_t tile_bytes = 16 * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float);
+// ---- images of the rows (RowMirror): a tier whose image is missing leaves its queries to the next one (8-bit -> fp16 -> split-bf16 ->
+// exact scan over the rows themselves; IVF scan: 8-bit -> fp16 -> f32 rows)
+bool RowMirror::attempt(const std::function<void()> &build) {
     try {
-        d_tiled.reserve(tiles * tile_bytes);
-    } catch (const AllocError &) {
-        tiled_failed_n = n;
-        mirror_alloc_failures += 1;
+        build();
+        return true;
+    } catch (const AllocError &) {  // (DevBuf::grow allocates before it frees: an old image, if any, is intact but stale)
+        for (DevBuf *b : bufs) b->release();
+        invalidate();
+        failures += 1;
         return false;
     }
-    for_tile_chunks(ws, 0, tiles, n, [&](const float *v, uint64_t ta, uint64_t tb, uint64_t, uint64_t) {
-        launch_tile_rows(v, n, (uint32_t)dim, ta, tb, d_tiled.as<float>(), ws.stream);
+}
+bool RowMirror::ensure(uint64_t n, const std::function<bool()> &current, const std::function<void()> &build) {
+    std::lock_guard<std::mutex> g(mu);
+    if (current()) return true;
+    if (failed_n == n) return false;
+    if (attempt(build)) return true;
+    failed_n = n;
+    return false;
+}
+
+bool Index::ensure_tiled(Workspace &ws) {
+    if (n == 0) return true;
+    return tiled_m.ensure(n, [&] { return tiled_m.covers(n); }, [&] {
+        const uint64_t tiles = mirror_tiles(n);
+        d_tiled.reserve(tiles * 16 * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float));
+        for_tile_chunks(ws, 0, tiles, n, [&](const float *v, uint64_t ta, uint64_t tb, uint64_t, uint64_t) {
+            launch_tile_rows(v, n, (uint32_t)dim, ta, tb, d_tiled.as<float>(), ws.stream);
+        });
+        VDB_SYNC(ws.stream);
+        tiled_m.set(n);
     });
-    VDB_SYNC(ws.stream);
-    tiled_built = true;
-    return true;
 }
 
 uint64_t Index::hbm_bytes_per_row() const {
     uint64_t b = dim * elem_size() + sizeof(float);  // VecSet row + dist_cache entry
     if (mfma_supported((uint32_t)dim)) {
-        if (tiled_built) b += uint64_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float);
-        if (half_valid) b += uint64_t(mfma_dim_pad((uint32_t)dim)) * sizeof(uint16_t);
+        if (tiled_m.valid) b += uint64_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float);
+        if (half_m.valid) b += uint64_t(mfma_dim_pad((uint32_t)dim)) * sizeof(uint16_t);
     }
-    if (i8_valid) b += uint64_t(mfma_dim_pad((uint32_t)dim)) + 2 * sizeof(float);
-    if (rows_h_n) b += dim * sizeof(uint16_t);
-    if (rows_q8_n) b += dim + 2 * sizeof(float);
+    if (i8_m.valid) b += uint64_t(mfma_dim_pad((uint32_t)dim)) + 2 * sizeof(float);
+    if (rows_h_m.valid) b += dim * sizeof(uint16_t);
+    if (rows_q8_m.valid) b += dim + 2 * sizeof(float);
     if (pq.present) b += pq.enc_dim * (pq.codes_t_valid ? 2 : 1);
     if (hnsw.present) b += hnsw.max_m0 * sizeof(uint32_t) + sizeof(uint32_t);
     return b;
@@ -219,15 +209,15 @@ uint64_t Index::hbm_bytes_per_row() const {
 void Index::half_refresh(Workspace &ws, uint64_t n_old, uint64_t n_new) {
     if (!gemm_f16_supported((uint32_t)dim)) return;
     if (!(xsq_max >= 0x1p-80f && xsq_max <= 0x1p80f)) {  // all-zero or extreme data: the split-bf16 / exact paths serve it
-        half_valid = false;
+        half_m.valid = false;
         return;
     }
     hipStream_t s = ws.stream;
     int e = 0;
     (void)std::frexp(xsq_max, &e);                           // xsq_max = m * 2^e, m in [0.5, 1)  =>  |x| < 2^ceil(e/2)
     const int need = e >= 0 ? (e + 1) / 2 : -((-e) / 2);
-    const bool rebuild = !half_valid || need > half_exp;
-    const uint64_t tiles_new = ((n_new + 15) / 16 + 11) / 12 * 12;  // whole units of k_flat_gemm (TW = 2 or 3)
+    const bool rebuild = !half_m.valid || need > half_exp;
+    const uint64_t tiles_new = mirror_tiles(n_new);
     const uint64_t tile_bytes = 16 * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(uint16_t);
     uint64_t t0 = n_old / 16, r0 = n_old;
     if (rebuild) {
@@ -244,14 +234,12 @@ void Index::half_refresh(Workspace &ws, uint64_t n_old, uint64_t n_new) {
         const uint64_t a = std::max(ra, r0);
         if (rb > a) launch_row_split_err(v, d_sq.as<float>(), a, rb, (uint32_t)dim, half_sx(), d_half_err.as<uint32_t>(), s);
     });
-    uint32_t *h = static_cast<uint32_t *>(ws.pinned(2 * sizeof(uint32_t)));
-    VDB_HIP(hipMemcpyAsync(h, d_half_err.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     VDB_SYNC(s);
-    float e2[2];
-    std::memcpy(e2, h, sizeof(e2));
+    float e2[2];  // (the f32 bits of the kernel's two maxima; read into this call's own storage, not the workspace's pinned block)
+    VDB_HIP(hipMemcpy(e2, d_half_err.p, sizeof(e2), hipMemcpyDeviceToHost));
     half_dx_abs = std::max(half_dx_abs, std::sqrt(e2[0]) * 1.001f);  // the kernel's f32 sums: relative error << 1e-3
     half_dx_rel = std::max(half_dx_rel, std::sqrt(e2[1]) * 1.001f);
-    half_valid = true;
+    half_m.valid = true;
 }
 
 // ---- centred 8-bit mirror (k_i8.hip) ---------------------------------------------------------------
@@ -263,30 +251,16 @@ bool Index::i8_applicable(uint32_t ksel) const {
     return flat_i8_mode == 2 || iq < 1024 || ir * 8 <= iq;
 }
 bool Index::ensure_i8(Workspace &ws) {
-    std::lock_guard<std::mutex> g(i8_mu);
-    if (i8_valid && i8_n == n) return true;
-    if (i8_failed_n == n) return false;
-    try {
-        ensure_i8_locked(ws);
-    } catch (const AllocError &) {
-        d_tiled_i8.release();
-        d_rowc_i8.release();
-        i8_valid = false;
-        i8_n = 0;
-        i8_failed_n = n;
-        mirror_alloc_failures += 1;
-        return false;
-    }
-    return true;
+    return i8_m.ensure(n, [&] { return i8_m.covers(n); }, [&] { build_i8(ws); });
 }
-void Index::ensure_i8_locked(Workspace &ws) {
+void Index::build_i8(Workspace &ws) {  // (under i8_m.mu)
     hipStream_t s = ws.stream;
     const uint32_t d = (uint32_t)dim;
-    const uint64_t tiles = ((n + 15) / 16 + 11) / 12 * 12;  // whole units of k_flat_gemm8
+    const uint64_t tiles = mirror_tiles(n);
     const uint64_t tile_bytes = 16 * size_t(mfma_dim_pad(d));
-    const bool rebuild = !i8_valid || i8_n > n || n >= 2 * i8_mu_rows;
+    const bool rebuild = !i8_m.valid || i8_m.rows > n || n >= 2 * i8_mu_rows;
     const float *xsq_cos = dist == 1 ? d_sq.as<float>() : nullptr;  // Cosine: the mirror of the UNIT rows (k_i8.hip)
-    uint64_t t0 = rebuild ? 0 : i8_n / 16;
+    uint64_t t0 = rebuild ? 0 : i8_m.rows / 16;
     d_tiled_i8.grow(tiles * tile_bytes, t0 * tile_bytes, s);
     d_rowc_i8.grow(tiles * 16 * 2 * sizeof(float), t0 * 16 * 2 * sizeof(float), s);
     if (rebuild) {
@@ -319,30 +293,17 @@ void Index::ensure_i8_locked(Workspace &ws) {
     }
     launch_tile_rows_i8(d_rows.as<float>(), n, d, t0, tiles, d_mu_i8.as<float>(), i8_l1, i8_l2, d_tiled_i8.p, d_rowc_i8.as<float>(), s, xsq_cos);
     VDB_SYNC(s);
-    i8_n = n;
-    i8_valid = true;
+    i8_m.set(n);
 }
 
 bool Index::i8_defers_half() const {
     return !elem_u8 && flat_i8_mode != 1 && (dim & 3) == 0 && gemm8_supported((uint32_t)dim);
 }
 bool Index::ensure_half(Workspace &ws) {
-    std::lock_guard<std::mutex> g(half_mu);
-    if (half_n != n) {
-        if (half_failed_n == n) return false;
-        try {
-            half_refresh(ws, half_n > n ? 0 : half_n, n);
-            half_n = n;
-        } catch (const AllocError &) {  // (DevBuf::grow allocates before it frees: the old mirror, if any, is intact but stale)
-            d_tiled_h.release();
-            half_valid = false;
-            half_n = 0;
-            half_failed_n = n;
-            mirror_alloc_failures += 1;
-            return false;
-        }
-    }
-    return half_valid;
+    return half_m.ensure(n, [&] { return half_m.rows == n; }, [&] {
+        half_refresh(ws, half_m.rows > n ? 0 : half_m.rows.load(), n);
+        half_m.rows = n;
+    }) && half_m.valid;
 }
 
 void Index::prepare_flat(bool all_tiers) {
@@ -356,42 +317,31 @@ void Index::prepare_flat(bool all_tiers) {
     if (!first || all_tiers) (void)ensure_tiled(*ws);
 }
 
+// the row-major images are accelerators (pre-passes, key refinement, the IVF scan's first tier): their callers go on without them
 bool Index::ensure_rows_h(Workspace &ws) {
     if (elem_u8 || dim % 64 != 0 || dim > 4096 || n == 0 || !ensure_half(ws)) return false;
-    std::lock_guard<std::mutex> g(rows_h_mu);
-    if (rows_h_n == n && rows_h_exp == half_exp) return true;
-    if (rows_h_failed_n == n) return false;
-    uint64_t r0 = rows_h_n;
-    if (rows_h_exp != half_exp || rows_h_n > n) r0 = 0;
-    try {
+    return rows_h_m.ensure(n, [&] { return rows_h_m.covers(n) && rows_h_exp == half_exp; }, [&] {
+        const uint64_t r0 = rows_h_exp != half_exp || rows_h_m.rows > n ? 0 : rows_h_m.rows.load();
         d_rows_h.grow(n * dim * sizeof(uint16_t) + 16, r0 * dim * sizeof(uint16_t), ws.stream);
-    } catch (const AllocError &) {  // the image is an accelerator (pre-passes, key refinement): its callers go on without it
-        d_rows_h.release();
-        rows_h_n = 0;
-        rows_h_failed_n = n;
-        mirror_alloc_failures += 1;
-        return false;
-    }
-    launch_rows_to_half(d_rows.as<float>() + r0 * dim, (n - r0) * dim, half_sx(), d_rows_h.as<uint16_t>() + r0 * dim, ws.stream);
-    VDB_SYNC(ws.stream);
-    rows_h_n = n;
-    rows_h_exp = half_exp;
-    return true;
+        launch_rows_to_half(d_rows.as<float>() + r0 * dim, (n - r0) * dim, half_sx(), d_rows_h.as<uint16_t>() + r0 * dim, ws.stream);
+        VDB_SYNC(ws.stream);
+        rows_h_m.set(n);
+        rows_h_exp = half_exp;
+    });
 }
 
 bool Index::ensure_rows_q8(Workspace &ws) {
     if (elem_u8 || dim % 64 != 0 || dim > 1024 || n == 0) return false;  // (dim * 127^2 < 2^24: the integer sums are exact as f32)
-    std::lock_guard<std::mutex> g(rows_q8_mu);
-    if (rows_q8_n == n) return true;
-    const uint64_t r0 = rows_q8_n > n ? 0 : rows_q8_n;
-    d_rows_q8.grow(n * dim + 16, r0 * dim, ws.stream);
-    d_q8_scale.grow((n + 64) * sizeof(float), r0 * sizeof(float), ws.stream);
-    d_q8_err.grow((n + 64) * sizeof(float), r0 * sizeof(float), ws.stream);
-    launch_rows_to_q8(d_rows.as<float>() + r0 * dim, n - r0, (uint32_t)dim, d_rows_q8.as<int8_t>() + r0 * dim, d_q8_scale.as<float>() + r0,
-                      d_q8_err.as<float>() + r0, ws.stream);
-    VDB_SYNC(ws.stream);
-    rows_q8_n = n;
-    return true;
+    return rows_q8_m.ensure(n, [&] { return rows_q8_m.covers(n); }, [&] {
+        const uint64_t r0 = rows_q8_m.rows > n ? 0 : rows_q8_m.rows.load();
+        d_rows_q8.grow(n * dim + 16, r0 * dim, ws.stream);
+        d_q8_scale.grow((n + 64) * sizeof(float), r0 * sizeof(float), ws.stream);
+        d_q8_err.grow((n + 64) * sizeof(float), r0 * sizeof(float), ws.stream);
+        launch_rows_to_q8(d_rows.as<float>() + r0 * dim, n - r0, (uint32_t)dim, d_rows_q8.as<int8_t>() + r0 * dim,
+                          d_q8_scale.as<float>() + r0, d_q8_err.as<float>() + r0, ws.stream);
+        VDB_SYNC(ws.stream);
+        rows_q8_m.set(n);
+    });
 }
 
 // ---- timing hooks ------------------------------------------------------------------------------
@@ -568,11 +518,11 @@ void Index::flat_small_device(Workspace &ws, const float *q, uint64_t nq, uint64
 }
 
 // ---- Flat: full pipeline ---------------------------------------------------------------------------
-void Index::flat_knn_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t *d_idx,
-                            float *d_dist, uint64_t *d_cnt, bool allow_half, uint32_t kprime_min, bool allow_i8, const float *d_dk_hint) {
+uint64_t Index::flat_knn_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t *d_idx,
+                                float *d_dist, uint64_t *d_cnt, bool allow_half, uint32_t kprime_min, bool allow_i8, const float *d_dk_hint) {
     FlatPending p;
     flat_knn_enqueue(ws, d_q, nq, k, d_idx, d_dist, d_cnt, allow_half, kprime_min, p, allow_i8, d_dk_hint);
-    flat_knn_finish(ws, p);
+    return flat_knn_finish(ws, p);
 }
 
 // Everything of a Flat call up to (not including) the host's look at the certification flags.  p.active on return: the MFMA
@@ -635,7 +585,7 @@ void Index::flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint6
     // bounds of the distances, its exact stage walks the hit list until the k-th distance is below the next bound
     // (k_flat_tail_lb).  What it cannot close in flat_i8_kprime rows goes through this function again (fp16 pass next).
     // Every tier falls through to the next when its mirror cannot be allocated (ensure_*: false).
-    const bool i8_first = allow_i8 && allow_half && kprime_min == 0 && flat_gemm_mode != 1 && (d_dk_hint ? i8_valid.load() : i8_applicable(ksel));
+    const bool i8_first = allow_i8 && allow_half && kprime_min == 0 && flat_gemm_mode != 1 && (d_dk_hint ? i8_m.valid.load() : i8_applicable(ksel));
     const bool i8 = i8_first && ensure_i8(ws);
     const bool half_wanted = !i8 && allow_half && flat_half_mode != 1 && kprime_h <= 1024 && n > kprime_h &&
                              (flat_half_mode == 2 || hq < 1024 || hr * 8 <= hq);
@@ -791,8 +741,8 @@ void Index::flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint6
         t.cosine = cosine;
         t.se = se;
         t.id_offset = id_offset;
-        // long walks (tight clusters): the keys of the hits are tightened from the row-major fp16 image first (k_redo.hip).  Decided -- and the
-        // image built, which may use the pinned block -- before this call takes its flags from that block.
+        // long walks (tight clusters): the keys of the hits are tightened from the row-major fp16 image first (k_redo.hip).  (Building the image
+        // leaves the pinned block alone, and the flags block taken below stays valid until this workspace's next, larger pinned() call.)
         bool refine = false;
         if (i8 && !i8_second && nq >= 64 && flat_i8_refine != 1) {
             bool on = flat_i8_refine == 2;
@@ -847,17 +797,11 @@ void Index::flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint6
 }
 
 // the host's half of a Flat call: wait for the stream, read the certification flags, redo what was not certified
-void Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
+uint64_t Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
     hipStream_t s = ws.stream;
-    if (!p.active) return;
+    if (!p.active) return 0;
     p.active = false;
-    const bool half = p.half, i8 = p.i8, i8_second = p.i8_second;
-    const uint32_t kprime = p.kprime, ksel = p.ksel;
     const uint64_t nq = p.nq, k = p.k;
-    const float *d_q = p.d_q;
-    uint64_t *d_idx = p.d_idx;
-    float *d_dist = p.d_dist;
-    uint64_t *d_cnt = p.d_cnt;
     // the flags go straight to pinned host memory (device-visible): no copy kernel between the last kernel and the sync
     const uint8_t *flags = static_cast<const uint8_t *>(ws.pinned(nq));
     VDB_SYNC(s);
@@ -867,16 +811,16 @@ void Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
     std::vector<uint64_t> redo;
     for (uint64_t q = 0; q < nq; q++)
         if (flags[q] & 1u) redo.push_back(q);  // (bits 1..7: rounds the 8-bit pass's exact stage walked)
-    if (half) {
+    if (p.half) {
         half_queries += nq;
         half_redo += redo.size();
     }
-    if (i8 && i8_second) {
+    if (p.i8 && p.i8_second) {
         i8_second_queries += nq;
         i8_second_redo += redo.size();
     }
-    const bool try_second = i8 && !i8_second && flat_i8_second != 1 && !redo.empty();
-    if (i8 && !i8_second) {
+    const bool try_second = p.i8 && !p.i8_second && flat_i8_second != 1 && !redo.empty();
+    if (p.i8 && !p.i8_second) {
         i8_queries += nq;
         if (!try_second) i8_redo += redo.size();  // (with a second attempt: what THAT passes on, counted below)
         if (flat_i8_refine == 0 && nq >= 64) {
@@ -895,7 +839,7 @@ void Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
                 }
             }
         }
-        if (flat_i8_stats) {
+        if (p.stats) {
             const uint32_t *qs = reinterpret_cast<const uint32_t *>(flags + ((nq + 15) & ~size_t(15)));
             uint64_t hs = 0, hm = 0;
             for (uint64_t q = 0; q < nq; q++) {
@@ -911,8 +855,8 @@ void Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
             }
         }
     }
-    if (redo.empty()) return;
-    if (!half && !i8) fallback_count += redo.size();
+    if (redo.empty()) return 0;
+    if (!p.half && !p.i8) fallback_count += redo.size();
     const uint64_t nr = redo.size();
     DevBuf rx, rq, rqs, ri, rd, rc, rdk;  // rare: allocated on demand
     rx.reserve(nr * sizeof(uint64_t));
@@ -922,28 +866,28 @@ void Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
     rd.reserve(nr * k * sizeof(float));
     rc.reserve(nr * sizeof(uint64_t));
     VDB_HIP(hipMemcpyAsync(rx.p, redo.data(), nr * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    launch_gather_rows_f32(d_q, rx.as<uint64_t>(), nr, (uint32_t)dim, rq.as<float>(), s);
+    launch_gather_rows_f32(p.d_q, rx.as<uint64_t>(), nr, (uint32_t)dim, rq.as<float>(), s);
     launch_gather_rows_f32(ws.qsq.as<float>(), rx.as<uint64_t>(), nr, 1, rqs.as<float>(), s);
     if (try_second) {
         rdk.reserve(nr * sizeof(float));
-        launch_gather_dk(d_dist, d_cnt, rx.as<uint64_t>(), nr, (uint32_t)k, ksel, rdk.as<float>(), s);
+        launch_gather_dk(p.d_dist, p.d_cnt, rx.as<uint64_t>(), nr, (uint32_t)k, p.ksel, rdk.as<float>(), s);
     }
     VDB_HIP(hipMemsetAsync(ri.p, 0, nr * k * sizeof(uint64_t), s));
     VDB_HIP(hipMemsetAsync(rd.p, 0, nr * k * sizeof(float), s));
     VDB_SYNC(s);  // (`redo` is pageable host memory: the copy above must have read it before it goes out of scope in a nested call's unwinding)
-    if (try_second) {
-        // the second 8-bit attempt; what it still cannot close goes to the fp16 tier from inside that call
-        const uint64_t before = i8_second_redo.load();
-        flat_knn_device(ws, rq.as<float>(), nr, k, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), true, 0, true, rdk.as<float>());
-        i8_redo += i8_second_redo.load() - before;  // the auto rule counts what left the 8-bit tier for good
-    } else if (i8)  // next tier: the fp16 pass (or whatever this index has instead), with its own shortlist rules
+    // the second 8-bit attempt: what it still cannot close goes to the fp16 tier from inside that call, and what it hands on is what the
+    // auto rule counts (what left the 8-bit tier for good)
+    if (try_second)
+        i8_redo += flat_knn_device(ws, rq.as<float>(), nr, k, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), true, 0, true, rdk.as<float>());
+    else if (p.i8)  // next tier: the fp16 pass (or whatever this index has instead), with its own shortlist rules
         flat_knn_device(ws, rq.as<float>(), nr, k, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), true, 0, false);
-    else if (half)
-        flat_knn_device(ws, rq.as<float>(), nr, k, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), false, kprime);
+    else if (p.half)
+        flat_knn_device(ws, rq.as<float>(), nr, k, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), false, p.kprime);
     else
-        flat_exact_device(ws, rq.as<float>(), rqs.as<float>(), nr, ksel, k, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>());
-    launch_scatter_results(ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), rx.as<uint64_t>(), nr, (uint32_t)k, d_idx, d_dist, d_cnt, s);
+        flat_exact_device(ws, rq.as<float>(), rqs.as<float>(), nr, p.ksel, k, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>());
+    launch_scatter_results(ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), rx.as<uint64_t>(), nr, (uint32_t)k, p.d_idx, p.d_dist, p.d_cnt, s);
     VDB_SYNC(s);  // rx..rc are freed on return
+    return p.i8 ? nr : 0;
 }
 
 // ---- the approximate keys of the Flat shortlist pass, for every row ------------------------------------------------

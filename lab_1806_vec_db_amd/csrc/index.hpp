@@ -4,6 +4,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -119,9 +120,14 @@ struct Workspace {
     void *h_pinned = nullptr;
     size_t h_pinned_cap = 0;
     hipEvent_t order_ev = nullptr;  // orders this workspace's stream behind a caller's stream without a host wait (vdb_*_begin)
+    // The block stays valid until the next pinned() call of a larger size, which waits for `stream` before it frees the block: nothing
+    // enqueued on the stream still uses it then.  (Mirror builds never take it: they read their results into storage of their own.)
     void *pinned(size_t bytes) {
         if (bytes > h_pinned_cap) {
-            if (h_pinned) (void)hipHostFree(h_pinned);
+            if (h_pinned) {
+                VDB_HIP(hipStreamSynchronize(stream));
+                (void)hipHostFree(h_pinned);
+            }
             h_pinned = nullptr;
             size_t want = bytes < (64u << 10) ? (64u << 10) : bytes;
             VDB_HIP(hipHostMalloc(&h_pinned, want, hipHostMallocDefault));
@@ -194,6 +200,34 @@ struct FlatPending {
     uint64_t *d_cnt = nullptr;
 };
 
+// 16-row tiles of a fragment-ordered mirror of `rows` rows: whole 64-row items (k_flat_mfma), whole 2/3-tile units (k_flat_gemm, k_flat_gemm8)
+inline uint64_t mirror_tiles(uint64_t rows) { return ((rows + 15) / 16 + 11) / 12 * 12; }
+
+// One image of the rows derived from d_rows (the Flat tiers' tiled mirrors, the row-major fp16 / 8-bit images): built by the first call
+// that wants it, kept in step by add_rows / swap_remove.  An image that cannot be allocated is not an error of the search that wanted it:
+// its buffers are released, the failure is counted, the tier is left to the next one, and ensure() does not try again until n changes.
+struct RowMirror {
+    std::mutex mu;                   // read-side calls are re-entrant: one of them builds, the others wait
+    std::atomic<bool> valid{false};  // the buffers hold the image of rows [0, rows) (both read without the lock)
+    std::atomic<uint64_t> rows{0};
+    uint64_t failed_n = ~0ull;       // row count at which the allocation failed
+    std::atomic<uint64_t> &failures;
+    std::vector<DevBuf *> bufs;      // released when an allocation fails
+    RowMirror(std::atomic<uint64_t> &f, std::initializer_list<DevBuf *> b) : failures(f), bufs(b) {}
+    bool covers(uint64_t n) const { return valid && rows == n; }
+    void set(uint64_t n) {
+        rows = n;
+        valid = true;
+    }
+    void invalidate() {  // (the buffers stay for the rebuild)
+        valid = false;
+        rows = 0;
+    }
+    bool attempt(const std::function<void()> &build);  // false: AllocError -- buffers released, image invalid, counted
+    // under the lock: current() -> true; failed at this n -> false; else attempt(build), a failure latched at n
+    bool ensure(uint64_t n, const std::function<bool()> &current, const std::function<void()> &build);
+};
+
 struct Index;
 // IVFIndex (ivf_index.rs:34-47): centroids as a small Flat index of their own, clusters as CSR over row ids
 struct IVFState {
@@ -242,21 +276,19 @@ struct Index {
         }
     }
     DevBuf d_rows, d_sq;
+    std::atomic<uint64_t> mirror_alloc_failures{0};  // images of the rows (RowMirror) whose allocation failed
     // MFMA-fragment-ordered split-bf16 mirror of d_rows (k_mfma.hip; 4 B/element), only when mfma_supported(dim).  Built
     // LAZILY by the first search that needs it (the redo tier of the fp16 pass, calls without an fp16 mirror,
     // flat_half = 1): an index whose queries all certify on the fp16 pass never pays its N*d*4 bytes of HBM.
     DevBuf d_tiled;
-    std::atomic<bool> tiled_built{false};  // d_tiled covers rows [0, n); kept in step by add_rows / swap_remove once built
-    std::mutex tiled_mu;            // read-side calls are re-entrant: one of them builds, the others wait
+    RowMirror tiled_m{mirror_alloc_failures, {&d_tiled}};
+    const std::atomic<bool> &tiled_built = tiled_m.valid;  // d_tiled covers rows [0, n) (read without the lock: statistics, tests)
     bool ensure_tiled(Workspace &ws);  // false: the split-bf16 mirror could not be allocated (the exact scan answers)
-    uint64_t tiled_failed_n = ~0ull, half_failed_n = ~0ull, i8_failed_n = ~0ull;  // row count at which a mirror's allocation failed (not retried until it changes)
-    std::atomic<uint64_t> mirror_alloc_failures{0};
     void prepare_flat(bool all_tiers);  // builds now what the first Flat search would build (vdb_index_prepare)
     uint64_t hbm_bytes_per_row() const;  // resident bytes per row over all per-row buffers (rows, norms, mirrors, codes, links)
     // scaled fp16 mirror for k_flat_gemm<GEMM_F16> (k_half.hip): rows stored as fp16(x * 2^(13 - half_exp)), every row
     // norm < 2^half_exp; half_dx_* = measured rounding error of the mirror (max |dx_r|, max |dx_r| / |x_r|)
     DevBuf d_tiled_h, d_half_err;
-    bool half_valid = false;
     int half_exp = 0;
     float half_dx_abs = 0.0f, half_dx_rel = 0.0f;
     int flat_half_mode = 0;        // 0 auto, 1 off, 2 on even after many uncertified queries
@@ -265,9 +297,8 @@ struct Index {
     void half_refresh(Workspace &ws, uint64_t n_old, uint64_t n_new);  // after rows [n_old, n_new) changed
     // An index the 8-bit pass serves (i8_defers_half) builds this mirror on FIRST NEED instead of at add time: a query the
     // 8-bit pass hands on, a call it does not take (k > 64), the walks' / IVF scan's row-major fp16 image (which shares its
-    // scale and measured error).  half_n = rows the mirror covers; ensure_half brings it up to n.
-    uint64_t half_n = 0;
-    std::mutex half_mu;
+    // scale and measured error).  half_m.rows = rows the mirror covers (valid = false with rows = n: this index has none).
+    RowMirror half_m{mirror_alloc_failures, {&d_tiled_h}};
     bool i8_defers_half() const;
     bool ensure_half(Workspace &ws);  // false: this index has no fp16 mirror (dimension, extreme norms)
     float half_sx() const { return std::ldexp(1.0f, 13 - half_exp); }
@@ -275,8 +306,7 @@ struct Index {
     // {C_r, M_r} per row.  Built by the first search that wants it (ensure_i8), extended after add_rows, kept in step by
     // swap_remove; mu / lambda are re-chosen (and everything rewritten) when the table has doubled since they were measured.
     DevBuf d_tiled_i8, d_rowc_i8, d_mu_i8;
-    std::atomic<bool> i8_valid{false};
-    uint64_t i8_n = 0;          // rows the mirror covers
+    RowMirror i8_m{mirror_alloc_failures, {&d_tiled_i8, &d_rowc_i8}};
     uint64_t i8_mu_rows = 0;    // table size when mu / lambda were measured
     float i8_l1 = 0.0f, i8_l2 = 0.0f, i8_mu_norm = 0.0f;
     int flat_i8_mode = 0;       // 0 auto, 1 off, 2 on even after many uncertified queries
@@ -301,25 +331,21 @@ struct Index {
     std::atomic<uint64_t> i8_rounds_hist[9] = {};
     std::atomic<uint64_t> i8_hits_sum{0}, i8_hits_max{0}, i8_stat_queries{0};
     std::atomic<uint64_t> i8_rows_walked{0};          // (measurement) not maintained in production
-    std::mutex i8_mu;
     bool i8_applicable(uint32_t ksel) const;
     bool ensure_i8(Workspace &ws);  // false: the mirror could not be allocated (the next tier answers)
-    void ensure_i8_locked(Workspace &ws);
+    void build_i8(Workspace &ws);
     // Row-major fp16 image of the rows, same scale and rounding as d_tiled_h (so half_dx_* bound its error as well): the
     // operand of the HNSW walk's certified pre-pass (hnsw.hip, hnsw_half_dots).  Built on the first walk that wants it,
     // extended when rows were added since, rebuilt when the scale changed.
     DevBuf d_rows_h;
-    uint64_t rows_h_n = 0;
-    uint64_t rows_h_failed_n = ~0ull;  // row count at which the image's allocation failed (not retried until it changes)
+    RowMirror rows_h_m{mirror_alloc_failures, {&d_rows_h}};
     int rows_h_exp = 0;
-    std::mutex rows_h_mu;
     bool ensure_rows_h(Workspace &ws);  // false: this index has no fp16 image (dim, element type, extreme norms)
     // 8-bit image of the rows with one scale and one measured error per row (half_rows.hpp, "8-bit tier"): the first tier of
     // the IVF scan's pre-pass; built on first use, extended after add, dropped by swap_remove
     DevBuf d_rows_q8, d_q8_scale, d_q8_err;
-    uint64_t rows_q8_n = 0;
-    std::mutex rows_q8_mu;
-    bool ensure_rows_q8(Workspace &ws);
+    RowMirror rows_q8_m{mirror_alloc_failures, {&d_rows_q8, &d_q8_scale, &d_q8_err}};
+    bool ensure_rows_q8(Workspace &ws);  // false: no 8-bit image (dim, element type, allocation): the IVF scan goes on with the fp16 tier
     std::vector<float> h_sq;  // host mirror of d_sq (4 B/row), kept in step by add_rows / swap_remove
     float xsq_max = 0.0f;
     float xsq_min_pos = 3.4e38f;  // smallest positive row |x|^2 seen (cosine certification: clamp check)
@@ -375,12 +401,13 @@ struct Index {
     // search entry points; d_* are device pointers, results [nq][k]
     // d_dk_hint (8-bit pass only): per query an upper bound of its k-th distance -> the pass runs with thresholds derived from it
     // instead of sampled ones and its exact stage may walk the whole candidate list (the second attempt of k_redo.hip)
-    void flat_knn_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t *d_idx, float *d_dist,
+    // flat_knn_device / flat_knn_finish return the queries the call's 8-bit pass handed on (0: the call did not run that pass)
+    uint64_t flat_knn_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t *d_idx, float *d_dist,
                          uint64_t *d_cnt, bool allow_half = true, uint32_t kprime_min = 0, bool allow_i8 = true,
                          const float *d_dk_hint = nullptr);
     void flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt,
                           bool allow_half, uint32_t kprime_min, FlatPending &p, bool allow_i8 = true, const float *d_dk_hint = nullptr);
-    void flat_knn_finish(Workspace &ws, FlatPending &p);
+    uint64_t flat_knn_finish(Workspace &ws, FlatPending &p);
     void flat_sorted_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t ksel, uint64_t k, uint64_t *d_idx,
                             float *d_dist, uint64_t *d_cnt);
     void scan_rows(uint64_t nrows, uint32_t d, const float *Q, uint32_t nq, int metric, const float *xsq, const float *qsq, float *out,

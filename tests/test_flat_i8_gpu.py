@@ -229,6 +229,28 @@ def test_i8_pass_redo_tiers(mods):
     _check_all(idx, d, cnt, oi, od, oc)
 
 
+def test_i8_redo_counts_what_the_second_attempt_handed_on(mods):
+    """a synchronous call whose first walk closes nothing (flat_gemm_debug = 1: nothing passes the filter) hands every query to the second
+    8-bit attempt, which hands them on again: what the call adds to flat_i8_redo is exactly what that attempt added to flat_i8_second_redo"""
+    vdb, O = mods
+    rng = np.random.default_rng(8)
+    n, dim, nq = 40000, 192, 96
+    base = rng.standard_normal((n, dim)).astype(np.float32)
+    qs = rng.standard_normal((nq, dim)).astype(np.float32)
+    oi, od, oc = O.flat_knn_batch(base, qs, 10, 0, nthreads=8)
+    ix = vdb.GpuIndex(dim, "l2sqr")
+    ix.batch_add(base)
+    ix.set_flat_mode(2)
+    ix.set_param("flat_i8", 2)
+    ix.set_param("flat_gemm_debug", 1)
+    r0, s0, q0 = ix.get_stat("flat_i8_redo"), ix.get_stat("flat_i8_second_redo"), ix.get_stat("flat_i8_second_queries")
+    idx, d, cnt = ix.flat_knn(qs, 10)
+    _check_all(idx, d, cnt, oi, od, oc)
+    assert ix.get_stat("flat_i8_second_queries") - q0 == nq
+    assert ix.get_stat("flat_i8_redo") - r0 == ix.get_stat("flat_i8_second_redo") - s0 > 0
+    ix.close()
+
+
 def test_i8_mirror_upkeep(mods):
     """rows added after the first search (extension), a table that doubles (re-centring), swap_remove of rows in the middle,
     at the end and down to a ragged tile -- every state against the oracle"""

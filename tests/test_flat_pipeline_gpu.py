@@ -51,3 +51,31 @@ def test_begin_end_equals_synchronous_call(n, dim, style):
     with pytest.raises(vdb.VdbError):
         ix.flat_knn_device_end(None)
     ix.close()
+
+
+def test_end_reads_the_statistics_its_begin_asked_for():
+    """flat_i8_stats switched on between _begin and _end: the call began without the per-query statistics block behind its flags, so its
+    _end adds nothing to them (it reads the call's own state, not the index's current setting); the next call is counted"""
+    torch = pytest.importorskip("torch")
+    import lab_1806_vec_db_amd as vdb
+
+    rng = np.random.default_rng(5)
+    n, dim, nq, k = 40000, 128, 100, 10
+    base = rng.standard_normal((n, dim)).astype(np.float32)
+    qs = rng.standard_normal((nq, dim)).astype(np.float32)
+    ix = vdb.GpuIndex(dim, "l2sqr")
+    ix.batch_add(base)
+    q = _dev(torch, qs)
+    o = (torch.zeros((nq, k), dtype=torch.int64, device="cuda"), torch.zeros((nq, k), dtype=torch.float32, device="cuda"),
+         torch.zeros((nq,), dtype=torch.int64, device="cuda"))
+    torch.cuda.synchronize()
+    st = torch.cuda.current_stream().cuda_stream
+    h = ix.flat_knn_device_begin(q.data_ptr(), nq, k, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), stream=st)
+    ix.set_param("flat_i8_stats", 1)
+    ix.flat_knn_device_end(h)
+    assert ix.get_stat("flat_i8_queries") == nq and ix.get_stat("flat_i8_stat_queries") == 0
+    si, sd, sc = ix.flat_knn(qs, k)
+    assert np.array_equal(o[0].cpu().numpy().astype(np.uint64), si) and np.array_equal(o[1].cpu().numpy(), sd)
+    assert o[2].cpu().numpy().tolist() == sc.tolist()
+    assert ix.get_stat("flat_i8_queries") == 2 * nq and ix.get_stat("flat_i8_stat_queries") == nq
+    ix.close()

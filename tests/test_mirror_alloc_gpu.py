@@ -142,3 +142,45 @@ def test_key_refinement_without_room_for_the_fp16_image(mods):
     finally:
         ix.set_param("debug_alloc_fail_over", 0)
         ix.close()
+
+
+def test_ivf_scan_without_room_for_the_8bit_image(mods):
+    """the IVF scan's 8-bit image (first tier of its certified pre-pass) is an accelerator like the Flat mirrors: when it cannot be allocated
+    the scan goes on with the fp16 tier (the oracle's answers), the failure is counted once and not retried until rows are added"""
+    vdb, O = mods
+    n, dim, nq, k, npb = 24000, 128, 24, 3, 30  # 30 clusters of ~800 rows, 30 probes: lists long enough for the 8-bit tier
+    base, qs = gist_like(n, dim=dim, seed=5), gist_like(nq, dim=dim, seed=6)
+    ix = vdb.GpuIndex(dim, "l2sqr")
+    ix.batch_add(base)
+    ix.ivf_build(30, train_n=2000, max_iter=5, seed=3)
+    ex = ix.ivf_export()
+    iv = O.IVF(base, ex["centroids"], 0, assign=ex["assign"])
+    ix.prof_enable(True)  # (the scan's tier statistics are kept by measurement calls)
+    try:
+        ix.set_param("ivf_q8", 0)  # the fp16 image and the workspaces of this shape exist after this call
+        i0, d0, c0 = ix.ivf_knn(qs, k, npb)
+        ix.set_param("ivf_q8", 1)
+        ix.set_param("debug_alloc_fail_over", n * dim // 2)
+        f0 = ix.get_stat("mirror_alloc_failures")
+        for _ in range(2):
+            idx, d, cnt = ix.ivf_knn(qs, k, npb)
+            assert ix.get_stat("ivf_last_kept_q8") == 0 and ix.get_stat("mirror_alloc_failures") == f0 + 1
+            assert np.array_equal(idx, i0) and np.array_equal(d, d0) and np.array_equal(cnt, c0)
+        for q in range(nq):
+            oi, od = iv.knn(qs[q], k, npb)
+            assert cnt[q] == len(oi) and idx[q, :len(oi)].tolist() == oi.tolist() and np.array_equal(d[q, :len(oi)], od), q
+        ix.set_param("debug_alloc_fail_over", 0)  # memory is back, the table is the same: still not retried
+        ix.ivf_knn(qs, k, npb)
+        assert ix.get_stat("ivf_last_kept_q8") == 0 and ix.get_stat("mirror_alloc_failures") == f0 + 1
+        ix.batch_add(base[:64])  # the table changes (the clusters are rebuilt): built and used
+        ix.ivf_build(30, train_n=2000, max_iter=5, seed=3)
+        ix.set_param("ivf_q8", 0)
+        i0, d0, c0 = ix.ivf_knn(qs, k, npb)
+        ix.set_param("ivf_q8", 1)
+        idx, d, cnt = ix.ivf_knn(qs, k, npb)
+        assert ix.get_stat("ivf_last_kept_q8") > 0 and ix.get_stat("mirror_alloc_failures") == f0 + 1
+        assert np.array_equal(idx, i0) and np.array_equal(d, d0) and np.array_equal(cnt, c0)
+    finally:
+        ix.set_param("debug_alloc_fail_over", 0)
+        ix.set_param("ivf_q8", 1)
+        ix.close()
