@@ -185,6 +185,8 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *   "flat_half_queries"  queries that went through the fp16 first pass,
  *   "flat_half_redo"     of those, the ones it could not certify (redone with the split-bf16 pass),
  *   "pq_adc16_queries"   queries whose ADC scan ran on the quantised 16-bit tables (k_pq_adc16) since the table was attached,
+ *   "pq_adc16_redo"      of those, the ones it handed to the f32 scan (candidate list overflowed, or fewer than ef rows at or
+ *                        below the threshold),
  *   "flat_half_valid"    1 when the index holds the fp16 mirror,
  *   "flat_i8_queries", "flat_i8_redo", "flat_i8_valid"  the same three for the 8-bit first pass (queries through it, queries it handed
  *                        on to the next tier, mirror present),

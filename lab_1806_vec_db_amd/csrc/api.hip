@@ -648,6 +648,8 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.ivf.last_kept.load();
     else if (n == "pq_adc16_queries")
         *out = idx->ix.pq.adc16_queries.load();
+    else if (n == "pq_adc16_redo")
+        *out = idx->ix.pq.adc16_redo.load();
     else if (n == "flat_i8_refine_queries")
         *out = idx->ix.i8_refine_queries.load();
     else if (n == "flat_i8_refine_on")

@@ -2603,6 +2603,7 @@ static void pq_adc_shortlist(Index &ix, Workspace &ws, const float *d_q, uint64_
     std::vector<uint64_t> redo;
     for (uint64_t q = 0; q < nq; q++)
         if (hv[q] > cap || (q16 ? hv[nq + q] : hv[q]) < need) redo.push_back(q);
+    if (q16) pq.adc16_redo += redo.size();
     for (uint64_t q : redo) dense_group(q, 1);
 }
 

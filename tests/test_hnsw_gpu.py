@@ -220,3 +220,25 @@ def test_gpu_assisted_builder_matches_oracle_builder(mods, dist, kind):
     for q in range(8):
         oi, od = oh.knn(qs[q], 5, 40)
         assert idx[q, :len(oi)].tolist() == oi.tolist() and np.array_equal(d[q, :len(od)], od)
+
+
+def test_gpu_assisted_builder_at_bench_settings(mods):
+    """The builder at the bench's settings (M 16, ef_construction 200, batches of 1024 -- they start once 8 x 1024 rows are in):
+    the GPU-assisted graph equals the oracle's all-host builder with the same level stream and batch size, list by list, and
+    the all-host run of this library's builder (hnsw_build_gpu = 1)."""
+    vdb, O = mods
+    base = gist_like(12000, dim=64, seed=1812)
+    ix = vdb.GpuIndex(64, "l2sqr")
+    ix.batch_add(base)
+    ix.hnsw_build(M=16, ef_construction=200, seed=42, batch=1024, nthreads=16)
+    g_gpu = ix.hnsw_export()
+    oh = O.HNSW.build(base, 0, M=16, ef_construction=200, seed=42, batch=1024)
+    ok, key = _graphs_equal(g_gpu, oh.graph())
+    assert ok, f"GPU-assisted graph differs from the oracle's in {key}"
+    try:
+        ix.set_param("hnsw_build_gpu", 1)
+        ix.hnsw_build(M=16, ef_construction=200, seed=42, batch=1024, nthreads=16)
+    finally:
+        ix.set_param("hnsw_build_gpu", 0)
+    ok, key = _graphs_equal(g_gpu, ix.hnsw_export())
+    assert ok, f"GPU-assisted graph differs from the all-host graph in {key}"

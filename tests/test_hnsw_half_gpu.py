@@ -123,3 +123,30 @@ def test_prepass_random_configuration(mods, seed):
     ix.hnsw_build(M=M, ef_construction=efc, seed=seed, batch=int(rng.choice([1, 16])), nthreads=4)
     ef = int(rng.choice([k, 40, 200]))
     _check(vdb, O, ix, base, qs, kind, k, ef, M, efc)
+
+
+def test_prepass_bound_under_load(mods):
+    """Rows whose fp16 rounding errors all point against the query: every element sits 0.45 of an fp16 step above a grid
+    value (the image rounds it down; the image's scale is a power of two, so the grid is the same), and every query
+    coordinate is positive.  Then dx . q = -|dx||q| (Cauchy-Schwarz with equality): the pre-pass's operand term is reached,
+    not merely bounded, and the approximate distance of every row sits 2|dx||q| above the reference's.  The distances of all
+    rows lie within a few times that term of one another, so the walk keeps meeting rows just inside its worst result: a
+    bound that kept only half of its slack would drop some of them and change the walk."""
+    vdb, O = mods
+    rng = np.random.default_rng(4343)
+    step = np.float32(2.0 ** -11)  # fp16 spacing in [0.5, 1)
+    base = (np.float32(0.75) + rng.integers(-8, 9, size=(4000, DIM)).astype(np.float32) * step
+            + np.float32(0.45) * step).astype(np.float32)
+    qs = (np.float32(1.0) + rng.uniform(0.0, 0.05, size=(24, DIM))).astype(np.float32)
+    # the construction, in float64: the error of each row's fp16 image is -0.45 steps per element, so |dx . q| = |dx||q|
+    # to within the queries' spread, and the approximate distance exceeds the reference's by >= 0.9 of the operand term
+    dx = base.astype(np.float16).astype(np.float64) - base.astype(np.float64)
+    assert np.allclose(dx, -0.45 * float(step), rtol=1e-3)
+    q64 = qs.astype(np.float64)
+    align = -(dx[:64] @ q64.T) / (np.linalg.norm(dx[:64], axis=1)[:, None] * np.linalg.norm(q64, axis=1)[None, :])
+    assert align.min() > 0.999
+    ix = vdb.GpuIndex(DIM, "l2sqr")
+    ix.batch_add(base)
+    ix.hnsw_build(M=16, ef_construction=60, seed=3, batch=32, nthreads=8)
+    dropped, nd = _check(vdb, O, ix, base, qs, 0, 10, 48, 16, 60)
+    assert dropped > 0  # the bound still rules rows out: the ones far enough above the worst result
