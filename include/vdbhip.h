@@ -108,6 +108,37 @@ typedef struct vdb_pending vdb_pending;
 int vdb_flat_knn_device_begin(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, void *d_out_idx,
                               void *d_out_dist, void *d_out_count, void *stream, vdb_pending **out);
 int vdb_flat_knn_device_end(vdb_pending *pending);
+/* ---- exact range search over the Flat rows ------------------------------------------------------------------------------------
+ * For query q with radius[q]: EVERY row whose distance D(row, q) -- the value FlatIndex::knn computes, bit for bit -- satisfies
+ * D <= radius[q], ascending by (distance, index).  This is what MetadataVecTable::search(k, upper_bound) (metadata_vec_table.rs:194-212,
+ * the comparison at :209) returns once k is at least the size of that set, without having to guess such a k: the boundary is inclusive,
+ * a NaN distance is never inside, a NaN radius gives an empty result, negative radii are compared like any other value.
+ * limit > 0: only the first `limit` pairs of every query's list, i.e. exactly search(k = limit, upper_bound = radius); 0 = no limit.
+ * Ids are local_row + id_offset.  Works on f32 and VecSet<u8> indexes (queries are f32), L2Sqr and Cosine, any dim.
+ * The output is variable-length: the call returns a result object that holds it on the index's device; read the CSR offsets with
+ * vdb_range_lims (nq + 1 values, lims[0] = 0, query q owns [lims[q], lims[q + 1])), copy the pairs out with vdb_range_copy
+ * (lims[nq] ids and distances each) and release it with vdb_range_destroy (NULL is fine).  The object does not depend on the index
+ * after the call (it may outlive writes to it, and the index itself).
+ * Read-side and re-entrant on one handle like vdb_flat_knn; nq == 0 and an empty index give empty results, a dim mismatch is an error.
+ * Memory: 12 B per returned pair in the result object, and 8 B per pair of scratch while the call runs, on top of the k-NN path's
+ * per-call scratch (128 KB per query of a 1024-query round on the 8-bit tier; 24 B per row and query of an 8-query scan pass whose radius
+ * takes in the whole table).  A result that does not fit -- device memory, or the per-index ceiling "flat_range_max_results"
+ * (vdb_set_param; pairs per call, 0 = none) -- fails the call with an error (vdb_last_error), nothing is returned and nothing aborts:
+ * radius = +inf on 1M rows x 1000 queries would be 12 GB; such calls want a limit or fewer queries per call.
+ * How it is answered (csrc/k_range.hip, docs/DESIGN_flat.md): tables of at least 16 384 f32 rows whose dimension the 8-bit pass takes run
+ * ONE pass of the 8-bit filter with a threshold derived from the radius by the certification bound itself, evaluate every hit exactly and
+ * cut at the radius; queries that bound cannot serve (NaN / infinite radius, more than 8192 hits, ...) and all other tables take the
+ * strict-order scan, 8 queries per corpus pass.  vdb_flat_set_mode applies (1 = scan only, 2 = the tier wherever the shape allows).
+ * vdb_get_stat: "flat_range_queries", "flat_range_i8_queries", "flat_range_scan_queries", "flat_range_hits" (hit-list lengths of the
+ * tier's queries; "flat_range_hits_max": the longest of them), "flat_range_results". */
+typedef struct vdb_range vdb_range;
+int vdb_flat_range(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit, vdb_range **out);
+/* device-resident queries (f32 [nq][dim]) and radii (f32 [nq]); synchronises `stream` first and returns synchronised */
+int vdb_flat_range_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, const void *d_radius, uint64_t limit,
+                          void *stream, vdb_range **out);
+int vdb_range_lims(const vdb_range *r, uint64_t *out_lims);
+int vdb_range_copy(const vdb_range *r, uint64_t *out_idx, float *out_dist);
+int vdb_range_destroy(vdb_range *r);
 /* the approximate keys the Flat shortlist pass compares with its threshold, for EVERY row, from the same kernel in its dense
  * mode (test / measurement entry point behind the certification-bound tests): out_keys [nq][len];
  * L2Sqr: key = |x|^2 - 2 S~, approximate distance = key + |q|^2;  Cosine: key = -S~ / |x|, approximate distance = 1 + key / |q|.

@@ -99,6 +99,32 @@ public:
         return out;
     }
 
+    // exact range search over the Flat rows (vdb_flat_range): per query every pair with distance <= radius[q], ascending by
+    // (distance, index) -- search(k, upper_bound) (metadata_vec_table.rs:194-212) without having to guess k; limit > 0 = at most
+    // that many per query (the nearest ones)
+    std::vector<std::vector<CandidatePair>> range_search_batch(const float *queries, uint64_t nq, const float *radius, uint64_t limit = 0) const {
+        vdb_range *r = nullptr;
+        check(vdb_flat_range(h_, queries, nq, dim_, radius, limit, &r));
+        std::vector<uint64_t> lims(nq + 1), idx;
+        std::vector<float> d;
+        int rc = vdb_range_lims(r, lims.data());
+        if (rc == VDB_OK) {
+            idx.resize(lims[nq]);
+            d.resize(lims[nq]);
+            rc = vdb_range_copy(r, idx.data(), d.data());
+        }
+        vdb_range_destroy(r);
+        check(rc);
+        std::vector<std::vector<CandidatePair>> out(nq);
+        for (uint64_t q = 0; q < nq; q++)
+            for (uint64_t j = lims[q]; j < lims[q + 1]; j++) out[q].push_back({idx[j], d[j]});
+        return out;
+    }
+    std::vector<CandidatePair> range_search(const std::vector<float> &query, float radius, uint64_t limit = 0) const {
+        require_dim(query.size());
+        return range_search_batch(query.data(), 1, &radius, limit)[0];
+    }
+
     // MetadataVecTable::build_hnsw_index / clear_hnsw_index, build_pq_table / clear_pq_table
     void build_hnsw(uint64_t M = 16, uint64_t ef_construction = 200, uint64_t seed = 42, uint64_t batch = 64,
                     int nthreads = 16) {

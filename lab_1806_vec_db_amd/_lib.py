@@ -43,6 +43,11 @@ SIGNATURES = {
     "vdb_flat_knn_device": [vp, vp, u64, u64, u64, vp, vp, vp, vp],
     "vdb_flat_knn_device_begin": [vp, vp, u64, u64, u64, vp, vp, vp, vp, C.POINTER(vp)],
     "vdb_flat_knn_device_end": [vp],
+    "vdb_flat_range": [vp, f32p, u64, u64, f32p, u64, C.POINTER(vp)],
+    "vdb_flat_range_device": [vp, vp, u64, u64, vp, u64, vp, C.POINTER(vp)],
+    "vdb_range_lims": [vp, u64p],
+    "vdb_range_copy": [vp, u64p, f32p],
+    "vdb_range_destroy": [vp],
     "vdb_flat_shortlist_keys": [vp, f32p, u64, u64, C.c_int, f32p, f32p, f32p, f32p],
     "vdb_flat_set_mode": [vp, C.c_int],
     "vdb_index_prepare": [vp, C.c_int],

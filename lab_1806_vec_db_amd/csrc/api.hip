@@ -448,6 +448,98 @@ int vdb_flat_knn_device_end(vdb_pending *pending) {
     VDB_API_END
 }
 
+// ---- exact Flat range search -------------------------------------------------------------------------------------------------------
+struct vdb_range {
+    RangeResult r;
+};
+
+static void range_check(const Index &ix, const void *queries, uint64_t nq, uint64_t dim, const void *radius, vdb_range **out) {
+    VDB_REQUIRE(out, "null out");
+    *out = nullptr;
+    VDB_REQUIRE(dim == ix.dim, "query dimension mismatch: index dim " + std::to_string(ix.dim) + ", got " + std::to_string(dim));
+    VDB_REQUIRE(nq == 0 || (queries && radius), "null argument");
+    VDB_REQUIRE(nq < (1ull << 32), "too many queries for one call");
+}
+
+int vdb_flat_range(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit, vdb_range **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    range_check(ix, queries, nq, dim, radius, out);
+    ix.use_device();
+    std::unique_ptr<vdb_range> res(new vdb_range);
+    WsLease ws(ix);
+    const float *d_q = nullptr, *d_r = nullptr;
+    if (nq) {
+        const size_t qb = nq * dim * sizeof(float), qb_pad = (qb + 255) & ~size_t(255);
+        ws->q.reserve(qb_pad + nq * sizeof(float));  // [queries | radii]
+        VDB_HIP(hipMemcpyAsync(ws->q.p, queries, qb, hipMemcpyHostToDevice, ws->stream));
+        VDB_HIP(hipMemcpyAsync(ws->q.as<char>() + qb_pad, radius, nq * sizeof(float), hipMemcpyHostToDevice, ws->stream));
+        d_q = ws->q.as<float>();
+        d_r = reinterpret_cast<const float *>(ws->q.as<char>() + qb_pad);
+    }
+    try {
+        ix.flat_range_device(*ws, d_q, nq, d_r, limit, res->r);
+    } catch (...) {
+        (void)hipStreamSynchronize(ws->stream);  // nothing of a failed call is still running when its buffers go
+        ix.prof_collect(*ws);
+        throw;
+    }
+    ix.prof_collect(*ws);
+    *out = res.release();
+    VDB_API_END
+}
+
+int vdb_flat_range_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, const void *d_radius, uint64_t limit, void *stream,
+                          vdb_range **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    range_check(ix, d_queries, nq, dim, d_radius, out);
+    ix.use_device();
+    std::unique_ptr<vdb_range> res(new vdb_range);
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
+    try {
+        ix.flat_range_device(*ws, static_cast<const float *>(d_queries), nq, static_cast<const float *>(d_radius), limit, res->r);
+    } catch (...) {
+        (void)hipStreamSynchronize(ws->stream);
+        ix.prof_collect(*ws);
+        throw;
+    }
+    ix.prof_collect(*ws);
+    *out = res.release();
+    VDB_API_END
+}
+
+int vdb_range_lims(const vdb_range *r, uint64_t *out_lims) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(r && out_lims, "null argument");
+    std::memcpy(out_lims, r->r.lims.data(), r->r.lims.size() * sizeof(uint64_t));
+    VDB_API_END
+}
+
+int vdb_range_copy(const vdb_range *r, uint64_t *out_idx, float *out_dist) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(r, "null argument");
+    const uint64_t total = r->r.lims.empty() ? 0 : r->r.lims.back();
+    if (total == 0) return VDB_OK;
+    VDB_REQUIRE(out_idx && out_dist, "null argument");
+    VDB_HIP(hipSetDevice(r->r.device));
+    VDB_HIP(hipMemcpy(out_idx, r->r.idx.p, total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    VDB_HIP(hipMemcpy(out_dist, r->r.dist.p, total * sizeof(float), hipMemcpyDeviceToHost));
+    VDB_API_END
+}
+
+int vdb_range_destroy(vdb_range *r) {
+    VDB_API_BEGIN
+    if (r) {
+        if (r->r.idx.base || r->r.dist.base) (void)hipSetDevice(r->r.device);
+        delete r;
+    }
+    VDB_API_END
+}
+
 int vdb_flat_shortlist_keys(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, int tier, float *out_keys,
                             float *out_qsq, float *out_qerr, float *out_dx4) {
     VDB_API_BEGIN
@@ -531,6 +623,10 @@ int vdb_set_param(vdb_index *idx, const char *name, int64_t value) {
     else if (n == "flat_i8_rows") {  // rows its exact stage may walk per query before giving up (multiple of 64)
         VDB_REQUIRE(value >= 64 && value <= 8192 && value % 64 == 0, "flat_i8_rows must be a multiple of 64 in [64, 8192]");
         idx->ix.flat_i8_kprime = (uint32_t)value;
+    }
+    else if (n == "flat_range_max_results") {  // ceiling on the pairs one range call may return (0: what the device can hold)
+        VDB_REQUIRE(value >= 0, "flat_range_max_results must be >= 0");
+        idx->ix.range_max_results = (uint64_t)value;
     }
     else if (n == "debug_alloc_fail_over")  // (testing aid, process-wide) device allocations of at least this many bytes fail; 0 = off
         devbuf_fail_over() = (size_t)value;
@@ -616,6 +712,18 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.i8_redo.load();
     else if (n == "flat_i8_valid")
         *out = idx->ix.i8_m.valid ? 1 : 0;
+    else if (n == "flat_range_queries")  // range calls: queries | answered by the 8-bit tier | by the strict-order scan | hits of the tier's | pairs returned
+        *out = idx->ix.range_queries.load();
+    else if (n == "flat_range_i8_queries")
+        *out = idx->ix.range_i8_queries.load();
+    else if (n == "flat_range_scan_queries")
+        *out = idx->ix.range_scan_queries.load();
+    else if (n == "flat_range_hits")
+        *out = idx->ix.range_hits.load();
+    else if (n == "flat_range_hits_max")  // (longest hit list of a query the tier answered)
+        *out = idx->ix.range_hits_max.load();
+    else if (n == "flat_range_results")
+        *out = idx->ix.range_results.load();
     else if (n.rfind("flat_i8_rounds_", 0) == 0 && n.size() == 16 && n[15] >= '0' && n[15] <= '8')  // queries whose exact stage walked N rounds (8: 8 or more)
         *out = idx->ix.i8_rounds_hist[n[15] - '0'].load();
     else if (n == "mirror_alloc_failures")  // mirrors of this index whose allocation failed (the tier was left to the next one)

@@ -89,6 +89,38 @@ constexpr uint64_t PAIR_NONE = ~0ull;  // sorts after every real pair
 
 
 #if defined(__HIPCC__)
+// ---- the 8-bit pass's bound (k_gemm8.hip / k_i8.hip keys are lower bounds: D(r, q) >= key + O_q) --------------------
+// true: every row whose key is ABOVE kappa has an exact (reference-order f32) distance above d.  One definition for its users:
+// the k-NN exact stages (flat_certify_lb, k_exact.hip: d = the k-th exact distance so far, kappa = the next key / the threshold),
+// the threshold inversion (k_i8_tau_from_dk, k_redo.hip: the tau that makes it hold for a given d) and the range search's admission
+// (k_range.hip: d = the radius, kappa = the threshold derived from it).  NaN anywhere -> false.
+// qsq_q = strict-fold |q|^2, qoff_q = O_q, mu_norm = |mu| of the centring vector, xsq_max / xsq_min_pos = largest / smallest positive
+// cached row |x|^2 of the index.
+__device__ __forceinline__ bool flat_lb_excludes(float d, float kappa, float qsq_q, float qoff_q, int cosine, float xsq_max, float xsq_min_pos,
+                                                 float mu_norm, uint32_t dim) {
+    if (cosine) {
+        // The keys bound the L2Sqr distance of the UNIT vectors: 1 - cos >= (kappa + O_q) / 2 for every row outside (k_i8.hip).  The
+        // reference's f32 value of a row outside (strict dot fold, two strict norm folds, sqrt, product, quotient, 1 - r:
+        // distance/mod.rs:60-69) is within (2 d + 8) u of the real-number cosine distance -- |dot_f - <x, q>| <= d u |x||q|, each norm
+        // (d / 2 + 1) u relative, |cos| <= 1 -- provided the max(|x||q|, 1e-10) clamp is inactive and no norm leaves [1e-30, 1e30]
+        // (checked here through the smallest positive row norm of the index; rows the cached |x|^2 does not describe carry keys of
+        // -FLT_MAX and are always evaluated).  The key's own two roundings: 2 u (|x~||q~| + |key|) <= 4 u (2 + 2 |mu|)^2 as for
+        // L2Sqr with unit norms, halved with the key; 4 u |lower| for kappa + O_q.
+        const float qs = qsq_q, qn = sqrtf(qs);
+        const bool plain = xsq_min_pos >= 1e-30f && qs >= 1e-30f && qs <= 1e30f && sqrtf(xsq_min_pos) * qn > 1e-9f;
+        const float nr = 2.0f + 2.0f * mu_norm;
+        float lower = 0.5f * (kappa + qoff_q);
+        lower = lower - 4.0f * 5.9604645e-8f * fabsf(lower) - float(2 * dim + 16) * 5.9604645e-8f * 1.01f - 2.0f * 5.9604645e-8f * nr * nr;
+        return plain && d < lower;
+    }
+    const float qn = sqrtf(qsq_q);
+    const float rx = fminf(sqrtf(xsq_max), (qn + sqrtf(fmaxf(d, 0.0f))) * 1.001f);  // (flat_certify_flag, k_exact.hip: why)
+    const float nr = rx + qn + 2.0f * mu_norm;
+    float lower = kappa + qoff_q;
+    lower = lower - float(dim + 8) * 5.9604645e-8f * 1.01f * fabsf(lower) - 4.0f * 5.9604645e-8f * nr * nr;
+    return d < lower;
+}
+
 // ---- 64-key bitonic networks across the lanes of a wave (no LDS) ---------------------------------------------------
 // The partner of a compare-exchange stage is lane ^ j with j a power of two known at compile time (the networks are fully
 // unrolled).  __shfl_xor is a ds_bpermute_b32 per 32-bit word -- an LDS-crossbar round trip of ~100 cycles that every stage of

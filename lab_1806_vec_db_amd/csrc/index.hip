@@ -243,10 +243,12 @@ void Index::half_refresh(Workspace &ws, uint64_t n_old, uint64_t n_new) {
 }
 
 // ---- centred 8-bit mirror (k_i8.hip) ---------------------------------------------------------------
+bool Index::i8_mirror_applicable() const {
+    if (elem_u8 || flat_i8_mode == 1 || (dim & 3) != 0 || !gemm8_supported((uint32_t)dim) || n <= 64) return false;
+    return xsq_max <= 0x1p80f;  // extreme data: the other tiers' own guards decide
+}
 bool Index::i8_applicable(uint32_t ksel) const {
-    if (elem_u8 || flat_i8_mode == 1 || (dim & 3) != 0 || !gemm8_supported((uint32_t)dim)) return false;
-    if (!flat_tail_lb_supported((uint32_t)dim, flat_i8_kprime, ksel) || n <= 64) return false;
-    if (!(xsq_max <= 0x1p80f)) return false;  // extreme data: the other tiers' own guards decide
+    if (!i8_mirror_applicable() || !flat_tail_lb_supported((uint32_t)dim, flat_i8_kprime, ksel)) return false;
     const uint64_t iq = i8_queries.load(), ir = i8_redo.load();
     return flat_i8_mode == 2 || iq < 1024 || ir * 8 <= iq;
 }
@@ -888,6 +890,197 @@ uint64_t Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
     launch_scatter_results(ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), rx.as<uint64_t>(), nr, (uint32_t)k, p.d_idx, p.d_dist, p.d_cnt, s);
     VDB_SYNC(s);  // rx..rc are freed on return
     return p.i8 ? nr : 0;
+}
+
+// ---- Flat: exact range search ----------------------------------------------------------------------------------------------------
+// Every row with D(row, q) <= r_q, D the reference-order f32 distance of FlatIndex::knn, ascending by (distance, index): what
+// `search(k, upper_bound = r)` (metadata_vec_table.rs:194-212) returns once k covers the whole set; limit > 0 = that call with k = limit.
+//   8-bit tier (k_range.hip, docs/DESIGN_flat.md "Range search"): tau_q from r_q by the inversion of the certification bound, admission by
+//     the bound itself, ONE filter pass, exact keys of every hit, cut at r_q + sort.  No sample, no selection, no rounds, no redo tier.
+//   scan tier: the strict-order scan, 8 queries per corpus pass, for scan mode, small tables, u8 rows, dimensions the 8-bit pass does not
+//     take, a mirror that cannot be allocated, and the queries the tier did not admit or whose hit list overflowed.
+// The sorted pair keys of both tiers go to a pool in the order they are produced; the CSR arrays are gathered from it at the end
+// (8 B per pair in the pool + 12 B per pair in the result).  Range calls neither read nor write the k-NN tiers' auto-off counters.
+void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit, RangeResult &out) {
+    hipStream_t s = ws.stream;
+    out.device = device;
+    out.nq = nq;
+    out.lims.assign(nq + 1, 0);
+    range_queries += nq;
+    if (nq == 0) return;
+    if (n == 0) {  // empty VecSet -> empty results
+        range_scan_queries += nq;
+        return;
+    }
+    constexpr uint32_t CAND_CAP = 8192;
+    constexpr uint64_t QCH = 1024;  // queries per round of the 8-bit tier (8 groups of 128: 64 MB of hit lists, 64 MB of exact keys)
+    constexpr uint32_t BQ = 8;      // queries per corpus pass of the scan
+    const int cosine = dist == 1 ? 1 : 0;
+    const int metric = cosine ? MET_COSINE : MET_L2_DIRECT;
+    const uint64_t cap_pairs = range_max_results ? range_max_results : ~0ull;
+    std::vector<uint64_t> h_off(nq, 0), h_cnt(nq, 0);
+    DevBuf pool;
+    uint64_t pool_used = 0;
+    // the pinned block of this call: [off u64 x QCH | cnt u32 x QCH | hits u32 x QCH | take u32 x QCH]; written by the kernels (cnt, hits) and
+    // by the host between two stream syncs (off, take) -- never while a kernel that reads them is in flight
+    char *hp = static_cast<char *>(ws.pinned(QCH * (sizeof(uint64_t) + 3 * sizeof(uint32_t))));
+    uint64_t *p_off = reinterpret_cast<uint64_t *>(hp);
+    uint32_t *p_cnt = reinterpret_cast<uint32_t *>(p_off + QCH), *p_hits = p_cnt + QCH, *p_take = p_hits + QCH;
+    auto pool_room = [&](uint64_t add) {
+        if (add > cap_pairs || pool_used > cap_pairs - add)
+            throw Error(1, "range search: more than " + std::to_string(cap_pairs) + " results in one call (flat_range_max_results); use a limit, "
+                           "smaller radii or fewer queries per call");
+        pool.grow((pool_used + add) * sizeof(uint64_t), pool_used * sizeof(uint64_t), s);
+    };
+    std::vector<uint64_t> scan;  // queries the scan tier answers
+    const bool tier = flat_mode != 1 && (flat_mode == 2 || n >= 16384) && flat_gemm_mode != 1 && i8_mirror_applicable() && ensure_i8(ws);
+    if (!tier) {
+        scan.resize(nq);
+        for (uint64_t q = 0; q < nq; q++) scan[q] = q;
+    }
+    for (uint64_t q0 = 0; tier && q0 < nq; q0 += QCH) {
+        const uint64_t nb = std::min<uint64_t>(QCH, nq - q0);
+        const uint64_t gq = gemm_group(), ngroups = (nb + gq - 1) / gq, nq_pad = ngroups * gq;
+        const float *Q = d_q + q0 * dim, *R = d_radius + q0;
+        ws.qsq.reserve(nq_pad * sizeof(float));
+        ws.qfrag_g.reserve(nq_pad * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float));
+        ws.qaux.reserve(3 * nq_pad * sizeof(float));
+        ws.misc.reserve(nq_pad * (sizeof(float) + sizeof(uint32_t)) + 128 * sizeof(uint32_t));  // tau | hit counters | the sets' rendezvous words
+        ws.lists.reserve(nq_pad * size_t(CAND_CAP) * sizeof(uint64_t));
+        ws.keys_b.reserve(nb * size_t(CAND_CAP) * sizeof(uint64_t));
+        float *d_tau = ws.misc.as<float>(), *d_qscale = ws.qaux.as<float>(), *d_qoff = d_qscale + nq_pad;
+        uint32_t *d_hits = reinterpret_cast<uint32_t *>(d_tau + nq_pad);
+        uint64_t *d_cand = ws.lists.as<uint64_t>(), *d_keys = ws.keys_b.as<uint64_t>();
+        launch_query_prep_i8(Q, (uint32_t)nb, (uint32_t)nq_pad, (uint32_t)dim, d_mu_i8.as<float>(), i8_l1, i8_l2, ws.qsq.as<float>(), d_qscale, d_qoff,
+                             d_hits, ws.qfrag_g.p, s, cosine);
+        launch_i8_tau_from_dk(R, (uint32_t)nb, (uint32_t)nq_pad, d_qoff, ws.qsq.as<float>(), xsq_max, i8_mu_norm, (uint32_t)dim, cosine, d_tau, s);
+        launch_range_admit(R, (uint32_t)nb, d_qoff, ws.qsq.as<float>(), xsq_max, xsq_min_pos, i8_mu_norm, (uint32_t)dim, cosine, d_tau, s);
+        {  // corpus passes of calls in flight on other workspaces take turns (flat_knn_enqueue)
+            std::lock_guard<std::mutex> g(pass_mu);
+            if (pass_ev_valid) VDB_HIP(hipStreamWaitEvent(s, pass_ev, 0));
+        }
+        prof_begin(ws, "flat_range_i8", double(ngroups) * double(n) * dim);
+        launch_flat_gemm8_filter(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, d_qscale, (uint32_t)ngroups, d_rowc_i8.as<float>(), d_tau, d_cand, d_hits,
+                                 CAND_CAP, flat_gemm_debug, num_cu, s, CAND_CAP);
+        prof_end(ws);
+        {
+            std::lock_guard<std::mutex> g(pass_mu);
+            if (!pass_ev) VDB_HIP(hipEventCreateWithFlags(&pass_ev, hipEventDisableTiming));
+            VDB_HIP(hipEventRecord(pass_ev, s));
+            pass_ev_valid = true;
+        }
+        prof_begin(ws, "flat_range_exact", 0.0);
+        launch_rerank(d_rows.as<float>(), (uint32_t)dim, Q, (uint32_t)nb, metric, d_sq.as<float>(), ws.qsq.as<float>(), d_cand, d_keys, CAND_CAP, CAND_CAP,
+                      s, d_hits);
+        launch_range_cut(d_keys, CAND_CAP, d_hits, R, d_tau, (uint32_t)nb, p_cnt, p_hits, s);
+        prof_end(ws);
+        VDB_SYNC(s);
+        uint64_t add = 0, max_take = 0, hits = 0, served = 0, hmax = 0;
+        for (uint64_t j = 0; j < nb; j++) {
+            if (p_cnt[j] == RANGE_LEFT) {  // not admitted, or more hits than the list holds
+                scan.push_back(q0 + j);
+                p_take[j] = 0;
+                p_off[j] = 0;
+                continue;
+            }
+            const uint64_t t = limit ? std::min<uint64_t>(p_cnt[j], limit) : p_cnt[j];
+            h_cnt[q0 + j] = t;
+            h_off[q0 + j] = pool_used + add;
+            p_off[j] = pool_used + add;
+            p_take[j] = (uint32_t)t;
+            add += t;
+            max_take = std::max(max_take, t);
+            hits += p_hits[j];
+            hmax = std::max<uint64_t>(hmax, p_hits[j]);
+            served++;
+        }
+        range_i8_queries += served;
+        range_hits += hits;
+        for (uint64_t cur = range_hits_max.load(); hmax > cur && !range_hits_max.compare_exchange_weak(cur, hmax);) {
+        }
+        if (add) {
+            pool_room(add);
+            launch_range_append(d_keys, CAND_CAP, p_off, p_take, (uint32_t)nb, max_take, pool.as<uint64_t>(), s);
+            pool_used += add;
+            VDB_SYNC(s);  // (the pinned block is rewritten by the next round)
+        }
+    }
+    range_scan_queries += scan.size();
+    if (!scan.empty()) {
+        const uint64_t ns = scan.size(), ld = (n + 63) & ~63ull;
+        const uint32_t nblk = range_scan_blocks(n);
+        const bool all = ns == nq;  // (then scan[j] == j: the queries are used where they are)
+        DevBuf rx, rq, rr, rqs, blk;  // (like flat_knn_finish's redo set: allocated on demand)
+        rqs.reserve(BQ * sizeof(float));
+        blk.reserve(size_t(BQ) * nblk * sizeof(uint32_t));
+        if (!all) {
+            rx.reserve(ns * sizeof(uint64_t));
+            rq.reserve(size_t(BQ) * dim * sizeof(float));
+            rr.reserve(BQ * sizeof(float));
+            VDB_HIP(hipMemcpyAsync(rx.p, scan.data(), ns * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        }
+        ws.dense.reserve(size_t(BQ) * ld * sizeof(float));
+        for (uint64_t g0 = 0; g0 < ns; g0 += BQ) {
+            const uint32_t nb = (uint32_t)std::min<uint64_t>(BQ, ns - g0);
+            const float *Q = d_q + g0 * dim, *R = d_radius + g0;
+            if (!all) {
+                launch_gather_rows_f32(d_q, rx.as<uint64_t>() + g0, nb, (uint32_t)dim, rq.as<float>(), s);
+                launch_gather_rows_f32(d_radius, rx.as<uint64_t>() + g0, nb, 1, rr.as<float>(), s);
+                Q = rq.as<float>();
+                R = rr.as<float>();
+            }
+            launch_row_sqnorm(Q, nb, (uint32_t)dim, rqs.as<float>(), s);
+            prof_begin(ws, "flat_range_scan", double(n) * dim * elem_size());
+            scan_rows(n, (uint32_t)dim, Q, nb, metric, d_sq.as<float>(), rqs.as<float>(), ws.dense.as<float>(), ld, n >= 4096, s);
+            prof_end(ws);
+            launch_range_scan_select(ws.dense.as<float>(), ld, n, R, nb, blk.as<uint32_t>(), p_cnt, s);
+            VDB_SYNC(s);
+            uint64_t add = 0, max_tot = 0, max_take = 0;
+            for (uint32_t j = 0; j < nb; j++) {
+                const uint64_t q = scan[g0 + j], t = limit ? std::min<uint64_t>(p_cnt[j], limit) : p_cnt[j];
+                h_cnt[q] = t;
+                h_off[q] = pool_used + add;
+                p_off[j] = pool_used + add;
+                p_take[j] = (uint32_t)t;
+                add += t;
+                max_tot = std::max<uint64_t>(max_tot, p_cnt[j]);
+                max_take = std::max(max_take, t);
+            }
+            if (add == 0) continue;
+            pool_room(add);
+            // survivors in row order -> one padded row of pair keys per query -> sorted rows -> the pool
+            const uint64_t ldo = (max_tot + 63) & ~63ull;
+            const size_t tb = sort_rows_temp_bytes(nb, ldo);
+            ws.keys_a.reserve(size_t(nb) * ldo * sizeof(uint64_t));
+            ws.keys_b.reserve(size_t(nb) * ldo * sizeof(uint64_t));
+            ws.lists.reserve(tb);
+            VDB_HIP(hipMemsetAsync(ws.keys_a.p, 0xFF, size_t(nb) * ldo * sizeof(uint64_t), s));  // PAIR_NONE pads sort last
+            launch_range_compact(ws.dense.as<float>(), ld, n, R, nb, blk.as<uint32_t>(), ws.keys_a.as<uint64_t>(), ldo, s);
+            launch_sort_rows(ws.keys_a.as<uint64_t>(), ws.keys_b.as<uint64_t>(), nb, ldo, ws.lists.p, tb, s);
+            launch_range_append(ws.keys_b.as<uint64_t>(), ldo, p_off, p_take, nb, max_take, pool.as<uint64_t>(), s);
+            pool_used += add;
+            VDB_SYNC(s);  // (the pinned block is rewritten by the next pass)
+        }
+        VDB_SYNC(s);  // (`scan` and rx..blk go out of scope)
+    }
+    uint64_t total = 0, max_take = 0;
+    for (uint64_t q = 0; q < nq; q++) {
+        out.lims[q] = total;
+        total += h_cnt[q];
+        max_take = std::max(max_take, h_cnt[q]);
+    }
+    out.lims[nq] = total;
+    range_results += total;
+    if (total == 0) return;
+    out.idx.reserve(total * sizeof(uint64_t));
+    out.dist.reserve(total * sizeof(float));
+    DevBuf meta;  // [off nq | lims nq + 1]
+    meta.reserve((2 * nq + 1) * sizeof(uint64_t));
+    VDB_HIP(hipMemcpyAsync(meta.p, h_off.data(), nq * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    VDB_HIP(hipMemcpyAsync(meta.as<uint64_t>() + nq, out.lims.data(), (nq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    launch_range_gather(pool.as<uint64_t>(), meta.as<uint64_t>(), meta.as<uint64_t>() + nq, nq, max_take, id_offset, out.idx.as<uint64_t>(),
+                        out.dist.as<float>(), s);
+    VDB_SYNC(s);
 }
 
 // ---- the approximate keys of the Flat shortlist pass, for every row ------------------------------------------------

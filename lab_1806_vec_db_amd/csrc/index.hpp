@@ -201,6 +201,14 @@ struct FlatPending {
     uint64_t *d_cnt = nullptr;
 };
 
+// the answer of a range call (Index::flat_range_device): CSR over the queries, arrays on the index's device
+struct RangeResult {
+    int device = 0;
+    uint64_t nq = 0;
+    std::vector<uint64_t> lims;  // nq + 1 offsets, lims[0] = 0
+    DevBuf idx, dist;            // lims[nq] ids (u64, local row + id_offset) / distances (f32), per query ascending by (distance, index)
+};
+
 // 16-row tiles of a fragment-ordered mirror of `rows` rows: whole 64-row items (k_flat_mfma), whole 2/3-tile units (k_flat_gemm, k_flat_gemm8)
 inline uint64_t mirror_tiles(uint64_t rows) { return ((rows + 15) / 16 + 11) / 12 * 12; }
 
@@ -333,6 +341,7 @@ struct Index {
     std::atomic<uint64_t> i8_hits_sum{0}, i8_hits_max{0}, i8_stat_queries{0};
     std::atomic<uint64_t> i8_rows_walked{0};          // (measurement) not maintained in production
     bool i8_applicable(uint32_t ksel) const;
+    bool i8_mirror_applicable() const;  // its clauses about the mirror and the data alone (no k, no auto-off counters: the range search's)
     bool ensure_i8(Workspace &ws);  // false: the mirror could not be allocated (the next tier answers)
     void build_i8(Workspace &ws);
     // Row-major fp16 image of the rows, same scale and rounding as d_tiled_h (so half_dx_* bound its error as well): the
@@ -419,6 +428,12 @@ struct Index {
                          float *h_dx /* [4]: dx_abs, dx_rel, xsq_max, xsq_min_pos */);
     void flat_exact_device(Workspace &ws, const float *d_q, const float *d_qsq, uint64_t nq, uint32_t ksel,
                            uint64_t k, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
+    // Exact range search (k_range.hip): per query every row with D <= d_radius[q] (the first `limit` of them when limit > 0), ascending by
+    // (distance, index); returns synchronised.  8-bit tier for the queries its bound admits, strict-order scan for the rest.
+    void flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit, RangeResult &out);
+    uint64_t range_max_results = 0;  // ceiling on the pairs of one call ("flat_range_max_results"; 0: what the device can hold)
+    std::atomic<uint64_t> range_queries{0}, range_i8_queries{0}, range_scan_queries{0}, range_hits{0}, range_results{0};
+    std::atomic<uint64_t> range_hits_max{0};  // longest hit list of a query the tier answered
 };
 
 struct WsLease {

@@ -968,27 +968,8 @@ __device__ __forceinline__ uint64_t block_top64_above(const uint64_t *__restrict
 __device__ __forceinline__ uint8_t flat_certify_lb(uint64_t ek, float kappa, uint32_t q, const FlatTailArgs &a) {
     if (ek == PAIR_NONE) return 1;
     const float dk = f32_from_orderable(uint32_t(ek >> 32));
-    if (a.cosine) {
-        // The keys bound the L2Sqr distance of the UNIT vectors: 1 - cos >= (kappa + O_q) / 2 for every row outside (k_i8.hip).  The
-        // reference's f32 value of a row outside (strict dot fold, two strict norm folds, sqrt, product, quotient, 1 - r:
-        // distance/mod.rs:60-69) is within (2 d + 8) u of the real-number cosine distance -- |dot_f - <x, q>| <= d u |x||q|, each norm
-        // (d / 2 + 1) u relative, |cos| <= 1 -- provided the max(|x||q|, 1e-10) clamp is inactive and no norm leaves [1e-30, 1e30]
-        // (checked here through the smallest positive row norm of the index; rows the cached |x|^2 does not describe carry keys of
-        // -FLT_MAX and are always evaluated).  The key's own two roundings: 2 u (|x~||q~| + |key|) <= 4 u (2 + 2 |mu|)^2 as for
-        // L2Sqr with unit norms, halved with the key; 4 u |lower| for kappa + O_q.
-        const float qs = a.qsq[q], qn = sqrtf(qs);
-        const bool plain = a.xsq_min_pos >= 1e-30f && qs >= 1e-30f && qs <= 1e30f && sqrtf(a.xsq_min_pos) * qn > 1e-9f;
-        const float nr = 2.0f + 2.0f * a.se.mu_norm;
-        float lower = 0.5f * (kappa + a.se.qoff[q]);
-        lower = lower - 4.0f * 5.9604645e-8f * fabsf(lower) - float(2 * a.dim + 16) * 5.9604645e-8f * 1.01f - 2.0f * 5.9604645e-8f * nr * nr;
-        return (plain && dk < lower) ? 0 : 1;  // NaN anywhere -> not certified
-    }
-    const float qn = sqrtf(a.qsq[q]);
-    const float rx = fminf(sqrtf(a.xsq_max), (qn + sqrtf(fmaxf(dk, 0.0f))) * 1.001f);  // (flat_certify_flag: why)
-    const float nr = rx + qn + 2.0f * a.se.mu_norm;
-    float lower = kappa + a.se.qoff[q];
-    lower = lower - float(a.dim + 8) * 5.9604645e-8f * 1.01f * fabsf(lower) - 4.0f * 5.9604645e-8f * nr * nr;
-    return dk < lower ? 0 : 1;  // NaN anywhere -> not certified
+    // (the bound itself: flat_lb_excludes, common.hpp -- shared with the range search's admission)
+    return flat_lb_excludes(dk, kappa, a.qsq[q], a.se.qoff[q], a.cosine, a.xsq_max, a.xsq_min_pos, a.se.mu_norm, a.dim) ? 0 : 1;  // NaN anywhere -> not certified
 }
 // NW waves of 64 (8, 4, 2 or 1): a round = one select + ONE re-rank stage of 63 rows, 64 / NW per wave (the last position of
 // the round's 64 keys opens the next round)

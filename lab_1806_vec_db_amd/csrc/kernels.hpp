@@ -262,6 +262,28 @@ void launch_flat_refine_half(const uint16_t *rows_h, uint32_t dim, float sx, flo
                              hipStream_t s);
 void launch_i8_tau_from_dk(const float *dk, uint32_t nq, uint32_t nq_pad, const float *qoff, const float *qsq, float xsq_max, float mu_norm,
                            uint32_t dim, int cosine, float *tau, hipStream_t s);
+// k_range.hip: exact Flat range search (Index::flat_range_device)
+constexpr uint32_t RANGE_LEFT = 0xFFFFFFFFu;  // launch_range_cut's count of a query the 8-bit tier does not answer
+// tau[q] (launch_i8_tau_from_dk with dk = radius) -> -inf unless flat_lb_excludes(radius[q], tau[q]) holds (common.hpp)
+void launch_range_admit(const float *radius, uint32_t nq, const float *qoff, const float *qsq, float xsq_max, float xsq_min_pos, float mu_norm,
+                        uint32_t dim, int cosine, float *tau, hipStream_t s);
+// keys [nq][cap]: exact pair keys of the counted hit lists -> first o_cnt[q] slots of the row = the pairs with distance <= radius[q], ascending;
+// o_cnt[q] = RANGE_LEFT for a query that was not admitted (tau = -inf) or whose list overflowed; o_hits[q] = length of its hit list
+void launch_range_cut(uint64_t *keys, uint32_t cap, const uint32_t *cnt, const float *radius, const float *tau, uint32_t nq, uint32_t *o_cnt,
+                      uint32_t *o_hits, hipStream_t s);
+// dense distances [nq][ld] of rows [0, n): blk [nq][range_scan_blocks(n)] = first output slot of every row segment, total[q] = rows inside the radius
+uint32_t range_scan_blocks(uint64_t n);
+void launch_range_scan_select(const float *dist, uint64_t ld, uint64_t n, const float *radius, uint32_t nq, uint32_t *blk, uint32_t *total,
+                              hipStream_t s);
+// ... their pair keys in row order at out[q * ldo ..) (slots past total[q] are left as they are)
+void launch_range_compact(const float *dist, uint64_t ld, uint64_t n, const float *radius, uint32_t nq, const uint32_t *blk_off, uint64_t *out,
+                          uint64_t ldo, hipStream_t s);
+// pool[off[q] + j] = keys[q * ld + j], j < take[q] <= max_take;  off / take / lims: device memory or device-visible pinned host memory
+void launch_range_append(const uint64_t *keys, uint64_t ld, const uint64_t *off, const uint32_t *take, uint32_t nq, uint64_t max_take, uint64_t *pool,
+                         hipStream_t s);
+// out_idx / out_dist [lims[q], lims[q + 1]) = the pairs pool[off[q] ..) as (row + id_offset, distance)
+void launch_range_gather(const uint64_t *pool, const uint64_t *off, const uint64_t *lims, uint64_t nq, uint64_t max_take, uint64_t id_offset,
+                         uint64_t *out_idx, float *out_dist, hipStream_t s);
 void mfma_set_sample_thin(int v);
 void mfma_sample_plan(uint64_t n, uint32_t kprime, uint32_t *step, uint32_t *rank, uint32_t target_floor = 1024);  // target_floor: expected hits per query
 uint64_t mfma_sample_rows(uint64_t n, uint32_t step);

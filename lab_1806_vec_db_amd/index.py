@@ -184,6 +184,40 @@ class GpuIndex:
     def flat_knn(self, queries, k: int):
         return self._search(self._lib.vdb_flat_knn, queries, k)
 
+    def _range_out(self, h, nq: int):
+        try:
+            lims = np.zeros(nq + 1, dtype=np.uint64)
+            L.check(self._lib.vdb_range_lims(h, _ptr(lims, L.u64p)))
+            total = int(lims[nq])
+            idx = np.zeros(total, dtype=np.uint64)
+            dist = np.zeros(total, dtype=np.float32)
+            L.check(self._lib.vdb_range_copy(h, _ptr(idx, L.u64p), _ptr(dist, L.f32p)))
+            return lims, idx, dist
+        finally:
+            self._lib.vdb_range_destroy(h)
+
+    def range_search(self, queries, radius, limit: int | None = None):
+        """Exact Flat range search (vdb_flat_range): for every query ALL rows with distance <= its radius -- the distance
+        FlatIndex::knn computes, boundary included -- ascending by (distance, index); with `limit` the first `limit` of them,
+        i.e. search(k = limit, upper_bound = radius).  `radius`: one value, or one per query.
+        Returns (lims, idx, dist): query q owns idx / dist [lims[q], lims[q + 1])."""
+        q = _f32(queries)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        nq, dim = q.shape
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (nq,)))
+        if limit is not None and int(limit) <= 0:
+            raise ValueError("limit must be positive (None: no limit)")
+        h = L.vp()
+        L.check(self._lib.vdb_flat_range(self._h, _ptr(q, L.f32p), nq, dim, _ptr(r, L.f32p), int(limit or 0), C.byref(h)))
+        return self._range_out(h, nq)
+
+    def range_search_device(self, q_ptr: int, nq: int, radius_ptr: int, limit: int | None = None, stream: int = 0):
+        """the same with device-resident queries (f32 [nq][dim]) and radii (f32 [nq]); returns synchronised, results on the host"""
+        h = L.vp()
+        L.check(self._lib.vdb_flat_range_device(self._h, L.vp(q_ptr), int(nq), self.dim, L.vp(radius_ptr), int(limit or 0),
+                                                L.vp(stream), C.byref(h)))
+        return self._range_out(h, int(nq))
+
     def knn_with_ef(self, queries, k: int, ef: int):
         """IndexKNNWithEf::knn_with_ef; Flat ignores ef (dynamic_index.rs:75-80)."""
         if self.has_hnsw():

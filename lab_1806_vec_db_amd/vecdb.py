@@ -13,6 +13,8 @@ Semantics reproduced from src/database/metadata_vec_table.rs:
     always built with 4 bits (:112-152 -- a reference quirk, kept);
   * search dispatch (:194-212): (ef, pq) -> knn_pq; (ef, no pq) -> knn_with_ef; else knn; then the
     `distance <= upper_bound` filter.
+
+Beyond the reference: search_within(key, query, upper_bound) returns the COMPLETE set inside the bound (exact Flat range search).
 """
 from __future__ import annotations
 
@@ -236,6 +238,16 @@ class VecDB:
                 idx, dist = ix.knn(q, k)
             ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
             return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist) if d <= ub]
+
+    def search_within(self, key: str, query, upper_bound: float, limit: int | None = None):
+        """Every row within `upper_bound` of the query (distance <= upper_bound, as search's filter compares), nearest first: what
+        search(k, upper_bound=...) returns once k covers the whole set, without having to guess k.  Always answered exactly from the
+        table's rows (FlatIndex::knn distances), whatever indexes the table has.  `limit`: at most that many, the nearest ones."""
+        t = self._t(key)
+        q = np.asarray(query, dtype=np.float32).ravel()
+        with t.lock.read():
+            _, idx, dist = t.index.range_search(q, np.float32(upper_bound), limit)
+            return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist)]
 
     def extract_data(self, key: str):
         t = self._t(key)
