@@ -314,6 +314,31 @@ int vdb_merge_topk_gathered_async(vdb_index *idx, const void *d_gathered, uint64
                                   uint64_t off_dists, uint64_t off_counts, uint64_t n_shards, uint64_t nq, uint64_t k,
                                   void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
 
+/* ---- merge of range results (row shards; csrc/k_range_merge.hip) ------------------------------------------------------------------
+ * Shard s of a row-sharded corpus answers a range search (vdb_flat_range with GLOBAL ids, vdb_index_set_id_offset) with a CSR result:
+ * lims_s [nq + 1] (lims_s[0] = 0, relative to the shard's own pairs) and its pairs, per query ascending by (distance, id).  The answer
+ * on the whole corpus is the union of the shards' pairs in the same order, cut after `limit` pairs per query (0 = no limit) -- the first
+ * `limit` of the union are among the first `limit` of every shard, so the shards may have been asked with the same limit.
+ *   lims  [n_shards][nq + 1];  ids (u64) / dists (f32) of shard s start at element s * pair_stride of their arrays (pair_stride >= the
+ *   largest lims_s[nq]: the padded blocks of an all-gather).  Ids are full 64-bit values (id_offset + row may pass 2^32) and must differ
+ *   between shards; no NaN distances (a NaN is never inside a radius); -0.0 and +0.0 compare equal (the id decides), as in every search.
+ *   Pairs that are equal in distance AND id across shards are taken in shard order.
+ * vdb_range_merge: host utility, works without a GPU (the twin of vdb_merge_topk).  out_lims [nq + 1] is always written:
+ * out_lims[q + 1] - out_lims[q] = min(limit, sum over s of the query's count).  out_idx / out_dist hold out_lims[nq] pairs; pass both as
+ * NULL to obtain the offsets (and so the size) alone.
+ * vdb_range_merge_device: the same on the index's GPU from device buffers (the all-gathered tensors), at most 256 shards; synchronises
+ * `stream` first, returns synchronised, and hands back a result object to be read with vdb_range_lims / vdb_range_copy and released
+ * with vdb_range_destroy.  One lane per input pair places it by rank (its position in its own list + S - 1 binary searches in the
+ * others); a query of at most 4096 pairs is searched in LDS, longer ones in global memory.  Memory: 12 B per returned pair in the result
+ * object + 16 B per query.  A result above the index's "flat_range_max_results" ceiling, or one that cannot be allocated, fails the call
+ * with an error as in vdb_flat_range: nothing is returned, nothing aborts.
+ * Both calls reject lims that do not start at 0, decrease, or declare more pairs than pair_stride (an error, not a crash); with
+ * consistent lims the device merge stays inside its buffers whatever the pairs hold.  "range_merge" in vdb_prof_get is the kernel's time. */
+int vdb_range_merge(const uint64_t *lims, const uint64_t *ids, const float *dists, uint64_t n_shards, uint64_t nq, uint64_t pair_stride,
+                    uint64_t limit, uint64_t *out_lims, uint64_t *out_idx, float *out_dist);
+int vdb_range_merge_device(vdb_index *idx, const void *d_lims, const void *d_ids, const void *d_dists, uint64_t n_shards, uint64_t nq,
+                           uint64_t pair_stride, uint64_t limit, void *stream, vdb_range **out);
+
 /* ---- IVFIndex (index_algorithm/ivf_index.rs) ------------------------------
  * from_vec_set (:66-118): k-means over all columns on train_n sampled rows (0 = all; host, RNG = splitmix64(seed),
  * parity unpinned), then every row joins its nearest centroid (k_means.rs:40-57: CandidatePair order) -- computed on
@@ -410,6 +435,30 @@ int vdb_sharded_hnsw_knn_pq(vdb_sharded *sh, const float *queries, uint64_t nq, 
 int vdb_sharded_ivf_build(vdb_sharded *sh, uint64_t k_clusters, uint64_t train_n, uint64_t max_iter, float tol, uint64_t seed);
 int vdb_sharded_ivf_knn(vdb_sharded *sh, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t n_probes, uint64_t *out_idx,
                         float *out_dist, uint64_t *out_count);
+/* Exact range search (the vdb_flat_range block above) over the whole corpus of a sharded index: the answer of vdb_flat_range on the
+ * unsharded rows, pair for pair, with global ids, on every rank.  The result object lives on the process's FIRST local GPU and, like
+ * every vdb_range, does not depend on the sharded index after the call (it may outlive vdb_sharded_destroy).
+ * ROWS layout: every shard runs the local range search with the same radii and limit, then a two-phase exchange per chunk of 2048
+ * queries: phase 1, fixed size, carries every rank's nq + 1 CSR offsets, one status word and the rank's result ceiling; phase 2 the pairs, every rank's block padded
+ * to the largest shard total phase 1 reported (ids and distances in one block), skipped when that is 0; then the device merge of
+ * vdb_range_merge_device on the first local GPU.  REPLICA layout: rank r answers the query block vdb_replica_query_block(chunk, world, r),
+ * the same two phases, and the blocks are concatenated in query order (no merge).  Without a communicator (one rank) the local result is
+ * the answer and nothing is exchanged.
+ * Memory, on top of vdb_flat_range's on every shard: the send block (largest shard total of the chunk x 12 B) and the receive buffer
+ * (S x that) on every local GPU while the chunk is exchanged -- released when the call returns -- and the result (12 B per pair).
+ * nq == 0, an index without rows, a dim mismatch, NaN / infinite / negative radii: as for vdb_flat_range.  vdb_flat_set_mode and
+ * vdb_set_param of the local indexes (vdb_sharded_local) apply.  "flat_range_max_results" bounds every shard's local result of a chunk,
+ * and the SMALLEST value set on any rank bounds the chunk's merged (ROWS) / concatenated (REPLICA) result.
+ * Failure: a LOCAL range search that fails (the ceiling, device memory) still takes part in phase 1, with status != 0 and no pairs; every
+ * rank reads the same status words, skips phase 2 and returns the same error.  Likewise a chunk whose merged total -- known on every rank
+ * from phase 1's offsets -- passes the smallest ceiling fails on every rank before phase 2.  In both cases the object is NOT poisoned and
+ * the next call may succeed.  An error inside a collective, or after phase 1 has committed the ranks to phase 2 (the staging buffers or
+ * the result cannot be allocated), poisons the object in a multi-process job as below.
+ * Exercised on hardware with ONE rank (both phases as real 1-rank ncclAllGather calls under VDB_CTX_FORCE_RCCL=1, the merge with S = 1);
+ * the merge with S > 1 is tested on one GPU through vdb_range_merge_device.  World > 1 over RCCL -- several local GPUs, several
+ * processes, the agreement of the ranks on a non-poisoning error -- is correct by construction, not by test. */
+int vdb_sharded_flat_range(vdb_sharded *sh, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit,
+                           vdb_range **out);
 /* Failed sharded calls.  vdb_sharded_set_rows[_replica] is all-or-nothing: when one GPU fails (out of memory, say) every
  * shard is rolled back to an empty index and the call may be repeated.  A SEARCH that fails on one rank of a multi-PROCESS
  * context (vdb_ctx_create_rank, world > 1) may leave the other ranks inside the all-gather; the object is then "poisoned"

@@ -32,6 +32,24 @@ inline void check(int status) {
     if (status != VDB_OK) throw Error(status, vdb_last_error());
 }
 
+// the pairs of a range result object, per query; releases the object
+inline std::vector<std::vector<CandidatePair>> take_range(vdb_range *r, uint64_t nq) {
+    std::vector<uint64_t> lims(nq + 1), idx;
+    std::vector<float> d;
+    int rc = vdb_range_lims(r, lims.data());
+    if (rc == VDB_OK) {
+        idx.resize(lims[nq]);
+        d.resize(lims[nq]);
+        rc = vdb_range_copy(r, idx.data(), d.data());
+    }
+    vdb_range_destroy(r);
+    check(rc);
+    std::vector<std::vector<CandidatePair>> out(nq);
+    for (uint64_t q = 0; q < nq; q++)
+        for (uint64_t j = lims[q]; j < lims[q + 1]; j++) out[q].push_back({idx[j], d[j]});
+    return out;
+}
+
 // DynamicIndex: starts as the Flat arm; build_hnsw() switches to the HNSW arm like
 // MetadataVecTable::build_hnsw_index (metadata_vec_table.rs:112-135), clear_hnsw() back (:137-152).
 // The PQ table hangs off the index handle (the reference passes &PQTable into knn_pq; here it is attached state).
@@ -105,20 +123,7 @@ public:
     std::vector<std::vector<CandidatePair>> range_search_batch(const float *queries, uint64_t nq, const float *radius, uint64_t limit = 0) const {
         vdb_range *r = nullptr;
         check(vdb_flat_range(h_, queries, nq, dim_, radius, limit, &r));
-        std::vector<uint64_t> lims(nq + 1), idx;
-        std::vector<float> d;
-        int rc = vdb_range_lims(r, lims.data());
-        if (rc == VDB_OK) {
-            idx.resize(lims[nq]);
-            d.resize(lims[nq]);
-            rc = vdb_range_copy(r, idx.data(), d.data());
-        }
-        vdb_range_destroy(r);
-        check(rc);
-        std::vector<std::vector<CandidatePair>> out(nq);
-        for (uint64_t q = 0; q < nq; q++)
-            for (uint64_t j = lims[q]; j < lims[q + 1]; j++) out[q].push_back({idx[j], d[j]});
-        return out;
+        return take_range(r, nq);
     }
     std::vector<CandidatePair> range_search(const std::vector<float> &query, float radius, uint64_t limit = 0) const {
         require_dim(query.size());
@@ -225,6 +230,12 @@ public:
     }
     std::vector<std::vector<CandidatePair>> knn_batch(const float *queries, uint64_t nq, uint64_t k) const {
         return run(nq, k, [&](uint64_t *i, float *d, uint64_t *c) { return vdb_sharded_flat_knn(h_, queries, nq, dim_, k, i, d, c); });
+    }
+    // every pair within radius[q] over the whole corpus (vdb_sharded_flat_range): DynamicIndex::range_search_batch's answer, global ids
+    std::vector<std::vector<CandidatePair>> range_search_batch(const float *queries, uint64_t nq, const float *radius, uint64_t limit = 0) const {
+        vdb_range *r = nullptr;
+        check(vdb_sharded_flat_range(h_, queries, nq, dim_, radius, limit, &r));
+        return take_range(r, nq);
     }
     void attach_pq(uint64_t n_bits, uint64_t m, const std::vector<float> &centroids) {
         check(vdb_sharded_pq_attach(h_, n_bits, m, centroids.data()));

@@ -89,6 +89,8 @@ SIGNATURES = {
     "vdb_hnsw_knn_pq": [vp, f32p, u64, u64, u64, u64, u64p, f32p, u64p],
     "vdb_hnsw_last_stats": [vp, u64p, u64p],
     "vdb_merge_topk": [f32p, u64p, u64p, u64, u64, u64, u64p, f32p, u64p],
+    "vdb_range_merge": [u64p, u64p, f32p, u64, u64, u64, u64, u64p, u64p, f32p],
+    "vdb_range_merge_device": [vp, vp, vp, vp, u64, u64, u64, u64, vp, C.POINTER(vp)],
     "vdb_merge_topk_device": [vp, vp, vp, vp, u64, u64, u64, vp, vp, vp, vp],
     "vdb_merge_topk_gathered": [vp, vp, u64, u64, u64, u64, u64, u64, u64, vp, vp, vp, vp],
     "vdb_merge_topk_gathered_async": [vp, vp, u64, u64, u64, u64, u64, u64, u64, vp, vp, vp, vp],
@@ -103,6 +105,7 @@ SIGNATURES = {
     "vdb_sharded_len": [vp, u64p],
     "vdb_sharded_local": [vp, C.c_int, C.POINTER(vp)],
     "vdb_sharded_flat_knn": [vp, f32p, u64, u64, u64, u64p, f32p, u64p],
+    "vdb_sharded_flat_range": [vp, f32p, u64, u64, f32p, u64, C.POINTER(vp)],
     "vdb_sharded_pq_attach": [vp, u64, u64, f32p],
     "vdb_sharded_knn_pq": [vp, f32p, u64, u64, u64, u64, u64p, f32p, u64p],
     "vdb_sharded_set_rows_replica": [vp, f32p, u64],

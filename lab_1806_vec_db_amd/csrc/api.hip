@@ -449,10 +449,6 @@ int vdb_flat_knn_device_end(vdb_pending *pending) {
 }
 
 // ---- exact Flat range search -------------------------------------------------------------------------------------------------------
-struct vdb_range {
-    RangeResult r;
-};
-
 static void range_check(const Index &ix, const void *queries, uint64_t nq, uint64_t dim, const void *radius, vdb_range **out) {
     VDB_REQUIRE(out, "null out");
     *out = nullptr;
@@ -1176,6 +1172,51 @@ int vdb_merge_topk(const float *dists, const uint64_t *ids, const uint64_t *coun
         }
         if (out_count) out_count[q] = c;
     }
+    VDB_API_END
+}
+
+// ---- merge of S range results (k_range_merge.hip) -----------------------------------------------------
+int vdb_range_merge(const uint64_t *lims, const uint64_t *ids, const float *dists, uint64_t n_shards, uint64_t nq, uint64_t pair_stride,
+                    uint64_t limit, uint64_t *out_lims, uint64_t *out_idx, float *out_dist) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(lims && out_lims && n_shards >= 1, "null argument");
+    VDB_REQUIRE(nq < (1ull << 32), "too many queries for one call");
+    VDB_REQUIRE((out_idx == nullptr) == (out_dist == nullptr), "out_idx and out_dist go together (both NULL: offsets only)");
+    range_merge_validate(lims, nq + 1, n_shards, nq, pair_stride);
+    range_merge_lims(lims, nq + 1, n_shards, nq, limit, out_lims);
+    if (out_idx && out_lims[nq]) {
+        VDB_REQUIRE(ids && dists, "null argument");
+        range_merge_host(lims, ids, dists, n_shards, nq, pair_stride, out_lims, out_idx, out_dist);
+    }
+    VDB_API_END
+}
+
+int vdb_range_merge_device(vdb_index *idx, const void *d_lims, const void *d_ids, const void *d_dists, uint64_t n_shards, uint64_t nq,
+                           uint64_t pair_stride, uint64_t limit, void *stream, vdb_range **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(out, "null out");
+    *out = nullptr;
+    VDB_REQUIRE(idx && n_shards >= 1, "null argument");
+    VDB_REQUIRE(nq == 0 || d_lims, "null argument");
+    VDB_REQUIRE(nq < (1ull << 32) && n_shards < (1ull << 16), "too many queries or shards for one call");
+    Index &ix = idx->ix;
+    ix.use_device();
+    std::unique_ptr<vdb_range> res(new vdb_range);
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the inputs on the caller's stream (the all-gather)
+    std::vector<uint64_t> h_lims(n_shards * (nq + 1), 0);
+    if (nq) VDB_HIP(hipMemcpy(h_lims.data(), d_lims, h_lims.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    range_merge_validate(h_lims.data(), nq + 1, n_shards, nq, pair_stride);
+    try {
+        range_merge_dev(ix, *ws, h_lims.data(), nq + 1, d_lims, d_ids, pair_stride * sizeof(uint64_t), d_dists, pair_stride * sizeof(float), n_shards,
+                        nq, limit, res->r);
+    } catch (...) {
+        (void)hipStreamSynchronize(ws->stream);
+        ix.prof_collect(*ws);
+        throw;
+    }
+    ix.prof_collect(*ws);
+    *out = res.release();
     VDB_API_END
 }
 

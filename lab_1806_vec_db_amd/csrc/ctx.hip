@@ -96,6 +96,7 @@ struct Shard {
     std::unique_ptr<vdb_index> handle;
     hipStream_t stream = nullptr;  // collectives + merge of this GPU
     DevBuf q, send, recv, adc, exact, g_adc, g_exact, o_idx, o_dist, o_cnt;
+    DevBuf r_send, r_recv;         // phase 2 of the range exchange (sized by the results: released when the call returns)
     uint64_t r0 = 0, r1 = 0;       // global row range
 };
 
@@ -155,6 +156,8 @@ struct vdb_sharded {
             shards[i]->o_idx.release();
             shards[i]->o_dist.release();
             shards[i]->o_cnt.release();
+            shards[i]->r_send.release();
+            shards[i]->r_recv.release();
             if (shards[i]->stream) (void)hipStreamDestroy(shards[i]->stream);
         }
     }
@@ -732,6 +735,256 @@ int vdb_sharded_ivf_knn(vdb_sharded *sh, const float *queries, uint64_t nq, uint
     VDB_SHARDED_SEARCH_END(sh)
     VDB_API_END
 }
+// ---- exact range search over the shards / replicas ------------------------------------------------------------------------------
+// FlatIndex rows within a radius over the whole corpus = the union of the shards' answers (a `limit` keeps the first `limit` of the union,
+// which are among the first `limit` of every shard), so every shard runs Index::flat_range_device with the same radii and limit and the
+// lists are merged by (distance, id) -- ids of different shards are disjoint, the order is total, the answer is the unsharded one pair for
+// pair.  The lists are variable-length, so the exchange has two phases per chunk of RANGE_CHUNK queries:
+//   phase 1, fixed size:  [per + 1 CSR offsets of the rank's result | status | ceiling]  (per = queries the rank answered: all of the
+//            chunk's in the ROWS layout, ceil(chunk / S) in the REPLICA layout, short blocks padded with their total; ceiling = the
+//            rank's flat_range_max_results, 0 = none);
+//   phase 2: [mx ids u64 | mx distances f32 | pad to 8], mx = the largest rank total phase 1 reported (ncclAllGather needs equal sizes);
+//            skipped when mx == 0.  Receive buffer: S * mx * 12 B on every local GPU.
+// then k_range_merge on the first local GPU (ROWS) or the concatenation of the blocks in query order (REPLICA).
+// The status word turns a local failure (the flat_range_max_results ceiling, device memory) into an ordinary error: the rank still takes
+// part in phase 1, with status 1 and no pairs; EVERY rank reads the same status words, skips phase 2 and fails the call -- nobody is left
+// inside a collective, so the object is NOT poisoned (AgreedError).  The same holds for the chunk's merged (ROWS) / concatenated (REPLICA)
+// total: every rank derives it from the same offsets and compares it with the SMALLEST ceiling any rank sent -- per-rank settings may
+// differ, the decision may not -- before phase 2.  Any other error -- inside a collective, or once phase 1 has committed
+// the ranks to phase 2 -- poisons it in a multi-process job like the k-NN calls' errors do.
+namespace {
+
+struct AgreedError : Error {  // a failure every rank of the job reaches at the same point of the call
+    using Error::Error;
+};
+constexpr uint64_t RANGE_CHUNK = 2048;  // queries per exchange
+
+struct RangeStagingGuard {  // phase 2's buffers do not outlive the call
+    vdb_sharded &sh;
+    ~RangeStagingGuard() {
+        for (size_t i = 0; i < sh.shards.size(); i++) {
+            if (!sh.shards[i]->r_send.base && !sh.shards[i]->r_recv.base) continue;
+            (void)hipSetDevice(sh.ctx->devices[i]);
+            sh.shards[i]->r_send.release();
+            sh.shards[i]->r_recv.release();
+        }
+    }
+};
+
+void sync_shards(vdb_sharded &sh) {
+    for (size_t i = 0; i < sh.shards.size(); i++) {
+        VDB_HIP(hipSetDevice(sh.ctx->devices[i]));
+        VDB_SYNC(sh.shards[i]->stream);
+    }
+}
+
+void sharded_range(vdb_sharded &sh, const float *queries, uint64_t nq, const float *radius, uint64_t limit, RangeResult &out) {
+    const bool replica = sh.layout == LAYOUT_REPLICA, comm = !sh.ctx->comms.empty();
+    const uint64_t S = (uint64_t)sh.ctx->world, ns = comm ? S : 1, dim = sh.dim;
+    const size_t nl = sh.shards.size();
+    RangeStagingGuard guard{sh};
+    Shard &s0 = *sh.shards[0];
+    Index &ix0 = s0.handle->ix;
+    std::vector<std::unique_ptr<RangeResult>> local(nl);
+    std::vector<std::vector<uint64_t>> blk(nl);
+    std::vector<std::string> lerr(nl);
+    std::vector<uint64_t> h1;
+    uint64_t used = 0;  // pairs in `out`
+    for (uint64_t c0 = 0; c0 < nq; c0 += RANGE_CHUNK) {
+        const uint64_t nb = std::min(RANGE_CHUNK, nq - c0), per = replica ? (nb + S - 1) / S : nb, ld1 = per + 3, p1 = ld1 * sizeof(uint64_t);
+        for_each_shard(nl, [&](size_t i) {
+            Shard &s = *sh.shards[i];
+            Index &ix = s.handle->ix;
+            ix.use_device();
+            uint64_t q0 = 0, q1 = nb;
+            if (replica) replica_block(nb, S, (uint64_t)sh.ctx->ranks[i], q0, q1);
+            const uint64_t nmine = q1 - q0;
+            std::vector<uint64_t> &b = blk[i];
+            local[i].reset(new RangeResult);
+            lerr[i].clear();
+            try {
+                if (nmine) {
+                    const size_t qb = nmine * dim * sizeof(float), qb_pad = (qb + 255) & ~size_t(255);
+                    s.q.reserve(qb_pad + nmine * sizeof(float));  // [queries | radii]
+                    VDB_HIP(hipMemcpyAsync(s.q.p, queries + (c0 + q0) * dim, qb, hipMemcpyHostToDevice, s.stream));
+                    VDB_HIP(hipMemcpyAsync(s.q.as<char>() + qb_pad, radius + c0 + q0, nmine * sizeof(float), hipMemcpyHostToDevice, s.stream));
+                    VDB_SYNC(s.stream);
+                    WsLease ws(ix);
+                    try {
+                        ix.flat_range_device(*ws, s.q.as<float>(), nmine, reinterpret_cast<const float *>(s.q.as<char>() + qb_pad), limit, *local[i]);
+                    } catch (...) {
+                        (void)hipStreamSynchronize(ws->stream);  // nothing of a failed call is still running when its buffers go
+                        ix.prof_collect(*ws);
+                        throw;
+                    }
+                    ix.prof_collect(*ws);
+                } else {
+                    local[i]->lims.assign(1, 0);
+                }
+                b.assign(ld1, 0);
+                for (uint64_t j = 0; j <= per; j++) b[j] = local[i]->lims[std::min(j, nmine)];
+            } catch (const Error &e) {  // this rank has no answer: it says so in phase 1
+                lerr[i] = e.what();
+                local[i].reset(new RangeResult);
+                b.assign(ld1, 0);
+                b[per + 1] = 1;
+            }
+            b[per + 2] = ix.range_max_results;
+            if (comm) {
+                s.send.reserve(p1);
+                s.recv.reserve(S * p1);
+                VDB_HIP(hipMemcpyAsync(s.send.p, b.data(), p1, hipMemcpyHostToDevice, s.stream));
+            }
+        });
+        if (comm) {  // phase 1
+            std::vector<std::pair<const void *, void *>> bufs;
+            for (auto &s : sh.shards) bufs.push_back({s->send.p, s->recv.p});
+            all_gather(sh, bufs, 1, p1);
+            h1.resize(S * ld1);
+            ix0.use_device();
+            VDB_HIP(hipMemcpyAsync(h1.data(), s0.recv.p, S * p1, hipMemcpyDeviceToHost, s0.stream));
+            sync_shards(sh);
+        } else {
+            h1 = blk[0];
+        }
+        std::string failed;
+        for (uint64_t r = 0; r < ns; r++)
+            if (h1[r * ld1 + per + 1] != 0) failed += (failed.empty() ? "" : ", ") + std::to_string(comm ? r : (uint64_t)sh.ctx->ranks[0]);
+        if (!failed.empty()) {
+            std::string msg = "sharded range search: the local range search failed on rank " + failed;
+            for (size_t i = 0; i < nl; i++)
+                if (!lerr[i].empty()) msg += "; rank " + std::to_string(sh.ctx->ranks[i]) + ": " + lerr[i];
+            throw AgreedError(1, msg);
+        }
+        range_merge_validate(h1.data(), ld1, ns, per, ~0ull);
+        uint64_t mx = 0, ceiling = ~0ull, merged = 0;
+        for (uint64_t r = 0; r < ns; r++) {
+            mx = std::max(mx, h1[r * ld1 + per]);
+            if (h1[r * ld1 + per + 2]) ceiling = std::min(ceiling, h1[r * ld1 + per + 2]);
+            merged += h1[r * ld1 + per];  // REPLICA: the blocks are concatenated
+        }
+        if (!replica) {  // ROWS: per query min(limit, sum over the shards)
+            std::vector<uint64_t> ml(per + 1);
+            range_merge_lims(h1.data(), ld1, ns, per, limit, ml.data());
+            merged = ml[per];
+        }
+        if (merged > ceiling)  // (the same offsets and the same ceiling on every rank: nobody goes on to phase 2)
+            throw AgreedError(1, "sharded range search: " + std::to_string(merged) + " results for a chunk of " + std::to_string(nb) +
+                                     " queries, more than " + std::to_string(ceiling) +
+                                     " (the smallest flat_range_max_results of the ranks); use a limit, smaller radii or fewer queries per call");
+        RangeResult chunk;
+        chunk.device = ix0.device;
+        chunk.nq = nb;
+        chunk.lims.assign(nb + 1, 0);
+        if (mx > 0 && !comm) {  // one rank, no communicator: the local result is the answer
+            chunk.lims = local[0]->lims;
+            chunk.idx.take(local[0]->idx);
+            chunk.dist.take(local[0]->dist);
+        } else if (mx > 0) {  // phase 2
+            const uint64_t off_d = mx * sizeof(uint64_t), block = (mx * 12 + 7) / 8 * 8;
+            for_each_shard(nl, [&](size_t i) {
+                Shard &s = *sh.shards[i];
+                s.handle->ix.use_device();
+                s.r_send.reserve(block);
+                s.r_recv.reserve(S * block);
+                const uint64_t t = local[i]->lims.back();
+                if (t) {
+                    VDB_HIP(hipMemcpyAsync(s.r_send.p, local[i]->idx.p, t * sizeof(uint64_t), hipMemcpyDeviceToDevice, s.stream));
+                    VDB_HIP(hipMemcpyAsync(s.r_send.as<char>() + off_d, local[i]->dist.p, t * sizeof(float), hipMemcpyDeviceToDevice, s.stream));
+                }
+            });
+            std::vector<std::pair<const void *, void *>> bufs;
+            for (auto &s : sh.shards) bufs.push_back({s->r_send.p, s->r_recv.p});
+            all_gather(sh, bufs, 1, block);
+            sync_shards(sh);
+            ix0.use_device();
+            const char *g = s0.r_recv.as<char>();
+            if (!replica) {
+                WsLease ws(ix0);
+                try {
+                    range_merge_dev(ix0, *ws, h1.data(), ld1, s0.recv.p, g, block, g + off_d, block, S, nb, limit, chunk);
+                } catch (...) {
+                    (void)hipStreamSynchronize(ws->stream);
+                    ix0.prof_collect(*ws);
+                    throw;
+                }
+                ix0.prof_collect(*ws);
+            } else {  // the blocks are disjoint query ranges of the answer: concatenate them in query order
+                uint64_t run = 0;
+                for (uint64_t r = 0; r < S; r++) {
+                    uint64_t q0, q1;
+                    replica_block(nb, S, r, q0, q1);
+                    for (uint64_t j = 0; j < q1 - q0; j++) chunk.lims[q0 + j + 1] = run + h1[r * ld1 + j + 1];
+                    run += h1[r * ld1 + (q1 - q0)];
+                }
+                chunk.idx.reserve(run * sizeof(uint64_t));
+                chunk.dist.reserve(run * sizeof(float));
+                for (uint64_t r = 0; r < S; r++) {
+                    uint64_t q0, q1;
+                    replica_block(nb, S, r, q0, q1);
+                    const uint64_t t = h1[r * ld1 + (q1 - q0)], o = chunk.lims[q0];
+                    if (t == 0) continue;
+                    VDB_HIP(hipMemcpyAsync(chunk.idx.as<uint64_t>() + o, g + r * block, t * sizeof(uint64_t), hipMemcpyDeviceToDevice, s0.stream));
+                    VDB_HIP(hipMemcpyAsync(chunk.dist.as<float>() + o, g + r * block + off_d, t * sizeof(float), hipMemcpyDeviceToDevice, s0.stream));
+                }
+                VDB_SYNC(s0.stream);
+            }
+        }
+        for (size_t i = 0; i < nl; i++) {  // (on their own devices)
+            (void)hipSetDevice(sh.ctx->devices[i]);
+            local[i].reset();
+        }
+        // the chunk joins the answer
+        ix0.use_device();
+        const uint64_t add = chunk.lims[nb];
+        for (uint64_t j = 1; j <= nb; j++) out.lims[c0 + j] = used + chunk.lims[j];
+        if (add && c0 == 0 && nb == nq) {
+            out.idx.take(chunk.idx);
+            out.dist.take(chunk.dist);
+        } else if (add) {
+            out.idx.grow((used + add) * sizeof(uint64_t), used * sizeof(uint64_t), s0.stream);
+            out.dist.grow((used + add) * sizeof(float), used * sizeof(float), s0.stream);
+            VDB_HIP(hipMemcpyAsync(out.idx.as<uint64_t>() + used, chunk.idx.p, add * sizeof(uint64_t), hipMemcpyDeviceToDevice, s0.stream));
+            VDB_HIP(hipMemcpyAsync(out.dist.as<float>() + used, chunk.dist.p, add * sizeof(float), hipMemcpyDeviceToDevice, s0.stream));
+            VDB_SYNC(s0.stream);  // (`chunk` goes out of scope)
+        }
+        used += add;
+    }
+}
+
+}  // namespace
+
+int vdb_sharded_flat_range(vdb_sharded *sh, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit,
+                           vdb_range **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(out, "null out");
+    *out = nullptr;
+    VDB_REQUIRE(sh, "null index");
+    VDB_REQUIRE(dim == sh->dim, "query dimension mismatch: index dim " + std::to_string(sh->dim) + ", got " + std::to_string(dim));
+    VDB_REQUIRE(nq == 0 || (queries && radius), "null argument");
+    VDB_REQUIRE(nq < (1ull << 32), "too many queries for one call");
+    VDB_REQUIRE(!sh->poisoned, "this sharded index is poisoned: an earlier collective call failed on this rank while other "
+                               "processes were inside the exchange; destroy it on every rank and build a new one");
+    std::unique_ptr<vdb_range> res(new vdb_range);
+    res->r.device = sh->ctx->devices[0];
+    res->r.nq = nq;
+    res->r.lims.assign(nq + 1, 0);
+    if (nq && sh->n_total) {  // (no rows, on every rank alike: empty results)
+        try {
+            sharded_range(*sh, queries, nq, radius, limit, res->r);
+        } catch (const AgreedError &) {
+            (void)hipSetDevice(res->r.device);  // (what earlier chunks left in the result is freed there)
+            throw;
+        } catch (...) {
+            if (multi_process(*sh)) sh->poisoned = true;
+            (void)hipSetDevice(res->r.device);
+            throw;
+        }
+    }
+    *out = res.release();
+    VDB_API_END
+}
+
 // partition arithmetic of the REPLICA layout, exported for the host's tests: the query block of `rank` among `world`
 int vdb_replica_query_block(uint64_t nq, uint64_t world, uint64_t rank, uint64_t *q0, uint64_t *q1) {
     VDB_API_BEGIN

@@ -91,6 +91,15 @@ struct DevBuf {
         p = np;
         cap = want;
     }
+    // takes over src's allocation (what this buffer held is released; src is left empty)
+    void take(DevBuf &src) {
+        release();
+        p = src.p;
+        cap = src.cap;
+        base = src.base;
+        src.p = src.base = nullptr;
+        src.cap = 0;
+    }
     template <class T>
     T *as() const { return reinterpret_cast<T *>(p); }
 };

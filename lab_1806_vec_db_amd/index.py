@@ -34,6 +34,20 @@ def _ptr(a, t):
     return a.ctypes.data_as(t) if a is not None else None
 
 
+def read_range(lib, h, nq: int):
+    """(lims, idx, dist) of a vdb_range result object on the host; releases the object"""
+    try:
+        lims = np.zeros(nq + 1, dtype=np.uint64)
+        L.check(lib.vdb_range_lims(h, _ptr(lims, L.u64p)))
+        total = int(lims[nq])
+        idx = np.zeros(total, dtype=np.uint64)
+        dist = np.zeros(total, dtype=np.float32)
+        L.check(lib.vdb_range_copy(h, _ptr(idx, L.u64p), _ptr(dist, L.f32p)))
+        return lims, idx, dist
+    finally:
+        lib.vdb_range_destroy(h)
+
+
 def calc_dist(a, b, dist="cosine", device: int = 0) -> float:
     """calc_dist (pyo3/mod.rs:43-48), evaluated on the GPU in reference order."""
     kind = parse_dist(dist)
@@ -185,16 +199,7 @@ class GpuIndex:
         return self._search(self._lib.vdb_flat_knn, queries, k)
 
     def _range_out(self, h, nq: int):
-        try:
-            lims = np.zeros(nq + 1, dtype=np.uint64)
-            L.check(self._lib.vdb_range_lims(h, _ptr(lims, L.u64p)))
-            total = int(lims[nq])
-            idx = np.zeros(total, dtype=np.uint64)
-            dist = np.zeros(total, dtype=np.float32)
-            L.check(self._lib.vdb_range_copy(h, _ptr(idx, L.u64p), _ptr(dist, L.f32p)))
-            return lims, idx, dist
-        finally:
-            self._lib.vdb_range_destroy(h)
+        return read_range(self._lib, h, nq)
 
     def range_search(self, queries, radius, limit: int | None = None):
         """Exact Flat range search (vdb_flat_range): for every query ALL rows with distance <= its radius -- the distance
@@ -263,6 +268,18 @@ class GpuIndex:
                           out_idx: int, out_dist: int, out_cnt: int, stream: int = 0):
         L.check(self._lib.vdb_merge_topk_device(self._h, L.vp(d_dists), L.vp(d_ids), L.vp(d_counts), n_shards, nq, k,
                                                 L.vp(out_idx), L.vp(out_dist), L.vp(out_cnt), L.vp(stream)))
+
+    def range_merge_device(self, d_lims: int, d_ids: int, d_dists: int, n_shards: int, nq: int, pair_stride: int,
+                           limit: int | None = None, stream: int = 0):
+        """Merge of S range results on this index's GPU (vdb_range_merge_device): device pointers to lims [S][nq + 1] (u64), ids
+        (u64) and distances (f32) with shard s's pairs at element s * pair_stride -- the all-gathered tensors.  Returns the merged
+        (lims, idx, dist) on the host like range_search; synchronises `stream` first."""
+        if limit is not None and int(limit) <= 0:
+            raise ValueError("limit must be positive (None: no limit)")
+        h = L.vp()
+        L.check(self._lib.vdb_range_merge_device(self._h, L.vp(d_lims), L.vp(d_ids), L.vp(d_dists), int(n_shards), int(nq),
+                                                 int(pair_stride), int(limit or 0), L.vp(stream), C.byref(h)))
+        return self._range_out(h, int(nq))
 
     # -- row-sharded knn_pq (SURVEY 8e): local ADC shortlist as pair-key rows, merged after the all-gather ------
     def knn_pq_shard(self, queries, k: int, ef: int):
@@ -545,6 +562,39 @@ def merge_topk(dists: np.ndarray, ids: np.ndarray, counts: np.ndarray, k: int):
     L.check(L.load().vdb_merge_topk(_ptr(d, L.f32p), _ptr(i, L.u64p), _ptr(c, L.u64p), S, nq, k, _ptr(oi, L.u64p),
                                     _ptr(od, L.f32p), _ptr(oc, L.u64p)))
     return oi, od, oc
+
+
+def range_merge(lims, ids, dists, limit: int | None = None):
+    """Merge per-shard range results (vdb_range_merge, host utility): `lims` [S][nq + 1] CSR offsets of every shard (each row from
+    0), `ids` / `dists` either [S][stride] arrays (shard s's pairs at the front of row s) or sequences of S arrays of lims[s][nq]
+    pairs.  Returns (lims, idx, dist) like GpuIndex.range_search: per query the union ascending by (distance, id), the first
+    `limit` of it when given."""
+    if limit is not None and int(limit) <= 0:
+        raise ValueError("limit must be positive (None: no limit)")
+    lm = np.ascontiguousarray(lims, dtype=np.uint64)
+    if lm.ndim != 2 or lm.shape[1] < 1:
+        raise ValueError("lims must be [S][nq + 1]")
+    S, nq = lm.shape[0], lm.shape[1] - 1
+    if isinstance(ids, np.ndarray) and ids.ndim == 2:
+        i = np.ascontiguousarray(ids, dtype=np.uint64)
+        d = _f32(dists)
+    else:
+        stride = max([len(x) for x in ids] + [1])
+        i = np.zeros((S, stride), dtype=np.uint64)
+        d = np.zeros((S, stride), dtype=np.float32)
+        for s in range(S):
+            i[s, :len(ids[s])] = ids[s]
+            d[s, :len(dists[s])] = dists[s]
+    if i.shape != d.shape or i.shape[0] != S:
+        raise ValueError("ids and dists must hold one row of pairs per shard")
+    lib = L.load()
+    ol = np.zeros(nq + 1, dtype=np.uint64)
+    L.check(lib.vdb_range_merge(_ptr(lm, L.u64p), None, None, S, nq, i.shape[1], int(limit or 0), _ptr(ol, L.u64p), None, None))
+    oi = np.zeros(int(ol[nq]), dtype=np.uint64)
+    od = np.zeros(int(ol[nq]), dtype=np.float32)
+    L.check(lib.vdb_range_merge(_ptr(lm, L.u64p), _ptr(i, L.u64p), _ptr(d, L.f32p), S, nq, i.shape[1], int(limit or 0), _ptr(ol, L.u64p),
+                                _ptr(oi, L.u64p), _ptr(od, L.f32p)))
+    return ol, oi, od
 
 
 def pq_merge_resort(adc_keys: np.ndarray, exact_keys: np.ndarray, k: int):

@@ -7,6 +7,12 @@ Every rank computes its local top-k for all queries; ONE all-gather of a single 
 CandidatePair order (distance, index) -- top-k under a total order is decomposable, so the result equals
 the unsharded one exactly.  One process per GPU; `torch.distributed` backend "nccl" is RCCL on ROCm,
 "gloo" is used for the CPU rehearsal in tests/.
+
+Range search (GpuIndex.range_search on every shard) has variable-length results, so its exchange takes TWO collectives
+(allgather_merge_range): the nq + 1 CSR offsets of every rank, then the pairs, every rank's block padded to the largest rank
+total the first one reported; the S sorted lists of a query are then merged by (distance, id) -- the union of the shards'
+answers IS the unsharded answer, and with a `limit` its first `limit` pairs are among the first `limit` of every shard.
+Replicas split the queries instead and concatenate (allgather_concat_range), no merge.
 """
 from __future__ import annotations
 
@@ -94,6 +100,94 @@ def allgather_merge_pq(adc_keys, exact_keys, k: int, group=None, gpu_index=None)
 
     oi, od, oc = pq_merge_resort(g_adc.numpy().view(np.uint64), g_ex.numpy().view(np.uint64), k)
     return (torch.from_numpy(oi.astype(np.int64)), torch.from_numpy(od), torch.from_numpy(oc.astype(np.int64)))
+
+
+def _gather_range(lims, idx, dist, group, world):
+    """the two collectives of a range exchange: (g_lims [world][len(lims)] i64, g_idx [world][mx] i64, g_dist [world][mx] f32, mx);
+    mx = the largest rank total (0: nothing was exchanged in phase 2, g_idx / g_dist are None)"""
+    import torch
+    import torch.distributed as dist_
+
+    lims = lims.contiguous()
+    g_lims = torch.empty((world, lims.numel()), dtype=lims.dtype, device=lims.device)
+    dist_.all_gather_into_tensor(g_lims.view(-1), lims, group=group)
+    mx = int(g_lims[:, -1].max().item())
+    if mx == 0:
+        return g_lims, None, None, 0
+    total = int(lims[-1].item())
+    block = (mx * 12 + 7) // 8 * 8  # [mx ids | mx distances | pad]: ONE buffer per rank
+    mine = torch.zeros(block, dtype=torch.uint8, device=idx.device)
+    mine[:total * 8] = idx.contiguous().view(torch.uint8).reshape(-1)[:total * 8]
+    mine[mx * 8:mx * 8 + total * 4] = dist.contiguous().view(torch.uint8).reshape(-1)[:total * 4]
+    gathered = torch.empty((world, block), dtype=torch.uint8, device=mine.device)
+    dist_.all_gather_into_tensor(gathered.view(-1), mine, group=group)
+    g_idx = gathered[:, :mx * 8].contiguous().view(idx.dtype).view(world, mx)
+    g_dist = gathered[:, mx * 8:mx * 12].contiguous().view(dist.dtype).view(world, mx)
+    return g_lims, g_idx, g_dist, mx
+
+
+def allgather_merge_range(lims, idx, dist, limit=None, group=None, gpu_index=None):
+    """Row-sharded range search: this rank's CSR result -- lims [nq + 1] int64, idx [lims[nq]] int64 with GLOBAL ids, dist
+    [lims[nq]] float32, per query ascending by (distance, id) (GpuIndex.range_search with set_id_offset) -- in, the merged result
+    of all ranks out, the same on every rank: (lims [nq + 1] int64 on the CPU, idx, dist on the inputs' device).  `limit`: the
+    first `limit` pairs of every query (the ranks may have searched with the same limit).
+    All three inputs live on the collective's device (CUDA for the nccl backend, `lims` included).
+    On CUDA tensors the merge runs on the GPU (vdb_range_merge_device, needs `gpu_index`; the merged arrays pass through the host,
+    where the result object is read); on CPU tensors (gloo rehearsal) it uses the host utility.  World 1 returns its input.
+    The CUDA branch needs a world of at least 2 over RCCL and has not run on hardware (the test boxes have one GPU): the device
+    merge it calls is tested on its own from tensors packed the same way, the exchange in front of it over gloo."""
+    import torch
+    import torch.distributed as dist_
+
+    if limit is not None and int(limit) <= 0:
+        raise ValueError("limit must be positive (None: no limit)")
+    world = dist_.get_world_size(group) if dist_.is_initialized() else 1
+    if world == 1:
+        return lims, idx, dist
+    nq = lims.numel() - 1
+    g_lims, g_idx, g_dist, mx = _gather_range(lims, idx, dist, group, world)
+    if mx == 0:
+        return torch.zeros(nq + 1, dtype=torch.int64), idx[:0], dist[:0]
+    if idx.is_cuda:
+        if gpu_index is None:
+            raise ValueError("allgather_merge_range on CUDA tensors needs the rank's GpuIndex")
+        torch.cuda.current_stream().synchronize()
+        ol, oi, od = gpu_index.range_merge_device(g_lims.data_ptr(), g_idx.data_ptr(), g_dist.data_ptr(), world, nq, mx, limit)
+    else:
+        from .index import range_merge
+
+        ol, oi, od = range_merge(g_lims.numpy().view(np.uint64), g_idx.numpy().view(np.uint64), g_dist.numpy(), limit)
+    return (torch.from_numpy(ol.astype(np.int64)), torch.from_numpy(oi.view(np.int64)).to(idx.device), torch.from_numpy(od).to(idx.device))
+
+
+def allgather_concat_range(lims, idx, dist, nq: int, group=None):
+    """Replica mode: rank r answered the queries replica_query_slice(nq, world, r) (lims has that many + 1 entries); every rank
+    receives the CSR result of all nq queries, the blocks concatenated in query order.  The same two collectives, no merge."""
+    import torch
+    import torch.distributed as dist_
+
+    world = dist_.get_world_size(group) if dist_.is_initialized() else 1
+    if world == 1:
+        return lims, idx, dist
+    per = -(-nq // world)
+    padded = torch.empty(per + 1, dtype=lims.dtype, device=lims.device)
+    padded[:lims.numel()] = lims
+    padded[lims.numel():] = lims[-1]  # (short and empty blocks repeat their total)
+    g_lims, g_idx, g_dist, mx = _gather_range(padded, idx, dist, group, world)
+    g_lims = g_lims.cpu()
+    out_lims = torch.zeros(nq + 1, dtype=torch.int64)
+    parts_i, parts_d, run = [], [], 0
+    for r in range(world):
+        q0, q1 = replica_query_slice(nq, world, r)
+        t = int(g_lims[r, q1 - q0])
+        out_lims[q0 + 1:q1 + 1] = g_lims[r, 1:q1 - q0 + 1] + run
+        if t:
+            parts_i.append(g_idx[r, :t])
+            parts_d.append(g_dist[r, :t])
+        run += t
+    if not parts_i:
+        return out_lims, idx[:0], dist[:0]
+    return out_lims, torch.cat(parts_i), torch.cat(parts_d)
 
 
 def replica_query_slice(nq: int, world: int, rank: int) -> tuple[int, int]:

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .index import _f32, _ptr, parse_dist
+from .index import _f32, _ptr, parse_dist, read_range
 
 
 class ShardedIndex:
@@ -119,6 +119,20 @@ class ShardedIndex:
 
     def flat_knn(self, queries, k: int):
         return self._search(self._lib.vdb_sharded_flat_knn, queries, k)
+
+    def range_search(self, queries, radius, limit: int | None = None):
+        """Exact range search over the whole corpus (vdb_sharded_flat_range): GpuIndex.range_search's answer on the unsharded rows,
+        global ids, on every rank -- (lims, idx, dist), query q owns [lims[q], lims[q + 1]).  `radius`: one value, or one per query.
+        A local failure (the shard's "flat_range_max_results" ceiling, device memory) is a VdbError that does not poison the object."""
+        q = _f32(queries)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        nq, dim = q.shape
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (nq,)))
+        if limit is not None and int(limit) <= 0:
+            raise ValueError("limit must be positive (None: no limit)")
+        h = L.vp()
+        L.check(self._lib.vdb_sharded_flat_range(self._h, _ptr(q, L.f32p), nq, dim, _ptr(r, L.f32p), int(limit or 0), C.byref(h)))
+        return read_range(self._lib, h, nq)
 
     def pq_attach(self, n_bits: int, m: int, centroids):
         c = _f32(centroids).ravel()
