@@ -169,6 +169,8 @@ int vdb_flat_set_mode(vdb_index *idx, int mode);
  *                      a row comes from HBM once per set and from the XCD's L2 for the other members; 0 auto = on, 1 off
  *   "flat_gemm8_res"   its kernel keeps the query group's whole 1-B/element image in LDS (dimensions up to 960: no workgroup barrier per chunk;
  *                      0 auto = on when the image fits, 1 off = chunked staging through two buffers)
+ *   "flat_gemm8_epi"   unit epilogue of its kernel: 0 (default) keys from scalar f32 multiply / fma and the wave's stage of passed lanes carried
+ *                      over units; 1 the earlier form (packed f32 arithmetic, one drain per unit).  Same key bits, same hit lists
  *   "flat_gemm8_kc", "flat_gemm8_burst", "flat_gemm8_nt"   variants of its kernel: k-blocks per Q chunk (0 auto, 5 / 3 / 2), staging of
  *                      the next chunk (0 auto, 1 per k-block, 2 one burst per chunk), cache policy of the row stream (as "flat_gemm_nt")
  *   "flat_gemm"        128-queries-per-pass kernel: 0 auto, 1 off (small-batch kernel), 2 forced

@@ -74,7 +74,13 @@ enum { G8_FILTER = 0, G8_SAMPLE = 1 };
 // flight; the chunked kernel got 5.3 - 5.7; the ablation build -DG8_ABLATE=4, no staging and no chunk barrier: -11 % kernel time).
 // Each wave now runs on its own counted waits, the ring is KC k-blocks deep without the staging registers, and a barrier is
 // left per group (Q image load, hit hand-over).  The hit buffer shrinks to G8_WGBUF_RES entries to make room.
-template <int KC, int MODE, bool XNT, bool BURST, bool RES>
+// EPI: the unit epilogue.  A wave's epilogue runs on a SIMD whose other wave is issuing MFMAs, so what it issues is paid in matrix
+// time.  0: the keys come from scalar v_mul_f32 / v_fma_f32 (packed f32 VALU beside MFMAs holds the pipe up far longer than its issue
+// slot; one rounded multiply and one fused fma per key either way, the bits are the same), and the wave's stage of passed lanes lives
+// ACROSS units: it is drained when the next pair would not fit and before a hand-over, not once per unit (~7 lanes per unit at 1M rows
+// into 64 slots: one LDS atomic with return and its wait per 8 - 9 units).  1: packed arithmetic and one drain per unit (the earlier
+// form, kept for the A/B in one binary and for the tests that hold the two to each other).
+template <int KC, int MODE, bool XNT, bool BURST, bool RES, int EPI>
 __global__ __launch_bounds__(512, 1) void k_flat_gemm8(Gemm8Args a) {
     constexpr int TW = G8_TW, NT = 512, NW = 8, NH = G8_NH, R = KC;
     constexpr uint32_t CHUNK = KC * NH * 64;  // uint4 per Q chunk (KC k-blocks of 8 KB)
@@ -187,6 +193,7 @@ __global__ __launch_bounds__(512, 1) void k_flat_gemm8(Gemm8Args a) {
     if constexpr (!RES) __syncthreads();
 
     const uint32_t g_begin = MODE == G8_SAMPLE ? blockIdx.y : 0, g_end = MODE == G8_SAMPLE ? blockIdx.y + 1 : a.ngroups;
+    uint32_t stage_n = 0;  // wave-uniform: lanes in the wave's stage (EPI 0: carried over units; empty at every hand-over, so at every change of group)
     for (uint32_t grp = g_begin + c_member; grp < g_end; grp += coop ? coopS : 1u) {
         const uint4 *qgrp = a.qfrag + uint64_t(grp) * nchunk * CHUNK;
         if constexpr (RES) {  // (the previous group's readers are past the hand-over's last barrier)
@@ -213,6 +220,63 @@ __global__ __launch_bounds__(512, 1) void k_flat_gemm8(Gemm8Args a) {
             qr1 = __builtin_bit_cast(i32x4, q0p[64]);
             qr2 = __builtin_bit_cast(i32x4, q0p[128]);
         }
+        // the wave's stage -> the workgroup's hit buffer (per key: exact test against the query's threshold, rows past n dropped)
+        auto drain = [&](const uint32_t lane) {  // (the caller's lane id: kept across the main loop it is spilled)
+            float4 *stage_k = reinterpret_cast<float4 *>(stage_s) + wave * G8_STAGE;
+            uint32_t *stage_r = reinterpret_cast<uint32_t *>(reinterpret_cast<float4 *>(stage_s) + 8 * G8_STAGE) + wave * G8_STAGE;
+            uint32_t *stage_q = stage_r + 8 * G8_STAGE;
+            const uint32_t cnt = stage_n < G8_STAGE ? stage_n : G8_STAGE;
+            for (uint32_t i = lane; i < cnt; i += 64) {
+                const float4 kv = stage_k[i];
+                const uint2 mt = make_uint2(stage_r[i], stage_q[i]);
+                const float tq = tau_s[mt.y];
+                const bool p0 = kv.x <= tq && mt.x + 0 < n, p1 = kv.y <= tq && mt.x + 1 < n;
+                const bool p2 = kv.z <= tq && mt.x + 2 < n, p3 = kv.w <= tq && mt.x + 3 < n;
+                const uint32_t mine = uint32_t(p0) + uint32_t(p1) + uint32_t(p2) + uint32_t(p3);
+                if (mine) {
+                    uint32_t pos = atomicAdd(hit_n, mine);
+                    // every reserved slot below WGBUF is written (the hand-off reads min(total, WGBUF) slots); a key that finds the
+                    // buffer full goes straight to its query's candidate list (one global atomic per key: the slow path of hit
+                    // densities above ~3 % of the rows -- small tables with long lists, the second attempt of k_redo.hip -- where
+                    // rounds 3 flagged the query as overflowed and sent it to the next tier)
+#ifdef G8_NOSPILL  /* measurement builds: the full buffer flags the query (rounds 3) */
+#define G8_SPILL(KEY, E) atomicAdd(&a.cnt[grp * G8_BQ + mt.y], a.cap + 1);
+#else
+#define G8_SPILL(KEY, E)                                                                  \
+    const uint32_t gslot = atomicAdd(&a.cnt[grp * G8_BQ + mt.y], 1u);                     \
+    if (gslot < a.cap) a.cand[(uint64_t(grp) * G8_BQ + mt.y) * a.cap + gslot] = pair_key(KEY, mt.x + E);
+#endif
+#define VDB_PARK8(P, KEY, E)                                                                          \
+    if (P) {                                                                                          \
+        if (pos < WGBUF) {                                                                            \
+            hit_key[pos] = pair_key(KEY, mt.x + E);                                                   \
+            hit_q[pos] = mt.y;                                                                        \
+        } else {                                                                                      \
+            G8_SPILL(KEY, E)                                                                          \
+        }                                                                                             \
+        pos++;                                                                                        \
+    }
+                    if constexpr (EPI == 0) {
+                        // (a rolled loop on purpose: the drain is inlined at every pair but runs once per 8 - 9 units, and four copies of the
+                        // parking code at 25 sites were 40 % of the kernel's instructions)
+#pragma clang loop unroll(disable)
+                        for (uint32_t e = 0; e < 4; e++) {
+                            const bool pe = e == 0 ? p0 : (e == 1 ? p1 : (e == 2 ? p2 : p3));
+                            const float ke = e == 0 ? kv.x : (e == 1 ? kv.y : (e == 2 ? kv.z : kv.w));
+                            VDB_PARK8(pe, ke, e)
+                        }
+                    } else {
+                        VDB_PARK8(p0, kv.x, 0)
+                        VDB_PARK8(p1, kv.y, 1)
+                        VDB_PARK8(p2, kv.z, 2)
+                        VDB_PARK8(p3, kv.w, 3)
+                    }
+#undef VDB_PARK8
+#undef G8_SPILL
+                }
+            }
+            stage_n = 0;
+        };
         const uint32_t steps = steps_of(slot_cur);
         const uint32_t steps_all = coop ? c_steps_max : steps;                       // workgroup-uniform
         const uint32_t blk = RES && a.coop_block ? a.coop_block : 0xFFFFFFFFu;       // units between two hand-overs
@@ -357,7 +421,7 @@ __global__ __launch_bounds__(512, 1) void k_flat_gemm8(Gemm8Args a) {
             }
             // ---- epilogue: lane holds rows 4*g4..4*g4+3 of each tile for query r of each half ----
             const uint64_t row0 = uint64_t(u_raw) * a.unit_step * (16 * TW);  // the unclamped unit: idle waves are past n
-            uint32_t stage_n = 0;                                             // wave-uniform
+            if constexpr (EPI == 1) stage_n = 0;
             uint32_t lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             asm volatile("" : "+v"(lane_e));  // lane constants recomputed here: carried across the main loop they are spilled
             const uint32_t r = lane_e & 15, g4 = lane_e >> 4, lane = lane_e;  // (shadows the kernel-wide lane)
@@ -372,49 +436,6 @@ __global__ __launch_bounds__(512, 1) void k_flat_gemm8(Gemm8Args a) {
                 tauv[h] = MODE == G8_FILTER ? tau_s[h * 16 + r] : 0.0f;
                 qsv[h] = qs_s[h * 16 + r];
             }
-            // the wave's stage -> the workgroup's hit buffer (per key: exact test against the query's threshold, rows past n dropped)
-            auto drain = [&]() {
-                const uint32_t cnt = stage_n < G8_STAGE ? stage_n : G8_STAGE;
-                for (uint32_t i = lane; i < cnt; i += 64) {
-                    const float4 kv = stage_k[i];
-                    const uint2 mt = make_uint2(stage_r[i], stage_q[i]);
-                    const float tq = tau_s[mt.y];
-                    const bool p0 = kv.x <= tq && mt.x + 0 < n, p1 = kv.y <= tq && mt.x + 1 < n;
-                    const bool p2 = kv.z <= tq && mt.x + 2 < n, p3 = kv.w <= tq && mt.x + 3 < n;
-                    const uint32_t mine = uint32_t(p0) + uint32_t(p1) + uint32_t(p2) + uint32_t(p3);
-                    if (mine) {
-                        uint32_t pos = atomicAdd(hit_n, mine);
-                        // every reserved slot below WGBUF is written (the hand-off reads min(total, WGBUF) slots); a key that finds the
-                        // buffer full goes straight to its query's candidate list (one global atomic per key: the slow path of hit
-                        // densities above ~3 % of the rows -- small tables with long lists, the second attempt of k_redo.hip -- where
-                        // rounds 3 flagged the query as overflowed and sent it to the next tier)
-#ifdef G8_NOSPILL  /* measurement builds: the full buffer flags the query (rounds 3) */
-#define G8_SPILL(KEY, E) atomicAdd(&a.cnt[grp * G8_BQ + mt.y], a.cap + 1);
-#else
-#define G8_SPILL(KEY, E)                                                                  \
-    const uint32_t gslot = atomicAdd(&a.cnt[grp * G8_BQ + mt.y], 1u);                     \
-    if (gslot < a.cap) a.cand[(uint64_t(grp) * G8_BQ + mt.y) * a.cap + gslot] = pair_key(KEY, mt.x + E);
-#endif
-#define VDB_PARK8(P, KEY, E)                                                                          \
-    if (P) {                                                                                          \
-        if (pos < WGBUF) {                                                                            \
-            hit_key[pos] = pair_key(KEY, mt.x + E);                                                   \
-            hit_q[pos] = mt.y;                                                                        \
-        } else {                                                                                      \
-            G8_SPILL(KEY, E)                                                                          \
-        }                                                                                             \
-        pos++;                                                                                        \
-    }
-                        VDB_PARK8(p0, kv.x, 0)
-                        VDB_PARK8(p1, kv.y, 1)
-                        VDB_PARK8(p2, kv.z, 2)
-                        VDB_PARK8(p3, kv.w, 3)
-#undef VDB_PARK8
-#undef G8_SPILL
-                    }
-                }
-                stage_n = 0;
-            };
             float umin[NH];  // (G8_SAMPLE with unit_min)
 #pragma unroll
             for (int h = 0; h < NH; h++) umin[h] = INFINITY;
@@ -422,7 +443,6 @@ __global__ __launch_bounds__(512, 1) void k_flat_gemm8(Gemm8Args a) {
             for (int t = 0; t < TW; t++) {
                 const float4 c4 = *reinterpret_cast<const float4 *>(&c_s[wave * 64 + t * 16 + 4 * g4]);
                 const float4 m4 = *reinterpret_cast<const float4 *>(&m_s[wave * 64 + t * 16 + 4 * g4]);
-                const f32x2 c01 = {c4.x, c4.y}, c23 = {c4.z, c4.w}, m01 = {m4.x, m4.y}, m23 = {m4.z, m4.w};
                 const uint32_t rb32 = uint32_t(row0) + t * 16 + 4 * g4;  // rows < 2^32
 #pragma unroll
                 for (int h = 0; h < NH; h++) {
@@ -433,33 +453,45 @@ __global__ __launch_bounds__(512, 1) void k_flat_gemm8(Gemm8Args a) {
                     const float tau_h = tauv[h], sq = qsv[h];
                     // I is an exact integer (|I| <= 127^2 dim); the conversion is exact up to 2^24, one rounding beyond.
                     // key = C + M * (s_q * I): two roundings, covered by the certification's rounding term
-                    const f32x2 sq2 = {sq, sq};
-                    f32x2 p01 = {float(acc[t][h][0]), float(acc[t][h][1])}, p23 = {float(acc[t][h][2]), float(acc[t][h][3])};
-                    p01 *= sq2;
-                    p23 *= sq2;
-                    const f32x2 k01 = __builtin_elementwise_fma(p01, m01, c01), k23 = __builtin_elementwise_fma(p23, m23, c23);
+                    float k0, k1, k2, k3;
+                    if constexpr (EPI == 1) {
+                        const f32x2 c01 = {c4.x, c4.y}, c23 = {c4.z, c4.w}, m01 = {m4.x, m4.y}, m23 = {m4.z, m4.w};
+                        const f32x2 sq2 = {sq, sq};
+                        f32x2 p01 = {float(acc[t][h][0]), float(acc[t][h][1])}, p23 = {float(acc[t][h][2]), float(acc[t][h][3])};
+                        p01 *= sq2;
+                        p23 *= sq2;
+                        const f32x2 k01 = __builtin_elementwise_fma(p01, m01, c01), k23 = __builtin_elementwise_fma(p23, m23, c23);
+                        k0 = k01.x, k1 = k01.y, k2 = k23.x, k3 = k23.y;
+                    } else {
+                        // (the empty asm keeps -O3 from packing the four adjacent operations into v_pk_mul_f32 / v_pk_fma_f32 again)
+                        float p0 = float(acc[t][h][0]) * sq, p1 = float(acc[t][h][1]) * sq, p2 = float(acc[t][h][2]) * sq, p3 = float(acc[t][h][3]) * sq;
+                        asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3));
+                        k0 = __builtin_fmaf(p0, m4.x, c4.x), k1 = __builtin_fmaf(p1, m4.y, c4.y);
+                        k2 = __builtin_fmaf(p2, m4.z, c4.z), k3 = __builtin_fmaf(p3, m4.w, c4.w);
+                        asm volatile("" : "+v"(k0), "+v"(k1), "+v"(k2), "+v"(k3));
+                    }
                     if (MODE == G8_SAMPLE && a.unit_min) {  // (wave-uniform) the running minimum of this lane's query of half h over the unit's rows
-                        float m4;
-                        asm("v_min3_f32 %0, %1, %2, %3" : "=v"(m4) : "v"(rb32 + 0 < n ? k01.x : INFINITY), "v"(rb32 + 1 < n ? k01.y : INFINITY),
-                            "v"(rb32 + 2 < n ? k23.x : INFINITY));
-                        asm("v_min3_f32 %0, %1, %2, %3" : "=v"(umin[h]) : "v"(m4), "v"(rb32 + 3 < n ? k23.y : INFINITY), "v"(umin[h]));
+                        float mn;
+                        asm("v_min3_f32 %0, %1, %2, %3" : "=v"(mn) : "v"(rb32 + 0 < n ? k0 : INFINITY), "v"(rb32 + 1 < n ? k1 : INFINITY),
+                            "v"(rb32 + 2 < n ? k2 : INFINITY));
+                        asm("v_min3_f32 %0, %1, %2, %3" : "=v"(umin[h]) : "v"(mn), "v"(rb32 + 3 < n ? k3 : INFINITY), "v"(umin[h]));
                         continue;
                     }
                     if (MODE == G8_SAMPLE) {
                         if (u_raw < a.n_units) {  // wave-uniform: waves past the last sampled unit write nothing
                             float4 kv;
-                            kv.x = rb32 + 0 < n ? k01.x : INFINITY;
-                            kv.y = rb32 + 1 < n ? k01.y : INFINITY;
-                            kv.z = rb32 + 2 < n ? k23.x : INFINITY;
-                            kv.w = rb32 + 3 < n ? k23.y : INFINITY;
+                            kv.x = rb32 + 0 < n ? k0 : INFINITY;
+                            kv.y = rb32 + 1 < n ? k1 : INFINITY;
+                            kv.z = rb32 + 2 < n ? k2 : INFINITY;
+                            kv.w = rb32 + 3 < n ? k3 : INFINITY;
                             const uint64_t col = uint64_t(u_raw) * (16 * TW) + t * 16 + 4 * g4;  // dense position in the sample
                             *reinterpret_cast<float4 *>(a.out + (uint64_t(grp) * G8_BQ + h * 16 + r) * a.ld + col) = kv;
                         }
                         continue;
                     }
                     float kmin3, kmin;  // NaN keys never pass: v_min returns the other operand, the per-key tests are ordered
-                    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(kmin3) : "v"(k01.x), "v"(k01.y), "v"(k23.x));
-                    asm("v_min_f32 %0, %1, %2" : "=v"(kmin) : "v"(kmin3), "v"(k23.y));
+                    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(kmin3) : "v"(k0), "v"(k1), "v"(k2));
+                    asm("v_min_f32 %0, %1, %2" : "=v"(kmin) : "v"(kmin3), "v"(k3));
                     const bool pass = kmin <= tau_h;
                     const uint64_t pm = __ballot(pass);
                     if (pm) {  // wave-uniform (a quarter of the pairs at ~1000 hits per query and 1M rows)
@@ -467,10 +499,10 @@ __global__ __launch_bounds__(512, 1) void k_flat_gemm8(Gemm8Args a) {
                         // the stage is drained BEFORE a pair that would not fit (np <= 64 = G8_STAGE always fits an empty one): no
                         // resume state -- the earlier break-and-redo form kept its loop state in vector registers and cost 14 % of
                         // the kernel (ablation -DG8_ABLATE=1 on the resident form: 1.30 -> 1.12 ms)
-                        if (stage_n + np > G8_STAGE) drain();
+                        if (stage_n + np > G8_STAGE) drain(lane);
                         if (pass) {
                             const uint32_t slot = stage_n + __builtin_amdgcn_mbcnt_hi(uint32_t(pm >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(pm), 0u));
-                            stage_k[slot] = make_float4(k01.x, k01.y, k23.x, k23.y);
+                            stage_k[slot] = make_float4(k0, k1, k2, k3);
                             stage_r[slot] = rb32;
                             stage_q[slot] = h * 16 + r;
                         }
@@ -489,10 +521,11 @@ __global__ __launch_bounds__(512, 1) void k_flat_gemm8(Gemm8Args a) {
                     if (g4 == 0) a.out[(uint64_t(grp) * G8_BQ + h * 16 + r) * a.ld + u_raw] = m;
                 }
             }
-            if (MODE == G8_FILTER && stage_n) drain();  // once per unit
+            if (EPI == 1 && MODE == G8_FILTER && stage_n) drain(lane);  // once per unit
         }
         // ---- group end (cooperative form: end of a block of units): hand the parked hits to the per-query candidate lists (one
         // global atomic per query) ----
+        if (EPI == 0 && MODE == G8_FILTER && stage_n) drain(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));  // what the wave still holds
         __syncthreads();
         if (MODE == G8_FILTER) {
             uint32_t total = hit_n[0];
@@ -545,8 +578,13 @@ bool gemm8_supported(uint32_t dim) {
 static size_t gemm8_res_lds(uint32_t KB) {
     return size_t(KB) * G8_NH * 64 * sizeof(uint4) + size_t(G8_WGBUF_RES) * 12 + (4 + 4 * G8_BQ + 2 * 8 * 64) * 4 + size_t(8) * G8_STAGE * 24 + 16;
 }
-template <int KC, int MODE, bool XNT, bool BURST, bool RES>
-static void flat_gemm8_launch1(const Gemm8Args &a0, int num_cu, hipStream_t s) {
+static std::atomic<int> g_gemm8_epi{0};  // unit epilogue: 0 = scalar key arithmetic, the stage carried over units; 1 = the earlier form (see the kernel)
+void gemm8_set_epi(int v) {
+    VDB_REQUIRE(v == 0 || v == 1, "flat_gemm8_epi: 0 (scalar arithmetic, carried stage) or 1 (packed arithmetic, one drain per unit)");
+    g_gemm8_epi = v;
+}
+template <int KC, int MODE, bool XNT, bool BURST, bool RES, int EPI>
+static void flat_gemm8_launch2(const Gemm8Args &a0, int num_cu, hipStream_t s) {
     Gemm8Args a = a0;
     const uint64_t n_tiles = (a.n + 15) / 16;
     const uint32_t units_all = (uint32_t)((n_tiles + G8_TW - 1) / G8_TW);
@@ -565,9 +603,16 @@ static void flat_gemm8_launch1(const Gemm8Args &a0, int num_cu, hipStream_t s) {
     const size_t lds = RES ? gemm8_res_lds(a.KB)
                            : size_t(2) * KC * G8_NH * 64 * sizeof(uint4) + size_t(G8_WGBUF) * 12 + (4 + 4 * G8_BQ + 2 * 8 * 64) * 4 +
                                  size_t(8) * G8_STAGE * 24 + 16;
-    func_max_lds(reinterpret_cast<const void *>(&k_flat_gemm8<KC, MODE, XNT, BURST, RES>), int(160 * 1024));
-    hipLaunchKernelGGL((k_flat_gemm8<KC, MODE, XNT, BURST, RES>), dim3(grid, MODE == G8_SAMPLE ? a.ngroups : 1), dim3(512), lds, s, a);
+    func_max_lds(reinterpret_cast<const void *>(&k_flat_gemm8<KC, MODE, XNT, BURST, RES, EPI>), int(160 * 1024));
+    hipLaunchKernelGGL((k_flat_gemm8<KC, MODE, XNT, BURST, RES, EPI>), dim3(grid, MODE == G8_SAMPLE ? a.ngroups : 1), dim3(512), lds, s, a);
     VDB_HIP(hipGetLastError());
+}
+template <int KC, int MODE, bool XNT, bool BURST, bool RES>
+static void flat_gemm8_launch1(const Gemm8Args &a, int num_cu, hipStream_t s) {
+    if (g_gemm8_epi == 1)
+        flat_gemm8_launch2<KC, MODE, XNT, BURST, RES, 1>(a, num_cu, s);
+    else
+        flat_gemm8_launch2<KC, MODE, XNT, BURST, RES, 0>(a, num_cu, s);
 }
 static std::atomic<int> g_gemm8_kc{0};  // 0 auto; 5 / 3 / 2: chunk length when the k-block count allows it
 void gemm8_set_kc(int v) { g_gemm8_kc = v; }
@@ -581,8 +626,13 @@ void gemm8_set_sample_res(int v) { g_gemm8_sample_res = v; }
 
 static std::atomic<int> g_gemm8_coop{0};  // 0 auto (cooperative sets when the shape allows), 1 off
 void gemm8_set_coop(int v) { g_gemm8_coop = v; }
-static std::atomic<int> g_gemm8_grid{0};  // measurement switch: workgroups of the cooperative filter (0 = 256; a multiple of 64: whole sets on every XCD)
-void gemm8_set_grid(int v) { g_gemm8_grid = (v >= 64 && v <= 256 && v % 64 == 0) ? v : 0; }
+// measurement switch: workgroups of the cooperative filter (0 = 256).  A multiple of 32 gives every XCD the same whole number of sets of 4
+// or 2; sets of 8 need a multiple of 64 (checked at the launch, where the set size is known).  Anything else is an error, not a rounding.
+static std::atomic<int> g_gemm8_grid{0};
+void gemm8_set_grid(int v) {
+    VDB_REQUIRE(v == 0 || (v >= 32 && v <= 256 && v % 32 == 0), "flat_gemm8_grid: 0, or a multiple of 32 up to 256");
+    g_gemm8_grid = v;
+}
 static std::atomic<uint32_t> g_gemm8_last_coop{0};  // set size of the most recent filter launch (0: no sets)
 uint32_t gemm8_last_coop() { return g_gemm8_last_coop; }
 
@@ -606,7 +656,9 @@ static void flat_gemm8_launch(const Gemm8Args &a0, int num_cu, hipStream_t s) {
                 const double per_unit = 8.0 * 48.0 * 128.0 * double(a.hits_expected ? a.hits_expected : 1024u) / double(a.n);
                 const double b = double(G8_WGBUF_RES) * 0.8 / per_unit;
                 a.coop_block = b < 1.0 ? 1u : (b > 4096.0 ? 4096u : uint32_t(b));
-                flat_gemm8_launch1<KC, MODE, false, false, true>(a, g_gemm8_grid ? (int)g_gemm8_grid : num_cu, s);  // default loads: the members meet in the L2
+                const int grid = g_gemm8_grid ? (int)g_gemm8_grid : num_cu;
+                VDB_REQUIRE((grid / 8) % S == 0, "flat_gemm8_grid: the sets do not divide the workgroups of an XCD (sets of 8 need a multiple of 64)");
+                flat_gemm8_launch1<KC, MODE, false, false, true>(a, grid, s);  // default loads: the members meet in the L2
                 return;
             }
         }

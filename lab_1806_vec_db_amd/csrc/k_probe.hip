@@ -164,53 +164,70 @@ double stream_probe_pattern(int device, uint64_t bytes, int iters, int pattern_s
 // ---- matrix-pipe rate of THIS box under sustained load ------------------------------------------------------------------
 // v_mfma_f32_16x16x32_f16 (the Flat filter's instruction) issued back to back from `waves_per_simd` waves per SIMD on
 // every CU, 8 independent accumulator tiles per wave: TFLOP/s over the whole launch and the shader clock the chip held
-// meanwhile (s_memtime cycles of one wave over the event time).  Measurement hook only.
+// meanwhile.  The clock is read INSIDE the kernel: every workgroup stamps the shader counter (s_memtime, one tick per shader cycle)
+// and the constant 100-MHz counter (s_memrealtime) around its loop, clock = d(shader) / d(real) x 100 MHz, median over the
+// workgroups.  (Shader cycles of one wave over the EVENT time read low by whatever part of the window the wave was not running:
+// with four waves per SIMD the figure was "1.06 GHz", i.e. 2 436 op/cycle/SIMD from an instruction that cannot exceed 2 048.)
+// The operands come from a pseudo-random table: lane-constant or zero patterns toggle few bits, the chip then holds a higher clock
+// than any real operand stream gets, and the probe reads high.  The stamps go to a buffer of their own.  Measurement hook only.
 typedef _Float16 pf16x8 __attribute__((ext_vector_type(8)));
 typedef float pf32x4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void k_probe_mfma(uint32_t iters, float *out, unsigned long long *cycles) {
+constexpr uint32_t PROBE_TAB_WORDS = 256 * 8;  // two 16-B operands per thread of a workgroup
+__global__ __launch_bounds__(256) void k_probe_mfma(uint32_t iters, float *out, const uint32_t *__restrict__ tab, unsigned long long *stamps) {
     pf32x4 acc[8];
     pf16x8 a, b;
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
-        a[i] = (_Float16)(float(threadIdx.x & 7) * 0.125f + float(i));
-        b[i] = (_Float16)(float(threadIdx.x & 3) * 0.25f - float(i));
+    for (int i = 0; i < 4; i++) {  // 16 random bits per element, scaled into [-1, 1): finite, full mantissa, both signs
+        const uint32_t wa = tab[threadIdx.x * 8 + i], wb = tab[threadIdx.x * 8 + 4 + i];
+        a[2 * i] = (_Float16)(float(int(wa & 0xFFFFu) - 32768) * (1.0f / 32768.0f));
+        a[2 * i + 1] = (_Float16)(float(int(wa >> 16) - 32768) * (1.0f / 32768.0f));
+        b[2 * i] = (_Float16)(float(int(wb & 0xFFFFu) - 32768) * (1.0f / 32768.0f));
+        b[2 * i + 1] = (_Float16)(float(int(wb >> 16) - 32768) * (1.0f / 32768.0f));
     }
 #pragma unroll
     for (int t = 0; t < 8; t++) acc[t] = (pf32x4){0.f, 0.f, 0.f, 0.f};
-    const unsigned long long c0 = clock64();
+    const unsigned long long c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
     for (uint32_t it = 0; it < iters; it++) {
 #pragma unroll
         for (int t = 0; t < 8; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc[t], 0, 0, 0);
     }
-    const unsigned long long c1 = clock64();
     float sum = 0.f;
 #pragma unroll
     for (int t = 0; t < 8; t++) sum += acc[t][0] + acc[t][1] + acc[t][2] + acc[t][3];
-    if (sum == 12345.678f) out[0] = sum;
-    if (blockIdx.x == 0 && threadIdx.x == 0) cycles[0] = c1 - c0;
+    if (sum == 12345.678f) out[0] = sum;  // (the sum waits for the last MFMA: the closing stamps are taken after it)
+    asm volatile("" ::"v"(sum));
+    const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    if (threadIdx.x == 0) {
+        stamps[2 * blockIdx.x] = c1 - c0;
+        stamps[2 * blockIdx.x + 1] = r1 - r0;
+    }
 }
 // the 8-bit filter's instruction (k_gemm8.hip): v_mfma_i32_16x16x64_i8, 2 x 16 x 16 x 64 integer operations each
 typedef int pi32x4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void k_probe_mfma_i8(uint32_t iters, float *out, unsigned long long *cycles) {
+__global__ __launch_bounds__(256) void k_probe_mfma_i8(uint32_t iters, float *out, const uint32_t *__restrict__ tab, unsigned long long *stamps) {
     pi32x4 acc[8], a, b;
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        a[i] = int(threadIdx.x * 0x01010101u + i * 0x00010203u);
-        b[i] = int(threadIdx.x * 0x01020304u - i * 0x01000100u);
+    for (int i = 0; i < 4; i++) {  // random bytes
+        a[i] = int(tab[threadIdx.x * 8 + i]);
+        b[i] = int(tab[threadIdx.x * 8 + 4 + i]);
     }
 #pragma unroll
     for (int t = 0; t < 8; t++) acc[t] = (pi32x4){0, 0, 0, 0};
-    const unsigned long long c0 = clock64();
+    const unsigned long long c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
     for (uint32_t it = 0; it < iters; it++) {
 #pragma unroll
         for (int t = 0; t < 8; t++) acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, acc[t], 0, 0, 0);
     }
-    const unsigned long long c1 = clock64();
     int sum = 0;
 #pragma unroll
     for (int t = 0; t < 8; t++) sum += acc[t][0] + acc[t][1] + acc[t][2] + acc[t][3];
     if (sum == 0x12345678) out[0] = float(sum);
-    if (blockIdx.x == 0 && threadIdx.x == 0) cycles[0] = c1 - c0;
+    asm volatile("" ::"v"(sum));
+    const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    if (threadIdx.x == 0) {
+        stamps[2 * blockIdx.x] = c1 - c0;
+        stamps[2 * blockIdx.x + 1] = r1 - r0;
+    }
 }
 void mfma_probe(int device, int waves_per_simd, int iters, double *tflops, double *clock_ghz, int i8) {
     VDB_HIP(hipSetDevice(device));
@@ -218,42 +235,64 @@ void mfma_probe(int device, int waves_per_simd, int iters, double *tflops, doubl
     hipDeviceProp_t prop;
     VDB_HIP(hipGetDeviceProperties(&prop, device));
     const unsigned grid = (unsigned)prop.multiProcessorCount * (unsigned)waves_per_simd;  // 4 waves per block: one per SIMD
-    void *out = nullptr, *cyc = nullptr;
+    std::vector<uint32_t> tab(PROBE_TAB_WORDS);
+    uint64_t st = 0x1806ull;
+    for (auto &w : tab) {  // splitmix64
+        st += 0x9E3779B97F4A7C15ull;
+        uint64_t z = st;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        w = uint32_t((z ^ (z >> 31)) >> 16);
+    }
+    void *out = nullptr, *dtab = nullptr, *stamps = nullptr;
     hipStream_t s = nullptr;
     hipEvent_t ea = nullptr, eb = nullptr;
     try {
         VDB_HIP(hipMalloc(&out, 64));
-        VDB_HIP(hipMalloc(&cyc, 64));
+        VDB_HIP(hipMalloc(&dtab, tab.size() * sizeof(uint32_t)));
+        VDB_HIP(hipMalloc(&stamps, size_t(grid) * 2 * sizeof(unsigned long long)));
+        VDB_HIP(hipMemcpy(dtab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         VDB_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         VDB_HIP(hipEventCreate(&ea));
         VDB_HIP(hipEventCreate(&eb));
         auto kern = i8 ? k_probe_mfma_i8 : k_probe_mfma;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, (uint32_t)iters, static_cast<float *>(out), static_cast<unsigned long long *>(cyc));
+        auto launch = [&]() {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, (uint32_t)iters, static_cast<float *>(out), static_cast<const uint32_t *>(dtab),
+                               static_cast<unsigned long long *>(stamps));
+        };
+        launch();  // (warm-up; the stamps kept are the timed launch's, which follows it back to back)
         VDB_HIP(hipEventRecord(ea, s));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, (uint32_t)iters, static_cast<float *>(out), static_cast<unsigned long long *>(cyc));
+        launch();
         VDB_HIP(hipEventRecord(eb, s));
         VDB_HIP(hipEventSynchronize(eb));
         VDB_HIP(hipGetLastError());
         float ms = 0;
         VDB_HIP(hipEventElapsedTime(&ms, ea, eb));
-        unsigned long long c = 0;
-        VDB_HIP(hipMemcpy(&c, cyc, sizeof(c), hipMemcpyDeviceToHost));
+        std::vector<unsigned long long> h(size_t(grid) * 2);
+        VDB_HIP(hipMemcpy(h.data(), stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        std::vector<double> ghz;
+        for (unsigned g = 0; g < grid; g++)
+            if (h[2 * g + 1] > 0) ghz.push_back(double(h[2 * g]) / double(h[2 * g + 1]) * 0.1);  // the real-time counter runs at 100 MHz
+        VDB_REQUIRE(!ghz.empty(), "mfma probe: no workgroup returned a stamp");
+        std::nth_element(ghz.begin(), ghz.begin() + ghz.size() / 2, ghz.end());
         const double flops = double(grid) * 4.0 * double(iters) * 8.0 * (2.0 * 16 * 16 * (i8 ? 64 : 32));
         *tflops = flops / (double(ms) * 1e-3) / 1e12;
-        *clock_ghz = double(c) / (double(ms) * 1e-3) / 1e9;  // (the timed wave runs for all but the launch overhead of the event window)
+        *clock_ghz = ghz[ghz.size() / 2];
     } catch (...) {
         if (ea) (void)hipEventDestroy(ea);
         if (eb) (void)hipEventDestroy(eb);
         if (s) (void)hipStreamDestroy(s);
         if (out) (void)hipFree(out);
-        if (cyc) (void)hipFree(cyc);
+        if (dtab) (void)hipFree(dtab);
+        if (stamps) (void)hipFree(stamps);
         throw;
     }
     (void)hipEventDestroy(ea);
     (void)hipEventDestroy(eb);
     (void)hipStreamDestroy(s);
     (void)hipFree(out);
-    (void)hipFree(cyc);
+    (void)hipFree(dtab);
+    (void)hipFree(stamps);
 }
 
 // ---- latency of ONE dependent HBM access on this box ------------------------------------------------------------------------
