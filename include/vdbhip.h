@@ -139,6 +139,41 @@ int vdb_flat_range_device(vdb_index *idx, const void *d_queries, uint64_t nq, ui
 int vdb_range_lims(const vdb_range *r, uint64_t *out_lims);
 int vdb_range_copy(const vdb_range *r, uint64_t *out_idx, float *out_dist);
 int vdb_range_destroy(vdb_range *r);
+/* ---- exact filtered search over the Flat rows: a row mask ------------------------------------------------------------------------
+ * A vdb_mask is an allow-list over the LOCAL rows of ONE index: row i is allowed iff (bits[i >> 6] >> (i & 63)) & 1; `bits` holds
+ * ceil(n_rows / 64) words, bits at and past n_rows are ignored, and n_rows must equal the index's length (else VDB_ERR_INVALID).
+ * vdb_mask_count gives the number m of allowed rows.  id_offset is added to reported ids as everywhere else.
+ * A mask belongs to the index it was made for AND to that state of its rows: a call with a mask of another index fails with
+ * VDB_ERR_INVALID, a call with a mask made before a later vdb_index_add* / vdb_index_swap_remove with VDB_ERR_STATE (both set
+ * vdb_last_error; nothing is computed).  Creating a mask is read-side; destroy it (NULL is fine) when no call is using it and
+ * before the index is destroyed.  Memory on the index's device: n/8 + 4 m bytes, plus 8 B per padded row once a call has run the
+ * 8-bit tier under the mask (a copy of that tier's per-row constants in which every disallowed row carries a key of +inf).
+ * vdb_flat_knn_filtered: per query the first min(k, m) pairs of FlatIndex::knn over the ALLOWED rows alone -- distances bit-exact,
+ * ascending by (distance, id), out_count[q] = min(k, m), slots past the count zero.  Any k, any dim, L2Sqr and Cosine, f32 indexes
+ * only: a VecSet<u8> index is VDB_ERR_INVALID ("needs f32 rows").  nq == 0, k == 0 and m == 0 give empty results; PQ / HNSW / IVF
+ * state of the index is irrelevant.  Read-side and re-entrant like vdb_flat_knn; the _device form takes device-resident queries and
+ * outputs (at most 32768 queries), synchronises `stream` first and returns synchronised.
+ * How it is answered (csrc/k_filter.hip, docs/DESIGN_flat.md "Filtered search"): allow-lists of at most "flat_filtered_direct_max"
+ * rows (vdb_set_param, per index, default 8192), k > 64, and every table the 8-bit pass does not serve take the DIRECT path: the
+ * strict-order scan over the gathered allowed rows, 8 queries per fetch of a row.  Longer lists on tables of at least 16 384 rows
+ * run the unfiltered search's 8-bit filter pass with the mask's row constants -- the same kernel over the same bytes -- and its exact
+ * stage; a query that stage cannot close is redone by the direct path.  vdb_flat_set_mode applies (1 = direct only, 2 = the tier
+ * wherever the shape allows).  The call never touches the unfiltered search's auto-off counters.
+ * vdb_get_stat: "flat_filtered_queries", "flat_filtered_direct_queries", "flat_filtered_i8_queries" (queries through the tier),
+ * "flat_filtered_fallback_queries" (of those, handed on to the direct path); vdb_prof_get: "flat_filtered_scan", "flat_filtered_i8".
+ * vdb_flat_range_filtered: vdb_flat_range over the allowed rows alone -- every ALLOWED row with D <= radius[q]; everything else as
+ * documented there (f32 and VecSet<u8> indexes, the same tiers and counters).
+ * Not covered: sharded and replica contexts, _begin / _end pipelining, filtered PQ / HNSW / IVF searches, k-NN on u8 indexes. */
+typedef struct vdb_mask vdb_mask;
+int vdb_mask_create(vdb_index *idx, const uint64_t *bits, uint64_t n_rows, vdb_mask **out);
+int vdb_mask_count(const vdb_mask *m, uint64_t *out);
+int vdb_mask_destroy(vdb_mask *m);
+int vdb_flat_knn_filtered(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, const vdb_mask *mask,
+                          uint64_t *out_idx, float *out_dist, uint64_t *out_count);
+int vdb_flat_knn_filtered_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, const vdb_mask *mask,
+                                 void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
+int vdb_flat_range_filtered(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit,
+                            const vdb_mask *mask, vdb_range **out);
 /* the approximate keys the Flat shortlist pass compares with its threshold, for EVERY row, from the same kernel in its dense
  * mode (test / measurement entry point behind the certification-bound tests): out_keys [nq][len];
  * L2Sqr: key = |x|^2 - 2 S~, approximate distance = key + |q|^2;  Cosine: key = -S~ / |x|, approximate distance = 1 + key / |q|.

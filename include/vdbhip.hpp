@@ -52,6 +52,37 @@ inline std::vector<std::vector<CandidatePair>> take_range(vdb_range *r, uint64_t
 
 // DynamicIndex: starts as the Flat arm; build_hnsw() switches to the HNSW arm like
 // MetadataVecTable::build_hnsw_index (metadata_vec_table.rs:112-135), clear_hnsw() back (:137-152).
+// A row allow-list of one DynamicIndex (vdb_mask; DynamicIndex::make_mask): valid until rows are added to or removed from that index,
+// destroyed before it.
+class Mask {
+public:
+    Mask() = default;
+    explicit Mask(vdb_mask *h) : h_(h) {}
+    ~Mask() {
+        if (h_) vdb_mask_destroy(h_);
+    }
+    Mask(const Mask &) = delete;
+    Mask &operator=(const Mask &) = delete;
+    Mask(Mask &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Mask &operator=(Mask &&o) noexcept {
+        if (this != &o) {
+            if (h_) vdb_mask_destroy(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    uint64_t count() const {  // allowed rows
+        uint64_t m = 0;
+        check(vdb_mask_count(h_, &m));
+        return m;
+    }
+    const vdb_mask *handle() const { return h_; }
+
+private:
+    vdb_mask *h_ = nullptr;
+};
+
 // The PQ table hangs off the index handle (the reference passes &PQTable into knn_pq; here it is attached state).
 class DynamicIndex {
 public:
@@ -128,6 +159,33 @@ public:
     std::vector<CandidatePair> range_search(const std::vector<float> &query, float radius, uint64_t limit = 0) const {
         require_dim(query.size());
         return range_search_batch(query.data(), 1, &radius, limit)[0];
+    }
+
+    // filtered exact searches over a row mask (vdb_mask_create): `allow[i]` says whether local row i may be returned
+    Mask make_mask(const std::vector<bool> &allow) const {
+        std::vector<uint64_t> bits((allow.size() + 63) / 64, 0);
+        for (size_t i = 0; i < allow.size(); i++)
+            if (allow[i]) bits[i >> 6] |= 1ull << (i & 63);
+        vdb_mask *m = nullptr;
+        check(vdb_mask_create(h_, bits.data(), allow.size(), &m));
+        return Mask(m);
+    }
+    // per query the first min(k, mask.count()) pairs of knn_batch over the allowed rows alone (vdb_flat_knn_filtered)
+    std::vector<std::vector<CandidatePair>> knn_filtered_batch(const float *queries, uint64_t nq, uint64_t k, const Mask &mask) const {
+        std::vector<uint64_t> idx(nq * (k ? k : 1)), cnt(nq);
+        std::vector<float> d(nq * (k ? k : 1));
+        check(vdb_flat_knn_filtered(h_, queries, nq, dim_, k, mask.handle(), idx.data(), d.data(), cnt.data()));
+        std::vector<std::vector<CandidatePair>> out(nq);
+        for (uint64_t q = 0; q < nq; q++)
+            for (uint64_t j = 0; j < cnt[q]; j++) out[q].push_back({idx[q * k + j], d[q * k + j]});
+        return out;
+    }
+    // range_search_batch over the allowed rows alone (vdb_flat_range_filtered)
+    std::vector<std::vector<CandidatePair>> range_search_filtered_batch(const float *queries, uint64_t nq, const float *radius, const Mask &mask,
+                                                                        uint64_t limit = 0) const {
+        vdb_range *r = nullptr;
+        check(vdb_flat_range_filtered(h_, queries, nq, dim_, radius, limit, mask.handle(), &r));
+        return take_range(r, nq);
     }
 
     // MetadataVecTable::build_hnsw_index / clear_hnsw_index, build_pq_table / clear_pq_table

@@ -48,6 +48,12 @@ SIGNATURES = {
     "vdb_range_lims": [vp, u64p],
     "vdb_range_copy": [vp, u64p, f32p],
     "vdb_range_destroy": [vp],
+    "vdb_mask_create": [vp, u64p, u64, C.POINTER(vp)],
+    "vdb_mask_count": [vp, u64p],
+    "vdb_mask_destroy": [vp],
+    "vdb_flat_knn_filtered": [vp, f32p, u64, u64, u64, vp, u64p, f32p, u64p],
+    "vdb_flat_knn_filtered_device": [vp, vp, u64, u64, u64, vp, vp, vp, vp, vp],
+    "vdb_flat_range_filtered": [vp, f32p, u64, u64, f32p, u64, vp, C.POINTER(vp)],
     "vdb_flat_shortlist_keys": [vp, f32p, u64, u64, C.c_int, f32p, f32p, f32p, f32p],
     "vdb_flat_set_mode": [vp, C.c_int],
     "vdb_index_prepare": [vp, C.c_int],

@@ -536,6 +536,164 @@ int vdb_range_destroy(vdb_range *r) {
     VDB_API_END
 }
 
+// ---- exact filtered Flat search over a row mask -----------------------------------------------------------------------------------------
+int vdb_mask_create(vdb_index *idx, const uint64_t *bits, uint64_t n_rows, vdb_mask **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx && out, "null argument");
+    *out = nullptr;
+    Index &ix = idx->ix;
+    VDB_REQUIRE(n_rows == ix.n, "mask: " + std::to_string(n_rows) + " rows, the index holds " + std::to_string(ix.n));
+    VDB_REQUIRE(n_rows == 0 || bits, "null argument");
+    ix.use_device();
+    std::unique_ptr<vdb_mask> mk(new vdb_mask);
+    RowMask &m = mk->m;
+    m.owner = &ix;
+    m.device = ix.device;
+    m.gen = ix.write_gen.load();
+    m.n_rows = n_rows;
+    const uint64_t nw = (n_rows + 63) / 64;
+    std::vector<uint64_t> w(bits, bits + nw);
+    if (n_rows & 63) w[nw - 1] &= (1ull << (n_rows & 63)) - 1;  // bits at and past n_rows are ignored
+    uint64_t cnt = 0;
+    for (uint64_t x : w) cnt += (uint64_t)__builtin_popcountll(x);
+    std::vector<uint32_t> ids;
+    ids.reserve(cnt);
+    for (uint64_t i = 0; i < nw; i++)
+        for (uint64_t x = w[i]; x; x &= x - 1) ids.push_back((uint32_t)(i * 64 + (uint64_t)__builtin_ctzll(x)));
+    m.m = cnt;
+    try {
+        m.d_bits.reserve(std::max<uint64_t>(nw, 1) * sizeof(uint64_t));
+        m.d_ids.reserve(std::max<uint64_t>(cnt, 1) * sizeof(uint32_t));
+        if (nw) VDB_HIP(hipMemcpy(m.d_bits.p, w.data(), nw * sizeof(uint64_t), hipMemcpyHostToDevice));
+        if (cnt) VDB_HIP(hipMemcpy(m.d_ids.p, ids.data(), cnt * sizeof(uint32_t), hipMemcpyHostToDevice));
+    } catch (...) {
+        m.d_bits.release();
+        m.d_ids.release();
+        throw;
+    }
+    *out = mk.release();
+    VDB_API_END
+}
+
+int vdb_mask_count(const vdb_mask *m, uint64_t *out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(m && out, "null argument");
+    *out = m->m.m;
+    VDB_API_END
+}
+
+int vdb_mask_destroy(vdb_mask *m) {
+    VDB_API_BEGIN
+    if (m) {
+        (void)hipSetDevice(m->m.device);
+        delete m;
+    }
+    VDB_API_END
+}
+
+static void filtered_check(const Index &ix, const vdb_mask *mask) {
+    VDB_REQUIRE(mask, "null mask");
+    VDB_REQUIRE(!ix.elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    ix.check_mask(mask->m);
+}
+
+int vdb_flat_knn_filtered(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, const vdb_mask *mask, uint64_t *out_idx,
+                          float *out_dist, uint64_t *out_count) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_query_args(ix, queries, nq, dim, out_idx, out_dist);
+    filtered_check(ix, mask);
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    hipStream_t s = ws->stream;
+    constexpr uint64_t CHUNK = 16384;
+    const uint64_t kk = std::max<uint64_t>(k, 1), ch = std::min(nq, CHUNK);
+    // one device block for the outputs of a chunk [ids | distances | counts], as host_search lays them out
+    const size_t off_d = ch * kk * sizeof(uint64_t), off_c = (off_d + ch * kk * sizeof(float) + 7) & ~size_t(7);
+    ws->q.reserve(ch * dim * sizeof(float));
+    ws->out_idx.reserve(off_c + ch * sizeof(uint64_t));
+    char *d_out = ws->out_idx.as<char>();
+    try {
+        for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
+            const uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
+            VDB_HIP(hipMemcpyAsync(ws->q.p, queries + q0 * dim, nb * dim * sizeof(float), hipMemcpyHostToDevice, s));
+            ix.flat_knn_masked_device(*ws, ws->q.as<float>(), nb, k, mask->m, reinterpret_cast<uint64_t *>(d_out), reinterpret_cast<float *>(d_out + off_d),
+                                      reinterpret_cast<uint64_t *>(d_out + off_c));
+            if (k) {
+                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
+            }
+            if (out_count) VDB_HIP(hipMemcpyAsync(out_count + q0, d_out + off_c, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            VDB_SYNC(s);
+        }
+    } catch (...) {
+        (void)hipStreamSynchronize(s);  // nothing of a failed call is still running when its buffers go
+        ix.prof_collect(*ws);
+        throw;
+    }
+    ix.prof_collect(*ws);
+    VDB_API_END
+}
+
+int vdb_flat_knn_filtered_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, const vdb_mask *mask, void *d_out_idx,
+                                 void *d_out_dist, void *d_out_count, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_query_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist);
+    VDB_REQUIRE(nq == 0 || d_out_count, "null out_count");
+    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
+    filtered_check(ix, mask);
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
+    try {
+        ix.flat_knn_masked_device(*ws, static_cast<const float *>(d_queries), nq, k, mask->m, static_cast<uint64_t *>(d_out_idx),
+                                  static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
+    } catch (...) {
+        (void)hipStreamSynchronize(ws->stream);
+        ix.prof_collect(*ws);
+        throw;
+    }
+    ix.prof_collect(*ws);
+    VDB_API_END
+}
+
+int vdb_flat_range_filtered(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit, const vdb_mask *mask,
+                            vdb_range **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    range_check(ix, queries, nq, dim, radius, out);
+    VDB_REQUIRE(mask, "null mask");
+    ix.check_mask(mask->m);
+    ix.use_device();
+    std::unique_ptr<vdb_range> res(new vdb_range);
+    WsLease ws(ix);
+    const float *d_q = nullptr, *d_r = nullptr;
+    if (nq) {
+        const size_t qb = nq * dim * sizeof(float), qb_pad = (qb + 255) & ~size_t(255);
+        ws->q.reserve(qb_pad + nq * sizeof(float));  // [queries | radii]
+        VDB_HIP(hipMemcpyAsync(ws->q.p, queries, qb, hipMemcpyHostToDevice, ws->stream));
+        VDB_HIP(hipMemcpyAsync(ws->q.as<char>() + qb_pad, radius, nq * sizeof(float), hipMemcpyHostToDevice, ws->stream));
+        d_q = ws->q.as<float>();
+        d_r = reinterpret_cast<const float *>(ws->q.as<char>() + qb_pad);
+    }
+    try {
+        ix.flat_range_device(*ws, d_q, nq, d_r, limit, res->r, &mask->m);
+    } catch (...) {
+        (void)hipStreamSynchronize(ws->stream);  // nothing of a failed call is still running when its buffers go
+        ix.prof_collect(*ws);
+        throw;
+    }
+    ix.prof_collect(*ws);
+    *out = res.release();
+    VDB_API_END
+}
+
 int vdb_flat_shortlist_keys(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, int tier, float *out_keys,
                             float *out_qsq, float *out_qerr, float *out_dx4) {
     VDB_API_BEGIN
@@ -623,6 +781,10 @@ int vdb_set_param(vdb_index *idx, const char *name, int64_t value) {
     else if (n == "flat_range_max_results") {  // ceiling on the pairs one range call may return (0: what the device can hold)
         VDB_REQUIRE(value >= 0, "flat_range_max_results must be >= 0");
         idx->ix.range_max_results = (uint64_t)value;
+    }
+    else if (n == "flat_filtered_direct_max") {  // filtered k-NN: allow-lists of up to this many rows take the gathered strict-order scan
+        VDB_REQUIRE(value >= 0, "flat_filtered_direct_max must be >= 0");
+        idx->ix.flat_filtered_direct_max = (uint64_t)value;
     }
     else if (n == "debug_alloc_fail_over")  // (testing aid, process-wide) device allocations of at least this many bytes fail; 0 = off
         devbuf_fail_over() = (size_t)value;
@@ -722,6 +884,14 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.range_hits_max.load();
     else if (n == "flat_range_results")
         *out = idx->ix.range_results.load();
+    else if (n == "flat_filtered_queries")  // filtered k-NN: queries | answered by the direct path | through the 8-bit tier | of those, handed on to the direct path
+        *out = idx->ix.filtered_queries.load();
+    else if (n == "flat_filtered_direct_queries")
+        *out = idx->ix.filtered_direct_queries.load();
+    else if (n == "flat_filtered_i8_queries")
+        *out = idx->ix.filtered_i8_queries.load();
+    else if (n == "flat_filtered_fallback_queries")
+        *out = idx->ix.filtered_fallback_queries.load();
     else if (n.rfind("flat_i8_rounds_", 0) == 0 && n.size() == 16 && n[15] >= '0' && n[15] <= '8')  // queries whose exact stage walked N rounds (8: 8 or more)
         *out = idx->ix.i8_rounds_hist[n[15] - '0'].load();
     else if (n == "mirror_alloc_failures")  // mirrors of this index whose allocation failed (the tier was left to the next one)

@@ -15,6 +15,11 @@ struct vdb_range {
     vdb::RangeResult r;
 };
 
+// a row allow-list of one index (api.hip: vdb_mask_create; the filtered searches)
+struct vdb_mask {
+    vdb::RowMask m;
+};
+
 namespace vdb {
 void set_last_error(const std::string &m);
 void require_gpu();  // throws VDB_ERR_NOGPU when no HIP device is usable

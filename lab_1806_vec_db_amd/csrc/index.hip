@@ -101,6 +101,7 @@ void Index::add_rows(const void *rows, uint64_t count, bool on_device) {
         }
     }
     n += count;
+    write_gen += 1;
 }
 
 // VecSet::swap_remove (vec_set.rs:131-137)
@@ -150,6 +151,7 @@ void Index::swap_remove(uint64_t i) {
     if (i < last) h_sq[i] = h_sq[last];
     h_sq.resize(last);
     n = last;
+    write_gen += 1;
     // xsq_max stays an upper bound (certification only needs a bound)
 }
 
@@ -901,8 +903,10 @@ uint64_t Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
 //     take, a mirror that cannot be allocated, and the queries the tier did not admit or whose hit list overflowed.
 // The sorted pair keys of both tiers go to a pool in the order they are produced; the CSR arrays are gathered from it at the end
 // (8 B per pair in the pool + 12 B per pair in the result).  Range calls neither read nor write the k-NN tiers' auto-off counters.
-void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit, RangeResult &out) {
+void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit, RangeResult &out,
+                              const RowMask *mask) {
     hipStream_t s = ws.stream;
+    if (mask) check_mask(*mask);
     out.device = device;
     out.nq = nq;
     out.lims.assign(nq + 1, 0);
@@ -934,6 +938,8 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
     };
     std::vector<uint64_t> scan;  // queries the scan tier answers
     const bool tier = flat_mode != 1 && (flat_mode == 2 || n >= 16384) && flat_gemm_mode != 1 && i8_mirror_applicable() && ensure_i8(ws);
+    // under a mask the filter pass reads the masked copy of the row constants: a disallowed row's key is +inf and passes no (finite) threshold
+    const float *rowc = tier ? (mask ? masked_rowc(ws, *mask) : d_rowc_i8.as<float>()) : nullptr;
     if (!tier) {
         scan.resize(nq);
         for (uint64_t q = 0; q < nq; q++) scan[q] = q;
@@ -955,12 +961,13 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
                              d_hits, ws.qfrag_g.p, s, cosine);
         launch_i8_tau_from_dk(R, (uint32_t)nb, (uint32_t)nq_pad, d_qoff, ws.qsq.as<float>(), xsq_max, i8_mu_norm, (uint32_t)dim, cosine, d_tau, s);
         launch_range_admit(R, (uint32_t)nb, d_qoff, ws.qsq.as<float>(), xsq_max, xsq_min_pos, i8_mu_norm, (uint32_t)dim, cosine, d_tau, s);
+        if (mask) launch_tau_clamp(d_tau, (uint32_t)nq_pad, s);
         {  // corpus passes of calls in flight on other workspaces take turns (flat_knn_enqueue)
             std::lock_guard<std::mutex> g(pass_mu);
             if (pass_ev_valid) VDB_HIP(hipStreamWaitEvent(s, pass_ev, 0));
         }
         prof_begin(ws, "flat_range_i8", double(ngroups) * double(n) * dim);
-        launch_flat_gemm8_filter(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, d_qscale, (uint32_t)ngroups, d_rowc_i8.as<float>(), d_tau, d_cand, d_hits,
+        launch_flat_gemm8_filter(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, d_qscale, (uint32_t)ngroups, rowc, d_tau, d_cand, d_hits,
                                  CAND_CAP, flat_gemm_debug, num_cu, s, CAND_CAP);
         prof_end(ws);
         {
@@ -1033,6 +1040,7 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
             prof_begin(ws, "flat_range_scan", double(n) * dim * elem_size());
             scan_rows(n, (uint32_t)dim, Q, nb, metric, d_sq.as<float>(), rqs.as<float>(), ws.dense.as<float>(), ld, n >= 4096, s);
             prof_end(ws);
+            if (mask) launch_mask_dense_nan(ws.dense.as<float>(), ld, n, nb, mask->d_bits.as<uint64_t>(), s);  // (a NaN distance is never inside)
             launch_range_scan_select(ws.dense.as<float>(), ld, n, R, nb, blk.as<uint32_t>(), p_cnt, s);
             VDB_SYNC(s);
             uint64_t add = 0, max_tot = 0, max_take = 0;
@@ -1081,6 +1089,225 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
     launch_range_gather(pool.as<uint64_t>(), meta.as<uint64_t>(), meta.as<uint64_t>() + nq, nq, max_take, id_offset, out.idx.as<uint64_t>(),
                         out.dist.as<float>(), s);
     VDB_SYNC(s);
+}
+
+// ---- Flat: exact filtered search over a row allow-list (k_filter.hip) ----------------------------------------------------------------
+// The first min(k, m) pairs of FlatIndex::knn over the m allowed rows of a RowMask, ascending by (distance, row id), distances bit-exact.
+//   direct path: strict-order scan of the GATHERED rows (column j of the dense matrix = row ids[j], ids ascending, so the order of
+//     (distance, column) IS the order of (distance, id)), the k-NN selections as they are, k_filter_finalize maps columns to rows.
+//     For m <= flat_filtered_direct_max, for shapes the 8-bit tier does not take, and for the queries that tier hands on.
+//   8-bit tier: the sequence of flat_knn_enqueue's 8-bit branch per chunk of 1024 queries, with the MASKED row constants in the sample and
+//     the filter launch (a disallowed row's key is +inf) and the thresholds clamped to FLT_MAX in between, so that no threshold admits such
+//     a key.  The hit list then holds allowed rows only and every allowed row outside it has key > tau: k_flat_tail_lb and its bound apply
+//     unchanged.  One attempt: no refinement, no second pass, no fp16 / split-bf16 tier; what is still open goes to the direct path.
+// Like the range search this call neither reads nor writes the k-NN tiers' auto-off counters (the tier's shape test is i8_applicable
+// without its clause about them).
+void Index::check_mask(const RowMask &mask) const {
+    if (mask.owner != this) throw Error(1, "mask: made for another index");
+    if (mask.gen != write_gen.load() || mask.n_rows != n)
+        throw Error(3, "mask: stale -- rows were added to or removed from the index after the mask was made; make a new one");
+}
+
+const float *Index::masked_rowc(Workspace &ws, const RowMask &mask) {
+    std::lock_guard<std::mutex> g(mask.mu);  // read-side calls are re-entrant: one of them builds, the others wait
+    if (mask.rowc_of == d_rowc_i8.p && mask.d_rowc.p) return mask.d_rowc.as<float>();
+    const uint64_t rows_pad = mirror_tiles(n) * 16;
+    mask.d_rowc.reserve(rows_pad * 2 * sizeof(float));
+    launch_mask_rowc(d_rowc_i8.as<float>(), mask.d_bits.as<uint64_t>(), n, rows_pad, mask.d_rowc.as<float>(), ws.stream);
+    VDB_SYNC(ws.stream);
+    mask.rowc_of = d_rowc_i8.p;
+    return mask.d_rowc.as<float>();
+}
+
+void Index::flat_masked_direct(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, const RowMask &mask, uint64_t *d_idx, float *d_dist,
+                               uint64_t *d_cnt) {
+    hipStream_t s = ws.stream;
+    const uint64_t m = mask.m;
+    if (nq == 0 || k == 0 || m == 0) return;
+    VDB_REQUIRE(k < (1ull << 31), "flat knn: k too large");
+    const int metric = dist == 0 ? MET_L2_DIRECT : MET_COSINE;
+    const uint64_t ksel = std::min<uint64_t>(k, m), ld = (m + 63) & ~63ull;
+    const uint32_t *ids = mask.d_ids.as<uint32_t>();
+    const bool use_lds = m >= 4096;
+    constexpr uint64_t BUDGET = 256ull << 20;  // bytes of the dense matrix (and of each key buffer) per chunk of queries
+    auto chunk_of = [&](uint64_t row_bytes) { return std::max<uint64_t>(8, std::min<uint64_t>(BUDGET / row_bytes, 32768) & ~7ull); };
+    ws.qsq.reserve(nq * sizeof(float));
+    launch_row_sqnorm(d_q, nq, (uint32_t)dim, ws.qsq.as<float>(), s);
+    if (ksel <= 1024) {
+        const uint32_t nl = topk_num_lists(m), cap = topk_capacity((uint32_t)ksel);
+        const uint64_t qch = std::min(nq, std::min(chunk_of(ld * sizeof(float)), chunk_of(uint64_t(nl) * cap * sizeof(uint64_t))));
+        ws.dense.reserve(qch * ld * sizeof(float));  // (before the loop: a later, larger reserve would free a buffer in use)
+        ws.lists.reserve(qch * nl * cap * sizeof(uint64_t));
+        ws.keys_c.reserve(qch * cap * sizeof(uint64_t));
+        for (uint64_t q0 = 0; q0 < nq; q0 += qch) {
+            const uint32_t nb = (uint32_t)std::min<uint64_t>(qch, nq - q0);
+            prof_begin(ws, "flat_filtered_scan", double((nb + 7) / 8) * double(m) * dim * sizeof(float));
+            launch_scan_gather(d_rows.as<float>(), ids, m, (uint32_t)dim, d_q + q0 * dim, nb, metric, d_sq.as<float>(), ws.qsq.as<float>() + q0,
+                               ws.dense.as<float>(), ld, use_lds, s);
+            prof_end(ws);
+            launch_topk_dense(ws.dense.as<float>(), ld, m, nb, (uint32_t)ksel, ws.lists.as<uint64_t>(), s);
+            launch_topk_merge(ws.lists.as<uint64_t>(), nl, cap, nb, (uint32_t)ksel, ws.keys_c.as<uint64_t>(), s);
+            launch_filter_finalize(ws.keys_c.as<uint64_t>(), cap, nb, (uint32_t)ksel, (uint32_t)k, ids, m, id_offset, d_idx + q0 * k, d_dist + q0 * k,
+                                   d_cnt + q0, s);
+        }
+        return;
+    }
+    // beyond the register-resident select: every (distance, column) pair of a query sorted, the first ksel kept
+    const uint64_t qch = std::min(nq, chunk_of(ld * sizeof(uint64_t)));
+    const size_t tb = sort_rows_temp_bytes(qch, ld);
+    ws.dense.reserve(qch * ld * sizeof(float));
+    ws.keys_a.reserve(qch * ld * sizeof(uint64_t));
+    ws.keys_b.reserve(qch * ld * sizeof(uint64_t));
+    ws.keys_c.reserve(qch * ksel * sizeof(uint64_t));
+    ws.lists.reserve(tb);
+    for (uint64_t q0 = 0; q0 < nq; q0 += qch) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(qch, nq - q0);
+        prof_begin(ws, "flat_filtered_scan", double((nb + 7) / 8) * double(m) * dim * sizeof(float));
+        launch_scan_gather(d_rows.as<float>(), ids, m, (uint32_t)dim, d_q + q0 * dim, nb, metric, d_sq.as<float>(), ws.qsq.as<float>() + q0,
+                           ws.dense.as<float>(), ld, use_lds, s);
+        prof_end(ws);
+        launch_pair_keys_rows(ws.dense.as<float>(), ld, m, nb, ws.keys_a.as<uint64_t>(), ld, s);
+        launch_sort_rows(ws.keys_a.as<uint64_t>(), ws.keys_b.as<uint64_t>(), nb, ld, ws.lists.p, tb, s);
+        launch_copy_prefix(ws.keys_b.as<uint64_t>(), ld, ws.keys_c.as<uint64_t>(), ksel, ksel, nb, s);
+        launch_filter_finalize(ws.keys_c.as<uint64_t>(), ksel, nb, (uint32_t)ksel, (uint32_t)k, ids, m, id_offset, d_idx + q0 * k, d_dist + q0 * k,
+                               d_cnt + q0, s);
+    }
+}
+
+void Index::flat_knn_masked_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, const RowMask &mask, uint64_t *d_idx, float *d_dist,
+                                   uint64_t *d_cnt) {
+    hipStream_t s = ws.stream;
+    check_mask(mask);
+    VDB_REQUIRE(!elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    filtered_queries += nq;
+    if (nq == 0) return;
+    const uint64_t m = mask.m;
+    const uint64_t ksel64 = std::min<uint64_t>(k, m);
+    VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
+    if (k > ksel64) {  // slots beyond min(k, m) are defined (zero) but not counted
+        VDB_HIP(hipMemsetAsync(d_idx, 0, nq * k * sizeof(uint64_t), s));
+        VDB_HIP(hipMemsetAsync(d_dist, 0, nq * k * sizeof(float), s));
+    }
+    if (ksel64 == 0) {  // k == 0, or nothing is allowed: empty results
+        filtered_direct_queries += nq;
+        VDB_SYNC(s);
+        return;
+    }
+    const bool tier = m > flat_filtered_direct_max && ksel64 <= 64 && flat_mode != 1 && (flat_mode == 2 || n >= 16384) && flat_gemm_mode != 1 &&
+                      i8_mirror_applicable() && flat_tail_lb_supported((uint32_t)dim, flat_i8_kprime, (uint32_t)ksel64) && ensure_i8(ws);
+    if (!tier) {
+        filtered_direct_queries += nq;
+        flat_masked_direct(ws, d_q, nq, k, mask, d_idx, d_dist, d_cnt);
+        VDB_SYNC(s);
+        return;
+    }
+    const float *rowc = masked_rowc(ws, mask);
+    constexpr uint32_t CAND_CAP = 8192;
+    constexpr uint64_t QCH = 1024;  // queries per round (8 groups of 128: 64 MB of hit lists)
+    const uint32_t ksel = (uint32_t)ksel64, kprime = flat_i8_kprime;
+    const int cosine = dist == 1 ? 1 : 0;
+    uint32_t s_step = 1, s_rank = 64;
+    mfma_sample_plan(n, 64u, &s_step, &s_rank, flat_i8_hits);  // (64 guaranteed hits, flat_i8_hits expected: flat_knn_enqueue)
+    const bool unit_min = flat_i8_unit_min != 1 && gemm8_sample_units(n, s_step) >= (flat_i8_unit_min == 2 ? 2ull : 16ull) * s_rank;
+    const uint64_t n_s = unit_min ? gemm8_sample_units(n, s_step) : gemm8_sample_rows(n, s_step);
+    const uint64_t ld_s = (n_s + 63) & ~63ull;
+    const uint32_t nl_s = topk_num_lists(n_s), cap_s = topk_capacity(s_rank);
+    std::vector<uint64_t> redo;  // queries the tier hands on
+    for (uint64_t q0 = 0; q0 < nq; q0 += QCH) {
+        const uint64_t nb = std::min<uint64_t>(QCH, nq - q0);
+        const uint64_t gq = gemm_group(), ngroups = (nb + gq - 1) / gq, nq_pad = ngroups * gq;
+        const float *Q = d_q + q0 * dim;
+        ws.qsq.reserve(nq_pad * sizeof(float));
+        ws.qfrag_g.reserve(nq_pad * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float));
+        ws.qaux.reserve(3 * nq_pad * sizeof(float));
+        ws.misc.reserve(nq_pad * (sizeof(float) + sizeof(uint32_t)) + 128 * sizeof(uint32_t));  // tau | hit counters | the sets' rendezvous words
+        ws.dense.reserve(nq_pad * ld_s * sizeof(float));
+        ws.lists.reserve(std::max<size_t>(nq_pad * size_t(nl_s) * cap_s, nq_pad * size_t(CAND_CAP)) * sizeof(uint64_t));
+        ws.keys_a.reserve(nq_pad * size_t(cap_s) * sizeof(uint64_t));
+        float *d_tau = ws.misc.as<float>(), *d_qscale = ws.qaux.as<float>(), *d_qoff = d_qscale + nq_pad;
+        uint32_t *d_hits = reinterpret_cast<uint32_t *>(d_tau + nq_pad);
+        launch_query_prep_i8(Q, (uint32_t)nb, (uint32_t)nq_pad, (uint32_t)dim, d_mu_i8.as<float>(), i8_l1, i8_l2, ws.qsq.as<float>(), d_qscale, d_qoff,
+                             d_hits, ws.qfrag_g.p, s, cosine);
+        // thresholds: the s_rank-th smallest sampled key among the ALLOWED rows (the others' keys are +inf) bounds the s_rank-th smallest
+        // key over all allowed rows
+        launch_flat_gemm8_sample(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, d_qscale, (uint32_t)ngroups, rowc, s_step, ws.dense.as<float>(), ld_s,
+                                 num_cu, s, unit_min ? 1 : 0);
+        if (n_s <= select_tau_max_n()) {
+            launch_select_tau(ws.dense.as<float>(), ld_s, (uint32_t)n_s, (uint32_t)nq_pad, (uint32_t)nb, s_rank, d_tau, s);
+        } else {
+            launch_topk_dense(ws.dense.as<float>(), ld_s, n_s, (uint32_t)nq_pad, s_rank, ws.lists.as<uint64_t>(), s);
+            launch_topk_merge(ws.lists.as<uint64_t>(), nl_s, cap_s, (uint32_t)nq_pad, s_rank, ws.keys_a.as<uint64_t>(), s);
+            launch_extract_tau(ws.keys_a.as<uint64_t>(), cap_s, (uint32_t)nq_pad, s_rank, d_tau, s);
+            if (nq_pad > nb)  // padding queries pass nothing (k_select_tau does it itself)
+                VDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_tau + nb), (int)0xFF800000u, nq_pad - nb, s));
+        }
+        // a sample with fewer than s_rank allowed rows selects +inf, which every masked row's key would pass: with tau = FLT_MAX the query
+        // collects every allowed row with a finite key instead -- certified if they fit the list, handed on if not
+        launch_tau_clamp(d_tau, (uint32_t)nq_pad, s);
+        uint64_t *d_cand = ws.lists.as<uint64_t>();  // the sample lists are dead now
+        {  // corpus passes of calls in flight on other workspaces take turns (flat_knn_enqueue)
+            std::lock_guard<std::mutex> g(pass_mu);
+            if (pass_ev_valid) VDB_HIP(hipStreamWaitEvent(s, pass_ev, 0));
+        }
+        prof_begin(ws, "flat_filtered_i8", double(ngroups) * double(n) * dim);
+        launch_flat_gemm8_filter(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, d_qscale, (uint32_t)ngroups, rowc, d_tau, d_cand, d_hits, CAND_CAP,
+                                 flat_gemm_debug, num_cu, s, std::max<uint32_t>(64u, s_step * s_rank));
+        prof_end(ws);
+        {
+            std::lock_guard<std::mutex> g(pass_mu);
+            if (!pass_ev) VDB_HIP(hipEventCreateWithFlags(&pass_ev, hipEventDisableTiming));
+            VDB_HIP(hipEventRecord(pass_ev, s));
+            pass_ev_valid = true;
+        }
+        FlatTailArgs t{};
+        t.cand = d_cand;
+        t.cap = CAND_CAP;
+        t.cnt = d_hits;
+        t.kprime = kprime;
+        t.ksel = ksel;
+        t.kstride = (uint32_t)k;
+        t.X = d_rows.as<float>();
+        t.dim = (uint32_t)dim;
+        t.Q = Q;
+        t.metric = cosine ? MET_COSINE : MET_L2_DIRECT;
+        t.xsq = d_sq.as<float>();
+        t.qsq = ws.qsq.as<float>();
+        t.n_rows = n;
+        t.xsq_max = xsq_max;
+        t.xsq_min_pos = xsq_min_pos;
+        t.cosine = cosine;
+        t.se.qoff = d_qoff;
+        t.se.mu_norm = i8_mu_norm;
+        t.id_offset = id_offset;
+        t.flags = static_cast<uint8_t *>(ws.pinned(nb));
+        t.out_idx = d_idx + q0 * k;
+        t.out_dist = d_dist + q0 * k;
+        t.out_count = d_cnt + q0;
+        t.tau = d_tau;
+        launch_flat_tail_lb(t, (uint32_t)nb, s);
+        VDB_SYNC(s);  // (the flags are in pinned host memory)
+        for (uint64_t q = 0; q < nb; q++)
+            if (t.flags[q] & 1u) redo.push_back(q0 + q);
+    }
+    filtered_i8_queries += nq;
+    filtered_fallback_queries += redo.size();
+    if (redo.empty()) return;
+    // the open queries over all m allowed rows on the direct path: gathered, answered, scattered back (as flat_knn_finish does)
+    const uint64_t nr = redo.size();
+    DevBuf rx, rq, ri, rd, rc;
+    rx.reserve(nr * sizeof(uint64_t));
+    rq.reserve(nr * dim * sizeof(float));
+    ri.reserve(nr * k * sizeof(uint64_t));
+    rd.reserve(nr * k * sizeof(float));
+    rc.reserve(nr * sizeof(uint64_t));
+    VDB_HIP(hipMemcpyAsync(rx.p, redo.data(), nr * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    launch_gather_rows_f32(d_q, rx.as<uint64_t>(), nr, (uint32_t)dim, rq.as<float>(), s);
+    VDB_HIP(hipMemsetAsync(ri.p, 0, nr * k * sizeof(uint64_t), s));
+    VDB_HIP(hipMemsetAsync(rd.p, 0, nr * k * sizeof(float), s));
+    VDB_HIP(hipMemsetAsync(rc.p, 0, nr * sizeof(uint64_t), s));
+    flat_masked_direct(ws, rq.as<float>(), nr, k, mask, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>());
+    launch_scatter_results(ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), rx.as<uint64_t>(), nr, (uint32_t)k, d_idx, d_dist, d_cnt, s);
+    VDB_SYNC(s);  // (`redo` and rx..rc go out of scope)
 }
 
 // ---- the approximate keys of the Flat shortlist pass, for every row ------------------------------------------------

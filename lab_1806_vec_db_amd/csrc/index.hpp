@@ -247,6 +247,21 @@ struct RowMirror {
 };
 
 struct Index;
+// A row allow-list of ONE index at ONE state of its rows (vdb_mask_create): the bit words, the ascending list of the allowed rows and, built
+// by the first call that runs the 8-bit tier under it, the masked copy of the index's {C_r, M_r} row constants (k_filter.hip).  Read-side
+// calls share a mask: everything but the lazily built copy is immutable after creation, and that copy is built under `mu`.
+struct RowMask {
+    const Index *owner = nullptr;
+    int device = 0;
+    uint64_t gen = 0;     // Index::write_gen when the mask was made: add_rows / swap_remove make it stale
+    uint64_t n_rows = 0;  // rows of the index then
+    uint64_t m = 0;       // allowed rows
+    DevBuf d_bits;        // u64 [ceil(n_rows / 64)], bits at and past n_rows clear
+    DevBuf d_ids;         // u32 [m], ascending
+    mutable std::mutex mu;
+    mutable DevBuf d_rowc;  // float2 [padded rows]: Index::d_rowc_i8 with {+inf, 0} for every disallowed row
+    mutable const void *rowc_of = nullptr;  // the d_rowc_i8 allocation it was copied from (nullptr: not built)
+};
 // IVFIndex (ivf_index.rs:34-47): centroids as a small Flat index of their own, clusters as CSR over row ids
 struct IVFState {
     bool present = false;
@@ -439,7 +454,22 @@ struct Index {
                            uint64_t k, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
     // Exact range search (k_range.hip): per query every row with D <= d_radius[q] (the first `limit` of them when limit > 0), ascending by
     // (distance, index); returns synchronised.  8-bit tier for the queries its bound admits, strict-order scan for the rest.
-    void flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit, RangeResult &out);
+    void flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit, RangeResult &out,
+                           const RowMask *mask = nullptr);
+    // (mask != nullptr: only the mask's allowed rows -- the filtered range search; nullptr: the unfiltered call, statement for statement)
+    // Exact filtered k-NN (k_filter.hip): the first min(k, m) pairs of FlatIndex::knn over the mask's allowed rows; returns synchronised.
+    // Direct path (gathered strict-order scan) for short allow-lists and wherever the 8-bit tier does not apply; otherwise the 8-bit
+    // filter pass with the masked row constants + the exact stage, its open queries redone by the direct path.  A sibling of
+    // flat_range_device: it neither reads nor writes the k-NN tiers' auto-off counters.
+    void flat_knn_masked_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, const RowMask &mask, uint64_t *d_idx, float *d_dist,
+                                uint64_t *d_cnt);
+    void flat_masked_direct(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, const RowMask &mask, uint64_t *d_idx, float *d_dist,
+                            uint64_t *d_cnt);  // enqueues; the caller synchronises
+    void check_mask(const RowMask &mask) const;  // throws: a mask of another index (invalid argument), a stale mask (state)
+    const float *masked_rowc(Workspace &ws, const RowMask &mask);  // after ensure_i8 succeeded; builds the copy on first use
+    std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove: what a RowMask is checked against
+    uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
+    std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};
     uint64_t range_max_results = 0;  // ceiling on the pairs of one call ("flat_range_max_results"; 0: what the device can hold)
     std::atomic<uint64_t> range_queries{0}, range_i8_queries{0}, range_scan_queries{0}, range_hits{0}, range_results{0};
     std::atomic<uint64_t> range_hits_max{0};  // longest hit list of a query the tier answered

@@ -285,6 +285,19 @@ void launch_range_append(const uint64_t *keys, uint64_t ld, const uint64_t *off,
 // out_idx / out_dist [lims[q], lims[q + 1]) = the pairs pool[off[q] ..) as (row + id_offset, distance)
 void launch_range_gather(const uint64_t *pool, const uint64_t *off, const uint64_t *lims, uint64_t nq, uint64_t max_take, uint64_t id_offset,
                          uint64_t *out_idx, float *out_dist, hipStream_t s);
+// k_filter.hip: filtered Flat search over a row allow-list (Index::flat_knn_masked_device, the mask of Index::flat_range_device)
+// dense exact distances out[q * ld + j] = D(row ids[j], query q), j < m, for any nq (8 queries per fetch of a row; ids ascending, u32)
+void launch_scan_gather(const float *X, const uint32_t *ids, uint64_t m, uint32_t dim, const float *Q, uint32_t nq, int metric, const float *xsq,
+                        const float *qsq, float *out, uint64_t ld, bool use_lds, hipStream_t s);
+// launch_finalize for pair keys whose low word is a COLUMN of that output: the id written is ids[column] + id_offset
+void launch_filter_finalize(const uint64_t *keys, uint64_t ldk, uint32_t nq, uint32_t ksel, uint32_t kstride, const uint32_t *ids, uint64_t m,
+                            uint64_t id_offset, uint64_t *out_idx, float *out_dist, uint64_t *out_count, hipStream_t s);
+// out[r] = bit r of `bits` set or r >= n ? rowc[r] : {+inf, 0}, r < rows_pad (the {C_r, M_r} pairs of the 8-bit pass)
+void launch_mask_rowc(const float *rowc, const uint64_t *bits, uint64_t n, uint64_t rows_pad, float *out, hipStream_t s);
+// tau[q] = min(tau[q], FLT_MAX), NaN -> -inf: no threshold lets the +inf key of a masked row through
+void launch_tau_clamp(float *tau, uint32_t nq, hipStream_t s);
+// dist[q * ld + i] = NaN for the rows i < n whose bit is clear
+void launch_mask_dense_nan(float *dist, uint64_t ld, uint64_t n, uint32_t nq, const uint64_t *bits, hipStream_t s);
 void mfma_set_sample_thin(int v);
 void mfma_sample_plan(uint64_t n, uint32_t kprime, uint32_t *step, uint32_t *rank, uint32_t target_floor = 1024);  // target_floor: expected hits per query
 uint64_t mfma_sample_rows(uint64_t n, uint32_t step);

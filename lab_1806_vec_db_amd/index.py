@@ -48,6 +48,57 @@ def read_range(lib, h, nq: int):
         lib.vdb_range_destroy(h)
 
 
+def pack_mask(allow, n: int) -> np.ndarray:
+    """The bit words of a row mask over n rows (vdb_mask_create): row i is allowed iff (words[i >> 6] >> (i & 63)) & 1.
+    `allow` is a bool array of length n, or an array of row ids (an id outside [0, n) raises).  Pure host code."""
+    n = int(n)
+    a = np.asarray(allow)
+    if a.dtype == np.bool_:
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"mask: a bool array of length {n} is needed, got shape {a.shape}")
+        flags = a
+    else:
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("mask: a bool array or an array of integer row ids is needed")
+        ids = a.reshape(-1).astype(np.int64)
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= n):
+            raise ValueError(f"mask: row id out of range for {n} rows")
+        flags = np.zeros(n, dtype=np.bool_)
+        flags[ids] = True
+    nw = (n + 63) // 64
+    padded = np.zeros(nw * 64, dtype=np.uint8)
+    padded[:n] = flags
+    return np.packbits(padded, bitorder="little").view(np.uint64).copy() if nw else np.zeros(0, dtype=np.uint64)
+
+
+class RowMask:
+    """An allow-list over the rows of one GpuIndex (vdb_mask): made by GpuIndex.make_mask, valid until rows are added to or removed
+    from the index, closed before the index is."""
+
+    def __init__(self, index: "GpuIndex", words: np.ndarray, n: int):
+        self._lib = index._lib
+        self._h = L.vp()
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        L.check(self._lib.vdb_mask_create(index._h, _ptr(w, L.u64p), int(n), C.byref(self._h)))
+        v = C.c_uint64()
+        L.check(self._lib.vdb_mask_count(self._h, C.byref(v)))
+        self._m = int(v.value)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.vdb_mask_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return self._m
+
+
 def calc_dist(a, b, dist="cosine", device: int = 0) -> float:
     """calc_dist (pyo3/mod.rs:43-48), evaluated on the GPU in reference order."""
     kind = parse_dist(dist)
@@ -198,10 +249,38 @@ class GpuIndex:
     def flat_knn(self, queries, k: int):
         return self._search(self._lib.vdb_flat_knn, queries, k)
 
+    def make_mask(self, allow) -> RowMask:
+        """a row mask for the filtered searches: `allow` is a bool array over the rows or an array of (local) row ids (pack_mask)"""
+        n = len(self)
+        return RowMask(self, pack_mask(allow, n), n)
+
+    def flat_knn_filtered(self, queries, k: int, mask: RowMask):
+        """Exact k-NN over the mask's allowed rows alone (vdb_flat_knn_filtered): the first min(k, len(mask)) pairs of flat_knn
+        restricted to them, distances bit-exact, ascending by (distance, id); same return shapes as flat_knn."""
+        q = _f32(queries)
+        single = q.ndim == 1
+        q = q.reshape(1, -1) if single else q
+        nq, dim = q.shape
+        kk = max(int(k), 1)
+        idx = np.zeros((nq, kk), dtype=np.uint64)
+        dist = np.zeros((nq, kk), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint64)
+        L.check(self._lib.vdb_flat_knn_filtered(self._h, _ptr(q, L.f32p), nq, dim, int(k), mask._h, _ptr(idx, L.u64p), _ptr(dist, L.f32p),
+                                                _ptr(cnt, L.u64p)))
+        if single:
+            c = int(cnt[0])
+            return idx[0, :c].copy(), dist[0, :c].copy()
+        return idx[:, :int(k)], dist[:, :int(k)], cnt
+
+    def flat_knn_filtered_device(self, q_ptr: int, nq: int, k: int, mask: RowMask, out_idx_ptr: int, out_dist_ptr: int, out_cnt_ptr: int,
+                                 stream: int = 0):
+        L.check(self._lib.vdb_flat_knn_filtered_device(self._h, L.vp(q_ptr), int(nq), self.dim, int(k), mask._h, L.vp(out_idx_ptr),
+                                                       L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
+
     def _range_out(self, h, nq: int):
         return read_range(self._lib, h, nq)
 
-    def range_search(self, queries, radius, limit: int | None = None):
+    def range_search(self, queries, radius, limit: int | None = None, mask: RowMask | None = None):
         """Exact Flat range search (vdb_flat_range): for every query ALL rows with distance <= its radius -- the distance
         FlatIndex::knn computes, boundary included -- ascending by (distance, index); with `limit` the first `limit` of them,
         i.e. search(k = limit, upper_bound = radius).  `radius`: one value, or one per query.
@@ -213,6 +292,10 @@ class GpuIndex:
         if limit is not None and int(limit) <= 0:
             raise ValueError("limit must be positive (None: no limit)")
         h = L.vp()
+        if mask is not None:  # only the mask's allowed rows (vdb_flat_range_filtered)
+            L.check(self._lib.vdb_flat_range_filtered(self._h, _ptr(q, L.f32p), nq, dim, _ptr(r, L.f32p), int(limit or 0), mask._h,
+                                                      C.byref(h)))
+            return self._range_out(h, nq)
         L.check(self._lib.vdb_flat_range(self._h, _ptr(q, L.f32p), nq, dim, _ptr(r, L.f32p), int(limit or 0), C.byref(h)))
         return self._range_out(h, nq)
 

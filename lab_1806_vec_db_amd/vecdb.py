@@ -14,7 +14,8 @@ Semantics reproduced from src/database/metadata_vec_table.rs:
   * search dispatch (:194-212): (ef, pq) -> knn_pq; (ef, no pq) -> knn_with_ef; else knn; then the
     `distance <= upper_bound` filter.
 
-Beyond the reference: search_within(key, query, upper_bound) returns the COMPLETE set inside the bound (exact Flat range search).
+Beyond the reference: search_within(key, query, upper_bound) returns the COMPLETE set inside the bound (exact Flat range search);
+search / search_within take `filter`, a metadata pattern matched as delete matches: only matching rows are searched, exactly.
 """
 from __future__ import annotations
 
@@ -24,7 +25,7 @@ from contextlib import contextmanager
 import numpy as np
 
 from ._lib import VdbError
-from .index import GpuIndex, parse_dist
+from .index import GpuIndex, RowMask, parse_dist
 
 _DIST_STR = {0: "l2sqr", 1: "cosine"}
 
@@ -78,6 +79,27 @@ class _Table:
         self.metadata: list[dict[str, str]] = []
         self.lock = _RwLock()
         self.seed = 0x1806
+        # row masks of the metadata patterns searched with (search(filter=...)), keyed by frozenset(pattern.items()): filled under
+        # mask_mu by searches (which hold the READ lock, several at a time), closed and cleared by every write under the WRITE lock
+        self.masks: dict[frozenset, RowMask] = {}
+        self.mask_mu = threading.Lock()
+
+    def mask_for(self, pattern: dict[str, str]) -> RowMask:
+        """the mask of the rows whose metadata holds every key of `pattern` with an equal value (an empty pattern: every row)"""
+        key = frozenset(pattern.items())
+        with self.mask_mu:
+            mk = self.masks.get(key)
+            if mk is None:
+                allow = np.fromiter((all(m.get(k) == v for k, v in pattern.items()) for m in self.metadata), dtype=np.bool_,
+                                    count=len(self.metadata))
+                mk = self.masks[key] = self.index.make_mask(allow)
+            return mk
+
+    def drop_masks(self):
+        with self.mask_mu:
+            for mk in self.masks.values():
+                mk.close()
+            self.masks.clear()
 
     def next_seed(self) -> int:
         self.seed = (self.seed * 6364136223846793005 + 1442695040888963407) & ((1 << 64) - 1)
@@ -123,6 +145,7 @@ class VecDB:
         if t is None:
             return False
         with t.lock.write():  # wait for searches still running on the table
+            t.drop_masks()
             t.index.close()
         return True
 
@@ -156,6 +179,7 @@ class VecDB:
         if len(metadata_list) != rows.shape[0]:
             raise RuntimeError("vec_list and metadata_list differ in length")
         with t.lock.write():
+            t.drop_masks()
             t.index.pq_clear()  # metadata_vec_table.rs:65,77
             t.metadata.extend(dict(m) for m in metadata_list)
             t.index.batch_add(rows)
@@ -163,6 +187,7 @@ class VecDB:
     def delete(self, key: str, pattern: dict[str, str]) -> int:
         t = self._t(key)
         with t.lock.write():
+            t.drop_masks()
             t.index.hnsw_clear()  # :170
             t.index.pq_clear()    # :171
             matches = [i for i, m in enumerate(t.metadata) if all(m.get(k) == v for k, v in pattern.items())]
@@ -225,11 +250,19 @@ class VecDB:
             return t.index.has_pq()
 
     # ---- reads ------------------------------------------------------------------------------------------------
-    def search(self, key: str, query, k: int, ef: int | None = None, upper_bound: float | None = None):
+    def search(self, key: str, query, k: int, ef: int | None = None, upper_bound: float | None = None,
+               filter: dict[str, str] | None = None):
+        """MetadataVecTable::search.  `filter`: a metadata pattern matched exactly as delete matches (every key present with an equal
+        value; an empty pattern matches every row) -- only matching rows are searched.  With a filter the answer is always EXACT, from
+        the table's Flat rows, whatever indexes the table has, and `ef` is ignored."""
         t = self._t(key)
         ix = t.index
         q = np.asarray(query, dtype=np.float32).ravel()
         with t.lock.read():  # database/mod.rs:255: read guard for the whole search, metadata lookup included
+            if filter is not None:
+                idx, dist = ix.flat_knn_filtered(q, k, t.mask_for(filter))
+                ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
+                return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist) if d <= ub]
             if ef is not None and ix.has_pq():
                 idx, dist = ix.knn_pq(q, k, ef)
             elif ef is not None:
@@ -239,13 +272,17 @@ class VecDB:
             ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
             return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist) if d <= ub]
 
-    def search_within(self, key: str, query, upper_bound: float, limit: int | None = None):
+    def search_within(self, key: str, query, upper_bound: float, limit: int | None = None, filter: dict[str, str] | None = None):
         """Every row within `upper_bound` of the query (distance <= upper_bound, as search's filter compares), nearest first: what
         search(k, upper_bound=...) returns once k covers the whole set, without having to guess k.  Always answered exactly from the
-        table's rows (FlatIndex::knn distances), whatever indexes the table has.  `limit`: at most that many, the nearest ones."""
+        table's rows (FlatIndex::knn distances), whatever indexes the table has.  `limit`: at most that many, the nearest ones.
+        `filter`: a metadata pattern as in search -- only matching rows are returned."""
         t = self._t(key)
         q = np.asarray(query, dtype=np.float32).ravel()
         with t.lock.read():
+            if filter is not None:
+                _, idx, dist = t.index.range_search(q, np.float32(upper_bound), limit, mask=t.mask_for(filter))
+                return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist)]
             _, idx, dist = t.index.range_search(q, np.float32(upper_bound), limit)
             return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist)]
 
