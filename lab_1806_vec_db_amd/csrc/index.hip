@@ -521,6 +521,142 @@ void Index::flat_small_device(Workspace &ws, const float *q, uint64_t nq, uint64
     prof_end(ws);
 }
 
+// ---- Flat: the pieces of a filter pass that k-NN, range search, filtered search and flat_debug_keys share ------------------------------
+constexpr uint64_t QCH = 1024;  // queries per round of the range / filtered 8-bit tiers (8 groups of 128: 64 MB of hit lists; range: 64 MB of exact keys)
+
+// Calls in flight on other workspaces (re-entrant readers, vdb_flat_knn_device_begin): their corpus passes take turns.
+// Each pass wants every CU (one persistent workgroup per CU); two of them resident at once only wait for each other's
+// workgroups, and their HIP-event durations would measure that wait.  The small kernels around the passes still overlap.
+template <class F>
+void Index::corpus_pass(Workspace &ws, const char *name, double bytes, F launch) {
+    {
+        std::lock_guard<std::mutex> g(pass_mu);
+        if (pass_ev_valid) VDB_HIP(hipStreamWaitEvent(ws.stream, pass_ev, 0));
+    }
+    prof_begin(ws, name, bytes);
+    launch();
+    prof_end(ws);
+    std::lock_guard<std::mutex> g(pass_mu);
+    if (!pass_ev) VDB_HIP(hipEventCreateWithFlags(&pass_ev, hipEventDisableTiming));
+    VDB_HIP(hipEventRecord(pass_ev, ws.stream));
+    pass_ev_valid = true;
+}
+
+// The query side of an 8-bit pass over the nb queries at Q.  What k_query_prep_i8 and k_flat_gemm8 ask of these buffers: ws.misc holds
+// tau | hit counters | rendezvous words in ONE allocation -- the prep kernel zeroes the nq_pad counters and the 128 words behind them, which
+// the filter's cooperative sets meet on; qsq is written for q < nb only; the padding queries [nb, nq_pad) get a zero image and scale 0 (their
+// tau = -inf comes from the threshold step).  Sizes are the largest any caller ever asked for (reserve never shrinks).
+I8Queries Index::i8_query_prep(Workspace &ws, const float *Q, uint64_t nb) {
+    I8Queries qp;
+    const uint64_t gq = gemm_group();
+    qp.ngroups = (nb + gq - 1) / gq;
+    qp.nq_pad = qp.ngroups * gq;
+    const size_t sync_words = std::max<size_t>(128, mfma_sync_words(uint32_t(qp.nq_pad / mfma_batch((uint32_t)dim)), num_cu));
+    ws.qsq.reserve(qp.nq_pad * sizeof(float));
+    ws.qfrag_g.reserve(qp.nq_pad * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float));
+    ws.qaux.reserve(3 * qp.nq_pad * sizeof(float));
+    ws.misc.reserve(qp.nq_pad * (sizeof(float) + sizeof(uint32_t)) + sync_words * sizeof(uint32_t));
+    qp.d_tau = ws.misc.as<float>();
+    qp.d_hits = reinterpret_cast<uint32_t *>(qp.d_tau + qp.nq_pad);
+    qp.d_qscale = ws.qaux.as<float>();
+    qp.d_qoff = qp.d_qscale + qp.nq_pad;
+    launch_query_prep_i8(Q, (uint32_t)nb, (uint32_t)qp.nq_pad, (uint32_t)dim, d_mu_i8.as<float>(), i8_l1, i8_l2, ws.qsq.as<float>(), qp.d_qscale,
+                         qp.d_qoff, qp.d_hits, ws.qfrag_g.p, ws.stream, dist == 1 ? 1 : 0);
+    return qp;
+}
+
+// The threshold sample of the 8-bit pass: planned for 64 guaranteed hits, flat_i8_hits (~1000) expected -- the exact stage takes tau itself
+// as the bound of everything outside the hit list, so a list shorter than flat_i8_kprime is no failure.  With many sampled units the sample
+// kernel hands the selection ONE value per (query, unit), the unit's smallest key: 48 x fewer values to write and select from (1M rows:
+// 31 MB -> 0.65 MB per 1000 queries; k_gemm8.hip).
+TauSample Index::i8_sample_plan() const {
+    TauSample sp;
+    sp.s_rank = 64;
+    mfma_sample_plan(n, 64u, &sp.s_step, &sp.s_rank, flat_i8_hits);
+    const uint64_t units = gemm8_sample_units(n, sp.s_step);
+    sp.unit_min = flat_i8_unit_min != 1 && units >= (flat_i8_unit_min == 2 ? 2ull : 16ull) * sp.s_rank;  // (2: tests force it on short samples)
+    sp.set_keys(sp.unit_min ? units : gemm8_sample_rows(n, sp.s_step));
+    return sp;
+}
+
+void Index::i8_sample(Workspace &ws, const I8Queries &qp, const float *rowc, const TauSample &sp) {
+    launch_flat_gemm8_sample(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, qp.d_qscale, (uint32_t)qp.ngroups, rowc, sp.s_step, ws.dense.as<float>(),
+                             sp.ld_s, num_cu, ws.stream, sp.unit_min ? 1 : 0);
+}
+
+// tau[q] = the s_rank-th smallest of the sample keys in ws.dense (scratch beyond select_tau_max_n() keys: ws.lists, ws.keys_a)
+void Index::select_tau(Workspace &ws, const TauSample &sp, uint64_t nq_pad, uint64_t nq, float *d_tau) {
+    hipStream_t s = ws.stream;
+    if (sp.n_s <= select_tau_max_n()) {  // tau only needs the s_rank-th smallest sampled key, not a sorted sample shortlist
+        launch_select_tau(ws.dense.as<float>(), sp.ld_s, (uint32_t)sp.n_s, (uint32_t)nq_pad, (uint32_t)nq, sp.s_rank, d_tau, s);
+        return;
+    }
+    // (lists of topk_capacity(s_rank) slots -- NOT of k' slots: a thinned sample's rank is below k', and so is the 8-bit pass's)
+    launch_topk_dense(ws.dense.as<float>(), sp.ld_s, sp.n_s, (uint32_t)nq_pad, sp.s_rank, ws.lists.as<uint64_t>(), s);
+    launch_topk_merge(ws.lists.as<uint64_t>(), sp.nl_s, sp.cap_s, (uint32_t)nq_pad, sp.s_rank, ws.keys_a.as<uint64_t>(), s);
+    launch_extract_tau(ws.keys_a.as<uint64_t>(), sp.cap_s, (uint32_t)nq_pad, sp.s_rank, d_tau, s);
+    // padding queries are zero vectors: under Cosine every row ties at key 0 = tau and would flood the hit buffers of
+    // the real queries that share their workgroup batch; tau = -inf lets nothing through  (k_select_tau does it itself)
+    if (nq_pad > nq) VDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_tau + nq), (int)0xFF800000u, nq_pad - nq, s));
+}
+
+// one corpus pass of k_flat_gemm8 per 128 queries: hits (key <= tau, keys by `rowc`) -> ws.lists, FLAT_CAND_CAP slots per query
+// (hits_expected per query sizes the hand-over blocks)
+void Index::i8_filter(Workspace &ws, const I8Queries &qp, const float *rowc, const char *name, uint32_t hits_expected) {
+    corpus_pass(ws, name, double(qp.ngroups) * double(n) * dim, [&] {
+        launch_flat_gemm8_filter(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, qp.d_qscale, (uint32_t)qp.ngroups, rowc, qp.d_tau, ws.lists.as<uint64_t>(),
+                                 qp.d_hits, FLAT_CAND_CAP, flat_gemm_debug, num_cu, ws.stream, hits_expected);
+    });
+}
+
+// the exact stage's arguments that come from the index and the filter pass (hit lists in ws.lists); Q, the outputs, kprime / ksel / kstride,
+// flags and qstat are the caller's
+FlatTailArgs Index::flat_tail_args(const Workspace &ws, const uint32_t *d_hits, const float *d_tau, const SplitErr &se) const {
+    FlatTailArgs t{};
+    t.cand = ws.lists.as<uint64_t>();
+    t.cap = FLAT_CAND_CAP;
+    t.cnt = d_hits;
+    t.X = d_rows.as<float>();
+    t.dim = (uint32_t)dim;
+    t.cosine = dist == 1 ? 1 : 0;
+    t.metric = t.cosine ? MET_COSINE : MET_L2_DIRECT;
+    t.xsq = d_sq.as<float>();
+    t.qsq = ws.qsq.as<float>();
+    t.n_rows = n;
+    t.xsq_max = xsq_max;
+    t.xsq_min_pos = xsq_min_pos;
+    t.se = se;
+    t.id_offset = id_offset;
+    t.tau = d_tau;
+    return t;
+}
+
+bool Index::i8_side_tier(Workspace &ws) {
+    return flat_mode != 1 && (flat_mode == 2 || n >= 16384) && flat_gemm_mode != 1 && i8_mirror_applicable() && ensure_i8(ws);
+}
+
+// Queries a tier leaves open: gathered into buffers of their own, answered elsewhere into ri / rd / rc, scattered back.  Rare: allocated on
+// demand.  `rows` is pageable host memory: the caller keeps it alive until a stream sync after the constructor.
+struct RedoSet {
+    const uint64_t nr, k;
+    DevBuf rx, rq, ri, rd, rc;
+    RedoSet(const std::vector<uint64_t> &rows, const float *d_q, uint64_t dim, uint64_t k_, hipStream_t s) : nr(rows.size()), k(k_) {
+        rx.reserve(nr * sizeof(uint64_t));
+        rq.reserve(nr * dim * sizeof(float));
+        ri.reserve(nr * k * sizeof(uint64_t));
+        rd.reserve(nr * k * sizeof(float));
+        rc.reserve(nr * sizeof(uint64_t));
+        VDB_HIP(hipMemcpyAsync(rx.p, rows.data(), nr * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        launch_gather_rows_f32(d_q, rx.as<uint64_t>(), nr, (uint32_t)dim, rq.as<float>(), s);
+        VDB_HIP(hipMemsetAsync(ri.p, 0, nr * k * sizeof(uint64_t), s));
+        VDB_HIP(hipMemsetAsync(rd.p, 0, nr * k * sizeof(float), s));
+    }
+    void scatter(uint64_t *d_idx, float *d_dist, uint64_t *d_cnt, hipStream_t s) {
+        launch_scatter_results(ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), rx.as<uint64_t>(), nr, (uint32_t)k, d_idx, d_dist, d_cnt, s);
+        VDB_SYNC(s);  // (the buffers are freed with the set)
+    }
+};
+
 // ---- Flat: full pipeline ---------------------------------------------------------------------------
 uint64_t Index::flat_knn_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t *d_idx,
                                 float *d_dist, uint64_t *d_cnt, bool allow_half, uint32_t kprime_min, bool allow_i8, const float *d_dk_hint) {
@@ -597,9 +733,8 @@ void Index::flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint6
     const bool gemm = i8 || flat_gemm_mode == 2 || (flat_gemm_mode == 0 && (nq > 64 || half_ok));
     const bool half = !i8 && half_ok && gemm;
     if (half) kprime = kprime_h;
-    constexpr uint32_t CAND_CAP = 8192;
     const bool i8_second = i8 && d_dk_hint != nullptr;
-    if (i8) kprime = i8_second ? CAND_CAP : flat_i8_kprime;  // (second attempt: the exact stage may walk the whole candidate list)
+    if (i8) kprime = i8_second ? FLAT_CAND_CAP : flat_i8_kprime;  // (second attempt: the exact stage may walk the whole candidate list)
     if (!half && !i8) launch_row_sqnorm(d_q, nq, (uint32_t)dim, ws.qsq.as<float>(), s);  // (the fp16 / 8-bit passes: k_query_prep_*)
     if (!half && !i8 && !ensure_tiled(ws)) {  // no mirror at all: the strict-order scan over the rows themselves
         flat_exact_device(ws, d_q, ws.qsq.as<float>(), nq, ksel, k, d_idx, d_dist, d_cnt);
@@ -611,42 +746,41 @@ void Index::flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint6
     const uint64_t ngroups = gemm ? (nq + gq - 1) / gq : 0;
     const uint64_t nq_pad = gemm ? ngroups * gq : (nq + bq - 1) / bq * bq;
     const uint64_t nbatch = nq_pad / bq;
-    uint32_t s_step = 1, s_rank = kprime;  // threshold sample: every s_step-th item, tau = s_rank-th smallest sampled key
-    // (8-bit pass: planned for 64 guaranteed hits, ~1000 expected -- its exact stage takes tau itself as the bound of everything
-    // outside the hit list, so a list shorter than flat_i8_kprime is no failure)
-    mfma_sample_plan(n, i8 ? 64u : kprime, &s_step, &s_rank, i8 ? flat_i8_hits : 1024u);
-    // 8-bit pass with many sampled units: the sample kernel hands the selection ONE value per (query, unit), the unit's smallest key --
-    // 48 x fewer values to write and select from (1M rows: 31 MB -> 0.65 MB per 1000 queries); k_gemm8.hip, launch_flat_gemm8_sample
-    const bool unit_min = i8 && flat_i8_unit_min != 1 && gemm8_sample_units(n, s_step) >= (flat_i8_unit_min == 2 ? 2ull : 16ull) * s_rank;  // (2: tests force it on short samples)
-    const uint64_t n_s = i8 ? (unit_min ? gemm8_sample_units(n, s_step) : gemm8_sample_rows(n, s_step))
-                            : (gemm ? gemm_sample_rows(n, s_step) : mfma_sample_rows(n, s_step));
-    const uint64_t ld_s = (n_s + 63) & ~63ull;
-    const uint32_t nl_s = topk_num_lists(n_s);
+    // threshold sample: every s_step-th item, tau = s_rank-th smallest sampled key
+    TauSample sp;
+    if (i8) {
+        sp = i8_sample_plan();
+    } else {
+        sp.s_rank = kprime;
+        mfma_sample_plan(n, kprime, &sp.s_step, &sp.s_rank);
+        sp.set_keys(gemm ? gemm_sample_rows(n, sp.s_step) : mfma_sample_rows(n, sp.s_step));
+    }
     const size_t qf = mfma_qfrag_floats((uint32_t)dim);
     ws.qfrag.reserve(nbatch * qf * sizeof(float));
-    ws.dense.reserve(nq_pad * ld_s * sizeof(float));
-    ws.lists.reserve(std::max<size_t>(nq_pad * nl_s * capp, nq_pad * size_t(CAND_CAP)) * sizeof(uint64_t));
+    ws.dense.reserve(nq_pad * sp.ld_s * sizeof(float));
+    ws.lists.reserve(std::max<size_t>(nq_pad * sp.nl_s * capp, nq_pad * size_t(FLAT_CAND_CAP)) * sizeof(uint64_t));
     ws.keys_a.reserve(nq_pad * capp * sizeof(uint64_t));  // approximate shortlist, sorted
     ws.keys_b.reserve(nq_pad * capp * sizeof(uint64_t));  // exact keys of the shortlist, unsorted
     ws.keys_c.reserve(nq_pad * capk * sizeof(uint64_t));  // exact top-k, sorted
     const size_t sync_words = mfma_sync_words((uint32_t)nbatch, num_cu);
-    ws.misc.reserve(nq_pad * (sizeof(float) + sizeof(uint32_t)) + sync_words * sizeof(uint32_t));  // tau | hit counters | rendezvous
-    float *d_tau = ws.misc.as<float>();
-    uint32_t *d_hits = reinterpret_cast<uint32_t *>(d_tau + nq_pad);
+    I8Queries qp;  // (of the 8-bit pass; the other passes fill in the thresholds and counters they share with it)
+    if (i8) {
+        qp = i8_query_prep(ws, d_q, nq);
+    } else {
+        ws.misc.reserve(nq_pad * (sizeof(float) + sizeof(uint32_t)) + sync_words * sizeof(uint32_t));  // tau | hit counters | rendezvous
+        qp.d_tau = ws.misc.as<float>();
+        qp.d_hits = reinterpret_cast<uint32_t *>(qp.d_tau + nq_pad);
+    }
+    float *const d_tau = qp.d_tau;
+    uint32_t *const d_hits = qp.d_hits;
     if (!gemm) launch_mfma_pack_queries(d_q, (uint32_t)nq, (uint32_t)nq_pad, (uint32_t)dim, ws.qfrag.as<float>(), s);
     const float *xt = half ? d_tiled_h.as<float>() : d_tiled.as<float>();
-    float *d_qscale = nullptr, *d_qmul = nullptr, *d_qerr = nullptr, *d_qoff = nullptr;
-    if (gemm) {
+    float *d_qmul = nullptr, *d_qerr = nullptr;
+    if (gemm && !i8) {
         ws.qfrag_g.reserve(nq_pad * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float));
-        if (i8) {
+        if (half) {
             ws.qaux.reserve(3 * nq_pad * sizeof(float));
-            d_qscale = ws.qaux.as<float>();
-            d_qoff = d_qscale + nq_pad;
-            launch_query_prep_i8(d_q, (uint32_t)nq, (uint32_t)nq_pad, (uint32_t)dim, d_mu_i8.as<float>(), i8_l1, i8_l2, ws.qsq.as<float>(),
-                                 d_qscale, d_qoff, d_hits, ws.qfrag_g.p, s, cosine);
-        } else if (half) {
-            ws.qaux.reserve(3 * nq_pad * sizeof(float));
-            d_qscale = ws.qaux.as<float>();
+            float *d_qscale = ws.qaux.as<float>();
             d_qmul = d_qscale + nq_pad;
             d_qerr = d_qmul + nq_pad;
             launch_query_prep_h(d_q, (uint32_t)nq, (uint32_t)nq_pad, (uint32_t)dim, half_sx(), ws.qsq.as<float>(), d_qscale, d_qmul,
@@ -657,63 +791,36 @@ void Index::flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint6
     }
     if (i8_second) {
         // thresholds from the k-th exact distances the first walk left behind (k_redo.hip): no sample, no selection
-        launch_i8_tau_from_dk(d_dk_hint, (uint32_t)nq, (uint32_t)nq_pad, d_qoff, ws.qsq.as<float>(), xsq_max, i8_mu_norm, (uint32_t)dim, cosine,
+        launch_i8_tau_from_dk(d_dk_hint, (uint32_t)nq, (uint32_t)nq_pad, qp.d_qoff, ws.qsq.as<float>(), xsq_max, i8_mu_norm, (uint32_t)dim, cosine,
                               d_tau, s);
     } else {
         if (i8)
-            launch_flat_gemm8_sample(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, d_qscale, (uint32_t)ngroups, d_rowc_i8.as<float>(), s_step,
-                                     ws.dense.as<float>(), ld_s, num_cu, s, unit_min ? 1 : 0);
+            i8_sample(ws, qp, d_rowc_i8.as<float>(), sp);
         else if (gemm)  // the sample through the 128-query kernel too: same arithmetic as the filter, 4x fewer re-reads of the sample
             launch_flat_gemm_sample(xt, n, (uint32_t)dim, ws.qfrag_g.as<float>(), d_qmul, (uint32_t)ngroups,
-                                    d_sq.as<float>(), cosine, s_step, ws.dense.as<float>(), ld_s, num_cu, s);
+                                    d_sq.as<float>(), cosine, sp.s_step, ws.dense.as<float>(), sp.ld_s, num_cu, s);
         else
             launch_flat_mfma_sample(d_tiled.as<float>(), n, (uint32_t)dim, ws.qfrag.as<float>(), (uint32_t)nbatch,
-                                    d_sq.as<float>(), cosine, s_step, ws.dense.as<float>(), ld_s, num_cu, s);
-        if (n_s <= select_tau_max_n()) {  // tau only needs the k'-th smallest sampled key, not a sorted sample shortlist
-            launch_select_tau(ws.dense.as<float>(), ld_s, (uint32_t)n_s, (uint32_t)nq_pad, (uint32_t)nq, s_rank, d_tau, s);
-        } else {
-            // (lists of topk_capacity(s_rank) slots -- NOT of k' slots: a thinned sample's rank is below k', and so is the 8-bit pass's)
-            const uint32_t cap_s = topk_capacity(s_rank);
-            launch_topk_dense(ws.dense.as<float>(), ld_s, n_s, (uint32_t)nq_pad, s_rank, ws.lists.as<uint64_t>(), s);
-            launch_topk_merge(ws.lists.as<uint64_t>(), nl_s, cap_s, (uint32_t)nq_pad, s_rank, ws.keys_a.as<uint64_t>(), s);
-            launch_extract_tau(ws.keys_a.as<uint64_t>(), cap_s, (uint32_t)nq_pad, s_rank, d_tau, s);
-        }
-        // padding queries are zero vectors: under Cosine every row ties at key 0 = tau and would flood the hit buffers of
-        // the real queries that share their workgroup batch; tau = -inf lets nothing through
-        if (nq_pad > nq && n_s > select_tau_max_n())  // (k_select_tau does it itself)
-            VDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_tau + nq), (int)0xFF800000u, nq_pad - nq, s));
+                                    d_sq.as<float>(), cosine, sp.s_step, ws.dense.as<float>(), sp.ld_s, num_cu, s);
+        select_tau(ws, sp, nq_pad, nq, d_tau);
     }
     uint64_t *d_cand = ws.lists.as<uint64_t>();  // the sample lists are dead now
-    uint32_t *d_sync = d_hits + nq_pad;
-    if (!half && !i8) VDB_HIP(hipMemsetAsync(d_hits, 0, (nq_pad + sync_words) * sizeof(uint32_t), s));  // (k_query_prep_* zero the counters)
-    // algorithmic bytes: one corpus pass (N*d*4) serves 32*share queries (bytes/query = N*d*4 / B)
-    // (the fp16 pass streams N*d*2 bytes per 128 queries: its own counter, so that GB/s are the bytes really read)
-    const uint64_t hbm_passes = gemm ? ngroups : (nbatch + mfma_share() - 1) / mfma_share();
-    // Calls in flight on other workspaces (re-entrant readers, vdb_flat_knn_device_begin): their corpus passes take turns.
-    // Each pass wants every CU (one persistent workgroup per CU); two of them resident at once only wait for each other's
-    // workgroups, and their HIP-event durations would measure that wait.  The small kernels around the passes still overlap.
-    {
-        std::lock_guard<std::mutex> g(pass_mu);
-        if (pass_ev_valid) VDB_HIP(hipStreamWaitEvent(s, pass_ev, 0));
-    }
-    prof_begin(ws, i8 ? "flat_i8" : (half ? "flat_half" : "flat_mfma"),
-               double(hbm_passes) * double(n) * dim * (i8 ? 1 : (half ? sizeof(uint16_t) : sizeof(float))));
-    if (i8)
-        launch_flat_gemm8_filter(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, d_qscale, (uint32_t)ngroups, d_rowc_i8.as<float>(), d_tau,
-                                 d_cand, d_hits, CAND_CAP, flat_gemm_debug, num_cu, s,
-                                 i8_second ? CAND_CAP : std::max<uint32_t>(64u, s_step * s_rank));  // (expected hits per query: sizes the hand-over blocks)
-    else if (gemm)
-        launch_flat_gemm_filter(xt, n, (uint32_t)dim, ws.qfrag_g.as<float>(), d_qmul, (uint32_t)ngroups,
-                                d_sq.as<float>(), cosine, d_tau, d_cand, d_hits, CAND_CAP, flat_gemm_debug, num_cu, s);
-    else
-        launch_flat_mfma_filter(d_tiled.as<float>(), n, (uint32_t)dim, ws.qfrag.as<float>(), (uint32_t)nbatch,
-                                d_sq.as<float>(), cosine, d_tau, d_cand, d_hits, CAND_CAP, d_sync, num_cu, s);
-    prof_end(ws);
-    {
-        std::lock_guard<std::mutex> g(pass_mu);
-        if (!pass_ev) VDB_HIP(hipEventCreateWithFlags(&pass_ev, hipEventDisableTiming));
-        VDB_HIP(hipEventRecord(pass_ev, s));
-        pass_ev_valid = true;
+    if (i8) {
+        // (expected hits per query: sizes the hand-over blocks)
+        i8_filter(ws, qp, d_rowc_i8.as<float>(), "flat_i8", i8_second ? FLAT_CAND_CAP : std::max<uint32_t>(64u, sp.s_step * sp.s_rank));
+    } else {
+        if (!half) VDB_HIP(hipMemsetAsync(d_hits, 0, (nq_pad + sync_words) * sizeof(uint32_t), s));  // (k_query_prep_h zeroes the counters)
+        // algorithmic bytes: one corpus pass (N*d*4) serves 32*share queries (bytes/query = N*d*4 / B)
+        // (the fp16 pass streams N*d*2 bytes per 128 queries: its own counter, so that GB/s are the bytes really read)
+        const uint64_t hbm_passes = gemm ? ngroups : (nbatch + mfma_share() - 1) / mfma_share();
+        corpus_pass(ws, half ? "flat_half" : "flat_mfma", double(hbm_passes) * double(n) * dim * (half ? sizeof(uint16_t) : sizeof(float)), [&] {
+            if (gemm)
+                launch_flat_gemm_filter(xt, n, (uint32_t)dim, ws.qfrag_g.as<float>(), d_qmul, (uint32_t)ngroups,
+                                        d_sq.as<float>(), cosine, d_tau, d_cand, d_hits, FLAT_CAND_CAP, flat_gemm_debug, num_cu, s);
+            else
+                launch_flat_mfma_filter(d_tiled.as<float>(), n, (uint32_t)dim, ws.qfrag.as<float>(), (uint32_t)nbatch,
+                                        d_sq.as<float>(), cosine, d_tau, d_cand, d_hits, FLAT_CAND_CAP, d_hits + nq_pad, num_cu, s);
+        });
     }
     SplitErr se;
     if (half) {
@@ -722,29 +829,15 @@ void Index::flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint6
         se.dx_rel = half_dx_rel;
     }
     if (i8) {
-        se.qoff = d_qoff;
+        se.qoff = qp.d_qoff;
         se.mu_norm = i8_mu_norm;
     }
     if (i8 || (flat_tail_mode != 1 && !elem_u8 && flat_tail64_supported((uint32_t)dim, kprime, ksel))) {
-        FlatTailArgs t{};
-        t.cand = d_cand;
-        t.cap = CAND_CAP;
-        t.cnt = d_hits;
+        FlatTailArgs t = flat_tail_args(ws, d_hits, d_tau, se);
         t.kprime = kprime;
         t.ksel = ksel;
         t.kstride = (uint32_t)k;
-        t.X = d_rows.as<float>();
-        t.dim = (uint32_t)dim;
         t.Q = d_q;
-        t.metric = cosine ? MET_COSINE : MET_L2_DIRECT;
-        t.xsq = d_sq.as<float>();
-        t.qsq = ws.qsq.as<float>();
-        t.n_rows = n;
-        t.xsq_max = xsq_max;
-        t.xsq_min_pos = xsq_min_pos;
-        t.cosine = cosine;
-        t.se = se;
-        t.id_offset = id_offset;
         // long walks (tight clusters): the keys of the hits are tightened from the row-major fp16 image first (k_redo.hip).  (Building the image
         // leaves the pinned block alone, and the flags block taken below stays valid until this workspace's next, larger pinned() call.)
         bool refine = false;
@@ -762,28 +855,27 @@ void Index::flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint6
         p.refined = refine;
         if (refine) {
             launch_flat_refine_half(d_rows_h.as<uint16_t>(), (uint32_t)dim, half_sx(), half_dx_abs, half_dx_rel, cosine, d_q, d_sq.as<float>(),
-                                    ws.qsq.as<float>(), d_qoff, d_cand, CAND_CAP, d_hits, (uint32_t)nq, CAND_CAP, s);  // (a list holds up to CAND_CAP hits; the walk selects among all of them)
+                                    ws.qsq.as<float>(), qp.d_qoff, d_cand, FLAT_CAND_CAP, d_hits, (uint32_t)nq, FLAT_CAND_CAP, s);  // (a list holds up to FLAT_CAND_CAP hits; the walk selects among all of them)
             i8_refine_queries += nq;
         }
         t.out_idx = d_idx;
         t.out_dist = d_dist;
         t.out_count = d_cnt;
-        t.tau = d_tau;
         if (i8 && i8_second && nq <= 96 && flat_i8_full != 1) {
             // a handful of queries on their second attempt: all their candidates at once instead of a chain of 63-row rounds (k_exact.hip)
-            ws.keys_b.reserve(nq * size_t(CAND_CAP) * sizeof(uint64_t));
+            ws.keys_b.reserve(nq * size_t(FLAT_CAND_CAP) * sizeof(uint64_t));
             launch_flat_full_lb(t, (uint32_t)nq, ws.keys_b.as<uint64_t>(), ws.keys_c.as<uint64_t>(), s);
         } else if (i8)
             launch_flat_tail_lb(t, (uint32_t)nq, s);
         else
             launch_flat_tail64(t, (uint32_t)nq, s);
     } else {
-        launch_topk_merge_counted(d_cand, CAND_CAP, d_hits, (uint32_t)nq, kprime, ws.keys_a.as<uint64_t>(), s);
+        launch_topk_merge_counted(d_cand, FLAT_CAND_CAP, d_hits, (uint32_t)nq, kprime, ws.keys_a.as<uint64_t>(), s);
         rerank_rows((uint32_t)dim, d_q, (uint32_t)nq, cosine ? MET_COSINE : MET_L2_DIRECT, d_sq.as<float>(),
                       ws.qsq.as<float>(), ws.keys_a.as<uint64_t>(), ws.keys_b.as<uint64_t>(), kprime, capp, s);  // pads its rows
         launch_topk_merge(ws.keys_b.as<uint64_t>(), 1, capp, (uint32_t)nq, ksel, ws.keys_c.as<uint64_t>(), s);
         launch_flat_finish(ws.keys_c.as<uint64_t>(), capk, ws.keys_a.as<uint64_t>(), capp, (uint32_t)nq, ksel, (uint32_t)k, kprime,
-                           n, ws.qsq.as<float>(), xsq_max, xsq_min_pos, cosine, (uint32_t)dim, se, d_hits, CAND_CAP, id_offset,
+                           n, ws.qsq.as<float>(), xsq_max, xsq_min_pos, cosine, (uint32_t)dim, se, d_hits, FLAT_CAND_CAP, id_offset,
                            static_cast<uint8_t *>(ws.pinned(nq)), d_idx, d_dist, d_cnt, s);
     }
     p.active = true;
@@ -862,35 +954,28 @@ uint64_t Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
     if (redo.empty()) return 0;
     if (!p.half && !p.i8) fallback_count += redo.size();
     const uint64_t nr = redo.size();
-    DevBuf rx, rq, rqs, ri, rd, rc, rdk;  // rare: allocated on demand
-    rx.reserve(nr * sizeof(uint64_t));
-    rq.reserve(nr * dim * sizeof(float));
+    RedoSet r(redo, p.d_q, dim, k, s);
+    DevBuf rqs, rdk;
     rqs.reserve(nr * sizeof(float));
-    ri.reserve(nr * k * sizeof(uint64_t));
-    rd.reserve(nr * k * sizeof(float));
-    rc.reserve(nr * sizeof(uint64_t));
-    VDB_HIP(hipMemcpyAsync(rx.p, redo.data(), nr * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    launch_gather_rows_f32(p.d_q, rx.as<uint64_t>(), nr, (uint32_t)dim, rq.as<float>(), s);
-    launch_gather_rows_f32(ws.qsq.as<float>(), rx.as<uint64_t>(), nr, 1, rqs.as<float>(), s);
+    launch_gather_rows_f32(ws.qsq.as<float>(), r.rx.as<uint64_t>(), nr, 1, rqs.as<float>(), s);
     if (try_second) {
         rdk.reserve(nr * sizeof(float));
-        launch_gather_dk(p.d_dist, p.d_cnt, rx.as<uint64_t>(), nr, (uint32_t)k, p.ksel, rdk.as<float>(), s);
+        launch_gather_dk(p.d_dist, p.d_cnt, r.rx.as<uint64_t>(), nr, (uint32_t)k, p.ksel, rdk.as<float>(), s);
     }
-    VDB_HIP(hipMemsetAsync(ri.p, 0, nr * k * sizeof(uint64_t), s));
-    VDB_HIP(hipMemsetAsync(rd.p, 0, nr * k * sizeof(float), s));
     VDB_SYNC(s);  // (`redo` is pageable host memory: the copy above must have read it before it goes out of scope in a nested call's unwinding)
+    uint64_t *ri = r.ri.as<uint64_t>(), *rc = r.rc.as<uint64_t>();
+    float *rq = r.rq.as<float>(), *rd = r.rd.as<float>();
     // the second 8-bit attempt: what it still cannot close goes to the fp16 tier from inside that call, and what it hands on is what the
     // auto rule counts (what left the 8-bit tier for good)
     if (try_second)
-        i8_redo += flat_knn_device(ws, rq.as<float>(), nr, k, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), true, 0, true, rdk.as<float>());
+        i8_redo += flat_knn_device(ws, rq, nr, k, ri, rd, rc, true, 0, true, rdk.as<float>());
     else if (p.i8)  // next tier: the fp16 pass (or whatever this index has instead), with its own shortlist rules
-        flat_knn_device(ws, rq.as<float>(), nr, k, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), true, 0, false);
+        flat_knn_device(ws, rq, nr, k, ri, rd, rc, true, 0, false);
     else if (p.half)
-        flat_knn_device(ws, rq.as<float>(), nr, k, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), false, p.kprime);
+        flat_knn_device(ws, rq, nr, k, ri, rd, rc, false, p.kprime);
     else
-        flat_exact_device(ws, rq.as<float>(), rqs.as<float>(), nr, p.ksel, k, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>());
-    launch_scatter_results(ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), rx.as<uint64_t>(), nr, (uint32_t)k, p.d_idx, p.d_dist, p.d_cnt, s);
-    VDB_SYNC(s);  // rx..rc are freed on return
+        flat_exact_device(ws, rq, rqs.as<float>(), nr, p.ksel, k, ri, rd, rc);
+    r.scatter(p.d_idx, p.d_dist, p.d_cnt, s);
     return p.i8 ? nr : 0;
 }
 
@@ -916,9 +1001,7 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
         range_scan_queries += nq;
         return;
     }
-    constexpr uint32_t CAND_CAP = 8192;
-    constexpr uint64_t QCH = 1024;  // queries per round of the 8-bit tier (8 groups of 128: 64 MB of hit lists, 64 MB of exact keys)
-    constexpr uint32_t BQ = 8;      // queries per corpus pass of the scan
+    constexpr uint32_t BQ = 8;  // queries per corpus pass of the scan
     const int cosine = dist == 1 ? 1 : 0;
     const int metric = cosine ? MET_COSINE : MET_L2_DIRECT;
     const uint64_t cap_pairs = range_max_results ? range_max_results : ~0ull;
@@ -937,7 +1020,7 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
         pool.grow((pool_used + add) * sizeof(uint64_t), pool_used * sizeof(uint64_t), s);
     };
     std::vector<uint64_t> scan;  // queries the scan tier answers
-    const bool tier = flat_mode != 1 && (flat_mode == 2 || n >= 16384) && flat_gemm_mode != 1 && i8_mirror_applicable() && ensure_i8(ws);
+    const bool tier = i8_side_tier(ws);
     // under a mask the filter pass reads the masked copy of the row constants: a disallowed row's key is +inf and passes no (finite) threshold
     const float *rowc = tier ? (mask ? masked_rowc(ws, *mask) : d_rowc_i8.as<float>()) : nullptr;
     if (!tier) {
@@ -946,40 +1029,19 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
     }
     for (uint64_t q0 = 0; tier && q0 < nq; q0 += QCH) {
         const uint64_t nb = std::min<uint64_t>(QCH, nq - q0);
-        const uint64_t gq = gemm_group(), ngroups = (nb + gq - 1) / gq, nq_pad = ngroups * gq;
         const float *Q = d_q + q0 * dim, *R = d_radius + q0;
-        ws.qsq.reserve(nq_pad * sizeof(float));
-        ws.qfrag_g.reserve(nq_pad * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float));
-        ws.qaux.reserve(3 * nq_pad * sizeof(float));
-        ws.misc.reserve(nq_pad * (sizeof(float) + sizeof(uint32_t)) + 128 * sizeof(uint32_t));  // tau | hit counters | the sets' rendezvous words
-        ws.lists.reserve(nq_pad * size_t(CAND_CAP) * sizeof(uint64_t));
-        ws.keys_b.reserve(nb * size_t(CAND_CAP) * sizeof(uint64_t));
-        float *d_tau = ws.misc.as<float>(), *d_qscale = ws.qaux.as<float>(), *d_qoff = d_qscale + nq_pad;
-        uint32_t *d_hits = reinterpret_cast<uint32_t *>(d_tau + nq_pad);
-        uint64_t *d_cand = ws.lists.as<uint64_t>(), *d_keys = ws.keys_b.as<uint64_t>();
-        launch_query_prep_i8(Q, (uint32_t)nb, (uint32_t)nq_pad, (uint32_t)dim, d_mu_i8.as<float>(), i8_l1, i8_l2, ws.qsq.as<float>(), d_qscale, d_qoff,
-                             d_hits, ws.qfrag_g.p, s, cosine);
-        launch_i8_tau_from_dk(R, (uint32_t)nb, (uint32_t)nq_pad, d_qoff, ws.qsq.as<float>(), xsq_max, i8_mu_norm, (uint32_t)dim, cosine, d_tau, s);
-        launch_range_admit(R, (uint32_t)nb, d_qoff, ws.qsq.as<float>(), xsq_max, xsq_min_pos, i8_mu_norm, (uint32_t)dim, cosine, d_tau, s);
-        if (mask) launch_tau_clamp(d_tau, (uint32_t)nq_pad, s);
-        {  // corpus passes of calls in flight on other workspaces take turns (flat_knn_enqueue)
-            std::lock_guard<std::mutex> g(pass_mu);
-            if (pass_ev_valid) VDB_HIP(hipStreamWaitEvent(s, pass_ev, 0));
-        }
-        prof_begin(ws, "flat_range_i8", double(ngroups) * double(n) * dim);
-        launch_flat_gemm8_filter(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, d_qscale, (uint32_t)ngroups, rowc, d_tau, d_cand, d_hits,
-                                 CAND_CAP, flat_gemm_debug, num_cu, s, CAND_CAP);
-        prof_end(ws);
-        {
-            std::lock_guard<std::mutex> g(pass_mu);
-            if (!pass_ev) VDB_HIP(hipEventCreateWithFlags(&pass_ev, hipEventDisableTiming));
-            VDB_HIP(hipEventRecord(pass_ev, s));
-            pass_ev_valid = true;
-        }
+        const I8Queries qp = i8_query_prep(ws, Q, nb);
+        ws.lists.reserve(qp.nq_pad * size_t(FLAT_CAND_CAP) * sizeof(uint64_t));
+        ws.keys_b.reserve(nb * size_t(FLAT_CAND_CAP) * sizeof(uint64_t));
+        uint64_t *d_keys = ws.keys_b.as<uint64_t>();
+        launch_i8_tau_from_dk(R, (uint32_t)nb, (uint32_t)qp.nq_pad, qp.d_qoff, ws.qsq.as<float>(), xsq_max, i8_mu_norm, (uint32_t)dim, cosine, qp.d_tau, s);
+        launch_range_admit(R, (uint32_t)nb, qp.d_qoff, ws.qsq.as<float>(), xsq_max, xsq_min_pos, i8_mu_norm, (uint32_t)dim, cosine, qp.d_tau, s);
+        if (mask) launch_tau_clamp(qp.d_tau, (uint32_t)qp.nq_pad, s);
+        i8_filter(ws, qp, rowc, "flat_range_i8", FLAT_CAND_CAP);
         prof_begin(ws, "flat_range_exact", 0.0);
-        launch_rerank(d_rows.as<float>(), (uint32_t)dim, Q, (uint32_t)nb, metric, d_sq.as<float>(), ws.qsq.as<float>(), d_cand, d_keys, CAND_CAP, CAND_CAP,
-                      s, d_hits);
-        launch_range_cut(d_keys, CAND_CAP, d_hits, R, d_tau, (uint32_t)nb, p_cnt, p_hits, s);
+        launch_rerank(d_rows.as<float>(), (uint32_t)dim, Q, (uint32_t)nb, metric, d_sq.as<float>(), ws.qsq.as<float>(), ws.lists.as<uint64_t>(), d_keys,
+                      FLAT_CAND_CAP, FLAT_CAND_CAP, s, qp.d_hits);
+        launch_range_cut(d_keys, FLAT_CAND_CAP, qp.d_hits, R, qp.d_tau, (uint32_t)nb, p_cnt, p_hits, s);
         prof_end(ws);
         VDB_SYNC(s);
         uint64_t add = 0, max_take = 0, hits = 0, served = 0, hmax = 0;
@@ -1007,7 +1069,7 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
         }
         if (add) {
             pool_room(add);
-            launch_range_append(d_keys, CAND_CAP, p_off, p_take, (uint32_t)nb, max_take, pool.as<uint64_t>(), s);
+            launch_range_append(d_keys, FLAT_CAND_CAP, p_off, p_take, (uint32_t)nb, max_take, pool.as<uint64_t>(), s);
             pool_used += add;
             VDB_SYNC(s);  // (the pinned block is rewritten by the next round)
         }
@@ -1096,7 +1158,7 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
 //   direct path: strict-order scan of the GATHERED rows (column j of the dense matrix = row ids[j], ids ascending, so the order of
 //     (distance, column) IS the order of (distance, id)), the k-NN selections as they are, k_filter_finalize maps columns to rows.
 //     For m <= flat_filtered_direct_max, for shapes the 8-bit tier does not take, and for the queries that tier hands on.
-//   8-bit tier: the sequence of flat_knn_enqueue's 8-bit branch per chunk of 1024 queries, with the MASKED row constants in the sample and
+//   8-bit tier: the shared pieces of the 8-bit pass (above) per chunk of QCH queries, with the MASKED row constants in the sample and
 //     the filter launch (a disallowed row's key is +inf) and the thresholds clamped to FLT_MAX in between, so that no threshold admits such
 //     a key.  The hit list then holds allowed rows only and every allowed row outside it has key > tau: k_flat_tail_lb and its bound apply
 //     unchanged.  One attempt: no refinement, no second pass, no fp16 / split-bf16 tier; what is still open goes to the direct path.
@@ -1193,8 +1255,8 @@ void Index::flat_knn_masked_device(Workspace &ws, const float *d_q, uint64_t nq,
         VDB_SYNC(s);
         return;
     }
-    const bool tier = m > flat_filtered_direct_max && ksel64 <= 64 && flat_mode != 1 && (flat_mode == 2 || n >= 16384) && flat_gemm_mode != 1 &&
-                      i8_mirror_applicable() && flat_tail_lb_supported((uint32_t)dim, flat_i8_kprime, (uint32_t)ksel64) && ensure_i8(ws);
+    const bool tier = m > flat_filtered_direct_max && ksel64 <= 64 && flat_tail_lb_supported((uint32_t)dim, flat_i8_kprime, (uint32_t)ksel64) &&
+                      i8_side_tier(ws);
     if (!tier) {
         filtered_direct_queries += nq;
         flat_masked_direct(ws, d_q, nq, k, mask, d_idx, d_dist, d_cnt);
@@ -1202,88 +1264,35 @@ void Index::flat_knn_masked_device(Workspace &ws, const float *d_q, uint64_t nq,
         return;
     }
     const float *rowc = masked_rowc(ws, mask);
-    constexpr uint32_t CAND_CAP = 8192;
-    constexpr uint64_t QCH = 1024;  // queries per round (8 groups of 128: 64 MB of hit lists)
-    const uint32_t ksel = (uint32_t)ksel64, kprime = flat_i8_kprime;
-    const int cosine = dist == 1 ? 1 : 0;
-    uint32_t s_step = 1, s_rank = 64;
-    mfma_sample_plan(n, 64u, &s_step, &s_rank, flat_i8_hits);  // (64 guaranteed hits, flat_i8_hits expected: flat_knn_enqueue)
-    const bool unit_min = flat_i8_unit_min != 1 && gemm8_sample_units(n, s_step) >= (flat_i8_unit_min == 2 ? 2ull : 16ull) * s_rank;
-    const uint64_t n_s = unit_min ? gemm8_sample_units(n, s_step) : gemm8_sample_rows(n, s_step);
-    const uint64_t ld_s = (n_s + 63) & ~63ull;
-    const uint32_t nl_s = topk_num_lists(n_s), cap_s = topk_capacity(s_rank);
+    const TauSample sp = i8_sample_plan();
     std::vector<uint64_t> redo;  // queries the tier hands on
     for (uint64_t q0 = 0; q0 < nq; q0 += QCH) {
         const uint64_t nb = std::min<uint64_t>(QCH, nq - q0);
-        const uint64_t gq = gemm_group(), ngroups = (nb + gq - 1) / gq, nq_pad = ngroups * gq;
         const float *Q = d_q + q0 * dim;
-        ws.qsq.reserve(nq_pad * sizeof(float));
-        ws.qfrag_g.reserve(nq_pad * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float));
-        ws.qaux.reserve(3 * nq_pad * sizeof(float));
-        ws.misc.reserve(nq_pad * (sizeof(float) + sizeof(uint32_t)) + 128 * sizeof(uint32_t));  // tau | hit counters | the sets' rendezvous words
-        ws.dense.reserve(nq_pad * ld_s * sizeof(float));
-        ws.lists.reserve(std::max<size_t>(nq_pad * size_t(nl_s) * cap_s, nq_pad * size_t(CAND_CAP)) * sizeof(uint64_t));
-        ws.keys_a.reserve(nq_pad * size_t(cap_s) * sizeof(uint64_t));
-        float *d_tau = ws.misc.as<float>(), *d_qscale = ws.qaux.as<float>(), *d_qoff = d_qscale + nq_pad;
-        uint32_t *d_hits = reinterpret_cast<uint32_t *>(d_tau + nq_pad);
-        launch_query_prep_i8(Q, (uint32_t)nb, (uint32_t)nq_pad, (uint32_t)dim, d_mu_i8.as<float>(), i8_l1, i8_l2, ws.qsq.as<float>(), d_qscale, d_qoff,
-                             d_hits, ws.qfrag_g.p, s, cosine);
+        const I8Queries qp = i8_query_prep(ws, Q, nb);
+        ws.dense.reserve(qp.nq_pad * sp.ld_s * sizeof(float));
+        ws.lists.reserve(std::max<size_t>(qp.nq_pad * size_t(sp.nl_s) * sp.cap_s, qp.nq_pad * size_t(FLAT_CAND_CAP)) * sizeof(uint64_t));
+        ws.keys_a.reserve(qp.nq_pad * size_t(sp.cap_s) * sizeof(uint64_t));
         // thresholds: the s_rank-th smallest sampled key among the ALLOWED rows (the others' keys are +inf) bounds the s_rank-th smallest
         // key over all allowed rows
-        launch_flat_gemm8_sample(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, d_qscale, (uint32_t)ngroups, rowc, s_step, ws.dense.as<float>(), ld_s,
-                                 num_cu, s, unit_min ? 1 : 0);
-        if (n_s <= select_tau_max_n()) {
-            launch_select_tau(ws.dense.as<float>(), ld_s, (uint32_t)n_s, (uint32_t)nq_pad, (uint32_t)nb, s_rank, d_tau, s);
-        } else {
-            launch_topk_dense(ws.dense.as<float>(), ld_s, n_s, (uint32_t)nq_pad, s_rank, ws.lists.as<uint64_t>(), s);
-            launch_topk_merge(ws.lists.as<uint64_t>(), nl_s, cap_s, (uint32_t)nq_pad, s_rank, ws.keys_a.as<uint64_t>(), s);
-            launch_extract_tau(ws.keys_a.as<uint64_t>(), cap_s, (uint32_t)nq_pad, s_rank, d_tau, s);
-            if (nq_pad > nb)  // padding queries pass nothing (k_select_tau does it itself)
-                VDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_tau + nb), (int)0xFF800000u, nq_pad - nb, s));
-        }
+        i8_sample(ws, qp, rowc, sp);
+        select_tau(ws, sp, qp.nq_pad, nb, qp.d_tau);
         // a sample with fewer than s_rank allowed rows selects +inf, which every masked row's key would pass: with tau = FLT_MAX the query
         // collects every allowed row with a finite key instead -- certified if they fit the list, handed on if not
-        launch_tau_clamp(d_tau, (uint32_t)nq_pad, s);
-        uint64_t *d_cand = ws.lists.as<uint64_t>();  // the sample lists are dead now
-        {  // corpus passes of calls in flight on other workspaces take turns (flat_knn_enqueue)
-            std::lock_guard<std::mutex> g(pass_mu);
-            if (pass_ev_valid) VDB_HIP(hipStreamWaitEvent(s, pass_ev, 0));
-        }
-        prof_begin(ws, "flat_filtered_i8", double(ngroups) * double(n) * dim);
-        launch_flat_gemm8_filter(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, d_qscale, (uint32_t)ngroups, rowc, d_tau, d_cand, d_hits, CAND_CAP,
-                                 flat_gemm_debug, num_cu, s, std::max<uint32_t>(64u, s_step * s_rank));
-        prof_end(ws);
-        {
-            std::lock_guard<std::mutex> g(pass_mu);
-            if (!pass_ev) VDB_HIP(hipEventCreateWithFlags(&pass_ev, hipEventDisableTiming));
-            VDB_HIP(hipEventRecord(pass_ev, s));
-            pass_ev_valid = true;
-        }
-        FlatTailArgs t{};
-        t.cand = d_cand;
-        t.cap = CAND_CAP;
-        t.cnt = d_hits;
-        t.kprime = kprime;
-        t.ksel = ksel;
+        launch_tau_clamp(qp.d_tau, (uint32_t)qp.nq_pad, s);
+        i8_filter(ws, qp, rowc, "flat_filtered_i8", std::max<uint32_t>(64u, sp.s_step * sp.s_rank));  // (the sample lists are dead now)
+        SplitErr se;
+        se.qoff = qp.d_qoff;
+        se.mu_norm = i8_mu_norm;
+        FlatTailArgs t = flat_tail_args(ws, qp.d_hits, qp.d_tau, se);
+        t.kprime = flat_i8_kprime;
+        t.ksel = (uint32_t)ksel64;
         t.kstride = (uint32_t)k;
-        t.X = d_rows.as<float>();
-        t.dim = (uint32_t)dim;
         t.Q = Q;
-        t.metric = cosine ? MET_COSINE : MET_L2_DIRECT;
-        t.xsq = d_sq.as<float>();
-        t.qsq = ws.qsq.as<float>();
-        t.n_rows = n;
-        t.xsq_max = xsq_max;
-        t.xsq_min_pos = xsq_min_pos;
-        t.cosine = cosine;
-        t.se.qoff = d_qoff;
-        t.se.mu_norm = i8_mu_norm;
-        t.id_offset = id_offset;
         t.flags = static_cast<uint8_t *>(ws.pinned(nb));
         t.out_idx = d_idx + q0 * k;
         t.out_dist = d_dist + q0 * k;
         t.out_count = d_cnt + q0;
-        t.tau = d_tau;
         launch_flat_tail_lb(t, (uint32_t)nb, s);
         VDB_SYNC(s);  // (the flags are in pinned host memory)
         for (uint64_t q = 0; q < nb; q++)
@@ -1292,22 +1301,11 @@ void Index::flat_knn_masked_device(Workspace &ws, const float *d_q, uint64_t nq,
     filtered_i8_queries += nq;
     filtered_fallback_queries += redo.size();
     if (redo.empty()) return;
-    // the open queries over all m allowed rows on the direct path: gathered, answered, scattered back (as flat_knn_finish does)
-    const uint64_t nr = redo.size();
-    DevBuf rx, rq, ri, rd, rc;
-    rx.reserve(nr * sizeof(uint64_t));
-    rq.reserve(nr * dim * sizeof(float));
-    ri.reserve(nr * k * sizeof(uint64_t));
-    rd.reserve(nr * k * sizeof(float));
-    rc.reserve(nr * sizeof(uint64_t));
-    VDB_HIP(hipMemcpyAsync(rx.p, redo.data(), nr * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    launch_gather_rows_f32(d_q, rx.as<uint64_t>(), nr, (uint32_t)dim, rq.as<float>(), s);
-    VDB_HIP(hipMemsetAsync(ri.p, 0, nr * k * sizeof(uint64_t), s));
-    VDB_HIP(hipMemsetAsync(rd.p, 0, nr * k * sizeof(float), s));
-    VDB_HIP(hipMemsetAsync(rc.p, 0, nr * sizeof(uint64_t), s));
-    flat_masked_direct(ws, rq.as<float>(), nr, k, mask, ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>());
-    launch_scatter_results(ri.as<uint64_t>(), rd.as<float>(), rc.as<uint64_t>(), rx.as<uint64_t>(), nr, (uint32_t)k, d_idx, d_dist, d_cnt, s);
-    VDB_SYNC(s);  // (`redo` and rx..rc go out of scope)
+    // the open queries over all m allowed rows on the direct path
+    RedoSet r(redo, d_q, dim, k, s);
+    VDB_HIP(hipMemsetAsync(r.rc.p, 0, r.nr * sizeof(uint64_t), s));
+    flat_masked_direct(ws, r.rq.as<float>(), r.nr, k, mask, r.ri.as<uint64_t>(), r.rd.as<float>(), r.rc.as<uint64_t>());
+    r.scatter(d_idx, d_dist, d_cnt, s);  // (its sync: before `redo` goes out of scope)
 }
 
 // ---- the approximate keys of the Flat shortlist pass, for every row ------------------------------------------------
@@ -1326,20 +1324,14 @@ void Index::flat_debug_keys(Workspace &ws, const float *d_q, uint64_t nq, int ti
     if (tier == 2) {  // 8-bit operands: keys are lower bounds, D >= key + qoff (h_qerr = qoff; h_dx = l1, l2, |mu|, 0)
         VDB_REQUIRE(!elem_u8 && (dim & 3) == 0 && gemm8_supported((uint32_t)dim), "debug keys: the index has no 8-bit pass");
         VDB_REQUIRE(ensure_i8(ws), "debug keys: the 8-bit mirror could not be allocated");
-        const uint64_t n_s8 = gemm8_sample_rows(n, 1), ld8 = (n_s8 + 63) & ~63ull;
-        ws.qsq.reserve(nq_pad * sizeof(float));
-        ws.qfrag_g.reserve(nq_pad * size_t(mfma_dim_pad((uint32_t)dim)));
-        ws.dense.reserve(nq_pad * ld8 * sizeof(float));
-        ws.qaux.reserve(2 * nq_pad * sizeof(float));
-        ws.misc.reserve((nq_pad + 128) * sizeof(uint32_t));  // (the preparation kernel also zeroes the 128 rendezvous words behind the counters)
-        float *d_qs8 = ws.qaux.as<float>(), *d_qoff = d_qs8 + nq_pad;
-        launch_query_prep_i8(d_q, (uint32_t)nq, (uint32_t)nq_pad, (uint32_t)dim, d_mu_i8.as<float>(), i8_l1, i8_l2, ws.qsq.as<float>(), d_qs8,
-                             d_qoff, ws.misc.as<uint32_t>(), ws.qfrag_g.p, s, cosine);
-        launch_flat_gemm8_sample(d_tiled_i8.p, n, (uint32_t)dim, ws.qfrag_g.p, d_qs8, (uint32_t)ngroups, d_rowc_i8.as<float>(), 1,
-                                 ws.dense.as<float>(), ld8, num_cu, s);
-        VDB_HIP(hipMemcpy2DAsync(h_keys, n * sizeof(float), ws.dense.p, ld8 * sizeof(float), n * sizeof(float), nq, hipMemcpyDeviceToHost, s));
+        TauSample sp;  // every row's key: step 1, no unit minima
+        sp.set_keys(gemm8_sample_rows(n, 1));
+        const I8Queries qp = i8_query_prep(ws, d_q, nq);
+        ws.dense.reserve(qp.nq_pad * sp.ld_s * sizeof(float));
+        i8_sample(ws, qp, d_rowc_i8.as<float>(), sp);
+        VDB_HIP(hipMemcpy2DAsync(h_keys, n * sizeof(float), ws.dense.p, sp.ld_s * sizeof(float), n * sizeof(float), nq, hipMemcpyDeviceToHost, s));
         if (h_qsq) VDB_HIP(hipMemcpyAsync(h_qsq, ws.qsq.p, nq * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (h_qerr) VDB_HIP(hipMemcpyAsync(h_qerr, d_qoff, nq * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (h_qerr) VDB_HIP(hipMemcpyAsync(h_qerr, qp.d_qoff, nq * sizeof(float), hipMemcpyDeviceToHost, s));
         VDB_SYNC(s);
         if (h_dx) {
             h_dx[0] = i8_l1;

@@ -210,6 +210,27 @@ struct FlatPending {
     uint64_t *d_cnt = nullptr;
 };
 
+// the query side of one 8-bit filter pass over a chunk of queries (Index::i8_query_prep): all in the workspace's buffers
+struct I8Queries {
+    uint64_t ngroups = 0, nq_pad = 0;  // groups of gemm_group() queries, queries with the last group's padding
+    float *d_tau = nullptr, *d_qscale = nullptr, *d_qoff = nullptr;  // [nq_pad] each; the thresholds are the caller's to fill
+    uint32_t *d_hits = nullptr;                                      // [nq_pad] hit counters, zeroed
+};
+
+// a threshold sample: tau = the s_rank-th smallest of n_s dense keys per query (rows of ld_s floats)
+struct TauSample {
+    uint32_t s_step = 1, s_rank = 0;  // every s_step-th item (8-bit pass: unit) is sampled
+    bool unit_min = false;            // 8-bit pass: one key per sampled unit, its smallest
+    uint64_t n_s = 0, ld_s = 0;
+    uint32_t nl_s = 0, cap_s = 0;     // the selection's lists beyond select_tau_max_n() keys: lists per query, slots per list
+    void set_keys(uint64_t keys) {
+        n_s = keys;
+        ld_s = (keys + 63) & ~63ull;
+        nl_s = topk_num_lists(keys);
+        cap_s = topk_capacity(s_rank);
+    }
+};
+
 // the answer of a range call (Index::flat_range_device): CSR over the queries, arrays on the index's device
 struct RangeResult {
     int device = 0;
@@ -403,7 +424,7 @@ struct Index {
 
     std::mutex ws_mu;
     std::vector<std::unique_ptr<Workspace>> ws_free;
-    // end of the most recent Flat corpus pass enqueued on any of this index's streams (flat_knn_enqueue orders passes by it)
+    // end of the most recent Flat corpus pass enqueued on any of this index's streams (corpus_pass orders passes by it)
     std::mutex pass_mu;
     hipEvent_t pass_ev = nullptr;
     bool pass_ev_valid = false;
@@ -442,6 +463,17 @@ struct Index {
     void flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt,
                           bool allow_half, uint32_t kprime_min, FlatPending &p, bool allow_i8 = true, const float *d_dk_hint = nullptr);
     uint64_t flat_knn_finish(Workspace &ws, FlatPending &p);
+    // The pieces of an 8-bit filter pass that Flat k-NN, the range search, the filtered search and flat_debug_keys share (index.hip).  They
+    // take data -- a chunk of queries, the row constants to filter by, an expected hit count -- and never which caller they serve.
+    template <class F>
+    void corpus_pass(Workspace &ws, const char *name, double bytes, F launch);  // launch() in this index's turn on the corpus, timed as `name`
+    I8Queries i8_query_prep(Workspace &ws, const float *Q, uint64_t nb);        // reserves the query-side buffers, enqueues k_query_prep_i8
+    TauSample i8_sample_plan() const;  // 64 guaranteed hits, flat_i8_hits expected
+    void i8_sample(Workspace &ws, const I8Queries &qp, const float *rowc, const TauSample &sp);  // dense sample keys -> ws.dense
+    void select_tau(Workspace &ws, const TauSample &sp, uint64_t nq_pad, uint64_t nq, float *d_tau);  // ws.dense -> tau; padding queries -inf
+    void i8_filter(Workspace &ws, const I8Queries &qp, const float *rowc, const char *name, uint32_t hits_expected);  // -> ws.lists, qp.d_hits
+    FlatTailArgs flat_tail_args(const Workspace &ws, const uint32_t *d_hits, const float *d_tau, const SplitErr &se) const;
+    bool i8_side_tier(Workspace &ws);  // the range / filtered tiers' shape test (no k, no auto-off counters); builds the mirror
     void flat_sorted_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t ksel, uint64_t k, uint64_t *d_idx,
                             float *d_dist, uint64_t *d_cnt);
     void scan_rows(uint64_t nrows, uint32_t d, const float *Q, uint32_t nq, int metric, const float *xsq, const float *qsq, float *out,

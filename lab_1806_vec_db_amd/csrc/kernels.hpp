@@ -46,6 +46,7 @@ void launch_flat_finish(const uint64_t *exact_sorted, uint32_t lde, const uint64
                         hipStream_t s);
 // the exact stage of the Flat pipeline fused into one launch (k' <= 64, k <= 64, dim % 4 == 0): counted select of the hit
 // list + re-rank + sort + certification + outputs (k_exact.hip)
+constexpr uint32_t FLAT_CAND_CAP = 8192;  // slots of a query's hit list in every Flat filter pass
 struct FlatTailArgs {
     const uint64_t *cand;  // [nq][cap] hit lists of the filter pass
     uint32_t cap;

@@ -325,6 +325,39 @@ def test_tier_hands_on_a_tight_cluster():
         ix.close()
 
 
+def test_many_queries_cross_the_tier_rounds():
+    """More queries than one round of the tier takes (1024): output offsets, per-round flags and the hand-on indices across the seam.  300
+    allowed near-copies of one row with queries next to them on both sides of query 1024 (walk limited to 256 rows): both rounds hand on."""
+    rng = np.random.default_rng(10)
+    base = gist_like(17000, dim=128, seed=2401)
+    centre = base[77].copy()
+    near = np.round(np.clip(np.abs(centre + rng.standard_normal((300, 128)).astype(np.float32) * np.float32(2e-4)), 0, 0.8), 4).astype(np.float32)
+    base[1000:1300] = near
+    qs = gist_like(1100, dim=128, seed=2402)
+    at = np.array([3, 500, 1023, 1024, 1025, 1099])  # queries next to the cluster, in the first round and in the second
+    qs[at] = near[: len(at)] + np.float32(1e-4)
+    allow = rng.random(17000) < 0.5
+    allow[1000:1300] = True
+    exp = _expect_knn(_full_order(base, qs, 0), allow, 10)
+    assert np.isin(exp[0][at], np.arange(1000, 1300)).all()  # (the cluster queries' neighbours ARE the cluster)
+    ix = _index("l2sqr", base, 2)
+    try:
+        ix.set_param("flat_filtered_direct_max", 0)
+        ix.set_param("flat_i8_rows", 256)
+        mk = ix.make_mask(allow)
+        s0 = _stats(ix)
+        got_t = ix.flat_knn_filtered(qs, 10, mk)
+        d = _delta(ix, s0)
+        print(d)
+        _same_knn(got_t, exp, "1100 queries: tier")
+        assert d["flat_filtered_i8_queries"] == 1100 and d["flat_filtered_fallback_queries"] > 0, d
+        ix.set_flat_mode(1)
+        _same_knn(got_t, ix.flat_knn_filtered(qs, 10, mk), "1100 queries: tier vs direct")
+        mk.close()
+    finally:
+        ix.close()
+
+
 def test_unfiltered_search_is_isolated(big):
     """an unfiltered flat_knn before and after filtered calls returns identical bits, and the k-NN tiers' counters move only by it"""
     base, qs, fulls = big
