@@ -334,19 +334,24 @@ int vdb_hnsw_last_stats(const vdb_index *idx, uint64_t *n_dist, uint64_t *n_expa
 int vdb_merge_topk(const float *dists, const uint64_t *ids, const uint64_t *counts, uint64_t n_shards,
                    uint64_t nq, uint64_t k, uint64_t *out_idx, float *out_dist, uint64_t *out_count);
 
-/* same merge on the index's GPU (inputs = the all-gathered tensors, ids < 2^32); returns synchronised */
+/* same merge on the index's GPU (inputs = the all-gathered tensors, ids < 2^32); returns synchronised.
+ * The three device merges keep an id in 32 bits of a pair key: every id in the lists must be below 2^32 (the host merge above carries
+ * 64).  The lists are not inspected; a call is refused when `idx` itself reports id_offset + len > 2^32, when n_shards is 0, or
+ * when k is outside 1..1024. */
 int vdb_merge_topk_device(vdb_index *idx, const void *d_dists, const void *d_ids, const void *d_counts,
                           uint64_t n_shards, uint64_t nq, uint64_t k, void *d_out_idx, void *d_out_dist,
                           void *d_out_count, void *stream);
 
 /* same merge reading the S per-rank blocks of ONE all-gather buffer in place (block s at s*block_bytes; ids, distances
- * and counts at the given byte offsets inside a block): no repacking between the collective and the merge */
+ * and counts at the given byte offsets inside a block): no repacking between the collective and the merge.  Ids < 2^32 and
+ * n_shards >= 1, as for vdb_merge_topk_device. */
 int vdb_merge_topk_gathered(vdb_index *idx, const void *d_gathered, uint64_t block_bytes, uint64_t off_ids,
                             uint64_t off_dists, uint64_t off_counts, uint64_t n_shards, uint64_t nq, uint64_t k,
                             void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
 
 /* the same, ENQUEUED on `stream` (the stream the all-gather was issued on) without any host synchronisation, k <= 64: the
- * exchange of one step can then run under the next step's search (outputs are valid once `stream` has passed this point) */
+ * exchange of one step can then run under the next step's search (outputs are valid once `stream` has passed this point).
+ * Ids < 2^32 and n_shards >= 1, as for vdb_merge_topk_device. */
 int vdb_merge_topk_gathered_async(vdb_index *idx, const void *d_gathered, uint64_t block_bytes, uint64_t off_ids,
                                   uint64_t off_dists, uint64_t off_counts, uint64_t n_shards, uint64_t nq, uint64_t k,
                                   void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);

@@ -18,13 +18,21 @@ void vdb::require_gpu() {
                                        hipGetErrorString(e));
 }
 
+// the device merges carry an id in the low word of a pair key: the ids of the lists must be below 2^32.  The lists themselves are
+// not inspected; the shard handed in stands for them (every rank merges with its own), as in flat_knn_pq_shard_device
+static void require_merge_ids_fit(const Index &ix) {
+    VDB_REQUIRE(ix.id_offset <= (1ull << 32) && ix.n <= (1ull << 32) - ix.id_offset, "shard merge: global row ids must fit 32 bits");
+}
+
 // device-resident variants: inputs/outputs on the index's GPU, ids < 2^32; synchronous on return
 void vdb::merge_topk_dev(Index &ix, const void *d_dists, const void *d_ids, const void *d_counts, uint64_t stride_d,
                            uint64_t stride_i, uint64_t stride_c, uint64_t n_shards, uint64_t nq, uint64_t k,
                            void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
     VDB_REQUIRE(d_dists && d_ids && d_counts && d_out_idx && d_out_dist && d_out_count, "null argument");
     VDB_REQUIRE(k >= 1 && k <= 1024, "k must be in 1..1024");
+    VDB_REQUIRE(n_shards >= 1, "shard merge: at least one shard is needed");
     VDB_REQUIRE(nq <= 65535 && n_shards <= 65535, "too many queries or shards for one call");
+    require_merge_ids_fit(ix);
     ix.use_device();
     WsLease ws(ix);
     VDB_SYNC(static_cast<hipStream_t>(stream));
@@ -1424,7 +1432,9 @@ int vdb_merge_topk_gathered_async(vdb_index *idx, const void *d_gathered, uint64
     VDB_REQUIRE((off_ids & 7) == 0 && (off_counts & 7) == 0 && (off_dists & 3) == 0 && (block_bytes & 7) == 0,
                 "misaligned block layout");
     VDB_REQUIRE(k >= 1 && k <= 64, "the enqueued merge serves k in 1..64 (one launch, no scratch); use vdb_merge_topk_gathered beyond");
+    VDB_REQUIRE(n_shards >= 1, "shard merge: at least one shard is needed");
     VDB_REQUIRE(nq <= 65535 && n_shards <= 65535, "too many queries or shards for one call");
+    require_merge_ids_fit(idx->ix);
     idx->ix.use_device();
     const char *g = static_cast<const char *>(d_gathered);
     launch_merge_shards64(reinterpret_cast<const float *>(g + off_dists), reinterpret_cast<const uint64_t *>(g + off_ids),

@@ -461,6 +461,7 @@ int vdb_sharded_flat_knn(vdb_sharded *sh, const float *queries, uint64_t nq, uin
         return VDB_OK;
     }
     VDB_REQUIRE(k <= 1024, "sharded knn: k must be <= 1024 (the merge of the gathered lists)");
+    VDB_REQUIRE(sh->n_total <= (1ull << 32), "sharded knn: global row ids must fit 32 bits (the merge of the gathered lists)");
     const uint64_t S = (uint64_t)sh->ctx->world;
     constexpr uint64_t CHUNK = 8192;
     for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {

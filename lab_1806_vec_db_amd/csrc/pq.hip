@@ -2764,7 +2764,7 @@ void flat_knn_pq_shard_device(Index &ix, Workspace &ws, const float *d_q, uint64
     if (nq == 0) return;
     const uint64_t efg = std::max(ef, k);
     VDB_REQUIRE(efg >= 1 && efg < (1ull << 31), "knn_pq shard: max(ef, k) must be in 1..2^31");
-    VDB_REQUIRE(ix.id_offset + ix.n <= (1ull << 32), "knn_pq shard: global row ids must fit 32 bits");
+    VDB_REQUIRE(ix.id_offset <= (1ull << 32) && ix.n <= (1ull << 32) - ix.id_offset, "knn_pq shard: global row ids must fit 32 bits");
     if (ix.n == 0) {
         VDB_HIP(hipMemsetAsync(d_adc_keys, 0xff, nq * efg * sizeof(uint64_t), s));
         VDB_HIP(hipMemsetAsync(d_exact_keys, 0xff, nq * efg * sizeof(uint64_t), s));

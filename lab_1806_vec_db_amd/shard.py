@@ -28,7 +28,7 @@ def allgather_merge(local_idx, local_dist, local_cnt, k: int, group=None, gpu_in
     """local_*: torch tensors [nq,k] int64 / [nq,k] float32 / [nq] int64 with GLOBAL ids.
 
     Returns merged (idx [nq,k] int64, dist [nq,k] float32, cnt [nq] int64) on every rank.
-    On CUDA tensors the merge runs on the GPU (vdb_merge_topk_device, needs `gpu_index`);
+    On CUDA tensors the merge runs on the GPU (vdb_merge_topk_device, needs `gpu_index`; global ids below 2^32);
     on CPU tensors (gloo rehearsal) it uses the host merge utility of the same library.
     """
     import torch
@@ -238,6 +238,9 @@ class ShardExchange:
     step's search, which the library issues on its own stream.  `begin_step()` hands out the buffers of the step and first
     waits until the exchange that used them two steps ago is done; the merged results of a step are valid once torch's stream
     has passed its exchange (the caller's fence, or `wait()`).
+
+    Both device merges keep an id in 32 bits of a pair key: every global id (id_offset + row) must be below 2^32.  They refuse a
+    `gpu_index` that reports id_offset + len > 2^32 (VdbError) and do not inspect the lists; the host `merge_topk` carries 64 bits.
     """
 
     def __init__(self, nq: int, k: int, device, world: int, force: bool = False, min_depth: int = 1):
