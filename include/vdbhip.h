@@ -15,7 +15,7 @@
  *    through vdb_last_error() (thread-local).  Nothing aborts the process.
  *  - read-side calls (knn*, row, len...) are re-entrant on one handle, like `&self` methods
  *    under the reference's RwLock read guard (database/mod.rs:248-256); write-side calls
- *    (add, swap_remove, *_build, *_attach, *_clear) need external exclusion, like `&mut self`.
+ *    (add, swap_remove, remove_rows, *_build, *_attach, *_clear) need external exclusion, like `&mut self`.
  *  - results for query q are written at out_idx[q*k .. q*k+out_count[q]) ascending by
  *    (distance, index) -- the order of `Vec<CandidatePair>` (candidate_pair.rs:36-41);
  *    out_count[q] = min(k, len) for Flat (flat_index.rs:163).
@@ -67,6 +67,23 @@ int vdb_index_add(vdb_index *idx, const float *rows, uint64_t n, uint64_t *first
 int vdb_index_add_device(vdb_index *idx, const void *d_rows, uint64_t n, uint64_t *first_id);
 /* VecSet::swap_remove (vec_set.rs:131-137); Flat only (metadata_vec_table.rs:163-187) */
 int vdb_index_swap_remove(vdb_index *idx, uint64_t i);
+/* ---- bulk removal: MetadataVecTable::delete (metadata_vec_table.rs:163-187) as ONE call --------------------------------------
+ * Removing the rows R (m of them) means swap_remove on every one of them in DESCENDING order; the state after that sequence is
+ * what these calls work with.  With n' = n - m, its net effect is a list of moves (dst, src): the row that was at src >= n' is
+ * now at dst < n', every other surviving row kept its place, and there are exactly |R below n'| moves.
+ * vdb_remove_plan: host utility, works without a GPU (like vdb_merge_topk).  rows [m] must be strictly ascending and below n; anything
+ * else is VDB_ERR_INVALID with a message, and nothing is written.  out_dst / out_src (room for m entries each) receive the moves in
+ * the order the replayed sequence makes them (descending dst), *out_moves their number; out_dst = out_src = NULL: the number alone.
+ * vdb_index_remove_rows: removes the LOCAL rows `rows` (same rules; id_offset plays no part) from the index in one pass -- one launch
+ * moves the rows and their norms (csrc/k_remove.hip), one launch per live mirror rewrites the touched 16-row tiles, one stream
+ * synchronisation for the whole call -- and leaves exactly the state the swap_remove sequence leaves: same rows in the same order,
+ * the 8-bit / fp16 / split-bf16 mirrors kept in step (not rebuilt), masks made before it stale (VDB_ERR_STATE).  The last three
+ * arguments return the plan, so that the caller can permute whatever it keeps per row (meta[dst] = meta[src], then truncate to
+ * n'); all three may be NULL.  Write-side.  Flat only, refused like vdb_index_swap_remove under an HNSW graph, a PQ table or IVF
+ * clusters.  An invalid list or a failed allocation leaves the index exactly as it was; m == 0 changes nothing (masks stay valid);
+ * m == n leaves an empty index. */
+int vdb_remove_plan(uint64_t n, const uint64_t *rows, uint64_t m, uint64_t *out_dst, uint64_t *out_src, uint64_t *out_moves);
+int vdb_index_remove_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, uint64_t *out_dst, uint64_t *out_src, uint64_t *out_moves);
 /* row sharding: ids reported by knn* are local_row + offset */
 int vdb_index_set_id_offset(vdb_index *idx, uint64_t offset);
 /* calc_dist (pyo3/mod.rs:43-48): one distance, evaluated on the GPU in reference order */

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "vdbhip.h"
@@ -124,6 +125,16 @@ public:
         return first;
     }
     void swap_remove(uint64_t i) { check(vdb_index_swap_remove(h_, i)); }  // vec_set.rs:131-137
+    // swap_remove on every row of `rows` (strictly ascending) in descending order, as one call (MetadataVecTable::delete,
+    // metadata_vec_table.rs:163-187).  Returns the moves (dst, src): the row that was at src is now at dst, all others kept their place.
+    std::vector<std::pair<uint64_t, uint64_t>> remove_rows(const std::vector<uint64_t> &rows) {
+        std::vector<uint64_t> dst(rows.size()), src(rows.size());
+        uint64_t moves = 0;
+        check(vdb_index_remove_rows(h_, rows.data(), rows.size(), dst.data(), src.data(), &moves));
+        std::vector<std::pair<uint64_t, uint64_t>> out(moves);
+        for (uint64_t j = 0; j < moves; j++) out[j] = {dst[j], src[j]};
+        return out;
+    }
 
     // knn (dynamic_index.rs:66-73): Flat -> FlatIndex::knn, HNSW -> HNSWIndex::knn (default ef)
     std::vector<CandidatePair> knn(const std::vector<float> &query, uint64_t k) const {

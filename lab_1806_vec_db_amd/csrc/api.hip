@@ -5,6 +5,7 @@
 
 #include "ctx.hpp"
 #include "pq_hnsw.hpp"
+#include "remove_plan.hpp"
 
 using namespace vdb;
 
@@ -191,6 +192,41 @@ int vdb_index_swap_remove(vdb_index *idx, uint64_t i) {
     VDB_REQUIRE(!idx->ix.pq.present, "swap_remove invalidates the PQ table: clear it first");
     VDB_REQUIRE(!idx->ix.ivf.present, "swap_remove invalidates the IVF clusters: clear them first");
     idx->ix.swap_remove(i);
+    VDB_API_END
+}
+// the plan's outputs: the count, and the moves when the caller asked for them (out_dst / out_src go together)
+static void remove_plan_out(const std::vector<uint64_t> &dst, const std::vector<uint64_t> &src, uint64_t *out_dst, uint64_t *out_src,
+                            uint64_t *out_moves) {
+    if (out_dst && !dst.empty()) {
+        std::memcpy(out_dst, dst.data(), dst.size() * sizeof(uint64_t));
+        std::memcpy(out_src, src.data(), src.size() * sizeof(uint64_t));
+    }
+    if (out_moves) *out_moves = dst.size();
+}
+int vdb_remove_plan(uint64_t n, const uint64_t *rows, uint64_t m, uint64_t *out_dst, uint64_t *out_src, uint64_t *out_moves) {
+    VDB_API_BEGIN
+    VDB_REQUIRE((out_dst == nullptr) == (out_src == nullptr), "out_dst and out_src go together (both NULL: the count only)");
+    const char *why = remove_plan_check(n, rows, m);
+    VDB_REQUIRE(!why, why);
+    if (!out_dst) {
+        if (out_moves) *out_moves = remove_plan_count(n, rows, m);
+        return VDB_OK;
+    }
+    std::vector<uint64_t> dst, src;
+    remove_plan(n, rows, m, dst, src);
+    remove_plan_out(dst, src, out_dst, out_src, out_moves);
+    VDB_API_END
+}
+int vdb_index_remove_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, uint64_t *out_dst, uint64_t *out_src, uint64_t *out_moves) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    VDB_REQUIRE((out_dst == nullptr) == (out_src == nullptr), "out_dst and out_src go together (both NULL: no plan returned)");
+    VDB_REQUIRE(!idx->ix.hnsw.present, "swap_remove needs a Flat index (clear the HNSW graph first)");
+    VDB_REQUIRE(!idx->ix.pq.present, "swap_remove invalidates the PQ table: clear it first");
+    VDB_REQUIRE(!idx->ix.ivf.present, "swap_remove invalidates the IVF clusters: clear them first");
+    std::vector<uint64_t> dst, src;
+    idx->ix.remove_rows(rows, m, dst, src);
+    remove_plan_out(dst, src, out_dst, out_src, out_moves);
     VDB_API_END
 }
 int vdb_index_set_id_offset(vdb_index *idx, uint64_t offset) {

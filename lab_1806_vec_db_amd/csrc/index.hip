@@ -1,5 +1,6 @@
 // index.hip -- Index object: HBM-resident VecSet + the Flat search pipeline.
 #include "index.hpp"
+#include "remove_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -153,6 +154,87 @@ void Index::swap_remove(uint64_t i) {
     n = last;
     write_gen += 1;
     // xsq_max stays an upper bound (certification only needs a bound)
+}
+
+// MetadataVecTable::delete's loop of swap_removes (metadata_vec_table.rs:170-186) as one pass; mirror upkeep as in swap_remove above
+void Index::remove_rows(const uint64_t *rows, uint64_t m, std::vector<uint64_t> &dst, std::vector<uint64_t> &src) {
+    dst.clear();
+    src.clear();
+    const char *why = remove_plan_check(n, rows, m);
+    VDB_REQUIRE(!why, why);
+    if (m == 0) return;
+    use_device();
+    WsLease ws(*this);
+    hipStream_t s = ws->stream;
+    const uint64_t n1 = n - m;
+    const size_t row_bytes = size_t(dim) * elem_size();
+    remove_plan(n, rows, m, dst, src);
+    const uint64_t moves = dst.size();
+    // the 16-row tiles whose rows change: those of the filled holes, and from the new end of the table to the end of a mirror of n1 rows
+    // (rows at and past n1 become padding)
+    const bool tiles_wanted = mfma_supported((uint32_t)dim) || i8_m.covers(n);
+    std::vector<uint32_t> h_moves(2 * moves), h_tiles;
+    for (uint64_t j = 0; j < moves; j++) {
+        h_moves[2 * j] = (uint32_t)dst[j];
+        h_moves[2 * j + 1] = (uint32_t)src[j];
+    }
+    if (tiles_wanted) {
+        for (uint64_t j = moves; j-- > 0;)  // (dst descends)
+            if (h_tiles.empty() || h_tiles.back() != dst[j] / 16) h_tiles.push_back(uint32_t(dst[j] / 16));
+        for (uint64_t t = n1 / 16; t < mirror_tiles(n1); t++)
+            if (h_tiles.empty() || h_tiles.back() != t) h_tiles.push_back((uint32_t)t);
+    }
+    const uint64_t n_tiles = h_tiles.size();
+    // a u8 index re-tiles through the widened chunks of the range path, from the first touched tile to the end
+    const bool list_form = !elem_u8;
+    ws->keys_a.reserve(std::max<size_t>(h_moves.size(), 1) * sizeof(uint32_t));
+    ws->keys_b.reserve(std::max<size_t>(n_tiles, 1) * sizeof(uint32_t));
+    if (!list_form && n_tiles) ws->dense.reserve(tile_chunk_bytes());  // (for_tile_chunks' buffer: its own reserve is then a no-op)
+    // ---- nothing was changed up to here; from here on nothing allocates on the device ----
+    const uint32_t *d_moves = ws->keys_a.as<uint32_t>(), *d_tiles = ws->keys_b.as<uint32_t>();
+    if (moves) VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_moves.data(), h_moves.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (n_tiles && list_form) VDB_HIP(hipMemcpyAsync(ws->keys_b.p, h_tiles.data(), n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    launch_rows_move(d_rows.p, row_bytes, d_sq.as<float>(), d_moves, moves, num_cu, s);
+    if (mfma_supported((uint32_t)dim) && n_tiles) {
+        const bool half_live = half_m.covers(n);  // same scale; the moved rows' rounding error is already part of half_dx_*
+        if (list_form) {
+            if (tiled_m.valid) launch_tile_rows_list(d_rows.as<float>(), n1, (uint32_t)dim, d_tiles, n_tiles, d_tiled.as<float>(), s);
+            if (half_live) launch_tile_rows_h_list(d_rows.as<float>(), n1, (uint32_t)dim, d_tiles, n_tiles, half_sx(), d_tiled_h.p, s);
+        } else if (tiled_m.valid || half_live) {
+            for_tile_chunks(*ws, h_tiles.front(), mirror_tiles(n1), n1, [&](const float *v, uint64_t ta, uint64_t tb, uint64_t, uint64_t) {
+                if (tiled_m.valid) launch_tile_rows(v, n1, (uint32_t)dim, ta, tb, d_tiled.as<float>(), s);
+                if (half_live) launch_tile_rows_h(v, n1, (uint32_t)dim, ta, tb, half_sx(), d_tiled_h.p, s);
+            });
+        }
+    }
+    if (tiled_m.valid) tiled_m.rows = n1;
+    // an fp16 mirror behind the table is rebuilt in full by its next use (the moved rows' error was never measured)
+    if (half_m.rows == n)
+        half_m.rows = n1;
+    else
+        half_m.invalidate();
+    if (i8_m.covers(n)) {  // (f32 rows only) tiles, codes and constants with the current mu / lambdas; d_sq already holds the moved rows'
+        launch_tile_rows_i8_list(d_rows.as<float>(), n1, (uint32_t)dim, d_tiles, n_tiles, d_mu_i8.as<float>(), i8_l1, i8_l2, d_tiled_i8.p,
+                                 d_rowc_i8.as<float>(), s, dist == 1 ? d_sq.as<float>() : nullptr);
+        i8_m.rows = n1;
+    } else {
+        i8_m.invalidate();  // rows were added since the last search: rebuilt by the next one
+    }
+    rows_h_m.invalidate();
+    rows_q8_m.invalidate();
+    VDB_SYNC(s);
+    {
+        std::lock_guard<std::mutex> g(host_mu);
+        if (host_valid && !elem_u8) {
+            for (uint64_t j = 0; j < moves; j++) std::memcpy(h_rows.data() + dst[j] * dim, h_rows.data() + src[j] * dim, dim * sizeof(float));
+            h_rows.resize(n1 * dim);
+        }
+    }
+    for (uint64_t j = 0; j < moves; j++) h_sq[dst[j]] = h_sq[src[j]];
+    h_sq.resize(n1);
+    n = n1;
+    write_gen += 1;
+    // xsq_max / xsq_min_pos stay bounds
 }
 
 // ---- images of the rows (RowMirror): a tier whose image is missing leaves its queries to the next one (8-bit -> fp16 -> split-bf16 ->

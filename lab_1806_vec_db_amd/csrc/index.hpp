@@ -316,14 +316,16 @@ struct Index {
     const float *rows_f32_view(DevBuf &scratch, uint64_t r0, uint64_t r1, hipStream_t s) const;
     // fn(view, tile_a, tile_b, row_a, row_b) over the 16-row tiles [t_begin, t_end), rows clipped to n_rows: one call on
     // the rows themselves (f32), or one per widened chunk (u8); view + r * dim addresses row r for row_a <= r < row_b
+    static constexpr uint64_t TILE_CHUNK = 12 * 64;  // tiles per widened chunk of a u8 index (whole mirror units): 12 288 rows
+    size_t tile_chunk_bytes() const { return TILE_CHUNK * 16 * dim * sizeof(float); }  // what for_tile_chunks reserves in ws.dense (u8 index)
     template <class F>
     void for_tile_chunks(Workspace &ws, uint64_t t_begin, uint64_t t_end, uint64_t n_rows, F fn) const {
         if (!elem_u8) {
             fn(d_rows.as<float>(), t_begin, t_end, std::min(t_begin * 16, n_rows), n_rows);
             return;
         }
-        constexpr uint64_t CH = 12 * 64;  // tiles per chunk (whole mirror units): 12 288 rows
-        ws.dense.reserve(CH * 16 * dim * sizeof(float));  // before the loop: a later, larger reserve would free a buffer in use
+        constexpr uint64_t CH = TILE_CHUNK;
+        ws.dense.reserve(tile_chunk_bytes());  // before the loop: a later, larger reserve would free a buffer in use
         for (uint64_t t = t_begin; t < t_end; t += CH) {
             const uint64_t tb = std::min(t_end, t + CH), ra = std::min(t * 16, n_rows), rb = std::min(tb * 16, n_rows);
             fn(rows_f32_view(ws.dense, ra, rb, ws.stream), t, tb, ra, rb);
@@ -447,6 +449,10 @@ struct Index {
 
     void add_rows(const void *rows, uint64_t count, bool on_device);  // elements of elem_size() bytes
     void swap_remove(uint64_t i);
+    // The state that swap_remove on rows[m - 1], .., rows[0] (strictly ascending) would leave, in one pass: the moves of the removal
+    // plan (remove_plan.hpp) on the device, the touched tiles of every live mirror rewritten once, one stream sync.  dst / src
+    // receive the plan.  An invalid list or a failed allocation throws before anything is changed.
+    void remove_rows(const uint64_t *rows, uint64_t m, std::vector<uint64_t> &dst, std::vector<uint64_t> &src);
 
     // timing hooks
     void prof_begin(Workspace &ws, const char *name, double bytes);
@@ -499,7 +505,7 @@ struct Index {
                             uint64_t *d_cnt);  // enqueues; the caller synchronises
     void check_mask(const RowMask &mask) const;  // throws: a mask of another index (invalid argument), a stale mask (state)
     const float *masked_rowc(Workspace &ws, const RowMask &mask);  // after ensure_i8 succeeded; builds the copy on first use
-    std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove: what a RowMask is checked against
+    std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};
     uint64_t range_max_results = 0;  // ceiling on the pairs of one call ("flat_range_max_results"; 0: what the device can hold)

@@ -40,8 +40,10 @@ __device__ __forceinline__ void load8_pad(const float *row, uint32_t dim, uint32
 // rows [16*tile0, 16*tile1) -> T[(tile*KB32 + kb32)*64 + lane] = 8 fp16: row 16*tile + (lane & 15), columns
 // 32*kb32 + 8*(lane >> 4) + j -- the A operand of v_mfma_f32_16x16x32_f16; a 64-column k-block of k_flat_gemm is two
 // consecutive 1-KB fragments, exactly like the [hi|lo] pair of the split-bf16 mirror.  Rows >= n: zero.
+// tiles != null (the list form, Index::remove_rows): the tiles tiles[tile0 .. tile1) instead of tile0 .. tile1 themselves
 __global__ __launch_bounds__(256) void k_tile_rows_h(const float *__restrict__ X, uint64_t n, uint32_t dim,
-                                                     uint64_t tile0, uint64_t tile1, float sx, uint4 *__restrict__ T) {
+                                                     uint64_t tile0, uint64_t tile1, float sx, uint4 *__restrict__ T,
+                                                     const uint32_t *__restrict__ tiles) {
     const uint32_t KB = ((dim + 63) & ~63u) / 32;
     uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;  // (tile, kb32, lane)
     uint64_t total = (tile1 - tile0) * KB * 64;
@@ -50,6 +52,7 @@ __global__ __launch_bounds__(256) void k_tile_rows_h(const float *__restrict__ X
     uint64_t tk = i >> 6;
     uint32_t kb = uint32_t(tk % KB);
     uint64_t tile = tile0 + tk / KB;
+    if (tiles) tile = tiles[tile];
     uint64_t row = tile * 16 + (l & 15);
     uint32_t col = kb * 32 + 8 * (l >> 4);
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
@@ -61,7 +64,14 @@ void launch_tile_rows_h(const float *X, uint64_t n, uint32_t dim, uint64_t tile0
     if (tile1 <= tile0) return;
     uint64_t total = (tile1 - tile0) * (mfma_dim_pad(dim) / 32) * 64;
     hipLaunchKernelGGL(k_tile_rows_h, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, X, n, dim, tile0, tile1, sx,
-                       reinterpret_cast<uint4 *>(T));
+                       reinterpret_cast<uint4 *>(T), (const uint32_t *)nullptr);
+}
+void launch_tile_rows_h_list(const float *X, uint64_t n, uint32_t dim, const uint32_t *tiles, uint64_t n_tiles, float sx, void *T,
+                             hipStream_t s) {
+    if (n_tiles == 0) return;
+    uint64_t total = n_tiles * (mfma_dim_pad(dim) / 32) * 64;
+    hipLaunchKernelGGL(k_tile_rows_h, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, X, n, dim, uint64_t(0), n_tiles, sx,
+                       reinterpret_cast<uint4 *>(T), tiles);
 }
 
 // the same rounding, row-major: H[i] = fp16(X[i] * sx) (the HNSW walk's pre-pass gathers whole rows; count % 8 == 0)

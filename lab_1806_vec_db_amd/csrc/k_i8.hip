@@ -164,10 +164,10 @@ template <bool COS>
 __global__ __launch_bounds__(256) void k_tile_rows_i8(const float *__restrict__ X, uint64_t n, uint32_t dim, uint64_t tile0,
                                                       const float *__restrict__ mu, float il1, float il2, uint4 *__restrict__ T,
                                                       float2 *__restrict__ rowc, float *__restrict__ stats, uint64_t stride,
-                                                      const float *__restrict__ xsq) {
+                                                      const float *__restrict__ xsq, const uint32_t *__restrict__ tiles) {
     const uint32_t KB = ((dim + 63) & ~63u) / 64;
     const uint32_t grp = threadIdx.x >> 4, sub = threadIdx.x & 15;
-    const uint64_t tile = tile0 + blockIdx.x;
+    const uint64_t tile = tiles ? uint64_t(tiles[blockIdx.x]) : tile0 + blockIdx.x;  // (the list form: Index::remove_rows)
     const uint64_t row = stats ? (uint64_t(blockIdx.x) * 16 + grp) * stride : tile * 16 + grp;
     const bool live = row < n;
     const float *v = X + (live ? row : 0) * dim;
@@ -225,10 +225,21 @@ void launch_tile_rows_i8(const float *X, uint64_t n, uint32_t dim, uint64_t tile
     if (tile1 <= tile0) return;
     if (xsq_cos)
         hipLaunchKernelGGL(k_tile_rows_i8<true>, dim3((unsigned)(tile1 - tile0)), dim3(256), 0, s, X, n, dim, tile0, mu, 1.0f / l1, 1.0f / l2,
-                           reinterpret_cast<uint4 *>(T), reinterpret_cast<float2 *>(rowc), (float *)nullptr, uint64_t(1), xsq_cos);
+                           reinterpret_cast<uint4 *>(T), reinterpret_cast<float2 *>(rowc), (float *)nullptr, uint64_t(1), xsq_cos, (const uint32_t *)nullptr);
     else
         hipLaunchKernelGGL(k_tile_rows_i8<false>, dim3((unsigned)(tile1 - tile0)), dim3(256), 0, s, X, n, dim, tile0, mu, 1.0f / l1, 1.0f / l2,
-                           reinterpret_cast<uint4 *>(T), reinterpret_cast<float2 *>(rowc), (float *)nullptr, uint64_t(1), (const float *)nullptr);
+                           reinterpret_cast<uint4 *>(T), reinterpret_cast<float2 *>(rowc), (float *)nullptr, uint64_t(1), (const float *)nullptr, (const uint32_t *)nullptr);
+}
+void launch_tile_rows_i8_list(const float *X, uint64_t n, uint32_t dim, const uint32_t *tiles, uint64_t n_tiles, const float *mu, float l1,
+                              float l2, void *T, float *rowc, hipStream_t s, const float *xsq_cos) {
+    if (n_tiles == 0) return;
+    if (xsq_cos)
+        hipLaunchKernelGGL(k_tile_rows_i8<true>, dim3((unsigned)n_tiles), dim3(256), 0, s, X, n, dim, uint64_t(0), mu, 1.0f / l1, 1.0f / l2,
+                           reinterpret_cast<uint4 *>(T), reinterpret_cast<float2 *>(rowc), (float *)nullptr, uint64_t(1), xsq_cos, tiles);
+    else
+        hipLaunchKernelGGL(k_tile_rows_i8<false>, dim3((unsigned)n_tiles), dim3(256), 0, s, X, n, dim, uint64_t(0), mu, 1.0f / l1, 1.0f / l2,
+                           reinterpret_cast<uint4 *>(T), reinterpret_cast<float2 *>(rowc), (float *)nullptr, uint64_t(1), (const float *)nullptr,
+                           tiles);
 }
 // |dx|^2 and |x_c|^2 of n_s rows taken `stride` apart: stats[2 i], stats[2 i + 1] (n_s rounded up to 16: the tail is zero)
 void launch_i8_row_stats(const float *X, uint64_t n, uint32_t dim, const float *mu, uint64_t n_s, uint64_t stride, float *stats,
@@ -236,10 +247,10 @@ void launch_i8_row_stats(const float *X, uint64_t n, uint32_t dim, const float *
     if (n_s == 0) return;
     if (xsq_cos)
         hipLaunchKernelGGL(k_tile_rows_i8<true>, dim3((unsigned)((n_s + 15) / 16)), dim3(256), 0, s, X, n, dim, uint64_t(0), mu, 1.0f, 1.0f,
-                           (uint4 *)nullptr, (float2 *)nullptr, stats, stride, xsq_cos);
+                           (uint4 *)nullptr, (float2 *)nullptr, stats, stride, xsq_cos, (const uint32_t *)nullptr);
     else
         hipLaunchKernelGGL(k_tile_rows_i8<false>, dim3((unsigned)((n_s + 15) / 16)), dim3(256), 0, s, X, n, dim, uint64_t(0), mu, 1.0f, 1.0f,
-                           (uint4 *)nullptr, (float2 *)nullptr, stats, stride, (const float *)nullptr);
+                           (uint4 *)nullptr, (float2 *)nullptr, stats, stride, (const float *)nullptr, (const uint32_t *)nullptr);
 }
 
 // ---- queries: |q|^2 in the reference's order (what the exact stage and the certification use, as k_query_prep_h), the

@@ -100,9 +100,11 @@ __device__ __forceinline__ void load8_padded(const float *row, uint32_t dim, uin
 
 // ---------------------------------------------------------------------------------------------------
 // rows [16*tile0, 16*tile1) of the row-major VecSet -> fragment-ordered split-bf16 mirror (rows >= n: zero)
+// tiles != null (the list form, Index::remove_rows): the tiles tiles[tile0 .. tile1) instead of tile0 .. tile1 themselves
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_tile_rows(const float *__restrict__ X, uint64_t n, uint32_t dim,
-                                                   uint64_t tile0, uint64_t tile1, uint4 *__restrict__ T) {
+                                                   uint64_t tile0, uint64_t tile1, uint4 *__restrict__ T,
+                                                   const uint32_t *__restrict__ tiles) {
     const uint32_t KB = ((dim + 63) & ~63u) / 32;
     uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;  // (tile, kb, lane)
     uint64_t total = (tile1 - tile0) * KB * 64;
@@ -111,6 +113,7 @@ __global__ __launch_bounds__(256) void k_tile_rows(const float *__restrict__ X, 
     uint64_t tk = i >> 6;
     uint32_t kb = uint32_t(tk % KB);
     uint64_t tile = tile0 + tk / KB;
+    if (tiles) tile = tiles[tile];
     uint64_t row = tile * 16 + (l & 15);
     uint32_t col = kb * 32 + 8 * (l >> 4);
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
@@ -126,7 +129,13 @@ void launch_tile_rows(const float *X, uint64_t n, uint32_t dim, uint64_t tile0, 
     if (tile1 <= tile0) return;
     uint64_t total = (tile1 - tile0) * (mfma_dim_pad(dim) / 32) * 64;
     hipLaunchKernelGGL(k_tile_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, X, n, dim, tile0, tile1,
-                       reinterpret_cast<uint4 *>(T));
+                       reinterpret_cast<uint4 *>(T), (const uint32_t *)nullptr);
+}
+void launch_tile_rows_list(const float *X, uint64_t n, uint32_t dim, const uint32_t *tiles, uint64_t n_tiles, float *T, hipStream_t s) {
+    if (n_tiles == 0) return;
+    uint64_t total = n_tiles * (mfma_dim_pad(dim) / 32) * 64;
+    hipLaunchKernelGGL(k_tile_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, X, n, dim, uint64_t(0), n_tiles,
+                       reinterpret_cast<uint4 *>(T), tiles);
 }
 
 // Q [nq][dim] -> per batch of 32 queries a B-operand image [kb][half][hi|lo][lane] (queries >= nq: zero)

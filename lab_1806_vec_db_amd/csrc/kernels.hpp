@@ -175,6 +175,9 @@ void launch_mfma_pack_queries(const float *Q, uint32_t nq, uint32_t nq_cover, ui
 // fragment-ordered mirror of rows: tiles [tile0, tile1) of 16 rows each; T holds ceil(n/16) tiles rounded up to 4
 void launch_tile_rows(const float *X, uint64_t n, uint32_t dim, uint64_t tile0, uint64_t tile1, float *T,
                       hipStream_t s);
+// the list forms of the three re-tiling kernels (launch_tile_rows, _h, _i8): the n_tiles tiles named by the device array `tiles`
+// (ascending, no duplicates), same bytes per tile as the range forms
+void launch_tile_rows_list(const float *X, uint64_t n, uint32_t dim, const uint32_t *tiles, uint64_t n_tiles, float *T, hipStream_t s);
 // approximate keys key(i,q) = xsq[i] - 2*dot(x_i, q); XT = fragment-ordered mirror; qfrag = nbatch images.
 // sample: keys of a strided sample of rows, dense: out[q*ld + j], j < mfma_sample_rows(n, step) (+inf past n)
 // cosine != 0: keys are -dot(x_i,q)/|x_i| (0 for zero rows), which rank like the cosine distance
@@ -210,6 +213,8 @@ bool gemm_f16_supported(uint32_t dim);
 // k_half.hip: scaled fp16 mirror / query images for the GEMM_F16 variant and their measured rounding errors
 void launch_tile_rows_h(const float *X, uint64_t n, uint32_t dim, uint64_t tile0, uint64_t tile1, float sx, void *T,
                         hipStream_t s);
+void launch_tile_rows_h_list(const float *X, uint64_t n, uint32_t dim, const uint32_t *tiles, uint64_t n_tiles, float sx, void *T,
+                             hipStream_t s);
 void launch_row_split_err(const float *X, const float *xsq, uint64_t row0, uint64_t row1, uint32_t dim, float sx,
                           uint32_t *out2 /* [2] float bits: max |dx|^2, max |dx|^2/|x|^2 (atomicMax) */, hipStream_t s);
 void launch_rows_to_half(const float *X, uint64_t count, float sx, uint16_t *H, hipStream_t s);
@@ -250,6 +255,11 @@ void launch_i8_row_stats(const float *X, uint64_t n, uint32_t dim, const float *
                          float *stats /* 2 * round_up(n_s, 16) */, hipStream_t s, const float *xsq_cos = nullptr);
 void launch_tile_rows_i8(const float *X, uint64_t n, uint32_t dim, uint64_t tile0, uint64_t tile1, const float *mu, float l1, float l2,
                          void *T, float *rowc, hipStream_t s, const float *xsq_cos = nullptr);
+void launch_tile_rows_i8_list(const float *X, uint64_t n, uint32_t dim, const uint32_t *tiles, uint64_t n_tiles, const float *mu, float l1,
+                              float l2, void *T, float *rowc, hipStream_t s, const float *xsq_cos = nullptr);
+// k_remove.hip: moves[2 j] = dst, [2 j + 1] = src -- row src -> row dst (row_bytes bytes each) and sq[src] -> sq[dst]; every src above
+// every dst (a removal plan, remove_plan.hpp)
+void launch_rows_move(void *rows, uint64_t row_bytes, float *sq, const uint32_t *moves, uint64_t n_moves, int num_cu, hipStream_t s);
 void launch_query_prep_i8(const float *Q, uint32_t nq, uint32_t nq_pad, uint32_t dim, const float *mu, float l1, float l2, float *qsq,
                           float *qscale, float *qoff, uint32_t *hits, void *qfrag, hipStream_t s, int cosine = 0);
 // k_redo.hip: second attempts of a Flat call

@@ -190,6 +190,25 @@ class GpuIndex:
     def swap_remove(self, i: int):
         L.check(self._lib.vdb_index_swap_remove(self._h, int(i)))
 
+    def remove_rows(self, rows):
+        """Remove many rows in one call (vdb_index_remove_rows): the state that swap_remove on every row of `rows`, in descending
+        order, would leave.  `rows` are local row ids in any order; a duplicate raises ValueError.  Returns (dst, src), u64 arrays: the
+        row that was at src[j] is now at dst[j], every other surviving row kept its place -- what a caller needs to permute whatever it
+        keeps per row (`meta[dst] = meta[src]`, then truncate)."""
+        a = np.asarray(rows).reshape(-1)
+        if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError("remove_rows: an array of integer row ids is needed")
+        if a.size and np.issubdtype(a.dtype, np.signedinteger) and int(a.min()) < 0:
+            raise ValueError("remove_rows: negative row id")
+        r = np.sort(a.astype(np.uint64))
+        if r.size > 1 and bool((r[1:] == r[:-1]).any()):
+            raise ValueError("remove_rows: duplicate row ids")
+        dst = np.zeros(r.size, dtype=np.uint64)
+        src = np.zeros(r.size, dtype=np.uint64)
+        moves = C.c_uint64()
+        L.check(self._lib.vdb_index_remove_rows(self._h, _ptr(r, L.u64p), r.size, _ptr(dst, L.u64p), _ptr(src, L.u64p), C.byref(moves)))
+        return dst[:int(moves.value)].copy(), src[:int(moves.value)].copy()
+
     def batch_add_u8(self, rows) -> int:
         """VecSet<u8> rows (widened exactly on the way in, distance/mod.rs:79-95)."""
         r = np.ascontiguousarray(rows, dtype=np.uint8)
@@ -631,6 +650,17 @@ def fold_probe(device: int = 0, adds: int = 1 << 22) -> float:
     v = C.c_double()
     L.check(L.load().vdb_fold_probe(int(device), int(adds), C.byref(v)))
     return float(v.value)
+
+
+def remove_plan(n: int, rows):
+    """(dst, src) of vdb_remove_plan: the moves that removing the strictly ascending `rows` from a table of n rows comes to -- the net
+    effect of swap_remove on them in descending order.  Pure host code; an unsorted, duplicate or out-of-range list raises VdbError."""
+    r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+    dst = np.zeros(r.size, dtype=np.uint64)
+    src = np.zeros(r.size, dtype=np.uint64)
+    moves = C.c_uint64()
+    L.check(L.load().vdb_remove_plan(int(n), _ptr(r, L.u64p), r.size, _ptr(dst, L.u64p), _ptr(src, L.u64p), C.byref(moves)))
+    return dst[:int(moves.value)].copy(), src[:int(moves.value)].copy()
 
 
 def merge_topk(dists: np.ndarray, ids: np.ndarray, counts: np.ndarray, k: int):

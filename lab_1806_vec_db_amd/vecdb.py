@@ -191,11 +191,11 @@ class VecDB:
             t.index.hnsw_clear()  # :170
             t.index.pq_clear()    # :171
             matches = [i for i, m in enumerate(t.metadata) if all(m.get(k) == v for k, v in pattern.items())]
-            for i in reversed(matches):
-                last = len(t.metadata) - 1
-                t.metadata[i] = t.metadata[last]
-                t.metadata.pop()
-                t.index.swap_remove(i)
+            if matches:  # one call; the metadata follow the moves it reports (the net effect of swap_remove in descending order)
+                dst, src = t.index.remove_rows(matches)
+                for d, s in zip(dst.tolist(), src.tolist()):
+                    t.metadata[d] = t.metadata[s]
+                del t.metadata[len(t.metadata) - len(matches):]
             return len(matches)
 
     def build_hnsw_index(self, key: str, ef_construction: int | None = None) -> None:
