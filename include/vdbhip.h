@@ -178,6 +178,23 @@ int vdb_range_destroy(vdb_range *r);
  * wherever the shape allows).  The call never touches the unfiltered search's auto-off counters.
  * vdb_get_stat: "flat_filtered_queries", "flat_filtered_direct_queries", "flat_filtered_i8_queries" (queries through the tier),
  * "flat_filtered_fallback_queries" (of those, handed on to the direct path); vdb_prof_get: "flat_filtered_scan", "flat_filtered_i8".
+ * vdb_flat_knn_filtered_multi: ONE MASK PER QUERY -- the multi-tenant batch.  Query q is answered exactly as vdb_flat_knn_filtered(idx,
+ * query q, 1, dim, k, masks[mask_of[q]], ..) answers it: the first min(k, m) pairs over that mask's allowed rows, bit-exact, ascending
+ * by (distance, id), out_count[q] = min(k, m of that mask), slots past the count zero, id_offset added.  `mask_of` is a HOST array of nq
+ * indexes into `masks` in both forms, in any order; a mask may serve any number of queries, none included.  Checked before anything is
+ * computed or written: EVERY mask of `masks` as for the single-mask call (another index: VDB_ERR_INVALID, stale: VDB_ERR_STATE),
+ * mask_of[q] >= n_masks (VDB_ERR_INVALID), a VecSet<u8> index (VDB_ERR_INVALID); the _device form refuses more than 32768 queries.
+ * nq == 0, k == 0 and n_masks == 0 with nq == 0 give empty results, a mask with m == 0 count 0 for its queries.  Read-side and
+ * re-entrant; the _device form synchronises `stream` first and returns synchronised; no auto-off counter is touched.
+ * How it is answered (csrc/multi_plan.hpp, k_filter.hip, docs/DESIGN_flat.md 4.1k): the queries are bucketed by mask on the host.
+ *   GROUPED direct path -- masks with m <= "flat_filtered_direct_max" when k <= 1024: all such buckets of the call are scanned by ONE
+ *   launch per chunk of queries (k_scan_gather_grouped: a workgroup per (mask, group of <= 8 of its queries, tile of 256 allowed rows)),
+ *   followed by one selection pass and one finalize for the chunk.
+ *   Single-mask machinery -- every other bucket (masks longer than "flat_filtered_direct_max", any mask when k > 1024): its queries are
+ *   gathered into a contiguous block, answered as vdb_flat_knn_filtered answers them (the 8-bit tier with the mask's row constants, or
+ *   the direct path) and scattered back.  vdb_flat_set_mode applies as above: with mode 1 long masks take the direct path per mask.
+ * The "flat_filtered_*" counters advance as if the per-mask calls had been made; "flat_filtered_multi_calls" counts these calls,
+ * "flat_filtered_grouped_queries" the queries the grouped launch answered; vdb_prof_get "flat_filtered_scan_grouped" is that kernel.
  * vdb_flat_range_filtered: vdb_flat_range over the allowed rows alone -- every ALLOWED row with D <= radius[q]; everything else as
  * documented there (f32 and VecSet<u8> indexes, the same tiers and counters).
  * Not covered: sharded and replica contexts, _begin / _end pipelining, filtered PQ / HNSW / IVF searches, k-NN on u8 indexes. */
@@ -189,6 +206,11 @@ int vdb_flat_knn_filtered(vdb_index *idx, const float *queries, uint64_t nq, uin
                           uint64_t *out_idx, float *out_dist, uint64_t *out_count);
 int vdb_flat_knn_filtered_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, const vdb_mask *mask,
                                  void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
+int vdb_flat_knn_filtered_multi(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, const vdb_mask *const *masks,
+                                uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx, float *out_dist, uint64_t *out_count);
+int vdb_flat_knn_filtered_multi_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k,
+                                       const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, void *d_out_idx,
+                                       void *d_out_dist, void *d_out_count, void *stream);
 int vdb_flat_range_filtered(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit,
                             const vdb_mask *mask, vdb_range **out);
 /* the approximate keys the Flat shortlist pass compares with its threshold, for EVERY row, from the same kernel in its dense

@@ -706,6 +706,92 @@ int vdb_flat_knn_filtered_device(vdb_index *idx, const void *d_queries, uint64_t
     VDB_API_END
 }
 
+// one mask per query: everything that can be refused is refused here, before anything is computed or written; -> the masks as RowMask pointers
+static std::vector<const RowMask *> filtered_multi_check(const Index &ix, uint64_t nq, const vdb_mask *const *masks, uint64_t n_masks,
+                                                         const uint32_t *mask_of) {
+    VDB_REQUIRE(!ix.elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    VDB_REQUIRE(n_masks == 0 || masks, "null masks");
+    VDB_REQUIRE(nq == 0 || mask_of, "null mask_of");
+    VDB_REQUIRE(n_masks < (1ull << 32), "too many masks");
+    std::vector<const RowMask *> rm(n_masks);
+    for (uint64_t g = 0; g < n_masks; g++) {
+        VDB_REQUIRE(masks[g], "null mask");
+        ix.check_mask(masks[g]->m);
+        rm[g] = &masks[g]->m;
+    }
+    for (uint64_t q = 0; q < nq; q++)
+        VDB_REQUIRE(mask_of[q] < n_masks, "mask_of[" + std::to_string(q) + "] = " + std::to_string(mask_of[q]) + ": the call has " +
+                                              std::to_string(n_masks) + " masks");
+    return rm;
+}
+
+int vdb_flat_knn_filtered_multi(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, const vdb_mask *const *masks,
+                                uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx, float *out_dist, uint64_t *out_count) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_query_args(ix, queries, nq, dim, out_idx, out_dist);
+    const std::vector<const RowMask *> rm = filtered_multi_check(ix, nq, masks, n_masks, mask_of);
+    ix.filtered_multi_calls++;
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    hipStream_t s = ws->stream;
+    constexpr uint64_t CHUNK = 16384;
+    const uint64_t kk = std::max<uint64_t>(k, 1), ch = std::min(nq, CHUNK);
+    // one device block for the outputs of a chunk [ids | distances | counts], as vdb_flat_knn_filtered lays them out
+    const size_t off_d = ch * kk * sizeof(uint64_t), off_c = (off_d + ch * kk * sizeof(float) + 7) & ~size_t(7);
+    ws->q.reserve(ch * dim * sizeof(float));
+    ws->out_idx.reserve(off_c + ch * sizeof(uint64_t));
+    char *d_out = ws->out_idx.as<char>();
+    try {
+        for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
+            const uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
+            VDB_HIP(hipMemcpyAsync(ws->q.p, queries + q0 * dim, nb * dim * sizeof(float), hipMemcpyHostToDevice, s));
+            ix.flat_knn_masked_multi_device(*ws, ws->q.as<float>(), nb, k, rm.data(), n_masks, mask_of + q0, reinterpret_cast<uint64_t *>(d_out),
+                                            reinterpret_cast<float *>(d_out + off_d), reinterpret_cast<uint64_t *>(d_out + off_c));
+            if (k) {
+                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
+            }
+            if (out_count) VDB_HIP(hipMemcpyAsync(out_count + q0, d_out + off_c, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            VDB_SYNC(s);
+        }
+    } catch (...) {
+        (void)hipStreamSynchronize(s);  // nothing of a failed call is still running when its buffers go
+        ix.prof_collect(*ws);
+        throw;
+    }
+    ix.prof_collect(*ws);
+    VDB_API_END
+}
+
+int vdb_flat_knn_filtered_multi_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, const vdb_mask *const *masks,
+                                       uint64_t n_masks, const uint32_t *mask_of, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_query_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist);
+    VDB_REQUIRE(nq == 0 || d_out_count, "null out_count");
+    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
+    const std::vector<const RowMask *> rm = filtered_multi_check(ix, nq, masks, n_masks, mask_of);
+    ix.filtered_multi_calls++;
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
+    try {
+        ix.flat_knn_masked_multi_device(*ws, static_cast<const float *>(d_queries), nq, k, rm.data(), n_masks, mask_of, static_cast<uint64_t *>(d_out_idx),
+                                        static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
+    } catch (...) {
+        (void)hipStreamSynchronize(ws->stream);
+        ix.prof_collect(*ws);
+        throw;
+    }
+    ix.prof_collect(*ws);
+    VDB_API_END
+}
+
 int vdb_flat_range_filtered(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit, const vdb_mask *mask,
                             vdb_range **out) {
     VDB_API_BEGIN
@@ -936,6 +1022,10 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.filtered_i8_queries.load();
     else if (n == "flat_filtered_fallback_queries")
         *out = idx->ix.filtered_fallback_queries.load();
+    else if (n == "flat_filtered_multi_calls")  // calls with a mask per query | queries their grouped launch answered
+        *out = idx->ix.filtered_multi_calls.load();
+    else if (n == "flat_filtered_grouped_queries")
+        *out = idx->ix.filtered_grouped_queries.load();
     else if (n.rfind("flat_i8_rounds_", 0) == 0 && n.size() == 16 && n[15] >= '0' && n[15] <= '8')  // queries whose exact stage walked N rounds (8: 8 or more)
         *out = idx->ix.i8_rounds_hist[n[15] - '0'].load();
     else if (n == "mirror_alloc_failures")  // mirrors of this index whose allocation failed (the tier was left to the next one)

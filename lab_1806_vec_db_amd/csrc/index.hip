@@ -1,5 +1,6 @@
 // index.hip -- Index object: HBM-resident VecSet + the Flat search pipeline.
 #include "index.hpp"
+#include "multi_plan.hpp"
 #include "remove_plan.hpp"
 
 #include <algorithm>
@@ -1388,6 +1389,117 @@ void Index::flat_knn_masked_device(Workspace &ws, const float *d_q, uint64_t nq,
     VDB_HIP(hipMemsetAsync(r.rc.p, 0, r.nr * sizeof(uint64_t), s));
     flat_masked_direct(ws, r.rq.as<float>(), r.nr, k, mask, r.ri.as<uint64_t>(), r.rd.as<float>(), r.rc.as<uint64_t>());
     r.scatter(d_idx, d_dist, d_cnt, s);  // (its sync: before `redo` goes out of scope)
+}
+
+// ---- Flat: exact filtered k-NN with one row mask per query (k_filter.hip, multi_plan.hpp) ------------------------------------------------
+// Query q is answered as flat_knn_masked_device answers it alone under masks[mask_of[q]].  The queries are bucketed by mask on the host:
+//   per-mask route: a bucket whose mask is longer than flat_filtered_direct_max (or any bucket when k > 1024) is gathered into a block of
+//     its own, goes through flat_knn_masked_device as it stands -- the 8-bit tier with that mask's row constants, or the direct path --
+//     and is scattered back (RedoSet).
+//   grouped route: every other bucket.  multi_plan lays them out as slots and cuts the slots into chunks; a chunk is ONE launch of
+//     k_scan_gather_grouped over all its (mask, query group, tile) work items into a dense matrix of leading dimension ld = the chunk's
+//     largest m rounded up to 64, ONE selection over (ld, max m) and ONE finalize.  Padding: the matrix is filled with 0xFF bytes first,
+//     so a slot's columns at and past its own m hold a NaN; pair_key canonicalises every NaN to one orderable image, the greatest
+//     (common.hpp), so (NaN, column j >= m) sorts behind every real key of that slot -- a real NaN included, whose column is smaller --
+//     and the real keys are a prefix of the slot's sorted row.  k_topk_dense / k_topk_merge compare whole u64 keys and treat only
+//     PAIR_NONE (~0, which no column below 2^32 - 1 produces) specially; k_filter_finalize_grouped cuts at column < m.
+// The caller has checked every mask and every mask_of entry.  Returns synchronised; touches no auto-off counter.
+void Index::flat_knn_masked_multi_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, const RowMask *const *masks, uint64_t n_masks,
+                                         const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
+    hipStream_t s = ws.stream;
+    VDB_REQUIRE(!elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 32) && k < (1ull << 31), "flat knn: too many queries or k too large");
+    if (k == 0) {
+        filtered_queries += nq;
+        filtered_direct_queries += nq;
+        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
+        VDB_SYNC(s);
+        return;
+    }
+    std::vector<uint64_t> m_of(n_masks);
+    std::vector<uint8_t> grouped(n_masks);
+    for (uint64_t g = 0; g < n_masks; g++) {
+        m_of[g] = masks[g]->m;
+        grouped[g] = k <= 1024 && m_of[g] <= flat_filtered_direct_max;
+    }
+    // per-mask route first: every such call returns synchronised, so the grouped route's reserves below free nothing in use
+    {
+        std::vector<std::vector<uint64_t>> bucket(n_masks);
+        for (uint64_t q = 0; q < nq; q++)
+            if (!grouped[mask_of[q]]) bucket[mask_of[q]].push_back(q);
+        for (uint64_t g = 0; g < n_masks; g++) {
+            if (bucket[g].empty()) continue;
+            RedoSet r(bucket[g], d_q, dim, k, s);
+            VDB_HIP(hipMemsetAsync(r.rc.p, 0, r.nr * sizeof(uint64_t), s));
+            flat_knn_masked_device(ws, r.rq.as<float>(), r.nr, k, *masks[g], r.ri.as<uint64_t>(), r.rd.as<float>(), r.rc.as<uint64_t>());
+            r.scatter(d_idx, d_dist, d_cnt, s);
+        }
+    }
+    const uint64_t max_m = multi_plan_max_m(m_of.data(), grouped.data(), n_masks, mask_of, nq);
+    const uint64_t ksel_all = std::min<uint64_t>(k, max_m);
+    const uint64_t list_bytes = ksel_all ? uint64_t(topk_num_lists(max_m)) * topk_capacity((uint32_t)ksel_all) * sizeof(uint64_t) : 64;
+    constexpr uint64_t BUDGET = 256ull << 20;  // bytes of the dense matrix (and of the selection's lists) per chunk, as in flat_masked_direct
+    MultiPlan plan;
+    multi_plan(m_of.data(), grouped.data(), n_masks, mask_of, nq, BUDGET, list_bytes, plan);
+    const uint64_t ns = plan.slot_query.size();
+    if (ns == 0) return;
+    filtered_queries += ns;
+    filtered_direct_queries += ns;
+    filtered_grouped_queries += ns;
+    const int metric = dist == 0 ? MET_L2_DIRECT : MET_COSINE;
+    // device image of the plan: [slot_ids (8 B) | items (24 B) | slot_q | slot_m], one upload for the call
+    std::vector<GroupedItem> h_items(plan.items.size());
+    for (size_t i = 0; i < h_items.size(); i++) {
+        const MultiItem &it = plan.items[i];
+        h_items[i] = GroupedItem{masks[it.mask]->d_ids.as<uint32_t>(), (uint32_t)m_of[it.mask], it.tile, it.slot, it.nb};
+    }
+    std::vector<const uint32_t *> h_ids(ns);
+    std::vector<uint32_t> h_m(ns);
+    for (uint64_t i = 0; i < ns; i++) {
+        h_ids[i] = masks[plan.slot_mask[i]]->d_ids.as<uint32_t>();
+        h_m[i] = (uint32_t)m_of[plan.slot_mask[i]];
+    }
+    static_assert(sizeof(GroupedItem) % 8 == 0, "the items follow the pointer array");
+    const size_t off_items = ns * sizeof(uint32_t *), off_q = off_items + h_items.size() * sizeof(GroupedItem), off_m = off_q + ns * sizeof(uint32_t);
+    // every buffer of the call reserved before its first launch (a later, larger reserve would free a buffer in use)
+    ws.misc.reserve(off_m + ns * sizeof(uint32_t));
+    ws.qsq.reserve(nq * sizeof(float));
+    const uint64_t ld_all = (max_m + 63) & ~63ull;
+    const uint64_t qch = std::min(plan.qch, ns);
+    if (ksel_all) {
+        ws.dense.reserve(qch * ld_all * sizeof(float));
+        ws.lists.reserve(qch * list_bytes);
+        ws.keys_c.reserve(qch * topk_capacity((uint32_t)ksel_all) * sizeof(uint64_t));
+    }
+    char *d_plan = ws.misc.as<char>();
+    VDB_HIP(hipMemcpyAsync(d_plan, h_ids.data(), ns * sizeof(uint32_t *), hipMemcpyHostToDevice, s));
+    if (!h_items.empty()) VDB_HIP(hipMemcpyAsync(d_plan + off_items, h_items.data(), h_items.size() * sizeof(GroupedItem), hipMemcpyHostToDevice, s));
+    VDB_HIP(hipMemcpyAsync(d_plan + off_q, plan.slot_query.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    VDB_HIP(hipMemcpyAsync(d_plan + off_m, h_m.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    const uint32_t *const *d_slot_ids = reinterpret_cast<const uint32_t *const *>(d_plan);
+    const GroupedItem *d_items = reinterpret_cast<const GroupedItem *>(d_plan + off_items);
+    const uint32_t *d_slot_q = reinterpret_cast<const uint32_t *>(d_plan + off_q), *d_slot_m = reinterpret_cast<const uint32_t *>(d_plan + off_m);
+    launch_row_sqnorm(d_q, nq, (uint32_t)dim, ws.qsq.as<float>(), s);
+    for (const MultiChunk &c : plan.chunks) {
+        const uint32_t nb = (uint32_t)c.nslots;
+        const uint64_t ksel = std::min<uint64_t>(k, c.max_m);
+        uint32_t cap = 0;
+        if (ksel) {
+            const uint32_t nl = topk_num_lists(c.max_m);
+            cap = topk_capacity((uint32_t)ksel);
+            VDB_HIP(hipMemsetAsync(ws.dense.p, 0xFF, uint64_t(nb) * c.ld * sizeof(float), s));  // padding columns: NaN, behind every real key
+            prof_begin(ws, "flat_filtered_scan_grouped", double(c.rows) * dim * sizeof(float));
+            launch_scan_gather_grouped(d_rows.as<float>(), (uint32_t)dim, d_items + c.item0, c.nitems, d_slot_q + c.slot0, d_q, metric, d_sq.as<float>(),
+                                       ws.qsq.as<float>(), ws.dense.as<float>(), c.ld, s);
+            prof_end(ws);
+            launch_topk_dense(ws.dense.as<float>(), c.ld, c.max_m, nb, (uint32_t)ksel, ws.lists.as<uint64_t>(), s);
+            launch_topk_merge(ws.lists.as<uint64_t>(), nl, cap, nb, (uint32_t)ksel, ws.keys_c.as<uint64_t>(), s);
+        }
+        launch_filter_finalize_grouped(ws.keys_c.as<uint64_t>(), cap, nb, (uint32_t)ksel, (uint32_t)k, d_slot_ids + c.slot0, d_slot_m + c.slot0,
+                                       d_slot_q + c.slot0, id_offset, d_idx, d_dist, d_cnt, s);
+    }
+    VDB_SYNC(s);  // (the plan's host arrays are pageable memory: alive until here)
 }
 
 // ---- the approximate keys of the Flat shortlist pass, for every row ------------------------------------------------

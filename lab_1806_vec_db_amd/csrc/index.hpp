@@ -503,11 +503,17 @@ struct Index {
                                 uint64_t *d_cnt);
     void flat_masked_direct(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, const RowMask &mask, uint64_t *d_idx, float *d_dist,
                             uint64_t *d_cnt);  // enqueues; the caller synchronises
+    // The same with one mask per query (multi_plan.hpp): query q under masks[mask_of[q]] (mask_of: host).  The buckets of masks of at most
+    // flat_filtered_direct_max rows (k <= 1024) are scanned by one k_scan_gather_grouped launch per chunk of queries; every other bucket
+    // goes through flat_knn_masked_device, gathered and scattered back.  The caller has checked the masks and mask_of; returns synchronised.
+    void flat_knn_masked_multi_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, const RowMask *const *masks, uint64_t n_masks,
+                                      const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
     void check_mask(const RowMask &mask) const;  // throws: a mask of another index (invalid argument), a stale mask (state)
     const float *masked_rowc(Workspace &ws, const RowMask &mask);  // after ensure_i8 succeeded; builds the copy on first use
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};
+    std::atomic<uint64_t> filtered_multi_calls{0}, filtered_grouped_queries{0};  // calls with a mask per query / queries their grouped launch answered
     uint64_t range_max_results = 0;  // ceiling on the pairs of one call ("flat_range_max_results"; 0: what the device can hold)
     std::atomic<uint64_t> range_queries{0}, range_i8_queries{0}, range_scan_queries{0}, range_hits{0}, range_results{0};
     std::atomic<uint64_t> range_hits_max{0};  // longest hit list of a query the tier answered

@@ -257,6 +257,126 @@ void launch_filter_finalize(const uint64_t *keys, uint64_t ldk, uint32_t nq, uin
 }
 
 // ---------------------------------------------------------------------------------------------
+// gathered scan over MANY allow-lists in one launch (one mask per query: Index::flat_knn_masked_multi_device, multi_plan.hpp).
+// One workgroup per work item = (a mask's id list, one tile of 256 of its rows, nb <= 8 slots of that mask's bucket); thread t folds
+// column tile * 256 + t for the item's nb queries with the statements of k_scan_gather_simple -- the same fold1 / epilogue, ascending in
+// the dimension, so the same bits.  The item and everything reached through it (the id list's base, the slots' query rows) are indexed by
+// blockIdx alone: wave-uniform, read by scalar loads.  Nothing is written but out[(slot + b) * ld + j], j < m.
+// Two folds, like the simple variant: float4 fetches of the row when dim % 4 == 0, element by element otherwise.
+// ---------------------------------------------------------------------------------------------
+template <int BQ, int FOLD>
+__device__ __forceinline__ void scan_grouped_body(const float *__restrict__ x, uint32_t r, uint64_t j, uint32_t dim, const uint32_t *__restrict__ sq,
+                                                  const float *__restrict__ Q, int metric, const float *__restrict__ xsq,
+                                                  const float *__restrict__ qsq, float *__restrict__ out, uint64_t ld) {
+    const float *qp[BQ];
+#pragma unroll
+    for (int b = 0; b < BQ; b++) qp[b] = Q + uint64_t(sq[b]) * dim;  // wave-uniform
+    float acc[BQ];
+#pragma unroll
+    for (int b = 0; b < BQ; b++) acc[b] = 0.0f;
+    if ((dim & 3) == 0) {
+        const float4 *x4 = reinterpret_cast<const float4 *>(x);
+        for (uint32_t c = 0; c < dim / 4; c++) {
+            float4 v = x4[c];
+#pragma unroll
+            for (int b = 0; b < BQ; b++) {
+                const float *q = qp[b] + 4 * c;
+                acc[b] = fold1<FOLD>(acc[b], v.x, q[0]);
+                acc[b] = fold1<FOLD>(acc[b], v.y, q[1]);
+                acc[b] = fold1<FOLD>(acc[b], v.z, q[2]);
+                acc[b] = fold1<FOLD>(acc[b], v.w, q[3]);
+            }
+        }
+    } else {
+        for (uint32_t c = 0; c < dim; c++) {
+            float v = x[c];
+#pragma unroll
+            for (int b = 0; b < BQ; b++) acc[b] = fold1<FOLD>(acc[b], v, qp[b][c]);
+        }
+    }
+    float xs = (metric == MET_L2_DIRECT) ? 0.0f : xsq[r];
+#pragma unroll
+    for (int b = 0; b < BQ; b++) {
+        float qs = (metric == MET_L2_DIRECT) ? 0.0f : qsq[sq[b]];
+        out[uint64_t(b) * ld + j] = epilogue(metric, acc[b], xs, qs);
+    }
+}
+
+template <int FOLD>
+__global__ __launch_bounds__(256) void k_scan_gather_grouped(const float *__restrict__ X, uint32_t dim, const GroupedItem *__restrict__ items,
+                                                             const uint32_t *__restrict__ slot_q, const float *__restrict__ Q, int metric,
+                                                             const float *__restrict__ xsq, const float *__restrict__ qsq, float *__restrict__ out,
+                                                             uint64_t ld) {
+    const GroupedItem it = items[blockIdx.x];
+    const uint64_t j = uint64_t(it.tile) * 256 + threadIdx.x;
+    if (j >= it.m) return;
+    const uint32_t r = it.ids[j];
+    const float *x = X + uint64_t(r) * dim;
+    const uint32_t *sq = slot_q + it.slot;
+    float *o = out + uint64_t(it.slot) * ld;
+    switch (it.nb) {  // wave-uniform
+        case 1: scan_grouped_body<1, FOLD>(x, r, j, dim, sq, Q, metric, xsq, qsq, o, ld); break;
+        case 2: scan_grouped_body<2, FOLD>(x, r, j, dim, sq, Q, metric, xsq, qsq, o, ld); break;
+        case 3: scan_grouped_body<3, FOLD>(x, r, j, dim, sq, Q, metric, xsq, qsq, o, ld); break;
+        case 4: scan_grouped_body<4, FOLD>(x, r, j, dim, sq, Q, metric, xsq, qsq, o, ld); break;
+        case 5: scan_grouped_body<5, FOLD>(x, r, j, dim, sq, Q, metric, xsq, qsq, o, ld); break;
+        case 6: scan_grouped_body<6, FOLD>(x, r, j, dim, sq, Q, metric, xsq, qsq, o, ld); break;
+        case 7: scan_grouped_body<7, FOLD>(x, r, j, dim, sq, Q, metric, xsq, qsq, o, ld); break;
+        case 8: scan_grouped_body<8, FOLD>(x, r, j, dim, sq, Q, metric, xsq, qsq, o, ld); break;
+        default: break;
+    }
+}
+
+void launch_scan_gather_grouped(const float *X, uint32_t dim, const GroupedItem *items, uint64_t nitems, const uint32_t *slot_q, const float *Q,
+                                int metric, const float *xsq, const float *qsq, float *out, uint64_t ld, hipStream_t s) {
+    if (nitems == 0) return;
+    VDB_REQUIRE(metric == MET_L2_DIRECT || metric == MET_COSINE, "scan_gather_grouped: metric");
+    VDB_REQUIRE(nitems < (1ull << 31), "scan_gather_grouped: too many work items");
+    dim3 grid((unsigned)nitems), block(256);
+    if (metric == MET_L2_DIRECT)
+        hipLaunchKernelGGL((k_scan_gather_grouped<FOLD_L2>), grid, block, 0, s, X, dim, items, slot_q, Q, metric, xsq, qsq, out, ld);
+    else
+        hipLaunchKernelGGL((k_scan_gather_grouped<FOLD_DOT>), grid, block, 0, s, X, dim, items, slot_q, Q, metric, xsq, qsq, out, ld);
+    VDB_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------
+// twin of k_filter_finalize for a chunk of slots with a list of their own each: slot s = query slot_q[s] of the call, the columns of its
+// keys index slot_ids[s], slot_m[s] of them are real.  A padding column (>= slot_m[s]) carries a NaN distance and sorts behind every
+// real column, so the real keys are a prefix of the sorted row and the cut is `column < slot_m[s]`.  Every one of the query's kstride
+// output slots is written (zero past the count), and its count.
+// ---------------------------------------------------------------------------------------------
+__global__ void k_filter_finalize_grouped(const uint64_t *__restrict__ keys, uint64_t ldk, uint32_t ksel, uint32_t kstride,
+                                          const uint32_t *const *__restrict__ slot_ids, const uint32_t *__restrict__ slot_m,
+                                          const uint32_t *__restrict__ slot_q, uint64_t id_offset, uint64_t *__restrict__ out_idx,
+                                          float *__restrict__ out_dist, uint64_t *__restrict__ out_count) {
+    const uint32_t sl = blockIdx.x;
+    const uint32_t q = slot_q[sl], mg = slot_m[sl];
+    const uint32_t *ids = slot_ids[sl];
+    uint32_t cnt = 0;
+    for (uint32_t j = threadIdx.x; j < kstride; j += blockDim.x) {
+        const uint64_t c = j < ksel ? keys[uint64_t(sl) * ldk + j] : PAIR_NONE;
+        const bool ok = c != PAIR_NONE && uint32_t(c) < mg;
+        out_idx[uint64_t(q) * kstride + j] = ok ? uint64_t(ids[uint32_t(c)]) + id_offset : 0;
+        out_dist[uint64_t(q) * kstride + j] = ok ? f32_from_orderable(uint32_t(c >> 32)) : 0.0f;
+        cnt += ok;
+    }
+    __shared__ uint32_t total;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    atomicAdd(&total, cnt);
+    __syncthreads();
+    if (threadIdx.x == 0) out_count[q] = total;
+}
+void launch_filter_finalize_grouped(const uint64_t *keys, uint64_t ldk, uint32_t nslots, uint32_t ksel, uint32_t kstride, const uint32_t *const *slot_ids,
+                                    const uint32_t *slot_m, const uint32_t *slot_q, uint64_t id_offset, uint64_t *out_idx, float *out_dist,
+                                    uint64_t *out_count, hipStream_t s) {
+    if (nslots == 0) return;
+    hipLaunchKernelGGL(k_filter_finalize_grouped, dim3(nslots), dim3(64), 0, s, keys, ldk, ksel, kstride, slot_ids, slot_m, slot_q, id_offset, out_idx,
+                       out_dist, out_count);
+}
+
+// ---------------------------------------------------------------------------------------------
 // masked copy of the 8-bit pass's row constants: {+inf, 0} where the bit is clear, the index's own pair elsewhere (rows in
 // [n, rows_pad) have no bit and are copied: they carry {+inf, 0} already)
 // ---------------------------------------------------------------------------------------------

@@ -303,6 +303,23 @@ void launch_scan_gather(const float *X, const uint32_t *ids, uint64_t m, uint32_
 // launch_finalize for pair keys whose low word is a COLUMN of that output: the id written is ids[column] + id_offset
 void launch_filter_finalize(const uint64_t *keys, uint64_t ldk, uint32_t nq, uint32_t ksel, uint32_t kstride, const uint32_t *ids, uint64_t m,
                             uint64_t id_offset, uint64_t *out_idx, float *out_dist, uint64_t *out_count, hipStream_t s);
+// The gathered scan for MANY (mask, query group) pairs in one launch (Index::flat_knn_masked_multi_device, multi_plan.hpp): one workgroup
+// per work item.  An item's queries are the slots [slot, slot + nb) of the chunk, slot s being query slot_q[s] of Q / qsq and row s of out.
+struct GroupedItem {
+    const uint32_t *ids;  // the mask's ascending allow-list (device)
+    uint32_t m;           // its length
+    uint32_t tile;        // the item's allowed rows: columns [tile * 256, min(m, tile * 256 + 256))
+    uint32_t slot;        // first slot
+    uint32_t nb;          // 1..8 slots
+};
+// out[(slot + b) * ld + j] = D(row ids[j], query slot_q[slot + b]) for every item, b < nb and column j of its tile; any dim
+void launch_scan_gather_grouped(const float *X, uint32_t dim, const GroupedItem *items, uint64_t nitems, const uint32_t *slot_q, const float *Q,
+                                int metric, const float *xsq, const float *qsq, float *out, uint64_t ld, hipStream_t s);
+// launch_filter_finalize with a list, a length and an output position per slot: slot s holds the keys of query slot_q[s] over the columns
+// of slot_ids[s] (slot_m[s] of them); columns at and past slot_m[s] are padding.  Writes all kstride slots and the count of that query.
+void launch_filter_finalize_grouped(const uint64_t *keys, uint64_t ldk, uint32_t nslots, uint32_t ksel, uint32_t kstride, const uint32_t *const *slot_ids,
+                                    const uint32_t *slot_m, const uint32_t *slot_q, uint64_t id_offset, uint64_t *out_idx, float *out_dist,
+                                    uint64_t *out_count, hipStream_t s);
 // out[r] = bit r of `bits` set or r >= n ? rowc[r] : {+inf, 0}, r < rows_pad (the {C_r, M_r} pairs of the 8-bit pass)
 void launch_mask_rowc(const float *rowc, const uint64_t *bits, uint64_t n, uint64_t rows_pad, float *out, hipStream_t s);
 // tau[q] = min(tau[q], FLT_MAX), NaN -> -inf: no threshold lets the +inf key of a masked row through

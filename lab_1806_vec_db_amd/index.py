@@ -296,6 +296,42 @@ class GpuIndex:
         L.check(self._lib.vdb_flat_knn_filtered_device(self._h, L.vp(q_ptr), int(nq), self.dim, int(k), mask._h, L.vp(out_idx_ptr),
                                                        L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
 
+    @staticmethod
+    def _mask_args(masks, mask_of, nq: int):
+        """(the vdb_mask* array, its length, mask_of as contiguous u32) of a call with one mask per query"""
+        masks = list(masks)
+        mo = np.ascontiguousarray(np.asarray(mask_of).reshape(-1), dtype=np.uint32)
+        if mo.shape[0] != nq:
+            raise ValueError(f"mask_of: one entry per query is needed ({nq}), got {mo.shape[0]}")
+        arr = (L.vp * max(len(masks), 1))(*[mk._h for mk in masks])
+        return arr, len(masks), mo
+
+    def flat_knn_filtered_multi(self, queries, k: int, masks, mask_of):
+        """flat_knn_filtered with ONE MASK PER QUERY (vdb_flat_knn_filtered_multi): query q is answered under masks[mask_of[q]], exactly
+        as flat_knn_filtered(queries[q], k, masks[mask_of[q]]) answers it; the buckets of short masks share one scan launch.  `masks`: a
+        sequence of RowMask of this index, `mask_of`: nq indexes into it, in any order.  Same return shapes as flat_knn_filtered."""
+        q = _f32(queries)
+        single = q.ndim == 1
+        q = q.reshape(1, -1) if single else q
+        nq, dim = q.shape
+        arr, n_masks, mo = self._mask_args(masks, mask_of, nq)
+        kk = max(int(k), 1)
+        idx = np.zeros((nq, kk), dtype=np.uint64)
+        dist = np.zeros((nq, kk), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint64)
+        L.check(self._lib.vdb_flat_knn_filtered_multi(self._h, _ptr(q, L.f32p), nq, dim, int(k), arr, n_masks, _ptr(mo, L.u32p), _ptr(idx, L.u64p),
+                                                      _ptr(dist, L.f32p), _ptr(cnt, L.u64p)))
+        if single:
+            c = int(cnt[0])
+            return idx[0, :c].copy(), dist[0, :c].copy()
+        return idx[:, :int(k)], dist[:, :int(k)], cnt
+
+    def flat_knn_filtered_multi_device(self, q_ptr: int, nq: int, k: int, masks, mask_of, out_idx_ptr: int, out_dist_ptr: int, out_cnt_ptr: int,
+                                       stream: int = 0):
+        arr, n_masks, mo = self._mask_args(masks, mask_of, int(nq))
+        L.check(self._lib.vdb_flat_knn_filtered_multi_device(self._h, L.vp(q_ptr), int(nq), self.dim, int(k), arr, n_masks, _ptr(mo, L.u32p),
+                                                             L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
+
     def _range_out(self, h, nq: int):
         return read_range(self._lib, h, nq)
 

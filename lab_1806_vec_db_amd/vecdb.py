@@ -15,7 +15,8 @@ Semantics reproduced from src/database/metadata_vec_table.rs:
     `distance <= upper_bound` filter.
 
 Beyond the reference: search_within(key, query, upper_bound) returns the COMPLETE set inside the bound (exact Flat range search);
-search / search_within take `filter`, a metadata pattern matched as delete matches: only matching rows are searched, exactly.
+search / search_within take `filter`, a metadata pattern matched as delete matches: only matching rows are searched, exactly;
+batch_search(key, queries, k, ..., filters) answers a batch of queries, each under a pattern of its own, in one library call.
 """
 from __future__ import annotations
 
@@ -271,6 +272,46 @@ class VecDB:
                 idx, dist = ix.knn(q, k)
             ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
             return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist) if d <= ub]
+
+    def batch_search(self, key: str, queries, k: int, ef: int | None = None, upper_bound: float | None = None, filters=None):
+        """search for a batch of queries in ONE library call: entry q of the returned list is what search(key, queries[q], k, ef,
+        upper_bound, filter) returns.  `filters`: None, ONE metadata pattern for every query, or a list of len(queries) patterns (the
+        multi-tenant batch: every query restricted to its own rows; {} matches every row).  With filters the answers are exact, from
+        the table's Flat rows, through one flat_knn_filtered_multi call over one mask per distinct pattern; without, the batch is
+        dispatched as search dispatches a query (knn_pq, knn_with_ef or knn)."""
+        t = self._t(key)
+        ix = t.index
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != ix.dim:
+            raise RuntimeError(f"Dimension mismatch: table dim {ix.dim}, got {q.shape}")
+        nq = q.shape[0]
+        if filters is not None and not isinstance(filters, dict):
+            filters = list(filters)
+            if len(filters) != nq:
+                raise RuntimeError(f"filters: one pattern per query is needed ({nq}), got {len(filters)}")
+        if nq == 0:
+            return []
+        with t.lock.read():  # one read guard for the whole batch, mask building and metadata lookup included
+            if filters is not None:
+                pats = [filters] * nq if isinstance(filters, dict) else filters
+                slot: dict[frozenset, int] = {}
+                masks, mask_of = [], np.zeros(nq, dtype=np.uint32)
+                for i, p in enumerate(pats):
+                    pk = frozenset(p.items())
+                    if pk not in slot:
+                        slot[pk] = len(masks)
+                        masks.append(t.mask_for(p))
+                    mask_of[i] = slot[pk]
+                idx, dist, cnt = ix.flat_knn_filtered_multi(q, k, masks, mask_of)
+            elif ef is not None and ix.has_pq():
+                idx, dist, cnt = ix.knn_pq(q, k, ef)
+            elif ef is not None:
+                idx, dist, cnt = ix.knn_with_ef(q, k, ef)
+            else:
+                idx, dist, cnt = ix.knn(q, k)
+            ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
+            return [[(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx[j, :int(cnt[j])], dist[j, :int(cnt[j])]) if d <= ub]
+                    for j in range(nq)]
 
     def search_within(self, key: str, query, upper_bound: float, limit: int | None = None, filter: dict[str, str] | None = None):
         """Every row within `upper_bound` of the query (distance <= upper_bound, as search's filter compares), nearest first: what

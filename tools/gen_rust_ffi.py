@@ -40,18 +40,22 @@ def c_decls(header: str | None = None):
 
 def rust_type(ctype: str) -> str:
     toks = ctype.split()
-    stars = toks.count("*")
-    toks = [t for t in toks if t != "*"]
-    const = "const" in toks
-    base = [t for t in toks if t not in ("const", "struct")]
+    first = toks.index("*") if "*" in toks else len(toks)
+    head, tail = toks[:first], toks[first:]
+    const = "const" in head
+    base = [t for t in head if t not in ("const", "struct")]
     assert len(base) == 1, ctype
     b = OPAQUE.get(base[0]) or SCALAR[base[0]]
-    if stars == 0:
-        return b
     inner = b
-    for level in range(stars):
-        # the innermost pointer carries the const of the pointee; outer levels are `*mut` (out-parameters)
-        inner = ("*const " if (const and level == 0) else "*mut ") + inner
+    for t in tail:
+        # a pointer carries the const of its pointee: the base type's for the innermost one, a `* const` level's for the one around it;
+        # every other level is `*mut` (out-parameters)
+        if t == "*":
+            inner = ("*const " if const else "*mut ") + inner
+            const = False
+        else:
+            assert t == "const", ctype
+            const = True
     return inner
 
 
