@@ -936,6 +936,12 @@ void launch_flat_tail64(const FlatTailArgs &a, uint32_t nq, hipStream_t s) {
 // shard | at 1M rows | 32 queries | 1 query, us): 8 waves 97 | 125 | 50 | 35, 4 waves 72 | 110 | 50 | 35, 40: 67 | 106 | 44 | 31,
 // 41: 71 | 108 | 45 | 32 (its extra depth costs the spills of a 128-register budget).
 #define TAIL_LB_AUTO_NW(nq) 40
+#ifndef TAIL_LB_WINDOW
+// keys per selection window of the default walk: 256 / 128 = four / two rounds per selection.  Measured (profiles/tail_lb_walk_ab.txt, 1000
+// queries at 1M rows): 78.0 / 86.9 us against 97.9 with a selection in every round -- the kernel lasts as long as the queries that walk three
+// or four rounds, and with 128 keys those select twice.
+#define TAIL_LB_WINDOW 256
+#endif
 template <int NW>
 __device__ __forceinline__ uint64_t block_top64_above(const uint64_t *__restrict__ src, uint32_t total, uint64_t (*sbest)[64], uint64_t above) {
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -965,6 +971,126 @@ __device__ __forceinline__ uint64_t block_top64_above(const uint64_t *__restrict
     for (int w = 1; w < NW; w++) m = merge64(m, sbest[w][lane], lane);
     return m;
 }
+// ---- the selection window of the default walk ("flat_tail_lb_walk" 0) ---------------------------------------------------------
+// The walk above selects anew in every round: the query's whole hit list is read from global memory and sorted in batches of 256 keys for
+// 64 of them.  A batch is sorted anyway, so the default walk keeps the W smallest pairs above `above` -- a window -- and serves
+// W / 64 rounds from it: round j of a window reads entries [63 j, 63 j + 63], 63 rows to evaluate and the key that opens the next round
+// (W = 256: 3 * 63 + 63 = 252 <= 255), and only every (W / 64)-th round selects again, above the last evaluated entry (251) -- the pair
+// the per-round selection would have been given.  Pairs are distinct (the row index is part of them), so entries [63 j, 63 j + 63] ARE the 64 smallest pairs above entry
+// 63 j - 1: every round sees the keys it saw before.
+// A sorted list of W = 64 U pairs lives in U registers per lane: element 64 u + lane in r[u].
+// compare-exchange between whole registers (partner distance >= 64): the smaller pair stays in a
+__device__ __forceinline__ void cmpx_regs(uint64_t &a, uint64_t &b) {
+    const uint64_t lo = a < b ? a : b, hi = a < b ? b : a;
+    a = lo;
+    b = hi;
+}
+// a bitonic sequence of 64 U pairs -> ascending: partner distances 32 U .. 64 between registers, then inside them
+template <int U>
+__device__ __forceinline__ void bitonic_merge_regs(uint64_t (&r)[U], uint32_t lane) {
+#pragma unroll
+    for (int dist = U / 2; dist >= 1; dist /= 2)
+#pragma unroll
+        for (int u = 0; u < U; u++)
+            if ((u & dist) == 0) cmpx_regs(r[u], r[u + dist]);
+    bitonic_stages<64, 32, U>(r, lane);
+}
+// best, r ascending lists of 64 U -> best = the 64 U smallest of both, ascending (merge64 with U registers: the minima against the
+// reversed partner hold them as a bitonic sequence)
+template <int U>
+__device__ __forceinline__ void merge_low(uint64_t (&best)[U], const uint64_t (&r)[U], uint32_t lane) {
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const uint64_t rev = lane_reverse64(r[U - 1 - u], lane);
+        best[u] = best[u] < rev ? best[u] : rev;
+    }
+    bitonic_merge_regs<U>(best, lane);
+}
+// four runs, each ascending across the lanes (bitonic_sort_from<2, 4>) -> r[0 .. U - 1] = their 64 U smallest pairs, ascending
+template <int U>
+__device__ __forceinline__ void sort_batch_low(uint64_t (&r)[4], uint32_t lane) {
+    // 64 + 64 twice: minima / maxima against the reversed partner are two bitonic halves with every minimum <= every maximum
+    const uint64_t v1 = lane_reverse64(r[1], lane), v3 = lane_reverse64(r[3], lane);
+    r[1] = v1;
+    r[3] = v3;
+    cmpx_regs(r[0], r[1]);
+    cmpx_regs(r[2], r[3]);
+    bitonic_stages<64, 32, 4>(r, lane);
+    // 128 + 128: the second list reversed is rev(r[3]), rev(r[2])
+    const uint64_t w0 = lane_reverse64(r[3], lane), w1 = lane_reverse64(r[2], lane);
+    if constexpr (U == 2) {
+        uint64_t m[2] = {r[0] < w0 ? r[0] : w0, r[1] < w1 ? r[1] : w1};
+        bitonic_merge_regs<2>(m, lane);
+        r[0] = m[0];
+        r[1] = m[1];
+    } else {
+        r[2] = w0;
+        r[3] = w1;
+        cmpx_regs(r[0], r[2]);
+        cmpx_regs(r[1], r[3]);
+        cmpx_regs(r[0], r[1]);
+        cmpx_regs(r[2], r[3]);
+        bitonic_stages<64, 32, 4>(r, lane);
+    }
+}
+// The W smallest pairs of the hit list above `above`, ascending, into swin[W] (PAIR_NONE where the list ends first).  A wave sorts every
+// NW-th batch of 256 keys and merges it into its running list; a batch whose smallest key is not below the wave's W-th is skipped
+// (wave-uniform).  The waves' lists meet in wlist, pairwise over log2(NW) levels with a __syncthreads() each (none for one wave); swin
+// is written by wave 0 AFTER the last: the caller's barrier publishes it.
+template <int NW, int W>
+__device__ __forceinline__ void block_topW_above(const uint64_t *__restrict__ src, uint32_t total, uint64_t *wlist /* [NW][W] */,
+                                                 uint64_t *swin /* [W] */, uint64_t above) {
+    static_assert(W == 256 || W == 128, "four or two registers per lane: a window serves four or two rounds");
+    constexpr int U = W / 64;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t batches = (total + 255) / 256;
+    uint64_t best[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) best[u] = PAIR_NONE;
+    bool empty = true;  // wave-uniform
+    for (uint32_t bt = wave; bt < batches; bt += NW) {
+        uint64_t r[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint32_t i = (bt * 4 + u) * 64 + lane;
+            const uint64_t v = i < total ? src[i] : PAIR_NONE;
+            r[u] = v > above ? v : PAIR_NONE;
+        }
+        const uint64_t tau = __shfl(best[U - 1], 63);
+        uint64_t lo = r[0] < r[1] ? r[0] : r[1], lo2 = r[2] < r[3] ? r[2] : r[3];
+        lo = lo < lo2 ? lo : lo2;
+        if (__ballot(lo < tau) == 0) continue;  // wave-uniform
+        bitonic_sort_from<2, 4>(r, lane);
+        sort_batch_low<U>(r, lane);
+        if (empty) {
+#pragma unroll
+            for (int u = 0; u < U; u++) best[u] = r[u];
+            empty = false;
+        } else {
+            uint64_t t[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) t[u] = r[u];
+            merge_low<U>(best, t, lane);
+        }
+    }
+#pragma unroll
+    for (int st = 1; st < NW; st *= 2) {  // wave w + st hands its list to wave w (w a multiple of 2 st); a slot is written once
+        if (wave % (2 * st) == st) {
+#pragma unroll
+            for (int u = 0; u < U; u++) wlist[wave * W + u * 64 + lane] = best[u];
+        }
+        __syncthreads();
+        if (wave % (2 * st) == 0 && wlist[(wave + st) * W] != PAIR_NONE) {  // (wave-uniform: the list's smallest pair)
+            uint64_t t[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) t[u] = wlist[(wave + st) * W + u * 64 + lane];
+            merge_low<U>(best, t, lane);
+        }
+    }
+    if (wave != 0) return;
+#pragma unroll
+    for (int u = 0; u < U; u++) swin[u * 64 + lane] = best[u];
+}
 __device__ __forceinline__ uint8_t flat_certify_lb(uint64_t ek, float kappa, uint32_t q, const FlatTailArgs &a) {
     if (ek == PAIR_NONE) return 1;
     const float dk = f32_from_orderable(uint32_t(ek >> 32));
@@ -972,17 +1098,24 @@ __device__ __forceinline__ uint8_t flat_certify_lb(uint64_t ek, float kappa, uin
     return flat_lb_excludes(dk, kappa, a.qsq[q], a.se.qoff[q], a.cosine, a.xsq_max, a.xsq_min_pos, a.se.mu_norm, a.dim) ? 0 : 1;  // NaN anywhere -> not certified
 }
 // NW waves of 64 (8, 4, 2 or 1): a round = one select + ONE re-rank stage of 63 rows, 64 / NW per wave (the last position of
-// the round's 64 keys opens the next round)
-template <int FOLD, int NW, int PCD>  // PCD: 0, or the load depth of the producer / consumer fold
+// the round's 64 keys opens the next round).
+// WALK ("flat_tail_lb_walk") 1: a selection in every round, every row of a round fetched.  0 (default): the same rounds over the same keys
+// with the same decisions at a lower cost -- a selection every fourth round (block_topW_above), and in rounds after the first no fetch
+// of rows that the k-th distance so far already excludes (below).  Outputs, flags, round counts and qstat are the same bits.
+template <int FOLD, int NW, int PCD, int WALK>  // PCD: 0, or the load depth of the producer / consumer fold
 __global__ __launch_bounds__(NW * 64, PCD ? 4 : 1) void k_flat_tail_lb(FlatTailArgs a) {
     constexpr bool PC = PCD != 0;
+    static_assert(WALK == 0 || WALK == 1, "0 windowed walk, 1 a selection per round");
     static_assert(NW == 8 || NW == 4 || NW == 2 || NW == 1, "a stage covers the 64 keys of a round");
     static_assert(!PC || NW == 4, "producer / consumer fold: four waves");
     constexpr int RW = 64 / NW, NP = RW / 8;
     constexpr int DEPTH = PC ? PCD : (NW == 8 ? 8 : (NW == 4 ? 4 : (NW == 2 ? 3 : 2)));  // chunks of row loads in flight per wave (NP KB each)
     extern __shared__ float4 ftl_smem[];  // [dim/4] query, then NW waves x [RW rows][9] float4 product tiles (PC: two [64][9] tiles)
-    __shared__ uint64_t sbest[NW][64];
+    __shared__ uint64_t sbest[WALK == 1 ? NW : 1][64];  // walk 1: the waves' lists, then [0] = the round's 64 keys
+    constexpr uint32_t W = TAIL_LB_WINDOW, RPW = W / 64;  // walk 0: keys per window, rounds per window
+    __shared__ uint64_t swin[WALK == 0 ? W : 1];        // walk 0: the window; the waves' lists of W meet in the product tiles
     __shared__ uint64_t skeys[64];
+    __shared__ uint64_t s_ek;  // walk 0: the k-th exact pair after the round (wave 0 holds `run`; every wave needs D_k)
     __shared__ uint32_t s_flag;
     const uint32_t q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t d4 = a.dim / 4;
@@ -1012,20 +1145,60 @@ __global__ __launch_bounds__(NW * 64, PCD ? 4 : 1) void k_flat_tail_lb(FlatTailA
     uint32_t rounds_done = 0;
     for (uint32_t rd = 0; rd < rounds; rd++) {
         rounds_done = rd + 1;
-        const uint64_t best = block_top64_above<NW>(a.cand + uint64_t(q) * a.cap, total, sbest, above);  // (its barrier also covers qs4)
-        __syncthreads();  // wave 0 is done with sbest[1..]
-        if (wave == 0) sbest[0][lane] = best;
+        const uint64_t *rk;  // the round's 64 keys, ascending
+        if constexpr (WALK == 1) {
+            const uint64_t best = block_top64_above<NW>(a.cand + uint64_t(q) * a.cap, total, sbest, above);  // (its barrier also covers qs4)
+            __syncthreads();  // wave 0 is done with sbest[1..]
+            if (wave == 0) sbest[0][lane] = best;
+            rk = sbest[0];
+        } else {
+            // the tiles are free here: the fold of the round before is two barriers back (NW lists of 256 pairs <= 16 KB of their 18)
+            if (rd % RPW == 0)  // (round 0 selects: qs4 is covered by its barrier, or by the one below when there is one wave)
+                block_topW_above<NW, W>(a.cand + uint64_t(q) * a.cap, total, reinterpret_cast<uint64_t *>(ftl_smem + d4), swin, above);
+            rk = swin + 63u * (rd % RPW);
+        }
         if (threadIdx.x < 64) skeys[threadIdx.x] = PAIR_NONE;
         __syncthreads();
         TAIL_STAMP();
-        // position 63 is not evaluated: it opens the next round
+        // Walk 0, rounds after the first: rows that D_k, the k-th exact distance so far, already excludes are not fetched.  Let p be the
+        // first position of the round with flat_lb_excludes(D_k, key_p): every row whose key is ABOVE key_p then has an exact distance
+        // strictly above D_k.  Candidate p itself and later ones with the same key are still evaluated; a later candidate with a greater
+        // key -- and, so that a NaN key never counts, with the bound holding for its own key too (it is monotone in kappa, so this
+        // only drops NaN) -- is dead: no fetch, no entry in skeys.  This is invisible.  D_k only falls from round to round (`run`
+        // keeps the smallest pairs), so such a row's distance e > D_k >= every later D_k: its pair is above the k-th pair of `run`
+        // whenever it would have been merged and ever after, i.e. never among the first ksel entries of `run`, which are all that the
+        // outputs and every certification (ek = entry ksel - 1) read.  By induction over the rounds ek, the certification against the
+        // same next key, the round count and the flag are what walk 1 computes.  Nothing is skipped while run has fewer than ksel pairs
+        // (ek = PAIR_NONE), when the bound does not hold (Cosine without plain norms, NaN in D_k, in the key or in the query's constants:
+        // flat_lb_excludes is false), or in round 0.
+        uint32_t cut_pos = 64, cut_hi = 0;
+        uint64_t exm = 0;
+        if constexpr (WALK == 0) {
+            if (rd > 0) {
+                const uint64_t ek = s_ek;  // block-uniform
+                if (ek != PAIR_NONE) {     // (the round before certified against it: qsq / qoff were read there)
+                    const uint64_t c = rk[lane];
+                    const bool ex = flat_lb_excludes(f32_from_orderable(uint32_t(ek >> 32)), f32_from_orderable(uint32_t(c >> 32)), a.qsq[q],
+                                                     a.se.qoff[q], a.cosine, a.xsq_max, a.xsq_min_pos, a.se.mu_norm, a.dim);
+                    exm = __ballot(ex && c != PAIR_NONE);
+                    if (exm) {
+                        cut_pos = uint32_t(__ffsll((unsigned long long)exm)) - 1u;
+                        cut_hi = uint32_t(rk[cut_pos] >> 32);
+                    }
+                }
+            }
+        }
+        auto evaluated = [&](uint32_t j, uint64_t c) -> bool {  // position 63 is not evaluated: it opens the next round
+            const bool dead = j > cut_pos && uint32_t(c >> 32) > cut_hi && ((exm >> j) & 1u);
+            return c != PAIR_NONE && j < 63 && !dead;
+        };
         uint32_t idx[NP];
         bool live[NP];
 #pragma unroll
         for (int i = 0; i < NP; i++) {
             const uint32_t j = wave * RW + 8 * i + (lane >> 3);
-            const uint64_t c = sbest[0][j];
-            live[i] = c != PAIR_NONE && j < 63;
+            const uint64_t c = rk[j];
+            live[i] = evaluated(j, c);
             idx[i] = live[i] ? uint32_t(c) : 0u;
 #if defined(VDB_TAIL_ABLATE) && VDB_TAIL_ABLATE == 1
             idx[i] &= 63u;
@@ -1035,8 +1208,8 @@ __global__ __launch_bounds__(NW * 64, PCD ? 4 : 1) void k_flat_tail_lb(FlatTailA
         if constexpr (PC) {
             const bool consumer = wave == (blockIdx.x & 3u);
             acc = pc_rerank_fold<FOLD, DEPTH>(a.X, a.dim, idx, live, qs4, ftl_smem + d4, wave, lane, consumer);
-            const uint64_t c = sbest[0][lane];  // the consumer's lane added row `lane`
-            if (consumer && c != PAIR_NONE && lane < 63)
+            const uint64_t c = rk[lane];  // the consumer's lane added row `lane`
+            if (consumer && evaluated(lane, c))
                 skeys[lane] = pair_key(FOLD == FOLD_L2 ? acc : epilogue(MET_COSINE, acc, a.xsq[uint32_t(c)], a.qsq[q]), uint32_t(c));
         } else {
             if constexpr (NW == 8)
@@ -1044,18 +1217,19 @@ __global__ __launch_bounds__(NW * 64, PCD ? 4 : 1) void k_flat_tail_lb(FlatTailA
             else
                 acc = group_rerank_fold_n<FOLD, DEPTH, RW>(a.X, a.dim, idx, live, qs4, tile, lane);
             const uint32_t j = wave * RW + lane / NW;  // the row whose chain this lane added (NW lanes each)
-            const uint64_t c = sbest[0][j];
-            if (c != PAIR_NONE && j < 63 && lane % NW == 0)
+            const uint64_t c = rk[j];
+            if (evaluated(j, c) && lane % NW == 0)
                 skeys[j] = pair_key(FOLD == FOLD_L2 ? acc : epilogue(MET_COSINE, acc, a.xsq[uint32_t(c)], a.qsq[q]), uint32_t(c));
         }
         __syncthreads();
         TAIL_STAMP();
         if (wave == 0) {
             run = merge64(run, sort64(skeys[lane], lane), lane);
-            const uint64_t ek = __shfl(run, kk - 1), nxt = sbest[0][63];
+            const uint64_t ek = __shfl(run, kk - 1), nxt = rk[63];
             if (lane == 0) {
                 const float kappa = nxt == PAIR_NONE ? tau_q : f32_from_orderable(uint32_t(nxt >> 32));
                 s_flag = flat_certify_lb(ek, kappa, q, a) | (nxt == PAIR_NONE ? 2u : 0u);
+                if constexpr (WALK == 0) s_ek = ek;
             }
         }
         __syncthreads();
@@ -1066,8 +1240,8 @@ __global__ __launch_bounds__(NW * 64, PCD ? 4 : 1) void k_flat_tail_lb(FlatTailA
             break;
         }
         if (f & 2u) break;  // the hit list is exhausted and the k-th distance is still above tau's bound
-        above = sbest[0][62];
-        __syncthreads();  // sbest is rewritten by the next round
+        above = rk[62];   // (walk 0: used by the next selection, i.e. as the last evaluated entry of the window)
+        __syncthreads();  // sbest / swin is rewritten by the next round
     }
 #ifdef VDB_TAIL_STAMPS
     if (a.stamps && threadIdx.x == 0) {
@@ -1093,6 +1267,8 @@ bool flat_tail_lb_supported(uint32_t dim, uint32_t kprime, uint32_t ksel) {
 }
 static std::atomic<int> g_tail_lb_nw{0};  // 0 auto; 8 / 4 / 2 / 1 waves per query
 void flat_tail_lb_set_nw(int v) { g_tail_lb_nw = v; }
+static std::atomic<int> g_tail_lb_walk{0};  // 0: a selection window per four rounds, excluded rows not fetched; 1: a selection per round
+void flat_tail_lb_set_walk(int v) { g_tail_lb_walk = v; }
 #ifdef VDB_TAIL_STAMPS
 static void tail_stamps_report(unsigned long long *d, uint32_t nq, hipStream_t s) {
     VDB_SYNC(s);
@@ -1136,25 +1312,34 @@ void launch_flat_tail_lb(const FlatTailArgs &a0, uint32_t nq, hipStream_t s) {
     const size_t lds = (size_t(a.dim / 4) + 2 * 64 * 9) * sizeof(float4);
     int nw = g_tail_lb_nw;
     if (nw != 8 && nw != 4 && nw != 2 && nw != 1 && nw != 40 && nw != 41) nw = TAIL_LB_AUTO_NW(nq);
+    const bool w1 = g_tail_lb_walk == 1;
+#define TAIL_LB_LAUNCH(FOLD, NW, PCD)                                                                                \
+    do {                                                                                                             \
+        if (w1)                                                                                                      \
+            hipLaunchKernelGGL((k_flat_tail_lb<FOLD, NW, PCD, 1>), dim3(nq), dim3(NW * 64), lds, s, a);              \
+        else                                                                                                         \
+            hipLaunchKernelGGL((k_flat_tail_lb<FOLD, NW, PCD, 0>), dim3(nq), dim3(NW * 64), lds, s, a);              \
+    } while (0)
     if (a.metric == MET_COSINE) {  // (Cosine: the producer / consumer form and the plain 8-wave form)
         if (nw == 8)
-            hipLaunchKernelGGL((k_flat_tail_lb<FOLD_DOT, 8, 0>), dim3(nq), dim3(512), lds, s, a);
+            TAIL_LB_LAUNCH(FOLD_DOT, 8, 0);
         else if (nw == 41)
-            hipLaunchKernelGGL((k_flat_tail_lb<FOLD_DOT, 4, 5>), dim3(nq), dim3(256), lds, s, a);
+            TAIL_LB_LAUNCH(FOLD_DOT, 4, 5);
         else
-            hipLaunchKernelGGL((k_flat_tail_lb<FOLD_DOT, 4, 3>), dim3(nq), dim3(256), lds, s, a);
+            TAIL_LB_LAUNCH(FOLD_DOT, 4, 3);
     } else if (nw == 40)  // four waves, producer / consumer fold
-        hipLaunchKernelGGL((k_flat_tail_lb<FOLD_L2, 4, 3>), dim3(nq), dim3(256), lds, s, a);
+        TAIL_LB_LAUNCH(FOLD_L2, 4, 3);
     else if (nw == 41)
-        hipLaunchKernelGGL((k_flat_tail_lb<FOLD_L2, 4, 5>), dim3(nq), dim3(256), lds, s, a);
+        TAIL_LB_LAUNCH(FOLD_L2, 4, 5);
     else if (nw == 8)
-        hipLaunchKernelGGL((k_flat_tail_lb<FOLD_L2, 8, 0>), dim3(nq), dim3(512), lds, s, a);
+        TAIL_LB_LAUNCH(FOLD_L2, 8, 0);
     else if (nw == 4)
-        hipLaunchKernelGGL((k_flat_tail_lb<FOLD_L2, 4, 0>), dim3(nq), dim3(256), lds, s, a);
+        TAIL_LB_LAUNCH(FOLD_L2, 4, 0);
     else if (nw == 2)
-        hipLaunchKernelGGL((k_flat_tail_lb<FOLD_L2, 2, 0>), dim3(nq), dim3(128), lds, s, a);
+        TAIL_LB_LAUNCH(FOLD_L2, 2, 0);
     else
-        hipLaunchKernelGGL((k_flat_tail_lb<FOLD_L2, 1, 0>), dim3(nq), dim3(64), lds, s, a);
+        TAIL_LB_LAUNCH(FOLD_L2, 1, 0);
+#undef TAIL_LB_LAUNCH
     VDB_HIP(hipGetLastError());
 #ifdef VDB_TAIL_STAMPS
     if (stamps) tail_stamps_report(stamps, nq, s);

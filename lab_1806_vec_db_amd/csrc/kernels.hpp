@@ -76,6 +76,7 @@ void launch_flat_tail_lb(const FlatTailArgs &a, uint32_t nq, hipStream_t s);
 // all candidates of a few queries evaluated at once (the second 8-bit attempt of a handful of queries): exact_keys nq x a.cap, topk nq x topk_capacity(ksel)
 void launch_flat_full_lb(const FlatTailArgs &a, uint32_t nq, uint64_t *exact_keys, uint64_t *topk, hipStream_t s);
 void flat_tail_lb_set_nw(int v);  // waves per query: 0 auto, 8 / 4 / 2 / 1
+void flat_tail_lb_set_walk(int v);  // 0: a selection per four rounds, rows the k-th distance excludes not fetched; 1: a selection per round
 bool flat_tail64_supported(uint32_t dim, uint32_t kprime, uint32_t ksel);
 void launch_flat_tail64(const FlatTailArgs &a, uint32_t nq, hipStream_t s);
 // k_small.hip: FlatIndex::knn of a few queries over a small table in ONE launch (the db.search() shape): coalesced rows ->

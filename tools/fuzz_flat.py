@@ -10,6 +10,7 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 240.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1806)
 rng2 = np.random.default_rng(7 + (int(sys.argv[2]) if len(sys.argv) > 2 else 1806))
 rng3 = np.random.default_rng(11 + (int(sys.argv[2]) if len(sys.argv) > 2 else 1806))
+rng4 = np.random.default_rng(13 + (int(sys.argv[2]) if len(sys.argv) > 2 else 1806))
 min_n = int(sys.argv[4]) if len(sys.argv) > 4 else 17000  # (below 16 384 rows calls of < 32 queries take the one-launch kernel)
 t_end = time.time() + budget
 it = bad = 0
@@ -56,12 +57,14 @@ while time.time() < t_end:
     ix.set_param("flat_i8_refine", ref)
     epi = int(rng3.choice([0, 0, 1]))  # unit epilogue of the 8-bit filter kernel: scalar arithmetic + carried stage / the earlier form (process-wide)
     ix.set_param("flat_gemm8_epi", epi)
+    walk = int(rng4.choice([0, 0, 1]))  # exact stage of the 8-bit pass: windowed walk / a selection in every round (process-wide)
+    ix.set_param("flat_tail_lb_walk", walk)
     idx, d, cnt = ix.flat_knn(qs, k)
     oi, od, oc = O.flat_knn_batch(base, qs, k, kind, nthreads=16)
     ok = cnt.tolist() == oc.tolist() and all(idx[q, :int(cnt[q])].tolist() == oi[q][:int(cnt[q])].tolist() and
                                              np.array_equal(d[q, :int(cnt[q])], od[q][:int(cnt[q])]) for q in range(nq))
     print(f"#{it} dim {dim} n {n} nq {nq} k {k} {dist} style {style}: {'ok' if ok else 'MISMATCH'} "
-          f"i8 {ix.get_stat('flat_i8_queries')} second {ix.get_stat('flat_i8_second_queries')} passed on {ix.get_stat('flat_i8_redo')} tail {nw} refine {ref}:{ix.get_stat('flat_i8_refine_queries')} epi {epi} sets {ix.get_stat('flat_gemm8_coop_sets')} half {ix.get_stat('flat_half_queries')} redo {ix.get_stat('flat_half_redo')} fallback {ix.flat_fallback_count()}", flush=True)
+          f"i8 {ix.get_stat('flat_i8_queries')} second {ix.get_stat('flat_i8_second_queries')} passed on {ix.get_stat('flat_i8_redo')} tail {nw} walk {walk} refine {ref}:{ix.get_stat('flat_i8_refine_queries')} epi {epi} sets {ix.get_stat('flat_gemm8_coop_sets')} half {ix.get_stat('flat_half_queries')} redo {ix.get_stat('flat_half_redo')} fallback {ix.flat_fallback_count()}", flush=True)
     bad += 0 if ok else 1
     del ix
 print(f"done: {it} configurations, {bad} mismatches")
