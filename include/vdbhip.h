@@ -213,6 +213,46 @@ int vdb_flat_knn_filtered_multi_device(vdb_index *idx, const void *d_queries, ui
                                        void *d_out_dist, void *d_out_count, void *stream);
 int vdb_flat_range_filtered(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit,
                             const vdb_mask *mask, vdb_range **out);
+/* ---- row labels on the device: masks built from them without a host pass ----------------------------------------------------------
+ * An index has VDB_LABEL_COLUMNS logical label columns of uint32_t, one value per LOCAL row: the filterable attributes of the rows as
+ * integer codes (the host keeps the dictionary; lab_1806_vec_db_amd/labels.py is one).  A column is allocated by its first write
+ * (4 B per row in HBM, grown with the rows); a column never written reads as VDB_LABEL_NONE for every row and takes no memory.  The
+ * allocated columns follow every change of the row set, on f32 and VecSet<u8> indexes alike: rows added by any call get
+ * VDB_LABEL_NONE in every column, vdb_index_swap_remove and vdb_index_remove_rows move the labels with the rows.  Labels are
+ * independent of PQ / HNSW / IVF state, and writing them does NOT make masks stale (a mask is a set of rows).
+ * vdb_index_labels_set: rows [first_row, first_row + count) of one column from a host array.  Write-side with respect to mask
+ * creation from labels (no vdb_mask_create_where* call may run on the index meanwhile); searches are not affected.  column >=
+ * VDB_LABEL_COLUMNS or a range past vdb_index_len is VDB_ERR_INVALID and nothing is written; count == 0 is fine and allocates nothing.
+ * vdb_index_labels_get: reads a range back (VDB_LABEL_NONE for a column never written); same errors; read-side.
+ * vdb_mask_create_where: the mask of the rows r with label[columns[t]][r] == codes[t] for EVERY t < n_terms -- a conjunction of
+ * equalities.  Plain equality: a term with code VDB_LABEL_NONE matches the unlabelled rows (all rows, for a column never written);
+ * n_terms == 0 allows every row; two terms on one column with different codes give an empty mask.  More than VDB_MASK_MAX_TERMS terms
+ * or a column >= VDB_LABEL_COLUMNS is VDB_ERR_INVALID.  Read-side, like vdb_mask_create, and the result IS the object vdb_mask_create
+ * would have made from the equivalent bits: same owner / staleness rules, same lazily built row constants, usable with every call that
+ * takes a vdb_mask.  An empty index gives a mask with m = 0.
+ * vdb_mask_create_where_many: n_masks masks in ONE call; mask g's terms are entries [term_lims[g], term_lims[g + 1]) of columns /
+ * codes, term_lims[0] == 0 and non-decreasing (n_masks + 1 entries); `out` has room for n_masks handles.  All-or-nothing: everything
+ * is validated before anything is launched, and on any error every mask built so far is destroyed, every out[g] is NULL and the index
+ * is unchanged.  n_masks == 0 succeeds.  The single form is this call with one mask.
+ * vdb_mask_rows: reads a mask of either constructor back -- out_bits: ceil(n_rows / 64) words, out_ids: the m allowed rows, ascending
+ * (vdb_mask_count gives m); either pointer may be NULL.
+ * How the masks are built (csrc/k_labels.hip, docs/DESIGN_flat.md 4.1l): per chunk of up to 1024 masks, k_mask_where -- a 64-lane wave
+ * owns one mask word, a lane one row; the lane compares its row's value in every term column and the wave's ballot is the word --
+ * counts the allowed rows per workgroup, k_mask_scan turns the counts into offsets, one read-back of the totals sizes the allow-lists,
+ * and k_mask_ids writes every allowed row at its offset: ascending without a sort.  Traffic per mask: 4 B x terms x rows read, rows / 8
+ * + 4 m written.  vdb_prof_get "mask_where" times the three kernels; vdb_get_stat "mask_where_masks" counts the masks built this way,
+ * "label_columns" the allocated columns ("hbm_bytes_per_row" includes them).
+ * Not covered: sharded and replica contexts, range or set predicates (equality conjunctions only), a single-pass partition of one
+ * column into the masks of all its values, labels in bincode files. */
+#define VDB_LABEL_COLUMNS 16
+#define VDB_LABEL_NONE 0xFFFFFFFFu
+#define VDB_MASK_MAX_TERMS 8
+int vdb_index_labels_set(vdb_index *idx, uint32_t column, uint64_t first_row, const uint32_t *codes, uint64_t count);
+int vdb_index_labels_get(const vdb_index *idx, uint32_t column, uint64_t first_row, uint64_t count, uint32_t *out);
+int vdb_mask_create_where(vdb_index *idx, const uint32_t *columns, const uint32_t *codes, uint64_t n_terms, vdb_mask **out);
+int vdb_mask_create_where_many(vdb_index *idx, const uint64_t *term_lims, const uint32_t *columns, const uint32_t *codes,
+                               uint64_t n_masks, vdb_mask **out);
+int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids);
 /* the approximate keys the Flat shortlist pass compares with its threshold, for EVERY row, from the same kernel in its dense
  * mode (test / measurement entry point behind the certification-bound tests): out_keys [nq][len];
  * L2Sqr: key = |x|^2 - 2 S~, approximate distance = key + |q|^2;  Cosine: key = -S~ / |x|, approximate distance = 1 + key / |q|.
@@ -309,7 +349,9 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *   "ivf_last_offers", "ivf_last_kept_q8", "ivf_last_kept"  (while vdb_prof_enable is on) rows the last IVF call offered to its result
  *                        sets, the ones the 8-bit tier passed on (0: tier not run) and the ones that reached the exact stage; "ivf_last_rows_fetched_q8":
  *                        rows the cluster-major 8-bit tier read, once each (0: query-major),
- *   "hbm_bytes_per_row"  resident HBM bytes per row over all per-row buffers (rows, norms, mirrors, PQ codes, level-0 links). */
+ *   "mask_where_masks"   masks built on the device from the label columns (vdb_mask_create_where*); "label_columns": allocated columns,
+ *   "hbm_bytes_per_row"  resident HBM bytes per row over all per-row buffers (rows, norms, mirrors, PQ codes, level-0 links, label
+ *                        columns). */
 int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out);
 
 /* ---- PQTable (distance/pq_table.rs) ----------------------------------------------------

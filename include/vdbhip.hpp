@@ -181,6 +181,21 @@ public:
         check(vdb_mask_create(h_, bits.data(), allow.size(), &m));
         return Mask(m);
     }
+    // label columns (vdb_index_labels_set) and the mask of the rows whose label in terms[t].first equals terms[t].second for every t,
+    // built on the device (vdb_mask_create_where); no terms: every row
+    void set_labels(uint32_t column, const std::vector<uint32_t> &codes, uint64_t first_row = 0) {
+        check(vdb_index_labels_set(h_, column, first_row, codes.data(), codes.size()));
+    }
+    Mask make_mask_where(const std::vector<std::pair<uint32_t, uint32_t>> &terms) const {
+        std::vector<uint32_t> cols, codes;
+        for (const auto &t : terms) {
+            cols.push_back(t.first);
+            codes.push_back(t.second);
+        }
+        vdb_mask *m = nullptr;
+        check(vdb_mask_create_where(h_, cols.data(), codes.data(), terms.size(), &m));
+        return Mask(m);
+    }
     // per query the first min(k, mask.count()) pairs of knn_batch over the allowed rows alone (vdb_flat_knn_filtered)
     std::vector<std::vector<CandidatePair>> knn_filtered_batch(const float *queries, uint64_t nq, uint64_t k, const Mask &mask) const {
         std::vector<uint64_t> idx(nq * (k ? k : 1)), cnt(nq);

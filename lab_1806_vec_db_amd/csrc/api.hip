@@ -619,6 +619,57 @@ int vdb_mask_create(vdb_index *idx, const uint64_t *bits, uint64_t n_rows, vdb_m
     VDB_API_END
 }
 
+// ---- label columns; masks built from them on the device (Index::masks_where, k_labels.hip) ------------------------------------------------
+static_assert(LABEL_COLUMNS == VDB_LABEL_COLUMNS && LABEL_NONE == VDB_LABEL_NONE && MASK_MAX_TERMS == VDB_MASK_MAX_TERMS, "vdbhip.h and kernels.hpp agree");
+int vdb_index_labels_set(vdb_index *idx, uint32_t column, uint64_t first_row, const uint32_t *codes, uint64_t count) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    idx->ix.labels_set(column, first_row, codes, count);
+    VDB_API_END
+}
+int vdb_index_labels_get(const vdb_index *idx, uint32_t column, uint64_t first_row, uint64_t count, uint32_t *out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    idx->ix.labels_get(column, first_row, count, out);
+    VDB_API_END
+}
+int vdb_mask_create_where_many(vdb_index *idx, const uint64_t *term_lims, const uint32_t *columns, const uint32_t *codes, uint64_t n_masks,
+                               vdb_mask **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    VDB_REQUIRE(n_masks == 0 || out, "null argument");
+    for (uint64_t g = 0; g < n_masks; g++) out[g] = nullptr;
+    std::vector<std::unique_ptr<vdb_mask>> made(n_masks);
+    std::vector<RowMask *> rm(n_masks);
+    for (uint64_t g = 0; g < n_masks; g++) {
+        made[g].reset(new vdb_mask);
+        rm[g] = &made[g]->m;
+    }
+    idx->ix.masks_where(term_lims, columns, codes, n_masks, rm.data());  // a throw destroys every mask made so far with `made`
+    for (uint64_t g = 0; g < n_masks; g++) out[g] = made[g].release();
+    VDB_API_END
+}
+int vdb_mask_create_where(vdb_index *idx, const uint32_t *columns, const uint32_t *codes, uint64_t n_terms, vdb_mask **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx && out, "null argument");
+    *out = nullptr;
+    VDB_REQUIRE(n_terms <= MASK_MAX_TERMS, "mask terms: " + std::to_string(n_terms) + " terms, at most " + std::to_string(MASK_MAX_TERMS) +
+                                               " are supported");
+    const uint64_t lims[2] = {0, n_terms};
+    return vdb_mask_create_where_many(idx, lims, columns, codes, 1, out);
+    VDB_API_END
+}
+int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(m, "null mask");
+    const RowMask &rm = m->m;
+    VDB_HIP(hipSetDevice(rm.device));
+    const uint64_t nw = (rm.n_rows + 63) / 64;
+    if (out_bits && nw) VDB_HIP(hipMemcpy(out_bits, rm.d_bits.p, nw * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (out_ids && rm.m) VDB_HIP(hipMemcpy(out_ids, rm.d_ids.p, rm.m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VDB_API_END
+}
+
 int vdb_mask_count(const vdb_mask *m, uint64_t *out) {
     VDB_API_BEGIN
     VDB_REQUIRE(m && out, "null argument");
@@ -1074,6 +1125,10 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.pq.q8_hits_sum.load();
     else if (n == "pq_q8_hits_max")
         *out = idx->ix.pq.q8_hits_max.load();
+    else if (n == "mask_where_masks")  // masks built on the device from the label columns (vdb_mask_create_where*)
+        *out = idx->ix.mask_where_masks.load();
+    else if (n == "label_columns")  // allocated label columns (4 B per row each)
+        *out = idx->ix.label_columns();
     else if (n == "hbm_bytes_per_row")
         *out = idx->ix.hbm_bytes_per_row();
     else

@@ -67,6 +67,9 @@ void Index::add_rows(const void *rows, uint64_t count, bool on_device) {
     size_t row_bytes = size_t(dim) * elem_size();
     d_rows.grow((n + count) * row_bytes + 16, n * row_bytes, s);  // +16: the u8 kernels may read a 16-B word at the last row's end
     d_sq.grow((n + count + 128) * sizeof(float), n * sizeof(float), s);  // +128: kernels may read a few entries past n
+    for (uint32_t c = 0; c < LABEL_COLUMNS; c++)  // (a failed allocation here leaves every buffer's contents and n as they were)
+        if (label_live[c]) d_labels[c].grow((n + count) * sizeof(uint32_t), n * sizeof(uint32_t), s);
+    launch_label_fill(label_cols(), n, n + count, num_cu, s);  // the new rows carry no label
     char *dst = d_rows.as<char>() + n * row_bytes;
     VDB_HIP(hipMemcpyAsync(dst, rows, count * row_bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     const uint64_t tiles_new = mirror_tiles(n + count), tiles_old = n / 16;  // (the partially filled tile is rewritten)
@@ -117,6 +120,7 @@ void Index::swap_remove(uint64_t i) {
     if (i < last) {
         VDB_HIP(hipMemcpyAsync(d_rows.as<char>() + i * row_bytes, d_rows.as<char>() + last * row_bytes, row_bytes, hipMemcpyDeviceToDevice, s));
         VDB_HIP(hipMemcpyAsync(d_sq.as<float>() + i, d_sq.as<float>() + last, sizeof(float), hipMemcpyDeviceToDevice, s));
+        launch_label_move_one(label_cols(), (uint32_t)i, (uint32_t)last, s);
     }
     if (mfma_supported((uint32_t)dim)) {  // rewrite the tiles of the moved row and of the removed last row
         for (uint64_t t : {i / 16, last / 16})
@@ -196,6 +200,7 @@ void Index::remove_rows(const uint64_t *rows, uint64_t m, std::vector<uint64_t> 
     if (moves) VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_moves.data(), h_moves.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     if (n_tiles && list_form) VDB_HIP(hipMemcpyAsync(ws->keys_b.p, h_tiles.data(), n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     launch_rows_move(d_rows.p, row_bytes, d_sq.as<float>(), d_moves, moves, num_cu, s);
+    launch_label_move(label_cols(), d_moves, moves, num_cu, s);  // (the columns only shrink here: nothing to reserve)
     if (mfma_supported((uint32_t)dim) && n_tiles) {
         const bool half_live = half_m.covers(n);  // same scale; the moved rows' rounding error is already part of half_dx_*
         if (list_form) {
@@ -236,6 +241,131 @@ void Index::remove_rows(const uint64_t *rows, uint64_t m, std::vector<uint64_t> 
     n = n1;
     write_gen += 1;
     // xsq_max / xsq_min_pos stay bounds
+}
+
+// ---- label columns and the masks built from them (k_labels.hip) ----------------------------------------------------------------------
+LabelCols Index::label_cols() const {
+    LabelCols lc{};
+    for (uint32_t c = 0; c < LABEL_COLUMNS; c++)
+        if (label_live[c]) lc.col[lc.n++] = d_labels[c].as<uint32_t>();
+    return lc;
+}
+
+static void labels_check_range(const Index &ix, uint32_t column, uint64_t first_row, uint64_t count) {
+    VDB_REQUIRE(column < LABEL_COLUMNS, "labels: column " + std::to_string(column) + ", an index has " + std::to_string(LABEL_COLUMNS));
+    VDB_REQUIRE(first_row <= ix.n && count <= ix.n - first_row, "labels: rows [" + std::to_string(first_row) + ", " + std::to_string(first_row) +
+                                                                    " + " + std::to_string(count) + ") pass the " + std::to_string(ix.n) +
+                                                                    " rows of the index");
+}
+
+void Index::labels_set(uint32_t column, uint64_t first_row, const uint32_t *codes, uint64_t count) {
+    labels_check_range(*this, column, first_row, count);
+    if (count == 0) return;
+    VDB_REQUIRE(codes, "null argument");
+    use_device();
+    WsLease ws(*this);
+    hipStream_t s = ws->stream;
+    if (!label_live[column]) {  // first write: the column comes to life with every row unlabelled
+        d_labels[column].grow(n * sizeof(uint32_t), 0, s);
+        LabelCols one{};
+        one.col[0] = d_labels[column].as<uint32_t>();
+        one.n = 1;
+        launch_label_fill(one, 0, n, num_cu, s);
+        label_live[column] = true;
+    }
+    VDB_HIP(hipMemcpyAsync(d_labels[column].as<uint32_t>() + first_row, codes, count * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    VDB_SYNC(s);
+}
+
+void Index::labels_get(uint32_t column, uint64_t first_row, uint64_t count, uint32_t *out) const {
+    labels_check_range(*this, column, first_row, count);
+    if (count == 0) return;
+    VDB_REQUIRE(out, "null argument");
+    if (!label_live[column]) {
+        std::fill(out, out + count, LABEL_NONE);
+        return;
+    }
+    use_device();
+    VDB_HIP(hipMemcpy(out, d_labels[column].as<uint32_t>() + first_row, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+}
+
+// Per chunk of masks: k_mask_where + k_mask_scan, ONE read-back of the totals (the only synchronisation before the allow-lists can be
+// allocated), k_mask_ids, synchronise.  The chunk bounds grid.y and the block-count scratch (at most 1024 masks and 64 MiB of counts).
+void Index::masks_where(const uint64_t *term_lims, const uint32_t *columns, const uint32_t *codes, uint64_t n_masks, RowMask *const *out) {
+    VDB_REQUIRE(n_masks == 0 || (term_lims && out), "null argument");
+    if (n_masks == 0) return;
+    VDB_REQUIRE(n_masks < (1ull << 28), "too many masks for one call");
+    VDB_REQUIRE(term_lims[0] == 0, "mask terms: term_lims[0] must be 0");
+    for (uint64_t g = 0; g < n_masks; g++) {
+        VDB_REQUIRE(term_lims[g + 1] >= term_lims[g], "mask terms: term_lims must not decrease (mask " + std::to_string(g) + ")");
+        VDB_REQUIRE(term_lims[g + 1] - term_lims[g] <= MASK_MAX_TERMS, "mask terms: mask " + std::to_string(g) + " has " +
+                                                                           std::to_string(term_lims[g + 1] - term_lims[g]) + " terms, at most " +
+                                                                           std::to_string(MASK_MAX_TERMS) + " are supported");
+    }
+    const uint64_t n_terms = term_lims[n_masks];
+    VDB_REQUIRE(n_terms == 0 || (columns && codes), "null argument");
+    for (uint64_t t = 0; t < n_terms; t++)
+        VDB_REQUIRE(columns[t] < LABEL_COLUMNS, "mask terms: column " + std::to_string(columns[t]) + " (term " + std::to_string(t) +
+                                                    "), an index has " + std::to_string(LABEL_COLUMNS));
+    use_device();
+    WsLease ws(*this);
+    hipStream_t s = ws->stream;
+    const uint64_t nw = (n + 63) / 64;
+    const uint32_t nblocks = mask_where_blocks(n);
+    const uint64_t gen = write_gen.load();
+    const uint64_t chunk = nblocks ? std::min<uint64_t>({n_masks, 1024, std::max<uint64_t>((64ull << 20) / (sizeof(uint32_t) * nblocks), 1)}) : n_masks;
+    std::vector<MaskTerm> h_terms(std::max<uint64_t>(n_terms, 1));
+    for (uint64_t t = 0; t < n_terms; t++) h_terms[t] = {label_live[columns[t]] ? d_labels[columns[t]].as<uint32_t>() : nullptr, codes[t]};
+    std::vector<MaskJob> h_jobs(chunk);
+    std::vector<uint32_t *> h_ids(chunk);
+    if (nblocks) {  // (contents not preserved by reserve: everything a chunk needs is sized here, once)
+        ws->keys_a.reserve(h_terms.size() * sizeof(MaskTerm));
+        ws->keys_b.reserve(chunk * sizeof(MaskJob));
+        ws->keys_c.reserve(chunk * sizeof(uint32_t *));
+        ws->flags.reserve(chunk * nblocks * sizeof(uint32_t));
+        ws->misc.reserve(chunk * sizeof(uint32_t));
+        VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_terms.data(), h_terms.size() * sizeof(MaskTerm), hipMemcpyHostToDevice, s));
+    }
+    for (uint64_t g0 = 0; g0 < n_masks; g0 += chunk) {
+        const uint64_t nb = std::min(chunk, n_masks - g0);
+        for (uint64_t j = 0; j < nb; j++) {
+            RowMask &m = *out[g0 + j];
+            m.owner = this;
+            m.device = device;
+            m.gen = gen;
+            m.n_rows = n;
+            m.m = 0;
+            m.d_bits.reserve(std::max<uint64_t>(nw, 1) * sizeof(uint64_t));
+            h_jobs[j] = {m.d_bits.as<uint64_t>(), (uint32_t)term_lims[g0 + j], (uint32_t)term_lims[g0 + j + 1]};
+        }
+        if (!nblocks) {  // an empty index: masks with m = 0
+            for (uint64_t j = 0; j < nb; j++) out[g0 + j]->d_ids.reserve(sizeof(uint32_t));
+            continue;
+        }
+        uint32_t *h_tot = static_cast<uint32_t *>(ws->pinned(chunk * sizeof(uint32_t)));
+        VDB_HIP(hipMemcpyAsync(ws->keys_b.p, h_jobs.data(), nb * sizeof(MaskJob), hipMemcpyHostToDevice, s));
+        uint64_t terms_chunk = term_lims[g0 + nb] - term_lims[g0];
+        prof_begin(*ws, "mask_where", double(terms_chunk) * double(n) * sizeof(uint32_t) + double(nb) * double(nw) * sizeof(uint64_t));
+        launch_mask_where(ws->keys_a.as<MaskTerm>(), ws->keys_b.as<MaskJob>(), (uint32_t)nb, n, ws->flags.as<uint32_t>(), ws->misc.as<uint32_t>(), s);
+        prof_end(*ws);
+        VDB_HIP(hipMemcpyAsync(h_tot, ws->misc.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        VDB_SYNC(s);
+        uint64_t sum_m = 0;
+        for (uint64_t j = 0; j < nb; j++) {
+            RowMask &m = *out[g0 + j];
+            m.m = h_tot[j];
+            sum_m += m.m;
+            m.d_ids.reserve(std::max<uint64_t>(m.m, 1) * sizeof(uint32_t));
+            h_ids[j] = m.d_ids.as<uint32_t>();
+        }
+        VDB_HIP(hipMemcpyAsync(ws->keys_c.p, h_ids.data(), nb * sizeof(uint32_t *), hipMemcpyHostToDevice, s));
+        prof_begin(*ws, "mask_where", double(nb) * double(nw) * sizeof(uint64_t) + double(sum_m) * sizeof(uint32_t));
+        launch_mask_ids(ws->keys_b.as<MaskJob>(), ws->keys_c.as<uint32_t *>(), (uint32_t)nb, n, ws->flags.as<uint32_t>(), s);
+        prof_end(*ws);
+        VDB_SYNC(s);
+        prof_collect(*ws);
+    }
+    mask_where_masks += n_masks;
 }
 
 // ---- images of the rows (RowMirror): a tier whose image is missing leaves its queries to the next one (8-bit -> fp16 -> split-bf16 ->
@@ -284,6 +414,7 @@ uint64_t Index::hbm_bytes_per_row() const {
     if (rows_q8_m.valid) b += dim + 2 * sizeof(float);
     if (pq.present) b += pq.enc_dim * (pq.codes_t_valid ? 2 : 1);
     if (hnsw.present) b += hnsw.max_m0 * sizeof(uint32_t) + sizeof(uint32_t);
+    b += uint64_t(label_columns()) * sizeof(uint32_t);
     return b;
 }
 

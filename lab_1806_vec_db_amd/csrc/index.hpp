@@ -510,6 +510,23 @@ struct Index {
                                       const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
     void check_mask(const RowMask &mask) const;  // throws: a mask of another index (invalid argument), a stale mask (state)
     const float *masked_rowc(Workspace &ws, const RowMask &mask);  // after ensure_i8 succeeded; builds the copy on first use
+    // Label columns (k_labels.hip, vdb_index_labels_*): LABEL_COLUMNS logical columns of one u32 per LOCAL row, the filterable attributes of
+    // the rows as codes.  A column is allocated by its first write (4 B per row, grown with the rows); one never written reads as
+    // LABEL_NONE for every row and takes no memory.  The allocated columns follow add_rows (new rows: LABEL_NONE), swap_remove and
+    // remove_rows on either element type; writing labels does not bump write_gen (a mask is a set of rows) and touches no PQ / HNSW /
+    // IVF state.
+    DevBuf d_labels[LABEL_COLUMNS];
+    bool label_live[LABEL_COLUMNS] = {};
+    LabelCols label_cols() const;  // the allocated columns
+    uint32_t label_columns() const { return label_cols().n; }
+    void labels_set(uint32_t column, uint64_t first_row, const uint32_t *codes, uint64_t count);  // write-side
+    void labels_get(uint32_t column, uint64_t first_row, uint64_t count, uint32_t *out) const;
+    // Row masks from the labels, on the device: mask g = the rows r with label[columns[t]][r] == codes[t] for every t in
+    // [term_lims[g], term_lims[g + 1]).  Fills out[g] (fresh RowMask objects of the caller) exactly as vdb_mask_create fills a mask from
+    // the equivalent bits; read-side; returns synchronised.  Everything is checked before anything is launched; on a throw the caller
+    // discards every out[g].
+    void masks_where(const uint64_t *term_lims, const uint32_t *columns, const uint32_t *codes, uint64_t n_masks, RowMask *const *out);
+    std::atomic<uint64_t> mask_where_masks{0};  // masks built by masks_where
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};

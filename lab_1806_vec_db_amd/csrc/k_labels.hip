@@ -1,0 +1,137 @@
+// k_labels.hip -- label columns (one u32 per row and column, Index::d_labels) and the row masks built from them on the device
+// (Index::masks_where): upkeep of the columns under add / swap_remove / remove_rows, and the three kernels that turn a conjunction of
+// `column == code` terms into a RowMask's bit words and its ascending allow-list.  docs/DESIGN_flat.md 4.1l.
+#include <algorithm>
+
+#include "kernels.hpp"
+
+namespace vdb {
+
+// ---- upkeep ------------------------------------------------------------------------------------------------------------------------------
+// col[r] = LABEL_NONE for r in [r0, r1) of every column of `cols` (blockIdx.y = column)
+__global__ __launch_bounds__(256) void k_label_fill(LabelCols cols, uint64_t r0, uint64_t r1) {
+    uint32_t *col = cols.col[blockIdx.y];
+    const uint64_t stride = uint64_t(gridDim.x) * 256;
+    for (uint64_t r = r0 + uint64_t(blockIdx.x) * 256 + threadIdx.x; r < r1; r += stride) col[r] = LABEL_NONE;
+}
+
+// col[dst] = col[src] for every move of a removal plan (moves[2 j] = dst, moves[2 j + 1] = src: k_remove.hip) and every column of `cols`
+// (blockIdx.y = column).  Every src lies above every dst, so no lane reads what another writes.  moves == nullptr: the one move
+// (one_dst, one_src) of swap_remove.
+__global__ __launch_bounds__(256) void k_label_move(LabelCols cols, const uint32_t *__restrict__ moves, uint64_t n_moves, uint32_t one_dst,
+                                                    uint32_t one_src) {
+    uint32_t *col = cols.col[blockIdx.y];
+    const uint64_t stride = uint64_t(gridDim.x) * 256;
+    for (uint64_t j = uint64_t(blockIdx.x) * 256 + threadIdx.x; j < n_moves; j += stride) {
+        const uint32_t dst = moves ? moves[2 * j] : one_dst, src = moves ? moves[2 * j + 1] : one_src;
+        col[dst] = col[src];
+    }
+}
+
+void launch_label_fill(const LabelCols &cols, uint64_t r0, uint64_t r1, int num_cu, hipStream_t s) {
+    if (cols.n == 0 || r1 <= r0) return;
+    const unsigned grid = (unsigned)std::min<uint64_t>((r1 - r0 + 255) / 256, uint64_t(num_cu) * 8);
+    hipLaunchKernelGGL(k_label_fill, dim3(grid, cols.n), dim3(256), 0, s, cols, r0, r1);
+}
+void launch_label_move(const LabelCols &cols, const uint32_t *moves, uint64_t n_moves, int num_cu, hipStream_t s) {
+    if (cols.n == 0 || n_moves == 0) return;
+    const unsigned grid = (unsigned)std::min<uint64_t>((n_moves + 255) / 256, uint64_t(num_cu) * 8);
+    hipLaunchKernelGGL(k_label_move, dim3(grid, cols.n), dim3(256), 0, s, cols, moves, n_moves, 0u, 0u);
+}
+void launch_label_move_one(const LabelCols &cols, uint32_t dst, uint32_t src, hipStream_t s) {
+    if (cols.n == 0) return;
+    hipLaunchKernelGGL(k_label_move, dim3(1, cols.n), dim3(256), 0, s, cols, static_cast<const uint32_t *>(nullptr), uint64_t(1), dst, src);
+}
+
+// ---- masks from labels ---------------------------------------------------------------------------------------------------------------------
+// One wave = one mask word, one lane = one row: on a 64-lane wave the ballot of "this row matches" IS the word (bit l = row 64 w + l), so
+// the bit words need no shuffles, no atomics and no LDS.  Grid (ceil(words / 4), masks of the chunk), 256 threads = 4 waves = 4 words.
+// A lane loads its row's value of every term column (4 B per lane, 256 B per wave and term, contiguous), ANDs the comparisons -- rows at
+// and past n are false, so the tail bits of the last word stay clear -- and lane 0 stores the ballot.  A null column (never written)
+// reads as LABEL_NONE for every row; zero terms allow every row.  blockcnt[mask][block] = allowed rows of the block's (up to) four words.
+__global__ __launch_bounds__(256) void k_mask_where(const MaskTerm *__restrict__ terms, const MaskJob *__restrict__ jobs, uint64_t n,
+                                                    uint32_t nwords, uint32_t nblocks, uint32_t *__restrict__ blockcnt) {
+    __shared__ uint32_t s_cnt[4];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const MaskJob job = jobs[blockIdx.y];
+    const uint32_t word = blockIdx.x * 4 + wave;
+    const uint64_t row = uint64_t(word) * 64 + lane;
+    const bool in = row < n;
+    bool ok = in;
+    for (uint32_t t = job.t0; t < job.t1; t++) {  // (wave-uniform)
+        const MaskTerm tm = terms[t];
+        const uint32_t v = (tm.col && in) ? tm.col[row] : LABEL_NONE;
+        ok = ok && v == tm.code;
+    }
+    const uint64_t w = __ballot(ok);
+    if (lane == 0) {
+        if (word < nwords) job.bits[word] = w;
+        s_cnt[wave] = (uint32_t)__popcll(w);  // (a word at or past nwords has no row below n: 0)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) blockcnt[size_t(blockIdx.y) * nblocks + blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// One workgroup per mask: blockcnt[mask][0 .. nblocks) -> its exclusive prefix sums, in place; totals[mask] = the sum (the mask's m).
+// 256 counts per iteration (a shuffle scan inside the wave, the four wave sums through LDS), the running sum carried over iterations.
+__global__ __launch_bounds__(256) void k_mask_scan(uint32_t *__restrict__ blockcnt, uint32_t nblocks, uint32_t *__restrict__ totals) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t *cnt = blockcnt + size_t(blockIdx.x) * nblocks;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < nblocks; base += 256) {  // (block-uniform trip count)
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < nblocks ? cnt[i] : 0;
+        uint32_t incl = v;
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(incl, d);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (uint32_t u = 0; u < 4; u++) {
+            const uint32_t x = s_wave[u];
+            if (u < wave) before += x;
+            all += x;
+        }
+        if (i < nblocks) cnt[i] = carry + before + incl - v;
+        carry += all;
+        __syncthreads();  // (s_wave is rewritten by the next iteration)
+    }
+    if (threadIdx.x == 0) totals[blockIdx.x] = carry;
+}
+
+// Same grid as k_mask_where.  A wave re-reads its word; the lane whose bit is set writes its row at
+//   blockoff[mask][block] + popcounts of the block's earlier words + popcount(word & lanes below):
+// positions ascend with the row, so the allow-list is ascending without a sort.  ids[mask] holds exactly totals[mask] entries.
+__global__ __launch_bounds__(256) void k_mask_ids(const MaskJob *__restrict__ jobs, uint32_t *const *__restrict__ ids, uint32_t nwords,
+                                                  uint32_t nblocks, const uint32_t *__restrict__ blockoff) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t word = blockIdx.x * 4 + wave;
+    if (word >= nwords) return;  // (wave-uniform; no barrier below)
+    const uint64_t *bits = jobs[blockIdx.y].bits;
+    uint32_t *out = ids[blockIdx.y];
+    const uint64_t w = bits[word];
+    if (w == 0) return;
+    uint32_t off = blockoff[size_t(blockIdx.y) * nblocks + blockIdx.x];
+    for (uint32_t u = 0; u < wave; u++) off += (uint32_t)__popcll(bits[blockIdx.x * 4 + u]);
+    if ((w >> lane) & 1) out[off + (uint32_t)__popcll(w & ((1ull << lane) - 1))] = word * 64 + lane;
+}
+
+void launch_mask_where(const MaskTerm *terms, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals,
+                       hipStream_t s) {
+    const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
+    if (n_masks == 0 || nblocks == 0) return;
+    hipLaunchKernelGGL(k_mask_where, dim3(nblocks, n_masks), dim3(256), 0, s, terms, jobs, n, nwords, nblocks, blockcnt);
+    hipLaunchKernelGGL(k_mask_scan, dim3(n_masks), dim3(256), 0, s, blockcnt, nblocks, totals);
+}
+void launch_mask_ids(const MaskJob *jobs, uint32_t *const *ids, uint32_t n_masks, uint64_t n, const uint32_t *blockoff, hipStream_t s) {
+    const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
+    if (n_masks == 0 || nblocks == 0) return;
+    hipLaunchKernelGGL(k_mask_ids, dim3(nblocks, n_masks), dim3(256), 0, s, jobs, ids, nwords, nblocks, blockoff);
+}
+
+}  // namespace vdb

@@ -327,6 +327,35 @@ void launch_mask_rowc(const float *rowc, const uint64_t *bits, uint64_t n, uint6
 void launch_tau_clamp(float *tau, uint32_t nq, hipStream_t s);
 // dist[q * ld + i] = NaN for the rows i < n whose bit is clear
 void launch_mask_dense_nan(float *dist, uint64_t ld, uint64_t n, uint32_t nq, const uint64_t *bits, hipStream_t s);
+// k_labels.hip: label columns (Index::d_labels) and the row masks built from them on the device (Index::masks_where)
+constexpr uint32_t LABEL_COLUMNS = 16;       // VDB_LABEL_COLUMNS
+constexpr uint32_t LABEL_NONE = 0xFFFFFFFFu;  // VDB_LABEL_NONE: a row without a value in that column
+constexpr uint32_t MASK_MAX_TERMS = 8;        // VDB_MASK_MAX_TERMS
+struct LabelCols {  // the allocated columns of an index (kernel argument, by value)
+    uint32_t *col[LABEL_COLUMNS];
+    uint32_t n;
+};
+struct MaskTerm {
+    const uint32_t *col;  // the term's column, nullptr: never written (every row reads LABEL_NONE)
+    uint32_t code;
+};
+struct MaskJob {
+    uint64_t *bits;   // the mask's d_bits
+    uint32_t t0, t1;  // its terms: [t0, t1) of the term table
+};
+// col[r] = LABEL_NONE, r0 <= r < r1, in every column of cols
+void launch_label_fill(const LabelCols &cols, uint64_t r0, uint64_t r1, int num_cu, hipStream_t s);
+// col[moves[2 j]] = col[moves[2 j + 1]], j < n_moves, in every column of cols (the move list of launch_rows_move) / the one move dst <- src
+void launch_label_move(const LabelCols &cols, const uint32_t *moves, uint64_t n_moves, int num_cu, hipStream_t s);
+void launch_label_move_one(const LabelCols &cols, uint32_t dst, uint32_t src, hipStream_t s);
+// workgroups per mask of the mask kernels = entries per mask of blockcnt: four 64-row words each
+inline uint32_t mask_where_blocks(uint64_t n) { return (uint32_t)(((n + 63) / 64 + 3) / 4); }
+// bit words of n_masks masks over rows [0, n) from their terms, then blockcnt [n_masks][mask_where_blocks(n)] = exclusive prefix of the
+// allowed rows per block and totals[g] = allowed rows of mask g  (k_mask_where + k_mask_scan; n_masks <= 65535)
+void launch_mask_where(const MaskTerm *terms, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals,
+                       hipStream_t s);
+// ids[g][0 .. totals[g]) = the allowed rows of mask g, ascending (k_mask_ids; after launch_mask_where on the same stream)
+void launch_mask_ids(const MaskJob *jobs, uint32_t *const *ids, uint32_t n_masks, uint64_t n, const uint32_t *blockoff, hipStream_t s);
 void mfma_set_sample_thin(int v);
 void mfma_sample_plan(uint64_t n, uint32_t kprime, uint32_t *step, uint32_t *rank, uint32_t target_floor = 1024);  // target_floor: expected hits per query
 uint64_t mfma_sample_rows(uint64_t n, uint32_t step);

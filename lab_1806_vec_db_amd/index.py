@@ -71,6 +71,20 @@ def pack_mask(allow, n: int) -> np.ndarray:
     return np.packbits(padded, bitorder="little").view(np.uint64).copy() if nw else np.zeros(0, dtype=np.uint64)
 
 
+LABEL_COLUMNS = 16         # VDB_LABEL_COLUMNS
+LABEL_NONE = 0xFFFFFFFF    # VDB_LABEL_NONE
+MASK_MAX_TERMS = 8         # VDB_MASK_MAX_TERMS
+
+
+def _terms_arrays(terms):
+    """(columns, codes) as u32 arrays of a sequence of (column, code) terms"""
+    t = [(int(c), int(v)) for c, v in terms]
+    for c, v in t:
+        if not (0 <= c < 2 ** 32 and 0 <= v < 2 ** 32):
+            raise ValueError(f"mask term ({c}, {v}): column and code are u32")
+    return (np.array([c for c, _ in t], dtype=np.uint32), np.array([v for _, v in t], dtype=np.uint32))
+
+
 class RowMask:
     """An allow-list over the rows of one GpuIndex (vdb_mask): made by GpuIndex.make_mask, valid until rows are added to or removed
     from the index, closed before the index is."""
@@ -83,6 +97,27 @@ class RowMask:
         v = C.c_uint64()
         L.check(self._lib.vdb_mask_count(self._h, C.byref(v)))
         self._m = int(v.value)
+        self._n = int(n)
+
+    @classmethod
+    def from_handle(cls, index: "GpuIndex", handle) -> "RowMask":
+        """wraps a vdb_mask the library made (vdb_mask_create_where*); the object owns the handle from here on"""
+        self = cls.__new__(cls)
+        self._lib = index._lib
+        self._h = handle if isinstance(handle, L.vp) else L.vp(handle)
+        v = C.c_uint64()
+        L.check(self._lib.vdb_mask_count(self._h, C.byref(v)))
+        self._m = int(v.value)
+        self._n = len(index)
+        return self
+
+    def rows(self):
+        """(words, ids) of the mask read back from the device (vdb_mask_rows): the u64 bit words over the rows and the u32 ids of the
+        allowed rows, ascending"""
+        words = np.zeros((self._n + 63) // 64, dtype=np.uint64)
+        ids = np.zeros(self._m, dtype=np.uint32)
+        L.check(self._lib.vdb_mask_rows(self._h, _ptr(words, L.u64p), _ptr(ids, L.u32p)))
+        return words, ids
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -272,6 +307,38 @@ class GpuIndex:
         """a row mask for the filtered searches: `allow` is a bool array over the rows or an array of (local) row ids (pack_mask)"""
         n = len(self)
         return RowMask(self, pack_mask(allow, n), n)
+
+    # -- row labels; masks built from them on the device -----------------------------------------------
+    def set_labels(self, column: int, codes, first_row: int = 0):
+        """rows [first_row, first_row + len(codes)) of label column `column` (vdb_index_labels_set): u32 codes, LABEL_NONE = no value"""
+        c = np.ascontiguousarray(np.asarray(codes).reshape(-1), dtype=np.uint32)
+        L.check(self._lib.vdb_index_labels_set(self._h, int(column), int(first_row), _ptr(c, L.u32p), c.shape[0]))
+
+    def get_labels(self, column: int, first_row: int = 0, count: int | None = None) -> np.ndarray:
+        """the codes of rows [first_row, first_row + count) of one column (to the last row by default); LABEL_NONE where never written"""
+        cnt = max(len(self) - int(first_row), 0) if count is None else int(count)
+        out = np.zeros(cnt, dtype=np.uint32)
+        L.check(self._lib.vdb_index_labels_get(self._h, int(column), int(first_row), cnt, _ptr(out, L.u32p)))
+        return out
+
+    def make_mask_where(self, terms) -> RowMask:
+        """the mask of the rows whose label in column c equals code for EVERY (c, code) of `terms`, built on the device
+        (vdb_mask_create_where); no terms: every row"""
+        cols, codes = _terms_arrays(terms)
+        h = L.vp()
+        L.check(self._lib.vdb_mask_create_where(self._h, _ptr(cols, L.u32p), _ptr(codes, L.u32p), cols.shape[0], C.byref(h)))
+        return RowMask.from_handle(self, h)
+
+    def make_masks_where(self, list_of_terms) -> list[RowMask]:
+        """one mask per entry of `list_of_terms` (each a sequence of (column, code)) in ONE library call (vdb_mask_create_where_many);
+        all-or-nothing: an invalid entry raises and no mask is made"""
+        lists = [list(t) for t in list_of_terms]
+        lims = np.zeros(len(lists) + 1, dtype=np.uint64)
+        lims[1:] = np.cumsum([len(t) for t in lists], dtype=np.uint64)
+        cols, codes = _terms_arrays([tm for t in lists for tm in t])
+        arr = (L.vp * max(len(lists), 1))()
+        L.check(self._lib.vdb_mask_create_where_many(self._h, _ptr(lims, L.u64p), _ptr(cols, L.u32p), _ptr(codes, L.u32p), len(lists), arr))
+        return [RowMask.from_handle(self, arr[g]) for g in range(len(lists))]
 
     def flat_knn_filtered(self, queries, k: int, mask: RowMask):
         """Exact k-NN over the mask's allowed rows alone (vdb_flat_knn_filtered): the first min(k, len(mask)) pairs of flat_knn

@@ -17,6 +17,9 @@ Semantics reproduced from src/database/metadata_vec_table.rs:
 Beyond the reference: search_within(key, query, upper_bound) returns the COMPLETE set inside the bound (exact Flat range search);
 search / search_within take `filter`, a metadata pattern matched as delete matches: only matching rows are searched, exactly;
 batch_search(key, queries, k, ..., filters) answers a batch of queries, each under a pattern of its own, in one library call.
+The keys filter patterns use are kept on the device as integer label columns (labels.py: a key gets a column when a pattern first names
+it, one pass over the metadata; add / delete keep the columns in step), and the patterns' row masks are built there
+(GpuIndex.make_masks_where); a pattern the columns cannot express (a 17th key, more than 8 keys) is matched on the host as before.
 """
 from __future__ import annotations
 
@@ -27,6 +30,7 @@ import numpy as np
 
 from ._lib import VdbError
 from .index import GpuIndex, RowMask, parse_dist
+from .labels import LabelCodec
 
 _DIST_STR = {0: "l2sqr", 1: "cosine"}
 
@@ -84,17 +88,67 @@ class _Table:
         # mask_mu by searches (which hold the READ lock, several at a time), closed and cleared by every write under the WRITE lock
         self.masks: dict[frozenset, RowMask] = {}
         self.mask_mu = threading.Lock()
+        # which metadata keys are label columns of the index, and the value -> code dictionary of each: changed under the WRITE lock only
+        self.codec = LabelCodec()
+
+    def host_match(self, pattern: dict[str, str]) -> np.ndarray:
+        """the host loop: a bool per row, True where the metadata holds every key of `pattern` with an equal value"""
+        return np.fromiter((all(m.get(k) == v for k, v in pattern.items()) for m in self.metadata), dtype=np.bool_, count=len(self.metadata))
+
+    def live_terms(self, pattern):
+        """the pattern's (column, code) terms when every key has a label column (labels.py: terms), else None"""
+        return self.codec.terms(pattern)
+
+    def create_columns(self, patterns) -> None:
+        """UNDER THE WRITE LOCK: gives the keys of every expressible pattern their label columns -- one pass over the metadata per new
+        key to encode it, then set_labels.  Patterns that cannot be expressed are left to the host loop."""
+        for p in patterns:
+            new = self.codec.assign(p) or []
+            for i, k in enumerate(new):
+                try:
+                    self.index.set_labels(self.codec.column_of(k), self.codec.encode_rows(k, self.metadata))
+                except BaseException:
+                    self.codec.unassign(new[i:])  # a column that was not written is no column: the host loop answers
+                    raise
+
+    def prepare(self, patterns) -> None:
+        """BEFORE the read lock of a search is taken: a key a pattern names for the first time gets its column under the WRITE lock --
+        readers build masks from the columns and read the codec's dictionaries, so nobody may be reading while one is made.  Two
+        threads that first-use a key at once both come here; the second finds the column made.  The check itself only reads the
+        codec, which changes under the write lock alone: a stale answer costs a useless turn through the lock, nothing else."""
+        if all(not self.codec.missing(p) or not self.codec.expressible(p) for p in patterns):
+            return
+        with self.lock.write():
+            self.create_columns(patterns)
 
     def mask_for(self, pattern: dict[str, str]) -> RowMask:
-        """the mask of the rows whose metadata holds every key of `pattern` with an equal value (an empty pattern: every row)"""
+        """the mask of the rows whose metadata holds every key of `pattern` with an equal value (an empty pattern: every row): built on
+        the device from the label columns when every key of the pattern has one, else from the host loop"""
         key = frozenset(pattern.items())
         with self.mask_mu:
             mk = self.masks.get(key)
             if mk is None:
-                allow = np.fromiter((all(m.get(k) == v for k, v in pattern.items()) for m in self.metadata), dtype=np.bool_,
-                                    count=len(self.metadata))
-                mk = self.masks[key] = self.index.make_mask(allow)
+                terms = self.live_terms(pattern)
+                if terms is not None:
+                    mk = self.masks[key] = self.index.make_mask_where(terms)
+                else:
+                    mk = self.masks[key] = self.index.make_mask(self.host_match(pattern))
             return mk
+
+    def masks_for(self, patterns) -> list[RowMask]:
+        """mask_for for many patterns: the ones not cached yet whose keys all have columns are built by ONE make_masks_where call"""
+        with self.mask_mu:
+            todo: dict[frozenset, list] = {}
+            for p in patterns:
+                key = frozenset(p.items())
+                if key not in self.masks and key not in todo:
+                    terms = self.live_terms(p)
+                    if terms is not None:
+                        todo[key] = terms
+            if todo:
+                for key, mk in zip(todo, self.index.make_masks_where(list(todo.values()))):
+                    self.masks[key] = mk
+        return [self.mask_for(p) for p in patterns]
 
     def drop_masks(self):
         with self.mask_mu:
@@ -182,8 +236,11 @@ class VecDB:
         with t.lock.write():
             t.drop_masks()
             t.index.pq_clear()  # metadata_vec_table.rs:65,77
+            first = len(t.metadata)
             t.metadata.extend(dict(m) for m in metadata_list)
             t.index.batch_add(rows)
+            for k in t.codec.keys():  # the new rows' values of the live columns (the library left them unlabelled)
+                t.index.set_labels(t.codec.column_of(k), t.codec.encode_rows(k, t.metadata[first:]), first_row=first)
 
     def delete(self, key: str, pattern: dict[str, str]) -> int:
         t = self._t(key)
@@ -191,7 +248,15 @@ class VecDB:
             t.drop_masks()
             t.index.hnsw_clear()  # :170
             t.index.pq_clear()    # :171
-            matches = [i for i, m in enumerate(t.metadata) if all(m.get(k) == v for k, v in pattern.items())]
+            # the matches from the device mask of the pattern when its keys are label columns already (a delete gives no key a column:
+            # deleting by id must not intern every id); the columns follow the removal inside the library
+            terms = t.live_terms(pattern)
+            if terms is not None:
+                mk = t.index.make_mask_where(terms)
+                matches = mk.rows()[1].tolist()
+                mk.close()
+            else:
+                matches = np.flatnonzero(t.host_match(pattern)).tolist()
             if matches:  # one call; the metadata follow the moves it reports (the net effect of swap_remove in descending order)
                 dst, src = t.index.remove_rows(matches)
                 for d, s in zip(dst.tolist(), src.tolist()):
@@ -259,6 +324,8 @@ class VecDB:
         t = self._t(key)
         ix = t.index
         q = np.asarray(query, dtype=np.float32).ravel()
+        if filter is not None:
+            t.prepare([filter])
         with t.lock.read():  # database/mod.rs:255: read guard for the whole search, metadata lookup included
             if filter is not None:
                 idx, dist = ix.flat_knn_filtered(q, k, t.mask_for(filter))
@@ -291,17 +358,21 @@ class VecDB:
                 raise RuntimeError(f"filters: one pattern per query is needed ({nq}), got {len(filters)}")
         if nq == 0:
             return []
+        pats = None
+        if filters is not None:
+            pats = [filters] * nq if isinstance(filters, dict) else filters
+            t.prepare(pats)
         with t.lock.read():  # one read guard for the whole batch, mask building and metadata lookup included
-            if filters is not None:
-                pats = [filters] * nq if isinstance(filters, dict) else filters
+            if pats is not None:
                 slot: dict[frozenset, int] = {}
-                masks, mask_of = [], np.zeros(nq, dtype=np.uint32)
+                distinct, mask_of = [], np.zeros(nq, dtype=np.uint32)
                 for i, p in enumerate(pats):
                     pk = frozenset(p.items())
                     if pk not in slot:
-                        slot[pk] = len(masks)
-                        masks.append(t.mask_for(p))
+                        slot[pk] = len(distinct)
+                        distinct.append(p)
                     mask_of[i] = slot[pk]
+                masks = t.masks_for(distinct)  # the ones not cached yet: one library call
                 idx, dist, cnt = ix.flat_knn_filtered_multi(q, k, masks, mask_of)
             elif ef is not None and ix.has_pq():
                 idx, dist, cnt = ix.knn_pq(q, k, ef)
@@ -320,6 +391,8 @@ class VecDB:
         `filter`: a metadata pattern as in search -- only matching rows are returned."""
         t = self._t(key)
         q = np.asarray(query, dtype=np.float32).ravel()
+        if filter is not None:
+            t.prepare([filter])
         with t.lock.read():
             if filter is not None:
                 _, idx, dist = t.index.range_search(q, np.float32(upper_bound), limit, mask=t.mask_for(filter))
