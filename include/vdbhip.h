@@ -242,8 +242,30 @@ int vdb_flat_range_filtered(vdb_index *idx, const float *queries, uint64_t nq, u
  * and k_mask_ids writes every allowed row at its offset: ascending without a sort.  Traffic per mask: 4 B x terms x rows read, rows / 8
  * + 4 m written.  vdb_prof_get "mask_where" times the three kernels; vdb_get_stat "mask_where_masks" counts the masks built this way,
  * "label_columns" the allocated columns ("hbm_bytes_per_row" includes them).
- * Not covered: sharded and replica contexts, range or set predicates (equality conjunctions only), a single-pass partition of one
- * column into the masks of all its values, labels in bincode files. */
+ * SET AND RANGE TERMS (vdb_mask_create_where_sets / _many; csrc/mask_sets.hpp, k_mask_where_sets, docs/DESIGN_flat.md 4.1m): a term is
+ * {column, lo, hi, flags, bitmap} and a mask the conjunction of its terms.  A row whose label in the column is v matches the term
+ *   - when v == VDB_LABEL_NONE (no value, or a column never written): iff flags has VDB_TERM_NONE; VDB_TERM_NEGATE never inverts this;
+ *   - otherwise: inside = lo <= v <= hi and (no bitmap, or bit (v - lo) of the bitmap); it matches iff inside != (flags has VDB_TERM_NEGATE).
+ * Any predicate on one attribute is a set of its codes plus "rows without a value": the host evaluates the predicate over its dictionary
+ * (one entry per distinct value), the device tests one bit per row -- IN, NOT IN, !=, order comparisons, existence.  Un-interned integers
+ * (timestamps) need no bitmap: [lo, hi] is the range.  The equality term (c, code) of vdb_mask_create_where is {lo = hi = code, flags 0};
+ * its term (c, VDB_LABEL_NONE) is {lo = 1, hi = 0, flags VDB_TERM_NONE}; both give bit-identical masks.
+ * term_lims as in vdb_mask_create_where_many.  set_lims: n_terms + 1 word offsets into set_words, set_lims[0] == 0, non-decreasing; term t
+ * carries a bitmap iff set_lims[t + 1] > set_lims[t], must then have lo <= hi and exactly ceil((uint64_t(hi) - lo + 1) / 64) words; bit j
+ * of the bitmap stands for code lo + j, bits past hi - lo in the last word are ignored.  set_lims == NULL: no term has a bitmap
+ * (set_words is not read).  A term without a bitmap and lo > hi is the empty range: legal, it matches nothing, or with VDB_TERM_NEGATE
+ * every labelled row.  hi == 0xFFFFFFFF is legal (a labelled row never carries that value).  n_terms == 0 allows every row.
+ * Everything is checked before anything is launched; VDB_ERR_INVALID with a message, every out[g] NULL, index and counters unchanged for:
+ * more than VDB_MASK_MAX_TERMS terms in a mask, a column >= VDB_LABEL_COLUMNS, unknown flag bits, set_lims not starting at 0 or
+ * decreasing, a bitmap on a term with lo > hi, a bitmap whose length does not match its span (computed in 64 bits), more than
+ * VDB_MASK_MAX_SET_BITS bitmap bits in the call.  n_masks == 0 succeeds.  Read-side, all-or-nothing and chunked like
+ * vdb_mask_create_where_many; the term table and all bitmaps of the call are uploaded once.  The result is the same vdb_mask object:
+ * owner / staleness rules, lazily built row constants, f32 and VecSet<u8> indexes, every call that takes a vdb_mask.  Traffic per mask:
+ * 4 B x terms x rows read as before plus one 8-byte bitmap gather per in-range row and bitmap term (from a block that stays cached).
+ * vdb_get_stat "mask_where_set_masks" counts the masks built by these two calls ("mask_where_masks" keeps counting the equality calls
+ * only); vdb_prof_get "mask_where_sets" times k_mask_where_sets with its scan and ids launches.
+ * Not covered: sharded and replica contexts, OR across columns and mask algebra (a mask is one conjunction), a single-pass partition of
+ * one column into the masks of all its values, labels in bincode files, filtered k-NN on VecSet<u8> indexes. */
 #define VDB_LABEL_COLUMNS 16
 #define VDB_LABEL_NONE 0xFFFFFFFFu
 #define VDB_MASK_MAX_TERMS 8
@@ -252,6 +274,14 @@ int vdb_index_labels_get(const vdb_index *idx, uint32_t column, uint64_t first_r
 int vdb_mask_create_where(vdb_index *idx, const uint32_t *columns, const uint32_t *codes, uint64_t n_terms, vdb_mask **out);
 int vdb_mask_create_where_many(vdb_index *idx, const uint64_t *term_lims, const uint32_t *columns, const uint32_t *codes,
                                uint64_t n_masks, vdb_mask **out);
+#define VDB_TERM_NEGATE 1u
+#define VDB_TERM_NONE 2u
+#define VDB_MASK_MAX_SET_BITS (1ull << 27) /* bitmap bits per call, 16 MiB */
+int vdb_mask_create_where_sets(vdb_index *idx, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi, const uint32_t *flags,
+                               const uint64_t *set_lims, const uint64_t *set_words, uint64_t n_terms, vdb_mask **out);
+int vdb_mask_create_where_sets_many(vdb_index *idx, const uint64_t *term_lims, const uint32_t *columns, const uint32_t *lo,
+                                    const uint32_t *hi, const uint32_t *flags, const uint64_t *set_lims, const uint64_t *set_words,
+                                    uint64_t n_masks, vdb_mask **out);
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids);
 /* the approximate keys the Flat shortlist pass compares with its threshold, for EVERY row, from the same kernel in its dense
  * mode (test / measurement entry point behind the certification-bound tests): out_keys [nq][len];
@@ -349,7 +379,8 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *   "ivf_last_offers", "ivf_last_kept_q8", "ivf_last_kept"  (while vdb_prof_enable is on) rows the last IVF call offered to its result
  *                        sets, the ones the 8-bit tier passed on (0: tier not run) and the ones that reached the exact stage; "ivf_last_rows_fetched_q8":
  *                        rows the cluster-major 8-bit tier read, once each (0: query-major),
- *   "mask_where_masks"   masks built on the device from the label columns (vdb_mask_create_where*); "label_columns": allocated columns,
+ *   "mask_where_masks"   masks built on the device from the label columns (vdb_mask_create_where*); "mask_where_set_masks": the ones
+ *                        built from set / range terms (vdb_mask_create_where_sets*); "label_columns": allocated columns,
  *   "hbm_bytes_per_row"  resident HBM bytes per row over all per-row buffers (rows, norms, mirrors, PQ codes, level-0 links, label
  *                        columns). */
 int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out);

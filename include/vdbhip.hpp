@@ -196,6 +196,28 @@ public:
         check(vdb_mask_create_where(h_, cols.data(), codes.data(), terms.size(), &m));
         return Mask(m);
     }
+    // set / range terms (vdb_mask_create_where_sets): a row with label v in `column` matches a term when v == VDB_LABEL_NONE ? none
+    // : (lo <= v <= hi && (set.empty() || bit (v - lo) of set)) != negate; `set` is empty or ceil((hi - lo + 1) / 64) words
+    struct LabelTerm {
+        uint32_t column = 0, lo = 1, hi = 0;
+        bool negate = false, none = false;
+        std::vector<uint64_t> set;
+    };
+    Mask make_mask_where_sets(const std::vector<LabelTerm> &terms) const {
+        std::vector<uint32_t> cols, lo, hi, flags;
+        std::vector<uint64_t> lims{0}, words;
+        for (const auto &t : terms) {
+            cols.push_back(t.column);
+            lo.push_back(t.lo);
+            hi.push_back(t.hi);
+            flags.push_back((t.negate ? VDB_TERM_NEGATE : 0u) | (t.none ? VDB_TERM_NONE : 0u));
+            words.insert(words.end(), t.set.begin(), t.set.end());
+            lims.push_back(words.size());
+        }
+        vdb_mask *m = nullptr;
+        check(vdb_mask_create_where_sets(h_, cols.data(), lo.data(), hi.data(), flags.data(), lims.data(), words.data(), terms.size(), &m));
+        return Mask(m);
+    }
     // per query the first min(k, mask.count()) pairs of knn_batch over the allowed rows alone (vdb_flat_knn_filtered)
     std::vector<std::vector<CandidatePair>> knn_filtered_batch(const float *queries, uint64_t nq, uint64_t k, const Mask &mask) const {
         std::vector<uint64_t> idx(nq * (k ? k : 1)), cnt(nq);

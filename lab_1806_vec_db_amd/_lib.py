@@ -57,6 +57,8 @@ SIGNATURES = {
     "vdb_index_labels_get": [vp, C.c_uint32, u64, u64, u32p],
     "vdb_mask_create_where": [vp, u32p, u32p, u64, C.POINTER(vp)],
     "vdb_mask_create_where_many": [vp, u64p, u32p, u32p, u64, C.POINTER(vp)],
+    "vdb_mask_create_where_sets": [vp, u32p, u32p, u32p, u32p, u64p, u64p, u64, C.POINTER(vp)],
+    "vdb_mask_create_where_sets_many": [vp, u64p, u32p, u32p, u32p, u32p, u64p, u64p, u64, C.POINTER(vp)],
     "vdb_mask_rows": [vp, u64p, u32p],
     "vdb_flat_knn_filtered": [vp, f32p, u64, u64, u64, vp, u64p, f32p, u64p],
     "vdb_flat_knn_filtered_device": [vp, vp, u64, u64, u64, vp, vp, vp, vp, vp],

@@ -659,6 +659,36 @@ int vdb_mask_create_where(vdb_index *idx, const uint32_t *columns, const uint32_
     return vdb_mask_create_where_many(idx, lims, columns, codes, 1, out);
     VDB_API_END
 }
+// set / range terms (Index::masks_where_sets, mask_sets.hpp)
+static_assert(TERM_NEGATE == VDB_TERM_NEGATE && TERM_NONE == VDB_TERM_NONE && MASK_MAX_SET_BITS == VDB_MASK_MAX_SET_BITS, "vdbhip.h and mask_sets.hpp agree");
+int vdb_mask_create_where_sets_many(vdb_index *idx, const uint64_t *term_lims, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi,
+                                    const uint32_t *flags, const uint64_t *set_lims, const uint64_t *set_words, uint64_t n_masks, vdb_mask **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    VDB_REQUIRE(n_masks == 0 || out, "null argument");
+    for (uint64_t g = 0; g < n_masks; g++) out[g] = nullptr;
+    VDB_REQUIRE(n_masks < (1ull << 28), "too many masks for one call");
+    std::vector<std::unique_ptr<vdb_mask>> made(n_masks);
+    std::vector<RowMask *> rm(n_masks);
+    for (uint64_t g = 0; g < n_masks; g++) {
+        made[g].reset(new vdb_mask);
+        rm[g] = &made[g]->m;
+    }
+    idx->ix.masks_where_sets(term_lims, columns, lo, hi, flags, set_lims, set_words, n_masks, rm.data());  // a throw destroys every mask with `made`
+    for (uint64_t g = 0; g < n_masks; g++) out[g] = made[g].release();
+    VDB_API_END
+}
+int vdb_mask_create_where_sets(vdb_index *idx, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi, const uint32_t *flags,
+                               const uint64_t *set_lims, const uint64_t *set_words, uint64_t n_terms, vdb_mask **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx && out, "null argument");
+    *out = nullptr;
+    VDB_REQUIRE(n_terms <= MASK_MAX_TERMS, "mask terms: " + std::to_string(n_terms) + " terms, at most " + std::to_string(MASK_MAX_TERMS) +
+                                               " are supported");
+    const uint64_t lims[2] = {0, n_terms};
+    return vdb_mask_create_where_sets_many(idx, lims, columns, lo, hi, flags, set_lims, set_words, 1, out);
+    VDB_API_END
+}
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids) {
     VDB_API_BEGIN
     VDB_REQUIRE(m, "null mask");
@@ -1127,6 +1157,8 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.pq.q8_hits_max.load();
     else if (n == "mask_where_masks")  // masks built on the device from the label columns (vdb_mask_create_where*)
         *out = idx->ix.mask_where_masks.load();
+    else if (n == "mask_where_set_masks")  // masks built from set / range terms (vdb_mask_create_where_sets*)
+        *out = idx->ix.mask_where_set_masks.load();
     else if (n == "label_columns")  // allocated label columns (4 B per row each)
         *out = idx->ix.label_columns();
     else if (n == "hbm_bytes_per_row")

@@ -368,6 +368,83 @@ void Index::masks_where(const uint64_t *term_lims, const uint32_t *columns, cons
     mask_where_masks += n_masks;
 }
 
+// The same call shape for set / range terms (mask_sets.hpp checks and lays out; k_mask_where_sets evaluates): the chunking, the single
+// read-back of the totals per chunk and the all-or-nothing behaviour of masks_where.  The term table and, behind it in the same buffer,
+// the packed bitmaps of the WHOLE call are uploaded once, before the first chunk.
+void Index::masks_where_sets(const uint64_t *term_lims, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi, const uint32_t *flags,
+                             const uint64_t *set_lims, const uint64_t *set_words, uint64_t n_masks, RowMask *const *out) {
+    VDB_REQUIRE(n_masks == 0 || out, "null argument");
+    uint64_t n_terms = 0, n_set_words = 0;
+    const std::string bad = mask_sets_check(term_lims, columns, lo, hi, flags, set_lims, set_words, n_masks, &n_terms, &n_set_words);
+    VDB_REQUIRE(bad.empty(), bad);
+    if (n_masks == 0) return;
+    use_device();
+    WsLease ws(*this);
+    hipStream_t s = ws->stream;
+    const uint64_t nw = (n + 63) / 64;
+    const uint32_t nblocks = mask_where_blocks(n);
+    const uint64_t gen = write_gen.load();
+    const uint64_t chunk = nblocks ? std::min<uint64_t>({n_masks, 1024, std::max<uint64_t>((64ull << 20) / (sizeof(uint32_t) * nblocks), 1)}) : n_masks;
+    std::vector<MaskJob> h_jobs(chunk);
+    std::vector<uint32_t *> h_ids(chunk);
+    std::vector<SetTerm> h_terms;
+    if (nblocks) {  // (contents not preserved by reserve: everything a chunk needs is sized here, once)
+        const size_t term_bytes = std::max<uint64_t>(n_terms, 1) * sizeof(SetTerm);  // (a multiple of 8: the bitmaps behind it are aligned)
+        ws->keys_a.reserve(term_bytes + n_set_words * sizeof(uint64_t));
+        ws->keys_b.reserve(chunk * sizeof(MaskJob));
+        ws->keys_c.reserve(chunk * sizeof(uint32_t *));
+        ws->flags.reserve(chunk * nblocks * sizeof(uint32_t));
+        ws->misc.reserve(chunk * sizeof(uint32_t));
+        const uint64_t *d_sets = reinterpret_cast<const uint64_t *>(ws->keys_a.as<char>() + term_bytes);
+        const uint32_t *col_ptrs[LABEL_COLUMNS];
+        for (uint32_t c = 0; c < LABEL_COLUMNS; c++) col_ptrs[c] = label_live[c] ? d_labels[c].as<uint32_t>() : nullptr;
+        mask_sets_layout(columns, lo, hi, flags, set_lims, n_terms, col_ptrs, d_sets, h_terms);
+        if (n_terms) VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_terms.data(), n_terms * sizeof(SetTerm), hipMemcpyHostToDevice, s));
+        if (n_set_words)
+            VDB_HIP(hipMemcpyAsync(ws->keys_a.as<char>() + term_bytes, set_words, n_set_words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    }
+    for (uint64_t g0 = 0; g0 < n_masks; g0 += chunk) {
+        const uint64_t nb = std::min(chunk, n_masks - g0);
+        for (uint64_t j = 0; j < nb; j++) {
+            RowMask &m = *out[g0 + j];
+            m.owner = this;
+            m.device = device;
+            m.gen = gen;
+            m.n_rows = n;
+            m.m = 0;
+            m.d_bits.reserve(std::max<uint64_t>(nw, 1) * sizeof(uint64_t));
+            h_jobs[j] = {m.d_bits.as<uint64_t>(), (uint32_t)term_lims[g0 + j], (uint32_t)term_lims[g0 + j + 1]};
+        }
+        if (!nblocks) {  // an empty index: masks with m = 0
+            for (uint64_t j = 0; j < nb; j++) out[g0 + j]->d_ids.reserve(sizeof(uint32_t));
+            continue;
+        }
+        uint32_t *h_tot = static_cast<uint32_t *>(ws->pinned(chunk * sizeof(uint32_t)));
+        VDB_HIP(hipMemcpyAsync(ws->keys_b.p, h_jobs.data(), nb * sizeof(MaskJob), hipMemcpyHostToDevice, s));
+        uint64_t terms_chunk = term_lims[g0 + nb] - term_lims[g0];
+        prof_begin(*ws, "mask_where_sets", double(terms_chunk) * double(n) * sizeof(uint32_t) + double(nb) * double(nw) * sizeof(uint64_t));
+        launch_mask_where_sets(ws->keys_a.as<SetTerm>(), ws->keys_b.as<MaskJob>(), (uint32_t)nb, n, ws->flags.as<uint32_t>(), ws->misc.as<uint32_t>(), s);
+        prof_end(*ws);
+        VDB_HIP(hipMemcpyAsync(h_tot, ws->misc.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        VDB_SYNC(s);
+        uint64_t sum_m = 0;
+        for (uint64_t j = 0; j < nb; j++) {
+            RowMask &m = *out[g0 + j];
+            m.m = h_tot[j];
+            sum_m += m.m;
+            m.d_ids.reserve(std::max<uint64_t>(m.m, 1) * sizeof(uint32_t));
+            h_ids[j] = m.d_ids.as<uint32_t>();
+        }
+        VDB_HIP(hipMemcpyAsync(ws->keys_c.p, h_ids.data(), nb * sizeof(uint32_t *), hipMemcpyHostToDevice, s));
+        prof_begin(*ws, "mask_where_sets", double(nb) * double(nw) * sizeof(uint64_t) + double(sum_m) * sizeof(uint32_t));
+        launch_mask_ids(ws->keys_b.as<MaskJob>(), ws->keys_c.as<uint32_t *>(), (uint32_t)nb, n, ws->flags.as<uint32_t>(), s);
+        prof_end(*ws);
+        VDB_SYNC(s);
+        prof_collect(*ws);
+    }
+    mask_where_set_masks += n_masks;
+}
+
 // ---- images of the rows (RowMirror): a tier whose image is missing leaves its queries to the next one (8-bit -> fp16 -> split-bf16 ->
 // exact scan over the rows themselves; IVF scan: 8-bit -> fp16 -> f32 rows)
 bool RowMirror::attempt(const std::function<void()> &build) {

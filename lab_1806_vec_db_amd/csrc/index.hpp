@@ -527,6 +527,11 @@ struct Index {
     // discards every out[g].
     void masks_where(const uint64_t *term_lims, const uint32_t *columns, const uint32_t *codes, uint64_t n_masks, RowMask *const *out);
     std::atomic<uint64_t> mask_where_masks{0};  // masks built by masks_where
+    // The same for set / range terms {columns[t], lo[t], hi[t], flags[t], bitmap words [set_lims[t], set_lims[t + 1]) of set_words}
+    // (mask_sets.hpp states the match and checks the arguments; set_lims == nullptr: no term has a bitmap).  Same contract as masks_where.
+    void masks_where_sets(const uint64_t *term_lims, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi, const uint32_t *flags,
+                          const uint64_t *set_lims, const uint64_t *set_words, uint64_t n_masks, RowMask *const *out);
+    std::atomic<uint64_t> mask_where_set_masks{0};  // masks built by masks_where_sets
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};

@@ -1,6 +1,7 @@
 // k_labels.hip -- label columns (one u32 per row and column, Index::d_labels) and the row masks built from them on the device
 // (Index::masks_where): upkeep of the columns under add / swap_remove / remove_rows, and the three kernels that turn a conjunction of
-// `column == code` terms into a RowMask's bit words and its ascending allow-list.  docs/DESIGN_flat.md 4.1l.
+// `column == code` terms into a RowMask's bit words and its ascending allow-list (docs/DESIGN_flat.md 4.1l), and the kernel that does the
+// same for set / range terms (Index::masks_where_sets, mask_sets.hpp; 4.1m).
 #include <algorithm>
 
 #include "kernels.hpp"
@@ -72,6 +73,41 @@ __global__ __launch_bounds__(256) void k_mask_where(const MaskTerm *__restrict__
     if (threadIdx.x == 0) blockcnt[size_t(blockIdx.y) * nblocks + blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
+// The same wave-per-word structure for SET / RANGE terms (mask_sets.hpp; docs/DESIGN_flat.md 4.1m): a term is {col, lo, hi, flags,
+// bitmap}.  A row without a value (LABEL_NONE, or a null column) matches iff the term has TERM_NONE, whatever TERM_NEGATE says; a
+// labelled row is inside when lo <= v <= hi and, with a bitmap, bit (v - lo) of it is set, and matches when inside != TERM_NEGATE.
+// Both loads are selects: a lane at or past n reads no column, and a lane reads a bitmap word only after ITS OWN range test passed, so
+// (v - lo) >> 6 is below the bitmap's ceil((hi - lo + 1) / 64) words.  The bitmap read is a per-lane gather of one 8-byte word from a
+// block of at most a few KiB that every wave of the mask re-reads: it stays in cache, and LDS staging per 256-row workgroup would move
+// more bytes than the gather does.
+__global__ __launch_bounds__(256) void k_mask_where_sets(const SetTerm *__restrict__ terms, const MaskJob *__restrict__ jobs, uint64_t n,
+                                                         uint32_t nwords, uint32_t nblocks, uint32_t *__restrict__ blockcnt) {
+    __shared__ uint32_t s_cnt[4];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const MaskJob job = jobs[blockIdx.y];
+    const uint32_t word = blockIdx.x * 4 + wave;
+    const uint64_t row = uint64_t(word) * 64 + lane;
+    const bool in = row < n;
+    bool ok = in;
+    for (uint32_t t = job.t0; t < job.t1; t++) {  // (wave-uniform)
+        const SetTerm tm = terms[t];
+        const uint32_t v = (tm.col && in) ? tm.col[row] : LABEL_NONE;
+        const bool labelled = v != LABEL_NONE;
+        const uint32_t off = v - tm.lo;
+        bool inside = labelled && tm.lo <= v && v <= tm.hi;
+        const uint64_t bw = (inside && tm.bitmap) ? tm.bitmap[off >> 6] : ~0ull;
+        inside = inside && ((bw >> (off & 63)) & 1);
+        ok = ok && (labelled ? inside != bool(tm.flags & TERM_NEGATE) : bool(tm.flags & TERM_NONE));
+    }
+    const uint64_t w = __ballot(ok);
+    if (lane == 0) {
+        if (word < nwords) job.bits[word] = w;
+        s_cnt[wave] = (uint32_t)__popcll(w);  // (a word at or past nwords has no row below n: 0)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) blockcnt[size_t(blockIdx.y) * nblocks + blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
 // One workgroup per mask: blockcnt[mask][0 .. nblocks) -> its exclusive prefix sums, in place; totals[mask] = the sum (the mask's m).
 // 256 counts per iteration (a shuffle scan inside the wave, the four wave sums through LDS), the running sum carried over iterations.
 __global__ __launch_bounds__(256) void k_mask_scan(uint32_t *__restrict__ blockcnt, uint32_t nblocks, uint32_t *__restrict__ totals) {
@@ -126,6 +162,13 @@ void launch_mask_where(const MaskTerm *terms, const MaskJob *jobs, uint32_t n_ma
     const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
     if (n_masks == 0 || nblocks == 0) return;
     hipLaunchKernelGGL(k_mask_where, dim3(nblocks, n_masks), dim3(256), 0, s, terms, jobs, n, nwords, nblocks, blockcnt);
+    hipLaunchKernelGGL(k_mask_scan, dim3(n_masks), dim3(256), 0, s, blockcnt, nblocks, totals);
+}
+void launch_mask_where_sets(const SetTerm *terms, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals,
+                            hipStream_t s) {
+    const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
+    if (n_masks == 0 || nblocks == 0) return;
+    hipLaunchKernelGGL(k_mask_where_sets, dim3(nblocks, n_masks), dim3(256), 0, s, terms, jobs, n, nwords, nblocks, blockcnt);
     hipLaunchKernelGGL(k_mask_scan, dim3(n_masks), dim3(256), 0, s, blockcnt, nblocks, totals);
 }
 void launch_mask_ids(const MaskJob *jobs, uint32_t *const *ids, uint32_t n_masks, uint64_t n, const uint32_t *blockoff, hipStream_t s) {

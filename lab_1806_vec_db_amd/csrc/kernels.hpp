@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "mask_sets.hpp"
+
 namespace vdb {
 
 // how a (row, query) pair turns into a distance; all folds are strict left-to-right f32
@@ -331,6 +333,7 @@ void launch_mask_dense_nan(float *dist, uint64_t ld, uint64_t n, uint32_t nq, co
 constexpr uint32_t LABEL_COLUMNS = 16;       // VDB_LABEL_COLUMNS
 constexpr uint32_t LABEL_NONE = 0xFFFFFFFFu;  // VDB_LABEL_NONE: a row without a value in that column
 constexpr uint32_t MASK_MAX_TERMS = 8;        // VDB_MASK_MAX_TERMS
+static_assert(SETS_LABEL_COLUMNS == LABEL_COLUMNS && SETS_LABEL_NONE == LABEL_NONE && SETS_MAX_TERMS == MASK_MAX_TERMS, "mask_sets.hpp and kernels.hpp agree");
 struct LabelCols {  // the allocated columns of an index (kernel argument, by value)
     uint32_t *col[LABEL_COLUMNS];
     uint32_t n;
@@ -354,6 +357,9 @@ inline uint32_t mask_where_blocks(uint64_t n) { return (uint32_t)(((n + 63) / 64
 // allowed rows per block and totals[g] = allowed rows of mask g  (k_mask_where + k_mask_scan; n_masks <= 65535)
 void launch_mask_where(const MaskTerm *terms, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals,
                        hipStream_t s);
+// the same for set / range terms (k_mask_where_sets + k_mask_scan; the term table of mask_sets.hpp, bitmaps resident on the device)
+void launch_mask_where_sets(const SetTerm *terms, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals,
+                            hipStream_t s);
 // ids[g][0 .. totals[g]) = the allowed rows of mask g, ascending (k_mask_ids; after launch_mask_where on the same stream)
 void launch_mask_ids(const MaskJob *jobs, uint32_t *const *ids, uint32_t n_masks, uint64_t n, const uint32_t *blockoff, hipStream_t s);
 void mfma_set_sample_thin(int v);

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .labels import LabelTerm
 
 DIST_NAMES = {"l2sqr": L.L2SQR, "cosine": L.COSINE}  # pyo3/mod.rs:15-22
 
@@ -83,6 +84,20 @@ def _terms_arrays(terms):
         if not (0 <= c < 2 ** 32 and 0 <= v < 2 ** 32):
             raise ValueError(f"mask term ({c}, {v}): column and code are u32")
     return (np.array([c for c, _ in t], dtype=np.uint32), np.array([v for _, v in t], dtype=np.uint32))
+
+
+def _set_terms_arrays(terms):
+    """(columns, lo, hi, flags, set_lims, set_words) of a sequence of LabelTerm (an equality term (column, code) stands for its
+    LabelTerm equivalent): the arrays of vdb_mask_create_where_sets*, the bitmaps packed back to back"""
+    ts = [LabelTerm.of(t) for t in terms]
+    maps = [t.bitmap() for t in ts if t.codes is not None]
+    lims = [0]
+    for t in ts:
+        lims.append(lims[-1] + t.set_bits // 64)
+    words = maps[0] if len(maps) == 1 else np.concatenate(maps) if maps else np.zeros(0, dtype=np.uint64)
+    return (np.array([t.column for t in ts], dtype=np.uint32), np.array([t.lo for t in ts], dtype=np.uint32),
+            np.array([t.hi for t in ts], dtype=np.uint32), np.array([t.flags for t in ts], dtype=np.uint32),
+            np.array(lims, dtype=np.uint64), words)
 
 
 class RowMask:
@@ -338,6 +353,27 @@ class GpuIndex:
         cols, codes = _terms_arrays([tm for t in lists for tm in t])
         arr = (L.vp * max(len(lists), 1))()
         L.check(self._lib.vdb_mask_create_where_many(self._h, _ptr(lims, L.u64p), _ptr(cols, L.u32p), _ptr(codes, L.u32p), len(lists), arr))
+        return [RowMask.from_handle(self, arr[g]) for g in range(len(lists))]
+
+    def make_mask_where_sets(self, terms) -> RowMask:
+        """the mask of the rows that match EVERY LabelTerm of `terms` -- set and range predicates over the label columns, built on the
+        device (vdb_mask_create_where_sets); no terms: every row"""
+        cols, lo, hi, flags, lims, words = _set_terms_arrays(terms)
+        h = L.vp()
+        L.check(self._lib.vdb_mask_create_where_sets(self._h, _ptr(cols, L.u32p), _ptr(lo, L.u32p), _ptr(hi, L.u32p), _ptr(flags, L.u32p),
+                                                     _ptr(lims, L.u64p), _ptr(words, L.u64p), cols.shape[0], C.byref(h)))
+        return RowMask.from_handle(self, h)
+
+    def make_masks_where_sets(self, list_of_terms) -> list[RowMask]:
+        """one mask per entry of `list_of_terms` (each a sequence of LabelTerm) in ONE library call (vdb_mask_create_where_sets_many);
+        all-or-nothing: an invalid entry raises and no mask is made"""
+        lists = [list(t) for t in list_of_terms]
+        tlims = np.zeros(len(lists) + 1, dtype=np.uint64)
+        tlims[1:] = np.cumsum([len(t) for t in lists], dtype=np.uint64)
+        cols, lo, hi, flags, lims, words = _set_terms_arrays([tm for t in lists for tm in t])
+        arr = (L.vp * max(len(lists), 1))()
+        L.check(self._lib.vdb_mask_create_where_sets_many(self._h, _ptr(tlims, L.u64p), _ptr(cols, L.u32p), _ptr(lo, L.u32p), _ptr(hi, L.u32p),
+                                                          _ptr(flags, L.u32p), _ptr(lims, L.u64p), _ptr(words, L.u64p), len(lists), arr))
         return [RowMask.from_handle(self, arr[g]) for g in range(len(lists))]
 
     def flat_knn_filtered(self, queries, k: int, mask: RowMask):

@@ -9,19 +9,257 @@ index holds the codes (GpuIndex.set_labels) and evaluates patterns over them (Gp
     LABEL_NONE, which is also what a pattern value of None encodes to -- `m.get(k) == v`, the match the host loop makes.
   * A pattern -- every key present with an equal value -- encodes to at most MASK_MAX_TERMS (column, code) terms, or to "matches
     nothing" when one of its values was never seen in its column (without growing the dictionary).
+  * A pattern value may also be a PREDICATE on the key's value x = metadata.get(key): In, NotIn, Ne, Exists, Lt, Le, Gt, Ge, Between.
+    `matches` is the one definition of what they mean.  Over a label column every predicate on one key is a SET OF CODES plus one bit for
+    "rows without a value": LabelCodec.compile evaluates the predicate over the column's dictionary (one entry per distinct value) and
+    emits LabelTerm objects (column, [lo, hi], negate, none, codes) that the index tests per row (GpuIndex.make_masks_where_sets).
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 
 LABEL_COLUMNS = 16       # VDB_LABEL_COLUMNS
 LABEL_NONE = 0xFFFFFFFF  # VDB_LABEL_NONE
 MASK_MAX_TERMS = 8       # VDB_MASK_MAX_TERMS
+TERM_NEGATE = 1          # VDB_TERM_NEGATE
+TERM_NONE = 2            # VDB_TERM_NONE
+MASK_MAX_SET_BITS = 1 << 27  # VDB_MASK_MAX_SET_BITS: bitmap bits per library call
 
 # terms no row satisfies, whatever the columns hold: two different codes asked of one column
 NOTHING = ((0, 0), (0, 1))
 
 _UNHASHABLE = object()  # stands in for row values a dictionary cannot hold (they equal no pattern value the codec accepts)
+
+
+class LabelTerm:
+    """One set / range term of a device-built mask (vdb_mask_create_where_sets): a frozen, hashable value.  A row whose label in
+    `column` is v matches when v is LABEL_NONE: iff `none` (negate never inverts this case); otherwise: inside = lo <= v <= hi and (codes
+    is None or v in codes), and the row matches iff inside != negate.  `codes`: an iterable of codes -- lo / hi default to its min / max;
+    with no codes and no bounds the term is the empty range (lo = 1, hi = 0): nothing, or with negate every labelled row.  Without
+    `codes` the term is the plain range [lo, hi] and carries no bitmap."""
+    __slots__ = ("column", "lo", "hi", "negate", "none", "codes")
+
+    def __init__(self, column, lo=None, hi=None, negate=False, none=False, codes=None):
+        cs = None if codes is None else tuple(sorted({int(c) for c in codes}))
+        if cs is not None and any(not 0 <= c < LABEL_NONE for c in cs):
+            raise ValueError("LabelTerm: codes are u32 below LABEL_NONE")
+        if cs:
+            lo = cs[0] if lo is None else int(lo)
+            hi = cs[-1] if hi is None else int(hi)
+            if not lo <= cs[0] <= cs[-1] <= hi:
+                raise ValueError(f"LabelTerm: codes {cs[0]} .. {cs[-1]} outside [{lo}, {hi}]")
+        elif cs is not None or (lo is None and hi is None):  # an empty set, whatever the bounds: the empty range
+            lo, hi, cs = 1, 0, None
+        elif lo is None or hi is None:
+            raise ValueError("LabelTerm: give both lo and hi, or codes")
+        lo, hi, column = int(lo), int(hi), int(column)
+        if not (0 <= lo < 2 ** 32 and 0 <= hi < 2 ** 32 and 0 <= column < 2 ** 32):
+            raise ValueError(f"LabelTerm({column}, {lo}, {hi}): column, lo and hi are u32")
+        for k, v in (("column", column), ("lo", lo), ("hi", hi), ("negate", bool(negate)), ("none", bool(none)), ("codes", cs)):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, k, v):
+        raise AttributeError("LabelTerm is frozen")
+
+    def _key(self):
+        return (self.column, self.lo, self.hi, self.negate, self.none, self.codes)
+
+    def __eq__(self, other):
+        return isinstance(other, LabelTerm) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"LabelTerm({self.column}, {self.lo}, {self.hi}, negate={self.negate}, none={self.none}, codes={self.codes})"
+
+    @property
+    def flags(self) -> int:
+        return (TERM_NEGATE if self.negate else 0) | (TERM_NONE if self.none else 0)
+
+    @property
+    def set_bits(self) -> int:
+        """bits of the term's bitmap, whole 64-bit words (0: no bitmap)"""
+        return 0 if self.codes is None else (self.hi - self.lo + 64) // 64 * 64
+
+    def bitmap(self) -> np.ndarray:
+        """the u64 words of the term's bitmap, bit j = code lo + j (no words without `codes`)"""
+        if self.codes is None:
+            return np.zeros(0, dtype=np.uint64)
+        if len(self.codes) <= 64:  # a handful of codes: plain integers beat the array round trip
+            words = [0] * (self.set_bits // 64)
+            for c in self.codes:
+                words[(c - self.lo) >> 6] |= 1 << ((c - self.lo) & 63)
+            return np.array(words, dtype=np.uint64)
+        bits = np.zeros(self.set_bits, dtype=np.uint8)
+        bits[np.asarray(self.codes, dtype=np.int64) - self.lo] = 1
+        return np.packbits(bits, bitorder="little").view(np.uint64)
+
+    def select(self, values) -> np.ndarray:
+        """the match over an array of u32 labels, in numpy (the arithmetic of k_mask_where_sets, for hosts and tests)"""
+        v = np.asarray(values, dtype=np.uint32).astype(np.int64)
+        inside = (v >= self.lo) & (v <= self.hi)
+        if self.codes is not None:
+            inside &= np.isin(v, np.asarray(self.codes, dtype=np.int64))
+        return np.where(v == LABEL_NONE, self.none, inside != self.negate)
+
+    @staticmethod
+    def of(term) -> "LabelTerm":
+        """a LabelTerm as it is; an equality term (column, code) of make_mask_where as its documented equivalent: {lo = hi = code}, and
+        (column, LABEL_NONE) as {lo = 1, hi = 0, none}"""
+        if isinstance(term, LabelTerm):
+            return term
+        c, code = term
+        return LabelTerm(c, 1, 0, none=True) if int(code) == LABEL_NONE else LabelTerm(c, int(code), int(code))
+
+
+# ---- predicates: pattern values beyond `str` (equality) and None (key missing) -------------------------------------------------------
+class _Pred:
+    """frozen and hashable, so a pattern that holds predicates still keys the mask cache as frozenset(pattern.items())"""
+    __slots__ = ("_k",)
+
+    def __init__(self, *k):
+        object.__setattr__(self, "_k", k)
+
+    def __setattr__(self, k, v):
+        raise AttributeError("predicates are frozen")
+
+    def __eq__(self, other):
+        return type(other) is type(self) and self._k == other._k
+
+    def __hash__(self):
+        return hash((type(self).__name__, self._k))
+
+    def __repr__(self):
+        return f"{type(self).__name__}{self._k!r}"
+
+
+class In(_Pred):
+    """x in values; None may be a member: rows without the key match then"""
+    __slots__ = ()
+
+    def __init__(self, values):
+        super().__init__(frozenset(values))
+
+    @property
+    def values(self):
+        return self._k[0]
+
+
+class NotIn(In):
+    """x not in values (rows without the key match unless None is a member)"""
+    __slots__ = ()
+
+
+class Ne(_Pred):
+    """x != v; rows without the key match, as negating m.get(k) == v would have it"""
+    __slots__ = ()
+
+    def __init__(self, v):
+        hash(v)
+        super().__init__(v)
+
+
+class Exists(_Pred):
+    """(x is not None) == flag"""
+    __slots__ = ()
+
+    def __init__(self, flag=True):
+        super().__init__(bool(flag))
+
+
+def _bound_kind(b, who):
+    if isinstance(b, bool) or not isinstance(b, (str, int, float)):
+        raise TypeError(f"{who}: a bound is a str (string order) or an int / float (numeric order), not {type(b).__name__}")
+    return "s" if isinstance(b, str) else "n"
+
+
+class _Order(_Pred):
+    """A str bound compares by Python string order and matches only when x is a str.  An int / float bound compares numerically and
+    matches only when x is a str that float(x) parses to a non-NaN number.  A missing key never matches; a NaN bound matches nothing."""
+    __slots__ = ()
+    _op = None
+
+    def __init__(self, bound):
+        _bound_kind(bound, type(self).__name__)
+        super().__init__(bound)
+
+    def _cmp(self, x):
+        return type(self)._op(x, self._k[0])
+
+    def _kind(self):
+        return "s" if isinstance(self._k[0], str) else "n"
+
+
+class Lt(_Order):
+    __slots__ = ()
+    _op = staticmethod(lambda x, b: x < b)
+
+
+class Le(_Order):
+    __slots__ = ()
+    _op = staticmethod(lambda x, b: x <= b)
+
+
+class Gt(_Order):
+    __slots__ = ()
+    _op = staticmethod(lambda x, b: x > b)
+
+
+class Ge(_Order):
+    __slots__ = ()
+    _op = staticmethod(lambda x, b: x >= b)
+
+
+class Between(_Order):
+    """lo <= x <= hi, both ends included; the two bounds are both strings or both numbers"""
+    __slots__ = ()
+
+    def __init__(self, lo, hi):
+        if _bound_kind(lo, "Between") != _bound_kind(hi, "Between"):
+            raise TypeError("Between: the two bounds are both strings or both numbers")
+        _Pred.__init__(self, lo, hi)
+
+    def _cmp(self, x):
+        return self._k[0] <= x <= self._k[1]
+
+
+def matches(value_or_pred, x) -> bool:
+    """THE definition of a pattern entry against x = metadata.get(key): a plain value is `x == value` (what the host loop always did),
+    a predicate what its class says."""
+    p = value_or_pred
+    if not isinstance(p, _Pred):
+        return bool(x == p)
+    if isinstance(p, In):  # (NotIn is a subclass)
+        try:
+            inside = x in p.values
+        except TypeError:  # x cannot be hashed: it equals no member
+            inside = False
+        return inside != isinstance(p, NotIn)
+    if isinstance(p, Ne):
+        return bool(x != p._k[0])
+    if isinstance(p, Exists):
+        return (x is not None) == p._k[0]
+    if not isinstance(x, str):
+        return False
+    if p._kind() == "n":
+        try:
+            x = float(x)
+        except ValueError:
+            return False
+        if math.isnan(x):
+            return False
+    return bool(p._cmp(x))  # (a comparison with a NaN bound is False)
+
+
+def is_predicate(v) -> bool:
+    return isinstance(v, _Pred)
+
+
+def has_predicates(pattern) -> bool:
+    return any(isinstance(v, _Pred) for v in pattern.values())
 
 
 class LabelCodec:
@@ -45,8 +283,8 @@ class LabelCodec:
 
     def expressible(self, pattern) -> bool:
         """True when the pattern can be evaluated over label columns: at most max_terms keys, every key has a column or can still get
-        one, every value a string (or None: the key is missing).  Assigns nothing."""
-        if len(pattern) > self.max_terms or not all(self._value_ok(v) for v in pattern.values()):
+        one, every value a string (or None: the key is missing) or a predicate.  Assigns nothing."""
+        if len(pattern) > self.max_terms or not all(self._value_ok(v) or isinstance(v, _Pred) for v in pattern.values()):
             return False
         new = sum(1 for k in pattern if k not in self.columns)
         return len(self.columns) + new <= self.max_columns
@@ -113,5 +351,52 @@ class LabelCodec:
                 out.append((col, code))
         return list(NOTHING) if nothing else out
 
+    def compile(self, pattern):
+        """the LabelTerm list of a pattern that may hold predicates, one term per key: a list (empty for the empty pattern), NOTHING
+        when some entry can match no row (an In whose values were all never seen, an unseen plain value), None when the pattern is not
+        expressible: a key without a column, more than max_terms keys, a plain value that is neither str nor None, a bitmap span over
+        MASK_MAX_SET_BITS.  The dictionary never grows.  In / NotIn / Ne are dictionary look-ups; the order predicates evaluate
+        `matches` over the column's dictionary entries: O(distinct values of the key), not O(rows) -- a column of unique ids makes that
+        as slow as the host loop, and still correct.  A row value the dictionary could not hold (the _UNHASHABLE entry) needs no
+        special case: it equals no pattern value and is no str."""
+        if len(pattern) > self.max_terms:
+            return None
+        out = []
+        nothing = False
+        for k, p in pattern.items():
+            col = self.columns.get(k)
+            if col is None or not (self._value_ok(p) or isinstance(p, _Pred)):
+                return None
+            table = self.codes[col]
+            negate = False
+            if p is None:
+                codes, none = [], True
+            elif isinstance(p, str):
+                codes, none = [table[p]] if p in table else [], False
+            elif isinstance(p, In):
+                codes, none = [table[v] for v in p.values if v is not None and v in table], None in p.values
+                negate = isinstance(p, NotIn)
+            elif isinstance(p, Ne):
+                v = p._k[0]
+                codes, none, negate = [table[v]] if v is not None and v in table else [], v is None, True
+            elif isinstance(p, Exists):
+                codes, none, negate = [], True, p._k[0]  # the rows without a value, or their complement
+            else:
+                codes, none = [c for v, c in table.items() if matches(p, v)], False
+            if negate:
+                none = not none  # the complement within "rows without a value" too
+            if not codes and not negate and not none:
+                nothing = True
+                continue
+            if codes and max(codes) - min(codes) + 1 == len(set(codes)):
+                term = LabelTerm(col, min(codes), max(codes), negate=negate, none=none)  # a run of codes: a range, no bitmap
+            else:
+                term = LabelTerm(col, negate=negate, none=none, codes=codes)
+            out.append(term)
+        if sum(t.set_bits for t in out) > MASK_MAX_SET_BITS:  # (one library call must be able to carry the pattern)
+            return None
+        return NOTHING if nothing else out
 
-__all__ = ["LabelCodec", "LABEL_COLUMNS", "LABEL_NONE", "MASK_MAX_TERMS", "NOTHING"]
+
+__all__ = ["LabelCodec", "LabelTerm", "LABEL_COLUMNS", "LABEL_NONE", "MASK_MAX_TERMS", "MASK_MAX_SET_BITS", "NOTHING", "TERM_NEGATE", "TERM_NONE",
+           "In", "NotIn", "Ne", "Exists", "Lt", "Le", "Gt", "Ge", "Between", "matches", "is_predicate", "has_predicates"]

@@ -20,6 +20,9 @@ batch_search(key, queries, k, ..., filters) answers a batch of queries, each und
 The keys filter patterns use are kept on the device as integer label columns (labels.py: a key gets a column when a pattern first names
 it, one pass over the metadata; add / delete keep the columns in step), and the patterns' row masks are built there
 (GpuIndex.make_masks_where); a pattern the columns cannot express (a 17th key, more than 8 keys) is matched on the host as before.
+A pattern value may be a predicate of labels.py (In, NotIn, Ne, Exists, Lt, Le, Gt, Ge, Between; labels.matches defines them): such a
+pattern is compiled over the columns' dictionaries into set / range terms and its mask is built on the device as well
+(GpuIndex.make_masks_where_sets); patterns of plain values keep their path.
 """
 from __future__ import annotations
 
@@ -30,7 +33,8 @@ import numpy as np
 
 from ._lib import VdbError
 from .index import GpuIndex, RowMask, parse_dist
-from .labels import LabelCodec
+from .labels import MASK_MAX_SET_BITS, LabelCodec, LabelTerm, has_predicates
+from .labels import matches as value_matches
 
 _DIST_STR = {0: "l2sqr", 1: "cosine"}
 
@@ -92,12 +96,18 @@ class _Table:
         self.codec = LabelCodec()
 
     def host_match(self, pattern: dict[str, str]) -> np.ndarray:
-        """the host loop: a bool per row, True where the metadata holds every key of `pattern` with an equal value"""
-        return np.fromiter((all(m.get(k) == v for k, v in pattern.items()) for m in self.metadata), dtype=np.bool_, count=len(self.metadata))
+        """the host loop: a bool per row, True where the metadata holds every key of `pattern` with an equal value -- or, for a
+        predicate, a value it accepts (labels.matches)"""
+        return np.fromiter((all(value_matches(v, m.get(k)) for k, v in pattern.items()) for m in self.metadata), dtype=np.bool_, count=len(self.metadata))
 
     def live_terms(self, pattern):
-        """the pattern's (column, code) terms when every key has a label column (labels.py: terms), else None"""
-        return self.codec.terms(pattern)
+        """the pattern's terms when every key has a label column, else None: (column, code) terms for a pattern of plain values
+        (labels.py: terms), LabelTerm set / range terms for one that holds predicates (labels.py: compile)"""
+        return self.codec.compile(pattern) if has_predicates(pattern) else self.codec.terms(pattern)
+
+    def device_mask(self, pattern, terms) -> RowMask:
+        """the mask of live_terms' terms: plain patterns through make_mask_where, patterns with a predicate through make_mask_where_sets"""
+        return self.index.make_mask_where_sets(terms) if has_predicates(pattern) else self.index.make_mask_where(terms)
 
     def create_columns(self, patterns) -> None:
         """UNDER THE WRITE LOCK: gives the keys of every expressible pattern their label columns -- one pass over the metadata per new
@@ -130,24 +140,37 @@ class _Table:
             if mk is None:
                 terms = self.live_terms(pattern)
                 if terms is not None:
-                    mk = self.masks[key] = self.index.make_mask_where(terms)
+                    mk = self.masks[key] = self.device_mask(pattern, terms)
                 else:
                     mk = self.masks[key] = self.index.make_mask(self.host_match(pattern))
             return mk
 
     def masks_for(self, patterns) -> list[RowMask]:
-        """mask_for for many patterns: the ones not cached yet whose keys all have columns are built by ONE make_masks_where call"""
+        """mask_for for many patterns: the ones not cached yet whose keys all have columns are built by ONE make_masks_where call for
+        the patterns of plain values and ONE make_masks_where_sets call for the ones that hold predicates (more than one only when
+        their bitmaps together pass the library's MASK_MAX_SET_BITS per call)"""
         with self.mask_mu:
             todo: dict[frozenset, list] = {}
+            todo_sets: dict[frozenset, list] = {}
             for p in patterns:
                 key = frozenset(p.items())
-                if key not in self.masks and key not in todo:
+                if key not in self.masks and key not in todo and key not in todo_sets:
                     terms = self.live_terms(p)
                     if terms is not None:
-                        todo[key] = terms
+                        (todo_sets if has_predicates(p) else todo)[key] = terms
             if todo:
                 for key, mk in zip(todo, self.index.make_masks_where(list(todo.values()))):
                     self.masks[key] = mk
+            batch, bits = [], 0
+            for key in list(todo_sets) + [None]:
+                need = 0 if key is None else sum(LabelTerm.of(t).set_bits for t in todo_sets[key])
+                if batch and (key is None or bits + need > MASK_MAX_SET_BITS):
+                    for bk, mk in zip(batch, self.index.make_masks_where_sets([todo_sets[bk] for bk in batch])):
+                        self.masks[bk] = mk
+                    batch, bits = [], 0
+                if key is not None:
+                    batch.append(key)
+                    bits += need
         return [self.mask_for(p) for p in patterns]
 
     def drop_masks(self):
@@ -252,7 +275,7 @@ class VecDB:
             # deleting by id must not intern every id); the columns follow the removal inside the library
             terms = t.live_terms(pattern)
             if terms is not None:
-                mk = t.index.make_mask_where(terms)
+                mk = t.device_mask(pattern, terms)
                 matches = mk.rows()[1].tolist()
                 mk.close()
             else:
