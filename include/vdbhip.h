@@ -197,7 +197,30 @@ int vdb_range_destroy(vdb_range *r);
  * "flat_filtered_grouped_queries" the queries the grouped launch answered; vdb_prof_get "flat_filtered_scan_grouped" is that kernel.
  * vdb_flat_range_filtered: vdb_flat_range over the allowed rows alone -- every ALLOWED row with D <= radius[q]; everything else as
  * documented there (f32 and VecSet<u8> indexes, the same tiers and counters).
- * Not covered: sharded and replica contexts, _begin / _end pipelining, filtered PQ / HNSW / IVF searches, k-NN on u8 indexes. */
+ * vdb_flat_range_filtered_multi: the range search with ONE MASK PER QUERY.  Query q's slice of the result is exactly what
+ * vdb_flat_range_filtered(idx, query q, 1, dim, &radius[q], limit, masks[mask_of[q]], ..) returns: every ALLOWED row with
+ * D <= radius[q], D bit-exact, ascending by (distance, id), the first `limit` pairs when limit > 0, id_offset added; a NaN distance is
+ * never inside and a NaN radius gives an empty slice.  The result object is vdb_flat_range's.  `mask_of` is a HOST array in both forms,
+ * in any order; a mask may serve any number of queries, none included.  Checked before anything is computed, with *out left NULL and
+ * every counter unchanged: EVERY mask of `masks` as for the single-mask call (another index: VDB_ERR_INVALID, stale: VDB_ERR_STATE),
+ * mask_of[q] >= n_masks (VDB_ERR_INVALID), a dim mismatch; the _device form refuses more than 32768 queries.  nq == 0 gives an empty
+ * result, a mask with m == 0 empty slices.  "flat_range_max_results" and a device-memory failure fail the whole call as documented for
+ * vdb_flat_range: nothing is returned, nothing aborts, and the counters below are as the call found them ("flat_range_hits_max", a
+ * high-water mark, excepted).  f32 and VecSet<u8> indexes.  Read-side and re-entrant; the _device form synchronises `stream` first and
+ * returns synchronised.
+ * How it is answered (csrc/multi_plan.hpp, k_filter.hip, docs/DESIGN_flat.md 4.1n): the queries are bucketed by mask on the host.
+ *   GROUPED path -- f32 indexes, masks with m <= "flat_filtered_direct_max", in every vdb_flat_set_mode: ONE launch per chunk of queries
+ *   (k_range_gather_grouped: a workgroup per (mask, group of <= 8 of its queries, tile of 256 allowed rows)) folds the gathered rows,
+ *   tests D <= radius on the spot and appends the pair keys of the pairs inside to the query's row; one sort and one append per chunk.
+ *   Per-mask route -- every other bucket (longer masks, every bucket of a u8 index): its queries and radii are gathered into a block and
+ *   answered by vdb_flat_range_filtered's machinery (8-bit tier with the mask's row constants, or the scan of all rows).
+ *   One pool of sorted keys and one gather into the result for the whole call.
+ * vdb_get_stat: "flat_range_queries" += nq and "flat_range_results" as usual; "flat_range_multi_calls" counts these calls,
+ * "flat_range_grouped_queries" the queries the grouped launch answered (they count in neither "flat_range_i8_queries" nor
+ * "flat_range_scan_queries"; the per-mask route advances those as the per-mask calls would).  vdb_prof_get
+ * "flat_range_gather_grouped" is the grouped kernel (bytes: the rows its work items fetch x dim x 4).
+ * Not covered: sharded and replica contexts, _begin / _end pipelining, filtered PQ / HNSW / IVF searches, k-NN on u8 indexes, a
+ * grouped path for u8 rows, the single-mask range call through the gathered path. */
 typedef struct vdb_mask vdb_mask;
 int vdb_mask_create(vdb_index *idx, const uint64_t *bits, uint64_t n_rows, vdb_mask **out);
 int vdb_mask_count(const vdb_mask *m, uint64_t *out);
@@ -213,6 +236,11 @@ int vdb_flat_knn_filtered_multi_device(vdb_index *idx, const void *d_queries, ui
                                        void *d_out_dist, void *d_out_count, void *stream);
 int vdb_flat_range_filtered(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit,
                             const vdb_mask *mask, vdb_range **out);
+int vdb_flat_range_filtered_multi(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit,
+                                  const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, vdb_range **out);
+int vdb_flat_range_filtered_multi_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, const void *d_radius,
+                                         uint64_t limit, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of,
+                                         void *stream, vdb_range **out);
 /* ---- row labels on the device: masks built from them without a host pass ----------------------------------------------------------
  * An index has VDB_LABEL_COLUMNS logical label columns of uint32_t, one value per LOCAL row: the filterable attributes of the rows as
  * integer codes (the host keeps the dictionary; lab_1806_vec_db_amd/labels.py is one).  A column is allocated by its first write

@@ -235,6 +235,17 @@ public:
         check(vdb_flat_range_filtered(h_, queries, nq, dim_, radius, limit, mask.handle(), &r));
         return take_range(r, nq);
     }
+    // the same with one mask per query: query q under *masks[mask_of[q]] (vdb_flat_range_filtered_multi)
+    std::vector<std::vector<CandidatePair>> range_search_filtered_multi_batch(const float *queries, uint64_t nq, const float *radius,
+                                                                              const std::vector<const Mask *> &masks,
+                                                                              const std::vector<uint32_t> &mask_of, uint64_t limit = 0) const {
+        if (mask_of.size() != nq) throw std::runtime_error("mask_of: one entry per query is needed");
+        std::vector<const vdb_mask *> hs;
+        for (const Mask *m : masks) hs.push_back(m->handle());
+        vdb_range *r = nullptr;
+        check(vdb_flat_range_filtered_multi(h_, queries, nq, dim_, radius, limit, hs.data(), hs.size(), mask_of.data(), &r));
+        return take_range(r, nq);
+    }
 
     // MetadataVecTable::build_hnsw_index / clear_hnsw_index, build_pq_table / clear_pq_table
     void build_hnsw(uint64_t M = 16, uint64_t ef_construction = 200, uint64_t seed = 42, uint64_t batch = 64,

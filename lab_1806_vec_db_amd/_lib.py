@@ -65,6 +65,8 @@ SIGNATURES = {
     "vdb_flat_knn_filtered_multi": [vp, f32p, u64, u64, u64, C.POINTER(vp), u64, u32p, u64p, f32p, u64p],
     "vdb_flat_knn_filtered_multi_device": [vp, vp, u64, u64, u64, C.POINTER(vp), u64, u32p, vp, vp, vp, vp],
     "vdb_flat_range_filtered": [vp, f32p, u64, u64, f32p, u64, vp, C.POINTER(vp)],
+    "vdb_flat_range_filtered_multi": [vp, f32p, u64, u64, f32p, u64, C.POINTER(vp), u64, u32p, C.POINTER(vp)],
+    "vdb_flat_range_filtered_multi_device": [vp, vp, u64, u64, vp, u64, C.POINTER(vp), u64, u32p, vp, C.POINTER(vp)],
     "vdb_flat_shortlist_keys": [vp, f32p, u64, u64, C.c_int, f32p, f32p, f32p, f32p],
     "vdb_flat_set_mode": [vp, C.c_int],
     "vdb_index_prepare": [vp, C.c_int],

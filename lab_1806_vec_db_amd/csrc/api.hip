@@ -789,8 +789,8 @@ int vdb_flat_knn_filtered_device(vdb_index *idx, const void *d_queries, uint64_t
 
 // one mask per query: everything that can be refused is refused here, before anything is computed or written; -> the masks as RowMask pointers
 static std::vector<const RowMask *> filtered_multi_check(const Index &ix, uint64_t nq, const vdb_mask *const *masks, uint64_t n_masks,
-                                                         const uint32_t *mask_of) {
-    VDB_REQUIRE(!ix.elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+                                                         const uint32_t *mask_of, bool knn = true) {
+    VDB_REQUIRE(!knn || !ix.elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
     VDB_REQUIRE(n_masks == 0 || masks, "null masks");
     VDB_REQUIRE(nq == 0 || mask_of, "null mask_of");
     VDB_REQUIRE(n_masks < (1ull << 32), "too many masks");
@@ -902,6 +902,59 @@ int vdb_flat_range_filtered(vdb_index *idx, const float *queries, uint64_t nq, u
     }
     ix.prof_collect(*ws);
     *out = res.release();
+    VDB_API_END
+}
+
+// one mask per query (Index::flat_range_masked_multi_device): the host form uploads queries and radii and runs the device form's body
+static void range_filtered_multi_body(Index &ix, Workspace &ws, const float *d_q, uint64_t nq, const float *d_r, uint64_t limit,
+                                      const std::vector<const RowMask *> &rm, const uint32_t *mask_of, vdb_range **out) {
+    std::unique_ptr<vdb_range> res(new vdb_range);
+    try {
+        ix.flat_range_masked_multi_device(ws, d_q, nq, d_r, limit, rm.data(), rm.size(), mask_of, res->r);
+    } catch (...) {
+        (void)hipStreamSynchronize(ws.stream);  // nothing of a failed call is still running when its buffers go
+        ix.prof_collect(ws);
+        throw;
+    }
+    ix.prof_collect(ws);
+    ix.range_multi_calls++;
+    *out = res.release();
+}
+
+int vdb_flat_range_filtered_multi(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit,
+                                  const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, vdb_range **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    range_check(ix, queries, nq, dim, radius, out);
+    const std::vector<const RowMask *> rm = filtered_multi_check(ix, nq, masks, n_masks, mask_of, false);
+    ix.use_device();
+    WsLease ws(ix);
+    const float *d_q = nullptr, *d_r = nullptr;
+    if (nq) {
+        const size_t qb = nq * dim * sizeof(float), qb_pad = (qb + 255) & ~size_t(255);
+        ws->q.reserve(qb_pad + nq * sizeof(float));  // [queries | radii]
+        VDB_HIP(hipMemcpyAsync(ws->q.p, queries, qb, hipMemcpyHostToDevice, ws->stream));
+        VDB_HIP(hipMemcpyAsync(ws->q.as<char>() + qb_pad, radius, nq * sizeof(float), hipMemcpyHostToDevice, ws->stream));
+        d_q = ws->q.as<float>();
+        d_r = reinterpret_cast<const float *>(ws->q.as<char>() + qb_pad);
+    }
+    range_filtered_multi_body(ix, *ws, d_q, nq, d_r, limit, rm, mask_of, out);
+    VDB_API_END
+}
+
+int vdb_flat_range_filtered_multi_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, const void *d_radius, uint64_t limit,
+                                         const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, void *stream, vdb_range **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    range_check(ix, d_queries, nq, dim, d_radius, out);
+    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
+    const std::vector<const RowMask *> rm = filtered_multi_check(ix, nq, masks, n_masks, mask_of, false);
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
+    range_filtered_multi_body(ix, *ws, static_cast<const float *>(d_queries), nq, static_cast<const float *>(d_radius), limit, rm, mask_of, out);
     VDB_API_END
 }
 
@@ -1109,6 +1162,10 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.filtered_multi_calls.load();
     else if (n == "flat_filtered_grouped_queries")
         *out = idx->ix.filtered_grouped_queries.load();
+    else if (n == "flat_range_multi_calls")  // range calls with a mask per query | queries their grouped launch answered
+        *out = idx->ix.range_multi_calls.load();
+    else if (n == "flat_range_grouped_queries")
+        *out = idx->ix.range_grouped_queries.load();
     else if (n.rfind("flat_i8_rounds_", 0) == 0 && n.size() == 16 && n[15] >= '0' && n[15] <= '8')  // queries whose exact stage walked N rounds (8: 8 or more)
         *out = idx->ix.i8_rounds_hist[n[15] - '0'].load();
     else if (n == "mirror_alloc_failures")  // mirrors of this index whose allocation failed (the tier was left to the next one)

@@ -1281,7 +1281,6 @@ uint64_t Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
 // (8 B per pair in the pool + 12 B per pair in the result).  Range calls neither read nor write the k-NN tiers' auto-off counters.
 void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit, RangeResult &out,
                               const RowMask *mask) {
-    hipStream_t s = ws.stream;
     if (mask) check_mask(*mask);
     out.device = device;
     out.nq = nq;
@@ -1292,24 +1291,31 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
         range_scan_queries += nq;
         return;
     }
+    std::vector<uint64_t> h_off(nq, 0), h_cnt(nq, 0);
+    RangePool pool;
+    flat_range_collect(ws, d_q, nq, d_radius, limit, mask, pool, h_off.data(), h_cnt.data(), nullptr);
+    flat_range_assemble(ws, nq, pool, h_off, h_cnt, out);
+}
+
+// The first half of a range call: the sorted pair keys of every query's slice into `rp`, in the order they are produced; h_off[q] / h_cnt[q]
+// (zero on entry) = where query q's slice lies in the pool and how many pairs it has.  n > 0, nq > 0; the mask has been checked; returns
+// synchronised.  Several collects may share one pool (flat_range_masked_multi_device): the ceiling is the call's.  tally: what this
+// collect added to the tier counters, for a caller that takes it back when the call fails later.
+void Index::flat_range_collect(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit, const RowMask *mask, RangePool &rp,
+                               uint64_t *h_off, uint64_t *h_cnt, RangeTally *tally) {
+    hipStream_t s = ws.stream;
     constexpr uint32_t BQ = 8;  // queries per corpus pass of the scan
     const int cosine = dist == 1 ? 1 : 0;
     const int metric = cosine ? MET_COSINE : MET_L2_DIRECT;
     const uint64_t cap_pairs = range_max_results ? range_max_results : ~0ull;
-    std::vector<uint64_t> h_off(nq, 0), h_cnt(nq, 0);
-    DevBuf pool;
-    uint64_t pool_used = 0;
+    DevBuf &pool = rp.buf;
+    uint64_t &pool_used = rp.used;
     // the pinned block of this call: [off u64 x QCH | cnt u32 x QCH | hits u32 x QCH | take u32 x QCH]; written by the kernels (cnt, hits) and
     // by the host between two stream syncs (off, take) -- never while a kernel that reads them is in flight
     char *hp = static_cast<char *>(ws.pinned(QCH * (sizeof(uint64_t) + 3 * sizeof(uint32_t))));
     uint64_t *p_off = reinterpret_cast<uint64_t *>(hp);
     uint32_t *p_cnt = reinterpret_cast<uint32_t *>(p_off + QCH), *p_hits = p_cnt + QCH, *p_take = p_hits + QCH;
-    auto pool_room = [&](uint64_t add) {
-        if (add > cap_pairs || pool_used > cap_pairs - add)
-            throw Error(1, "range search: more than " + std::to_string(cap_pairs) + " results in one call (flat_range_max_results); use a limit, "
-                           "smaller radii or fewer queries per call");
-        pool.grow((pool_used + add) * sizeof(uint64_t), pool_used * sizeof(uint64_t), s);
-    };
+    auto pool_room = [&](uint64_t add) { rp.room(add, cap_pairs, s); };
     std::vector<uint64_t> scan;  // queries the scan tier answers
     const bool tier = i8_side_tier(ws);
     // under a mask the filter pass reads the masked copy of the row constants: a disallowed row's key is +inf and passes no (finite) threshold
@@ -1356,6 +1362,7 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
         }
         range_i8_queries += served;
         range_hits += hits;
+        if (tally) tally->i8 += served, tally->hits += hits;
         for (uint64_t cur = range_hits_max.load(); hmax > cur && !range_hits_max.compare_exchange_weak(cur, hmax);) {
         }
         if (add) {
@@ -1366,6 +1373,7 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
         }
     }
     range_scan_queries += scan.size();
+    if (tally) tally->scan += scan.size();
     if (!scan.empty()) {
         const uint64_t ns = scan.size(), ld = (n + 63) & ~63ull;
         const uint32_t nblk = range_scan_blocks(n);
@@ -1424,6 +1432,20 @@ void Index::flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, cons
         }
         VDB_SYNC(s);  // (`scan` and rx..blk go out of scope)
     }
+}
+
+void RangePool::room(uint64_t add, uint64_t cap_pairs, hipStream_t s) {
+    if (add > cap_pairs || used > cap_pairs - add)
+        throw Error(1, "range search: more than " + std::to_string(cap_pairs) + " results in one call (flat_range_max_results); use a limit, "
+                       "smaller radii or fewer queries per call");
+    buf.grow((used + add) * sizeof(uint64_t), used * sizeof(uint64_t), s);
+}
+
+// The second half: the CSR arrays of `out` (lims assigned to nq + 1 zeros by the caller) from the pool and every query's (offset, count).
+void Index::flat_range_assemble(Workspace &ws, uint64_t nq, const RangePool &rp, const std::vector<uint64_t> &h_off, const std::vector<uint64_t> &h_cnt,
+                                RangeResult &out) {
+    hipStream_t s = ws.stream;
+    const DevBuf &pool = rp.buf;
     uint64_t total = 0, max_take = 0;
     for (uint64_t q = 0; q < nq; q++) {
         out.lims[q] = total;
@@ -1708,6 +1730,153 @@ void Index::flat_knn_masked_multi_device(Workspace &ws, const float *d_q, uint64
                                        d_slot_q + c.slot0, id_offset, d_idx, d_dist, d_cnt, s);
     }
     VDB_SYNC(s);  // (the plan's host arrays are pageable memory: alive until here)
+}
+
+// ---- Flat: exact filtered range search with one row mask per query (k_filter.hip, multi_plan.hpp) --------------------------------------
+// Query q's slice is what flat_range_device returns for it alone under masks[mask_of[q]].  The queries are bucketed by mask on the host:
+//   per-mask route: a bucket whose mask is longer than flat_filtered_direct_max, and every bucket of a u8 index, is gathered (queries and
+//     radii) into a block of its own and goes through flat_range_collect under its mask as it stands -- the 8-bit tier with that mask's row
+//     constants, or the scan of all rows -- into the call's pool.
+//   grouped route: every other bucket, in every flat mode (the path is exact and reads f32 rows only).  multi_plan lays them out as slots
+//     and cuts the slots into chunks; a chunk is ONE launch of k_range_gather_grouped, which decides d <= r on the spot and appends the
+//     pair keys (distance, ROW) of the pairs inside to the slot's row of a [slot][ld] matrix filled with PAIR_NONE, one read-back of the
+//     slots' counters, ONE sort of the rows (ld wide: launch_sort_rows has one figure for a row's stride and its length) and ONE append of
+//     every slot's first `take` keys to the pool.  No dense matrix, no selection, no finalize: the keys carry rows, not columns.
+// One pool and one k_range_gather for the whole call.  The counters of the call are added when it has succeeded; what the per-mask route
+// added on the way is taken back when it fails.
+void Index::flat_range_masked_multi_device(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit,
+                                           const RowMask *const *masks, uint64_t n_masks, const uint32_t *mask_of, RangeResult &out) {
+    hipStream_t s = ws.stream;
+    out.device = device;
+    out.nq = nq;
+    out.lims.assign(nq + 1, 0);
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 32), "flat range: too many queries");
+    if (n == 0) {  // empty VecSet -> empty results
+        range_queries += nq;
+        range_scan_queries += nq;
+        return;
+    }
+    std::vector<uint64_t> m_of(n_masks);
+    std::vector<uint8_t> grouped(n_masks);
+    for (uint64_t g = 0; g < n_masks; g++) {
+        m_of[g] = masks[g]->m;
+        grouped[g] = !elem_u8 && m_of[g] <= flat_filtered_direct_max;
+    }
+    std::vector<uint64_t> h_off(nq, 0), h_cnt(nq, 0);
+    RangePool pool;
+    RangeTally tally;
+    const uint64_t cap_pairs = range_max_results ? range_max_results : ~0ull;
+    uint64_t ns = 0;
+    try {
+        // per-mask route first: every collect returns synchronised, so the grouped route's reserves below free nothing in use
+        {
+            std::vector<std::vector<uint64_t>> bucket(n_masks);
+            uint64_t longest = 0;
+            for (uint64_t q = 0; q < nq; q++)
+                if (!grouped[mask_of[q]]) bucket[mask_of[q]].push_back(q);
+            for (uint64_t g = 0; g < n_masks; g++) longest = std::max<uint64_t>(longest, bucket[g].size());
+            DevBuf rx, rq, rr;
+            if (longest) {
+                rx.reserve(longest * sizeof(uint64_t));
+                rq.reserve(longest * dim * sizeof(float));
+                rr.reserve(longest * sizeof(float));
+            }
+            std::vector<uint64_t> b_off, b_cnt;
+            for (uint64_t g = 0; g < n_masks; g++) {
+                const std::vector<uint64_t> &bq = bucket[g];
+                const uint64_t nb = bq.size();
+                if (nb == 0) continue;
+                VDB_HIP(hipMemcpyAsync(rx.p, bq.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+                launch_gather_rows_f32(d_q, rx.as<uint64_t>(), nb, (uint32_t)dim, rq.as<float>(), s);
+                launch_gather_rows_f32(d_radius, rx.as<uint64_t>(), nb, 1, rr.as<float>(), s);
+                b_off.assign(nb, 0);
+                b_cnt.assign(nb, 0);
+                flat_range_collect(ws, rq.as<float>(), nb, rr.as<float>(), limit, masks[g], pool, b_off.data(), b_cnt.data(), &tally);
+                for (uint64_t j = 0; j < nb; j++) {
+                    h_off[bq[j]] = b_off[j];
+                    h_cnt[bq[j]] = b_cnt[j];
+                }
+            }
+        }
+        const uint64_t max_m = multi_plan_max_m(m_of.data(), grouped.data(), n_masks, mask_of, nq);
+        const uint64_t ld_all = (max_m + 63) & ~63ull;
+        constexpr uint64_t BUDGET = 256ull << 20;  // bytes of each of the two key matrices per chunk
+        MultiPlan plan;
+        multi_plan(m_of.data(), grouped.data(), n_masks, mask_of, nq, BUDGET, std::max<uint64_t>(ld_all * sizeof(uint64_t), 64), plan);
+        ns = plan.slot_query.size();
+        if (ns && max_m) {
+            const int metric = dist == 0 ? MET_L2_DIRECT : MET_COSINE;
+            // device image of the plan: [items (24 B) | slot_q | counters], one upload for the call
+            std::vector<GroupedItem> h_items(plan.items.size());
+            for (size_t i = 0; i < h_items.size(); i++) {
+                const MultiItem &it = plan.items[i];
+                h_items[i] = GroupedItem{masks[it.mask]->d_ids.as<uint32_t>(), (uint32_t)m_of[it.mask], it.tile, it.slot, it.nb};
+            }
+            const size_t off_q = h_items.size() * sizeof(GroupedItem), off_c = off_q + ns * sizeof(uint32_t);
+            const uint64_t qch = std::min(plan.qch, ns);
+            const size_t tb = sort_rows_temp_bytes(qch, ld_all);
+            // every buffer of the route reserved before its first launch (a later, larger reserve would free a buffer in use)
+            ws.misc.reserve(off_c + ns * sizeof(uint32_t));
+            ws.qsq.reserve(nq * sizeof(float));
+            ws.keys_a.reserve(qch * ld_all * sizeof(uint64_t));
+            ws.keys_b.reserve(qch * ld_all * sizeof(uint64_t));
+            ws.lists.reserve(tb);
+            // the pinned block of the route: [off u64 x qch | cnt u32 x qch | take u32 x qch]; cnt is copied from the device, off and take are
+            // written by the host between two stream syncs -- never while a kernel that reads them is in flight
+            char *hp = static_cast<char *>(ws.pinned(qch * (sizeof(uint64_t) + 2 * sizeof(uint32_t))));
+            uint64_t *p_off = reinterpret_cast<uint64_t *>(hp);
+            uint32_t *p_cnt = reinterpret_cast<uint32_t *>(p_off + qch), *p_take = p_cnt + qch;
+            char *d_plan = ws.misc.as<char>();
+            if (!h_items.empty()) VDB_HIP(hipMemcpyAsync(d_plan, h_items.data(), h_items.size() * sizeof(GroupedItem), hipMemcpyHostToDevice, s));
+            VDB_HIP(hipMemcpyAsync(d_plan + off_q, plan.slot_query.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            VDB_HIP(hipMemsetAsync(d_plan + off_c, 0, ns * sizeof(uint32_t), s));
+            const GroupedItem *d_items = reinterpret_cast<const GroupedItem *>(d_plan);
+            const uint32_t *d_slot_q = reinterpret_cast<const uint32_t *>(d_plan + off_q);
+            uint32_t *d_slot_c = reinterpret_cast<uint32_t *>(d_plan + off_c);
+            if (metric == MET_COSINE) launch_row_sqnorm(d_q, nq, (uint32_t)dim, ws.qsq.as<float>(), s);
+            for (const MultiChunk &c : plan.chunks) {
+                if (c.nitems == 0) continue;  // (only masks without rows: every count stays 0)
+                const uint32_t nb = (uint32_t)c.nslots;
+                VDB_HIP(hipMemsetAsync(ws.keys_a.p, 0xFF, uint64_t(nb) * c.ld * sizeof(uint64_t), s));  // PAIR_NONE pads sort last
+                prof_begin(ws, "flat_range_gather_grouped", double(c.rows) * dim * sizeof(float));
+                launch_range_gather_grouped(d_rows.as<float>(), (uint32_t)dim, d_items + c.item0, c.nitems, d_slot_q + c.slot0, d_q, metric,
+                                            d_sq.as<float>(), ws.qsq.as<float>(), d_radius, ws.keys_a.as<uint64_t>(), c.ld, d_slot_c + c.slot0, s);
+                prof_end(ws);
+                VDB_HIP(hipMemcpyAsync(p_cnt, d_slot_c + c.slot0, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+                VDB_SYNC(s);
+                uint64_t add = 0, max_take = 0;
+                for (uint32_t j = 0; j < nb; j++) {
+                    const uint64_t q = plan.slot_query[c.slot0 + j], t = limit ? std::min<uint64_t>(p_cnt[j], limit) : p_cnt[j];
+                    h_cnt[q] = t;
+                    h_off[q] = pool.used + add;
+                    p_off[j] = pool.used + add;
+                    p_take[j] = (uint32_t)t;
+                    add += t;
+                    max_take = std::max(max_take, t);
+                }
+                if (add == 0) continue;
+                pool.room(add, cap_pairs, s);
+                launch_sort_rows(ws.keys_a.as<uint64_t>(), ws.keys_b.as<uint64_t>(), nb, c.ld, ws.lists.p, tb, s);
+                launch_range_append(ws.keys_b.as<uint64_t>(), c.ld, p_off, p_take, nb, max_take, pool.buf.as<uint64_t>(), s);
+                pool.used += add;
+                VDB_SYNC(s);  // (the pinned block is rewritten by the next chunk)
+            }
+        }
+        VDB_SYNC(s);  // (the plan's host arrays are pageable memory: alive until here)
+        uint64_t total = 0;
+        for (uint64_t q = 0; q < nq; q++) total += h_cnt[q];
+        out.idx.reserve(total * sizeof(uint64_t));  // (what can fail for want of memory fails before the assemble counts the results)
+        out.dist.reserve(total * sizeof(float));
+        flat_range_assemble(ws, nq, pool, h_off, h_cnt, out);
+    } catch (...) {
+        range_i8_queries -= tally.i8;
+        range_scan_queries -= tally.scan;
+        range_hits -= tally.hits;
+        throw;
+    }
+    range_queries += nq;
+    range_grouped_queries += ns;
 }
 
 // ---- the approximate keys of the Flat shortlist pass, for every row ------------------------------------------------

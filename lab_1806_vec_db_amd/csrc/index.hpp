@@ -238,6 +238,16 @@ struct RangeResult {
     std::vector<uint64_t> lims;  // nq + 1 offsets, lims[0] = 0
     DevBuf idx, dist;            // lims[nq] ids (u64, local row + id_offset) / distances (f32), per query ascending by (distance, index)
 };
+// the sorted pair keys of a range call before the CSR arrays are gathered from them (Index::flat_range_collect / _assemble)
+struct RangePool {
+    DevBuf buf;
+    uint64_t used = 0;                                           // pair keys in buf
+    void room(uint64_t add, uint64_t cap_pairs, hipStream_t s);  // room for `add` more; throws past the ceiling of the call
+};
+// what a flat_range_collect added to the index's range counters
+struct RangeTally {
+    uint64_t i8 = 0, scan = 0, hits = 0;
+};
 
 // 16-row tiles of a fragment-ordered mirror of `rows` rows: whole 64-row items (k_flat_mfma), whole 2/3-tile units (k_flat_gemm, k_flat_gemm8)
 inline uint64_t mirror_tiles(uint64_t rows) { return ((rows + 15) / 16 + 11) / 12 * 12; }
@@ -495,6 +505,18 @@ struct Index {
     void flat_range_device(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit, RangeResult &out,
                            const RowMask *mask = nullptr);
     // (mask != nullptr: only the mask's allowed rows -- the filtered range search; nullptr: the unfiltered call, statement for statement)
+    // Its two halves: the sorted pair keys of every query into a pool, then the CSR arrays from (pool, offsets, counts).
+    void flat_range_collect(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit, const RowMask *mask, RangePool &rp,
+                            uint64_t *h_off, uint64_t *h_cnt, RangeTally *tally);
+    void flat_range_assemble(Workspace &ws, uint64_t nq, const RangePool &rp, const std::vector<uint64_t> &h_off, const std::vector<uint64_t> &h_cnt,
+                             RangeResult &out);
+    // The filtered range search with one mask per query (multi_plan.hpp): query q's slice is what flat_range_device returns for it alone
+    // under masks[mask_of[q]] (mask_of: host).  On an f32 index the buckets of masks of at most flat_filtered_direct_max rows are answered by
+    // one k_range_gather_grouped launch per chunk of queries; every other bucket is gathered and goes through flat_range_collect under its
+    // mask.  One pool, one assemble.  The caller has checked the masks and mask_of; returns synchronised.  A call that fails leaves every
+    // counter but the high-water mark range_hits_max as it found it.
+    void flat_range_masked_multi_device(Workspace &ws, const float *d_q, uint64_t nq, const float *d_radius, uint64_t limit,
+                                        const RowMask *const *masks, uint64_t n_masks, const uint32_t *mask_of, RangeResult &out);
     // Exact filtered k-NN (k_filter.hip): the first min(k, m) pairs of FlatIndex::knn over the mask's allowed rows; returns synchronised.
     // Direct path (gathered strict-order scan) for short allow-lists and wherever the 8-bit tier does not apply; otherwise the 8-bit
     // filter pass with the masked row constants + the exact stage, its open queries redone by the direct path.  A sibling of
@@ -539,6 +561,7 @@ struct Index {
     uint64_t range_max_results = 0;  // ceiling on the pairs of one call ("flat_range_max_results"; 0: what the device can hold)
     std::atomic<uint64_t> range_queries{0}, range_i8_queries{0}, range_scan_queries{0}, range_hits{0}, range_results{0};
     std::atomic<uint64_t> range_hits_max{0};  // longest hit list of a query the tier answered
+    std::atomic<uint64_t> range_multi_calls{0}, range_grouped_queries{0};  // range calls with a mask per query / queries their grouped launch answered
 };
 
 struct WsLease {

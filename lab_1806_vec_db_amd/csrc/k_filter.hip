@@ -13,6 +13,8 @@
 // unchanged: the hit list holds allowed rows only and every allowed row outside it has key > tau.
 //
 // Range scan.  k_mask_dense_nan turns the dense distance of every disallowed row into NaN: "a NaN distance is never inside".
+// With one mask per query (Index::flat_range_masked_multi_device) k_range_gather_grouped folds the gathered rows of many allow-lists in
+// one launch and keeps the pairs with D <= radius itself.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -337,6 +339,105 @@ void launch_scan_gather_grouped(const float *X, uint32_t dim, const GroupedItem 
         hipLaunchKernelGGL((k_scan_gather_grouped<FOLD_L2>), grid, block, 0, s, X, dim, items, slot_q, Q, metric, xsq, qsq, out, ld);
     else
         hipLaunchKernelGGL((k_scan_gather_grouped<FOLD_DOT>), grid, block, 0, s, X, dim, items, slot_q, Q, metric, xsq, qsq, out, ld);
+    VDB_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------
+// gathered RANGE scan over many allow-lists in one launch (one mask per query: Index::flat_range_masked_multi_device).  The work item,
+// the fold and the epilogue are those of k_scan_gather_grouped -- the same statements, so the same bits -- but the radius is known, so the
+// distance is not stored: the pair (slot b, column j) is inside when d <= radius[slot_q[b]] (false for a NaN on either side), and its
+// pair key (orderable(d), ROW ids[j]) is appended to the slot's row of `keys`.  The append: a wave ballot, one atomicAdd on the slot's
+// counter by lane 0, every lane writing at base + its prefix in the ballot.  Every (slot, column) is evaluated once, so a slot's counter
+// never passes its m <= ld.  The order of arrival is not deterministic; the keys of a slot are distinct (distinct rows) and are sorted next.
+// A thread whose column is past the list folds nothing and votes "outside": every wave reaches every ballot with all its lanes.
+// ---------------------------------------------------------------------------------------------
+template <int BQ, int FOLD>
+__device__ __forceinline__ void range_grouped_body(const float *__restrict__ x, uint32_t r, bool valid, uint32_t dim, const uint32_t *__restrict__ sq,
+                                                   const float *__restrict__ Q, int metric, const float *__restrict__ xsq,
+                                                   const float *__restrict__ qsq, const float *__restrict__ radius, uint64_t *__restrict__ keys,
+                                                   uint64_t ld, uint32_t *__restrict__ cnt) {
+    const float *qp[BQ];
+#pragma unroll
+    for (int b = 0; b < BQ; b++) qp[b] = Q + uint64_t(sq[b]) * dim;  // wave-uniform
+    float acc[BQ];
+#pragma unroll
+    for (int b = 0; b < BQ; b++) acc[b] = 0.0f;
+    if (valid) {
+        if ((dim & 3) == 0) {
+            const float4 *x4 = reinterpret_cast<const float4 *>(x);
+            for (uint32_t c = 0; c < dim / 4; c++) {
+                float4 v = x4[c];
+#pragma unroll
+                for (int b = 0; b < BQ; b++) {
+                    const float *q = qp[b] + 4 * c;
+                    acc[b] = fold1<FOLD>(acc[b], v.x, q[0]);
+                    acc[b] = fold1<FOLD>(acc[b], v.y, q[1]);
+                    acc[b] = fold1<FOLD>(acc[b], v.z, q[2]);
+                    acc[b] = fold1<FOLD>(acc[b], v.w, q[3]);
+                }
+            }
+        } else {
+            for (uint32_t c = 0; c < dim; c++) {
+                float v = x[c];
+#pragma unroll
+                for (int b = 0; b < BQ; b++) acc[b] = fold1<FOLD>(acc[b], v, qp[b][c]);
+            }
+        }
+    }
+    const float xs = (metric == MET_L2_DIRECT || !valid) ? 0.0f : xsq[r];
+    const uint32_t lane = threadIdx.x & 63;
+#pragma unroll
+    for (int b = 0; b < BQ; b++) {
+        const float qs = (metric == MET_L2_DIRECT) ? 0.0f : qsq[sq[b]];
+        const float d = epilogue(metric, acc[b], xs, qs);
+        const bool keep = valid && d <= radius[sq[b]];  // (the radius is wave-uniform, like the query rows)
+        const uint64_t vote = __ballot(keep);
+        if (vote == 0) continue;  // wave-uniform
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(cnt + b, (uint32_t)__builtin_popcountll(vote));
+        base = __shfl(base, 0);
+        if (keep) keys[uint64_t(b) * ld + base + (uint32_t)__builtin_popcountll(vote & ((1ull << lane) - 1))] = pair_key(d, r);
+    }
+}
+
+template <int FOLD>
+__global__ __launch_bounds__(256) void k_range_gather_grouped(const float *__restrict__ X, uint32_t dim, const GroupedItem *__restrict__ items,
+                                                              const uint32_t *__restrict__ slot_q, const float *__restrict__ Q, int metric,
+                                                              const float *__restrict__ xsq, const float *__restrict__ qsq,
+                                                              const float *__restrict__ radius, uint64_t *__restrict__ keys, uint64_t ld,
+                                                              uint32_t *__restrict__ cnt) {
+    const GroupedItem it = items[blockIdx.x];
+    const uint64_t j = uint64_t(it.tile) * 256 + threadIdx.x;
+    const bool valid = j < it.m;
+    const uint32_t r = valid ? it.ids[j] : 0;
+    const float *x = X + uint64_t(r) * dim;
+    const uint32_t *sq = slot_q + it.slot;
+    uint64_t *o = keys + uint64_t(it.slot) * ld;
+    uint32_t *c = cnt + it.slot;
+    switch (it.nb) {  // wave-uniform
+        case 1: range_grouped_body<1, FOLD>(x, r, valid, dim, sq, Q, metric, xsq, qsq, radius, o, ld, c); break;
+        case 2: range_grouped_body<2, FOLD>(x, r, valid, dim, sq, Q, metric, xsq, qsq, radius, o, ld, c); break;
+        case 3: range_grouped_body<3, FOLD>(x, r, valid, dim, sq, Q, metric, xsq, qsq, radius, o, ld, c); break;
+        case 4: range_grouped_body<4, FOLD>(x, r, valid, dim, sq, Q, metric, xsq, qsq, radius, o, ld, c); break;
+        case 5: range_grouped_body<5, FOLD>(x, r, valid, dim, sq, Q, metric, xsq, qsq, radius, o, ld, c); break;
+        case 6: range_grouped_body<6, FOLD>(x, r, valid, dim, sq, Q, metric, xsq, qsq, radius, o, ld, c); break;
+        case 7: range_grouped_body<7, FOLD>(x, r, valid, dim, sq, Q, metric, xsq, qsq, radius, o, ld, c); break;
+        case 8: range_grouped_body<8, FOLD>(x, r, valid, dim, sq, Q, metric, xsq, qsq, radius, o, ld, c); break;
+        default: break;
+    }
+}
+
+void launch_range_gather_grouped(const float *X, uint32_t dim, const GroupedItem *items, uint64_t nitems, const uint32_t *slot_q, const float *Q,
+                                 int metric, const float *xsq, const float *qsq, const float *radius, uint64_t *keys, uint64_t ld, uint32_t *cnt,
+                                 hipStream_t s) {
+    if (nitems == 0) return;
+    VDB_REQUIRE(metric == MET_L2_DIRECT || metric == MET_COSINE, "range_gather_grouped: metric");
+    VDB_REQUIRE(nitems < (1ull << 31), "range_gather_grouped: too many work items");
+    dim3 grid((unsigned)nitems), block(256);
+    if (metric == MET_L2_DIRECT)
+        hipLaunchKernelGGL((k_range_gather_grouped<FOLD_L2>), grid, block, 0, s, X, dim, items, slot_q, Q, metric, xsq, qsq, radius, keys, ld, cnt);
+    else
+        hipLaunchKernelGGL((k_range_gather_grouped<FOLD_DOT>), grid, block, 0, s, X, dim, items, slot_q, Q, metric, xsq, qsq, radius, keys, ld, cnt);
     VDB_HIP(hipGetLastError());
 }
 

@@ -318,6 +318,12 @@ struct GroupedItem {
 // out[(slot + b) * ld + j] = D(row ids[j], query slot_q[slot + b]) for every item, b < nb and column j of its tile; any dim
 void launch_scan_gather_grouped(const float *X, uint32_t dim, const GroupedItem *items, uint64_t nitems, const uint32_t *slot_q, const float *Q,
                                 int metric, const float *xsq, const float *qsq, float *out, uint64_t ld, hipStream_t s);
+// The same work items for a RANGE call (Index::flat_range_masked_multi_device): instead of storing D, every pair with
+// D <= radius[slot_q[slot + b]] appends its key (orderable(D), ROW ids[j]) to keys[(slot + b) * ld + ..] at the position cnt[slot + b]
+// hands out (cnt: zeroed u32 per slot; keys: filled with PAIR_NONE, ld >= every m).  Unordered within a slot; cnt[s] <= m afterwards.
+void launch_range_gather_grouped(const float *X, uint32_t dim, const GroupedItem *items, uint64_t nitems, const uint32_t *slot_q, const float *Q,
+                                 int metric, const float *xsq, const float *qsq, const float *radius, uint64_t *keys, uint64_t ld, uint32_t *cnt,
+                                 hipStream_t s);
 // launch_filter_finalize with a list, a length and an output position per slot: slot s holds the keys of query slot_q[s] over the columns
 // of slot_ids[s] (slot_m[s] of them); columns at and past slot_m[s] are padding.  Writes all kstride slots and the count of that query.
 void launch_filter_finalize_grouped(const uint64_t *keys, uint64_t ldk, uint32_t nslots, uint32_t ksel, uint32_t kstride, const uint32_t *const *slot_ids,

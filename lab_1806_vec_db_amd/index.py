@@ -464,6 +464,31 @@ class GpuIndex:
                                                 L.vp(stream), C.byref(h)))
         return self._range_out(h, int(nq))
 
+    def range_search_multi(self, queries, radius, masks, mask_of, limit: int | None = None):
+        """range_search with ONE MASK PER QUERY (vdb_flat_range_filtered_multi): query q's slice is what
+        range_search(queries[q], radius[q], limit, mask=masks[mask_of[q]]) returns; the buckets of short masks share one scan launch.
+        `radius`: one value, or one per query; `masks`: a sequence of RowMask of this index, `mask_of`: nq indexes into it, in any
+        order.  Returns (lims, idx, dist) as range_search does."""
+        q = _f32(queries)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        nq, dim = q.shape
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (nq,)))
+        if limit is not None and int(limit) <= 0:
+            raise ValueError("limit must be positive (None: no limit)")
+        arr, n_masks, mo = self._mask_args(masks, mask_of, nq)
+        h = L.vp()
+        L.check(self._lib.vdb_flat_range_filtered_multi(self._h, _ptr(q, L.f32p), nq, dim, _ptr(r, L.f32p), int(limit or 0), arr, n_masks,
+                                                        _ptr(mo, L.u32p), C.byref(h)))
+        return self._range_out(h, nq)
+
+    def range_search_multi_device(self, q_ptr: int, nq: int, radius_ptr: int, masks, mask_of, limit: int | None = None, stream: int = 0):
+        """the same with device-resident queries (f32 [nq][dim]) and radii (f32 [nq]); returns synchronised, results on the host"""
+        arr, n_masks, mo = self._mask_args(masks, mask_of, int(nq))
+        h = L.vp()
+        L.check(self._lib.vdb_flat_range_filtered_multi_device(self._h, L.vp(q_ptr), int(nq), self.dim, L.vp(radius_ptr), int(limit or 0), arr,
+                                                               n_masks, _ptr(mo, L.u32p), L.vp(stream), C.byref(h)))
+        return self._range_out(h, int(nq))
+
     def knn_with_ef(self, queries, k: int, ef: int):
         """IndexKNNWithEf::knn_with_ef; Flat ignores ef (dynamic_index.rs:75-80)."""
         if self.has_hnsw():

@@ -423,6 +423,47 @@ class VecDB:
             _, idx, dist = t.index.range_search(q, np.float32(upper_bound), limit)
             return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist)]
 
+    def batch_search_within(self, key: str, queries, upper_bound, limit: int | None = None, filters=None):
+        """search_within for a batch of queries in ONE library call: entry q of the returned list is what search_within(key,
+        queries[q], upper_bound[q], limit, filter_q) returns.  `upper_bound`: one value, or one per query.  `filters`: None, ONE
+        metadata pattern for every query, or a list of len(queries) patterns ({} matches every row).  With filters the batch is one
+        range_search_multi call over one mask per distinct pattern; without, one range_search call."""
+        t = self._t(key)
+        ix = t.index
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != ix.dim:
+            raise RuntimeError(f"Dimension mismatch: table dim {ix.dim}, got {q.shape}")
+        nq = q.shape[0]
+        if filters is not None and not isinstance(filters, dict):
+            filters = list(filters)
+            if len(filters) != nq:
+                raise RuntimeError(f"filters: one pattern per query is needed ({nq}), got {len(filters)}")
+        ub = np.asarray(upper_bound, dtype=np.float32).reshape(-1)
+        if ub.shape[0] not in (1, nq):
+            raise RuntimeError(f"upper_bound: one value, or one per query ({nq}), got {ub.shape[0]}")
+        if nq == 0:
+            return []
+        pats = None
+        if filters is not None:
+            pats = [filters] * nq if isinstance(filters, dict) else filters
+            t.prepare(pats)
+        with t.lock.read():  # one read guard for the whole batch, mask building and metadata lookup included
+            if pats is not None:
+                slot: dict[frozenset, int] = {}
+                distinct, mask_of = [], np.zeros(nq, dtype=np.uint32)
+                for i, p in enumerate(pats):
+                    pk = frozenset(p.items())
+                    if pk not in slot:
+                        slot[pk] = len(distinct)
+                        distinct.append(p)
+                    mask_of[i] = slot[pk]
+                masks = t.masks_for(distinct)  # the ones not cached yet: one library call
+                lims, idx, dist = ix.range_search_multi(q, ub, masks, mask_of, limit)
+            else:
+                lims, idx, dist = ix.range_search(q, ub, limit)
+            return [[(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx[int(lims[j]):int(lims[j + 1])], dist[int(lims[j]):int(lims[j + 1])])]
+                    for j in range(nq)]
+
     def extract_data(self, key: str):
         t = self._t(key)
         with t.lock.read():
