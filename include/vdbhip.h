@@ -567,7 +567,16 @@ int vdb_pq_merge_resort_device(vdb_index *idx, const void *d_adc_keys, const voi
  *                         (dynamic_index.rs:11-94) lives in one process;
  *   vdb_ctx_create_rank   one process per GPU (ncclCommInitRank): rank 0 obtains a 128-byte id from vdb_ctx_unique_id, the
  *                         host distributes it (MPI, a file, torch.distributed's store ...), every rank passes it in.
- * RCCL is loaded at run time (dlopen) by the first context that needs a communicator (world > 1). */
+ * RCCL is loaded at run time (dlopen) by the first context that needs a communicator (world > 1).
+ * Two environment variables, both read when a context is created, exist for the tests of this layer on a 1-GPU box:
+ *   VDB_CTX_FORCE_RCCL=1  builds the communicator even for one rank, so that the real (1-rank) ncclAllGather calls run;
+ *   VDB_CTX_LOOPBACK=1    vdb_ctx_create only: the same device id may appear more than once, every entry becomes a rank of its own
+ *                         (world = n_dev, ranks 0..n_dev-1), NO communicator is built (vdb_ctx_info: has_comm = 0) and the exchange
+ *                         is done with device copies between the local shards.  Partition, block layouts, merges, the two-phase
+ *                         range exchange, the replica query split and the per-shard host threads then run as they do with n_dev
+ *                         GPUs.  A test seam, not a way to gain throughput: S shards of one GPU share that GPU and add the
+ *                         exchange on top.  Refused (invalid argument) together with VDB_CTX_FORCE_RCCL=1; vdb_ctx_create_rank
+ *                         ignores it. */
 typedef struct vdb_ctx vdb_ctx;
 typedef struct vdb_sharded vdb_sharded;
 int vdb_ctx_create(const int *device_ids, int n_dev, vdb_ctx **out);
@@ -639,17 +648,19 @@ int vdb_sharded_ivf_knn(vdb_sharded *sh, const float *queries, uint64_t nq, uint
  * from phase 1's offsets -- passes the smallest ceiling fails on every rank before phase 2.  In both cases the object is NOT poisoned and
  * the next call may succeed.  An error inside a collective, or after phase 1 has committed the ranks to phase 2 (the staging buffers or
  * the result cannot be allocated), poisons the object in a multi-process job as below.
- * Exercised on hardware with ONE rank (both phases as real 1-rank ncclAllGather calls under VDB_CTX_FORCE_RCCL=1, the merge with S = 1);
- * the merge with S > 1 is tested on one GPU through vdb_range_merge_device.  World > 1 over RCCL -- several local GPUs, several
- * processes, the agreement of the ranks on a non-poisoning error -- is correct by construction, not by test. */
+ * Exercised on hardware with ONE rank over RCCL (both phases as real 1-rank ncclAllGather calls under VDB_CTX_FORCE_RCCL=1, the merge with
+ * S = 1) and with 3 and 8 ranks on one GPU through the loopback exchange (VDB_CTX_LOOPBACK=1: both phases, the merge, the concatenation,
+ * a failing rank's status word and the merged-total check with S > 1).  World > 1 over RCCL itself -- several GPUs, several processes -- is
+ * correct by construction, not by test. */
 int vdb_sharded_flat_range(vdb_sharded *sh, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit,
                            vdb_range **out);
 /* Failed sharded calls.  vdb_sharded_set_rows[_replica] is all-or-nothing: when one GPU fails (out of memory, say) every
  * shard is rolled back to an empty index and the call may be repeated.  A SEARCH that fails on one rank of a multi-PROCESS
  * context (vdb_ctx_create_rank, world > 1) may leave the other ranks inside the all-gather; the object is then "poisoned"
  * (vdb_sharded_poisoned -> 1) and refuses further searches with VDB_ERR_STATE-style errors: destroy it on every rank.
- * Exercised on hardware with ONE rank only (the test boxes have one GPU): the N > 1 paths -- ncclCommInitAll, grouped
- * all-gathers over several local GPUs, cross-process ordering -- are correct by construction, not by test. */
+ * RCCL has run on hardware with ONE rank only (the test boxes have one GPU): ncclCommInitAll and grouped all-gathers over several
+ * local GPUs, cross-process ordering and the poisoning above are correct by construction, not by test.  Everything around the
+ * collective runs with up to 8 ranks on one GPU under VDB_CTX_LOOPBACK=1 (tests/test_ctx_many_shards_gpu.py). */
 int vdb_sharded_poisoned(const vdb_sharded *sh, int *out);
 
 /* ---- measurement hooks -------------------------------------------------------------------

@@ -10,6 +10,9 @@
 //                                               vdb_ctx_unique_id that the host distributes), the layout of bench.py.
 // RCCL is bound at run time (dlopen of librccl.so.1, the library of this ROCm image / of the PyTorch wheel already in
 // the process): single-GPU users of libvdbhip.so never load it.
+// VDB_CTX_LOOPBACK=1 (read by vdb_ctx_create; a test seam, vdbhip.h) forms no communicator at all: the listed devices, repeats
+// allowed, become ranks 0..n_dev-1 and all_gather copies the blocks between the local shards.  Everything but the ncclAllGather call
+// is then the code a real n_dev-rank single-process context runs, on one GPU.
 //
 // Row partition: rank r of S holds rows [r * ceil(N/S), min(N, (r+1) * ceil(N/S))) and reports global ids
 // (id_offset).  Exchange block of a rank: [nq*k ids u64 | nq*k distances f32 | pad to 8 | nq counts u64]; the merge
@@ -82,6 +85,9 @@ struct vdb_ctx {
     std::vector<int> devices;    // this process's GPUs ...
     std::vector<int> ranks;      // ... and their ranks
     std::vector<ncclComm_t> comms;  // one per local GPU; empty when no communicator exists (world == 1 without force)
+    bool loopback = false;       // VDB_CTX_LOOPBACK=1: no communicator, the all-gather is device copies between the local shards
+    // the searches exchange their blocks (the receive buffer holds world blocks); otherwise the send buffer is the answer
+    bool exchanges() const { return !comms.empty() || loopback; }
     ~vdb_ctx() {
         for (size_t i = 0; i < comms.size(); i++) {
             (void)hipSetDevice(devices[i]);
@@ -180,10 +186,39 @@ bool multi_process(const vdb_sharded &sh) { return (size_t)sh.ctx->world > sh.sh
 
 // one all-gather (or two, for the PQ key rows) over the communicator: every local GPU contributes `bytes` from send[i]
 // and receives world * bytes into recv[i], ordered on the shard's stream; without a communicator (world == 1) the
-// receive buffer IS the send buffer
+// receive buffer IS the send buffer.
+// A loopback context (every rank is a local shard) gathers with device copies on the receiving shard's stream.  RCCL orders a
+// rank's collective after what its own stream holds -- the callers that fill the send buffer with an async copy rely on it -- and
+// ends it on every rank together; copies on another shard's stream know neither, so all streams are synchronised before the first
+// copy (the sources are complete) and after the last (nobody overwrites a send buffer a peer still reads).
 void all_gather(vdb_sharded &sh, const std::vector<std::pair<const void *, void *>> &bufs_per_shard, size_t n_ops, size_t bytes) {
     vdb_ctx &c = *sh.ctx;
-    if (c.comms.empty()) return;
+    if (!c.exchanges()) return;
+    if (c.loopback) {
+        const size_t nl = sh.shards.size();  // == world, rank r is shard r
+        auto sync_all = [&] {
+            for (size_t i = 0; i < nl; i++) {
+                VDB_HIP(hipSetDevice(c.devices[i]));
+                VDB_SYNC(sh.shards[i]->stream);
+            }
+        };
+        sync_all();
+        for (size_t i = 0; i < nl; i++) {
+            VDB_HIP(hipSetDevice(c.devices[i]));
+            for (size_t o = 0; o < n_ops; o++) {
+                char *recv = static_cast<char *>(bufs_per_shard[i * n_ops + o].second);
+                for (size_t r = 0; r < nl; r++) {
+                    const void *send = bufs_per_shard[r * n_ops + o].first;
+                    if (c.devices[r] == c.devices[i])
+                        VDB_HIP(hipMemcpyAsync(recv + r * bytes, send, bytes, hipMemcpyDeviceToDevice, sh.shards[i]->stream));
+                    else
+                        VDB_HIP(hipMemcpyPeerAsync(recv + r * bytes, c.devices[i], send, c.devices[r], bytes, sh.shards[i]->stream));
+                }
+            }
+        }
+        sync_all();
+        return;
+    }
     Rccl &r = Rccl::get();
     VDB_NCCL(r.GroupStart());
     for (size_t i = 0; i < sh.shards.size(); i++) {
@@ -222,6 +257,7 @@ void replica_search(vdb_sharded &sh, const float *queries, uint64_t nq, uint64_t
     for (uint64_t c0 = 0; c0 < nq; c0 += CHUNK) {
         const uint64_t nb = std::min(CHUNK, nq - c0), per = (nb + S - 1) / S;
         const uint64_t off_d = per * k * 8, off_c = (per * k * 12 + 7) / 8 * 8, block = off_c + per * 8;
+        VDB_REQUIRE((off_c & 7) == 0 && (block & 7) == 0, "misaligned block layout");  // (u64 counts, and u64 ids of the next rank's block)
         for_each_shard(sh.shards.size(), [&](size_t i) {
             Shard &s = *sh.shards[i];
             Index &ix = s.handle->ix;
@@ -230,7 +266,7 @@ void replica_search(vdb_sharded &sh, const float *queries, uint64_t nq, uint64_t
             replica_block(nb, S, (uint64_t)sh.ctx->ranks[i], q0, q1);
             s.q.reserve(std::max<uint64_t>(per, 1) * dim * sizeof(float));
             s.send.reserve(block);
-            if (!sh.ctx->comms.empty()) s.recv.reserve(S * block);
+            if (sh.ctx->exchanges()) s.recv.reserve(S * block);
             VDB_HIP(hipMemsetAsync(s.send.p, 0, block, s.stream));
             if (q1 > q0)
                 VDB_HIP(hipMemcpyAsync(s.q.p, queries + (c0 + q0) * dim, (q1 - q0) * dim * sizeof(float), hipMemcpyHostToDevice, s.stream));
@@ -250,7 +286,7 @@ void replica_search(vdb_sharded &sh, const float *queries, uint64_t nq, uint64_t
         Shard &s0 = *sh.shards[0];
         s0.handle->ix.use_device();
         VDB_SYNC(s0.stream);  // the collective
-        const bool comm = !sh.ctx->comms.empty();
+        const bool comm = sh.ctx->exchanges();
         const uint64_t ns = comm ? S : 1;
         host.resize(ns * block);
         VDB_HIP(hipMemcpy(host.data(), comm ? s0.recv.p : s0.send.p, ns * block, hipMemcpyDeviceToHost));
@@ -266,19 +302,26 @@ void replica_search(vdb_sharded &sh, const float *queries, uint64_t nq, uint64_t
     }
 }
 
-void ctx_validate_devices(const int *device_ids, int n_dev) {
+void ctx_validate_devices(const int *device_ids, int n_dev, bool allow_repeats = false) {
     VDB_REQUIRE(device_ids && n_dev >= 1 && n_dev <= 64, "device list must hold 1..64 device ids");
     require_gpu();
     int cnt = 0;
     VDB_HIP(hipGetDeviceCount(&cnt));
     for (int i = 0; i < n_dev; i++) {
         VDB_REQUIRE(device_ids[i] >= 0 && device_ids[i] < cnt, "device id out of range");
-        for (int j = 0; j < i; j++) VDB_REQUIRE(device_ids[j] != device_ids[i], "a device may appear once in a context");
+        for (int j = 0; j < i && !allow_repeats; j++) VDB_REQUIRE(device_ids[j] != device_ids[i], "a device may appear once in a context");
     }
 }
 
 bool force_rccl() {
     const char *e = std::getenv("VDB_CTX_FORCE_RCCL");  // build the communicator even for one rank (exercises the RCCL path on a 1-GPU box)
+    return e && e[0] == '1';
+}
+
+bool loopback_exchange() {
+    // test seam: vdb_ctx_create makes every listed device (the same one may repeat) a rank of its own and exchanges with device copies
+    // instead of RCCL, so that the S > 1 paths run on a 1-GPU box
+    const char *e = std::getenv("VDB_CTX_LOOPBACK");
     return e && e[0] == '1';
 }
 
@@ -289,12 +332,15 @@ extern "C" {
 int vdb_ctx_create(const int *device_ids, int n_dev, vdb_ctx **out) {
     VDB_API_BEGIN
     VDB_REQUIRE(out, "null out");
-    ctx_validate_devices(device_ids, n_dev);
+    const bool loopback = loopback_exchange();
+    VDB_REQUIRE(!(loopback && force_rccl()), "VDB_CTX_LOOPBACK=1 and VDB_CTX_FORCE_RCCL=1 exclude each other (a loopback context has no communicator)");
+    ctx_validate_devices(device_ids, n_dev, loopback);
     std::unique_ptr<vdb_ctx> c(new vdb_ctx);
     c->world = n_dev;
     c->devices.assign(device_ids, device_ids + n_dev);
     for (int i = 0; i < n_dev; i++) c->ranks.push_back(i);
-    if (n_dev > 1 || force_rccl()) {
+    c->loopback = loopback;
+    if (!loopback && (n_dev > 1 || force_rccl())) {
         c->comms.assign(n_dev, nullptr);
         VDB_NCCL(Rccl::get().CommInitAll(c->comms.data(), n_dev, c->devices.data()));
     }
@@ -467,13 +513,14 @@ int vdb_sharded_flat_knn(vdb_sharded *sh, const float *queries, uint64_t nq, uin
     for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
         const uint64_t nb = std::min(CHUNK, nq - q0), kk = std::max<uint64_t>(k, 1);
         const uint64_t off_d = nb * kk * 8, off_c = (nb * kk * 12 + 7) / 8 * 8, block = off_c + nb * 8;
+        VDB_REQUIRE((off_c & 7) == 0 && (block & 7) == 0, "misaligned block layout");  // (u64 counts, and u64 ids of the next rank's block)
         for_each_shard(sh->shards.size(), [&](size_t i) {
             Shard &s = *sh->shards[i];
             Index &ix = s.handle->ix;
             ix.use_device();
             s.q.reserve(nb * dim * sizeof(float));
             s.send.reserve(block);
-            if (!sh->ctx->comms.empty()) s.recv.reserve(S * block);
+            if (sh->ctx->exchanges()) s.recv.reserve(S * block);
             VDB_HIP(hipMemcpyAsync(s.q.p, queries + q0 * dim, nb * dim * sizeof(float), hipMemcpyHostToDevice, s.stream));
             VDB_HIP(hipMemsetAsync(s.send.p, 0, block, s.stream));
             VDB_SYNC(s.stream);
@@ -491,8 +538,8 @@ int vdb_sharded_flat_knn(vdb_sharded *sh, const float *queries, uint64_t nq, uin
         Shard &s0 = *sh->shards[0];
         Index &ix0 = s0.handle->ix;
         ix0.use_device();
-        const char *g = sh->ctx->comms.empty() ? s0.send.as<char>() : s0.recv.as<char>();
-        const uint64_t ns = sh->ctx->comms.empty() ? 1 : S;
+        const char *g = sh->ctx->exchanges() ? s0.recv.as<char>() : s0.send.as<char>();
+        const uint64_t ns = sh->ctx->exchanges() ? S : 1;
         if (k > 0) {
             s0.o_idx.reserve(nb * kk * 8);
             s0.o_dist.reserve(nb * kk * 4);
@@ -553,7 +600,7 @@ int vdb_sharded_knn_pq(vdb_sharded *sh, const float *queries, uint64_t nq, uint6
             s.q.reserve(nb * dim * sizeof(float));
             s.adc.reserve(bytes);
             s.exact.reserve(bytes);
-            if (!sh->ctx->comms.empty()) {
+            if (sh->ctx->exchanges()) {
                 s.g_adc.reserve(S * bytes);
                 s.g_exact.reserve(S * bytes);
             }
@@ -573,7 +620,7 @@ int vdb_sharded_knn_pq(vdb_sharded *sh, const float *queries, uint64_t nq, uint6
         Shard &s0 = *sh->shards[0];
         Index &ix0 = s0.handle->ix;
         ix0.use_device();
-        const bool comm = !sh->ctx->comms.empty();
+        const bool comm = sh->ctx->exchanges();
         s0.o_idx.reserve(nb * k * 8);
         s0.o_dist.reserve(nb * k * 4);
         s0.o_cnt.reserve(nb * 8);
@@ -631,7 +678,7 @@ int vdb_sharded_hnsw_build(vdb_sharded *sh, uint64_t M, uint64_t ef_construction
         hnsw_attach(ix, h.m, h.ef_construction, h.level0.data(), h.len0.data(), h.vec_level.data(), h.upper.data(), h.upper_len.data(),
                     h.has_enter ? 1 : 0, h.enter_point, h.enter_level);
     }
-    if (!sh->ctx->comms.empty() && sh->ctx->world > 1) {
+    if (sh->ctx->exchanges() && sh->ctx->world > 1) {
         const uint64_t mine = hnsw_graph_hash(h), S = (uint64_t)sh->ctx->world;
         std::vector<std::pair<const void *, void *>> bufs;
         for (size_t i = 0; i < sh->shards.size(); i++) {
@@ -780,7 +827,7 @@ void sync_shards(vdb_sharded &sh) {
 }
 
 void sharded_range(vdb_sharded &sh, const float *queries, uint64_t nq, const float *radius, uint64_t limit, RangeResult &out) {
-    const bool replica = sh.layout == LAYOUT_REPLICA, comm = !sh.ctx->comms.empty();
+    const bool replica = sh.layout == LAYOUT_REPLICA, comm = sh.ctx->exchanges();
     const uint64_t S = (uint64_t)sh.ctx->world, ns = comm ? S : 1, dim = sh.dim;
     const size_t nl = sh.shards.size();
     RangeStagingGuard guard{sh};

@@ -5,7 +5,12 @@ VDB_CTX_FORCE_RCCL=1, where both phases are real 1-rank ncclAllGather calls and 
 block is copied out of the receive buffer (REPLICA layout).  Expected answers come from the oracle -- oracle.flat_knn_batch(base, qs,
 k = len) cut after the last pair with distance <= r, then after `limit` -- bit for bit; equality with GpuIndex.range_search is asserted in
 addition.  The call with more queries than one exchange chunk holds (2048) derives its expectation from the oracle's top-64 lists: with
-the radius at the 10th distance and the 64th distance asserted to lie outside it, the pairs inside the radius are a prefix of that list."""
+the radius at the 10th distance and the 64th distance asserted to lie outside it, the pairs inside the radius are a prefix of that list.
+
+More than one rank on the one GPU: under VDB_CTX_LOOPBACK=1 the context takes device 0 three or eight times and exchanges with device
+copies (modes loop3, loop8; the 40000x96 table only).  Phase 1 with short and empty replica blocks padded, phase 2 at the largest rank
+total, k_range_merge over S received blocks (ROWS), the concatenation of the blocks in query order (REPLICA), the status words of a rank
+whose local search failed and the merged-total check against the smallest ceiling then run with S > 1 -- same oracle, same equality."""
 import numpy as np
 import pytest
 
@@ -16,6 +21,7 @@ pytestmark = pytest.mark.gpu
 TABLES = {"40000x96": (40000, 96, 91, 92), "30000x960": (30000, 960, 1806, 1807)}
 ROWS_MODES = [("rows", m) for m in ("nocomm", "comm_all", "comm_rank")]
 REPLICA_MODES = [("replica", m) for m in ("nocomm", "comm_all")]
+LOOP_MODES = [(layout, m) for layout in ("rows", "replica") for m in ("loop3", "loop8")]  # S = 3, S = 8 through the loopback exchange
 NQ_CHUNKED = 2500  # more than one exchange chunk (2048 queries)
 
 
@@ -82,9 +88,35 @@ def tables():
     return out
 
 
+@pytest.fixture(scope="module")
+def chunked(tables):
+    """the call with more queries than one exchange chunk, on the 40000x96 table: queries, the oracle's top-64 lists, the radii"""
+    from oracle import oracle as O
+
+    base = tables["40000x96"][0]
+    many = gist_like(NQ_CHUNKED, dim=base.shape[1], seed=93)
+    oi, od, oc = O.flat_knn_batch(base, many, 64, 0, nthreads=16)
+    assert (oc == 64).all()
+    top = (oi.astype(np.uint64), od)
+    r = _kth(top, 10)
+    assert (od[:, 63] > r).all()  # the 64th pair is outside: the pairs inside the radius are a prefix of the top-64
+    return many, top, r
+
+
+def _loop_shards(mode):
+    return int(mode[4:]) if mode.startswith("loop") else 0
+
+
 def _make(layout, mode, dim, monkeypatch):
     from lab_1806_vec_db_amd.sharded import ShardedIndex
 
+    S = _loop_shards(mode)
+    if S:
+        monkeypatch.setenv("VDB_CTX_LOOPBACK", "1")
+        monkeypatch.delenv("VDB_CTX_FORCE_RCCL", raising=False)
+        sh = ShardedIndex(dim, "l2sqr", devices=[0] * S)
+        assert sh.info() == {"world": S, "n_local": S, "first_rank": 0, "has_comm": False}
+        return sh
     if mode != "nocomm":
         monkeypatch.setenv("VDB_CTX_FORCE_RCCL", "1")
     if mode == "comm_rank":
@@ -98,9 +130,17 @@ def _make(layout, mode, dim, monkeypatch):
 
 @pytest.mark.parametrize("table", list(TABLES))
 @pytest.mark.parametrize("layout,mode", ROWS_MODES + REPLICA_MODES)
-def test_sharded_range_search_one_gpu(tables, table, layout, mode, monkeypatch):
+def test_sharded_range_search_one_gpu(tables, chunked, table, layout, mode, monkeypatch):
+    _range_search_cases(tables, chunked, table, layout, mode, monkeypatch)
+
+
+@pytest.mark.parametrize("layout,mode", LOOP_MODES)
+def test_sharded_range_search_many_shards(tables, chunked, layout, mode, monkeypatch):
+    _range_search_cases(tables, chunked, "40000x96", layout, mode, monkeypatch)
+
+
+def _range_search_cases(tables, chunked, table, layout, mode, monkeypatch):
     import lab_1806_vec_db_amd as vdb
-    from oracle import oracle as O
 
     base, qs, full = tables[table]
     n, dim = base.shape
@@ -148,12 +188,7 @@ def test_sharded_range_search_one_gpu(tables, table, layout, mode, monkeypatch):
             assert sh.local_stat(0, "flat_range_scan_queries") - s0 == len(qs)
         else:
             # more queries in one call than one exchange chunk holds
-            many = gist_like(NQ_CHUNKED, dim=dim, seed=93)
-            oi, od, oc = O.flat_knn_batch(base, many, 64, 0, nthreads=16)
-            assert (oc == 64).all()
-            top = (oi.astype(np.uint64), od)
-            r = _kth(top, 10)
-            assert (od[:, 63] > r).all()  # the 64th pair is outside: the pairs inside the radius are a prefix of the top-64
+            many, top, r = chunked
             for limit in (None, 4):
                 got = sh.range_search(many, r, limit)
                 _same(got, _expect(top, r, limit), (layout, mode, "chunked", limit, "oracle"))
@@ -173,5 +208,61 @@ def test_sharded_range_on_an_index_with_zero_rows(layout):
         lims, idx, dist = sh.range_search(np.ones((7, 16), dtype=np.float32), np.inf)
         assert lims.tolist() == [0] * 8 and len(idx) == 0 and len(dist) == 0
         assert not sh.poisoned
+    finally:
+        sh.close()
+
+
+def _rank_totals(layout, S, n, exp):
+    """pairs every rank holds of the expected answer `exp` (no limit): ROWS -- the ids of its row block; REPLICA -- its query block"""
+    lims, ids, _ = exp
+    nq = len(lims) - 1
+    if layout == "rows":
+        per = -(-n // S)
+        return [int(((ids >= r * per) & (ids < (r + 1) * per)).sum()) for r in range(S)]
+    per = -(-nq // S)
+    return [int(lims[min(nq, (r + 1) * per)] - lims[min(nq, r * per)]) for r in range(S)]
+
+
+@pytest.mark.parametrize("layout", ["rows", "replica"])
+def test_sharded_range_ceilings_with_three_ranks(tables, layout, monkeypatch):
+    """S = 3: (a) the ceiling of ONE rank's local search -- its status word reaches every rank in phase 1, the error names that rank;
+    (b) every rank within its own ceiling but the merged (ROWS) / concatenated (REPLICA) total above the smallest one -- the check
+    between the phases.  Both fail without poisoning the object, and the next call is correct."""
+    import lab_1806_vec_db_amd as vdb
+
+    base, qs, full = tables["40000x96"]
+    n, dim = base.shape
+    cases = _radius_cases(full)
+    sh = _make(layout, "loop3", dim, monkeypatch)
+    try:
+        (sh.set_rows if layout == "rows" else sh.set_rows_replica)(base)
+        exp64 = _expect(full, cases["kth64"])
+        totals = _rank_totals(layout, 3, n, exp64)
+        merged = int(exp64[0][-1])
+        assert sum(totals) == merged and min(totals) > 0
+
+        def small_calls(what):
+            assert not sh.poisoned
+            _same(sh.range_search(qs, cases["below1"]), _expect(full, cases["below1"]), what)
+            _same(sh.range_search(qs[:2], cases["kth10"][:2]), _expect((full[0][:2], full[1][:2]), cases["kth10"][:2]), what)
+
+        # (a) rank 1 alone has a ceiling, below its share of the answer
+        small = 40
+        assert totals[1] > small >= int(_expect((full[0][:2], full[1][:2]), cases["kth10"][:2])[0][-1])
+        sh.local_index(1).set_param("flat_range_max_results", small)
+        with pytest.raises(vdb.VdbError, match=r"failed on rank 1; rank 1: .*flat_range_max_results"):
+            sh.range_search(qs, cases["kth64"])
+        small_calls("after rank 1's ceiling")
+        sh.local_index(1).set_param("flat_range_max_results", 0)
+        _same(sh.range_search(qs, cases["kth64"]), exp64, "ceiling lifted")
+        # (b) a ceiling every rank's own total passes, set on the last rank only: the smallest one bounds the merged total
+        ceiling = (max(totals) + merged) // 2
+        assert max(totals) < ceiling < merged
+        sh.local_index(2).set_param("flat_range_max_results", ceiling)
+        with pytest.raises(vdb.VdbError, match=rf"{merged} results for a chunk of {len(qs)} queries, more than {ceiling} "):
+            sh.range_search(qs, cases["kth64"])
+        small_calls("after the merged-total check")
+        sh.local_index(2).set_param("flat_range_max_results", merged)  # exactly the total: allowed
+        _same(sh.range_search(qs, cases["kth64"]), exp64, "ceiling == total")
     finally:
         sh.close()

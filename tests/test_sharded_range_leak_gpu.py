@@ -1,5 +1,5 @@
 """GPU: the sharded range search leaves no device memory behind -- create / set_rows / range / close cycles in both layouts, with and
-without the 1-rank communicator, return all of it (hipMemGetInfo through torch); and at the ctypes level a vdb_range returned by
+without the 1-rank communicator and with three ranks on the one GPU (VDB_CTX_LOOPBACK=1), return all of it (hipMemGetInfo through torch); and at the ctypes level a vdb_range returned by
 vdb_sharded_flat_range is still readable after vdb_sharded_destroy and gives its memory back on vdb_range_destroy."""
 import ctypes as C
 import gc
@@ -32,6 +32,20 @@ def test_sharded_range_cycles_return_all_memory(monkeypatch):
             sh.set_rows_replica(base[:3000])
             sh.range_search(qs, np.inf)
             sh.close()
+        # three ranks on the one GPU through the loopback exchange: the phase-2 staging (send block, 3 x that to receive) of every shard
+        monkeypatch.setenv("VDB_CTX_FORCE_RCCL", "0")
+        monkeypatch.setenv("VDB_CTX_LOOPBACK", "1")
+        sh = ShardedIndex(64, "l2sqr", devices=[0, 0, 0])
+        sh.set_rows(base)
+        lims, idx, dist = sh.range_search(qs, np.inf)
+        assert int(lims[-1]) == 40 * 20000
+        sh.range_search(qs, np.inf, limit=7)
+        sh.close()
+        sh = ShardedIndex(64, "l2sqr", devices=[0, 0, 0])
+        sh.set_rows_replica(base[:3000])
+        sh.range_search(qs, np.inf)
+        sh.close()
+        monkeypatch.delenv("VDB_CTX_LOOPBACK")
 
     cycle()  # first use: the runtime's own pools, the library's code objects, RCCL's
     gc.collect()
