@@ -292,8 +292,34 @@ int vdb_flat_range_filtered_multi_device(vdb_index *idx, const void *d_queries, 
  * 4 B x terms x rows read as before plus one 8-byte bitmap gather per in-range row and bitmap term (from a block that stays cached).
  * vdb_get_stat "mask_where_set_masks" counts the masks built by these two calls ("mask_where_masks" keeps counting the equality calls
  * only); vdb_prof_get "mask_where_sets" times k_mask_where_sets with its scan and ids launches.
- * Not covered: sharded and replica contexts, OR across columns and mask algebra (a mask is one conjunction), a single-pass partition of
- * one column into the masks of all its values, labels in bincode files, filtered k-NN on VecSet<u8> indexes. */
+ * OR OF CONJUNCTIONS (vdb_mask_create_where_any / _many; csrc/mask_any.hpp, k_mask_where_any, docs/DESIGN_flat.md 4.1o): a mask is the
+ * OR of up to VDB_MASK_MAX_CLAUSES clauses, a clause the AND of up to VDB_MASK_MAX_TERMS terms, a term exactly the set / range term above
+ * with the same match -- a filter expression in disjunctive normal form, NOT pushed down to the terms (toggling VDB_TERM_NEGATE and
+ * VDB_TERM_NONE complements a term exactly).  Clause c's terms are entries [clause_lims[c], clause_lims[c + 1]) of the term arrays
+ * (n_clauses + 1 entries, clause_lims[0] == 0, non-decreasing); in the _many form mask g's clauses are [mask_lims[g], mask_lims[g + 1])
+ * (n_masks + 1 entries, the same rules); set_lims / set_words as above, over all terms of the call.
+ *   - n_clauses == 0 gives the EMPTY mask (m = 0) -- unlike n_terms == 0 of the conjunction calls, which allows every row;
+ *   - a clause with zero terms allows every row;
+ *   - a mask of ONE clause is bit-identical to the vdb_mask_create_where_sets mask of that clause's terms.
+ * Everything is checked before anything is launched; VDB_ERR_INVALID with a message, every out[g] NULL, index and counters unchanged for:
+ * more than VDB_MASK_MAX_CLAUSES clauses in a mask, more than VDB_MASK_MAX_TERMS terms in a clause, mask_lims / clause_lims not starting
+ * at 0 or decreasing, every argument error vdb_mask_create_where_sets_many lists, more than VDB_MASK_MAX_SET_BITS bitmap bits in the
+ * call.  n_masks == 0 succeeds.  Read-side, all-or-nothing and chunked like the other _many calls; terms, clause limits and bitmaps of
+ * the call are uploaded once.  One kernel pass per chunk: a wave owns a mask word and loops over the mask's clauses, so a column is
+ * read once per term that names it (4 B x terms x rows over all clauses, repeated reads of a column served by cache).  The
+ * result is the same vdb_mask object: owner / staleness rules, lazily built row constants, f32 and VecSet<u8> indexes, every call that
+ * takes a vdb_mask.  vdb_get_stat "mask_where_any_masks" counts the masks built by these two calls (the older counters keep counting
+ * only their own calls); vdb_prof_get "mask_where_any" times k_mask_where_any with its scan and ids launches.
+ * MASK ALGEBRA (vdb_mask_combine; k_mask_combine): out = the AND (VDB_MASK_OP_AND) or OR (VDB_MASK_OP_OR) over n_in (1 .. 8) masks of
+ * this index, input i complemented first when invert != NULL and invert[i] != 0; n_in == 1 with invert set is NOT.  For what the
+ * columns cannot express: inputs may come from any constructor, host-built masks (vdb_mask_create) included.  A complement is taken
+ * within the index's rows: bits at and past vdb_index_len are clear in the result.  Every input is checked as the filtered searches
+ * check a mask -- a mask of another index: VDB_ERR_INVALID, a stale mask: VDB_ERR_STATE -- and n_in == 0, n_in > 8, a NULL input or
+ * an unknown op is VDB_ERR_INVALID; nothing is computed on error and *out is NULL.  Read-side; the result is an ordinary mask.
+ * vdb_get_stat "mask_combine_masks" counts them; vdb_prof_get "mask_combine" times k_mask_combine with its scan and ids launches.
+ * Not covered: sharded and replica contexts, normal forms past VDB_MASK_MAX_CLAUSES clauses in one call (combine the parts with
+ * vdb_mask_combine), a single-pass partition of one column into the masks of all its values, labels in bincode files, filtered k-NN on
+ * VecSet<u8> indexes. */
 #define VDB_LABEL_COLUMNS 16
 #define VDB_LABEL_NONE 0xFFFFFFFFu
 #define VDB_MASK_MAX_TERMS 8
@@ -310,6 +336,16 @@ int vdb_mask_create_where_sets(vdb_index *idx, const uint32_t *columns, const ui
 int vdb_mask_create_where_sets_many(vdb_index *idx, const uint64_t *term_lims, const uint32_t *columns, const uint32_t *lo,
                                     const uint32_t *hi, const uint32_t *flags, const uint64_t *set_lims, const uint64_t *set_words,
                                     uint64_t n_masks, vdb_mask **out);
+#define VDB_MASK_MAX_CLAUSES 64
+int vdb_mask_create_where_any(vdb_index *idx, const uint64_t *clause_lims, uint64_t n_clauses, const uint32_t *columns, const uint32_t *lo,
+                              const uint32_t *hi, const uint32_t *flags, const uint64_t *set_lims, const uint64_t *set_words,
+                              vdb_mask **out);
+int vdb_mask_create_where_any_many(vdb_index *idx, const uint64_t *mask_lims, const uint64_t *clause_lims, const uint32_t *columns,
+                                   const uint32_t *lo, const uint32_t *hi, const uint32_t *flags, const uint64_t *set_lims,
+                                   const uint64_t *set_words, uint64_t n_masks, vdb_mask **out);
+#define VDB_MASK_OP_AND 0
+#define VDB_MASK_OP_OR 1
+int vdb_mask_combine(vdb_index *idx, int op, const vdb_mask *const *in, const uint8_t *invert, uint64_t n_in, vdb_mask **out);
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids);
 /* the approximate keys the Flat shortlist pass compares with its threshold, for EVERY row, from the same kernel in its dense
  * mode (test / measurement entry point behind the certification-bound tests): out_keys [nq][len];
@@ -408,7 +444,9 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *                        sets, the ones the 8-bit tier passed on (0: tier not run) and the ones that reached the exact stage; "ivf_last_rows_fetched_q8":
  *                        rows the cluster-major 8-bit tier read, once each (0: query-major),
  *   "mask_where_masks"   masks built on the device from the label columns (vdb_mask_create_where*); "mask_where_set_masks": the ones
- *                        built from set / range terms (vdb_mask_create_where_sets*); "label_columns": allocated columns,
+ *                        built from set / range terms (vdb_mask_create_where_sets*); "mask_where_any_masks": the ones built from an OR of
+ *                        conjunctions (vdb_mask_create_where_any*); "mask_combine_masks": the ones vdb_mask_combine made;
+ *                        "label_columns": allocated columns,
  *   "hbm_bytes_per_row"  resident HBM bytes per row over all per-row buffers (rows, norms, mirrors, PQ codes, level-0 links, label
  *                        columns). */
 int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out);

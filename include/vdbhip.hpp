@@ -218,6 +218,37 @@ public:
         check(vdb_mask_create_where_sets(h_, cols.data(), lo.data(), hi.data(), flags.data(), lims.data(), words.data(), terms.size(), &m));
         return Mask(m);
     }
+    // an OR of conjunctions of such terms (vdb_mask_create_where_any): a row is allowed when it matches every term of SOME clause; no
+    // clauses: the empty mask; a clause without terms: every row
+    Mask make_mask_where_any(const std::vector<std::vector<LabelTerm>> &clauses) const {
+        std::vector<uint32_t> cols, lo, hi, flags;
+        std::vector<uint64_t> clims{0}, lims{0}, words;
+        for (const auto &c : clauses) {
+            for (const auto &t : c) {
+                cols.push_back(t.column);
+                lo.push_back(t.lo);
+                hi.push_back(t.hi);
+                flags.push_back((t.negate ? VDB_TERM_NEGATE : 0u) | (t.none ? VDB_TERM_NONE : 0u));
+                words.insert(words.end(), t.set.begin(), t.set.end());
+                lims.push_back(words.size());
+            }
+            clims.push_back(cols.size());
+        }
+        vdb_mask *m = nullptr;
+        check(vdb_mask_create_where_any(h_, clims.data(), clauses.size(), cols.data(), lo.data(), hi.data(), flags.data(), lims.data(), words.data(), &m));
+        return Mask(m);
+    }
+    // the AND (VDB_MASK_OP_AND) or OR (VDB_MASK_OP_OR) of 1 .. 8 masks of this index, mask i complemented within the rows first when
+    // invert[i] (vdb_mask_combine); `invert` is empty or as long as `masks`
+    Mask combine_masks(int op, const std::vector<const Mask *> &masks, const std::vector<bool> &invert = {}) const {
+        std::vector<const vdb_mask *> hs;
+        for (const Mask *mk : masks) hs.push_back(mk->handle());
+        std::vector<uint8_t> inv(invert.begin(), invert.end());
+        inv.resize(masks.size(), 0);
+        vdb_mask *m = nullptr;
+        check(vdb_mask_combine(h_, op, hs.data(), invert.empty() ? nullptr : inv.data(), hs.size(), &m));
+        return Mask(m);
+    }
     // per query the first min(k, mask.count()) pairs of knn_batch over the allowed rows alone (vdb_flat_knn_filtered)
     std::vector<std::vector<CandidatePair>> knn_filtered_batch(const float *queries, uint64_t nq, uint64_t k, const Mask &mask) const {
         std::vector<uint64_t> idx(nq * (k ? k : 1)), cnt(nq);

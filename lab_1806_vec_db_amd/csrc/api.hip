@@ -689,6 +689,51 @@ int vdb_mask_create_where_sets(vdb_index *idx, const uint32_t *columns, const ui
     return vdb_mask_create_where_sets_many(idx, lims, columns, lo, hi, flags, set_lims, set_words, 1, out);
     VDB_API_END
 }
+// an OR of conjunctions of set / range terms (Index::masks_where_any, mask_any.hpp); AND / OR / NOT of masks (Index::mask_combine)
+static_assert(MASK_MAX_CLAUSES == VDB_MASK_MAX_CLAUSES && MASK_OP_AND == VDB_MASK_OP_AND && MASK_OP_OR == VDB_MASK_OP_OR, "vdbhip.h, mask_any.hpp and kernels.hpp agree");
+int vdb_mask_create_where_any_many(vdb_index *idx, const uint64_t *mask_lims, const uint64_t *clause_lims, const uint32_t *columns,
+                                   const uint32_t *lo, const uint32_t *hi, const uint32_t *flags, const uint64_t *set_lims,
+                                   const uint64_t *set_words, uint64_t n_masks, vdb_mask **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    VDB_REQUIRE(n_masks == 0 || out, "null argument");
+    for (uint64_t g = 0; g < n_masks; g++) out[g] = nullptr;
+    VDB_REQUIRE(n_masks < (1ull << 28), "too many masks for one call");
+    std::vector<std::unique_ptr<vdb_mask>> made(n_masks);
+    std::vector<RowMask *> rm(n_masks);
+    for (uint64_t g = 0; g < n_masks; g++) {
+        made[g].reset(new vdb_mask);
+        rm[g] = &made[g]->m;
+    }
+    idx->ix.masks_where_any(mask_lims, clause_lims, columns, lo, hi, flags, set_lims, set_words, n_masks, rm.data());  // a throw destroys every mask with `made`
+    for (uint64_t g = 0; g < n_masks; g++) out[g] = made[g].release();
+    VDB_API_END
+}
+int vdb_mask_create_where_any(vdb_index *idx, const uint64_t *clause_lims, uint64_t n_clauses, const uint32_t *columns, const uint32_t *lo,
+                              const uint32_t *hi, const uint32_t *flags, const uint64_t *set_lims, const uint64_t *set_words, vdb_mask **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx && out, "null argument");
+    *out = nullptr;
+    const uint64_t lims[2] = {0, n_clauses};
+    return vdb_mask_create_where_any_many(idx, lims, clause_lims, columns, lo, hi, flags, set_lims, set_words, 1, out);
+    VDB_API_END
+}
+int vdb_mask_combine(vdb_index *idx, int op, const vdb_mask *const *in, const uint8_t *invert, uint64_t n_in, vdb_mask **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx && out, "null argument");
+    *out = nullptr;
+    VDB_REQUIRE(n_in >= 1 && n_in <= MASK_COMBINE_MAX, "mask combine: " + std::to_string(n_in) + " inputs, 1 .. " + std::to_string(MASK_COMBINE_MAX) + " are supported");
+    VDB_REQUIRE(in, "null argument");
+    const RowMask *rm[MASK_COMBINE_MAX];
+    for (uint64_t i = 0; i < n_in; i++) {
+        VDB_REQUIRE(in[i], "null mask");
+        rm[i] = &in[i]->m;
+    }
+    std::unique_ptr<vdb_mask> mk(new vdb_mask);
+    idx->ix.mask_combine(op, rm, invert, n_in, mk->m);
+    *out = mk.release();
+    VDB_API_END
+}
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids) {
     VDB_API_BEGIN
     VDB_REQUIRE(m, "null mask");
@@ -1216,6 +1261,10 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.mask_where_masks.load();
     else if (n == "mask_where_set_masks")  // masks built from set / range terms (vdb_mask_create_where_sets*)
         *out = idx->ix.mask_where_set_masks.load();
+    else if (n == "mask_where_any_masks")  // masks built from an OR of conjunctions (vdb_mask_create_where_any*)
+        *out = idx->ix.mask_where_any_masks.load();
+    else if (n == "mask_combine_masks")  // masks built by vdb_mask_combine
+        *out = idx->ix.mask_combine_masks.load();
     else if (n == "label_columns")  // allocated label columns (4 B per row each)
         *out = idx->ix.label_columns();
     else if (n == "hbm_bytes_per_row")

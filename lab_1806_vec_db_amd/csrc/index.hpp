@@ -554,6 +554,23 @@ struct Index {
     void masks_where_sets(const uint64_t *term_lims, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi, const uint32_t *flags,
                           const uint64_t *set_lims, const uint64_t *set_words, uint64_t n_masks, RowMask *const *out);
     std::atomic<uint64_t> mask_where_set_masks{0};  // masks built by masks_where_sets
+    // An OR of conjunctions of such terms (mask_any.hpp; k_mask_where_any): mask g = the rows that match EVERY term of SOME clause in
+    // [mask_lims[g], mask_lims[g + 1]); clause c's terms are [clause_lims[c], clause_lims[c + 1]) of the term arrays.  A mask without
+    // clauses is empty, a clause without terms allows every row.  Same contract as masks_where_sets.
+    void masks_where_any(const uint64_t *mask_lims, const uint64_t *clause_lims, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi,
+                         const uint32_t *flags, const uint64_t *set_lims, const uint64_t *set_words, uint64_t n_masks, RowMask *const *out);
+    std::atomic<uint64_t> mask_where_any_masks{0};  // masks built by masks_where_any
+    // out = AND (op 0) / OR (op 1) over n_in (1 .. MASK_COMBINE_MAX) masks of this index, input i complemented within the rows first when
+    // invert && invert[i] (k_mask_combine).  Every input is checked with check_mask before anything is computed; read-side; returns
+    // synchronised; on a throw the caller discards `out`.
+    void mask_combine(int op, const RowMask *const *in, const uint8_t *invert, uint64_t n_in, RowMask &out);
+    std::atomic<uint64_t> mask_combine_masks{0};  // masks built by mask_combine
+    // The second half of all four: given the bit-word kernel as `launch(g0, nb)` (it enqueues the kernel and k_mask_scan for masks
+    // [g0, g0 + nb) of the call, whose jobs are in ws.keys_b, block counts in ws.flags, totals in ws.misc; the caller's tables are in
+    // ws.keys_a), runs the chunk loop -- headers and jobs, launch, ONE read-back of the totals, allow-lists, k_mask_ids.
+    // lims[g] .. lims[g + 1] = the range a job carries (nullptr: none); bytes(g0, nb) = what the launch reads, for the profile entry `prof`.
+    void masks_finish(Workspace &ws, const uint64_t *lims, uint64_t n_masks, RowMask *const *out, const char *prof,
+                      const std::function<double(uint64_t, uint64_t)> &bytes, const std::function<void(uint64_t, uint64_t)> &launch);
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};

@@ -1,7 +1,8 @@
 // k_labels.hip -- label columns (one u32 per row and column, Index::d_labels) and the row masks built from them on the device
 // (Index::masks_where): upkeep of the columns under add / swap_remove / remove_rows, and the three kernels that turn a conjunction of
 // `column == code` terms into a RowMask's bit words and its ascending allow-list (docs/DESIGN_flat.md 4.1l), and the kernel that does the
-// same for set / range terms (Index::masks_where_sets, mask_sets.hpp; 4.1m).
+// same for set / range terms (Index::masks_where_sets, mask_sets.hpp; 4.1m), for an OR of such conjunctions (Index::masks_where_any,
+// mask_any.hpp; 4.1o) and for the AND / OR / NOT of finished masks (Index::mask_combine; 4.1o).
 #include <algorithm>
 
 #include "kernels.hpp"
@@ -80,6 +81,15 @@ __global__ __launch_bounds__(256) void k_mask_where(const MaskTerm *__restrict__
 // (v - lo) >> 6 is below the bitmap's ceil((hi - lo + 1) / 64) words.  The bitmap read is a per-lane gather of one 8-byte word from a
 // block of at most a few KiB that every wave of the mask re-reads: it stays in cache, and LDS staging per 256-row workgroup would move
 // more bytes than the gather does.
+__device__ __forceinline__ bool set_term_match(const SetTerm tm, uint64_t row, bool in) {
+    const uint32_t v = (tm.col && in) ? tm.col[row] : LABEL_NONE;
+    const bool labelled = v != LABEL_NONE;
+    const uint32_t off = v - tm.lo;
+    bool inside = labelled && tm.lo <= v && v <= tm.hi;
+    const uint64_t bw = (inside && tm.bitmap) ? tm.bitmap[off >> 6] : ~0ull;
+    inside = inside && ((bw >> (off & 63)) & 1);
+    return labelled ? inside != bool(tm.flags & TERM_NEGATE) : bool(tm.flags & TERM_NONE);
+}
 __global__ __launch_bounds__(256) void k_mask_where_sets(const SetTerm *__restrict__ terms, const MaskJob *__restrict__ jobs, uint64_t n,
                                                          uint32_t nwords, uint32_t nblocks, uint32_t *__restrict__ blockcnt) {
     __shared__ uint32_t s_cnt[4];
@@ -90,14 +100,7 @@ __global__ __launch_bounds__(256) void k_mask_where_sets(const SetTerm *__restri
     const bool in = row < n;
     bool ok = in;
     for (uint32_t t = job.t0; t < job.t1; t++) {  // (wave-uniform)
-        const SetTerm tm = terms[t];
-        const uint32_t v = (tm.col && in) ? tm.col[row] : LABEL_NONE;
-        const bool labelled = v != LABEL_NONE;
-        const uint32_t off = v - tm.lo;
-        bool inside = labelled && tm.lo <= v && v <= tm.hi;
-        const uint64_t bw = (inside && tm.bitmap) ? tm.bitmap[off >> 6] : ~0ull;
-        inside = inside && ((bw >> (off & 63)) & 1);
-        ok = ok && (labelled ? inside != bool(tm.flags & TERM_NEGATE) : bool(tm.flags & TERM_NONE));
+        ok = ok && set_term_match(terms[t], row, in);
     }
     const uint64_t w = __ballot(ok);
     if (lane == 0) {
@@ -106,6 +109,61 @@ __global__ __launch_bounds__(256) void k_mask_where_sets(const SetTerm *__restri
     }
     __syncthreads();
     if (threadIdx.x == 0) blockcnt[size_t(blockIdx.y) * nblocks + blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// An OR of up to MASK_MAX_CLAUSES such conjunctions (mask_any.hpp; docs/DESIGN_flat.md 4.1o): the same wave, word and ballot, with an
+// outer loop over the mask's clauses [job.t0, job.t1) of the clause table -- clause c is terms [clims[c], clims[c + 1]).  Both loops are
+// wave-uniform.  okc = in-range AND every term of the clause (set_term_match: the loads keep their two rules), any |= okc; rows at and
+// past n are false in every clause, so the tail bits stay clear; a mask without clauses is empty, a clause without terms allows every
+// row.  A column that several clauses name is re-read from cache.  (A wave-uniform exit from the clause loop once every in-range lane
+// is allowed was measured and bought nothing: docs/DESIGN_flat.md 4.1o.)
+__global__ __launch_bounds__(256) void k_mask_where_any(const SetTerm *__restrict__ terms, const uint32_t *__restrict__ clims,
+                                                        const MaskJob *__restrict__ jobs, uint64_t n, uint32_t nwords, uint32_t nblocks,
+                                                        uint32_t *__restrict__ blockcnt) {
+    __shared__ uint32_t s_cnt[4];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const MaskJob job = jobs[blockIdx.y];
+    const uint32_t word = blockIdx.x * 4 + wave;
+    const uint64_t row = uint64_t(word) * 64 + lane;
+    const bool in = row < n;
+    bool any = false;
+    for (uint32_t c = job.t0; c < job.t1; c++) {  // (wave-uniform)
+        const uint32_t t1 = clims[c + 1];
+        bool okc = in;
+        for (uint32_t t = clims[c]; t < t1; t++) okc = okc && set_term_match(terms[t], row, in);  // (wave-uniform)
+        any = any || okc;
+    }
+    const uint64_t w = __ballot(any);
+    if (lane == 0) {
+        if (word < nwords) job.bits[word] = w;
+        s_cnt[wave] = (uint32_t)__popcll(w);  // (a word at or past nwords has no row below n: 0)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) blockcnt[size_t(blockIdx.y) * nblocks + blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// AND / OR of up to MASK_COMBINE_MAX finished masks, input i complemented first when bit i of a.invert is set.  One thread per entry of
+// blockcnt, i.e. per four output words (32 contiguous bytes of every input): it writes the words and their popcount, which is the
+// blockcnt contract of the kernels above, so k_mask_scan and k_mask_ids follow unchanged.  The bits at and past n of the last word are
+// cleared after the operation: a complement stays within the index's rows.
+__global__ __launch_bounds__(256) void k_mask_combine(MaskCombine a, uint64_t *__restrict__ out, uint64_t n, uint32_t nwords, uint32_t nblocks,
+                                                      uint32_t *__restrict__ blockcnt) {
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= nblocks) return;
+    uint32_t cnt = 0;
+    for (uint32_t u = 0; u < 4; u++) {
+        const uint32_t word = b * 4 + u;
+        if (word >= nwords) break;
+        uint64_t acc = a.op == MASK_OP_AND ? ~0ull : 0ull;
+        for (uint32_t i = 0; i < a.n_in; i++) {
+            const uint64_t w = a.in[i][word] ^ (((a.invert >> i) & 1) ? ~0ull : 0ull);
+            acc = a.op == MASK_OP_AND ? acc & w : acc | w;
+        }
+        if (word == nwords - 1 && (n & 63)) acc &= (1ull << (n & 63)) - 1;
+        out[word] = acc;
+        cnt += (uint32_t)__popcll(acc);
+    }
+    blockcnt[b] = cnt;
 }
 
 // One workgroup per mask: blockcnt[mask][0 .. nblocks) -> its exclusive prefix sums, in place; totals[mask] = the sum (the mask's m).
@@ -170,6 +228,19 @@ void launch_mask_where_sets(const SetTerm *terms, const MaskJob *jobs, uint32_t 
     if (n_masks == 0 || nblocks == 0) return;
     hipLaunchKernelGGL(k_mask_where_sets, dim3(nblocks, n_masks), dim3(256), 0, s, terms, jobs, n, nwords, nblocks, blockcnt);
     hipLaunchKernelGGL(k_mask_scan, dim3(n_masks), dim3(256), 0, s, blockcnt, nblocks, totals);
+}
+void launch_mask_where_any(const SetTerm *terms, const uint32_t *clims, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt,
+                           uint32_t *totals, hipStream_t s) {
+    const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
+    if (n_masks == 0 || nblocks == 0) return;
+    hipLaunchKernelGGL(k_mask_where_any, dim3(nblocks, n_masks), dim3(256), 0, s, terms, clims, jobs, n, nwords, nblocks, blockcnt);
+    hipLaunchKernelGGL(k_mask_scan, dim3(n_masks), dim3(256), 0, s, blockcnt, nblocks, totals);
+}
+void launch_mask_combine(const MaskCombine &a, uint64_t *out, uint64_t n, uint32_t *blockcnt, uint32_t *totals, hipStream_t s) {
+    const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
+    if (nblocks == 0) return;
+    hipLaunchKernelGGL(k_mask_combine, dim3((nblocks + 255) / 256), dim3(256), 0, s, a, out, n, nwords, nblocks, blockcnt);
+    hipLaunchKernelGGL(k_mask_scan, dim3(1), dim3(256), 0, s, blockcnt, nblocks, totals);
 }
 void launch_mask_ids(const MaskJob *jobs, uint32_t *const *ids, uint32_t n_masks, uint64_t n, const uint32_t *blockoff, hipStream_t s) {
     const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);

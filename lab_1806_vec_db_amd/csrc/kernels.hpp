@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "mask_any.hpp"
 #include "mask_sets.hpp"
 
 namespace vdb {
@@ -366,6 +367,20 @@ void launch_mask_where(const MaskTerm *terms, const MaskJob *jobs, uint32_t n_ma
 // the same for set / range terms (k_mask_where_sets + k_mask_scan; the term table of mask_sets.hpp, bitmaps resident on the device)
 void launch_mask_where_sets(const SetTerm *terms, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals,
                             hipStream_t s);
+// the same for an OR of conjunctions (k_mask_where_any + k_mask_scan; mask_any.hpp): jobs[g].t0 / t1 = the mask's clauses in the clause
+// table clims, clims[c] .. clims[c + 1] = the clause's terms
+void launch_mask_where_any(const SetTerm *terms, const uint32_t *clims, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt,
+                           uint32_t *totals, hipStream_t s);
+// out = AND / OR over the bit words of n_in finished masks over the same n rows, input i complemented first when bit i of invert is set;
+// bits at and past n clear; blockcnt / totals as above for the one mask  (k_mask_combine + k_mask_scan)
+constexpr uint32_t MASK_COMBINE_MAX = 8;
+constexpr int MASK_OP_AND = 0, MASK_OP_OR = 1;  // VDB_MASK_OP_AND / VDB_MASK_OP_OR
+struct MaskCombine {  // (kernel argument, by value)
+    const uint64_t *in[MASK_COMBINE_MAX];
+    uint32_t n_in, invert;
+    int op;
+};
+void launch_mask_combine(const MaskCombine &a, uint64_t *out, uint64_t n, uint32_t *blockcnt, uint32_t *totals, hipStream_t s);
 // ids[g][0 .. totals[g]) = the allowed rows of mask g, ascending (k_mask_ids; after launch_mask_where on the same stream)
 void launch_mask_ids(const MaskJob *jobs, uint32_t *const *ids, uint32_t n_masks, uint64_t n, const uint32_t *blockoff, hipStream_t s);
 void mfma_set_sample_thin(int v);

@@ -75,6 +75,7 @@ def pack_mask(allow, n: int) -> np.ndarray:
 LABEL_COLUMNS = 16         # VDB_LABEL_COLUMNS
 LABEL_NONE = 0xFFFFFFFF    # VDB_LABEL_NONE
 MASK_MAX_TERMS = 8         # VDB_MASK_MAX_TERMS
+MASK_OP_AND, MASK_OP_OR = 0, 1  # VDB_MASK_OP_AND / VDB_MASK_OP_OR
 
 
 def _terms_arrays(terms):
@@ -375,6 +376,51 @@ class GpuIndex:
         L.check(self._lib.vdb_mask_create_where_sets_many(self._h, _ptr(tlims, L.u64p), _ptr(cols, L.u32p), _ptr(lo, L.u32p), _ptr(hi, L.u32p),
                                                           _ptr(flags, L.u32p), _ptr(lims, L.u64p), _ptr(words, L.u64p), len(lists), arr))
         return [RowMask.from_handle(self, arr[g]) for g in range(len(lists))]
+
+    def make_mask_where_any(self, clauses) -> RowMask:
+        """the mask of the rows that match every LabelTerm of SOME clause of `clauses` (a sequence of sequences of LabelTerm) -- an OR of
+        conjunctions over the label columns, built on the device in one pass (vdb_mask_create_where_any).  No clauses: the empty mask;
+        a clause without terms: every row"""
+        cl = [list(c) for c in clauses]
+        clims = np.zeros(len(cl) + 1, dtype=np.uint64)
+        clims[1:] = np.cumsum([len(c) for c in cl], dtype=np.uint64)
+        cols, lo, hi, flags, lims, words = _set_terms_arrays([tm for c in cl for tm in c])
+        h = L.vp()
+        L.check(self._lib.vdb_mask_create_where_any(self._h, _ptr(clims, L.u64p), len(cl), _ptr(cols, L.u32p), _ptr(lo, L.u32p), _ptr(hi, L.u32p),
+                                                    _ptr(flags, L.u32p), _ptr(lims, L.u64p), _ptr(words, L.u64p), C.byref(h)))
+        return RowMask.from_handle(self, h)
+
+    def make_masks_where_any(self, list_of_clause_lists) -> list[RowMask]:
+        """one mask per entry of `list_of_clause_lists` (each what make_mask_where_any takes) in ONE library call
+        (vdb_mask_create_where_any_many); all-or-nothing: an invalid entry raises and no mask is made"""
+        masks = [[list(c) for c in clauses] for clauses in list_of_clause_lists]
+        mlims = np.zeros(len(masks) + 1, dtype=np.uint64)
+        mlims[1:] = np.cumsum([len(m) for m in masks], dtype=np.uint64)
+        cl = [c for m in masks for c in m]
+        clims = np.zeros(len(cl) + 1, dtype=np.uint64)
+        clims[1:] = np.cumsum([len(c) for c in cl], dtype=np.uint64)
+        cols, lo, hi, flags, lims, words = _set_terms_arrays([tm for c in cl for tm in c])
+        arr = (L.vp * max(len(masks), 1))()
+        L.check(self._lib.vdb_mask_create_where_any_many(self._h, _ptr(mlims, L.u64p), _ptr(clims, L.u64p), _ptr(cols, L.u32p), _ptr(lo, L.u32p),
+                                                         _ptr(hi, L.u32p), _ptr(flags, L.u32p), _ptr(lims, L.u64p), _ptr(words, L.u64p),
+                                                         len(masks), arr))
+        return [RowMask.from_handle(self, arr[g]) for g in range(len(masks))]
+
+    def combine_masks(self, op, masks, invert=None) -> RowMask:
+        """the AND (op "and" / MASK_OP_AND) or OR ("or" / MASK_OP_OR) of 1 .. 8 masks of this index, mask i complemented within the
+        rows first where invert[i] is true, computed on the device (vdb_mask_combine).  One mask with invert=[True] is NOT.  The inputs
+        may come from any constructor; a stale mask or one of another index raises"""
+        code = {"and": MASK_OP_AND, "or": MASK_OP_OR}.get(op.lower(), -1) if isinstance(op, str) else int(op)
+        ms = list(masks)
+        arr = (L.vp * max(len(ms), 1))(*[m._h for m in ms])
+        inv = None
+        if invert is not None:
+            inv = np.ascontiguousarray([bool(x) for x in invert], dtype=np.uint8)
+            if inv.shape[0] != len(ms):
+                raise ValueError(f"combine_masks: {len(ms)} masks, {inv.shape[0]} invert flags")
+        h = L.vp()
+        L.check(self._lib.vdb_mask_combine(self._h, code, arr, None if inv is None else _ptr(inv, L.u8p), len(ms), C.byref(h)))
+        return RowMask.from_handle(self, h)
 
     def flat_knn_filtered(self, queries, k: int, mask: RowMask):
         """Exact k-NN over the mask's allowed rows alone (vdb_flat_knn_filtered): the first min(k, len(mask)) pairs of flat_knn

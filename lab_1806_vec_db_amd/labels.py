@@ -13,6 +13,10 @@ index holds the codes (GpuIndex.set_labels) and evaluates patterns over them (Gp
     `matches` is the one definition of what they mean.  Over a label column every predicate on one key is a SET OF CODES plus one bit for
     "rows without a value": LabelCodec.compile evaluates the predicate over the column's dictionary (one entry per distinct value) and
     emits LabelTerm objects (column, [lo, hi], negate, none, codes) that the index tests per row (GpuIndex.make_masks_where_sets).
+  * A FILTER EXPRESSION joins patterns with AnyOf, AllOf and Not; `matches_filter` is the one definition of what it means.  Every term
+    has an exact complement (LabelTerm.complement), so LabelCodec.compile_any pushes NOT down to the terms and returns the expression's
+    disjunctive normal form: a list of clauses, each a list of LabelTerm, that the index evaluates in one pass
+    (GpuIndex.make_masks_where_any).
 """
 from __future__ import annotations
 
@@ -26,6 +30,7 @@ MASK_MAX_TERMS = 8       # VDB_MASK_MAX_TERMS
 TERM_NEGATE = 1          # VDB_TERM_NEGATE
 TERM_NONE = 2            # VDB_TERM_NONE
 MASK_MAX_SET_BITS = 1 << 27  # VDB_MASK_MAX_SET_BITS: bitmap bits per library call
+MASK_MAX_CLAUSES = 64    # VDB_MASK_MAX_CLAUSES
 
 # terms no row satisfies, whatever the columns hold: two different codes asked of one column
 NOTHING = ((0, 0), (0, 1))
@@ -104,6 +109,18 @@ class LabelTerm:
         if self.codes is not None:
             inside &= np.isin(v, np.asarray(self.codes, dtype=np.int64))
         return np.where(v == LABEL_NONE, self.none, inside != self.negate)
+
+    def complement(self) -> "LabelTerm":
+        """the term that matches exactly the rows this one does not: `negate` and `none` toggled (negate never touches the rows without
+        a value, so their bit is toggled on its own)"""
+        return LabelTerm(self.column, self.lo, self.hi, negate=not self.negate, none=not self.none, codes=self.codes)
+
+    def matches_nothing(self) -> bool:
+        """True when no label value can match: the empty range, plain"""
+        return self.lo > self.hi and not self.negate and not self.none
+
+    def matches_everything(self) -> bool:
+        return self.lo > self.hi and self.negate and self.none
 
     @staticmethod
     def of(term) -> "LabelTerm":
@@ -262,6 +279,92 @@ def has_predicates(pattern) -> bool:
     return any(isinstance(v, _Pred) for v in pattern.values())
 
 
+# ---- filter expressions: patterns joined by OR, AND and NOT ---------------------------------------------------------------------------
+def _leaf_key(e):
+    """what an operand contributes to its parent's identity: a pattern dict as frozenset(items) -- the key the mask cache files a
+    pattern under -- an expression as itself"""
+    if isinstance(e, _Expr):
+        return e
+    if isinstance(e, dict):
+        return frozenset(e.items())
+    raise TypeError(f"a filter expression is built from pattern dicts, AnyOf, AllOf and Not, not {type(e).__name__}")
+
+
+class _Expr:
+    """frozen and hashable, so an expression keys the mask cache; operand order matters to equality, not to meaning"""
+    __slots__ = ("exprs", "_k")
+
+    def __init__(self, *exprs):
+        k = tuple(_leaf_key(e) for e in exprs)
+        hash(k)  # (a pattern value that cannot be hashed fails here, not inside a search)
+        object.__setattr__(self, "exprs", tuple(dict(e) if isinstance(e, dict) else e for e in exprs))
+        object.__setattr__(self, "_k", k)
+
+    def __setattr__(self, k, v):
+        raise AttributeError("filter expressions are frozen")
+
+    def __eq__(self, other):
+        return type(other) is type(self) and self._k == other._k
+
+    def __hash__(self):
+        return hash((type(self).__name__, self._k))
+
+    def __repr__(self):
+        return f"{type(self).__name__}({', '.join(repr(e) for e in self.exprs)})"
+
+
+class AnyOf(_Expr):
+    """matches when ANY operand matches; AnyOf() matches nothing"""
+    __slots__ = ()
+
+
+class AllOf(_Expr):
+    """matches when EVERY operand matches; AllOf() matches everything"""
+    __slots__ = ()
+
+
+class Not(_Expr):
+    """matches when its operand does not"""
+    __slots__ = ()
+
+    def __init__(self, expr):
+        super().__init__(expr)
+
+    @property
+    def expr(self):
+        return self.exprs[0]
+
+
+def is_expression(f) -> bool:
+    return isinstance(f, _Expr)
+
+
+def filter_key(f):
+    """the hashable identity of a filter: frozenset(items) of a pattern, an expression as itself"""
+    return _leaf_key(f)
+
+
+def filter_patterns(f) -> list:
+    """the pattern dicts of a filter, left to right (a pattern: itself)"""
+    if isinstance(f, dict):
+        return [f]
+    return [p for e in f.exprs for p in filter_patterns(e)]
+
+
+def matches_filter(expr, metadata_row) -> bool:
+    """THE definition of a filter against one metadata dict: a pattern matches when every entry does (`matches` on
+    metadata_row.get(key): what the host loop does), AnyOf is any, AllOf is all, Not is not."""
+    if isinstance(expr, dict):
+        return all(matches(v, metadata_row.get(k)) for k, v in expr.items())
+    if isinstance(expr, AnyOf):
+        return any(matches_filter(e, metadata_row) for e in expr.exprs)
+    if isinstance(expr, AllOf):
+        return all(matches_filter(e, metadata_row) for e in expr.exprs)
+    if isinstance(expr, Not):
+        return not matches_filter(expr.expr, metadata_row)
+    raise TypeError(f"a filter is a pattern dict, AnyOf, AllOf or Not, not {type(expr).__name__}")
+
+
 class LabelCodec:
     def __init__(self, max_columns: int = LABEL_COLUMNS, max_terms: int = MASK_MAX_TERMS):
         self.max_columns = int(max_columns)
@@ -351,6 +454,34 @@ class LabelCodec:
                 out.append((col, code))
         return list(NOTHING) if nothing else out
 
+    def _entry_term(self, k, p):
+        """the one LabelTerm of a pattern entry (key k, value or predicate p) over the key's column -- the empty range when it can match
+        no row -- or None: the key has no column, or p is neither str, None nor a predicate"""
+        col = self.columns.get(k)
+        if col is None or not (self._value_ok(p) or isinstance(p, _Pred)):
+            return None
+        table = self.codes[col]
+        negate = False
+        if p is None:
+            return LabelTerm.of((col, LABEL_NONE))
+        if isinstance(p, str):
+            return LabelTerm.of((col, table[p])) if p in table else LabelTerm(col)
+        if isinstance(p, In):
+            codes, none = [table[v] for v in p.values if v is not None and v in table], None in p.values
+            negate = isinstance(p, NotIn)
+        elif isinstance(p, Ne):
+            v = p._k[0]
+            codes, none, negate = [table[v]] if v is not None and v in table else [], v is None, True
+        elif isinstance(p, Exists):
+            codes, none, negate = [], True, p._k[0]  # the rows without a value, or their complement
+        else:
+            codes, none = [c for v, c in table.items() if matches(p, v)], False
+        if negate:
+            none = not none  # the complement within "rows without a value" too
+        if codes and max(codes) - min(codes) + 1 == len(set(codes)):
+            return LabelTerm(col, min(codes), max(codes), negate=negate, none=none)  # a run of codes: a range, no bitmap
+        return LabelTerm(col, negate=negate, none=none, codes=codes)
+
     def compile(self, pattern):
         """the LabelTerm list of a pattern that may hold predicates, one term per key: a list (empty for the empty pattern), NOTHING
         when some entry can match no row (an In whose values were all never seen, an unseen plain value), None when the pattern is not
@@ -364,39 +495,75 @@ class LabelCodec:
         out = []
         nothing = False
         for k, p in pattern.items():
-            col = self.columns.get(k)
-            if col is None or not (self._value_ok(p) or isinstance(p, _Pred)):
+            term = self._entry_term(k, p)
+            if term is None:
                 return None
-            table = self.codes[col]
-            negate = False
-            if p is None:
-                codes, none = [], True
-            elif isinstance(p, str):
-                codes, none = [table[p]] if p in table else [], False
-            elif isinstance(p, In):
-                codes, none = [table[v] for v in p.values if v is not None and v in table], None in p.values
-                negate = isinstance(p, NotIn)
-            elif isinstance(p, Ne):
-                v = p._k[0]
-                codes, none, negate = [table[v]] if v is not None and v in table else [], v is None, True
-            elif isinstance(p, Exists):
-                codes, none, negate = [], True, p._k[0]  # the rows without a value, or their complement
-            else:
-                codes, none = [c for v, c in table.items() if matches(p, v)], False
-            if negate:
-                none = not none  # the complement within "rows without a value" too
-            if not codes and not negate and not none:
+            if term.matches_nothing():
                 nothing = True
                 continue
-            if codes and max(codes) - min(codes) + 1 == len(set(codes)):
-                term = LabelTerm(col, min(codes), max(codes), negate=negate, none=none)  # a run of codes: a range, no bitmap
-            else:
-                term = LabelTerm(col, negate=negate, none=none, codes=codes)
             out.append(term)
         if sum(t.set_bits for t in out) > MASK_MAX_SET_BITS:  # (one library call must be able to carry the pattern)
             return None
         return NOTHING if nothing else out
 
+    def compile_any(self, expr, max_clauses: int = MASK_MAX_CLAUSES):
+        """the disjunctive normal form of a filter (a pattern dict, AnyOf, AllOf, Not, nested) over the label columns: a list of clauses,
+        each a list of LabelTerm -- a row matches when it matches every term of some clause.  [] means nothing matches, a clause []
+        every row.  None when the filter is not expressible: a key without a column, a value that is not a str, None or a predicate, a
+        normal form over max_clauses clauses (at any stage of the expansion), a clause over max_terms terms, bitmaps over
+        MASK_MAX_SET_BITS.  NOT is pushed to the terms by De Morgan and LabelTerm.complement, which is exact.  A clause that holds a
+        term no row can match is dropped, a term every row matches is left out, equal terms and equal clauses are kept once.  The
+        dictionary never grows."""
+        clauses = self._dnf(expr, False, max_clauses)
+        if clauses is None:
+            return None
+        if sum(t.set_bits for c in clauses for t in c) > MASK_MAX_SET_BITS:  # (one library call must be able to carry the filter)
+            return None
+        return [list(c) for c in clauses]
 
-__all__ = ["LabelCodec", "LabelTerm", "LABEL_COLUMNS", "LABEL_NONE", "MASK_MAX_TERMS", "MASK_MAX_SET_BITS", "NOTHING", "TERM_NEGATE", "TERM_NONE",
-           "In", "NotIn", "Ne", "Exists", "Lt", "Le", "Gt", "Ge", "Between", "matches", "is_predicate", "has_predicates"]
+    def _clauses(self, clauses, max_clauses):
+        """tidies a list of clauses (tuples of terms): see compile_any; None when a limit is passed"""
+        out, seen = [], set()
+        for c in clauses:
+            if any(t.matches_nothing() for t in c):
+                continue
+            c = tuple(dict.fromkeys(t for t in c if not t.matches_everything()))
+            if not c:
+                return [()]  # a clause every row matches: so does the filter
+            if len(c) > self.max_terms:
+                return None
+            if c not in seen:
+                seen.add(c)
+                out.append(c)
+        return out if len(out) <= max_clauses else None
+
+    def _dnf(self, e, negated, max_clauses):
+        if isinstance(e, dict):
+            terms = [self._entry_term(k, p) for k, p in e.items()]
+            if any(t is None for t in terms):
+                return None
+            # a pattern is the AND of its entries; negated, the OR of their complements
+            return self._clauses([(t.complement(),) for t in terms] if negated else [tuple(terms)], max_clauses)
+        if isinstance(e, Not):
+            return self._dnf(e.expr, not negated, max_clauses)
+        if not isinstance(e, (AnyOf, AllOf)):
+            return None
+        parts = []
+        for sub in e.exprs:
+            d = self._dnf(sub, negated, max_clauses)
+            if d is None:
+                return None
+            parts.append(d)
+        if isinstance(e, AnyOf) != negated:  # an OR: the clauses of all operands
+            return self._clauses([c for d in parts for c in d], max_clauses)
+        acc = [()]  # an AND: the products of one clause per operand, operand by operand
+        for d in parts:
+            acc = self._clauses([a + c for a in acc for c in d], max_clauses)
+            if acc is None:
+                return None
+        return acc
+
+
+__all__ = ["LabelCodec", "LabelTerm", "LABEL_COLUMNS", "LABEL_NONE", "MASK_MAX_TERMS", "MASK_MAX_SET_BITS", "MASK_MAX_CLAUSES", "NOTHING", "TERM_NEGATE",
+           "TERM_NONE", "In", "NotIn", "Ne", "Exists", "Lt", "Le", "Gt", "Ge", "Between", "matches", "is_predicate", "has_predicates",
+           "AnyOf", "AllOf", "Not", "matches_filter", "is_expression", "filter_key", "filter_patterns"]

@@ -23,6 +23,10 @@ it, one pass over the metadata; add / delete keep the columns in step), and the 
 A pattern value may be a predicate of labels.py (In, NotIn, Ne, Exists, Lt, Le, Gt, Ge, Between; labels.matches defines them): such a
 pattern is compiled over the columns' dictionaries into set / range terms and its mask is built on the device as well
 (GpuIndex.make_masks_where_sets); patterns of plain values keep their path.
+A filter may also be an EXPRESSION of labels.py -- AnyOf, AllOf and Not over patterns, nested (labels.matches_filter defines them): its
+disjunctive normal form over the label columns (LabelCodec.compile_any) is evaluated on the device in one pass
+(GpuIndex.make_masks_where_any); an expression that has no such form (a 17th key, more than 64 clauses) is assembled from the masks of
+its operands with GpuIndex.combine_masks.  A pattern dict keeps its path; delete takes a pattern only.
 """
 from __future__ import annotations
 
@@ -33,7 +37,7 @@ import numpy as np
 
 from ._lib import VdbError
 from .index import GpuIndex, RowMask, parse_dist
-from .labels import MASK_MAX_SET_BITS, LabelCodec, LabelTerm, has_predicates
+from .labels import MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, filter_key, filter_patterns, has_predicates, is_expression
 from .labels import matches as value_matches
 
 _DIST_STR = {0: "l2sqr", 1: "cosine"}
@@ -88,9 +92,10 @@ class _Table:
         self.metadata: list[dict[str, str]] = []
         self.lock = _RwLock()
         self.seed = 0x1806
-        # row masks of the metadata patterns searched with (search(filter=...)), keyed by frozenset(pattern.items()): filled under
-        # mask_mu by searches (which hold the READ lock, several at a time), closed and cleared by every write under the WRITE lock
-        self.masks: dict[frozenset, RowMask] = {}
+        # row masks of the filters searched with (search(filter=...)), keyed by labels.filter_key -- frozenset(pattern.items()) of a
+        # pattern, an expression as itself: filled under mask_mu by searches (which hold the READ lock, several at a time), closed and
+        # cleared by every write under the WRITE lock
+        self.masks: dict[object, RowMask] = {}
         self.mask_mu = threading.Lock()
         # which metadata keys are label columns of the index, and the value -> code dictionary of each: changed under the WRITE lock only
         self.codec = LabelCodec()
@@ -126,6 +131,7 @@ class _Table:
         readers build masks from the columns and read the codec's dictionaries, so nobody may be reading while one is made.  Two
         threads that first-use a key at once both come here; the second finds the column made.  The check itself only reads the
         codec, which changes under the write lock alone: a stale answer costs a useless turn through the lock, nothing else."""
+        patterns = [p for f in patterns for p in filter_patterns(f)]  # (an expression: its patterns, each as if searched with alone)
         if all(not self.codec.missing(p) or not self.codec.expressible(p) for p in patterns):
             return
         with self.lock.write():
@@ -134,25 +140,83 @@ class _Table:
     def mask_for(self, pattern: dict[str, str]) -> RowMask:
         """the mask of the rows whose metadata holds every key of `pattern` with an equal value (an empty pattern: every row): built on
         the device from the label columns when every key of the pattern has one, else from the host loop"""
-        key = frozenset(pattern.items())
         with self.mask_mu:
-            mk = self.masks.get(key)
-            if mk is None:
-                terms = self.live_terms(pattern)
-                if terms is not None:
-                    mk = self.masks[key] = self.device_mask(pattern, terms)
-                else:
-                    mk = self.masks[key] = self.index.make_mask(self.host_match(pattern))
-            return mk
+            return self.mask_locked(pattern)
+
+    def mask_locked(self, f) -> RowMask:
+        """UNDER mask_mu: the cached mask of a pattern or an expression, made on first use"""
+        key = filter_key(f)
+        mk = self.masks.get(key)
+        if mk is None:
+            if is_expression(f):
+                self.expr_masks([f])
+                return self.masks[key]
+            terms = self.live_terms(f)
+            if terms is not None:
+                mk = self.masks[key] = self.device_mask(f, terms)
+            else:
+                mk = self.masks[key] = self.index.make_mask(self.host_match(f))
+        return mk
+
+    def expr_masks(self, exprs) -> None:
+        """UNDER mask_mu: caches the masks of the expressions not cached yet.  The ones with a normal form over the label columns
+        (LabelCodec.compile_any) are built by ONE make_masks_where_any call (more than one only when their bitmaps together pass the
+        library's MASK_MAX_SET_BITS per call); every other one is assembled from its operands' masks (assemble)."""
+        todo: dict[object, list] = {}
+        rest = []
+        for e in exprs:
+            if e in self.masks or e in todo:
+                continue
+            clauses = self.codec.compile_any(e)
+            if clauses is not None:
+                todo[e] = clauses
+            elif e not in rest:
+                rest.append(e)
+        batch, bits = [], 0
+        for e in list(todo) + [None]:
+            need = 0 if e is None else sum(t.set_bits for c in todo[e] for t in c)
+            if batch and (e is None or bits + need > MASK_MAX_SET_BITS):
+                for be, mk in zip(batch, self.index.make_masks_where_any([todo[be] for be in batch])):
+                    self.masks[be] = mk
+                batch, bits = [], 0
+            if e is not None:
+                batch.append(e)
+                bits += need
+        for e in rest:
+            self.masks[e] = self.assemble(e)
+
+    def assemble(self, e) -> RowMask:
+        """UNDER mask_mu: the mask of an expression the columns cannot express, from the masks of its operands -- each cached under
+        its own key, built on the device where it can be and by the host loop where not -- joined with combine_masks, eight at a
+        time; a Not operand is its operand's mask, complemented inside the join"""
+        if isinstance(e, Not):
+            return self.index.combine_masks("and", [self.mask_locked(e.expr)], [True])
+        op = "or" if isinstance(e, AnyOf) else "and"
+        self.expr_masks([y for y in (x.expr if isinstance(x, Not) else x for x in e.exprs) if is_expression(y)])  # (one call for those the columns express)
+        parts = [(self.mask_locked(x.expr), True) if isinstance(x, Not) else (self.mask_locked(x), False) for x in e.exprs]
+        acc = None  # the join of the operands so far: an intermediate mask of this call, closed once it has been read
+        while parts:
+            take = 8 if acc is None else 7
+            head, parts = parts[:take], parts[take:]
+            if acc is not None:
+                head.insert(0, (acc, False))
+            nxt = self.index.combine_masks(op, [m for m, _ in head], [inv for _, inv in head])
+            if acc is not None:
+                acc.close()
+            acc = nxt
+        return acc
 
     def masks_for(self, patterns) -> list[RowMask]:
         """mask_for for many patterns: the ones not cached yet whose keys all have columns are built by ONE make_masks_where call for
         the patterns of plain values and ONE make_masks_where_sets call for the ones that hold predicates (more than one only when
         their bitmaps together pass the library's MASK_MAX_SET_BITS per call)"""
         with self.mask_mu:
+            self.expr_masks([p for p in patterns if is_expression(p)])  # expressions: one make_masks_where_any call of their own
             todo: dict[frozenset, list] = {}
             todo_sets: dict[frozenset, list] = {}
             for p in patterns:
+                if is_expression(p):
+                    continue
                 key = frozenset(p.items())
                 if key not in self.masks and key not in todo and key not in todo_sets:
                     terms = self.live_terms(p)
@@ -266,6 +330,8 @@ class VecDB:
                 t.index.set_labels(t.codec.column_of(k), t.codec.encode_rows(k, t.metadata[first:]), first_row=first)
 
     def delete(self, key: str, pattern: dict[str, str]) -> int:
+        if not isinstance(pattern, dict):
+            raise TypeError("delete takes a metadata pattern (a dict), not a filter expression")
         t = self._t(key)
         with t.lock.write():
             t.drop_masks()
@@ -375,7 +441,7 @@ class VecDB:
         if q.ndim != 2 or q.shape[1] != ix.dim:
             raise RuntimeError(f"Dimension mismatch: table dim {ix.dim}, got {q.shape}")
         nq = q.shape[0]
-        if filters is not None and not isinstance(filters, dict):
+        if filters is not None and not isinstance(filters, dict) and not is_expression(filters):
             filters = list(filters)
             if len(filters) != nq:
                 raise RuntimeError(f"filters: one pattern per query is needed ({nq}), got {len(filters)}")
@@ -383,14 +449,14 @@ class VecDB:
             return []
         pats = None
         if filters is not None:
-            pats = [filters] * nq if isinstance(filters, dict) else filters
+            pats = [filters] * nq if isinstance(filters, dict) or is_expression(filters) else filters
             t.prepare(pats)
         with t.lock.read():  # one read guard for the whole batch, mask building and metadata lookup included
             if pats is not None:
-                slot: dict[frozenset, int] = {}
+                slot: dict[object, int] = {}
                 distinct, mask_of = [], np.zeros(nq, dtype=np.uint32)
                 for i, p in enumerate(pats):
-                    pk = frozenset(p.items())
+                    pk = filter_key(p)
                     if pk not in slot:
                         slot[pk] = len(distinct)
                         distinct.append(p)
@@ -434,7 +500,7 @@ class VecDB:
         if q.ndim != 2 or q.shape[1] != ix.dim:
             raise RuntimeError(f"Dimension mismatch: table dim {ix.dim}, got {q.shape}")
         nq = q.shape[0]
-        if filters is not None and not isinstance(filters, dict):
+        if filters is not None and not isinstance(filters, dict) and not is_expression(filters):
             filters = list(filters)
             if len(filters) != nq:
                 raise RuntimeError(f"filters: one pattern per query is needed ({nq}), got {len(filters)}")
@@ -445,14 +511,14 @@ class VecDB:
             return []
         pats = None
         if filters is not None:
-            pats = [filters] * nq if isinstance(filters, dict) else filters
+            pats = [filters] * nq if isinstance(filters, dict) or is_expression(filters) else filters
             t.prepare(pats)
         with t.lock.read():  # one read guard for the whole batch, mask building and metadata lookup included
             if pats is not None:
-                slot: dict[frozenset, int] = {}
+                slot: dict[object, int] = {}
                 distinct, mask_of = [], np.zeros(nq, dtype=np.uint32)
                 for i, p in enumerate(pats):
-                    pk = frozenset(p.items())
+                    pk = filter_key(p)
                     if pk not in slot:
                         slot[pk] = len(distinct)
                         distinct.append(p)
