@@ -317,9 +317,36 @@ int vdb_flat_range_filtered_multi_device(vdb_index *idx, const void *d_queries, 
  * check a mask -- a mask of another index: VDB_ERR_INVALID, a stale mask: VDB_ERR_STATE -- and n_in == 0, n_in > 8, a NULL input or
  * an unknown op is VDB_ERR_INVALID; nothing is computed on error and *out is NULL.  Read-side; the result is an ordinary mask.
  * vdb_get_stat "mask_combine_masks" counts them; vdb_prof_get "mask_combine" times k_mask_combine with its scan and ids launches.
+ * ONE COLUMN GROUPED BY CODE (vdb_mask_create_partition, vdb_index_label_counts; csrc/mask_partition.hpp, k_mask_partition,
+ * k_label_counts, docs/DESIGN_flat.md 4.1p): the masks of many values of one column, or the rows per value, from ONE read of the column
+ * per chunk of 1024 codes instead of one read per value.
+ * vdb_mask_create_partition: out[j] = the mask of the rows whose label in `column` equals codes[j] -- bit-identical (words, ascending
+ * allow-list, m) to what vdb_mask_create_where(idx, &column, &codes[j], 1, ...) makes.  VDB_LABEL_NONE is a legal code (the unlabelled
+ * rows; every row of a column never written); a code no row carries gives m = 0; the codes come in any order, arbitrarily sparse, and
+ * the output order follows the input order.  The codes of a call are DISTINCT.  Everything is checked before anything is launched;
+ * VDB_ERR_INVALID with a message, every out[j] NULL, index and counters unchanged for: a code named twice, column >= VDB_LABEL_COLUMNS,
+ * a NULL array with n_codes > 0, n_codes >= 2^28 (`out` is not written then).  n_codes == 0 succeeds.  All-or-nothing on a
+ * device-memory failure.  Read-side and re-entrant.  Each result is an ordinary vdb_mask: owner / staleness rules, lazily built row
+ * constants, f32 and VecSet<u8> indexes, every call that takes a vdb_mask (vdb_mask_combine and vdb_mask_rows included), destroyed on
+ * its own with vdb_mask_destroy, in any order.
+ *   STORAGE: the masks of one chunk share two device allocations, one for their bit words and one for their allow-lists (the codes are
+ *   distinct, so the masks are disjoint and the lists of a chunk hold at most n entries together); every mask holds a reference, and
+ *   ONE SURVIVING MASK KEEPS ITS CHUNK'S TWO ALLOCATIONS ALIVE -- up to 1024 x ceil(n / 64) x 8 B of bit words.  A caller that keeps
+ *   a few masks of a large partition for long should build those with vdb_mask_create_where.  Every mask starts 256-B aligned inside
+ *   its slab, as a buffer of its own would.  (Under VDB_EFENCE every mask keeps allocations of its own.)
+ *   How: the host sorts a chunk's codes; a workgroup stages the sorted table in LDS, a lane loads its row's code once and
+ *   binary-searches it, and the wave walks its distinct codes -- the ballot of "my code is this one" is that mask's word.  The bit
+ *   words and block counts are cleared first; k_mask_scan and k_mask_ids follow as for every other constructor.
+ * vdb_index_label_counts: out_counts[j] = the number of rows allowed by `mask` (NULL: every row) whose label in `column` equals
+ * codes[j]; the same code rules and errors (VDB_LABEL_NONE counts the unlabelled rows).  The mask is checked as the filtered searches
+ * check one: another index is VDB_ERR_INVALID, a stale mask VDB_ERR_STATE; out_counts is not written on error.  Read-side and
+ * re-entrant.  A workgroup keeps a chunk's counters in LDS and flushes the non-zero ones with integer adds; an index has fewer than
+ * 2^32 rows, so no counter overflows.
+ * vdb_get_stat "mask_partition_masks" counts the masks vdb_mask_create_partition built, "label_count_calls" the
+ * vdb_index_label_counts calls (the older counters keep counting only their own calls); vdb_prof_get "mask_partition" times
+ * k_mask_partition with its clears, scan and ids launches, "label_counts" k_label_counts with its clear.
  * Not covered: sharded and replica contexts, normal forms past VDB_MASK_MAX_CLAUSES clauses in one call (combine the parts with
- * vdb_mask_combine), a single-pass partition of one column into the masks of all its values, labels in bincode files, filtered k-NN on
- * VecSet<u8> indexes. */
+ * vdb_mask_combine), partitions by more than one column, labels in bincode files, filtered k-NN on VecSet<u8> indexes. */
 #define VDB_LABEL_COLUMNS 16
 #define VDB_LABEL_NONE 0xFFFFFFFFu
 #define VDB_MASK_MAX_TERMS 8
@@ -346,6 +373,9 @@ int vdb_mask_create_where_any_many(vdb_index *idx, const uint64_t *mask_lims, co
 #define VDB_MASK_OP_AND 0
 #define VDB_MASK_OP_OR 1
 int vdb_mask_combine(vdb_index *idx, int op, const vdb_mask *const *in, const uint8_t *invert, uint64_t n_in, vdb_mask **out);
+int vdb_mask_create_partition(vdb_index *idx, uint32_t column, const uint32_t *codes, uint64_t n_codes, vdb_mask **out);
+int vdb_index_label_counts(vdb_index *idx, uint32_t column, const vdb_mask *mask, const uint32_t *codes, uint64_t n_codes,
+                           uint64_t *out_counts);
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids);
 /* the approximate keys the Flat shortlist pass compares with its threshold, for EVERY row, from the same kernel in its dense
  * mode (test / measurement entry point behind the certification-bound tests): out_keys [nq][len];
@@ -446,7 +476,8 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *   "mask_where_masks"   masks built on the device from the label columns (vdb_mask_create_where*); "mask_where_set_masks": the ones
  *                        built from set / range terms (vdb_mask_create_where_sets*); "mask_where_any_masks": the ones built from an OR of
  *                        conjunctions (vdb_mask_create_where_any*); "mask_combine_masks": the ones vdb_mask_combine made;
- *                        "label_columns": allocated columns,
+ *                        "mask_partition_masks": the ones vdb_mask_create_partition made; "label_count_calls":
+ *                        vdb_index_label_counts calls; "label_columns": allocated columns,
  *   "hbm_bytes_per_row"  resident HBM bytes per row over all per-row buffers (rows, norms, mirrors, PQ codes, level-0 links, label
  *                        columns). */
 int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out);

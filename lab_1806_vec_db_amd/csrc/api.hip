@@ -734,6 +734,31 @@ int vdb_mask_combine(vdb_index *idx, int op, const vdb_mask *const *in, const ui
     *out = mk.release();
     VDB_API_END
 }
+// one column grouped by code in a single read of it (Index::masks_partition / Index::label_counts, mask_partition.hpp)
+int vdb_mask_create_partition(vdb_index *idx, uint32_t column, const uint32_t *codes, uint64_t n_codes, vdb_mask **out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    VDB_REQUIRE(n_codes < (1ull << 28), "too many codes for one call");  // (before `out` is written: it has room for n_codes handles)
+    VDB_REQUIRE(n_codes == 0 || out, "null argument");
+    for (uint64_t g = 0; g < n_codes; g++) out[g] = nullptr;
+    const std::string bad = mask_partition_check(column, codes, n_codes);  // (before a mask object is made)
+    VDB_REQUIRE(bad.empty(), bad);
+    std::vector<std::unique_ptr<vdb_mask>> made(n_codes);
+    std::vector<RowMask *> rm(n_codes);
+    for (uint64_t g = 0; g < n_codes; g++) {
+        made[g].reset(new vdb_mask);
+        rm[g] = &made[g]->m;
+    }
+    idx->ix.masks_partition(column, codes, n_codes, rm.data());  // a throw destroys every mask with `made`, and with the last its slabs
+    for (uint64_t g = 0; g < n_codes; g++) out[g] = made[g].release();
+    VDB_API_END
+}
+int vdb_index_label_counts(vdb_index *idx, uint32_t column, const vdb_mask *mask, const uint32_t *codes, uint64_t n_codes, uint64_t *out_counts) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    idx->ix.label_counts(column, mask ? &mask->m : nullptr, codes, n_codes, out_counts);
+    VDB_API_END
+}
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids) {
     VDB_API_BEGIN
     VDB_REQUIRE(m, "null mask");
@@ -1265,6 +1290,10 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.mask_where_any_masks.load();
     else if (n == "mask_combine_masks")  // masks built by vdb_mask_combine
         *out = idx->ix.mask_combine_masks.load();
+    else if (n == "mask_partition_masks")  // masks built by vdb_mask_create_partition
+        *out = idx->ix.mask_partition_masks.load();
+    else if (n == "label_count_calls")  // vdb_index_label_counts calls
+        *out = idx->ix.label_count_calls.load();
     else if (n == "label_columns")  // allocated label columns (4 B per row each)
         *out = idx->ix.label_columns();
     else if (n == "hbm_bytes_per_row")

@@ -361,8 +361,10 @@ void Index::masks_where_sets(const uint64_t *term_lims, const uint32_t *columns,
 // Per chunk of masks: that kernel + k_mask_scan, ONE read-back of the totals (the only synchronisation before the allow-lists can be
 // allocated), k_mask_ids, synchronise.  The chunk bounds grid.y and the block-count scratch (at most 1024 masks and 64 MiB of counts).
 void Index::masks_finish(Workspace &ws, const uint64_t *lims, uint64_t n_masks, RowMask *const *out, const char *prof,
-                         const std::function<double(uint64_t, uint64_t)> &bytes, const std::function<void(uint64_t, uint64_t)> &launch) {
+                         const std::function<double(uint64_t, uint64_t)> &bytes, const std::function<void(uint64_t, uint64_t)> &launch,
+                         bool slabs) {
     hipStream_t s = ws.stream;
+    slabs = slabs && !devbuf_efence();  // (a mask's own end stays fenced: per-mask allocations)
     const uint64_t nw = (n + 63) / 64;
     const uint32_t nblocks = mask_where_blocks(n);
     const uint64_t gen = write_gen.load();
@@ -375,8 +377,15 @@ void Index::masks_finish(Workspace &ws, const uint64_t *lims, uint64_t n_masks, 
         ws.flags.reserve(chunk * nblocks * sizeof(uint32_t));
         ws.misc.reserve(chunk * sizeof(uint32_t));
     }
+    const size_t bits_bytes = std::max<uint64_t>(nw, 1) * sizeof(uint64_t), bits_step = devbuf_align_up(bits_bytes);
     for (uint64_t g0 = 0; g0 < n_masks; g0 += chunk) {
         const uint64_t nb = std::min(chunk, n_masks - g0);
+        std::shared_ptr<DevBuf> slab_bits, slab_ids;
+        if (slabs) {  // ONE allocation for the chunk's bit words, every mask a view at a multiple of bits_step
+            slab_bits = std::make_shared<DevBuf>();
+            slab_bits->reserve(nb * bits_step);
+            slab_ids = std::make_shared<DevBuf>();
+        }
         for (uint64_t j = 0; j < nb; j++) {
             RowMask &m = *out[g0 + j];
             m.owner = this;
@@ -384,11 +393,25 @@ void Index::masks_finish(Workspace &ws, const uint64_t *lims, uint64_t n_masks, 
             m.gen = gen;
             m.n_rows = n;
             m.m = 0;
-            m.d_bits.reserve(std::max<uint64_t>(nw, 1) * sizeof(uint64_t));
+            if (slabs) {
+                m.slab_bits = slab_bits;
+                m.d_bits.view(slab_bits->as<char>() + j * bits_step, bits_step);
+            } else {
+                m.d_bits.reserve(bits_bytes);
+            }
             h_jobs[j] = {m.d_bits.as<uint64_t>(), lims ? (uint32_t)lims[g0 + j] : 0u, lims ? (uint32_t)lims[g0 + j + 1] : 0u};
         }
         if (!nblocks) {  // an empty index: masks with m = 0
-            for (uint64_t j = 0; j < nb; j++) out[g0 + j]->d_ids.reserve(sizeof(uint32_t));
+            if (slabs) slab_ids->reserve(nb * DEVBUF_ALIGN);
+            for (uint64_t j = 0; j < nb; j++) {
+                RowMask &m = *out[g0 + j];
+                if (slabs) {
+                    m.slab_ids = slab_ids;
+                    m.d_ids.view(slab_ids->as<char>() + j * DEVBUF_ALIGN, DEVBUF_ALIGN);
+                } else {
+                    m.d_ids.reserve(sizeof(uint32_t));
+                }
+            }
             continue;
         }
         uint32_t *h_tot = static_cast<uint32_t *>(ws.pinned(chunk * sizeof(uint32_t)));
@@ -399,11 +422,24 @@ void Index::masks_finish(Workspace &ws, const uint64_t *lims, uint64_t n_masks, 
         VDB_HIP(hipMemcpyAsync(h_tot, ws.misc.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         VDB_SYNC(s);
         uint64_t sum_m = 0;
+        if (slabs) {  // ONE allocation for the chunk's allow-lists: the lists back to back, each start rounded up to DEVBUF_ALIGN
+            size_t total = 0;
+            for (uint64_t j = 0; j < nb; j++) total += devbuf_align_up(std::max<uint64_t>(h_tot[j], 1) * sizeof(uint32_t));
+            slab_ids->reserve(total);
+        }
+        size_t ids_at = 0;
         for (uint64_t j = 0; j < nb; j++) {
             RowMask &m = *out[g0 + j];
             m.m = h_tot[j];
             sum_m += m.m;
-            m.d_ids.reserve(std::max<uint64_t>(m.m, 1) * sizeof(uint32_t));
+            if (slabs) {
+                const size_t step = devbuf_align_up(std::max<uint64_t>(m.m, 1) * sizeof(uint32_t));
+                m.slab_ids = slab_ids;
+                m.d_ids.view(slab_ids->as<char>() + ids_at, step);
+                ids_at += step;
+            } else {
+                m.d_ids.reserve(std::max<uint64_t>(m.m, 1) * sizeof(uint32_t));
+            }
             h_ids[j] = m.d_ids.as<uint32_t>();
         }
         VDB_HIP(hipMemcpyAsync(ws.keys_c.p, h_ids.data(), nb * sizeof(uint32_t *), hipMemcpyHostToDevice, s));
@@ -476,6 +512,76 @@ void Index::mask_combine(int op, const RowMask *const *in, const uint8_t *invert
         *ws, nullptr, 1, &outp, "mask_combine", [&](uint64_t, uint64_t) { return double(n_in) * double((n + 63) / 64) * sizeof(uint64_t); },
         [&](uint64_t, uint64_t) { launch_mask_combine(a, out.d_bits.as<uint64_t>(), n, ws->flags.as<uint32_t>(), ws->misc.as<uint32_t>(), ws->stream); });
     mask_combine_masks += 1;
+}
+
+// ONE column grouped by code (mask_partition.hpp checks the codes and lays out a chunk's table; k_mask_partition reads the column once
+// per chunk).  masks_finish cuts the call into chunks and places every chunk's masks in two slabs; per chunk the launch clears the bit
+// words and the block counts, uploads the chunk's table and runs the kernel -- all of it inside the profile entry.
+void Index::masks_partition(uint32_t column, const uint32_t *codes, uint64_t n_codes, RowMask *const *out) {
+    const std::string bad = mask_partition_check(column, codes, n_codes);
+    VDB_REQUIRE(bad.empty(), bad);
+    VDB_REQUIRE(n_codes == 0 || out, "null argument");
+    if (n_codes == 0) return;
+    use_device();
+    WsLease ws(*this);
+    hipStream_t s = ws->stream;
+    const uint32_t *col = label_live[column] ? d_labels[column].as<uint32_t>() : nullptr;
+    const uint32_t nblocks = mask_where_blocks(n);
+    const size_t bits_bytes = std::max<uint64_t>((n + 63) / 64, 1) * sizeof(uint64_t);
+    std::vector<uint32_t> h_sorted, h_slot, h_table;  // (alive until masks_finish has synchronised the chunk that reads them)
+    if (n) ws->keys_a.reserve(2 * size_t(PART_MAX_CHUNK) * sizeof(uint32_t));
+    masks_finish(
+        *ws, nullptr, n_codes, out, "mask_partition", [&](uint64_t, uint64_t nb) { return double(n) * sizeof(uint32_t) + double(nb) * double(nblocks) * sizeof(uint32_t); },
+        [&](uint64_t g0, uint64_t nb) {
+            if (out[g0]->slab_bits) {  // the chunk's masks are one slab: one clear
+                VDB_HIP(hipMemsetAsync(out[g0]->slab_bits->p, 0, nb * out[g0]->d_bits.cap, s));
+            } else {
+                for (uint64_t j = 0; j < nb; j++) VDB_HIP(hipMemsetAsync(out[g0 + j]->d_bits.p, 0, bits_bytes, s));
+            }
+            VDB_HIP(hipMemsetAsync(ws->flags.p, 0, nb * size_t(nblocks) * sizeof(uint32_t), s));
+            mask_partition_layout(codes + g0, (uint32_t)nb, h_sorted, h_slot);
+            h_table.assign(h_sorted.begin(), h_sorted.end());
+            h_table.insert(h_table.end(), h_slot.begin(), h_slot.end());
+            VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_table.data(), h_table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            launch_mask_partition(col, ws->keys_a.as<uint32_t>(), (uint32_t)nb, ws->keys_b.as<MaskJob>(), n, ws->flags.as<uint32_t>(), ws->misc.as<uint32_t>(), s);
+        },
+        true);
+    mask_partition_masks += n_codes;
+}
+
+// Rows per code of one column, over all rows or under a mask (k_label_counts): per chunk of PART_MAX_CHUNK codes one launch over the
+// column, the counters read back in the table's order and handed out in the caller's.
+void Index::label_counts(uint32_t column, const RowMask *mask, const uint32_t *codes, uint64_t n_codes, uint64_t *out_counts) {
+    const std::string bad = mask_partition_check(column, codes, n_codes);
+    VDB_REQUIRE(bad.empty(), bad);
+    VDB_REQUIRE(n_codes == 0 || out_counts, "null argument");
+    if (mask) check_mask(*mask);
+    label_count_calls += 1;
+    if (n_codes == 0) return;
+    std::fill(out_counts, out_counts + n_codes, uint64_t(0));
+    if (n == 0) return;
+    use_device();
+    WsLease ws(*this);
+    hipStream_t s = ws->stream;
+    const uint32_t *col = label_live[column] ? d_labels[column].as<uint32_t>() : nullptr;
+    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
+    std::vector<uint32_t> h_sorted, h_slot;
+    ws->keys_a.reserve(size_t(PART_MAX_CHUNK) * sizeof(uint32_t));
+    ws->misc.reserve(size_t(PART_MAX_CHUNK) * sizeof(uint32_t));
+    uint32_t *h_cnt = static_cast<uint32_t *>(ws->pinned(size_t(PART_MAX_CHUNK) * sizeof(uint32_t)));
+    for (uint64_t g0 = 0; g0 < n_codes; g0 += PART_MAX_CHUNK) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(PART_MAX_CHUNK, n_codes - g0);
+        mask_partition_layout(codes + g0, nb, h_sorted, h_slot);
+        VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_sorted.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        prof_begin(*ws, "label_counts", double(n) * sizeof(uint32_t) + (bits ? double((n + 63) / 64) * sizeof(uint64_t) : 0.0));
+        VDB_HIP(hipMemsetAsync(ws->misc.p, 0, nb * sizeof(uint32_t), s));
+        launch_label_counts(col, ws->keys_a.as<uint32_t>(), nb, bits, n, ws->misc.as<uint32_t>(), num_cu, s);
+        prof_end(*ws);
+        VDB_HIP(hipMemcpyAsync(h_cnt, ws->misc.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        VDB_SYNC(s);
+        prof_collect(*ws);
+        for (uint32_t i = 0; i < nb; i++) out_counts[g0 + h_slot[i]] = h_cnt[i];
+    }
 }
 
 // ---- images of the rows (RowMirror): a tier whose image is missing leaves its queries to the next one (8-bit -> fp16 -> split-bf16 ->

@@ -100,9 +100,19 @@ struct DevBuf {
         src.p = src.base = nullptr;
         src.cap = 0;
     }
+    // becomes a view of `bytes` bytes at `at` inside somebody else's allocation: base stays null, so release() frees nothing (what this
+    // buffer held is released first); the owner of that allocation must outlive the view
+    void view(void *at, size_t bytes) {
+        release();
+        p = at;
+        cap = bytes;
+    }
     template <class T>
     T *as() const { return reinterpret_cast<T *>(p); }
 };
+// every view into a slab starts at a multiple of this: how hipMalloc aligns whole buffers
+constexpr size_t DEVBUF_ALIGN = 256;
+inline size_t devbuf_align_up(size_t bytes) { return (bytes + DEVBUF_ALIGN - 1) / DEVBUF_ALIGN * DEVBUF_ALIGN; }
 
 struct ProfEntry {
     double ms = 0;
@@ -289,6 +299,10 @@ struct RowMask {
     uint64_t m = 0;       // allowed rows
     DevBuf d_bits;        // u64 [ceil(n_rows / 64)], bits at and past n_rows clear
     DevBuf d_ids;         // u32 [m], ascending
+    // A mask of Index::masks_partition: d_bits / d_ids are VIEWS (base == nullptr: release() frees nothing) into two allocations that
+    // the masks of one chunk of the call share; every mask holds a reference and the last one destroyed frees them.  Empty for every
+    // other constructor.
+    std::shared_ptr<DevBuf> slab_bits, slab_ids;
     mutable std::mutex mu;
     mutable DevBuf d_rowc;  // float2 [padded rows]: Index::d_rowc_i8 with {+inf, 0} for every disallowed row
     mutable const void *rowc_of = nullptr;  // the d_rowc_i8 allocation it was copied from (nullptr: not built)
@@ -565,12 +579,24 @@ struct Index {
     // synchronised; on a throw the caller discards `out`.
     void mask_combine(int op, const RowMask *const *in, const uint8_t *invert, uint64_t n_in, RowMask &out);
     std::atomic<uint64_t> mask_combine_masks{0};  // masks built by mask_combine
-    // The second half of all four: given the bit-word kernel as `launch(g0, nb)` (it enqueues the kernel and k_mask_scan for masks
+    // ONE column grouped by code in a single read of it (mask_partition.hpp, k_mask_partition): out[j] = the mask of the rows whose
+    // label in `column` equals codes[j], bit-identical to masks_where's mask of that one term; the codes are distinct.  The masks of a
+    // chunk share two allocations (RowMask::slab_bits / slab_ids) unless VDB_EFENCE.  Same contract as masks_where.
+    void masks_partition(uint32_t column, const uint32_t *codes, uint64_t n_codes, RowMask *const *out);
+    std::atomic<uint64_t> mask_partition_masks{0};  // masks built by masks_partition
+    // out_counts[j] = the rows allowed by `mask` (nullptr: every row) whose label in `column` equals codes[j] (k_label_counts); the same
+    // code rules; the mask is checked with check_mask before anything is computed; read-side; returns synchronised.
+    void label_counts(uint32_t column, const RowMask *mask, const uint32_t *codes, uint64_t n_codes, uint64_t *out_counts);
+    std::atomic<uint64_t> label_count_calls{0};  // label_counts calls
+    // The second half of all five: given the bit-word kernel as `launch(g0, nb)` (it enqueues the kernel and k_mask_scan for masks
     // [g0, g0 + nb) of the call, whose jobs are in ws.keys_b, block counts in ws.flags, totals in ws.misc; the caller's tables are in
     // ws.keys_a), runs the chunk loop -- headers and jobs, launch, ONE read-back of the totals, allow-lists, k_mask_ids.
     // lims[g] .. lims[g + 1] = the range a job carries (nullptr: none); bytes(g0, nb) = what the launch reads, for the profile entry `prof`.
     void masks_finish(Workspace &ws, const uint64_t *lims, uint64_t n_masks, RowMask *const *out, const char *prof,
-                      const std::function<double(uint64_t, uint64_t)> &bytes, const std::function<void(uint64_t, uint64_t)> &launch);
+                      const std::function<double(uint64_t, uint64_t)> &bytes, const std::function<void(uint64_t, uint64_t)> &launch,
+                      bool slabs = false);
+    // (slabs: the bit words of a chunk's masks are views into ONE allocation, zeroed, and their allow-lists views into another, every
+    // view DEVBUF_ALIGN-aligned -- masks_partition's; false: an allocation per mask and list, as every other caller has it.)
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};

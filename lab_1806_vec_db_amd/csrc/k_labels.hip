@@ -2,7 +2,9 @@
 // (Index::masks_where): upkeep of the columns under add / swap_remove / remove_rows, and the three kernels that turn a conjunction of
 // `column == code` terms into a RowMask's bit words and its ascending allow-list (docs/DESIGN_flat.md 4.1l), and the kernel that does the
 // same for set / range terms (Index::masks_where_sets, mask_sets.hpp; 4.1m), for an OR of such conjunctions (Index::masks_where_any,
-// mask_any.hpp; 4.1o) and for the AND / OR / NOT of finished masks (Index::mask_combine; 4.1o).
+// mask_any.hpp; 4.1o) and for the AND / OR / NOT of finished masks (Index::mask_combine; 4.1o); and the two kernels that group ONE column
+// by code in a single read of it -- into the masks of many values (Index::masks_partition) or into rows per value (Index::label_counts;
+// mask_partition.hpp; 4.1p).
 #include <algorithm>
 
 #include "kernels.hpp"
@@ -246,6 +248,88 @@ void launch_mask_ids(const MaskJob *jobs, uint32_t *const *ids, uint32_t n_masks
     const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
     if (n_masks == 0 || nblocks == 0) return;
     hipLaunchKernelGGL(k_mask_ids, dim3(nblocks, n_masks), dim3(256), 0, s, jobs, ids, nwords, nblocks, blockoff);
+}
+
+// ---- one column grouped by code (mask_partition.hpp; docs/DESIGN_flat.md 4.1p) -----------------------------------------------------------
+// The masks of up to PART_MAX_CHUNK DISTINCT codes of ONE column in one read of it: the grid over words of k_mask_where with grid.y == 1.
+// The workgroup stages the chunk's table -- the codes ascending, and for each the mask (slot) it belongs to -- in LDS; a lane loads its
+// row's code once and binary-searches it (mask_partition_find), which gives it one slot or none.  The wave then walks its distinct
+// slots: the slot of the first pending lane (uniform), the ballot of "my slot is that one" IS that mask's word, lane 0 stores it and adds
+// its popcount to blockcnt[slot][block], and those lanes retire -- at most 64 rounds, usually as many as the wave has distinct codes.
+// The bit words and the counts are zero before the launch (launch_mask_partition clears them), so every word no wave writes is already
+// right; rows at and past n have no slot, so the tail bits stay clear; a null column is LABEL_NONE in every row without a load.  The
+// four waves of a block may add to one count: integer adds, the sum does not depend on their order.  blockcnt then holds what
+// k_mask_where leaves there, so k_mask_scan and k_mask_ids follow unchanged.
+__global__ __launch_bounds__(256) void k_mask_partition(const uint32_t *__restrict__ col, const uint32_t *__restrict__ table, uint32_t nb,
+                                                        const MaskJob *__restrict__ jobs, uint64_t n, uint32_t nwords, uint32_t nblocks,
+                                                        uint32_t *__restrict__ blockcnt) {
+    __shared__ uint32_t s_code[PART_MAX_CHUNK], s_slot[PART_MAX_CHUNK];
+    for (uint32_t i = threadIdx.x; i < nb; i += 256) {
+        s_code[i] = table[i];
+        s_slot[i] = table[nb + i];
+    }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t word = blockIdx.x * 4 + wave;
+    const uint64_t row = uint64_t(word) * 64 + lane;
+    const bool in = row < n;
+    const uint32_t v = (col && in) ? col[row] : LABEL_NONE;
+    const uint32_t pos = mask_partition_find(s_code, nb, v);
+    uint32_t slot = (in && pos != PART_NO_SLOT) ? s_slot[pos] : PART_NO_SLOT;  // (a lane in range makes word < nwords)
+    uint64_t pending = __ballot(slot != PART_NO_SLOT);
+    while (pending) {  // (wave-uniform)
+        const uint32_t cur = (uint32_t)__shfl((int)slot, __ffsll((unsigned long long)pending) - 1);
+        const uint64_t w = __ballot(slot == cur);
+        if (lane == 0) {
+            jobs[cur].bits[word] = w;
+            atomicAdd(&blockcnt[size_t(cur) * nblocks + blockIdx.x], (uint32_t)__popcll(w));
+        }
+        pending &= ~w;
+    }
+}
+
+// The number of rows per code of the same table, over all rows or under a mask: counts[i] += rows whose code is table[i].  A workgroup
+// keeps the chunk's counters in LDS and walks the words grid-strided, a wave per word as above; under a mask the wave reads its 8-byte
+// mask word and lanes with a clear bit sit out.  At the end the non-zero counters are flushed with global integer adds (counts is zero
+// before the launch).  An index has fewer than 2^32 rows: no counter overflows.
+__global__ __launch_bounds__(256) void k_label_counts(const uint32_t *__restrict__ col, const uint32_t *__restrict__ table, uint32_t nb,
+                                                      const uint64_t *__restrict__ bits, uint64_t n, uint32_t nwords,
+                                                      uint32_t *__restrict__ counts) {
+    __shared__ uint32_t s_code[PART_MAX_CHUNK], s_cnt[PART_MAX_CHUNK];
+    for (uint32_t i = threadIdx.x; i < nb; i += 256) {
+        s_code[i] = table[i];
+        s_cnt[i] = 0;
+    }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t word = blockIdx.x * 4 + wave; word < nwords; word += gridDim.x * 4) {  // (wave-uniform)
+        const uint64_t row = uint64_t(word) * 64 + lane;
+        const uint64_t mw = bits ? bits[word] : ~0ull;
+        const bool in = row < n && ((mw >> lane) & 1);
+        const uint32_t v = (col && in) ? col[row] : LABEL_NONE;
+        const uint32_t pos = mask_partition_find(s_code, nb, v);
+        if (in && pos != PART_NO_SLOT) atomicAdd(&s_cnt[pos], 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < nb; i += 256) {
+        const uint32_t c = s_cnt[i];
+        if (c) atomicAdd(&counts[i], c);
+    }
+}
+
+void launch_mask_partition(const uint32_t *col, const uint32_t *table, uint32_t nb, const MaskJob *jobs, uint64_t n, uint32_t *blockcnt,
+                           uint32_t *totals, hipStream_t s) {
+    const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
+    if (nb == 0 || nblocks == 0) return;
+    hipLaunchKernelGGL(k_mask_partition, dim3(nblocks), dim3(256), 0, s, col, table, nb, jobs, n, nwords, nblocks, blockcnt);
+    hipLaunchKernelGGL(k_mask_scan, dim3(nb), dim3(256), 0, s, blockcnt, nblocks, totals);
+}
+void launch_label_counts(const uint32_t *col, const uint32_t *table, uint32_t nb, const uint64_t *bits, uint64_t n, uint32_t *counts,
+                         int num_cu, hipStream_t s) {
+    const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
+    if (nb == 0 || nblocks == 0) return;
+    const unsigned grid = (unsigned)std::min<uint64_t>(nblocks, uint64_t(num_cu) * 8);
+    hipLaunchKernelGGL(k_label_counts, dim3(grid), dim3(256), 0, s, col, table, nb, bits, n, nwords, counts);
 }
 
 }  // namespace vdb

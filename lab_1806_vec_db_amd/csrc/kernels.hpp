@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "mask_any.hpp"
+#include "mask_partition.hpp"
 #include "mask_sets.hpp"
 
 namespace vdb {
@@ -383,6 +384,17 @@ struct MaskCombine {  // (kernel argument, by value)
 void launch_mask_combine(const MaskCombine &a, uint64_t *out, uint64_t n, uint32_t *blockcnt, uint32_t *totals, hipStream_t s);
 // ids[g][0 .. totals[g]) = the allowed rows of mask g, ascending (k_mask_ids; after launch_mask_where on the same stream)
 void launch_mask_ids(const MaskJob *jobs, uint32_t *const *ids, uint32_t n_masks, uint64_t n, const uint32_t *blockoff, hipStream_t s);
+// One column grouped by code (mask_partition.hpp; k_mask_partition, k_label_counts).  table = the chunk's nb (<= PART_MAX_CHUNK) distinct
+// codes ascending, then for each the mask (index into jobs) it belongs to: 2 nb u32 on the device.
+static_assert(PART_LABEL_COLUMNS == LABEL_COLUMNS && PART_LABEL_NONE == LABEL_NONE, "mask_partition.hpp and kernels.hpp agree");
+// The bit words of the nb masks "col == code" and blockcnt / totals as launch_mask_where leaves them (k_mask_partition + k_mask_scan).
+// The caller has zeroed the bit words of every mask and blockcnt [nb][mask_where_blocks(n)] on the same stream; col == nullptr: a
+// column never written.
+void launch_mask_partition(const uint32_t *col, const uint32_t *table, uint32_t nb, const MaskJob *jobs, uint64_t n, uint32_t *blockcnt,
+                           uint32_t *totals, hipStream_t s);
+// counts[i] += the rows allowed by bits (nullptr: every row) whose code is table[i]; the caller has zeroed counts [nb] on the same stream
+void launch_label_counts(const uint32_t *col, const uint32_t *table, uint32_t nb, const uint64_t *bits, uint64_t n, uint32_t *counts,
+                         int num_cu, hipStream_t s);
 void mfma_set_sample_thin(int v);
 void mfma_sample_plan(uint64_t n, uint32_t kprime, uint32_t *step, uint32_t *rank, uint32_t target_floor = 1024);  // target_floor: expected hits per query
 uint64_t mfma_sample_rows(uint64_t n, uint32_t step);

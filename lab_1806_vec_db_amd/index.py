@@ -116,15 +116,16 @@ class RowMask:
         self._n = int(n)
 
     @classmethod
-    def from_handle(cls, index: "GpuIndex", handle) -> "RowMask":
-        """wraps a vdb_mask the library made (vdb_mask_create_where*); the object owns the handle from here on"""
+    def from_handle(cls, index: "GpuIndex", handle, n: int | None = None) -> "RowMask":
+        """wraps a vdb_mask the library made (vdb_mask_create_where*); the object owns the handle from here on.  `n`: the rows of the
+        index, when the caller has them already"""
         self = cls.__new__(cls)
         self._lib = index._lib
         self._h = handle if isinstance(handle, L.vp) else L.vp(handle)
         v = C.c_uint64()
         L.check(self._lib.vdb_mask_count(self._h, C.byref(v)))
         self._m = int(v.value)
-        self._n = len(index)
+        self._n = len(index) if n is None else int(n)
         return self
 
     def rows(self):
@@ -355,6 +356,35 @@ class GpuIndex:
         arr = (L.vp * max(len(lists), 1))()
         L.check(self._lib.vdb_mask_create_where_many(self._h, _ptr(lims, L.u64p), _ptr(cols, L.u32p), _ptr(codes, L.u32p), len(lists), arr))
         return [RowMask.from_handle(self, arr[g]) for g in range(len(lists))]
+
+    @staticmethod
+    def _codes_array(codes) -> np.ndarray:
+        """the u32 array of a sequence of label codes (make_masks_partition, label_counts)"""
+        c = [int(v) for v in codes]
+        for v in c:
+            if not 0 <= v < 2 ** 32:
+                raise ValueError(f"label code {v}: a code is u32")
+        return np.array(c, dtype=np.uint32)
+
+    def make_masks_partition(self, column: int, codes) -> list[RowMask]:
+        """one mask per entry of `codes`: the rows whose label in `column` equals it -- what make_masks_where([[(column, c)] for c in
+        codes]) returns, bit for bit, from ONE read of the column per 1024 codes (vdb_mask_create_partition).  The codes are distinct,
+        in any order, LABEL_NONE (the unlabelled rows) among them; a duplicate raises and no mask is made.  The masks of a call share
+        their device memory by chunks of 1024: it is returned when the last mask of a chunk is closed."""
+        c = self._codes_array(codes)
+        arr = (L.vp * max(c.shape[0], 1))()
+        L.check(self._lib.vdb_mask_create_partition(self._h, int(column), _ptr(c, L.u32p), c.shape[0], arr))
+        n = len(self)
+        return [RowMask.from_handle(self, arr[g], n) for g in range(c.shape[0])]
+
+    def label_counts(self, column: int, codes, mask: RowMask | None = None) -> np.ndarray:
+        """counts[j] = the number of rows -- of the rows `mask` allows, when one is given -- whose label in `column` equals codes[j], as
+        uint64 (vdb_index_label_counts); the same rules for the codes; LABEL_NONE counts the unlabelled rows"""
+        c = self._codes_array(codes)
+        out = np.zeros(c.shape[0], dtype=np.uint64)
+        L.check(self._lib.vdb_index_label_counts(self._h, int(column), None if mask is None else mask._h, _ptr(c, L.u32p), c.shape[0],
+                                                 _ptr(out, L.u64p)))
+        return out
 
     def make_mask_where_sets(self, terms) -> RowMask:
         """the mask of the rows that match EVERY LabelTerm of `terms` -- set and range predicates over the label columns, built on the

@@ -433,6 +433,16 @@ class LabelCodec:
             out[i] = c
         return out
 
+    def value_codes(self, key):
+        """(values, codes) of the key's dictionary, entry for entry -- what decodes a count per code (GpuIndex.label_counts) into a count
+        per value -- or None when the key has no column, or when its dictionary holds the stand-in for values it could not hold (a
+        count under that code is a count of several different values: the host has to look at the rows)"""
+        col = self.columns.get(key)
+        if col is None or _UNHASHABLE in self.codes[col]:
+            return None
+        table = self.codes[col]
+        return list(table), list(table.values())
+
     def terms(self, pattern):
         """the (column, code) terms of a pattern whose keys all have columns: a list (empty for the empty pattern), NOTHING when a value
         was never seen in its column (the dictionary does not grow), None when the pattern is not expressible or a key has no column"""

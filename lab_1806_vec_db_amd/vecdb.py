@@ -27,9 +27,12 @@ A filter may also be an EXPRESSION of labels.py -- AnyOf, AllOf and Not over pat
 disjunctive normal form over the label columns (LabelCodec.compile_any) is evaluated on the device in one pass
 (GpuIndex.make_masks_where_any); an expression that has no such form (a 17th key, more than 64 clauses) is assembled from the masks of
 its operands with GpuIndex.combine_masks.  A pattern dict keeps its path; delete takes a pattern only.
+count(key, filter) is the number of matching rows (the mask's count); count_by(key, field, filter) the matching rows per value of a
+metadata key, from one pass over the key's label column on the device (GpuIndex.label_counts).
 """
 from __future__ import annotations
 
+import collections
 import threading
 from contextlib import contextmanager
 
@@ -37,10 +40,17 @@ import numpy as np
 
 from ._lib import VdbError
 from .index import GpuIndex, RowMask, parse_dist
-from .labels import MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, filter_key, filter_patterns, has_predicates, is_expression
+from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, filter_key, filter_patterns, has_predicates, is_expression
 from .labels import matches as value_matches
 
 _DIST_STR = {0: "l2sqr", 1: "cosine"}
+
+# _Table.masks_for: the smallest group of uncached one-key patterns on one column that is built by GpuIndex.make_masks_partition instead
+# of make_masks_where; None: never.  The masks are the same either way.  The value is the smallest group size of the sweep of
+# tools/bench_mask_partition.py (profiles/mask_partition_1M.json) FROM WHICH ON the partition call was the faster of the two: it also won
+# at 2 .. 16 codes, by microseconds, and lost at 32, and batches of up to 50 patterns keep the one make_masks_where call they are
+# tested to make (docs/DESIGN_flat.md 4.1p has the sweep and the decision).
+PARTITION_MIN: int | None = 64
 
 
 class _RwLock:
@@ -209,7 +219,9 @@ class _Table:
     def masks_for(self, patterns) -> list[RowMask]:
         """mask_for for many patterns: the ones not cached yet whose keys all have columns are built by ONE make_masks_where call for
         the patterns of plain values and ONE make_masks_where_sets call for the ones that hold predicates (more than one only when
-        their bitmaps together pass the library's MASK_MAX_SET_BITS per call)"""
+        their bitmaps together pass the library's MASK_MAX_SET_BITS per call).  Among the plain ones, those of exactly one (column,
+        code) term are grouped by column first, and a group of at least PARTITION_MIN goes to ONE make_masks_partition call: the
+        same masks from one read of the column."""
         with self.mask_mu:
             self.expr_masks([p for p in patterns if is_expression(p)])  # expressions: one make_masks_where_any call of their own
             todo: dict[frozenset, list] = {}
@@ -222,6 +234,16 @@ class _Table:
                     terms = self.live_terms(p)
                     if terms is not None:
                         (todo_sets if has_predicates(p) else todo)[key] = terms
+            if todo and PARTITION_MIN is not None:  # one-term patterns, by column: a large enough group is ONE read of its column
+                groups: dict[int, list] = {}
+                for key, terms in todo.items():
+                    if len(terms) == 1:
+                        groups.setdefault(terms[0][0], []).append(key)
+                for col, keys in groups.items():
+                    if len(keys) >= PARTITION_MIN:  # (different patterns on one key have different values, so different codes)
+                        for key, mk in zip(keys, self.index.make_masks_partition(col, [todo[key][0][1] for key in keys])):
+                            self.masks[key] = mk
+                            del todo[key]
             if todo:
                 for key, mk in zip(todo, self.index.make_masks_where(list(todo.values()))):
                     self.masks[key] = mk
@@ -529,6 +551,33 @@ class VecDB:
                 lims, idx, dist = ix.range_search(q, ub, limit)
             return [[(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx[int(lims[j]):int(lims[j + 1])], dist[int(lims[j]):int(lims[j + 1])])]
                     for j in range(nq)]
+
+    def count(self, key: str, filter=None) -> int:
+        """the number of rows that match `filter` -- a pattern, a pattern with predicates or an expression, handled exactly as search
+        handles it -- from the count of its cached mask; no filter: get_len"""
+        t = self._t(key)
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.read():
+            return len(t.index) if filter is None else len(t.mask_for(filter))
+
+    def count_by(self, key: str, field: str, filter=None) -> dict:
+        """{value: rows} over the values of the metadata key `field` among the rows that match `filter` (every row without one); rows
+        without the key are counted under None; values no matching row carries are left out.  `field` gets a label column on first
+        use, as a filter key does, and the answer is then ONE pass over that column on the device (GpuIndex.label_counts over every
+        code of the column's dictionary, under the filter's mask).  A field that cannot have a column (a 17th key) or whose column
+        holds values a dictionary cannot keep apart is counted by the host loop over the metadata."""
+        t = self._t(key)
+        t.prepare(([] if filter is None else [filter]) + [{field: None}])
+        with t.lock.read():
+            mk = None if filter is None else t.mask_for(filter)
+            vc = t.codec.value_codes(field)
+            if vc is not None:
+                values, codes = vc
+                cnt = t.index.label_counts(t.codec.column_of(field), codes + [LABEL_NONE], mk)
+                return {v: int(c) for v, c in zip(values + [None], cnt.tolist()) if c}
+            rows = range(len(t.metadata)) if mk is None else mk.rows()[1].tolist()
+            return dict(collections.Counter(t.metadata[i].get(field) for i in rows))
 
     def extract_data(self, key: str):
         t = self._t(key)
