@@ -377,6 +377,49 @@ int vdb_mask_create_partition(vdb_index *idx, uint32_t column, const uint32_t *c
 int vdb_index_label_counts(vdb_index *idx, uint32_t column, const vdb_mask *mask, const uint32_t *codes, uint64_t n_codes,
                            uint64_t *out_counts);
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids);
+/* ---- grouped Flat k-NN: at most group_size hits per value of one label column -----------------------------------------------------------
+ * "The 10 nearest chunks, at most 2 per document": the label columns so far restrict WHICH rows may be found; this call shapes the answer.
+ * For one query let L be its allowed rows in FlatIndex::knn's order -- ascending by (distance, id), NaN distances last; all rows, or
+ * the rows of the query's mask.  Walking L from its start, a row whose label in `column` is VDB_LABEL_NONE (never labelled, or a column
+ * never written) is always kept -- every such row is a group of its own -- and a row with label v is kept iff fewer than group_size
+ * rows EARLIER IN L carry v.  The answer is the first k kept rows in L's order: out_idx / out_dist [nq][k], out_count[q] = min(k, kept
+ * rows in all of L), slots past the count zero, id_offset added to the ids, distances the bit-exact f32 of the unfiltered search.  With
+ * group_size at least the largest group, or a column never written, the answer is that of vdb_flat_knn / vdb_flat_knn_filtered_multi
+ * at the same k, bit for bit.
+ *   n_masks == 0: unfiltered, masks / mask_of are not read; otherwise they mean what they mean for vdb_flat_knn_filtered_multi.
+ *   How: whether a row is kept depends only on the rows before it, so the capped walk of a prefix of L yields a prefix of the answer.
+ *   Round 0 takes the exact sorted list of K' = min(m, k x "flat_grouped_oversample") rows per query (m: the query's allowed rows) from the
+ *   existing exact search -- the unfiltered call exactly as vdb_flat_knn_device runs it, or the filtered call with a mask per query,
+ *   whose counters advance as if those calls had been made -- and k_group_cap walks it: one wave per query, tiles of 64 positions, the
+ *   labels gathered one tile ahead, a hash table label -> kept count (while fewer than k rows are kept it holds fewer than k labels,
+ *   however long L is: in LDS, or in device scratch for a k past ~2000), ballots and prefix popcounts for the rank inside a tile and the
+ *   output slot.  One read-back of a done byte per query ends the round; a query that neither kept k rows nor saw its whole allowed
+ *   set goes round again in a compacted block with 4 x K', clamped to m, and the longer list is walked again from its start.  A list of
+ *   m rows is everything, so the loop ends.  Later rounds run in sub-chunks of queries whose lists stay under 256 MiB.
+ *   "flat_grouped_oversample" (vdb_set_param, per index, >= 1, default 2: the winner of the sweep of tools/bench_grouped.py) never changes an answer, only the rounds.  Under masks longer
+ *   than "flat_filtered_direct_max" a K' above 64 takes the filtered call's direct path instead of its 8-bit tier, and without masks a K'
+ *   above 64 leaves the 8-bit first pass of vdb_flat_knn: a step in cost either way (measured: DESIGN 4.1q).
+ * vdb_flat_knn_grouped_device: queries and outputs on the index's GPU, at most 32768 queries, returns synchronised.
+ * vdb_group_cap_device: the walk alone over caller-supplied lists -- d_ids (u64, id_offset included) / d_dists (f32) [nq][ld] in ANY
+ * order, walked as given, and d_counts [nq] (u64; entries past min(count, ld) are not read) -- into d_out_idx / d_out_dist [nq][k] and
+ * d_out_count [nq]: what a sharded merge needs behind its top-k merge, and how the tests drive the kernel.  Every counted id is checked
+ * on the device first (one flag read back): an id that, after id_offset is subtracted, is not below len is VDB_ERR_INVALID with the
+ * outputs untouched; nothing is gathered out of bounds.
+ * Refused before anything is computed or written, counters unchanged (VDB_ERR_INVALID): group_size == 0, column >= VDB_LABEL_COLUMNS, a
+ * VecSet<u8> index, and every mask / mask_of error of vdb_flat_knn_filtered_multi (a stale mask: VDB_ERR_STATE).  nq == 0, k == 0 and
+ * m == 0 give empty results.  Read-side and re-entrant.
+ * vdb_get_stat "flat_grouped_calls", "flat_grouped_queries", "flat_grouped_rounds" (sum over calls of the rounds run),
+ * "flat_grouped_exhausted_queries" (queries whose last list was their whole allowed set); vdb_prof_get "group_cap" times k_group_cap.
+ * Not covered: sharded and replica contexts, VecSet<u8> indexes, PQ / HNSW / IVF searches, grouping by more than one column, range
+ * search. */
+int vdb_flat_knn_grouped(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint32_t column, uint64_t group_size,
+                         const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx, float *out_dist,
+                         uint64_t *out_count);
+int vdb_flat_knn_grouped_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, uint32_t column,
+                                uint64_t group_size, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, void *d_out_idx,
+                                void *d_out_dist, void *d_out_count, void *stream);
+int vdb_group_cap_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                         uint32_t column, uint64_t group_size, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
 /* the approximate keys the Flat shortlist pass compares with its threshold, for EVERY row, from the same kernel in its dense
  * mode (test / measurement entry point behind the certification-bound tests): out_keys [nq][len];
  * L2Sqr: key = |x|^2 - 2 S~, approximate distance = key + |q|^2;  Cosine: key = -S~ / |x|, approximate distance = 1 + key / |q|.

@@ -277,6 +277,22 @@ public:
         check(vdb_flat_range_filtered_multi(h_, queries, nq, dim_, radius, limit, hs.data(), hs.size(), mask_of.data(), &r));
         return take_range(r, nq);
     }
+    // per query the first k pairs of knn_batch of which at most group_size carry any one value of label column `column`; rows without a
+    // label are always kept (vdb_flat_knn_grouped).  masks empty: over all rows; otherwise query q under *masks[mask_of[q]]
+    std::vector<std::vector<CandidatePair>> knn_grouped_batch(const float *queries, uint64_t nq, uint64_t k, uint32_t column, uint64_t group_size = 1,
+                                                              const std::vector<const Mask *> &masks = {},
+                                                              const std::vector<uint32_t> &mask_of = {}) const {
+        if (!masks.empty() && mask_of.size() != nq) throw std::runtime_error("mask_of: one entry per query is needed");
+        std::vector<const vdb_mask *> hs;
+        for (const Mask *m : masks) hs.push_back(m->handle());
+        std::vector<uint64_t> idx(nq * (k ? k : 1)), cnt(nq);
+        std::vector<float> d(nq * (k ? k : 1));
+        check(vdb_flat_knn_grouped(h_, queries, nq, dim_, k, column, group_size, hs.data(), hs.size(), mask_of.data(), idx.data(), d.data(), cnt.data()));
+        std::vector<std::vector<CandidatePair>> out(nq);
+        for (uint64_t q = 0; q < nq; q++)
+            for (uint64_t j = 0; j < cnt[q]; j++) out[q].push_back({idx[q * k + j], d[q * k + j]});
+        return out;
+    }
 
     // MetadataVecTable::build_hnsw_index / clear_hnsw_index, build_pq_table / clear_pq_table
     void build_hnsw(uint64_t M = 16, uint64_t ef_construction = 200, uint64_t seed = 42, uint64_t batch = 64,

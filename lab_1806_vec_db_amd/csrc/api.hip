@@ -943,6 +943,109 @@ int vdb_flat_knn_filtered_multi_device(vdb_index *idx, const void *d_queries, ui
     VDB_API_END
 }
 
+// ---- grouped k-NN: at most group_size hits per value of one label column (Index::flat_knn_grouped_device, k_group.hip) ------------------
+// everything that can be refused is refused here, before anything is computed or written; -> the masks as RowMask pointers (none: unfiltered)
+static std::vector<const RowMask *> grouped_check(const Index &ix, uint64_t nq, uint32_t column, uint64_t group_size, const vdb_mask *const *masks,
+                                                  uint64_t n_masks, const uint32_t *mask_of) {
+    VDB_REQUIRE(group_size >= 1, "grouped k-NN: group_size must be at least 1");
+    VDB_REQUIRE(column < LABEL_COLUMNS, "grouped k-NN: column " + std::to_string(column) + ", an index has " + std::to_string(LABEL_COLUMNS));
+    VDB_REQUIRE(!ix.elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    if (n_masks == 0) return {};
+    return filtered_multi_check(ix, nq, masks, n_masks, mask_of);
+}
+
+int vdb_flat_knn_grouped(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint32_t column, uint64_t group_size,
+                         const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx, float *out_dist,
+                         uint64_t *out_count) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_query_args(ix, queries, nq, dim, out_idx, out_dist);
+    const std::vector<const RowMask *> rm = grouped_check(ix, nq, column, group_size, masks, n_masks, mask_of);
+    ix.grouped_calls++;
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    hipStream_t s = ws->stream;
+    constexpr uint64_t CHUNK = 16384;
+    const uint64_t kk = std::max<uint64_t>(k, 1), ch = std::min(nq, CHUNK);
+    // one device block for the outputs of a chunk [ids | distances | counts], as vdb_flat_knn_filtered lays them out
+    const size_t off_d = ch * kk * sizeof(uint64_t), off_c = (off_d + ch * kk * sizeof(float) + 7) & ~size_t(7);
+    ws->q.reserve(ch * dim * sizeof(float));
+    ws->out_idx.reserve(off_c + ch * sizeof(uint64_t));
+    char *d_out = ws->out_idx.as<char>();
+    try {
+        for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
+            const uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
+            VDB_HIP(hipMemcpyAsync(ws->q.p, queries + q0 * dim, nb * dim * sizeof(float), hipMemcpyHostToDevice, s));
+            ix.flat_knn_grouped_device(*ws, ws->q.as<float>(), nb, k, column, group_size, rm.data(), n_masks, n_masks ? mask_of + q0 : nullptr,
+                                       reinterpret_cast<uint64_t *>(d_out), reinterpret_cast<float *>(d_out + off_d), reinterpret_cast<uint64_t *>(d_out + off_c));
+            if (k) {
+                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
+            }
+            if (out_count) VDB_HIP(hipMemcpyAsync(out_count + q0, d_out + off_c, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            VDB_SYNC(s);
+        }
+    } catch (...) {
+        (void)hipStreamSynchronize(s);  // nothing of a failed call is still running when its buffers go
+        ix.prof_collect(*ws);
+        throw;
+    }
+    ix.prof_collect(*ws);
+    VDB_API_END
+}
+
+int vdb_flat_knn_grouped_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, uint32_t column, uint64_t group_size,
+                                const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, void *d_out_idx, void *d_out_dist,
+                                void *d_out_count, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_query_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist);
+    VDB_REQUIRE(nq == 0 || d_out_count, "null out_count");
+    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
+    const std::vector<const RowMask *> rm = grouped_check(ix, nq, column, group_size, masks, n_masks, mask_of);
+    ix.grouped_calls++;
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
+    try {
+        ix.flat_knn_grouped_device(*ws, static_cast<const float *>(d_queries), nq, k, column, group_size, rm.data(), n_masks, n_masks ? mask_of : nullptr,
+                                   static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
+    } catch (...) {
+        (void)hipStreamSynchronize(ws->stream);
+        ix.prof_collect(*ws);
+        throw;
+    }
+    ix.prof_collect(*ws);
+    VDB_API_END
+}
+
+int vdb_group_cap_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                         uint32_t column, uint64_t group_size, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    VDB_REQUIRE(group_size >= 1, "grouped k-NN: group_size must be at least 1");
+    VDB_REQUIRE(column < LABEL_COLUMNS, "grouped k-NN: column " + std::to_string(column) + ", an index has " + std::to_string(LABEL_COLUMNS));
+    VDB_REQUIRE(nq == 0 || (d_counts && d_out_count && (ld == 0 || (d_ids && d_dists)) && (k == 0 || (d_out_idx && d_out_dist))), "null argument");
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the lists on the caller's stream
+    try {
+        ix.group_cap_device(*ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), nq, ld, k,
+                            column, group_size, static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
+    } catch (...) {
+        (void)hipStreamSynchronize(ws->stream);
+        ix.prof_collect(*ws);
+        throw;
+    }
+    VDB_API_END
+}
+
 int vdb_flat_range_filtered(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit, const vdb_mask *mask,
                             vdb_range **out) {
     VDB_API_BEGIN
@@ -1122,6 +1225,10 @@ int vdb_set_param(vdb_index *idx, const char *name, int64_t value) {
         VDB_REQUIRE(value >= 0, "flat_filtered_direct_max must be >= 0");
         idx->ix.flat_filtered_direct_max = (uint64_t)value;
     }
+    else if (n == "flat_grouped_oversample") {  // grouped k-NN: round 0 fetches min(m, k x this) rows per query
+        VDB_REQUIRE(value >= 1, "flat_grouped_oversample must be >= 1");
+        idx->ix.flat_grouped_oversample = (uint64_t)value;
+    }
     else if (n == "debug_alloc_fail_over")  // (testing aid, process-wide) device allocations of at least this many bytes fail; 0 = off
         devbuf_fail_over() = (size_t)value;
     else if (n == "flat_i8_unit_min")  // threshold sample of the 8-bit pass: one value per sampled unit when the units are many (0 auto, 1 off, 2 on from 2 x rank units: tests)
@@ -1294,6 +1401,14 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.mask_partition_masks.load();
     else if (n == "label_count_calls")  // vdb_index_label_counts calls
         *out = idx->ix.label_count_calls.load();
+    else if (n == "flat_grouped_calls")  // grouped k-NN: calls | queries | rounds run, summed over calls | queries whose last list was their whole allowed set
+        *out = idx->ix.grouped_calls.load();
+    else if (n == "flat_grouped_queries")
+        *out = idx->ix.grouped_queries.load();
+    else if (n == "flat_grouped_rounds")
+        *out = idx->ix.grouped_rounds.load();
+    else if (n == "flat_grouped_exhausted_queries")
+        *out = idx->ix.grouped_exhausted.load();
     else if (n == "label_columns")  // allocated label columns (4 B per row each)
         *out = idx->ix.label_columns();
     else if (n == "hbm_bytes_per_row")

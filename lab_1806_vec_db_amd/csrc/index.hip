@@ -1871,6 +1871,134 @@ void Index::flat_knn_masked_multi_device(Workspace &ws, const float *d_q, uint64
     VDB_SYNC(s);  // (the plan's host arrays are pageable memory: alive until here)
 }
 
+// ---- Flat: grouped k-NN, at most g hits per value of one label column (k_group.hip, grouped_plan.hpp; docs/DESIGN_flat.md 4.1q) ----------
+// Whether a row is kept depends only on the rows before it in the query's order, so the capped walk of a PREFIX of that order gives a
+// prefix of the answer: a round fetches the exact sorted list of K' rows and walks it, and a query that neither filled its k slots nor
+// saw its whole allowed set goes round again with a longer list, walked again from its start (the walk is cheap beside the search that
+// made the list, and nothing is carried between rounds but the list of open queries).  Round 0 runs on the call's own query block and
+// mask_of; later rounds on a compacted block.  A round's queries are cut into sub-chunks whose lists stay under GROUPED_LIST_BUDGET; its
+// done bytes are read back once, at its end.
+void Index::flat_knn_grouped_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint32_t column, uint64_t g, const RowMask *const *masks,
+                                    uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
+    hipStream_t s = ws.stream;
+    VDB_REQUIRE(!elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    VDB_REQUIRE(column < LABEL_COLUMNS && g >= 1, "grouped k-NN: bad column or group size");
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 32) && k <= (1ull << 30) - GROUPED_TILE, "flat knn: too many queries or k too large");  // (the walk's table: 2^31 entries at most)
+    grouped_queries += nq;
+    if (k == 0) {
+        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
+        VDB_SYNC(s);
+        return;
+    }
+    std::vector<uint64_t> m_of(nq);
+    uint64_t max_m = 0;
+    for (uint64_t q = 0; q < nq; q++) {
+        m_of[q] = n_masks ? masks[mask_of[q]]->m : n;
+        max_m = std::max(max_m, m_of[q]);
+    }
+    const uint32_t *col = label_live[column] ? d_labels[column].as<uint32_t>() : nullptr;
+    const uint32_t g32 = (uint32_t)std::min<uint64_t>(g, 0xFFFFFFFFull);
+    std::vector<uint64_t> active(nq), next;
+    for (uint64_t q = 0; q < nq; q++) active[q] = q;
+    std::vector<uint32_t> slot, mo;
+    uint64_t kp = grouped_first_k(k, flat_grouped_oversample, max_m);
+    uint64_t exhausted = 0, rounds = 0;
+    for (bool first = true; !active.empty(); first = false) {
+        const uint64_t na = active.size();
+        uint64_t sub = grouped_sub_chunk(na, kp);
+        const size_t table1 = group_cap_scratch_bytes(1, k, kp);
+        if (table1) sub = std::max<uint64_t>(1, std::min<uint64_t>(sub, GROUPED_LIST_BUDGET / table1));
+        // every buffer of the round before its first launch; the round before has synchronised
+        const size_t off_slot = na * sizeof(uint64_t), off_done = off_slot + na * sizeof(uint32_t);
+        ws.grp_ids.reserve(sub * kp * sizeof(uint64_t));
+        ws.grp_dist.reserve(sub * kp * sizeof(float));
+        ws.grp_cnt.reserve(sub * sizeof(uint64_t));
+        ws.grp_aux.reserve(off_done + na);
+        if (table1) ws.grp_table.reserve(sub * table1);
+        char *aux = ws.grp_aux.as<char>();
+        const uint32_t *d_slot = nullptr;
+        uint8_t *d_done = reinterpret_cast<uint8_t *>(aux + off_done);
+        const float *Q = d_q;
+        const uint32_t *mof = mask_of;
+        if (!first) {  // the open queries as a block of their own: rows, the map back to the call's positions, their masks
+            ws.grp_q.reserve(na * dim * sizeof(float));
+            slot.resize(na);
+            for (uint64_t i = 0; i < na; i++) slot[i] = (uint32_t)active[i];
+            VDB_HIP(hipMemcpyAsync(aux, active.data(), na * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            VDB_HIP(hipMemcpyAsync(aux + off_slot, slot.data(), na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            launch_gather_rows_f32(d_q, reinterpret_cast<const uint64_t *>(aux), na, (uint32_t)dim, ws.grp_q.as<float>(), s);
+            d_slot = reinterpret_cast<const uint32_t *>(aux + off_slot);
+            Q = ws.grp_q.as<float>();
+            if (n_masks) {
+                mo.resize(na);
+                for (uint64_t i = 0; i < na; i++) mo[i] = mask_of[active[i]];
+                mof = mo.data();
+            }
+        }
+        if (n_masks) filtered_multi_calls++;
+        for (uint64_t c0 = 0; c0 < na; c0 += sub) {
+            const uint64_t nb = std::min(sub, na - c0);
+            uint64_t *l_ids = ws.grp_ids.as<uint64_t>(), *l_cnt = ws.grp_cnt.as<uint64_t>();
+            float *l_dist = ws.grp_dist.as<float>();
+            if (n_masks)
+                flat_knn_masked_multi_device(ws, Q + c0 * dim, nb, kp, masks, n_masks, mof + c0, l_ids, l_dist, l_cnt);
+            else
+                flat_knn_device(ws, Q + c0 * dim, nb, kp, l_ids, l_dist, l_cnt);
+            prof_begin(ws, "group_cap", double(nb) * kp * (GROUPED_PAIR_BYTES + sizeof(uint32_t)));
+            if (first)
+                launch_group_cap(l_ids, l_dist, l_cnt, nb, kp, col, n, id_offset, (uint32_t)k, g32, ws.grp_table.as<uint32_t>(), nullptr, d_idx + c0 * k,
+                                 d_dist + c0 * k, d_cnt + c0, d_done + c0, s);
+            else
+                launch_group_cap(l_ids, l_dist, l_cnt, nb, kp, col, n, id_offset, (uint32_t)k, g32, ws.grp_table.as<uint32_t>(), d_slot + c0, d_idx, d_dist,
+                                 d_cnt, d_done + c0, s);
+            prof_end(ws);
+        }
+        uint8_t *h_done = static_cast<uint8_t *>(ws.pinned(na));  // (the list calls have synchronised: their use of the block is over)
+        VDB_HIP(hipMemcpyAsync(h_done, d_done, na, hipMemcpyDeviceToHost, s));
+        VDB_SYNC(s);  // (ends the round: the host arrays uploaded above are free again)
+        prof_collect(ws);
+        rounds++;
+        const uint64_t open_m = grouped_compact(active, h_done, m_of.data(), kp, next, exhausted);
+        active.swap(next);
+        if (!active.empty()) kp = grouped_next_k(kp, open_m);
+    }
+    grouped_rounds += rounds;
+    grouped_exhausted += exhausted;
+}
+
+void Index::group_cap_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                             uint32_t column, uint64_t g, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
+    hipStream_t s = ws.stream;
+    VDB_REQUIRE(column < LABEL_COLUMNS && g >= 1, "grouped k-NN: bad column or group size");
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 32) && k < (1ull << 31), "flat knn: too many queries or k too large");
+    VDB_REQUIRE(std::min(k, ld) <= (1ull << 30) - GROUPED_TILE, "grouped k-NN: k too large");
+    const size_t table1 = group_cap_scratch_bytes(1, k, ld);
+    const uint64_t sub = table1 ? std::max<uint64_t>(1, std::min<uint64_t>(nq, GROUPED_LIST_BUDGET / table1)) : nq;
+    ws.grp_aux.reserve(sizeof(uint32_t) + nq);
+    if (table1) ws.grp_table.reserve(sub * table1);
+    uint32_t *d_flag = ws.grp_aux.as<uint32_t>();
+    uint8_t *d_done = ws.grp_aux.as<uint8_t>() + sizeof(uint32_t);
+    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+    launch_group_check(d_ids, d_counts, nq, ld, n, id_offset, d_flag, s);
+    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
+    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDB_SYNC(s);
+    VDB_REQUIRE(*h_flag == 0, "group cap: a list holds an id that is no row of this index (id - id_offset must be below len)");
+    const uint32_t *col = label_live[column] ? d_labels[column].as<uint32_t>() : nullptr;
+    const uint32_t g32 = (uint32_t)std::min<uint64_t>(g, 0xFFFFFFFFull);
+    for (uint64_t c0 = 0; c0 < nq; c0 += sub) {
+        const uint64_t nb = std::min(sub, nq - c0);
+        prof_begin(ws, "group_cap", double(nb) * ld * (GROUPED_PAIR_BYTES + sizeof(uint32_t)));
+        launch_group_cap(d_ids + c0 * ld, d_dists + c0 * ld, d_counts + c0, nb, ld, col, n, id_offset, (uint32_t)k, g32, ws.grp_table.as<uint32_t>(), nullptr,
+                         d_idx + c0 * k, d_dist + c0 * k, d_cnt + c0, d_done + c0, s);
+        prof_end(ws);
+    }
+    VDB_SYNC(s);
+    prof_collect(ws);
+}
+
 // ---- Flat: exact filtered range search with one row mask per query (k_filter.hip, multi_plan.hpp) --------------------------------------
 // Query q's slice is what flat_range_device returns for it alone under masks[mask_of[q]].  The queries are bucketed by mask on the host:
 //   per-mask route: a bucket whose mask is longer than flat_filtered_direct_max, and every bucket of a u8 index, is gathered (queries and

@@ -126,6 +126,9 @@ struct Workspace {
     DevBuf q, qsq, qfrag, qfrag_g, qaux, dense, lists, keys_a, keys_b, keys_c, flags, out_idx, out_dist, out_cnt, lut, misc;
     DevBuf pq_img16, pq_aux16;     // 8-bit PQ codes: the sliced 16-bit table images of a round of queries, their minima / offsets / steps (pq.hip)
     DevBuf small_part, small_cnt;  // k_flat_small: per-workgroup key lists, arrival counters (zero between launches)
+    // grouped k-NN (Index::flat_knn_grouped_device): the compacted queries of a round, the candidate lists of a sub-chunk (ids, distances,
+    // counts), [slot map | done bytes | flag], the walk's table beyond LDS -- buffers of their own, because the list calls use the others
+    DevBuf grp_q, grp_ids, grp_dist, grp_cnt, grp_aux, grp_table;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     struct Pending {
         std::string name;
@@ -597,6 +600,20 @@ struct Index {
                       bool slabs = false);
     // (slabs: the bit words of a chunk's masks are views into ONE allocation, zeroed, and their allow-lists views into another, every
     // view DEVBUF_ALIGN-aligned -- masks_partition's; false: an allocation per mask and list, as every other caller has it.)
+    // Grouped Flat k-NN (k_group.hip, grouped_plan.hpp; docs/DESIGN_flat.md 4.1q): per query the first k rows, in FlatIndex::knn's order over
+    // the allowed rows, of which at most g carry any one value of label column `column` (rows without a label are always kept).  Rounds:
+    // the exact sorted list of K' rows per open query -- flat_knn_device without masks, flat_knn_masked_multi_device over the call's masks,
+    // whose counters advance as for those calls -- walked by k_group_cap, ONE read-back of the done bytes, the open queries compacted and
+    // sent round again with 4 K' until a list is the query's whole allowed set.  n_masks == 0: unfiltered (masks / mask_of not read).  The
+    // caller has checked column, g >= 1, the masks and mask_of; returns synchronised.
+    void flat_knn_grouped_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint32_t column, uint64_t g, const RowMask *const *masks,
+                                 uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
+    // k_group_cap alone over caller-supplied lists [nq][ld] (device): every id of the counted ranges is checked on the device first (one
+    // flag read back; a bad one throws before an output is written).  Returns synchronised.
+    void group_cap_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                          uint32_t column, uint64_t g, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
+    uint64_t flat_grouped_oversample = GROUPED_OVERSAMPLE_DEFAULT;  // "flat_grouped_oversample": round 0 fetches min(m, k x this) rows
+    std::atomic<uint64_t> grouped_calls{0}, grouped_queries{0}, grouped_rounds{0}, grouped_exhausted{0};
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};

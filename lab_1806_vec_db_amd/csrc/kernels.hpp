@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "grouped_plan.hpp"
 #include "mask_any.hpp"
 #include "mask_partition.hpp"
 #include "mask_sets.hpp"
@@ -395,6 +396,18 @@ void launch_mask_partition(const uint32_t *col, const uint32_t *table, uint32_t 
 // counts[i] += the rows allowed by bits (nullptr: every row) whose code is table[i]; the caller has zeroed counts [nb] on the same stream
 void launch_label_counts(const uint32_t *col, const uint32_t *table, uint32_t nb, const uint64_t *bits, uint64_t n, uint32_t *counts,
                          int num_cu, hipStream_t s);
+// The capped walk of the grouped k-NN (k_group.hip, grouped_plan.hpp): query b's list ids / dists [b][0 .. min(counts[b], ld)) walked in the order
+// given, at most g rows kept per value of `labels` (u32 per LOCAL row = id - id_offset; nullptr: a column never written; a row without a
+// label is always kept), the first k kept pairs to row slot_q[b] (nullptr: b) of out_idx / out_dist [..][k] with zeros behind them, their
+// number to out_cnt[that row], done[b] = k rows were kept | counts[b] < ld.  An id that is no row of the index is not gathered (it reads as
+// unlabelled).  scratch: group_cap_scratch_bytes(nq, k, ld) bytes, 0 when the walk's table fits LDS.
+size_t group_cap_scratch_bytes(uint64_t nq, uint64_t k, uint64_t ld);
+void launch_group_cap(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nq, uint64_t ld, const uint32_t *labels, uint64_t n,
+                      uint64_t id_offset, uint32_t k, uint32_t g, uint32_t *scratch, const uint32_t *slot_q, uint64_t *out_idx, float *out_dist,
+                      uint64_t *out_cnt, uint8_t *done, hipStream_t s);
+// *flag = 1 when an id of the counted part of a list is no row of the index (id - id_offset not in [0, n)); the caller has zeroed it
+void launch_group_check(const uint64_t *ids, const uint64_t *counts, uint64_t nq, uint64_t ld, uint64_t n, uint64_t id_offset, uint32_t *flag,
+                        hipStream_t s);
 void mfma_set_sample_thin(int v);
 void mfma_sample_plan(uint64_t n, uint32_t kprime, uint32_t *step, uint32_t *rank, uint32_t target_floor = 1024);  // target_floor: expected hits per query
 uint64_t mfma_sample_rows(uint64_t n, uint32_t step);

@@ -511,6 +511,54 @@ class GpuIndex:
         L.check(self._lib.vdb_flat_knn_filtered_multi_device(self._h, L.vp(q_ptr), int(nq), self.dim, int(k), arr, n_masks, _ptr(mo, L.u32p),
                                                              L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
 
+    def _grouped_mask_args(self, masks, mask_of, nq: int):
+        """(array, count, mask_of pointer) of a grouped call: no masks = unfiltered; one mask without mask_of = that mask for every query"""
+        if masks is None:
+            return None, 0, None, None
+        if isinstance(masks, RowMask):
+            masks = [masks]
+        if mask_of is None:
+            masks = list(masks)
+            if len(masks) != 1:
+                raise ValueError("mask_of is needed with more than one mask")
+            mask_of = np.zeros(nq, dtype=np.uint32)
+        arr, n_masks, mo = self._mask_args(masks, mask_of, nq)
+        return arr, n_masks, _ptr(mo, L.u32p), mo
+
+    def flat_knn_grouped(self, queries, k: int, column: int, group_size: int = 1, masks=None, mask_of=None):
+        """Exact k-NN with at most `group_size` hits per value of label column `column` (vdb_flat_knn_grouped): per query the first k rows,
+        in flat_knn's order, such that fewer than group_size earlier rows of that order carry the same label; rows without a label are
+        always kept.  masks=None: over all rows; otherwise query q under masks[mask_of[q]] as in flat_knn_filtered_multi (one RowMask and
+        no mask_of: that mask for every query).  Same return shapes as flat_knn_filtered."""
+        q = _f32(queries)
+        single = q.ndim == 1
+        q = q.reshape(1, -1) if single else q
+        nq, dim = q.shape
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, nq)
+        kk = max(int(k), 1)
+        idx = np.zeros((nq, kk), dtype=np.uint64)
+        dist = np.zeros((nq, kk), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint64)
+        L.check(self._lib.vdb_flat_knn_grouped(self._h, _ptr(q, L.f32p), nq, dim, int(k), int(column), int(group_size), arr, n_masks, mo_p,
+                                               _ptr(idx, L.u64p), _ptr(dist, L.f32p), _ptr(cnt, L.u64p)))
+        if single:
+            c = int(cnt[0])
+            return idx[0, :c].copy(), dist[0, :c].copy()
+        return idx[:, :int(k)], dist[:, :int(k)], cnt
+
+    def flat_knn_grouped_device(self, q_ptr: int, nq: int, k: int, column: int, group_size: int, out_idx_ptr: int, out_dist_ptr: int,
+                                out_cnt_ptr: int, masks=None, mask_of=None, stream: int = 0):
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, int(nq))
+        L.check(self._lib.vdb_flat_knn_grouped_device(self._h, L.vp(q_ptr), int(nq), self.dim, int(k), int(column), int(group_size), arr, n_masks,
+                                                      mo_p, L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
+
+    def group_cap_device(self, ids_ptr: int, dists_ptr: int, counts_ptr: int, nq: int, ld: int, k: int, column: int, group_size: int,
+                         out_idx_ptr: int, out_dist_ptr: int, out_cnt_ptr: int, stream: int = 0):
+        """the capped walk alone over caller-supplied device lists [nq][ld] (u64 ids, f32 distances) and u64 counts, walked in the order
+        given (vdb_group_cap_device); an id that is no row of this index raises and leaves the outputs untouched"""
+        L.check(self._lib.vdb_group_cap_device(self._h, L.vp(ids_ptr), L.vp(dists_ptr), L.vp(counts_ptr), int(nq), int(ld), int(k), int(column),
+                                               int(group_size), L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
+
     def _range_out(self, h, nq: int):
         return read_range(self._lib, h, nq)
 

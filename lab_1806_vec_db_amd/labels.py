@@ -365,6 +365,30 @@ def matches_filter(expr, metadata_row) -> bool:
     raise TypeError(f"a filter is a pattern dict, AnyOf, AllOf or Not, not {type(expr).__name__}")
 
 
+def cap_groups(codes_in_order, group_size: int, k: int) -> list[int]:
+    """THE host statement of the grouped k-NN's walk (GpuIndex.flat_knn_grouped, k_group_cap): the positions kept from a list of label codes
+    given in the query's order -- a position without a label (None or LABEL_NONE) always, a position with code v iff fewer than
+    group_size earlier positions carry v -- cut to the first k kept.  The codes may be any hashable values."""
+    if int(group_size) < 1:
+        raise ValueError("group_size must be at least 1")
+    kept: list[int] = []
+    seen: dict[object, int] = {}
+    if k <= 0:
+        return kept
+    for pos, c in enumerate(codes_in_order):
+        if isinstance(c, np.integer):
+            c = int(c)
+        if c is not None and c != LABEL_NONE:
+            n = seen.get(c, 0)
+            if n >= group_size:
+                continue
+            seen[c] = n + 1
+        kept.append(pos)
+        if len(kept) >= k:
+            break
+    return kept
+
+
 class LabelCodec:
     def __init__(self, max_columns: int = LABEL_COLUMNS, max_terms: int = MASK_MAX_TERMS):
         self.max_columns = int(max_columns)
@@ -576,4 +600,4 @@ class LabelCodec:
 
 __all__ = ["LabelCodec", "LabelTerm", "LABEL_COLUMNS", "LABEL_NONE", "MASK_MAX_TERMS", "MASK_MAX_SET_BITS", "MASK_MAX_CLAUSES", "NOTHING", "TERM_NEGATE",
            "TERM_NONE", "In", "NotIn", "Ne", "Exists", "Lt", "Le", "Gt", "Ge", "Between", "matches", "is_predicate", "has_predicates",
-           "AnyOf", "AllOf", "Not", "matches_filter", "is_expression", "filter_key", "filter_patterns"]
+           "AnyOf", "AllOf", "Not", "matches_filter", "is_expression", "filter_key", "filter_patterns", "cap_groups"]

@@ -29,6 +29,8 @@ disjunctive normal form over the label columns (LabelCodec.compile_any) is evalu
 its operands with GpuIndex.combine_masks.  A pattern dict keeps its path; delete takes a pattern only.
 count(key, filter) is the number of matching rows (the mask's count); count_by(key, field, filter) the matching rows per value of a
 metadata key, from one pass over the key's label column on the device (GpuIndex.label_counts).
+search / batch_search take `group_by`, a metadata key, and `group_size`: at most that many hits per value of the key, nearest first, rows
+without the key always kept -- exact, from the Flat rows, in one library call over the key's label column (GpuIndex.flat_knn_grouped).
 """
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ import numpy as np
 
 from ._lib import VdbError
 from .index import GpuIndex, RowMask, parse_dist
-from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, filter_key, filter_patterns, has_predicates, is_expression
+from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, filter_patterns, has_predicates, is_expression
 from .labels import matches as value_matches
 
 _DIST_STR = {0: "l2sqr", 1: "cosine"}
@@ -428,13 +430,16 @@ class VecDB:
 
     # ---- reads ------------------------------------------------------------------------------------------------
     def search(self, key: str, query, k: int, ef: int | None = None, upper_bound: float | None = None,
-               filter: dict[str, str] | None = None):
+               filter: dict[str, str] | None = None, group_by: str | None = None, group_size: int = 1):
         """MetadataVecTable::search.  `filter`: a metadata pattern matched exactly as delete matches (every key present with an equal
         value; an empty pattern matches every row) -- only matching rows are searched.  With a filter the answer is always EXACT, from
-        the table's Flat rows, whatever indexes the table has, and `ef` is ignored."""
+        the table's Flat rows, whatever indexes the table has, and `ef` is ignored.  `group_by`: a metadata key -- at most `group_size`
+        hits per value of it (batch_search states the rule); exact as with a filter, same return shape."""
         t = self._t(key)
         ix = t.index
         q = np.asarray(query, dtype=np.float32).ravel()
+        if group_by is not None:
+            return self.batch_search(key, q.reshape(1, -1), k, ef, upper_bound, filter, group_by, group_size)[0]
         if filter is not None:
             t.prepare([filter])
         with t.lock.read():  # database/mod.rs:255: read guard for the whole search, metadata lookup included
@@ -451,12 +456,21 @@ class VecDB:
             ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
             return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist) if d <= ub]
 
-    def batch_search(self, key: str, queries, k: int, ef: int | None = None, upper_bound: float | None = None, filters=None):
+    def batch_search(self, key: str, queries, k: int, ef: int | None = None, upper_bound: float | None = None, filters=None,
+                     group_by: str | None = None, group_size: int = 1):
         """search for a batch of queries in ONE library call: entry q of the returned list is what search(key, queries[q], k, ef,
         upper_bound, filter) returns.  `filters`: None, ONE metadata pattern for every query, or a list of len(queries) patterns (the
         multi-tenant batch: every query restricted to its own rows; {} matches every row).  With filters the answers are exact, from
         the table's Flat rows, through one flat_knn_filtered_multi call over one mask per distinct pattern; without, the batch is
-        dispatched as search dispatches a query (knn_pq, knn_with_ef or knn)."""
+        dispatched as search dispatches a query (knn_pq, knn_with_ef or knn).
+        `group_by`: a metadata key.  Walking a query's matching rows nearest first (ties by row), a row without the key is always kept
+        and a row with value v is kept iff fewer than `group_size` rows before it carry v; the answer is the first k kept rows -- always
+        exact, from the Flat rows (`ef` is ignored), a flat list as without it; `upper_bound` is applied afterwards.  The key gets a label
+        column on first use, as count_by's field does, and the batch is ONE flat_knn_grouped call (under the filters' masks when there
+        are filters).  A key that cannot have a column (a 17th key) or whose values a dictionary cannot keep apart takes the host
+        fallback: the ungrouped search at a growing k, walked by labels.cap_groups over the metadata values."""
+        if group_by is not None and int(group_size) < 1:
+            raise ValueError("group_size must be at least 1")
         t = self._t(key)
         ix = t.index
         q = np.asarray(queries, dtype=np.float32)
@@ -473,7 +487,10 @@ class VecDB:
         if filters is not None:
             pats = [filters] * nq if isinstance(filters, dict) or is_expression(filters) else filters
             t.prepare(pats)
+        if group_by is not None:
+            t.prepare([{group_by: None}])  # (the key's column, as count_by makes it)
         with t.lock.read():  # one read guard for the whole batch, mask building and metadata lookup included
+            masks = mask_of = None
             if pats is not None:
                 slot: dict[object, int] = {}
                 distinct, mask_of = [], np.zeros(nq, dtype=np.uint32)
@@ -484,6 +501,12 @@ class VecDB:
                         distinct.append(p)
                     mask_of[i] = slot[pk]
                 masks = t.masks_for(distinct)  # the ones not cached yet: one library call
+            if group_by is not None:
+                if t.codec.value_codes(group_by) is not None:
+                    idx, dist, cnt = ix.flat_knn_grouped(q, k, t.codec.column_of(group_by), group_size, masks, mask_of)
+                else:
+                    idx, dist, cnt = self._grouped_on_host(t, q, k, group_by, group_size, masks, mask_of)
+            elif pats is not None:
                 idx, dist, cnt = ix.flat_knn_filtered_multi(q, k, masks, mask_of)
             elif ef is not None and ix.has_pq():
                 idx, dist, cnt = ix.knn_pq(q, k, ef)
@@ -494,6 +517,44 @@ class VecDB:
             ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
             return [[(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx[j, :int(cnt[j])], dist[j, :int(cnt[j])]) if d <= ub]
                     for j in range(nq)]
+
+    @staticmethod
+    def _grouped_on_host(t: _Table, q: np.ndarray, k: int, field: str, group_size: int, masks, mask_of):
+        """UNDER THE READ LOCK: group_by for a field without a usable label column -- the exact ungrouped search at a growing k (4 k, then
+        4 x that), each query's list walked by cap_groups over the metadata values, until every query has k kept rows or its list was
+        every row it may see.  Values are told apart by equality (unhashable ones by a scan)."""
+        ix = t.index
+        nq = q.shape[0]
+        k = int(k)
+        kk = max(k, 1) * 4
+        n = len(ix)
+        while True:
+            if masks is None:
+                idx, dist, cnt = ix.flat_knn(q, kk)
+            else:
+                idx, dist, cnt = ix.flat_knn_filtered_multi(q, kk, masks, mask_of)
+            o_idx, o_dist, o_cnt = np.zeros((nq, max(k, 1)), np.uint64), np.zeros((nq, max(k, 1)), np.float32), np.zeros(nq, np.uint64)
+            short = False
+            for j in range(nq):
+                c = int(cnt[j])
+                codes, odd = [], []
+                for i in idx[j, :c]:
+                    v = t.metadata[int(i)].get(field)
+                    try:
+                        hash(v)
+                    except TypeError:
+                        if v not in odd:
+                            odd.append(v)
+                        v = ("unhashable", odd.index(v), id(odd))
+                    codes.append(v)
+                kept = cap_groups(codes, group_size, k)
+                short = short or (len(kept) < k and c == kk and kk < n)
+                o_cnt[j] = len(kept)
+                o_idx[j, :len(kept)] = idx[j, kept]
+                o_dist[j, :len(kept)] = dist[j, kept]
+            if not short:
+                return o_idx[:, :k], o_dist[:, :k], o_cnt
+            kk = min(kk * 4, n)
 
     def search_within(self, key: str, query, upper_bound: float, limit: int | None = None, filter: dict[str, str] | None = None):
         """Every row within `upper_bound` of the query (distance <= upper_bound, as search's filter compares), nearest first: what
