@@ -59,6 +59,140 @@ void vdb::merge_topk_dev(Index &ix, const void *d_dists, const void *d_ids, cons
     VDB_SYNC(ws->stream);
 }
 
+// ---- the front ends the search entry points below share (templates: in front of the extern "C" block) ------------------------------
+static void check_query_args(const Index &ix, const void *queries, uint64_t nq, uint64_t dim, const void *out_idx,
+                             const void *out_dist) {
+    VDB_REQUIRE(dim == ix.dim, "query dimension mismatch: index dim " + std::to_string(ix.dim) + ", got " +
+                                   std::to_string(dim));
+    VDB_REQUIRE(nq == 0 || (queries && out_idx && out_dist), "null argument");
+}
+
+// the failure path of every search front end: nothing of a failed call is still running when its buffers go
+template <class Body>
+static void run_synced(Index &ix, Workspace &ws, Body &&body) {
+    try {
+        body();
+    } catch (...) {
+        (void)hipStreamSynchronize(ws.stream);
+        ix.prof_collect(ws);
+        throw;
+    }
+    ix.prof_collect(ws);
+}
+
+// The k-NN front ends take the search as fn(ws, d_q, q0, nb, d_idx, d_dist, d_cnt): nb queries at d_q, which are the call's queries
+// q0 .. q0 + nb (what a per-query argument such as mask_of is advanced by), answered into the three device outputs (`auto... o` in the
+// lambdas below); k, ef and whatever else the search needs are the callable's own captures.
+// host-pointer front end shared by all searches: stage queries, run, copy results back
+template <class Fn>
+static void host_search(Index &ix, const float *queries, uint64_t nq, uint64_t k, uint64_t *out_idx, float *out_dist, uint64_t *out_count, Fn &&fn) {
+    if (nq == 0) return;
+    ix.use_device();
+    WsLease ws(ix);
+    hipStream_t s = ws->stream;
+    constexpr uint64_t CHUNK = 16384;
+    run_synced(ix, *ws, [&] {
+        for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
+            uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
+            uint64_t kk = std::max<uint64_t>(k, 1);
+            // ONE device block for the three outputs [ids | distances | counts] and ONE pinned host block [queries | that block]:
+            // a call moves two async copies through page-locked memory instead of four pageable ones (each of which the runtime
+            // stages and waits for on its own) -- what a db.search()-shaped call of one query pays for besides its kernels
+            const size_t qb = nb * ix.dim * sizeof(float), ib = nb * kk * sizeof(uint64_t), db = nb * kk * sizeof(float), cb = nb * sizeof(uint64_t);
+            const size_t off_d = ib, off_c = (ib + db + 7) & ~size_t(7), ob = off_c + cb, q_pad = (qb + 15) & ~size_t(15);
+            const bool staged = q_pad + ob <= (size_t(8) << 20);
+            ws->q.reserve(qb);
+            ws->out_idx.reserve(ob);
+            char *d_out = ws->out_idx.as<char>();
+            char *h = staged ? static_cast<char *>(ws->pinned(q_pad + ob)) : nullptr;
+            if (staged) {
+                std::memcpy(h, queries + q0 * ix.dim, qb);
+                VDB_HIP(hipMemcpyAsync(ws->q.p, h, qb, hipMemcpyHostToDevice, s));
+            } else {
+                VDB_HIP(hipMemcpyAsync(ws->q.p, queries + q0 * ix.dim, qb, hipMemcpyHostToDevice, s));
+            }
+            fn(*ws, ws->q.as<float>(), q0, nb, reinterpret_cast<uint64_t *>(d_out), reinterpret_cast<float *>(d_out + off_d),
+               reinterpret_cast<uint64_t *>(d_out + off_c));
+            // (fn may have used the pinned block for its own flags and has synchronised after reading them: the block is free again)
+            if (staged) {
+                h = static_cast<char *>(ws->pinned(q_pad + ob));
+                VDB_HIP(hipMemcpyAsync(h + q_pad, d_out, ob, hipMemcpyDeviceToHost, s));
+                VDB_SYNC(s);
+                if (k) {
+                    std::memcpy(out_idx + q0 * k, h + q_pad, nb * k * sizeof(uint64_t));
+                    std::memcpy(out_dist + q0 * k, h + q_pad + off_d, nb * k * sizeof(float));
+                }
+                if (out_count) std::memcpy(out_count + q0, h + q_pad + off_c, cb);
+            } else {
+                if (k) {
+                    VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                    VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
+                }
+                std::vector<uint64_t> cnt(nb);
+                VDB_HIP(hipMemcpyAsync(cnt.data(), d_out + off_c, cb, hipMemcpyDeviceToHost, s));
+                VDB_SYNC(s);
+                if (out_count) std::memcpy(out_count + q0, cnt.data(), cb);
+            }
+        }
+    });
+}
+
+// what every device-pointer k-NN call requires of its arguments
+static void check_device_args(const Index &ix, const void *d_queries, uint64_t nq, uint64_t dim, const void *d_out_idx, const void *d_out_dist,
+                              const void *d_out_count) {
+    check_query_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist);
+    VDB_REQUIRE(nq == 0 || d_out_count, "null out_count");
+    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
+}
+
+// device-pointer front end shared by all searches (queries and outputs already on the index's GPU); fn always gets q0 = 0.  (An entry
+// point with checks of its own behind these calls check_device_args itself first: the order of the refusals is part of the contract.)
+template <class Fn>
+static void device_search(Index &ix, const void *d_queries, uint64_t nq, uint64_t dim, void *d_out_idx, void *d_out_dist, void *d_out_count,
+                          void *stream, Fn &&fn) {
+    check_device_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count);
+    if (nq == 0) return;
+    ix.use_device();
+    WsLease ws(ix);
+    // order after whatever produced the queries on the caller's stream
+    VDB_SYNC(static_cast<hipStream_t>(stream));
+    run_synced(ix, *ws, [&] {
+        fn(*ws, static_cast<const float *>(d_queries), uint64_t(0), nq, static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist),
+           static_cast<uint64_t *>(d_out_count));
+        VDB_SYNC(ws->stream);
+    });
+}
+
+// exact Flat range search
+static void range_check(const Index &ix, const void *queries, uint64_t nq, uint64_t dim, const void *radius, vdb_range **out) {
+    VDB_REQUIRE(out, "null out");
+    *out = nullptr;
+    VDB_REQUIRE(dim == ix.dim, "query dimension mismatch: index dim " + std::to_string(ix.dim) + ", got " + std::to_string(dim));
+    VDB_REQUIRE(nq == 0 || (queries && radius), "null argument");
+    VDB_REQUIRE(nq < (1ull << 32), "too many queries for one call");
+}
+
+// the host forms' upload: [queries | radii] in ws.q -> the device pointers to the two (null without queries)
+struct RangeArgs {
+    const float *q = nullptr, *r = nullptr;
+};
+static RangeArgs stage_range_args(const Index &ix, Workspace &ws, const float *queries, const float *radius, uint64_t nq) {
+    if (nq == 0) return {};
+    const size_t qb = nq * ix.dim * sizeof(float), qb_pad = (qb + 255) & ~size_t(255);
+    ws.q.reserve(qb_pad + nq * sizeof(float));
+    VDB_HIP(hipMemcpyAsync(ws.q.p, queries, qb, hipMemcpyHostToDevice, ws.stream));
+    VDB_HIP(hipMemcpyAsync(ws.q.as<char>() + qb_pad, radius, nq * sizeof(float), hipMemcpyHostToDevice, ws.stream));
+    return {ws.q.as<float>(), reinterpret_cast<const float *>(ws.q.as<char>() + qb_pad)};
+}
+
+// runs body(RangeResult &) into a new vdb_range and hands that out when the body has succeeded
+template <class Body>
+static void range_call(Index &ix, Workspace &ws, vdb_range **out, Body &&body) {
+    std::unique_ptr<vdb_range> res(new vdb_range);
+    run_synced(ix, ws, [&] { body(res->r); });
+    *out = res.release();
+}
+
 extern "C" {
 
 const char *vdb_last_error(void) { return g_last_error.c_str(); }
@@ -289,74 +423,6 @@ int vdb_index_add_u8(vdb_index *idx, const uint8_t *rows, uint64_t n, uint64_t *
 }
 
 // ---- Flat ----------------------------------------------------------------------------------------
-static void check_query_args(const Index &ix, const void *queries, uint64_t nq, uint64_t dim, const void *out_idx,
-                             const void *out_dist) {
-    VDB_REQUIRE(dim == ix.dim, "query dimension mismatch: index dim " + std::to_string(ix.dim) + ", got " +
-                                   std::to_string(dim));
-    VDB_REQUIRE(nq == 0 || (queries && out_idx && out_dist), "null argument");
-}
-
-typedef void (*dev_search_fn)(Index &, Workspace &, const float *, uint64_t, uint64_t, uint64_t, uint64_t *, float *,
-                              uint64_t *);
-
-// host-pointer front end shared by all searches: stage queries, run, copy results back
-static void host_search(Index &ix, const float *queries, uint64_t nq, uint64_t k, uint64_t ef, uint64_t *out_idx,
-                        float *out_dist, uint64_t *out_count, dev_search_fn fn) {
-    if (nq == 0) return;
-    ix.use_device();
-    WsLease ws(ix);
-    hipStream_t s = ws->stream;
-    constexpr uint64_t CHUNK = 16384;
-    for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
-        uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
-        uint64_t kk = std::max<uint64_t>(k, 1);
-        // ONE device block for the three outputs [ids | distances | counts] and ONE pinned host block [queries | that block]:
-        // a call moves two async copies through page-locked memory instead of four pageable ones (each of which the runtime
-        // stages and waits for on its own) -- what a db.search()-shaped call of one query pays for besides its kernels
-        const size_t qb = nb * ix.dim * sizeof(float), ib = nb * kk * sizeof(uint64_t), db = nb * kk * sizeof(float), cb = nb * sizeof(uint64_t);
-        const size_t off_d = ib, off_c = (ib + db + 7) & ~size_t(7), ob = off_c + cb, q_pad = (qb + 15) & ~size_t(15);
-        const bool staged = q_pad + ob <= (size_t(8) << 20);
-        ws->q.reserve(qb);
-        ws->out_idx.reserve(ob);
-        char *d_out = ws->out_idx.as<char>();
-        char *h = staged ? static_cast<char *>(ws->pinned(q_pad + ob)) : nullptr;
-        if (staged) {
-            std::memcpy(h, queries + q0 * ix.dim, qb);
-            VDB_HIP(hipMemcpyAsync(ws->q.p, h, qb, hipMemcpyHostToDevice, s));
-        } else {
-            VDB_HIP(hipMemcpyAsync(ws->q.p, queries + q0 * ix.dim, qb, hipMemcpyHostToDevice, s));
-        }
-        fn(ix, *ws, ws->q.as<float>(), nb, k, ef, reinterpret_cast<uint64_t *>(d_out), reinterpret_cast<float *>(d_out + off_d),
-           reinterpret_cast<uint64_t *>(d_out + off_c));
-        // (fn may have used the pinned block for its own flags and has synchronised after reading them: the block is free again)
-        if (staged) {
-            h = static_cast<char *>(ws->pinned(q_pad + ob));
-            VDB_HIP(hipMemcpyAsync(h + q_pad, d_out, ob, hipMemcpyDeviceToHost, s));
-            VDB_SYNC(s);
-            if (k) {
-                std::memcpy(out_idx + q0 * k, h + q_pad, nb * k * sizeof(uint64_t));
-                std::memcpy(out_dist + q0 * k, h + q_pad + off_d, nb * k * sizeof(float));
-            }
-            if (out_count) std::memcpy(out_count + q0, h + q_pad + off_c, cb);
-        } else {
-            if (k) {
-                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
-            }
-            std::vector<uint64_t> cnt(nb);
-            VDB_HIP(hipMemcpyAsync(cnt.data(), d_out + off_c, cb, hipMemcpyDeviceToHost, s));
-            VDB_SYNC(s);
-            if (out_count) std::memcpy(out_count + q0, cnt.data(), cb);
-        }
-        ix.prof_collect(*ws);
-    }
-}
-
-static void flat_dev(Index &ix, Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t, uint64_t *d_idx,
-                     float *d_dist, uint64_t *d_cnt) {
-    ix.flat_knn_device(ws, d_q, nq, k, d_idx, d_dist, d_cnt);
-}
-
 int vdb_flat_knn(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t *out_idx,
                  float *out_dist, uint64_t *out_count) {
     VDB_API_BEGIN
@@ -390,25 +456,9 @@ int vdb_flat_knn(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim
         if (out_count) std::memcpy(out_count, h + off_c, nq * sizeof(uint64_t));
         return VDB_OK;
     }
-    host_search(idx->ix, queries, nq, k, 0, out_idx, out_dist, out_count, flat_dev);
+    host_search(ix, queries, nq, k, out_idx, out_dist, out_count,
+                [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { ix.flat_knn_device(w, q, nb, k, o...); });
     VDB_API_END
-}
-
-// device-pointer front end shared by all searches (queries and outputs already on the index's GPU)
-static void device_search(Index &ix, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t ef,
-                          void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream, dev_search_fn fn) {
-    check_query_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist);
-    VDB_REQUIRE(nq == 0 || d_out_count, "null out_count");
-    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
-    if (nq == 0) return;
-    ix.use_device();
-    WsLease ws(ix);
-    // order after whatever produced the queries on the caller's stream
-    VDB_SYNC(static_cast<hipStream_t>(stream));
-    fn(ix, *ws, static_cast<const float *>(d_queries), nq, k, ef, static_cast<uint64_t *>(d_out_idx),
-       static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
-    VDB_SYNC(ws->stream);
-    ix.prof_collect(*ws);
 }
 
 int vdb_flat_knn_u8(vdb_index *idx, const uint8_t *queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t *out_idx,
@@ -417,8 +467,10 @@ int vdb_flat_knn_u8(vdb_index *idx, const uint8_t *queries, uint64_t nq, uint64_
     VDB_REQUIRE(idx, "null index");
     VDB_REQUIRE(nq == 0 || queries, "null argument");
     std::vector<float> f = widen_u8(queries, nq * dim);
-    check_query_args(idx->ix, f.data(), nq, dim, out_idx, out_dist);
-    host_search(idx->ix, f.data(), nq, k, 0, out_idx, out_dist, out_count, flat_dev);
+    Index &ix = idx->ix;
+    check_query_args(ix, f.data(), nq, dim, out_idx, out_dist);
+    host_search(ix, f.data(), nq, k, out_idx, out_dist, out_count,
+                [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { ix.flat_knn_device(w, q, nb, k, o...); });
     VDB_API_END
 }
 
@@ -426,7 +478,9 @@ int vdb_flat_knn_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint
                         void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
-    device_search(idx->ix, d_queries, nq, dim, k, 0, d_out_idx, d_out_dist, d_out_count, stream, flat_dev);
+    Index &ix = idx->ix;
+    device_search(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count, stream,
+                  [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { ix.flat_knn_device(w, q, nb, k, o...); });
     VDB_API_END
 }
 
@@ -449,9 +503,7 @@ int vdb_flat_knn_device_begin(vdb_index *idx, const void *d_queries, uint64_t nq
     VDB_API_BEGIN
     VDB_REQUIRE(idx && out, "null argument");
     Index &ix = idx->ix;
-    check_query_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist);
-    VDB_REQUIRE(nq == 0 || d_out_count, "null out_count");
-    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
+    check_device_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count);
     ix.use_device();
     std::unique_ptr<vdb_pending> pd(new vdb_pending);
     pd->idx = idx;
@@ -493,40 +545,15 @@ int vdb_flat_knn_device_end(vdb_pending *pending) {
 }
 
 // ---- exact Flat range search -------------------------------------------------------------------------------------------------------
-static void range_check(const Index &ix, const void *queries, uint64_t nq, uint64_t dim, const void *radius, vdb_range **out) {
-    VDB_REQUIRE(out, "null out");
-    *out = nullptr;
-    VDB_REQUIRE(dim == ix.dim, "query dimension mismatch: index dim " + std::to_string(ix.dim) + ", got " + std::to_string(dim));
-    VDB_REQUIRE(nq == 0 || (queries && radius), "null argument");
-    VDB_REQUIRE(nq < (1ull << 32), "too many queries for one call");
-}
-
 int vdb_flat_range(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit, vdb_range **out) {
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
     Index &ix = idx->ix;
     range_check(ix, queries, nq, dim, radius, out);
     ix.use_device();
-    std::unique_ptr<vdb_range> res(new vdb_range);
     WsLease ws(ix);
-    const float *d_q = nullptr, *d_r = nullptr;
-    if (nq) {
-        const size_t qb = nq * dim * sizeof(float), qb_pad = (qb + 255) & ~size_t(255);
-        ws->q.reserve(qb_pad + nq * sizeof(float));  // [queries | radii]
-        VDB_HIP(hipMemcpyAsync(ws->q.p, queries, qb, hipMemcpyHostToDevice, ws->stream));
-        VDB_HIP(hipMemcpyAsync(ws->q.as<char>() + qb_pad, radius, nq * sizeof(float), hipMemcpyHostToDevice, ws->stream));
-        d_q = ws->q.as<float>();
-        d_r = reinterpret_cast<const float *>(ws->q.as<char>() + qb_pad);
-    }
-    try {
-        ix.flat_range_device(*ws, d_q, nq, d_r, limit, res->r);
-    } catch (...) {
-        (void)hipStreamSynchronize(ws->stream);  // nothing of a failed call is still running when its buffers go
-        ix.prof_collect(*ws);
-        throw;
-    }
-    ix.prof_collect(*ws);
-    *out = res.release();
+    const RangeArgs a = stage_range_args(ix, *ws, queries, radius, nq);
+    range_call(ix, *ws, out, [&](RangeResult &r) { ix.flat_range_device(*ws, a.q, nq, a.r, limit, r); });
     VDB_API_END
 }
 
@@ -537,18 +564,11 @@ int vdb_flat_range_device(vdb_index *idx, const void *d_queries, uint64_t nq, ui
     Index &ix = idx->ix;
     range_check(ix, d_queries, nq, dim, d_radius, out);
     ix.use_device();
-    std::unique_ptr<vdb_range> res(new vdb_range);
     WsLease ws(ix);
     VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
-    try {
-        ix.flat_range_device(*ws, static_cast<const float *>(d_queries), nq, static_cast<const float *>(d_radius), limit, res->r);
-    } catch (...) {
-        (void)hipStreamSynchronize(ws->stream);
-        ix.prof_collect(*ws);
-        throw;
-    }
-    ix.prof_collect(*ws);
-    *out = res.release();
+    range_call(ix, *ws, out, [&](RangeResult &r) {
+        ix.flat_range_device(*ws, static_cast<const float *>(d_queries), nq, static_cast<const float *>(d_radius), limit, r);
+    });
     VDB_API_END
 }
 
@@ -788,7 +808,7 @@ int vdb_mask_destroy(vdb_mask *m) {
 
 static void filtered_check(const Index &ix, const vdb_mask *mask) {
     VDB_REQUIRE(mask, "null mask");
-    VDB_REQUIRE(!ix.elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    require_f32_rows(ix);
     ix.check_mask(mask->m);
 }
 
@@ -799,36 +819,8 @@ int vdb_flat_knn_filtered(vdb_index *idx, const float *queries, uint64_t nq, uin
     Index &ix = idx->ix;
     check_query_args(ix, queries, nq, dim, out_idx, out_dist);
     filtered_check(ix, mask);
-    if (nq == 0) return VDB_OK;
-    ix.use_device();
-    WsLease ws(ix);
-    hipStream_t s = ws->stream;
-    constexpr uint64_t CHUNK = 16384;
-    const uint64_t kk = std::max<uint64_t>(k, 1), ch = std::min(nq, CHUNK);
-    // one device block for the outputs of a chunk [ids | distances | counts], as host_search lays them out
-    const size_t off_d = ch * kk * sizeof(uint64_t), off_c = (off_d + ch * kk * sizeof(float) + 7) & ~size_t(7);
-    ws->q.reserve(ch * dim * sizeof(float));
-    ws->out_idx.reserve(off_c + ch * sizeof(uint64_t));
-    char *d_out = ws->out_idx.as<char>();
-    try {
-        for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
-            const uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
-            VDB_HIP(hipMemcpyAsync(ws->q.p, queries + q0 * dim, nb * dim * sizeof(float), hipMemcpyHostToDevice, s));
-            ix.flat_knn_masked_device(*ws, ws->q.as<float>(), nb, k, mask->m, reinterpret_cast<uint64_t *>(d_out), reinterpret_cast<float *>(d_out + off_d),
-                                      reinterpret_cast<uint64_t *>(d_out + off_c));
-            if (k) {
-                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
-            }
-            if (out_count) VDB_HIP(hipMemcpyAsync(out_count + q0, d_out + off_c, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            VDB_SYNC(s);
-        }
-    } catch (...) {
-        (void)hipStreamSynchronize(s);  // nothing of a failed call is still running when its buffers go
-        ix.prof_collect(*ws);
-        throw;
-    }
-    ix.prof_collect(*ws);
+    host_search(ix, queries, nq, k, out_idx, out_dist, out_count,
+                [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { ix.flat_knn_masked_device(w, q, nb, k, mask->m, o...); });
     VDB_API_END
 }
 
@@ -837,30 +829,17 @@ int vdb_flat_knn_filtered_device(vdb_index *idx, const void *d_queries, uint64_t
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
     Index &ix = idx->ix;
-    check_query_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist);
-    VDB_REQUIRE(nq == 0 || d_out_count, "null out_count");
-    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
+    check_device_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count);
     filtered_check(ix, mask);
-    if (nq == 0) return VDB_OK;
-    ix.use_device();
-    WsLease ws(ix);
-    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
-    try {
-        ix.flat_knn_masked_device(*ws, static_cast<const float *>(d_queries), nq, k, mask->m, static_cast<uint64_t *>(d_out_idx),
-                                  static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
-    } catch (...) {
-        (void)hipStreamSynchronize(ws->stream);
-        ix.prof_collect(*ws);
-        throw;
-    }
-    ix.prof_collect(*ws);
+    device_search(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count, stream,
+                  [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { ix.flat_knn_masked_device(w, q, nb, k, mask->m, o...); });
     VDB_API_END
 }
 
 // one mask per query: everything that can be refused is refused here, before anything is computed or written; -> the masks as RowMask pointers
 static std::vector<const RowMask *> filtered_multi_check(const Index &ix, uint64_t nq, const vdb_mask *const *masks, uint64_t n_masks,
                                                          const uint32_t *mask_of, bool knn = true) {
-    VDB_REQUIRE(!knn || !ix.elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    if (knn) require_f32_rows(ix);
     VDB_REQUIRE(n_masks == 0 || masks, "null masks");
     VDB_REQUIRE(nq == 0 || mask_of, "null mask_of");
     VDB_REQUIRE(n_masks < (1ull << 32), "too many masks");
@@ -876,6 +855,7 @@ static std::vector<const RowMask *> filtered_multi_check(const Index &ix, uint64
     return rm;
 }
 
+// (the checks and the call counter stay in front of the shared front end: they hold for a call without queries too)
 int vdb_flat_knn_filtered_multi(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, const vdb_mask *const *masks,
                                 uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx, float *out_dist, uint64_t *out_count) {
     VDB_API_BEGIN
@@ -884,36 +864,9 @@ int vdb_flat_knn_filtered_multi(vdb_index *idx, const float *queries, uint64_t n
     check_query_args(ix, queries, nq, dim, out_idx, out_dist);
     const std::vector<const RowMask *> rm = filtered_multi_check(ix, nq, masks, n_masks, mask_of);
     ix.filtered_multi_calls++;
-    if (nq == 0) return VDB_OK;
-    ix.use_device();
-    WsLease ws(ix);
-    hipStream_t s = ws->stream;
-    constexpr uint64_t CHUNK = 16384;
-    const uint64_t kk = std::max<uint64_t>(k, 1), ch = std::min(nq, CHUNK);
-    // one device block for the outputs of a chunk [ids | distances | counts], as vdb_flat_knn_filtered lays them out
-    const size_t off_d = ch * kk * sizeof(uint64_t), off_c = (off_d + ch * kk * sizeof(float) + 7) & ~size_t(7);
-    ws->q.reserve(ch * dim * sizeof(float));
-    ws->out_idx.reserve(off_c + ch * sizeof(uint64_t));
-    char *d_out = ws->out_idx.as<char>();
-    try {
-        for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
-            const uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
-            VDB_HIP(hipMemcpyAsync(ws->q.p, queries + q0 * dim, nb * dim * sizeof(float), hipMemcpyHostToDevice, s));
-            ix.flat_knn_masked_multi_device(*ws, ws->q.as<float>(), nb, k, rm.data(), n_masks, mask_of + q0, reinterpret_cast<uint64_t *>(d_out),
-                                            reinterpret_cast<float *>(d_out + off_d), reinterpret_cast<uint64_t *>(d_out + off_c));
-            if (k) {
-                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
-            }
-            if (out_count) VDB_HIP(hipMemcpyAsync(out_count + q0, d_out + off_c, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            VDB_SYNC(s);
-        }
-    } catch (...) {
-        (void)hipStreamSynchronize(s);  // nothing of a failed call is still running when its buffers go
-        ix.prof_collect(*ws);
-        throw;
-    }
-    ix.prof_collect(*ws);
+    host_search(ix, queries, nq, k, out_idx, out_dist, out_count, [&](Workspace &w, const float *q, uint64_t q0, uint64_t nb, auto... o) {
+        ix.flat_knn_masked_multi_device(w, q, nb, k, rm.data(), n_masks, mask_of + q0, o...);
+    });
     VDB_API_END
 }
 
@@ -922,24 +875,12 @@ int vdb_flat_knn_filtered_multi_device(vdb_index *idx, const void *d_queries, ui
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
     Index &ix = idx->ix;
-    check_query_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist);
-    VDB_REQUIRE(nq == 0 || d_out_count, "null out_count");
-    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
+    check_device_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count);
     const std::vector<const RowMask *> rm = filtered_multi_check(ix, nq, masks, n_masks, mask_of);
     ix.filtered_multi_calls++;
-    if (nq == 0) return VDB_OK;
-    ix.use_device();
-    WsLease ws(ix);
-    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
-    try {
-        ix.flat_knn_masked_multi_device(*ws, static_cast<const float *>(d_queries), nq, k, rm.data(), n_masks, mask_of, static_cast<uint64_t *>(d_out_idx),
-                                        static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
-    } catch (...) {
-        (void)hipStreamSynchronize(ws->stream);
-        ix.prof_collect(*ws);
-        throw;
-    }
-    ix.prof_collect(*ws);
+    device_search(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count, stream, [&](Workspace &w, const float *q, uint64_t q0, uint64_t nb, auto... o) {
+        ix.flat_knn_masked_multi_device(w, q, nb, k, rm.data(), n_masks, mask_of + q0, o...);
+    });
     VDB_API_END
 }
 
@@ -949,7 +890,7 @@ static std::vector<const RowMask *> grouped_check(const Index &ix, uint64_t nq, 
                                                   uint64_t n_masks, const uint32_t *mask_of) {
     VDB_REQUIRE(group_size >= 1, "grouped k-NN: group_size must be at least 1");
     VDB_REQUIRE(column < LABEL_COLUMNS, "grouped k-NN: column " + std::to_string(column) + ", an index has " + std::to_string(LABEL_COLUMNS));
-    VDB_REQUIRE(!ix.elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    require_f32_rows(ix);
     if (n_masks == 0) return {};
     return filtered_multi_check(ix, nq, masks, n_masks, mask_of);
 }
@@ -963,36 +904,9 @@ int vdb_flat_knn_grouped(vdb_index *idx, const float *queries, uint64_t nq, uint
     check_query_args(ix, queries, nq, dim, out_idx, out_dist);
     const std::vector<const RowMask *> rm = grouped_check(ix, nq, column, group_size, masks, n_masks, mask_of);
     ix.grouped_calls++;
-    if (nq == 0) return VDB_OK;
-    ix.use_device();
-    WsLease ws(ix);
-    hipStream_t s = ws->stream;
-    constexpr uint64_t CHUNK = 16384;
-    const uint64_t kk = std::max<uint64_t>(k, 1), ch = std::min(nq, CHUNK);
-    // one device block for the outputs of a chunk [ids | distances | counts], as vdb_flat_knn_filtered lays them out
-    const size_t off_d = ch * kk * sizeof(uint64_t), off_c = (off_d + ch * kk * sizeof(float) + 7) & ~size_t(7);
-    ws->q.reserve(ch * dim * sizeof(float));
-    ws->out_idx.reserve(off_c + ch * sizeof(uint64_t));
-    char *d_out = ws->out_idx.as<char>();
-    try {
-        for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
-            const uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
-            VDB_HIP(hipMemcpyAsync(ws->q.p, queries + q0 * dim, nb * dim * sizeof(float), hipMemcpyHostToDevice, s));
-            ix.flat_knn_grouped_device(*ws, ws->q.as<float>(), nb, k, column, group_size, rm.data(), n_masks, n_masks ? mask_of + q0 : nullptr,
-                                       reinterpret_cast<uint64_t *>(d_out), reinterpret_cast<float *>(d_out + off_d), reinterpret_cast<uint64_t *>(d_out + off_c));
-            if (k) {
-                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
-            }
-            if (out_count) VDB_HIP(hipMemcpyAsync(out_count + q0, d_out + off_c, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            VDB_SYNC(s);
-        }
-    } catch (...) {
-        (void)hipStreamSynchronize(s);  // nothing of a failed call is still running when its buffers go
-        ix.prof_collect(*ws);
-        throw;
-    }
-    ix.prof_collect(*ws);
+    host_search(ix, queries, nq, k, out_idx, out_dist, out_count, [&](Workspace &w, const float *q, uint64_t q0, uint64_t nb, auto... o) {
+        ix.flat_knn_grouped_device(w, q, nb, k, column, group_size, rm.data(), n_masks, n_masks ? mask_of + q0 : nullptr, o...);
+    });
     VDB_API_END
 }
 
@@ -1002,24 +916,12 @@ int vdb_flat_knn_grouped_device(vdb_index *idx, const void *d_queries, uint64_t 
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
     Index &ix = idx->ix;
-    check_query_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist);
-    VDB_REQUIRE(nq == 0 || d_out_count, "null out_count");
-    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
+    check_device_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count);
     const std::vector<const RowMask *> rm = grouped_check(ix, nq, column, group_size, masks, n_masks, mask_of);
     ix.grouped_calls++;
-    if (nq == 0) return VDB_OK;
-    ix.use_device();
-    WsLease ws(ix);
-    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
-    try {
-        ix.flat_knn_grouped_device(*ws, static_cast<const float *>(d_queries), nq, k, column, group_size, rm.data(), n_masks, n_masks ? mask_of : nullptr,
-                                   static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
-    } catch (...) {
-        (void)hipStreamSynchronize(ws->stream);
-        ix.prof_collect(*ws);
-        throw;
-    }
-    ix.prof_collect(*ws);
+    device_search(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count, stream, [&](Workspace &w, const float *q, uint64_t q0, uint64_t nb, auto... o) {
+        ix.flat_knn_grouped_device(w, q, nb, k, column, group_size, rm.data(), n_masks, n_masks ? mask_of + q0 : nullptr, o...);
+    });
     VDB_API_END
 }
 
@@ -1055,45 +957,13 @@ int vdb_flat_range_filtered(vdb_index *idx, const float *queries, uint64_t nq, u
     VDB_REQUIRE(mask, "null mask");
     ix.check_mask(mask->m);
     ix.use_device();
-    std::unique_ptr<vdb_range> res(new vdb_range);
     WsLease ws(ix);
-    const float *d_q = nullptr, *d_r = nullptr;
-    if (nq) {
-        const size_t qb = nq * dim * sizeof(float), qb_pad = (qb + 255) & ~size_t(255);
-        ws->q.reserve(qb_pad + nq * sizeof(float));  // [queries | radii]
-        VDB_HIP(hipMemcpyAsync(ws->q.p, queries, qb, hipMemcpyHostToDevice, ws->stream));
-        VDB_HIP(hipMemcpyAsync(ws->q.as<char>() + qb_pad, radius, nq * sizeof(float), hipMemcpyHostToDevice, ws->stream));
-        d_q = ws->q.as<float>();
-        d_r = reinterpret_cast<const float *>(ws->q.as<char>() + qb_pad);
-    }
-    try {
-        ix.flat_range_device(*ws, d_q, nq, d_r, limit, res->r, &mask->m);
-    } catch (...) {
-        (void)hipStreamSynchronize(ws->stream);  // nothing of a failed call is still running when its buffers go
-        ix.prof_collect(*ws);
-        throw;
-    }
-    ix.prof_collect(*ws);
-    *out = res.release();
+    const RangeArgs a = stage_range_args(ix, *ws, queries, radius, nq);
+    range_call(ix, *ws, out, [&](RangeResult &r) { ix.flat_range_device(*ws, a.q, nq, a.r, limit, r, &mask->m); });
     VDB_API_END
 }
 
-// one mask per query (Index::flat_range_masked_multi_device): the host form uploads queries and radii and runs the device form's body
-static void range_filtered_multi_body(Index &ix, Workspace &ws, const float *d_q, uint64_t nq, const float *d_r, uint64_t limit,
-                                      const std::vector<const RowMask *> &rm, const uint32_t *mask_of, vdb_range **out) {
-    std::unique_ptr<vdb_range> res(new vdb_range);
-    try {
-        ix.flat_range_masked_multi_device(ws, d_q, nq, d_r, limit, rm.data(), rm.size(), mask_of, res->r);
-    } catch (...) {
-        (void)hipStreamSynchronize(ws.stream);  // nothing of a failed call is still running when its buffers go
-        ix.prof_collect(ws);
-        throw;
-    }
-    ix.prof_collect(ws);
-    ix.range_multi_calls++;
-    *out = res.release();
-}
-
+// one mask per query (Index::flat_range_masked_multi_device); the call counter moves when the call has succeeded
 int vdb_flat_range_filtered_multi(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit,
                                   const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, vdb_range **out) {
     VDB_API_BEGIN
@@ -1103,16 +973,9 @@ int vdb_flat_range_filtered_multi(vdb_index *idx, const float *queries, uint64_t
     const std::vector<const RowMask *> rm = filtered_multi_check(ix, nq, masks, n_masks, mask_of, false);
     ix.use_device();
     WsLease ws(ix);
-    const float *d_q = nullptr, *d_r = nullptr;
-    if (nq) {
-        const size_t qb = nq * dim * sizeof(float), qb_pad = (qb + 255) & ~size_t(255);
-        ws->q.reserve(qb_pad + nq * sizeof(float));  // [queries | radii]
-        VDB_HIP(hipMemcpyAsync(ws->q.p, queries, qb, hipMemcpyHostToDevice, ws->stream));
-        VDB_HIP(hipMemcpyAsync(ws->q.as<char>() + qb_pad, radius, nq * sizeof(float), hipMemcpyHostToDevice, ws->stream));
-        d_q = ws->q.as<float>();
-        d_r = reinterpret_cast<const float *>(ws->q.as<char>() + qb_pad);
-    }
-    range_filtered_multi_body(ix, *ws, d_q, nq, d_r, limit, rm, mask_of, out);
+    const RangeArgs a = stage_range_args(ix, *ws, queries, radius, nq);
+    range_call(ix, *ws, out, [&](RangeResult &r) { ix.flat_range_masked_multi_device(*ws, a.q, nq, a.r, limit, rm.data(), rm.size(), mask_of, r); });
+    ix.range_multi_calls++;
     VDB_API_END
 }
 
@@ -1127,7 +990,11 @@ int vdb_flat_range_filtered_multi_device(vdb_index *idx, const void *d_queries, 
     ix.use_device();
     WsLease ws(ix);
     VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
-    range_filtered_multi_body(ix, *ws, static_cast<const float *>(d_queries), nq, static_cast<const float *>(d_radius), limit, rm, mask_of, out);
+    range_call(ix, *ws, out, [&](RangeResult &r) {
+        ix.flat_range_masked_multi_device(*ws, static_cast<const float *>(d_queries), nq, static_cast<const float *>(d_radius), limit, rm.data(), rm.size(),
+                                          mask_of, r);
+    });
+    ix.range_multi_calls++;
     VDB_API_END
 }
 
@@ -1466,17 +1333,15 @@ int vdb_pq_export(const vdb_index *idx, float *centroids, uint8_t *codes) {
     VDB_API_END
 }
 
-static void flat_pq_dev(Index &ix, Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t ef,
-                        uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
-    flat_knn_pq_device(ix, ws, d_q, nq, k, ef, d_idx, d_dist, d_cnt);
-}
 int vdb_flat_knn_pq(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t ef,
                     uint64_t *out_idx, float *out_dist, uint64_t *out_count) {
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
-    check_query_args(idx->ix, queries, nq, dim, out_idx, out_dist);
-    VDB_REQUIRE(idx->ix.pq.present, "knn_pq needs a PQ table (vdb_pq_build / vdb_pq_attach)");
-    host_search(idx->ix, queries, nq, k, ef, out_idx, out_dist, out_count, flat_pq_dev);
+    Index &ix = idx->ix;
+    check_query_args(ix, queries, nq, dim, out_idx, out_dist);
+    VDB_REQUIRE(ix.pq.present, "knn_pq needs a PQ table (vdb_pq_build / vdb_pq_attach)");
+    host_search(ix, queries, nq, k, out_idx, out_dist, out_count,
+                [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { flat_knn_pq_device(ix, w, q, nb, k, ef, o...); });
     VDB_API_END
 }
 
@@ -1484,8 +1349,10 @@ int vdb_flat_knn_pq_device(vdb_index *idx, const void *d_queries, uint64_t nq, u
                            void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
-    VDB_REQUIRE(idx->ix.pq.present, "knn_pq needs a PQ table (vdb_pq_build / vdb_pq_attach)");
-    device_search(idx->ix, d_queries, nq, dim, k, ef, d_out_idx, d_out_dist, d_out_count, stream, flat_pq_dev);
+    Index &ix = idx->ix;
+    VDB_REQUIRE(ix.pq.present, "knn_pq needs a PQ table (vdb_pq_build / vdb_pq_attach)");
+    device_search(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count, stream,
+                  [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { flat_knn_pq_device(ix, w, q, nb, k, ef, o...); });
     VDB_API_END
 }
 
@@ -1658,18 +1525,16 @@ int vdb_ivf_export(vdb_index *idx, float *centroids, uint64_t *assign) {
     ivf_export(idx->ix, centroids, assign);
     VDB_API_END
 }
-static void ivf_dev(Index &ix, Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t n_probes,
-                    uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
-    ivf_knn_device(ix, ws, d_q, nq, k, n_probes, d_idx, d_dist, d_cnt);
-}
 int vdb_ivf_knn(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t n_probes,
                 uint64_t *out_idx, float *out_dist, uint64_t *out_count) {
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
-    check_query_args(idx->ix, queries, nq, dim, out_idx, out_dist);
-    VDB_REQUIRE(idx->ix.ivf.present, "knn needs an IVF index (vdb_ivf_build / vdb_ivf_attach)");
-    if (n_probes == 0) n_probes = idx->ix.ivf.default_n_probes;
-    host_search(idx->ix, queries, nq, k, n_probes, out_idx, out_dist, out_count, ivf_dev);
+    Index &ix = idx->ix;
+    check_query_args(ix, queries, nq, dim, out_idx, out_dist);
+    VDB_REQUIRE(ix.ivf.present, "knn needs an IVF index (vdb_ivf_build / vdb_ivf_attach)");
+    if (n_probes == 0) n_probes = ix.ivf.default_n_probes;
+    host_search(ix, queries, nq, k, out_idx, out_dist, out_count,
+                [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { ivf_knn_device(ix, w, q, nb, k, n_probes, o...); });
     VDB_API_END
 }
 
@@ -1677,9 +1542,11 @@ int vdb_ivf_knn_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint6
                        void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
-    VDB_REQUIRE(idx->ix.ivf.present, "knn needs an IVF index (vdb_ivf_build / vdb_ivf_attach)");
-    if (n_probes == 0) n_probes = idx->ix.ivf.default_n_probes;
-    device_search(idx->ix, d_queries, nq, dim, k, n_probes, d_out_idx, d_out_dist, d_out_count, stream, ivf_dev);
+    Index &ix = idx->ix;
+    VDB_REQUIRE(ix.ivf.present, "knn needs an IVF index (vdb_ivf_build / vdb_ivf_attach)");
+    if (n_probes == 0) n_probes = ix.ivf.default_n_probes;
+    device_search(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count, stream,
+                  [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { ivf_knn_device(ix, w, q, nb, k, n_probes, o...); });
     VDB_API_END
 }
 
@@ -1741,43 +1608,40 @@ int vdb_hnsw_export(const vdb_index *idx, uint32_t *level0, uint64_t *len0, uint
     VDB_API_END
 }
 
-static void hnsw_dev(Index &ix, Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t ef,
-                     uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
-    hnsw_knn_device(ix, ws, d_q, nq, k, ef, false, d_idx, d_dist, d_cnt);
-}
-static void hnsw_pq_dev(Index &ix, Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t ef,
-                        uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
-    hnsw_knn_device(ix, ws, d_q, nq, k, ef, true, d_idx, d_dist, d_cnt);
-}
 int vdb_hnsw_knn(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t ef,
                  uint64_t *out_idx, float *out_dist, uint64_t *out_count) {
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
-    check_query_args(idx->ix, queries, nq, dim, out_idx, out_dist);
-    VDB_REQUIRE(idx->ix.hnsw.present, "knn_with_ef needs an HNSW graph (vdb_hnsw_build / vdb_hnsw_attach)");
-    if (ef == 0) ef = idx->ix.hnsw.default_ef;
-    host_search(idx->ix, queries, nq, k, ef, out_idx, out_dist, out_count, hnsw_dev);
+    Index &ix = idx->ix;
+    check_query_args(ix, queries, nq, dim, out_idx, out_dist);
+    VDB_REQUIRE(ix.hnsw.present, "knn_with_ef needs an HNSW graph (vdb_hnsw_build / vdb_hnsw_attach)");
+    if (ef == 0) ef = ix.hnsw.default_ef;
+    host_search(ix, queries, nq, k, out_idx, out_dist, out_count,
+                [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { hnsw_knn_device(ix, w, q, nb, k, ef, false, o...); });
     VDB_API_END
 }
 int vdb_hnsw_knn_pq(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t ef,
                     uint64_t *out_idx, float *out_dist, uint64_t *out_count) {
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
-    check_query_args(idx->ix, queries, nq, dim, out_idx, out_dist);
-    VDB_REQUIRE(idx->ix.hnsw.present, "knn_pq needs an HNSW graph");
-    VDB_REQUIRE(idx->ix.pq.present, "knn_pq needs a PQ table");
-    host_search(idx->ix, queries, nq, k, ef, out_idx, out_dist, out_count, hnsw_pq_dev);
+    Index &ix = idx->ix;
+    check_query_args(ix, queries, nq, dim, out_idx, out_dist);
+    VDB_REQUIRE(ix.hnsw.present, "knn_pq needs an HNSW graph");
+    VDB_REQUIRE(ix.pq.present, "knn_pq needs a PQ table");
+    host_search(ix, queries, nq, k, out_idx, out_dist, out_count,
+                [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { hnsw_knn_device(ix, w, q, nb, k, ef, true, o...); });
     VDB_API_END
 }
 int vdb_hnsw_knn_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t ef,
                         int use_pq, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
-    VDB_REQUIRE(idx->ix.hnsw.present, "knn_with_ef needs an HNSW graph (vdb_hnsw_build / vdb_hnsw_attach)");
-    VDB_REQUIRE(!use_pq || idx->ix.pq.present, "knn_pq needs a PQ table");
-    if (ef == 0) ef = idx->ix.hnsw.default_ef;
-    device_search(idx->ix, d_queries, nq, dim, k, ef, d_out_idx, d_out_dist, d_out_count, stream,
-                  use_pq ? hnsw_pq_dev : hnsw_dev);
+    Index &ix = idx->ix;
+    VDB_REQUIRE(ix.hnsw.present, "knn_with_ef needs an HNSW graph (vdb_hnsw_build / vdb_hnsw_attach)");
+    VDB_REQUIRE(!use_pq || ix.pq.present, "knn_pq needs a PQ table");
+    if (ef == 0) ef = ix.hnsw.default_ef;
+    device_search(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count, stream,
+                  [&](Workspace &w, const float *q, uint64_t, uint64_t nb, auto... o) { hnsw_knn_device(ix, w, q, nb, k, ef, use_pq != 0, o...); });
     VDB_API_END
 }
 int vdb_hnsw_last_stats(const vdb_index *idx, uint64_t *n_dist, uint64_t *n_expanded) {

@@ -1692,7 +1692,7 @@ void Index::flat_knn_masked_device(Workspace &ws, const float *d_q, uint64_t nq,
                                    uint64_t *d_cnt) {
     hipStream_t s = ws.stream;
     check_mask(mask);
-    VDB_REQUIRE(!elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    require_f32_rows(*this);
     filtered_queries += nq;
     if (nq == 0) return;
     const uint64_t m = mask.m;
@@ -1760,6 +1760,84 @@ void Index::flat_knn_masked_device(Workspace &ws, const float *d_q, uint64_t nq,
     r.scatter(d_idx, d_dist, d_cnt, s);  // (its sync: before `redo` goes out of scope)
 }
 
+// ---- shared by the two searches with one row mask per query (k-NN and range, below) ------------------------------------------------------
+// The rows of every mask, which masks take the grouped route (grouped_if(m)), and for every other mask the positions of its queries in
+// the call: the buckets of the per-mask route.
+namespace {
+struct MaskRoutes {
+    std::vector<uint64_t> m_of;
+    std::vector<uint8_t> grouped;
+    std::vector<std::vector<uint64_t>> bucket;
+};
+template <class Pred>
+MaskRoutes mask_routes(const RowMask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint64_t nq, Pred grouped_if) {
+    MaskRoutes r;
+    r.m_of = std::vector<uint64_t>(n_masks);
+    r.grouped = std::vector<uint8_t>(n_masks);
+    r.bucket = std::vector<std::vector<uint64_t>>(n_masks);
+    for (uint64_t g = 0; g < n_masks; g++) {
+        r.m_of[g] = masks[g]->m;
+        r.grouped[g] = grouped_if(r.m_of[g]);
+    }
+    for (uint64_t q = 0; q < nq; q++)
+        if (!r.grouped[mask_of[q]]) r.bucket[mask_of[q]].push_back(q);
+    return r;
+}
+
+// The device image of a MultiPlan in ws.misc, one reserve and one upload for the call: [slot_ids (8 B) | items (24 B) | slot_q | slot_m |
+// slot_c], the 8-byte members first.  with_ids: the id list and m of every slot's mask (what the k-NN finalize reads); with_counters: a
+// zeroed u32 per slot (what the range gather counts into).  The image owns the host arrays it uploads from -- pageable memory: keep it (and
+// the plan, whose slot_query is uploaded as it stands) alive until the call's final stream sync.
+struct PlanImage {
+    const uint32_t *const *slot_ids = nullptr;
+    const GroupedItem *items = nullptr;
+    const uint32_t *slot_q = nullptr, *slot_m = nullptr;
+    uint32_t *slot_c = nullptr;
+    std::vector<GroupedItem> h_items;
+    std::vector<const uint32_t *> h_ids;
+    std::vector<uint32_t> h_m;
+};
+PlanImage plan_image(Workspace &ws, const MultiPlan &plan, const RowMask *const *masks, const std::vector<uint64_t> &m_of, bool with_ids,
+                            bool with_counters) {
+    hipStream_t s = ws.stream;
+    PlanImage im;
+    const uint64_t ns = plan.slot_query.size();
+    im.h_items = std::vector<GroupedItem>(plan.items.size());
+    for (size_t i = 0; i < im.h_items.size(); i++) {
+        const MultiItem &it = plan.items[i];
+        im.h_items[i] = GroupedItem{masks[it.mask]->d_ids.as<uint32_t>(), (uint32_t)m_of[it.mask], it.tile, it.slot, it.nb};
+    }
+    if (with_ids) {
+        im.h_ids = std::vector<const uint32_t *>(ns);
+        im.h_m = std::vector<uint32_t>(ns);
+        for (uint64_t i = 0; i < ns; i++) {
+            im.h_ids[i] = masks[plan.slot_mask[i]]->d_ids.as<uint32_t>();
+            im.h_m[i] = (uint32_t)m_of[plan.slot_mask[i]];
+        }
+    }
+    static_assert(sizeof(GroupedItem) % 8 == 0, "the items follow the pointer array");
+    const size_t sb = ns * sizeof(uint32_t), off_items = with_ids ? ns * sizeof(uint32_t *) : 0, off_q = off_items + im.h_items.size() * sizeof(GroupedItem);
+    const size_t off_m = off_q + sb, off_c = off_m + (with_ids ? sb : 0);
+    ws.misc.reserve(off_c + (with_counters ? sb : 0));
+    char *d = ws.misc.as<char>();
+    if (!im.h_items.empty()) VDB_HIP(hipMemcpyAsync(d + off_items, im.h_items.data(), im.h_items.size() * sizeof(GroupedItem), hipMemcpyHostToDevice, s));
+    VDB_HIP(hipMemcpyAsync(d + off_q, plan.slot_query.data(), sb, hipMemcpyHostToDevice, s));
+    im.items = reinterpret_cast<const GroupedItem *>(d + off_items);
+    im.slot_q = reinterpret_cast<const uint32_t *>(d + off_q);
+    if (with_ids) {
+        VDB_HIP(hipMemcpyAsync(d, im.h_ids.data(), ns * sizeof(uint32_t *), hipMemcpyHostToDevice, s));
+        VDB_HIP(hipMemcpyAsync(d + off_m, im.h_m.data(), sb, hipMemcpyHostToDevice, s));
+        im.slot_ids = reinterpret_cast<const uint32_t *const *>(d);
+        im.slot_m = reinterpret_cast<const uint32_t *>(d + off_m);
+    }
+    if (with_counters) {
+        VDB_HIP(hipMemsetAsync(d + off_c, 0, sb, s));
+        im.slot_c = reinterpret_cast<uint32_t *>(d + off_c);
+    }
+    return im;
+}
+}  // namespace
+
 // ---- Flat: exact filtered k-NN with one row mask per query (k_filter.hip, multi_plan.hpp) ------------------------------------------------
 // Query q is answered as flat_knn_masked_device answers it alone under masks[mask_of[q]].  The queries are bucketed by mask on the host:
 //   per-mask route: a bucket whose mask is longer than flat_filtered_direct_max (or any bucket when k > 1024) is gathered into a block of
@@ -1776,7 +1854,7 @@ void Index::flat_knn_masked_device(Workspace &ws, const float *d_q, uint64_t nq,
 void Index::flat_knn_masked_multi_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, const RowMask *const *masks, uint64_t n_masks,
                                          const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
     hipStream_t s = ws.stream;
-    VDB_REQUIRE(!elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    require_f32_rows(*this);
     if (nq == 0) return;
     VDB_REQUIRE(nq < (1ull << 32) && k < (1ull << 31), "flat knn: too many queries or k too large");
     if (k == 0) {
@@ -1786,53 +1864,28 @@ void Index::flat_knn_masked_multi_device(Workspace &ws, const float *d_q, uint64
         VDB_SYNC(s);
         return;
     }
-    std::vector<uint64_t> m_of(n_masks);
-    std::vector<uint8_t> grouped(n_masks);
-    for (uint64_t g = 0; g < n_masks; g++) {
-        m_of[g] = masks[g]->m;
-        grouped[g] = k <= 1024 && m_of[g] <= flat_filtered_direct_max;
-    }
+    const MaskRoutes rt = mask_routes(masks, n_masks, mask_of, nq, [&](uint64_t m) { return k <= 1024 && m <= flat_filtered_direct_max; });
     // per-mask route first: every such call returns synchronised, so the grouped route's reserves below free nothing in use
-    {
-        std::vector<std::vector<uint64_t>> bucket(n_masks);
-        for (uint64_t q = 0; q < nq; q++)
-            if (!grouped[mask_of[q]]) bucket[mask_of[q]].push_back(q);
-        for (uint64_t g = 0; g < n_masks; g++) {
-            if (bucket[g].empty()) continue;
-            RedoSet r(bucket[g], d_q, dim, k, s);
-            VDB_HIP(hipMemsetAsync(r.rc.p, 0, r.nr * sizeof(uint64_t), s));
-            flat_knn_masked_device(ws, r.rq.as<float>(), r.nr, k, *masks[g], r.ri.as<uint64_t>(), r.rd.as<float>(), r.rc.as<uint64_t>());
-            r.scatter(d_idx, d_dist, d_cnt, s);
-        }
+    for (uint64_t g = 0; g < n_masks; g++) {
+        if (rt.bucket[g].empty()) continue;
+        RedoSet r(rt.bucket[g], d_q, dim, k, s);
+        VDB_HIP(hipMemsetAsync(r.rc.p, 0, r.nr * sizeof(uint64_t), s));
+        flat_knn_masked_device(ws, r.rq.as<float>(), r.nr, k, *masks[g], r.ri.as<uint64_t>(), r.rd.as<float>(), r.rc.as<uint64_t>());
+        r.scatter(d_idx, d_dist, d_cnt, s);
     }
-    const uint64_t max_m = multi_plan_max_m(m_of.data(), grouped.data(), n_masks, mask_of, nq);
+    const uint64_t max_m = multi_plan_max_m(rt.m_of.data(), rt.grouped.data(), n_masks, mask_of, nq);
     const uint64_t ksel_all = std::min<uint64_t>(k, max_m);
     const uint64_t list_bytes = ksel_all ? uint64_t(topk_num_lists(max_m)) * topk_capacity((uint32_t)ksel_all) * sizeof(uint64_t) : 64;
     constexpr uint64_t BUDGET = 256ull << 20;  // bytes of the dense matrix (and of the selection's lists) per chunk, as in flat_masked_direct
     MultiPlan plan;
-    multi_plan(m_of.data(), grouped.data(), n_masks, mask_of, nq, BUDGET, list_bytes, plan);
+    multi_plan(rt.m_of.data(), rt.grouped.data(), n_masks, mask_of, nq, BUDGET, list_bytes, plan);
     const uint64_t ns = plan.slot_query.size();
     if (ns == 0) return;
     filtered_queries += ns;
     filtered_direct_queries += ns;
     filtered_grouped_queries += ns;
     const int metric = dist == 0 ? MET_L2_DIRECT : MET_COSINE;
-    // device image of the plan: [slot_ids (8 B) | items (24 B) | slot_q | slot_m], one upload for the call
-    std::vector<GroupedItem> h_items(plan.items.size());
-    for (size_t i = 0; i < h_items.size(); i++) {
-        const MultiItem &it = plan.items[i];
-        h_items[i] = GroupedItem{masks[it.mask]->d_ids.as<uint32_t>(), (uint32_t)m_of[it.mask], it.tile, it.slot, it.nb};
-    }
-    std::vector<const uint32_t *> h_ids(ns);
-    std::vector<uint32_t> h_m(ns);
-    for (uint64_t i = 0; i < ns; i++) {
-        h_ids[i] = masks[plan.slot_mask[i]]->d_ids.as<uint32_t>();
-        h_m[i] = (uint32_t)m_of[plan.slot_mask[i]];
-    }
-    static_assert(sizeof(GroupedItem) % 8 == 0, "the items follow the pointer array");
-    const size_t off_items = ns * sizeof(uint32_t *), off_q = off_items + h_items.size() * sizeof(GroupedItem), off_m = off_q + ns * sizeof(uint32_t);
-    // every buffer of the call reserved before its first launch (a later, larger reserve would free a buffer in use)
-    ws.misc.reserve(off_m + ns * sizeof(uint32_t));
+    // every buffer of the call reserved before its first launch (a later, larger reserve would free a buffer in use); ws.misc: plan_image
     ws.qsq.reserve(nq * sizeof(float));
     const uint64_t ld_all = (max_m + 63) & ~63ull;
     const uint64_t qch = std::min(plan.qch, ns);
@@ -1841,14 +1894,7 @@ void Index::flat_knn_masked_multi_device(Workspace &ws, const float *d_q, uint64
         ws.lists.reserve(qch * list_bytes);
         ws.keys_c.reserve(qch * topk_capacity((uint32_t)ksel_all) * sizeof(uint64_t));
     }
-    char *d_plan = ws.misc.as<char>();
-    VDB_HIP(hipMemcpyAsync(d_plan, h_ids.data(), ns * sizeof(uint32_t *), hipMemcpyHostToDevice, s));
-    if (!h_items.empty()) VDB_HIP(hipMemcpyAsync(d_plan + off_items, h_items.data(), h_items.size() * sizeof(GroupedItem), hipMemcpyHostToDevice, s));
-    VDB_HIP(hipMemcpyAsync(d_plan + off_q, plan.slot_query.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    VDB_HIP(hipMemcpyAsync(d_plan + off_m, h_m.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    const uint32_t *const *d_slot_ids = reinterpret_cast<const uint32_t *const *>(d_plan);
-    const GroupedItem *d_items = reinterpret_cast<const GroupedItem *>(d_plan + off_items);
-    const uint32_t *d_slot_q = reinterpret_cast<const uint32_t *>(d_plan + off_q), *d_slot_m = reinterpret_cast<const uint32_t *>(d_plan + off_m);
+    const PlanImage im = plan_image(ws, plan, masks, rt.m_of, true, false);
     launch_row_sqnorm(d_q, nq, (uint32_t)dim, ws.qsq.as<float>(), s);
     for (const MultiChunk &c : plan.chunks) {
         const uint32_t nb = (uint32_t)c.nslots;
@@ -1859,16 +1905,16 @@ void Index::flat_knn_masked_multi_device(Workspace &ws, const float *d_q, uint64
             cap = topk_capacity((uint32_t)ksel);
             VDB_HIP(hipMemsetAsync(ws.dense.p, 0xFF, uint64_t(nb) * c.ld * sizeof(float), s));  // padding columns: NaN, behind every real key
             prof_begin(ws, "flat_filtered_scan_grouped", double(c.rows) * dim * sizeof(float));
-            launch_scan_gather_grouped(d_rows.as<float>(), (uint32_t)dim, d_items + c.item0, c.nitems, d_slot_q + c.slot0, d_q, metric, d_sq.as<float>(),
+            launch_scan_gather_grouped(d_rows.as<float>(), (uint32_t)dim, im.items + c.item0, c.nitems, im.slot_q + c.slot0, d_q, metric, d_sq.as<float>(),
                                        ws.qsq.as<float>(), ws.dense.as<float>(), c.ld, s);
             prof_end(ws);
             launch_topk_dense(ws.dense.as<float>(), c.ld, c.max_m, nb, (uint32_t)ksel, ws.lists.as<uint64_t>(), s);
             launch_topk_merge(ws.lists.as<uint64_t>(), nl, cap, nb, (uint32_t)ksel, ws.keys_c.as<uint64_t>(), s);
         }
-        launch_filter_finalize_grouped(ws.keys_c.as<uint64_t>(), cap, nb, (uint32_t)ksel, (uint32_t)k, d_slot_ids + c.slot0, d_slot_m + c.slot0,
-                                       d_slot_q + c.slot0, id_offset, d_idx, d_dist, d_cnt, s);
+        launch_filter_finalize_grouped(ws.keys_c.as<uint64_t>(), cap, nb, (uint32_t)ksel, (uint32_t)k, im.slot_ids + c.slot0, im.slot_m + c.slot0,
+                                       im.slot_q + c.slot0, id_offset, d_idx, d_dist, d_cnt, s);
     }
-    VDB_SYNC(s);  // (the plan's host arrays are pageable memory: alive until here)
+    VDB_SYNC(s);  // (the plan's and the image's host arrays are pageable memory: alive until here)
 }
 
 // ---- Flat: grouped k-NN, at most g hits per value of one label column (k_group.hip, grouped_plan.hpp; docs/DESIGN_flat.md 4.1q) ----------
@@ -1881,7 +1927,7 @@ void Index::flat_knn_masked_multi_device(Workspace &ws, const float *d_q, uint64
 void Index::flat_knn_grouped_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint32_t column, uint64_t g, const RowMask *const *masks,
                                     uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
     hipStream_t s = ws.stream;
-    VDB_REQUIRE(!elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+    require_f32_rows(*this);
     VDB_REQUIRE(column < LABEL_COLUMNS && g >= 1, "grouped k-NN: bad column or group size");
     if (nq == 0) return;
     VDB_REQUIRE(nq < (1ull << 32) && k <= (1ull << 30) - GROUPED_TILE, "flat knn: too many queries or k too large");  // (the walk's table: 2^31 entries at most)
@@ -2024,12 +2070,7 @@ void Index::flat_range_masked_multi_device(Workspace &ws, const float *d_q, uint
         range_scan_queries += nq;
         return;
     }
-    std::vector<uint64_t> m_of(n_masks);
-    std::vector<uint8_t> grouped(n_masks);
-    for (uint64_t g = 0; g < n_masks; g++) {
-        m_of[g] = masks[g]->m;
-        grouped[g] = !elem_u8 && m_of[g] <= flat_filtered_direct_max;
-    }
+    const MaskRoutes rt = mask_routes(masks, n_masks, mask_of, nq, [&](uint64_t m) { return !elem_u8 && m <= flat_filtered_direct_max; });
     std::vector<uint64_t> h_off(nq, 0), h_cnt(nq, 0);
     RangePool pool;
     RangeTally tally;
@@ -2038,11 +2079,8 @@ void Index::flat_range_masked_multi_device(Workspace &ws, const float *d_q, uint
     try {
         // per-mask route first: every collect returns synchronised, so the grouped route's reserves below free nothing in use
         {
-            std::vector<std::vector<uint64_t>> bucket(n_masks);
             uint64_t longest = 0;
-            for (uint64_t q = 0; q < nq; q++)
-                if (!grouped[mask_of[q]]) bucket[mask_of[q]].push_back(q);
-            for (uint64_t g = 0; g < n_masks; g++) longest = std::max<uint64_t>(longest, bucket[g].size());
+            for (uint64_t g = 0; g < n_masks; g++) longest = std::max<uint64_t>(longest, rt.bucket[g].size());
             DevBuf rx, rq, rr;
             if (longest) {
                 rx.reserve(longest * sizeof(uint64_t));
@@ -2051,7 +2089,7 @@ void Index::flat_range_masked_multi_device(Workspace &ws, const float *d_q, uint
             }
             std::vector<uint64_t> b_off, b_cnt;
             for (uint64_t g = 0; g < n_masks; g++) {
-                const std::vector<uint64_t> &bq = bucket[g];
+                const std::vector<uint64_t> &bq = rt.bucket[g];
                 const uint64_t nb = bq.size();
                 if (nb == 0) continue;
                 VDB_HIP(hipMemcpyAsync(rx.p, bq.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, s));
@@ -2066,25 +2104,17 @@ void Index::flat_range_masked_multi_device(Workspace &ws, const float *d_q, uint
                 }
             }
         }
-        const uint64_t max_m = multi_plan_max_m(m_of.data(), grouped.data(), n_masks, mask_of, nq);
+        const uint64_t max_m = multi_plan_max_m(rt.m_of.data(), rt.grouped.data(), n_masks, mask_of, nq);
         const uint64_t ld_all = (max_m + 63) & ~63ull;
         constexpr uint64_t BUDGET = 256ull << 20;  // bytes of each of the two key matrices per chunk
         MultiPlan plan;
-        multi_plan(m_of.data(), grouped.data(), n_masks, mask_of, nq, BUDGET, std::max<uint64_t>(ld_all * sizeof(uint64_t), 64), plan);
+        multi_plan(rt.m_of.data(), rt.grouped.data(), n_masks, mask_of, nq, BUDGET, std::max<uint64_t>(ld_all * sizeof(uint64_t), 64), plan);
         ns = plan.slot_query.size();
         if (ns && max_m) {
             const int metric = dist == 0 ? MET_L2_DIRECT : MET_COSINE;
-            // device image of the plan: [items (24 B) | slot_q | counters], one upload for the call
-            std::vector<GroupedItem> h_items(plan.items.size());
-            for (size_t i = 0; i < h_items.size(); i++) {
-                const MultiItem &it = plan.items[i];
-                h_items[i] = GroupedItem{masks[it.mask]->d_ids.as<uint32_t>(), (uint32_t)m_of[it.mask], it.tile, it.slot, it.nb};
-            }
-            const size_t off_q = h_items.size() * sizeof(GroupedItem), off_c = off_q + ns * sizeof(uint32_t);
             const uint64_t qch = std::min(plan.qch, ns);
             const size_t tb = sort_rows_temp_bytes(qch, ld_all);
-            // every buffer of the route reserved before its first launch (a later, larger reserve would free a buffer in use)
-            ws.misc.reserve(off_c + ns * sizeof(uint32_t));
+            // every buffer of the route reserved before its first launch (a later, larger reserve would free a buffer in use); ws.misc: plan_image
             ws.qsq.reserve(nq * sizeof(float));
             ws.keys_a.reserve(qch * ld_all * sizeof(uint64_t));
             ws.keys_b.reserve(qch * ld_all * sizeof(uint64_t));
@@ -2094,23 +2124,17 @@ void Index::flat_range_masked_multi_device(Workspace &ws, const float *d_q, uint
             char *hp = static_cast<char *>(ws.pinned(qch * (sizeof(uint64_t) + 2 * sizeof(uint32_t))));
             uint64_t *p_off = reinterpret_cast<uint64_t *>(hp);
             uint32_t *p_cnt = reinterpret_cast<uint32_t *>(p_off + qch), *p_take = p_cnt + qch;
-            char *d_plan = ws.misc.as<char>();
-            if (!h_items.empty()) VDB_HIP(hipMemcpyAsync(d_plan, h_items.data(), h_items.size() * sizeof(GroupedItem), hipMemcpyHostToDevice, s));
-            VDB_HIP(hipMemcpyAsync(d_plan + off_q, plan.slot_query.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            VDB_HIP(hipMemsetAsync(d_plan + off_c, 0, ns * sizeof(uint32_t), s));
-            const GroupedItem *d_items = reinterpret_cast<const GroupedItem *>(d_plan);
-            const uint32_t *d_slot_q = reinterpret_cast<const uint32_t *>(d_plan + off_q);
-            uint32_t *d_slot_c = reinterpret_cast<uint32_t *>(d_plan + off_c);
+            const PlanImage im = plan_image(ws, plan, masks, rt.m_of, false, true);
             if (metric == MET_COSINE) launch_row_sqnorm(d_q, nq, (uint32_t)dim, ws.qsq.as<float>(), s);
             for (const MultiChunk &c : plan.chunks) {
                 if (c.nitems == 0) continue;  // (only masks without rows: every count stays 0)
                 const uint32_t nb = (uint32_t)c.nslots;
                 VDB_HIP(hipMemsetAsync(ws.keys_a.p, 0xFF, uint64_t(nb) * c.ld * sizeof(uint64_t), s));  // PAIR_NONE pads sort last
                 prof_begin(ws, "flat_range_gather_grouped", double(c.rows) * dim * sizeof(float));
-                launch_range_gather_grouped(d_rows.as<float>(), (uint32_t)dim, d_items + c.item0, c.nitems, d_slot_q + c.slot0, d_q, metric,
-                                            d_sq.as<float>(), ws.qsq.as<float>(), d_radius, ws.keys_a.as<uint64_t>(), c.ld, d_slot_c + c.slot0, s);
+                launch_range_gather_grouped(d_rows.as<float>(), (uint32_t)dim, im.items + c.item0, c.nitems, im.slot_q + c.slot0, d_q, metric,
+                                            d_sq.as<float>(), ws.qsq.as<float>(), d_radius, ws.keys_a.as<uint64_t>(), c.ld, im.slot_c + c.slot0, s);
                 prof_end(ws);
-                VDB_HIP(hipMemcpyAsync(p_cnt, d_slot_c + c.slot0, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+                VDB_HIP(hipMemcpyAsync(p_cnt, im.slot_c + c.slot0, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                 VDB_SYNC(s);
                 uint64_t add = 0, max_take = 0;
                 for (uint32_t j = 0; j < nb; j++) {

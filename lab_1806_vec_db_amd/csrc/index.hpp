@@ -624,6 +624,11 @@ struct Index {
     std::atomic<uint64_t> range_multi_calls{0}, range_grouped_queries{0};  // range calls with a mask per query / queries their grouped launch answered
 };
 
+// what every filtered, mask-per-query and grouped k-NN entry point and search requires of the index
+inline void require_f32_rows(const Index &ix) {
+    VDB_REQUIRE(!ix.elem_u8, "filtered k-NN needs f32 rows: a VecSet<u8> index serves the filtered range search only");
+}
+
 struct WsLease {
     Index &ix;
     std::unique_ptr<Workspace> ws;

@@ -31,6 +31,11 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _nq(queries) -> int:
+    """how many queries a host call carries: one when `queries` is a single vector"""
+    return 1 if np.ndim(queries) == 1 else len(queries)
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(t) if a is not None else None
 
@@ -291,7 +296,9 @@ class GpuIndex:
         L.check(self._lib.vdb_index_set_id_offset(self._h, int(off)))
 
     # -- searches ------------------------------------------------------------------------------------------
-    def _search(self, fn, queries, k, ef=None):
+    def _knn_call(self, fn, queries, k, *mid):
+        """every host k-NN call: fn(handle, queries, nq, dim, k, *mid, idx, dist, cnt) -- `mid`: what the entry point takes between k and the
+        outputs (ef; a mask handle; the mask array, its length and mask_of; ...).  One query (1-D): (idx, dist) cut at its count."""
         q = _f32(queries)
         single = q.ndim == 1
         q = q.reshape(1, -1) if single else q
@@ -300,25 +307,23 @@ class GpuIndex:
         idx = np.zeros((nq, kk), dtype=np.uint64)
         dist = np.zeros((nq, kk), dtype=np.float32)
         cnt = np.zeros(nq, dtype=np.uint64)
-        args = [self._h, _ptr(q, L.f32p), nq, dim, int(k)]
-        if ef is not None:
-            args.append(int(ef))
-        args += [_ptr(idx, L.u64p), _ptr(dist, L.f32p), _ptr(cnt, L.u64p)]
-        L.check(fn(*args))
+        L.check(fn(self._h, _ptr(q, L.f32p), nq, dim, int(k), *mid, _ptr(idx, L.u64p), _ptr(dist, L.f32p), _ptr(cnt, L.u64p)))
         if single:
             c = int(cnt[0])
             return idx[0, :c].copy(), dist[0, :c].copy()
         return idx[:, :int(k)], dist[:, :int(k)], cnt
 
+    _search = _knn_call  # (its name before it took more than ef: what the tests of the sharded context compare against)
+
     def knn(self, queries, k: int):
         """IndexKNN::knn: Flat -> FlatIndex::knn; with an HNSW graph -> HNSWIndex::knn (default ef)
         (dynamic_index.rs:68-73)."""
         if self.has_hnsw():
-            return self._search(self._lib.vdb_hnsw_knn, queries, k, 0)
-        return self._search(self._lib.vdb_flat_knn, queries, k)
+            return self._knn_call(self._lib.vdb_hnsw_knn, queries, k, 0)
+        return self._knn_call(self._lib.vdb_flat_knn, queries, k)
 
     def flat_knn(self, queries, k: int):
-        return self._search(self._lib.vdb_flat_knn, queries, k)
+        return self._knn_call(self._lib.vdb_flat_knn, queries, k)
 
     def make_mask(self, allow) -> RowMask:
         """a row mask for the filtered searches: `allow` is a bool array over the rows or an array of (local) row ids (pack_mask)"""
@@ -455,20 +460,7 @@ class GpuIndex:
     def flat_knn_filtered(self, queries, k: int, mask: RowMask):
         """Exact k-NN over the mask's allowed rows alone (vdb_flat_knn_filtered): the first min(k, len(mask)) pairs of flat_knn
         restricted to them, distances bit-exact, ascending by (distance, id); same return shapes as flat_knn."""
-        q = _f32(queries)
-        single = q.ndim == 1
-        q = q.reshape(1, -1) if single else q
-        nq, dim = q.shape
-        kk = max(int(k), 1)
-        idx = np.zeros((nq, kk), dtype=np.uint64)
-        dist = np.zeros((nq, kk), dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint64)
-        L.check(self._lib.vdb_flat_knn_filtered(self._h, _ptr(q, L.f32p), nq, dim, int(k), mask._h, _ptr(idx, L.u64p), _ptr(dist, L.f32p),
-                                                _ptr(cnt, L.u64p)))
-        if single:
-            c = int(cnt[0])
-            return idx[0, :c].copy(), dist[0, :c].copy()
-        return idx[:, :int(k)], dist[:, :int(k)], cnt
+        return self._knn_call(self._lib.vdb_flat_knn_filtered, queries, k, mask._h)
 
     def flat_knn_filtered_device(self, q_ptr: int, nq: int, k: int, mask: RowMask, out_idx_ptr: int, out_dist_ptr: int, out_cnt_ptr: int,
                                  stream: int = 0):
@@ -489,21 +481,8 @@ class GpuIndex:
         """flat_knn_filtered with ONE MASK PER QUERY (vdb_flat_knn_filtered_multi): query q is answered under masks[mask_of[q]], exactly
         as flat_knn_filtered(queries[q], k, masks[mask_of[q]]) answers it; the buckets of short masks share one scan launch.  `masks`: a
         sequence of RowMask of this index, `mask_of`: nq indexes into it, in any order.  Same return shapes as flat_knn_filtered."""
-        q = _f32(queries)
-        single = q.ndim == 1
-        q = q.reshape(1, -1) if single else q
-        nq, dim = q.shape
-        arr, n_masks, mo = self._mask_args(masks, mask_of, nq)
-        kk = max(int(k), 1)
-        idx = np.zeros((nq, kk), dtype=np.uint64)
-        dist = np.zeros((nq, kk), dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint64)
-        L.check(self._lib.vdb_flat_knn_filtered_multi(self._h, _ptr(q, L.f32p), nq, dim, int(k), arr, n_masks, _ptr(mo, L.u32p), _ptr(idx, L.u64p),
-                                                      _ptr(dist, L.f32p), _ptr(cnt, L.u64p)))
-        if single:
-            c = int(cnt[0])
-            return idx[0, :c].copy(), dist[0, :c].copy()
-        return idx[:, :int(k)], dist[:, :int(k)], cnt
+        arr, n_masks, mo = self._mask_args(masks, mask_of, _nq(queries))
+        return self._knn_call(self._lib.vdb_flat_knn_filtered_multi, queries, k, arr, n_masks, _ptr(mo, L.u32p))
 
     def flat_knn_filtered_multi_device(self, q_ptr: int, nq: int, k: int, masks, mask_of, out_idx_ptr: int, out_dist_ptr: int, out_cnt_ptr: int,
                                        stream: int = 0):
@@ -530,21 +509,8 @@ class GpuIndex:
         in flat_knn's order, such that fewer than group_size earlier rows of that order carry the same label; rows without a label are
         always kept.  masks=None: over all rows; otherwise query q under masks[mask_of[q]] as in flat_knn_filtered_multi (one RowMask and
         no mask_of: that mask for every query).  Same return shapes as flat_knn_filtered."""
-        q = _f32(queries)
-        single = q.ndim == 1
-        q = q.reshape(1, -1) if single else q
-        nq, dim = q.shape
-        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, nq)
-        kk = max(int(k), 1)
-        idx = np.zeros((nq, kk), dtype=np.uint64)
-        dist = np.zeros((nq, kk), dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint64)
-        L.check(self._lib.vdb_flat_knn_grouped(self._h, _ptr(q, L.f32p), nq, dim, int(k), int(column), int(group_size), arr, n_masks, mo_p,
-                                               _ptr(idx, L.u64p), _ptr(dist, L.f32p), _ptr(cnt, L.u64p)))
-        if single:
-            c = int(cnt[0])
-            return idx[0, :c].copy(), dist[0, :c].copy()
-        return idx[:, :int(k)], dist[:, :int(k)], cnt
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, _nq(queries))
+        return self._knn_call(self._lib.vdb_flat_knn_grouped, queries, k, int(column), int(group_size), arr, n_masks, mo_p)
 
     def flat_knn_grouped_device(self, q_ptr: int, nq: int, k: int, column: int, group_size: int, out_idx_ptr: int, out_dist_ptr: int,
                                 out_cnt_ptr: int, masks=None, mask_of=None, stream: int = 0):
@@ -562,23 +528,29 @@ class GpuIndex:
     def _range_out(self, h, nq: int):
         return read_range(self._lib, h, nq)
 
-    def range_search(self, queries, radius, limit: int | None = None, mask: RowMask | None = None):
-        """Exact Flat range search (vdb_flat_range): for every query ALL rows with distance <= its radius -- the distance
-        FlatIndex::knn computes, boundary included -- ascending by (distance, index); with `limit` the first `limit` of them,
-        i.e. search(k = limit, upper_bound = radius).  `radius`: one value, or one per query.
-        Returns (lims, idx, dist): query q owns idx / dist [lims[q], lims[q + 1])."""
+    @staticmethod
+    def _range_args(queries, radius, limit):
+        """(queries as [nq][dim] f32, nq, dim, one radius per query as f32, limit as the C calls take it: 0 = none) of a host range call"""
         q = _f32(queries)
         q = q.reshape(1, -1) if q.ndim == 1 else q
         nq, dim = q.shape
         r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (nq,)))
         if limit is not None and int(limit) <= 0:
             raise ValueError("limit must be positive (None: no limit)")
+        return q, nq, dim, r, int(limit or 0)
+
+    def range_search(self, queries, radius, limit: int | None = None, mask: RowMask | None = None):
+        """Exact Flat range search (vdb_flat_range): for every query ALL rows with distance <= its radius -- the distance
+        FlatIndex::knn computes, boundary included -- ascending by (distance, index); with `limit` the first `limit` of them,
+        i.e. search(k = limit, upper_bound = radius).  `radius`: one value, or one per query.
+        Returns (lims, idx, dist): query q owns idx / dist [lims[q], lims[q + 1])."""
+        q, nq, dim, r, limit = self._range_args(queries, radius, limit)
         h = L.vp()
         if mask is not None:  # only the mask's allowed rows (vdb_flat_range_filtered)
-            L.check(self._lib.vdb_flat_range_filtered(self._h, _ptr(q, L.f32p), nq, dim, _ptr(r, L.f32p), int(limit or 0), mask._h,
+            L.check(self._lib.vdb_flat_range_filtered(self._h, _ptr(q, L.f32p), nq, dim, _ptr(r, L.f32p), limit, mask._h,
                                                       C.byref(h)))
             return self._range_out(h, nq)
-        L.check(self._lib.vdb_flat_range(self._h, _ptr(q, L.f32p), nq, dim, _ptr(r, L.f32p), int(limit or 0), C.byref(h)))
+        L.check(self._lib.vdb_flat_range(self._h, _ptr(q, L.f32p), nq, dim, _ptr(r, L.f32p), limit, C.byref(h)))
         return self._range_out(h, nq)
 
     def range_search_device(self, q_ptr: int, nq: int, radius_ptr: int, limit: int | None = None, stream: int = 0):
@@ -593,15 +565,10 @@ class GpuIndex:
         range_search(queries[q], radius[q], limit, mask=masks[mask_of[q]]) returns; the buckets of short masks share one scan launch.
         `radius`: one value, or one per query; `masks`: a sequence of RowMask of this index, `mask_of`: nq indexes into it, in any
         order.  Returns (lims, idx, dist) as range_search does."""
-        q = _f32(queries)
-        q = q.reshape(1, -1) if q.ndim == 1 else q
-        nq, dim = q.shape
-        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1), (nq,)))
-        if limit is not None and int(limit) <= 0:
-            raise ValueError("limit must be positive (None: no limit)")
+        q, nq, dim, r, limit = self._range_args(queries, radius, limit)
         arr, n_masks, mo = self._mask_args(masks, mask_of, nq)
         h = L.vp()
-        L.check(self._lib.vdb_flat_range_filtered_multi(self._h, _ptr(q, L.f32p), nq, dim, _ptr(r, L.f32p), int(limit or 0), arr, n_masks,
+        L.check(self._lib.vdb_flat_range_filtered_multi(self._h, _ptr(q, L.f32p), nq, dim, _ptr(r, L.f32p), limit, arr, n_masks,
                                                         _ptr(mo, L.u32p), C.byref(h)))
         return self._range_out(h, nq)
 
@@ -616,14 +583,14 @@ class GpuIndex:
     def knn_with_ef(self, queries, k: int, ef: int):
         """IndexKNNWithEf::knn_with_ef; Flat ignores ef (dynamic_index.rs:75-80)."""
         if self.has_hnsw():
-            return self._search(self._lib.vdb_hnsw_knn, queries, k, ef)
-        return self._search(self._lib.vdb_flat_knn, queries, k)
+            return self._knn_call(self._lib.vdb_hnsw_knn, queries, k, int(ef))
+        return self._knn_call(self._lib.vdb_flat_knn, queries, k)
 
     def knn_pq(self, queries, k: int, ef: int):
         """IndexPQ::knn_pq (dynamic_index.rs:82-93)."""
         if self.has_hnsw():
-            return self._search(self._lib.vdb_hnsw_knn_pq, queries, k, ef)
-        return self._search(self._lib.vdb_flat_knn_pq, queries, k, ef)
+            return self._knn_call(self._lib.vdb_hnsw_knn_pq, queries, k, int(ef))
+        return self._knn_call(self._lib.vdb_flat_knn_pq, queries, k, int(ef))
 
     def flat_knn_device(self, q_ptr: int, nq: int, k: int, out_idx_ptr: int, out_dist_ptr: int, out_cnt_ptr: int,
                         stream: int = 0):
@@ -883,7 +850,7 @@ class GpuIndex:
 
     def ivf_knn(self, queries, k: int, n_probes: int = 0):
         """IVFIndex::knn_with_ef (ef = n_probes; 0 -> default 4)."""
-        return self._search(self._lib.vdb_ivf_knn, queries, k, n_probes)
+        return self._knn_call(self._lib.vdb_ivf_knn, queries, k, int(n_probes))
 
     def ivf_knn_device(self, q_ptr: int, nq: int, k: int, n_probes: int, out_idx_ptr: int, out_dist_ptr: int,
                        out_cnt_ptr: int, stream: int = 0):

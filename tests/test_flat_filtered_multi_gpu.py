@@ -393,6 +393,8 @@ def test_errors_leave_the_outputs_untouched(small):
         assert raw([fresh, good], [0] * 6) == (3, True)
         with pytest.raises(vdb.VdbError, match="error 3.*stale"):
             ix.flat_knn_filtered_multi(qs, 5, [fresh, good], [0] * 6)
+        with pytest.raises(vdb.VdbError, match="error 3.*stale"):  # ... also in a call without queries
+            ix.flat_knn_filtered_multi(qs[:0], 5, [fresh, good], [])
         assert raw([fresh], [0] * 6) == (0, False)
         for m in (good, foreign, fresh):
             m.close()
