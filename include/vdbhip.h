@@ -15,7 +15,7 @@
  *    through vdb_last_error() (thread-local).  Nothing aborts the process.
  *  - read-side calls (knn*, row, len...) are re-entrant on one handle, like `&self` methods
  *    under the reference's RwLock read guard (database/mod.rs:248-256); write-side calls
- *    (add, swap_remove, remove_rows, *_build, *_attach, *_clear) need external exclusion, like `&mut self`.
+ *    (add, swap_remove, remove_rows, update_rows, *_build, *_attach, *_clear) need external exclusion, like `&mut self`.
  *  - results for query q are written at out_idx[q*k .. q*k+out_count[q]) ascending by
  *    (distance, index) -- the order of `Vec<CandidatePair>` (candidate_pair.rs:36-41);
  *    out_count[q] = min(k, len) for Flat (flat_index.rs:163).
@@ -84,6 +84,34 @@ int vdb_index_swap_remove(vdb_index *idx, uint64_t i);
  * m == n leaves an empty index. */
 int vdb_remove_plan(uint64_t n, const uint64_t *rows, uint64_t m, uint64_t *out_dst, uint64_t *out_src, uint64_t *out_moves);
 int vdb_index_remove_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, uint64_t *out_dst, uint64_t *out_src, uint64_t *out_moves);
+/* ---- in-place update: new vectors for many rows as ONE call (no counterpart in the reference) --------------------------------------
+ * The reference can only delete a row and add it again, which gives the row a new id, moves an unrelated row into the hole and makes
+ * every mask stale.  These calls replace the VECTORS of the rows R (m of them) where they are; afterwards every search answers exactly
+ * as it would on a table built with those rows replaced.
+ * vdb_update_plan: host utility, works without a GPU (like vdb_remove_plan).  rows [m] must be distinct and below n (n < 2^32), in any
+ * order; a NULL rows with m > 0, a row at or past n or a duplicate is VDB_ERR_INVALID with a message, and nothing is written.  out_tiles
+ * (room for min(m, ceil(n / 16)) entries) receives the 16-row mirror tiles rows[j] / 16 the update touches, ascending and distinct,
+ * *out_n_tiles their number; out_tiles = NULL: the number alone.
+ * vdb_index_update_rows: vecs is m x dim row-major on the host, vecs[j] the new vector of LOCAL row rows[j] (same rules; id_offset plays
+ * no part).  One launch scatters the rows and their norms (csrc/k_update.hip; the norms are the strict fold that vdb_index_add caches, so
+ * they are bit-identical to those of a table built from the updated rows), one launch per live mirror rewrites the touched 16-row tiles:
+ *   - split-bf16 mirror: rewritten in step;
+ *   - fp16 mirror: rewritten in step, the measured rounding error of the new rows folded into its error terms, while the largest row
+ *     norm still fits the mirror's scale; dropped and rebuilt by its next use when it does not, or when the mirror was behind the table;
+ *   - 8-bit mirror: tiles, codes and row constants rewritten with the current mean / lambdas (they bound any row; only the tightness
+ *     of the bound depends on them), not rebuilt; dropped when it was behind the table;
+ *   - the row-major fp16 / 8-bit images of the HNSW walk and the IVF scan are dropped.
+ * Host vectors are staged through a bounded workspace buffer (64 MiB at a time), never through an allocation the size of the input.
+ * The row count, id_offset and every label column are untouched, and masks made BEFORE the call stay valid: a mask is a set of rows
+ * and the set did not change (their cached copies of the 8-bit row constants are rebuilt by the next call that needs them).
+ * "update_calls" / "update_rows" of vdb_get_stat count the calls and the rows.  Write-side.  Flat only, refused under an HNSW graph, a PQ
+ * table or IVF clusters with a message each (clear them first), and on a VecSet<u8> index (f32 rows only).  An invalid list, a refusal
+ * or a failed allocation leaves the index exactly as it was; m == 0 changes nothing and counts nothing.
+ * vdb_index_update_rows_device: the same with the vectors already in HBM on the index's GPU (16-byte aligned); rows stays a host array.
+ * The call returns synchronised; no host copy of the rows is kept until one is needed. */
+int vdb_update_plan(uint64_t n, const uint64_t *rows, uint64_t m, uint32_t *out_tiles, uint64_t *out_n_tiles);
+int vdb_index_update_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, const float *vecs /* m x dim, host */);
+int vdb_index_update_rows_device(vdb_index *idx, const uint64_t *rows /* host */, uint64_t m, const void *d_vecs);
 /* row sharding: ids reported by knn* are local_row + offset */
 int vdb_index_set_id_offset(vdb_index *idx, uint64_t offset);
 /* calc_dist (pyo3/mod.rs:43-48): one distance, evaluated on the GPU in reference order */
@@ -162,7 +190,8 @@ int vdb_range_destroy(vdb_range *r);
  * vdb_mask_count gives the number m of allowed rows.  id_offset is added to reported ids as everywhere else.
  * A mask belongs to the index it was made for AND to that state of its rows: a call with a mask of another index fails with
  * VDB_ERR_INVALID, a call with a mask made before a later vdb_index_add* / vdb_index_swap_remove with VDB_ERR_STATE (both set
- * vdb_last_error; nothing is computed).  Creating a mask is read-side; destroy it (NULL is fine) when no call is using it and
+ * vdb_last_error; nothing is computed).  vdb_index_update_rows* changes no row SET: masks made before it stay valid and are applied to
+ * the new vectors (the copy of the row constants named below is rebuilt by the next call that needs it).  Creating a mask is read-side; destroy it (NULL is fine) when no call is using it and
  * before the index is destroyed.  Memory on the index's device: n/8 + 4 m bytes, plus 8 B per padded row once a call has run the
  * 8-bit tier under the mask (a copy of that tier's per-row constants in which every disallowed row carries a key of +inf).
  * vdb_flat_knn_filtered: per query the first min(k, m) pairs of FlatIndex::knn over the ALLOWED rows alone -- distances bit-exact,
@@ -521,6 +550,7 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *                        conjunctions (vdb_mask_create_where_any*); "mask_combine_masks": the ones vdb_mask_combine made;
  *                        "mask_partition_masks": the ones vdb_mask_create_partition made; "label_count_calls":
  *                        vdb_index_label_counts calls; "label_columns": allocated columns,
+ *   "update_calls"       vdb_index_update_rows / _device calls that changed rows (m > 0, not refused); "update_rows": the rows they rewrote,
  *   "hbm_bytes_per_row"  resident HBM bytes per row over all per-row buffers (rows, norms, mirrors, PQ codes, level-0 links, label
  *                        columns). */
 int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out);

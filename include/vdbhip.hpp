@@ -135,6 +135,8 @@ public:
         for (uint64_t j = 0; j < moves; j++) out[j] = {dst[j], src[j]};
         return out;
     }
+    // new vectors (rows.size() x dim, row-major) for the distinct rows `rows`, in place: ids, labels and masks stay (vdb_index_update_rows)
+    void update_rows(const std::vector<uint64_t> &rows, const float *vecs) { check(vdb_index_update_rows(h_, rows.data(), rows.size(), vecs)); }
 
     // knn (dynamic_index.rs:66-73): Flat -> FlatIndex::knn, HNSW -> HNSWIndex::knn (default ef)
     std::vector<CandidatePair> knn(const std::vector<float> &query, uint64_t k) const {

@@ -39,6 +39,9 @@ SIGNATURES = {
     "vdb_index_swap_remove": [vp, u64],
     "vdb_remove_plan": [u64, u64p, u64, u64p, u64p, u64p],
     "vdb_index_remove_rows": [vp, u64p, u64, u64p, u64p, u64p],
+    "vdb_update_plan": [u64, u64p, u64, u32p, u64p],
+    "vdb_index_update_rows": [vp, u64p, u64, f32p],
+    "vdb_index_update_rows_device": [vp, u64p, u64, vp],
     "vdb_index_set_id_offset": [vp, u64],
     "vdb_calc_dist": [C.c_int, f32p, f32p, u64, C.c_int, f32p],
     "vdb_flat_knn": [vp, f32p, u64, u64, u64, u64p, f32p, u64p],

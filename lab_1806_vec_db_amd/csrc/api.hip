@@ -6,6 +6,7 @@
 #include "ctx.hpp"
 #include "pq_hnsw.hpp"
 #include "remove_plan.hpp"
+#include "update_plan.hpp"
 
 using namespace vdb;
 
@@ -361,6 +362,38 @@ int vdb_index_remove_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, uint
     std::vector<uint64_t> dst, src;
     idx->ix.remove_rows(rows, m, dst, src);
     remove_plan_out(dst, src, out_dst, out_src, out_moves);
+    VDB_API_END
+}
+int vdb_update_plan(uint64_t n, const uint64_t *rows, uint64_t m, uint32_t *out_tiles, uint64_t *out_n_tiles) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(n < (1ull << 32), "update_plan: a shard holds at most 2^32-1 rows");
+    const char *why = update_plan_check(n, rows, m);
+    VDB_REQUIRE(!why, why);
+    std::vector<uint32_t> tiles;
+    update_plan(n, rows, m, tiles);
+    if (out_tiles && !tiles.empty()) std::memcpy(out_tiles, tiles.data(), tiles.size() * sizeof(uint32_t));
+    if (out_n_tiles) *out_n_tiles = tiles.size();
+    VDB_API_END
+}
+static void update_common(vdb_index *idx, const uint64_t *rows, uint64_t m, const void *vecs, bool on_device) {
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    VDB_REQUIRE(!ix.hnsw.present, "update_rows needs a Flat index (clear the HNSW graph first)");
+    VDB_REQUIRE(!ix.pq.present, "update_rows invalidates the PQ table: clear it first");
+    VDB_REQUIRE(!ix.ivf.present, "update_rows invalidates the IVF clusters: clear them first");
+    VDB_REQUIRE(!ix.elem_u8, "update_rows needs f32 rows: a VecSet<u8> index is not updated in place");
+    VDB_REQUIRE(vecs || m == 0, "update_rows: null vectors");
+    VDB_REQUIRE(!on_device || reinterpret_cast<uintptr_t>(vecs) % 16 == 0, "update_rows: device vectors must be 16-byte aligned");
+    ix.update_rows(rows, m, vecs, on_device);
+}
+int vdb_index_update_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, const float *vecs) {
+    VDB_API_BEGIN
+    update_common(idx, rows, m, vecs, false);
+    VDB_API_END
+}
+int vdb_index_update_rows_device(vdb_index *idx, const uint64_t *rows, uint64_t m, const void *d_vecs) {
+    VDB_API_BEGIN
+    update_common(idx, rows, m, d_vecs, true);
     VDB_API_END
 }
 int vdb_index_set_id_offset(vdb_index *idx, uint64_t offset) {
@@ -1276,6 +1309,10 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.grouped_rounds.load();
     else if (n == "flat_grouped_exhausted_queries")
         *out = idx->ix.grouped_exhausted.load();
+    else if (n == "update_calls")  // vdb_index_update_rows* calls that changed rows | rows they rewrote
+        *out = idx->ix.update_calls.load();
+    else if (n == "update_rows")
+        *out = idx->ix.updated_rows.load();
     else if (n == "label_columns")  // allocated label columns (4 B per row each)
         *out = idx->ix.label_columns();
     else if (n == "hbm_bytes_per_row")

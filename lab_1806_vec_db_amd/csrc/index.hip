@@ -2,6 +2,7 @@
 #include "index.hpp"
 #include "multi_plan.hpp"
 #include "remove_plan.hpp"
+#include "update_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -241,6 +242,100 @@ void Index::remove_rows(const uint64_t *rows, uint64_t m, std::vector<uint64_t> 
     n = n1;
     write_gen += 1;
     // xsq_max / xsq_min_pos stay bounds
+}
+
+// New vectors for the rows `rows` (distinct, any order), in place: no row moves, n / id_offset / the label columns stay, and so does
+// write_gen -- a RowMask is a set of rows and the set did not change (docs/DESIGN_flat.md 4.1r).  Mirror upkeep as in remove_rows above.
+void Index::update_rows(const uint64_t *rows, uint64_t m, const void *vecs, bool on_device) {
+    const char *why = update_plan_check(n, rows, m);
+    VDB_REQUIRE(!why, why);
+    if (m == 0) return;
+    VDB_REQUIRE(vecs, "update_rows: null vectors");
+    VDB_REQUIRE(!elem_u8, "update_rows needs f32 rows: a VecSet<u8> index is not updated in place");
+    use_device();
+    WsLease ws(*this);
+    hipStream_t s = ws->stream;
+    const uint32_t d = (uint32_t)dim;
+    const size_t row_bytes = size_t(dim) * sizeof(float);
+    std::vector<uint32_t> h_ids(m), h_tiles;
+    for (uint64_t j = 0; j < m; j++) h_ids[j] = (uint32_t)rows[j];
+    update_plan(n, rows, m, h_tiles);
+    const uint64_t n_tiles = h_tiles.size();
+    const bool tiled_live = mfma_supported(d) && tiled_m.valid;
+    const bool half_live = mfma_supported(d) && half_m.covers(n);  // in step: its touched tiles are rewritten if the scale still fits
+    const bool i8_live = i8_m.covers(n);
+    // host vectors go through a bounded staging buffer, a chunk of rows at a time; device vectors are read where they are
+    const uint64_t chunk = std::min<uint64_t>(m, std::max<uint64_t>(UPDATE_STAGE_BYTES / row_bytes, 1));
+    std::vector<float> sq(m);
+    ws->keys_a.reserve(m * sizeof(uint32_t));
+    ws->keys_b.reserve(n_tiles * sizeof(uint32_t));
+    ws->misc.reserve(m * sizeof(float));
+    if (!on_device) ws->dense.reserve(chunk * row_bytes);
+    if (half_live) d_half_err.reserve(2 * sizeof(uint32_t));
+    // ---- nothing was changed up to here; from here on nothing allocates on the device ----
+    const uint32_t *d_ids = ws->keys_a.as<uint32_t>(), *d_tiles = ws->keys_b.as<uint32_t>();
+    float *d_sq_new = ws->misc.as<float>();
+    VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_ids.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    VDB_HIP(hipMemcpyAsync(ws->keys_b.p, h_tiles.data(), n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (half_live) VDB_HIP(hipMemsetAsync(d_half_err.p, 0, 2 * sizeof(uint32_t), s));
+    for (uint64_t j0 = 0; j0 < m; j0 += chunk) {
+        const uint64_t nb = std::min(chunk, m - j0);
+        const char *from = static_cast<const char *>(vecs) + j0 * row_bytes;
+        const float *d_new = reinterpret_cast<const float *>(from);
+        if (!on_device) {
+            VDB_HIP(hipMemcpyAsync(ws->dense.p, from, nb * row_bytes, hipMemcpyHostToDevice, s));
+            d_new = ws->dense.as<float>();
+        }
+        launch_row_sqnorm(d_new, nb, d, d_sq_new + j0, s);  // the strict fold of add_rows: the norms of a table built with these rows
+        launch_rows_scatter(d_rows.p, row_bytes, d_sq.as<float>(), d_ids + j0, d_new, d_sq_new + j0, nb, num_cu, s);
+        // the new rows' rounding error under the CURRENT fp16 scale (dropped below if that scale no longer fits)
+        if (half_live) launch_row_split_err(d_new, d_sq_new + j0, 0, nb, d, half_sx(), d_half_err.as<uint32_t>(), s);
+    }
+    if (tiled_live) launch_tile_rows_list(d_rows.as<float>(), n, d, d_tiles, n_tiles, d_tiled.as<float>(), s);
+    if (i8_live)  // tiles, codes and constants with the current mu / lambdas (bounds for any row); Cosine reads d_sq: the new norms are in place
+        launch_tile_rows_i8_list(d_rows.as<float>(), n, d, d_tiles, n_tiles, d_mu_i8.as<float>(), i8_l1, i8_l2, d_tiled_i8.p, d_rowc_i8.as<float>(), s,
+                                 dist == 1 ? d_sq.as<float>() : nullptr);
+    else
+        i8_m.invalidate();  // rows were added since the last search: rebuilt by the next one
+    VDB_HIP(hipMemcpyAsync(sq.data(), d_sq_new, m * sizeof(float), hipMemcpyDeviceToHost, s));
+    VDB_SYNC(s);
+    for (uint64_t j = 0; j < m; j++) {  // the bounds are widened, never narrowed
+        const float v = sq[j];
+        if (v > xsq_max && std::isfinite(v)) xsq_max = v;
+        if (v > 0.0f && v < xsq_min_pos) xsq_min_pos = v;
+        h_sq[rows[j]] = v;
+    }
+    // fp16 mirror: half_refresh's test of the scale against the new xsq_max
+    bool half_fits = half_live && xsq_max >= 0x1p-80f && xsq_max <= 0x1p80f;
+    if (half_fits) {
+        int e = 0;
+        (void)std::frexp(xsq_max, &e);
+        half_fits = (e >= 0 ? (e + 1) / 2 : -((-e) / 2)) <= half_exp;
+    }
+    if (half_fits) {
+        launch_tile_rows_h_list(d_rows.as<float>(), n, d, d_tiles, n_tiles, half_sx(), d_tiled_h.p, s);
+        VDB_SYNC(s);
+        float e2[2];
+        VDB_HIP(hipMemcpy(e2, d_half_err.p, sizeof(e2), hipMemcpyDeviceToHost));
+        half_dx_abs = std::max(half_dx_abs, std::sqrt(e2[0]) * 1.001f);
+        half_dx_rel = std::max(half_dx_rel, std::sqrt(e2[1]) * 1.001f);
+    } else {
+        half_m.invalidate();  // behind the table, or the scale is too small now: rebuilt in full by its next use
+    }
+    rows_h_m.invalidate();
+    rows_q8_m.invalidate();
+    {
+        std::lock_guard<std::mutex> g(host_mu);
+        if (on_device) {
+            host_valid = false;
+        } else if (host_valid) {
+            const float *fr = static_cast<const float *>(vecs);
+            for (uint64_t j = 0; j < m; j++) std::memcpy(h_rows.data() + rows[j] * dim, fr + j * dim, row_bytes);
+        }
+    }
+    rowc_gen += 1;  // the masks' copies of the row constants are stale; the masks themselves are not
+    update_calls += 1;
+    updated_rows += m;
 }
 
 // ---- label columns and the masks built from them (k_labels.hip) ----------------------------------------------------------------------
@@ -1624,12 +1719,15 @@ void Index::check_mask(const RowMask &mask) const {
 
 const float *Index::masked_rowc(Workspace &ws, const RowMask &mask) {
     std::lock_guard<std::mutex> g(mask.mu);  // read-side calls are re-entrant: one of them builds, the others wait
-    if (mask.rowc_of == d_rowc_i8.p && mask.d_rowc.p) return mask.d_rowc.as<float>();
+    // (update_rows rewrites constants inside the same allocation: the generation tells, the pointer alone would not)
+    const uint64_t gen = rowc_gen.load();
+    if (mask.rowc_of == d_rowc_i8.p && mask.rowc_gen == gen && mask.d_rowc.p) return mask.d_rowc.as<float>();
     const uint64_t rows_pad = mirror_tiles(n) * 16;
     mask.d_rowc.reserve(rows_pad * 2 * sizeof(float));
     launch_mask_rowc(d_rowc_i8.as<float>(), mask.d_bits.as<uint64_t>(), n, rows_pad, mask.d_rowc.as<float>(), ws.stream);
     VDB_SYNC(ws.stream);
     mask.rowc_of = d_rowc_i8.p;
+    mask.rowc_gen = gen;
     return mask.d_rowc.as<float>();
 }
 

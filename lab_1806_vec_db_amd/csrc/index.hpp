@@ -309,6 +309,7 @@ struct RowMask {
     mutable std::mutex mu;
     mutable DevBuf d_rowc;  // float2 [padded rows]: Index::d_rowc_i8 with {+inf, 0} for every disallowed row
     mutable const void *rowc_of = nullptr;  // the d_rowc_i8 allocation it was copied from (nullptr: not built)
+    mutable uint64_t rowc_gen = 0;          // Index::rowc_gen then: update_rows rewrites constants inside that allocation
 };
 // IVFIndex (ivf_index.rs:34-47): centroids as a small Flat index of their own, clusters as CSR over row ids
 struct IVFState {
@@ -480,6 +481,15 @@ struct Index {
     // plan (remove_plan.hpp) on the device, the touched tiles of every live mirror rewritten once, one stream sync.  dst / src
     // receive the plan.  An invalid list or a failed allocation throws before anything is changed.
     void remove_rows(const uint64_t *rows, uint64_t m, std::vector<uint64_t> &dst, std::vector<uint64_t> &src);
+    // New vectors (m x dim f32, host or device) for the distinct rows rows[0..m) in any order, in place (update_plan.hpp, k_update.hip): rows,
+    // d_sq / h_sq (launch_row_sqnorm's strict fold) and the touched 16-row tiles of every live mirror rewritten once; xsq_max /
+    // xsq_min_pos widened; the fp16 mirror's measured error folded in, or the mirror dropped when its scale no longer fits.  n, id_offset,
+    // the label columns and write_gen stay: masks made before the call remain valid, rowc_gen makes their row-constant copies rebuild.
+    // f32 rows only.  An invalid list or a failed allocation throws before anything is changed.
+    void update_rows(const uint64_t *rows, uint64_t m, const void *vecs, bool on_device);
+    static constexpr size_t UPDATE_STAGE_BYTES = size_t(64) << 20;  // host vectors are staged through at most this much of ws.dense at a time
+    std::atomic<uint64_t> rowc_gen{0};  // bumped by update_rows: what a RowMask's d_rowc copy is checked against (with the allocation)
+    std::atomic<uint64_t> update_calls{0}, updated_rows{0};  // update_rows calls that changed rows / rows they rewrote
 
     // timing hooks
     void prof_begin(Workspace &ws, const char *name, double bytes);

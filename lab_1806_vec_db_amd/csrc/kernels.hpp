@@ -266,6 +266,9 @@ void launch_tile_rows_i8_list(const float *X, uint64_t n, uint32_t dim, const ui
 // k_remove.hip: moves[2 j] = dst, [2 j + 1] = src -- row src -> row dst (row_bytes bytes each) and sq[src] -> sq[dst]; every src above
 // every dst (a removal plan, remove_plan.hpp)
 void launch_rows_move(void *rows, uint64_t row_bytes, float *sq, const uint32_t *moves, uint64_t n_moves, int num_cu, hipStream_t s);
+// k_update.hip: row j of src (m contiguous rows) -> row ids[j] of `rows` and sq_new[j] -> sq[ids[j]]; the ids are distinct (update_plan.hpp)
+void launch_rows_scatter(void *rows, uint64_t row_bytes, float *sq, const uint32_t *ids, const void *src, const float *sq_new, uint64_t m,
+                         int num_cu, hipStream_t s);
 void launch_query_prep_i8(const float *Q, uint32_t nq, uint32_t nq_pad, uint32_t dim, const float *mu, float l1, float l2, float *qsq,
                           float *qscale, float *qoff, uint32_t *hits, void *qfrag, hipStream_t s, int cosine = 0);
 // k_redo.hip: second attempts of a Flat call

@@ -266,6 +266,37 @@ class GpuIndex:
         L.check(self._lib.vdb_index_remove_rows(self._h, _ptr(r, L.u64p), r.size, _ptr(dst, L.u64p), _ptr(src, L.u64p), C.byref(moves)))
         return dst[:int(moves.value)].copy(), src[:int(moves.value)].copy()
 
+    @staticmethod
+    def _update_ids(rows) -> np.ndarray:
+        a = np.asarray(rows).reshape(-1)
+        if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError("update_rows: an array of integer row ids is needed")
+        if a.size and np.issubdtype(a.dtype, np.signedinteger) and int(a.min()) < 0:
+            raise ValueError("update_rows: negative row id")
+        r = np.ascontiguousarray(a.astype(np.uint64))
+        if r.size > 1 and np.unique(r).size != r.size:
+            raise ValueError("update_rows: duplicate row ids")
+        return r
+
+    def update_rows(self, rows, vecs):
+        """New vectors for existing rows, in place (vdb_index_update_rows): row rows[j] gets vecs[j].  `rows` are local row ids in any
+        order (bool / float / negative / duplicate ids raise ValueError), `vecs` has shape (len(rows), dim).  Row ids, the row count, the
+        label columns and every mask made before the call stay as they are; the mirrors of the Flat tiers are kept in step.  Refused
+        (VdbError, index unchanged) under an HNSW graph, a PQ table or IVF clusters, and on a u8 index."""
+        r = self._update_ids(rows)
+        v = _f32(vecs)
+        if r.size == 0 and v.size == 0:
+            v = v.reshape(0, self.dim)
+        if v.ndim != 2 or v.shape != (r.size, self.dim):
+            raise L.VdbError(f"dimension mismatch: index dim {self.dim}, {r.size} rows, got shape {v.shape}")
+        L.check(self._lib.vdb_index_update_rows(self._h, _ptr(r, L.u64p), r.size, _ptr(v, L.f32p)))
+
+    def update_rows_device(self, rows, data_ptr: int):
+        """The same with the len(rows) x dim f32 vectors already resident on this GPU (e.g. torch tensor .data_ptr(), 16-byte aligned);
+        `rows` stays a host array."""
+        r = self._update_ids(rows)
+        L.check(self._lib.vdb_index_update_rows_device(self._h, _ptr(r, L.u64p), r.size, L.vp(data_ptr)))
+
     def batch_add_u8(self, rows) -> int:
         """VecSet<u8> rows (widened exactly on the way in, distance/mod.rs:79-95)."""
         r = np.ascontiguousarray(rows, dtype=np.uint8)

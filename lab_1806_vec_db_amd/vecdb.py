@@ -377,6 +377,65 @@ class VecDB:
                 del t.metadata[len(t.metadata) - len(matches):]
             return len(matches)
 
+    def update(self, key: str, pattern: dict[str, str], vec) -> int:
+        """New vector for every row `pattern` matches (batch_update with one pattern); returns the number of rows."""
+        return self.batch_update(key, [pattern], [vec])[0]
+
+    def batch_update(self, key: str, patterns, vec_list) -> list[int]:
+        """Replaces the VECTORS of existing rows in place: every row that patterns[i] matches -- a metadata pattern exactly as delete
+        takes one -- gets vec_list[i]; a row several patterns match gets the LAST one's vector.  Returns the matches per pattern.  The rows
+        keep their ids and their metadata, nothing else moves, and the table's cached filter masks stay valid (a filter is a set of rows,
+        and the set did not change).  One library call for the whole batch; like delete it clears the HNSW index and the PQ table first --
+        unless nothing matched, then nothing at all is changed.
+        Out of scope: changing the METADATA of existing rows (that needs a scattered write of the label columns).  An upsert is
+        batch_update plus batch_add of what matched nothing."""
+        t = self._t(key)
+        patterns = list(patterns)
+        for p in patterns:
+            if not isinstance(p, dict):
+                raise TypeError("update takes a metadata pattern (a dict), not a filter expression")
+        vecs = np.asarray(vec_list, dtype=np.float32)
+        if len(patterns) == 0 and vecs.size == 0:
+            return []
+        if vecs.ndim != 2 or vecs.shape[1] != t.index.dim:  # (batch_add's wording)
+            raise RuntimeError(f"Dimension mismatch: table dim {t.index.dim}, got {vecs.shape}")
+        if len(patterns) != vecs.shape[0]:
+            raise RuntimeError("patterns and vec_list differ in length")
+        with t.lock.write():
+            # the matches as delete finds them: from a cached or device-built mask when the pattern's keys are label columns already (an
+            # update gives no key a column), from the host loop otherwise; the plain patterns not cached yet share ONE make_masks_where call
+            matches: list = [None] * len(patterns)
+            todo = []
+            with t.mask_mu:
+                for i, p in enumerate(patterns):
+                    mk = t.masks.get(frozenset(p.items()))
+                    if mk is not None:
+                        matches[i] = mk.rows()[1]
+                        continue
+                    terms = t.live_terms(p)
+                    if terms is None:
+                        matches[i] = np.flatnonzero(t.host_match(p))
+                    elif has_predicates(p):
+                        mk = t.device_mask(p, terms)
+                        matches[i] = mk.rows()[1]
+                        mk.close()
+                    else:
+                        todo.append((i, terms))
+            if todo:
+                for (i, _), mk in zip(todo, t.index.make_masks_where([terms for _, terms in todo])):
+                    matches[i] = mk.rows()[1]
+                    mk.close()
+            winner: dict[int, int] = {}  # row -> the last pattern that matches it (the library wants distinct ids)
+            for i, rows in enumerate(matches):
+                for r in np.asarray(rows).tolist():
+                    winner[int(r)] = i
+            if winner:
+                t.index.hnsw_clear()
+                t.index.pq_clear()
+                rows = np.fromiter(winner.keys(), dtype=np.uint64, count=len(winner))
+                t.index.update_rows(rows, vecs[np.fromiter(winner.values(), dtype=np.int64, count=len(winner))])
+            return [int(len(m)) for m in matches]
+
     def build_hnsw_index(self, key: str, ef_construction: int | None = None) -> None:
         t = self._t(key)
         with t.lock.write():
