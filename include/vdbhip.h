@@ -449,6 +449,42 @@ int vdb_flat_knn_grouped_device(vdb_index *idx, const void *d_queries, uint64_t 
                                 void *d_out_dist, void *d_out_count, void *stream);
 int vdb_group_cap_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
                          uint32_t column, uint64_t group_size, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
+/* ---- bulk row fetch: the vectors of many rows as ONE call (no counterpart in the reference) ----------------------------------------
+ * vdb_index_row reads one row with one blocking copy.  These calls return the vectors of a LIST of rows: out[j] = row rows[j].  The
+ * list only names what is read, so its order is free and repeats are allowed (m may exceed len); every rows[j] must be below len, and a
+ * NULL list or a NULL out with m > 0, or a row at or past len, is VDB_ERR_INVALID with a message: nothing is read, `out` and the counters
+ * below are untouched.  m == 0 succeeds, touches nothing and counts nothing.
+ * vdb_fetch_plan: host utility, works without a GPU (like vdb_update_plan): how a list over a table of n rows is carried out.
+ *   *out_route = VDB_FETCH_DIRECT when the list is one ascending run of consecutive rows (rows[j] == rows[0] + j, m >= 1): the result
+ *   is a contiguous piece of the table; VDB_FETCH_GATHER otherwise.  The gathered route passes the result through a bounded staging
+ *   buffer in chunks: *out_chunk_rows = max(1, chunk_bytes / out_row_bytes) output rows each, *out_n_chunks = ceil(m / that).
+ *   out_row_bytes and chunk_bytes at least 1; m x out_row_bytes must fit 64 bits.  Any output pointer may be NULL.
+ * vdb_index_get_rows: rows are LOCAL row ids (id_offset plays no part), out is m x dim f32 row-major on the host; a VecSet<u8> index is
+ *   widened exactly ((float)byte).  On the DIRECT route of an index that needs no widening: ONE copy straight out of the table, no
+ *   kernel.  Otherwise the ids are uploaded once as u32 and per chunk one launch (csrc/k_fetch.hip) gathers the rows into one of TWO
+ *   device staging buffers, from which the chunk is copied straight into `out`; the gather of the next chunk runs while the current
+ *   one is copied.  Extra device memory: 2 x "fetch_chunk_bytes" (vdb_set_param, per index, >= 1: one row per chunk; default 128 MiB, the winner of the sweep of tools/bench_fetch.py)
+ *   plus 4 m bytes of ids, whatever m is.  No host copy of the table is built or read.
+ * vdb_index_get_rows_u8: the same with the rows as stored, m x dim bytes; a VecSet<u8> index only (as vdb_index_row_u8).
+ * vdb_index_get_rows_mask: the mask's allowed rows in ascending order, vdb_mask_count(mask) x dim f32: the mask's own id list on
+ *   the device is the gather list, nothing is uploaded.  A mask of another index is VDB_ERR_INVALID and a stale one VDB_ERR_STATE, as in
+ *   the filtered searches; an empty mask succeeds and writes nothing.
+ * vdb_index_get_rows_device: d_ids = m u64 GLOBAL ids (row + id_offset) on the index's GPU, as the *_device searches write them;
+ *   d_out = m x dim f32 there (a u8 index is widened), 4-byte aligned -- 16-byte alignment gets the 16-byte copy, anything else a
+ *   narrower one.  The ids are checked on the device first (one flag read back): an id that is no row of the index is VDB_ERR_INVALID
+ *   and d_out is untouched.  Then ONE gather launch straight into d_out.  Everything runs on `stream`; the call returns synchronised.
+ * All four are read-side: re-entrant with each other and with the searches on one handle.
+ * vdb_get_stat: "fetch_calls" (calls that fetched rows: m > 0, not refused), "fetch_rows" (rows they returned), "fetch_chunks" (gather
+ * launches: the chunks of the host forms, one per device call), "fetch_direct" (calls answered by the plain copy).
+ * Not covered: the sharded contexts, PQ codes, graph export. */
+#define VDB_FETCH_GATHER 0
+#define VDB_FETCH_DIRECT 1
+int vdb_fetch_plan(uint64_t n, const uint64_t *rows, uint64_t m, uint64_t out_row_bytes, uint64_t chunk_bytes, int *out_route,
+                   uint64_t *out_chunk_rows, uint64_t *out_n_chunks);
+int vdb_index_get_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, float *out /* m x dim, host */);
+int vdb_index_get_rows_u8(vdb_index *idx, const uint64_t *rows, uint64_t m, uint8_t *out /* m x dim, host */);
+int vdb_index_get_rows_mask(vdb_index *idx, const vdb_mask *mask, float *out /* count x dim, host */);
+int vdb_index_get_rows_device(vdb_index *idx, const void *d_ids, uint64_t m, void *d_out, void *stream);
 /* the approximate keys the Flat shortlist pass compares with its threshold, for EVERY row, from the same kernel in its dense
  * mode (test / measurement entry point behind the certification-bound tests): out_keys [nq][len];
  * L2Sqr: key = |x|^2 - 2 S~, approximate distance = key + |q|^2;  Cosine: key = -S~ / |x|, approximate distance = 1 + key / |q|.
@@ -551,6 +587,8 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *                        "mask_partition_masks": the ones vdb_mask_create_partition made; "label_count_calls":
  *                        vdb_index_label_counts calls; "label_columns": allocated columns,
  *   "update_calls"       vdb_index_update_rows / _device calls that changed rows (m > 0, not refused); "update_rows": the rows they rewrote,
+ *   "fetch_calls"        vdb_index_get_rows* calls that fetched rows (m > 0, not refused); "fetch_rows": the rows they returned;
+ *                        "fetch_chunks": their gather launches; "fetch_direct": the calls answered by one plain copy,
  *   "hbm_bytes_per_row"  resident HBM bytes per row over all per-row buffers (rows, norms, mirrors, PQ codes, level-0 links, label
  *                        columns). */
 int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out);

@@ -111,6 +111,12 @@ public:
         check(vdb_index_row(h_, i, v.data()));
         return v;
     }
+    // the vectors of many rows in one call (vdb_index_get_rows): ids.size() x dim row-major, row j = row ids[j]; any order, repeats allowed
+    std::vector<float> rows(const std::vector<uint64_t> &ids) {
+        std::vector<float> v(ids.size() * dim_);
+        check(vdb_index_get_rows(h_, ids.data(), ids.size(), v.data()));
+        return v;
+    }
 
     // add / batch_add (dynamic_index.rs:44-58): returns the index of the (first) new vector
     uint64_t add(const std::vector<float> &vec) {

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "ctx.hpp"
+#include "fetch_plan.hpp"
 #include "pq_hnsw.hpp"
 #include "remove_plan.hpp"
 #include "update_plan.hpp"
@@ -394,6 +395,18 @@ int vdb_index_update_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, cons
 int vdb_index_update_rows_device(vdb_index *idx, const uint64_t *rows, uint64_t m, const void *d_vecs) {
     VDB_API_BEGIN
     update_common(idx, rows, m, d_vecs, true);
+    VDB_API_END
+}
+int vdb_fetch_plan(uint64_t n, const uint64_t *rows, uint64_t m, uint64_t out_row_bytes, uint64_t chunk_bytes, int *out_route,
+                   uint64_t *out_chunk_rows, uint64_t *out_n_chunks) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(out_row_bytes >= 1 && chunk_bytes >= 1, "fetch_plan: out_row_bytes and chunk_bytes must be at least 1");
+    const char *why = fetch_plan_check(n, rows, m, out_row_bytes);
+    VDB_REQUIRE(!why, why);
+    const FetchPlan p = fetch_plan(rows, m, out_row_bytes, chunk_bytes);
+    if (out_route) *out_route = p.route;
+    if (out_chunk_rows) *out_chunk_rows = p.chunk_rows;
+    if (out_n_chunks) *out_n_chunks = p.n_chunks;
     VDB_API_END
 }
 int vdb_index_set_id_offset(vdb_index *idx, uint64_t offset) {
@@ -981,6 +994,48 @@ int vdb_group_cap_device(vdb_index *idx, const void *d_ids, const void *d_dists,
     VDB_API_END
 }
 
+// ---- bulk row fetch (Index::get_rows*) ----------------------------------------------------------------------------------------------
+int vdb_index_get_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, float *out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    idx->ix.get_rows(rows, m, out, true);
+    VDB_API_END
+}
+int vdb_index_get_rows_u8(vdb_index *idx, const uint64_t *rows, uint64_t m, uint8_t *out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    idx->ix.get_rows(rows, m, out, false);
+    VDB_API_END
+}
+int vdb_index_get_rows_mask(vdb_index *idx, const vdb_mask *mask, float *out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    VDB_REQUIRE(mask, "null mask");
+    idx->ix.check_mask(mask->m);
+    idx->ix.get_rows_mask(mask->m, out);
+    VDB_API_END
+}
+int vdb_index_get_rows_device(vdb_index *idx, const void *d_ids, uint64_t m, void *d_out, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    VDB_REQUIRE(m <= ~uint64_t(0) / (ix.dim * sizeof(float)), "get_rows: the result does not fit the address space");
+    if (m == 0) return VDB_OK;
+    VDB_REQUIRE(d_ids && d_out, "get_rows: null argument");
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_ids) % 8 == 0 && reinterpret_cast<uintptr_t>(d_out) % 4 == 0,
+                "get_rows: d_ids must be 8-byte and d_out 4-byte aligned");
+    ix.use_device();
+    WsLease ws(ix);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    try {
+        ix.get_rows_device(*ws, static_cast<const uint64_t *>(d_ids), m, d_out, s);
+    } catch (...) {
+        (void)hipStreamSynchronize(s);
+        throw;
+    }
+    VDB_API_END
+}
+
 int vdb_flat_range_filtered(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, const float *radius, uint64_t limit, const vdb_mask *mask,
                             vdb_range **out) {
     VDB_API_BEGIN
@@ -1128,6 +1183,10 @@ int vdb_set_param(vdb_index *idx, const char *name, int64_t value) {
     else if (n == "flat_grouped_oversample") {  // grouped k-NN: round 0 fetches min(m, k x this) rows per query
         VDB_REQUIRE(value >= 1, "flat_grouped_oversample must be >= 1");
         idx->ix.flat_grouped_oversample = (uint64_t)value;
+    }
+    else if (n == "fetch_chunk_bytes") {  // bulk row fetch: staging bytes per chunk of the gathered route (a chunk holds at least one row)
+        VDB_REQUIRE(value >= 1, "fetch_chunk_bytes must be >= 1");
+        idx->ix.fetch_chunk_bytes = (uint64_t)value;
     }
     else if (n == "debug_alloc_fail_over")  // (testing aid, process-wide) device allocations of at least this many bytes fail; 0 = off
         devbuf_fail_over() = (size_t)value;
@@ -1313,6 +1372,14 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.update_calls.load();
     else if (n == "update_rows")
         *out = idx->ix.updated_rows.load();
+    else if (n == "fetch_calls")  // vdb_index_get_rows* calls that fetched rows | rows returned | gather launches | calls answered by a plain copy
+        *out = idx->ix.fetch_calls.load();
+    else if (n == "fetch_rows")
+        *out = idx->ix.fetch_rows.load();
+    else if (n == "fetch_chunks")
+        *out = idx->ix.fetch_chunks.load();
+    else if (n == "fetch_direct")
+        *out = idx->ix.fetch_direct.load();
     else if (n == "label_columns")  // allocated label columns (4 B per row each)
         *out = idx->ix.label_columns();
     else if (n == "hbm_bytes_per_row")

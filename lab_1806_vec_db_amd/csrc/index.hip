@@ -1,5 +1,6 @@
 // index.hip -- Index object: HBM-resident VecSet + the Flat search pipeline.
 #include "index.hpp"
+#include "fetch_plan.hpp"
 #include "multi_plan.hpp"
 #include "remove_plan.hpp"
 #include "update_plan.hpp"
@@ -336,6 +337,112 @@ void Index::update_rows(const uint64_t *rows, uint64_t m, const void *vecs, bool
     rowc_gen += 1;  // the masks' copies of the row constants are stale; the masks themselves are not
     update_calls += 1;
     updated_rows += m;
+}
+
+// ---- bulk row fetch (fetch_plan.hpp, k_fetch.hip; docs/DESIGN_flat.md 4.1s) -----------------------------------------------------------
+// Chunk c is gathered into staging buffer c & 1 on ws.stream and copied to the host from there on ws.copy_stream.  The gather of chunk
+// c + 1 is enqueued BEFORE the copy of chunk c: a copy into pageable memory holds the calling thread until it is done, and the gather
+// runs meanwhile.  The copies go straight into `out` (no pinned bounce buffer of the library's: that would add a second pass over the
+// result on the host behind the runtime's own staging of pageable copies).
+void Index::fetch_gathered(Workspace &ws, const uint32_t *d_ids, uint64_t m, void *out, bool widen, uint64_t chunk_rows) {
+    const size_t out_row = widen ? size_t(dim) * sizeof(float) : size_t(dim) * elem_size();
+    const uint64_t n_chunks = m / chunk_rows + (m % chunk_rows ? 1 : 0);
+    DevBuf *stage[2] = {&ws.dense, &ws.lists};
+    stage[0]->reserve(std::min(m, chunk_rows) * out_row);
+    if (n_chunks > 1) {
+        stage[1]->reserve(chunk_rows * out_row);
+        ws.fetch_streams();
+    }
+    hipStream_t s = ws.stream, cs = n_chunks > 1 ? ws.copy_stream : ws.stream;
+    auto gather = [&](uint64_t c) {
+        const uint64_t j0 = c * chunk_rows, nb = std::min(chunk_rows, m - j0);
+        const int b = int(c & 1);
+        if (c >= 2) VDB_HIP(hipStreamWaitEvent(s, ws.fetch_ev[2 + b], 0));  // the copy that last read this buffer
+        if (widen)
+            launch_rows_gather_widen(d_rows.as<uint8_t>(), dim, d_ids + j0, false, 0, stage[b]->as<float>(), nb, num_cu, s);
+        else
+            launch_rows_gather(d_rows.p, out_row, d_ids + j0, false, 0, stage[b]->p, nb, num_cu, s);
+        if (n_chunks > 1) VDB_HIP(hipEventRecord(ws.fetch_ev[b], s));
+    };
+    try {
+        gather(0);
+        for (uint64_t c = 0; c < n_chunks; c++) {
+            if (c + 1 < n_chunks) gather(c + 1);
+            const uint64_t j0 = c * chunk_rows, nb = std::min(chunk_rows, m - j0);
+            const int b = int(c & 1);
+            if (n_chunks > 1) VDB_HIP(hipStreamWaitEvent(cs, ws.fetch_ev[b], 0));
+            VDB_HIP(hipMemcpyAsync(static_cast<char *>(out) + j0 * out_row, stage[b]->p, nb * out_row, hipMemcpyDeviceToHost, cs));
+            if (n_chunks > 1) VDB_HIP(hipEventRecord(ws.fetch_ev[2 + b], cs));
+        }
+        if (cs != s) VDB_SYNC(cs);
+        VDB_SYNC(s);
+    } catch (...) {  // nothing of a failed call still writes to the caller's memory or reads the staging buffers
+        if (cs != s) (void)hipStreamSynchronize(cs);
+        (void)hipStreamSynchronize(s);
+        throw;
+    }
+}
+
+void Index::get_rows(const uint64_t *rows, uint64_t m, void *out, bool as_f32) {
+    VDB_REQUIRE(as_f32 || elem_u8, "not a VecSet<u8> index");
+    const bool widen = as_f32 && elem_u8;
+    const uint64_t out_row = as_f32 ? dim * sizeof(float) : dim;
+    const char *why = fetch_plan_check(n, rows, m, out_row);
+    VDB_REQUIRE(!why, why);
+    if (m == 0) return;
+    VDB_REQUIRE(out, "get_rows: null out");
+    VDB_REQUIRE(n <= (1ull << 32), "get_rows: a shard holds at most 2^32 rows");
+    const FetchPlan plan = fetch_plan(rows, m, out_row, fetch_chunk_bytes);
+    use_device();
+    WsLease ws(*this);
+    hipStream_t s = ws->stream;
+    if (plan.route == FETCH_DIRECT && !widen) {  // a contiguous piece of the table, as it stands
+        VDB_HIP(hipMemcpyAsync(out, d_rows.as<char>() + rows[0] * out_row, m * out_row, hipMemcpyDeviceToHost, s));
+        VDB_SYNC(s);
+        fetch_direct += 1;
+    } else {
+        std::vector<uint32_t> h_ids(m);
+        for (uint64_t j = 0; j < m; j++) h_ids[j] = (uint32_t)rows[j];
+        ws->keys_a.reserve(m * sizeof(uint32_t));
+        VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_ids.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        fetch_gathered(*ws, ws->keys_a.as<uint32_t>(), m, out, widen, plan.chunk_rows);  // (synchronised: h_ids may go)
+        fetch_chunks += plan.n_chunks;
+    }
+    fetch_calls += 1;
+    fetch_rows += m;
+}
+
+void Index::get_rows_mask(const RowMask &mask, float *out) {
+    const uint64_t m = mask.m, out_row = dim * sizeof(float);
+    VDB_REQUIRE(m <= ~uint64_t(0) / out_row, "get_rows: the result does not fit the address space");
+    if (m == 0) return;
+    VDB_REQUIRE(out, "get_rows: null out");
+    const FetchPlan plan = fetch_plan_chunks(m, out_row, fetch_chunk_bytes);
+    use_device();
+    WsLease ws(*this);
+    fetch_gathered(*ws, mask.d_ids.as<uint32_t>(), m, out, elem_u8, plan.chunk_rows);
+    fetch_chunks += plan.n_chunks;
+    fetch_calls += 1;
+    fetch_rows += m;
+}
+
+void Index::get_rows_device(Workspace &ws, const uint64_t *d_ids, uint64_t m, void *d_out, hipStream_t s) {
+    ws.flags.reserve(sizeof(uint32_t));
+    uint32_t *d_flag = ws.flags.as<uint32_t>();
+    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+    launch_fetch_check(d_ids, m, n, id_offset, d_flag, num_cu, s);
+    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
+    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDB_SYNC(s);
+    VDB_REQUIRE(*h_flag == 0, "get_rows: the list holds an id that is no row of this index (id - id_offset must be below len)");
+    if (elem_u8)
+        launch_rows_gather_widen(d_rows.as<uint8_t>(), dim, d_ids, true, id_offset, static_cast<float *>(d_out), m, num_cu, s);
+    else
+        launch_rows_gather(d_rows.p, dim * sizeof(float), d_ids, true, id_offset, d_out, m, num_cu, s);
+    VDB_SYNC(s);
+    fetch_chunks += 1;
+    fetch_calls += 1;
+    fetch_rows += m;
 }
 
 // ---- label columns and the masks built from them (k_labels.hip) ----------------------------------------------------------------------

@@ -142,6 +142,15 @@ struct Workspace {
     void *h_pinned = nullptr;
     size_t h_pinned_cap = 0;
     hipEvent_t order_ev = nullptr;  // orders this workspace's stream behind a caller's stream without a host wait (vdb_*_begin)
+    // bulk row fetch (Index::fetch_gathered): the stream its device-to-host copies run on while `stream` gathers the next chunk, and
+    // per staging buffer the events "gathered" / "copied out".  Made by the first fetch that has more than one chunk.
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t fetch_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    void fetch_streams() {
+        if (!copy_stream) VDB_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+        for (auto &e : fetch_ev)
+            if (!e) VDB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
     // The block stays valid until the next pinned() call of a larger size, which waits for `stream` before it frees the block: nothing
     // enqueued on the stream still uses it then.  (Mirror builds never take it: they read their results into storage of their own.)
     void *pinned(size_t bytes) {
@@ -165,6 +174,9 @@ struct Workspace {
     ~Workspace() {
         if (h_pinned) (void)hipHostFree(h_pinned);
         if (order_ev) (void)hipEventDestroy(order_ev);
+        for (auto &e : fetch_ev)
+            if (e) (void)hipEventDestroy(e);
+        if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (auto &e : ev_pool) {
             (void)hipEventDestroy(e.first);
             (void)hipEventDestroy(e.second);
@@ -490,6 +502,26 @@ struct Index {
     static constexpr size_t UPDATE_STAGE_BYTES = size_t(64) << 20;  // host vectors are staged through at most this much of ws.dense at a time
     std::atomic<uint64_t> rowc_gen{0};  // bumped by update_rows: what a RowMask's d_rowc copy is checked against (with the allocation)
     std::atomic<uint64_t> update_calls{0}, updated_rows{0};  // update_rows calls that changed rows / rows they rewrote
+    // Bulk row fetch (fetch_plan.hpp, k_fetch.hip; docs/DESIGN_flat.md 4.1s): out[j] = LOCAL row rows[j], m rows on the host, in any order,
+    // repeats allowed.  as_f32: f32 output (a u8 index is widened, exactly); else the u8 rows as stored (u8 index only).  The list is
+    // checked before anything is touched.  A run of consecutive rows that needs no conversion is ONE copy out of d_rows; everything
+    // else uploads the ids once (u32) and goes through fetch_gathered.  Read-side and re-entrant: workspace from acquire_ws, no index state
+    // written but the counters, h_rows neither read nor built.  Returns synchronised.
+    void get_rows(const uint64_t *rows, uint64_t m, void *out, bool as_f32);
+    // the mask's allowed rows, ascending, as f32: the ids are the mask's own d_ids, nothing is uploaded.  The caller ran check_mask.
+    void get_rows_mask(const RowMask &mask, float *out);
+    // d_ids: m u64 GLOBAL ids on the device (row + id_offset), d_out: m x dim f32 on the device, any alignment.  k_fetch_check and one
+    // read-back of its flag first -- an id that is no row of the index throws with d_out untouched --, then ONE gather launch straight
+    // into d_out, all on `s`.  Returns synchronised.
+    void get_rows_device(Workspace &ws, const uint64_t *d_ids, uint64_t m, void *d_out, hipStream_t s);
+    // The chunk loop of the host forms: d_ids (u32, local, checked) -> `out` through TWO staging buffers of the workspace (ws.dense,
+    // ws.lists; chunk_rows output rows each, so at most 2 x fetch_chunk_bytes whatever m is): chunk c + 1 is gathered on ws.stream while
+    // chunk c is copied to the host on ws.copy_stream.  widen: u8 rows -> f32 output.  Returns synchronised, also when it throws.
+    void fetch_gathered(Workspace &ws, const uint32_t *d_ids, uint64_t m, void *out, bool widen, uint64_t chunk_rows);
+    static constexpr uint64_t FETCH_CHUNK_BYTES_DEFAULT = uint64_t(128) << 20;  // the winner of the sweep of tools/bench_fetch.py
+    uint64_t fetch_chunk_bytes = FETCH_CHUNK_BYTES_DEFAULT;  // "fetch_chunk_bytes": staging bytes per chunk (at least one row)
+    // calls that fetched rows (m > 0, not refused) / rows they returned / gather launches / calls answered by a copy with no kernel
+    std::atomic<uint64_t> fetch_calls{0}, fetch_rows{0}, fetch_chunks{0}, fetch_direct{0};
 
     // timing hooks
     void prof_begin(Workspace &ws, const char *name, double bytes);

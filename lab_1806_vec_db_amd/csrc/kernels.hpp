@@ -269,6 +269,15 @@ void launch_rows_move(void *rows, uint64_t row_bytes, float *sq, const uint32_t 
 // k_update.hip: row j of src (m contiguous rows) -> row ids[j] of `rows` and sq_new[j] -> sq[ids[j]]; the ids are distinct (update_plan.hpp)
 void launch_rows_scatter(void *rows, uint64_t row_bytes, float *sq, const uint32_t *ids, const void *src, const float *sq_new, uint64_t m,
                          int num_cu, hipStream_t s);
+// k_fetch.hip: row ids[j] - id_offset of `rows` -> row j of dst (m contiguous rows); ids: u32 local rows (id_offset 0) or, ids_u64, u64
+// global ids; any order, repeats allowed; the ids are checked by the caller (fetch_plan.hpp, launch_fetch_check).  dst of any alignment.
+void launch_rows_gather(const void *rows, uint64_t row_bytes, const void *ids, bool ids_u64, uint64_t id_offset, void *dst, uint64_t m,
+                        int num_cu, hipStream_t s);
+// ... over u8 rows of `dim` bytes into f32 output rows, (float)byte
+void launch_rows_gather_widen(const uint8_t *rows, uint64_t dim, const void *ids, bool ids_u64, uint64_t id_offset, float *dst, uint64_t m,
+                              int num_cu, hipStream_t s);
+// *flag = 1 when some ids[j] - id_offset is not in [0, n) (flag zeroed by the caller)
+void launch_fetch_check(const uint64_t *ids, uint64_t m, uint64_t n, uint64_t id_offset, uint32_t *flag, int num_cu, hipStream_t s);
 void launch_query_prep_i8(const float *Q, uint32_t nq, uint32_t nq_pad, uint32_t dim, const float *mu, float l1, float l2, float *qsq,
                           float *qscale, float *qoff, uint32_t *hits, void *qfrag, hipStream_t s, int cosine = 0);
 // k_redo.hip: second attempts of a Flat call

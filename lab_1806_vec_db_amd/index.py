@@ -81,6 +81,7 @@ LABEL_COLUMNS = 16         # VDB_LABEL_COLUMNS
 LABEL_NONE = 0xFFFFFFFF    # VDB_LABEL_NONE
 MASK_MAX_TERMS = 8         # VDB_MASK_MAX_TERMS
 MASK_OP_AND, MASK_OP_OR = 0, 1  # VDB_MASK_OP_AND / VDB_MASK_OP_OR
+FETCH_CHUNK_BYTES_DEFAULT = 128 << 20  # what "fetch_chunk_bytes" is until set_param changes it (Index::FETCH_CHUNK_BYTES_DEFAULT)
 
 
 def _terms_arrays(terms):
@@ -221,10 +222,67 @@ class GpuIndex:
         L.check(self._lib.vdb_index_dist(self._h, C.byref(v)))
         return int(v.value)
 
-    def __getitem__(self, i: int) -> np.ndarray:
+    def __getitem__(self, i) -> np.ndarray:
+        """index[i]: one row (vdb_index_row); index[a:b:c] or index[array of row ids]: those rows, (m, dim), through get_rows"""
+        if isinstance(i, slice):
+            return self.get_rows(np.arange(*i.indices(len(self)), dtype=np.int64))
+        if isinstance(i, (np.ndarray, list, tuple)):
+            a = np.asarray(i)
+            if a.dtype == np.bool_:
+                raise IndexError("index[...]: row ids are needed, not a bool mask")
+            if a.size and np.issubdtype(a.dtype, np.signedinteger):
+                a = np.where(a < 0, a + len(self), a)  # (what is still negative is refused below)
+            return self.get_rows(a)
         out = np.empty(self.dim, dtype=np.float32)
         L.check(self._lib.vdb_index_row(self._h, int(i), _ptr(out, L.f32p)))
         return out
+
+    @staticmethod
+    def _fetch_ids(rows) -> np.ndarray:
+        a = np.asarray(rows).reshape(-1)
+        if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError("get_rows: an array of integer row ids is needed")
+        if a.size and np.issubdtype(a.dtype, np.signedinteger) and int(a.min()) < 0:
+            raise ValueError("get_rows: negative row id")
+        return np.ascontiguousarray(a.astype(np.uint64))
+
+    def get_rows(self, rows, out: np.ndarray | None = None) -> np.ndarray:
+        """The vectors of many rows in ONE call (vdb_index_get_rows): (len(rows), dim) f32, row j = local row rows[j]; a u8 index is
+        widened.  `rows` in any order, repeats allowed (bool / float / negative ids raise ValueError, an id at or past len VdbError).
+        `out`: a C-contiguous float32 array of that shape to fill instead of a new one."""
+        r = self._fetch_ids(rows)
+        if out is None:
+            out = np.empty((r.size, self.dim), dtype=np.float32)
+        elif out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != (r.size, self.dim):
+            raise ValueError(f"get_rows: out must be a C-contiguous float32 array of shape {(r.size, self.dim)}")
+        L.check(self._lib.vdb_index_get_rows(self._h, _ptr(r, L.u64p), r.size, _ptr(out, L.f32p)))
+        return out
+
+    def get_rows_u8(self, rows, out: np.ndarray | None = None) -> np.ndarray:
+        """The same for a u8 index, rows as stored: (len(rows), dim) uint8 (vdb_index_get_rows_u8; refused on an f32 index)."""
+        r = self._fetch_ids(rows)
+        if out is None:
+            out = np.empty((r.size, self.dim), dtype=np.uint8)
+        elif out.dtype != np.uint8 or not out.flags.c_contiguous or out.shape != (r.size, self.dim):
+            raise ValueError(f"get_rows_u8: out must be a C-contiguous uint8 array of shape {(r.size, self.dim)}")
+        L.check(self._lib.vdb_index_get_rows_u8(self._h, _ptr(r, L.u64p), r.size, _ptr(out, L.u8p)))
+        return out
+
+    def get_rows_mask(self, mask: "RowMask", out: np.ndarray | None = None) -> np.ndarray:
+        """The vectors of the rows a mask allows, ascending by row: (len(mask), dim) f32 (vdb_index_get_rows_mask).  The mask's id list
+        on the device is the gather list; a stale mask or one of another index raises VdbError as in the filtered searches."""
+        if out is None:
+            out = np.empty((len(mask), self.dim), dtype=np.float32)
+        elif out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != (len(mask), self.dim):
+            raise ValueError(f"get_rows_mask: out must be a C-contiguous float32 array of shape {(len(mask), self.dim)}")
+        L.check(self._lib.vdb_index_get_rows_mask(self._h, mask._h, _ptr(out, L.f32p)))
+        return out
+
+    def get_rows_device(self, ids_ptr: int, m: int, out_ptr: int, stream: int = 0):
+        """Device form (vdb_index_get_rows_device): `ids_ptr` -> m u64 GLOBAL ids on this GPU (row + id_offset, as the *_device searches
+        write them), `out_ptr` -> m x dim f32 there (e.g. torch tensor .data_ptr(); any 4-byte alignment).  An id that is no row of the
+        index raises VdbError and the output is untouched.  Runs on `stream`, returns synchronised."""
+        L.check(self._lib.vdb_index_get_rows_device(self._h, L.vp(ids_ptr), int(m), L.vp(out_ptr), L.vp(stream)))
 
     # -- IndexBuilder ----------------------------------------------------------------------------------
     def add(self, vec) -> int:

@@ -31,6 +31,8 @@ count(key, filter) is the number of matching rows (the mask's count); count_by(k
 metadata key, from one pass over the key's label column on the device (GpuIndex.label_counts).
 search / batch_search take `group_by`, a metadata key, and `group_size`: at most that many hits per value of the key, nearest first, rows
 without the key always kept -- exact, from the Flat rows, in one library call over the key's label column (GpuIndex.flat_knn_grouped).
+get(key, filter, limit) returns the vectors and metadata of the matching rows, and every search takes `with_vectors`: the hits' vectors
+ride along, all of a call's from one bulk fetch (GpuIndex.get_rows / get_rows_mask); extract_data reads the table with one such call.
 """
 from __future__ import annotations
 
@@ -489,22 +491,25 @@ class VecDB:
 
     # ---- reads ------------------------------------------------------------------------------------------------
     def search(self, key: str, query, k: int, ef: int | None = None, upper_bound: float | None = None,
-               filter: dict[str, str] | None = None, group_by: str | None = None, group_size: int = 1):
+               filter: dict[str, str] | None = None, group_by: str | None = None, group_size: int = 1, with_vectors: bool = False):
         """MetadataVecTable::search.  `filter`: a metadata pattern matched exactly as delete matches (every key present with an equal
         value; an empty pattern matches every row) -- only matching rows are searched.  With a filter the answer is always EXACT, from
         the table's Flat rows, whatever indexes the table has, and `ef` is ignored.  `group_by`: a metadata key -- at most `group_size`
-        hits per value of it (batch_search states the rule); exact as with a filter, same return shape."""
+        hits per value of it (batch_search states the rule); exact as with a filter, same return shape.  `with_vectors`: entries become
+        (metadata, distance, vector) -- the hits' vectors (float32 arrays) from ONE get_rows call over the hit ids."""
         t = self._t(key)
         ix = t.index
         q = np.asarray(query, dtype=np.float32).ravel()
         if group_by is not None:
-            return self.batch_search(key, q.reshape(1, -1), k, ef, upper_bound, filter, group_by, group_size)[0]
+            return self.batch_search(key, q.reshape(1, -1), k, ef, upper_bound, filter, group_by, group_size, with_vectors)[0]
         if filter is not None:
             t.prepare([filter])
         with t.lock.read():  # database/mod.rs:255: read guard for the whole search, metadata lookup included
             if filter is not None:
                 idx, dist = ix.flat_knn_filtered(q, k, t.mask_for(filter))
                 ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
+                if with_vectors:
+                    return self._hits_with_vectors(t, [idx], [dist], ub)[0]
                 return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist) if d <= ub]
             if ef is not None and ix.has_pq():
                 idx, dist = ix.knn_pq(q, k, ef)
@@ -513,10 +518,12 @@ class VecDB:
             else:
                 idx, dist = ix.knn(q, k)
             ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
+            if with_vectors:
+                return self._hits_with_vectors(t, [idx], [dist], ub)[0]
             return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist) if d <= ub]
 
     def batch_search(self, key: str, queries, k: int, ef: int | None = None, upper_bound: float | None = None, filters=None,
-                     group_by: str | None = None, group_size: int = 1):
+                     group_by: str | None = None, group_size: int = 1, with_vectors: bool = False):
         """search for a batch of queries in ONE library call: entry q of the returned list is what search(key, queries[q], k, ef,
         upper_bound, filter) returns.  `filters`: None, ONE metadata pattern for every query, or a list of len(queries) patterns (the
         multi-tenant batch: every query restricted to its own rows; {} matches every row).  With filters the answers are exact, from
@@ -527,7 +534,9 @@ class VecDB:
         exact, from the Flat rows (`ef` is ignored), a flat list as without it; `upper_bound` is applied afterwards.  The key gets a label
         column on first use, as count_by's field does, and the batch is ONE flat_knn_grouped call (under the filters' masks when there
         are filters).  A key that cannot have a column (a 17th key) or whose values a dictionary cannot keep apart takes the host
-        fallback: the ungrouped search at a growing k, walked by labels.cap_groups over the metadata values."""
+        fallback: the ungrouped search at a growing k, walked by labels.cap_groups over the metadata values.
+        `with_vectors`: entries become (metadata, distance, vector); the vectors of all hits of the batch come from ONE get_rows call
+        over the hit ids (no call when the batch has no hit)."""
         if group_by is not None and int(group_size) < 1:
             raise ValueError("group_size must be at least 1")
         t = self._t(key)
@@ -574,6 +583,8 @@ class VecDB:
             else:
                 idx, dist, cnt = ix.knn(q, k)
             ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
+            if with_vectors:
+                return self._hits_with_vectors(t, [idx[j, :int(cnt[j])] for j in range(nq)], [dist[j, :int(cnt[j])] for j in range(nq)], ub)
             return [[(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx[j, :int(cnt[j])], dist[j, :int(cnt[j])]) if d <= ub]
                     for j in range(nq)]
 
@@ -615,11 +626,12 @@ class VecDB:
                 return o_idx[:, :k], o_dist[:, :k], o_cnt
             kk = min(kk * 4, n)
 
-    def search_within(self, key: str, query, upper_bound: float, limit: int | None = None, filter: dict[str, str] | None = None):
+    def search_within(self, key: str, query, upper_bound: float, limit: int | None = None, filter: dict[str, str] | None = None,
+                      with_vectors: bool = False):
         """Every row within `upper_bound` of the query (distance <= upper_bound, as search's filter compares), nearest first: what
         search(k, upper_bound=...) returns once k covers the whole set, without having to guess k.  Always answered exactly from the
         table's rows (FlatIndex::knn distances), whatever indexes the table has.  `limit`: at most that many, the nearest ones.
-        `filter`: a metadata pattern as in search -- only matching rows are returned."""
+        `filter`: a metadata pattern as in search -- only matching rows are returned.  `with_vectors`: as in search."""
         t = self._t(key)
         q = np.asarray(query, dtype=np.float32).ravel()
         if filter is not None:
@@ -627,15 +639,19 @@ class VecDB:
         with t.lock.read():
             if filter is not None:
                 _, idx, dist = t.index.range_search(q, np.float32(upper_bound), limit, mask=t.mask_for(filter))
+                if with_vectors:
+                    return self._hits_with_vectors(t, [idx], [dist], None)[0]
                 return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist)]
             _, idx, dist = t.index.range_search(q, np.float32(upper_bound), limit)
+            if with_vectors:
+                return self._hits_with_vectors(t, [idx], [dist], None)[0]
             return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist)]
 
-    def batch_search_within(self, key: str, queries, upper_bound, limit: int | None = None, filters=None):
+    def batch_search_within(self, key: str, queries, upper_bound, limit: int | None = None, filters=None, with_vectors: bool = False):
         """search_within for a batch of queries in ONE library call: entry q of the returned list is what search_within(key,
         queries[q], upper_bound[q], limit, filter_q) returns.  `upper_bound`: one value, or one per query.  `filters`: None, ONE
         metadata pattern for every query, or a list of len(queries) patterns ({} matches every row).  With filters the batch is one
-        range_search_multi call over one mask per distinct pattern; without, one range_search call."""
+        range_search_multi call over one mask per distinct pattern; without, one range_search call.  `with_vectors`: as in batch_search."""
         t = self._t(key)
         ix = t.index
         q = np.asarray(queries, dtype=np.float32)
@@ -669,6 +685,9 @@ class VecDB:
                 lims, idx, dist = ix.range_search_multi(q, ub, masks, mask_of, limit)
             else:
                 lims, idx, dist = ix.range_search(q, ub, limit)
+            if with_vectors:
+                return self._hits_with_vectors(t, [idx[int(lims[j]):int(lims[j + 1])] for j in range(nq)],
+                                               [dist[int(lims[j]):int(lims[j + 1])] for j in range(nq)], None)
             return [[(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx[int(lims[j]):int(lims[j + 1])], dist[int(lims[j]):int(lims[j + 1])])]
                     for j in range(nq)]
 
@@ -699,10 +718,48 @@ class VecDB:
             rows = range(len(t.metadata)) if mk is None else mk.rows()[1].tolist()
             return dict(collections.Counter(t.metadata[i].get(field) for i in rows))
 
+    def get(self, key: str, filter=None, limit: int | None = None):
+        """(vectors, metadata) of the rows that match `filter`, ascending by row: an (m, dim) float32 array and the list of the rows'
+        metadata dicts.  `filter`: a pattern, a pattern with predicates or an expression, resolved exactly as count resolves it; None:
+        every row.  `limit`: the first `limit` matching rows.  The vectors come from ONE library call under the read lock
+        (GpuIndex.get_rows_mask over the filter's cached mask; get_rows over a run of rows without a filter or under a limit)."""
+        if limit is not None and int(limit) < 0:
+            raise ValueError("limit must be at least 0")
+        t = self._t(key)
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.read():
+            ix = t.index
+            if filter is None:
+                m = len(ix) if limit is None else min(int(limit), len(ix))
+                return ix.get_rows(np.arange(m, dtype=np.uint64)), [dict(x) for x in t.metadata[:m]]
+            mk = t.mask_for(filter)
+            if limit is None or int(limit) >= len(mk):
+                rows = mk.rows()[1]
+                return ix.get_rows_mask(mk), [dict(t.metadata[int(i)]) for i in rows]
+            rows = mk.rows()[1][:int(limit)]
+            return ix.get_rows(rows), [dict(t.metadata[int(i)]) for i in rows]
+
     def extract_data(self, key: str):
         t = self._t(key)
         with t.lock.read():
-            return [(t.index[i].tolist(), dict(t.metadata[i])) for i in range(len(t.index))]
+            n = len(t.index)
+            vecs = t.index.get_rows(np.arange(n, dtype=np.uint64))  # ONE call (a run of rows: one copy out of the table)
+            return [(vecs[i].tolist(), dict(t.metadata[i])) for i in range(n)]
+
+    @staticmethod
+    def _hits_with_vectors(t: _Table, idx_per_query, dist_per_query, ub):
+        """UNDER THE READ LOCK: per query the entries (metadata, distance, vector) of its hits (ids / distances already cut at the
+        query's count) with distance <= ub (None: all of them).  The vectors of all hits of the call come from ONE get_rows call over
+        the hit ids; a call without a hit makes none."""
+        hits = [[(int(i), float(d)) for i, d in zip(ids, ds) if ub is None or d <= ub] for ids, ds in zip(idx_per_query, dist_per_query)]
+        flat = np.fromiter((i for h in hits for i, _ in h), dtype=np.uint64)
+        vecs = t.index.get_rows(flat) if flat.size else np.zeros((0, t.index.dim), dtype=np.float32)
+        out, at = [], 0
+        for h in hits:
+            out.append([(dict(t.metadata[i]), d, vecs[at + r].copy()) for r, (i, d) in enumerate(h)])
+            at += len(h)
+        return out
 
 
 __all__ = ["VecDB", "VdbError"]
