@@ -381,6 +381,50 @@ int vdb_flat_range_filtered_multi_device(vdb_index *idx, const void *d_queries, 
 #define VDB_MASK_MAX_TERMS 8
 int vdb_index_labels_set(vdb_index *idx, uint32_t column, uint64_t first_row, const uint32_t *codes, uint64_t count);
 int vdb_index_labels_get(const vdb_index *idx, uint32_t column, uint64_t first_row, uint64_t count, uint32_t *out);
+/* ---- scattered label writes: the metadata of existing rows changed in place (no counterpart in the reference) -----------------------
+ * vdb_index_labels_set copies one contiguous range of one column.  These calls write label[columns[c]][row] for rows that are no run,
+ * n_cols columns in ONE kernel launch (csrc/k_labels.hip: k_labels_scatter, k_labels_set_mask; docs/DESIGN_flat.md 4.1t) and without a
+ * host copy of a column: a lane owns one list entry, loads its row id once and stores one code per column with plain stores.
+ * vdb_labels_scatter_plan: host utility, works without a GPU (like vdb_update_plan): the argument check of the list form over a table of
+ *   n rows (n <= 2^32) -- n_cols in 1 .. VDB_LABEL_COLUMNS, every column below VDB_LABEL_COLUMNS and named once, rows distinct and below
+ *   n, no NULL array with m > 0 -- and the ids as they are uploaded: out_ids32[j] = (uint32_t)rows[j].  out_ids32 may be NULL (check
+ *   only).  On any error nothing is written.
+ * vdb_index_labels_scatter: label[columns[c]][rows[j]] = codes[c * m + j]; rows are m DISTINCT LOCAL row ids on the host in any order
+ *   (a duplicate is refused, as vdb_index_update_rows refuses it), codes [n_cols][m] on the host.  Ids (as u32) and codes are uploaded
+ *   once each through workspace buffers: no allocation per call once the workspace has grown.
+ * vdb_index_labels_scatter_device: d_ids = m u64 GLOBAL ids (row + id_offset) on the index's GPU, 8-byte aligned, exactly as
+ *   vdb_flat_knn_device writes them; d_codes = u32 [n_cols][m] there; `columns` on the host.  Both arrays must be complete when the call
+ *   is made (it runs on a stream of the library's).  The ids are range-checked on the device first (one flag read back): an id that is no
+ *   row of the index is VDB_ERR_INVALID and nothing is written.  An id named twice with different codes gets one of them, whole; which
+ *   one is unspecified.
+ * vdb_index_labels_set_mask: label[columns[c]][r] = codes[c] for every row r the mask allows and every c < n_cols.  The list is the
+ *   mask's own id list on the device and the (column, code) pairs travel as kernel arguments: nothing is uploaded.  A mask of another
+ *   index is VDB_ERR_INVALID and a stale one VDB_ERR_STATE, as in the filtered searches.
+ * Rules of all three:
+ *   Check before write: everything is checked before anything is written or allocated.  On VDB_ERR_INVALID (and on VDB_ERR_STATE for a
+ *   stale mask) no column has changed, no column has come to life ("label_columns" is unchanged) and no counter has moved.
+ *   First write allocates: a target column never written before comes to life as in vdb_index_labels_set -- allocated for len rows,
+ *   VDB_LABEL_NONE everywhere -- and then the listed rows are written.
+ *   Empty calls: m == 0 (a mask without rows) succeeds, writes and allocates nothing and counts nothing; n_cols == 0 with m > 0 is
+ *   VDB_ERR_INVALID, as are n_cols > VDB_LABEL_COLUMNS, a column >= VDB_LABEL_COLUMNS, a column named twice, a row >= len and a NULL
+ *   array with m > 0.
+ *   Codes: any u32; VDB_LABEL_NONE is legal and takes the value away from the row.
+ *   They work on f32 and VecSet<u8> indexes alike.
+ *   Write-side with respect to everything that reads label columns (vdb_mask_create_where*, vdb_mask_create_partition,
+ *   vdb_index_label_counts, the grouped searches); they return synchronised.  They do NOT make masks stale: masks made before the call
+ *   stay valid and keep selecting the rows they selected (a mask is a set of rows), vectors and mirrors are untouched, PQ / HNSW / IVF
+ *   state is untouched.
+ * vdb_get_stat: "labels_scatter_calls" (calls of the three that wrote rows: m > 0, not refused), "labels_scatter_rows" (rows they
+ * wrote), "labels_scatter_span" (list entries one launch covers before its grid-stride loop wraps: 256 x 8 blocks per CU, or 256 x
+ * "labels_scatter_max_blocks" when vdb_set_param gave one).  vdb_prof_get "labels_scatter" times the two kernels.
+ * Not covered: the sharded contexts. */
+int vdb_labels_scatter_plan(uint64_t n, const uint64_t *rows, uint64_t m, const uint32_t *columns, uint64_t n_cols, uint32_t *out_ids32);
+int vdb_index_labels_scatter(vdb_index *idx, const uint64_t *rows /* host, LOCAL, distinct */, uint64_t m, const uint32_t *columns,
+                             uint64_t n_cols, const uint32_t *codes /* host, [n_cols][m] */);
+int vdb_index_labels_scatter_device(vdb_index *idx, const void *d_ids /* u64 GLOBAL ids, 8-B aligned */, uint64_t m,
+                                    const uint32_t *columns /* host */, uint64_t n_cols, const void *d_codes /* u32 [n_cols][m] */);
+int vdb_index_labels_set_mask(vdb_index *idx, const vdb_mask *mask, const uint32_t *columns, const uint32_t *codes /* one per column */,
+                              uint64_t n_cols);
 int vdb_mask_create_where(vdb_index *idx, const uint32_t *columns, const uint32_t *codes, uint64_t n_terms, vdb_mask **out);
 int vdb_mask_create_where_many(vdb_index *idx, const uint64_t *term_lims, const uint32_t *columns, const uint32_t *codes,
                                uint64_t n_masks, vdb_mask **out);

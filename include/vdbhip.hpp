@@ -194,6 +194,16 @@ public:
     void set_labels(uint32_t column, const std::vector<uint32_t> &codes, uint64_t first_row = 0) {
         check(vdb_index_labels_set(h_, column, first_row, codes.data(), codes.size()));
     }
+    // scattered label writes: codes[c * rows.size() + j] to column columns[c] of row rows[j] (vdb_index_labels_scatter; distinct LOCAL
+    // rows, distinct columns), and codes[c] to column columns[c] of every row a mask allows (vdb_index_labels_set_mask)
+    void set_labels_rows(const std::vector<uint64_t> &rows, const std::vector<uint32_t> &columns, const std::vector<uint32_t> &codes) {
+        if (codes.size() != rows.size() * columns.size()) throw std::invalid_argument("set_labels_rows: codes is columns x rows");
+        check(vdb_index_labels_scatter(h_, rows.data(), rows.size(), columns.data(), columns.size(), codes.data()));
+    }
+    void set_labels_mask(const Mask &mask, const std::vector<uint32_t> &columns, const std::vector<uint32_t> &codes) {
+        if (codes.size() != columns.size()) throw std::invalid_argument("set_labels_mask: one code per column");
+        check(vdb_index_labels_set_mask(h_, mask.handle(), columns.data(), codes.data(), columns.size()));
+    }
     Mask make_mask_where(const std::vector<std::pair<uint32_t, uint32_t>> &terms) const {
         std::vector<uint32_t> cols, codes;
         for (const auto &t : terms) {

@@ -58,6 +58,10 @@ SIGNATURES = {
     "vdb_mask_destroy": [vp],
     "vdb_index_labels_set": [vp, C.c_uint32, u64, u32p, u64],
     "vdb_index_labels_get": [vp, C.c_uint32, u64, u64, u32p],
+    "vdb_labels_scatter_plan": [u64, u64p, u64, u32p, u64, u32p],
+    "vdb_index_labels_scatter": [vp, u64p, u64, u32p, u64, u32p],
+    "vdb_index_labels_scatter_device": [vp, vp, u64, u32p, u64, vp],
+    "vdb_index_labels_set_mask": [vp, vp, u32p, u32p, u64],
     "vdb_mask_create_where": [vp, u32p, u32p, u64, C.POINTER(vp)],
     "vdb_mask_create_where_many": [vp, u64p, u32p, u32p, u64, C.POINTER(vp)],
     "vdb_mask_create_where_sets": [vp, u32p, u32p, u32p, u32p, u64p, u64p, u64, C.POINTER(vp)],

@@ -699,6 +699,35 @@ int vdb_index_labels_get(const vdb_index *idx, uint32_t column, uint64_t first_r
     idx->ix.labels_get(column, first_row, count, out);
     VDB_API_END
 }
+// ---- scattered label writes (Index::labels_scatter*, labels_set_mask) -------------------------------------------------------------------
+int vdb_labels_scatter_plan(uint64_t n, const uint64_t *rows, uint64_t m, const uint32_t *columns, uint64_t n_cols, uint32_t *out_ids32) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(n <= (1ull << 32), "labels_scatter_plan: a shard holds at most 2^32 rows");
+    const char *why = labels_scatter_check(n, rows, m, columns, n_cols);
+    VDB_REQUIRE(!why, why);
+    if (out_ids32) labels_scatter_ids(rows, m, out_ids32);
+    VDB_API_END
+}
+int vdb_index_labels_scatter(vdb_index *idx, const uint64_t *rows, uint64_t m, const uint32_t *columns, uint64_t n_cols, const uint32_t *codes) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    idx->ix.labels_scatter(rows, m, columns, n_cols, codes);
+    VDB_API_END
+}
+int vdb_index_labels_scatter_device(vdb_index *idx, const void *d_ids, uint64_t m, const uint32_t *columns, uint64_t n_cols, const void *d_codes) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    idx->ix.labels_scatter_device(static_cast<const uint64_t *>(d_ids), m, columns, n_cols, static_cast<const uint32_t *>(d_codes));
+    VDB_API_END
+}
+int vdb_index_labels_set_mask(vdb_index *idx, const vdb_mask *mask, const uint32_t *columns, const uint32_t *codes, uint64_t n_cols) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    VDB_REQUIRE(mask, "null mask");
+    idx->ix.check_mask(mask->m);
+    idx->ix.labels_set_mask(mask->m, columns, codes, n_cols);
+    VDB_API_END
+}
 int vdb_mask_create_where_many(vdb_index *idx, const uint64_t *term_lims, const uint32_t *columns, const uint32_t *codes, uint64_t n_masks,
                                vdb_mask **out) {
     VDB_API_BEGIN
@@ -1188,6 +1217,10 @@ int vdb_set_param(vdb_index *idx, const char *name, int64_t value) {
         VDB_REQUIRE(value >= 1, "fetch_chunk_bytes must be >= 1");
         idx->ix.fetch_chunk_bytes = (uint64_t)value;
     }
+    else if (n == "labels_scatter_max_blocks") {  // scattered label writes: grid cap of their kernels (0: 8 blocks per CU); a small cap makes the grid-stride loop wrap at a small list (tests)
+        VDB_REQUIRE(value >= 0 && value <= 0x7FFFFFFF, "labels_scatter_max_blocks must be in 0 .. 2^31-1");
+        idx->ix.labels_scatter_max_blocks = (uint32_t)value;
+    }
     else if (n == "debug_alloc_fail_over")  // (testing aid, process-wide) device allocations of at least this many bytes fail; 0 = off
         devbuf_fail_over() = (size_t)value;
     else if (n == "flat_i8_unit_min")  // threshold sample of the 8-bit pass: one value per sampled unit when the units are many (0 auto, 1 off, 2 on from 2 x rank units: tests)
@@ -1380,6 +1413,12 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.fetch_chunks.load();
     else if (n == "fetch_direct")
         *out = idx->ix.fetch_direct.load();
+    else if (n == "labels_scatter_calls")  // vdb_index_labels_scatter / _device / _set_mask calls that wrote rows | rows they wrote | list entries per launch before the grid-stride loop wraps
+        *out = idx->ix.labels_scatter_calls.load();
+    else if (n == "labels_scatter_rows")
+        *out = idx->ix.labels_scatter_rows.load();
+    else if (n == "labels_scatter_span")
+        *out = labels_scatter_span(idx->ix.num_cu, idx->ix.labels_scatter_max_blocks);
     else if (n == "label_columns")  // allocated label columns (4 B per row each)
         *out = idx->ix.label_columns();
     else if (n == "hbm_bytes_per_row")

@@ -491,6 +491,101 @@ void Index::labels_get(uint32_t column, uint64_t first_row, uint64_t count, uint
     VDB_HIP(hipMemcpy(out, d_labels[column].as<uint32_t>() + first_row, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
 }
 
+// ---- scattered label writes (labels_scatter_plan.hpp, k_labels.hip; docs/DESIGN_flat.md 4.1t) --------------------------------------------
+LabelCols Index::labels_targets(const uint32_t *columns, uint64_t n_cols, hipStream_t s) {
+    LabelCols fresh{};
+    for (uint64_t c = 0; c < n_cols; c++)
+        if (!label_live[columns[c]]) {
+            d_labels[columns[c]].grow(n * sizeof(uint32_t), 0, s);
+            fresh.col[fresh.n++] = d_labels[columns[c]].as<uint32_t>();
+        }
+    launch_label_fill(fresh, 0, n, num_cu, s);  // first write: the columns come to life with every row unlabelled
+    LabelCols target{};
+    for (uint64_t c = 0; c < n_cols; c++) {  // (live only now: an allocation that failed above left no column half made)
+        label_live[columns[c]] = true;
+        target.col[target.n++] = d_labels[columns[c]].as<uint32_t>();
+    }
+    return target;
+}
+
+void Index::labels_scatter(const uint64_t *rows, uint64_t m, const uint32_t *columns, uint64_t n_cols, const uint32_t *codes) {
+    const char *why = labels_scatter_check(n, rows, m, columns, n_cols);
+    VDB_REQUIRE(!why, why);
+    if (m == 0) return;
+    VDB_REQUIRE(codes, "labels_scatter: null codes");
+    VDB_REQUIRE(n <= (1ull << 32), "labels_scatter: a shard holds at most 2^32 rows");
+    use_device();
+    WsLease ws(*this);
+    hipStream_t s = ws->stream;
+    std::vector<uint32_t> h_ids(m);
+    labels_scatter_ids(rows, m, h_ids.data());
+    ws->keys_a.reserve(m * sizeof(uint32_t));
+    ws->misc.reserve(n_cols * m * sizeof(uint32_t));
+    const LabelCols target = labels_targets(columns, n_cols, s);
+    VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_ids.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    VDB_HIP(hipMemcpyAsync(ws->misc.p, codes, n_cols * m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    prof_begin(*ws, "labels_scatter", double(m) * sizeof(uint32_t) * double(1 + 2 * n_cols));
+    launch_labels_scatter(target, ws->keys_a.p, false, 0, ws->misc.as<uint32_t>(), m, num_cu, labels_scatter_max_blocks, s);
+    prof_end(*ws);
+    VDB_SYNC(s);  // (h_ids and the caller's codes may go)
+    prof_collect(*ws);
+    labels_scatter_calls += 1;
+    labels_scatter_rows += m;
+}
+
+void Index::labels_scatter_device(const uint64_t *d_ids, uint64_t m, const uint32_t *columns, uint64_t n_cols, const uint32_t *d_codes) {
+    const char *why = labels_scatter_columns_check(m, columns, n_cols);
+    VDB_REQUIRE(!why, why);
+    if (m == 0) return;
+    VDB_REQUIRE(d_ids && d_codes, "labels_scatter: null argument");
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_ids) % 8 == 0 && reinterpret_cast<uintptr_t>(d_codes) % 4 == 0,
+                "labels_scatter: d_ids must be 8-byte and d_codes 4-byte aligned");
+    use_device();
+    WsLease ws(*this);
+    hipStream_t s = ws->stream;
+    ws->flags.reserve(sizeof(uint32_t));
+    uint32_t *d_flag = ws->flags.as<uint32_t>();
+    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+    launch_fetch_check(d_ids, m, n, id_offset, d_flag, num_cu, s);
+    uint32_t *h_flag = static_cast<uint32_t *>(ws->pinned(sizeof(uint32_t)));
+    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDB_SYNC(s);
+    VDB_REQUIRE(*h_flag == 0, "labels_scatter: the list holds an id that is no row of this index (id - id_offset must be below len)");
+    const LabelCols target = labels_targets(columns, n_cols, s);
+    prof_begin(*ws, "labels_scatter", double(m) * (sizeof(uint64_t) + sizeof(uint32_t) * double(2 * n_cols)));
+    launch_labels_scatter(target, d_ids, true, id_offset, d_codes, m, num_cu, labels_scatter_max_blocks, s);
+    prof_end(*ws);
+    VDB_SYNC(s);
+    prof_collect(*ws);
+    labels_scatter_calls += 1;
+    labels_scatter_rows += m;
+}
+
+void Index::labels_set_mask(const RowMask &mask, const uint32_t *columns, const uint32_t *codes, uint64_t n_cols) {
+    const uint64_t m = mask.m;
+    const char *why = labels_scatter_columns_check(m, columns, n_cols);
+    VDB_REQUIRE(!why, why);
+    if (m == 0) return;
+    VDB_REQUIRE(codes, "labels_set_mask: null codes");
+    use_device();
+    WsLease ws(*this);
+    hipStream_t s = ws->stream;
+    const LabelCols target = labels_targets(columns, n_cols, s);
+    LabelSet set{};
+    for (uint32_t c = 0; c < target.n; c++) {
+        set.col[c] = target.col[c];
+        set.code[c] = codes[c];
+    }
+    set.n = target.n;
+    prof_begin(*ws, "labels_scatter", double(m) * sizeof(uint32_t) * double(1 + n_cols));
+    launch_labels_set_mask(set, mask.d_ids.as<uint32_t>(), m, num_cu, labels_scatter_max_blocks, s);
+    prof_end(*ws);
+    VDB_SYNC(s);
+    prof_collect(*ws);
+    labels_scatter_calls += 1;
+    labels_scatter_rows += m;
+}
+
 // The argument check and the term table; the masks themselves through masks_finish (below).
 void Index::masks_where(const uint64_t *term_lims, const uint32_t *columns, const uint32_t *codes, uint64_t n_masks, RowMask *const *out) {
     VDB_REQUIRE(n_masks == 0 || (term_lims && out), "null argument");

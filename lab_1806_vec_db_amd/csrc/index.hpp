@@ -602,6 +602,24 @@ struct Index {
     uint32_t label_columns() const { return label_cols().n; }
     void labels_set(uint32_t column, uint64_t first_row, const uint32_t *codes, uint64_t count);  // write-side
     void labels_get(uint32_t column, uint64_t first_row, uint64_t count, uint32_t *out) const;
+    // Scattered label writes (labels_scatter_plan.hpp, k_labels_scatter / k_labels_set_mask; docs/DESIGN_flat.md 4.1t), write-side like
+    // labels_set: label[columns[c]][row] for rows that are no contiguous run, n_cols columns in ONE launch, no host copy of a column.
+    // Everything is checked before a column is allocated or written; a target column never written comes to life first, as in
+    // labels_set (allocated for n rows, LABEL_NONE everywhere).  write_gen and rowc_gen stay: a mask is a set of rows.  All return
+    // synchronised.
+    //   labels_scatter: rows = m distinct LOCAL rows on the host, codes [n_cols][m] on the host; ids (as u32) and codes are uploaded once
+    //     each through the workspace (keys_a, misc).
+    //   labels_scatter_device: d_ids = m u64 GLOBAL ids on the device, d_codes u32 [n_cols][m] there; k_fetch_check and one read-back of its
+    //     flag first -- an id that is no row of the index throws with nothing written.  An id named twice gets one of its codes.
+    //   labels_set_mask: codes[c] to column columns[c] of every row the mask allows; the list is the mask's own d_ids, the pairs travel
+    //     by value, nothing is uploaded.  The caller ran check_mask.
+    void labels_scatter(const uint64_t *rows, uint64_t m, const uint32_t *columns, uint64_t n_cols, const uint32_t *codes);
+    void labels_scatter_device(const uint64_t *d_ids, uint64_t m, const uint32_t *columns, uint64_t n_cols, const uint32_t *d_codes);
+    void labels_set_mask(const RowMask &mask, const uint32_t *columns, const uint32_t *codes, uint64_t n_cols);
+    // the target columns in the caller's order, the ones never written brought to life on `s` (allocates: call it after every check)
+    LabelCols labels_targets(const uint32_t *columns, uint64_t n_cols, hipStream_t s);
+    uint32_t labels_scatter_max_blocks = 0;  // "labels_scatter_max_blocks": grid cap of the two kernels, 0 = 8 blocks per CU
+    std::atomic<uint64_t> labels_scatter_calls{0}, labels_scatter_rows{0};  // the three calls that wrote rows (m > 0, not refused) / rows they wrote
     // Row masks from the labels, on the device: mask g = the rows r with label[columns[t]][r] == codes[t] for every t in
     // [term_lims[g], term_lims[g + 1]).  Fills out[g] (fresh RowMask objects of the caller) exactly as vdb_mask_create fills a mask from
     // the equivalent bits; read-side; returns synchronised.  Everything is checked before anything is launched; on a throw the caller

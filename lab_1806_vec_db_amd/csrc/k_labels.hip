@@ -4,7 +4,8 @@
 // same for set / range terms (Index::masks_where_sets, mask_sets.hpp; 4.1m), for an OR of such conjunctions (Index::masks_where_any,
 // mask_any.hpp; 4.1o) and for the AND / OR / NOT of finished masks (Index::mask_combine; 4.1o); and the two kernels that group ONE column
 // by code in a single read of it -- into the masks of many values (Index::masks_partition) or into rows per value (Index::label_counts;
-// mask_partition.hpp; 4.1p).
+// mask_partition.hpp; 4.1p); and the two kernels that write codes to scattered rows of several columns in one launch -- per row of an id
+// list, or one code per column over a mask's rows (Index::labels_scatter, labels_set_mask; labels_scatter_plan.hpp; 4.1t).
 #include <algorithm>
 
 #include "kernels.hpp"
@@ -330,6 +331,53 @@ void launch_label_counts(const uint32_t *col, const uint32_t *table, uint32_t nb
     if (nb == 0 || nblocks == 0) return;
     const unsigned grid = (unsigned)std::min<uint64_t>(nblocks, uint64_t(num_cu) * 8);
     hipLaunchKernelGGL(k_label_counts, dim3(grid), dim3(256), 0, s, col, table, nb, bits, n, nwords, counts);
+}
+
+// ---- scattered writes (Index::labels_scatter*, labels_set_mask; docs/DESIGN_flat.md 4.1t) ---------------------------------------------------
+// col[c][ids[j] - id_offset] = codes[c][j] for every column c of `cols` and every list entry j < m: ONE launch whatever cols.n is.  A
+// lane owns entry j, grid-stride: it loads its id once (coalesced), then per column one coalesced load of its code and one plain
+// scattered 4-byte store.  The column loop is wave-uniform, the column pointers come from the by-value table.  No atomics, no LDS: the ids
+// are distinct (labels_scatter_plan.hpp) or, in the device form, an id named twice gets one of its codes, whole.  Id = u32 local rows
+// (id_offset 0) or u64 global ids; the caller checked them (k_fetch_check for the device form), and a row fits 32 bits since an index
+// has fewer than 2^32 rows.  codes + c * m is formed in 64 bits: n_cols x m may pass 2^32.
+template <class Id>
+__global__ __launch_bounds__(256) void k_labels_scatter(LabelCols cols, const Id *__restrict__ ids, uint64_t id_offset,
+                                                        const uint32_t *__restrict__ codes, uint64_t m) {
+    const uint64_t stride = uint64_t(gridDim.x) * 256;
+    for (uint64_t j = uint64_t(blockIdx.x) * 256 + threadIdx.x; j < m; j += stride) {
+        const uint32_t row = uint32_t(uint64_t(ids[j]) - id_offset);
+        for (uint32_t c = 0; c < cols.n; c++) cols.col[c][row] = codes[uint64_t(c) * m + j];
+    }
+}
+
+// col[c][ids[j]] = set.code[c] for every (column, code) pair of `set` and every j < m: ids = a RowMask's ascending allow-list (u32 local
+// rows).  Pairs and list travel by value / by pointer: nothing is uploaded.
+__global__ __launch_bounds__(256) void k_labels_set_mask(LabelSet set, const uint32_t *__restrict__ ids, uint64_t m) {
+    const uint64_t stride = uint64_t(gridDim.x) * 256;
+    for (uint64_t j = uint64_t(blockIdx.x) * 256 + threadIdx.x; j < m; j += stride) {
+        const uint32_t row = ids[j];
+        for (uint32_t c = 0; c < set.n; c++) set.col[c][row] = set.code[c];
+    }
+}
+
+uint64_t labels_scatter_span(int num_cu, uint32_t max_blocks) {
+    return (max_blocks ? uint64_t(max_blocks) : uint64_t(std::max(num_cu, 1)) * 8) * 256;
+}
+static unsigned labels_scatter_grid(uint64_t m, int num_cu, uint32_t max_blocks) {
+    return (unsigned)std::min<uint64_t>((m + 255) / 256, labels_scatter_span(num_cu, max_blocks) / 256);
+}
+void launch_labels_scatter(const LabelCols &cols, const void *ids, bool ids_u64, uint64_t id_offset, const uint32_t *codes, uint64_t m,
+                           int num_cu, uint32_t max_blocks, hipStream_t s) {
+    if (cols.n == 0 || m == 0) return;
+    const unsigned grid = labels_scatter_grid(m, num_cu, max_blocks);
+    if (ids_u64)
+        hipLaunchKernelGGL(k_labels_scatter<uint64_t>, dim3(grid), dim3(256), 0, s, cols, static_cast<const uint64_t *>(ids), id_offset, codes, m);
+    else
+        hipLaunchKernelGGL(k_labels_scatter<uint32_t>, dim3(grid), dim3(256), 0, s, cols, static_cast<const uint32_t *>(ids), id_offset, codes, m);
+}
+void launch_labels_set_mask(const LabelSet &set, const uint32_t *ids, uint64_t m, int num_cu, uint32_t max_blocks, hipStream_t s) {
+    if (set.n == 0 || m == 0) return;
+    hipLaunchKernelGGL(k_labels_set_mask, dim3(labels_scatter_grid(m, num_cu, max_blocks)), dim3(256), 0, s, set, ids, m);
 }
 
 }  // namespace vdb

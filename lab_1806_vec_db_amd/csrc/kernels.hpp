@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "grouped_plan.hpp"
+#include "labels_scatter_plan.hpp"
 #include "mask_any.hpp"
 #include "mask_partition.hpp"
 #include "mask_sets.hpp"
@@ -372,6 +373,21 @@ void launch_label_fill(const LabelCols &cols, uint64_t r0, uint64_t r1, int num_
 // col[moves[2 j]] = col[moves[2 j + 1]], j < n_moves, in every column of cols (the move list of launch_rows_move) / the one move dst <- src
 void launch_label_move(const LabelCols &cols, const uint32_t *moves, uint64_t n_moves, int num_cu, hipStream_t s);
 void launch_label_move_one(const LabelCols &cols, uint32_t dst, uint32_t src, hipStream_t s);
+// Scattered label writes (labels_scatter_plan.hpp; k_labels_scatter, k_labels_set_mask), ONE launch per call whatever the column count.
+static_assert(SCATTER_LABEL_COLUMNS == LABEL_COLUMNS, "labels_scatter_plan.hpp and kernels.hpp agree");
+struct LabelSet {  // (column, code) pairs of a write by mask (kernel argument, by value)
+    uint32_t *col[LABEL_COLUMNS];
+    uint32_t code[LABEL_COLUMNS];
+    uint32_t n;
+};
+// list entries one launch covers before its grid-stride loop wraps: 256 x (max_blocks, or 8 blocks per CU when max_blocks is 0)
+uint64_t labels_scatter_span(int num_cu, uint32_t max_blocks);
+// cols.col[c][ids[j] - id_offset] = codes[c * m + j], c < cols.n, j < m; ids: u32 local rows (id_offset 0) or, ids_u64, u64 global ids,
+// checked by the caller (labels_scatter_plan.hpp, launch_fetch_check); cols here = the TARGET columns in the caller's order
+void launch_labels_scatter(const LabelCols &cols, const void *ids, bool ids_u64, uint64_t id_offset, const uint32_t *codes, uint64_t m,
+                           int num_cu, uint32_t max_blocks, hipStream_t s);
+// set.col[c][ids[j]] = set.code[c], c < set.n, j < m; ids = a RowMask's d_ids
+void launch_labels_set_mask(const LabelSet &set, const uint32_t *ids, uint64_t m, int num_cu, uint32_t max_blocks, hipStream_t s);
 // workgroups per mask of the mask kernels = entries per mask of blockcnt: four 64-row words each
 inline uint32_t mask_where_blocks(uint64_t n) { return (uint32_t)(((n + 63) / 64 + 3) / 4); }
 // bit words of n_masks masks over rows [0, n) from their terms, then blockcnt [n_masks][mask_where_blocks(n)] = exclusive prefix of the

@@ -432,6 +432,47 @@ class GpuIndex:
         L.check(self._lib.vdb_index_labels_get(self._h, int(column), int(first_row), cnt, _ptr(out, L.u32p)))
         return out
 
+    @staticmethod
+    def _columns_array(columns) -> np.ndarray:
+        c = [int(v) for v in np.asarray(columns).reshape(-1).tolist()]
+        for v in c:
+            if not 0 <= v < 2 ** 32:
+                raise ValueError(f"label column {v}: a column is u32")
+        return np.array(c, dtype=np.uint32)
+
+    def set_labels_rows(self, rows, columns, codes):
+        """Scattered label write (vdb_index_labels_scatter): label column columns[c] of row rows[j] becomes codes[c][j], every column in
+        ONE launch.  `rows`: distinct local row ids in any order (bool / float / negative / duplicate ids raise ValueError, as in
+        update_rows); `columns`: distinct columns; `codes`: shape (len(columns), len(rows)), or 1-D for one column; LABEL_NONE takes a
+        row's value away.  A column never written comes to life first (LABEL_NONE elsewhere).  Masks made before the call stay valid;
+        vectors, mirrors, PQ / HNSW / IVF state are untouched.  A refused call (VdbError) changes nothing."""
+        r = self._update_ids(rows)
+        cols = self._columns_array(columns)
+        c = np.ascontiguousarray(codes, dtype=np.uint32)
+        if c.ndim == 1 and cols.size == 1:
+            c = c.reshape(1, -1)
+        elif c.size == 0 and cols.size == 0:  # (no column: the library refuses it when there are rows)
+            c = np.zeros((0, r.size), dtype=np.uint32)
+        if c.shape != (cols.size, r.size):
+            raise ValueError(f"set_labels_rows: codes must have shape {(cols.size, r.size)}, got {c.shape}")
+        L.check(self._lib.vdb_index_labels_scatter(self._h, _ptr(r, L.u64p), r.size, _ptr(cols, L.u32p), cols.size, _ptr(c, L.u32p)))
+
+    def set_labels_rows_device(self, ids_ptr: int, m: int, columns, codes_ptr: int):
+        """Device form (vdb_index_labels_scatter_device): `ids_ptr` -> m u64 GLOBAL ids on this GPU (row + id_offset, as the *_device
+        searches write them; 8-byte aligned), `codes_ptr` -> u32 [len(columns)][m] there; both complete when the call is made.  An id that
+        is no row of the index raises VdbError and nothing is written; an id named twice gets one of its codes."""
+        cols = self._columns_array(columns)
+        L.check(self._lib.vdb_index_labels_scatter_device(self._h, L.vp(ids_ptr), int(m), _ptr(cols, L.u32p), cols.size, L.vp(codes_ptr)))
+
+    def set_labels_mask(self, mask: RowMask, columns, codes):
+        """codes[c] into label column columns[c] of EVERY row `mask` allows (vdb_index_labels_set_mask): the mask's id list on the device
+        is the write list, nothing is uploaded.  A stale mask or one of another index raises VdbError and nothing changes."""
+        cols = self._columns_array(columns)
+        c = self._codes_array(np.asarray(codes).reshape(-1).tolist())
+        if c.size != cols.size:
+            raise ValueError(f"set_labels_mask: one code per column ({cols.size}), got {c.size}")
+        L.check(self._lib.vdb_index_labels_set_mask(self._h, mask._h, _ptr(cols, L.u32p), _ptr(c, L.u32p), cols.size))
+
     def make_mask_where(self, terms) -> RowMask:
         """the mask of the rows whose label in column c equals code for EVERY (c, code) of `terms`, built on the device
         (vdb_mask_create_where); no terms: every row"""

@@ -351,6 +351,21 @@ def filter_patterns(f) -> list:
     return [p for e in f.exprs for p in filter_patterns(e)]
 
 
+def filter_keys(f) -> frozenset:
+    """the metadata keys a filter names: a pattern's keys, for an expression the union over filter_patterns.  `f` may also be a key of the
+    mask cache (filter_key: frozenset(items) of a pattern, an expression as itself).  A write that changes the values of some keys makes
+    stale exactly the cached masks whose filter_keys intersect them -- the mask of {} names no key and survives every such write."""
+    if isinstance(f, frozenset):
+        return frozenset(k for k, _ in f)
+    return frozenset(k for p in filter_patterns(f) for k in p)
+
+
+def stale_filters(cache, changed_keys) -> list:
+    """the entries of a mask cache (a dict keyed by filter_key) that a write to the metadata keys `changed_keys` makes stale"""
+    changed = frozenset(changed_keys)
+    return [key for key in cache if filter_keys(key) & changed]
+
+
 def matches_filter(expr, metadata_row) -> bool:
     """THE definition of a filter against one metadata dict: a pattern matches when every entry does (`matches` on
     metadata_row.get(key): what the host loop does), AnyOf is any, AllOf is all, Not is not."""
@@ -456,6 +471,20 @@ class LabelCodec:
                 c = table[v] = len(table)
             out[i] = c
         return out
+
+    def encode_value(self, key, v) -> int:
+        """the code of ONE value in the key's column, interning a value not seen before; None is LABEL_NONE.  An unhashable value takes
+        encode_rows' stand-in: encode_value(k, m.get(k)) == encode_rows(k, [m])[0] for every metadata dict m."""
+        if v is None:
+            return LABEL_NONE
+        table = self.codes[self.columns[key]]
+        try:
+            c = table.get(v)
+        except TypeError:
+            v, c = _UNHASHABLE, table.get(_UNHASHABLE)
+        if c is None:
+            c = table[v] = len(table)
+        return c
 
     def value_codes(self, key):
         """(values, codes) of the key's dictionary, entry for entry -- what decodes a count per code (GpuIndex.label_counts) into a count
@@ -600,4 +629,5 @@ class LabelCodec:
 
 __all__ = ["LabelCodec", "LabelTerm", "LABEL_COLUMNS", "LABEL_NONE", "MASK_MAX_TERMS", "MASK_MAX_SET_BITS", "MASK_MAX_CLAUSES", "NOTHING", "TERM_NEGATE",
            "TERM_NONE", "In", "NotIn", "Ne", "Exists", "Lt", "Le", "Gt", "Ge", "Between", "matches", "is_predicate", "has_predicates",
-           "AnyOf", "AllOf", "Not", "matches_filter", "is_expression", "filter_key", "filter_patterns", "cap_groups"]
+           "AnyOf", "AllOf", "Not", "matches_filter", "is_expression", "filter_key", "filter_patterns", "filter_keys", "stale_filters",
+           "cap_groups"]

@@ -33,6 +33,9 @@ search / batch_search take `group_by`, a metadata key, and `group_size`: at most
 without the key always kept -- exact, from the Flat rows, in one library call over the key's label column (GpuIndex.flat_knn_grouped).
 get(key, filter, limit) returns the vectors and metadata of the matching rows, and every search takes `with_vectors`: the hits' vectors
 ride along, all of a call's from one bulk fetch (GpuIndex.get_rows / get_rows_mask); extract_data reads the table with one such call.
+update_metadata(key, pattern, changes) / batch_update_metadata change the METADATA of the matching rows in place: row ids, vectors, the
+HNSW graph and the PQ table stay, the live label columns are written by one scattered write on the device (GpuIndex.set_labels_mask /
+set_labels_rows), and only the cached masks whose filter names a changed key are dropped.
 """
 from __future__ import annotations
 
@@ -44,7 +47,7 @@ import numpy as np
 
 from ._lib import VdbError
 from .index import GpuIndex, RowMask, parse_dist
-from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, filter_patterns, has_predicates, is_expression
+from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, filter_patterns, has_predicates, is_expression, stale_filters
 from .labels import matches as value_matches
 
 _DIST_STR = {0: "l2sqr", 1: "cosine"}
@@ -269,6 +272,41 @@ class _Table:
                 mk.close()
             self.masks.clear()
 
+    def drop_masks_naming(self, changed_keys) -> None:
+        """UNDER THE WRITE LOCK, after a write that changed the VALUES of the metadata keys `changed_keys` and nothing else: closes and
+        drops exactly the cached masks whose filter names one of them (labels.filter_keys); every other mask selects the rows it
+        selected -- the {} mask included -- and stays, host-built ones too."""
+        with self.mask_mu:
+            for key in stale_filters(self.masks, changed_keys):
+                self.masks.pop(key).close()
+
+    def match_rows(self, patterns) -> list:
+        """UNDER THE WRITE LOCK: per pattern the ascending rows it matches, as delete finds them: from a cached or device-built mask
+        when the pattern's keys are label columns already (no key gets a column here), from the host loop otherwise; the plain patterns
+        not cached yet share ONE make_masks_where call."""
+        matches: list = [None] * len(patterns)
+        todo = []
+        with self.mask_mu:
+            for i, p in enumerate(patterns):
+                mk = self.masks.get(frozenset(p.items()))
+                if mk is not None:
+                    matches[i] = mk.rows()[1]
+                    continue
+                terms = self.live_terms(p)
+                if terms is None:
+                    matches[i] = np.flatnonzero(self.host_match(p))
+                elif has_predicates(p):
+                    mk = self.device_mask(p, terms)
+                    matches[i] = mk.rows()[1]
+                    mk.close()
+                else:
+                    todo.append((i, terms))
+        if todo:
+            for (i, _), mk in zip(todo, self.index.make_masks_where([terms for _, terms in todo])):
+                matches[i] = mk.rows()[1]
+                mk.close()
+        return matches
+
     def next_seed(self) -> int:
         self.seed = (self.seed * 6364136223846793005 + 1442695040888963407) & ((1 << 64) - 1)
         return self.seed
@@ -389,8 +427,8 @@ class VecDB:
         keep their ids and their metadata, nothing else moves, and the table's cached filter masks stay valid (a filter is a set of rows,
         and the set did not change).  One library call for the whole batch; like delete it clears the HNSW index and the PQ table first --
         unless nothing matched, then nothing at all is changed.
-        Out of scope: changing the METADATA of existing rows (that needs a scattered write of the label columns).  An upsert is
-        batch_update plus batch_add of what matched nothing."""
+        The METADATA of existing rows is changed by update_metadata / batch_update_metadata.  An upsert is batch_update plus batch_add of
+        what matched nothing."""
         t = self._t(key)
         patterns = list(patterns)
         for p in patterns:
@@ -406,27 +444,7 @@ class VecDB:
         with t.lock.write():
             # the matches as delete finds them: from a cached or device-built mask when the pattern's keys are label columns already (an
             # update gives no key a column), from the host loop otherwise; the plain patterns not cached yet share ONE make_masks_where call
-            matches: list = [None] * len(patterns)
-            todo = []
-            with t.mask_mu:
-                for i, p in enumerate(patterns):
-                    mk = t.masks.get(frozenset(p.items()))
-                    if mk is not None:
-                        matches[i] = mk.rows()[1]
-                        continue
-                    terms = t.live_terms(p)
-                    if terms is None:
-                        matches[i] = np.flatnonzero(t.host_match(p))
-                    elif has_predicates(p):
-                        mk = t.device_mask(p, terms)
-                        matches[i] = mk.rows()[1]
-                        mk.close()
-                    else:
-                        todo.append((i, terms))
-            if todo:
-                for (i, _), mk in zip(todo, t.index.make_masks_where([terms for _, terms in todo])):
-                    matches[i] = mk.rows()[1]
-                    mk.close()
+            matches = t.match_rows(patterns)
             winner: dict[int, int] = {}  # row -> the last pattern that matches it (the library wants distinct ids)
             for i, rows in enumerate(matches):
                 for r in np.asarray(rows).tolist():
@@ -436,6 +454,85 @@ class VecDB:
                 t.index.pq_clear()
                 rows = np.fromiter(winner.keys(), dtype=np.uint64, count=len(winner))
                 t.index.update_rows(rows, vecs[np.fromiter(winner.values(), dtype=np.int64, count=len(winner))])
+            return [int(len(m)) for m in matches]
+
+    @staticmethod
+    def _apply_changes(m: dict, changes: dict) -> None:
+        for k, v in changes.items():
+            if v is None:
+                m.pop(k, None)
+            else:
+                m[k] = v
+
+    def update_metadata(self, key: str, pattern: dict[str, str], changes: dict) -> int:
+        """metadata.update(changes) for every row `pattern` matches -- a metadata pattern exactly as delete takes one; a value None in
+        `changes` REMOVES the key from the row.  Returns the number of rows matched.  The rows keep their ids and vectors, nothing moves,
+        and the HNSW graph and the PQ table stay.  Like delete and update it gives NO key a label column: for the keys of `changes`
+        that have one already the new values are interned and written by ONE GpuIndex.set_labels_mask call over the pattern's mask
+        (cached, built on the device, or from the host loop); the other keys change on the host only -- a column they get later is encoded
+        from the updated metadata.  Order: intern, device write, host dicts, so a failed library call leaves the table as it was.
+        Afterwards exactly the cached filter masks that name a changed key are dropped (labels.filter_keys).  Nothing matched, or empty
+        `changes`: nothing changes at all and no mask is dropped."""
+        if not isinstance(pattern, dict):
+            raise TypeError("update_metadata takes a metadata pattern (a dict), not a filter expression")
+        changes = dict(changes)
+        t = self._t(key)
+        with t.lock.write():
+            with t.mask_mu:
+                mk = t.masks.get(frozenset(pattern.items()))
+            own = mk is None
+            if own:
+                terms = t.live_terms(pattern)
+                mk = t.device_mask(pattern, terms) if terms is not None else t.index.make_mask(t.host_match(pattern))
+            try:
+                rows = mk.rows()[1].tolist()
+                if not rows or not changes:
+                    return len(rows)
+                live = [k for k in changes if t.codec.column_of(k) is not None]
+                if live:
+                    t.index.set_labels_mask(mk, [t.codec.column_of(k) for k in live], [t.codec.encode_value(k, changes[k]) for k in live])
+            finally:
+                if own:
+                    mk.close()
+            for r in rows:
+                self._apply_changes(t.metadata[r], changes)
+            t.drop_masks_naming(changes)
+            return len(rows)
+
+    def batch_update_metadata(self, key: str, patterns, changes_list) -> list[int]:
+        """update_metadata for many (pattern, changes) pairs at once; returns the matches per pattern.  ALL patterns are matched against
+        the table as it stands BEFORE the call (the unbuilt plain ones share one make_masks_where call, as in batch_update); a row several
+        patterns match receives their changes in pattern order, so per key the LAST one wins.  The device write is ONE
+        GpuIndex.set_labels_rows call over the union of the matched rows and every live column some change names: the code of (row,
+        column) is that of the row's FINAL value, so a row a column's changes do not reach is re-written with the value it has."""
+        t = self._t(key)
+        patterns = list(patterns)
+        for p in patterns:
+            if not isinstance(p, dict):
+                raise TypeError("update_metadata takes a metadata pattern (a dict), not a filter expression")
+        changes_list = [dict(c) for c in changes_list]
+        if len(patterns) != len(changes_list):
+            raise RuntimeError("patterns and changes_list differ in length")
+        with t.lock.write():
+            matches = t.match_rows(patterns)
+            merged: dict[int, dict] = {}  # row -> its changes, merged in pattern order
+            changed: dict[str, None] = {}  # the keys some effective change names, in order of first appearance
+            for rows, ch in zip(matches, changes_list):
+                if ch and len(rows):
+                    changed.update(dict.fromkeys(ch))
+                    for r in np.asarray(rows).tolist():
+                        merged.setdefault(int(r), {}).update(ch)
+            if merged:
+                live = [k for k in changed if t.codec.column_of(k) is not None]
+                if live:
+                    codes = np.empty((len(live), len(merged)), dtype=np.uint32)
+                    for c, k in enumerate(live):
+                        codes[c] = [t.codec.encode_value(k, ch[k] if k in ch else t.metadata[r].get(k)) for r, ch in merged.items()]
+                    t.index.set_labels_rows(np.fromiter(merged.keys(), dtype=np.uint64, count=len(merged)),
+                                            [t.codec.column_of(k) for k in live], codes)
+                for r, ch in merged.items():
+                    self._apply_changes(t.metadata[r], ch)
+                t.drop_masks_naming(changed)
             return [int(len(m)) for m in matches]
 
     def build_hnsw_index(self, key: str, ef_construction: int | None = None) -> None:
