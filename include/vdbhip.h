@@ -493,6 +493,52 @@ int vdb_flat_knn_grouped_device(vdb_index *idx, const void *d_queries, uint64_t 
                                 void *d_out_dist, void *d_out_count, void *stream);
 int vdb_group_cap_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
                          uint32_t column, uint64_t group_size, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
+/* ---- diversified Flat k-NN: maximal marginal relevance (MMR) over the fetch_k nearest allowed rows -------------------------------------
+ * "The k results that are close to the query and not near-copies of each other": the max_marginal_relevance_search(query, k, fetch_k,
+ * lambda_mult) of the common retrieval stacks, with the library's bit-exact distances and nothing dragged to the host.  Grouping needs
+ * a label that says which rows are redundant; this call takes redundancy from the vectors themselves.
+ *   All arithmetic is f32, one rounding per operation, no FMA.  For one query let L be its allowed rows in FlatIndex::knn's order --
+ *   ascending by (distance, id), NaN distances last; all rows, or the rows of the query's mask -- m their number, F = min(fetch_k, m),
+ *   C the first F entries of L (positions 0 .. F - 1) and d_p the distance the search reports for position p.  D(p, s) is the distance
+ *   between the ROWS at positions p and s under the index's metric in the reference's arithmetic, DistanceAlgorithm::d(row_p, row_s):
+ *   what vdb_flat_knn reports for row s when row p is the query (Cosine: norms = sqrtf of the cached strict-fold |x|^2, denominator
+ *   max(na * nb, 1e-10)).  D is symmetric bit for bit under both metrics.  mu = 1.0f - lambda, kk = min(k, F).
+ *   Selection: position 0 first.  Every later step gives each unselected p the score (lambda * d_p) - (mu * m_p), m_p = min over the
+ *   selected s of D(p, s) -- m_p starts at +inf and takes D only if D < m_p, so a NaN D is ignored; a NaN score counts as +inf -- and
+ *   selects the smallest score, ties (-0 == +0, +inf == +inf) to the lowest position, until kk are selected.
+ *   Output: the selected rows IN SELECTION ORDER (not sorted by distance): out_idx (id_offset added) / out_dist (d_p) [nq][k],
+ *   out_count[q] = kk, slots past the count zero.  On rows without NaN or inf, lambda = 1 is vdb_flat_knn /
+ *   vdb_flat_knn_filtered_multi at the same k bit for bit; lambda = 0 is farthest-first traversal of C from the nearest row;
+ *   fetch_k == k returns the rows of the plain search in another order.  fetch_k changes the answer: an argument, not a vdb_set_param.
+ *   n_masks == 0: unfiltered, masks / mask_of are not read; otherwise they mean what they mean for vdb_flat_knn_filtered_multi.
+ *   How: ONE round.  The exact sorted list of min(m, fetch_k) rows per query comes from the existing exact search -- the unfiltered
+ *   call exactly as vdb_flat_knn_device runs it, or the filtered call with a mask per query, whose counters advance as if those calls
+ *   had been made -- and k_mmr_select picks from it: one workgroup per query, a lane per candidate, d_p / m_p / selected flags in LDS,
+ *   no F x F matrix: a step folds only D(p, row selected last) into m_p, the selected row staged in LDS (in pieces of 2048 floats when
+ *   longer) while each lane walks its own candidate row with the reference's strict left fold; the argmin is a wave shuffle reduction
+ *   and one LDS exchange.  At most (kk - 1) x F folds per query.  Queries run in sub-chunks whose lists stay under 256 MiB.  A fetch_k
+ *   above 64 leaves the 8-bit first pass of the searches, a step in cost.
+ * vdb_flat_knn_mmr_device: queries and outputs on the index's GPU, at most 32768 queries, returns synchronised.
+ * vdb_mmr_select_device: the selection alone over caller-supplied lists -- d_ids (u64, id_offset included) / d_dists (f32) [nq][ld],
+ * ld <= 4096, k <= ld, in ANY order, walked as given (list position is the tie order; position 0 is selected first), and d_counts [nq]
+ * (u64; entries past min(count, ld) are not read) -- into d_out_idx / d_out_dist [nq][k] and d_out_count [nq]: what a sharded merge
+ * needs behind its top-k merge, and how the tests drive the kernel.  Every counted id is checked on the device first (one flag read
+ * back): an id that, after id_offset is subtracted, is not below len is VDB_ERR_INVALID with the outputs untouched; nothing is
+ * gathered out of bounds.
+ * Refused before anything is computed or written, counters unchanged (VDB_ERR_INVALID): lambda NaN or outside [0, 1], fetch_k < k,
+ * fetch_k > 4096, a VecSet<u8> index, and every mask / mask_of error of vdb_flat_knn_filtered_multi (a stale mask: VDB_ERR_STATE).
+ * nq == 0, k == 0 and m == 0 give empty results.  Read-side and re-entrant.
+ * vdb_get_stat "flat_mmr_calls", "flat_mmr_queries" (the two search forms); vdb_prof_get "mmr_select" times k_mmr_select.
+ * Not covered: sharded and replica contexts, VecSet<u8> indexes, candidates from PQ / HNSW / IVF searches, combination with grouping,
+ * range search. */
+int vdb_flat_knn_mmr(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t fetch_k, float lambda,
+                     const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx, float *out_dist,
+                     uint64_t *out_count);
+int vdb_flat_knn_mmr_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t fetch_k, float lambda,
+                            const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, void *d_out_idx, void *d_out_dist,
+                            void *d_out_count, void *stream);
+int vdb_mmr_select_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                          float lambda, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
 /* ---- bulk row fetch: the vectors of many rows as ONE call (no counterpart in the reference) ----------------------------------------
  * vdb_index_row reads one row with one blocking copy.  These calls return the vectors of a LIST of rows: out[j] = row rows[j].  The
  * list only names what is read, so its order is free and repeats are allowed (m may exceed len); every rows[j] must be below len, and a

@@ -311,6 +311,23 @@ public:
             for (uint64_t j = 0; j < cnt[q]; j++) out[q].push_back({idx[q * k + j], d[q * k + j]});
         return out;
     }
+    // diversified k-NN, maximal marginal relevance (vdb_flat_knn_mmr): per query, from the first min(fetch_k, allowed rows) pairs of
+    // knn_batch, the nearest and then greedily the pair with the smallest lambda * d(query, row) - (1 - lambda) * min over the selected rows
+    // of d(row, selected); the pairs come in SELECTION order.  masks empty: over all rows; otherwise query q under *masks[mask_of[q]]
+    std::vector<std::vector<CandidatePair>> knn_mmr_batch(const float *queries, uint64_t nq, uint64_t k, uint64_t fetch_k, float lambda = 0.5f,
+                                                          const std::vector<const Mask *> &masks = {},
+                                                          const std::vector<uint32_t> &mask_of = {}) const {
+        if (!masks.empty() && mask_of.size() != nq) throw std::runtime_error("mask_of: one entry per query is needed");
+        std::vector<const vdb_mask *> hs;
+        for (const Mask *m : masks) hs.push_back(m->handle());
+        std::vector<uint64_t> idx(nq * (k ? k : 1)), cnt(nq);
+        std::vector<float> d(nq * (k ? k : 1));
+        check(vdb_flat_knn_mmr(h_, queries, nq, dim_, k, fetch_k, lambda, hs.data(), hs.size(), mask_of.data(), idx.data(), d.data(), cnt.data()));
+        std::vector<std::vector<CandidatePair>> out(nq);
+        for (uint64_t q = 0; q < nq; q++)
+            for (uint64_t j = 0; j < cnt[q]; j++) out[q].push_back({idx[q * k + j], d[q * k + j]});
+        return out;
+    }
 
     // MetadataVecTable::build_hnsw_index / clear_hnsw_index, build_pq_table / clear_pq_table
     void build_hnsw(uint64_t M = 16, uint64_t ef_construction = 200, uint64_t seed = 42, uint64_t batch = 64,

@@ -1023,6 +1023,67 @@ int vdb_group_cap_device(vdb_index *idx, const void *d_ids, const void *d_dists,
     VDB_API_END
 }
 
+// ---- diversified k-NN: maximal marginal relevance over the fetch_k nearest allowed rows (Index::flat_knn_mmr_device, k_mmr.hip) ---------
+// everything that can be refused is refused here, before anything is computed or written; -> the masks as RowMask pointers (none: unfiltered)
+static std::vector<const RowMask *> mmr_check(const Index &ix, uint64_t nq, uint64_t k, uint64_t fetch_k, float lambda, const vdb_mask *const *masks,
+                                              uint64_t n_masks, const uint32_t *mask_of) {
+    const char *bad = mmr_check_args(k, fetch_k, lambda);
+    VDB_REQUIRE(bad == nullptr, bad);
+    require_f32_rows(ix);
+    if (n_masks == 0) return {};
+    return filtered_multi_check(ix, nq, masks, n_masks, mask_of);
+}
+
+int vdb_flat_knn_mmr(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t fetch_k, float lambda,
+                     const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx, float *out_dist,
+                     uint64_t *out_count) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_query_args(ix, queries, nq, dim, out_idx, out_dist);
+    const std::vector<const RowMask *> rm = mmr_check(ix, nq, k, fetch_k, lambda, masks, n_masks, mask_of);
+    ix.mmr_calls++;
+    host_search(ix, queries, nq, k, out_idx, out_dist, out_count, [&](Workspace &w, const float *q, uint64_t q0, uint64_t nb, auto... o) {
+        ix.flat_knn_mmr_device(w, q, nb, k, fetch_k, lambda, rm.data(), n_masks, n_masks ? mask_of + q0 : nullptr, o...);
+    });
+    VDB_API_END
+}
+
+int vdb_flat_knn_mmr_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t fetch_k, float lambda,
+                            const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, void *d_out_idx, void *d_out_dist,
+                            void *d_out_count, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_device_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count);
+    const std::vector<const RowMask *> rm = mmr_check(ix, nq, k, fetch_k, lambda, masks, n_masks, mask_of);
+    ix.mmr_calls++;
+    device_search(ix, d_queries, nq, dim, d_out_idx, d_out_dist, d_out_count, stream, [&](Workspace &w, const float *q, uint64_t q0, uint64_t nb, auto... o) {
+        ix.flat_knn_mmr_device(w, q, nb, k, fetch_k, lambda, rm.data(), n_masks, n_masks ? mask_of + q0 : nullptr, o...);
+    });
+    VDB_API_END
+}
+
+int vdb_mmr_select_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k, float lambda,
+                          void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const char *bad = mmr_check_args(k, ld, lambda);
+    VDB_REQUIRE(bad == nullptr, bad);
+    require_f32_rows(ix);
+    VDB_REQUIRE(nq == 0 || (d_counts && d_out_count && (ld == 0 || (d_ids && d_dists)) && (k == 0 || (d_out_idx && d_out_dist))), "null argument");
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the lists on the caller's stream
+    run_synced(ix, *ws, [&] {
+        ix.mmr_select_device(*ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), nq, ld, k,
+                             lambda, static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
+    });
+    VDB_API_END
+}
+
 // ---- bulk row fetch (Index::get_rows*) ----------------------------------------------------------------------------------------------
 int vdb_index_get_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, float *out) {
     VDB_API_BEGIN
@@ -1401,6 +1462,10 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.grouped_rounds.load();
     else if (n == "flat_grouped_exhausted_queries")
         *out = idx->ix.grouped_exhausted.load();
+    else if (n == "flat_mmr_calls")  // diversified k-NN: calls | queries
+        *out = idx->ix.mmr_calls.load();
+    else if (n == "flat_mmr_queries")
+        *out = idx->ix.mmr_queries.load();
     else if (n == "update_calls")  // vdb_index_update_rows* calls that changed rows | rows they rewrote
         *out = idx->ix.update_calls.load();
     else if (n == "update_rows")

@@ -2345,6 +2345,77 @@ void Index::group_cap_device(Workspace &ws, const uint64_t *d_ids, const float *
     prof_collect(ws);
 }
 
+// ---- Flat: diversified k-NN, maximal marginal relevance over the fetch_k nearest allowed rows (k_mmr.hip, mmr_plan.hpp; 4.1u) ------------
+// The candidates of a query are a PREFIX of its order of fixed length, so one round is the whole call: the exact sorted list of
+// kp = min(fetch_k, longest allowed set) rows per query (a query with fewer allowed rows gets a shorter count), then the selection.  The
+// queries are cut into sub-chunks whose lists stay under MMR_LIST_BUDGET; the lists live in the grouped call's buffers.
+void Index::flat_knn_mmr_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t fetch_k, float lambda, const RowMask *const *masks,
+                                uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
+    hipStream_t s = ws.stream;
+    require_f32_rows(*this);
+    VDB_REQUIRE(mmr_check_args(k, fetch_k, lambda) == nullptr, "mmr: bad k, fetch_k or lambda");
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 31), "flat knn: too many queries");
+    mmr_queries += nq;
+    if (k == 0) {
+        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
+        VDB_SYNC(s);
+        return;
+    }
+    uint64_t max_m = n_masks ? 0 : n;
+    for (uint64_t q = 0; n_masks && q < nq; q++) max_m = std::max<uint64_t>(max_m, masks[mask_of[q]]->m);
+    const uint64_t kp = mmr_list_len(fetch_k, max_m);
+    const uint64_t sub = mmr_sub_chunk(nq, kp);
+    // every buffer of the call before its first launch
+    ws.grp_ids.reserve(sub * kp * sizeof(uint64_t));
+    ws.grp_dist.reserve(sub * kp * sizeof(float));
+    ws.grp_cnt.reserve(sub * sizeof(uint64_t));
+    uint64_t *l_ids = ws.grp_ids.as<uint64_t>(), *l_cnt = ws.grp_cnt.as<uint64_t>();
+    float *l_dist = ws.grp_dist.as<float>();
+    if (n_masks) filtered_multi_calls++;
+    for (uint64_t c0 = 0; c0 < nq; c0 += sub) {
+        const uint64_t nb = std::min(sub, nq - c0);
+        if (n_masks)
+            flat_knn_masked_multi_device(ws, d_q + c0 * dim, nb, kp, masks, n_masks, mask_of + c0, l_ids, l_dist, l_cnt);
+        else
+            flat_knn_device(ws, d_q + c0 * dim, nb, kp, l_ids, l_dist, l_cnt);
+        prof_begin(ws, "mmr_select", double(nb) * kp * (MMR_PAIR_BYTES + dim * sizeof(float)));
+        launch_mmr_select(l_ids, l_dist, l_cnt, nb, kp, d_rows.as<float>(), d_sq.as<float>(), n, (uint32_t)dim, dist != 0, id_offset, (uint32_t)k, lambda,
+                          nullptr, d_idx + c0 * k, d_dist + c0 * k, d_cnt + c0, s);
+        prof_end(ws);
+    }
+    VDB_SYNC(s);
+    prof_collect(ws);
+}
+
+void Index::mmr_select_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                              float lambda, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
+    hipStream_t s = ws.stream;
+    require_f32_rows(*this);
+    VDB_REQUIRE(mmr_check_args(k, ld, lambda) == nullptr, "mmr: bad k, ld or lambda");
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 31), "flat knn: too many queries");
+    if (k == 0) {  // (ld == 0 implies it)
+        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
+        VDB_SYNC(s);
+        return;
+    }
+    ws.grp_aux.reserve(sizeof(uint32_t));
+    uint32_t *d_flag = ws.grp_aux.as<uint32_t>();
+    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+    launch_mmr_check(d_ids, d_counts, nq, ld, n, id_offset, d_flag, s);
+    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
+    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDB_SYNC(s);
+    VDB_REQUIRE(*h_flag == 0, "mmr select: a list holds an id that is no row of this index (id - id_offset must be below len)");
+    prof_begin(ws, "mmr_select", double(nq) * ld * (MMR_PAIR_BYTES + dim * sizeof(float)));
+    launch_mmr_select(d_ids, d_dists, d_counts, nq, ld, d_rows.as<float>(), d_sq.as<float>(), n, (uint32_t)dim, dist != 0, id_offset, (uint32_t)k, lambda,
+                      nullptr, d_idx, d_dist, d_cnt, s);
+    prof_end(ws);
+    VDB_SYNC(s);
+    prof_collect(ws);
+}
+
 // ---- Flat: exact filtered range search with one row mask per query (k_filter.hip, multi_plan.hpp) --------------------------------------
 // Query q's slice is what flat_range_device returns for it alone under masks[mask_of[q]].  The queries are bucketed by mask on the host:
 //   per-mask route: a bucket whose mask is longer than flat_filtered_direct_max, and every bucket of a u8 index, is gathered (queries and

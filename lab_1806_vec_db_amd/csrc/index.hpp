@@ -127,7 +127,8 @@ struct Workspace {
     DevBuf pq_img16, pq_aux16;     // 8-bit PQ codes: the sliced 16-bit table images of a round of queries, their minima / offsets / steps (pq.hip)
     DevBuf small_part, small_cnt;  // k_flat_small: per-workgroup key lists, arrival counters (zero between launches)
     // grouped k-NN (Index::flat_knn_grouped_device): the compacted queries of a round, the candidate lists of a sub-chunk (ids, distances,
-    // counts), [slot map | done bytes | flag], the walk's table beyond LDS -- buffers of their own, because the list calls use the others
+    // counts), [slot map | done bytes | flag], the walk's table beyond LDS -- buffers of their own, because the list calls use the others.
+    // The diversified k-NN (Index::flat_knn_mmr_device) keeps its candidate lists and its flag in the same ones.
     DevBuf grp_q, grp_ids, grp_dist, grp_cnt, grp_aux, grp_table;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     struct Pending {
@@ -674,6 +675,19 @@ struct Index {
                           uint32_t column, uint64_t g, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
     uint64_t flat_grouped_oversample = GROUPED_OVERSAMPLE_DEFAULT;  // "flat_grouped_oversample": round 0 fetches min(m, k x this) rows
     std::atomic<uint64_t> grouped_calls{0}, grouped_queries{0}, grouped_rounds{0}, grouped_exhausted{0};
+    // Diversified Flat k-NN (k_mmr.hip, mmr_plan.hpp; docs/DESIGN_flat.md 4.1u): per query the greedy maximal-marginal-relevance selection
+    // of min(k, F) rows from the first F = min(fetch_k, m) rows of FlatIndex::knn's order over the allowed rows, in selection order.  ONE
+    // round: the exact sorted list of F rows per query -- flat_knn_device without masks, flat_knn_masked_multi_device over the call's
+    // masks, whose counters advance as for those calls -- then k_mmr_select, in sub-chunks of queries whose lists stay under
+    // MMR_LIST_BUDGET.  n_masks == 0: unfiltered (masks / mask_of not read).  The caller has checked k, fetch_k, lambda (mmr_check_args),
+    // the masks and mask_of; returns synchronised.
+    void flat_knn_mmr_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t fetch_k, float lambda, const RowMask *const *masks,
+                             uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
+    // k_mmr_select alone over caller-supplied lists [nq][ld] (device), walked as given: every id of the counted ranges is checked on the
+    // device first (one flag read back; a bad one throws before an output is written).  Returns synchronised.
+    void mmr_select_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                           float lambda, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
+    std::atomic<uint64_t> mmr_calls{0}, mmr_queries{0};
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};

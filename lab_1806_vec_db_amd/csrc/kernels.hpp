@@ -9,6 +9,7 @@
 #include "mask_any.hpp"
 #include "mask_partition.hpp"
 #include "mask_sets.hpp"
+#include "mmr_plan.hpp"
 
 namespace vdb {
 
@@ -436,6 +437,18 @@ void launch_group_cap(const uint64_t *ids, const float *dists, const uint64_t *c
 // *flag = 1 when an id of the counted part of a list is no row of the index (id - id_offset not in [0, n)); the caller has zeroed it
 void launch_group_check(const uint64_t *ids, const uint64_t *counts, uint64_t nq, uint64_t ld, uint64_t n, uint64_t id_offset, uint32_t *flag,
                         hipStream_t s);
+// The greedy selection of the diversified k-NN (k_mmr.hip, mmr_plan.hpp): from query b's list ids / dists [b][0 .. F), F = min(counts[b], ld),
+// 1 <= ld <= MMR_MAX_FETCH, position 0 and then min(k, F) - 1 times the unselected position with the smallest
+// (lambda * d_p) - ((1 - lambda) * min over the selected s of D(p, s)), ties to the lowest position; D = the exact distance between the ROWS
+// id - id_offset of X [n][dim] (cosine: 1 - dot / max(|a| |b|, 1e-10) with xsq = the rows' strict-fold |x|^2; otherwise sum (a - b)^2).
+// The selected pairs go in selection order to row slot_q[b] (nullptr: b) of out_idx / out_dist [..][k] with zeros behind them, their
+// number to out_cnt[that row].  An id that is no row of the index is not gathered (its distances read as NaN).
+void launch_mmr_select(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nq, uint64_t ld, const float *X, const float *xsq,
+                       uint64_t n, uint32_t dim, bool cosine, uint64_t id_offset, uint32_t k, float lambda, const uint32_t *slot_q, uint64_t *out_idx,
+                       float *out_dist, uint64_t *out_cnt, hipStream_t s);
+// *flag = 1 when an id of the counted part of a list is no row of the index (id - id_offset not in [0, n)); the caller has zeroed it
+void launch_mmr_check(const uint64_t *ids, const uint64_t *counts, uint64_t nq, uint64_t ld, uint64_t n, uint64_t id_offset, uint32_t *flag,
+                      hipStream_t s);
 void mfma_set_sample_thin(int v);
 void mfma_sample_plan(uint64_t n, uint32_t kprime, uint32_t *step, uint32_t *rank, uint32_t target_floor = 1024);  // target_floor: expected hits per query
 uint64_t mfma_sample_rows(uint64_t n, uint32_t step);

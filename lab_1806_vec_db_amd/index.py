@@ -81,6 +81,7 @@ LABEL_COLUMNS = 16         # VDB_LABEL_COLUMNS
 LABEL_NONE = 0xFFFFFFFF    # VDB_LABEL_NONE
 MASK_MAX_TERMS = 8         # VDB_MASK_MAX_TERMS
 MASK_OP_AND, MASK_OP_OR = 0, 1  # VDB_MASK_OP_AND / VDB_MASK_OP_OR
+MMR_MAX_FETCH = 4096       # longest candidate list of flat_knn_mmr / mmr_select_device (MMR_MAX_FETCH of csrc/mmr_plan.hpp)
 FETCH_CHUNK_BYTES_DEFAULT = 128 << 20  # what "fetch_chunk_bytes" is until set_param changes it (Index::FETCH_CHUNK_BYTES_DEFAULT)
 
 
@@ -654,6 +655,29 @@ class GpuIndex:
         given (vdb_group_cap_device); an id that is no row of this index raises and leaves the outputs untouched"""
         L.check(self._lib.vdb_group_cap_device(self._h, L.vp(ids_ptr), L.vp(dists_ptr), L.vp(counts_ptr), int(nq), int(ld), int(k), int(column),
                                                int(group_size), L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
+
+    def flat_knn_mmr(self, queries, k: int, fetch_k: int, lambda_mult: float = 0.5, masks=None, mask_of=None):
+        """Diversified exact k-NN, maximal marginal relevance (vdb_flat_knn_mmr): per query, from the first min(fetch_k, allowed rows)
+        rows of flat_knn's order, the nearest row and then greedily the row with the smallest
+        lambda_mult * d(query, row) - (1 - lambda_mult) * min over the selected rows of d(row, selected), ties to the earlier row; the hits
+        come IN SELECTION ORDER with the distances of flat_knn.  k <= fetch_k <= 4096, 0 <= lambda_mult <= 1 (1: flat_knn itself, 0:
+        farthest-first among the candidates).  masks / mask_of as in flat_knn_grouped.  Same return shapes as flat_knn_filtered."""
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, _nq(queries))
+        return self._knn_call(self._lib.vdb_flat_knn_mmr, queries, k, int(fetch_k), float(lambda_mult), arr, n_masks, mo_p)
+
+    def flat_knn_mmr_device(self, q_ptr: int, nq: int, k: int, fetch_k: int, lambda_mult: float, out_idx_ptr: int, out_dist_ptr: int,
+                            out_cnt_ptr: int, masks=None, mask_of=None, stream: int = 0):
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, int(nq))
+        L.check(self._lib.vdb_flat_knn_mmr_device(self._h, L.vp(q_ptr), int(nq), self.dim, int(k), int(fetch_k), float(lambda_mult), arr, n_masks,
+                                                  mo_p, L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
+
+    def mmr_select_device(self, ids_ptr: int, dists_ptr: int, counts_ptr: int, nq: int, ld: int, k: int, lambda_mult: float,
+                          out_idx_ptr: int, out_dist_ptr: int, out_cnt_ptr: int, stream: int = 0):
+        """the greedy selection alone over caller-supplied device lists [nq][ld] (u64 ids, f32 distances; ld <= 4096, k <= ld) and u64
+        counts, walked in the order given: position 0 is selected first and position is the tie order (vdb_mmr_select_device); an id that
+        is no row of this index raises and leaves the outputs untouched"""
+        L.check(self._lib.vdb_mmr_select_device(self._h, L.vp(ids_ptr), L.vp(dists_ptr), L.vp(counts_ptr), int(nq), int(ld), int(k),
+                                                float(lambda_mult), L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
 
     def _range_out(self, h, nq: int):
         return read_range(self._lib, h, nq)

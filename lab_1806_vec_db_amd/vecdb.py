@@ -31,6 +31,8 @@ count(key, filter) is the number of matching rows (the mask's count); count_by(k
 metadata key, from one pass over the key's label column on the device (GpuIndex.label_counts).
 search / batch_search take `group_by`, a metadata key, and `group_size`: at most that many hits per value of the key, nearest first, rows
 without the key always kept -- exact, from the Flat rows, in one library call over the key's label column (GpuIndex.flat_knn_grouped).
+search / batch_search take `mmr_lambda` and `fetch_k`: maximal marginal relevance, the k hits close to the query and not near-copies of
+each other, chosen greedily among the fetch_k nearest -- exact, from the Flat rows, in one library call (GpuIndex.flat_knn_mmr).
 get(key, filter, limit) returns the vectors and metadata of the matching rows, and every search takes `with_vectors`: the hits' vectors
 ride along, all of a call's from one bulk fetch (GpuIndex.get_rows / get_rows_mask); extract_data reads the table with one such call.
 update_metadata(key, pattern, changes) / batch_update_metadata change the METADATA of the matching rows in place: row ids, vectors, the
@@ -46,7 +48,7 @@ from contextlib import contextmanager
 import numpy as np
 
 from ._lib import VdbError
-from .index import GpuIndex, RowMask, parse_dist
+from .index import MMR_MAX_FETCH, GpuIndex, RowMask, parse_dist
 from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, filter_patterns, has_predicates, is_expression, stale_filters
 from .labels import matches as value_matches
 
@@ -588,17 +590,19 @@ class VecDB:
 
     # ---- reads ------------------------------------------------------------------------------------------------
     def search(self, key: str, query, k: int, ef: int | None = None, upper_bound: float | None = None,
-               filter: dict[str, str] | None = None, group_by: str | None = None, group_size: int = 1, with_vectors: bool = False):
+               filter: dict[str, str] | None = None, group_by: str | None = None, group_size: int = 1, with_vectors: bool = False,
+               mmr_lambda: float | None = None, fetch_k: int | None = None):
         """MetadataVecTable::search.  `filter`: a metadata pattern matched exactly as delete matches (every key present with an equal
         value; an empty pattern matches every row) -- only matching rows are searched.  With a filter the answer is always EXACT, from
         the table's Flat rows, whatever indexes the table has, and `ef` is ignored.  `group_by`: a metadata key -- at most `group_size`
         hits per value of it (batch_search states the rule); exact as with a filter, same return shape.  `with_vectors`: entries become
-        (metadata, distance, vector) -- the hits' vectors (float32 arrays) from ONE get_rows call over the hit ids."""
+        (metadata, distance, vector) -- the hits' vectors (float32 arrays) from ONE get_rows call over the hit ids.  `mmr_lambda` /
+        `fetch_k`: diversified hits in selection order (batch_search states the rule); exact as with a filter."""
         t = self._t(key)
         ix = t.index
         q = np.asarray(query, dtype=np.float32).ravel()
-        if group_by is not None:
-            return self.batch_search(key, q.reshape(1, -1), k, ef, upper_bound, filter, group_by, group_size, with_vectors)[0]
+        if group_by is not None or mmr_lambda is not None or fetch_k is not None:
+            return self.batch_search(key, q.reshape(1, -1), k, ef, upper_bound, filter, group_by, group_size, with_vectors, mmr_lambda, fetch_k)[0]
         if filter is not None:
             t.prepare([filter])
         with t.lock.read():  # database/mod.rs:255: read guard for the whole search, metadata lookup included
@@ -620,7 +624,8 @@ class VecDB:
             return [(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx, dist) if d <= ub]
 
     def batch_search(self, key: str, queries, k: int, ef: int | None = None, upper_bound: float | None = None, filters=None,
-                     group_by: str | None = None, group_size: int = 1, with_vectors: bool = False):
+                     group_by: str | None = None, group_size: int = 1, with_vectors: bool = False, mmr_lambda: float | None = None,
+                     fetch_k: int | None = None):
         """search for a batch of queries in ONE library call: entry q of the returned list is what search(key, queries[q], k, ef,
         upper_bound, filter) returns.  `filters`: None, ONE metadata pattern for every query, or a list of len(queries) patterns (the
         multi-tenant batch: every query restricted to its own rows; {} matches every row).  With filters the answers are exact, from
@@ -633,9 +638,19 @@ class VecDB:
         are filters).  A key that cannot have a column (a 17th key) or whose values a dictionary cannot keep apart takes the host
         fallback: the ungrouped search at a growing k, walked by labels.cap_groups over the metadata values.
         `with_vectors`: entries become (metadata, distance, vector); the vectors of all hits of the batch come from ONE get_rows call
-        over the hit ids (no call when the batch has no hit)."""
+        over the hit ids (no call when the batch has no hit).
+        `mmr_lambda`: a number in [0, 1] -- maximal marginal relevance.  From a query's `fetch_k` nearest matching rows (default 4 k,
+        raised to k, clamped to 4096) the nearest is taken first and then, greedily, the row with the smallest
+        mmr_lambda * d(query, row) - (1 - mmr_lambda) * min over the rows taken of d(row, taken), ties to the nearer row, until k are taken:
+        1 is the plain search, 0 the farthest-first walk of the candidates.  Always exact, from the Flat rows (`ef` is ignored); the batch
+        is ONE flat_knn_mmr call (under the filters' masks when there are filters); entries come IN SELECTION ORDER, not by distance;
+        `upper_bound` is applied afterwards.  Not together with `group_by`; `fetch_k` without `mmr_lambda` is an error."""
         if group_by is not None and int(group_size) < 1:
             raise ValueError("group_size must be at least 1")
+        if mmr_lambda is not None and group_by is not None:
+            raise ValueError("mmr_lambda and group_by cannot be combined")
+        if fetch_k is not None and mmr_lambda is None:
+            raise ValueError("fetch_k needs mmr_lambda")
         t = self._t(key)
         ix = t.index
         q = np.asarray(queries, dtype=np.float32)
@@ -671,6 +686,9 @@ class VecDB:
                     idx, dist, cnt = ix.flat_knn_grouped(q, k, t.codec.column_of(group_by), group_size, masks, mask_of)
                 else:
                     idx, dist, cnt = self._grouped_on_host(t, q, k, group_by, group_size, masks, mask_of)
+            elif mmr_lambda is not None:
+                fk = min(max(4 * int(k) if fetch_k is None else int(fetch_k), int(k)), MMR_MAX_FETCH)
+                idx, dist, cnt = ix.flat_knn_mmr(q, k, fk, mmr_lambda, masks, mask_of)
             elif pats is not None:
                 idx, dist, cnt = ix.flat_knn_filtered_multi(q, k, masks, mask_of)
             elif ef is not None and ix.has_pq():
