@@ -539,6 +539,66 @@ int vdb_flat_knn_mmr_device(vdb_index *idx, const void *d_queries, uint64_t nq, 
                             void *d_out_count, void *stream);
 int vdb_mmr_select_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
                           float lambda, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
+/* ---- search by example rows ("recommend", "more like this"): positives, negatives, the examples left out ------------------------------
+ * "More like these rows, and not like those": the query vector is made on the device from rows the index already holds, searched
+ * exactly, and the examples are taken out of the answer -- no vector is dragged to the host and no k is guessed.
+ *   All arithmetic is f32, one rounding per operation, no FMA.  For query q the caller gives two lists of rows, positives P_q with
+ *   |P_q| >= 1 and negatives N_q, which may be empty; each is read in list order and a repeat counts as often as it appears.
+ *   Query vector, per element j: sp = +0.0f, then sp = sp + row[j] for each positive in list order (a strict left fold);
+ *   ap = sp / (float)|P_q|.  With negatives an is the same fold and divide over N_q and query[j] = (ap + ap) - an; without,
+ *   query[j] = ap (so one positive gives the row itself, with -0.0 turned into +0.0).  This is the usual "average vector" rule
+ *   avg_pos + (avg_pos - avg_neg).  It holds for both metrics: Cosine needs no extra normalisation, the search treats this query as it
+ *   treats any other.  A NaN element keeps no particular sign or payload.
+ *   Search: let L be the query's allowed rows in FlatIndex::knn's order -- ascending by (distance, id), NaN distances last; all rows,
+ *   or the rows of the query's mask (masks / mask_of mean what they mean for vdb_flat_knn_filtered_multi; n_masks == 0: unfiltered,
+ *   they are not read).  exclude != 0: the answer is the first k entries of L whose row is in neither P_q nor N_q; exclude == 0: the
+ *   first k entries of L.  out_idx (id_offset added) / out_dist [nq][k]; the distances are bit for bit those of the plain search for
+ *   that query vector; out_count[q] is the number written, slots past the count are zero.
+ *   How: ONE round.  e_max = max over q of (|P_q| + |N_q|) -- the lists as given, not distinct rows: an upper bound that needs no
+ *   read-back -- and K' = min(max_m, k + e_max) when excluding, else min(max_m, k), max_m the longest allowed set.  A list of K' rows
+ *   always holds k rows that are no examples whenever that many exist.  k_like_build writes the query vectors (a thread per element,
+ *   wave-uniform row ids, 64-bit row offsets); the exact sorted list of K' rows per query comes from the existing search, unchanged --
+ *   the unfiltered call exactly as vdb_flat_knn_device runs it, or the filtered call with a mask per query, whose counters advance as
+ *   if those calls had been made -- and k_like_drop compacts it: one wave per query, tiles of 64, a lane tests its id against the
+ *   query's example ids staged in LDS, a ballot and a prefix popcount give the output slot, it stops at k.  Queries run in sub-chunks
+ *   whose lists stay under 256 MiB.  K' never changes an answer, only the cost: past 64 it leaves the 8-bit first pass of the
+ *   searches, the step in cost DESIGN 4.1q and 4.1u measured.
+ * The lims arrays are HOST pointers in every form (as mask_of is): pos_lims [nq + 1] with pos_lims[0] == 0, query q's positives are
+ * entries pos_lims[q] .. pos_lims[q + 1] of the list; neg_lims likewise, or NULL when no query has negatives.  At most 1024 examples
+ * per query, positives plus negatives.  Host forms take LOCAL row ids (u64, below len); device forms take u64 GLOBAL ids (row +
+ * id_offset) on the index's GPU, 8-byte aligned, as vdb_index_get_rows_device does, and check them on the device with one flag
+ * read-back: nothing is gathered out of bounds.
+ * vdb_like_queries: the builder alone, into nq x dim f32 on the host.  vdb_like_queries_device: into device memory (4-byte aligned),
+ * returns synchronised; its output is a valid d_queries for every *_device search -- range, grouped, MMR, HNSW, IVF: that is how those
+ * combine with examples, no further variants exist.
+ * vdb_flat_knn_like_device: outputs on the index's GPU, at most 32768 queries, returns synchronised.
+ * vdb_drop_listed_device: the compaction alone over caller-supplied lists -- d_ids (u64, id_offset included) / d_dists (f32) [nq][ld]
+ * in ANY order, walked as given, and d_counts [nq] (u64; entries past min(count, ld) are not read) -- against the global ids
+ * d_drop_ids under the HOST limits drop_lims [nq + 1] (a query's list may be empty, at most 1024 ids), into d_out_idx / d_out_dist
+ * [nq][k] and d_out_count [nq]: the first k entries whose id is not listed, in list order; the same id twice in a list is dropped
+ * twice.  What a sharded merge needs behind its top-k merge, and how the tests drive the kernel.  Every counted id and every listed
+ * id is checked on the device first: one that is no row of the index is VDB_ERR_INVALID with the outputs untouched.
+ * Refused before anything is computed or written, counters unchanged (VDB_ERR_INVALID): limits that do not start at 0 or descend, a
+ * query without a positive or with more than 1024 examples, a NULL list with entries, a row or id that is no row of the index, a
+ * VecSet<u8> index, and every mask / mask_of error of vdb_flat_knn_filtered_multi (a stale mask: VDB_ERR_STATE).  nq == 0, k == 0
+ * and m == 0 give empty results.  Read-side and re-entrant.
+ * vdb_get_stat "flat_like_calls", "flat_like_queries" (the two search forms), "like_example_rows" (list entries the builder walked,
+ * all four forms); vdb_prof_get "like_build", "like_drop" time the two kernels.
+ * Not covered: the "best score" strategy (every candidate scored against every example), per-example weights, VecSet<u8> indexes,
+ * sharded and replica contexts, PQ / HNSW / IVF candidate lists (beyond feeding them the built queries through
+ * vdb_like_queries_device), combination with group_by / mmr_lambda at the VecDB level. */
+int vdb_like_queries(vdb_index *idx, const uint64_t *pos_lims, const uint64_t *pos_rows, const uint64_t *neg_lims, const uint64_t *neg_rows,
+                     uint64_t nq, float *out_queries);
+int vdb_like_queries_device(vdb_index *idx, const uint64_t *pos_lims, const void *d_pos_ids, const uint64_t *neg_lims, const void *d_neg_ids,
+                            uint64_t nq, void *d_out_queries, void *stream);
+int vdb_flat_knn_like(vdb_index *idx, const uint64_t *pos_lims, const uint64_t *pos_rows, const uint64_t *neg_lims, const uint64_t *neg_rows,
+                      uint64_t nq, uint64_t k, int exclude, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of,
+                      uint64_t *out_idx, float *out_dist, uint64_t *out_count);
+int vdb_flat_knn_like_device(vdb_index *idx, const uint64_t *pos_lims, const void *d_pos_ids, const uint64_t *neg_lims, const void *d_neg_ids,
+                             uint64_t nq, uint64_t k, int exclude, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of,
+                             void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
+int vdb_drop_listed_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                           const uint64_t *drop_lims, const void *d_drop_ids, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
 /* ---- bulk row fetch: the vectors of many rows as ONE call (no counterpart in the reference) ----------------------------------------
  * vdb_index_row reads one row with one blocking copy.  These calls return the vectors of a LIST of rows: out[j] = row rows[j].  The
  * list only names what is read, so its order is free and repeats are allowed (m may exceed len); every rows[j] must be below len, and a

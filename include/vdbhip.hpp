@@ -329,6 +329,36 @@ public:
         return out;
     }
 
+    // search by example rows (vdb_like_queries / vdb_flat_knn_like): positives[q] / negatives[q] are the LOCAL rows of query q's examples
+    // (negatives empty: none; otherwise one list per query).  The query vector is the strict-fold f32 average of the positives, plus its
+    // difference from the average of the negatives; like_batch returns per query the first k pairs of knn_batch for it whose row is no
+    // example (exclude = false: the first k pairs).  masks empty: over all rows; otherwise query q under *masks[mask_of[q]]
+    std::vector<float> like_queries(const std::vector<std::vector<uint64_t>> &positives,
+                                    const std::vector<std::vector<uint64_t>> &negatives = {}) const {
+        const LikeArgs a(positives, negatives);
+        std::vector<float> out(positives.size() * dim_);
+        check(vdb_like_queries(h_, a.pl.data(), a.pr.data(), a.nl_ptr(), a.nr.data(), positives.size(), out.data()));
+        return out;
+    }
+    std::vector<std::vector<CandidatePair>> like_batch(const std::vector<std::vector<uint64_t>> &positives, uint64_t k,
+                                                       const std::vector<std::vector<uint64_t>> &negatives = {}, bool exclude = true,
+                                                       const std::vector<const Mask *> &masks = {},
+                                                       const std::vector<uint32_t> &mask_of = {}) const {
+        const uint64_t nq = positives.size();
+        if (!masks.empty() && mask_of.size() != nq) throw std::runtime_error("mask_of: one entry per query is needed");
+        const LikeArgs a(positives, negatives);
+        std::vector<const vdb_mask *> hs;
+        for (const Mask *m : masks) hs.push_back(m->handle());
+        std::vector<uint64_t> idx(nq * (k ? k : 1)), cnt(nq);
+        std::vector<float> d(nq * (k ? k : 1));
+        check(vdb_flat_knn_like(h_, a.pl.data(), a.pr.data(), a.nl_ptr(), a.nr.data(), nq, k, exclude ? 1 : 0, hs.data(), hs.size(), mask_of.data(),
+                                idx.data(), d.data(), cnt.data()));
+        std::vector<std::vector<CandidatePair>> out(nq);
+        for (uint64_t q = 0; q < nq; q++)
+            for (uint64_t j = 0; j < cnt[q]; j++) out[q].push_back({idx[q * k + j], d[q * k + j]});
+        return out;
+    }
+
     // MetadataVecTable::build_hnsw_index / clear_hnsw_index, build_pq_table / clear_pq_table
     void build_hnsw(uint64_t M = 16, uint64_t ef_construction = 200, uint64_t seed = 42, uint64_t batch = 64,
                     int nthreads = 16) {
@@ -378,6 +408,25 @@ private:
         check(fn(h_, query.data(), 1, query.size(), k, ef, idx.data(), d.data(), &cnt));
         return collect(idx, d, cnt);
     }
+    // the example lists of like_queries / like_batch as the C ABI takes them: limits of nq + 1 entries and the rows behind each other
+    struct LikeArgs {
+        std::vector<uint64_t> pl, pr, nl, nr;
+        LikeArgs(const std::vector<std::vector<uint64_t>> &positives, const std::vector<std::vector<uint64_t>> &negatives) {
+            if (!negatives.empty() && negatives.size() != positives.size()) throw std::runtime_error("negatives: one list per query is needed");
+            pl.push_back(0);
+            for (const auto &p : positives) {
+                pr.insert(pr.end(), p.begin(), p.end());
+                pl.push_back(pr.size());
+            }
+            if (negatives.empty()) return;
+            nl.push_back(0);
+            for (const auto &g : negatives) {
+                nr.insert(nr.end(), g.begin(), g.end());
+                nl.push_back(nr.size());
+            }
+        }
+        const uint64_t *nl_ptr() const { return nl.empty() ? nullptr : nl.data(); }
+    };
     vdb_index *h_ = nullptr;
     uint64_t dim_;
     DistanceAlgorithm dist_;

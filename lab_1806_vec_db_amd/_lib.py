@@ -82,6 +82,11 @@ SIGNATURES = {
     "vdb_flat_knn_mmr": [vp, f32p, u64, u64, u64, u64, C.c_float, C.POINTER(vp), u64, u32p, u64p, f32p, u64p],
     "vdb_flat_knn_mmr_device": [vp, vp, u64, u64, u64, u64, C.c_float, C.POINTER(vp), u64, u32p, vp, vp, vp, vp],
     "vdb_mmr_select_device": [vp, vp, vp, vp, u64, u64, u64, C.c_float, vp, vp, vp, vp],
+    "vdb_like_queries": [vp, u64p, u64p, u64p, u64p, u64, f32p],
+    "vdb_like_queries_device": [vp, u64p, vp, u64p, vp, u64, vp, vp],
+    "vdb_flat_knn_like": [vp, u64p, u64p, u64p, u64p, u64, u64, C.c_int, C.POINTER(vp), u64, u32p, u64p, f32p, u64p],
+    "vdb_flat_knn_like_device": [vp, u64p, vp, u64p, vp, u64, u64, C.c_int, C.POINTER(vp), u64, u32p, vp, vp, vp, vp],
+    "vdb_drop_listed_device": [vp, vp, vp, vp, u64, u64, u64, u64p, vp, vp, vp, vp, vp],
     "vdb_fetch_plan": [u64, u64p, u64, u64, u64, intp, u64p, u64p],
     "vdb_index_get_rows": [vp, u64p, u64, f32p],
     "vdb_index_get_rows_u8": [vp, u64p, u64, u8p],

@@ -1084,6 +1084,225 @@ int vdb_mmr_select_device(vdb_index *idx, const void *d_ids, const void *d_dists
     VDB_API_END
 }
 
+// ---- search by example rows (Index::flat_knn_like_device / like_queries_device / drop_listed_device, k_like.hip, like_plan.hpp) ----------
+// what every form refuses before anything is uploaded: a u8 index, limits the plan refuses, a NULL list with entries
+static void like_check_lists(const Index &ix, const uint64_t *pos_lims, const void *pos, const uint64_t *neg_lims, const void *neg, uint64_t nq) {
+    require_f32_rows(ix);
+    const char *bad = like_check_lims(pos_lims, neg_lims, nq);
+    VDB_REQUIRE(bad == nullptr, bad);
+    VDB_REQUIRE(pos_lims[nq] == 0 || pos, "like: null positives");
+    VDB_REQUIRE(!neg_lims || neg_lims[nq] == 0 || neg, "like: null negatives");
+}
+
+// the host forms: every row below len, then [pos_lims | neg_lims | positives u32 | negatives u32] into ws.grp_table with one copy out of
+// `blob`, which the caller keeps until the stream has been waited for
+static Index::LikeLists like_upload_rows(const Index &ix, Workspace &ws, std::vector<char> &blob, const uint64_t *pos_lims, const uint64_t *pos_rows,
+                                         const uint64_t *neg_lims, const uint64_t *neg_rows, uint64_t nq) {
+    const uint64_t np = pos_lims[nq], nn = neg_lims ? neg_lims[nq] : 0;
+    const size_t lb = (nq + 1) * sizeof(uint64_t), off_nl = lb, off_p = neg_lims ? 2 * lb : lb, off_n = off_p + np * sizeof(uint32_t);
+    blob.resize(off_n + nn * sizeof(uint32_t));
+    std::memcpy(blob.data(), pos_lims, lb);
+    if (neg_lims) std::memcpy(blob.data() + off_nl, neg_lims, lb);
+    uint32_t *hp = reinterpret_cast<uint32_t *>(blob.data() + off_p), *hn = reinterpret_cast<uint32_t *>(blob.data() + off_n);
+    for (uint64_t j = 0; j < np; j++) hp[j] = (uint32_t)pos_rows[j];
+    for (uint64_t j = 0; j < nn; j++) hn[j] = (uint32_t)neg_rows[j];
+    ws.grp_table.reserve(blob.size());
+    VDB_HIP(hipMemcpyAsync(ws.grp_table.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ws.stream));
+    char *d = ws.grp_table.as<char>();
+    Index::LikeLists ll;
+    ll.pos_lims = reinterpret_cast<const uint64_t *>(d);
+    ll.neg_lims = neg_lims ? reinterpret_cast<const uint64_t *>(d + off_nl) : nullptr;
+    ll.pos_ids = d + off_p;
+    ll.neg_ids = d + off_n;
+    ll.global_ids = false;
+    ll.e_max = like_e_max(pos_lims, neg_lims, nq);
+    ll.n_examples = np + nn;
+    return ll;
+}
+static void like_check_rows(const Index &ix, const uint64_t *lims, const uint64_t *rows, uint64_t nq) {
+    for (uint64_t j = 0; lims && j < lims[nq]; j++)
+        VDB_REQUIRE(rows[j] < ix.n, "like: row " + std::to_string(rows[j]) + " is no row of this index (len " + std::to_string(ix.n) + ")");
+}
+
+// the device forms: [pos_lims | neg_lims] into ws.grp_table, the ids where the caller has them; every id checked with one flag read-back
+// (which waits for the stream: the caller's arrays are free again)
+static Index::LikeLists like_upload_lims(Index &ix, Workspace &ws, const uint64_t *pos_lims, const void *d_pos_ids, const uint64_t *neg_lims,
+                                         const void *d_neg_ids, uint64_t nq) {
+    const size_t lb = (nq + 1) * sizeof(uint64_t);
+    ws.grp_table.reserve(2 * lb);
+    char *d = ws.grp_table.as<char>();
+    VDB_HIP(hipMemcpyAsync(d, pos_lims, lb, hipMemcpyHostToDevice, ws.stream));
+    if (neg_lims) VDB_HIP(hipMemcpyAsync(d + lb, neg_lims, lb, hipMemcpyHostToDevice, ws.stream));
+    Index::LikeLists ll;
+    ll.pos_lims = reinterpret_cast<const uint64_t *>(d);
+    ll.neg_lims = neg_lims ? reinterpret_cast<const uint64_t *>(d + lb) : nullptr;
+    ll.pos_ids = d_pos_ids;
+    ll.neg_ids = d_neg_ids;
+    ll.global_ids = true;
+    ll.e_max = like_e_max(pos_lims, neg_lims, nq);
+    ll.n_examples = pos_lims[nq] + (neg_lims ? neg_lims[nq] : 0);
+    ix.like_check_ids_device(ws, static_cast<const uint64_t *>(d_pos_ids), pos_lims[nq], static_cast<const uint64_t *>(d_neg_ids),
+                             neg_lims ? neg_lims[nq] : 0);
+    VDB_SYNC(ws.stream);  // (a call whose lists are all empty has not waited yet)
+    return ll;
+}
+static void like_check_device_ids(const void *d_pos_ids, const void *d_neg_ids) {
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_pos_ids) % 8 == 0 && reinterpret_cast<uintptr_t>(d_neg_ids) % 8 == 0, "like: id lists must be 8-byte aligned");
+}
+
+int vdb_like_queries(vdb_index *idx, const uint64_t *pos_lims, const uint64_t *pos_rows, const uint64_t *neg_lims, const uint64_t *neg_rows, uint64_t nq,
+                     float *out_queries) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    like_check_lists(ix, pos_lims, pos_rows, neg_lims, neg_rows, nq);
+    like_check_rows(ix, pos_lims, pos_rows, nq);
+    like_check_rows(ix, neg_lims, neg_rows, nq);
+    if (nq == 0) return VDB_OK;
+    VDB_REQUIRE(out_queries, "null argument");
+    ix.use_device();
+    WsLease ws(ix);
+    hipStream_t s = ws->stream;
+    std::vector<char> blob;
+    constexpr uint64_t CHUNK = 16384;
+    run_synced(ix, *ws, [&] {
+        const Index::LikeLists ll = like_upload_rows(ix, *ws, blob, pos_lims, pos_rows, neg_lims, neg_rows, nq);
+        ws->q.reserve(std::min(nq, CHUNK) * ix.dim * sizeof(float));
+        for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
+            const uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
+            ix.like_queries_device(*ws, ll, q0, nb, ws->q.as<float>());
+            VDB_HIP(hipMemcpyAsync(out_queries + q0 * ix.dim, ws->q.p, nb * ix.dim * sizeof(float), hipMemcpyDeviceToHost, s));
+            VDB_SYNC(s);
+        }
+        ix.like_example_rows += ll.n_examples;
+    });
+    VDB_API_END
+}
+
+int vdb_like_queries_device(vdb_index *idx, const uint64_t *pos_lims, const void *d_pos_ids, const uint64_t *neg_lims, const void *d_neg_ids, uint64_t nq,
+                            void *d_out_queries, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    like_check_lists(ix, pos_lims, d_pos_ids, neg_lims, d_neg_ids, nq);
+    like_check_device_ids(d_pos_ids, d_neg_ids);
+    if (nq == 0) return VDB_OK;
+    VDB_REQUIRE(d_out_queries, "null argument");
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_out_queries) % 4 == 0, "like: d_out_queries must be 4-byte aligned");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the ids on the caller's stream
+    run_synced(ix, *ws, [&] {
+        const Index::LikeLists ll = like_upload_lims(ix, *ws, pos_lims, d_pos_ids, neg_lims, d_neg_ids, nq);
+        ix.like_queries_device(*ws, ll, 0, nq, static_cast<float *>(d_out_queries));
+        VDB_SYNC(ws->stream);
+        ix.like_example_rows += ll.n_examples;
+    });
+    VDB_API_END
+}
+
+int vdb_flat_knn_like(vdb_index *idx, const uint64_t *pos_lims, const uint64_t *pos_rows, const uint64_t *neg_lims, const uint64_t *neg_rows, uint64_t nq,
+                      uint64_t k, int exclude, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx,
+                      float *out_dist, uint64_t *out_count) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    like_check_lists(ix, pos_lims, pos_rows, neg_lims, neg_rows, nq);
+    like_check_rows(ix, pos_lims, pos_rows, nq);
+    like_check_rows(ix, neg_lims, neg_rows, nq);
+    VDB_REQUIRE(nq == 0 || k == 0 || (out_idx && out_dist), "null argument");
+    VDB_REQUIRE(k < (1ull << 31), "flat knn: k too large");
+    std::vector<const RowMask *> rm;
+    if (n_masks) rm = filtered_multi_check(ix, nq, masks, n_masks, mask_of);
+    ix.like_calls++;
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    hipStream_t s = ws->stream;
+    std::vector<char> blob;
+    constexpr uint64_t CHUNK = 16384;
+    run_synced(ix, *ws, [&] {
+        const Index::LikeLists ll = like_upload_rows(ix, *ws, blob, pos_lims, pos_rows, neg_lims, neg_rows, nq);
+        ix.like_example_rows += ll.n_examples;
+        const uint64_t kk = std::max<uint64_t>(k, 1);
+        for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
+            const uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
+            const size_t ib = nb * kk * sizeof(uint64_t), db = nb * kk * sizeof(float), cb = nb * sizeof(uint64_t);
+            const size_t off_d = ib, off_c = (ib + db + 7) & ~size_t(7);
+            ws->out_idx.reserve(off_c + cb);
+            char *d_out = ws->out_idx.as<char>();
+            ix.flat_knn_like_device(*ws, ll, q0, nb, k, exclude != 0, rm.data(), n_masks, n_masks ? mask_of + q0 : nullptr,
+                                    reinterpret_cast<uint64_t *>(d_out), reinterpret_cast<float *>(d_out + off_d), reinterpret_cast<uint64_t *>(d_out + off_c));
+            if (k) {
+                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
+            }
+            std::vector<uint64_t> cnt(nb);
+            VDB_HIP(hipMemcpyAsync(cnt.data(), d_out + off_c, cb, hipMemcpyDeviceToHost, s));
+            VDB_SYNC(s);
+            if (out_count) std::memcpy(out_count + q0, cnt.data(), cb);
+        }
+    });
+    VDB_API_END
+}
+
+int vdb_flat_knn_like_device(vdb_index *idx, const uint64_t *pos_lims, const void *d_pos_ids, const uint64_t *neg_lims, const void *d_neg_ids, uint64_t nq,
+                             uint64_t k, int exclude, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, void *d_out_idx,
+                             void *d_out_dist, void *d_out_count, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    like_check_lists(ix, pos_lims, d_pos_ids, neg_lims, d_neg_ids, nq);
+    like_check_device_ids(d_pos_ids, d_neg_ids);
+    VDB_REQUIRE(nq == 0 || (d_out_count && (k == 0 || (d_out_idx && d_out_dist))), "null argument");
+    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
+    VDB_REQUIRE(k < (1ull << 31), "flat knn: k too large");
+    std::vector<const RowMask *> rm;
+    if (n_masks) rm = filtered_multi_check(ix, nq, masks, n_masks, mask_of);
+    if (nq == 0) {
+        ix.like_calls++;
+        return VDB_OK;
+    }
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the ids on the caller's stream
+    run_synced(ix, *ws, [&] {
+        const Index::LikeLists ll = like_upload_lims(ix, *ws, pos_lims, d_pos_ids, neg_lims, d_neg_ids, nq);  // (throws on a bad id)
+        ix.like_calls++;
+        ix.like_example_rows += ll.n_examples;
+        ix.flat_knn_like_device(*ws, ll, 0, nq, k, exclude != 0, rm.data(), n_masks, mask_of, static_cast<uint64_t *>(d_out_idx),
+                                static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
+    });
+    VDB_API_END
+}
+
+int vdb_drop_listed_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                           const uint64_t *drop_lims, const void *d_drop_ids, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    require_f32_rows(ix);
+    const char *bad = like_check_drop_lims(drop_lims, nq);
+    VDB_REQUIRE(bad == nullptr, bad);
+    VDB_REQUIRE(drop_lims[nq] == 0 || d_drop_ids, "drop listed: null drop list");
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_drop_ids) % 8 == 0, "drop listed: d_drop_ids must be 8-byte aligned");
+    VDB_REQUIRE(nq == 0 || (d_counts && d_out_count && (ld == 0 || (d_ids && d_dists)) && (k == 0 || (d_out_idx && d_out_dist))), "null argument");
+    VDB_REQUIRE(ld < (1ull << 31) && k < (1ull << 31), "drop listed: list length or k too large");
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the lists on the caller's stream
+    run_synced(ix, *ws, [&] {
+        const size_t lb = (nq + 1) * sizeof(uint64_t);
+        ws->grp_table.reserve(lb);
+        VDB_HIP(hipMemcpyAsync(ws->grp_table.p, drop_lims, lb, hipMemcpyHostToDevice, ws->stream));
+        ix.drop_listed_device(*ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), nq,
+                              ld, k, ws->grp_table.as<uint64_t>(), static_cast<const uint64_t *>(d_drop_ids), drop_lims[nq],
+                              static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
+    });
+    VDB_API_END
+}
+
 // ---- bulk row fetch (Index::get_rows*) ----------------------------------------------------------------------------------------------
 int vdb_index_get_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, float *out) {
     VDB_API_BEGIN
@@ -1466,6 +1685,12 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.mmr_calls.load();
     else if (n == "flat_mmr_queries")
         *out = idx->ix.mmr_queries.load();
+    else if (n == "flat_like_calls")  // search by example rows: calls | queries (the two search forms) | list entries the builder walked
+        *out = idx->ix.like_calls.load();
+    else if (n == "flat_like_queries")
+        *out = idx->ix.like_queries.load();
+    else if (n == "like_example_rows")
+        *out = idx->ix.like_example_rows.load();
     else if (n == "update_calls")  // vdb_index_update_rows* calls that changed rows | rows they rewrote
         *out = idx->ix.update_calls.load();
     else if (n == "update_rows")

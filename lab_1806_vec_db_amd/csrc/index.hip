@@ -2416,6 +2416,102 @@ void Index::mmr_select_device(Workspace &ws, const uint64_t *d_ids, const float 
     prof_collect(ws);
 }
 
+// ---- Flat: search by example rows (k_like.hip, like_plan.hpp; 4.1v) ----------------------------------------------------------------------
+// The answer of a query is a prefix of its order with the examples taken out, and a list of k + e_max rows always holds it: one round is
+// the whole call.  The query vectors of a sub-chunk live in grp_q, its lists in the grouped call's buffers; the caller keeps the example
+// lists in grp_table and the flag of the id check is in grp_aux -- none of which the list calls touch.
+void Index::like_queries_device(Workspace &ws, const LikeLists &ll, uint64_t q0, uint64_t nq, float *d_out) {
+    require_f32_rows(*this);
+    if (nq == 0) return;
+    prof_begin(ws, "like_build", double(nq) * dim * sizeof(float));
+    launch_like_build(ll.pos_ids, ll.pos_lims + q0, ll.neg_ids, ll.neg_lims ? ll.neg_lims + q0 : nullptr, ll.global_ids, nq, d_rows.as<float>(), n,
+                      (uint32_t)dim, id_offset, d_out, ws.stream);
+    prof_end(ws);
+}
+
+void Index::flat_knn_like_device(Workspace &ws, const LikeLists &ll, uint64_t q0, uint64_t nq, uint64_t k, bool exclude, const RowMask *const *masks,
+                                 uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
+    hipStream_t s = ws.stream;
+    require_f32_rows(*this);
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 31) && k < (1ull << 31), "flat knn: too many queries or k too large");
+    like_queries += nq;
+    if (k == 0) {
+        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
+        VDB_SYNC(s);
+        return;
+    }
+    uint64_t max_m = n_masks ? 0 : n;
+    for (uint64_t q = 0; n_masks && q < nq; q++) max_m = std::max<uint64_t>(max_m, masks[mask_of[q]]->m);
+    const uint64_t kp = like_list_len(k, ll.e_max, exclude, max_m);
+    const uint64_t sub = like_sub_chunk(nq, kp);
+    // every buffer of the call before its first launch
+    ws.grp_q.reserve(sub * dim * sizeof(float));
+    ws.grp_ids.reserve(sub * kp * sizeof(uint64_t));
+    ws.grp_dist.reserve(sub * kp * sizeof(float));
+    ws.grp_cnt.reserve(sub * sizeof(uint64_t));
+    float *l_q = ws.grp_q.as<float>(), *l_dist = ws.grp_dist.as<float>();
+    uint64_t *l_ids = ws.grp_ids.as<uint64_t>(), *l_cnt = ws.grp_cnt.as<uint64_t>();
+    if (n_masks) filtered_multi_calls++;
+    for (uint64_t c0 = 0; c0 < nq; c0 += sub) {
+        const uint64_t nb = std::min(sub, nq - c0);
+        like_queries_device(ws, ll, q0 + c0, nb, l_q);
+        if (n_masks)
+            flat_knn_masked_multi_device(ws, l_q, nb, kp, masks, n_masks, mask_of + c0, l_ids, l_dist, l_cnt);
+        else
+            flat_knn_device(ws, l_q, nb, kp, l_ids, l_dist, l_cnt);
+        const uint64_t *pl = exclude ? ll.pos_lims + q0 + c0 : nullptr;
+        const uint64_t *nl = exclude && ll.neg_lims ? ll.neg_lims + q0 + c0 : nullptr;
+        prof_begin(ws, "like_drop", double(nb) * kp * LIKE_PAIR_BYTES);
+        launch_like_drop(l_ids, l_dist, l_cnt, nb, kp, ll.pos_ids, pl, ll.neg_ids, nl, ll.global_ids, id_offset, (uint32_t)k, d_idx + c0 * k,
+                         d_dist + c0 * k, d_cnt + c0, s);
+        prof_end(ws);
+    }
+    VDB_SYNC(s);
+    prof_collect(ws);
+}
+
+void Index::like_check_ids_device(Workspace &ws, const uint64_t *d_a, uint64_t ma, const uint64_t *d_b, uint64_t mb) {
+    if (ma + mb == 0) return;
+    hipStream_t s = ws.stream;
+    ws.grp_aux.reserve(sizeof(uint32_t));
+    uint32_t *d_flag = ws.grp_aux.as<uint32_t>();
+    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+    launch_fetch_check(d_a, ma, n, id_offset, d_flag, num_cu, s);
+    launch_fetch_check(d_b, mb, n, id_offset, d_flag, num_cu, s);
+    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
+    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDB_SYNC(s);
+    VDB_REQUIRE(*h_flag == 0, "like: a list holds an id that is no row of this index (id - id_offset must be below len)");
+}
+
+void Index::drop_listed_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                               const uint64_t *d_drop_lims, const uint64_t *d_drop_ids, uint64_t n_drop, uint64_t *d_idx, float *d_dist,
+                               uint64_t *d_cnt) {
+    hipStream_t s = ws.stream;
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 31) && k < (1ull << 31), "drop listed: too many queries or k too large");
+    if (k == 0) {
+        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
+        VDB_SYNC(s);
+        return;
+    }
+    ws.grp_aux.reserve(sizeof(uint32_t));
+    uint32_t *d_flag = ws.grp_aux.as<uint32_t>();
+    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+    launch_group_check(d_ids, d_counts, nq, ld, n, id_offset, d_flag, s);
+    if (n_drop) launch_fetch_check(d_drop_ids, n_drop, n, id_offset, d_flag, num_cu, s);
+    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
+    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDB_SYNC(s);
+    VDB_REQUIRE(*h_flag == 0, "drop listed: a list holds an id that is no row of this index (id - id_offset must be below len)");
+    prof_begin(ws, "like_drop", double(nq) * ld * LIKE_PAIR_BYTES);
+    launch_like_drop(d_ids, d_dists, d_counts, nq, ld, d_drop_ids, d_drop_lims, nullptr, nullptr, true, id_offset, (uint32_t)k, d_idx, d_dist, d_cnt, s);
+    prof_end(ws);
+    VDB_SYNC(s);
+    prof_collect(ws);
+}
+
 // ---- Flat: exact filtered range search with one row mask per query (k_filter.hip, multi_plan.hpp) --------------------------------------
 // Query q's slice is what flat_range_device returns for it alone under masks[mask_of[q]].  The queries are bucketed by mask on the host:
 //   per-mask route: a bucket whose mask is longer than flat_filtered_direct_max, and every bucket of a u8 index, is gathered (queries and

@@ -688,6 +688,31 @@ struct Index {
     void mmr_select_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
                            float lambda, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
     std::atomic<uint64_t> mmr_calls{0}, mmr_queries{0};
+    // Search by example rows (k_like.hip, like_plan.hpp; docs/DESIGN_flat.md 4.1v).  LikeLists: the example lists of a call on the device --
+    // ids (u32 LOCAL rows, or global: u64 row + id_offset) and limits of nq + 1 entries each; neg_lims == nullptr: no negatives.  The caller
+    // has checked the limits (like_check_lims) and every id.
+    struct LikeLists {
+        const void *pos_ids = nullptr, *neg_ids = nullptr;
+        const uint64_t *pos_lims = nullptr, *neg_lims = nullptr;
+        bool global_ids = false;
+        uint64_t e_max = 0, n_examples = 0;  // like_e_max | every list entry of the call
+    };
+    // k_like_build alone: the query vectors of queries q0 .. q0 + nq of the lists into d_out [nq][dim]; enqueued on ws.stream, not synchronised
+    void like_queries_device(Workspace &ws, const LikeLists &ll, uint64_t q0, uint64_t nq, float *d_out);
+    // ONE round: the query vectors, the exact sorted list of K' = like_list_len(..) rows per query -- flat_knn_device without masks,
+    // flat_knn_masked_multi_device over the call's masks, whose counters advance as for those calls -- then k_like_drop, in sub-chunks of
+    // queries whose lists stay under LIKE_LIST_BUDGET.  The queries are q0 .. q0 + nq of the lists (mask_of already advanced).  n_masks == 0:
+    // unfiltered (masks / mask_of not read).  Returns synchronised.
+    void flat_knn_like_device(Workspace &ws, const LikeLists &ll, uint64_t q0, uint64_t nq, uint64_t k, bool exclude, const RowMask *const *masks,
+                              uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
+    // k_like_drop alone over caller-supplied lists [nq][ld] (device), walked as given, against the global ids d_drop_ids under the DEVICE
+    // limits d_drop_lims (n_drop = their last entry): every id of the counted ranges and every listed id is checked on the device first
+    // (one flag read back; a bad one throws before an output is written).  Returns synchronised.
+    void drop_listed_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                            const uint64_t *d_drop_lims, const uint64_t *d_drop_ids, uint64_t n_drop, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
+    // one flag read-back: throws when one of the global ids d_a[0 .. ma) / d_b[0 .. mb) is no row of this index (an empty list is not read)
+    void like_check_ids_device(Workspace &ws, const uint64_t *d_a, uint64_t ma, const uint64_t *d_b, uint64_t mb);
+    std::atomic<uint64_t> like_calls{0}, like_queries{0}, like_example_rows{0};
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};

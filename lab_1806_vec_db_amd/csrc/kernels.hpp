@@ -6,6 +6,7 @@
 
 #include "grouped_plan.hpp"
 #include "labels_scatter_plan.hpp"
+#include "like_plan.hpp"
 #include "mask_any.hpp"
 #include "mask_partition.hpp"
 #include "mask_sets.hpp"
@@ -449,6 +450,19 @@ void launch_mmr_select(const uint64_t *ids, const float *dists, const uint64_t *
 // *flag = 1 when an id of the counted part of a list is no row of the index (id - id_offset not in [0, n)); the caller has zeroed it
 void launch_mmr_check(const uint64_t *ids, const uint64_t *counts, uint64_t nq, uint64_t ld, uint64_t n, uint64_t id_offset, uint32_t *flag,
                       hipStream_t s);
+// The search by example rows (k_like.hip, like_plan.hpp).  launch_like_build: out[q][j] for q < nq, j < dim = the "average vector" of query
+// q's example rows of X [n][dim] -- ap = (strict left fold of the positives pos_ids[pos_lims[q] .. pos_lims[q + 1]) in list order) /
+// their number; with negatives (neg_lims != nullptr and the query's range not empty) an likewise and (ap + ap) - an, otherwise ap.  The
+// ids are u32 LOCAL rows, or (global_ids) u64 row + id_offset; the lims are device arrays of nq + 1 entries; out of any 4-byte alignment.
+void launch_like_build(const void *pos_ids, const uint64_t *pos_lims, const void *neg_ids, const uint64_t *neg_lims, bool global_ids, uint64_t nq,
+                       const float *X, uint64_t n, uint32_t dim, uint64_t id_offset, float *out, hipStream_t s);
+// launch_like_drop: from query b's list ids / dists [b][0 .. min(counts[b], ld)), in the order given, the first k entries whose id is in
+// neither a_ids[a_lims[b] .. a_lims[b + 1]) nor b_ids[b_lims[b] .. ) (a null lims: no such list; at most LIKE_MAX_EXAMPLES ids per query
+// in all; u32 LOCAL rows to which id_offset is added, or u64 global ids) to out_idx / out_dist [b][k] with zeros behind them, their
+// number to out_cnt[b].  k >= 1.
+void launch_like_drop(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nq, uint64_t ld, const void *a_ids,
+                      const uint64_t *a_lims, const void *b_ids, const uint64_t *b_lims, bool global_ids, uint64_t id_offset, uint32_t k,
+                      uint64_t *out_idx, float *out_dist, uint64_t *out_cnt, hipStream_t s);
 void mfma_set_sample_thin(int v);
 void mfma_sample_plan(uint64_t n, uint32_t kprime, uint32_t *step, uint32_t *rank, uint32_t target_floor = 1024);  // target_floor: expected hits per query
 uint64_t mfma_sample_rows(uint64_t n, uint32_t step);

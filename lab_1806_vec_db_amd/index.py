@@ -81,6 +81,7 @@ LABEL_COLUMNS = 16         # VDB_LABEL_COLUMNS
 LABEL_NONE = 0xFFFFFFFF    # VDB_LABEL_NONE
 MASK_MAX_TERMS = 8         # VDB_MASK_MAX_TERMS
 MASK_OP_AND, MASK_OP_OR = 0, 1  # VDB_MASK_OP_AND / VDB_MASK_OP_OR
+LIKE_MAX_EXAMPLES = 1024   # examples of one query of flat_knn_like, positives plus negatives (LIKE_MAX_EXAMPLES of csrc/like_plan.hpp)
 MMR_MAX_FETCH = 4096       # longest candidate list of flat_knn_mmr / mmr_select_device (MMR_MAX_FETCH of csrc/mmr_plan.hpp)
 FETCH_CHUNK_BYTES_DEFAULT = 128 << 20  # what "fetch_chunk_bytes" is until set_param changes it (Index::FETCH_CHUNK_BYTES_DEFAULT)
 
@@ -678,6 +679,78 @@ class GpuIndex:
         is no row of this index raises and leaves the outputs untouched"""
         L.check(self._lib.vdb_mmr_select_device(self._h, L.vp(ids_ptr), L.vp(dists_ptr), L.vp(counts_ptr), int(nq), int(ld), int(k),
                                                 float(lambda_mult), L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
+
+    @staticmethod
+    def _like_lists(lists, nq=None):
+        """(lims, ids) of a list of id lists as u64 arrays: query q's ids are ids[lims[q]:lims[q + 1]]; None -> (None, None)"""
+        if lists is None:
+            return None, None
+        lists = [np.asarray(x, dtype=np.uint64).ravel() for x in lists]
+        if nq is not None and len(lists) != nq:
+            raise ValueError(f"{len(lists)} id lists for {nq} queries")
+        lims = np.zeros(len(lists) + 1, dtype=np.uint64)
+        if lists:
+            lims[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64)
+        ids = np.concatenate(lists).astype(np.uint64) if lists else np.zeros(0, dtype=np.uint64)
+        return lims, np.ascontiguousarray(ids)
+
+    def like_queries(self, positives, negatives=None):
+        """The query vectors of a search by example rows (vdb_like_queries): `positives` / `negatives` are lists of LOCAL row id lists,
+        one per query (negatives=None: none).  Per element, in f32: the strict left fold of a query's positive rows in list order divided
+        by their number, ap; with negatives an likewise and (ap + ap) - an.  -> float32 [nq][dim]."""
+        pl, pr = self._like_lists(positives)
+        nq = len(pl) - 1
+        nl, nr = self._like_lists(negatives, nq)
+        out = np.zeros((nq, self.dim), dtype=np.float32)
+        L.check(self._lib.vdb_like_queries(self._h, _ptr(pl, L.u64p), _ptr(pr, L.u64p), _ptr(nl, L.u64p), _ptr(nr, L.u64p), nq, _ptr(out, L.f32p)))
+        return out
+
+    def like_queries_device(self, pos_lims, pos_ids_ptr: int, neg_lims, neg_ids_ptr: int, nq: int, out_ptr: int, stream: int = 0):
+        """Device form (vdb_like_queries_device): `pos_lims` / `neg_lims` are HOST u64 arrays of nq + 1 limits (neg_lims None: no
+        negatives), the id pointers -> u64 GLOBAL ids (row + id_offset) on this GPU, `out_ptr` -> nq x dim f32 there: a valid query
+        pointer for every *_device search.  An id that is no row of the index raises and leaves the output untouched."""
+        pl = np.ascontiguousarray(pos_lims, dtype=np.uint64)
+        nl = None if neg_lims is None else np.ascontiguousarray(neg_lims, dtype=np.uint64)
+        L.check(self._lib.vdb_like_queries_device(self._h, _ptr(pl, L.u64p), L.vp(pos_ids_ptr), _ptr(nl, L.u64p), L.vp(neg_ids_ptr), int(nq),
+                                                  L.vp(out_ptr), L.vp(stream)))
+
+    def flat_knn_like(self, positives, k: int, negatives=None, exclude: bool = True, masks=None, mask_of=None):
+        """Exact search by example rows (vdb_flat_knn_like): per query the k nearest allowed rows, in flat_knn's order, of the query vector
+        like_queries makes from its `positives` / `negatives` (lists of LOCAL row id lists, at least one positive and at most 1024
+        examples per query); exclude=True leaves every example out of the answer.  masks / mask_of as in flat_knn_grouped.
+        -> (idx [nq][k], dist [nq][k], count [nq]); slots past a count are zero."""
+        pl, pr = self._like_lists(positives)
+        nq = len(pl) - 1
+        nl, nr = self._like_lists(negatives, nq)
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, nq)
+        kk = max(int(k), 1)
+        idx = np.zeros((nq, kk), dtype=np.uint64)
+        dist = np.zeros((nq, kk), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint64)
+        L.check(self._lib.vdb_flat_knn_like(self._h, _ptr(pl, L.u64p), _ptr(pr, L.u64p), _ptr(nl, L.u64p), _ptr(nr, L.u64p), nq, int(k),
+                                            int(bool(exclude)), arr, n_masks, mo_p, _ptr(idx, L.u64p), _ptr(dist, L.f32p), _ptr(cnt, L.u64p)))
+        return idx[:, :int(k)], dist[:, :int(k)], cnt
+
+    def flat_knn_like_device(self, pos_lims, pos_ids_ptr: int, neg_lims, neg_ids_ptr: int, nq: int, k: int, out_idx_ptr: int,
+                             out_dist_ptr: int, out_cnt_ptr: int, exclude: bool = True, masks=None, mask_of=None, stream: int = 0):
+        """Device form (vdb_flat_knn_like_device): limits on the host, u64 GLOBAL ids and the outputs on this GPU, at most 32768 queries"""
+        pl = np.ascontiguousarray(pos_lims, dtype=np.uint64)
+        nl = None if neg_lims is None else np.ascontiguousarray(neg_lims, dtype=np.uint64)
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, int(nq))
+        L.check(self._lib.vdb_flat_knn_like_device(self._h, _ptr(pl, L.u64p), L.vp(pos_ids_ptr), _ptr(nl, L.u64p), L.vp(neg_ids_ptr), int(nq),
+                                                   int(k), int(bool(exclude)), arr, n_masks, mo_p, L.vp(out_idx_ptr), L.vp(out_dist_ptr),
+                                                   L.vp(out_cnt_ptr), L.vp(stream)))
+
+    def drop_listed_device(self, ids_ptr: int, dists_ptr: int, counts_ptr: int, nq: int, ld: int, k: int, drop_lims, drop_ids_ptr: int,
+                           out_idx_ptr: int, out_dist_ptr: int, out_cnt_ptr: int, stream: int = 0):
+        """the compaction alone over caller-supplied device lists [nq][ld] (u64 ids, f32 distances) and u64 counts, walked in the order
+        given (vdb_drop_listed_device): per query the first k entries whose id is not among drop_ids[drop_lims[q]:drop_lims[q + 1]]
+        (HOST limits, u64 global ids on the device, at most 1024 per query); an id that is no row of this index raises and leaves the
+        outputs untouched"""
+        dl = np.ascontiguousarray(drop_lims, dtype=np.uint64)
+        L.check(self._lib.vdb_drop_listed_device(self._h, L.vp(ids_ptr), L.vp(dists_ptr), L.vp(counts_ptr), int(nq), int(ld), int(k),
+                                                 _ptr(dl, L.u64p), L.vp(drop_ids_ptr), L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr),
+                                                 L.vp(stream)))
 
     def _range_out(self, h, nq: int):
         return read_range(self._lib, h, nq)

@@ -33,6 +33,8 @@ search / batch_search take `group_by`, a metadata key, and `group_size`: at most
 without the key always kept -- exact, from the Flat rows, in one library call over the key's label column (GpuIndex.flat_knn_grouped).
 search / batch_search take `mmr_lambda` and `fetch_k`: maximal marginal relevance, the k hits close to the query and not near-copies of
 each other, chosen greedily among the fetch_k nearest -- exact, from the Flat rows, in one library call (GpuIndex.flat_knn_mmr).
+search_like / batch_search_like search by EXAMPLE ROWS: the rows a `positive` filter matches, steered away from the rows a `negative` filter
+matches, the examples left out of the answer -- the query vector is made on the device, the batch is one library call (GpuIndex.flat_knn_like).
 get(key, filter, limit) returns the vectors and metadata of the matching rows, and every search takes `with_vectors`: the hits' vectors
 ride along, all of a call's from one bulk fetch (GpuIndex.get_rows / get_rows_mask); extract_data reads the table with one such call.
 update_metadata(key, pattern, changes) / batch_update_metadata change the METADATA of the matching rows in place: row ids, vectors, the
@@ -48,7 +50,7 @@ from contextlib import contextmanager
 import numpy as np
 
 from ._lib import VdbError
-from .index import MMR_MAX_FETCH, GpuIndex, RowMask, parse_dist
+from .index import LIKE_MAX_EXAMPLES, MMR_MAX_FETCH, GpuIndex, RowMask, parse_dist
 from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, filter_patterns, has_predicates, is_expression, stale_filters
 from .labels import matches as value_matches
 
@@ -697,6 +699,85 @@ class VecDB:
                 idx, dist, cnt = ix.knn_with_ef(q, k, ef)
             else:
                 idx, dist, cnt = ix.knn(q, k)
+            ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
+            if with_vectors:
+                return self._hits_with_vectors(t, [idx[j, :int(cnt[j])] for j in range(nq)], [dist[j, :int(cnt[j])] for j in range(nq)], ub)
+            return [[(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx[j, :int(cnt[j])], dist[j, :int(cnt[j])]) if d <= ub]
+                    for j in range(nq)]
+
+    def search_like(self, key: str, positive, k: int, negative=None, filter=None, upper_bound: float | None = None,
+                    exclude_examples: bool = True, with_vectors: bool = False):
+        """Search by example rows: batch_search_like for one query (it states the rule); same return shape as search."""
+        return self.batch_search_like(key, [positive], k, None if negative is None else [negative], filter, upper_bound, exclude_examples,
+                                      with_vectors)[0]
+
+    def batch_search_like(self, key: str, positives, k: int, negatives=None, filters=None, upper_bound: float | None = None,
+                          exclude_examples: bool = True, with_vectors: bool = False):
+        """"More like these rows, and not like those", for a batch of queries in ONE library call (GpuIndex.flat_knn_like).  `positives`:
+        one filter per query, of any kind search accepts (a pattern, a pattern with predicates, an expression) -- the rows it matches,
+        in ascending row order, are the query's positive examples; `negatives`: None, or one filter (or None) per query for the rows to
+        steer away from.  The query vector is the average of the positives, plus its difference from the average of the negatives
+        (ap + ap - an per element, in f32), made on the device from the stored rows; the k nearest rows to it come back exactly, from the
+        table's Flat rows, with every example left out unless `exclude_examples` is False.  `filters` restricts the rows searched, as in
+        batch_search; `upper_bound` is applied afterwards; `with_vectors` as in batch_search.  A positive filter that matches no row,
+        and a query with more than 1024 examples, raise ValueError and name the query.  Entry q of the returned list is what
+        search(key, <that query vector>, k, ...) returns, less the examples."""
+        t = self._t(key)
+        ix = t.index
+        positives = list(positives)
+        nq = len(positives)
+        negatives = [None] * nq if negatives is None else list(negatives)
+        if len(negatives) != nq:
+            raise RuntimeError(f"negatives: one filter (or None) per query is needed ({nq}), got {len(negatives)}")
+        if filters is not None and not isinstance(filters, dict) and not is_expression(filters):
+            filters = list(filters)
+            if len(filters) != nq:
+                raise RuntimeError(f"filters: one pattern per query is needed ({nq}), got {len(filters)}")
+        if nq == 0:
+            return []
+        pats = None
+        if filters is not None:
+            pats = [filters] * nq if isinstance(filters, dict) or is_expression(filters) else filters
+        wanted = positives + [f for f in negatives if f is not None] + (pats or [])
+        t.prepare(wanted)
+        with t.lock.read():  # one read guard for the whole batch: masks, example rows, the search and the metadata lookup
+            slot: dict[object, int] = {}
+            distinct = []
+            for f in wanted:
+                fk = filter_key(f)
+                if fk not in slot:
+                    slot[fk] = len(distinct)
+                    distinct.append(f)
+            all_masks = t.masks_for(distinct)  # the ones not cached yet: one library call per kind
+            rows_of: dict[int, np.ndarray] = {}
+
+            def rows(f):
+                s = slot[filter_key(f)]
+                if s not in rows_of:
+                    rows_of[s] = all_masks[s].rows()[1]  # ascending row ids
+                return rows_of[s]
+
+            pos_rows, neg_rows = [], []
+            for i in range(nq):
+                p = rows(positives[i])
+                g = rows(negatives[i]) if negatives[i] is not None else p[:0]
+                if len(p) == 0:
+                    raise ValueError(f"search_like: query {i}: the positive filter matches no row")
+                if len(p) + len(g) > LIKE_MAX_EXAMPLES:
+                    raise ValueError(f"search_like: query {i} has {len(p) + len(g)} example rows, at most {LIKE_MAX_EXAMPLES} are allowed")
+                pos_rows.append(p)
+                neg_rows.append(g)
+            masks = mask_of = None
+            if pats is not None:
+                used: dict[int, int] = {}
+                masks, mask_of = [], np.zeros(nq, dtype=np.uint32)
+                for i, f in enumerate(pats):
+                    s = slot[filter_key(f)]
+                    if s not in used:
+                        used[s] = len(masks)
+                        masks.append(all_masks[s])
+                    mask_of[i] = used[s]
+            idx, dist, cnt = ix.flat_knn_like(pos_rows, k, neg_rows if any(len(g) for g in neg_rows) else None, exclude_examples, masks, mask_of)
             ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
             if with_vectors:
                 return self._hits_with_vectors(t, [idx[j, :int(cnt[j])] for j in range(nq)], [dist[j, :int(cnt[j])] for j in range(nq)], ub)
