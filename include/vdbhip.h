@@ -599,6 +599,78 @@ int vdb_flat_knn_like_device(vdb_index *idx, const uint64_t *pos_lims, const voi
                              void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
 int vdb_drop_listed_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
                            const uint64_t *drop_lims, const void *d_drop_ids, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
+/* ---- fused multi-query Flat search: several searches of one question joined into one ranked answer (RRF, min-distance) ----------------
+ * One question sent as several query vectors (paraphrases, a HyDE passage, sub-questions), or as one vector under several filters, and
+ * the lists joined by reciprocal rank fusion or by "nearest to any of them" -- on the device, exact, deterministic, nothing dragged to
+ * the host.
+ *   All arithmetic is f32, one rounding per operation, no FMA; the divide is the correctly rounded one.  A call holds nq FUSED queries.
+ *   Fused query q owns the sub-queries lims[q] .. lims[q + 1] - 1 of one flat array of query vectors (S_q of them); lims [nq + 1] is a HOST
+ *   array in every form (as mask_of and pos_lims are), lims[0] == 0.  Each sub-query may have its own mask: masks / mask_of are indexed by
+ *   SUB-query and mean what they mean for vdb_flat_knn_filtered_multi; n_masks == 0: unfiltered, they are not read.
+ *   For sub-query s let L_s be its allowed rows in FlatIndex::knn's order -- ascending by (distance, id), NaN distances last -- m_s their
+ *   number, F_s = min(fetch_k, m_s), C_s the first F_s entries of L_s, p_s(row) a row's 0-based position in C_s and d_s(row) its reported
+ *   distance.  U_q = the rows that occur in at least one C_s of the fused query.
+ *   VDB_FUSE_RRF: the score of a row of U_q starts at acc = +0.0f; for s ascending over the sub-queries whose C_s holds the row:
+ *     den = (float)(p_s + 1) + c, term = w_s / den, acc = acc + term.  c = rrf_c, finite and >= 0 (the usual value is 60); w_s =
+ *     weights[s], finite and > 0, a NULL `weights` (HOST, one per sub-query) means 1.0f everywhere.  The answer is the first
+ *     min(k, |U_q|) rows of U_q by score DESCENDING, ties by ascending row id; out_dist carries the score.
+ *   VDB_FUSE_MIN: the score is the smallest d_s(row) over the sub-queries whose C_s holds the row, "smallest" under the knn order (a NaN
+ *     loses to any number, -0 == +0), with the bits of the first s that attains it; `weights` must be NULL.  The answer is ascending by
+ *     (score, id), NaN last.  For fetch_k >= k this is EXACTLY the k allowed rows nearest to any of the sub-queries over the whole table
+ *     (a row allowed to sub-query s counts with d_s): take a row r of that true top-k and the list s* in which its true minimum d* sits.
+ *     If C_s* did not fetch r, C_s* holds fetch_k >= k rows that are before r in L_s*, each with a minimum at or before (d*, their id) --
+ *     k rows better than r, a contradiction.  So r is in C_s*, its fused score is d*, and every other row of U_q carries its true
+ *     minimum or something larger: the first k of U_q are the true top-k, bit for bit.
+ *   Outputs: out_idx (id_offset added) / out_dist [nq][k], out_count[q] = min(k, |U_q|); slots past the count are zero.  fetch_k changes
+ *   the answer: an argument, not a vdb_set_param.  1 <= S_q <= 32, k <= fetch_k <= 4096, S_q x fetch_k <= 16384.  With S_q == 1, MIN is
+ *   vdb_flat_knn / vdb_flat_knn_filtered_multi at the same k bit for bit, and RRF returns the same rows in the same order.
+ *   How: ONE round per sub-chunk of fused queries (their lists, S_max x K' x 12 B each with K' = min(fetch_k, longest allowed set), stay
+ *   under 256 MiB).  The exact sorted lists of ALL its sub-queries come from ONE existing exact search -- the unfiltered call exactly as
+ *   vdb_flat_knn_device runs it, or the filtered call with a mask per query, whose counters advance as if those calls had been made --
+ *   then ONE k_fuse_lists launch (csrc/k_fuse.hip), a workgroup per fused query: the lists are walked in ascending s, which IS the fold
+ *   order, a tile of 256 positions at a time; the rows live in an open-addressing table keyed by the local row (key, accumulator,
+ *   stamp; load <= 1/2; in LDS up to 8192 slots, past that the same code on a slice of device scratch).  A lane claims its slot with a
+ *   compare-and-swap, raises the slot's stamp to (s << 16) | (0xFFFF - position) with an atomic max, and after a barrier only the lane
+ *   whose value IS the stamp folds its term in: one writer per slot per list, no float atomic, no order-dependent sum.  The occupied
+ *   slots are then sorted as (score key, row) pairs and the first k leave with the accumulator's own bits.  A fetch_k above 64 leaves
+ *   the 8-bit first pass of the searches, a step in cost.
+ * vdb_fuse_plan: host utility, works without a GPU (like vdb_fetch_plan): *out_code = 0 when (mode, lims, nq, k, fetch_k, weights, rrf_c)
+ *   is a call the search forms accept, otherwise which refusal: 1 mode, 2 NULL lims, 3 lims[0] != 0, 4 a descent, 5 a fused query without
+ *   a sub-query, 6 more than 32, 7 fetch_k < k, 8 fetch_k > 4096, 9 S x fetch_k > 16384, 10 weights with MIN, 11 a weight that is NaN,
+ *   inf or <= 0, 12 rrf_c NaN, inf or negative -- the first that applies, in this order; nothing else is written then.  Accepted:
+ *   *out_s_max = the most sub-queries of a fused query, *out_table_lg = lg of the kernel's table for lists of fetch_k rows (2^lg slots,
+ *   the smallest power of two >= 2 x S_max x fetch_k, at least 64), *out_in_lds = 1 when it lives in LDS (lg <= 13), *out_scratch_bytes =
+ *   device scratch per fused query otherwise (16 B per slot), *out_sub_chunk = fused queries per sub-chunk under `budget` bytes of lists
+ *   (0: the 256 MiB the calls use; also at most 16384 sub-queries, and the scratch under the same budget).  Any output but out_code may
+ *   be NULL.
+ * vdb_flat_knn_fused_device: queries and outputs on the index's GPU, at most 32768 SUB-queries, returns synchronised.
+ * vdb_fuse_lists_device: the fusion alone over caller-supplied lists -- d_ids (u64, id_offset included) / d_dists (f32) [n_lists][ld],
+ *   d_counts [n_lists] (u64), HOST lims [nq + 1] over the lists, HOST weights [n_lists] or NULL -- into d_out_idx / d_out_dist [nq][k] and
+ *   d_out_count [nq]: what a sharded merge would call, and how the tests drive the kernel.  Lists are walked as given; position is the
+ *   rank; entries past min(count, ld) are not read; k may exceed ld.  If an id occurs more than once in ONE list only its FIRST
+ *   occurrence counts, for the rank and for the distance.  ld <= 4096, S_q x ld <= 16384.  Every counted id is checked on the device
+ *   first (one flag read back): an id that is no row of the index is VDB_ERR_INVALID with the outputs untouched.
+ * Refused before anything is computed or written, counters unchanged (VDB_ERR_INVALID): everything vdb_fuse_plan reports, a VecSet<u8>
+ * index, and every mask / mask_of error of vdb_flat_knn_filtered_multi (a stale mask: VDB_ERR_STATE).  nq == 0, k == 0 and empty lists
+ * give empty results.  Read-side and re-entrant.
+ * vdb_get_stat "flat_fused_calls", "flat_fused_queries" (fused queries), "flat_fused_lists" (sub-queries) count the two search forms;
+ * vdb_prof_get "fuse_lists" times k_fuse_lists.
+ * Not covered: distribution-based score fusion, lists from PQ / HNSW / IVF searches (beyond feeding them to vdb_fuse_lists_device),
+ * VecSet<u8> indexes, sharded and replica contexts, combination with group_by / mmr_lambda. */
+#define VDB_FUSE_RRF 0
+#define VDB_FUSE_MIN 1
+int vdb_fuse_plan(int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, const float *weights, float rrf_c, uint64_t budget,
+                  int *out_code, uint64_t *out_s_max, uint32_t *out_table_lg, int *out_in_lds, uint64_t *out_scratch_bytes,
+                  uint64_t *out_sub_chunk);
+int vdb_flat_knn_fused(vdb_index *idx, const float *queries, const uint64_t *lims, uint64_t nq, uint64_t dim, uint64_t k, uint64_t fetch_k,
+                       int mode, const float *weights, float rrf_c, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of,
+                       uint64_t *out_idx, float *out_dist, uint64_t *out_count);
+int vdb_flat_knn_fused_device(vdb_index *idx, const void *d_queries, const uint64_t *lims, uint64_t nq, uint64_t dim, uint64_t k,
+                              uint64_t fetch_k, int mode, const float *weights, float rrf_c, const vdb_mask *const *masks, uint64_t n_masks,
+                              const uint32_t *mask_of, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
+int vdb_fuse_lists_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, const uint64_t *lims, uint64_t nq,
+                          uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, void *d_out_idx, void *d_out_dist,
+                          void *d_out_count, void *stream);
 /* ---- bulk row fetch: the vectors of many rows as ONE call (no counterpart in the reference) ----------------------------------------
  * vdb_index_row reads one row with one blocking copy.  These calls return the vectors of a LIST of rows: out[j] = row rows[j].  The
  * list only names what is read, so its order is free and repeats are allowed (m may exceed len); every rows[j] must be below len, and a

@@ -359,6 +359,31 @@ public:
         return out;
     }
 
+    // fused multi-query search (vdb_flat_knn_fused): fused query q owns the sub-queries lims[q] .. lims[q + 1] - 1 of `queries` (lims[0] ==
+    // 0, 1 to 32 each); every sub-query contributes its first min(fetch_k, allowed rows) pairs of knn_batch and the lists are joined on the
+    // device.  mode VDB_FUSE_RRF: distance = the score, the f32 left fold over the sub-queries of weight / ((rank + 1) + rrf_c), pairs by
+    // score descending (ties: ascending id); VDB_FUSE_MIN: the smallest distance over the sub-queries, pairs ascending (weights must be
+    // empty).  weights empty: all 1.  masks empty: over all rows; otherwise SUB-query j under *masks[mask_of[j]]
+    std::vector<std::vector<CandidatePair>> knn_fused_batch(const float *queries, const std::vector<uint64_t> &lims, uint64_t k, uint64_t fetch_k,
+                                                            int mode = VDB_FUSE_RRF, const std::vector<float> &weights = {}, float rrf_c = 60.0f,
+                                                            const std::vector<const Mask *> &masks = {},
+                                                            const std::vector<uint32_t> &mask_of = {}) const {
+        if (lims.empty()) throw std::runtime_error("lims: nq + 1 entries are needed");
+        const uint64_t nq = lims.size() - 1, nsub = lims.back();
+        if (!masks.empty() && mask_of.size() != nsub) throw std::runtime_error("mask_of: one entry per sub-query is needed");
+        if (!weights.empty() && weights.size() != nsub) throw std::runtime_error("weights: one entry per sub-query is needed");
+        std::vector<const vdb_mask *> hs;
+        for (const Mask *m : masks) hs.push_back(m->handle());
+        std::vector<uint64_t> idx(nq * (k ? k : 1)), cnt(nq);
+        std::vector<float> d(nq * (k ? k : 1));
+        check(vdb_flat_knn_fused(h_, queries, lims.data(), nq, dim_, k, fetch_k, mode, weights.empty() ? nullptr : weights.data(), rrf_c, hs.data(),
+                                 hs.size(), mask_of.data(), idx.data(), d.data(), cnt.data()));
+        std::vector<std::vector<CandidatePair>> out(nq);
+        for (uint64_t q = 0; q < nq; q++)
+            for (uint64_t j = 0; j < cnt[q]; j++) out[q].push_back({idx[q * k + j], d[q * k + j]});
+        return out;
+    }
+
     // MetadataVecTable::build_hnsw_index / clear_hnsw_index, build_pq_table / clear_pq_table
     void build_hnsw(uint64_t M = 16, uint64_t ef_construction = 200, uint64_t seed = 42, uint64_t batch = 64,
                     int nthreads = 16) {

@@ -87,6 +87,10 @@ SIGNATURES = {
     "vdb_flat_knn_like": [vp, u64p, u64p, u64p, u64p, u64, u64, C.c_int, C.POINTER(vp), u64, u32p, u64p, f32p, u64p],
     "vdb_flat_knn_like_device": [vp, u64p, vp, u64p, vp, u64, u64, C.c_int, C.POINTER(vp), u64, u32p, vp, vp, vp, vp],
     "vdb_drop_listed_device": [vp, vp, vp, vp, u64, u64, u64, u64p, vp, vp, vp, vp, vp],
+    "vdb_fuse_plan": [C.c_int, u64p, u64, u64, u64, f32p, C.c_float, u64, intp, u64p, u32p, intp, u64p, u64p],
+    "vdb_flat_knn_fused": [vp, f32p, u64p, u64, u64, u64, u64, C.c_int, f32p, C.c_float, C.POINTER(vp), u64, u32p, u64p, f32p, u64p],
+    "vdb_flat_knn_fused_device": [vp, vp, u64p, u64, u64, u64, u64, C.c_int, f32p, C.c_float, C.POINTER(vp), u64, u32p, vp, vp, vp, vp],
+    "vdb_fuse_lists_device": [vp, vp, vp, vp, u64p, u64, u64, u64, C.c_int, f32p, C.c_float, vp, vp, vp, vp],
     "vdb_fetch_plan": [u64, u64p, u64, u64, u64, intp, u64p, u64p],
     "vdb_index_get_rows": [vp, u64p, u64, f32p],
     "vdb_index_get_rows_u8": [vp, u64p, u64, u8p],

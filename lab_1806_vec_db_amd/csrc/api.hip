@@ -1303,6 +1303,120 @@ int vdb_drop_listed_device(vdb_index *idx, const void *d_ids, const void *d_dist
     VDB_API_END
 }
 
+// ---- fused multi-query search: several lists per question joined on the device (Index::flat_knn_fused_device, k_fuse.hip, fuse_plan.hpp) --
+// everything that can be refused is refused here, before anything is computed or written; -> the masks as RowMask pointers (none: unfiltered)
+static std::vector<const RowMask *> fused_check(const Index &ix, int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k,
+                                                const float *weights, float rrf_c, const vdb_mask *const *masks, uint64_t n_masks,
+                                                const uint32_t *mask_of) {
+    const char *bad = fuse_bad_text(fuse_check_args(mode, lims, nq, k, fetch_k, weights, rrf_c));
+    VDB_REQUIRE(bad == nullptr, bad);
+    require_f32_rows(ix);
+    if (n_masks == 0) return {};
+    return filtered_multi_check(ix, lims[nq], masks, n_masks, mask_of);
+}
+
+int vdb_fuse_plan(int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, const float *weights, float rrf_c, uint64_t budget,
+                  int *out_code, uint64_t *out_s_max, uint32_t *out_table_lg, int *out_in_lds, uint64_t *out_scratch_bytes, uint64_t *out_sub_chunk) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(out_code, "fuse_plan: null out_code");
+    *out_code = fuse_check_args(mode, lims, nq, k, fetch_k, weights, rrf_c);
+    if (*out_code != FUSE_OK) return VDB_OK;
+    const uint64_t s_max = fuse_s_max(lims, nq);
+    const uint32_t lg = fuse_table_lg(s_max, fetch_k);
+    if (out_s_max) *out_s_max = s_max;
+    if (out_table_lg) *out_table_lg = lg;
+    if (out_in_lds) *out_in_lds = fuse_in_lds(lg) ? 1 : 0;
+    if (out_scratch_bytes) *out_scratch_bytes = fuse_scratch_bytes(1, lg);
+    if (out_sub_chunk) *out_sub_chunk = fuse_sub_chunk(nq, s_max, fetch_k, true, budget ? budget : FUSE_LIST_BUDGET);
+    VDB_API_END
+}
+
+int vdb_flat_knn_fused(vdb_index *idx, const float *queries, const uint64_t *lims, uint64_t nq, uint64_t dim, uint64_t k, uint64_t fetch_k, int mode,
+                       const float *weights, float rrf_c, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx,
+                       float *out_dist, uint64_t *out_count) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_query_args(ix, queries, nq, dim, out_idx, out_dist);
+    const std::vector<const RowMask *> rm = fused_check(ix, mode, lims, nq, k, fetch_k, weights, rrf_c, masks, n_masks, mask_of);
+    ix.fused_calls++;
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    hipStream_t s = ws->stream;
+    const uint64_t kk = std::max<uint64_t>(k, 1);
+    run_synced(ix, *ws, [&] {
+        for (uint64_t q0 = 0; q0 < nq;) {  // chunks of whole fused queries with at most FUSE_MAX_SUBQ sub-queries (a fused query has at most 32)
+            uint64_t q1 = q0 + 1;
+            while (q1 < nq && lims[q1 + 1] - lims[q0] <= FUSE_MAX_SUBQ) q1++;
+            const uint64_t nb = q1 - q0, j0 = lims[q0], nj = lims[q1] - j0;
+            const size_t ib = nb * kk * sizeof(uint64_t), db = nb * kk * sizeof(float), cb = nb * sizeof(uint64_t);
+            const size_t off_d = ib, off_c = (ib + db + 7) & ~size_t(7);
+            ws->q.reserve(nj * ix.dim * sizeof(float));
+            ws->out_idx.reserve(off_c + cb);
+            char *d_out = ws->out_idx.as<char>();
+            VDB_HIP(hipMemcpyAsync(ws->q.p, queries + j0 * ix.dim, nj * ix.dim * sizeof(float), hipMemcpyHostToDevice, s));
+            ix.flat_knn_fused_device(*ws, ws->q.as<float>(), lims + q0, nb, k, fetch_k, mode, weights ? weights + j0 : nullptr, rrf_c, rm.data(), n_masks,
+                                     n_masks ? mask_of + j0 : nullptr, reinterpret_cast<uint64_t *>(d_out), reinterpret_cast<float *>(d_out + off_d),
+                                     reinterpret_cast<uint64_t *>(d_out + off_c));
+            if (k) {
+                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
+            }
+            std::vector<uint64_t> cnt(nb);
+            VDB_HIP(hipMemcpyAsync(cnt.data(), d_out + off_c, cb, hipMemcpyDeviceToHost, s));
+            VDB_SYNC(s);
+            if (out_count) std::memcpy(out_count + q0, cnt.data(), cb);
+            q0 = q1;
+        }
+    });
+    VDB_API_END
+}
+
+int vdb_flat_knn_fused_device(vdb_index *idx, const void *d_queries, const uint64_t *lims, uint64_t nq, uint64_t dim, uint64_t k, uint64_t fetch_k,
+                              int mode, const float *weights, float rrf_c, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of,
+                              void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_query_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist);
+    VDB_REQUIRE(nq == 0 || d_out_count, "null out_count");
+    const std::vector<const RowMask *> rm = fused_check(ix, mode, lims, nq, k, fetch_k, weights, rrf_c, masks, n_masks, mask_of);
+    VDB_REQUIRE(lims[nq] <= 32768, "at most 32768 sub-queries per device call");
+    ix.fused_calls++;
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
+    run_synced(ix, *ws, [&] {
+        ix.flat_knn_fused_device(*ws, static_cast<const float *>(d_queries), lims, nq, k, fetch_k, mode, weights, rrf_c, rm.data(), n_masks, mask_of,
+                                 static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
+    });
+    VDB_API_END
+}
+
+int vdb_fuse_lists_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, const uint64_t *lims, uint64_t nq, uint64_t ld,
+                          uint64_t k, int mode, const float *weights, float rrf_c, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const char *bad = fuse_bad_text(fuse_check_args(mode, lims, nq, k, ld, weights, rrf_c, true));
+    VDB_REQUIRE(bad == nullptr, bad);
+    require_f32_rows(ix);
+    VDB_REQUIRE(k < (1ull << 31), "fuse lists: k too large");
+    VDB_REQUIRE(nq == 0 || (d_counts && d_out_count && (ld == 0 || (d_ids && d_dists)) && (k == 0 || (d_out_idx && d_out_dist))), "null argument");
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the lists on the caller's stream
+    run_synced(ix, *ws, [&] {
+        ix.fuse_lists_device(*ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), lims, nq,
+                             ld, k, mode, weights, rrf_c, static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist),
+                             static_cast<uint64_t *>(d_out_count));
+    });
+    VDB_API_END
+}
+
 // ---- bulk row fetch (Index::get_rows*) ----------------------------------------------------------------------------------------------
 int vdb_index_get_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, float *out) {
     VDB_API_BEGIN
@@ -1691,6 +1805,12 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.like_queries.load();
     else if (n == "like_example_rows")
         *out = idx->ix.like_example_rows.load();
+    else if (n == "flat_fused_calls")  // fused multi-query search: calls | fused queries | sub-queries (the two search forms)
+        *out = idx->ix.fused_calls.load();
+    else if (n == "flat_fused_queries")
+        *out = idx->ix.fused_queries.load();
+    else if (n == "flat_fused_lists")
+        *out = idx->ix.fused_lists.load();
     else if (n == "update_calls")  // vdb_index_update_rows* calls that changed rows | rows they rewrote
         *out = idx->ix.update_calls.load();
     else if (n == "update_rows")

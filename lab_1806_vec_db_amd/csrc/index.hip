@@ -2512,6 +2512,114 @@ void Index::drop_listed_device(Workspace &ws, const uint64_t *d_ids, const float
     prof_collect(ws);
 }
 
+// ---- Flat: fused multi-query search, several lists per question joined on the device (k_fuse.hip, fuse_plan.hpp; 4.1w) --------------------
+// The candidates of a sub-query are a PREFIX of its order of fixed length, so one round is the whole call: the exact sorted lists of
+// kp = min(fetch_k, longest allowed set) rows of every sub-query of a sub-chunk from ONE list call, then ONE fusion launch.  The lists live in
+// the grouped call's buffers, the kernel's scratch in grp_table, [flag | limits | weights] in grp_aux -- which the list calls do not touch.
+struct FuseUpload {
+    const uint64_t *lims;
+    const float *weights;
+};
+// [u64 flag word | lims rebased to 0 | weights] into ws.grp_aux with one copy out of `blob`, which the caller keeps until the stream has been
+// waited for
+static FuseUpload fuse_upload(Workspace &ws, std::vector<char> &blob, const uint64_t *lims, uint64_t nq, const float *weights) {
+    const uint64_t nl = lims[nq] - lims[0];
+    const size_t off_l = sizeof(uint64_t), off_w = off_l + (nq + 1) * sizeof(uint64_t);
+    blob.assign(off_w + (weights ? nl * sizeof(float) : 0), 0);
+    uint64_t *hl = reinterpret_cast<uint64_t *>(blob.data() + off_l);
+    for (uint64_t q = 0; q <= nq; q++) hl[q] = lims[q] - lims[0];
+    if (weights) std::memcpy(blob.data() + off_w, weights, nl * sizeof(float));
+    ws.grp_aux.reserve(blob.size());
+    VDB_HIP(hipMemcpyAsync(ws.grp_aux.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ws.stream));
+    char *d = ws.grp_aux.as<char>();
+    return {reinterpret_cast<const uint64_t *>(d + off_l), weights ? reinterpret_cast<const float *>(d + off_w) : nullptr};
+}
+
+void Index::flat_knn_fused_device(Workspace &ws, const float *d_q, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, int mode,
+                                  const float *weights, float rrf_c, const RowMask *const *masks, uint64_t n_masks, const uint32_t *mask_of,
+                                  uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
+    hipStream_t s = ws.stream;
+    require_f32_rows(*this);
+    if (nq == 0) return;
+    const uint64_t base = lims[0], nl = lims[nq] - base;
+    fused_queries += nq;
+    fused_lists += nl;
+    if (k == 0) {
+        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
+        VDB_SYNC(s);
+        return;
+    }
+    uint64_t max_m = n_masks ? 0 : n;
+    for (uint64_t j = 0; n_masks && j < nl; j++) max_m = std::max<uint64_t>(max_m, masks[mask_of[j]]->m);
+    const uint64_t s_max = fuse_s_max(lims, nq);
+    const uint64_t kp = fuse_list_len(fetch_k, max_m);
+    const uint32_t lg = fuse_table_lg(s_max, kp);
+    const uint64_t sub = fuse_sub_chunk(nq, s_max, kp);
+    // every buffer of the call before its first launch
+    const uint64_t sub_lists = std::min(nl, sub * s_max);
+    ws.grp_ids.reserve(sub_lists * kp * sizeof(uint64_t));
+    ws.grp_dist.reserve(sub_lists * kp * sizeof(float));
+    ws.grp_cnt.reserve(sub_lists * sizeof(uint64_t));
+    if (const size_t tb = fuse_scratch_bytes(sub, lg)) ws.grp_table.reserve(tb);
+    std::vector<char> blob;
+    const FuseUpload up = fuse_upload(ws, blob, lims, nq, weights);
+    uint64_t *l_ids = ws.grp_ids.as<uint64_t>(), *l_cnt = ws.grp_cnt.as<uint64_t>();
+    float *l_dist = ws.grp_dist.as<float>();
+    if (n_masks) filtered_multi_calls++;
+    for (uint64_t c0 = 0; c0 < nq; c0 += sub) {
+        const uint64_t nb = std::min(sub, nq - c0);
+        const uint64_t j0 = lims[c0] - base, nj = lims[c0 + nb] - base - j0;  // the sub-chunk's sub-queries
+        if (n_masks)
+            flat_knn_masked_multi_device(ws, d_q + j0 * dim, nj, kp, masks, n_masks, mask_of + j0, l_ids, l_dist, l_cnt);
+        else
+            flat_knn_device(ws, d_q + j0 * dim, nj, kp, l_ids, l_dist, l_cnt);
+        prof_begin(ws, "fuse_lists", double(nj) * kp * FUSE_PAIR_BYTES);
+        launch_fuse_lists(l_ids, l_dist, l_cnt, nb, kp, up.lims + c0, j0, up.weights, mode, rrf_c, id_offset, (uint32_t)k, lg, ws.grp_table.as<uint32_t>(),
+                          d_idx + c0 * k, d_dist + c0 * k, d_cnt + c0, s);
+        prof_end(ws);
+    }
+    VDB_SYNC(s);  // (`blob` is pageable memory: alive until here)
+    prof_collect(ws);
+}
+
+void Index::fuse_lists_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, const uint64_t *lims, uint64_t nq,
+                              uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
+    hipStream_t s = ws.stream;
+    require_f32_rows(*this);
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 31) && k < (1ull << 31), "fuse lists: too many fused queries or k too large");
+    if (k == 0 || ld == 0) {
+        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
+        if (k) {
+            VDB_HIP(hipMemsetAsync(d_idx, 0, nq * k * sizeof(uint64_t), s));
+            VDB_HIP(hipMemsetAsync(d_dist, 0, nq * k * sizeof(float), s));
+        }
+        VDB_SYNC(s);
+        return;
+    }
+    const uint64_t s_max = fuse_s_max(lims, nq);
+    const uint32_t lg = fuse_table_lg(s_max, ld);
+    const uint64_t sub = fuse_sub_chunk(nq, s_max, ld, false);
+    if (const size_t tb = fuse_scratch_bytes(sub, lg)) ws.grp_table.reserve(tb);
+    std::vector<char> blob;
+    const FuseUpload up = fuse_upload(ws, blob, lims, nq, weights);  // (the flag word in front: zero)
+    uint32_t *d_flag = ws.grp_aux.as<uint32_t>();
+    launch_group_check(d_ids, d_counts, lims[nq], ld, n, id_offset, d_flag, s);
+    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
+    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDB_SYNC(s);
+    VDB_REQUIRE(*h_flag == 0, "fuse lists: a list holds an id that is no row of this index (id - id_offset must be below len)");
+    for (uint64_t c0 = 0; c0 < nq; c0 += sub) {
+        const uint64_t nb = std::min(sub, nq - c0);
+        prof_begin(ws, "fuse_lists", double(lims[c0 + nb] - lims[c0]) * ld * FUSE_PAIR_BYTES);
+        launch_fuse_lists(d_ids, d_dists, d_counts, nb, ld, up.lims + c0, 0, up.weights, mode, rrf_c, id_offset, (uint32_t)k, lg,
+                          ws.grp_table.as<uint32_t>(), d_idx + c0 * k, d_dist + c0 * k, d_cnt + c0, s);
+        prof_end(ws);
+    }
+    VDB_SYNC(s);
+    prof_collect(ws);
+}
+
 // ---- Flat: exact filtered range search with one row mask per query (k_filter.hip, multi_plan.hpp) --------------------------------------
 // Query q's slice is what flat_range_device returns for it alone under masks[mask_of[q]].  The queries are bucketed by mask on the host:
 //   per-mask route: a bucket whose mask is longer than flat_filtered_direct_max, and every bucket of a u8 index, is gathered (queries and

@@ -713,6 +713,22 @@ struct Index {
     // one flag read-back: throws when one of the global ids d_a[0 .. ma) / d_b[0 .. mb) is no row of this index (an empty list is not read)
     void like_check_ids_device(Workspace &ws, const uint64_t *d_a, uint64_t ma, const uint64_t *d_b, uint64_t mb);
     std::atomic<uint64_t> like_calls{0}, like_queries{0}, like_example_rows{0};
+    // Fused multi-query Flat search (k_fuse.hip, fuse_plan.hpp; docs/DESIGN_flat.md 4.1w): fused query q owns the sub-queries
+    // lims[q] - lims[0] .. lims[q + 1] - lims[0] - 1 of d_q (lims: HOST, nq + 1 entries, any base); its answer is the fusion (mode FUSE_RRF /
+    // FUSE_MIN) of their lists, each the first min(fetch_k, m_s) rows of FlatIndex::knn's order over the sub-query's allowed rows.  ONE round
+    // per sub-chunk of fused queries (fuse_sub_chunk): the lists of all its sub-queries from ONE flat_knn_device call, or ONE
+    // flat_knn_masked_multi_device call over the call's masks, whose counters advance as for those calls, then ONE k_fuse_lists launch.
+    // weights (HOST, one per sub-query, nullptr: all 1.0f) and mask_of (one per sub-query) start at the call's first sub-query.
+    // n_masks == 0: unfiltered (masks / mask_of not read).  The caller has checked the arguments (fuse_check_args), the masks and mask_of;
+    // returns synchronised.
+    void flat_knn_fused_device(Workspace &ws, const float *d_q, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, int mode,
+                               const float *weights, float rrf_c, const RowMask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx,
+                               float *d_dist, uint64_t *d_cnt);
+    // k_fuse_lists alone over caller-supplied lists [lims[nq]][ld] (device), walked as given (lims: HOST, from 0): every id of the counted
+    // ranges is checked on the device first (one flag read back; a bad one throws before an output is written).  Returns synchronised.
+    void fuse_lists_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, const uint64_t *lims, uint64_t nq,
+                           uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
+    std::atomic<uint64_t> fused_calls{0}, fused_queries{0}, fused_lists{0};
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};

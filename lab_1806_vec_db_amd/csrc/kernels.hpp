@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "fuse_plan.hpp"
 #include "grouped_plan.hpp"
 #include "labels_scatter_plan.hpp"
 #include "like_plan.hpp"
@@ -463,6 +464,17 @@ void launch_like_build(const void *pos_ids, const uint64_t *pos_lims, const void
 void launch_like_drop(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nq, uint64_t ld, const void *a_ids,
                       const uint64_t *a_lims, const void *b_ids, const uint64_t *b_lims, bool global_ids, uint64_t id_offset, uint32_t k,
                       uint64_t *out_idx, float *out_dist, uint64_t *out_cnt, hipStream_t s);
+// The fusion of the fused multi-query search (k_fuse.hip, fuse_plan.hpp): fused query b owns the lists lims[b] .. lims[b + 1] - 1 (device
+// array of nq + 1 entries; at most FUSE_MAX_LISTS each); list l is ids / dists [l - list_base][0 .. min(counts[l - list_base], ld)), walked as
+// given, its weight weights[l] (nullptr: 1.0f).  mode FUSE_RRF: score = the left fold over the lists, ascending, of
+// w / ((float)(position + 1) + c) at the row's FIRST position in the list, the answer descending by (score, then ascending row);
+// FUSE_MIN: score = the smallest distance under the knn order, the bits of the first list that attains it, ascending by (score, row).
+// The first min(k, distinct rows) go to out_idx (id_offset added) / out_dist [b][k] with zeros behind them, their number to out_cnt[b].
+// lg = fuse_table_lg(most lists of a fused query, ld); scratch: fuse_scratch_bytes(nq, lg) bytes, unused while the table fits LDS.
+// Every counted id must be a row of the index (id - id_offset < 2^32 - 1).
+void launch_fuse_lists(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nq, uint64_t ld, const uint64_t *lims,
+                       uint64_t list_base, const float *weights, int mode, float c, uint64_t id_offset, uint32_t k, uint32_t lg, uint32_t *scratch,
+                       uint64_t *out_idx, float *out_dist, uint64_t *out_cnt, hipStream_t s);
 void mfma_set_sample_thin(int v);
 void mfma_sample_plan(uint64_t n, uint32_t kprime, uint32_t *step, uint32_t *rank, uint32_t target_floor = 1024);  // target_floor: expected hits per query
 uint64_t mfma_sample_rows(uint64_t n, uint32_t step);

@@ -82,6 +82,8 @@ LABEL_NONE = 0xFFFFFFFF    # VDB_LABEL_NONE
 MASK_MAX_TERMS = 8         # VDB_MASK_MAX_TERMS
 MASK_OP_AND, MASK_OP_OR = 0, 1  # VDB_MASK_OP_AND / VDB_MASK_OP_OR
 LIKE_MAX_EXAMPLES = 1024   # examples of one query of flat_knn_like, positives plus negatives (LIKE_MAX_EXAMPLES of csrc/like_plan.hpp)
+FUSE_MODES = {"rrf": 0, "min": 1}  # VDB_FUSE_RRF / VDB_FUSE_MIN
+FUSE_MAX_FETCH = 4096      # longest list of flat_knn_fused / fuse_lists_device (FUSE_MAX_FETCH of csrc/fuse_plan.hpp)
 MMR_MAX_FETCH = 4096       # longest candidate list of flat_knn_mmr / mmr_select_device (MMR_MAX_FETCH of csrc/mmr_plan.hpp)
 FETCH_CHUNK_BYTES_DEFAULT = 128 << 20  # what "fetch_chunk_bytes" is until set_param changes it (Index::FETCH_CHUNK_BYTES_DEFAULT)
 
@@ -679,6 +681,65 @@ class GpuIndex:
         is no row of this index raises and leaves the outputs untouched"""
         L.check(self._lib.vdb_mmr_select_device(self._h, L.vp(ids_ptr), L.vp(dists_ptr), L.vp(counts_ptr), int(nq), int(ld), int(k),
                                                 float(lambda_mult), L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
+
+    @staticmethod
+    def _fuse_args(lims, mode, weights):
+        """(lims u64, mode code, weights f32 or None) of a fused call; `mode` is "rrf" / "min" or the library's code"""
+        lm = np.ascontiguousarray(lims, dtype=np.uint64).ravel()
+        if lm.size == 0:
+            raise ValueError("lims: nq + 1 entries are needed")
+        code = FUSE_MODES.get(mode, mode) if isinstance(mode, str) else int(mode)
+        if isinstance(code, str):
+            raise ValueError(f"fusion mode {mode!r}: 'rrf' or 'min'")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+            if w.size != int(lm[-1]):
+                raise ValueError(f"{w.size} weights for {int(lm[-1])} sub-queries")
+        return lm, code, w
+
+    def flat_knn_fused(self, queries, lims, k: int, fetch_k: int, mode="rrf", weights=None, rrf_c: float = 60.0, masks=None, mask_of=None):
+        """Fused multi-query exact search (vdb_flat_knn_fused): fused query q owns the sub-queries lims[q] .. lims[q + 1] - 1 of `queries`
+        (1 to 32 each); each sub-query contributes the first min(fetch_k, allowed rows) rows of flat_knn's order and the lists are joined
+        on the device.  mode="rrf": score = the f32 left fold over the sub-queries, ascending, of weight / ((rank + 1) + rrf_c), hits by
+        score descending (ties: ascending id), `dist` carries the score.  mode="min": the smallest distance over the sub-queries, hits
+        ascending -- for fetch_k >= k exactly the k rows nearest to any sub-query; weights must be None.  masks / mask_of as in
+        flat_knn_grouped, indexed by SUB-query.  k <= fetch_k <= 4096, sub-queries x fetch_k <= 16384.
+        -> (idx [nq][k], dist [nq][k], count [nq]); slots past a count are zero."""
+        lm, code, w = self._fuse_args(lims, mode, weights)
+        q = _f32(queries)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        if q.shape[0] != int(lm[-1]):
+            raise ValueError(f"{q.shape[0]} query vectors for {int(lm[-1])} sub-queries")
+        nq = lm.size - 1
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, q.shape[0])
+        kk = max(int(k), 1)
+        idx = np.zeros((nq, kk), dtype=np.uint64)
+        dist = np.zeros((nq, kk), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint64)
+        L.check(self._lib.vdb_flat_knn_fused(self._h, _ptr(q, L.f32p), _ptr(lm, L.u64p), nq, q.shape[1], int(k), int(fetch_k), code, _ptr(w, L.f32p),
+                                             float(rrf_c), arr, n_masks, mo_p, _ptr(idx, L.u64p), _ptr(dist, L.f32p), _ptr(cnt, L.u64p)))
+        return idx[:, :int(k)], dist[:, :int(k)], cnt
+
+    def flat_knn_fused_device(self, q_ptr: int, lims, k: int, fetch_k: int, out_idx_ptr: int, out_dist_ptr: int, out_cnt_ptr: int, mode="rrf",
+                              weights=None, rrf_c: float = 60.0, masks=None, mask_of=None, stream: int = 0):
+        """Device form (vdb_flat_knn_fused_device): lims and weights on the host, the sub-queries' vectors and the outputs on this GPU, at
+        most 32768 sub-queries"""
+        lm, code, w = self._fuse_args(lims, mode, weights)
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, int(lm[-1]))
+        L.check(self._lib.vdb_flat_knn_fused_device(self._h, L.vp(q_ptr), _ptr(lm, L.u64p), lm.size - 1, self.dim, int(k), int(fetch_k), code,
+                                                    _ptr(w, L.f32p), float(rrf_c), arr, n_masks, mo_p, L.vp(out_idx_ptr), L.vp(out_dist_ptr),
+                                                    L.vp(out_cnt_ptr), L.vp(stream)))
+
+    def fuse_lists_device(self, ids_ptr: int, dists_ptr: int, counts_ptr: int, lims, ld: int, k: int, out_idx_ptr: int, out_dist_ptr: int,
+                          out_cnt_ptr: int, mode="rrf", weights=None, rrf_c: float = 60.0, stream: int = 0):
+        """the fusion alone over caller-supplied device lists [lims[-1]][ld] (u64 ids, f32 distances; ld <= 4096) and u64 counts, walked in
+        the order given: position is the rank, and of an id that occurs twice in one list only the first occurrence counts
+        (vdb_fuse_lists_device); an id that is no row of this index raises and leaves the outputs untouched"""
+        lm, code, w = self._fuse_args(lims, mode, weights)
+        L.check(self._lib.vdb_fuse_lists_device(self._h, L.vp(ids_ptr), L.vp(dists_ptr), L.vp(counts_ptr), _ptr(lm, L.u64p), lm.size - 1, int(ld),
+                                                int(k), code, _ptr(w, L.f32p), float(rrf_c), L.vp(out_idx_ptr), L.vp(out_dist_ptr),
+                                                L.vp(out_cnt_ptr), L.vp(stream)))
 
     @staticmethod
     def _like_lists(lists, nq=None):

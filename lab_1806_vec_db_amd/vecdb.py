@@ -35,6 +35,9 @@ search / batch_search take `mmr_lambda` and `fetch_k`: maximal marginal relevanc
 each other, chosen greedily among the fetch_k nearest -- exact, from the Flat rows, in one library call (GpuIndex.flat_knn_mmr).
 search_like / batch_search_like search by EXAMPLE ROWS: the rows a `positive` filter matches, steered away from the rows a `negative` filter
 matches, the examples left out of the answer -- the query vector is made on the device, the batch is one library call (GpuIndex.flat_knn_like).
+search_fused / batch_search_fused join SEVERAL searches of one question -- several query vectors, or one vector under several filters --
+into one ranked answer on the device, by reciprocal rank fusion or by the smallest distance; the batch is one library call
+(GpuIndex.flat_knn_fused).
 get(key, filter, limit) returns the vectors and metadata of the matching rows, and every search takes `with_vectors`: the hits' vectors
 ride along, all of a call's from one bulk fetch (GpuIndex.get_rows / get_rows_mask); extract_data reads the table with one such call.
 update_metadata(key, pattern, changes) / batch_update_metadata change the METADATA of the matching rows in place: row ids, vectors, the
@@ -50,7 +53,7 @@ from contextlib import contextmanager
 import numpy as np
 
 from ._lib import VdbError
-from .index import LIKE_MAX_EXAMPLES, MMR_MAX_FETCH, GpuIndex, RowMask, parse_dist
+from .index import FUSE_MAX_FETCH, LIKE_MAX_EXAMPLES, MMR_MAX_FETCH, GpuIndex, RowMask, parse_dist
 from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, filter_patterns, has_predicates, is_expression, stale_filters
 from .labels import matches as value_matches
 
@@ -778,6 +781,95 @@ class VecDB:
                         masks.append(all_masks[s])
                     mask_of[i] = used[s]
             idx, dist, cnt = ix.flat_knn_like(pos_rows, k, neg_rows if any(len(g) for g in neg_rows) else None, exclude_examples, masks, mask_of)
+            ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
+            if with_vectors:
+                return self._hits_with_vectors(t, [idx[j, :int(cnt[j])] for j in range(nq)], [dist[j, :int(cnt[j])] for j in range(nq)], ub)
+            return [[(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx[j, :int(cnt[j])], dist[j, :int(cnt[j])]) if d <= ub]
+                    for j in range(nq)]
+
+    def search_fused(self, key: str, queries, k: int, fusion: str = "rrf", weights=None, filters=None, fetch_k: int | None = None,
+                     rrf_c: float = 60.0, upper_bound: float | None = None, with_vectors: bool = False):
+        """Several searches of ONE question joined into one ranked answer: batch_search_fused for one question (it states the rule).
+        `queries`: the vectors of the question; `weights`: None or one per vector; `filters`: None, one filter for every vector, or one
+        per vector.  Entries are (metadata, score[, vector])."""
+        return self.batch_search_fused(key, [queries], k, fusion, None if weights is None else [weights], None if filters is None else [filters],
+                                       fetch_k, rrf_c, upper_bound, with_vectors)[0]
+
+    def batch_search_fused(self, key: str, query_groups, k: int, fusion: str = "rrf", weights=None, filters=None, fetch_k: int | None = None,
+                           rrf_c: float = 60.0, upper_bound: float | None = None, with_vectors: bool = False):
+        """Fused multi-query search for a batch of questions in ONE library call (GpuIndex.flat_knn_fused).  `query_groups`: per
+        question its 1 to 32 query vectors (paraphrases, a HyDE passage, sub-questions -- or one vector repeated under several filters).
+        Every vector is searched exactly, from the table's Flat rows, for its `fetch_k` nearest matching rows (default 4 k, raised to k,
+        clamped to 4096) and the lists of a question are joined on the device:
+          fusion="rrf": reciprocal rank fusion -- a row's score is the sum, over the lists that hold it in list order, of
+            weight / (rank + 1 + rrf_c) in f32; hits by score descending (ties: the lower row), the entry's second item is the score.
+          fusion="min": a row's score is its smallest distance to any of the vectors; hits ascending -- exactly the k matching rows
+            nearest to any of the vectors; `weights` must be None.
+        `weights`: None, or per question None or one positive number per vector.  `filters`: None; ONE filter for every vector of the
+        batch; or per question None, one filter, or one filter (or None: every row) per vector -- of any kind search accepts, through
+        the mask cache, one mask per distinct filter.  `upper_bound`: fusion="min" only (the score is a distance), applied afterwards;
+        with "rrf" it is a ValueError.  `with_vectors` as in batch_search.  One read guard covers the batch."""
+        if fusion not in ("rrf", "min"):
+            raise ValueError(f"fusion {fusion!r}: 'rrf' or 'min'")
+        if upper_bound is not None and fusion != "min":
+            raise ValueError("upper_bound applies to fusion='min' only: an RRF score is no distance")
+        t = self._t(key)
+        ix = t.index
+        groups = [np.asarray(g, dtype=np.float32) for g in query_groups]
+        groups = [g.reshape(1, -1) if g.ndim == 1 else g for g in groups]
+        nq = len(groups)
+        for i, g in enumerate(groups):
+            if g.ndim != 2 or g.shape[1] != ix.dim or g.shape[0] == 0:
+                raise RuntimeError(f"Dimension mismatch: table dim {ix.dim}, question {i} got {g.shape}")
+        if nq == 0:
+            return []
+        sizes = [g.shape[0] for g in groups]
+        lims = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+        w = None
+        if weights is not None:
+            weights = list(weights)
+            if len(weights) != nq:
+                raise RuntimeError(f"weights: one list (or None) per question is needed ({nq}), got {len(weights)}")
+            if any(x is not None for x in weights):
+                parts = [np.ones(sizes[i], dtype=np.float32) if x is None else np.asarray(x, dtype=np.float32).ravel() for i, x in enumerate(weights)]
+                for i, x in enumerate(parts):
+                    if x.shape[0] != sizes[i]:
+                        raise RuntimeError(f"weights: question {i} has {sizes[i]} vectors and {x.shape[0]} weights")
+                w = np.concatenate(parts)
+        pats = None  # one filter per sub-query, or None: unfiltered
+        if filters is not None:
+            one = lambda f: isinstance(f, dict) or is_expression(f)  # noqa: E731
+            if one(filters):
+                pats = [filters] * int(lims[-1])
+            else:
+                filters = list(filters)
+                if len(filters) != nq:
+                    raise RuntimeError(f"filters: one entry per question is needed ({nq}), got {len(filters)}")
+                pats = []
+                for i, f in enumerate(filters):
+                    if f is None or one(f):
+                        pats += [{} if f is None else f] * sizes[i]
+                    else:
+                        f = list(f)
+                        if len(f) != sizes[i]:
+                            raise RuntimeError(f"filters: question {i} has {sizes[i]} vectors and {len(f)} filters")
+                        pats += [{} if x is None else x for x in f]
+            t.prepare(pats)
+        q = np.ascontiguousarray(np.concatenate(groups, axis=0))
+        fk = min(max(4 * int(k) if fetch_k is None else int(fetch_k), int(k)), FUSE_MAX_FETCH)
+        with t.lock.read():  # one read guard for the whole batch, mask building and metadata lookup included
+            masks = mask_of = None
+            if pats is not None:
+                slot: dict[object, int] = {}
+                distinct, mask_of = [], np.zeros(len(pats), dtype=np.uint32)
+                for i, p in enumerate(pats):
+                    pk = filter_key(p)
+                    if pk not in slot:
+                        slot[pk] = len(distinct)
+                        distinct.append(p)
+                    mask_of[i] = slot[pk]
+                masks = t.masks_for(distinct)  # the ones not cached yet: one library call
+            idx, dist, cnt = ix.flat_knn_fused(q, lims, k, fk, fusion, w, rrf_c, masks, mask_of)
             ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
             if with_vectors:
                 return self._hits_with_vectors(t, [idx[j, :int(cnt[j])] for j in range(nq)], [dist[j, :int(cnt[j])] for j in range(nq)], ub)
