@@ -82,6 +82,52 @@ static void run_synced(Index &ix, Workspace &ws, Body &&body) {
     ix.prof_collect(ws);
 }
 
+// The outputs of nb queries of a host call: ONE device block [ids | distances | counts] in ws.out_idx, and its way back to the host --
+// through the workspace's pinned block (one async copy, then memcpy) when `staged`, else three copies into the caller's pageable arrays.
+struct OutBlock {
+    static constexpr size_t STAGE_MAX = size_t(8) << 20;  // a call whose pinned block would pass this goes unstaged
+    uint64_t nb, k;
+    size_t off_d, off_c, bytes;
+    char *d;
+    OutBlock(Workspace &ws, uint64_t nb_, uint64_t k_) : nb(nb_), k(k_) {
+        const uint64_t kk = std::max<uint64_t>(k, 1);
+        off_d = nb * kk * sizeof(uint64_t);
+        off_c = (off_d + nb * kk * sizeof(float) + 7) & ~size_t(7);
+        bytes = off_c + nb * sizeof(uint64_t);
+        ws.out_idx.reserve(bytes);
+        d = ws.out_idx.as<char>();
+    }
+    uint64_t *idx() const { return reinterpret_cast<uint64_t *>(d); }
+    float *dist() const { return reinterpret_cast<float *>(d + off_d); }
+    uint64_t *cnt() const { return reinterpret_cast<uint64_t *>(d + off_c); }
+    // -> out_idx / out_dist [q0 ..][k], out_count [q0 ..] (nullptr: not wanted); staged: the block goes to pin_off of the pinned block, whose
+    // pointer is fetched here, after the search (which may have used the block for its own flags and has synchronised after reading
+    // them: the block is free again).  Returns synchronised.
+    void download(Workspace &ws, bool staged, size_t pin_off, uint64_t q0, uint64_t *out_idx, float *out_dist, uint64_t *out_count) const {
+        hipStream_t s = ws.stream;
+        const size_t cb = nb * sizeof(uint64_t);
+        if (staged) {
+            char *h = static_cast<char *>(ws.pinned(pin_off + bytes)) + pin_off;
+            VDB_HIP(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s));
+            VDB_SYNC(s);
+            if (k) {
+                std::memcpy(out_idx + q0 * k, h, nb * k * sizeof(uint64_t));
+                std::memcpy(out_dist + q0 * k, h + off_d, nb * k * sizeof(float));
+            }
+            if (out_count) std::memcpy(out_count + q0, h + off_c, cb);
+        } else {
+            if (k) {
+                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
+            }
+            std::vector<uint64_t> cnt(nb);
+            VDB_HIP(hipMemcpyAsync(cnt.data(), d + off_c, cb, hipMemcpyDeviceToHost, s));
+            VDB_SYNC(s);
+            if (out_count) std::memcpy(out_count + q0, cnt.data(), cb);
+        }
+    }
+};
+
 // The k-NN front ends take the search as fn(ws, d_q, q0, nb, d_idx, d_dist, d_cnt): nb queries at d_q, which are the call's queries
 // q0 .. q0 + nb (what a per-query argument such as mask_of is advanced by), answered into the three device outputs (`auto... o` in the
 // lambdas below); k, ef and whatever else the search needs are the callable's own captures.
@@ -96,45 +142,22 @@ static void host_search(Index &ix, const float *queries, uint64_t nq, uint64_t k
     run_synced(ix, *ws, [&] {
         for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
             uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
-            uint64_t kk = std::max<uint64_t>(k, 1);
-            // ONE device block for the three outputs [ids | distances | counts] and ONE pinned host block [queries | that block]:
+            // ONE device block for the three outputs (OutBlock) and ONE pinned host block [queries | that block]:
             // a call moves two async copies through page-locked memory instead of four pageable ones (each of which the runtime
             // stages and waits for on its own) -- what a db.search()-shaped call of one query pays for besides its kernels
-            const size_t qb = nb * ix.dim * sizeof(float), ib = nb * kk * sizeof(uint64_t), db = nb * kk * sizeof(float), cb = nb * sizeof(uint64_t);
-            const size_t off_d = ib, off_c = (ib + db + 7) & ~size_t(7), ob = off_c + cb, q_pad = (qb + 15) & ~size_t(15);
-            const bool staged = q_pad + ob <= (size_t(8) << 20);
+            const size_t qb = nb * ix.dim * sizeof(float), q_pad = (qb + 15) & ~size_t(15);
             ws->q.reserve(qb);
-            ws->out_idx.reserve(ob);
-            char *d_out = ws->out_idx.as<char>();
-            char *h = staged ? static_cast<char *>(ws->pinned(q_pad + ob)) : nullptr;
+            const OutBlock out(*ws, nb, k);
+            const bool staged = q_pad + out.bytes <= OutBlock::STAGE_MAX;
             if (staged) {
+                char *h = static_cast<char *>(ws->pinned(q_pad + out.bytes));
                 std::memcpy(h, queries + q0 * ix.dim, qb);
                 VDB_HIP(hipMemcpyAsync(ws->q.p, h, qb, hipMemcpyHostToDevice, s));
             } else {
                 VDB_HIP(hipMemcpyAsync(ws->q.p, queries + q0 * ix.dim, qb, hipMemcpyHostToDevice, s));
             }
-            fn(*ws, ws->q.as<float>(), q0, nb, reinterpret_cast<uint64_t *>(d_out), reinterpret_cast<float *>(d_out + off_d),
-               reinterpret_cast<uint64_t *>(d_out + off_c));
-            // (fn may have used the pinned block for its own flags and has synchronised after reading them: the block is free again)
-            if (staged) {
-                h = static_cast<char *>(ws->pinned(q_pad + ob));
-                VDB_HIP(hipMemcpyAsync(h + q_pad, d_out, ob, hipMemcpyDeviceToHost, s));
-                VDB_SYNC(s);
-                if (k) {
-                    std::memcpy(out_idx + q0 * k, h + q_pad, nb * k * sizeof(uint64_t));
-                    std::memcpy(out_dist + q0 * k, h + q_pad + off_d, nb * k * sizeof(float));
-                }
-                if (out_count) std::memcpy(out_count + q0, h + q_pad + off_c, cb);
-            } else {
-                if (k) {
-                    VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                    VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
-                }
-                std::vector<uint64_t> cnt(nb);
-                VDB_HIP(hipMemcpyAsync(cnt.data(), d_out + off_c, cb, hipMemcpyDeviceToHost, s));
-                VDB_SYNC(s);
-                if (out_count) std::memcpy(out_count + q0, cnt.data(), cb);
-            }
+            fn(*ws, ws->q.as<float>(), q0, nb, out.idx(), out.dist(), out.cnt());
+            out.download(*ws, staged, q_pad, q0, out_idx, out_dist, out_count);
         }
     });
 }
@@ -163,6 +186,29 @@ static void device_search(Index &ix, const void *d_queries, uint64_t nq, uint64_
            static_cast<uint64_t *>(d_out_count));
         VDB_SYNC(ws->stream);
     });
+}
+
+// The front end of the list forms (vdb_group_cap_device, vdb_mmr_select_device, vdb_drop_listed_device, vdb_fuse_lists_device): caller-supplied
+// lists d_ids / d_dists [..][ld] with d_counts, outputs [nq][k] and d_out_count, all on the index's GPU.  An entry point keeps its own
+// checks in front of these, in its order: the order of the refusals is part of the contract.
+static void list_form_check(const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k, const void *d_out_idx,
+                            const void *d_out_dist, const void *d_out_count) {
+    VDB_REQUIRE(nq == 0 || (d_counts && d_out_count && (ld == 0 || (d_ids && d_dists)) && (k == 0 || (d_out_idx && d_out_dist))), "null argument");
+}
+// body(Workspace &) behind whatever produced the lists on the caller's stream; nothing to do without queries
+template <class Body>
+static void list_form_run(Index &ix, void *stream, uint64_t nq, Body &&body) {
+    if (nq == 0) return;
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));
+    run_synced(ix, *ws, [&] { body(*ws); });
+}
+template <class Body>
+static void list_form_call(Index &ix, void *stream, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
+                           const void *d_out_idx, const void *d_out_dist, const void *d_out_count, Body &&body) {
+    list_form_check(d_ids, d_dists, d_counts, nq, ld, k, d_out_idx, d_out_dist, d_out_count);
+    list_form_run(ix, stream, nq, body);
 }
 
 // exact Flat range search
@@ -930,6 +976,14 @@ static std::vector<const RowMask *> filtered_multi_check(const Index &ix, uint64
     return rm;
 }
 
+// the masks of an entry point that takes them optionally (grouped, diversified, by example, fused): none -> unfiltered, no RowMask pointers
+static std::vector<const RowMask *> optional_masks_check(const Index &ix, uint64_t rows, const vdb_mask *const *masks, uint64_t n_masks,
+                                                         const uint32_t *mask_of) {
+    require_f32_rows(ix);
+    if (n_masks == 0) return {};
+    return filtered_multi_check(ix, rows, masks, n_masks, mask_of);
+}
+
 // (the checks and the call counter stay in front of the shared front end: they hold for a call without queries too)
 int vdb_flat_knn_filtered_multi(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, const vdb_mask *const *masks,
                                 uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx, float *out_dist, uint64_t *out_count) {
@@ -965,9 +1019,7 @@ static std::vector<const RowMask *> grouped_check(const Index &ix, uint64_t nq, 
                                                   uint64_t n_masks, const uint32_t *mask_of) {
     VDB_REQUIRE(group_size >= 1, "grouped k-NN: group_size must be at least 1");
     VDB_REQUIRE(column < LABEL_COLUMNS, "grouped k-NN: column " + std::to_string(column) + ", an index has " + std::to_string(LABEL_COLUMNS));
-    require_f32_rows(ix);
-    if (n_masks == 0) return {};
-    return filtered_multi_check(ix, nq, masks, n_masks, mask_of);
+    return optional_masks_check(ix, nq, masks, n_masks, mask_of);
 }
 
 int vdb_flat_knn_grouped(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint32_t column, uint64_t group_size,
@@ -1007,19 +1059,10 @@ int vdb_group_cap_device(vdb_index *idx, const void *d_ids, const void *d_dists,
     Index &ix = idx->ix;
     VDB_REQUIRE(group_size >= 1, "grouped k-NN: group_size must be at least 1");
     VDB_REQUIRE(column < LABEL_COLUMNS, "grouped k-NN: column " + std::to_string(column) + ", an index has " + std::to_string(LABEL_COLUMNS));
-    VDB_REQUIRE(nq == 0 || (d_counts && d_out_count && (ld == 0 || (d_ids && d_dists)) && (k == 0 || (d_out_idx && d_out_dist))), "null argument");
-    if (nq == 0) return VDB_OK;
-    ix.use_device();
-    WsLease ws(ix);
-    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the lists on the caller's stream
-    try {
-        ix.group_cap_device(*ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), nq, ld, k,
+    list_form_call(ix, stream, d_ids, d_dists, d_counts, nq, ld, k, d_out_idx, d_out_dist, d_out_count, [&](Workspace &ws) {
+        ix.group_cap_device(ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), nq, ld, k,
                             column, group_size, static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
-    } catch (...) {
-        (void)hipStreamSynchronize(ws->stream);
-        ix.prof_collect(*ws);
-        throw;
-    }
+    });
     VDB_API_END
 }
 
@@ -1029,9 +1072,7 @@ static std::vector<const RowMask *> mmr_check(const Index &ix, uint64_t nq, uint
                                               uint64_t n_masks, const uint32_t *mask_of) {
     const char *bad = mmr_check_args(k, fetch_k, lambda);
     VDB_REQUIRE(bad == nullptr, bad);
-    require_f32_rows(ix);
-    if (n_masks == 0) return {};
-    return filtered_multi_check(ix, nq, masks, n_masks, mask_of);
+    return optional_masks_check(ix, nq, masks, n_masks, mask_of);
 }
 
 int vdb_flat_knn_mmr(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint64_t fetch_k, float lambda,
@@ -1072,13 +1113,8 @@ int vdb_mmr_select_device(vdb_index *idx, const void *d_ids, const void *d_dists
     const char *bad = mmr_check_args(k, ld, lambda);
     VDB_REQUIRE(bad == nullptr, bad);
     require_f32_rows(ix);
-    VDB_REQUIRE(nq == 0 || (d_counts && d_out_count && (ld == 0 || (d_ids && d_dists)) && (k == 0 || (d_out_idx && d_out_dist))), "null argument");
-    if (nq == 0) return VDB_OK;
-    ix.use_device();
-    WsLease ws(ix);
-    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the lists on the caller's stream
-    run_synced(ix, *ws, [&] {
-        ix.mmr_select_device(*ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), nq, ld, k,
+    list_form_call(ix, stream, d_ids, d_dists, d_counts, nq, ld, k, d_out_idx, d_out_dist, d_out_count, [&](Workspace &ws) {
+        ix.mmr_select_device(ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), nq, ld, k,
                              lambda, static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
     });
     VDB_API_END
@@ -1212,35 +1248,21 @@ int vdb_flat_knn_like(vdb_index *idx, const uint64_t *pos_lims, const uint64_t *
     like_check_rows(ix, neg_lims, neg_rows, nq);
     VDB_REQUIRE(nq == 0 || k == 0 || (out_idx && out_dist), "null argument");
     VDB_REQUIRE(k < (1ull << 31), "flat knn: k too large");
-    std::vector<const RowMask *> rm;
-    if (n_masks) rm = filtered_multi_check(ix, nq, masks, n_masks, mask_of);
+    const std::vector<const RowMask *> rm = optional_masks_check(ix, nq, masks, n_masks, mask_of);
     ix.like_calls++;
     if (nq == 0) return VDB_OK;
     ix.use_device();
     WsLease ws(ix);
-    hipStream_t s = ws->stream;
     std::vector<char> blob;
     constexpr uint64_t CHUNK = 16384;
     run_synced(ix, *ws, [&] {
         const Index::LikeLists ll = like_upload_rows(ix, *ws, blob, pos_lims, pos_rows, neg_lims, neg_rows, nq);
         ix.like_example_rows += ll.n_examples;
-        const uint64_t kk = std::max<uint64_t>(k, 1);
         for (uint64_t q0 = 0; q0 < nq; q0 += CHUNK) {
             const uint64_t nb = std::min<uint64_t>(CHUNK, nq - q0);
-            const size_t ib = nb * kk * sizeof(uint64_t), db = nb * kk * sizeof(float), cb = nb * sizeof(uint64_t);
-            const size_t off_d = ib, off_c = (ib + db + 7) & ~size_t(7);
-            ws->out_idx.reserve(off_c + cb);
-            char *d_out = ws->out_idx.as<char>();
-            ix.flat_knn_like_device(*ws, ll, q0, nb, k, exclude != 0, rm.data(), n_masks, n_masks ? mask_of + q0 : nullptr,
-                                    reinterpret_cast<uint64_t *>(d_out), reinterpret_cast<float *>(d_out + off_d), reinterpret_cast<uint64_t *>(d_out + off_c));
-            if (k) {
-                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
-            }
-            std::vector<uint64_t> cnt(nb);
-            VDB_HIP(hipMemcpyAsync(cnt.data(), d_out + off_c, cb, hipMemcpyDeviceToHost, s));
-            VDB_SYNC(s);
-            if (out_count) std::memcpy(out_count + q0, cnt.data(), cb);
+            const OutBlock out(*ws, nb, k);
+            ix.flat_knn_like_device(*ws, ll, q0, nb, k, exclude != 0, rm.data(), n_masks, n_masks ? mask_of + q0 : nullptr, out.idx(), out.dist(), out.cnt());
+            out.download(*ws, out.bytes <= OutBlock::STAGE_MAX, 0, q0, out_idx, out_dist, out_count);
         }
     });
     VDB_API_END
@@ -1257,8 +1279,7 @@ int vdb_flat_knn_like_device(vdb_index *idx, const uint64_t *pos_lims, const voi
     VDB_REQUIRE(nq == 0 || (d_out_count && (k == 0 || (d_out_idx && d_out_dist))), "null argument");
     VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
     VDB_REQUIRE(k < (1ull << 31), "flat knn: k too large");
-    std::vector<const RowMask *> rm;
-    if (n_masks) rm = filtered_multi_check(ix, nq, masks, n_masks, mask_of);
+    const std::vector<const RowMask *> rm = optional_masks_check(ix, nq, masks, n_masks, mask_of);
     if (nq == 0) {
         ix.like_calls++;
         return VDB_OK;
@@ -1286,18 +1307,14 @@ int vdb_drop_listed_device(vdb_index *idx, const void *d_ids, const void *d_dist
     VDB_REQUIRE(bad == nullptr, bad);
     VDB_REQUIRE(drop_lims[nq] == 0 || d_drop_ids, "drop listed: null drop list");
     VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_drop_ids) % 8 == 0, "drop listed: d_drop_ids must be 8-byte aligned");
-    VDB_REQUIRE(nq == 0 || (d_counts && d_out_count && (ld == 0 || (d_ids && d_dists)) && (k == 0 || (d_out_idx && d_out_dist))), "null argument");
-    VDB_REQUIRE(ld < (1ull << 31) && k < (1ull << 31), "drop listed: list length or k too large");
-    if (nq == 0) return VDB_OK;
-    ix.use_device();
-    WsLease ws(ix);
-    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the lists on the caller's stream
-    run_synced(ix, *ws, [&] {
+    list_form_check(d_ids, d_dists, d_counts, nq, ld, k, d_out_idx, d_out_dist, d_out_count);
+    VDB_REQUIRE(ld < (1ull << 31) && k < (1ull << 31), "drop listed: list length or k too large");  // (refused behind a null argument: no list_form_call)
+    list_form_run(ix, stream, nq, [&](Workspace &ws) {
         const size_t lb = (nq + 1) * sizeof(uint64_t);
-        ws->grp_table.reserve(lb);
-        VDB_HIP(hipMemcpyAsync(ws->grp_table.p, drop_lims, lb, hipMemcpyHostToDevice, ws->stream));
-        ix.drop_listed_device(*ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), nq,
-                              ld, k, ws->grp_table.as<uint64_t>(), static_cast<const uint64_t *>(d_drop_ids), drop_lims[nq],
+        ws.grp_table.reserve(lb);
+        VDB_HIP(hipMemcpyAsync(ws.grp_table.p, drop_lims, lb, hipMemcpyHostToDevice, ws.stream));
+        ix.drop_listed_device(ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), nq,
+                              ld, k, ws.grp_table.as<uint64_t>(), static_cast<const uint64_t *>(d_drop_ids), drop_lims[nq],
                               static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
     });
     VDB_API_END
@@ -1310,9 +1327,7 @@ static std::vector<const RowMask *> fused_check(const Index &ix, int mode, const
                                                 const uint32_t *mask_of) {
     const char *bad = fuse_bad_text(fuse_check_args(mode, lims, nq, k, fetch_k, weights, rrf_c));
     VDB_REQUIRE(bad == nullptr, bad);
-    require_f32_rows(ix);
-    if (n_masks == 0) return {};
-    return filtered_multi_check(ix, lims[nq], masks, n_masks, mask_of);
+    return optional_masks_check(ix, lims[nq], masks, n_masks, mask_of);
 }
 
 int vdb_fuse_plan(int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, const float *weights, float rrf_c, uint64_t budget,
@@ -1327,7 +1342,7 @@ int vdb_fuse_plan(int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint6
     if (out_table_lg) *out_table_lg = lg;
     if (out_in_lds) *out_in_lds = fuse_in_lds(lg) ? 1 : 0;
     if (out_scratch_bytes) *out_scratch_bytes = fuse_scratch_bytes(1, lg);
-    if (out_sub_chunk) *out_sub_chunk = fuse_sub_chunk(nq, s_max, fetch_k, true, budget ? budget : FUSE_LIST_BUDGET);
+    if (out_sub_chunk) *out_sub_chunk = fuse_sub_chunk(nq, s_max, fetch_k, true, budget ? budget : LIST_BUDGET);
     VDB_API_END
 }
 
@@ -1344,29 +1359,17 @@ int vdb_flat_knn_fused(vdb_index *idx, const float *queries, const uint64_t *lim
     ix.use_device();
     WsLease ws(ix);
     hipStream_t s = ws->stream;
-    const uint64_t kk = std::max<uint64_t>(k, 1);
     run_synced(ix, *ws, [&] {
         for (uint64_t q0 = 0; q0 < nq;) {  // chunks of whole fused queries with at most FUSE_MAX_SUBQ sub-queries (a fused query has at most 32)
             uint64_t q1 = q0 + 1;
             while (q1 < nq && lims[q1 + 1] - lims[q0] <= FUSE_MAX_SUBQ) q1++;
             const uint64_t nb = q1 - q0, j0 = lims[q0], nj = lims[q1] - j0;
-            const size_t ib = nb * kk * sizeof(uint64_t), db = nb * kk * sizeof(float), cb = nb * sizeof(uint64_t);
-            const size_t off_d = ib, off_c = (ib + db + 7) & ~size_t(7);
             ws->q.reserve(nj * ix.dim * sizeof(float));
-            ws->out_idx.reserve(off_c + cb);
-            char *d_out = ws->out_idx.as<char>();
+            const OutBlock out(*ws, nb, k);
             VDB_HIP(hipMemcpyAsync(ws->q.p, queries + j0 * ix.dim, nj * ix.dim * sizeof(float), hipMemcpyHostToDevice, s));
             ix.flat_knn_fused_device(*ws, ws->q.as<float>(), lims + q0, nb, k, fetch_k, mode, weights ? weights + j0 : nullptr, rrf_c, rm.data(), n_masks,
-                                     n_masks ? mask_of + j0 : nullptr, reinterpret_cast<uint64_t *>(d_out), reinterpret_cast<float *>(d_out + off_d),
-                                     reinterpret_cast<uint64_t *>(d_out + off_c));
-            if (k) {
-                VDB_HIP(hipMemcpyAsync(out_idx + q0 * k, d_out, nb * k * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                VDB_HIP(hipMemcpyAsync(out_dist + q0 * k, d_out + off_d, nb * k * sizeof(float), hipMemcpyDeviceToHost, s));
-            }
-            std::vector<uint64_t> cnt(nb);
-            VDB_HIP(hipMemcpyAsync(cnt.data(), d_out + off_c, cb, hipMemcpyDeviceToHost, s));
-            VDB_SYNC(s);
-            if (out_count) std::memcpy(out_count + q0, cnt.data(), cb);
+                                     n_masks ? mask_of + j0 : nullptr, out.idx(), out.dist(), out.cnt());
+            out.download(*ws, out.bytes <= OutBlock::STAGE_MAX, 0, q0, out_idx, out_dist, out_count);
             q0 = q1;
         }
     });
@@ -1404,13 +1407,8 @@ int vdb_fuse_lists_device(vdb_index *idx, const void *d_ids, const void *d_dists
     VDB_REQUIRE(bad == nullptr, bad);
     require_f32_rows(ix);
     VDB_REQUIRE(k < (1ull << 31), "fuse lists: k too large");
-    VDB_REQUIRE(nq == 0 || (d_counts && d_out_count && (ld == 0 || (d_ids && d_dists)) && (k == 0 || (d_out_idx && d_out_dist))), "null argument");
-    if (nq == 0) return VDB_OK;
-    ix.use_device();
-    WsLease ws(ix);
-    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the lists on the caller's stream
-    run_synced(ix, *ws, [&] {
-        ix.fuse_lists_device(*ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), lims, nq,
+    list_form_call(ix, stream, d_ids, d_dists, d_counts, nq, ld, k, d_out_idx, d_out_dist, d_out_count, [&](Workspace &ws) {
+        ix.fuse_lists_device(ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), lims, nq,
                              ld, k, mode, weights, rrf_c, static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist),
                              static_cast<uint64_t *>(d_out_count));
     });

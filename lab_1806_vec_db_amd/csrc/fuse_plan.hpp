@@ -11,16 +11,14 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "list_plan.hpp"
+
 namespace vdb {
 
 constexpr int FUSE_RRF = 0, FUSE_MIN = 1;        // VDB_FUSE_RRF / VDB_FUSE_MIN
 constexpr uint64_t FUSE_MAX_LISTS = 32;          // sub-queries (lists) of one fused query
 constexpr uint64_t FUSE_MAX_FETCH = 4096;        // longest list: fetch_k of the search forms, ld of the list form
 constexpr uint64_t FUSE_MAX_ENTRIES = 16384;     // lists x list length of one fused query
-// the lists of one sub-chunk -- fused queries x S_max x K' x (8 B id + 4 B distance) -- stay at or under this many bytes, and so does
-// the kernel's scratch (as the MMR call's)
-constexpr uint64_t FUSE_LIST_BUDGET = 256ull << 20;
-constexpr uint64_t FUSE_PAIR_BYTES = 12;
 constexpr uint64_t FUSE_MAX_SUBQ = 16384;        // sub-queries one list call of the search forms takes
 constexpr uint32_t FUSE_THREADS = 256;           // the workgroup of k_fuse_lists; a tile of a list is that many positions
 constexpr uint32_t FUSE_MIN_LG = 6, FUSE_LDS_MAX_LG = 13;  // the table has 2^lg slots; up to 2^13 of them live in LDS (128 KiB)
@@ -100,8 +98,8 @@ inline uint64_t fuse_s_max(const uint64_t *lims, uint64_t nq) {
     return s;
 }
 
-// list length of the search forms' one round: fetch_k clamped to the longest allowed set among the sub-queries, at least 1
-inline uint64_t fuse_list_len(uint64_t fetch_k, uint64_t max_m) { return std::max<uint64_t>(1, std::min(fetch_k, max_m)); }
+// list length of the search forms' one round: fetch_k clamped to the longest allowed set among the sub-queries (list_plan.hpp)
+inline uint64_t fuse_list_len(uint64_t fetch_k, uint64_t max_m) { return list_len(fetch_k, max_m); }
 
 // The table of a launch whose fused queries hold up to s_max lists of ld positions: 2^lg slots, the smallest power of two that keeps the
 // load at or under one half, at least 2^FUSE_MIN_LG.  s_max x ld <= FUSE_MAX_ENTRIES: lg <= 15.
@@ -119,13 +117,13 @@ inline size_t fuse_scratch_bytes(uint64_t nq, uint32_t lg) { return fuse_in_lds(
 // where the table starts probing for a LOCAL row (the tests build colliding ids from it)
 inline uint32_t fuse_hash(uint32_t row, uint32_t lg) { return (row * 2654435761u) >> (32 - lg); }
 
-// Fused queries per sub-chunk: as many as keep the lists (s_max x kp pairs each) and the scratch under the budget and the sub-queries of
+// Fused queries per sub-chunk: as many as keep the lists (s_max x kp pairs each) and the scratch under LIST_BUDGET and the sub-queries of
 // one list call at or under FUSE_MAX_SUBQ; at least 1, at most nq (0 for nq == 0).  search == false (the list form): only the scratch counts.
-inline uint64_t fuse_sub_chunk(uint64_t nq, uint64_t s_max, uint64_t kp, bool search = true, uint64_t budget = FUSE_LIST_BUDGET) {
+inline uint64_t fuse_sub_chunk(uint64_t nq, uint64_t s_max, uint64_t kp, bool search = true, uint64_t budget = LIST_BUDGET) {
     if (nq == 0) return 0;
     const uint64_t sm = std::min<uint64_t>(std::max<uint64_t>(s_max, 1), FUSE_MAX_LISTS), kk = std::min<uint64_t>(std::max<uint64_t>(kp, 1), FUSE_MAX_FETCH);
     uint64_t fit = nq;
-    if (search) fit = std::min(fit, std::min(budget / (sm * kk * FUSE_PAIR_BYTES), FUSE_MAX_SUBQ / sm));
+    if (search) fit = std::min(list_sub_chunk(fit, sm * kk, budget), FUSE_MAX_SUBQ / sm);  // (its floor of 1 is the one below)
     const uint32_t lg = fuse_table_lg(sm, kk);
     if (!fuse_in_lds(lg)) fit = std::min<uint64_t>(fit, budget / fuse_table_bytes(lg));
     return std::max<uint64_t>(1, fit);

@@ -13,35 +13,26 @@
 #include <cstdint>
 #include <vector>
 
+#include "list_plan.hpp"
+
 namespace vdb {
 
 // "flat_grouped_oversample": round 0 fetches min(m, k x this) rows per query.  2 had the smallest summed median of the sweep 1, 2, 4, 8, 16
 // of tools/bench_grouped.py (profiles/flat_grouped_1M.json; docs/DESIGN_flat.md 4.1q has the sweep and what decided it)
 constexpr uint64_t GROUPED_OVERSAMPLE_DEFAULT = 2;
 constexpr uint64_t GROUPED_GROWTH = 4;              // every later round: 4 x the list length of the one before
-// the candidate lists of one sub-chunk -- sub x K' x (8 B id + 4 B distance) -- stay at or under this many bytes
-constexpr uint64_t GROUPED_LIST_BUDGET = 256ull << 20;
-constexpr uint64_t GROUPED_PAIR_BYTES = 12;
 constexpr uint32_t GROUPED_TILE = 64;                // positions the walk takes per step (one wave)
 constexpr uint32_t GROUPED_LDS_MAX_LG = 12;          // tables of up to 2^12 entries (32 KiB) live in LDS, larger ones in global scratch
-
-inline uint64_t grouped_sat_mul(uint64_t a, uint64_t b) { return (a && b > ~0ull / a) ? ~0ull : a * b; }
 
 // list length of round 0: k x oversample (saturating; oversample 0 counts as 1), at least 1, at most max_m (the longest allowed set
 // among the queries of the round; 0: nothing is allowed -- one slot is still asked for so that every buffer has a size)
 inline uint64_t grouped_first_k(uint64_t k, uint64_t oversample, uint64_t max_m) {
-    const uint64_t want = std::max<uint64_t>(1, grouped_sat_mul(k, std::max<uint64_t>(oversample, 1)));
-    return std::max<uint64_t>(1, std::min(want, max_m));
+    return list_len(list_sat_mul(k, std::max<uint64_t>(oversample, 1)), max_m);
 }
 // list length of the round after one of length kp, for queries whose longest allowed set is max_m (> kp, or nothing would be open)
-inline uint64_t grouped_next_k(uint64_t kp, uint64_t max_m) {
-    return std::max<uint64_t>(1, std::min(grouped_sat_mul(kp, GROUPED_GROWTH), max_m));
-}
-// queries per sub-chunk of a round with lists of kp rows: as many as the budget holds, at least 1, at most nq
-inline uint64_t grouped_sub_chunk(uint64_t nq, uint64_t kp, uint64_t budget = GROUPED_LIST_BUDGET) {
-    const uint64_t per = grouped_sat_mul(std::max<uint64_t>(kp, 1), GROUPED_PAIR_BYTES);
-    return std::max<uint64_t>(1, std::min(nq, budget / per));
-}
+inline uint64_t grouped_next_k(uint64_t kp, uint64_t max_m) { return list_len(list_sat_mul(kp, GROUPED_GROWTH), max_m); }
+// queries per sub-chunk of a round with lists of kp rows (list_plan.hpp)
+inline uint64_t grouped_sub_chunk(uint64_t nq, uint64_t kp, uint64_t budget = LIST_BUDGET) { return list_sub_chunk(nq, kp, budget); }
 // a list of kp rows is the whole allowed set of a query with m allowed rows
 inline bool grouped_exhausts(uint64_t kp, uint64_t m) { return m <= kp; }
 

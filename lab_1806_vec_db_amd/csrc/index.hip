@@ -428,13 +428,8 @@ void Index::get_rows_mask(const RowMask &mask, float *out) {
 
 void Index::get_rows_device(Workspace &ws, const uint64_t *d_ids, uint64_t m, void *d_out, hipStream_t s) {
     ws.flags.reserve(sizeof(uint32_t));
-    uint32_t *d_flag = ws.flags.as<uint32_t>();
-    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
-    launch_fetch_check(d_ids, m, n, id_offset, d_flag, num_cu, s);
-    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
-    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    VDB_SYNC(s);
-    VDB_REQUIRE(*h_flag == 0, "get_rows: the list holds an id that is no row of this index (id - id_offset must be below len)");
+    ids_ok(ws, s, ws.flags.as<uint32_t>(), "get_rows: the list holds an id that is no row of this index (id - id_offset must be below len)",
+           [&](uint32_t *d_flag) { launch_fetch_check(d_ids, m, n, id_offset, d_flag, num_cu, s); });
     if (elem_u8)
         launch_rows_gather_widen(d_rows.as<uint8_t>(), dim, d_ids, true, id_offset, static_cast<float *>(d_out), m, num_cu, s);
     else
@@ -544,13 +539,8 @@ void Index::labels_scatter_device(const uint64_t *d_ids, uint64_t m, const uint3
     WsLease ws(*this);
     hipStream_t s = ws->stream;
     ws->flags.reserve(sizeof(uint32_t));
-    uint32_t *d_flag = ws->flags.as<uint32_t>();
-    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
-    launch_fetch_check(d_ids, m, n, id_offset, d_flag, num_cu, s);
-    uint32_t *h_flag = static_cast<uint32_t *>(ws->pinned(sizeof(uint32_t)));
-    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    VDB_SYNC(s);
-    VDB_REQUIRE(*h_flag == 0, "labels_scatter: the list holds an id that is no row of this index (id - id_offset must be below len)");
+    ids_ok(*ws, s, ws->flags.as<uint32_t>(), "labels_scatter: the list holds an id that is no row of this index (id - id_offset must be below len)",
+           [&](uint32_t *d_flag) { launch_fetch_check(d_ids, m, n, id_offset, d_flag, num_cu, s); });
     const LabelCols target = labels_targets(columns, n_cols, s);
     prof_begin(*ws, "labels_scatter", double(m) * (sizeof(uint64_t) + sizeof(uint32_t) * double(2 * n_cols)));
     launch_labels_scatter(target, d_ids, true, id_offset, d_codes, m, num_cu, labels_scatter_max_blocks, s);
@@ -2215,409 +2205,6 @@ void Index::flat_knn_masked_multi_device(Workspace &ws, const float *d_q, uint64
                                        im.slot_q + c.slot0, id_offset, d_idx, d_dist, d_cnt, s);
     }
     VDB_SYNC(s);  // (the plan's and the image's host arrays are pageable memory: alive until here)
-}
-
-// ---- Flat: grouped k-NN, at most g hits per value of one label column (k_group.hip, grouped_plan.hpp; docs/DESIGN_flat.md 4.1q) ----------
-// Whether a row is kept depends only on the rows before it in the query's order, so the capped walk of a PREFIX of that order gives a
-// prefix of the answer: a round fetches the exact sorted list of K' rows and walks it, and a query that neither filled its k slots nor
-// saw its whole allowed set goes round again with a longer list, walked again from its start (the walk is cheap beside the search that
-// made the list, and nothing is carried between rounds but the list of open queries).  Round 0 runs on the call's own query block and
-// mask_of; later rounds on a compacted block.  A round's queries are cut into sub-chunks whose lists stay under GROUPED_LIST_BUDGET; its
-// done bytes are read back once, at its end.
-void Index::flat_knn_grouped_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint32_t column, uint64_t g, const RowMask *const *masks,
-                                    uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
-    hipStream_t s = ws.stream;
-    require_f32_rows(*this);
-    VDB_REQUIRE(column < LABEL_COLUMNS && g >= 1, "grouped k-NN: bad column or group size");
-    if (nq == 0) return;
-    VDB_REQUIRE(nq < (1ull << 32) && k <= (1ull << 30) - GROUPED_TILE, "flat knn: too many queries or k too large");  // (the walk's table: 2^31 entries at most)
-    grouped_queries += nq;
-    if (k == 0) {
-        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
-        VDB_SYNC(s);
-        return;
-    }
-    std::vector<uint64_t> m_of(nq);
-    uint64_t max_m = 0;
-    for (uint64_t q = 0; q < nq; q++) {
-        m_of[q] = n_masks ? masks[mask_of[q]]->m : n;
-        max_m = std::max(max_m, m_of[q]);
-    }
-    const uint32_t *col = label_live[column] ? d_labels[column].as<uint32_t>() : nullptr;
-    const uint32_t g32 = (uint32_t)std::min<uint64_t>(g, 0xFFFFFFFFull);
-    std::vector<uint64_t> active(nq), next;
-    for (uint64_t q = 0; q < nq; q++) active[q] = q;
-    std::vector<uint32_t> slot, mo;
-    uint64_t kp = grouped_first_k(k, flat_grouped_oversample, max_m);
-    uint64_t exhausted = 0, rounds = 0;
-    for (bool first = true; !active.empty(); first = false) {
-        const uint64_t na = active.size();
-        uint64_t sub = grouped_sub_chunk(na, kp);
-        const size_t table1 = group_cap_scratch_bytes(1, k, kp);
-        if (table1) sub = std::max<uint64_t>(1, std::min<uint64_t>(sub, GROUPED_LIST_BUDGET / table1));
-        // every buffer of the round before its first launch; the round before has synchronised
-        const size_t off_slot = na * sizeof(uint64_t), off_done = off_slot + na * sizeof(uint32_t);
-        ws.grp_ids.reserve(sub * kp * sizeof(uint64_t));
-        ws.grp_dist.reserve(sub * kp * sizeof(float));
-        ws.grp_cnt.reserve(sub * sizeof(uint64_t));
-        ws.grp_aux.reserve(off_done + na);
-        if (table1) ws.grp_table.reserve(sub * table1);
-        char *aux = ws.grp_aux.as<char>();
-        const uint32_t *d_slot = nullptr;
-        uint8_t *d_done = reinterpret_cast<uint8_t *>(aux + off_done);
-        const float *Q = d_q;
-        const uint32_t *mof = mask_of;
-        if (!first) {  // the open queries as a block of their own: rows, the map back to the call's positions, their masks
-            ws.grp_q.reserve(na * dim * sizeof(float));
-            slot.resize(na);
-            for (uint64_t i = 0; i < na; i++) slot[i] = (uint32_t)active[i];
-            VDB_HIP(hipMemcpyAsync(aux, active.data(), na * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-            VDB_HIP(hipMemcpyAsync(aux + off_slot, slot.data(), na * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            launch_gather_rows_f32(d_q, reinterpret_cast<const uint64_t *>(aux), na, (uint32_t)dim, ws.grp_q.as<float>(), s);
-            d_slot = reinterpret_cast<const uint32_t *>(aux + off_slot);
-            Q = ws.grp_q.as<float>();
-            if (n_masks) {
-                mo.resize(na);
-                for (uint64_t i = 0; i < na; i++) mo[i] = mask_of[active[i]];
-                mof = mo.data();
-            }
-        }
-        if (n_masks) filtered_multi_calls++;
-        for (uint64_t c0 = 0; c0 < na; c0 += sub) {
-            const uint64_t nb = std::min(sub, na - c0);
-            uint64_t *l_ids = ws.grp_ids.as<uint64_t>(), *l_cnt = ws.grp_cnt.as<uint64_t>();
-            float *l_dist = ws.grp_dist.as<float>();
-            if (n_masks)
-                flat_knn_masked_multi_device(ws, Q + c0 * dim, nb, kp, masks, n_masks, mof + c0, l_ids, l_dist, l_cnt);
-            else
-                flat_knn_device(ws, Q + c0 * dim, nb, kp, l_ids, l_dist, l_cnt);
-            prof_begin(ws, "group_cap", double(nb) * kp * (GROUPED_PAIR_BYTES + sizeof(uint32_t)));
-            if (first)
-                launch_group_cap(l_ids, l_dist, l_cnt, nb, kp, col, n, id_offset, (uint32_t)k, g32, ws.grp_table.as<uint32_t>(), nullptr, d_idx + c0 * k,
-                                 d_dist + c0 * k, d_cnt + c0, d_done + c0, s);
-            else
-                launch_group_cap(l_ids, l_dist, l_cnt, nb, kp, col, n, id_offset, (uint32_t)k, g32, ws.grp_table.as<uint32_t>(), d_slot + c0, d_idx, d_dist,
-                                 d_cnt, d_done + c0, s);
-            prof_end(ws);
-        }
-        uint8_t *h_done = static_cast<uint8_t *>(ws.pinned(na));  // (the list calls have synchronised: their use of the block is over)
-        VDB_HIP(hipMemcpyAsync(h_done, d_done, na, hipMemcpyDeviceToHost, s));
-        VDB_SYNC(s);  // (ends the round: the host arrays uploaded above are free again)
-        prof_collect(ws);
-        rounds++;
-        const uint64_t open_m = grouped_compact(active, h_done, m_of.data(), kp, next, exhausted);
-        active.swap(next);
-        if (!active.empty()) kp = grouped_next_k(kp, open_m);
-    }
-    grouped_rounds += rounds;
-    grouped_exhausted += exhausted;
-}
-
-void Index::group_cap_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
-                             uint32_t column, uint64_t g, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
-    hipStream_t s = ws.stream;
-    VDB_REQUIRE(column < LABEL_COLUMNS && g >= 1, "grouped k-NN: bad column or group size");
-    if (nq == 0) return;
-    VDB_REQUIRE(nq < (1ull << 32) && k < (1ull << 31), "flat knn: too many queries or k too large");
-    VDB_REQUIRE(std::min(k, ld) <= (1ull << 30) - GROUPED_TILE, "grouped k-NN: k too large");
-    const size_t table1 = group_cap_scratch_bytes(1, k, ld);
-    const uint64_t sub = table1 ? std::max<uint64_t>(1, std::min<uint64_t>(nq, GROUPED_LIST_BUDGET / table1)) : nq;
-    ws.grp_aux.reserve(sizeof(uint32_t) + nq);
-    if (table1) ws.grp_table.reserve(sub * table1);
-    uint32_t *d_flag = ws.grp_aux.as<uint32_t>();
-    uint8_t *d_done = ws.grp_aux.as<uint8_t>() + sizeof(uint32_t);
-    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
-    launch_group_check(d_ids, d_counts, nq, ld, n, id_offset, d_flag, s);
-    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
-    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    VDB_SYNC(s);
-    VDB_REQUIRE(*h_flag == 0, "group cap: a list holds an id that is no row of this index (id - id_offset must be below len)");
-    const uint32_t *col = label_live[column] ? d_labels[column].as<uint32_t>() : nullptr;
-    const uint32_t g32 = (uint32_t)std::min<uint64_t>(g, 0xFFFFFFFFull);
-    for (uint64_t c0 = 0; c0 < nq; c0 += sub) {
-        const uint64_t nb = std::min(sub, nq - c0);
-        prof_begin(ws, "group_cap", double(nb) * ld * (GROUPED_PAIR_BYTES + sizeof(uint32_t)));
-        launch_group_cap(d_ids + c0 * ld, d_dists + c0 * ld, d_counts + c0, nb, ld, col, n, id_offset, (uint32_t)k, g32, ws.grp_table.as<uint32_t>(), nullptr,
-                         d_idx + c0 * k, d_dist + c0 * k, d_cnt + c0, d_done + c0, s);
-        prof_end(ws);
-    }
-    VDB_SYNC(s);
-    prof_collect(ws);
-}
-
-// ---- Flat: diversified k-NN, maximal marginal relevance over the fetch_k nearest allowed rows (k_mmr.hip, mmr_plan.hpp; 4.1u) ------------
-// The candidates of a query are a PREFIX of its order of fixed length, so one round is the whole call: the exact sorted list of
-// kp = min(fetch_k, longest allowed set) rows per query (a query with fewer allowed rows gets a shorter count), then the selection.  The
-// queries are cut into sub-chunks whose lists stay under MMR_LIST_BUDGET; the lists live in the grouped call's buffers.
-void Index::flat_knn_mmr_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t fetch_k, float lambda, const RowMask *const *masks,
-                                uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
-    hipStream_t s = ws.stream;
-    require_f32_rows(*this);
-    VDB_REQUIRE(mmr_check_args(k, fetch_k, lambda) == nullptr, "mmr: bad k, fetch_k or lambda");
-    if (nq == 0) return;
-    VDB_REQUIRE(nq < (1ull << 31), "flat knn: too many queries");
-    mmr_queries += nq;
-    if (k == 0) {
-        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
-        VDB_SYNC(s);
-        return;
-    }
-    uint64_t max_m = n_masks ? 0 : n;
-    for (uint64_t q = 0; n_masks && q < nq; q++) max_m = std::max<uint64_t>(max_m, masks[mask_of[q]]->m);
-    const uint64_t kp = mmr_list_len(fetch_k, max_m);
-    const uint64_t sub = mmr_sub_chunk(nq, kp);
-    // every buffer of the call before its first launch
-    ws.grp_ids.reserve(sub * kp * sizeof(uint64_t));
-    ws.grp_dist.reserve(sub * kp * sizeof(float));
-    ws.grp_cnt.reserve(sub * sizeof(uint64_t));
-    uint64_t *l_ids = ws.grp_ids.as<uint64_t>(), *l_cnt = ws.grp_cnt.as<uint64_t>();
-    float *l_dist = ws.grp_dist.as<float>();
-    if (n_masks) filtered_multi_calls++;
-    for (uint64_t c0 = 0; c0 < nq; c0 += sub) {
-        const uint64_t nb = std::min(sub, nq - c0);
-        if (n_masks)
-            flat_knn_masked_multi_device(ws, d_q + c0 * dim, nb, kp, masks, n_masks, mask_of + c0, l_ids, l_dist, l_cnt);
-        else
-            flat_knn_device(ws, d_q + c0 * dim, nb, kp, l_ids, l_dist, l_cnt);
-        prof_begin(ws, "mmr_select", double(nb) * kp * (MMR_PAIR_BYTES + dim * sizeof(float)));
-        launch_mmr_select(l_ids, l_dist, l_cnt, nb, kp, d_rows.as<float>(), d_sq.as<float>(), n, (uint32_t)dim, dist != 0, id_offset, (uint32_t)k, lambda,
-                          nullptr, d_idx + c0 * k, d_dist + c0 * k, d_cnt + c0, s);
-        prof_end(ws);
-    }
-    VDB_SYNC(s);
-    prof_collect(ws);
-}
-
-void Index::mmr_select_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
-                              float lambda, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
-    hipStream_t s = ws.stream;
-    require_f32_rows(*this);
-    VDB_REQUIRE(mmr_check_args(k, ld, lambda) == nullptr, "mmr: bad k, ld or lambda");
-    if (nq == 0) return;
-    VDB_REQUIRE(nq < (1ull << 31), "flat knn: too many queries");
-    if (k == 0) {  // (ld == 0 implies it)
-        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
-        VDB_SYNC(s);
-        return;
-    }
-    ws.grp_aux.reserve(sizeof(uint32_t));
-    uint32_t *d_flag = ws.grp_aux.as<uint32_t>();
-    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
-    launch_mmr_check(d_ids, d_counts, nq, ld, n, id_offset, d_flag, s);
-    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
-    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    VDB_SYNC(s);
-    VDB_REQUIRE(*h_flag == 0, "mmr select: a list holds an id that is no row of this index (id - id_offset must be below len)");
-    prof_begin(ws, "mmr_select", double(nq) * ld * (MMR_PAIR_BYTES + dim * sizeof(float)));
-    launch_mmr_select(d_ids, d_dists, d_counts, nq, ld, d_rows.as<float>(), d_sq.as<float>(), n, (uint32_t)dim, dist != 0, id_offset, (uint32_t)k, lambda,
-                      nullptr, d_idx, d_dist, d_cnt, s);
-    prof_end(ws);
-    VDB_SYNC(s);
-    prof_collect(ws);
-}
-
-// ---- Flat: search by example rows (k_like.hip, like_plan.hpp; 4.1v) ----------------------------------------------------------------------
-// The answer of a query is a prefix of its order with the examples taken out, and a list of k + e_max rows always holds it: one round is
-// the whole call.  The query vectors of a sub-chunk live in grp_q, its lists in the grouped call's buffers; the caller keeps the example
-// lists in grp_table and the flag of the id check is in grp_aux -- none of which the list calls touch.
-void Index::like_queries_device(Workspace &ws, const LikeLists &ll, uint64_t q0, uint64_t nq, float *d_out) {
-    require_f32_rows(*this);
-    if (nq == 0) return;
-    prof_begin(ws, "like_build", double(nq) * dim * sizeof(float));
-    launch_like_build(ll.pos_ids, ll.pos_lims + q0, ll.neg_ids, ll.neg_lims ? ll.neg_lims + q0 : nullptr, ll.global_ids, nq, d_rows.as<float>(), n,
-                      (uint32_t)dim, id_offset, d_out, ws.stream);
-    prof_end(ws);
-}
-
-void Index::flat_knn_like_device(Workspace &ws, const LikeLists &ll, uint64_t q0, uint64_t nq, uint64_t k, bool exclude, const RowMask *const *masks,
-                                 uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
-    hipStream_t s = ws.stream;
-    require_f32_rows(*this);
-    if (nq == 0) return;
-    VDB_REQUIRE(nq < (1ull << 31) && k < (1ull << 31), "flat knn: too many queries or k too large");
-    like_queries += nq;
-    if (k == 0) {
-        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
-        VDB_SYNC(s);
-        return;
-    }
-    uint64_t max_m = n_masks ? 0 : n;
-    for (uint64_t q = 0; n_masks && q < nq; q++) max_m = std::max<uint64_t>(max_m, masks[mask_of[q]]->m);
-    const uint64_t kp = like_list_len(k, ll.e_max, exclude, max_m);
-    const uint64_t sub = like_sub_chunk(nq, kp);
-    // every buffer of the call before its first launch
-    ws.grp_q.reserve(sub * dim * sizeof(float));
-    ws.grp_ids.reserve(sub * kp * sizeof(uint64_t));
-    ws.grp_dist.reserve(sub * kp * sizeof(float));
-    ws.grp_cnt.reserve(sub * sizeof(uint64_t));
-    float *l_q = ws.grp_q.as<float>(), *l_dist = ws.grp_dist.as<float>();
-    uint64_t *l_ids = ws.grp_ids.as<uint64_t>(), *l_cnt = ws.grp_cnt.as<uint64_t>();
-    if (n_masks) filtered_multi_calls++;
-    for (uint64_t c0 = 0; c0 < nq; c0 += sub) {
-        const uint64_t nb = std::min(sub, nq - c0);
-        like_queries_device(ws, ll, q0 + c0, nb, l_q);
-        if (n_masks)
-            flat_knn_masked_multi_device(ws, l_q, nb, kp, masks, n_masks, mask_of + c0, l_ids, l_dist, l_cnt);
-        else
-            flat_knn_device(ws, l_q, nb, kp, l_ids, l_dist, l_cnt);
-        const uint64_t *pl = exclude ? ll.pos_lims + q0 + c0 : nullptr;
-        const uint64_t *nl = exclude && ll.neg_lims ? ll.neg_lims + q0 + c0 : nullptr;
-        prof_begin(ws, "like_drop", double(nb) * kp * LIKE_PAIR_BYTES);
-        launch_like_drop(l_ids, l_dist, l_cnt, nb, kp, ll.pos_ids, pl, ll.neg_ids, nl, ll.global_ids, id_offset, (uint32_t)k, d_idx + c0 * k,
-                         d_dist + c0 * k, d_cnt + c0, s);
-        prof_end(ws);
-    }
-    VDB_SYNC(s);
-    prof_collect(ws);
-}
-
-void Index::like_check_ids_device(Workspace &ws, const uint64_t *d_a, uint64_t ma, const uint64_t *d_b, uint64_t mb) {
-    if (ma + mb == 0) return;
-    hipStream_t s = ws.stream;
-    ws.grp_aux.reserve(sizeof(uint32_t));
-    uint32_t *d_flag = ws.grp_aux.as<uint32_t>();
-    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
-    launch_fetch_check(d_a, ma, n, id_offset, d_flag, num_cu, s);
-    launch_fetch_check(d_b, mb, n, id_offset, d_flag, num_cu, s);
-    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
-    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    VDB_SYNC(s);
-    VDB_REQUIRE(*h_flag == 0, "like: a list holds an id that is no row of this index (id - id_offset must be below len)");
-}
-
-void Index::drop_listed_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
-                               const uint64_t *d_drop_lims, const uint64_t *d_drop_ids, uint64_t n_drop, uint64_t *d_idx, float *d_dist,
-                               uint64_t *d_cnt) {
-    hipStream_t s = ws.stream;
-    if (nq == 0) return;
-    VDB_REQUIRE(nq < (1ull << 31) && k < (1ull << 31), "drop listed: too many queries or k too large");
-    if (k == 0) {
-        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
-        VDB_SYNC(s);
-        return;
-    }
-    ws.grp_aux.reserve(sizeof(uint32_t));
-    uint32_t *d_flag = ws.grp_aux.as<uint32_t>();
-    VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
-    launch_group_check(d_ids, d_counts, nq, ld, n, id_offset, d_flag, s);
-    if (n_drop) launch_fetch_check(d_drop_ids, n_drop, n, id_offset, d_flag, num_cu, s);
-    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
-    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    VDB_SYNC(s);
-    VDB_REQUIRE(*h_flag == 0, "drop listed: a list holds an id that is no row of this index (id - id_offset must be below len)");
-    prof_begin(ws, "like_drop", double(nq) * ld * LIKE_PAIR_BYTES);
-    launch_like_drop(d_ids, d_dists, d_counts, nq, ld, d_drop_ids, d_drop_lims, nullptr, nullptr, true, id_offset, (uint32_t)k, d_idx, d_dist, d_cnt, s);
-    prof_end(ws);
-    VDB_SYNC(s);
-    prof_collect(ws);
-}
-
-// ---- Flat: fused multi-query search, several lists per question joined on the device (k_fuse.hip, fuse_plan.hpp; 4.1w) --------------------
-// The candidates of a sub-query are a PREFIX of its order of fixed length, so one round is the whole call: the exact sorted lists of
-// kp = min(fetch_k, longest allowed set) rows of every sub-query of a sub-chunk from ONE list call, then ONE fusion launch.  The lists live in
-// the grouped call's buffers, the kernel's scratch in grp_table, [flag | limits | weights] in grp_aux -- which the list calls do not touch.
-struct FuseUpload {
-    const uint64_t *lims;
-    const float *weights;
-};
-// [u64 flag word | lims rebased to 0 | weights] into ws.grp_aux with one copy out of `blob`, which the caller keeps until the stream has been
-// waited for
-static FuseUpload fuse_upload(Workspace &ws, std::vector<char> &blob, const uint64_t *lims, uint64_t nq, const float *weights) {
-    const uint64_t nl = lims[nq] - lims[0];
-    const size_t off_l = sizeof(uint64_t), off_w = off_l + (nq + 1) * sizeof(uint64_t);
-    blob.assign(off_w + (weights ? nl * sizeof(float) : 0), 0);
-    uint64_t *hl = reinterpret_cast<uint64_t *>(blob.data() + off_l);
-    for (uint64_t q = 0; q <= nq; q++) hl[q] = lims[q] - lims[0];
-    if (weights) std::memcpy(blob.data() + off_w, weights, nl * sizeof(float));
-    ws.grp_aux.reserve(blob.size());
-    VDB_HIP(hipMemcpyAsync(ws.grp_aux.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ws.stream));
-    char *d = ws.grp_aux.as<char>();
-    return {reinterpret_cast<const uint64_t *>(d + off_l), weights ? reinterpret_cast<const float *>(d + off_w) : nullptr};
-}
-
-void Index::flat_knn_fused_device(Workspace &ws, const float *d_q, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, int mode,
-                                  const float *weights, float rrf_c, const RowMask *const *masks, uint64_t n_masks, const uint32_t *mask_of,
-                                  uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
-    hipStream_t s = ws.stream;
-    require_f32_rows(*this);
-    if (nq == 0) return;
-    const uint64_t base = lims[0], nl = lims[nq] - base;
-    fused_queries += nq;
-    fused_lists += nl;
-    if (k == 0) {
-        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
-        VDB_SYNC(s);
-        return;
-    }
-    uint64_t max_m = n_masks ? 0 : n;
-    for (uint64_t j = 0; n_masks && j < nl; j++) max_m = std::max<uint64_t>(max_m, masks[mask_of[j]]->m);
-    const uint64_t s_max = fuse_s_max(lims, nq);
-    const uint64_t kp = fuse_list_len(fetch_k, max_m);
-    const uint32_t lg = fuse_table_lg(s_max, kp);
-    const uint64_t sub = fuse_sub_chunk(nq, s_max, kp);
-    // every buffer of the call before its first launch
-    const uint64_t sub_lists = std::min(nl, sub * s_max);
-    ws.grp_ids.reserve(sub_lists * kp * sizeof(uint64_t));
-    ws.grp_dist.reserve(sub_lists * kp * sizeof(float));
-    ws.grp_cnt.reserve(sub_lists * sizeof(uint64_t));
-    if (const size_t tb = fuse_scratch_bytes(sub, lg)) ws.grp_table.reserve(tb);
-    std::vector<char> blob;
-    const FuseUpload up = fuse_upload(ws, blob, lims, nq, weights);
-    uint64_t *l_ids = ws.grp_ids.as<uint64_t>(), *l_cnt = ws.grp_cnt.as<uint64_t>();
-    float *l_dist = ws.grp_dist.as<float>();
-    if (n_masks) filtered_multi_calls++;
-    for (uint64_t c0 = 0; c0 < nq; c0 += sub) {
-        const uint64_t nb = std::min(sub, nq - c0);
-        const uint64_t j0 = lims[c0] - base, nj = lims[c0 + nb] - base - j0;  // the sub-chunk's sub-queries
-        if (n_masks)
-            flat_knn_masked_multi_device(ws, d_q + j0 * dim, nj, kp, masks, n_masks, mask_of + j0, l_ids, l_dist, l_cnt);
-        else
-            flat_knn_device(ws, d_q + j0 * dim, nj, kp, l_ids, l_dist, l_cnt);
-        prof_begin(ws, "fuse_lists", double(nj) * kp * FUSE_PAIR_BYTES);
-        launch_fuse_lists(l_ids, l_dist, l_cnt, nb, kp, up.lims + c0, j0, up.weights, mode, rrf_c, id_offset, (uint32_t)k, lg, ws.grp_table.as<uint32_t>(),
-                          d_idx + c0 * k, d_dist + c0 * k, d_cnt + c0, s);
-        prof_end(ws);
-    }
-    VDB_SYNC(s);  // (`blob` is pageable memory: alive until here)
-    prof_collect(ws);
-}
-
-void Index::fuse_lists_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, const uint64_t *lims, uint64_t nq,
-                              uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt) {
-    hipStream_t s = ws.stream;
-    require_f32_rows(*this);
-    if (nq == 0) return;
-    VDB_REQUIRE(nq < (1ull << 31) && k < (1ull << 31), "fuse lists: too many fused queries or k too large");
-    if (k == 0 || ld == 0) {
-        VDB_HIP(hipMemsetAsync(d_cnt, 0, nq * sizeof(uint64_t), s));
-        if (k) {
-            VDB_HIP(hipMemsetAsync(d_idx, 0, nq * k * sizeof(uint64_t), s));
-            VDB_HIP(hipMemsetAsync(d_dist, 0, nq * k * sizeof(float), s));
-        }
-        VDB_SYNC(s);
-        return;
-    }
-    const uint64_t s_max = fuse_s_max(lims, nq);
-    const uint32_t lg = fuse_table_lg(s_max, ld);
-    const uint64_t sub = fuse_sub_chunk(nq, s_max, ld, false);
-    if (const size_t tb = fuse_scratch_bytes(sub, lg)) ws.grp_table.reserve(tb);
-    std::vector<char> blob;
-    const FuseUpload up = fuse_upload(ws, blob, lims, nq, weights);  // (the flag word in front: zero)
-    uint32_t *d_flag = ws.grp_aux.as<uint32_t>();
-    launch_group_check(d_ids, d_counts, lims[nq], ld, n, id_offset, d_flag, s);
-    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
-    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    VDB_SYNC(s);
-    VDB_REQUIRE(*h_flag == 0, "fuse lists: a list holds an id that is no row of this index (id - id_offset must be below len)");
-    for (uint64_t c0 = 0; c0 < nq; c0 += sub) {
-        const uint64_t nb = std::min(sub, nq - c0);
-        prof_begin(ws, "fuse_lists", double(lims[c0 + nb] - lims[c0]) * ld * FUSE_PAIR_BYTES);
-        launch_fuse_lists(d_ids, d_dists, d_counts, nb, ld, up.lims + c0, 0, up.weights, mode, rrf_c, id_offset, (uint32_t)k, lg,
-                          ws.grp_table.as<uint32_t>(), d_idx + c0 * k, d_dist + c0 * k, d_cnt + c0, s);
-        prof_end(ws);
-    }
-    VDB_SYNC(s);
-    prof_collect(ws);
 }
 
 // ---- Flat: exact filtered range search with one row mask per query (k_filter.hip, multi_plan.hpp) --------------------------------------

@@ -186,6 +186,19 @@ struct Workspace {
     }
 };
 
+// The id check of every call that takes ids from the device: the flag word d_flag zeroed on `s` (zeroed: the caller's upload has done
+// that), enqueue(d_flag) -- launch_fetch_check / launch_list_check, which set it for an id that is no row --, ONE read-back through the
+// workspace's pinned block and a wait for `s`; throws `message` when the flag is set, with nothing else of the call enqueued yet.
+template <class Enqueue>
+void ids_ok(Workspace &ws, hipStream_t s, uint32_t *d_flag, const char *message, Enqueue &&enqueue, bool zeroed = false) {
+    if (!zeroed) VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+    enqueue(d_flag);
+    uint32_t *h_flag = static_cast<uint32_t *>(ws.pinned(sizeof(uint32_t)));
+    VDB_HIP(hipMemcpyAsync(h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDB_SYNC(s);
+    VDB_REQUIRE(*h_flag == 0, message);
+}
+
 struct PQState {
     bool present = false;
     uint64_t n_bits = 0, m = 0, kc = 0, enc_dim = 0;
@@ -661,6 +674,7 @@ struct Index {
                       bool slabs = false);
     // (slabs: the bit words of a chunk's masks are views into ONE allocation, zeroed, and their allow-lists views into another, every
     // view DEVBUF_ALIGN-aligned -- masks_partition's; false: an allocation per mask and list, as every other caller has it.)
+    // The four Flat list re-rankers below -- grouped, diversified, by example, fused -- are in flat_rerank.hip, on one shared driver (4.1x).
     // Grouped Flat k-NN (k_group.hip, grouped_plan.hpp; docs/DESIGN_flat.md 4.1q): per query the first k rows, in FlatIndex::knn's order over
     // the allowed rows, of which at most g carry any one value of label column `column` (rows without a label are always kept).  Rounds:
     // the exact sorted list of K' rows per open query -- flat_knn_device without masks, flat_knn_masked_multi_device over the call's masks,
@@ -679,7 +693,7 @@ struct Index {
     // of min(k, F) rows from the first F = min(fetch_k, m) rows of FlatIndex::knn's order over the allowed rows, in selection order.  ONE
     // round: the exact sorted list of F rows per query -- flat_knn_device without masks, flat_knn_masked_multi_device over the call's
     // masks, whose counters advance as for those calls -- then k_mmr_select, in sub-chunks of queries whose lists stay under
-    // MMR_LIST_BUDGET.  n_masks == 0: unfiltered (masks / mask_of not read).  The caller has checked k, fetch_k, lambda (mmr_check_args),
+    // LIST_BUDGET.  n_masks == 0: unfiltered (masks / mask_of not read).  The caller has checked k, fetch_k, lambda (mmr_check_args),
     // the masks and mask_of; returns synchronised.
     void flat_knn_mmr_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t fetch_k, float lambda, const RowMask *const *masks,
                              uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
@@ -701,7 +715,7 @@ struct Index {
     void like_queries_device(Workspace &ws, const LikeLists &ll, uint64_t q0, uint64_t nq, float *d_out);
     // ONE round: the query vectors, the exact sorted list of K' = like_list_len(..) rows per query -- flat_knn_device without masks,
     // flat_knn_masked_multi_device over the call's masks, whose counters advance as for those calls -- then k_like_drop, in sub-chunks of
-    // queries whose lists stay under LIKE_LIST_BUDGET.  The queries are q0 .. q0 + nq of the lists (mask_of already advanced).  n_masks == 0:
+    // queries whose lists stay under LIST_BUDGET.  The queries are q0 .. q0 + nq of the lists (mask_of already advanced).  n_masks == 0:
     // unfiltered (masks / mask_of not read).  Returns synchronised.
     void flat_knn_like_device(Workspace &ws, const LikeLists &ll, uint64_t q0, uint64_t nq, uint64_t k, bool exclude, const RowMask *const *masks,
                               uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);

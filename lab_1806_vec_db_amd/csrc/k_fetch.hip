@@ -57,6 +57,20 @@ __global__ __launch_bounds__(256) void k_fetch_check(const uint64_t *__restrict_
     if (bad) *flag = 1;  // (every writer stores the same value)
 }
 
+// the same for the counted part ids[b][0 .. min(counts[b], ld)) of every list b of an [..][ld] block (blockIdx.y = b): what the list forms of the
+// Flat re-rankers check before anything is walked (flat_rerank.hip)
+__global__ __launch_bounds__(256) void k_list_check(const uint64_t *__restrict__ ids, const uint64_t *__restrict__ counts, uint64_t ld,
+                                                    uint64_t n, uint64_t id_offset, uint32_t *__restrict__ flag) {
+    const uint64_t b = blockIdx.y;
+    const uint64_t cnt = counts[b] < ld ? counts[b] : ld;
+    bool bad = false;
+    for (uint64_t p = uint64_t(blockIdx.x) * 256 + threadIdx.x; p < cnt; p += uint64_t(gridDim.x) * 256) {
+        const uint64_t id = ids[b * ld + p];
+        bad |= id < id_offset || id - id_offset >= n;
+    }
+    if (bad) *flag = 1;  // (every writer stores the same value)
+}
+
 static unsigned fetch_grid(uint64_t m, int num_cu) { return (unsigned)std::min<uint64_t>((m + 3) / 4, uint64_t(std::max(num_cu, 1)) * 8); }
 
 template <class Id>
@@ -101,6 +115,16 @@ void launch_fetch_check(const uint64_t *ids, uint64_t m, uint64_t n, uint64_t id
     if (m == 0) return;
     const unsigned grid = (unsigned)std::min<uint64_t>((m + 255) / 256, uint64_t(std::max(num_cu, 1)) * 8);
     hipLaunchKernelGGL(k_fetch_check, dim3(grid), dim3(256), 0, s, ids, m, n, id_offset, flag);
+}
+
+void launch_list_check(const uint64_t *ids, const uint64_t *counts, uint64_t nq, uint64_t ld, uint64_t n, uint64_t id_offset, uint32_t *flag,
+                       hipStream_t s) {
+    if (nq == 0 || ld == 0) return;
+    const unsigned gx = (unsigned)std::min<uint64_t>((ld + 255) / 256, 64);
+    for (uint64_t q0 = 0; q0 < nq; q0 += 32768) {  // (grid.y)
+        const uint64_t nb = std::min<uint64_t>(32768, nq - q0);
+        hipLaunchKernelGGL(k_list_check, dim3(gx, (unsigned)nb), dim3(256), 0, s, ids + q0 * ld, counts + q0, ld, n, id_offset, flag);
+    }
 }
 
 }  // namespace vdb

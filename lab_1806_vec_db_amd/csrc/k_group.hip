@@ -18,8 +18,6 @@
 // later round is walked again from its start (no table or position is carried between launches).  Outputs of query b go to row
 // slot_q[b] (nullptr: b) of [..][k] arrays: the kept pairs, zeros behind them, the count, and done[b] = k rows were kept | the list held
 // fewer than ld entries (it was everything its maker had).
-//
-// k_group_check: flag |= an id of the counted part of a list that is no row of the index, before anything is walked.
 #include "kernels.hpp"
 
 namespace vdb {
@@ -129,28 +127,6 @@ __global__ __launch_bounds__(64) void k_group_cap(const uint64_t *__restrict__ i
     if (lane == 0) {
         out_cnt[o] = kept;
         done[b] = (kept == k || cnt < ld) ? 1 : 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_group_check(const uint64_t *__restrict__ ids, const uint64_t *__restrict__ counts, uint64_t ld,
-                                                     uint64_t n, uint64_t id_offset, uint32_t *__restrict__ flag) {
-    const uint64_t b = blockIdx.y;
-    const uint64_t cnt = counts[b] < ld ? counts[b] : ld;
-    bool bad = false;
-    for (uint64_t p = uint64_t(blockIdx.x) * 256 + threadIdx.x; p < cnt; p += uint64_t(gridDim.x) * 256) {
-        const uint64_t id = ids[b * ld + p];
-        bad |= id < id_offset || id - id_offset >= n;
-    }
-    if (bad) *flag = 1;  // (every writer stores the same value)
-}
-
-void launch_group_check(const uint64_t *ids, const uint64_t *counts, uint64_t nq, uint64_t ld, uint64_t n, uint64_t id_offset, uint32_t *flag,
-                        hipStream_t s) {
-    if (nq == 0 || ld == 0) return;
-    const unsigned gx = (unsigned)std::min<uint64_t>((ld + 255) / 256, 64);
-    for (uint64_t q0 = 0; q0 < nq; q0 += 32768) {  // (grid.y)
-        const uint64_t nb = std::min<uint64_t>(32768, nq - q0);
-        hipLaunchKernelGGL(k_group_check, dim3(gx, (unsigned)nb), dim3(256), 0, s, ids + q0 * ld, counts + q0, ld, n, id_offset, flag);
     }
 }
 

@@ -21,8 +21,6 @@
 // bytes live in LDS; the argmin under (score, position) is a shuffle reduction per wave and one LDS exchange between waves.  An id that
 // is no row of the index is never gathered: its distances read as NaN (mmr_select_device refuses such a list before the launch).
 // Outputs of query b go to row slot_q[b] (nullptr: b) of [..][k] arrays: the selected pairs, zeros behind them, and the count.
-//
-// k_mmr_check: flag |= an id of the counted part of a list that is no row of the index, before anything is selected (as k_group_check).
 #include <algorithm>
 #include <cmath>
 
@@ -203,28 +201,6 @@ __global__ __launch_bounds__(MMR_THREADS) void k_mmr_select(const uint64_t *__re
             o_dist[t] = s_d[last];
         }
         __syncthreads();  // the selected byte is out, and the per-wave pairs are read before the next step writes them
-    }
-}
-
-__global__ __launch_bounds__(256) void k_mmr_check(const uint64_t *__restrict__ ids, const uint64_t *__restrict__ counts, uint64_t ld, uint64_t n,
-                                                   uint64_t id_offset, uint32_t *__restrict__ flag) {
-    const uint64_t b = blockIdx.y;
-    const uint64_t cnt = counts[b] < ld ? counts[b] : ld;
-    bool bad = false;
-    for (uint64_t p = uint64_t(blockIdx.x) * 256 + threadIdx.x; p < cnt; p += uint64_t(gridDim.x) * 256) {
-        const uint64_t id = ids[b * ld + p];
-        bad |= id < id_offset || id - id_offset >= n;
-    }
-    if (bad) *flag = 1;  // (every writer stores the same value)
-}
-
-void launch_mmr_check(const uint64_t *ids, const uint64_t *counts, uint64_t nq, uint64_t ld, uint64_t n, uint64_t id_offset, uint32_t *flag,
-                      hipStream_t s) {
-    if (nq == 0 || ld == 0) return;
-    const unsigned gx = (unsigned)((ld + 255) / 256);  // (ld <= MMR_MAX_FETCH: at most 16)
-    for (uint64_t q0 = 0; q0 < nq; q0 += 32768) {      // (grid.y)
-        const uint64_t nb = std::min<uint64_t>(32768, nq - q0);
-        hipLaunchKernelGGL(k_mmr_check, dim3(gx, (unsigned)nb), dim3(256), 0, s, ids + q0 * ld, counts + q0, ld, n, id_offset, flag);
     }
 }
 

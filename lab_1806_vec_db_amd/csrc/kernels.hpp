@@ -282,6 +282,9 @@ void launch_rows_gather_widen(const uint8_t *rows, uint64_t dim, const void *ids
                               int num_cu, hipStream_t s);
 // *flag = 1 when some ids[j] - id_offset is not in [0, n) (flag zeroed by the caller)
 void launch_fetch_check(const uint64_t *ids, uint64_t m, uint64_t n, uint64_t id_offset, uint32_t *flag, int num_cu, hipStream_t s);
+// the same for an id of the counted part ids[b][0 .. min(counts[b], ld)) of a list b < nq of an [nq][ld] block
+void launch_list_check(const uint64_t *ids, const uint64_t *counts, uint64_t nq, uint64_t ld, uint64_t n, uint64_t id_offset, uint32_t *flag,
+                       hipStream_t s);
 void launch_query_prep_i8(const float *Q, uint32_t nq, uint32_t nq_pad, uint32_t dim, const float *mu, float l1, float l2, float *qsq,
                           float *qscale, float *qoff, uint32_t *hits, void *qfrag, hipStream_t s, int cosine = 0);
 // k_redo.hip: second attempts of a Flat call
@@ -436,9 +439,6 @@ size_t group_cap_scratch_bytes(uint64_t nq, uint64_t k, uint64_t ld);
 void launch_group_cap(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nq, uint64_t ld, const uint32_t *labels, uint64_t n,
                       uint64_t id_offset, uint32_t k, uint32_t g, uint32_t *scratch, const uint32_t *slot_q, uint64_t *out_idx, float *out_dist,
                       uint64_t *out_cnt, uint8_t *done, hipStream_t s);
-// *flag = 1 when an id of the counted part of a list is no row of the index (id - id_offset not in [0, n)); the caller has zeroed it
-void launch_group_check(const uint64_t *ids, const uint64_t *counts, uint64_t nq, uint64_t ld, uint64_t n, uint64_t id_offset, uint32_t *flag,
-                        hipStream_t s);
 // The greedy selection of the diversified k-NN (k_mmr.hip, mmr_plan.hpp): from query b's list ids / dists [b][0 .. F), F = min(counts[b], ld),
 // 1 <= ld <= MMR_MAX_FETCH, position 0 and then min(k, F) - 1 times the unselected position with the smallest
 // (lambda * d_p) - ((1 - lambda) * min over the selected s of D(p, s)), ties to the lowest position; D = the exact distance between the ROWS
@@ -448,9 +448,6 @@ void launch_group_check(const uint64_t *ids, const uint64_t *counts, uint64_t nq
 void launch_mmr_select(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nq, uint64_t ld, const float *X, const float *xsq,
                        uint64_t n, uint32_t dim, bool cosine, uint64_t id_offset, uint32_t k, float lambda, const uint32_t *slot_q, uint64_t *out_idx,
                        float *out_dist, uint64_t *out_cnt, hipStream_t s);
-// *flag = 1 when an id of the counted part of a list is no row of the index (id - id_offset not in [0, n)); the caller has zeroed it
-void launch_mmr_check(const uint64_t *ids, const uint64_t *counts, uint64_t nq, uint64_t ld, uint64_t n, uint64_t id_offset, uint32_t *flag,
-                      hipStream_t s);
 // The search by example rows (k_like.hip, like_plan.hpp).  launch_like_build: out[q][j] for q < nq, j < dim = the "average vector" of query
 // q's example rows of X [n][dim] -- ap = (strict left fold of the positives pos_ids[pos_lims[q] .. pos_lims[q + 1]) in list order) /
 // their number; with negatives (neg_lims != nullptr and the query's range not empty) an likewise and (ap + ap) - an, otherwise ap.  The

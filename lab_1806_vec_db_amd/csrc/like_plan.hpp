@@ -11,12 +11,11 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "list_plan.hpp"
+
 namespace vdb {
 
 constexpr uint64_t LIKE_MAX_EXAMPLES = 1024;  // examples of one query, positives plus negatives, as listed (repeats count)
-// the candidate lists of one sub-chunk -- sub x K' x (8 B id + 4 B distance) -- stay at or under this many bytes (as the MMR call's)
-constexpr uint64_t LIKE_LIST_BUDGET = 256ull << 20;
-constexpr uint64_t LIKE_PAIR_BYTES = 12;
 
 // nullptr when lims[0 .. nq] is a list of limits: lims[0] == 0 and no descent.  (nq == 0: lims[0] is still read.)
 inline const char *like_check_one_lims(const uint64_t *lims, uint64_t nq) {
@@ -62,16 +61,10 @@ inline uint64_t like_e_max(const uint64_t *pos_lims, const uint64_t *neg_lims, u
 // list length K' of the call's one round: k + e_max when the examples are dropped (k otherwise), clamped to the longest allowed set among
 // its queries, at least 1 (max_m == 0 or k == 0: one slot is still asked for so that every buffer has a size)
 inline uint64_t like_list_len(uint64_t k, uint64_t e_max, bool exclude, uint64_t max_m) {
-    const uint64_t want = exclude ? (k > ~uint64_t(0) - e_max ? ~uint64_t(0) : k + e_max) : k;
-    return std::max<uint64_t>(1, std::min(want, max_m));
+    return list_len(exclude ? (k > ~uint64_t(0) - e_max ? ~uint64_t(0) : k + e_max) : k, max_m);
 }
 
-// queries per sub-chunk of a call with lists of kp rows: as many as the budget holds, at least 1, at most nq (0 for nq == 0)
-inline uint64_t like_sub_chunk(uint64_t nq, uint64_t kp, uint64_t budget = LIKE_LIST_BUDGET) {
-    if (nq == 0) return 0;
-    const uint64_t kk = std::max<uint64_t>(kp, 1);
-    const uint64_t fit = kk > budget / LIKE_PAIR_BYTES ? 0 : budget / (kk * LIKE_PAIR_BYTES);
-    return std::max<uint64_t>(1, std::min(nq, fit));
-}
+// queries per sub-chunk of a call with lists of kp rows (list_plan.hpp); 0 for nq == 0
+inline uint64_t like_sub_chunk(uint64_t nq, uint64_t kp, uint64_t budget = LIST_BUDGET) { return nq ? list_sub_chunk(nq, kp, budget) : 0; }
 
 }  // namespace vdb

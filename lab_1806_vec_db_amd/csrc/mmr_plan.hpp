@@ -10,12 +10,11 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "list_plan.hpp"
+
 namespace vdb {
 
 constexpr uint64_t MMR_MAX_FETCH = 4096;          // longest candidate list: fetch_k of the search form, ld of the list form
-// the candidate lists of one sub-chunk -- sub x K' x (8 B id + 4 B distance) -- stay at or under this many bytes (as the grouped call's)
-constexpr uint64_t MMR_LIST_BUDGET = 256ull << 20;
-constexpr uint64_t MMR_PAIR_BYTES = 12;
 constexpr uint32_t MMR_STAGE_FLOATS = 2048;       // floats of the row selected last that LDS holds at a time: a longer row goes through in pieces
 constexpr uint32_t MMR_SMALL_THREADS = 64;        // a list of up to 64 positions: one wave
 constexpr uint32_t MMR_THREADS = 256;             // every longer list: four waves
@@ -43,13 +42,8 @@ inline size_t mmr_lds_bytes(uint64_t ld, uint64_t dim) {
     const size_t fp = mmr_positions(ld);
     return fp * 3 * sizeof(float) + size_t(mmr_stage_floats(dim)) * sizeof(float) + MMR_MAX_WAVES * 2 * sizeof(uint32_t) + fp;
 }
-// queries per sub-chunk of a call with lists of kp rows: as many as the budget holds, at least 1, at most nq
-inline uint64_t mmr_sub_chunk(uint64_t nq, uint64_t kp, uint64_t budget = MMR_LIST_BUDGET) {
-    const uint64_t per = std::max<uint64_t>(kp, 1) * MMR_PAIR_BYTES;  // (kp <= MMR_MAX_FETCH: no overflow)
-    return std::max<uint64_t>(1, std::min(nq, budget / per));
-}
-// list length of the call's one round: fetch_k clamped to the longest allowed set among its queries, at least 1 (max_m == 0: nothing is
-// allowed -- one slot is still asked for so that every buffer has a size)
-inline uint64_t mmr_list_len(uint64_t fetch_k, uint64_t max_m) { return std::max<uint64_t>(1, std::min(fetch_k, max_m)); }
+// queries per sub-chunk of a call with lists of kp rows, and the list length of the call's one round: fetch_k clamped (list_plan.hpp)
+inline uint64_t mmr_sub_chunk(uint64_t nq, uint64_t kp, uint64_t budget = LIST_BUDGET) { return list_sub_chunk(nq, kp, budget); }
+inline uint64_t mmr_list_len(uint64_t fetch_k, uint64_t max_m) { return list_len(fetch_k, max_m); }
 
 }  // namespace vdb

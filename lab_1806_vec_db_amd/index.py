@@ -389,6 +389,18 @@ class GpuIndex:
         L.check(self._lib.vdb_index_set_id_offset(self._h, int(off)))
 
     # -- searches ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _knn_outputs(nq, k):
+        """the host outputs of nq queries, zeroed -- (idx, dist) [nq][max(k, 1)] and cnt [nq] -- and the three pointers an entry point takes"""
+        kk = max(int(k), 1)
+        out = np.zeros((nq, kk), dtype=np.uint64), np.zeros((nq, kk), dtype=np.float32), np.zeros(nq, dtype=np.uint64)
+        return out, (_ptr(out[0], L.u64p), _ptr(out[1], L.f32p), _ptr(out[2], L.u64p))
+
+    @staticmethod
+    def _knn_cut(out, k):
+        """-> (idx [nq][k], dist [nq][k], count [nq]) of _knn_outputs' arrays"""
+        return out[0][:, :int(k)], out[1][:, :int(k)], out[2]
+
     def _knn_call(self, fn, queries, k, *mid):
         """every host k-NN call: fn(handle, queries, nq, dim, k, *mid, idx, dist, cnt) -- `mid`: what the entry point takes between k and the
         outputs (ef; a mask handle; the mask array, its length and mask_of; ...).  One query (1-D): (idx, dist) cut at its count."""
@@ -396,15 +408,12 @@ class GpuIndex:
         single = q.ndim == 1
         q = q.reshape(1, -1) if single else q
         nq, dim = q.shape
-        kk = max(int(k), 1)
-        idx = np.zeros((nq, kk), dtype=np.uint64)
-        dist = np.zeros((nq, kk), dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint64)
-        L.check(fn(self._h, _ptr(q, L.f32p), nq, dim, int(k), *mid, _ptr(idx, L.u64p), _ptr(dist, L.f32p), _ptr(cnt, L.u64p)))
+        out, ptrs = self._knn_outputs(nq, k)
+        L.check(fn(self._h, _ptr(q, L.f32p), nq, dim, int(k), *mid, *ptrs))
         if single:
-            c = int(cnt[0])
-            return idx[0, :c].copy(), dist[0, :c].copy()
-        return idx[:, :int(k)], dist[:, :int(k)], cnt
+            c = int(out[2][0])
+            return out[0][0, :c].copy(), out[1][0, :c].copy()
+        return self._knn_cut(out, k)
 
     _search = _knn_call  # (its name before it took more than ef: what the tests of the sharded context compare against)
 
@@ -713,13 +722,10 @@ class GpuIndex:
             raise ValueError(f"{q.shape[0]} query vectors for {int(lm[-1])} sub-queries")
         nq = lm.size - 1
         arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, q.shape[0])
-        kk = max(int(k), 1)
-        idx = np.zeros((nq, kk), dtype=np.uint64)
-        dist = np.zeros((nq, kk), dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint64)
+        out, ptrs = self._knn_outputs(nq, k)
         L.check(self._lib.vdb_flat_knn_fused(self._h, _ptr(q, L.f32p), _ptr(lm, L.u64p), nq, q.shape[1], int(k), int(fetch_k), code, _ptr(w, L.f32p),
-                                             float(rrf_c), arr, n_masks, mo_p, _ptr(idx, L.u64p), _ptr(dist, L.f32p), _ptr(cnt, L.u64p)))
-        return idx[:, :int(k)], dist[:, :int(k)], cnt
+                                             float(rrf_c), arr, n_masks, mo_p, *ptrs))
+        return self._knn_cut(out, k)
 
     def flat_knn_fused_device(self, q_ptr: int, lims, k: int, fetch_k: int, out_idx_ptr: int, out_dist_ptr: int, out_cnt_ptr: int, mode="rrf",
                               weights=None, rrf_c: float = 60.0, masks=None, mask_of=None, stream: int = 0):
@@ -784,13 +790,10 @@ class GpuIndex:
         nq = len(pl) - 1
         nl, nr = self._like_lists(negatives, nq)
         arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, nq)
-        kk = max(int(k), 1)
-        idx = np.zeros((nq, kk), dtype=np.uint64)
-        dist = np.zeros((nq, kk), dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint64)
+        out, ptrs = self._knn_outputs(nq, k)
         L.check(self._lib.vdb_flat_knn_like(self._h, _ptr(pl, L.u64p), _ptr(pr, L.u64p), _ptr(nl, L.u64p), _ptr(nr, L.u64p), nq, int(k),
-                                            int(bool(exclude)), arr, n_masks, mo_p, _ptr(idx, L.u64p), _ptr(dist, L.f32p), _ptr(cnt, L.u64p)))
-        return idx[:, :int(k)], dist[:, :int(k)], cnt
+                                            int(bool(exclude)), arr, n_masks, mo_p, *ptrs))
+        return self._knn_cut(out, k)
 
     def flat_knn_like_device(self, pos_lims, pos_ids_ptr: int, neg_lims, neg_ids_ptr: int, nq: int, k: int, out_idx_ptr: int,
                              out_dist_ptr: int, out_cnt_ptr: int, exclude: bool = True, masks=None, mask_of=None, stream: int = 0):

@@ -237,3 +237,37 @@ def test_out_of_range_id_is_refused(env):
         assert (_run.last[0] == np.uint64(-7 & 0xFFFFFFFFFFFFFFFF)).all()
     assert before == {s: ix.get_stat(s) for s in before}
     _check(env, [np.arange(10)], 10, 5, COL, 1)  # the index still answers
+
+
+def test_bad_id_text_and_the_call_after_it():
+    """64 rows x dim 8, lists [2][4] with an id equal to len + id_offset, an id below id_offset, and both: the call raises with the exact
+    text, the outputs keep their sentinel, and the valid call that follows on the same index is answered -- the flag word of the id check
+    is zeroed by every call"""
+    import re
+
+    import lab_1806_vec_db_amd as vdb
+
+    rng = np.random.default_rng(6)
+    ix = vdb.GpuIndex(8, "l2sqr", device=0)
+    try:
+        ix.batch_add(rng.random((64, 8), dtype=np.float32))
+        col = (np.arange(64) % 2).astype(np.uint32)
+        ix.set_labels(COL, col)
+        off = 1000
+        ix.set_id_offset(off)
+        good = [np.array([0, 1, 2, 3]), np.array([4, 5, 6, 7])]
+        text = "group cap: a list holds an id that is no row of this index (id - id_offset must be below len)"
+        sent = np.uint64(-7 & 0xFFFFFFFFFFFFFFFF)
+        for past, below in ((True, False), (False, True), (True, True)):
+            lists = [g + off for g in good]  # (the ids as passed: id_offset included)
+            if past:
+                lists[0][2] = 64 + off
+            if below:
+                lists[1][1] = off - 1
+            with pytest.raises(vdb.VdbError, match=re.escape(text)):
+                _run(ix, lists, 4, 3, COL, 1)
+            assert (_run.last[0] == sent).all() and (_run.last[1] == -7.0).all() and (_run.last[2] == sent).all()
+            _, _, gc = _check((ix, {COL: col}, rng), good, 4, 3, COL, 1, id_offset=off, what=("after", past, below))
+            assert gc.tolist() == [2, 2]  # (one row per label value: two values in every list)
+    finally:
+        ix.close()

@@ -32,10 +32,10 @@ def _base(dim):
 
 
 class Env:
-    def __init__(self, dim, dist, kind):
+    def __init__(self, dim, dist, kind, base=None):
         import lab_1806_vec_db_amd as vdb
 
-        self.base = _base(dim)
+        self.base = _base(dim) if base is None else base
         self.ix = vdb.GpuIndex(dim, dist, device=0)
         self.ix.batch_add(self.base)
         self.rd = R.RowDist(self.base, kind)
@@ -264,3 +264,33 @@ def test_refusals_leave_outputs_and_counters(env):
     assert before == {s: ix.get_stat(s) for s in stats}
     _check(env, one[0], one[1], 4, 2, 0.5)  # the index still answers
     assert before == {s: ix.get_stat(s) for s in stats}  # (the selection alone counts nothing)
+
+
+def test_bad_id_text_and_the_call_after_it():
+    """64 rows x dim 8, lists [2][4] with an id equal to len + id_offset, an id below id_offset, and both: the call raises with the exact
+    text, the outputs keep their sentinel, and the valid call that follows on the same index is answered -- the flag word of the id check
+    is zeroed by every call"""
+    import re
+
+    import lab_1806_vec_db_amd as vdb
+
+    env = Env(8, "l2sqr", 0, base=np.random.default_rng(5).standard_normal((64, 8)).astype(np.float32))
+    off = 1000
+    env.ix.set_id_offset(off)
+    try:
+        good = [np.array([0, 1, 2, 3]), np.array([4, 5, 6, 7])]
+        dists = [_dists(env, 4), _dists(env, 4)]
+        text = "mmr select: a list holds an id that is no row of this index (id - id_offset must be below len)"
+        for past, below in ((True, False), (False, True), (True, True)):
+            lists = [g + off for g in good]  # (the ids as passed: id_offset included)
+            if past:
+                lists[0][2] = 64 + off
+            if below:
+                lists[1][1] = off - 1
+            with pytest.raises(vdb.VdbError, match=re.escape(text)):
+                _run(env.ix, lists, dists, 4, 2, 0.5)
+            assert (_run.last[0] == SENT).all() and (_run.last[1] == -7.0).all() and (_run.last[2] == SENT).all()
+            _, _, gc = _check(env, good, dists, 4, 2, 0.5, id_offset=off, what=("after", past, below))
+            assert gc.tolist() == [2, 2]
+    finally:
+        env.ix.close()
