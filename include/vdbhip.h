@@ -293,13 +293,13 @@ int vdb_flat_range_filtered_multi_device(vdb_index *idx, const void *d_queries, 
  * is unchanged.  n_masks == 0 succeeds.  The single form is this call with one mask.
  * vdb_mask_rows: reads a mask of either constructor back -- out_bits: ceil(n_rows / 64) words, out_ids: the m allowed rows, ascending
  * (vdb_mask_count gives m); either pointer may be NULL.
- * How the masks are built (csrc/k_labels.hip, docs/DESIGN_flat.md 4.1l): per chunk of up to 1024 masks, k_mask_where -- a 64-lane wave
+ * How the masks are built (csrc/k_labels.hip, docs/DESIGN_flat.md 4.1l): per chunk of up to 1024 masks, k_mask_rows<MaskEq> -- a 64-lane wave
  * owns one mask word, a lane one row; the lane compares its row's value in every term column and the wave's ballot is the word --
  * counts the allowed rows per workgroup, k_mask_scan turns the counts into offsets, one read-back of the totals sizes the allow-lists,
  * and k_mask_ids writes every allowed row at its offset: ascending without a sort.  Traffic per mask: 4 B x terms x rows read, rows / 8
  * + 4 m written.  vdb_prof_get "mask_where" times the three kernels; vdb_get_stat "mask_where_masks" counts the masks built this way,
  * "label_columns" the allocated columns ("hbm_bytes_per_row" includes them).
- * SET AND RANGE TERMS (vdb_mask_create_where_sets / _many; csrc/mask_sets.hpp, k_mask_where_sets, docs/DESIGN_flat.md 4.1m): a term is
+ * SET AND RANGE TERMS (vdb_mask_create_where_sets / _many; csrc/mask_sets.hpp, k_mask_rows<MaskAll>, docs/DESIGN_flat.md 4.1m): a term is
  * {column, lo, hi, flags, bitmap} and a mask the conjunction of its terms.  A row whose label in the column is v matches the term
  *   - when v == VDB_LABEL_NONE (no value, or a column never written): iff flags has VDB_TERM_NONE; VDB_TERM_NEGATE never inverts this;
  *   - otherwise: inside = lo <= v <= hi and (no bitmap, or bit (v - lo) of the bitmap); it matches iff inside != (flags has VDB_TERM_NEGATE).
@@ -320,8 +320,8 @@ int vdb_flat_range_filtered_multi_device(vdb_index *idx, const void *d_queries, 
  * owner / staleness rules, lazily built row constants, f32 and VecSet<u8> indexes, every call that takes a vdb_mask.  Traffic per mask:
  * 4 B x terms x rows read as before plus one 8-byte bitmap gather per in-range row and bitmap term (from a block that stays cached).
  * vdb_get_stat "mask_where_set_masks" counts the masks built by these two calls ("mask_where_masks" keeps counting the equality calls
- * only); vdb_prof_get "mask_where_sets" times k_mask_where_sets with its scan and ids launches.
- * OR OF CONJUNCTIONS (vdb_mask_create_where_any / _many; csrc/mask_any.hpp, k_mask_where_any, docs/DESIGN_flat.md 4.1o): a mask is the
+ * only); vdb_prof_get "mask_where_sets" times k_mask_rows<MaskAll> with its scan and ids launches.
+ * OR OF CONJUNCTIONS (vdb_mask_create_where_any / _many; csrc/mask_any.hpp, k_mask_rows<MaskAny>, docs/DESIGN_flat.md 4.1o): a mask is the
  * OR of up to VDB_MASK_MAX_CLAUSES clauses, a clause the AND of up to VDB_MASK_MAX_TERMS terms, a term exactly the set / range term above
  * with the same match -- a filter expression in disjunctive normal form, NOT pushed down to the terms (toggling VDB_TERM_NEGATE and
  * VDB_TERM_NONE complements a term exactly).  Clause c's terms are entries [clause_lims[c], clause_lims[c + 1]) of the term arrays
@@ -338,7 +338,7 @@ int vdb_flat_range_filtered_multi_device(vdb_index *idx, const void *d_queries, 
  * read once per term that names it (4 B x terms x rows over all clauses, repeated reads of a column served by cache).  The
  * result is the same vdb_mask object: owner / staleness rules, lazily built row constants, f32 and VecSet<u8> indexes, every call that
  * takes a vdb_mask.  vdb_get_stat "mask_where_any_masks" counts the masks built by these two calls (the older counters keep counting
- * only their own calls); vdb_prof_get "mask_where_any" times k_mask_where_any with its scan and ids launches.
+ * only their own calls); vdb_prof_get "mask_where_any" times k_mask_rows<MaskAny> with its scan and ids launches.
  * MASK ALGEBRA (vdb_mask_combine; k_mask_combine): out = the AND (VDB_MASK_OP_AND) or OR (VDB_MASK_OP_OR) over n_in (1 .. 8) masks of
  * this index, input i complemented first when invert != NULL and invert[i] != 0; n_in == 1 with invert set is NOT.  For what the
  * columns cannot express: inputs may come from any constructor, host-built masks (vdb_mask_create) included.  A complement is taken

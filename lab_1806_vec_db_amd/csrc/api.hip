@@ -241,6 +241,23 @@ static void range_call(Index &ix, Workspace &ws, vdb_range **out, Body &&body) {
     *out = res.release();
 }
 
+// "Make n masks or none", the body of the four entry points that fill out[0 .. n): every out[g] is null first; then refuse() may throw
+// what the entry point checks before a mask object exists; then n fresh masks go to body(rm), and only when it returns are they
+// released into `out` -- a throw destroys every one of them (and with the last of a chunk its slabs).
+template <class Refuse, class Body>
+static void make_masks(uint64_t n, vdb_mask **out, Refuse refuse, Body body) {
+    for (uint64_t g = 0; g < n; g++) out[g] = nullptr;
+    refuse();
+    std::vector<std::unique_ptr<vdb_mask>> made(n);
+    std::vector<RowMask *> rm(n);
+    for (uint64_t g = 0; g < n; g++) {
+        made[g].reset(new vdb_mask);
+        rm[g] = &made[g]->m;
+    }
+    body(rm.data());
+    for (uint64_t g = 0; g < n; g++) out[g] = made[g].release();
+}
+
 extern "C" {
 
 const char *vdb_last_error(void) { return g_last_error.c_str(); }
@@ -779,15 +796,7 @@ int vdb_mask_create_where_many(vdb_index *idx, const uint64_t *term_lims, const 
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
     VDB_REQUIRE(n_masks == 0 || out, "null argument");
-    for (uint64_t g = 0; g < n_masks; g++) out[g] = nullptr;
-    std::vector<std::unique_ptr<vdb_mask>> made(n_masks);
-    std::vector<RowMask *> rm(n_masks);
-    for (uint64_t g = 0; g < n_masks; g++) {
-        made[g].reset(new vdb_mask);
-        rm[g] = &made[g]->m;
-    }
-    idx->ix.masks_where(term_lims, columns, codes, n_masks, rm.data());  // a throw destroys every mask made so far with `made`
-    for (uint64_t g = 0; g < n_masks; g++) out[g] = made[g].release();
+    make_masks(n_masks, out, [] {}, [&](RowMask *const *rm) { idx->ix.masks_where(term_lims, columns, codes, n_masks, rm); });
     VDB_API_END
 }
 int vdb_mask_create_where(vdb_index *idx, const uint32_t *columns, const uint32_t *codes, uint64_t n_terms, vdb_mask **out) {
@@ -807,16 +816,9 @@ int vdb_mask_create_where_sets_many(vdb_index *idx, const uint64_t *term_lims, c
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
     VDB_REQUIRE(n_masks == 0 || out, "null argument");
-    for (uint64_t g = 0; g < n_masks; g++) out[g] = nullptr;
-    VDB_REQUIRE(n_masks < (1ull << 28), "too many masks for one call");
-    std::vector<std::unique_ptr<vdb_mask>> made(n_masks);
-    std::vector<RowMask *> rm(n_masks);
-    for (uint64_t g = 0; g < n_masks; g++) {
-        made[g].reset(new vdb_mask);
-        rm[g] = &made[g]->m;
-    }
-    idx->ix.masks_where_sets(term_lims, columns, lo, hi, flags, set_lims, set_words, n_masks, rm.data());  // a throw destroys every mask with `made`
-    for (uint64_t g = 0; g < n_masks; g++) out[g] = made[g].release();
+    make_masks(
+        n_masks, out, [&] { VDB_REQUIRE(n_masks < (1ull << 28), "too many masks for one call"); },
+        [&](RowMask *const *rm) { idx->ix.masks_where_sets(term_lims, columns, lo, hi, flags, set_lims, set_words, n_masks, rm); });
     VDB_API_END
 }
 int vdb_mask_create_where_sets(vdb_index *idx, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi, const uint32_t *flags,
@@ -838,16 +840,9 @@ int vdb_mask_create_where_any_many(vdb_index *idx, const uint64_t *mask_lims, co
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
     VDB_REQUIRE(n_masks == 0 || out, "null argument");
-    for (uint64_t g = 0; g < n_masks; g++) out[g] = nullptr;
-    VDB_REQUIRE(n_masks < (1ull << 28), "too many masks for one call");
-    std::vector<std::unique_ptr<vdb_mask>> made(n_masks);
-    std::vector<RowMask *> rm(n_masks);
-    for (uint64_t g = 0; g < n_masks; g++) {
-        made[g].reset(new vdb_mask);
-        rm[g] = &made[g]->m;
-    }
-    idx->ix.masks_where_any(mask_lims, clause_lims, columns, lo, hi, flags, set_lims, set_words, n_masks, rm.data());  // a throw destroys every mask with `made`
-    for (uint64_t g = 0; g < n_masks; g++) out[g] = made[g].release();
+    make_masks(
+        n_masks, out, [&] { VDB_REQUIRE(n_masks < (1ull << 28), "too many masks for one call"); },
+        [&](RowMask *const *rm) { idx->ix.masks_where_any(mask_lims, clause_lims, columns, lo, hi, flags, set_lims, set_words, n_masks, rm); });
     VDB_API_END
 }
 int vdb_mask_create_where_any(vdb_index *idx, const uint64_t *clause_lims, uint64_t n_clauses, const uint32_t *columns, const uint32_t *lo,
@@ -881,17 +876,13 @@ int vdb_mask_create_partition(vdb_index *idx, uint32_t column, const uint32_t *c
     VDB_REQUIRE(idx, "null index");
     VDB_REQUIRE(n_codes < (1ull << 28), "too many codes for one call");  // (before `out` is written: it has room for n_codes handles)
     VDB_REQUIRE(n_codes == 0 || out, "null argument");
-    for (uint64_t g = 0; g < n_codes; g++) out[g] = nullptr;
-    const std::string bad = mask_partition_check(column, codes, n_codes);  // (before a mask object is made)
-    VDB_REQUIRE(bad.empty(), bad);
-    std::vector<std::unique_ptr<vdb_mask>> made(n_codes);
-    std::vector<RowMask *> rm(n_codes);
-    for (uint64_t g = 0; g < n_codes; g++) {
-        made[g].reset(new vdb_mask);
-        rm[g] = &made[g]->m;
-    }
-    idx->ix.masks_partition(column, codes, n_codes, rm.data());  // a throw destroys every mask with `made`, and with the last its slabs
-    for (uint64_t g = 0; g < n_codes; g++) out[g] = made[g].release();
+    make_masks(
+        n_codes, out,
+        [&] {  // (before a mask object is made)
+            const std::string bad = mask_partition_check(column, codes, n_codes);
+            VDB_REQUIRE(bad.empty(), bad);
+        },
+        [&](RowMask *const *rm) { idx->ix.masks_partition(column, codes, n_codes, rm); });
     VDB_API_END
 }
 int vdb_index_label_counts(vdb_index *idx, uint32_t column, const vdb_mask *mask, const uint32_t *codes, uint64_t n_codes, uint64_t *out_counts) {

@@ -440,11 +440,11 @@ void Index::get_rows_device(Workspace &ws, const uint64_t *d_ids, uint64_t m, vo
     fetch_rows += m;
 }
 
-// ---- label columns and the masks built from them (k_labels.hip) ----------------------------------------------------------------------
+// ---- label columns (k_labels.hip; the masks built from them: index_masks.hip) ----------------------------------------------------------
 LabelCols Index::label_cols() const {
     LabelCols lc{};
     for (uint32_t c = 0; c < LABEL_COLUMNS; c++)
-        if (label_live[c]) lc.col[lc.n++] = d_labels[c].as<uint32_t>();
+        if (uint32_t *col = label_col(c)) lc.col[lc.n++] = col;
     return lc;
 }
 
@@ -574,301 +574,6 @@ void Index::labels_set_mask(const RowMask &mask, const uint32_t *columns, const 
     prof_collect(*ws);
     labels_scatter_calls += 1;
     labels_scatter_rows += m;
-}
-
-// The argument check and the term table; the masks themselves through masks_finish (below).
-void Index::masks_where(const uint64_t *term_lims, const uint32_t *columns, const uint32_t *codes, uint64_t n_masks, RowMask *const *out) {
-    VDB_REQUIRE(n_masks == 0 || (term_lims && out), "null argument");
-    if (n_masks == 0) return;
-    VDB_REQUIRE(n_masks < (1ull << 28), "too many masks for one call");
-    VDB_REQUIRE(term_lims[0] == 0, "mask terms: term_lims[0] must be 0");
-    for (uint64_t g = 0; g < n_masks; g++) {
-        VDB_REQUIRE(term_lims[g + 1] >= term_lims[g], "mask terms: term_lims must not decrease (mask " + std::to_string(g) + ")");
-        VDB_REQUIRE(term_lims[g + 1] - term_lims[g] <= MASK_MAX_TERMS, "mask terms: mask " + std::to_string(g) + " has " +
-                                                                           std::to_string(term_lims[g + 1] - term_lims[g]) + " terms, at most " +
-                                                                           std::to_string(MASK_MAX_TERMS) + " are supported");
-    }
-    const uint64_t n_terms = term_lims[n_masks];
-    VDB_REQUIRE(n_terms == 0 || (columns && codes), "null argument");
-    for (uint64_t t = 0; t < n_terms; t++)
-        VDB_REQUIRE(columns[t] < LABEL_COLUMNS, "mask terms: column " + std::to_string(columns[t]) + " (term " + std::to_string(t) +
-                                                    "), an index has " + std::to_string(LABEL_COLUMNS));
-    use_device();
-    WsLease ws(*this);
-    hipStream_t s = ws->stream;
-    std::vector<MaskTerm> h_terms(std::max<uint64_t>(n_terms, 1));
-    for (uint64_t t = 0; t < n_terms; t++) h_terms[t] = {label_live[columns[t]] ? d_labels[columns[t]].as<uint32_t>() : nullptr, codes[t]};
-    if (n) {  // (contents not preserved by reserve: the term table of the call is sized and uploaded here, once)
-        ws->keys_a.reserve(h_terms.size() * sizeof(MaskTerm));
-        VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_terms.data(), h_terms.size() * sizeof(MaskTerm), hipMemcpyHostToDevice, s));
-    }
-    masks_finish(
-        *ws, term_lims, n_masks, out, "mask_where",
-        [&](uint64_t g0, uint64_t nb) { return double(term_lims[g0 + nb] - term_lims[g0]) * double(n) * sizeof(uint32_t); },
-        [&](uint64_t, uint64_t nb) {
-            launch_mask_where(ws->keys_a.as<MaskTerm>(), ws->keys_b.as<MaskJob>(), (uint32_t)nb, n, ws->flags.as<uint32_t>(), ws->misc.as<uint32_t>(), s);
-        });
-    mask_where_masks += n_masks;
-}
-
-// The same for set / range terms (mask_sets.hpp checks and lays out; k_mask_where_sets evaluates).  The term table and, behind it in
-// the same buffer, the packed bitmaps of the WHOLE call are uploaded once, before the first chunk.
-void Index::masks_where_sets(const uint64_t *term_lims, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi, const uint32_t *flags,
-                             const uint64_t *set_lims, const uint64_t *set_words, uint64_t n_masks, RowMask *const *out) {
-    VDB_REQUIRE(n_masks == 0 || out, "null argument");
-    uint64_t n_terms = 0, n_set_words = 0;
-    const std::string bad = mask_sets_check(term_lims, columns, lo, hi, flags, set_lims, set_words, n_masks, &n_terms, &n_set_words);
-    VDB_REQUIRE(bad.empty(), bad);
-    if (n_masks == 0) return;
-    use_device();
-    WsLease ws(*this);
-    hipStream_t s = ws->stream;
-    std::vector<SetTerm> h_terms;
-    if (n) {  // (contents not preserved by reserve: the buffer of the call is sized and uploaded here, once)
-        const size_t term_bytes = std::max<uint64_t>(n_terms, 1) * sizeof(SetTerm);  // (a multiple of 8: the bitmaps behind it are aligned)
-        ws->keys_a.reserve(term_bytes + n_set_words * sizeof(uint64_t));
-        const uint64_t *d_sets = reinterpret_cast<const uint64_t *>(ws->keys_a.as<char>() + term_bytes);
-        const uint32_t *col_ptrs[LABEL_COLUMNS];
-        for (uint32_t c = 0; c < LABEL_COLUMNS; c++) col_ptrs[c] = label_live[c] ? d_labels[c].as<uint32_t>() : nullptr;
-        mask_sets_layout(columns, lo, hi, flags, set_lims, n_terms, col_ptrs, d_sets, h_terms);
-        if (n_terms) VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_terms.data(), n_terms * sizeof(SetTerm), hipMemcpyHostToDevice, s));
-        if (n_set_words)
-            VDB_HIP(hipMemcpyAsync(ws->keys_a.as<char>() + term_bytes, set_words, n_set_words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    }
-    masks_finish(
-        *ws, term_lims, n_masks, out, "mask_where_sets",
-        [&](uint64_t g0, uint64_t nb) { return double(term_lims[g0 + nb] - term_lims[g0]) * double(n) * sizeof(uint32_t); },
-        [&](uint64_t, uint64_t nb) {
-            launch_mask_where_sets(ws->keys_a.as<SetTerm>(), ws->keys_b.as<MaskJob>(), (uint32_t)nb, n, ws->flags.as<uint32_t>(), ws->misc.as<uint32_t>(), s);
-        });
-    mask_where_set_masks += n_masks;
-}
-
-// What every device-built mask goes through behind the kernel that writes its bit words and per-block counts (index.hpp: masks_finish).
-// Per chunk of masks: that kernel + k_mask_scan, ONE read-back of the totals (the only synchronisation before the allow-lists can be
-// allocated), k_mask_ids, synchronise.  The chunk bounds grid.y and the block-count scratch (at most 1024 masks and 64 MiB of counts).
-void Index::masks_finish(Workspace &ws, const uint64_t *lims, uint64_t n_masks, RowMask *const *out, const char *prof,
-                         const std::function<double(uint64_t, uint64_t)> &bytes, const std::function<void(uint64_t, uint64_t)> &launch,
-                         bool slabs) {
-    hipStream_t s = ws.stream;
-    slabs = slabs && !devbuf_efence();  // (a mask's own end stays fenced: per-mask allocations)
-    const uint64_t nw = (n + 63) / 64;
-    const uint32_t nblocks = mask_where_blocks(n);
-    const uint64_t gen = write_gen.load();
-    const uint64_t chunk = nblocks ? std::min<uint64_t>({n_masks, 1024, std::max<uint64_t>((64ull << 20) / (sizeof(uint32_t) * nblocks), 1)}) : n_masks;
-    std::vector<MaskJob> h_jobs(chunk);
-    std::vector<uint32_t *> h_ids(chunk);
-    if (nblocks) {  // (contents not preserved by reserve: everything a chunk needs is sized here, once)
-        ws.keys_b.reserve(chunk * sizeof(MaskJob));
-        ws.keys_c.reserve(chunk * sizeof(uint32_t *));
-        ws.flags.reserve(chunk * nblocks * sizeof(uint32_t));
-        ws.misc.reserve(chunk * sizeof(uint32_t));
-    }
-    const size_t bits_bytes = std::max<uint64_t>(nw, 1) * sizeof(uint64_t), bits_step = devbuf_align_up(bits_bytes);
-    for (uint64_t g0 = 0; g0 < n_masks; g0 += chunk) {
-        const uint64_t nb = std::min(chunk, n_masks - g0);
-        std::shared_ptr<DevBuf> slab_bits, slab_ids;
-        if (slabs) {  // ONE allocation for the chunk's bit words, every mask a view at a multiple of bits_step
-            slab_bits = std::make_shared<DevBuf>();
-            slab_bits->reserve(nb * bits_step);
-            slab_ids = std::make_shared<DevBuf>();
-        }
-        for (uint64_t j = 0; j < nb; j++) {
-            RowMask &m = *out[g0 + j];
-            m.owner = this;
-            m.device = device;
-            m.gen = gen;
-            m.n_rows = n;
-            m.m = 0;
-            if (slabs) {
-                m.slab_bits = slab_bits;
-                m.d_bits.view(slab_bits->as<char>() + j * bits_step, bits_step);
-            } else {
-                m.d_bits.reserve(bits_bytes);
-            }
-            h_jobs[j] = {m.d_bits.as<uint64_t>(), lims ? (uint32_t)lims[g0 + j] : 0u, lims ? (uint32_t)lims[g0 + j + 1] : 0u};
-        }
-        if (!nblocks) {  // an empty index: masks with m = 0
-            if (slabs) slab_ids->reserve(nb * DEVBUF_ALIGN);
-            for (uint64_t j = 0; j < nb; j++) {
-                RowMask &m = *out[g0 + j];
-                if (slabs) {
-                    m.slab_ids = slab_ids;
-                    m.d_ids.view(slab_ids->as<char>() + j * DEVBUF_ALIGN, DEVBUF_ALIGN);
-                } else {
-                    m.d_ids.reserve(sizeof(uint32_t));
-                }
-            }
-            continue;
-        }
-        uint32_t *h_tot = static_cast<uint32_t *>(ws.pinned(chunk * sizeof(uint32_t)));
-        VDB_HIP(hipMemcpyAsync(ws.keys_b.p, h_jobs.data(), nb * sizeof(MaskJob), hipMemcpyHostToDevice, s));
-        prof_begin(ws, prof, bytes(g0, nb) + double(nb) * double(nw) * sizeof(uint64_t));
-        launch(g0, nb);
-        prof_end(ws);
-        VDB_HIP(hipMemcpyAsync(h_tot, ws.misc.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        VDB_SYNC(s);
-        uint64_t sum_m = 0;
-        if (slabs) {  // ONE allocation for the chunk's allow-lists: the lists back to back, each start rounded up to DEVBUF_ALIGN
-            size_t total = 0;
-            for (uint64_t j = 0; j < nb; j++) total += devbuf_align_up(std::max<uint64_t>(h_tot[j], 1) * sizeof(uint32_t));
-            slab_ids->reserve(total);
-        }
-        size_t ids_at = 0;
-        for (uint64_t j = 0; j < nb; j++) {
-            RowMask &m = *out[g0 + j];
-            m.m = h_tot[j];
-            sum_m += m.m;
-            if (slabs) {
-                const size_t step = devbuf_align_up(std::max<uint64_t>(m.m, 1) * sizeof(uint32_t));
-                m.slab_ids = slab_ids;
-                m.d_ids.view(slab_ids->as<char>() + ids_at, step);
-                ids_at += step;
-            } else {
-                m.d_ids.reserve(std::max<uint64_t>(m.m, 1) * sizeof(uint32_t));
-            }
-            h_ids[j] = m.d_ids.as<uint32_t>();
-        }
-        VDB_HIP(hipMemcpyAsync(ws.keys_c.p, h_ids.data(), nb * sizeof(uint32_t *), hipMemcpyHostToDevice, s));
-        prof_begin(ws, prof, double(nb) * double(nw) * sizeof(uint64_t) + double(sum_m) * sizeof(uint32_t));
-        launch_mask_ids(ws.keys_b.as<MaskJob>(), ws.keys_c.as<uint32_t *>(), (uint32_t)nb, n, ws.flags.as<uint32_t>(), s);
-        prof_end(ws);
-        VDB_SYNC(s);
-        prof_collect(ws);
-    }
-}
-
-// An OR of conjunctions (mask_any.hpp checks and lays out; k_mask_where_any evaluates).  The term table, the clause table and the packed
-// bitmaps of the WHOLE call are one buffer, uploaded once before the first chunk.
-void Index::masks_where_any(const uint64_t *mask_lims, const uint64_t *clause_lims, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi,
-                            const uint32_t *flags, const uint64_t *set_lims, const uint64_t *set_words, uint64_t n_masks, RowMask *const *out) {
-    VDB_REQUIRE(n_masks == 0 || out, "null argument");
-    uint64_t n_clauses = 0, n_terms = 0, n_set_words = 0;
-    const std::string bad = mask_any_check(mask_lims, clause_lims, columns, lo, hi, flags, set_lims, set_words, n_masks, &n_clauses, &n_terms, &n_set_words);
-    VDB_REQUIRE(bad.empty(), bad);
-    if (n_masks == 0) return;
-    use_device();
-    WsLease ws(*this);
-    hipStream_t s = ws->stream;
-    const AnyLayout L = mask_any_buffer(n_clauses, n_terms, n_set_words);
-    std::vector<SetTerm> h_terms;
-    std::vector<uint32_t> h_clims;
-    if (n) {  // (contents not preserved by reserve: the buffer of the call is sized and uploaded here, once)
-        ws->keys_a.reserve(L.total);
-        char *base = ws->keys_a.as<char>();
-        const uint32_t *col_ptrs[LABEL_COLUMNS];
-        for (uint32_t c = 0; c < LABEL_COLUMNS; c++) col_ptrs[c] = label_live[c] ? d_labels[c].as<uint32_t>() : nullptr;
-        mask_sets_layout(columns, lo, hi, flags, set_lims, n_terms, col_ptrs, reinterpret_cast<const uint64_t *>(base + L.sets_off), h_terms);
-        mask_any_layout(clause_lims, n_clauses, h_clims);
-        if (n_terms) VDB_HIP(hipMemcpyAsync(base, h_terms.data(), n_terms * sizeof(SetTerm), hipMemcpyHostToDevice, s));
-        VDB_HIP(hipMemcpyAsync(base + L.clause_off, h_clims.data(), h_clims.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        if (n_set_words) VDB_HIP(hipMemcpyAsync(base + L.sets_off, set_words, n_set_words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    }
-    masks_finish(
-        *ws, mask_lims, n_masks, out, "mask_where_any",
-        [&](uint64_t g0, uint64_t nb) {  // 4 B x terms x rows over all clauses of the chunk
-            const uint64_t c0 = mask_lims[g0], c1 = mask_lims[g0 + nb];
-            return c1 > c0 ? double(clause_lims[c1] - clause_lims[c0]) * double(n) * sizeof(uint32_t) : 0.0;
-        },
-        [&](uint64_t, uint64_t nb) {
-            const char *base = ws->keys_a.as<char>();
-            launch_mask_where_any(reinterpret_cast<const SetTerm *>(base), reinterpret_cast<const uint32_t *>(base + L.clause_off),
-                                  ws->keys_b.as<MaskJob>(), (uint32_t)nb, n, ws->flags.as<uint32_t>(), ws->misc.as<uint32_t>(), s);
-        });
-    mask_where_any_masks += n_masks;
-}
-
-// AND / OR / NOT of finished masks (k_mask_combine): one output mask through the same second half.
-void Index::mask_combine(int op, const RowMask *const *in, const uint8_t *invert, uint64_t n_in, RowMask &out) {
-    VDB_REQUIRE(op == MASK_OP_AND || op == MASK_OP_OR, "mask combine: unknown op " + std::to_string(op));
-    VDB_REQUIRE(n_in >= 1 && n_in <= MASK_COMBINE_MAX, "mask combine: " + std::to_string(n_in) + " inputs, 1 .. " + std::to_string(MASK_COMBINE_MAX) + " are supported");
-    VDB_REQUIRE(in, "null argument");
-    for (uint64_t i = 0; i < n_in; i++) VDB_REQUIRE(in[i], "null mask");
-    for (uint64_t i = 0; i < n_in; i++) check_mask(*in[i]);
-    use_device();
-    WsLease ws(*this);
-    MaskCombine a{};
-    a.n_in = (uint32_t)n_in;
-    a.op = op;
-    for (uint64_t i = 0; i < n_in; i++) {
-        a.in[i] = in[i]->d_bits.as<uint64_t>();
-        if (invert && invert[i]) a.invert |= 1u << i;
-    }
-    RowMask *outp = &out;
-    masks_finish(
-        *ws, nullptr, 1, &outp, "mask_combine", [&](uint64_t, uint64_t) { return double(n_in) * double((n + 63) / 64) * sizeof(uint64_t); },
-        [&](uint64_t, uint64_t) { launch_mask_combine(a, out.d_bits.as<uint64_t>(), n, ws->flags.as<uint32_t>(), ws->misc.as<uint32_t>(), ws->stream); });
-    mask_combine_masks += 1;
-}
-
-// ONE column grouped by code (mask_partition.hpp checks the codes and lays out a chunk's table; k_mask_partition reads the column once
-// per chunk).  masks_finish cuts the call into chunks and places every chunk's masks in two slabs; per chunk the launch clears the bit
-// words and the block counts, uploads the chunk's table and runs the kernel -- all of it inside the profile entry.
-void Index::masks_partition(uint32_t column, const uint32_t *codes, uint64_t n_codes, RowMask *const *out) {
-    const std::string bad = mask_partition_check(column, codes, n_codes);
-    VDB_REQUIRE(bad.empty(), bad);
-    VDB_REQUIRE(n_codes == 0 || out, "null argument");
-    if (n_codes == 0) return;
-    use_device();
-    WsLease ws(*this);
-    hipStream_t s = ws->stream;
-    const uint32_t *col = label_live[column] ? d_labels[column].as<uint32_t>() : nullptr;
-    const uint32_t nblocks = mask_where_blocks(n);
-    const size_t bits_bytes = std::max<uint64_t>((n + 63) / 64, 1) * sizeof(uint64_t);
-    std::vector<uint32_t> h_sorted, h_slot, h_table;  // (alive until masks_finish has synchronised the chunk that reads them)
-    if (n) ws->keys_a.reserve(2 * size_t(PART_MAX_CHUNK) * sizeof(uint32_t));
-    masks_finish(
-        *ws, nullptr, n_codes, out, "mask_partition", [&](uint64_t, uint64_t nb) { return double(n) * sizeof(uint32_t) + double(nb) * double(nblocks) * sizeof(uint32_t); },
-        [&](uint64_t g0, uint64_t nb) {
-            if (out[g0]->slab_bits) {  // the chunk's masks are one slab: one clear
-                VDB_HIP(hipMemsetAsync(out[g0]->slab_bits->p, 0, nb * out[g0]->d_bits.cap, s));
-            } else {
-                for (uint64_t j = 0; j < nb; j++) VDB_HIP(hipMemsetAsync(out[g0 + j]->d_bits.p, 0, bits_bytes, s));
-            }
-            VDB_HIP(hipMemsetAsync(ws->flags.p, 0, nb * size_t(nblocks) * sizeof(uint32_t), s));
-            mask_partition_layout(codes + g0, (uint32_t)nb, h_sorted, h_slot);
-            h_table.assign(h_sorted.begin(), h_sorted.end());
-            h_table.insert(h_table.end(), h_slot.begin(), h_slot.end());
-            VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_table.data(), h_table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            launch_mask_partition(col, ws->keys_a.as<uint32_t>(), (uint32_t)nb, ws->keys_b.as<MaskJob>(), n, ws->flags.as<uint32_t>(), ws->misc.as<uint32_t>(), s);
-        },
-        true);
-    mask_partition_masks += n_codes;
-}
-
-// Rows per code of one column, over all rows or under a mask (k_label_counts): per chunk of PART_MAX_CHUNK codes one launch over the
-// column, the counters read back in the table's order and handed out in the caller's.
-void Index::label_counts(uint32_t column, const RowMask *mask, const uint32_t *codes, uint64_t n_codes, uint64_t *out_counts) {
-    const std::string bad = mask_partition_check(column, codes, n_codes);
-    VDB_REQUIRE(bad.empty(), bad);
-    VDB_REQUIRE(n_codes == 0 || out_counts, "null argument");
-    if (mask) check_mask(*mask);
-    label_count_calls += 1;
-    if (n_codes == 0) return;
-    std::fill(out_counts, out_counts + n_codes, uint64_t(0));
-    if (n == 0) return;
-    use_device();
-    WsLease ws(*this);
-    hipStream_t s = ws->stream;
-    const uint32_t *col = label_live[column] ? d_labels[column].as<uint32_t>() : nullptr;
-    const uint64_t *bits = mask ? mask->d_bits.as<uint64_t>() : nullptr;
-    std::vector<uint32_t> h_sorted, h_slot;
-    ws->keys_a.reserve(size_t(PART_MAX_CHUNK) * sizeof(uint32_t));
-    ws->misc.reserve(size_t(PART_MAX_CHUNK) * sizeof(uint32_t));
-    uint32_t *h_cnt = static_cast<uint32_t *>(ws->pinned(size_t(PART_MAX_CHUNK) * sizeof(uint32_t)));
-    for (uint64_t g0 = 0; g0 < n_codes; g0 += PART_MAX_CHUNK) {
-        const uint32_t nb = (uint32_t)std::min<uint64_t>(PART_MAX_CHUNK, n_codes - g0);
-        mask_partition_layout(codes + g0, nb, h_sorted, h_slot);
-        VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_sorted.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        prof_begin(*ws, "label_counts", double(n) * sizeof(uint32_t) + (bits ? double((n + 63) / 64) * sizeof(uint64_t) : 0.0));
-        VDB_HIP(hipMemsetAsync(ws->misc.p, 0, nb * sizeof(uint32_t), s));
-        launch_label_counts(col, ws->keys_a.as<uint32_t>(), nb, bits, n, ws->misc.as<uint32_t>(), num_cu, s);
-        prof_end(*ws);
-        VDB_HIP(hipMemcpyAsync(h_cnt, ws->misc.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        VDB_SYNC(s);
-        prof_collect(*ws);
-        for (uint32_t i = 0; i < nb; i++) out_counts[g0 + h_slot[i]] = h_cnt[i];
-    }
 }
 
 // ---- images of the rows (RowMirror): a tier whose image is missing leaves its queries to the next one (8-bit -> fp16 -> split-bf16 ->

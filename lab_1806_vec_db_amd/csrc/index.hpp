@@ -612,6 +612,7 @@ struct Index {
     // IVF state.
     DevBuf d_labels[LABEL_COLUMNS];
     bool label_live[LABEL_COLUMNS] = {};
+    uint32_t *label_col(uint32_t c) const { return label_live[c] ? d_labels[c].as<uint32_t>() : nullptr; }  // nullptr: never written
     LabelCols label_cols() const;  // the allocated columns
     uint32_t label_columns() const { return label_cols().n; }
     void labels_set(uint32_t column, uint64_t first_row, const uint32_t *codes, uint64_t count);  // write-side
@@ -645,7 +646,7 @@ struct Index {
     void masks_where_sets(const uint64_t *term_lims, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi, const uint32_t *flags,
                           const uint64_t *set_lims, const uint64_t *set_words, uint64_t n_masks, RowMask *const *out);
     std::atomic<uint64_t> mask_where_set_masks{0};  // masks built by masks_where_sets
-    // An OR of conjunctions of such terms (mask_any.hpp; k_mask_where_any): mask g = the rows that match EVERY term of SOME clause in
+    // An OR of conjunctions of such terms (mask_any.hpp; k_mask_rows<MaskAny>): mask g = the rows that match EVERY term of SOME clause in
     // [mask_lims[g], mask_lims[g + 1]); clause c's terms are [clause_lims[c], clause_lims[c + 1]) of the term arrays.  A mask without
     // clauses is empty, a clause without terms allows every row.  Same contract as masks_where_sets.
     void masks_where_any(const uint64_t *mask_lims, const uint64_t *clause_lims, const uint32_t *columns, const uint32_t *lo, const uint32_t *hi,
@@ -665,15 +666,7 @@ struct Index {
     // code rules; the mask is checked with check_mask before anything is computed; read-side; returns synchronised.
     void label_counts(uint32_t column, const RowMask *mask, const uint32_t *codes, uint64_t n_codes, uint64_t *out_counts);
     std::atomic<uint64_t> label_count_calls{0};  // label_counts calls
-    // The second half of all five: given the bit-word kernel as `launch(g0, nb)` (it enqueues the kernel and k_mask_scan for masks
-    // [g0, g0 + nb) of the call, whose jobs are in ws.keys_b, block counts in ws.flags, totals in ws.misc; the caller's tables are in
-    // ws.keys_a), runs the chunk loop -- headers and jobs, launch, ONE read-back of the totals, allow-lists, k_mask_ids.
-    // lims[g] .. lims[g + 1] = the range a job carries (nullptr: none); bytes(g0, nb) = what the launch reads, for the profile entry `prof`.
-    void masks_finish(Workspace &ws, const uint64_t *lims, uint64_t n_masks, RowMask *const *out, const char *prof,
-                      const std::function<double(uint64_t, uint64_t)> &bytes, const std::function<void(uint64_t, uint64_t)> &launch,
-                      bool slabs = false);
-    // (slabs: the bit words of a chunk's masks are views into ONE allocation, zeroed, and their allow-lists views into another, every
-    // view DEVBUF_ALIGN-aligned -- masks_partition's; false: an allocation per mask and list, as every other caller has it.)
+    // The five builders and label_counts are in index_masks.hip, on two shared halves that are local to that file (4.1y).
     // The four Flat list re-rankers below -- grouped, diversified, by example, fused -- are in flat_rerank.hip, on one shared driver (4.1x).
     // Grouped Flat k-NN (k_group.hip, grouped_plan.hpp; docs/DESIGN_flat.md 4.1q): per query the first k rows, in FlatIndex::knn's order over
     // the allowed rows, of which at most g carry any one value of label column `column` (rows without a label are always kept).  Rounds:

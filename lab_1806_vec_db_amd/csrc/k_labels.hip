@@ -1,8 +1,8 @@
 // k_labels.hip -- label columns (one u32 per row and column, Index::d_labels) and the row masks built from them on the device
-// (Index::masks_where): upkeep of the columns under add / swap_remove / remove_rows, and the three kernels that turn a conjunction of
-// `column == code` terms into a RowMask's bit words and its ascending allow-list (docs/DESIGN_flat.md 4.1l), and the kernel that does the
-// same for set / range terms (Index::masks_where_sets, mask_sets.hpp; 4.1m), for an OR of such conjunctions (Index::masks_where_any,
-// mask_any.hpp; 4.1o) and for the AND / OR / NOT of finished masks (Index::mask_combine; 4.1o); and the two kernels that group ONE column
+// (index_masks.hip): upkeep of the columns under add / swap_remove / remove_rows; k_mask_rows<Pred>, k_mask_scan and k_mask_ids, which turn
+// a predicate over the columns into a RowMask's bit words and its ascending allow-list -- Pred = a conjunction of `column == code` terms
+// (MaskEq; docs/DESIGN_flat.md 4.1l), of set / range terms (MaskAll, mask_sets.hpp; 4.1m) or an OR of such conjunctions (MaskAny,
+// mask_any.hpp; 4.1o) -- and the same for the AND / OR / NOT of finished masks (k_mask_combine; 4.1o); and the two kernels that group ONE column
 // by code in a single read of it -- into the masks of many values (Index::masks_partition) or into rows per value (Index::label_counts;
 // mask_partition.hpp; 4.1p); and the two kernels that write codes to scattered rows of several columns in one launch -- per row of an id
 // list, or one code per column over a mask's rows (Index::labels_scatter, labels_set_mask; labels_scatter_plan.hpp; 4.1t).
@@ -51,24 +51,20 @@ void launch_label_move_one(const LabelCols &cols, uint32_t dst, uint32_t src, hi
 // ---- masks from labels ---------------------------------------------------------------------------------------------------------------------
 // One wave = one mask word, one lane = one row: on a 64-lane wave the ballot of "this row matches" IS the word (bit l = row 64 w + l), so
 // the bit words need no shuffles, no atomics and no LDS.  Grid (ceil(words / 4), masks of the chunk), 256 threads = 4 waves = 4 words.
-// A lane loads its row's value of every term column (4 B per lane, 256 B per wave and term, contiguous), ANDs the comparisons -- rows at
-// and past n are false, so the tail bits of the last word stay clear -- and lane 0 stores the ballot.  A null column (never written)
-// reads as LABEL_NONE for every row; zero terms allow every row.  blockcnt[mask][block] = allowed rows of the block's (up to) four words.
-__global__ __launch_bounds__(256) void k_mask_where(const MaskTerm *__restrict__ terms, const MaskJob *__restrict__ jobs, uint64_t n,
-                                                    uint32_t nwords, uint32_t nblocks, uint32_t *__restrict__ blockcnt) {
+// A lane asks the predicate about its row -- rows at and past n are false, so the tail bits of the last word stay clear -- and lane 0
+// stores the ballot.  blockcnt[mask][block] = allowed rows of the block's (up to) four words.  Pred (kernels.hpp: MaskEq, MaskAll,
+// MaskAny; by value, its tables in scalars) says whether row `row` of the index matches job's range [job.t0, job.t1) of its table;
+// `in` = row < n, and a predicate loads nothing of a row that is not in.
+template <class Pred>
+__global__ __launch_bounds__(256) void k_mask_rows(Pred pred, const MaskJob *__restrict__ jobs, uint64_t n, uint32_t nwords, uint32_t nblocks,
+                                                   uint32_t *__restrict__ blockcnt) {
     __shared__ uint32_t s_cnt[4];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const MaskJob job = jobs[blockIdx.y];
     const uint32_t word = blockIdx.x * 4 + wave;
     const uint64_t row = uint64_t(word) * 64 + lane;
     const bool in = row < n;
-    bool ok = in;
-    for (uint32_t t = job.t0; t < job.t1; t++) {  // (wave-uniform)
-        const MaskTerm tm = terms[t];
-        const uint32_t v = (tm.col && in) ? tm.col[row] : LABEL_NONE;
-        ok = ok && v == tm.code;
-    }
-    const uint64_t w = __ballot(ok);
+    const uint64_t w = __ballot(pred(job, row, in));
     if (lane == 0) {
         if (word < nwords) job.bits[word] = w;
         s_cnt[wave] = (uint32_t)__popcll(w);  // (a word at or past nwords has no row below n: 0)
@@ -77,9 +73,22 @@ __global__ __launch_bounds__(256) void k_mask_where(const MaskTerm *__restrict__
     if (threadIdx.x == 0) blockcnt[size_t(blockIdx.y) * nblocks + blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
-// The same wave-per-word structure for SET / RANGE terms (mask_sets.hpp; docs/DESIGN_flat.md 4.1m): a term is {col, lo, hi, flags,
-// bitmap}.  A row without a value (LABEL_NONE, or a null column) matches iff the term has TERM_NONE, whatever TERM_NEGATE says; a
-// labelled row is inside when lo <= v <= hi and, with a bitmap, bit (v - lo) of it is set, and matches when inside != TERM_NEGATE.
+// A conjunction of `column == code` terms (docs/DESIGN_flat.md 4.1l).  A lane loads its row's value of every term column (4 B per lane,
+// 256 B per wave and term, contiguous) and ANDs the comparisons.  A null column (never written) reads as LABEL_NONE for every row; zero
+// terms allow every row.
+__device__ __forceinline__ bool MaskEq::operator()(const MaskJob &job, uint64_t row, bool in) const {
+    bool ok = in;
+    for (uint32_t t = job.t0; t < job.t1; t++) {  // (wave-uniform)
+        const MaskTerm tm = terms[t];
+        const uint32_t v = (tm.col && in) ? tm.col[row] : LABEL_NONE;
+        ok = ok && v == tm.code;
+    }
+    return ok;
+}
+
+// SET / RANGE terms (mask_sets.hpp; docs/DESIGN_flat.md 4.1m): a term is {col, lo, hi, flags, bitmap}.  A row without a value
+// (LABEL_NONE, or a null column) matches iff the term has TERM_NONE, whatever TERM_NEGATE says; a labelled row is inside when
+// lo <= v <= hi and, with a bitmap, bit (v - lo) of it is set, and matches when inside != TERM_NEGATE.
 // Both loads are selects: a lane at or past n reads no column, and a lane reads a bitmap word only after ITS OWN range test passed, so
 // (v - lo) >> 6 is below the bitmap's ceil((hi - lo + 1) / 64) words.  The bitmap read is a per-lane gather of one 8-byte word from a
 // block of at most a few KiB that every wave of the mask re-reads: it stays in cache, and LDS staging per 256-row workgroup would move
@@ -93,42 +102,22 @@ __device__ __forceinline__ bool set_term_match(const SetTerm tm, uint64_t row, b
     inside = inside && ((bw >> (off & 63)) & 1);
     return labelled ? inside != bool(tm.flags & TERM_NEGATE) : bool(tm.flags & TERM_NONE);
 }
-__global__ __launch_bounds__(256) void k_mask_where_sets(const SetTerm *__restrict__ terms, const MaskJob *__restrict__ jobs, uint64_t n,
-                                                         uint32_t nwords, uint32_t nblocks, uint32_t *__restrict__ blockcnt) {
-    __shared__ uint32_t s_cnt[4];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const MaskJob job = jobs[blockIdx.y];
-    const uint32_t word = blockIdx.x * 4 + wave;
-    const uint64_t row = uint64_t(word) * 64 + lane;
-    const bool in = row < n;
+// a conjunction of such terms
+__device__ __forceinline__ bool MaskAll::operator()(const MaskJob &job, uint64_t row, bool in) const {
     bool ok = in;
     for (uint32_t t = job.t0; t < job.t1; t++) {  // (wave-uniform)
         ok = ok && set_term_match(terms[t], row, in);
     }
-    const uint64_t w = __ballot(ok);
-    if (lane == 0) {
-        if (word < nwords) job.bits[word] = w;
-        s_cnt[wave] = (uint32_t)__popcll(w);  // (a word at or past nwords has no row below n: 0)
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) blockcnt[size_t(blockIdx.y) * nblocks + blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    return ok;
 }
 
-// An OR of up to MASK_MAX_CLAUSES such conjunctions (mask_any.hpp; docs/DESIGN_flat.md 4.1o): the same wave, word and ballot, with an
-// outer loop over the mask's clauses [job.t0, job.t1) of the clause table -- clause c is terms [clims[c], clims[c + 1]).  Both loops are
-// wave-uniform.  okc = in-range AND every term of the clause (set_term_match: the loads keep their two rules), any |= okc; rows at and
-// past n are false in every clause, so the tail bits stay clear; a mask without clauses is empty, a clause without terms allows every
-// row.  A column that several clauses name is re-read from cache.  (A wave-uniform exit from the clause loop once every in-range lane
-// is allowed was measured and bought nothing: docs/DESIGN_flat.md 4.1o.)
-__global__ __launch_bounds__(256) void k_mask_where_any(const SetTerm *__restrict__ terms, const uint32_t *__restrict__ clims,
-                                                        const MaskJob *__restrict__ jobs, uint64_t n, uint32_t nwords, uint32_t nblocks,
-                                                        uint32_t *__restrict__ blockcnt) {
-    __shared__ uint32_t s_cnt[4];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const MaskJob job = jobs[blockIdx.y];
-    const uint32_t word = blockIdx.x * 4 + wave;
-    const uint64_t row = uint64_t(word) * 64 + lane;
-    const bool in = row < n;
+// An OR of up to MASK_MAX_CLAUSES such conjunctions (mask_any.hpp; docs/DESIGN_flat.md 4.1o): an outer loop over the mask's clauses
+// [job.t0, job.t1) of the clause table -- clause c is terms [clims[c], clims[c + 1]).  Both loops are wave-uniform.  okc = in-range AND
+// every term of the clause (set_term_match: the loads keep their two rules), any |= okc; rows at and past n are false in every clause,
+// so the tail bits stay clear; a mask without clauses is empty, a clause without terms allows every row.  A column that several
+// clauses name is re-read from cache.  (A wave-uniform exit from the clause loop once every in-range lane is allowed was measured and
+// bought nothing: docs/DESIGN_flat.md 4.1o.)
+__device__ __forceinline__ bool MaskAny::operator()(const MaskJob &job, uint64_t row, bool in) const {
     bool any = false;
     for (uint32_t c = job.t0; c < job.t1; c++) {  // (wave-uniform)
         const uint32_t t1 = clims[c + 1];
@@ -136,13 +125,7 @@ __global__ __launch_bounds__(256) void k_mask_where_any(const SetTerm *__restric
         for (uint32_t t = clims[c]; t < t1; t++) okc = okc && set_term_match(terms[t], row, in);  // (wave-uniform)
         any = any || okc;
     }
-    const uint64_t w = __ballot(any);
-    if (lane == 0) {
-        if (word < nwords) job.bits[word] = w;
-        s_cnt[wave] = (uint32_t)__popcll(w);  // (a word at or past nwords has no row below n: 0)
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) blockcnt[size_t(blockIdx.y) * nblocks + blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    return any;
 }
 
 // AND / OR of up to MASK_COMBINE_MAX finished masks, input i complemented first when bit i of a.invert is set.  One thread per entry of
@@ -201,7 +184,7 @@ __global__ __launch_bounds__(256) void k_mask_scan(uint32_t *__restrict__ blockc
     if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
 
-// Same grid as k_mask_where.  A wave re-reads its word; the lane whose bit is set writes its row at
+// Same grid as k_mask_rows.  A wave re-reads its word; the lane whose bit is set writes its row at
 //   blockoff[mask][block] + popcounts of the block's earlier words + popcount(word & lanes below):
 // positions ascend with the row, so the allow-list is ascending without a sort.  ids[mask] holds exactly totals[mask] entries.
 __global__ __launch_bounds__(256) void k_mask_ids(const MaskJob *__restrict__ jobs, uint32_t *const *__restrict__ ids, uint32_t nwords,
@@ -218,27 +201,16 @@ __global__ __launch_bounds__(256) void k_mask_ids(const MaskJob *__restrict__ jo
     if ((w >> lane) & 1) out[off + (uint32_t)__popcll(w & ((1ull << lane) - 1))] = word * 64 + lane;
 }
 
-void launch_mask_where(const MaskTerm *terms, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals,
-                       hipStream_t s) {
+template <class Pred>
+void launch_mask_rows(Pred pred, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals, hipStream_t s) {
     const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
     if (n_masks == 0 || nblocks == 0) return;
-    hipLaunchKernelGGL(k_mask_where, dim3(nblocks, n_masks), dim3(256), 0, s, terms, jobs, n, nwords, nblocks, blockcnt);
+    hipLaunchKernelGGL(k_mask_rows<Pred>, dim3(nblocks, n_masks), dim3(256), 0, s, pred, jobs, n, nwords, nblocks, blockcnt);
     hipLaunchKernelGGL(k_mask_scan, dim3(n_masks), dim3(256), 0, s, blockcnt, nblocks, totals);
 }
-void launch_mask_where_sets(const SetTerm *terms, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals,
-                            hipStream_t s) {
-    const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
-    if (n_masks == 0 || nblocks == 0) return;
-    hipLaunchKernelGGL(k_mask_where_sets, dim3(nblocks, n_masks), dim3(256), 0, s, terms, jobs, n, nwords, nblocks, blockcnt);
-    hipLaunchKernelGGL(k_mask_scan, dim3(n_masks), dim3(256), 0, s, blockcnt, nblocks, totals);
-}
-void launch_mask_where_any(const SetTerm *terms, const uint32_t *clims, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt,
-                           uint32_t *totals, hipStream_t s) {
-    const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
-    if (n_masks == 0 || nblocks == 0) return;
-    hipLaunchKernelGGL(k_mask_where_any, dim3(nblocks, n_masks), dim3(256), 0, s, terms, clims, jobs, n, nwords, nblocks, blockcnt);
-    hipLaunchKernelGGL(k_mask_scan, dim3(n_masks), dim3(256), 0, s, blockcnt, nblocks, totals);
-}
+template void launch_mask_rows(MaskEq, const MaskJob *, uint32_t, uint64_t, uint32_t *, uint32_t *, hipStream_t);
+template void launch_mask_rows(MaskAll, const MaskJob *, uint32_t, uint64_t, uint32_t *, uint32_t *, hipStream_t);
+template void launch_mask_rows(MaskAny, const MaskJob *, uint32_t, uint64_t, uint32_t *, uint32_t *, hipStream_t);
 void launch_mask_combine(const MaskCombine &a, uint64_t *out, uint64_t n, uint32_t *blockcnt, uint32_t *totals, hipStream_t s) {
     const uint32_t nwords = (uint32_t)((n + 63) / 64), nblocks = mask_where_blocks(n);
     if (nblocks == 0) return;
@@ -252,7 +224,7 @@ void launch_mask_ids(const MaskJob *jobs, uint32_t *const *ids, uint32_t n_masks
 }
 
 // ---- one column grouped by code (mask_partition.hpp; docs/DESIGN_flat.md 4.1p) -----------------------------------------------------------
-// The masks of up to PART_MAX_CHUNK DISTINCT codes of ONE column in one read of it: the grid over words of k_mask_where with grid.y == 1.
+// The masks of up to PART_MAX_CHUNK DISTINCT codes of ONE column in one read of it: the grid over words of k_mask_rows with grid.y == 1.
 // The workgroup stages the chunk's table -- the codes ascending, and for each the mask (slot) it belongs to -- in LDS; a lane loads its
 // row's code once and binary-searches it (mask_partition_find), which gives it one slot or none.  The wave then walks its distinct
 // slots: the slot of the first pending lane (uniform), the ballot of "my slot is that one" IS that mask's word, lane 0 stores it and adds
@@ -260,7 +232,7 @@ void launch_mask_ids(const MaskJob *jobs, uint32_t *const *ids, uint32_t n_masks
 // The bit words and the counts are zero before the launch (launch_mask_partition clears them), so every word no wave writes is already
 // right; rows at and past n have no slot, so the tail bits stay clear; a null column is LABEL_NONE in every row without a load.  The
 // four waves of a block may add to one count: integer adds, the sum does not depend on their order.  blockcnt then holds what
-// k_mask_where leaves there, so k_mask_scan and k_mask_ids follow unchanged.
+// k_mask_rows leaves there, so k_mask_scan and k_mask_ids follow unchanged.
 __global__ __launch_bounds__(256) void k_mask_partition(const uint32_t *__restrict__ col, const uint32_t *__restrict__ table, uint32_t nb,
                                                         const MaskJob *__restrict__ jobs, uint64_t n, uint32_t nwords, uint32_t nblocks,
                                                         uint32_t *__restrict__ blockcnt) {

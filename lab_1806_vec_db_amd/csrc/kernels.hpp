@@ -357,7 +357,7 @@ void launch_mask_rowc(const float *rowc, const uint64_t *bits, uint64_t n, uint6
 void launch_tau_clamp(float *tau, uint32_t nq, hipStream_t s);
 // dist[q * ld + i] = NaN for the rows i < n whose bit is clear
 void launch_mask_dense_nan(float *dist, uint64_t ld, uint64_t n, uint32_t nq, const uint64_t *bits, hipStream_t s);
-// k_labels.hip: label columns (Index::d_labels) and the row masks built from them on the device (Index::masks_where)
+// k_labels.hip: label columns (Index::d_labels) and the row masks built from them on the device (index_masks.hip)
 constexpr uint32_t LABEL_COLUMNS = 16;       // VDB_LABEL_COLUMNS
 constexpr uint32_t LABEL_NONE = 0xFFFFFFFFu;  // VDB_LABEL_NONE: a row without a value in that column
 constexpr uint32_t MASK_MAX_TERMS = 8;        // VDB_MASK_MAX_TERMS
@@ -396,17 +396,25 @@ void launch_labels_scatter(const LabelCols &cols, const void *ids, bool ids_u64,
 void launch_labels_set_mask(const LabelSet &set, const uint32_t *ids, uint64_t m, int num_cu, uint32_t max_blocks, hipStream_t s);
 // workgroups per mask of the mask kernels = entries per mask of blockcnt: four 64-row words each
 inline uint32_t mask_where_blocks(uint64_t n) { return (uint32_t)(((n + 63) / 64 + 3) / 4); }
-// bit words of n_masks masks over rows [0, n) from their terms, then blockcnt [n_masks][mask_where_blocks(n)] = exclusive prefix of the
-// allowed rows per block and totals[g] = allowed rows of mask g  (k_mask_where + k_mask_scan; n_masks <= 65535)
-void launch_mask_where(const MaskTerm *terms, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals,
-                       hipStream_t s);
-// the same for set / range terms (k_mask_where_sets + k_mask_scan; the term table of mask_sets.hpp, bitmaps resident on the device)
-void launch_mask_where_sets(const SetTerm *terms, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals,
-                            hipStream_t s);
-// the same for an OR of conjunctions (k_mask_where_any + k_mask_scan; mask_any.hpp): jobs[g].t0 / t1 = the mask's clauses in the clause
-// table clims, clims[c] .. clims[c + 1] = the clause's terms
-void launch_mask_where_any(const SetTerm *terms, const uint32_t *clims, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt,
-                           uint32_t *totals, hipStream_t s);
+// The three predicates a mask is built from (k_mask_rows<Pred>; kernel argument, by value; the bodies are in k_labels.hip).  A job's
+// [t0, t1) indexes `terms` -- for MaskAny the clause table clims, whose clims[c] .. clims[c + 1] are the clause's terms.
+struct MaskEq {  // every `column == code` term (Index::masks_where)
+    const MaskTerm *terms;
+    __device__ bool operator()(const MaskJob &job, uint64_t row, bool in) const;
+};
+struct MaskAll {  // every set / range term (Index::masks_where_sets; the term table of mask_sets.hpp, bitmaps resident on the device)
+    const SetTerm *terms;
+    __device__ bool operator()(const MaskJob &job, uint64_t row, bool in) const;
+};
+struct MaskAny {  // every term of some clause (Index::masks_where_any; mask_any.hpp)
+    const SetTerm *terms;
+    const uint32_t *clims;
+    __device__ bool operator()(const MaskJob &job, uint64_t row, bool in) const;
+};
+// bit words of n_masks masks over rows [0, n) from their jobs under pred, then blockcnt [n_masks][mask_where_blocks(n)] = exclusive prefix
+// of the allowed rows per block and totals[g] = allowed rows of mask g  (k_mask_rows<Pred> + k_mask_scan; n_masks <= 65535; the three above)
+template <class Pred>
+void launch_mask_rows(Pred pred, const MaskJob *jobs, uint32_t n_masks, uint64_t n, uint32_t *blockcnt, uint32_t *totals, hipStream_t s);
 // out = AND / OR over the bit words of n_in finished masks over the same n rows, input i complemented first when bit i of invert is set;
 // bits at and past n clear; blockcnt / totals as above for the one mask  (k_mask_combine + k_mask_scan)
 constexpr uint32_t MASK_COMBINE_MAX = 8;
@@ -417,12 +425,12 @@ struct MaskCombine {  // (kernel argument, by value)
     int op;
 };
 void launch_mask_combine(const MaskCombine &a, uint64_t *out, uint64_t n, uint32_t *blockcnt, uint32_t *totals, hipStream_t s);
-// ids[g][0 .. totals[g]) = the allowed rows of mask g, ascending (k_mask_ids; after launch_mask_where on the same stream)
+// ids[g][0 .. totals[g]) = the allowed rows of mask g, ascending (k_mask_ids; after launch_mask_rows on the same stream)
 void launch_mask_ids(const MaskJob *jobs, uint32_t *const *ids, uint32_t n_masks, uint64_t n, const uint32_t *blockoff, hipStream_t s);
 // One column grouped by code (mask_partition.hpp; k_mask_partition, k_label_counts).  table = the chunk's nb (<= PART_MAX_CHUNK) distinct
 // codes ascending, then for each the mask (index into jobs) it belongs to: 2 nb u32 on the device.
 static_assert(PART_LABEL_COLUMNS == LABEL_COLUMNS && PART_LABEL_NONE == LABEL_NONE, "mask_partition.hpp and kernels.hpp agree");
-// The bit words of the nb masks "col == code" and blockcnt / totals as launch_mask_where leaves them (k_mask_partition + k_mask_scan).
+// The bit words of the nb masks "col == code" and blockcnt / totals as launch_mask_rows leaves them (k_mask_partition + k_mask_scan).
 // The caller has zeroed the bit words of every mask and blockcnt [nb][mask_where_blocks(n)] on the same stream; col == nullptr: a
 // column never written.
 void launch_mask_partition(const uint32_t *col, const uint32_t *table, uint32_t nb, const MaskJob *jobs, uint64_t n, uint32_t *blockcnt,

@@ -1,4 +1,4 @@
-// mask_any.hpp -- the host part of the OR-of-conjunctions masks over label columns (Index::masks_where_any, k_mask_where_any): checks the
+// mask_any.hpp -- the host part of the OR-of-conjunctions masks over label columns (Index::masks_where_any, MaskAny of k_labels.hip): checks the
 // arguments of vdb_mask_create_where_any* and lays out the clause table over the term table of mask_sets.hpp.  Host only: no HIP, no
 // other header of the library but mask_sets.hpp for SetTerm (tests/cpp/mask_any_asan.cpp builds it on its own).  docs/DESIGN_flat.md 4.1o.
 //
@@ -30,25 +30,15 @@ inline std::string mask_any_check(const uint64_t *mask_lims, const uint64_t *cla
     if (n_masks == 0) return "";
     if (!mask_lims) return "null argument";
     if (n_masks >= (1ull << 28)) return "too many masks for one call";
-    if (mask_lims[0] != 0) return "mask clauses: mask_lims[0] must be 0";
-    for (uint64_t g = 0; g < n_masks; g++) {
-        if (mask_lims[g + 1] < mask_lims[g]) return "mask clauses: mask_lims must not decrease (mask " + std::to_string(g) + ")";
-        if (mask_lims[g + 1] - mask_lims[g] > MASK_MAX_CLAUSES)
-            return "mask clauses: mask " + std::to_string(g) + " has " + std::to_string(mask_lims[g + 1] - mask_lims[g]) +
-                   " clauses, at most " + std::to_string(MASK_MAX_CLAUSES) + " are supported";
-    }
+    std::string bad = mask_lims_check(mask_lims, n_masks, MASK_MAX_CLAUSES, "mask clauses", "mask_lims", "mask", "clauses");
+    if (!bad.empty()) return bad;
     const uint64_t n_clauses = mask_lims[n_masks];
     if (n_clauses == 0) return "";  // every mask is empty: nothing else is read
     if (n_clauses >= (1ull << 28)) return "too many clauses for one call";  // (so a term index fits 32 bits)
     if (!clause_lims) return "null argument";
-    if (clause_lims[0] != 0) return "mask clauses: clause_lims[0] must be 0";
-    for (uint64_t c = 0; c < n_clauses; c++) {
-        if (clause_lims[c + 1] < clause_lims[c]) return "mask clauses: clause_lims must not decrease (clause " + std::to_string(c) + ")";
-        if (clause_lims[c + 1] - clause_lims[c] > SETS_MAX_TERMS)
-            return "mask clauses: clause " + std::to_string(c) + " has " + std::to_string(clause_lims[c + 1] - clause_lims[c]) +
-                   " terms, at most " + std::to_string(SETS_MAX_TERMS) + " are supported";
-    }
-    const std::string bad = mask_sets_check(clause_lims, columns, lo, hi, flags, set_lims, set_words, n_clauses, n_terms_out, set_words_out);
+    bad = mask_lims_check(clause_lims, n_clauses, SETS_MAX_TERMS, "mask clauses", "clause_lims", "clause", "terms");
+    if (!bad.empty()) return bad;
+    bad = mask_sets_check(clause_lims, columns, lo, hi, flags, set_lims, set_words, n_clauses, n_terms_out, set_words_out);
     if (!bad.empty()) return bad;
     *n_clauses_out = n_clauses;
     return "";
@@ -57,12 +47,16 @@ inline std::string mask_any_check(const uint64_t *mask_lims, const uint64_t *cla
 struct AnyLayout {  // byte offsets of the three parts of the device buffer of a checked call
     size_t clause_off, sets_off, total;
 };
-inline AnyLayout mask_any_buffer(uint64_t n_clauses, uint64_t n_terms, uint64_t n_set_words) {
+// clause_entries u32 behind the term table: 0 for a masks_where_sets call, whose bitmaps follow the terms directly
+inline AnyLayout mask_terms_buffer(uint64_t n_terms, uint64_t clause_entries, uint64_t n_set_words) {
     AnyLayout L;
     L.clause_off = size_t(n_terms ? n_terms : 1) * sizeof(SetTerm);  // (a multiple of 8)
-    L.sets_off = L.clause_off + (size_t(n_clauses + 1) * sizeof(uint32_t) + 7) / 8 * 8;
+    L.sets_off = L.clause_off + (size_t(clause_entries) * sizeof(uint32_t) + 7) / 8 * 8;
     L.total = L.sets_off + size_t(n_set_words) * sizeof(uint64_t);
     return L;
+}
+inline AnyLayout mask_any_buffer(uint64_t n_clauses, uint64_t n_terms, uint64_t n_set_words) {
+    return mask_terms_buffer(n_terms, n_clauses + 1, n_set_words);
 }
 // the clause table: out[c] = first term of clause c, out[n_clauses] = n_terms (the term table itself is mask_sets_layout's)
 inline void mask_any_layout(const uint64_t *clause_lims, uint64_t n_clauses, std::vector<uint32_t> &out) {
@@ -70,7 +64,7 @@ inline void mask_any_layout(const uint64_t *clause_lims, uint64_t n_clauses, std
     for (uint64_t c = 0; n_clauses && c <= n_clauses; c++) out[c] = (uint32_t)clause_lims[c];
 }
 
-// The match of row `row` against clauses [c0, c1) of a laid-out call, as k_mask_where_any evaluates it with the columns and bitmaps
+// The match of row `row` against clauses [c0, c1) of a laid-out call, as the kernel (MaskAny, k_labels.hip) evaluates it with the columns and bitmaps
 // readable on the host (the restatement the CPU test checks by brute force).
 inline bool mask_any_match(const SetTerm *terms, const uint32_t *clause_tab, uint32_t c0, uint32_t c1, uint64_t row) {
     bool any = false;

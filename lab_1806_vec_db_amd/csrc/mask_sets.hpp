@@ -1,6 +1,7 @@
-// mask_sets.hpp -- the host part of the set / range predicates over label columns (Index::masks_where_sets, k_mask_where_sets): checks
-// the arguments of vdb_mask_create_where_sets* and lays out the device term table over the packed bitmap block.  Host only: no HIP, no
-// other header of the library (tests/cpp/mask_sets_asan.cpp builds it on its own).  docs/DESIGN_flat.md 4.1m.
+// mask_sets.hpp -- the host part of the label predicates of one conjunction per mask: checks the arguments of the equality terms
+// (vdb_mask_create_where*; Index::masks_where, MaskEq) and of the set / range terms (vdb_mask_create_where_sets*; Index::masks_where_sets,
+// MaskAll) and lays out the device term table over the packed bitmap block.  Host only: no HIP, no other header of the library
+// (tests/cpp/mask_terms_asan.cpp and mask_sets_asan.cpp build it on its own).  docs/DESIGN_flat.md 4.1l, 4.1m.
 //
 // A term is {column, lo, hi, flags, bitmap}.  A row whose label in the column is v matches it
 //  - when v == LABEL_NONE (no value, or a column never written): iff flags has TERM_NONE -- TERM_NEGATE never inverts this case;
@@ -30,6 +31,43 @@ struct SetTerm {            // one entry of the device term table (32 B)
 // 64-bit words of a bitmap over the codes [lo, hi] (lo <= hi): up to 2^26, so never in 32-bit arithmetic
 inline uint64_t mask_sets_span_words(uint32_t lo, uint32_t hi) { return (uint64_t(hi) - uint64_t(lo) + 1 + 63) / 64; }
 
+// The check every limits array of the mask calls gets: lims[0 .. n_groups] starts at 0, does not decrease, and no group
+// [lims[g], lims[g + 1]) has more than `cap` entries.  Empty string: fine; otherwise "<what>: ..." with the array's name and the nouns
+// of a group and of its entries.  Reads lims[g + 1] only after lims[g] passed.
+inline std::string mask_lims_check(const uint64_t *lims, uint64_t n_groups, uint64_t cap, const char *what, const char *name, const char *group,
+                                   const char *entries) {
+    const std::string w = std::string(what) + ": ";
+    if (lims[0] != 0) return w + name + "[0] must be 0";
+    for (uint64_t g = 0; g < n_groups; g++) {
+        if (lims[g + 1] < lims[g]) return w + name + " must not decrease (" + group + " " + std::to_string(g) + ")";
+        if (lims[g + 1] - lims[g] > cap)
+            return w + group + " " + std::to_string(g) + " has " + std::to_string(lims[g + 1] - lims[g]) + " " + entries + ", at most " +
+                   std::to_string(cap) + " are supported";
+    }
+    return "";
+}
+
+// Checks everything vdb_mask_create_where_many states about its arguments (`out` = where the masks go, only tested for null).  Empty
+// string: fine, and *n_terms_out holds the number of terms of the call; otherwise the message.  term_lims is read before the term arrays,
+// those up to term_lims[n_masks], `codes` never.
+inline std::string mask_terms_check(const uint64_t *term_lims, const uint32_t *columns, const uint32_t *codes, uint64_t n_masks, const void *out,
+                                    uint64_t *n_terms_out) {
+    *n_terms_out = 0;
+    if (n_masks == 0) return "";
+    if (!term_lims || !out) return "null argument";
+    if (n_masks >= (1ull << 28)) return "too many masks for one call";
+    const std::string bad = mask_lims_check(term_lims, n_masks, SETS_MAX_TERMS, "mask terms", "term_lims", "mask", "terms");
+    if (!bad.empty()) return bad;
+    const uint64_t n_terms = term_lims[n_masks];
+    if (n_terms && (!columns || !codes)) return "null argument";
+    for (uint64_t t = 0; t < n_terms; t++)
+        if (columns[t] >= SETS_LABEL_COLUMNS)
+            return "mask terms: column " + std::to_string(columns[t]) + " (term " + std::to_string(t) + "), an index has " +
+                   std::to_string(SETS_LABEL_COLUMNS);
+    *n_terms_out = n_terms;
+    return "";
+}
+
 // Checks everything vdb_mask_create_where_sets_many states about its arguments.  Empty string: fine, and *n_terms_out / *set_words_out
 // hold the number of terms and of bitmap words of the call; otherwise the message.  Reads nothing past what the limits allow: term_lims
 // before the term arrays, set_lims entry by entry, set_words never.
@@ -40,13 +78,8 @@ inline std::string mask_sets_check(const uint64_t *term_lims, const uint32_t *co
     if (n_masks == 0) return "";
     if (!term_lims) return "null argument";
     if (n_masks >= (1ull << 28)) return "too many masks for one call";
-    if (term_lims[0] != 0) return "mask terms: term_lims[0] must be 0";
-    for (uint64_t g = 0; g < n_masks; g++) {
-        if (term_lims[g + 1] < term_lims[g]) return "mask terms: term_lims must not decrease (mask " + std::to_string(g) + ")";
-        if (term_lims[g + 1] - term_lims[g] > SETS_MAX_TERMS)
-            return "mask terms: mask " + std::to_string(g) + " has " + std::to_string(term_lims[g + 1] - term_lims[g]) + " terms, at most " +
-                   std::to_string(SETS_MAX_TERMS) + " are supported";
-    }
+    const std::string bad = mask_lims_check(term_lims, n_masks, SETS_MAX_TERMS, "mask terms", "term_lims", "mask", "terms");
+    if (!bad.empty()) return bad;
     const uint64_t n_terms = term_lims[n_masks];
     if (n_terms == 0) return "";
     if (!columns || !lo || !hi || !flags) return "null argument";
@@ -96,8 +129,8 @@ inline void mask_sets_layout(const uint32_t *columns, const uint32_t *lo, const 
     }
 }
 
-// The match of one laid-out term against a label value, as k_mask_where_sets evaluates it with `bitmap` readable on the host (the
-// restatement the CPU test checks by brute force; the kernel has its own copy of these four lines).
+// The match of one laid-out term against a label value, as set_term_match of k_labels.hip evaluates it with `bitmap` readable on the
+// host (the restatement the CPU test checks by brute force; the kernel has its own copy of these four lines).
 inline bool mask_sets_match(const SetTerm &tm, uint32_t v) {
     if (v == SETS_LABEL_NONE) return (tm.flags & TERM_NONE) != 0;
     bool inside = tm.lo <= v && v <= tm.hi;

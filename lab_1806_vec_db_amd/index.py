@@ -111,6 +111,19 @@ def _set_terms_arrays(terms):
             np.array(lims, dtype=np.uint64), words)
 
 
+def _set_terms_ptrs(arrays):
+    """the pointer tail of a set-term call for _set_terms_arrays' tuple (which the caller keeps alive): cols, lo, hi, flags, lims, words"""
+    cols, lo, hi, flags, lims, words = arrays
+    return (_ptr(cols, L.u32p), _ptr(lo, L.u32p), _ptr(hi, L.u32p), _ptr(flags, L.u32p), _ptr(lims, L.u64p), _ptr(words, L.u64p))
+
+
+def _lims(lists) -> np.ndarray:
+    """the u64 limits of a list of lists: list g is entries [lims[g], lims[g + 1]) of their concatenation"""
+    lims = np.zeros(len(lists) + 1, dtype=np.uint64)
+    lims[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64)
+    return lims
+
+
 class RowMask:
     """An allow-list over the rows of one GpuIndex (vdb_mask): made by GpuIndex.make_mask, valid until rows are added to or removed
     from the index, closed before the index is."""
@@ -498,12 +511,16 @@ class GpuIndex:
         """one mask per entry of `list_of_terms` (each a sequence of (column, code)) in ONE library call (vdb_mask_create_where_many);
         all-or-nothing: an invalid entry raises and no mask is made"""
         lists = [list(t) for t in list_of_terms]
-        lims = np.zeros(len(lists) + 1, dtype=np.uint64)
-        lims[1:] = np.cumsum([len(t) for t in lists], dtype=np.uint64)
+        lims = _lims(lists)
         cols, codes = _terms_arrays([tm for t in lists for tm in t])
-        arr = (L.vp * max(len(lists), 1))()
-        L.check(self._lib.vdb_mask_create_where_many(self._h, _ptr(lims, L.u64p), _ptr(cols, L.u32p), _ptr(codes, L.u32p), len(lists), arr))
-        return [RowMask.from_handle(self, arr[g]) for g in range(len(lists))]
+        return self._masks_many(len(lists), lambda arr: self._lib.vdb_mask_create_where_many(
+            self._h, _ptr(lims, L.u64p), _ptr(cols, L.u32p), _ptr(codes, L.u32p), len(lists), arr))
+
+    def _masks_many(self, count: int, call, n: int | None = None) -> list[RowMask]:
+        """the masks of a library call that fills `count` handles or none: call(handle array) -> status.  `n` as in from_handle"""
+        arr = (L.vp * max(count, 1))()
+        L.check(call(arr))
+        return [RowMask.from_handle(self, arr[g], n) for g in range(count)]
 
     @staticmethod
     def _codes_array(codes) -> np.ndarray:
@@ -520,10 +537,8 @@ class GpuIndex:
         in any order, LABEL_NONE (the unlabelled rows) among them; a duplicate raises and no mask is made.  The masks of a call share
         their device memory by chunks of 1024: it is returned when the last mask of a chunk is closed."""
         c = self._codes_array(codes)
-        arr = (L.vp * max(c.shape[0], 1))()
-        L.check(self._lib.vdb_mask_create_partition(self._h, int(column), _ptr(c, L.u32p), c.shape[0], arr))
-        n = len(self)
-        return [RowMask.from_handle(self, arr[g], n) for g in range(c.shape[0])]
+        return self._masks_many(c.shape[0], lambda arr: self._lib.vdb_mask_create_partition(self._h, int(column), _ptr(c, L.u32p), c.shape[0], arr),
+                                len(self))
 
     def label_counts(self, column: int, codes, mask: RowMask | None = None) -> np.ndarray:
         """counts[j] = the number of rows -- of the rows `mask` allows, when one is given -- whose label in `column` equals codes[j], as
@@ -537,52 +552,41 @@ class GpuIndex:
     def make_mask_where_sets(self, terms) -> RowMask:
         """the mask of the rows that match EVERY LabelTerm of `terms` -- set and range predicates over the label columns, built on the
         device (vdb_mask_create_where_sets); no terms: every row"""
-        cols, lo, hi, flags, lims, words = _set_terms_arrays(terms)
+        a = _set_terms_arrays(terms)
         h = L.vp()
-        L.check(self._lib.vdb_mask_create_where_sets(self._h, _ptr(cols, L.u32p), _ptr(lo, L.u32p), _ptr(hi, L.u32p), _ptr(flags, L.u32p),
-                                                     _ptr(lims, L.u64p), _ptr(words, L.u64p), cols.shape[0], C.byref(h)))
+        L.check(self._lib.vdb_mask_create_where_sets(self._h, *_set_terms_ptrs(a), a[0].shape[0], C.byref(h)))
         return RowMask.from_handle(self, h)
 
     def make_masks_where_sets(self, list_of_terms) -> list[RowMask]:
         """one mask per entry of `list_of_terms` (each a sequence of LabelTerm) in ONE library call (vdb_mask_create_where_sets_many);
         all-or-nothing: an invalid entry raises and no mask is made"""
         lists = [list(t) for t in list_of_terms]
-        tlims = np.zeros(len(lists) + 1, dtype=np.uint64)
-        tlims[1:] = np.cumsum([len(t) for t in lists], dtype=np.uint64)
-        cols, lo, hi, flags, lims, words = _set_terms_arrays([tm for t in lists for tm in t])
-        arr = (L.vp * max(len(lists), 1))()
-        L.check(self._lib.vdb_mask_create_where_sets_many(self._h, _ptr(tlims, L.u64p), _ptr(cols, L.u32p), _ptr(lo, L.u32p), _ptr(hi, L.u32p),
-                                                          _ptr(flags, L.u32p), _ptr(lims, L.u64p), _ptr(words, L.u64p), len(lists), arr))
-        return [RowMask.from_handle(self, arr[g]) for g in range(len(lists))]
+        tlims = _lims(lists)
+        a = _set_terms_arrays([tm for t in lists for tm in t])
+        return self._masks_many(len(lists), lambda arr: self._lib.vdb_mask_create_where_sets_many(
+            self._h, _ptr(tlims, L.u64p), *_set_terms_ptrs(a), len(lists), arr))
 
     def make_mask_where_any(self, clauses) -> RowMask:
         """the mask of the rows that match every LabelTerm of SOME clause of `clauses` (a sequence of sequences of LabelTerm) -- an OR of
         conjunctions over the label columns, built on the device in one pass (vdb_mask_create_where_any).  No clauses: the empty mask;
         a clause without terms: every row"""
         cl = [list(c) for c in clauses]
-        clims = np.zeros(len(cl) + 1, dtype=np.uint64)
-        clims[1:] = np.cumsum([len(c) for c in cl], dtype=np.uint64)
-        cols, lo, hi, flags, lims, words = _set_terms_arrays([tm for c in cl for tm in c])
+        clims = _lims(cl)
+        a = _set_terms_arrays([tm for c in cl for tm in c])
         h = L.vp()
-        L.check(self._lib.vdb_mask_create_where_any(self._h, _ptr(clims, L.u64p), len(cl), _ptr(cols, L.u32p), _ptr(lo, L.u32p), _ptr(hi, L.u32p),
-                                                    _ptr(flags, L.u32p), _ptr(lims, L.u64p), _ptr(words, L.u64p), C.byref(h)))
+        L.check(self._lib.vdb_mask_create_where_any(self._h, _ptr(clims, L.u64p), len(cl), *_set_terms_ptrs(a), C.byref(h)))
         return RowMask.from_handle(self, h)
 
     def make_masks_where_any(self, list_of_clause_lists) -> list[RowMask]:
         """one mask per entry of `list_of_clause_lists` (each what make_mask_where_any takes) in ONE library call
         (vdb_mask_create_where_any_many); all-or-nothing: an invalid entry raises and no mask is made"""
         masks = [[list(c) for c in clauses] for clauses in list_of_clause_lists]
-        mlims = np.zeros(len(masks) + 1, dtype=np.uint64)
-        mlims[1:] = np.cumsum([len(m) for m in masks], dtype=np.uint64)
+        mlims = _lims(masks)
         cl = [c for m in masks for c in m]
-        clims = np.zeros(len(cl) + 1, dtype=np.uint64)
-        clims[1:] = np.cumsum([len(c) for c in cl], dtype=np.uint64)
-        cols, lo, hi, flags, lims, words = _set_terms_arrays([tm for c in cl for tm in c])
-        arr = (L.vp * max(len(masks), 1))()
-        L.check(self._lib.vdb_mask_create_where_any_many(self._h, _ptr(mlims, L.u64p), _ptr(clims, L.u64p), _ptr(cols, L.u32p), _ptr(lo, L.u32p),
-                                                         _ptr(hi, L.u32p), _ptr(flags, L.u32p), _ptr(lims, L.u64p), _ptr(words, L.u64p),
-                                                         len(masks), arr))
-        return [RowMask.from_handle(self, arr[g]) for g in range(len(masks))]
+        clims = _lims(cl)
+        a = _set_terms_arrays([tm for c in cl for tm in c])
+        return self._masks_many(len(masks), lambda arr: self._lib.vdb_mask_create_where_any_many(
+            self._h, _ptr(mlims, L.u64p), _ptr(clims, L.u64p), *_set_terms_ptrs(a), len(masks), arr))
 
     def combine_masks(self, op, masks, invert=None) -> RowMask:
         """the AND (op "and" / MASK_OP_AND) or OR ("or" / MASK_OP_OR) of 1 .. 8 masks of this index, mask i complemented within the
@@ -755,9 +759,7 @@ class GpuIndex:
         lists = [np.asarray(x, dtype=np.uint64).ravel() for x in lists]
         if nq is not None and len(lists) != nq:
             raise ValueError(f"{len(lists)} id lists for {nq} queries")
-        lims = np.zeros(len(lists) + 1, dtype=np.uint64)
-        if lists:
-            lims[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64)
+        lims = _lims(lists)
         ids = np.concatenate(lists).astype(np.uint64) if lists else np.zeros(0, dtype=np.uint64)
         return lims, np.ascontiguousarray(ids)
 

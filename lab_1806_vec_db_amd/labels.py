@@ -103,7 +103,7 @@ class LabelTerm:
         return np.packbits(bits, bitorder="little").view(np.uint64)
 
     def select(self, values) -> np.ndarray:
-        """the match over an array of u32 labels, in numpy (the arithmetic of k_mask_where_sets, for hosts and tests)"""
+        """the match over an array of u32 labels, in numpy (the arithmetic of k_mask_rows<MaskAll>, for hosts and tests)"""
         v = np.asarray(values, dtype=np.uint32).astype(np.int64)
         inside = (v >= self.lo) & (v <= self.hi)
         if self.codes is not None:

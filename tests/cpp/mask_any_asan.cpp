@@ -114,6 +114,49 @@ int main() {
         uint64_t a, b, c3;
         if (vdb::mask_any_check(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, &a, &b, &c3) != "null argument") fail("null mask_lims");
     }
+    // ---- the limits check the four callers share (mask_lims_check): the equality form, the conjunction form, the masks and the clauses
+    // of this form.  Each is driven through its own check function with limits that start wrong, descend, or pass the cap by one in
+    // group 1; the messages are compared whole with the texts the library has always given.  A limits vector ends where the check
+    // must stop reading. ----
+    {
+        struct Variant {
+            const char *who;
+            uint64_t cap;
+            const char *start, *order, *over;
+        };
+        const Variant variants[4] = {
+            {"equality terms", 8, "mask terms: term_lims[0] must be 0", "mask terms: term_lims must not decrease (mask 1)",
+             "mask terms: mask 1 has 9 terms, at most 8 are supported"},
+            {"set terms", 8, "mask terms: term_lims[0] must be 0", "mask terms: term_lims must not decrease (mask 1)",
+             "mask terms: mask 1 has 9 terms, at most 8 are supported"},
+            {"clauses of a mask", 64, "mask clauses: mask_lims[0] must be 0", "mask clauses: mask_lims must not decrease (mask 1)",
+             "mask clauses: mask 1 has 65 clauses, at most 64 are supported"},
+            {"terms of a clause", 8, "mask clauses: clause_lims[0] must be 0", "mask clauses: clause_lims must not decrease (clause 1)",
+             "mask clauses: clause 1 has 9 terms, at most 8 are supported"},
+        };
+        const std::vector<uint64_t> two_clauses{0, 2};
+        int dummy_out = 0;
+        for (int v = 0; v < 4; v++) {
+            const Variant &V = variants[v];
+            const std::vector<uint64_t> cases[3] = {{1}, {0, 2, 1}, {0, 1, 1 + V.cap + 1}};
+            const char *want[3] = {V.start, V.order, V.over};
+            for (int k = 0; k < 3; k++) {
+                const uint64_t *lims = cases[k].data();
+                uint64_t a = 0, b = 0, c = 0;
+                std::string got;
+                if (v == 0) got = vdb::mask_terms_check(lims, nullptr, nullptr, 2, &dummy_out, &a);
+                if (v == 1) got = vdb::mask_sets_check(lims, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 2, &a, &b);
+                if (v == 2) got = vdb::mask_any_check(lims, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 2, &a, &b, &c);
+                if (v == 3) got = vdb::mask_any_check(two_clauses.data(), lims, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, &a, &b, &c);
+                if (got != want[k] || a || b || c) {
+                    std::printf("FAILED: limits of the %s, case %d: got \"%s\", wanted \"%s\"\n", V.who, k, got.c_str(), want[k]);
+                    std::exit(1);
+                }
+            }
+        }
+        const std::vector<uint64_t> fine{0, 8, 8, 16};  // the cap itself, an empty group
+        if (!vdb::mask_lims_check(fine.data(), 3, 8, "w", "l", "g", "e").empty()) fail("limits at the cap");
+    }
     // ---- every argument error of the conjunction call, through the clause layer ----
     {
         Call c;

@@ -1,5 +1,5 @@
 """GPU: row masks built on the device from an OR of conjunctions of set / range terms over label columns (vdb_mask_create_where_any /
-_many, k_mask_where_any in csrc/k_labels.hip) and the AND / OR / NOT of finished masks (vdb_mask_combine, k_mask_combine).  Every mask
+_many, k_mask_rows<MaskAny> in csrc/k_labels.hip) and the AND / OR / NOT of finished masks (vdb_mask_combine, k_mask_combine).  Every mask
 is read back (vdb_mask_rows) and compared EXACTLY -- bit words and ascending allow-list -- with the mask numpy computes from the label
 arrays by the rule the header states; a mask of one clause is the vdb_mask_create_where_sets mask of its terms; searches under a
 device-built OR mask are compared with the reference's order restricted to the same rows and with the same searches under

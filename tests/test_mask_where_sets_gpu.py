@@ -1,5 +1,5 @@
 """GPU: row masks built on the device from SET and RANGE terms over label columns (vdb_mask_create_where_sets / _many,
-k_mask_where_sets in csrc/k_labels.hip).  Every mask is read back (vdb_mask_rows) and compared EXACTLY -- bit words and ascending
+k_mask_rows<MaskAll> in csrc/k_labels.hip).  Every mask is read back (vdb_mask_rows) and compared EXACTLY -- bit words and ascending
 allow-list -- with the mask numpy computes from the label arrays by the rule the header states; the two documented equivalences with the
 equality terms of vdb_mask_create_where give identical masks; searches under a set mask are compared with the same searches under
 vdb_mask_create's mask of the same rows."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What a row mask of a filter EXPRESSION costs: vdb_mask_create_where_any (k_mask_where_any, one pass over an OR of conjunctions) against
+"""What a row mask of a filter EXPRESSION costs: vdb_mask_create_where_any (k_mask_rows<MaskAny>, one pass over an OR of conjunctions) against
 (a) the one-term equality mask of vdb_mask_create_where -- the yardstick of the mask line --, (b) the same normal form built clause by
 clause with vdb_mask_create_where_sets_many and joined with vdb_mask_combine, and (c) the host loop over the metadata + vdb_mask_create,
 the only path such a filter had before.  Same process, same table, one run.

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What a row mask of a SET or RANGE predicate costs: vdb_mask_create_where_sets (k_mask_where_sets) against the one-term equality mask of
+"""What a row mask of a SET or RANGE predicate costs: vdb_mask_create_where_sets (k_mask_rows<MaskAll>) against the one-term equality mask of
 vdb_mask_create_where -- which reads the same column bytes and is the yardstick -- and against the host loop over the metadata +
 vdb_mask_create, the path such a filter took before.  Same process, same table, one run.
 
