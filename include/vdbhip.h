@@ -656,7 +656,7 @@ int vdb_drop_listed_device(vdb_index *idx, const void *d_ids, const void *d_dist
  * vdb_get_stat "flat_fused_calls", "flat_fused_queries" (fused queries), "flat_fused_lists" (sub-queries) count the two search forms;
  * vdb_prof_get "fuse_lists" times k_fuse_lists.
  * Not covered: distribution-based score fusion, lists from PQ / HNSW / IVF searches (beyond feeding them to vdb_fuse_lists_device),
- * VecSet<u8> indexes, sharded and replica contexts, combination with group_by / mmr_lambda. */
+ * VecSet<u8> indexes, sharded and replica contexts, combination with mmr_lambda (fusion by a label: vdb_flat_knn_fused_groups below). */
 #define VDB_FUSE_RRF 0
 #define VDB_FUSE_MIN 1
 int vdb_fuse_plan(int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, const float *weights, float rrf_c, uint64_t budget,
@@ -671,6 +671,77 @@ int vdb_flat_knn_fused_device(vdb_index *idx, const void *d_queries, const uint6
 int vdb_fuse_lists_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, const uint64_t *lims, uint64_t nq,
                           uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, void *d_out_idx, void *d_out_dist,
                           void *d_out_count, void *stream);
+/* ---- document-level fused Flat search: the lists of several sub-queries joined by the value of a label column ------------------------
+ * Rows are chunks and a label column says which document a chunk belongs to: a question asked as several vectors (paraphrases,
+ * sub-questions, the token vectors of a late-interaction query) ranks DOCUMENTS.  The unit of ranking is a GROUP: all rows that share a
+ * value of label column `column`.
+ *   The lists, the limits `lims`, masks / mask_of, fetch_k, C_s and the knn order (ascending by (distance, id), -0 == +0, every NaN equal
+ *   and last) are exactly those of vdb_flat_knn_fused.
+ *   Group of a row: if the row's code is not VDB_LABEL_NONE its group is that code; an unlabelled row (VDB_LABEL_NONE, or a column never
+ *   written) is a group of its own, as the grouped search always keeps unlabelled rows.  The two key spaces are distinct: unlabelled row 5
+ *   and label code 5 are different groups.
+ *   Per list s and group g: p_s(g) is the smallest position in C_s of a row of g (the first-occurrence rule; in a sorted list that row is
+ *   the group's nearest), r_s(g) that row and d_s(g) its distance; rho_s(g) is the number of distinct groups whose first occurrence lies
+ *   before p_s(g) -- the group's 0-based RANK AMONG GROUPS, not its row position; f_s is the distance of the LAST counted entry of list s
+ *   (position min(count, length) - 1, whatever its id).  A list with no counted entry is SKIPPED in every fold below.  List s is
+ *   truncated when it counts at least trunc_len entries; trunc_len is fetch_k in the search forms and an argument of the list form
+ *   (its ld, usually).  One refinement in the search forms: when fetch_k reaches the longest allowed set among the sub-queries of the
+ *   call (the table, unfiltered; per block of 16384 sub-queries in the host form) every list is whole and none is truncated.
+ *   U_q = the groups that occur in at least one C_s of the fused query.
+ *   Scores: each a strict left fold over s ascending, f32, one rounding per operation, no FMA, no float atomic.
+ *   VDB_FUSE_RRF: acc = +0.0f; for each non-empty list that holds g: den = (float)(rho_s(g) + 1) + c, term = w_s / den, acc = acc + term.
+ *     Descending by score, ties by representative id ascending.
+ *   VDB_FUSE_MIN: the smallest d_s(g) under the knn order, the bits of the first list that attains it; ascending; weights must be NULL.
+ *   VDB_FUSE_SUM (late interaction): acc = +0.0f; for EVERY non-empty list s ascending: term = d_s(g) if C_s holds g, else f_s;
+ *     acc = acc + term.  Ascending, NaN last; weights must be NULL.  A row the list did not fetch is at least as far as f_s, so when
+ *     list s is truncated the score is a LOWER BOUND of the true sum of per-vector best-chunk distances (f32 addition is monotone); it IS
+ *     that sum when no list is truncated.  IEEE 754 leaves the payload of a NaN sum open: a NaN score is reported as 0x7FC00000.
+ *   Representative of a group: the row r_s*(g) of the list that minimises (order key of d_s(g), s).  Ties in MIN and SUM go to the lower
+ *   representative id as well.  Over a column never written every row is a group of its own: MIN is vdb_flat_knn_fused bit for bit, and so
+ *   is RRF where no id occurs twice in a list (a repeat moves the row POSITIONS behind it, not the group ranks).
+ *   Outputs: out_idx (the representative, id_offset added) / out_dist (the group's score: the accumulator's own bits) [nq][k], slots
+ *   behind the count zero; out_count[q] = min(k, |U_q|); out_exact[q] (u8, may be NULL): RRF and SUM: 1 iff no list of the query is
+ *   truncated; MIN: 1 iff no list is truncated, or count == k and the order key of the k-th score is STRICTLY below the key of f_s for
+ *   every truncated list s -- every unfetched row is then at or beyond some f_s, so the k groups are the true k nearest groups over the
+ *   whole table with their true distances (a tie AT f_s gives 0).  k == 0: nothing is fetched or ranked, counts and out_exact are zero.
+ *   Limits as vdb_fuse_plan: 1 <= S_q <= 32, k <= fetch_k <= 4096, S_q x fetch_k <= 16384.
+ *   How: the ONE list call per sub-chunk of vdb_flat_knn_fused, then ONE k_fuse_groups launch (csrc/k_fuse_groups.hip), a workgroup per
+ *   fused query: every lane gathers the label of its entry (the gathers of the next tile of 256 positions issued before this one is
+ *   worked on); the groups live in an open-addressing table keyed by a 64-bit key (the code, or bit 32 | row for an unlabelled row) --
+ *   per slot the key, accumulator, stamp, representative row and its distance, 28 B with the sort key: in LDS up to 4096 slots (112 KiB
+ *   of the 160 KiB of a CU), past that the same code on a slice of device scratch.  Claim by compare-and-swap, stamp by atomic max of
+ *   (s << 16) | (0xFFFF - position), and after a barrier only the stamp's owner writes: one writer per slot per list.  The owners of a
+ *   tile are the first occurrences of their groups: wave ballots, prefix popcounts and per-wave sums give rho_s.  Under SUM a group first
+ *   seen in list s starts from the fold of f_0 .. f_(s-1), and after list s the occupied slots it did not stamp add f_s.
+ * vdb_fuse_groups_plan: host utility, works without a GPU: vdb_fuse_plan's codes 1 .. 12 in its order with VDB_FUSE_SUM an accepted
+ *   mode, 13 weights with VDB_FUSE_SUM (where 10 stands), 14 column >= VDB_LABEL_COLUMNS (last).  Accepted: the outputs of vdb_fuse_plan for
+ *   this kernel's table (lg as there; in LDS when lg <= 12; 28 B of scratch per slot otherwise).
+ * vdb_flat_knn_fused_groups_device: queries and outputs on the index's GPU, at most 32768 SUB-queries, returns synchronised.
+ * vdb_fuse_groups_device: the fusion alone over caller-supplied lists, the arguments of vdb_fuse_lists_device plus column, trunc_len
+ *   (>= 1) and d_out_exact: what a sharded merge would call, and how the tests drive the kernel.  If a group occurs more than once in
+ *   ONE list only its FIRST occurrence counts.  Every counted id is checked on the device first: an id that is no row of the index is
+ *   VDB_ERR_INVALID with the outputs untouched.
+ * Refused before anything is computed or written, counters unchanged (VDB_ERR_INVALID): everything vdb_fuse_groups_plan reports, a
+ * VecSet<u8> index, every mask / mask_of error of vdb_flat_knn_filtered_multi (a stale mask: VDB_ERR_STATE), trunc_len == 0.
+ * vdb_get_stat "flat_fused_groups_calls", "flat_fused_groups_queries", "flat_fused_groups_lists" count the two search forms (the list
+ * call under them advances its own counters); vdb_prof_get "fuse_groups" times k_fuse_groups.
+ * Not covered: rounds that grow fetch_k until MIN is exact (out_exact tells the caller), exact rescoring of candidate documents over
+ * all their rows, weighted SUM, sharded contexts, VecSet<u8> indexes, lists from PQ / HNSW / IVF beyond feeding them to the list form. */
+#define VDB_FUSE_SUM 2
+int vdb_fuse_groups_plan(int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, const float *weights, float rrf_c,
+                         uint32_t column, uint64_t budget, int *out_code, uint64_t *out_s_max, uint32_t *out_table_lg, int *out_in_lds,
+                         uint64_t *out_scratch_bytes, uint64_t *out_sub_chunk);
+int vdb_flat_knn_fused_groups(vdb_index *idx, const float *queries, const uint64_t *lims, uint64_t nq, uint64_t dim, uint64_t k,
+                              uint64_t fetch_k, int mode, const float *weights, float rrf_c, uint32_t column, const vdb_mask *const *masks,
+                              uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx, float *out_dist, uint64_t *out_count,
+                              uint8_t *out_exact);
+int vdb_flat_knn_fused_groups_device(vdb_index *idx, const void *d_queries, const uint64_t *lims, uint64_t nq, uint64_t dim, uint64_t k,
+                                     uint64_t fetch_k, int mode, const float *weights, float rrf_c, uint32_t column,
+                                     const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, void *d_out_idx,
+                                     void *d_out_dist, void *d_out_count, void *d_out_exact, void *stream);
+int vdb_fuse_groups_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, const uint64_t *lims, uint64_t nq,
+                           uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, uint32_t column, uint64_t trunc_len,
+                           void *d_out_idx, void *d_out_dist, void *d_out_count, void *d_out_exact, void *stream);
 /* ---- bulk row fetch: the vectors of many rows as ONE call (no counterpart in the reference) ----------------------------------------
  * vdb_index_row reads one row with one blocking copy.  These calls return the vectors of a LIST of rows: out[j] = row rows[j].  The
  * list only names what is read, so its order is free and repeats are allowed (m may exceed len); every rows[j] must be below len, and a

@@ -91,6 +91,12 @@ SIGNATURES = {
     "vdb_flat_knn_fused": [vp, f32p, u64p, u64, u64, u64, u64, C.c_int, f32p, C.c_float, C.POINTER(vp), u64, u32p, u64p, f32p, u64p],
     "vdb_flat_knn_fused_device": [vp, vp, u64p, u64, u64, u64, u64, C.c_int, f32p, C.c_float, C.POINTER(vp), u64, u32p, vp, vp, vp, vp],
     "vdb_fuse_lists_device": [vp, vp, vp, vp, u64p, u64, u64, u64, C.c_int, f32p, C.c_float, vp, vp, vp, vp],
+    "vdb_fuse_groups_plan": [C.c_int, u64p, u64, u64, u64, f32p, C.c_float, C.c_uint32, u64, intp, u64p, u32p, intp, u64p, u64p],
+    "vdb_flat_knn_fused_groups": [vp, f32p, u64p, u64, u64, u64, u64, C.c_int, f32p, C.c_float, C.c_uint32, C.POINTER(vp), u64, u32p, u64p, f32p,
+                                  u64p, u8p],
+    "vdb_flat_knn_fused_groups_device": [vp, vp, u64p, u64, u64, u64, u64, C.c_int, f32p, C.c_float, C.c_uint32, C.POINTER(vp), u64, u32p, vp, vp,
+                                         vp, vp, vp],
+    "vdb_fuse_groups_device": [vp, vp, vp, vp, u64p, u64, u64, u64, C.c_int, f32p, C.c_float, C.c_uint32, u64, vp, vp, vp, vp, vp],
     "vdb_fetch_plan": [u64, u64p, u64, u64, u64, intp, u64p, u64p],
     "vdb_index_get_rows": [vp, u64p, u64, f32p],
     "vdb_index_get_rows_u8": [vp, u64p, u64, u8p],

@@ -1406,6 +1406,112 @@ int vdb_fuse_lists_device(vdb_index *idx, const void *d_ids, const void *d_dists
     VDB_API_END
 }
 
+// ---- document-level fused search: the lists joined by the value of a label column (Index::flat_knn_fused_groups_device, k_fuse_groups.hip) --
+// everything that can be refused is refused here, before anything is computed or written; -> the masks as RowMask pointers (none: unfiltered)
+static std::vector<const RowMask *> fused_groups_check(const Index &ix, int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k,
+                                                       const float *weights, float rrf_c, uint32_t column, const vdb_mask *const *masks,
+                                                       uint64_t n_masks, const uint32_t *mask_of) {
+    const char *bad = fuse_groups_bad_text(fuse_groups_check_args(mode, lims, nq, k, fetch_k, weights, rrf_c, column));
+    VDB_REQUIRE(bad == nullptr, bad);
+    return optional_masks_check(ix, lims[nq], masks, n_masks, mask_of);
+}
+
+int vdb_fuse_groups_plan(int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, const float *weights, float rrf_c, uint32_t column,
+                         uint64_t budget, int *out_code, uint64_t *out_s_max, uint32_t *out_table_lg, int *out_in_lds, uint64_t *out_scratch_bytes,
+                         uint64_t *out_sub_chunk) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(out_code, "fuse_groups_plan: null out_code");
+    *out_code = fuse_groups_check_args(mode, lims, nq, k, fetch_k, weights, rrf_c, column);
+    if (*out_code != FUSE_OK) return VDB_OK;
+    const uint64_t s_max = fuse_s_max(lims, nq);
+    const uint32_t lg = fuse_table_lg(s_max, fetch_k);
+    if (out_s_max) *out_s_max = s_max;
+    if (out_table_lg) *out_table_lg = lg;
+    if (out_in_lds) *out_in_lds = fuse_groups_in_lds(lg) ? 1 : 0;
+    if (out_scratch_bytes) *out_scratch_bytes = fuse_groups_scratch_bytes(1, lg);
+    if (out_sub_chunk) *out_sub_chunk = fuse_groups_sub_chunk(nq, s_max, fetch_k, true, budget ? budget : LIST_BUDGET);
+    VDB_API_END
+}
+
+int vdb_flat_knn_fused_groups(vdb_index *idx, const float *queries, const uint64_t *lims, uint64_t nq, uint64_t dim, uint64_t k, uint64_t fetch_k,
+                              int mode, const float *weights, float rrf_c, uint32_t column, const vdb_mask *const *masks, uint64_t n_masks,
+                              const uint32_t *mask_of, uint64_t *out_idx, float *out_dist, uint64_t *out_count, uint8_t *out_exact) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_query_args(ix, queries, nq, dim, out_idx, out_dist);
+    const std::vector<const RowMask *> rm = fused_groups_check(ix, mode, lims, nq, k, fetch_k, weights, rrf_c, column, masks, n_masks, mask_of);
+    ix.fused_groups_calls++;
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    hipStream_t s = ws->stream;
+    run_synced(ix, *ws, [&] {
+        for (uint64_t q0 = 0; q0 < nq;) {  // chunks of whole fused queries with at most FUSE_MAX_SUBQ sub-queries (a fused query has at most 32)
+            uint64_t q1 = q0 + 1;
+            while (q1 < nq && lims[q1 + 1] - lims[q0] <= FUSE_MAX_SUBQ) q1++;
+            const uint64_t nb = q1 - q0, j0 = lims[q0], nj = lims[q1] - j0;
+            ws->q.reserve(nj * ix.dim * sizeof(float));
+            const OutBlock out(*ws, nb, k);
+            uint8_t *d_exact = nullptr;
+            if (out_exact) {  // (grp_q: no buffer of the list calls or of the fusion)
+                ws->grp_q.reserve(nb);
+                d_exact = ws->grp_q.as<uint8_t>();
+            }
+            VDB_HIP(hipMemcpyAsync(ws->q.p, queries + j0 * ix.dim, nj * ix.dim * sizeof(float), hipMemcpyHostToDevice, s));
+            ix.flat_knn_fused_groups_device(*ws, ws->q.as<float>(), lims + q0, nb, k, fetch_k, mode, weights ? weights + j0 : nullptr, rrf_c, column,
+                                            rm.data(), n_masks, n_masks ? mask_of + j0 : nullptr, out.idx(), out.dist(), out.cnt(), d_exact);
+            if (out_exact) VDB_HIP(hipMemcpyAsync(out_exact + q0, d_exact, nb, hipMemcpyDeviceToHost, s));
+            out.download(*ws, out.bytes <= OutBlock::STAGE_MAX, 0, q0, out_idx, out_dist, out_count);
+            q0 = q1;
+        }
+    });
+    VDB_API_END
+}
+
+int vdb_flat_knn_fused_groups_device(vdb_index *idx, const void *d_queries, const uint64_t *lims, uint64_t nq, uint64_t dim, uint64_t k,
+                                     uint64_t fetch_k, int mode, const float *weights, float rrf_c, uint32_t column, const vdb_mask *const *masks,
+                                     uint64_t n_masks, const uint32_t *mask_of, void *d_out_idx, void *d_out_dist, void *d_out_count,
+                                     void *d_out_exact, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    check_query_args(ix, d_queries, nq, dim, d_out_idx, d_out_dist);
+    VDB_REQUIRE(nq == 0 || d_out_count, "null out_count");
+    const std::vector<const RowMask *> rm = fused_groups_check(ix, mode, lims, nq, k, fetch_k, weights, rrf_c, column, masks, n_masks, mask_of);
+    VDB_REQUIRE(lims[nq] <= 32768, "at most 32768 sub-queries per device call");
+    ix.fused_groups_calls++;
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
+    run_synced(ix, *ws, [&] {
+        ix.flat_knn_fused_groups_device(*ws, static_cast<const float *>(d_queries), lims, nq, k, fetch_k, mode, weights, rrf_c, column, rm.data(), n_masks,
+                                        mask_of, static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist),
+                                        static_cast<uint64_t *>(d_out_count), static_cast<uint8_t *>(d_out_exact));
+    });
+    VDB_API_END
+}
+
+int vdb_fuse_groups_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, const uint64_t *lims, uint64_t nq, uint64_t ld,
+                           uint64_t k, int mode, const float *weights, float rrf_c, uint32_t column, uint64_t trunc_len, void *d_out_idx,
+                           void *d_out_dist, void *d_out_count, void *d_out_exact, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const char *bad = fuse_groups_bad_text(fuse_groups_check_args(mode, lims, nq, k, ld, weights, rrf_c, column, true));
+    VDB_REQUIRE(bad == nullptr, bad);
+    VDB_REQUIRE(trunc_len >= 1, "fuse groups: trunc_len must be at least 1");
+    require_f32_rows(ix);
+    VDB_REQUIRE(k < (1ull << 31), "fuse groups: k too large");
+    list_form_call(ix, stream, d_ids, d_dists, d_counts, nq, ld, k, d_out_idx, d_out_dist, d_out_count, [&](Workspace &ws) {
+        ix.fuse_groups_device(ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), lims,
+                              nq, ld, k, mode, weights, rrf_c, column, trunc_len, static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist),
+                              static_cast<uint64_t *>(d_out_count), static_cast<uint8_t *>(d_out_exact));
+    });
+    VDB_API_END
+}
+
 // ---- bulk row fetch (Index::get_rows*) ----------------------------------------------------------------------------------------------
 int vdb_index_get_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, float *out) {
     VDB_API_BEGIN
@@ -1800,6 +1906,12 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.fused_queries.load();
     else if (n == "flat_fused_lists")
         *out = idx->ix.fused_lists.load();
+    else if (n == "flat_fused_groups_calls")  // document-level fused search: calls | fused queries | sub-queries (the two search forms)
+        *out = idx->ix.fused_groups_calls.load();
+    else if (n == "flat_fused_groups_queries")
+        *out = idx->ix.fused_groups_queries.load();
+    else if (n == "flat_fused_groups_lists")
+        *out = idx->ix.fused_groups_lists.load();
     else if (n == "update_calls")  // vdb_index_update_rows* calls that changed rows | rows they rewrote
         *out = idx->ix.update_calls.load();
     else if (n == "update_rows")

@@ -1,7 +1,8 @@
 // flat_rerank.hip -- the Flat list re-rankers of Index: grouped k-NN, diversified k-NN (MMR), search by example rows and the fused
-// multi-query search, each as a search form and as a list form over caller-supplied lists (docs/DESIGN_flat.md 4.1x and 4.1q/u/v/w).
+// multi-query search -- by row and by document, the value of a label column --, each as a search form and as a list form over
+// caller-supplied lists (docs/DESIGN_flat.md 4.1x and 4.1q/u/v/w/z).
 //
-// All four have one shape.  A search form fetches the exact sorted list of K' rows per query -- flat_knn_device, or
+// All of them have one shape.  A search form fetches the exact sorted list of K' rows per query -- flat_knn_device, or
 // flat_knn_masked_multi_device when the call has masks -- for a sub-chunk of queries whose lists fit LIST_BUDGET (list_plan.hpp) and runs
 // ONE small kernel over those lists; a list form checks the ids of the caller's lists (ids_ok, index.hpp) and runs that kernel alone.  The
 // kernels differ; what stands around them is here once: zero_counts, max_allowed, reserve_lists / fetch_lists, sub_chunk_loop, end_call.
@@ -390,6 +391,82 @@ void Index::fuse_lists_device(Workspace &ws, const uint64_t *d_ids, const float 
         [&](const Chunk &c) {
             launch_fuse_lists(d_ids, d_dists, d_counts, c.nb, ld, up.lims + c.c0, 0, up.weights, mode, rrf_c, id_offset, (uint32_t)k, lg,
                               ws.grp_table.as<uint32_t>(), d_idx + c.c0 * k, d_dist + c.c0 * k, d_cnt + c.c0, s);
+        });
+    end_call(*this, ws);
+}
+
+// ---- Flat: document-level fused search, the lists joined by the value of a label column (k_fuse_groups.hip, fuse_groups_plan.hpp; 4.1z) ---
+// The fused search with another kernel behind the same list call: the table is keyed by the row's GROUP, its slot is wider, so the
+// sub-chunk and the scratch come from fuse_groups_plan.hpp.  k == 0: nothing is fetched or ranked -- zero counts, zero `exact`.
+static void zero_exact(Workspace &ws, uint8_t *d_exact, uint64_t nq) {
+    if (d_exact) VDB_HIP(hipMemsetAsync(d_exact, 0, nq, ws.stream));
+}
+
+void Index::flat_knn_fused_groups_device(Workspace &ws, const float *d_q, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, int mode,
+                                         const float *weights, float rrf_c, uint32_t column, const RowMask *const *masks, uint64_t n_masks,
+                                         const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt, uint8_t *d_exact) {
+    hipStream_t s = ws.stream;
+    require_f32_rows(*this);
+    VDB_REQUIRE(column < LABEL_COLUMNS, "fuse groups: bad column");
+    if (nq == 0) return;
+    const uint64_t nl = lims[nq] - lims[0];
+    fused_groups_queries += nq;
+    fused_groups_lists += nl;
+    if (k == 0) {
+        zero_exact(ws, d_exact, nq);
+        return zero_counts(ws, d_cnt, nq);
+    }
+    const Allowed all{masks, n_masks, mask_of};
+    const uint64_t s_max = fuse_s_max(lims, nq);
+    const uint64_t max_m = max_allowed(*this, all, nl);
+    const uint64_t kp = fuse_list_len(fetch_k, max_m);
+    // a list of fetch_k entries may have left rows behind -- unless fetch_k reaches the longest allowed set: every list is whole then
+    const uint64_t trunc_len = fetch_k >= max_m ? kp + 1 : fetch_k;
+    const uint32_t lg = fuse_table_lg(s_max, kp);
+    const uint64_t sub = fuse_groups_sub_chunk(nq, s_max, kp);
+    const Lists l = reserve_lists(*this, ws, std::min(nl, sub * s_max), kp, n_masks);
+    if (const size_t tb = fuse_groups_scratch_bytes(sub, lg)) ws.grp_table.reserve(tb);
+    std::vector<char> blob;
+    const FuseUpload up = fuse_upload(ws, blob, lims, nq, weights);
+    const uint32_t *col = label_live[column] ? d_labels[column].as<uint32_t>() : nullptr;
+    sub_chunk_loop(
+        *this, ws, nq, sub, lims, "fuse_groups", [&](const Chunk &c) { fetch_lists(*this, ws, d_q + c.j0 * dim, c.nj, all, c.j0, l); },
+        [&](const Chunk &c) { return double(c.nj) * kp * (LIST_PAIR_BYTES + sizeof(uint32_t)); },
+        [&](const Chunk &c) {
+            launch_fuse_groups(l.ids, l.dist, l.cnt, c.nb, kp, up.lims + c.c0, c.j0, up.weights, col, n, mode, rrf_c, id_offset, trunc_len, (uint32_t)k, lg,
+                               ws.grp_table.as<uint32_t>(), d_idx + c.c0 * k, d_dist + c.c0 * k, d_cnt + c.c0, d_exact ? d_exact + c.c0 : nullptr, s);
+        });
+    end_call(*this, ws);  // (`blob` is pageable memory: alive until here)
+}
+
+void Index::fuse_groups_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, const uint64_t *lims, uint64_t nq,
+                               uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, uint32_t column, uint64_t trunc_len,
+                               uint64_t *d_idx, float *d_dist, uint64_t *d_cnt, uint8_t *d_exact) {
+    hipStream_t s = ws.stream;
+    require_f32_rows(*this);
+    VDB_REQUIRE(column < LABEL_COLUMNS && trunc_len >= 1, "fuse groups: bad column or trunc_len");
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 31) && k < (1ull << 31), "fuse groups: too many fused queries or k too large");
+    if (k == 0) {
+        zero_exact(ws, d_exact, nq);
+        return zero_counts(ws, d_cnt, nq);
+    }
+    const uint64_t s_max = fuse_s_max(lims, nq);
+    const uint32_t lg = fuse_table_lg(s_max, ld);
+    const uint64_t sub = fuse_groups_sub_chunk(nq, s_max, ld, false);
+    if (const size_t tb = fuse_groups_scratch_bytes(sub, lg)) ws.grp_table.reserve(tb);
+    std::vector<char> blob;
+    const FuseUpload up = fuse_upload(ws, blob, lims, nq, weights);
+    if (ld)
+        ids_ok(
+            ws, s, ws.grp_aux.as<uint32_t>(), "fuse groups: a list holds an id that is no row of this index (id - id_offset must be below len)",
+            [&](uint32_t *d_flag) { launch_list_check(d_ids, d_counts, lims[nq], ld, n, id_offset, d_flag, s); }, true);  // (the upload's first word: zero)
+    const uint32_t *col = label_live[column] ? d_labels[column].as<uint32_t>() : nullptr;
+    sub_chunk_loop(
+        *this, ws, nq, sub, lims, "fuse_groups", no_fetch, [&](const Chunk &c) { return double(c.nj) * ld * (LIST_PAIR_BYTES + sizeof(uint32_t)); },
+        [&](const Chunk &c) {  // (ld == 0: every list is empty and nothing of d_ids / d_dists is read)
+            launch_fuse_groups(d_ids, d_dists, d_counts, c.nb, ld, up.lims + c.c0, 0, up.weights, col, n, mode, rrf_c, id_offset, trunc_len, (uint32_t)k, lg,
+                               ws.grp_table.as<uint32_t>(), d_idx + c.c0 * k, d_dist + c.c0 * k, d_cnt + c.c0, d_exact ? d_exact + c.c0 : nullptr, s);
         });
     end_call(*this, ws);
 }

@@ -736,6 +736,21 @@ struct Index {
     void fuse_lists_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, const uint64_t *lims, uint64_t nq,
                            uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
     std::atomic<uint64_t> fused_calls{0}, fused_queries{0}, fused_lists{0};
+    // Document-level fused Flat search (k_fuse_groups.hip, fuse_groups_plan.hpp; docs/DESIGN_flat.md 4.1z): flat_knn_fused_device with the
+    // lists joined by GROUP, the value of label column `column` (a row without one: a group of its own), mode FUSE_RRF / FUSE_MIN /
+    // FUSE_SUM; the same ONE list call per sub-chunk (fuse_groups_sub_chunk), then ONE k_fuse_groups launch.  d_exact (device u8 [nq],
+    // nullptr: not wanted): whether the answer is the one the whole table would give.  The caller has checked the arguments
+    // (fuse_groups_check_args), the masks and mask_of; returns synchronised.
+    void flat_knn_fused_groups_device(Workspace &ws, const float *d_q, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, int mode,
+                                      const float *weights, float rrf_c, uint32_t column, const RowMask *const *masks, uint64_t n_masks,
+                                      const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt, uint8_t *d_exact);
+    // k_fuse_groups alone over caller-supplied lists [lims[nq]][ld] (device), walked as given (lims: HOST, from 0); a list that counts
+    // trunc_len entries or more is a truncated one.  Every id of the counted ranges is checked on the device first (one flag read back; a
+    // bad one throws before an output is written).  Returns synchronised.
+    void fuse_groups_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, const uint64_t *lims, uint64_t nq,
+                            uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, uint32_t column, uint64_t trunc_len, uint64_t *d_idx,
+                            float *d_dist, uint64_t *d_cnt, uint8_t *d_exact);
+    std::atomic<uint64_t> fused_groups_calls{0}, fused_groups_queries{0}, fused_groups_lists{0};
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};

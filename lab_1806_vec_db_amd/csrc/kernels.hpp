@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "fuse_groups_plan.hpp"
 #include "fuse_plan.hpp"
 #include "grouped_plan.hpp"
 #include "labels_scatter_plan.hpp"
@@ -480,6 +481,19 @@ void launch_like_drop(const uint64_t *ids, const float *dists, const uint64_t *c
 void launch_fuse_lists(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nq, uint64_t ld, const uint64_t *lims,
                        uint64_t list_base, const float *weights, int mode, float c, uint64_t id_offset, uint32_t k, uint32_t lg, uint32_t *scratch,
                        uint64_t *out_idx, float *out_dist, uint64_t *out_cnt, hipStream_t s);
+// The fusion of the document-level fused search (k_fuse_groups.hip, fuse_groups_plan.hpp): the lists as for launch_fuse_lists, joined by
+// GROUP -- the value of `labels` (u32 per LOCAL row; nullptr: a column never written) at the row, a row without one being a group of its
+// own.  Per list a group counts at its first position: FUSE_RRF folds w / ((float)(rank among the list's groups + 1) + c), descending;
+// FUSE_MIN takes the smallest such distance, ascending; FUSE_SUM folds that distance, or the list's last distance where the list does
+// not hold the group, over every non-empty list, ascending.  The representative of a group is its row of the smallest (distance, list);
+// ties in the order go to the lower representative.  The first min(k, groups) go to out_idx (representative + id_offset) / out_dist
+// (score) [b][k] with zeros behind them, their number to out_cnt[b]; out_exact[b] (nullptr: not wanted) = no list counts trunc_len
+// entries or more, or (FUSE_MIN) k groups came out and the k-th score is strictly before the last distance of every such list.
+// lg = fuse_table_lg(most lists of a fused query, ld); scratch: fuse_groups_scratch_bytes(nq, lg) bytes, unused while the table fits LDS.
+void launch_fuse_groups(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nq, uint64_t ld, const uint64_t *lims,
+                        uint64_t list_base, const float *weights, const uint32_t *labels, uint64_t n, int mode, float c, uint64_t id_offset,
+                        uint64_t trunc_len, uint32_t k, uint32_t lg, uint32_t *scratch, uint64_t *out_idx, float *out_dist, uint64_t *out_cnt,
+                        uint8_t *out_exact, hipStream_t s);
 void mfma_set_sample_thin(int v);
 void mfma_sample_plan(uint64_t n, uint32_t kprime, uint32_t *step, uint32_t *rank, uint32_t target_floor = 1024);  // target_floor: expected hits per query
 uint64_t mfma_sample_rows(uint64_t n, uint32_t step);

@@ -83,6 +83,7 @@ MASK_MAX_TERMS = 8         # VDB_MASK_MAX_TERMS
 MASK_OP_AND, MASK_OP_OR = 0, 1  # VDB_MASK_OP_AND / VDB_MASK_OP_OR
 LIKE_MAX_EXAMPLES = 1024   # examples of one query of flat_knn_like, positives plus negatives (LIKE_MAX_EXAMPLES of csrc/like_plan.hpp)
 FUSE_MODES = {"rrf": 0, "min": 1}  # VDB_FUSE_RRF / VDB_FUSE_MIN
+FUSE_GROUP_MODES = {"rrf": 0, "min": 1, "sum": 2}  # ... and VDB_FUSE_SUM, which only the document-level fusion has
 FUSE_MAX_FETCH = 4096      # longest list of flat_knn_fused / fuse_lists_device (FUSE_MAX_FETCH of csrc/fuse_plan.hpp)
 MMR_MAX_FETCH = 4096       # longest candidate list of flat_knn_mmr / mmr_select_device (MMR_MAX_FETCH of csrc/mmr_plan.hpp)
 FETCH_CHUNK_BYTES_DEFAULT = 128 << 20  # what "fetch_chunk_bytes" is until set_param changes it (Index::FETCH_CHUNK_BYTES_DEFAULT)
@@ -696,14 +697,14 @@ class GpuIndex:
                                                 float(lambda_mult), L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
 
     @staticmethod
-    def _fuse_args(lims, mode, weights):
-        """(lims u64, mode code, weights f32 or None) of a fused call; `mode` is "rrf" / "min" or the library's code"""
+    def _fuse_args(lims, mode, weights, modes=FUSE_MODES):
+        """(lims u64, mode code, weights f32 or None) of a fused call; `mode` is a name of `modes` or the library's code"""
         lm = np.ascontiguousarray(lims, dtype=np.uint64).ravel()
         if lm.size == 0:
             raise ValueError("lims: nq + 1 entries are needed")
-        code = FUSE_MODES.get(mode, mode) if isinstance(mode, str) else int(mode)
+        code = modes.get(mode, mode) if isinstance(mode, str) else int(mode)
         if isinstance(code, str):
-            raise ValueError(f"fusion mode {mode!r}: 'rrf' or 'min'")
+            raise ValueError(f"fusion mode {mode!r}: " + " or ".join(repr(m) for m in modes))
         w = None
         if weights is not None:
             w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
@@ -750,6 +751,69 @@ class GpuIndex:
         L.check(self._lib.vdb_fuse_lists_device(self._h, L.vp(ids_ptr), L.vp(dists_ptr), L.vp(counts_ptr), _ptr(lm, L.u64p), lm.size - 1, int(ld),
                                                 int(k), code, _ptr(w, L.f32p), float(rrf_c), L.vp(out_idx_ptr), L.vp(out_dist_ptr),
                                                 L.vp(out_cnt_ptr), L.vp(stream)))
+
+    @staticmethod
+    def fuse_groups_plan(lims, k: int, fetch_k: int, mode="rrf", weights=None, rrf_c: float = 60.0, column: int = 0, budget: int = 0):
+        """vdb_fuse_groups_plan, no GPU needed -> (code, s_max, table_lg, in_lds, scratch bytes per fused query, sub-chunk); code 0: the
+        search forms accept the call, and only then are the others meaningful (they are None otherwise)"""
+        lm = np.ascontiguousarray(lims, dtype=np.uint64).ravel()
+        code = FUSE_GROUP_MODES.get(mode, -1) if isinstance(mode, str) else int(mode)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).ravel()
+        rc, in_lds, lg = C.c_int(-1), C.c_int(-1), C.c_uint32(0)
+        s_max, scratch, sub = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.check(L.load().vdb_fuse_groups_plan(code, _ptr(lm, L.u64p) if lm.size else None, max(lm.size, 1) - 1, int(k), int(fetch_k), _ptr(w, L.f32p),
+                                              float(rrf_c), int(column), int(budget), C.byref(rc), C.byref(s_max), C.byref(lg), C.byref(in_lds),
+                                              C.byref(scratch), C.byref(sub)))
+        if rc.value:
+            return rc.value, None, None, None, None, None
+        return 0, s_max.value, lg.value, in_lds.value, scratch.value, sub.value
+
+    def flat_knn_fused_groups(self, queries, lims, k: int, fetch_k: int, column: int, mode="rrf", weights=None, rrf_c: float = 60.0, masks=None,
+                              mask_of=None, return_exact: bool = False):
+        """Document-level fused exact search (vdb_flat_knn_fused_groups): flat_knn_fused with the lists joined by GROUP -- the rows that
+        share a value of label column `column`; a row without one is a group of its own.  Per list a group counts once, at its first
+        (nearest) row.  mode="rrf": the f32 left fold of weight / ((rank among the list's groups + 1) + rrf_c), descending; "min": the
+        smallest such distance, ascending; "sum": the fold, over every non-empty list, of that distance -- or of the list's last distance
+        where the list does not hold the group -- ascending (late interaction; a lower bound of the true sum while a list is cut at
+        fetch_k).  `idx` carries each group's representative row (its nearest), `dist` the score.
+        -> (idx [nq][k], dist [nq][k], count [nq]), and with return_exact a u8 array [nq]: whether the whole table would give this answer."""
+        lm, code, w = self._fuse_args(lims, mode, weights, FUSE_GROUP_MODES)
+        q = _f32(queries)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        if q.shape[0] != int(lm[-1]):
+            raise ValueError(f"{q.shape[0]} query vectors for {int(lm[-1])} sub-queries")
+        nq = lm.size - 1
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, q.shape[0])
+        out, ptrs = self._knn_outputs(nq, k)
+        exact = np.zeros(max(nq, 1), dtype=np.uint8)
+        L.check(self._lib.vdb_flat_knn_fused_groups(self._h, _ptr(q, L.f32p), _ptr(lm, L.u64p), nq, q.shape[1], int(k), int(fetch_k), code,
+                                                    _ptr(w, L.f32p), float(rrf_c), int(column), arr, n_masks, mo_p, *ptrs,
+                                                    _ptr(exact, L.u8p) if return_exact else None))
+        res = self._knn_cut(out, k)
+        return res + (exact[:nq],) if return_exact else res
+
+    def flat_knn_fused_groups_device(self, q_ptr: int, lims, k: int, fetch_k: int, column: int, out_idx_ptr: int, out_dist_ptr: int,
+                                     out_cnt_ptr: int, out_exact_ptr: int = 0, mode="rrf", weights=None, rrf_c: float = 60.0, masks=None,
+                                     mask_of=None, stream: int = 0):
+        """Device form (vdb_flat_knn_fused_groups_device): lims and weights on the host, the sub-queries' vectors and the outputs (exact: u8,
+        0 = not wanted) on this GPU, at most 32768 sub-queries"""
+        lm, code, w = self._fuse_args(lims, mode, weights, FUSE_GROUP_MODES)
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, int(lm[-1]))
+        L.check(self._lib.vdb_flat_knn_fused_groups_device(self._h, L.vp(q_ptr), _ptr(lm, L.u64p), lm.size - 1, self.dim, int(k), int(fetch_k), code,
+                                                           _ptr(w, L.f32p), float(rrf_c), int(column), arr, n_masks, mo_p, L.vp(out_idx_ptr),
+                                                           L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(out_exact_ptr), L.vp(stream)))
+
+    def fuse_groups_device(self, ids_ptr: int, dists_ptr: int, counts_ptr: int, lims, ld: int, k: int, column: int, out_idx_ptr: int,
+                           out_dist_ptr: int, out_cnt_ptr: int, out_exact_ptr: int = 0, mode="rrf", weights=None, rrf_c: float = 60.0,
+                           trunc_len: int | None = None, stream: int = 0):
+        """the document-level fusion alone over caller-supplied device lists [lims[-1]][ld] (u64 ids, f32 distances; ld <= 4096) and u64
+        counts, walked in the order given; a list that counts `trunc_len` entries (default ld, at least 1) or more is a truncated one
+        (vdb_fuse_groups_device); an id that is no row of this index raises and leaves the outputs untouched"""
+        lm, code, w = self._fuse_args(lims, mode, weights, FUSE_GROUP_MODES)
+        tl = max(int(ld), 1) if trunc_len is None else int(trunc_len)
+        L.check(self._lib.vdb_fuse_groups_device(self._h, L.vp(ids_ptr), L.vp(dists_ptr), L.vp(counts_ptr), _ptr(lm, L.u64p), lm.size - 1, int(ld),
+                                                 int(k), code, _ptr(w, L.f32p), float(rrf_c), int(column), tl, L.vp(out_idx_ptr), L.vp(out_dist_ptr),
+                                                 L.vp(out_cnt_ptr), L.vp(out_exact_ptr), L.vp(stream)))
 
     @staticmethod
     def _like_lists(lists, nq=None):

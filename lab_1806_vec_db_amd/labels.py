@@ -404,6 +404,75 @@ def cap_groups(codes_in_order, group_size: int, k: int) -> list[int]:
     return kept
 
 
+def _f32_order_key(d) -> int:
+    """the knn order of an f32 as an integer: -0 == +0, every NaN equal and last (f32_orderable of the library)"""
+    u = int(np.array(np.float32(d) + np.float32(0.0), dtype=np.float32).view(np.uint32))
+    if (u & 0x7FFFFFFF) > 0x7F800000:
+        u = 0x7FC00000
+    return (~u & 0xFFFFFFFF) if u & 0x80000000 else (u | 0x80000000)
+
+
+def fuse_groups(lists, k: int, mode: str = "rrf", weights=None, c: float = 60.0, trunc_len=None):
+    """THE host statement of the document-level fusion (GpuIndex.flat_knn_fused_groups, k_fuse_groups), for keys without a label column.
+    `lists`: per sub-query (ids, distances, values) in rank order -- values[i] is the group of entry i, any hashable; None: the row is a
+    group of its own.  Per list a group counts at its first entry; "rrf": the f32 fold of weight / ((rank among the list's groups + 1) + c),
+    descending; "min": the smallest such distance; "sum": the fold over every non-empty list of that distance, or of the list's last
+    distance where the list lacks the group; both ascending.  The representative of a group is its entry of the smallest (distance,
+    list); ties go to the lower representative.  A list of trunc_len entries or more is a truncated one (None: none is).
+    -> (representative ids, scores as float32, exact) cut at k; the arithmetic is the device's, rounding for rounding."""
+    if mode not in ("rrf", "min", "sum"):
+        raise ValueError(f"fusion {mode!r}: 'rrf', 'min' or 'sum'")
+    f32 = np.float32
+    c = f32(c)
+    table: dict[object, list] = {}  # group -> [accumulator, representative id, its distance, the list that touched it last]
+    prefix = f32(0.0)               # "sum": the fold of the last distances of the non-empty lists so far
+    trunc_keys = []
+    with np.errstate(all="ignore"):
+        for s, (ids, dists, values) in enumerate(lists):
+            if len(ids) == 0:
+                continue
+            f_s = f32(dists[len(ids) - 1])
+            if trunc_len is not None and len(ids) >= trunc_len:
+                trunc_keys.append(_f32_order_key(f_s))
+            w = f32(1.0) if weights is None else f32(weights[s])
+            rank = 0
+            for i, d, v in zip(ids, dists, values):
+                g = ("r", int(i)) if v is None else ("l", v)
+                e = table.get(g)
+                if e is not None and e[3] == s:
+                    continue  # not the group's first entry in this list
+                d = f32(d)
+                if e is None:
+                    e = table[g] = [prefix if mode == "sum" else f32(0.0), int(i), d, s]
+                else:
+                    e[3] = s
+                    if _f32_order_key(d) < _f32_order_key(e[2]):
+                        e[1], e[2] = int(i), d
+                if mode == "rrf":
+                    den = f32(f32(rank + 1) + c)
+                    e[0] = f32(e[0] + f32(w / den))
+                elif mode == "sum":
+                    e[0] = f32(e[0] + d)
+                rank += 1
+            if mode == "sum":
+                for e in table.values():
+                    if e[3] != s:
+                        e[0] = f32(e[0] + f_s)
+                prefix = f32(prefix + f_s)
+        nan = np.array(0x7FC00000, dtype=np.uint32).view(np.float32)[()]
+        scored = []
+        for e in table.values():
+            score = e[2] if mode == "min" else (nan if mode == "sum" and np.isnan(e[0]) else e[0])
+            scored.append((_f32_order_key(-score if mode == "rrf" else score), e[1], score))
+    scored.sort(key=lambda t: t[:2])
+    k = max(int(k), 0)
+    exact = not trunc_keys and k > 0  # (k == 0: nothing is ranked, and `exact` is 0, as the library answers)
+    if trunc_keys and mode == "min" and 0 < k <= len(scored):
+        exact = scored[k - 1][0] < min(trunc_keys)
+    top = scored[:k]
+    return np.array([t[1] for t in top], dtype=np.uint64), np.array([t[2] for t in top], dtype=np.float32), int(exact)
+
+
 class LabelCodec:
     def __init__(self, max_columns: int = LABEL_COLUMNS, max_terms: int = MASK_MAX_TERMS):
         self.max_columns = int(max_columns)

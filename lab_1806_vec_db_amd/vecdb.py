@@ -37,7 +37,8 @@ search_like / batch_search_like search by EXAMPLE ROWS: the rows a `positive` fi
 matches, the examples left out of the answer -- the query vector is made on the device, the batch is one library call (GpuIndex.flat_knn_like).
 search_fused / batch_search_fused join SEVERAL searches of one question -- several query vectors, or one vector under several filters --
 into one ranked answer on the device, by reciprocal rank fusion or by the smallest distance; the batch is one library call
-(GpuIndex.flat_knn_fused).
+(GpuIndex.flat_knn_fused).  With `group_by` they rank DOCUMENTS, the rows that share a value of a metadata key -- also by the
+late-interaction sum, fusion="sum" -- still one library call (GpuIndex.flat_knn_fused_groups).
 get(key, filter, limit) returns the vectors and metadata of the matching rows, and every search takes `with_vectors`: the hits' vectors
 ride along, all of a call's from one bulk fetch (GpuIndex.get_rows / get_rows_mask); extract_data reads the table with one such call.
 update_metadata(key, pattern, changes) / batch_update_metadata change the METADATA of the matching rows in place: row ids, vectors, the
@@ -54,7 +55,7 @@ import numpy as np
 
 from ._lib import VdbError
 from .index import FUSE_MAX_FETCH, LIKE_MAX_EXAMPLES, MMR_MAX_FETCH, GpuIndex, RowMask, parse_dist
-from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, filter_patterns, has_predicates, is_expression, stale_filters
+from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, fuse_groups, filter_patterns, has_predicates, is_expression, stale_filters
 from .labels import matches as value_matches
 
 _DIST_STR = {0: "l2sqr", 1: "cosine"}
@@ -788,15 +789,18 @@ class VecDB:
                     for j in range(nq)]
 
     def search_fused(self, key: str, queries, k: int, fusion: str = "rrf", weights=None, filters=None, fetch_k: int | None = None,
-                     rrf_c: float = 60.0, upper_bound: float | None = None, with_vectors: bool = False):
+                     rrf_c: float = 60.0, upper_bound: float | None = None, with_vectors: bool = False, group_by: str | None = None,
+                     return_exact: bool = False):
         """Several searches of ONE question joined into one ranked answer: batch_search_fused for one question (it states the rule).
         `queries`: the vectors of the question; `weights`: None or one per vector; `filters`: None, one filter for every vector, or one
-        per vector.  Entries are (metadata, score[, vector])."""
-        return self.batch_search_fused(key, [queries], k, fusion, None if weights is None else [weights], None if filters is None else [filters],
-                                       fetch_k, rrf_c, upper_bound, with_vectors)[0]
+        per vector.  Entries are (metadata, score[, vector]); with return_exact the result is (entries, exact)."""
+        res = self.batch_search_fused(key, [queries], k, fusion, None if weights is None else [weights], None if filters is None else [filters],
+                                      fetch_k, rrf_c, upper_bound, with_vectors, group_by, return_exact)
+        return (res[0][0], res[1][0]) if return_exact else res[0]
 
     def batch_search_fused(self, key: str, query_groups, k: int, fusion: str = "rrf", weights=None, filters=None, fetch_k: int | None = None,
-                           rrf_c: float = 60.0, upper_bound: float | None = None, with_vectors: bool = False):
+                           rrf_c: float = 60.0, upper_bound: float | None = None, with_vectors: bool = False, group_by: str | None = None,
+                           return_exact: bool = False):
         """Fused multi-query search for a batch of questions in ONE library call (GpuIndex.flat_knn_fused).  `query_groups`: per
         question its 1 to 32 query vectors (paraphrases, a HyDE passage, sub-questions -- or one vector repeated under several filters).
         Every vector is searched exactly, from the table's Flat rows, for its `fetch_k` nearest matching rows (default 4 k, raised to k,
@@ -808,11 +812,26 @@ class VecDB:
         `weights`: None, or per question None or one positive number per vector.  `filters`: None; ONE filter for every vector of the
         batch; or per question None, one filter, or one filter (or None: every row) per vector -- of any kind search accepts, through
         the mask cache, one mask per distinct filter.  `upper_bound`: fusion="min" only (the score is a distance), applied afterwards;
-        with "rrf" it is a ValueError.  `with_vectors` as in batch_search.  One read guard covers the batch."""
-        if fusion not in ("rrf", "min"):
-            raise ValueError(f"fusion {fusion!r}: 'rrf' or 'min'")
+        with "rrf" it is a ValueError.  `with_vectors` as in batch_search.  One read guard covers the batch.
+        `group_by`: a metadata key -- the unit of ranking becomes the GROUP, the matching rows that share a value of the key (rows are
+        chunks, the key names the document); a row without the key is a group of its own.  In every list a group counts once, at its
+        first (nearest) row, and an entry is (metadata of the group's representative row -- its nearest over the vectors --, score[,
+        vector]).  "rrf" ranks by the group's rank among the GROUPS of each list; "min" by its smallest distance; fusion="sum" (with
+        group_by only) by the sum over the vectors of the group's nearest distance, a vector whose list lacks the group counting with its
+        list's last distance: the late-interaction score, a lower bound of the true sum while a list is cut at fetch_k.  `weights` go
+        with "rrf" only.  ONE library call (GpuIndex.flat_knn_fused_groups); the key gets a label column on first use, as
+        batch_search(group_by=) gives it one, and a key that cannot have a column (a 17th key) or whose values a dictionary cannot keep
+        apart takes the host fallback: batch_search's lists at fetch_k, joined by labels.fuse_groups over the metadata values.
+        `return_exact` (group_by only): the result becomes (answers, exact) -- exact[q] is True when the whole table would give this
+        answer ("rrf", "sum": no list was cut at fetch_k; "min": that, or the k-th score lies strictly before every cut)."""
+        if fusion not in ("rrf", "min") and not (fusion == "sum" and group_by is not None):
+            raise ValueError(f"fusion {fusion!r}: 'rrf' or 'min'" + (", or 'sum'" if group_by is not None else " ('sum' needs group_by)"))
         if upper_bound is not None and fusion != "min":
-            raise ValueError("upper_bound applies to fusion='min' only: an RRF score is no distance")
+            raise ValueError("upper_bound applies to fusion='min' only: an RRF score or a sum is no distance")
+        if return_exact and group_by is None:
+            raise ValueError("return_exact needs group_by")
+        if group_by is not None and weights is not None and fusion != "rrf" and any(x is not None for x in weights):
+            raise ValueError("weights belong to fusion='rrf' only")
         t = self._t(key)
         ix = t.index
         groups = [np.asarray(g, dtype=np.float32) for g in query_groups]
@@ -822,7 +841,7 @@ class VecDB:
             if g.ndim != 2 or g.shape[1] != ix.dim or g.shape[0] == 0:
                 raise RuntimeError(f"Dimension mismatch: table dim {ix.dim}, question {i} got {g.shape}")
         if nq == 0:
-            return []
+            return ([], []) if return_exact else []
         sizes = [g.shape[0] for g in groups]
         lims = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
         w = None
@@ -857,6 +876,8 @@ class VecDB:
             t.prepare(pats)
         q = np.ascontiguousarray(np.concatenate(groups, axis=0))
         fk = min(max(4 * int(k) if fetch_k is None else int(fetch_k), int(k)), FUSE_MAX_FETCH)
+        if group_by is not None:
+            t.prepare([{group_by: None}])  # (the key's column, as count_by makes it)
         with t.lock.read():  # one read guard for the whole batch, mask building and metadata lookup included
             masks = mask_of = None
             if pats is not None:
@@ -869,12 +890,60 @@ class VecDB:
                         distinct.append(p)
                     mask_of[i] = slot[pk]
                 masks = t.masks_for(distinct)  # the ones not cached yet: one library call
-            idx, dist, cnt = ix.flat_knn_fused(q, lims, k, fk, fusion, w, rrf_c, masks, mask_of)
+            exact = None
+            if group_by is None:
+                idx, dist, cnt = ix.flat_knn_fused(q, lims, k, fk, fusion, w, rrf_c, masks, mask_of)
+            elif t.codec.value_codes(group_by) is not None:
+                idx, dist, cnt, exact = ix.flat_knn_fused_groups(q, lims, k, fk, t.codec.column_of(group_by), fusion, w, rrf_c, masks, mask_of,
+                                                                 return_exact=True)
+            else:
+                idx, dist, cnt, exact = self._fused_groups_on_host(t, q, lims, k, fk, group_by, fusion, w, rrf_c, masks, mask_of)
             ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
             if with_vectors:
-                return self._hits_with_vectors(t, [idx[j, :int(cnt[j])] for j in range(nq)], [dist[j, :int(cnt[j])] for j in range(nq)], ub)
-            return [[(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx[j, :int(cnt[j])], dist[j, :int(cnt[j])]) if d <= ub]
-                    for j in range(nq)]
+                res = self._hits_with_vectors(t, [idx[j, :int(cnt[j])] for j in range(nq)], [dist[j, :int(cnt[j])] for j in range(nq)], ub)
+            else:
+                res = [[(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx[j, :int(cnt[j])], dist[j, :int(cnt[j])]) if d <= ub]
+                       for j in range(nq)]
+            return (res, [bool(x) for x in exact]) if return_exact else res
+
+    @staticmethod
+    def _fused_groups_on_host(t: _Table, q: np.ndarray, lims, k: int, fk: int, field: str, fusion: str, w, rrf_c: float, masks, mask_of):
+        """UNDER THE READ LOCK: search_fused(group_by=) for a field without a usable label column -- the exact lists of every vector at
+        fetch_k from ONE ungrouped search, joined per question by labels.fuse_groups over the metadata values (unhashable values are told
+        apart by a scan).  -> (idx, dist, cnt, exact) as GpuIndex.flat_knn_fused_groups(return_exact=True) returns them."""
+        ix = t.index
+        nq, k = len(lims) - 1, int(k)
+        if masks is None:
+            idx, dist, cnt = ix.flat_knn(q, fk)
+            max_m = len(ix)
+        else:
+            idx, dist, cnt = ix.flat_knn_filtered_multi(q, fk, masks, mask_of)
+            max_m = max(len(masks[int(m)]) for m in mask_of)
+        trunc = None if fk >= max_m else fk  # (fetch_k reaches the longest allowed set: every list is whole, as the library reasons)
+        o_idx, o_dist = np.zeros((nq, max(k, 1)), np.uint64), np.zeros((nq, max(k, 1)), np.float32)
+        o_cnt, o_exact = np.zeros(nq, np.uint64), np.zeros(nq, np.uint8)
+        for j in range(nq):
+            if k == 0:
+                continue  # (nothing is ranked: zero counts, zero exact, as the library answers)
+            odd, lists = [], []
+            for s in range(int(lims[j]), int(lims[j + 1])):
+                c = int(cnt[s])
+                values = []
+                for i in idx[s, :c]:
+                    v = t.metadata[int(i)].get(field)
+                    try:
+                        hash(v)
+                    except TypeError:
+                        if v not in odd:
+                            odd.append(v)
+                        v = ("unhashable", odd.index(v), id(odd))
+                    values.append(v)
+                lists.append((idx[s, :c], dist[s, :c], values))
+            ws = None if w is None else w[int(lims[j]):int(lims[j + 1])]
+            gi, gd, ge = fuse_groups(lists, k, fusion, ws, rrf_c, trunc_len=trunc)
+            o_cnt[j], o_exact[j] = len(gi), ge
+            o_idx[j, :len(gi)], o_dist[j, :len(gi)] = gi, gd
+        return o_idx[:, :k], o_dist[:, :k], o_cnt, o_exact
 
     @staticmethod
     def _grouped_on_host(t: _Table, q: np.ndarray, k: int, field: str, group_size: int, masks, mask_of):
