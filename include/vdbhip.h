@@ -374,6 +374,30 @@ int vdb_flat_range_filtered_multi_device(vdb_index *idx, const void *d_queries, 
  * vdb_get_stat "mask_partition_masks" counts the masks vdb_mask_create_partition built, "label_count_calls" the
  * vdb_index_label_counts calls (the older counters keep counting only their own calls); vdb_prof_get "mask_partition" times
  * k_mask_partition with its clears, scan and ids launches, "label_counts" k_label_counts with its clear.
+ * KEY LOOKUP (vdb_index_label_lookup, vdb_label_lookup_plan; csrc/lookup_plan.hpp, csrc/k_lookup.hip, docs/DESIGN_flat.md 4.1aa): from a
+ * list of codes to rows -- what an upsert or a fetch by a key field needs -- without a mask per code.
+ * vdb_index_label_lookup: out_counts[j] = the number of rows whose label in `column` equals codes[j]; out_first[j] = the lowest such LOCAL
+ * row, VDB_ROW_NONE when there is none.  The code rules are those of vdb_mask_create_partition / vdb_index_label_counts: distinct codes,
+ * any order, arbitrarily sparse, VDB_LABEL_NONE (the unlabelled rows) allowed among them; a column never written reads as VDB_LABEL_NONE
+ * in every row, without a load.  Refused with VDB_ERR_INVALID, outputs and every counter untouched: column >= VDB_LABEL_COLUMNS, a code
+ * named twice, a NULL pointer with n_codes > 0 (n_codes >= 2^28 as well).  n_codes == 0 and an empty index (counts 0, VDB_ROW_NONE)
+ * succeed.  Read-side, re-entrant on one handle, returns synchronised; f32 and VecSet<u8> indexes alike.  There is NO _device form: the
+ * codes come from a dictionary the host keeps (value -> code), so the list is on the host when the call is made.
+ *   How: a wave per 64-row word, grid-strided from 8 workgroups per CU ("label_lookup_max_blocks": another grid cap).  A lane loads its
+ *   row's code once and resolves it to a position of the list; the wave walks its distinct positions by ballot, and one lane per
+ *   distinct position adds the popcount and takes the min with its row.  Both outputs come from integer atomicAdd / atomicMin alone:
+ *   the answer does not depend on the order of waves; no float, no second pass, no sort on the device.
+ *   Two routes, chosen on the host.  SORTED (route 0): any codes, in chunks of 1024 -- the chunk's sorted table, counters and firsts in
+ *   LDS, a binary search per row, one read of the column per chunk.  DIRECT (route 1): a table slot_of[code - base] of `span` u32 in
+ *   workspace memory (span = highest - lowest + 1 over the codes other than VDB_LABEL_NONE, which never enters the table), filled by a
+ *   scatter kernel; one gather per row and ONE read of the column whatever n_codes is.  Taken when n_codes > 1024 and 4 B x span <=
+ *   "label_lookup_table_bytes" (vdb_set_param; default 64 MiB; a cap on scratch memory, not a tuned value; 0: sorted route only).
+ * vdb_label_lookup_plan: host utility, works without a GPU: the argument check of (column, codes, n_codes) and, for table_bytes, the
+ *   route, base, span and the number of column reads (chunks: ceil(n_codes / 1024) sorted, 1 direct, 0 without codes).  Any output may be
+ *   NULL; on an error nothing is written.
+ * vdb_get_stat: "label_lookup_calls" (accepted calls), "label_lookup_codes" (codes they named), "label_lookup_direct" (calls that ran
+ * the direct route), "label_lookup_passes" (reads of the column, summed; none on an empty index).  vdb_prof_get "label_lookup" times the
+ * fills, the table kernel and the lookup kernels.
  * Not covered: sharded and replica contexts, normal forms past VDB_MASK_MAX_CLAUSES clauses in one call (combine the parts with
  * vdb_mask_combine), partitions by more than one column, labels in bincode files, filtered k-NN on VecSet<u8> indexes. */
 #define VDB_LABEL_COLUMNS 16
@@ -449,6 +473,11 @@ int vdb_mask_combine(vdb_index *idx, int op, const vdb_mask *const *in, const ui
 int vdb_mask_create_partition(vdb_index *idx, uint32_t column, const uint32_t *codes, uint64_t n_codes, vdb_mask **out);
 int vdb_index_label_counts(vdb_index *idx, uint32_t column, const vdb_mask *mask, const uint32_t *codes, uint64_t n_codes,
                            uint64_t *out_counts);
+#define VDB_ROW_NONE 0xFFFFFFFFFFFFFFFFull /* vdb_index_label_lookup: no row carries the code */
+int vdb_label_lookup_plan(uint32_t column, const uint32_t *codes, uint64_t n_codes, uint64_t table_bytes, int *out_route, uint32_t *out_base,
+                          uint64_t *out_span, uint64_t *out_chunks);
+int vdb_index_label_lookup(vdb_index *idx, uint32_t column, const uint32_t *codes, uint64_t n_codes, uint64_t *out_first /* [n_codes] */,
+                           uint64_t *out_counts /* [n_codes] */);
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids);
 /* ---- grouped Flat k-NN: at most group_size hits per value of one label column -----------------------------------------------------------
  * "The 10 nearest chunks, at most 2 per document": the label columns so far restrict WHICH rows may be found; this call shapes the answer.
@@ -879,6 +908,8 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *                        conjunctions (vdb_mask_create_where_any*); "mask_combine_masks": the ones vdb_mask_combine made;
  *                        "mask_partition_masks": the ones vdb_mask_create_partition made; "label_count_calls":
  *                        vdb_index_label_counts calls; "label_columns": allocated columns,
+ *   "label_lookup_calls" vdb_index_label_lookup calls that were accepted; "label_lookup_codes": the codes they named;
+ *                        "label_lookup_direct": the calls that ran the direct route; "label_lookup_passes": reads of the column, summed,
  *   "update_calls"       vdb_index_update_rows / _device calls that changed rows (m > 0, not refused); "update_rows": the rows they rewrote,
  *   "fetch_calls"        vdb_index_get_rows* calls that fetched rows (m > 0, not refused); "fetch_rows": the rows they returned;
  *                        "fetch_chunks": their gather launches; "fetch_direct": the calls answered by one plain copy,

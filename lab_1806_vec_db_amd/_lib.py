@@ -71,6 +71,8 @@ SIGNATURES = {
     "vdb_mask_combine": [vp, C.c_int, C.POINTER(vp), u8p, u64, C.POINTER(vp)],
     "vdb_mask_create_partition": [vp, C.c_uint32, u32p, u64, C.POINTER(vp)],
     "vdb_index_label_counts": [vp, C.c_uint32, vp, u32p, u64, u64p],
+    "vdb_label_lookup_plan": [C.c_uint32, u32p, u64, u64, intp, u32p, u64p, u64p],
+    "vdb_index_label_lookup": [vp, C.c_uint32, u32p, u64, u64p, u64p],
     "vdb_mask_rows": [vp, u64p, u32p],
     "vdb_flat_knn_filtered": [vp, f32p, u64, u64, u64, vp, u64p, f32p, u64p],
     "vdb_flat_knn_filtered_device": [vp, vp, u64, u64, u64, vp, vp, vp, vp, vp],

@@ -891,6 +891,25 @@ int vdb_index_label_counts(vdb_index *idx, uint32_t column, const vdb_mask *mask
     idx->ix.label_counts(column, mask ? &mask->m : nullptr, codes, n_codes, out_counts);
     VDB_API_END
 }
+// the key lookup over one column (Index::label_lookup, lookup_plan.hpp)
+int vdb_label_lookup_plan(uint32_t column, const uint32_t *codes, uint64_t n_codes, uint64_t table_bytes, int *out_route, uint32_t *out_base,
+                          uint64_t *out_span, uint64_t *out_chunks) {
+    VDB_API_BEGIN
+    const std::string bad = label_lookup_check(column, codes, n_codes);
+    VDB_REQUIRE(bad.empty(), bad);
+    const LookupPlan p = label_lookup_plan(codes, n_codes, table_bytes);
+    if (out_route) *out_route = p.route;
+    if (out_base) *out_base = p.base;
+    if (out_span) *out_span = p.span;
+    if (out_chunks) *out_chunks = p.chunks;
+    VDB_API_END
+}
+int vdb_index_label_lookup(vdb_index *idx, uint32_t column, const uint32_t *codes, uint64_t n_codes, uint64_t *out_first, uint64_t *out_counts) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    idx->ix.label_lookup(column, codes, n_codes, out_first, out_counts);
+    VDB_API_END
+}
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids) {
     VDB_API_BEGIN
     VDB_REQUIRE(m, "null mask");
@@ -1710,6 +1729,14 @@ int vdb_set_param(vdb_index *idx, const char *name, int64_t value) {
         VDB_REQUIRE(value >= 0 && value <= 0x7FFFFFFF, "labels_scatter_max_blocks must be in 0 .. 2^31-1");
         idx->ix.labels_scatter_max_blocks = (uint32_t)value;
     }
+    else if (n == "label_lookup_table_bytes") {  // key lookup: scratch cap of the direct route's slot table (4 B per code of the list's span); 0: sorted route only
+        VDB_REQUIRE(value >= 0 && (uint64_t)value <= LOOKUP_TABLE_BYTES_MAX, "label_lookup_table_bytes must be in 0 .. 2^32");
+        idx->ix.label_lookup_table_bytes = (uint64_t)value;
+    }
+    else if (n == "label_lookup_max_blocks") {  // key lookup: grid cap of its kernels (0: 8 blocks per CU); a small cap makes the grid-stride loop wrap on a small table (tests)
+        VDB_REQUIRE(value >= 0 && value <= 0x7FFFFFFF, "label_lookup_max_blocks must be in 0 .. 2^31-1");
+        idx->ix.label_lookup_max_blocks = (uint32_t)value;
+    }
     else if (n == "debug_alloc_fail_over")  // (testing aid, process-wide) device allocations of at least this many bytes fail; 0 = off
         devbuf_fail_over() = (size_t)value;
     else if (n == "flat_i8_unit_min")  // threshold sample of the 8-bit pass: one value per sampled unit when the units are many (0 auto, 1 off, 2 on from 2 x rank units: tests)
@@ -1882,6 +1909,14 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.mask_partition_masks.load();
     else if (n == "label_count_calls")  // vdb_index_label_counts calls
         *out = idx->ix.label_count_calls.load();
+    else if (n == "label_lookup_calls")  // vdb_index_label_lookup: accepted calls | codes they named | calls on the direct route | reads of the column
+        *out = idx->ix.label_lookup_calls.load();
+    else if (n == "label_lookup_codes")
+        *out = idx->ix.label_lookup_codes.load();
+    else if (n == "label_lookup_direct")
+        *out = idx->ix.label_lookup_direct.load();
+    else if (n == "label_lookup_passes")
+        *out = idx->ix.label_lookup_passes.load();
     else if (n == "flat_grouped_calls")  // grouped k-NN: calls | queries | rounds run, summed over calls | queries whose last list was their whole allowed set
         *out = idx->ix.grouped_calls.load();
     else if (n == "flat_grouped_queries")

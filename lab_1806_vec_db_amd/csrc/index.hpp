@@ -666,7 +666,16 @@ struct Index {
     // code rules; the mask is checked with check_mask before anything is computed; read-side; returns synchronised.
     void label_counts(uint32_t column, const RowMask *mask, const uint32_t *codes, uint64_t n_codes, uint64_t *out_counts);
     std::atomic<uint64_t> label_count_calls{0};  // label_counts calls
-    // The five builders and label_counts are in index_masks.hip, on two shared halves that are local to that file (4.1y).
+    // out_counts[j] = the rows whose label in `column` equals codes[j], out_first[j] = the lowest such LOCAL row (LOOKUP_ROW_NONE when
+    // there is none), from ONE read of the column (direct route) or one per PART_MAX_CHUNK codes (sorted route): lookup_plan.hpp checks
+    // and routes, k_lookup.hip computes.  The same code rules as label_counts; everything is checked before an output or a counter is
+    // touched; read-side; returns synchronised.  docs/DESIGN_flat.md 4.1aa.
+    void label_lookup(uint32_t column, const uint32_t *codes, uint64_t n_codes, uint64_t *out_first, uint64_t *out_counts);
+    uint64_t label_lookup_table_bytes = LOOKUP_TABLE_BYTES_DEFAULT;  // "label_lookup_table_bytes": scratch cap of the direct route's table, 0 = sorted route only
+    uint32_t label_lookup_max_blocks = 0;                            // "label_lookup_max_blocks": grid cap of the lookup kernels, 0 = 8 blocks per CU
+    // accepted calls | codes they named | calls that took the direct route | reads of the column (kernel launches), summed
+    std::atomic<uint64_t> label_lookup_calls{0}, label_lookup_codes{0}, label_lookup_direct{0}, label_lookup_passes{0};
+    // The five builders, label_counts and label_lookup are in index_masks.hip, on two shared halves that are local to that file (4.1y).
     // The four Flat list re-rankers below -- grouped, diversified, by example, fused -- are in flat_rerank.hip, on one shared driver (4.1x).
     // Grouped Flat k-NN (k_group.hip, grouped_plan.hpp; docs/DESIGN_flat.md 4.1q): per query the first k rows, in FlatIndex::knn's order over
     // the allowed rows, of which at most g carry any one value of label column `column` (rows without a label are always kept).  Rounds:

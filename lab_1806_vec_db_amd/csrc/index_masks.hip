@@ -1,5 +1,5 @@
 // index_masks.hip -- the row masks Index builds on the device from its label columns (k_labels.hip; docs/DESIGN_flat.md 4.1l/m/o/p/y):
-// masks_where, masks_where_sets, masks_where_any, mask_combine, masks_partition, and label_counts beside them.  All five builders have
+// masks_where, masks_where_sets, masks_where_any, mask_combine, masks_partition, and label_counts and label_lookup (4.1aa) beside them.  All five builders have
 // one second half, masks_finish; the three predicate forms also have one first half behind their argument checks, masks_from_table.
 #include <algorithm>
 #include <array>
@@ -295,6 +295,74 @@ void Index::label_counts(uint32_t column, const RowMask *mask, const uint32_t *c
         prof_collect(*ws);
         for (uint32_t i = 0; i < nb; i++) out_counts[g0 + h_slot[i]] = h_cnt[i];
     }
+}
+
+// Rows per code and the lowest row of each (k_lookup.hip; lookup_plan.hpp checks the list and picks the route).  Both routes keep
+// [counts | firsts] of all n_codes entries in ws.misc, prepared by two fills, and read them back ONCE.  Sorted: the tables of all
+// chunks are uploaded together (keys_a) and chunk c's launch writes entries [c * PART_MAX_CHUNK, ...) in its table's order; the host
+// hands them out in the caller's.  Direct: the codes go up as they are (keys_a), k_lookup_table scatters their positions into slot_of
+// (keys_b, span u32) and one launch over the column writes the entries in the caller's order.
+void Index::label_lookup(uint32_t column, const uint32_t *codes, uint64_t n_codes, uint64_t *out_first, uint64_t *out_counts) {
+    const std::string bad = label_lookup_check(column, codes, n_codes);
+    VDB_REQUIRE(bad.empty(), bad);
+    VDB_REQUIRE(n_codes == 0 || (out_first && out_counts), "null argument");
+    const LookupPlan plan = label_lookup_plan(codes, n_codes, label_lookup_table_bytes);
+    uint64_t passes = 0;
+    if (n_codes && n) {
+        use_device();
+        WsLease ws(*this);
+        hipStream_t s = ws->stream;
+        const uint32_t *col = label_col(column);
+        ws->keys_a.reserve(n_codes * sizeof(uint32_t));
+        ws->misc.reserve(2 * n_codes * sizeof(uint32_t));
+        uint32_t *d_cnt = ws->misc.as<uint32_t>(), *d_first = d_cnt + n_codes;
+        uint32_t *h_out = static_cast<uint32_t *>(ws->pinned(2 * n_codes * sizeof(uint32_t)));
+        std::vector<uint32_t> h_table, h_slot, c_sorted, c_slot;  // (alive until the stream has been synchronised)
+        prof_begin(*ws, "label_lookup", double(plan.chunks) * double(n) * sizeof(uint32_t) + (plan.route == LOOKUP_DIRECT ? double(plan.span) * sizeof(uint32_t) : 0.0));
+        VDB_HIP(hipMemsetAsync(d_cnt, 0, n_codes * sizeof(uint32_t), s));
+        VDB_HIP(hipMemsetAsync(d_first, 0xFF, n_codes * sizeof(uint32_t), s));
+        if (plan.route == LOOKUP_DIRECT) {
+            ws->keys_b.reserve(plan.span * sizeof(uint32_t));
+            VDB_HIP(hipMemcpyAsync(ws->keys_a.p, codes, n_codes * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            VDB_HIP(hipMemsetAsync(ws->keys_b.p, 0xFF, plan.span * sizeof(uint32_t), s));
+            launch_lookup_table(ws->keys_a.as<uint32_t>(), n_codes, plan.base, (uint32_t)plan.span, ws->keys_b.as<uint32_t>(), num_cu, s);
+            launch_label_lookup_direct(col, ws->keys_b.as<uint32_t>(), plan.base, (uint32_t)plan.span,
+                                       plan.none_at == ~uint64_t(0) ? LOOKUP_NO_SLOT : (uint32_t)plan.none_at, n, d_cnt, d_first, num_cu,
+                                       label_lookup_max_blocks, s);
+            passes = 1;
+        } else {
+            h_table.resize(n_codes);
+            h_slot.resize(n_codes);
+            for (uint64_t g0 = 0; g0 < n_codes; g0 += PART_MAX_CHUNK) {
+                const uint32_t nb = (uint32_t)std::min<uint64_t>(PART_MAX_CHUNK, n_codes - g0);
+                mask_partition_layout(codes + g0, nb, c_sorted, c_slot);
+                std::copy(c_sorted.begin(), c_sorted.end(), h_table.begin() + g0);
+                std::copy(c_slot.begin(), c_slot.end(), h_slot.begin() + g0);
+            }
+            VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_table.data(), n_codes * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            for (uint64_t g0 = 0; g0 < n_codes; g0 += PART_MAX_CHUNK) {
+                const uint32_t nb = (uint32_t)std::min<uint64_t>(PART_MAX_CHUNK, n_codes - g0);
+                launch_label_lookup(col, ws->keys_a.as<uint32_t>() + g0, nb, n, d_cnt + g0, d_first + g0, num_cu, label_lookup_max_blocks, s);
+                passes++;
+            }
+        }
+        prof_end(*ws);
+        VDB_HIP(hipMemcpyAsync(h_out, d_cnt, 2 * n_codes * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        VDB_SYNC(s);
+        prof_collect(*ws);
+        for (uint64_t i = 0; i < n_codes; i++) {
+            const uint64_t j = plan.route == LOOKUP_DIRECT ? i : (i / PART_MAX_CHUNK) * PART_MAX_CHUNK + h_slot[i];
+            out_counts[j] = h_out[i];
+            out_first[j] = h_out[n_codes + i] == LOOKUP_ROW_NONE32 ? LOOKUP_ROW_NONE : uint64_t(h_out[n_codes + i]);
+        }
+    } else if (n_codes) {  // an empty index: no row carries anything
+        std::fill(out_counts, out_counts + n_codes, uint64_t(0));
+        std::fill(out_first, out_first + n_codes, LOOKUP_ROW_NONE);
+    }
+    label_lookup_calls += 1;
+    label_lookup_codes += n_codes;
+    label_lookup_direct += passes && plan.route == LOOKUP_DIRECT ? 1 : 0;
+    label_lookup_passes += passes;
 }
 
 }  // namespace vdb

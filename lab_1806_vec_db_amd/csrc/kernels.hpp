@@ -9,6 +9,7 @@
 #include "grouped_plan.hpp"
 #include "labels_scatter_plan.hpp"
 #include "like_plan.hpp"
+#include "lookup_plan.hpp"
 #include "mask_any.hpp"
 #include "mask_partition.hpp"
 #include "mask_sets.hpp"
@@ -439,6 +440,16 @@ void launch_mask_partition(const uint32_t *col, const uint32_t *table, uint32_t 
 // counts[i] += the rows allowed by bits (nullptr: every row) whose code is table[i]; the caller has zeroed counts [nb] on the same stream
 void launch_label_counts(const uint32_t *col, const uint32_t *table, uint32_t nb, const uint64_t *bits, uint64_t n, uint32_t *counts,
                          int num_cu, hipStream_t s);
+// The key lookup over one column (k_lookup.hip, lookup_plan.hpp): counts[i] += the rows whose code is entry i, first[i] = min(first[i],
+// the lowest such row); the caller has set counts [..] to zero and first [..] to LOOKUP_ROW_NONE32 on the same stream.  Sorted route:
+// table = a chunk's nb (<= PART_MAX_CHUNK) codes ascending, entry i = table[i].  Direct route: entry = slot_of[code - base] for codes in
+// [base, base + span), none_slot for LABEL_NONE (LOOKUP_NO_SLOT: not asked for); launch_lookup_table fills slot_of [span] (set to
+// LOOKUP_NO_SLOT by the caller) from the list's codes.  Grid: min(mask_where_blocks(n), max_blocks ? max_blocks : 8 x num_cu), grid-stride.
+void launch_label_lookup(const uint32_t *col, const uint32_t *table, uint32_t nb, uint64_t n, uint32_t *counts, uint32_t *first, int num_cu,
+                         uint32_t max_blocks, hipStream_t s);
+void launch_label_lookup_direct(const uint32_t *col, const uint32_t *slot_of, uint32_t base, uint32_t span, uint32_t none_slot, uint64_t n,
+                                uint32_t *counts, uint32_t *first, int num_cu, uint32_t max_blocks, hipStream_t s);
+void launch_lookup_table(const uint32_t *codes, uint64_t n_codes, uint32_t base, uint32_t span, uint32_t *slot_of, int num_cu, hipStream_t s);
 // The capped walk of the grouped k-NN (k_group.hip, grouped_plan.hpp): query b's list ids / dists [b][0 .. min(counts[b], ld)) walked in the order
 // given, at most g rows kept per value of `labels` (u32 per LOCAL row = id - id_offset; nullptr: a column never written; a row without a
 // label is always kept), the first k kept pairs to row slot_q[b] (nullptr: b) of out_idx / out_dist [..][k] with zeros behind them, their

@@ -79,6 +79,7 @@ def pack_mask(allow, n: int) -> np.ndarray:
 
 LABEL_COLUMNS = 16         # VDB_LABEL_COLUMNS
 LABEL_NONE = 0xFFFFFFFF    # VDB_LABEL_NONE
+ROW_NONE = 2 ** 64 - 1     # VDB_ROW_NONE: label_lookup's "no row carries the code"
 MASK_MAX_TERMS = 8         # VDB_MASK_MAX_TERMS
 MASK_OP_AND, MASK_OP_OR = 0, 1  # VDB_MASK_OP_AND / VDB_MASK_OP_OR
 LIKE_MAX_EXAMPLES = 1024   # examples of one query of flat_knn_like, positives plus negatives (LIKE_MAX_EXAMPLES of csrc/like_plan.hpp)
@@ -549,6 +550,38 @@ class GpuIndex:
         L.check(self._lib.vdb_index_label_counts(self._h, int(column), None if mask is None else mask._h, _ptr(c, L.u32p), c.shape[0],
                                                  _ptr(out, L.u64p)))
         return out
+
+    @classmethod
+    def _lookup_codes(cls, codes) -> np.ndarray:
+        """_codes_array, with a vectorised path for an integer array (a lookup may name a million codes)"""
+        if isinstance(codes, np.ndarray) and codes.dtype != np.bool_ and np.issubdtype(codes.dtype, np.integer):
+            a = codes.reshape(-1)
+            if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 32):
+                raise ValueError("label code out of range: a code is u32")
+            return np.ascontiguousarray(a, dtype=np.uint32)
+        return cls._codes_array(codes)
+
+    def label_lookup(self, column: int, codes):
+        """(first, counts), both uint64 of len(codes): counts[j] = the number of rows whose label in `column` equals codes[j], first[j] =
+        the lowest such row, ROW_NONE where there is none (vdb_index_label_lookup) -- from one read of the column when the codes are
+        many and dense (the direct route), one per 1024 codes otherwise.  The codes are distinct, in any order, LABEL_NONE (the
+        unlabelled rows) among them; a duplicate raises VdbError and nothing is counted."""
+        c = self._lookup_codes(codes)
+        first = np.full(c.shape[0], ROW_NONE, dtype=np.uint64)
+        counts = np.zeros(c.shape[0], dtype=np.uint64)
+        L.check(self._lib.vdb_index_label_lookup(self._h, int(column), _ptr(c, L.u32p), c.shape[0], _ptr(first, L.u64p), _ptr(counts, L.u64p)))
+        return first, counts
+
+    @classmethod
+    def label_lookup_plan(cls, column: int, codes, table_bytes: int = 64 << 20):
+        """(route, base, span, chunks) of a label_lookup over `codes` under a scratch cap of table_bytes (vdb_label_lookup_plan; host only,
+        no GPU): route 0 = sorted, 1 = direct; base / span over the codes other than LABEL_NONE; chunks = reads of the column.  Raises
+        VdbError for what label_lookup refuses."""
+        c = cls._lookup_codes(codes)
+        route, base, span, chunks = C.c_int(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+        L.check(L.load().vdb_label_lookup_plan(int(column), _ptr(c, L.u32p), c.shape[0], int(table_bytes), C.byref(route), C.byref(base),
+                                               C.byref(span), C.byref(chunks)))
+        return int(route.value), int(base.value), int(span.value), int(chunks.value)
 
     def make_mask_where_sets(self, terms) -> RowMask:
         """the mask of the rows that match EVERY LabelTerm of `terms` -- set and range predicates over the label columns, built on the

@@ -44,6 +44,9 @@ ride along, all of a call's from one bulk fetch (GpuIndex.get_rows / get_rows_ma
 update_metadata(key, pattern, changes) / batch_update_metadata change the METADATA of the matching rows in place: row ids, vectors, the
 HNSW graph and the PQ table stay, the live label columns are written by one scattered write on the device (GpuIndex.set_labels_mask /
 set_labels_rows), and only the cached masks whose filter names a changed key are dropped.
+upsert(key, id_field, vec, metadata) / batch_upsert write BY A KEY FIELD: an entry whose value of the field a row carries replaces that row's
+vector and metadata in place, the others are appended; get_by(key, field, values) fetches the rows that carry given values.  Both find
+their rows with ONE pass over the field's label column whatever the number of values (GpuIndex.label_lookup), not with a mask per value.
 """
 from __future__ import annotations
 
@@ -54,7 +57,7 @@ from contextlib import contextmanager
 import numpy as np
 
 from ._lib import VdbError
-from .index import FUSE_MAX_FETCH, LIKE_MAX_EXAMPLES, MMR_MAX_FETCH, GpuIndex, RowMask, parse_dist
+from .index import FUSE_MAX_FETCH, LIKE_MAX_EXAMPLES, MMR_MAX_FETCH, ROW_NONE, GpuIndex, RowMask, parse_dist
 from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, fuse_groups, filter_patterns, has_predicates, is_expression, stale_filters
 from .labels import matches as value_matches
 
@@ -66,6 +69,22 @@ _DIST_STR = {0: "l2sqr", 1: "cosine"}
 # at 2 .. 16 codes, by microseconds, and lost at 32, and batches of up to 50 patterns keep the one make_masks_where call they are
 # tested to make (docs/DESIGN_flat.md 4.1p has the sweep and the decision).
 PARTITION_MIN: int | None = 64
+
+# _Table.match_rows: the smallest group of uncached, plain, one-key patterns on one column whose rows are found by ONE
+# GpuIndex.label_lookup call -- the patterns that match at most one row are answered from it, the others join the make_masks_where call --
+# instead of a mask per pattern; None: never.  The rows are the same either way.  Never below 64: batches of up to 50 patterns keep the
+# one make_masks_where call they are tested to make.  In the sweep behind it, part B of tools/bench_lookup.py
+# (profiles/label_lookup_1M.json; docs/DESIGN_flat.md 4.1aa), the lookup won at every group size from 2 to 4096, by 4.5 x to 43 x, so the
+# value is that floor.
+LOOKUP_MIN: int | None = 64
+
+
+def _differ(a, b) -> bool:
+    """True unless two metadata values are known to be equal (a comparison that raises or answers with no bool counts as a change)"""
+    try:
+        return bool(a != b)
+    except Exception:
+        return True
 
 
 class _RwLock:
@@ -291,7 +310,9 @@ class _Table:
     def match_rows(self, patterns) -> list:
         """UNDER THE WRITE LOCK: per pattern the ascending rows it matches, as delete finds them: from a cached or device-built mask
         when the pattern's keys are label columns already (no key gets a column here), from the host loop otherwise; the plain patterns
-        not cached yet share ONE make_masks_where call."""
+        not cached yet share ONE make_masks_where call.  Among those, the patterns of exactly one (column, code) term are grouped by
+        column first, and a group of at least LOOKUP_MIN distinct codes goes through ONE label_lookup call: a pattern that matches no
+        row or one row is answered from it, one that matches more stays with the make_masks_where call."""
         matches: list = [None] * len(patterns)
         todo = []
         with self.mask_mu:
@@ -309,11 +330,57 @@ class _Table:
                     mk.close()
                 else:
                     todo.append((i, terms))
+        if todo and LOOKUP_MIN is not None:  # one-term patterns, by column and code: a large enough group is ONE read of its column
+            groups: dict[int, dict[int, list[int]]] = {}
+            for at, (_, terms) in enumerate(todo):
+                if len(terms) == 1:
+                    groups.setdefault(terms[0][0], {}).setdefault(terms[0][1], []).append(at)
+            done = set()
+            for col, by_code in groups.items():
+                if len(by_code) < LOOKUP_MIN:
+                    continue
+                first, counts = self.index.label_lookup(col, np.fromiter(by_code, dtype=np.uint64, count=len(by_code)))
+                for ats, f, c in zip(by_code.values(), first.tolist(), counts.tolist()):
+                    if c <= 1:  # (more rows than one: the pattern's mask lists them)
+                        for at in ats:
+                            matches[todo[at][0]] = np.array([f] if c else [], dtype=np.uint32)
+                        done.update(ats)
+            todo = [x for at, x in enumerate(todo) if at not in done]
         if todo:
             for (i, _), mk in zip(todo, self.index.make_masks_where([terms for _, terms in todo])):
                 matches[i] = mk.rows()[1]
                 mk.close()
         return matches
+
+    def find_values(self, field: str, values):
+        """UNDER THE TABLE'S LOCK: (first, counts, rows_of) for the DISTINCT hashable `values` of the metadata key `field` (None: the rows
+        without the key) -- counts[j] = the rows whose metadata carries values[j], first[j] = the lowest of them (ROW_NONE: none),
+        both uint64.  With a usable label column (LabelCodec.value_codes): values the dictionary has never seen match nothing and do not
+        grow it, the others go through ONE label_lookup call, and rows_of is None.  Otherwise -- no column (a 17th key), or a dictionary
+        that holds the stand-in for unhashable values -- ONE pass over the metadata builds rows_of: value -> its ascending rows."""
+        first = np.full(len(values), ROW_NONE, dtype=np.uint64)
+        counts = np.zeros(len(values), dtype=np.uint64)
+        if self.codec.value_codes(field) is not None:
+            col = self.codec.column_of(field)
+            table = self.codec.codes[col]
+            known = [(j, LABEL_NONE if v is None else table[v]) for j, v in enumerate(values) if v is None or v in table]
+            if known:
+                at = [j for j, _ in known]
+                first[at], counts[at] = self.index.label_lookup(col, np.array([c for _, c in known], dtype=np.uint64))
+            return first, counts, None
+        rows_of: dict[object, list[int]] = {v: [] for v in values}
+        for r, m in enumerate(self.metadata):
+            v = m.get(field)
+            try:
+                hit = rows_of.get(v)
+            except TypeError:  # (an unhashable row value equals no value asked for)
+                continue
+            if hit is not None:
+                hit.append(r)
+        for j, v in enumerate(values):
+            if rows_of[v]:
+                first[j], counts[j] = rows_of[v][0], len(rows_of[v])
+        return first, counts, rows_of
 
     def next_seed(self) -> int:
         self.seed = (self.seed * 6364136223846793005 + 1442695040888963407) & ((1 << 64) - 1)
@@ -435,8 +502,8 @@ class VecDB:
         keep their ids and their metadata, nothing else moves, and the table's cached filter masks stay valid (a filter is a set of rows,
         and the set did not change).  One library call for the whole batch; like delete it clears the HNSW index and the PQ table first --
         unless nothing matched, then nothing at all is changed.
-        The METADATA of existing rows is changed by update_metadata / batch_update_metadata.  An upsert is batch_update plus batch_add of
-        what matched nothing."""
+        The METADATA of existing rows is changed by update_metadata / batch_update_metadata.  An upsert -- batch_update plus batch_add of
+        what matched nothing -- is batch_upsert, which finds its rows in one pass over the key's column."""
         t = self._t(key)
         patterns = list(patterns)
         for p in patterns:
@@ -542,6 +609,111 @@ class VecDB:
                     self._apply_changes(t.metadata[r], ch)
                 t.drop_masks_naming(changed)
             return [int(len(m)) for m in matches]
+
+    def upsert(self, key: str, id_field: str, vec, metadata: dict[str, str]) -> tuple[int, int]:
+        """batch_upsert of one entry."""
+        return self.batch_upsert(key, id_field, [vec], [metadata])
+
+    def batch_upsert(self, key: str, id_field: str, vec_list, metadata_list) -> tuple[int, int]:
+        """The idempotent write by a key field: entry i is (vec_list[i], metadata_list[i]), and metadata_list[i][id_field] -- a str --
+        names it.  A value no row carries: the entry is appended, in the batch order of the surviving entries.  A value ONE row carries:
+        that row gets the new vector and its metadata dict is REPLACED by the new one; its row id is kept.  A value several rows carry:
+        ValueError naming it -- the key is not unique -- and nothing at all is changed.  Two entries with the same value: the LAST one
+        wins and the earlier ones are dropped (batch_update's rule).  Returns (rows updated, rows added).
+        `id_field` gets a label column on first use, as count_by's field does, and the rows are found by ONE GpuIndex.label_lookup call
+        over the values the column's dictionary knows (a value it has never seen matches nothing and does not grow it for the lookup).
+        A key that cannot have a column (a 17th key) or whose dictionary holds the stand-in for unhashable values is looked up by one
+        pass over the metadata.  Everything is validated before anything changes; then hnsw_clear / pq_clear as batch_update does them
+        when a row is updated (pq_clear alone, as batch_add, when rows are only added), ONE update_rows, ONE set_labels_rows over the
+        updated rows and every live column, ONE batch_add with set_labels per live column, the host dicts.  Masks: all dropped when a
+        row was added; otherwise exactly those whose filter names a key whose value changed in some updated row."""
+        t = self._t(key)
+        rows = np.asarray(vec_list, dtype=np.float32)
+        metadata_list = list(metadata_list)
+        if len(metadata_list) == 0 and rows.size == 0:
+            return 0, 0
+        if rows.ndim != 2 or rows.shape[1] != t.index.dim:  # (batch_add's checks and wording)
+            raise RuntimeError(f"Dimension mismatch: table dim {t.index.dim}, got {rows.shape}")
+        if len(metadata_list) != rows.shape[0]:
+            raise RuntimeError("vec_list and metadata_list differ in length")
+        last: dict[str, int] = {}
+        for i, m in enumerate(metadata_list):
+            v = m.get(id_field) if isinstance(m, dict) else None
+            if not isinstance(v, str):
+                raise ValueError(f"upsert: entry {i} carries no str value of {id_field!r}")
+            last[v] = i
+        keep = sorted(last.values())  # the surviving entries, in batch order
+        values = [metadata_list[i][id_field] for i in keep]
+        with t.lock.write():
+            if t.codec.column_of(id_field) is None:
+                t.create_columns([{id_field: None}])  # (taken back if its write fails; a 17th key gets none)
+            first, counts, _ = t.find_values(id_field, values)
+            many = np.flatnonzero(counts > 1)
+            if many.size:
+                j = int(many[0])
+                raise ValueError(f"upsert: {id_field} = {values[j]!r} is carried by {int(counts[j])} rows: the key is not unique")
+            upd = np.flatnonzero(counts == 1)
+            add = np.flatnonzero(counts == 0)
+            live = t.codec.keys()
+            if upd.size:
+                t.index.hnsw_clear()
+            t.index.pq_clear()
+            changed: dict[str, None] = {}
+            if upd.size:
+                urows = first[upd]
+                new = [metadata_list[keep[j]] for j in upd.tolist()]
+                t.index.update_rows(urows, rows[[keep[j] for j in upd.tolist()]])
+                if live:
+                    codes = np.empty((len(live), len(new)), dtype=np.uint32)
+                    for c, k in enumerate(live):
+                        codes[c] = [t.codec.encode_value(k, m.get(k)) for m in new]
+                    t.index.set_labels_rows(urows, [t.codec.column_of(k) for k in live], codes)
+            if add.size:
+                fresh = [dict(metadata_list[keep[j]]) for j in add.tolist()]
+                first_new = len(t.metadata)
+                t.index.batch_add(rows[[keep[j] for j in add.tolist()]])
+                for k in live:
+                    t.index.set_labels(t.codec.column_of(k), t.codec.encode_rows(k, fresh), first_row=first_new)
+            if upd.size:
+                for r, m in zip(urows.tolist(), new):
+                    old = t.metadata[r]
+                    changed.update(dict.fromkeys(k for k in old.keys() | m.keys() if _differ(old.get(k), m.get(k))))
+                    t.metadata[r] = dict(m)
+            if add.size:
+                t.metadata.extend(fresh)
+                t.drop_masks()
+            elif changed:
+                t.drop_masks_naming(changed)
+            return int(upd.size), int(add.size)
+
+    def get_by(self, key: str, field: str, values, with_vectors: bool = False) -> list:
+        """The fetch by a key field: per entry of `values` (hashable; None: the rows without the key) the list of (metadata,) -- or
+        (metadata, vector) with `with_vectors` -- of the rows whose metadata carries it under `field`, ascending by row; a value no row
+        carries, or one never seen, gives [].  `field` gets a label column on first use, as a filter key does; the rows come from ONE
+        GpuIndex.label_lookup call, the few values that several rows carry from ONE make_masks_where call on top of it, and all vectors
+        from ONE get_rows call.  A field without a usable column takes one pass over the metadata instead."""
+        t = self._t(key)
+        values = list(values)
+        distinct = list(dict.fromkeys(values))
+        t.prepare([{field: None}])
+        with t.lock.read():
+            first, counts, rows_of = t.find_values(field, distinct)
+            if rows_of is None:
+                rows_of = {v: [int(f)] if c == 1 else [] for v, f, c in zip(distinct, first.tolist(), counts.tolist())}
+                many = [v for v, c in zip(distinct, counts.tolist()) if c > 1]
+                if many:
+                    col = t.codec.column_of(field)
+                    table = t.codec.codes[col]
+                    for v, mk in zip(many, t.index.make_masks_where([[(col, LABEL_NONE if v is None else table[v])] for v in many])):
+                        rows_of[v] = mk.rows()[1].tolist()
+                        mk.close()
+            flat = [r for v in values for r in rows_of[v]]
+            if not with_vectors:
+                it = iter((dict(t.metadata[r]),) for r in flat)
+            else:
+                vecs = t.index.get_rows(np.array(flat, dtype=np.uint64)) if flat else np.zeros((0, t.index.dim), dtype=np.float32)
+                it = iter((dict(t.metadata[r]), vecs[j].copy()) for j, r in enumerate(flat))
+            return [[next(it) for _ in rows_of[v]] for v in values]
 
     def build_hnsw_index(self, key: str, ef_construction: int | None = None) -> None:
         t = self._t(key)
