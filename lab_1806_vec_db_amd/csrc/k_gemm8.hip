@@ -165,9 +165,14 @@ __global__ __launch_bounds__(512, 1) void k_flat_gemm8(Gemm8Args a) {
     for (int t = 0; t < TW; t++) voff[t] = lane * 16 + t * KB * 1024;
     uint4 ring[R][TW];
     auto fetch_at = [&](uint4(&dst)[TW], const char *base, uint32_t kb) {
-        const char *sb = base + kb * 1024;  // scalar
+        const char *sb = base + kb * 1024;  // scalar: a 64-bit base per unit and k-block (mirrors beyond 4 GB), 32-bit lane offsets below it
 #pragma unroll
         for (int t = 0; t < TW; t++) {
+            // The widening of the lane offset has to stand in the load's own block: -O3 hoists a plain zero-extension out of the loops,
+            // the load then loses its scalar-base form (global_load v, s[base:base+1]) and every refill pays a 64-bit vector add for its
+            // address -- 15 v_lshl_add_u64 per chunk in the wave's OWN matrix stream, and 6 offset registers instead of 3.  Made opaque in
+            // place it costs no instruction (on a copy: a move per load).  1M x 960: filter 0.821 -> 0.803 ms (profiles/gemm8_unit_valu_ab.txt)
+            asm volatile("" : "+v"(voff[t]));
             if constexpr (XNT) {
                 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                 dst[t] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(sb + voff[t])));
