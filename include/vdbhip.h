@@ -479,6 +479,51 @@ int vdb_label_lookup_plan(uint32_t column, const uint32_t *codes, uint64_t n_cod
 int vdb_index_label_lookup(vdb_index *idx, uint32_t column, const uint32_t *codes, uint64_t n_codes, uint64_t *out_first /* [n_codes] */,
                            uint64_t *out_counts /* [n_codes] */);
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids);
+/* ---- near-duplicate grouping: a range self-join over the table's own rows and the connected components of its pairs ---------------------
+ * "Which rows are copies, or near copies, of each other?"  (csrc/dup_plan.hpp, csrc/flat_dups.hip, csrc/k_components.hip;
+ * docs/DESIGN_flat.md 4.1ab.)  The reference has no counterpart; this is the rule.
+ *   EDGES.  For every allowed row i (all rows, or the rows of `mask`) take the list vdb_flat_range / vdb_flat_range_filtered returns for
+ *     query = row i, radius, limit and the mask: every allowed row j with D(row j, row i) <= radius in the (distance, index) order, the first
+ *     `limit` of them when limit > 0.  Every j != i on it is an edge {i, j}.  Edges are undirected: one exists if either end lists the
+ *     other, so nothing rests on D being symmetric in its last bit.
+ *   GROUPS.  The connected components of the allowed rows under these edges.  This is SINGLE LINKAGE at the radius: A-B and B-C put A and
+ *     C into one group even when D(A, C) > radius.
+ *   REPRESENTATIVE.  A group is named by its lowest row: out_group[i] = that LOCAL row + id_offset; a row alone in its group gets its own
+ *     id, a row outside the mask VDB_ROW_NONE.
+ *   What follows from the range search as it stands: a row with a NaN distance to everything is alone; identical rows are linked at
+ *     radius 0; a negative radius links nothing; radius = +inf gives one group (of the rows without NaN); a disallowed row never bridges
+ *     two allowed ones.
+ *   LIMIT.  With limit > 0 a list may be cut; every edge is still a true one, so each returned group is a SUBSET of a true component and
+ *     never a union of two.  out_stats[3] counts the rows whose list reached `limit`.
+ *   out_stats [4]: groups of at least 2 rows | rows in them | non-self pairs seen (a pair both ends list counts twice) | truncated rows.
+ *   The answer is a pure function of table, radius, mask and limit: not of launch order, "flat_dup_chunk" or run.
+ * How: the allowed rows are the queries, "flat_dup_chunk" of them per range call (vdb_set_param; default 16384) -- in place on an unfiltered
+ * f32 index, gathered (u8 rows: widened) otherwise; each chunk's CSR result is hooked into a union-find over 4 B per row (a lane per
+ * pair, roots hooked under LOWER roots by an integer compare-and-swap, path halving; no float atomics, no waiting on another thread) and
+ * dropped before the next chunk.  Peak memory: one chunk's range result + 8 B per row + the chunk's gathered queries.  The range calls
+ * under it advance the "flat_range_*" counters as always and obey "flat_range_max_results" PER CHUNK.
+ * Refused, outputs and the three counters below untouched: a NaN radius (VDB_ERR_INVALID), a mask of another index (VDB_ERR_INVALID) or a
+ * stale one (VDB_ERR_STATE), a NULL output; a chunk whose range call fails fails the whole call the same way.  `limit` has no cap (the
+ * range call has none).  An empty index succeeds (stats 0).  Read-side, re-entrant, f32 and VecSet<u8> indexes; both forms return
+ * synchronised; the _device form writes d_out_group (u64 [len], 8-byte aligned, on the index's GPU) after waiting for `stream`.
+ * vdb_link_pairs_device: the component stage alone over a caller-supplied CSR edge list on the index's GPU -- d_src [nq] the u64 ids of the
+ *   lists' source rows, d_lims [nq + 1] u64 ascending from 0, d_ids [d_lims[nq]] u64 ids (row + id_offset, as the range calls write
+ *   them; non-NULL whenever nq > 0), d_group [len] u64.  The limits and every id are checked on the device first; ONE read-back, and a
+ *   descending limit or an id that is no row fails the call (VDB_ERR_INVALID) before any output is written, as vdb_group_cap_device does.
+ *   Every row is allowed; out_stats[3] is 0.  nq == 0: every row alone.
+ * vdb_dup_plan: host utility, works without a GPU: the argument check and, for (n_rows, dim, element type, masked, allowed rows, chunk),
+ *   the number of range calls, the last chunk's length, whether the queries are gathered, and the scratch bytes besides a chunk's
+ *   result.  Any output may be NULL; on an error nothing is written.
+ * vdb_get_stat: "flat_dup_calls" (calls that succeeded), "flat_dup_chunks" (their range calls), "flat_dup_pairs" (non-self pairs they
+ * saw).  vdb_prof_get "dup_hook" / "dup_flatten" time the component kernels. */
+int vdb_dup_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m_allowed, float radius, uint64_t limit, uint64_t chunk,
+                 uint64_t *out_chunks, uint64_t *out_last, int *out_gather, uint64_t *out_scratch_bytes);
+int vdb_flat_dup_groups(vdb_index *idx, float radius, uint64_t limit, const vdb_mask *mask /* NULL: all rows */, uint64_t *out_group /* [len] */,
+                        uint64_t *out_stats /* [4] */);
+int vdb_flat_dup_groups_device(vdb_index *idx, float radius, uint64_t limit, const vdb_mask *mask, void *d_out_group, uint64_t *out_stats,
+                               void *stream);
+int vdb_link_pairs_device(vdb_index *idx, const void *d_src, const void *d_lims, const void *d_ids, uint64_t nq, void *d_group,
+                          uint64_t *out_stats, void *stream);
 /* ---- grouped Flat k-NN: at most group_size hits per value of one label column -----------------------------------------------------------
  * "The 10 nearest chunks, at most 2 per document": the label columns so far restrict WHICH rows may be found; this call shapes the answer.
  * For one query let L be its allowed rows in FlatIndex::knn's order -- ascending by (distance, id), NaN distances last; all rows, or
@@ -910,6 +955,8 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *                        vdb_index_label_counts calls; "label_columns": allocated columns,
  *   "label_lookup_calls" vdb_index_label_lookup calls that were accepted; "label_lookup_codes": the codes they named;
  *                        "label_lookup_direct": the calls that ran the direct route; "label_lookup_passes": reads of the column, summed,
+ *   "flat_dup_calls"     vdb_flat_dup_groups / _device calls that succeeded; "flat_dup_chunks": the range calls under them;
+ *                        "flat_dup_pairs": the non-self pairs they saw,
  *   "update_calls"       vdb_index_update_rows / _device calls that changed rows (m > 0, not refused); "update_rows": the rows they rewrote,
  *   "fetch_calls"        vdb_index_get_rows* calls that fetched rows (m > 0, not refused); "fetch_rows": the rows they returned;
  *                        "fetch_chunks": their gather launches; "fetch_direct": the calls answered by one plain copy,

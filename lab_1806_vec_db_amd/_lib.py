@@ -73,6 +73,10 @@ SIGNATURES = {
     "vdb_index_label_counts": [vp, C.c_uint32, vp, u32p, u64, u64p],
     "vdb_label_lookup_plan": [C.c_uint32, u32p, u64, u64, intp, u32p, u64p, u64p],
     "vdb_index_label_lookup": [vp, C.c_uint32, u32p, u64, u64p, u64p],
+    "vdb_dup_plan": [u64, u64, C.c_int, C.c_int, u64, C.c_float, u64, u64, u64p, u64p, intp, u64p],
+    "vdb_flat_dup_groups": [vp, C.c_float, u64, vp, u64p, u64p],
+    "vdb_flat_dup_groups_device": [vp, C.c_float, u64, vp, vp, u64p, vp],
+    "vdb_link_pairs_device": [vp, vp, vp, vp, u64, vp, u64p, vp],
     "vdb_mask_rows": [vp, u64p, u32p],
     "vdb_flat_knn_filtered": [vp, f32p, u64, u64, u64, vp, u64p, f32p, u64p],
     "vdb_flat_knn_filtered_device": [vp, vp, u64, u64, u64, vp, vp, vp, vp, vp],

@@ -910,6 +910,81 @@ int vdb_index_label_lookup(vdb_index *idx, uint32_t column, const uint32_t *code
     idx->ix.label_lookup(column, codes, n_codes, out_first, out_counts);
     VDB_API_END
 }
+// near-duplicate grouping: the range self-join and the components of its pairs (Index::flat_dup_groups_device, dup_plan.hpp, flat_dups.hip)
+int vdb_dup_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m_allowed, float radius, uint64_t limit, uint64_t chunk,
+                 uint64_t *out_chunks, uint64_t *out_last, int *out_gather, uint64_t *out_scratch_bytes) {
+    VDB_API_BEGIN
+    (void)limit;  // (the range call has no cap on it)
+    const std::string bad = dup_check_args(n_rows, m_allowed, masked != 0, radius, chunk);
+    VDB_REQUIRE(bad.empty(), bad);
+    const DupPlan p = dup_plan(n_rows, dim, elem_u8 != 0, masked != 0, m_allowed, chunk);
+    if (out_chunks) *out_chunks = p.n_chunks;
+    if (out_last) *out_last = p.last_len;
+    if (out_gather) *out_gather = p.gather ? 1 : 0;
+    if (out_scratch_bytes) *out_scratch_bytes = p.scratch_bytes;
+    VDB_API_END
+}
+// what both forms refuse before a workspace is taken -> the mask as a RowMask (nullptr: all rows)
+static const RowMask *dup_groups_check(const Index &ix, float radius, const vdb_mask *mask, const void *out_group, const void *out_stats) {
+    VDB_REQUIRE(out_stats && (ix.n == 0 || out_group), "dup groups: null argument");
+    if (mask) ix.check_mask(mask->m);
+    const std::string bad = dup_check_args(ix.n, mask ? mask->m.m : ix.n, mask != nullptr, radius, ix.dup_chunk);
+    VDB_REQUIRE(bad.empty(), bad);
+    return mask ? &mask->m : nullptr;
+}
+int vdb_flat_dup_groups(vdb_index *idx, float radius, uint64_t limit, const vdb_mask *mask, uint64_t *out_group, uint64_t *out_stats) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const RowMask *rm = dup_groups_check(ix, radius, mask, out_group, out_stats);
+    ix.use_device();
+    WsLease ws(ix);
+    DevBuf d_group;
+    d_group.reserve(std::max<uint64_t>(ix.n, 1) * sizeof(uint64_t));
+    uint64_t stats[DUP_STATS];
+    run_synced(ix, *ws, [&] {
+        ix.flat_dup_groups_device(*ws, radius, limit, rm, d_group.as<uint64_t>(), stats);
+        if (ix.n) VDB_HIP(hipMemcpyAsync(out_group, d_group.p, ix.n * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+        VDB_SYNC(ws->stream);
+    });
+    std::memcpy(out_stats, stats, sizeof(stats));
+    VDB_API_END
+}
+int vdb_flat_dup_groups_device(vdb_index *idx, float radius, uint64_t limit, const vdb_mask *mask, void *d_out_group, uint64_t *out_stats, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const RowMask *rm = dup_groups_check(ix, radius, mask, d_out_group, out_stats);
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_out_group) % 8 == 0, "dup groups: d_out_group must be 8-byte aligned");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever last used the output on the caller's stream
+    uint64_t stats[DUP_STATS];
+    run_synced(ix, *ws, [&] { ix.flat_dup_groups_device(*ws, radius, limit, rm, static_cast<uint64_t *>(d_out_group), stats); });
+    std::memcpy(out_stats, stats, sizeof(stats));
+    VDB_API_END
+}
+int vdb_link_pairs_device(vdb_index *idx, const void *d_src, const void *d_lims, const void *d_ids, uint64_t nq, void *d_group, uint64_t *out_stats,
+                          void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    VDB_REQUIRE(out_stats && (ix.n == 0 || d_group) && (nq == 0 || (d_src && d_lims && d_ids)), "link pairs: null argument");
+    VDB_REQUIRE(nq < (1ull << 32), "link pairs: too many lists for one call");
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % 8 == 0 && reinterpret_cast<uintptr_t>(d_lims) % 8 == 0 && reinterpret_cast<uintptr_t>(d_ids) % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(d_group) % 8 == 0,
+                "link pairs: the device arrays must be 8-byte aligned");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the lists on the caller's stream
+    uint64_t stats[DUP_STATS];
+    run_synced(ix, *ws, [&] {
+        ix.link_pairs_device(*ws, static_cast<const uint64_t *>(d_src), static_cast<const uint64_t *>(d_lims), static_cast<const uint64_t *>(d_ids), nq,
+                             static_cast<uint64_t *>(d_group), stats);
+    });
+    std::memcpy(out_stats, stats, sizeof(stats));
+    VDB_API_END
+}
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids) {
     VDB_API_BEGIN
     VDB_REQUIRE(m, "null mask");
@@ -1737,6 +1812,10 @@ int vdb_set_param(vdb_index *idx, const char *name, int64_t value) {
         VDB_REQUIRE(value >= 0 && value <= 0x7FFFFFFF, "label_lookup_max_blocks must be in 0 .. 2^31-1");
         idx->ix.label_lookup_max_blocks = (uint32_t)value;
     }
+    else if (n == "flat_dup_chunk") {  // near-duplicate grouping: queries (rows of the table) per range call of the self-join
+        VDB_REQUIRE(value >= 1 && (uint64_t)value <= DUP_CHUNK_MAX, "flat_dup_chunk must be in 1 .. 2^20");
+        idx->ix.dup_chunk = (uint64_t)value;
+    }
     else if (n == "debug_alloc_fail_over")  // (testing aid, process-wide) device allocations of at least this many bytes fail; 0 = off
         devbuf_fail_over() = (size_t)value;
     else if (n == "flat_i8_unit_min")  // threshold sample of the 8-bit pass: one value per sampled unit when the units are many (0 auto, 1 off, 2 on from 2 x rank units: tests)
@@ -1917,6 +1996,12 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.label_lookup_direct.load();
     else if (n == "label_lookup_passes")
         *out = idx->ix.label_lookup_passes.load();
+    else if (n == "flat_dup_calls")  // vdb_flat_dup_groups / _device: calls that succeeded | range calls (chunks) under them | non-self pairs they saw
+        *out = idx->ix.dup_calls.load();
+    else if (n == "flat_dup_chunks")
+        *out = idx->ix.dup_chunks.load();
+    else if (n == "flat_dup_pairs")
+        *out = idx->ix.dup_pairs.load();
     else if (n == "flat_grouped_calls")  // grouped k-NN: calls | queries | rounds run, summed over calls | queries whose last list was their whole allowed set
         *out = idx->ix.grouped_calls.load();
     else if (n == "flat_grouped_queries")

@@ -760,6 +760,22 @@ struct Index {
                             uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, uint32_t column, uint64_t trunc_len, uint64_t *d_idx,
                             float *d_dist, uint64_t *d_cnt, uint8_t *d_exact);
     std::atomic<uint64_t> fused_groups_calls{0}, fused_groups_queries{0}, fused_groups_lists{0};
+    // Near-duplicate grouping (flat_dups.hip, k_components.hip, dup_plan.hpp; docs/DESIGN_flat.md 4.1ab): the connected components of the
+    // allowed rows (mask == nullptr: all rows) under the edges {i, j}, j != i on the list flat_range_device returns for query = row i at
+    // `radius` under `limit` and the mask -- SINGLE LINKAGE at the radius.  d_group [n] u64 on the device: the lowest row of row i's
+    // component + id_offset, DUP_ROW_NONE for a row outside the mask; stats [DUP_STATS] on the host: groups of >= 2 rows, rows in them,
+    // non-self pairs seen, rows whose list reached `limit`.  The allowed rows are walked in chunks of dup_chunk queries: in place on an
+    // unfiltered f32 index, gathered (widened) into ws.grp_q otherwise; ONE flat_range_device call per chunk, whose counters advance as for
+    // that call, its result hooked and dropped.  Read-side, re-entrant; d_group, stats and the dup_* counters are written only when every
+    // chunk has succeeded.  The caller has run dup_check_args; the mask is checked here.  Returns synchronised.
+    void flat_dup_groups_device(Workspace &ws, float radius, uint64_t limit, const RowMask *mask, uint64_t *d_group, uint64_t *stats);
+    // The component stage alone over a caller-supplied CSR edge list on the device: d_src [nq] u64 ids of the lists' source rows, d_lims
+    // [nq + 1] from 0, d_ids [d_lims[nq]] u64 ids.  Limits and every id are checked on the device first (one read-back: the flag and the
+    // pair count; a bad one throws before an output is written).  stats as above, truncated = 0.  Returns synchronised.
+    void link_pairs_device(Workspace &ws, const uint64_t *d_src, const uint64_t *d_lims, const uint64_t *d_ids, uint64_t nq, uint64_t *d_group,
+                           uint64_t *stats);
+    uint64_t dup_chunk = DUP_CHUNK_DEFAULT;  // "flat_dup_chunk": queries per range call of the self-join
+    std::atomic<uint64_t> dup_calls{0}, dup_chunks{0}, dup_pairs{0};  // flat_dup_groups calls that succeeded / their range calls / non-self pairs they saw
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};

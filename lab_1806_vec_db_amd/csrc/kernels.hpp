@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "dup_plan.hpp"
 #include "fuse_groups_plan.hpp"
 #include "fuse_plan.hpp"
 #include "grouped_plan.hpp"
@@ -450,6 +451,22 @@ void launch_label_lookup(const uint32_t *col, const uint32_t *table, uint32_t nb
 void launch_label_lookup_direct(const uint32_t *col, const uint32_t *slot_of, uint32_t base, uint32_t span, uint32_t none_slot, uint64_t n,
                                 uint32_t *counts, uint32_t *first, int num_cu, uint32_t max_blocks, hipStream_t s);
 void launch_lookup_table(const uint32_t *codes, uint64_t n_codes, uint32_t base, uint32_t span, uint32_t *slot_of, int num_cu, hipStream_t s);
+// Connected components over CSR edge lists (k_components.hip, dup_plan.hpp): a union-find over parent [n] (u32 per row), size [n] beside it.
+// init: parent[i] = i, size[i] = 0.  hook: the pairs [0, total) of a CSR list over nq queries (lims [nq + 1] from 0, ids u64 = row +
+// id_offset, checked by the caller); query q's source row is src64[q] - id_offset, else src32[q], else src_base + q; roots are hooked under
+// lower roots by atomicCAS; counters[2] += the pairs whose ends differ, counters[3] += the lists of exactly `limit` entries (limit > 0).
+// flatten: parent[i] = its root, group[i] = root + id_offset (DUP_ROW_NONE for a row bits -- nullptr: every row -- does not allow),
+// size[root] = its rows, counters[0] += the roots of at least 2 rows, counters[1] += the rows under them.  counters: 4 u64, zeroed by the
+// caller.  Integer atomics only: the answer does not depend on the order of waves.
+void launch_comp_init(uint32_t *parent, uint32_t *size, uint64_t n, int num_cu, hipStream_t s);
+void launch_comp_hook(const uint64_t *src64, const uint32_t *src32, uint64_t src_base, const uint64_t *lims, const uint64_t *ids, uint64_t nq,
+                      uint64_t total, uint64_t id_offset, uint64_t limit, uint32_t *parent, uint64_t *counters, int num_cu, hipStream_t s);
+void launch_comp_flatten(uint32_t *parent, const uint64_t *bits, uint64_t n, uint64_t id_offset, uint64_t *group, uint32_t *size, uint64_t *counters,
+                         int num_cu, hipStream_t s);
+// out[0] |= 1 when lims[0] != 0, the limits descend, or some src[q] / ids[j < lims[nq]] is no row of the index; out[1] = lims[nq]; out
+// zeroed by the caller; nq > 0
+void launch_pairs_check(const uint64_t *src, const uint64_t *lims, const uint64_t *ids, uint64_t nq, uint64_t n, uint64_t id_offset, uint64_t *out,
+                        int num_cu, hipStream_t s);
 // The capped walk of the grouped k-NN (k_group.hip, grouped_plan.hpp): query b's list ids / dists [b][0 .. min(counts[b], ld)) walked in the order
 // given, at most g rows kept per value of `labels` (u32 per LOCAL row = id - id_offset; nullptr: a column never written; a row without a
 // label is always kept), the first k kept pairs to row slot_q[b] (nullptr: b) of out_idx / out_dist [..][k] with zeros behind them, their

@@ -583,6 +583,56 @@ class GpuIndex:
                                                C.byref(span), C.byref(chunks)))
         return int(route.value), int(base.value), int(span.value), int(chunks.value)
 
+    @staticmethod
+    def _dup_limit(limit) -> int:
+        if limit is not None and int(limit) <= 0:
+            raise ValueError("limit must be positive (None: no limit)")
+        return int(limit or 0)
+
+    def dup_groups(self, radius: float, mask: RowMask | None = None, limit: int | None = None):
+        """Near-duplicate groups of the index's own rows (vdb_flat_dup_groups): (group, stats).  Row i's neighbours are the rows
+        range_search(query = row i, radius, limit, mask) lists; every listed j != i is an undirected edge; the groups are the connected
+        components of the allowed rows (all rows, or the mask's) under these edges.  This is SINGLE LINKAGE at the radius: A-B and B-C put
+        A and C into one group even when d(A, C) > radius.  group: uint64 [len], the LOWEST row of row i's group + id_offset (its own id
+        for a row alone), ROW_NONE for a row outside the mask.  stats: dict with `groups` (of at least 2 rows), `rows` (in them), `pairs`
+        (non-self pairs seen) and `truncated` (rows whose list reached `limit`: with a limit a group is a subset of a true component,
+        never a union of two).  A NaN radius and a stale or foreign mask raise VdbError."""
+        group = np.full(len(self), ROW_NONE, dtype=np.uint64)
+        stats = np.zeros(4, dtype=np.uint64)
+        L.check(self._lib.vdb_flat_dup_groups(self._h, float(radius), self._dup_limit(limit), None if mask is None else mask._h,
+                                              _ptr(group, L.u64p), _ptr(stats, L.u64p)))
+        return group, dict(zip(("groups", "rows", "pairs", "truncated"), (int(x) for x in stats)))
+
+    def dup_groups_device(self, radius: float, out_group_ptr: int, mask: RowMask | None = None, limit: int | None = None, stream: int = 0):
+        """the same with the group ids written to device memory (u64 [len], 8-byte aligned; vdb_flat_dup_groups_device); returns the
+        stats dict, synchronised"""
+        stats = np.zeros(4, dtype=np.uint64)
+        L.check(self._lib.vdb_flat_dup_groups_device(self._h, float(radius), self._dup_limit(limit), None if mask is None else mask._h,
+                                                     L.vp(out_group_ptr), _ptr(stats, L.u64p), L.vp(stream)))
+        return dict(zip(("groups", "rows", "pairs", "truncated"), (int(x) for x in stats)))
+
+    def link_pairs_device(self, src_ptr: int, lims_ptr: int, ids_ptr: int, nq: int, out_group_ptr: int, stream: int = 0):
+        """the component stage alone over a caller-supplied CSR edge list on the device (vdb_link_pairs_device): src u64 [nq] the ids of
+        the lists' source rows, lims u64 [nq + 1] ascending from 0, ids u64 [lims[nq]] (row + id_offset, as the range calls write them),
+        out_group u64 [len]: the lowest row of each row's component + id_offset (single linkage over the listed pairs).  Limits that
+        descend or an id that is no row of this index raise and leave the output untouched.  Returns the stats dict (truncated = 0)."""
+        stats = np.zeros(4, dtype=np.uint64)
+        L.check(self._lib.vdb_link_pairs_device(self._h, L.vp(src_ptr), L.vp(lims_ptr), L.vp(ids_ptr), int(nq), L.vp(out_group_ptr),
+                                                _ptr(stats, L.u64p), L.vp(stream)))
+        return dict(zip(("groups", "rows", "pairs", "truncated"), (int(x) for x in stats)))
+
+    @staticmethod
+    def dup_plan(n_rows: int, dim: int, radius: float, m_allowed: int | None = None, chunk: int = 16384, elem_u8: bool = False,
+                 limit: int | None = None):
+        """(chunks, last, gather, scratch_bytes) of a dup_groups call (vdb_dup_plan; host only, no GPU): the range calls it makes, the
+        queries of the last one, whether the queries are gathered (a mask -- m_allowed given -- or u8 rows) and the device bytes held
+        besides one chunk's range result.  Raises VdbError for what dup_groups refuses by its arguments (a NaN radius, a bad chunk)."""
+        masked = m_allowed is not None
+        chunks, last, gather, scratch = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_uint64()
+        L.check(L.load().vdb_dup_plan(int(n_rows), int(dim), int(bool(elem_u8)), int(masked), int(m_allowed if masked else n_rows), float(radius),
+                                      int(limit or 0), int(chunk), C.byref(chunks), C.byref(last), C.byref(gather), C.byref(scratch)))
+        return int(chunks.value), int(last.value), bool(gather.value), int(scratch.value)
+
     def make_mask_where_sets(self, terms) -> RowMask:
         """the mask of the rows that match EVERY LabelTerm of `terms` -- set and range predicates over the label columns, built on the
         device (vdb_mask_create_where_sets); no terms: every row"""

@@ -1220,6 +1220,86 @@ class VecDB:
             return [[(dict(t.metadata[int(i)]), float(d)) for i, d in zip(idx[int(lims[j]):int(lims[j + 1])], dist[int(lims[j]):int(lims[j + 1])])]
                     for j in range(nq)]
 
+    @staticmethod
+    def _dup_rows(t: _Table, radius: float, filter, limit):
+        """UNDER THE TABLE'S LOCK: (matched, groups, stats) of GpuIndex.dup_groups under the filter's mask -- matched: the ascending rows
+        the filter matches (None without a filter: every row); groups: the groups of at least two rows, each the ascending array of its
+        rows (so the representative, the lowest row, comes first), ordered by representative; stats: the call's dict."""
+        mk = None if filter is None else t.mask_for(filter)
+        group, stats = t.index.dup_groups(radius, mk, limit)
+        matched = None if mk is None else mk.rows()[1]
+        rows = np.arange(group.shape[0], dtype=np.int64) if matched is None else np.asarray(matched, dtype=np.int64)
+        counts = np.unique(group[rows], return_counts=True)[1]  # (per representative, ascending)
+        order = np.argsort(group[rows], kind="stable")      # (rows ascending: a stable sort by representative keeps them so)
+        groups, at = [], 0
+        for c in counts.tolist():
+            if c >= 2:
+                groups.append(rows[order[at:at + c]])
+            at += c
+        return matched, groups, stats
+
+    def find_duplicates(self, key: str, radius: float, filter=None, limit: int | None = None):
+        """(groups, truncated): the groups of at least two rows that lie within `radius` of each other, by SINGLE LINKAGE -- rows A and C
+        share a group when a chain A-B-..-C of rows exists whose neighbours are within `radius` (the distance search_within compares),
+        even when d(A, C) > radius.  Each group is the list of its rows' metadata dicts in ascending row order, the representative (the
+        lowest row) first; the groups are ordered by representative.  `filter`: a pattern, a pattern with predicates or an expression, as
+        in search -- only matching rows are grouped, and a row outside it never bridges two inside.  `limit`: every row looks at its
+        `limit` nearest rows within the radius only (itself included); each group is then a subset of a true one, and `truncated` counts
+        the rows whose list was full.  One library call (GpuIndex.dup_groups) under the read lock."""
+        t = self._t(key)
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.read():
+            _, groups, stats = self._dup_rows(t, radius, filter, limit)
+            return [[dict(t.metadata[int(r)]) for r in g] for g in groups], stats["truncated"]
+
+    def mark_duplicates(self, key: str, radius: float, field: str, filter=None, limit: int | None = None) -> tuple[int, int]:
+        """Writes find_duplicates' grouping into the metadata key `field`: first `field` is REMOVED from every row the filter matches
+        (every row without one), then every row of a group of at least two gets the decimal ordinal of its group ("0", "1", ..: the
+        order find_duplicates lists them in).  Rows alone keep no value, and under group_by a row without the key is always kept, so
+        search(..., group_by=field, group_size=1) then returns at most one hit per duplicate group and every unique row.  Returns
+        (groups, rows in them).  The write goes the way batch_update_metadata's does: ONE GpuIndex.set_labels_rows call when `field`
+        has a label column, then the host dicts, then exactly the cached masks that name `field` are dropped; ids, vectors, HNSW and PQ
+        state stay."""
+        t = self._t(key)
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.write():
+            matched, groups, _ = self._dup_rows(t, radius, filter, limit)
+            rows = np.arange(len(t.metadata), dtype=np.int64) if matched is None else np.asarray(matched, dtype=np.int64)
+            value: dict[int, str] = {int(r): str(g) for g, members in enumerate(groups) for r in members.tolist()}
+            touched = [r for r in rows.tolist() if r in value or field in t.metadata[r]]
+            if touched:
+                col = t.codec.column_of(field)
+                if col is not None:
+                    codes = np.array([[t.codec.encode_value(field, value.get(r)) for r in touched]], dtype=np.uint32)
+                    t.index.set_labels_rows(np.asarray(touched, dtype=np.uint64), [col], codes)
+                for r in touched:
+                    self._apply_changes(t.metadata[r], {field: value.get(r)})
+                t.drop_masks_naming([field])
+            return len(groups), len(value)
+
+    def delete_duplicates(self, key: str, radius: float, filter=None, limit: int | None = None) -> int:
+        """Removes every row of a find_duplicates group except its representative (the lowest row); returns the number removed.  ONE
+        GpuIndex.remove_rows call; the metadata follow the moves it reports, and the HNSW index and the PQ table are cleared, as delete
+        does.  Because the grouping is single linkage, the representatives that remain may again lie within `radius` of each other
+        through a row that is gone: a second call at the same radius need not return 0."""
+        t = self._t(key)
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.write():
+            _, groups, _ = self._dup_rows(t, radius, filter, limit)
+            gone = sorted(int(r) for g in groups for r in g[1:].tolist())
+            t.drop_masks()
+            t.index.hnsw_clear()
+            t.index.pq_clear()
+            if gone:
+                dst, src = t.index.remove_rows(gone)
+                for d, s in zip(dst.tolist(), src.tolist()):
+                    t.metadata[d] = t.metadata[s]
+                del t.metadata[len(t.metadata) - len(gone):]
+            return len(gone)
+
     def count(self, key: str, filter=None) -> int:
         """the number of rows that match `filter` -- a pattern, a pattern with predicates or an expression, handled exactly as search
         handles it -- from the count of its cached mask; no filter: get_len"""
