@@ -384,12 +384,16 @@ int vdb_index_add_device(vdb_index *idx, const void *d_rows, uint64_t n, uint64_
     add_common(idx->ix, static_cast<const float *>(d_rows), n, first_id, true);
     VDB_API_END
 }
+// the row edits of a Flat table are refused while a structure built over the rows is attached; `call` is the edit the message names
+static void require_flat_only(const Index &ix, const char *call) {
+    VDB_REQUIRE(!ix.hnsw.present, std::string(call) + " needs a Flat index (clear the HNSW graph first)");
+    VDB_REQUIRE(!ix.pq.present, std::string(call) + " invalidates the PQ table: clear it first");
+    VDB_REQUIRE(!ix.ivf.present, std::string(call) + " invalidates the IVF clusters: clear them first");
+}
 int vdb_index_swap_remove(vdb_index *idx, uint64_t i) {
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
-    VDB_REQUIRE(!idx->ix.hnsw.present, "swap_remove needs a Flat index (clear the HNSW graph first)");
-    VDB_REQUIRE(!idx->ix.pq.present, "swap_remove invalidates the PQ table: clear it first");
-    VDB_REQUIRE(!idx->ix.ivf.present, "swap_remove invalidates the IVF clusters: clear them first");
+    require_flat_only(idx->ix, "swap_remove");
     idx->ix.swap_remove(i);
     VDB_API_END
 }
@@ -420,9 +424,7 @@ int vdb_index_remove_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, uint
     VDB_API_BEGIN
     VDB_REQUIRE(idx, "null index");
     VDB_REQUIRE((out_dst == nullptr) == (out_src == nullptr), "out_dst and out_src go together (both NULL: no plan returned)");
-    VDB_REQUIRE(!idx->ix.hnsw.present, "swap_remove needs a Flat index (clear the HNSW graph first)");
-    VDB_REQUIRE(!idx->ix.pq.present, "swap_remove invalidates the PQ table: clear it first");
-    VDB_REQUIRE(!idx->ix.ivf.present, "swap_remove invalidates the IVF clusters: clear them first");
+    require_flat_only(idx->ix, "swap_remove");  // (the bulk form of swap_remove: its refusals carry that name)
     std::vector<uint64_t> dst, src;
     idx->ix.remove_rows(rows, m, dst, src);
     remove_plan_out(dst, src, out_dst, out_src, out_moves);
@@ -442,9 +444,7 @@ int vdb_update_plan(uint64_t n, const uint64_t *rows, uint64_t m, uint32_t *out_
 static void update_common(vdb_index *idx, const uint64_t *rows, uint64_t m, const void *vecs, bool on_device) {
     VDB_REQUIRE(idx, "null index");
     Index &ix = idx->ix;
-    VDB_REQUIRE(!ix.hnsw.present, "update_rows needs a Flat index (clear the HNSW graph first)");
-    VDB_REQUIRE(!ix.pq.present, "update_rows invalidates the PQ table: clear it first");
-    VDB_REQUIRE(!ix.ivf.present, "update_rows invalidates the IVF clusters: clear them first");
+    require_flat_only(ix, "update_rows");
     VDB_REQUIRE(!ix.elem_u8, "update_rows needs f32 rows: a VecSet<u8> index is not updated in place");
     VDB_REQUIRE(vecs || m == 0, "update_rows: null vectors");
     VDB_REQUIRE(!on_device || reinterpret_cast<uintptr_t>(vecs) % 16 == 0, "update_rows: device vectors must be 16-byte aligned");

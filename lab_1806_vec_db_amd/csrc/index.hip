@@ -59,6 +59,78 @@ const float *Index::host_rows() const {
     return h_rows.data();
 }
 
+// ---- mirror upkeep of the row edits (index.hpp, the private section of Index; docs/DESIGN_flat.md 4.1ac) ---------------------------------
+Index::MirrorSet Index::live_mirrors() const {
+    const bool mfma = mfma_supported((uint32_t)dim);
+    return {mfma && tiled_m.valid, mfma && half_m.covers(n), i8_m.covers(n)};
+}
+void Index::retile_tiles(MirrorSet live, const float *v, uint64_t n_rows, uint64_t ta, uint64_t tb, hipStream_t s) {
+    const uint32_t d = (uint32_t)dim;
+    if (live.tiled) launch_tile_rows(v, n_rows, d, ta, tb, d_tiled.as<float>(), s);
+    if (live.half) launch_tile_rows_h(v, n_rows, d, ta, tb, half_sx(), d_tiled_h.p, s);
+    if (live.i8)  // (f32 rows only) tiles, codes and constants; Cosine: the mirror of the UNIT rows, from the norms in d_sq
+        launch_tile_rows_i8(v, n_rows, d, ta, tb, d_mu_i8.as<float>(), i8_l1, i8_l2, d_tiled_i8.p, d_rowc_i8.as<float>(), s,
+                            dist == 1 ? d_sq.as<float>() : nullptr);
+}
+void Index::retile(Workspace &ws, MirrorSet live, uint64_t n_rows, const uint32_t *d_tiles, uint64_t n_tiles, uint64_t t_begin, uint64_t t_end) {
+    if (!(live.tiled || live.half || live.i8)) return;
+    hipStream_t s = ws.stream;
+    if (d_tiles && !elem_u8) {
+        const uint32_t d = (uint32_t)dim;
+        const float *x = d_rows.as<float>();
+        if (live.tiled) launch_tile_rows_list(x, n_rows, d, d_tiles, n_tiles, d_tiled.as<float>(), s);
+        if (live.half) launch_tile_rows_h_list(x, n_rows, d, d_tiles, n_tiles, half_sx(), d_tiled_h.p, s);
+        if (live.i8)
+            launch_tile_rows_i8_list(x, n_rows, d, d_tiles, n_tiles, d_mu_i8.as<float>(), i8_l1, i8_l2, d_tiled_i8.p, d_rowc_i8.as<float>(), s,
+                                     dist == 1 ? d_sq.as<float>() : nullptr);
+    } else if (t_end > t_begin) {  // a u8 index re-tiles through widened chunks
+        for_tile_chunks(ws, t_begin, t_end, n_rows,
+                        [&](const float *v, uint64_t ta, uint64_t tb, uint64_t, uint64_t) { retile_tiles(live, v, n_rows, ta, tb, s); });
+    }
+}
+void Index::mirrors_shrunk(uint64_t n1) {
+    if (tiled_m.valid) tiled_m.rows = n1;
+    // the fp16 scale stays and the moved rows' rounding error is already part of half_dx_*; behind the table, it was never measured
+    if (half_m.rows == n)
+        half_m.rows = n1;
+    else
+        half_m.invalidate();
+    if (i8_m.covers(n))
+        i8_m.rows = n1;
+    else
+        i8_m.invalidate();  // rows were added since the last search: rebuilt by the next one
+    rows_h_m.invalidate();  // (rebuilt by the next walk / scan that uses them)
+    rows_q8_m.invalidate();
+}
+void Index::widen_norm_bounds(const float *sq, uint64_t count) {
+    for (uint64_t j = 0; j < count; j++) {
+        const float v = sq[j];
+        if (v > xsq_max && std::isfinite(v)) xsq_max = v;
+        if (v > 0.0f && v < xsq_min_pos) xsq_min_pos = v;
+    }
+}
+bool Index::half_exp_needed(float xsq_max, int &need) {
+    if (!(xsq_max >= 0x1p-80f && xsq_max <= 0x1p80f)) return false;
+    int e = 0;
+    (void)std::frexp(xsq_max, &e);  // xsq_max = m * 2^e, m in [0.5, 1)  =>  |x| < 2^ceil(e/2)
+    need = e >= 0 ? (e + 1) / 2 : -((-e) / 2);
+    return true;
+}
+void Index::half_fold_err(hipStream_t s) {
+    VDB_SYNC(s);
+    float e2[2];  // (the f32 bits of the kernel's two maxima; read into this call's own storage, not the workspace's pinned block)
+    VDB_HIP(hipMemcpy(e2, d_half_err.p, sizeof(e2), hipMemcpyDeviceToHost));
+    half_dx_abs = std::max(half_dx_abs, std::sqrt(e2[0]) * 1.001f);  // the kernel's f32 sums: relative error << 1e-3
+    half_dx_rel = std::max(half_dx_rel, std::sqrt(e2[1]) * 1.001f);
+}
+const uint32_t *Index::upload_ids(Workspace &ws, const uint64_t *rows, uint64_t m, std::vector<uint32_t> &h_ids) {
+    h_ids.resize(m);
+    labels_scatter_ids(rows, m, h_ids.data());
+    ws.keys_a.reserve(m * sizeof(uint32_t));
+    VDB_HIP(hipMemcpyAsync(ws.keys_a.p, h_ids.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, ws.stream));
+    return ws.keys_a.as<uint32_t>();
+}
+
 // VecSet::push (vec_set.rs:113-118) for `count` rows + dist_cache (hnsw_index.rs:251-254)
 void Index::add_rows(const void *rows, uint64_t count, bool on_device) {
     if (count == 0) return;
@@ -84,15 +156,12 @@ void Index::add_rows(const void *rows, uint64_t count, bool on_device) {
     for_tile_chunks(*ws, tiles_old, tiles_new, n + count, [&](const float *v, uint64_t ta, uint64_t tb, uint64_t ra, uint64_t rb) {
         const uint64_t a = std::max(ra, n);
         if (rb > a) launch_row_sqnorm(v + a * dim, rb - a, (uint32_t)dim, d_sq.as<float>() + a, s);
-        if (mirror) launch_tile_rows(v, n + count, (uint32_t)dim, ta, tb, d_tiled.as<float>(), s);
+        retile_tiles({mirror, false, false}, v, n + count, ta, tb, s);
     });
     std::vector<float> sq(count);
     VDB_HIP(hipMemcpyAsync(sq.data(), d_sq.as<float>() + n, count * sizeof(float), hipMemcpyDeviceToHost, s));
     VDB_SYNC(s);
-    for (float v : sq) {
-        if (v > xsq_max && std::isfinite(v)) xsq_max = v;
-        if (v > 0.0f && v < xsq_min_pos) xsq_min_pos = v;
-    }
+    widen_norm_bounds(sq.data(), count);
     h_sq.insert(h_sq.end(), sq.begin(), sq.end());
     if (mirror) tiled_m.rows = n + count;
     // an fp16 mirror in step is extended (needs the new xsq_max) unless the 8-bit pass is this index's first tier: then it waits for its
@@ -124,30 +193,11 @@ void Index::swap_remove(uint64_t i) {
         VDB_HIP(hipMemcpyAsync(d_sq.as<float>() + i, d_sq.as<float>() + last, sizeof(float), hipMemcpyDeviceToDevice, s));
         launch_label_move_one(label_cols(), (uint32_t)i, (uint32_t)last, s);
     }
-    if (mfma_supported((uint32_t)dim)) {  // rewrite the tiles of the moved row and of the removed last row
-        for (uint64_t t : {i / 16, last / 16})
-            for_tile_chunks(*ws, t, t + 1, last, [&](const float *v, uint64_t ta, uint64_t tb, uint64_t, uint64_t) {
-                if (tiled_m.valid) launch_tile_rows(v, last, (uint32_t)dim, ta, tb, d_tiled.as<float>(), s);
-                // same scale; the moved row's rounding error is already part of half_dx_*
-                if (half_m.covers(n)) launch_tile_rows_h(v, last, (uint32_t)dim, ta, tb, half_sx(), d_tiled_h.p, s);
-            });
-    }
-    if (tiled_m.valid) tiled_m.rows = last;
-    // an fp16 mirror behind the table is rebuilt in full by its next use (the moved row's error was never measured)
-    if (half_m.rows == n)
-        half_m.rows = last;
-    else
-        half_m.invalidate();
-    if (i8_m.covers(n)) {  // (f32 rows only) the moved row's and the removed row's tiles, codes and constants
-        for (uint64_t t : {i / 16, last / 16})
-            launch_tile_rows_i8(d_rows.as<float>(), last, (uint32_t)dim, t, t + 1, d_mu_i8.as<float>(), i8_l1, i8_l2, d_tiled_i8.p,
-                                d_rowc_i8.as<float>(), s, dist == 1 ? d_sq.as<float>() : nullptr);  // (d_sq[i] already holds the moved row's)
-        i8_m.rows = last;
-    } else {
-        i8_m.invalidate();  // rows were added since the last search: rebuilt by the next one
-    }
-    rows_h_m.invalidate();  // (rebuilt by the next walk / scan that uses them)
-    rows_q8_m.invalidate();
+    // the tiles of the moved row and of the removed last row, once each (d_sq[i] already holds the moved row's norm)
+    const MirrorSet live = live_mirrors();
+    retile(*ws, live, last, nullptr, 0, i / 16, i / 16 + 1);
+    if (last / 16 != i / 16) retile(*ws, live, last, nullptr, 0, last / 16, last / 16 + 1);
+    mirrors_shrunk(last);
     VDB_SYNC(s);
     {
         std::lock_guard<std::mutex> g(host_mu);
@@ -163,7 +213,7 @@ void Index::swap_remove(uint64_t i) {
     // xsq_max stays an upper bound (certification only needs a bound)
 }
 
-// MetadataVecTable::delete's loop of swap_removes (metadata_vec_table.rs:170-186) as one pass; mirror upkeep as in swap_remove above
+// MetadataVecTable::delete's loop of swap_removes (metadata_vec_table.rs:170-186) as one pass
 void Index::remove_rows(const uint64_t *rows, uint64_t m, std::vector<uint64_t> &dst, std::vector<uint64_t> &src) {
     dst.clear();
     src.clear();
@@ -179,7 +229,8 @@ void Index::remove_rows(const uint64_t *rows, uint64_t m, std::vector<uint64_t> 
     const uint64_t moves = dst.size();
     // the 16-row tiles whose rows change: those of the filled holes, and from the new end of the table to the end of a mirror of n1 rows
     // (rows at and past n1 become padding)
-    const bool tiles_wanted = mfma_supported((uint32_t)dim) || i8_m.covers(n);
+    const MirrorSet live = live_mirrors();
+    const bool tiles_wanted = mfma_supported((uint32_t)dim) || live.i8;
     std::vector<uint32_t> h_moves(2 * moves), h_tiles;
     for (uint64_t j = 0; j < moves; j++) {
         h_moves[2 * j] = (uint32_t)dst[j];
@@ -203,33 +254,8 @@ void Index::remove_rows(const uint64_t *rows, uint64_t m, std::vector<uint64_t> 
     if (n_tiles && list_form) VDB_HIP(hipMemcpyAsync(ws->keys_b.p, h_tiles.data(), n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     launch_rows_move(d_rows.p, row_bytes, d_sq.as<float>(), d_moves, moves, num_cu, s);
     launch_label_move(label_cols(), d_moves, moves, num_cu, s);  // (the columns only shrink here: nothing to reserve)
-    if (mfma_supported((uint32_t)dim) && n_tiles) {
-        const bool half_live = half_m.covers(n);  // same scale; the moved rows' rounding error is already part of half_dx_*
-        if (list_form) {
-            if (tiled_m.valid) launch_tile_rows_list(d_rows.as<float>(), n1, (uint32_t)dim, d_tiles, n_tiles, d_tiled.as<float>(), s);
-            if (half_live) launch_tile_rows_h_list(d_rows.as<float>(), n1, (uint32_t)dim, d_tiles, n_tiles, half_sx(), d_tiled_h.p, s);
-        } else if (tiled_m.valid || half_live) {
-            for_tile_chunks(*ws, h_tiles.front(), mirror_tiles(n1), n1, [&](const float *v, uint64_t ta, uint64_t tb, uint64_t, uint64_t) {
-                if (tiled_m.valid) launch_tile_rows(v, n1, (uint32_t)dim, ta, tb, d_tiled.as<float>(), s);
-                if (half_live) launch_tile_rows_h(v, n1, (uint32_t)dim, ta, tb, half_sx(), d_tiled_h.p, s);
-            });
-        }
-    }
-    if (tiled_m.valid) tiled_m.rows = n1;
-    // an fp16 mirror behind the table is rebuilt in full by its next use (the moved rows' error was never measured)
-    if (half_m.rows == n)
-        half_m.rows = n1;
-    else
-        half_m.invalidate();
-    if (i8_m.covers(n)) {  // (f32 rows only) tiles, codes and constants with the current mu / lambdas; d_sq already holds the moved rows'
-        launch_tile_rows_i8_list(d_rows.as<float>(), n1, (uint32_t)dim, d_tiles, n_tiles, d_mu_i8.as<float>(), i8_l1, i8_l2, d_tiled_i8.p,
-                                 d_rowc_i8.as<float>(), s, dist == 1 ? d_sq.as<float>() : nullptr);
-        i8_m.rows = n1;
-    } else {
-        i8_m.invalidate();  // rows were added since the last search: rebuilt by the next one
-    }
-    rows_h_m.invalidate();
-    rows_q8_m.invalidate();
+    retile(*ws, live, n1, d_tiles, n_tiles, n_tiles ? h_tiles.front() : mirror_tiles(n1), mirror_tiles(n1));  // (d_sq already holds the moved rows')
+    mirrors_shrunk(n1);
     VDB_SYNC(s);
     {
         std::lock_guard<std::mutex> g(host_mu);
@@ -246,7 +272,7 @@ void Index::remove_rows(const uint64_t *rows, uint64_t m, std::vector<uint64_t> 
 }
 
 // New vectors for the rows `rows` (distinct, any order), in place: no row moves, n / id_offset / the label columns stay, and so does
-// write_gen -- a RowMask is a set of rows and the set did not change (docs/DESIGN_flat.md 4.1r).  Mirror upkeep as in remove_rows above.
+// write_gen -- a RowMask is a set of rows and the set did not change (docs/DESIGN_flat.md 4.1r).
 void Index::update_rows(const uint64_t *rows, uint64_t m, const void *vecs, bool on_device) {
     const char *why = update_plan_check(n, rows, m);
     VDB_REQUIRE(!why, why);
@@ -258,27 +284,22 @@ void Index::update_rows(const uint64_t *rows, uint64_t m, const void *vecs, bool
     hipStream_t s = ws->stream;
     const uint32_t d = (uint32_t)dim;
     const size_t row_bytes = size_t(dim) * sizeof(float);
-    std::vector<uint32_t> h_ids(m), h_tiles;
-    for (uint64_t j = 0; j < m; j++) h_ids[j] = (uint32_t)rows[j];
+    std::vector<uint32_t> h_ids, h_tiles;
     update_plan(n, rows, m, h_tiles);
     const uint64_t n_tiles = h_tiles.size();
-    const bool tiled_live = mfma_supported(d) && tiled_m.valid;
-    const bool half_live = mfma_supported(d) && half_m.covers(n);  // in step: its touched tiles are rewritten if the scale still fits
-    const bool i8_live = i8_m.covers(n);
+    const MirrorSet live = live_mirrors();  // (the fp16 mirror's touched tiles are rewritten only if the scale still fits)
     // host vectors go through a bounded staging buffer, a chunk of rows at a time; device vectors are read where they are
     const uint64_t chunk = std::min<uint64_t>(m, std::max<uint64_t>(UPDATE_STAGE_BYTES / row_bytes, 1));
     std::vector<float> sq(m);
-    ws->keys_a.reserve(m * sizeof(uint32_t));
     ws->keys_b.reserve(n_tiles * sizeof(uint32_t));
     ws->misc.reserve(m * sizeof(float));
     if (!on_device) ws->dense.reserve(chunk * row_bytes);
-    if (half_live) d_half_err.reserve(2 * sizeof(uint32_t));
+    if (live.half) d_half_err.reserve(2 * sizeof(uint32_t));
+    const uint32_t *d_ids = upload_ids(*ws, rows, m, h_ids), *d_tiles = ws->keys_b.as<uint32_t>();  // (the last reserve: ws.keys_a)
     // ---- nothing was changed up to here; from here on nothing allocates on the device ----
-    const uint32_t *d_ids = ws->keys_a.as<uint32_t>(), *d_tiles = ws->keys_b.as<uint32_t>();
     float *d_sq_new = ws->misc.as<float>();
-    VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_ids.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     VDB_HIP(hipMemcpyAsync(ws->keys_b.p, h_tiles.data(), n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    if (half_live) VDB_HIP(hipMemsetAsync(d_half_err.p, 0, 2 * sizeof(uint32_t), s));
+    if (live.half) VDB_HIP(hipMemsetAsync(d_half_err.p, 0, 2 * sizeof(uint32_t), s));
     for (uint64_t j0 = 0; j0 < m; j0 += chunk) {
         const uint64_t nb = std::min(chunk, m - j0);
         const char *from = static_cast<const char *>(vecs) + j0 * row_bytes;
@@ -290,36 +311,20 @@ void Index::update_rows(const uint64_t *rows, uint64_t m, const void *vecs, bool
         launch_row_sqnorm(d_new, nb, d, d_sq_new + j0, s);  // the strict fold of add_rows: the norms of a table built with these rows
         launch_rows_scatter(d_rows.p, row_bytes, d_sq.as<float>(), d_ids + j0, d_new, d_sq_new + j0, nb, num_cu, s);
         // the new rows' rounding error under the CURRENT fp16 scale (dropped below if that scale no longer fits)
-        if (half_live) launch_row_split_err(d_new, d_sq_new + j0, 0, nb, d, half_sx(), d_half_err.as<uint32_t>(), s);
+        if (live.half) launch_row_split_err(d_new, d_sq_new + j0, 0, nb, d, half_sx(), d_half_err.as<uint32_t>(), s);
     }
-    if (tiled_live) launch_tile_rows_list(d_rows.as<float>(), n, d, d_tiles, n_tiles, d_tiled.as<float>(), s);
-    if (i8_live)  // tiles, codes and constants with the current mu / lambdas (bounds for any row); Cosine reads d_sq: the new norms are in place
-        launch_tile_rows_i8_list(d_rows.as<float>(), n, d, d_tiles, n_tiles, d_mu_i8.as<float>(), i8_l1, i8_l2, d_tiled_i8.p, d_rowc_i8.as<float>(), s,
-                                 dist == 1 ? d_sq.as<float>() : nullptr);
-    else
-        i8_m.invalidate();  // rows were added since the last search: rebuilt by the next one
+    // the 8-bit mirror keeps its mu / lambdas (bounds for any row); Cosine reads d_sq: the new norms are in place
+    retile(*ws, {live.tiled, false, live.i8}, n, d_tiles, n_tiles, 0, 0);
+    if (!live.i8) i8_m.invalidate();  // rows were added since the last search: rebuilt by the next one
     VDB_HIP(hipMemcpyAsync(sq.data(), d_sq_new, m * sizeof(float), hipMemcpyDeviceToHost, s));
     VDB_SYNC(s);
-    for (uint64_t j = 0; j < m; j++) {  // the bounds are widened, never narrowed
-        const float v = sq[j];
-        if (v > xsq_max && std::isfinite(v)) xsq_max = v;
-        if (v > 0.0f && v < xsq_min_pos) xsq_min_pos = v;
-        h_sq[rows[j]] = v;
-    }
-    // fp16 mirror: half_refresh's test of the scale against the new xsq_max
-    bool half_fits = half_live && xsq_max >= 0x1p-80f && xsq_max <= 0x1p80f;
-    if (half_fits) {
-        int e = 0;
-        (void)std::frexp(xsq_max, &e);
-        half_fits = (e >= 0 ? (e + 1) / 2 : -((-e) / 2)) <= half_exp;
-    }
-    if (half_fits) {
-        launch_tile_rows_h_list(d_rows.as<float>(), n, d, d_tiles, n_tiles, half_sx(), d_tiled_h.p, s);
-        VDB_SYNC(s);
-        float e2[2];
-        VDB_HIP(hipMemcpy(e2, d_half_err.p, sizeof(e2), hipMemcpyDeviceToHost));
-        half_dx_abs = std::max(half_dx_abs, std::sqrt(e2[0]) * 1.001f);
-        half_dx_rel = std::max(half_dx_rel, std::sqrt(e2[1]) * 1.001f);
+    widen_norm_bounds(sq.data(), m);
+    for (uint64_t j = 0; j < m; j++) h_sq[rows[j]] = sq[j];
+    // fp16 mirror: patched when the new xsq_max still fits the scale it was built with
+    int need = 0;
+    if (live.half && half_exp_needed(xsq_max, need) && need <= half_exp) {
+        retile(*ws, {false, true, false}, n, d_tiles, n_tiles, 0, 0);
+        half_fold_err(s);
     } else {
         half_m.invalidate();  // behind the table, or the scale is too small now: rebuilt in full by its next use
     }
@@ -401,11 +406,8 @@ void Index::get_rows(const uint64_t *rows, uint64_t m, void *out, bool as_f32) {
         VDB_SYNC(s);
         fetch_direct += 1;
     } else {
-        std::vector<uint32_t> h_ids(m);
-        for (uint64_t j = 0; j < m; j++) h_ids[j] = (uint32_t)rows[j];
-        ws->keys_a.reserve(m * sizeof(uint32_t));
-        VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_ids.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        fetch_gathered(*ws, ws->keys_a.as<uint32_t>(), m, out, widen, plan.chunk_rows);  // (synchronised: h_ids may go)
+        std::vector<uint32_t> h_ids;
+        fetch_gathered(*ws, upload_ids(*ws, rows, m, h_ids), m, out, widen, plan.chunk_rows);  // (synchronised: h_ids may go)
         fetch_chunks += plan.n_chunks;
     }
     fetch_calls += 1;
@@ -512,15 +514,13 @@ void Index::labels_scatter(const uint64_t *rows, uint64_t m, const uint32_t *col
     use_device();
     WsLease ws(*this);
     hipStream_t s = ws->stream;
-    std::vector<uint32_t> h_ids(m);
-    labels_scatter_ids(rows, m, h_ids.data());
-    ws->keys_a.reserve(m * sizeof(uint32_t));
+    std::vector<uint32_t> h_ids;
     ws->misc.reserve(n_cols * m * sizeof(uint32_t));
+    const uint32_t *d_ids = upload_ids(*ws, rows, m, h_ids);  // (into the workspace: no column is allocated or written yet)
     const LabelCols target = labels_targets(columns, n_cols, s);
-    VDB_HIP(hipMemcpyAsync(ws->keys_a.p, h_ids.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     VDB_HIP(hipMemcpyAsync(ws->misc.p, codes, n_cols * m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     prof_begin(*ws, "labels_scatter", double(m) * sizeof(uint32_t) * double(1 + 2 * n_cols));
-    launch_labels_scatter(target, ws->keys_a.p, false, 0, ws->misc.as<uint32_t>(), m, num_cu, labels_scatter_max_blocks, s);
+    launch_labels_scatter(target, d_ids, false, 0, ws->misc.as<uint32_t>(), m, num_cu, labels_scatter_max_blocks, s);
     prof_end(*ws);
     VDB_SYNC(s);  // (h_ids and the caller's codes may go)
     prof_collect(*ws);
@@ -604,7 +604,7 @@ bool Index::ensure_tiled(Workspace &ws) {
         const uint64_t tiles = mirror_tiles(n);
         d_tiled.reserve(tiles * 16 * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(float));
         for_tile_chunks(ws, 0, tiles, n, [&](const float *v, uint64_t ta, uint64_t tb, uint64_t, uint64_t) {
-            launch_tile_rows(v, n, (uint32_t)dim, ta, tb, d_tiled.as<float>(), ws.stream);
+            retile_tiles({true, false, false}, v, n, ta, tb, ws.stream);
         });
         VDB_SYNC(ws.stream);
         tiled_m.set(n);
@@ -632,14 +632,12 @@ uint64_t Index::hbm_bytes_per_row() const {
 // headroom, so this happens at most once per doubling of the largest norm).
 void Index::half_refresh(Workspace &ws, uint64_t n_old, uint64_t n_new) {
     if (!gemm_f16_supported((uint32_t)dim)) return;
-    if (!(xsq_max >= 0x1p-80f && xsq_max <= 0x1p80f)) {  // all-zero or extreme data: the split-bf16 / exact paths serve it
+    int need = 0;
+    if (!half_exp_needed(xsq_max, need)) {  // the split-bf16 / exact paths serve such data
         half_m.valid = false;
         return;
     }
     hipStream_t s = ws.stream;
-    int e = 0;
-    (void)std::frexp(xsq_max, &e);                           // xsq_max = m * 2^e, m in [0.5, 1)  =>  |x| < 2^ceil(e/2)
-    const int need = e >= 0 ? (e + 1) / 2 : -((-e) / 2);
     const bool rebuild = !half_m.valid || need > half_exp;
     const uint64_t tiles_new = mirror_tiles(n_new);
     const uint64_t tile_bytes = 16 * size_t(mfma_dim_pad((uint32_t)dim)) * sizeof(uint16_t);
@@ -654,15 +652,11 @@ void Index::half_refresh(Workspace &ws, uint64_t n_old, uint64_t n_new) {
     d_half_err.reserve(2 * sizeof(uint32_t));
     VDB_HIP(hipMemsetAsync(d_half_err.p, 0, 2 * sizeof(uint32_t), s));
     for_tile_chunks(ws, t0, tiles_new, n_new, [&](const float *v, uint64_t ta, uint64_t tb, uint64_t ra, uint64_t rb) {
-        launch_tile_rows_h(v, n_new, (uint32_t)dim, ta, tb, half_sx(), d_tiled_h.p, s);
+        retile_tiles({false, true, false}, v, n_new, ta, tb, s);
         const uint64_t a = std::max(ra, r0);
         if (rb > a) launch_row_split_err(v, d_sq.as<float>(), a, rb, (uint32_t)dim, half_sx(), d_half_err.as<uint32_t>(), s);
     });
-    VDB_SYNC(s);
-    float e2[2];  // (the f32 bits of the kernel's two maxima; read into this call's own storage, not the workspace's pinned block)
-    VDB_HIP(hipMemcpy(e2, d_half_err.p, sizeof(e2), hipMemcpyDeviceToHost));
-    half_dx_abs = std::max(half_dx_abs, std::sqrt(e2[0]) * 1.001f);  // the kernel's f32 sums: relative error << 1e-3
-    half_dx_rel = std::max(half_dx_rel, std::sqrt(e2[1]) * 1.001f);
+    half_fold_err(s);
     half_m.valid = true;
 }
 
@@ -717,7 +711,7 @@ void Index::build_i8(Workspace &ws) {  // (under i8_m.mu)
         i8_mu_norm = (float)std::sqrt(m2) * 1.001f;
         i8_mu_rows = n;
     }
-    launch_tile_rows_i8(d_rows.as<float>(), n, d, t0, tiles, d_mu_i8.as<float>(), i8_l1, i8_l2, d_tiled_i8.p, d_rowc_i8.as<float>(), s, xsq_cos);
+    retile_tiles({false, false, true}, d_rows.as<float>(), n, t0, tiles, s);
     VDB_SYNC(s);
     i8_m.set(n);
 }

@@ -292,8 +292,9 @@ struct RangeTally {
 inline uint64_t mirror_tiles(uint64_t rows) { return ((rows + 15) / 16 + 11) / 12 * 12; }
 
 // One image of the rows derived from d_rows (the Flat tiers' tiled mirrors, the row-major fp16 / 8-bit images): built by the first call
-// that wants it, kept in step by add_rows / swap_remove.  An image that cannot be allocated is not an error of the search that wanted it:
-// its buffers are released, the failure is counted, the tier is left to the next one, and ensure() does not try again until n changes.
+// that wants it, kept in step with every row edit by Index's mirror upkeep (the private section at the end of Index: THE place a write path
+// goes through).  An image that cannot be allocated is not an error of the search that wanted it: its buffers are released, the failure is
+// counted, the tier is left to the next one, and ensure() does not try again until n changes.
 struct RowMirror {
     std::mutex mu;                   // read-side calls are re-entrant: one of them builds, the others wait
     std::atomic<bool> valid{false};  // the buffers hold the image of rows [0, rows) (both read without the lock)
@@ -413,8 +414,8 @@ struct Index {
     bool ensure_half(Workspace &ws);  // false: this index has no fp16 mirror (dimension, extreme norms)
     float half_sx() const { return std::ldexp(1.0f, 13 - half_exp); }
     // Centred 8-bit mirror for k_flat_gemm8 (k_gemm8.hip, k_i8.hip; L2Sqr over f32 rows): 1 B/element in fragment order +
-    // {C_r, M_r} per row.  Built by the first search that wants it (ensure_i8), extended after add_rows, kept in step by
-    // swap_remove; mu / lambda are re-chosen (and everything rewritten) when the table has doubled since they were measured.
+    // {C_r, M_r} per row.  Built by the first search that wants it (ensure_i8), extended after add_rows, kept in step by the
+    // mirror upkeep below; mu / lambda are re-chosen (and everything rewritten) when the table has doubled since they were measured.
     DevBuf d_tiled_i8, d_rowc_i8, d_mu_i8;
     RowMirror i8_m{mirror_alloc_failures, {&d_tiled_i8, &d_rowc_i8}};
     uint64_t i8_mu_rows = 0;    // table size when mu / lambda were measured
@@ -453,11 +454,11 @@ struct Index {
     int rows_h_exp = 0;
     bool ensure_rows_h(Workspace &ws);  // false: this index has no fp16 image (dim, element type, extreme norms)
     // 8-bit image of the rows with one scale and one measured error per row (half_rows.hpp, "8-bit tier"): the first tier of
-    // the IVF scan's pre-pass; built on first use, extended after add, dropped by swap_remove
+    // the IVF scan's pre-pass; built on first use, extended after add, dropped by every other row edit (mirrors_shrunk, update_rows)
     DevBuf d_rows_q8, d_q8_scale, d_q8_err;
     RowMirror rows_q8_m{mirror_alloc_failures, {&d_rows_q8, &d_q8_scale, &d_q8_err}};
     bool ensure_rows_q8(Workspace &ws);  // false: no 8-bit image (dim, element type, allocation): the IVF scan goes on with the fp16 tier
-    std::vector<float> h_sq;  // host mirror of d_sq (4 B/row), kept in step by add_rows / swap_remove
+    std::vector<float> h_sq;  // host mirror of d_sq (4 B/row), kept in step by each row edit itself (add, remove, update)
     float xsq_max = 0.0f;
     float xsq_min_pos = 3.4e38f;  // smallest positive row |x|^2 seen (cosine certification: clamp check)
     // lazily materialised host mirror of the rows (needed by the host-side builders and vdb_index_row)
@@ -784,6 +785,31 @@ struct Index {
     std::atomic<uint64_t> range_queries{0}, range_i8_queries{0}, range_scan_queries{0}, range_hits{0}, range_results{0};
     std::atomic<uint64_t> range_hits_max{0};  // longest hit list of a query the tier answered
     std::atomic<uint64_t> range_multi_calls{0}, range_grouped_queries{0};  // range calls with a mask per query / queries their grouped launch answered
+
+private:
+    // ---- Mirror upkeep: how a row edit (add_rows, swap_remove, remove_rows, update_rows) is carried into the tiled images of d_rows.  A
+    // write path asks live_mirrors() BEFORE its edit which images are in step, rewrites the 16-row tiles it touched with retile(), and
+    // calls mirrors_shrunk() when the table got shorter; an image it cannot patch it invalidates.  docs/DESIGN_flat.md 4.1ac.
+    struct MirrorSet {
+        bool tiled = false, half = false, i8 = false;  // d_tiled | d_tiled_h | d_tiled_i8 + d_rowc_i8
+    };
+    MirrorSet live_mirrors() const;  // the tiled images that cover all n rows now (the only ones an edit may patch)
+    // tiles [ta, tb) of the named images from the f32 view v of n_rows rows (v + r * dim = row r), with the current scale / mu / lambdas
+    void retile_tiles(MirrorSet live, const float *v, uint64_t n_rows, uint64_t ta, uint64_t tb, hipStream_t s);
+    // The touched tiles of the named images, for a table of n_rows rows (rows at and past n_rows become padding): the n_tiles tiles of the
+    // device list d_tiles in one launch per image when there is a list and the rows are f32, else the range [t_begin, t_end) through
+    // for_tile_chunks.  Enqueues on ws.stream; allocates nothing on an f32 index (u8: for_tile_chunks' ws.dense, reserved by the caller).
+    void retile(Workspace &ws, MirrorSet live, uint64_t n_rows, const uint32_t *d_tiles, uint64_t n_tiles, uint64_t t_begin, uint64_t t_end);
+    // the table shrank from n to n1 rows (n not yet updated) and the touched tiles were rewritten: an image that was in step follows, one
+    // that was behind is rebuilt in full by its next use; the row-major images are dropped
+    void mirrors_shrunk(uint64_t n1);
+    void widen_norm_bounds(const float *sq, uint64_t count);  // xsq_max / xsq_min_pos over more row norms: widened, never narrowed
+    // THE fp16 scale rule: false for all-zero or extreme data (no fp16 mirror); else need = the E with |x| < 2^E for every |x|^2 <= xsq_max
+    static bool half_exp_needed(float xsq_max, int &need);
+    void half_fold_err(hipStream_t s);  // syncs s, reads d_half_err's two maxima and folds them into half_dx_abs / half_dx_rel
+    // rows[0..m) (checked, n <= 2^32) narrowed into h_ids and uploaded to ws.keys_a on ws.stream; h_ids lives until the caller's sync.
+    // Reserves keys_a: call it before the first write.
+    const uint32_t *upload_ids(Workspace &ws, const uint64_t *rows, uint64_t m, std::vector<uint32_t> &h_ids);
 };
 
 // what every filtered, mask-per-query and grouped k-NN entry point and search requires of the index

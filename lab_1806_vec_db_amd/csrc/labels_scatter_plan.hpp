@@ -40,7 +40,7 @@ inline const char *labels_scatter_check(uint64_t n, const uint64_t *rows, uint64
     }
 }
 
-// the ids as uploaded (rows checked, n at most 2^32: every id fits)
+// the ids as uploaded (rows checked, n at most 2^32: every id fits); the narrowing of every host id list (Index::upload_ids)
 inline void labels_scatter_ids(const uint64_t *rows, uint64_t m, uint32_t *out_ids32) {
     for (uint64_t j = 0; j < m; j++) out_ids32[j] = uint32_t(rows[j]);
 }

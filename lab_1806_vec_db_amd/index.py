@@ -257,19 +257,29 @@ class GpuIndex:
         return out
 
     @staticmethod
-    def _fetch_ids(rows) -> np.ndarray:
+    def _row_ids(rows, what: str, sort: bool = False, distinct: bool = True) -> np.ndarray:
+        """THE check of a host list of local row ids, for the call `what` names in the messages: a flat u64 array of `rows` (ascending
+        when `sort`); bool / float / negative ids raise ValueError, and so does a duplicate when `distinct`.  An id at or past len is
+        the library's to refuse (VdbError)."""
         a = np.asarray(rows).reshape(-1)
         if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
-            raise ValueError("get_rows: an array of integer row ids is needed")
+            raise ValueError(f"{what}: an array of integer row ids is needed")
         if a.size and np.issubdtype(a.dtype, np.signedinteger) and int(a.min()) < 0:
-            raise ValueError("get_rows: negative row id")
-        return np.ascontiguousarray(a.astype(np.uint64))
+            raise ValueError(f"{what}: negative row id")
+        r = np.ascontiguousarray(a.astype(np.uint64))
+        if sort or distinct:
+            ordered = np.sort(r)
+            if distinct and bool((ordered[1:] == ordered[:-1]).any()):
+                raise ValueError(f"{what}: duplicate row ids")
+            if sort:
+                return ordered
+        return r
 
     def get_rows(self, rows, out: np.ndarray | None = None) -> np.ndarray:
         """The vectors of many rows in ONE call (vdb_index_get_rows): (len(rows), dim) f32, row j = local row rows[j]; a u8 index is
         widened.  `rows` in any order, repeats allowed (bool / float / negative ids raise ValueError, an id at or past len VdbError).
         `out`: a C-contiguous float32 array of that shape to fill instead of a new one."""
-        r = self._fetch_ids(rows)
+        r = self._row_ids(rows, "get_rows", distinct=False)
         if out is None:
             out = np.empty((r.size, self.dim), dtype=np.float32)
         elif out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != (r.size, self.dim):
@@ -279,7 +289,7 @@ class GpuIndex:
 
     def get_rows_u8(self, rows, out: np.ndarray | None = None) -> np.ndarray:
         """The same for a u8 index, rows as stored: (len(rows), dim) uint8 (vdb_index_get_rows_u8; refused on an f32 index)."""
-        r = self._fetch_ids(rows)
+        r = self._row_ids(rows, "get_rows", distinct=False)
         if out is None:
             out = np.empty((r.size, self.dim), dtype=np.uint8)
         elif out.dtype != np.uint8 or not out.flags.c_contiguous or out.shape != (r.size, self.dim):
@@ -329,31 +339,16 @@ class GpuIndex:
         order, would leave.  `rows` are local row ids in any order; a duplicate raises ValueError.  Returns (dst, src), u64 arrays: the
         row that was at src[j] is now at dst[j], every other surviving row kept its place -- what a caller needs to permute whatever it
         keeps per row (`meta[dst] = meta[src]`, then truncate)."""
-        a = np.asarray(rows).reshape(-1)
-        if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
-            raise ValueError("remove_rows: an array of integer row ids is needed")
-        if a.size and np.issubdtype(a.dtype, np.signedinteger) and int(a.min()) < 0:
-            raise ValueError("remove_rows: negative row id")
-        r = np.sort(a.astype(np.uint64))
-        if r.size > 1 and bool((r[1:] == r[:-1]).any()):
-            raise ValueError("remove_rows: duplicate row ids")
+        r = self._row_ids(rows, "remove_rows", sort=True)
         dst = np.zeros(r.size, dtype=np.uint64)
         src = np.zeros(r.size, dtype=np.uint64)
         moves = C.c_uint64()
         L.check(self._lib.vdb_index_remove_rows(self._h, _ptr(r, L.u64p), r.size, _ptr(dst, L.u64p), _ptr(src, L.u64p), C.byref(moves)))
         return dst[:int(moves.value)].copy(), src[:int(moves.value)].copy()
 
-    @staticmethod
-    def _update_ids(rows) -> np.ndarray:
-        a = np.asarray(rows).reshape(-1)
-        if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
-            raise ValueError("update_rows: an array of integer row ids is needed")
-        if a.size and np.issubdtype(a.dtype, np.signedinteger) and int(a.min()) < 0:
-            raise ValueError("update_rows: negative row id")
-        r = np.ascontiguousarray(a.astype(np.uint64))
-        if r.size > 1 and np.unique(r).size != r.size:
-            raise ValueError("update_rows: duplicate row ids")
-        return r
+    @classmethod
+    def _update_ids(cls, rows) -> np.ndarray:  # (update_rows and the label scatter, whose refusals carry update_rows' name)
+        return cls._row_ids(rows, "update_rows")
 
     def update_rows(self, rows, vecs):
         """New vectors for existing rows, in place (vdb_index_update_rows): row rows[j] gets vecs[j].  `rows` are local row ids in any

@@ -94,6 +94,20 @@ int main() {
         std::printf("FAILED: argument validation\n");
         return 1;
     }
+    // labels_scatter_ids is the narrowing of every host id list: nothing (no read, no write), one id, the largest id a shard can hold
+    // (exactly m elements on the heap on both sides: a step past either list is the sanitizer's to find)
+    for (uint64_t m : {uint64_t(0), uint64_t(1), uint64_t(3)}) {
+        std::vector<uint64_t> rows(m);
+        for (uint64_t j = 0; j < m; j++) rows[j] = j ? 0xFFFFFFFFull - (j - 1) : 7;  // 7, 2^32 - 1, 2^32 - 2
+        std::vector<uint32_t> ids(m, 77u);
+        vdb::labels_scatter_ids(rows.data(), m, ids.data());
+        for (uint64_t j = 0; j < m; j++)
+            if (uint64_t(ids[j]) != rows[j]) {
+                std::printf("FAILED: labels_scatter_ids at m = %llu, j = %llu\n", (unsigned long long)m, (unsigned long long)j);
+                return 1;
+            }
+    }
+    vdb::labels_scatter_ids(nullptr, 0, nullptr);
     std::printf("labels_scatter_plan ok: %llu cases, %llu refused\n", (unsigned long long)cases, (unsigned long long)refused);
     return 0;
 }
