@@ -207,7 +207,7 @@ struct PQState {
     std::vector<float> h_centroids;  // kc*dim
     std::vector<float> h_cent_cache; // m*kc
     DevBuf d_centroids, d_cent_cache, d_codes, d_gstart;
-    DevBuf d_codes_t;                // word-major mirror of d_codes for the quantised ADC scan (pq.hip: k_pq_tile_codes)
+    DevBuf d_codes_t;                // word-major mirror of d_codes for the quantised ADC scan (k_pq.hip: k_pq_tile_codes)
     bool codes_t_valid = false;
     std::atomic<uint64_t> adc16_queries{0};  // queries whose ADC scan ran on the quantised tables (k_pq_adc16)
     std::atomic<uint64_t> adc16_redo{0};     // of those, the ones handed to the f32 scan (list overflowed | fewer than ef sums at or below tau)

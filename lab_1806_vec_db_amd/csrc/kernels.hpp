@@ -522,6 +522,138 @@ void launch_fuse_groups(const uint64_t *ids, const float *dists, const uint64_t 
                         uint64_t list_base, const float *weights, const uint32_t *labels, uint64_t n, int mode, float c, uint64_t id_offset,
                         uint64_t trunc_len, uint32_t k, uint32_t lg, uint32_t *scratch, uint64_t *out_idx, float *out_dist, uint64_t *out_cnt,
                         uint8_t *out_exact, hipStream_t s);
+// ---- k_pq.hip: product quantisation -- lookup tables, the ADC scans and their exact stages, encoder, re-sort, shard merge ----------
+// The argument structs are filled by the search drivers (pq.hip); every launcher works out its own grid and dynamic LDS bytes.  Where a
+// driver has to ASK whether a scan's LDS image fits before it chooses that scan, the same *_lds_bytes() the launcher uses answers.
+void launch_pq_lut(const float *Q, uint32_t dim, const float *cent, const uint64_t *gstart, uint32_t m, uint32_t kc, int cosine, uint32_t nq,
+                   float *lut, hipStream_t s);
+void launch_pq_encode(const float *X, uint64_t n, uint32_t dim, const float *cent, const float *cent_cache, const uint64_t *gstart, uint32_t m,
+                      uint32_t kc, uint32_t n_bits, int cosine, uint32_t enc_dim, uint8_t *codes, hipStream_t s);
+// word-major mirror of the code rows: (n rounded up to 64) * nwords 16-B words
+void launch_pq_tile_codes(const uint8_t *codes, uint64_t n, uint32_t enc_dim, uint32_t nwords, uint4 *tiled, hipStream_t s);
+void launch_pq_resort(const uint64_t *exact_keys, uint32_t ncand, uint32_t ldc, uint32_t nq, uint32_t k, uint64_t *out, hipStream_t s);
+// the f32 scan (k_pq_adc): MODE 0 dense, MODE 1 filter -- see the kernel
+struct AdcArgs {
+    const uint8_t *codes;
+    uint64_t n;
+    uint32_t enc_dim, m;
+    const float *lut;         // [BQ][m*kc]
+    const float *cent_cache;  // [m*kc]
+    const float *qsq;         // [BQ]
+    uint32_t nq;              // valid queries of this pass (<= BQ)
+    int cosine;
+    uint32_t blk_step;
+    float *out;               // MODE 0
+    uint64_t ld;
+    const float *tau;         // MODE 1: [BQ]
+    uint64_t *cand;           //         [BQ][cap]
+    uint32_t *cnt;            //         [BQ]
+    uint32_t cap;
+    uint32_t nq_total;        // queries of the whole launch; blockIdx.y selects the sub-batch of BQ queries
+    int fast;                 // batched-lookup inner loop (tuning switch, vdb_set_param "pq_adc_fast")
+};
+// queries per pass = as many f32 lookup tables (lut_bytes each; Cosine: the |centroid|^2 table beside them) as fit in 120 KB of LDS
+// (<= 4), and the rows per row block = workgroup size that goes with it: 1024 with the tables in LDS, else 256 (tables through L1 / L2)
+struct AdcPlan {
+    uint32_t BQ, nt;
+    bool in_lds;
+};
+AdcPlan pq_adc_plan(size_t lut_bytes, bool cosine);
+void launch_pq_adc(const AdcArgs &a, uint32_t n_bits, int mode, int num_cu, hipStream_t s);
+// 4-bit codes on 16-bit tables, 8 queries (Cosine: 7) per pass (k_pq_quant16, k_pq_adc16, k_pq_adc_exact)
+constexpr uint32_t ADC16_Q = 8;          // queries per workgroup pass
+struct Adc16Args {
+    const uint4 *codes_t;    // word-major mirror of the code rows (k_pq_tile_codes)
+    uint64_t n;
+    uint32_t enc_dim, m;     // m = groups of the IMAGE (32 per code word, >= the table's m); enc_dim = bytes of a code row
+    const uint4 *img;        // [ceil(nq/8)][m*16] 16-B entries
+    const double *qM, *qD;   // [nq]
+    const double *qMC, *qDC; // [nq] Cosine: offset / step of the |centroid|^2 table (identical for all queries)
+    const float *qsq;        // [nq] Cosine: |q|^2
+    const uint32_t *qflag;   // [nq]
+    const float *tau;        // [nq]
+    uint32_t nq;
+    uint64_t rows_per_wg;    // multiple of 64
+    uint64_t *cand;          // [nq][cap] row ids (upper word 0)
+    uint32_t *cnt;           // [nq]
+    uint32_t cap;
+    // SAMPLE mode (threshold sample on the quantised tables): every blk_step-th 1024-row block, dense sums out
+    uint32_t blk_step;       // >= 1
+    float *s16_out;          // [nq][ld_s] quantised sums of the sampled rows as floats (exact: <= 65000 + m), +inf past n
+    uint64_t ld_s;
+};
+size_t pq_adc16_lds_bytes(uint32_t nwords);  // nwords = 16-B code words per row
+void launch_pq_quant16(const float *lut, const float *cent_cache, uint32_t m, uint32_t m_pad, uint32_t nq, int cosine, uint16_t *img, double *qM,
+                       double *qD, double *qMC, double *qDC, uint32_t *qflag, hipStream_t s);
+// sample: the strided sample of a.blk_step (L2Sqr only), as few workgroups per image group as still fill the chip; else the filter scan
+void launch_pq_adc16(const Adc16Args &a, bool cosine, bool sample, uint32_t nwords, int num_cu, hipStream_t s);
+void launch_pq_adc_exact(bool cosine, const uint8_t *codes, uint32_t enc_dim, uint32_t m, const float *lut, const float *cent_cache, const float *qsq,
+                         const float *tau, uint64_t *cand, const uint32_t *cnt, uint32_t cap, uint32_t *valid, uint32_t nq, hipStream_t s);
+// tau[q] = M + D (s* + m/2) from the r-th smallest quantised sample sum s* (in tau[q] on entry); +inf for a flagged table
+void launch_pq_tau_from16(float *tau, const double *qM, const double *qD, const uint32_t *qflag, uint32_t m, uint32_t nq, hipStream_t s);
+// 8-bit codes, one query per pass on a one-byte table (k_pq_quant8, k_pq_adc8)
+struct Adc8Args {
+    const uint4 *codes_t;   // word-major mirror of the (zero-padded) code rows
+    uint64_t n;
+    uint32_t nwords, m;     // 16-B code words per row; groups of the table (the image holds 16 * nwords of them)
+    const uint8_t *img;     // [nq][16 * nwords * 256]
+    const double *qM, *qD;
+    const uint32_t *qflag;
+    const float *tau;
+    uint32_t nq;
+    uint64_t rows_per_wg;   // multiple of 64
+    uint64_t *cand;         // [nq][cap] row ids
+    uint32_t *cnt;          // [nq]
+    uint32_t cap;
+    uint32_t blk_step;      // SAMPLE: every blk_step-th 1024-row block
+    float *s8_out;          // SAMPLE: [nq][ld_s] quantised sums as floats, +inf past n
+    uint64_t ld_s;
+};
+size_t pq_adc8_lds_bytes(uint32_t nwords);
+void launch_pq_quant8(const float *lut, uint32_t m, uint32_t m_pad, uint32_t nq, uint8_t *img, double *qM, double *qD, uint32_t *qflag, hipStream_t s);
+// sample: every workgroup loads its query's table -- few workgroups per query, enough of them to fill the chip; else the filter scan
+void launch_pq_adc8(const Adc8Args &a, bool sample, int num_cu, hipStream_t s);
+// 8-bit codes on sliced images: eight queries per pass on 16-bit entries (k_pq_adc16x8), sixteen on one-byte entries (k_pq_adc8x16)
+constexpr uint32_t ADC16X8_RPT = 4;       // rows per thread
+constexpr uint32_t ADC16X8_GS = 32;       // groups per slice (two 16-B code words)
+constexpr uint32_t ADC8X16_RPT = 2;       // rows per thread
+constexpr uint32_t ADC8X16_GS = 16;       // groups per slice (one 16-B code word): 16 x 256 x 16 B = 64 KB, two blocks in LDS
+struct Adc16x8Args {
+    const uint4 *codes_t;   // word-major mirror of the (zero-padded) code rows
+    uint64_t n;
+    uint32_t nwords, m;     // 16-B code words per row; groups of the table
+    uint32_t nslices;       // slices of 32 groups of the image (m_pad = 32 nslices)
+    const uint4 *img;       // [ngrp][m_pad * 256] 16-B entries
+    const double *qM, *qD;  // [nq] of the 16-bit quantisation
+    const uint32_t *qflag;
+    const float *tau;
+    uint32_t nq;
+    uint64_t rows_per_wg;   // multiple of 64
+    uint64_t *cand;         // [nq][cap] row ids
+    uint32_t *cnt;          // [nq]
+    uint32_t cap;
+    // k_pq_adc8x16<SAMPLE>: the quantised sums of every blk_step-th block of 1024 rows, as floats (+inf past the table), [nq][ld_s]
+    uint32_t blk_step = 0;
+    uint64_t n_sb = 0;      // sampled blocks
+    float *s8_out = nullptr;
+    uint64_t ld_s = 0;
+};
+size_t pq_adc16x8_lds_bytes();
+size_t pq_adc8x16_lds_bytes();
+// per query the group minima mn [nq][m], M, D = sum of the ranges / divisor and the flag, then the image of ceil(nq / 8) (sixteen: / 16)
+// query groups, m_pad groups each (k_pq_quant16x8_stats + k_pq_quant16x8_img | k_pq_quant8x16_img)
+void launch_pq_quant_sliced(bool sixteen, const float *lut, uint32_t m, uint32_t m_pad, uint32_t nq, double divisor, float *mn, double *qM, double *qD,
+                            uint32_t *qflag, uint4 *img, hipStream_t s);
+void launch_pq_adc16x8(const Adc16x8Args &a, hipStream_t s);
+void launch_pq_adc8x16(const Adc16x8Args &a, bool sample, hipStream_t s);
+// exact f32 sums of the candidates of the 8-bit scans (k_pq_adc_exact8)
+void launch_pq_adc_exact8(const uint8_t *codes, uint32_t enc_dim, const uint4 *codes_t, uint32_t nwords, uint32_t m, const float *lut,
+                          const float *tau, uint64_t *cand, const uint32_t *cnt, uint32_t cap, uint32_t *valid, uint32_t nq, hipStream_t s);
+// row-sharded knn_pq: a shard's key rows with global ids, and the merge of n_shards sorted rows per query by ADC key
+void launch_pq_export_keys(const uint64_t *adc, const uint64_t *exact, uint32_t ld, uint32_t efk_local, uint32_t efk_out, uint64_t id_offset,
+                           uint64_t *out_adc, uint64_t *out_exact, uint32_t nq, hipStream_t s);
+void launch_pq_shard_merge(const uint64_t *adc, const uint64_t *exact, uint32_t n_shards, uint32_t nq, uint32_t efg, uint64_t *merged, hipStream_t s);
+
 void mfma_set_sample_thin(int v);
 void mfma_sample_plan(uint64_t n, uint32_t kprime, uint32_t *step, uint32_t *rank, uint32_t target_floor = 1024);  // target_floor: expected hits per query
 uint64_t mfma_sample_rows(uint64_t n, uint32_t step);

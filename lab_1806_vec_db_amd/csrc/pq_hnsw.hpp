@@ -1,4 +1,4 @@
-// pq_hnsw.hpp -- PQ (pq.hip) and HNSW (hnsw.hip, hnsw_build.cpp) entry points used by api.hip.
+// pq_hnsw.hpp -- PQ (pq.hip; kernels in k_pq.hip) and HNSW (hnsw.hip, hnsw_build.cpp) entry points used by api.hip.
 #pragma once
 #include <functional>
 
@@ -11,9 +11,11 @@ void pq_attach(Index &ix, uint64_t n_bits, uint64_t m, const float *centroids, c
 void pq_build(Index &ix, uint64_t n_bits, uint64_t m, uint64_t train_n, uint64_t max_iter, float tol, uint64_t seed);
 void pq_clear(Index &ix);
 void pq_set_adc_fast(int v);
-void pq_set_adc16(int v);
-void pq_set_adc8_sliced(int v);  // 8-bit codes: 0 = eight queries per pass on sliced 16-bit tables, 1 = one query per pass (byte table)
-void pq_set_adc16_sample(int v);  // threshold sample of the quantised scan on the quantised tables too: 0 auto, 1 off (f32 sample)  // quantised first pass of the ADC scan: 0 auto, 1 off
+void pq_set_adc16(int v);         // quantised first pass of the threshold-filter scan: 0 auto, 1 off (f32 scan)
+// 8-bit codes: 0 = sixteen queries per pass on sliced one-byte tables (k_pq_adc8x16), 1 = one query per pass on a byte table
+// (k_pq_adc8), 2 = eight queries per pass on sliced 16-bit tables (k_pq_adc16x8)
+void pq_set_adc8_sliced(int v);
+void pq_set_adc16_sample(int v);  // threshold sample on the quantised tables (L2Sqr): 0 auto (on with the quantised scan), 1 off (f32 sample)
 void flat_knn_pq_device(Index &ix, Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t ef,
                         uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
 
