@@ -478,6 +478,51 @@ int vdb_label_lookup_plan(uint32_t column, const uint32_t *codes, uint64_t n_cod
                           uint64_t *out_span, uint64_t *out_chunks);
 int vdb_index_label_lookup(vdb_index *idx, uint32_t column, const uint32_t *codes, uint64_t n_codes, uint64_t *out_first /* [n_codes] */,
                            uint64_t *out_counts /* [n_codes] */);
+/* ---- k-means clustering of a table's rows (csrc/kmeans_plan.hpp, csrc/flat_kmeans.hip, csrc/k_kmeans.hip; docs/DESIGN_flat.md 4.1ad) ----------
+ * "What are the c groups these rows fall into, and which group is each row in?"  Lloyd's algorithm over the rows of an f32 index, or over
+ * the rows a mask allows.  THE RULE:
+ *   Assignment.  Row i goes to the centroid with the smallest (D(centroid, row), centroid id): D is the pair distance the re-rank reports --
+ *   the strict left-to-right f32 fold, the direct form for L2Sqr, 1 - dot / max(|a||b|, 1e-10) with strict-fold norms for Cosine -- compared
+ *   in the library's total order (NaN greatest, all NaN equal), ties to the LOWEST centroid id.  So a row whose distance to every centroid is
+ *   NaN goes to centroid 0.  The assignment is a function of (rows, centroids) alone, bit for bit.
+ *   Update.  centroid[j] = f32((sum over the members in ascending row order of double(x[j])) / count): an f64 sum, one rounding, under both
+ *   metrics.  The members are summed in 16 segments whose bounds depend on the count alone.  A cluster without members keeps its centroid
+ *   (kmeans_group, the PQ / IVF trainer, does the same).
+ *   Stop.  Assignment t = 0, 1, .. is made against the centroids after t updates.  After assignment t the loop stops when t == max_iter, or
+ *   when t > 0 and no row changed cluster, or when t > 0 and |inertia_t - inertia_(t-1)| <= tol * inertia_(t-1); inertia = the f64 sum of the
+ *   rows' best distances in a fixed order.  Otherwise the centroids are updated.  max_iter = 0: the assignment to the initial centroids.
+ *   Initial centroids: init [c][dim] when given; else min(m, 64 c) allowed rows are drawn by a splitmix64 stream from `seed` (all of them
+ *   when m <= 64 c), fetched with the bulk row fetch (whose counters advance) and seeded by the trainer's k-means++ -- the same for the same
+ *   (table, mask, c, seed).
+ * Refused, with outputs and counters untouched: a u8 index, c = 0, c > 65535, c > m (m = rows clustered; the assignment step alone accepts
+ * it), dim > 8192, a stale or foreign mask, init_dim != dim.
+ * How: per iteration one matrix pass (split-bf16 MFMA, a fused argmin that keeps best and second-best score per row) settles every row whose
+ * margin exceeds the error bound E of kmeans_plan.hpp; the others -- "kmeans_unsure_rows" -- go through the exact fold against every
+ * centroid.  Both together give exactly the rule above.
+ * Outputs: out_centroids [c][dim]; out_assign [len] u32, VDB_LABEL_NONE for a row outside the mask; out_sizes [c]; *out_iters = updates made;
+ * *out_inertia.  The assignment is the one to the returned centroids.  _device: the three arrays in device memory (8-byte aligned).
+ * vdb_kmeans_assign_device: the assignment step alone -- d_centroids [c][dim] in, d_out_assign [len] u32 and d_out_best [len] f32 (the exact
+ * distance to the row's centroid; NULL: not wanted; NaN outside the mask) out, *out_unsure = rows that took the exact fold.
+ * vdb_kmeans_plan (host only): the argument check and the layout -- row tiles of 128, centroid tiles of 64, k-blocks of 32, digit passes of the
+ * member sort, scratch bytes; *out_err = E for (dim, metric, |x| <= xn, every |c| <= cn, best distance <= d_best).  vdb_kmeans_segment: the
+ * members [first, first + len) of segment s < 16 of a cluster of `count` members.
+ * vdb_get_stat: "kmeans_calls" (vdb_flat_kmeans calls that succeeded), "kmeans_iterations" (their updates), "kmeans_rows_assigned",
+ * "kmeans_unsure_rows" (rows through an assignment step / of them through the exact fold).  vdb_prof_get: "kmeans_assign", "kmeans_resolve"
+ * (with the exact best distances), "kmeans_update" (member sort, sums, the iteration's reductions). */
+int vdb_kmeans_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m, uint64_t c, int lloyd, int cosine, float xn, float cn,
+                    float d_best, uint64_t *out_row_tiles, uint64_t *out_cent_tiles, uint64_t *out_k_blocks, uint64_t *out_order_passes,
+                    uint64_t *out_scratch_bytes, float *out_err);
+int vdb_kmeans_segment(uint64_t count, uint64_t s, uint64_t *out_first, uint64_t *out_len);
+int vdb_flat_kmeans(vdb_index *idx, uint64_t c, uint64_t max_iter, float tol, uint64_t seed, const float *init /* NULL: seeded */, uint64_t init_dim,
+                    const vdb_mask *mask /* NULL: all rows */, float *out_centroids, uint32_t *out_assign, uint64_t *out_sizes, uint64_t *out_iters,
+                    double *out_inertia);
+int vdb_flat_kmeans_device(vdb_index *idx, uint64_t c, uint64_t max_iter, float tol, uint64_t seed, const float *init, uint64_t init_dim,
+                           const vdb_mask *mask, void *d_out_centroids, void *d_out_assign, void *d_out_sizes, uint64_t *out_iters,
+                           double *out_inertia, void *stream);
+int vdb_kmeans_assign(vdb_index *idx, const float *centroids, uint64_t c, uint64_t dim, const vdb_mask *mask, uint32_t *out_assign /* [len] */,
+                      float *out_best /* [len] or NULL */, uint64_t *out_unsure); /* the host form of the call below */
+int vdb_kmeans_assign_device(vdb_index *idx, const void *d_centroids, uint64_t c, uint64_t dim, const vdb_mask *mask, void *d_out_assign,
+                             void *d_out_best, uint64_t *out_unsure, void *stream);
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids);
 /* ---- near-duplicate grouping: a range self-join over the table's own rows and the connected components of its pairs ---------------------
  * "Which rows are copies, or near copies, of each other?"  (csrc/dup_plan.hpp, csrc/flat_dups.hip, csrc/k_components.hip;
@@ -955,6 +1000,8 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *                        vdb_index_label_counts calls; "label_columns": allocated columns,
  *   "label_lookup_calls" vdb_index_label_lookup calls that were accepted; "label_lookup_codes": the codes they named;
  *                        "label_lookup_direct": the calls that ran the direct route; "label_lookup_passes": reads of the column, summed,
+ *   "kmeans_calls"       vdb_flat_kmeans / _device calls that succeeded; "kmeans_iterations": their centroid updates; "kmeans_rows_assigned":
+ *                        rows through an assignment step; "kmeans_unsure_rows": of them through the exact fold,
  *   "flat_dup_calls"     vdb_flat_dup_groups / _device calls that succeeded; "flat_dup_chunks": the range calls under them;
  *                        "flat_dup_pairs": the non-self pairs they saw,
  *   "update_calls"       vdb_index_update_rows / _device calls that changed rows (m > 0, not refused); "update_rows": the rows they rewrote,

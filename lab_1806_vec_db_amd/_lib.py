@@ -77,6 +77,12 @@ SIGNATURES = {
     "vdb_flat_dup_groups": [vp, C.c_float, u64, vp, u64p, u64p],
     "vdb_flat_dup_groups_device": [vp, C.c_float, u64, vp, vp, u64p, vp],
     "vdb_link_pairs_device": [vp, vp, vp, vp, u64, vp, u64p, vp],
+    "vdb_kmeans_plan": [u64, u64, C.c_int, C.c_int, u64, u64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, u64p, u64p, u64p, u64p, u64p, f32p],
+    "vdb_kmeans_segment": [u64, u64, u64p, u64p],
+    "vdb_flat_kmeans": [vp, u64, u64, C.c_float, u64, f32p, u64, vp, f32p, u32p, u64p, u64p, f64p],
+    "vdb_flat_kmeans_device": [vp, u64, u64, C.c_float, u64, f32p, u64, vp, vp, vp, vp, u64p, f64p, vp],
+    "vdb_kmeans_assign": [vp, f32p, u64, u64, vp, u32p, f32p, u64p],
+    "vdb_kmeans_assign_device": [vp, vp, u64, u64, vp, vp, vp, u64p, vp],
     "vdb_mask_rows": [vp, u64p, u32p],
     "vdb_flat_knn_filtered": [vp, f32p, u64, u64, u64, vp, u64p, f32p, u64p],
     "vdb_flat_knn_filtered_device": [vp, vp, u64, u64, u64, vp, vp, vp, vp, vp],

@@ -985,6 +985,138 @@ int vdb_link_pairs_device(vdb_index *idx, const void *d_src, const void *d_lims,
     std::memcpy(out_stats, stats, sizeof(stats));
     VDB_API_END
 }
+// k-means over the rows (Index::flat_kmeans_device / kmeans_assign_device, kmeans_plan.hpp, flat_kmeans.hip)
+int vdb_kmeans_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m, uint64_t c, int lloyd, int cosine, float xn, float cn,
+                    float d_best, uint64_t *out_row_tiles, uint64_t *out_cent_tiles, uint64_t *out_k_blocks, uint64_t *out_order_passes,
+                    uint64_t *out_scratch_bytes, float *out_err) {
+    VDB_API_BEGIN
+    std::string bad = kmeans_check_args(n_rows, dim, elem_u8 != 0, masked != 0, m, c);
+    if (bad.empty() && lloyd) bad = kmeans_check_fit(m, c);
+    VDB_REQUIRE(bad.empty(), bad);
+    const KmeansPlan p = kmeans_plan(n_rows, dim, m, c);
+    if (out_row_tiles) *out_row_tiles = p.row_tiles;
+    if (out_cent_tiles) *out_cent_tiles = p.cent_tiles;
+    if (out_k_blocks) *out_k_blocks = p.k_blocks;
+    if (out_order_passes) *out_order_passes = p.order_passes;
+    if (out_scratch_bytes) *out_scratch_bytes = p.scratch_bytes;
+    if (out_err) *out_err = kmeans_err_bound((uint32_t)dim, cosine != 0, xn, cn, d_best);
+    VDB_API_END
+}
+int vdb_kmeans_segment(uint64_t count, uint64_t s, uint64_t *out_first, uint64_t *out_len) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(s < KM_SEGMENTS && count < (1ull << 32), "kmeans segment: s must be below 16, count below 2^32");
+    uint32_t first, len;
+    kmeans_segment((uint32_t)count, (uint32_t)s, first, len);
+    if (out_first) *out_first = first;
+    if (out_len) *out_len = len;
+    VDB_API_END
+}
+// what the forms refuse before a workspace is taken -> the mask as a RowMask (nullptr: all rows)
+static const RowMask *kmeans_check(const Index &ix, uint64_t c, bool lloyd, uint64_t cent_dim, bool has_cent, const vdb_mask *mask) {
+    if (mask) ix.check_mask(mask->m);
+    const uint64_t m = mask ? mask->m.m : ix.n;
+    std::string bad = kmeans_check_args(ix.n, ix.dim, ix.elem_u8, mask != nullptr, m, c);
+    if (bad.empty() && lloyd) bad = kmeans_check_fit(m, c);
+    VDB_REQUIRE(bad.empty(), bad);
+    VDB_REQUIRE(!has_cent || cent_dim == ix.dim, "kmeans: centroid dimension mismatch: index dim " + std::to_string(ix.dim) + ", got " +
+                                                     std::to_string(cent_dim));
+    return mask ? &mask->m : nullptr;
+}
+int vdb_flat_kmeans(vdb_index *idx, uint64_t c, uint64_t max_iter, float tol, uint64_t seed, const float *init, uint64_t init_dim,
+                    const vdb_mask *mask, float *out_centroids, uint32_t *out_assign, uint64_t *out_sizes, uint64_t *out_iters, double *out_inertia) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const RowMask *rm = kmeans_check(ix, c, true, init_dim, init != nullptr, mask);
+    VDB_REQUIRE(out_centroids && out_assign && out_sizes && out_iters && out_inertia, "kmeans: null argument");
+    ix.use_device();
+    WsLease ws(ix);
+    DevBuf d_cent, d_assign, d_sizes;
+    d_cent.reserve(c * ix.dim * sizeof(float));
+    d_assign.reserve(ix.n * sizeof(uint32_t));
+    d_sizes.reserve(c * sizeof(uint64_t));
+    uint64_t iters = 0;
+    double inertia = 0.0;
+    run_synced(ix, *ws, [&] {
+        ix.flat_kmeans_device(*ws, c, max_iter, tol, seed, init, rm, d_cent.as<float>(), d_assign.as<uint32_t>(), d_sizes.as<uint64_t>(), &iters, &inertia);
+        VDB_HIP(hipMemcpyAsync(out_centroids, d_cent.p, c * ix.dim * sizeof(float), hipMemcpyDeviceToHost, ws->stream));
+        VDB_HIP(hipMemcpyAsync(out_assign, d_assign.p, ix.n * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+        VDB_HIP(hipMemcpyAsync(out_sizes, d_sizes.p, c * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+        VDB_SYNC(ws->stream);
+    });
+    *out_iters = iters;
+    *out_inertia = inertia;
+    VDB_API_END
+}
+int vdb_flat_kmeans_device(vdb_index *idx, uint64_t c, uint64_t max_iter, float tol, uint64_t seed, const float *init, uint64_t init_dim,
+                           const vdb_mask *mask, void *d_out_centroids, void *d_out_assign, void *d_out_sizes, uint64_t *out_iters,
+                           double *out_inertia, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const RowMask *rm = kmeans_check(ix, c, true, init_dim, init != nullptr, mask);
+    VDB_REQUIRE(d_out_centroids && d_out_assign && d_out_sizes && out_iters && out_inertia, "kmeans: null argument");
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_out_centroids) % 8 == 0 && reinterpret_cast<uintptr_t>(d_out_assign) % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(d_out_sizes) % 8 == 0,
+                "kmeans: the device outputs must be 8-byte aligned");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever last used the outputs on the caller's stream
+    uint64_t iters = 0;
+    double inertia = 0.0;
+    run_synced(ix, *ws, [&] {
+        ix.flat_kmeans_device(*ws, c, max_iter, tol, seed, init, rm, static_cast<float *>(d_out_centroids), static_cast<uint32_t *>(d_out_assign),
+                              static_cast<uint64_t *>(d_out_sizes), &iters, &inertia);
+    });
+    *out_iters = iters;
+    *out_inertia = inertia;
+    VDB_API_END
+}
+int vdb_kmeans_assign(vdb_index *idx, const float *centroids, uint64_t c, uint64_t dim, const vdb_mask *mask, uint32_t *out_assign, float *out_best,
+                      uint64_t *out_unsure) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const RowMask *rm = kmeans_check(ix, c, false, dim, true, mask);
+    VDB_REQUIRE(centroids && out_unsure && (ix.n == 0 || out_assign), "kmeans assign: null argument");
+    ix.use_device();
+    WsLease ws(ix);
+    DevBuf d_cent, d_assign, d_best;
+    d_cent.reserve(c * ix.dim * sizeof(float));
+    d_assign.reserve(ix.n * sizeof(uint32_t));
+    d_best.reserve(ix.n * sizeof(float));
+    uint64_t unsure = 0;
+    run_synced(ix, *ws, [&] {
+        VDB_HIP(hipMemcpyAsync(d_cent.p, centroids, c * ix.dim * sizeof(float), hipMemcpyHostToDevice, ws->stream));
+        ix.kmeans_assign_device(*ws, d_cent.as<float>(), c, rm, d_assign.as<uint32_t>(), d_best.as<float>(), &unsure);
+        if (ix.n) VDB_HIP(hipMemcpyAsync(out_assign, d_assign.p, ix.n * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+        if (ix.n && out_best) VDB_HIP(hipMemcpyAsync(out_best, d_best.p, ix.n * sizeof(float), hipMemcpyDeviceToHost, ws->stream));
+        VDB_SYNC(ws->stream);
+    });
+    *out_unsure = unsure;
+    VDB_API_END
+}
+int vdb_kmeans_assign_device(vdb_index *idx, const void *d_centroids, uint64_t c, uint64_t dim, const vdb_mask *mask, void *d_out_assign,
+                             void *d_out_best, uint64_t *out_unsure, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const RowMask *rm = kmeans_check(ix, c, false, dim, true, mask);
+    VDB_REQUIRE(d_centroids && out_unsure && (ix.n == 0 || d_out_assign), "kmeans assign: null argument");
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_centroids) % 4 == 0 && reinterpret_cast<uintptr_t>(d_out_assign) % 4 == 0 &&
+                    reinterpret_cast<uintptr_t>(d_out_best) % 4 == 0,
+                "kmeans assign: the device arrays must be 4-byte aligned");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the centroids on the caller's stream
+    uint64_t unsure = 0;
+    run_synced(ix, *ws, [&] {
+        ix.kmeans_assign_device(*ws, static_cast<const float *>(d_centroids), c, rm, static_cast<uint32_t *>(d_out_assign),
+                                static_cast<float *>(d_out_best), &unsure);
+    });
+    *out_unsure = unsure;
+    VDB_API_END
+}
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids) {
     VDB_API_BEGIN
     VDB_REQUIRE(m, "null mask");
@@ -1996,6 +2128,14 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.label_lookup_direct.load();
     else if (n == "label_lookup_passes")
         *out = idx->ix.label_lookup_passes.load();
+    else if (n == "kmeans_calls")  // vdb_flat_kmeans / _device: calls that succeeded | their updates | rows through an assignment step | of them through the exact fold
+        *out = idx->ix.kmeans_calls.load();
+    else if (n == "kmeans_iterations")
+        *out = idx->ix.kmeans_iterations.load();
+    else if (n == "kmeans_rows_assigned")
+        *out = idx->ix.kmeans_rows_assigned.load();
+    else if (n == "kmeans_unsure_rows")
+        *out = idx->ix.kmeans_unsure_rows.load();
     else if (n == "flat_dup_calls")  // vdb_flat_dup_groups / _device: calls that succeeded | range calls (chunks) under them | non-self pairs they saw
         *out = idx->ix.dup_calls.load();
     else if (n == "flat_dup_chunks")

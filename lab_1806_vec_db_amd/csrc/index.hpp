@@ -777,6 +777,18 @@ struct Index {
                            uint64_t *stats);
     uint64_t dup_chunk = DUP_CHUNK_DEFAULT;  // "flat_dup_chunk": queries per range call of the self-join
     std::atomic<uint64_t> dup_calls{0}, dup_chunks{0}, dup_pairs{0};  // flat_dup_groups calls that succeeded / their range calls / non-self pairs they saw
+    // k-means over the rows (flat_kmeans.hip, k_kmeans.hip, kmeans_plan.hpp; docs/DESIGN_flat.md 4.1ad).  The rows clustered are the mask's
+    // allowed rows (nullptr: all); d_assign [n] u32 and d_best [n] f32 are indexed by row, KM_LABEL_NONE / NaN for a row outside the mask.
+    // kmeans_assign_device: the assignment step alone against d_cent [c][dim] on the device -- row i to the centroid with the smallest
+    // pair_key(D(centroid, row), id), D the re-rank's strict-fold pair distance; d_best the exact distances; *unsure = rows the matrix pass
+    // left to the exact fold.  flat_kmeans_device: Lloyd's algorithm from init [c][dim] on the HOST (nullptr: seeded from `seed`), at most
+    // max_iter updates; d_cent [c][dim], d_sizes [c] u64, *iters = updates made, *inertia = the f64 sum of the final best distances.  Both
+    // are read-side and re-entrant, write outputs and counters only when every step has succeeded (the caller has run kmeans_check_args;
+    // the mask is checked here) and return synchronised.
+    void kmeans_assign_device(Workspace &ws, const float *d_cent, uint64_t c, const RowMask *mask, uint32_t *d_assign, float *d_best, uint64_t *unsure);
+    void flat_kmeans_device(Workspace &ws, uint64_t c, uint64_t max_iter, float tol, uint64_t seed, const float *init, const RowMask *mask,
+                            float *d_cent, uint32_t *d_assign, uint64_t *d_sizes, uint64_t *iters, double *inertia);
+    std::atomic<uint64_t> kmeans_calls{0}, kmeans_iterations{0}, kmeans_rows_assigned{0}, kmeans_unsure_rows{0};
     std::atomic<uint64_t> write_gen{0};  // bumped by add_rows / swap_remove / remove_rows: what a RowMask is checked against
     uint64_t flat_filtered_direct_max = 8192;  // allow-lists up to this many rows take the direct path ("flat_filtered_direct_max")
     std::atomic<uint64_t> filtered_queries{0}, filtered_direct_queries{0}, filtered_i8_queries{0}, filtered_fallback_queries{0};

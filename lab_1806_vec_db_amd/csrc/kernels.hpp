@@ -8,6 +8,7 @@
 #include "fuse_groups_plan.hpp"
 #include "fuse_plan.hpp"
 #include "grouped_plan.hpp"
+#include "kmeans_plan.hpp"
 #include "labels_scatter_plan.hpp"
 #include "like_plan.hpp"
 #include "lookup_plan.hpp"
@@ -467,6 +468,31 @@ void launch_comp_flatten(uint32_t *parent, const uint64_t *bits, uint64_t n, uin
 // zeroed by the caller; nq > 0
 void launch_pairs_check(const uint64_t *src, const uint64_t *lims, const uint64_t *ids, uint64_t nq, uint64_t n, uint64_t id_offset, uint64_t *out,
                         int num_cu, hipStream_t s);
+// One Lloyd iteration over the rows X [..][dim] of an f32 index (k_kmeans.hip, kmeans_plan.hpp).  Positions 0 .. m are the rows ids[0 .. m)
+// (nullptr: position = row); assign / best are indexed by ROW.  prep: the centroids C [c][dim] as split-bf16 planes in fragment order, csq =
+// their strict-fold |c|^2 padded with zeros to whole tiles of 64, *cmax_bits = max of its bits (zeroed by the caller).  assign: the matrix
+// pass -- assign[row], best[row] (approximate) for every position, the positions it could not settle appended to unsure[0 .. *unsure_n)
+// (*unsure_n zeroed by the caller).  resolve: the exact (distance, id) minimum of every listed position.  best: best[row] = the exact
+// distance of every position's row to centroid assign[row].  order: count [c] (zeroed by the caller) / offsets [c + 1] / sizes [c] = the
+// members per cluster and members [m] = the positions by cluster, ascending inside a cluster (tmp [m], hist [256 x ceil(m / 4096)]:
+// scratch).  update: C[j] = the f64 mean of cluster j's member rows, rounded once; untouched for a cluster without members.  reduce:
+// *changed += positions with assign != prev, *inertia = the f64 sum of best over the positions in a fixed order (partial
+// [ceil(m / 4096)]: scratch).
+void launch_kmeans_prep(const float *C, uint32_t c, uint32_t dim, uint4 *planes, float *csq, uint32_t *cmax_bits, hipStream_t s);
+void launch_kmeans_assign(const float *X, const float *xsq, const uint32_t *ids, uint64_t m, uint32_t dim, uint32_t c, const uint4 *planes,
+                          const float *csq, const uint32_t *cmax_bits, bool cosine, uint32_t *assign, float *best, uint32_t *unsure,
+                          uint64_t *unsure_n, hipStream_t s);
+void launch_kmeans_resolve(const float *X, const float *xsq, const uint32_t *ids, uint64_t m, uint32_t dim, const float *C, const float *csq,
+                           uint32_t c, bool cosine, const uint32_t *unsure, const uint64_t *unsure_n, uint32_t *assign, float *best, int num_cu,
+                           hipStream_t s);
+void launch_kmeans_best(const float *X, const float *xsq, const uint32_t *ids, uint64_t m, uint32_t dim, const float *C, const float *csq,
+                        uint32_t c, bool cosine, const uint32_t *assign, float *best, hipStream_t s);
+void launch_kmeans_order(const uint32_t *assign, const uint32_t *ids, uint64_t m, uint32_t c, uint32_t *count, uint32_t *offsets, uint64_t *sizes,
+                         uint32_t *hist, uint32_t *tmp, uint32_t *members, hipStream_t s);
+void launch_kmeans_update(const float *X, const uint32_t *ids, uint32_t dim, uint32_t c, const uint32_t *offsets, const uint32_t *members, float *C,
+                          hipStream_t s);
+void launch_kmeans_reduce(const uint32_t *assign, const uint32_t *prev, const float *best, const uint32_t *ids, uint64_t m, double *partial,
+                          uint64_t *changed, double *inertia, hipStream_t s);
 // The capped walk of the grouped k-NN (k_group.hip, grouped_plan.hpp): query b's list ids / dists [b][0 .. min(counts[b], ld)) walked in the order
 // given, at most g rows kept per value of `labels` (u32 per LOCAL row = id - id_offset; nullptr: a column never written; a row without a
 // label is always kept), the first k kept pairs to row slot_q[b] (nullptr: b) of out_idx / out_dist [..][k] with zeros behind them, their

@@ -628,6 +628,78 @@ class GpuIndex:
                                       int(limit or 0), int(chunk), C.byref(chunks), C.byref(last), C.byref(gather), C.byref(scratch)))
         return int(chunks.value), int(last.value), bool(gather.value), int(scratch.value)
 
+    def kmeans(self, c: int, max_iter: int = 20, tol: float = 1e-4, seed: int = 0, init=None, mask: RowMask | None = None):
+        """k-means over the index's rows, or the mask's (vdb_flat_kmeans): (centroids f32 [c][dim], assign uint32 [len], sizes uint64 [c],
+        iters, inertia).  Rows go to the centroid with the smallest (pair distance as the re-rank reports it, centroid id); a centroid becomes
+        the f64 mean of its members, rounded once; a cluster without members keeps its centroid.  Assignment t is made against the centroids
+        after t updates; the loop stops after it when t == max_iter, or from t = 1 on when no row changed cluster or the inertia moved by at
+        most tol x itself.  `init`: c x dim starting centroids; None: seeded from `seed` (k-means++ over at most 64 c sampled rows).
+        assign is LABEL_NONE for a row outside the mask; iters counts the updates; the assignment is the one to the returned centroids.
+        A u8 index, c = 0, c > 65535, c > the rows clustered, a stale or foreign mask and an init of another dim raise VdbError."""
+        c = int(c)
+        ini = None if init is None else np.atleast_2d(np.ascontiguousarray(init, dtype=np.float32))
+        if ini is not None and (ini.ndim != 2 or ini.shape[0] != c):
+            raise L.VdbError(f"kmeans: init must hold c = {c} centroids, got shape {ini.shape}")
+        cent = np.zeros((max(c, 0), self.dim), dtype=np.float32)
+        assign = np.full(len(self), LABEL_NONE, dtype=np.uint32)
+        sizes = np.zeros(max(c, 0), dtype=np.uint64)
+        iters, inertia = C.c_uint64(), C.c_double()
+        L.check(self._lib.vdb_flat_kmeans(self._h, c, int(max_iter), float(tol), int(seed) & (2 ** 64 - 1), None if ini is None else _ptr(ini, L.f32p),
+                                          0 if ini is None else ini.shape[1], None if mask is None else mask._h, _ptr(cent, L.f32p),
+                                          _ptr(assign, L.u32p), _ptr(sizes, L.u64p), C.byref(iters), C.byref(inertia)))
+        return cent, assign, sizes, int(iters.value), float(inertia.value)
+
+    def kmeans_device(self, c: int, out_centroids_ptr: int, out_assign_ptr: int, out_sizes_ptr: int, max_iter: int = 20, tol: float = 1e-4,
+                      seed: int = 0, init=None, mask: RowMask | None = None, stream: int = 0):
+        """kmeans with the outputs written to device memory (vdb_flat_kmeans_device): centroids f32 [c][dim], assign u32 [len], sizes u64
+        [c], each 8-byte aligned; returns (iters, inertia), synchronised"""
+        c = int(c)
+        ini = None if init is None else np.atleast_2d(np.ascontiguousarray(init, dtype=np.float32))
+        if ini is not None and (ini.ndim != 2 or ini.shape[0] != c):
+            raise L.VdbError(f"kmeans: init must hold c = {c} centroids, got shape {ini.shape}")
+        iters, inertia = C.c_uint64(), C.c_double()
+        L.check(self._lib.vdb_flat_kmeans_device(self._h, c, int(max_iter), float(tol), int(seed) & (2 ** 64 - 1),
+                                                 None if ini is None else _ptr(ini, L.f32p), 0 if ini is None else ini.shape[1],
+                                                 None if mask is None else mask._h, L.vp(out_centroids_ptr), L.vp(out_assign_ptr),
+                                                 L.vp(out_sizes_ptr), C.byref(iters), C.byref(inertia), L.vp(stream)))
+        return int(iters.value), float(inertia.value)
+
+    def kmeans_assign(self, centroids, mask: RowMask | None = None):
+        """the assignment step alone (vdb_kmeans_assign): (assign uint32 [len], best f32 [len], unsure) -- every row's (mask: allowed row's)
+        nearest centroid under (pair distance, centroid id), the exact distance to it, and how many rows the matrix pass left to the exact
+        fold.  Rows outside the mask read LABEL_NONE / NaN."""
+        cent = np.ascontiguousarray(centroids, dtype=np.float32)
+        cent = cent.reshape(1, -1) if cent.ndim == 1 else cent
+        assign = np.full(len(self), LABEL_NONE, dtype=np.uint32)
+        best = np.full(len(self), np.nan, dtype=np.float32)
+        unsure = C.c_uint64()
+        L.check(self._lib.vdb_kmeans_assign(self._h, _ptr(cent, L.f32p), cent.shape[0], cent.shape[1], None if mask is None else mask._h,
+                                            _ptr(assign, L.u32p), _ptr(best, L.f32p), C.byref(unsure)))
+        return assign, best, int(unsure.value)
+
+    def kmeans_assign_device(self, centroids_ptr: int, c: int, out_assign_ptr: int, out_best_ptr: int = 0, mask: RowMask | None = None, stream: int = 0):
+        """the same on device memory (vdb_kmeans_assign_device): centroids f32 [c][dim] in, assign u32 [len] and best f32 [len] (0: not
+        wanted) out; returns the unsure count, synchronised"""
+        unsure = C.c_uint64()
+        L.check(self._lib.vdb_kmeans_assign_device(self._h, L.vp(centroids_ptr), int(c), self.dim, None if mask is None else mask._h,
+                                                   L.vp(out_assign_ptr), L.vp(out_best_ptr) if out_best_ptr else None, C.byref(unsure), L.vp(stream)))
+        return int(unsure.value)
+
+    @staticmethod
+    def kmeans_plan(n_rows: int, dim: int, c: int, m_allowed: int | None = None, elem_u8: bool = False, lloyd: bool = True, cosine: bool = False,
+                    xn: float = 1.0, cn: float = 1.0, d_best: float = 0.0):
+        """(row_tiles, cent_tiles, k_blocks, order_passes, scratch_bytes, err) of a k-means call (vdb_kmeans_plan; host only, no GPU): the
+        workgroups of the matrix pass, the centroid tiles each streams, the MFMA k-blocks per product, the digit passes of the member sort,
+        the device bytes held besides the outputs, and the margin E below which a row takes the exact fold, for rows of norm <= xn,
+        centroids of norm <= cn and a best distance <= d_best.  Raises VdbError for what the call refuses by its arguments."""
+        masked = m_allowed is not None
+        o = [C.c_uint64() for _ in range(5)]
+        err = C.c_float()
+        L.check(L.load().vdb_kmeans_plan(int(n_rows), int(dim), int(bool(elem_u8)), int(masked), int(m_allowed if masked else n_rows), int(c),
+                                         int(bool(lloyd)), int(bool(cosine)), float(xn), float(cn), float(d_best), *(C.byref(x) for x in o),
+                                         C.byref(err)))
+        return tuple(int(x.value) for x in o) + (float(err.value),)
+
     def make_mask_where_sets(self, terms) -> RowMask:
         """the mask of the rows that match EVERY LabelTerm of `terms` -- set and range predicates over the label columns, built on the
         device (vdb_mask_create_where_sets); no terms: every row"""

@@ -1279,6 +1279,31 @@ class VecDB:
                 t.drop_masks_naming([field])
             return len(groups), len(value)
 
+    def cluster(self, key: str, n_clusters: int, field: str, filter=None, max_iter: int = 20, tol: float = 1e-4, seed: int | None = None):
+        """k-means over the rows that match `filter` (every row without one): (centroids, sizes) -- an (n_clusters, dim) float32 array and
+        the rows per cluster -- and the cluster id of every clustered row, as a decimal string ("0", "1", ..), written into the metadata key
+        `field`; rows outside the filter keep their value of `field`.  So filter={field: "7"}, group_by=field, count_by(key, field) and
+        search_like work on the clusters at once.  ONE GpuIndex.kmeans call under the write lock and the filter's mask (seed None: 0), then
+        the write goes the way mark_duplicates' does: ONE GpuIndex.set_labels_rows call when `field` has a label column, then the host
+        dicts, then exactly the cached masks that name `field` are dropped; ids, vectors, HNSW and PQ state stay."""
+        t = self._t(key)
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.write():
+            mk = None if filter is None else t.mask_for(filter)
+            cent, assign, sizes, _, _ = t.index.kmeans(n_clusters, max_iter, tol, 0 if seed is None else seed, mask=mk)
+            rows = np.arange(len(t.metadata), dtype=np.int64) if mk is None else np.asarray(mk.rows()[1], dtype=np.int64)
+            if rows.size:
+                ids = assign[rows].tolist()
+                col = t.codec.column_of(field)
+                if col is not None:
+                    code_of = {c: t.codec.encode_value(field, str(c)) for c in set(ids)}
+                    t.index.set_labels_rows(rows.astype(np.uint64), [col], np.array([[code_of[c] for c in ids]], dtype=np.uint32))
+                for r, c in zip(rows.tolist(), ids):
+                    self._apply_changes(t.metadata[r], {field: str(c)})
+                t.drop_masks_naming([field])
+            return cent, sizes
+
     def delete_duplicates(self, key: str, radius: float, filter=None, limit: int | None = None) -> int:
         """Removes every row of a find_duplicates group except its representative (the lowest row); returns the number removed.  ONE
         GpuIndex.remove_rows call; the metadata follow the moves it reports, and the HNSW index and the PQ table are cleared, as delete
