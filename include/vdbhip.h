@@ -569,6 +569,56 @@ int vdb_flat_dup_groups_device(vdb_index *idx, float radius, uint64_t limit, con
                                void *stream);
 int vdb_link_pairs_device(vdb_index *idx, const void *d_src, const void *d_lims, const void *d_ids, uint64_t nq, void *d_group,
                           uint64_t *out_stats, void *stream);
+/* ---- density clustering (DBSCAN) of a table's rows: the same range self-join, then core test, core components, border rows, noise --------
+ * "Which rows form dense regions of any shape, and which are outliers?"  No n_clusters; one stray row does not join two topics, as it does
+ * under single linkage (vdb_flat_dup_groups is this call at min_samples = 1).  (csrc/dbscan_plan.hpp, csrc/flat_dbscan.hip,
+ * csrc/k_dbscan.hip; docs/DESIGN_flat.md 4.1ae.)  The reference has no counterpart; this is THE RULE.
+ * The allowed rows are all rows, or the rows of a mask.
+ *   Neighbourhood.  N(i) is the set of allowed rows the exact range search lists for query = row i at radius eps with no limit.  This is
+ *     the list vdb_flat_range / vdb_flat_range_filtered returns, boundary included.  Row i itself is on it when D(i, i) <= eps.  A NaN row
+ *     lists nothing.
+ *   Core.  Row i is CORE iff |N(i)| >= min_samples.  The row itself counts, as in scikit-learn.
+ *   Clusters.  Two core rows are linked when one is in the other's neighbourhood.  A CLUSTER is a connected component of the core rows.  It
+ *     is named by its LOWEST CORE ROW.
+ *   Border.  A non-core row with at least one core row in N(i) is a BORDER row.  It joins the cluster of the core row with the smallest
+ *     (distance, row) key, the order the range list already has.
+ *   Noise.  Every other allowed row is NOISE.
+ *   Determinism.  The answer is a function of the table, eps, min_samples and the mask alone.  The order of waves, chunks
+ *     ("flat_dup_chunk") and launches does not matter.
+ *   There is no `limit` parameter: a truncated list breaks the core test.
+ * Outputs per row: out_label [len] u64 = the cluster's lowest core row + id_offset, VDB_ROW_NOISE for noise, VDB_ROW_NONE for a row outside
+ * the mask; out_kind [len] u8 = 0 outside, 1 noise, 2 border, 3 core; out_stats [5] = clusters | core rows | border rows | noise rows |
+ * non-self pairs seen (a pair both ends list counts twice).
+ * How: the chunks of queries are those of vdb_flat_dup_groups (one walk, csrc/self_join.hpp).  Behind each range call k_dbscan_core takes
+ * |N(i)| from the CSR limits and k_dbscan_link walks every list with a wave, in tiles of 64: core-core pairs go into a union-find over 4 B
+ * per row, a core row offers its (distance, row) key to each non-core neighbour by a 64-bit integer atomic min, a non-core row takes the
+ * first core row of its own list.  A listed row above the chunk's last query is left to its own chunk -- ONE pass is enough because the pair
+ * distances are symmetric bit for bit.  Integer atomics only, nothing waits for another thread.  Peak memory: one chunk's range result + 13 B
+ * per row + the chunk's gathered queries.  The range calls advance the "flat_range_*" counters and obey "flat_range_max_results" per chunk.
+ * Refused, outputs and the three counters below untouched: a NaN eps, min_samples outside 1 .. 2^32 - 1 (VDB_ERR_INVALID), a mask of
+ * another index (VDB_ERR_INVALID) or a stale one (VDB_ERR_STATE), a NULL output; a chunk whose range call fails fails the whole call the
+ * same way.  An empty index and an empty mask succeed (stats 0).  Read-side, re-entrant, f32 and VecSet<u8> indexes; both forms return
+ * synchronised; the _device form writes d_out_label (u64 [len], 8-byte aligned) and d_out_kind (u8 [len]) after waiting for `stream`.
+ * vdb_dbscan_pairs_device: the stage alone over a caller-supplied CSR list on the index's GPU -- d_src [nq] the u64 ids of the lists'
+ *   source rows, d_lims [nq + 1] u64 ascending from 0, d_ids / d_dists [d_lims[nq]] u64 ids and f32 distances, every list
+ *   ascending by (distance, id) and naming an id at most once (all four non-NULL whenever nq > 0).  The list is checked as
+ *   vdb_link_pairs_device checks its list, and two lists with the same source row are refused too (they would race for its kind; one bit
+ *   per row, set by an integer atomic OR), all before any output is written.  All lists count as one chunk, so every listed pair is
+ *   processed; every row is allowed; a row that is no source has an empty neighbourhood.
+ * vdb_dbscan_plan: host utility, works without a GPU: the argument check (also: an index of 2^32 rows or more, a chunk outside 1 .. 2^20,
+ *   an allowed count that does not fit the index) and the number of range calls, the last chunk's length, whether the queries are gathered,
+ *   and the scratch bytes besides a chunk's result.  Any output may be NULL; on an error nothing is written.
+ * vdb_get_stat: "flat_dbscan_calls" (calls that succeeded), "flat_dbscan_chunks" (their range calls), "flat_dbscan_pairs" (non-self pairs
+ * they saw).  vdb_prof_get "dbscan_link" (core test + list walk) / "dbscan_labels" time the kernels. */
+#define VDB_ROW_NOISE (VDB_ROW_NONE - 1) /* vdb_flat_dbscan: an allowed row in no cluster */
+int vdb_dbscan_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m_allowed, float eps, uint64_t min_samples, uint64_t chunk,
+                    uint64_t *out_chunks, uint64_t *out_last, int *out_gather, uint64_t *out_scratch_bytes);
+int vdb_flat_dbscan(vdb_index *idx, float eps, uint64_t min_samples, const vdb_mask *mask /* NULL: all rows */, uint64_t *out_label /* [len] */,
+                    uint8_t *out_kind /* [len] */, uint64_t *out_stats /* [5] */);
+int vdb_flat_dbscan_device(vdb_index *idx, float eps, uint64_t min_samples, const vdb_mask *mask, void *d_out_label, void *d_out_kind,
+                           uint64_t *out_stats, void *stream);
+int vdb_dbscan_pairs_device(vdb_index *idx, const void *d_src, const void *d_lims, const void *d_ids, const void *d_dists, uint64_t nq,
+                            uint64_t min_samples, void *d_out_label, void *d_out_kind, uint64_t *out_stats, void *stream);
 /* ---- grouped Flat k-NN: at most group_size hits per value of one label column -----------------------------------------------------------
  * "The 10 nearest chunks, at most 2 per document": the label columns so far restrict WHICH rows may be found; this call shapes the answer.
  * For one query let L be its allowed rows in FlatIndex::knn's order -- ascending by (distance, id), NaN distances last; all rows, or
@@ -1004,6 +1054,8 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *                        rows through an assignment step; "kmeans_unsure_rows": of them through the exact fold,
  *   "flat_dup_calls"     vdb_flat_dup_groups / _device calls that succeeded; "flat_dup_chunks": the range calls under them;
  *                        "flat_dup_pairs": the non-self pairs they saw,
+ *   "flat_dbscan_calls"  vdb_flat_dbscan / _device calls that succeeded; "flat_dbscan_chunks": the range calls under them;
+ *                        "flat_dbscan_pairs": the non-self pairs they saw,
  *   "update_calls"       vdb_index_update_rows / _device calls that changed rows (m > 0, not refused); "update_rows": the rows they rewrote,
  *   "fetch_calls"        vdb_index_get_rows* calls that fetched rows (m > 0, not refused); "fetch_rows": the rows they returned;
  *                        "fetch_chunks": their gather launches; "fetch_direct": the calls answered by one plain copy,

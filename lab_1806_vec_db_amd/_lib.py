@@ -77,6 +77,10 @@ SIGNATURES = {
     "vdb_flat_dup_groups": [vp, C.c_float, u64, vp, u64p, u64p],
     "vdb_flat_dup_groups_device": [vp, C.c_float, u64, vp, vp, u64p, vp],
     "vdb_link_pairs_device": [vp, vp, vp, vp, u64, vp, u64p, vp],
+    "vdb_dbscan_plan": [u64, u64, C.c_int, C.c_int, u64, C.c_float, u64, u64, u64p, u64p, intp, u64p],
+    "vdb_flat_dbscan": [vp, C.c_float, u64, vp, u64p, u8p, u64p],
+    "vdb_flat_dbscan_device": [vp, C.c_float, u64, vp, vp, vp, u64p, vp],
+    "vdb_dbscan_pairs_device": [vp, vp, vp, vp, vp, u64, u64, vp, vp, u64p, vp],
     "vdb_kmeans_plan": [u64, u64, C.c_int, C.c_int, u64, u64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, u64p, u64p, u64p, u64p, u64p, f32p],
     "vdb_kmeans_segment": [u64, u64, u64p, u64p],
     "vdb_flat_kmeans": [vp, u64, u64, C.c_float, u64, f32p, u64, vp, f32p, u32p, u64p, u64p, f64p],

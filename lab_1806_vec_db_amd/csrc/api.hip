@@ -985,6 +985,91 @@ int vdb_link_pairs_device(vdb_index *idx, const void *d_src, const void *d_lims,
     std::memcpy(out_stats, stats, sizeof(stats));
     VDB_API_END
 }
+// density clustering: the same self-join, then core test, core components, border rows, noise (Index::flat_dbscan_device, dbscan_plan.hpp,
+// flat_dbscan.hip)
+int vdb_dbscan_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m_allowed, float eps, uint64_t min_samples, uint64_t chunk,
+                    uint64_t *out_chunks, uint64_t *out_last, int *out_gather, uint64_t *out_scratch_bytes) {
+    VDB_API_BEGIN
+    const std::string bad = dbscan_check_args(n_rows, m_allowed, masked != 0, eps, min_samples, chunk);
+    VDB_REQUIRE(bad.empty(), bad);
+    const DbscanPlan p = dbscan_plan(n_rows, dim, elem_u8 != 0, masked != 0, m_allowed, chunk);
+    if (out_chunks) *out_chunks = p.walk.n_chunks;
+    if (out_last) *out_last = p.walk.last_len;
+    if (out_gather) *out_gather = p.walk.gather ? 1 : 0;
+    if (out_scratch_bytes) *out_scratch_bytes = p.scratch_bytes;
+    VDB_API_END
+}
+// what both forms refuse before a workspace is taken -> the mask as a RowMask (nullptr: all rows)
+static const RowMask *dbscan_check(const Index &ix, float eps, uint64_t min_samples, const vdb_mask *mask, const void *out_label, const void *out_kind,
+                                   const void *out_stats) {
+    VDB_REQUIRE(out_stats && (ix.n == 0 || (out_label && out_kind)), "dbscan: null argument");
+    if (mask) ix.check_mask(mask->m);
+    const std::string bad = dbscan_check_args(ix.n, mask ? mask->m.m : ix.n, mask != nullptr, eps, min_samples, ix.dup_chunk);
+    VDB_REQUIRE(bad.empty(), bad);
+    return mask ? &mask->m : nullptr;
+}
+int vdb_flat_dbscan(vdb_index *idx, float eps, uint64_t min_samples, const vdb_mask *mask, uint64_t *out_label, uint8_t *out_kind, uint64_t *out_stats) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const RowMask *rm = dbscan_check(ix, eps, min_samples, mask, out_label, out_kind, out_stats);
+    ix.use_device();
+    WsLease ws(ix);
+    DevBuf d_label, d_kind;
+    d_label.reserve(std::max<uint64_t>(ix.n, 1) * sizeof(uint64_t));
+    d_kind.reserve(std::max<uint64_t>(ix.n, 1));
+    uint64_t stats[DBSCAN_STATS];
+    run_synced(ix, *ws, [&] {
+        ix.flat_dbscan_device(*ws, eps, min_samples, rm, d_label.as<uint64_t>(), d_kind.as<uint8_t>(), stats);
+        if (ix.n) VDB_HIP(hipMemcpyAsync(out_label, d_label.p, ix.n * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+        if (ix.n) VDB_HIP(hipMemcpyAsync(out_kind, d_kind.p, ix.n, hipMemcpyDeviceToHost, ws->stream));
+        VDB_SYNC(ws->stream);
+    });
+    std::memcpy(out_stats, stats, sizeof(stats));
+    VDB_API_END
+}
+int vdb_flat_dbscan_device(vdb_index *idx, float eps, uint64_t min_samples, const vdb_mask *mask, void *d_out_label, void *d_out_kind,
+                           uint64_t *out_stats, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const RowMask *rm = dbscan_check(ix, eps, min_samples, mask, d_out_label, d_out_kind, out_stats);
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_out_label) % 8 == 0, "dbscan: d_out_label must be 8-byte aligned");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever last used the outputs on the caller's stream
+    uint64_t stats[DBSCAN_STATS];
+    run_synced(ix, *ws, [&] {
+        ix.flat_dbscan_device(*ws, eps, min_samples, rm, static_cast<uint64_t *>(d_out_label), static_cast<uint8_t *>(d_out_kind), stats);
+    });
+    std::memcpy(out_stats, stats, sizeof(stats));
+    VDB_API_END
+}
+int vdb_dbscan_pairs_device(vdb_index *idx, const void *d_src, const void *d_lims, const void *d_ids, const void *d_dists, uint64_t nq,
+                            uint64_t min_samples, void *d_out_label, void *d_out_kind, uint64_t *out_stats, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    VDB_REQUIRE(out_stats && (ix.n == 0 || (d_out_label && d_out_kind)) && (nq == 0 || (d_src && d_lims && d_ids && d_dists)),
+                "dbscan pairs: null argument");
+    VDB_REQUIRE(nq < (1ull << 32), "dbscan pairs: too many lists for one call");
+    const std::string bad = dbscan_check_min_samples(min_samples);
+    VDB_REQUIRE(bad.empty(), bad);
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % 8 == 0 && reinterpret_cast<uintptr_t>(d_lims) % 8 == 0 && reinterpret_cast<uintptr_t>(d_ids) % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(d_dists) % 4 == 0 && reinterpret_cast<uintptr_t>(d_out_label) % 8 == 0,
+                "dbscan pairs: the device arrays must be 8-byte aligned (the distances: 4)");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the lists on the caller's stream
+    uint64_t stats[DBSCAN_STATS];
+    run_synced(ix, *ws, [&] {
+        ix.dbscan_pairs_device(*ws, static_cast<const uint64_t *>(d_src), static_cast<const uint64_t *>(d_lims), static_cast<const uint64_t *>(d_ids),
+                               static_cast<const float *>(d_dists), nq, min_samples, static_cast<uint64_t *>(d_out_label),
+                               static_cast<uint8_t *>(d_out_kind), stats);
+    });
+    std::memcpy(out_stats, stats, sizeof(stats));
+    VDB_API_END
+}
 // k-means over the rows (Index::flat_kmeans_device / kmeans_assign_device, kmeans_plan.hpp, flat_kmeans.hip)
 int vdb_kmeans_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m, uint64_t c, int lloyd, int cosine, float xn, float cn,
                     float d_best, uint64_t *out_row_tiles, uint64_t *out_cent_tiles, uint64_t *out_k_blocks, uint64_t *out_order_passes,
@@ -2142,6 +2227,12 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.dup_chunks.load();
     else if (n == "flat_dup_pairs")
         *out = idx->ix.dup_pairs.load();
+    else if (n == "flat_dbscan_calls")  // vdb_flat_dbscan / _device: calls that succeeded | range calls (chunks) under them | non-self pairs they saw
+        *out = idx->ix.dbscan_calls.load();
+    else if (n == "flat_dbscan_chunks")
+        *out = idx->ix.dbscan_chunks.load();
+    else if (n == "flat_dbscan_pairs")
+        *out = idx->ix.dbscan_pairs.load();
     else if (n == "flat_grouped_calls")  // grouped k-NN: calls | queries | rounds run, summed over calls | queries whose last list was their whole allowed set
         *out = idx->ix.grouped_calls.load();
     else if (n == "flat_grouped_queries")

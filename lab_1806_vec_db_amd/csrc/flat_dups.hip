@@ -3,12 +3,13 @@
 // flat_range_device returns for query = row i (radius, limit, mask) names its neighbours; every j != i on it is an undirected edge;
 // the groups are the connected components of the allowed rows under these edges -- SINGLE LINKAGE at the radius: A-B and B-C put A and
 // C together even when D(A, C) > radius -- and a group is named by its lowest row.  dup_plan.hpp checks and lays out the chunks,
-// k_components.hip holds the union-find.
+// self_join.hpp walks them (shared with flat_dbscan.hip), k_components.hip holds the union-find.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 #include "index.hpp"
+#include "self_join.hpp"
 
 namespace vdb {
 
@@ -51,43 +52,15 @@ void Index::flat_dup_groups_device(Workspace &ws, float radius, uint64_t limit, 
         return;
     }
     const DupPlan plan = dup_plan(n, dim, elem_u8, mask != nullptr, mask ? mask->m : n, dup_chunk);
-    // every buffer of the call before its first launch: the range calls use the workspace's other buffers
     Components cc;
-    DevBuf aux;  // [radii f32 x chunk_len | limits u64 x (chunk_len + 1)]
-    const size_t lims_off = (plan.chunk_len * sizeof(float) + 7) & ~size_t(7);
-    aux.reserve(lims_off + (plan.chunk_len + 1) * sizeof(uint64_t));
-    if (plan.gather) ws.grp_q.reserve(std::max<uint64_t>(plan.chunk_len, 1) * dim * sizeof(float));
-    const std::vector<float> h_radius(plan.chunk_len, radius);  // (alive until the call has synchronised)
-    if (plan.chunk_len) VDB_HIP(hipMemcpyAsync(aux.p, h_radius.data(), plan.chunk_len * sizeof(float), hipMemcpyHostToDevice, s));
-    cc.start(*this, s);
-    VDB_SYNC(s);
-    uint64_t *d_lims = reinterpret_cast<uint64_t *>(aux.as<char>() + lims_off);
-    for (uint64_t c = 0; c < plan.n_chunks; c++) {
-        const uint64_t a = c * dup_chunk, nb = c + 1 == plan.n_chunks ? plan.last_len : dup_chunk;
-        const float *Q;
-        if (!plan.gather)
-            Q = d_rows.as<float>() + a * dim;  // the rows are the queries, where they lie
-        else {
-            Q = ws.grp_q.as<float>();
-            if (mask && elem_u8)
-                launch_rows_gather_widen(d_rows.as<uint8_t>(), dim, mask->d_ids.as<uint32_t>() + a, false, 0, ws.grp_q.as<float>(), nb, num_cu, s);
-            else if (mask)
-                launch_rows_gather(d_rows.p, dim * sizeof(float), mask->d_ids.as<uint32_t>() + a, false, 0, ws.grp_q.p, nb, num_cu, s);
-            else
-                launch_widen_u8(d_rows.as<uint8_t>() + a * dim, nb * dim, ws.grp_q.as<float>(), s);
-        }
-        RangeResult r;  // dropped at the end of the chunk: peak memory is one chunk's result
-        flat_range_device(ws, Q, nb, aux.as<float>(), limit, r, mask);
-        const uint64_t total = r.lims[nb];
-        if (total) {
-            VDB_HIP(hipMemcpyAsync(d_lims, r.lims.data(), (nb + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-            prof_begin(ws, "dup_hook", double(total) * sizeof(uint64_t));
-            launch_comp_hook(nullptr, mask ? mask->d_ids.as<uint32_t>() + a : nullptr, a, d_lims, r.idx.as<uint64_t>(), nb, total, id_offset, limit,
-                             cc.parent.as<uint32_t>(), cc.cnt(), num_cu, s);
+    walk_self_join(
+        *this, ws, plan, dup_chunk, radius, limit, mask, [&] { cc.start(*this, s); },
+        [&](const SelfJoinChunk &ch) {
+            prof_begin(ws, "dup_hook", double(ch.total) * sizeof(uint64_t));
+            launch_comp_hook(nullptr, ch.src32, ch.a, ch.d_lims, ch.r.idx.as<uint64_t>(), ch.nb, ch.total, id_offset, limit, cc.parent.as<uint32_t>(),
+                             cc.cnt(), num_cu, s);
             prof_end(ws);
-            VDB_SYNC(s);  // (r and its limits go out of scope)
-        }
-    }
+        });
     uint64_t h_stats[DUP_STATS];
     cc.finish(*this, ws, mask ? mask->d_bits.as<uint64_t>() : nullptr, d_group, h_stats);
     std::memcpy(stats, h_stats, sizeof(h_stats));

@@ -777,6 +777,22 @@ struct Index {
                            uint64_t *stats);
     uint64_t dup_chunk = DUP_CHUNK_DEFAULT;  // "flat_dup_chunk": queries per range call of the self-join
     std::atomic<uint64_t> dup_calls{0}, dup_chunks{0}, dup_pairs{0};  // flat_dup_groups calls that succeeded / their range calls / non-self pairs they saw
+    // Density clustering, DBSCAN (flat_dbscan.hip, k_dbscan.hip, dbscan_plan.hpp -- which states the rule; docs/DESIGN_flat.md 4.1ae) over the
+    // same self-join with no limit: row i is core iff its list holds at least min_samples rows (itself included), the clusters are the
+    // components of the core rows, a non-core row with a core row on its list joins the one with the smallest (distance, row) key, the rest
+    // is noise.  d_label [n] u64 on the device: the lowest core row of the row's cluster + id_offset, DBSCAN_ROW_NOISE, DBSCAN_ROW_NONE
+    // outside the mask; d_kind [n] u8: 0 outside, 1 noise, 2 border, 3 core; stats [DBSCAN_STATS] on the host: clusters, core, border and
+    // noise rows, non-self pairs seen.  Walks the chunks flat_dup_groups_device walks (self_join.hpp; dup_chunk).  Read-side, re-entrant;
+    // the outputs and the dbscan_* counters are written only when every chunk has succeeded.  The caller has run dbscan_check_args; the mask
+    // is checked here.  Returns synchronised.
+    void flat_dbscan_device(Workspace &ws, float eps, uint64_t min_samples, const RowMask *mask, uint64_t *d_label, uint8_t *d_kind, uint64_t *stats);
+    // The stage alone over a caller-supplied CSR list on the device: d_src [nq] u64 ids of the lists' source rows (distinct: checked), d_lims [nq + 1]
+    // from 0, d_ids / d_dists [d_lims[nq]], every list ascending by (distance, index) and holding an id at most once.  Checked as
+    // link_pairs_device checks its list.  All lists count as one chunk, so every listed pair is processed; every row is allowed, and a row
+    // that is no source has an empty neighbourhood.  Returns synchronised.
+    void dbscan_pairs_device(Workspace &ws, const uint64_t *d_src, const uint64_t *d_lims, const uint64_t *d_ids, const float *d_dists, uint64_t nq,
+                             uint64_t min_samples, uint64_t *d_label, uint8_t *d_kind, uint64_t *stats);
+    std::atomic<uint64_t> dbscan_calls{0}, dbscan_chunks{0}, dbscan_pairs{0};  // flat_dbscan calls that succeeded / their range calls / non-self pairs they saw
     // k-means over the rows (flat_kmeans.hip, k_kmeans.hip, kmeans_plan.hpp; docs/DESIGN_flat.md 4.1ad).  The rows clustered are the mask's
     // allowed rows (nullptr: all); d_assign [n] u32 and d_best [n] f32 are indexed by row, KM_LABEL_NONE / NaN for a row outside the mask.
     // kmeans_assign_device: the assignment step alone against d_cent [c][dim] on the device -- row i to the centroid with the smallest

@@ -15,50 +15,19 @@
 // read by find is an older ancestor, which is still an ancestor.  No float atomics anywhere.
 #include <algorithm>
 
+#include "comp_uf.hpp"
 #include "kernels.hpp"
 
 namespace vdb {
 
-#define COMP_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+// (comp_find, comp_find_ro, comp_link: comp_uf.hpp, shared with k_dbscan.hip)
 
-__device__ __forceinline__ uint32_t comp_load(uint32_t *p) { return __hip_atomic_load(p, COMP_RLX); }
-
-// the root of x, halving the path on the way: every other row of it is pointed at its grandparent
-__device__ __forceinline__ uint32_t comp_find(uint32_t *parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = comp_load(parent + x);
-        if (p == x) return x;
-        const uint32_t g = comp_load(parent + p);
-        if (g == p) return p;
-        __hip_atomic_store(parent + x, g, COMP_RLX);  // (x is no root and never will be: no CAS of a hook can succeed on it)
-        x = g;
-    }
-}
-__device__ __forceinline__ uint32_t comp_find_ro(uint32_t *parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = comp_load(parent + x);
-        if (p == x) return x;
-        x = p;
-    }
-}
-__device__ __forceinline__ void comp_link(uint32_t *parent, uint32_t u, uint32_t v) {
-    for (;;) {
-        u = comp_find(parent, u);
-        v = comp_find(parent, v);
-        if (u == v) return;
-        const uint32_t hi = u > v ? u : v, lo = u > v ? v : u;
-        uint32_t seen = hi;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, COMP_RLX)) return;
-        u = seen;  // hi was hooked by somebody else in the meantime: on from where it points now
-        v = lo;
-    }
-}
-
+// (size == nullptr: the caller keeps no sizes)
 __global__ __launch_bounds__(256) void k_comp_init(uint32_t *__restrict__ parent, uint32_t *__restrict__ size, uint64_t n) {
     const uint64_t stride = uint64_t(gridDim.x) * 256;
     for (uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += stride) {
         parent[i] = (uint32_t)i;
-        size[i] = 0;
+        if (size) size[i] = 0;
     }
 }
 

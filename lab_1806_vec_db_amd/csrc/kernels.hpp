@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "dbscan_plan.hpp"
 #include "dup_plan.hpp"
 #include "fuse_groups_plan.hpp"
 #include "fuse_plan.hpp"
@@ -468,6 +469,24 @@ void launch_comp_flatten(uint32_t *parent, const uint64_t *bits, uint64_t n, uin
 // zeroed by the caller; nq > 0
 void launch_pairs_check(const uint64_t *src, const uint64_t *lims, const uint64_t *ids, uint64_t nq, uint64_t n, uint64_t id_offset, uint64_t *out,
                         int num_cu, hipStream_t s);
+// Density clustering over CSR neighbour lists with distances (k_dbscan.hip, dbscan_plan.hpp; the union-find of comp_uf.hpp).  State: parent
+// [n] u32, border [n] u64, kind [n] u8, counters [8] u64 (clusters | core | border | noise | non-self pairs | spare | two check words).
+// init: parent[i] = i, border = PAIR_NONE, kind = 1 for a row bits allows (nullptr: every row) else 0, counters [0, 6) zero.  chunk: the
+// lists of nq queries (lims [nq + 1] from 0, ids u64 = row + id_offset, dists f32, each list ascending by (distance, index), all checked by
+// the caller; query q's source row as for launch_comp_hook) -- k_dbscan_core sets kind of the source rows from the list lengths, then
+// k_dbscan_link, a wave per list, links core rows and offers (distance, core row) keys to non-core rows; with more_chunks (the queries
+// ascend by row, later chunks follow) every listed row above the last query's row is left to that row's own list.  labels: label[i] = the
+// lowest core row of i's cluster + id_offset, DBSCAN_ROW_NOISE, or DBSCAN_ROW_NONE outside the mask; kind_out[i] = 0 outside, 1 noise, 2
+// border, 3 core; the four counts, from the final kinds.  Integer atomics only.
+void launch_dbscan_init(const uint64_t *bits, uint64_t n, uint32_t *parent, uint64_t *border, uint8_t *kind, uint64_t *counters, int num_cu,
+                        hipStream_t s);
+// out[0] |= 2 when two of the nq source ids src[q] name one row below n; seen: ceil(n / 32) u32 words zeroed by the caller
+void launch_dbscan_sources(const uint64_t *src, uint64_t nq, uint64_t n, uint64_t id_offset, uint32_t *seen, uint64_t *out, int num_cu, hipStream_t s);
+void launch_dbscan_chunk(const uint64_t *src64, const uint32_t *src32, uint64_t src_base, const uint64_t *lims, const uint64_t *ids,
+                         const float *dists, uint64_t nq, uint64_t id_offset, uint64_t min_samples, bool more_chunks, uint8_t *kind, uint32_t *parent,
+                         uint64_t *border, uint64_t *counters, int num_cu, hipStream_t s);
+void launch_dbscan_labels(uint32_t *parent, const uint8_t *kind, const uint64_t *border, uint64_t n, uint64_t id_offset, uint64_t *label,
+                          uint8_t *kind_out, uint64_t *counters, int num_cu, hipStream_t s);
 // One Lloyd iteration over the rows X [..][dim] of an f32 index (k_kmeans.hip, kmeans_plan.hpp).  Positions 0 .. m are the rows ids[0 .. m)
 // (nullptr: position = row); assign / best are indexed by ROW.  prep: the centroids C [c][dim] as split-bf16 planes in fragment order, csq =
 // their strict-fold |c|^2 padded with zeros to whole tiles of 64, *cmax_bits = max of its bits (zeroed by the caller).  assign: the matrix

@@ -80,6 +80,8 @@ def pack_mask(allow, n: int) -> np.ndarray:
 LABEL_COLUMNS = 16         # VDB_LABEL_COLUMNS
 LABEL_NONE = 0xFFFFFFFF    # VDB_LABEL_NONE
 ROW_NONE = 2 ** 64 - 1     # VDB_ROW_NONE: label_lookup's "no row carries the code"
+ROW_NOISE = ROW_NONE - 1   # VDB_ROW_NOISE: dbscan's "an allowed row in no cluster"
+_DBSCAN_STATS = ("clusters", "core", "border", "noise", "pairs")
 MASK_MAX_TERMS = 8         # VDB_MASK_MAX_TERMS
 MASK_OP_AND, MASK_OP_OR = 0, 1  # VDB_MASK_OP_AND / VDB_MASK_OP_OR
 LIKE_MAX_EXAMPLES = 1024   # examples of one query of flat_knn_like, positives plus negatives (LIKE_MAX_EXAMPLES of csrc/like_plan.hpp)
@@ -626,6 +628,66 @@ class GpuIndex:
         chunks, last, gather, scratch = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_uint64()
         L.check(L.load().vdb_dup_plan(int(n_rows), int(dim), int(bool(elem_u8)), int(masked), int(m_allowed if masked else n_rows), float(radius),
                                       int(limit or 0), int(chunk), C.byref(chunks), C.byref(last), C.byref(gather), C.byref(scratch)))
+        return int(chunks.value), int(last.value), bool(gather.value), int(scratch.value)
+
+    def dbscan(self, eps: float, min_samples: int, mask: RowMask | None = None):
+        """Density clustering (DBSCAN) of the index's own rows, or the mask's (vdb_flat_dbscan): (label, kind, stats).  The rule:
+          Neighbourhood.  N(i) is the set of allowed rows the exact range search lists for query = row i at radius eps with no limit:
+            the list range_search returns, boundary included.  Row i itself is on it when D(i, i) <= eps.  A NaN row lists nothing.
+          Core.  Row i is core iff |N(i)| >= min_samples.  The row itself counts, as in scikit-learn.
+          Clusters.  Two core rows are linked when one is in the other's neighbourhood.  A cluster is a connected component of the core
+            rows.  It is named by its lowest core row.
+          Border.  A non-core row with at least one core row in N(i) is a border row.  It joins the cluster of the core row with the
+            smallest (distance, row) key, the order the range list already has.
+          Noise.  Every other allowed row is noise.
+          Determinism.  The answer is a function of the table, eps, min_samples and the mask alone.  The order of waves, chunks and
+            launches does not matter.  There is no `limit` parameter: a truncated list breaks the core test.
+        label: uint64 [len], the cluster's lowest core row + id_offset, ROW_NOISE for noise, ROW_NONE for a row outside the mask.  kind:
+        uint8 [len], 0 outside, 1 noise, 2 border, 3 core.  stats: dict with `clusters`, `core`, `border`, `noise` (rows) and `pairs`
+        (non-self pairs seen).  A NaN eps, min_samples outside 1 .. 2^32 - 1 and a stale or foreign mask raise VdbError."""
+        label = np.full(len(self), ROW_NONE, dtype=np.uint64)
+        kind = np.zeros(len(self), dtype=np.uint8)
+        stats = np.zeros(5, dtype=np.uint64)
+        L.check(self._lib.vdb_flat_dbscan(self._h, float(eps), self._min_samples(min_samples), None if mask is None else mask._h,
+                                          _ptr(label, L.u64p), _ptr(kind, L.u8p), _ptr(stats, L.u64p)))
+        return label, kind, dict(zip(_DBSCAN_STATS, (int(x) for x in stats)))
+
+    @staticmethod
+    def _min_samples(v) -> int:
+        """as the C ABI's u64: what does not fit one (a negative count) becomes 0, which the library refuses with its own message"""
+        return int(v) if 0 <= int(v) < 2 ** 64 else 0
+
+    def dbscan_device(self, eps: float, min_samples: int, out_label_ptr: int, out_kind_ptr: int, mask: RowMask | None = None, stream: int = 0):
+        """the same with label (u64 [len], 8-byte aligned) and kind (u8 [len]) written to device memory (vdb_flat_dbscan_device); returns
+        the stats dict, synchronised"""
+        stats = np.zeros(5, dtype=np.uint64)
+        L.check(self._lib.vdb_flat_dbscan_device(self._h, float(eps), self._min_samples(min_samples), None if mask is None else mask._h,
+                                                 L.vp(out_label_ptr), L.vp(out_kind_ptr), _ptr(stats, L.u64p), L.vp(stream)))
+        return dict(zip(_DBSCAN_STATS, (int(x) for x in stats)))
+
+    def dbscan_pairs_device(self, src_ptr: int, lims_ptr: int, ids_ptr: int, dists_ptr: int, nq: int, min_samples: int, out_label_ptr: int,
+                            out_kind_ptr: int, stream: int = 0):
+        """the stage behind the self-join alone over a caller-supplied CSR list on the device (vdb_dbscan_pairs_device): src u64 [nq] the
+        ids of the lists' source rows (distinct, or the call raises), lims u64 [nq + 1] ascending from 0, ids u64 / dists f32 [lims[nq]], every list ascending
+        by (distance, id) and naming an id at most once; label u64 [len] and kind u8 [len] as dbscan writes them.  All lists count as one
+        chunk; every row is allowed; a row that is no source has an empty neighbourhood.  Limits that descend or an id that is no row of
+        this index raise and leave the outputs untouched.  Returns the stats dict."""
+        stats = np.zeros(5, dtype=np.uint64)
+        L.check(self._lib.vdb_dbscan_pairs_device(self._h, L.vp(src_ptr), L.vp(lims_ptr), L.vp(ids_ptr), L.vp(dists_ptr), int(nq),
+                                                  self._min_samples(min_samples), L.vp(out_label_ptr), L.vp(out_kind_ptr), _ptr(stats, L.u64p),
+                                                  L.vp(stream)))
+        return dict(zip(_DBSCAN_STATS, (int(x) for x in stats)))
+
+    @staticmethod
+    def dbscan_plan(n_rows: int, dim: int, eps: float, min_samples: int, m_allowed: int | None = None, chunk: int = 16384, elem_u8: bool = False):
+        """(chunks, last, gather, scratch_bytes) of a dbscan call (vdb_dbscan_plan; host only, no GPU): the range calls it makes, the
+        queries of the last one, whether the queries are gathered (a mask -- m_allowed given -- or u8 rows) and the device bytes held
+        besides one chunk's range result.  Raises VdbError for what dbscan refuses by its arguments."""
+        masked = m_allowed is not None
+        chunks, last, gather, scratch = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_uint64()
+        L.check(L.load().vdb_dbscan_plan(int(n_rows), int(dim), int(bool(elem_u8)), int(masked), int(m_allowed if masked else n_rows), float(eps),
+                                         GpuIndex._min_samples(min_samples), int(chunk), C.byref(chunks), C.byref(last), C.byref(gather),
+                                         C.byref(scratch)))
         return int(chunks.value), int(last.value), bool(gather.value), int(scratch.value)
 
     def kmeans(self, c: int, max_iter: int = 20, tol: float = 1e-4, seed: int = 0, init=None, mask: RowMask | None = None):

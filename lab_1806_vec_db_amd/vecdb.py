@@ -1304,6 +1304,47 @@ class VecDB:
                 t.drop_masks_naming([field])
             return cent, sizes
 
+    def cluster_density(self, key: str, radius: float, min_samples: int, field: str, filter=None) -> dict:
+        """Density clustering (DBSCAN) of the rows that match `filter` (every row without one), written into the metadata key `field`.
+        The rule (GpuIndex.dbscan's, eps = `radius`); the allowed rows are the matching rows:
+          Neighbourhood.  N(i) is the set of allowed rows the exact range search lists for query = row i at radius eps with no limit:
+            the list search_within returns, boundary included.  Row i itself is on it when D(i, i) <= eps.  A NaN row lists nothing.
+          Core.  Row i is core iff |N(i)| >= min_samples.  The row itself counts, as in scikit-learn.
+          Clusters.  Two core rows are linked when one is in the other's neighbourhood.  A cluster is a connected component of the core
+            rows.  It is named by its lowest core row.
+          Border.  A non-core row with at least one core row in N(i) is a border row.  It joins the cluster of the core row with the
+            smallest (distance, row) key, the order the range list already has.
+          Noise.  Every other allowed row is noise.
+          Determinism.  The answer is a function of the table, eps, min_samples and the filter alone.  There is no `limit` parameter: a
+            truncated list breaks the core test.
+        First `field` is REMOVED from every row the filter matches; then every clustered row, core or border, gets the decimal ordinal of
+        its cluster ("0", "1", ..: the clusters ordered by their lowest core row).  Noise rows keep no value; rows outside the filter keep
+        theirs.  So filter={field: "3"}, count_by(key, field) and group_by=field work on the clusters at once, as after cluster.
+        Returns {"clusters", "core", "border", "noise", "sizes"}: counts of clusters and of rows of each kind, and the rows per cluster
+        in ordinal order.  ONE GpuIndex.dbscan call under the write lock and the filter's mask, then the write goes the way
+        mark_duplicates' does: ONE GpuIndex.set_labels_rows call when `field` has a label column, then the host dicts, then exactly the
+        cached masks that name `field` are dropped; ids, vectors, HNSW and PQ state stay."""
+        t = self._t(key)
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.write():
+            mk = None if filter is None else t.mask_for(filter)
+            label, kind, stats = t.index.dbscan(radius, min_samples, mk)
+            rows = np.flatnonzero(kind)  # (the matching rows, ascending)
+            names, ordinal = np.unique(label[rows][kind[rows] >= 2], return_inverse=True)  # (ascending by lowest core row)
+            value: dict[int, str] = {int(r): str(g) for r, g in zip(rows[kind[rows] >= 2].tolist(), ordinal.tolist())}
+            touched = [r for r in rows.tolist() if r in value or field in t.metadata[r]]
+            if touched:
+                col = t.codec.column_of(field)
+                if col is not None:
+                    codes = np.array([[t.codec.encode_value(field, value.get(r)) for r in touched]], dtype=np.uint32)
+                    t.index.set_labels_rows(np.asarray(touched, dtype=np.uint64), [col], codes)
+                for r in touched:
+                    self._apply_changes(t.metadata[r], {field: value.get(r)})
+                t.drop_masks_naming([field])
+            return {"clusters": stats["clusters"], "core": stats["core"], "border": stats["border"], "noise": stats["noise"],
+                    "sizes": np.bincount(ordinal, minlength=len(names)).astype(np.int64)}
+
     def delete_duplicates(self, key: str, radius: float, filter=None, limit: int | None = None) -> int:
         """Removes every row of a find_duplicates group except its representative (the lowest row); returns the number removed.  ONE
         GpuIndex.remove_rows call; the metadata follow the moves it reports, and the HNSW index and the PQ table are cleared, as delete
