@@ -950,7 +950,9 @@ int vdb_index_get_rows_device(vdb_index *idx, const void *d_ids, uint64_t m, voi
 /* the approximate keys the Flat shortlist pass compares with its threshold, for EVERY row, from the same kernel in its dense
  * mode (test / measurement entry point behind the certification-bound tests): out_keys [nq][len];
  * L2Sqr: key = |x|^2 - 2 S~, approximate distance = key + |q|^2;  Cosine: key = -S~ / |x|, approximate distance = 1 + key / |q|.
- * tier 0 = scaled fp16 operands, 1 = split-bf16 operands.  out_qsq [nq] = |q|^2 (strict fold), out_qerr [nq] = measured
+ * tier 0 = scaled fp16 operands, 1 = split-bf16 operands, 2 = the centred 8-bit mirror (lower bounds: D >= key + out_qerr[q]).
+ * tier 3 = the native 8-bit pass of a u8 index: key <= D for every pair, the reference's own f32 value (out_qerr = 0, out_dx4 =
+ * {E(dim), 0, max |x|^2, min positive |x|^2}); queries must be integers in [0, 255].  out_qsq [nq] = |q|^2 (strict fold), out_qerr [nq] = measured
  * |q - q~| of the fp16 query images (0 for tier 1), out_dx4 = {max |dx_r|, max |dx_r| / |x_r|, max |x|^2, min positive |x|^2}.
  * nq <= 1024; any of the last three outputs may be NULL. */
 int vdb_flat_shortlist_keys(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, int tier, float *out_keys,
@@ -971,6 +973,14 @@ int vdb_flat_set_mode(vdb_index *idx, int mode);
  *                      0 auto (off once > 1/8 of its queries were handed on), 1 off, 2 on.  While it is the first tier the fp16 mirror is
  *                      built by its first use instead of at add time (set "flat_i8" = 1 BEFORE adding rows to have it built at add time)
  *   "flat_i8_rows"     rows its exact stage may walk per query before handing the query on (multiple of 64, default 256)
+ *   "flat_u8"          native 8-bit pass of a VecSet<u8> index (dim % 16 == 0, dim <= 1024, k <= 512): the int8 matrix pass runs on the stored
+ *                      bytes themselves -- no mirror, 8 B of exact integer row constants -- and its keys are certified lower bounds of the
+ *                      distances (L2Sqr up to dim 258: the distances).  Queries must be integers in [0, 255] (vdb_flat_knn_u8 always is);
+ *                      any other query, an overflowed hit list or a k-th pair above the bound goes through today's path.  0 auto, 1 off,
+ *                      2 forced.  Auto engages for NO shape yet: at 20k .. 1M rows, dim 128 and 960, both metrics, the pass measured
+ *                      0.43 - 0.75 of the speed of the fp16 route (tools/bench_u8.py), so it runs only when forced.  Forced, the fp16
+ *                      mirror is built by its first use instead of at add time (set "flat_u8" = 2 BEFORE adding rows for an index that
+ *                      holds no mirror at all).  Per index
  *   "flat_gemm_coop"   the same sets for the fp16 / split-bf16 filter kernel (0 auto = on, 1 off)
  *   "flat_gemm8_coop"  cooperative sets of the resident form (calls whose group count is even, tables of >= 98 304 rows, 256-CU chips): the 32
  *                      workgroups of an XCD in sets of 8 / 4 / 2 that take different query groups and walk the same rows at the same time, so
@@ -1034,7 +1044,9 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *   "flat_half_valid"    1 when the index holds the fp16 mirror,
  *   "flat_i8_queries", "flat_i8_redo", "flat_i8_valid"  the same three for the 8-bit first pass (queries through it, queries it handed
  *                        on to the next tier, mirror present),
- *   "flat_bf16_mirror"   1 once the split-bf16 mirror (4 B/element) has been built -- lazily, by the first search that
+ *   "flat_u8_queries", "flat_u8_redo", "flat_u8_valid"  the native 8-bit pass of a u8 index: queries it took, queries it passed on to
+ *                        today's path, 1 when its row constants cover the table (dropped by a removal, rebuilt by the next search),
+ *   "flat_bf16_mirror"  1 once the split-bf16 mirror (4 B/element) has been built -- lazily, by the first search that
  *                        needs it (redo tier, flat_half = 1, calls without an fp16 mirror),
  *   "hnsw_heap_walk_queries"  HNSW queries answered by the any-size heap walk (max(ef, k) > 1024, or the LDS candidate
  *                        pool of the fast walk overflowed),

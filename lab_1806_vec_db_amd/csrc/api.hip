@@ -1921,7 +1921,8 @@ int vdb_flat_shortlist_keys(vdb_index *idx, const float *queries, uint64_t nq, u
     VDB_REQUIRE(idx && queries && out_keys, "null argument");
     Index &ix = idx->ix;
     VDB_REQUIRE(dim == ix.dim, "query dimension mismatch");
-    VDB_REQUIRE(tier >= 0 && tier <= 2, "tier must be 0 (fp16 operands), 1 (split-bf16 operands) or 2 (8-bit operands, lower-bound keys)");
+    VDB_REQUIRE(tier >= 0 && tier <= 3,
+                "tier must be 0 (fp16 operands), 1 (split-bf16 operands), 2 (8-bit operands, lower-bound keys) or 3 (native pass of a u8 table)");
     ix.use_device();
     WsLease ws(ix);
     ws->q.reserve(nq * ix.dim * sizeof(float));
@@ -1997,6 +1998,10 @@ int vdb_set_param(vdb_index *idx, const char *name, int64_t value) {
         idx->ix.flat_half_mode = (int)value;
     else if (n == "flat_i8")  // 8-bit first pass (L2Sqr): 0 auto, 1 off, 2 on regardless of the redo rate
         idx->ix.flat_i8_mode = (int)value;
+    else if (n == "flat_u8") {  // native 8-bit pass of a u8 table (k_gemm_u8.hip): 0 auto, 1 off, 2 forced
+        VDB_REQUIRE(value >= 0 && value <= 2, "flat_u8 must be 0, 1 or 2");
+        idx->ix.flat_u8_mode = (int)value;
+    }
     else if (n == "flat_i8_rows") {  // rows its exact stage may walk per query before giving up (multiple of 64)
         VDB_REQUIRE(value >= 64 && value <= 8192 && value % 64 == 0, "flat_i8_rows must be a multiple of 64 in [64, 8192]");
         idx->ix.flat_i8_kprime = (uint32_t)value;
@@ -2119,6 +2124,12 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.i8_redo.load();
     else if (n == "flat_i8_valid")
         *out = idx->ix.i8_m.valid ? 1 : 0;
+    else if (n == "flat_u8_queries")  // native u8 pass: queries it took | queries it passed on | the row constants cover the table
+        *out = idx->ix.u8_queries.load();
+    else if (n == "flat_u8_redo")
+        *out = idx->ix.u8_redo.load();
+    else if (n == "flat_u8_valid")
+        *out = idx->ix.u8c_m.covers(idx->ix.n) ? 1 : 0;
     else if (n == "flat_range_queries")  // range calls: queries | answered by the 8-bit tier | by the strict-order scan | hits of the tier's | pairs returned
         *out = idx->ix.range_queries.load();
     else if (n == "flat_range_i8_queries")

@@ -99,6 +99,7 @@ void Index::mirrors_shrunk(uint64_t n1) {
         i8_m.rows = n1;
     else
         i8_m.invalidate();  // rows were added since the last search: rebuilt by the next one
+    u8c_m.invalidate();     // (8 B per row: one pass over the table by the next search of the native u8 tier)
     rows_h_m.invalidate();  // (rebuilt by the next walk / scan that uses them)
     rows_q8_m.invalidate();
 }
@@ -166,7 +167,8 @@ void Index::add_rows(const void *rows, uint64_t count, bool on_device) {
     if (mirror) tiled_m.rows = n + count;
     // an fp16 mirror in step is extended (needs the new xsq_max) unless the 8-bit pass is this index's first tier: then it waits for its
     // first use, as does one already behind (ensure_half catches up); one that cannot grow is dropped (as above)
-    if (half_m.rows == n && !i8_defers_half() && half_m.attempt([&] { half_refresh(*ws, n, n + count); })) half_m.rows = n + count;
+    // (nor on a u8 table the native 8-bit tier serves: a search that tier answers builds no mirror at all)
+    if (half_m.rows == n && !i8_defers_half() && !flat_u8_shape() && half_m.attempt([&] { half_refresh(*ws, n, n + count); })) half_m.rows = n + count;
     {
         std::lock_guard<std::mutex> g(host_mu);
         if (on_device || elem_u8) {
@@ -618,6 +620,7 @@ uint64_t Index::hbm_bytes_per_row() const {
         if (half_m.valid) b += uint64_t(mfma_dim_pad((uint32_t)dim)) * sizeof(uint16_t);
     }
     if (i8_m.valid) b += uint64_t(mfma_dim_pad((uint32_t)dim)) + 2 * sizeof(float);
+    if (u8c_m.valid) b += 2 * sizeof(uint32_t);
     if (rows_h_m.valid) b += dim * sizeof(uint16_t);
     if (rows_q8_m.valid) b += dim + 2 * sizeof(float);
     if (pq.present) b += pq.enc_dim * (pq.codes_t_valid ? 2 : 1);
@@ -726,10 +729,27 @@ bool Index::ensure_half(Workspace &ws) {
     }) && half_m.valid;
 }
 
+// ---- row constants of the native u8 tier (k_gemm_u8.hip) --------------------------------------------
+// Auto engages NOWHERE yet: tools/bench_u8.py (profiles/flat_u8_1M.json) has the pass at 0.43 - 0.75 of the speed of the fp16 route on
+// every shape measured (20k, 64k and 1M rows, dim 128 and 960, both metrics), and auto excludes a shape that is slower.  "flat_u8" = 2
+// runs it.  A shape that measures faster is added here, under flat_mode, flat_half and flat_gemm at their defaults and n >= 16 384.
+bool Index::flat_u8_shape() const { return elem_u8 && flat_u8_mode == 2 && flat_u8_supported((uint32_t)dim); }
+bool Index::flat_u8_applies(uint32_t kprime) const { return flat_u8_shape() && kprime <= 1024 && n > kprime; }
+bool Index::ensure_u8c(Workspace &ws) {
+    return u8c_m.ensure(n, [&] { return u8c_m.covers(n); }, [&] {
+        const uint64_t r0 = u8c_m.valid && u8c_m.rows <= n ? u8c_m.rows.load() : 0;  // rows were added: extended; anything else: one pass
+        d_rowc_u8.grow((n + 64) * 2 * sizeof(uint32_t), r0 * 2 * sizeof(uint32_t), ws.stream);
+        launch_u8_row_consts(d_rows.as<uint8_t>(), r0, n, (uint32_t)dim, d_rowc_u8.p, ws.stream);
+        VDB_SYNC(ws.stream);
+        u8c_m.set(n);
+    });
+}
+
 void Index::prepare_flat(bool all_tiers) {
     if (n == 0) return;
     use_device();
     WsLease ws(*this);
+    if (elem_u8 && flat_u8_applies(32)) (void)ensure_u8c(*ws);
     if (!mfma_supported((uint32_t)dim) || elem_u8) return;  // the exact scan needs nothing beyond the rows
     bool first = false;
     if (i8_defers_half() && n > 64) first = ensure_i8(*ws);
@@ -1075,17 +1095,78 @@ struct RedoSet {
 
 // ---- Flat: full pipeline ---------------------------------------------------------------------------
 uint64_t Index::flat_knn_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t *d_idx,
-                                float *d_dist, uint64_t *d_cnt, bool allow_half, uint32_t kprime_min, bool allow_i8, const float *d_dk_hint) {
+                                float *d_dist, uint64_t *d_cnt, bool allow_half, uint32_t kprime_min, bool allow_i8, const float *d_dk_hint,
+                                bool allow_u8) {
     FlatPending p;
-    flat_knn_enqueue(ws, d_q, nq, k, d_idx, d_dist, d_cnt, allow_half, kprime_min, p, allow_i8, d_dk_hint);
+    flat_knn_enqueue(ws, d_q, nq, k, d_idx, d_dist, d_cnt, allow_half, kprime_min, p, allow_i8, d_dk_hint, allow_u8);
     return flat_knn_finish(ws, p);
+}
+
+// The native 8-bit tier of a u8 table (k_gemm_u8.hip; docs/DESIGN_flat.md 4.1af): the shape of the split-bf16 tier's call -- sample,
+// thresholds, ONE filter pass per 128 queries, the k' smallest key pairs, native re-rank, top-k, finish -- over d_rows itself.  The
+// keys are lower bounds of the reference's distances (equal to them for L2Sqr up to dim 258), so the finish certifies by the
+// lower-bound rule with no error term.  Queries that are not integers in [0, 255] get tau = -inf and come back uncertified.
+void Index::flat_u8_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint32_t ksel, uint32_t kprime, uint64_t *d_idx,
+                            float *d_dist, uint64_t *d_cnt, FlatPending &p) {
+    hipStream_t s = ws.stream;
+    const uint32_t d = (uint32_t)dim;
+    const int cosine = dist == 1 ? 1 : 0;
+    const uint64_t gq = gemm_group(), ngroups = (nq + gq - 1) / gq, nq_pad = ngroups * gq;
+    const uint32_t capp = topk_capacity(kprime), capk = topk_capacity(ksel);
+    TauSample sp;
+    sp.s_rank = kprime;
+    mfma_sample_plan(n, kprime, &sp.s_step, &sp.s_rank);
+    sp.set_keys(flat_u8_sample_rows(n, sp.s_step));
+    ws.qsq.reserve(nq_pad * sizeof(float));
+    ws.qfrag_g.reserve(nq_pad * size_t(mfma_dim_pad(d)));
+    ws.qaux.reserve(nq_pad * (2 * sizeof(int32_t) + sizeof(uint32_t)));  // {sum q'^2, sum q'} | eligible
+    ws.misc.reserve(nq_pad * (sizeof(float) + sizeof(uint32_t)));       // tau | hit counters
+    ws.dense.reserve(nq_pad * sp.ld_s * sizeof(float));
+    ws.lists.reserve(std::max<size_t>(nq_pad * sp.nl_s * sp.cap_s, nq_pad * size_t(FLAT_CAND_CAP)) * sizeof(uint64_t));
+    ws.keys_a.reserve(nq_pad * std::max(capp, sp.cap_s) * sizeof(uint64_t));
+    ws.keys_b.reserve(nq_pad * capp * sizeof(uint64_t));
+    ws.keys_c.reserve(nq_pad * capk * sizeof(uint64_t));
+    float *d_tau = ws.misc.as<float>();
+    uint32_t *d_hits = reinterpret_cast<uint32_t *>(d_tau + nq_pad);
+    void *d_qc = ws.qaux.p;
+    uint32_t *d_elig = ws.qaux.as<uint32_t>() + 2 * nq_pad;
+    const uint8_t *X = d_rows.as<uint8_t>();
+    const float *xsq = d_sq.as<float>(), *qsq = ws.qsq.as<float>();
+    VDB_HIP(hipMemsetAsync(ws.qsq.p, 0, nq_pad * sizeof(float), s));  // (the padding queries' norms are read by the Cosine epilogue)
+    launch_row_sqnorm(d_q, nq, d, ws.qsq.as<float>(), s);
+    launch_u8_query_prep(d_q, (uint32_t)nq, (uint32_t)nq_pad, d, ws.qfrag_g.p, d_qc, d_elig, d_hits, s);
+    launch_flat_u8_sample(X, n, d, ws.qfrag_g.p, d_qc, (uint32_t)ngroups, d_rowc_u8.p, xsq, qsq, cosine, sp.s_step, ws.dense.as<float>(), sp.ld_s,
+                          num_cu, s);
+    select_tau(ws, sp, nq_pad, nq, d_tau);
+    launch_u8_tau_close(d_tau, d_elig, (uint32_t)nq_pad, s);
+    uint64_t *d_cand = ws.lists.as<uint64_t>();  // the sample lists are dead now
+    corpus_pass(ws, "flat_u8", double(ngroups) * double(n) * dim, [&] {
+        launch_flat_u8_filter(X, n, d, ws.qfrag_g.p, d_qc, (uint32_t)ngroups, d_rowc_u8.p, xsq, qsq, cosine, d_tau, d_cand, d_hits, FLAT_CAND_CAP, num_cu,
+                              s);
+    });
+    launch_topk_merge_counted(d_cand, FLAT_CAND_CAP, d_hits, (uint32_t)nq, kprime, ws.keys_a.as<uint64_t>(), s);
+    rerank_rows(d, d_q, (uint32_t)nq, cosine ? MET_COSINE : MET_L2_DIRECT, xsq, qsq, ws.keys_a.as<uint64_t>(), ws.keys_b.as<uint64_t>(), kprime, capp, s);
+    launch_topk_merge(ws.keys_b.as<uint64_t>(), 1, capp, (uint32_t)nq, ksel, ws.keys_c.as<uint64_t>(), s);
+    launch_u8_finish(ws.keys_c.as<uint64_t>(), capk, ws.keys_a.as<uint64_t>(), capp, (uint32_t)nq, ksel, (uint32_t)k, kprime, d_tau, d_elig, d_hits,
+                     FLAT_CAND_CAP, id_offset, static_cast<uint8_t *>(ws.pinned(nq)), d_idx, d_dist, d_cnt, s);
+    p.active = true;
+    p.u8 = true;
+    p.kprime = kprime;
+    p.ksel = ksel;
+    p.nq = nq;
+    p.k = k;
+    p.d_q = d_q;
+    p.d_idx = d_idx;
+    p.d_dist = d_dist;
+    p.d_cnt = d_cnt;
 }
 
 // Everything of a Flat call up to (not including) the host's look at the certification flags.  p.active on return: the MFMA
 // pipeline is enqueued on ws.stream and flat_knn_finish must follow (same workspace); otherwise the call took one of the
 // synchronous-by-nature paths (small table, exact scan, k > 1024) and is enqueued in full -- nothing left but the stream sync.
 void Index::flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t *d_idx, float *d_dist,
-                             uint64_t *d_cnt, bool allow_half, uint32_t kprime_min, FlatPending &p, bool allow_i8, const float *d_dk_hint) {
+                             uint64_t *d_cnt, bool allow_half, uint32_t kprime_min, FlatPending &p, bool allow_i8, const float *d_dk_hint,
+                             bool allow_u8) {
     hipStream_t s = ws.stream;
     p = FlatPending{};
     if (nq == 0) return;
@@ -1114,6 +1195,11 @@ void Index::flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint6
     // near-duplicates -- need rows, not precision, and the split-bf16 tier should never certify less than the tier before it
     if (kprime_min > kprime && kprime_min <= 1024 && n > kprime_min) kprime = kprime_min;
     const int cosine = dist == 1 ? 1 : 0;
+    // a u8 table whose shape the native 8-bit pass serves takes it first (never a redo: those arrive with allow_u8 = false)
+    if (allow_u8 && allow_half && kprime_min == 0 && !d_dk_hint && flat_u8_applies(kprime) && ensure_u8c(ws)) {
+        flat_u8_enqueue(ws, d_q, nq, k, ksel, kprime, d_idx, d_dist, d_cnt, p);
+        return;
+    }
     bool mfma = mfma_supported((uint32_t)dim) && kprime <= 1024 && n > kprime &&
                 (flat_mode == 2 || (flat_mode == 0 && n >= 16384));
     if (flat_mode == 1) mfma = false;
@@ -1327,6 +1413,10 @@ uint64_t Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
         half_queries += nq;
         half_redo += redo.size();
     }
+    if (p.u8) {
+        u8_queries += nq;
+        u8_redo += redo.size();
+    }
     if (p.i8 && p.i8_second) {
         i8_second_queries += nq;
         i8_second_redo += redo.size();
@@ -1368,7 +1458,7 @@ uint64_t Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
         }
     }
     if (redo.empty()) return 0;
-    if (!p.half && !p.i8) fallback_count += redo.size();
+    if (!p.half && !p.i8 && !p.u8) fallback_count += redo.size();
     const uint64_t nr = redo.size();
     RedoSet r(redo, p.d_q, dim, k, s);
     DevBuf rqs, rdk;
@@ -1383,7 +1473,9 @@ uint64_t Index::flat_knn_finish(Workspace &ws, FlatPending &p) {
     float *rq = r.rq.as<float>(), *rd = r.rd.as<float>();
     // the second 8-bit attempt: what it still cannot close goes to the fp16 tier from inside that call, and what it hands on is what the
     // auto rule counts (what left the 8-bit tier for good)
-    if (try_second)
+    if (p.u8)  // today's path, with the native u8 tier disallowed: ineligible queries, overflowed lists, a k-th pair above the bound
+        flat_knn_device(ws, rq, nr, k, ri, rd, rc, true, 0, true, nullptr, false);
+    else if (try_second)
         i8_redo += flat_knn_device(ws, rq, nr, k, ri, rd, rc, true, 0, true, rdk.as<float>());
     else if (p.i8)  // next tier: the fp16 pass (or whatever this index has instead), with its own shortlist rules
         flat_knn_device(ws, rq, nr, k, ri, rd, rc, true, 0, false);
@@ -2044,6 +2136,34 @@ void Index::flat_debug_keys(Workspace &ws, const float *d_q, uint64_t nq, int ti
     VDB_REQUIRE(mfma_supported((uint32_t)dim), "debug keys: the dimension has no MFMA shortlist path");
     const int cosine = dist == 1 ? 1 : 0;
     const uint64_t gq = gemm_group(), ngroups = (nq + gq - 1) / gq, nq_pad = ngroups * gq;
+    if (tier == 3) {  // the native pass of a u8 table: keys are lower bounds of the distances themselves (h_qerr = 0; h_dx = E(dim), 0, xsq_max, xsq_min_pos)
+        VDB_REQUIRE(elem_u8 && flat_u8_supported((uint32_t)dim), "debug keys: the index has no native u8 pass");
+        VDB_REQUIRE(ensure_u8c(ws), "debug keys: the row constants could not be allocated");
+        TauSample sp;  // every row's key: step 1
+        sp.set_keys(flat_u8_sample_rows(n, 1));
+        ws.qsq.reserve(nq_pad * sizeof(float));
+        ws.qfrag_g.reserve(nq_pad * size_t(mfma_dim_pad((uint32_t)dim)));
+        ws.qaux.reserve(nq_pad * 3 * sizeof(uint32_t));
+        ws.misc.reserve(nq_pad * sizeof(uint32_t));
+        ws.dense.reserve(nq_pad * sp.ld_s * sizeof(float));
+        VDB_HIP(hipMemsetAsync(ws.qsq.p, 0, nq_pad * sizeof(float), s));
+        launch_row_sqnorm(d_q, nq, (uint32_t)dim, ws.qsq.as<float>(), s);
+        launch_u8_query_prep(d_q, (uint32_t)nq, (uint32_t)nq_pad, (uint32_t)dim, ws.qfrag_g.p, ws.qaux.p, ws.qaux.as<uint32_t>() + 2 * nq_pad,
+                             ws.misc.as<uint32_t>(), s);
+        launch_flat_u8_sample(d_rows.as<uint8_t>(), n, (uint32_t)dim, ws.qfrag_g.p, ws.qaux.p, (uint32_t)ngroups, d_rowc_u8.p, d_sq.as<float>(),
+                              ws.qsq.as<float>(), cosine, 1, ws.dense.as<float>(), sp.ld_s, num_cu, s);
+        VDB_HIP(hipMemcpy2DAsync(h_keys, n * sizeof(float), ws.dense.p, sp.ld_s * sizeof(float), n * sizeof(float), nq, hipMemcpyDeviceToHost, s));
+        if (h_qsq) VDB_HIP(hipMemcpyAsync(h_qsq, ws.qsq.p, nq * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (h_qerr) std::memset(h_qerr, 0, nq * sizeof(float));
+        VDB_SYNC(s);
+        if (h_dx) {
+            h_dx[0] = (float)flat_u8_fold_slack((uint32_t)dim);
+            h_dx[1] = 0.0f;
+            h_dx[2] = xsq_max;
+            h_dx[3] = xsq_min_pos;
+        }
+        return;
+    }
     if (tier == 2) {  // 8-bit operands: keys are lower bounds, D >= key + qoff (h_qerr = qoff; h_dx = l1, l2, |mu|, 0)
         VDB_REQUIRE(!elem_u8 && (dim & 3) == 0 && gemm8_supported((uint32_t)dim), "debug keys: the index has no 8-bit pass");
         VDB_REQUIRE(ensure_i8(ws), "debug keys: the 8-bit mirror could not be allocated");

@@ -238,6 +238,7 @@ struct FlatPending {
     bool active = false;  // the MFMA pipeline is on the stream, its certification flags are still to be read
     bool half = false;
     bool i8 = false;      // first pass on the 8-bit mirror (its uncertified queries go to the fp16 / split-bf16 tiers)
+    bool u8 = false;      // first pass on the stored bytes of a u8 table (k_gemm_u8.hip; its uncertified queries go through the call again without it)
     bool i8_second = false;  // ... its second attempt: thresholds from the first walk's k-th distances (k_redo.hip)
     bool stats = false;      // the exact stage wrote one word of statistics per query behind the flags
     bool refined = false;    // the hit keys were tightened from the fp16 image before the walk
@@ -446,6 +447,18 @@ struct Index {
     bool i8_mirror_applicable() const;  // its clauses about the mirror and the data alone (no k, no auto-off counters: the range search's)
     bool ensure_i8(Workspace &ws);  // false: the mirror could not be allocated (the next tier answers)
     void build_i8(Workspace &ws);
+    // Native 8-bit pass of a u8 table (k_gemm_u8.hip): the operand is d_rows itself; d_rowc_u8 holds {sum x'^2, sum x'} per row (8 B, exact
+    // integers, x' = x - 128).  Built by the first search that wants it, extended after add_rows, dropped by a removal (mirrors_shrunk).
+    DevBuf d_rowc_u8;
+    RowMirror u8c_m{mirror_alloc_failures, {&d_rowc_u8}};
+    int flat_u8_mode = 0;  // "flat_u8": 0 auto (no shape yet: every one measured is slower than the fp16 route, see flat_u8_shape), 1 off, 2 forced
+    std::atomic<uint64_t> u8_queries{0}, u8_redo{0};  // queries the tier took / passed on to today's path
+    bool flat_u8_shape() const;                // its conditions about the table alone (element type, dim, mode)
+    bool flat_u8_applies(uint32_t kprime) const;  // ... and about the call's shortlist and the routing parameters
+    bool ensure_u8c(Workspace &ws);            // false: the constants could not be allocated (today's path answers)
+    // the tier's call: prep, sample, thresholds, filter, shortlist, native re-rank, finish -- enqueued; flat_knn_finish follows
+    void flat_u8_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint32_t ksel, uint32_t kprime, uint64_t *d_idx, float *d_dist,
+                         uint64_t *d_cnt, FlatPending &p);
     // Row-major fp16 image of the rows, same scale and rounding as d_tiled_h (so half_dx_* bound its error as well): the
     // operand of the HNSW walk's certified pre-pass (hnsw.hip, hnsw_half_dots).  Built on the first walk that wants it,
     // extended when rows were added since, rebuilt when the scale changed.
@@ -549,9 +562,10 @@ struct Index {
     // flat_knn_device / flat_knn_finish return the queries the call's 8-bit pass handed on (0: the call did not run that pass)
     uint64_t flat_knn_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t *d_idx, float *d_dist,
                          uint64_t *d_cnt, bool allow_half = true, uint32_t kprime_min = 0, bool allow_i8 = true,
-                         const float *d_dk_hint = nullptr);
+                         const float *d_dk_hint = nullptr, bool allow_u8 = true);
     void flat_knn_enqueue(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt,
-                          bool allow_half, uint32_t kprime_min, FlatPending &p, bool allow_i8 = true, const float *d_dk_hint = nullptr);
+                          bool allow_half, uint32_t kprime_min, FlatPending &p, bool allow_i8 = true, const float *d_dk_hint = nullptr,
+                          bool allow_u8 = true);
     uint64_t flat_knn_finish(Workspace &ws, FlatPending &p);
     // The pieces of an 8-bit filter pass that Flat k-NN, the range search, the filtered search and flat_debug_keys share (index.hip).  They
     // take data -- a chunk of queries, the row constants to filter by, an expected hit count -- and never which caller they serve.

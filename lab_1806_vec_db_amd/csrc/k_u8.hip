@@ -1,9 +1,10 @@
 // k_u8.hip -- VecSet<u8> (scalar.rs:117-119): rows stored at ONE byte per element in HBM.
-// DistanceScalar for u8 converts every element with `as f32` and then runs the f32 folds (distance/mod.rs:79-95), so a
-// u8 corpus needs no arithmetic of its own -- only loads that widen on the fly.  Search-time kernels that read the
-// row-major rows (exact scan, re-rank of a shortlist) have the native-u8 variants below; build-time kernels (row norms,
-// the MFMA mirrors) run on widened chunks (k_widen_u8) -- both mirrors hold a u8 value exactly (8 significant bits fit
-// bf16's hi plane and fp16), so the shortlist pass of a u8 index has zero operand rounding error.
+// DistanceScalar for u8 converts every element with `as f32` and then runs the f32 folds (distance/mod.rs:79-95), so the
+// EXACT distances of a u8 corpus need no arithmetic of their own -- only loads that widen on the fly: the native-u8 exact
+// scan and shortlist re-rank below.  The shortlist pass does have arithmetic of its own: k_gemm_u8.hip runs the int8 matrix
+// instruction on the stored bytes and certifies its integer keys against this fold.  Where that pass does not apply, the
+// build-time kernels (row norms, the MFMA mirrors) run on widened chunks (k_widen_u8) -- both mirrors hold a u8 value exactly
+// (8 significant bits fit bf16's hi plane and fp16), so that shortlist pass has zero operand rounding error.
 #include "common.hpp"
 #include "kernels.hpp"
 

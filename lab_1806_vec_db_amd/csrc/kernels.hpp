@@ -159,6 +159,28 @@ void launch_scan_exact_u8(const uint8_t *X, uint64_t n, uint32_t dim, const floa
 void launch_rerank_u8(const uint8_t *X, uint32_t dim, const float *Q, uint32_t nq, int metric, const float *xsq, const float *qsq,
                       const uint64_t *cand, uint64_t *out, uint32_t ncand, uint32_t ldc, hipStream_t s);
 
+// ---- k_gemm_u8.hip: the Flat shortlist pass on the stored bytes of a u8 table (int8 MFMA, exact integer sums, lower-bound keys) ----
+bool flat_u8_supported(uint32_t dim);      // dim % 16 == 0, dim <= 1024
+int32_t flat_u8_fold_slack(uint32_t dim);  // E(dim): what the reference's f32 fold can lose or gain (0 for dim <= 258)
+// rowc[r] = {sum x'^2 (u32), sum x' (i32)}, x' = x - 128, for rows [r0, r1)
+void launch_u8_row_consts(const uint8_t *X, uint64_t r0, uint64_t r1, uint32_t dim, void *rowc, hipStream_t s);
+// img: nq_pad x round_up(dim, 64) int8 in fragment order; qc [nq_pad] {sum q'^2, sum q'}; elig [nq_pad] 1 = every element an integer in
+// [0, 255]; hits [nq_pad] zeroed.  nq_pad = whole groups of 128
+void launch_u8_query_prep(const float *Q, uint32_t nq, uint32_t nq_pad, uint32_t dim, void *img, void *qc, uint32_t *elig, uint32_t *hits,
+                          hipStream_t s);
+void launch_u8_tau_close(float *tau, const uint32_t *elig, uint32_t nq_pad, hipStream_t s);  // tau = -inf where not eligible
+// hits (key <= tau, row < n) -> cand[q][0 .. cap), cnt[q] counts every hit; xsq / qsq: the stored norms (read when cosine != 0)
+void launch_flat_u8_filter(const uint8_t *X, uint64_t n, uint32_t dim, const void *img, const void *qc, uint32_t ngroups, const void *rowc,
+                           const float *xsq, const float *qsq, int cosine, const float *tau, uint64_t *cand, uint32_t *cnt, uint32_t cap,
+                           int num_cu, hipStream_t s);
+uint64_t flat_u8_sample_rows(uint64_t n, uint32_t unit_step);
+void launch_flat_u8_sample(const uint8_t *X, uint64_t n, uint32_t dim, const void *img, const void *qc, uint32_t ngroups, const void *rowc,
+                           const float *xsq, const float *qsq, int cosine, uint32_t unit_step, float *out, uint64_t ld, int num_cu, hipStream_t s);
+// launch_flat_finish for that pass: certified when the ksel-th exact pair is at or below the k'-th key pair (the threshold, for a list shorter than k')
+void launch_u8_finish(const uint64_t *exact_sorted, uint32_t lde, const uint64_t *approx_sorted, uint32_t lda, uint32_t nq, uint32_t ksel,
+                      uint32_t kstride, uint32_t kprime, const float *tau, const uint32_t *elig, const uint32_t *cnt, uint32_t cap,
+                      uint64_t id_offset, uint8_t *flags, uint64_t *out_idx, float *out_dist, uint64_t *out_count, hipStream_t s);
+
 // ---- k_probe.hip ---------------------------------------------------------------------------
 // attainable HBM read bandwidth in GB/s: pure streaming read of `bytes`, `iters` timed passes, best of two patterns
 double stream_probe(int device, uint64_t bytes, int iters);
