@@ -662,6 +662,57 @@ int vdb_flat_knn_grouped_device(vdb_index *idx, const void *d_queries, uint64_t 
                                 void *d_out_dist, void *d_out_count, void *stream);
 int vdb_group_cap_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint64_t k,
                          uint32_t column, uint64_t group_size, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream);
+/* ---- k-NN label vote (classification): which values of one label column the k nearest rows carry, and how strongly -------------------
+ * "Which tenant / topic / cluster does this vector belong to?": auto-tagging, routing, filling a missing metadata key from neighbours,
+ * assigning a new vector to a cluster that vdb_flat_dbscan or a duplicate grouping wrote into a label column.  The answer is a function
+ * of the table, the column, the queries, k, the masks and the mode alone.
+ *   For one query let L be the exact list vdb_flat_knn (vdb_flat_knn_filtered_multi under masks) returns for k: sorted by (distance,
+ *   id), length cnt <= k.  A hit votes iff its row's code in `column` is not VDB_LABEL_NONE (a column never written: nobody votes).
+ *   Weight of a vote: VDB_VOTE_UNIFORM 1.0f; VDB_VOTE_INVERSE 1.0f / (d + eps) in f32, IEEE division, eps > 0 an argument; a NaN
+ *   distance weighs 0.0f (and is still counted), +inf gives 0.0f by the arithmetic.
+ *   Per value: score = the STRICT LEFT FOLD in f32 of its voters' weights in list order from +0.0f (one rounding per addition, no
+ *   other order, no float atomic); votes = the number of voters; first = the list position of its first voter.
+ *   Values are ranked by score descending, then first ascending -- a total order: on a tie the value with the nearer row wins.
+ *   Outputs per query: out_code (u32) / out_score (f32) / out_votes (u32) [nq][c], the top min(c, distinct values) -- that number goes
+ *   to out_count[q] --, the rest of the row VDB_LABEL_NONE, 0.0f, 0; out_voters[q] = the voting hits of the query, what a share or a
+ *   confidence is normalised by.
+ *   Limits: 1 <= k <= 4096, 1 <= c <= k: a longer list is refused, never truncated.
+ *   How: the ONE list call per sub-chunk of queries, then ONE k_vote_lists launch (csrc/k_vote.hip), a wave per query: tiles of 64
+ *   positions, the labels gathered one tile ahead; an open-addressing table code -> {score, votes, first} claimed by compare-and-swap
+ *   on the code word, 20 B a slot with the sort key, in LDS up to 2048 slots (k <= 1024; 40 KiB, four queries per CU), past that the
+ *   same code on a slice of device scratch.  Within a tile the wave walks its distinct codes by ballot; the lowest lane of every value
+ *   then adds the tile's matching weights to its slot in ascending lane order -- one writer per slot per tile, so the fold is the list
+ *   order.  A bitonic sort of (inverted order image of the score, first) keys ranks the values.
+ * vdb_vote_plan: host utility, works without a GPU: *out_code = 0 when the call is accepted, else the first of 1 k outside 1 .. 4096,
+ *   2 c outside 1 .. k, 3 unknown mode, 4 eps not > 0 or not finite with VDB_VOTE_INVERSE, 5 column >= VDB_LABEL_COLUMNS.  Accepted:
+ *   *out_table_lg = log2 of the slots (the power of two at or above 2 k, at least 2^7), *out_in_lds, *out_scratch_bytes per query (0 in
+ *   LDS), *out_sub_chunk = queries per list call out of nq when lists and scratch may take `budget` bytes (0: 256 MiB).  Any output
+ *   pointer but out_code may be NULL.
+ * vdb_flat_knn_vote_device: queries and outputs on the index's GPU, at most 32768 queries, returns synchronised.
+ * vdb_vote_lists_device: the vote alone over caller-supplied lists -- d_ids (u64, id_offset included) / d_dists (f32) [nq][ld] in ANY
+ *   order, walked as given, and d_counts [nq] (u64; entries past min(count, ld) are not read); ld takes k's place in the limits.  Every
+ *   counted id is checked on the device first (one flag read back): an id that is no row of the index is VDB_ERR_INVALID with the
+ *   outputs and counters untouched; nothing is gathered out of bounds.
+ * Refused before anything is computed or written, counters unchanged (VDB_ERR_INVALID): a dim mismatch, everything vdb_vote_plan
+ * reports, a NULL output, and with masks a VecSet<u8> index and every mask / mask_of error of vdb_flat_knn_filtered_multi (a stale mask:
+ * VDB_ERR_STATE).  Without masks a VecSet<u8> index is served.  nq == 0 succeeds and writes nothing.  Read-side and re-entrant.
+ * vdb_get_stat "flat_vote_queries" (queries voted for, all three forms), "flat_vote_scratch" (of those, the ones whose table left
+ * LDS); the list call under the search forms advances its own counters; vdb_prof_get "vote_lists" times k_vote_lists.
+ * Not covered: sharded and replica contexts, lists from PQ / HNSW / IVF beyond feeding them to the list form, votes over more than one
+ * column, regression (a weighted mean of a numeric column). */
+#define VDB_VOTE_UNIFORM 0
+#define VDB_VOTE_INVERSE 1
+int vdb_vote_plan(uint64_t k, uint64_t c, int mode, float eps, uint32_t column, uint64_t nq, uint64_t budget, int *out_code,
+                  uint32_t *out_table_lg, int *out_in_lds, uint64_t *out_scratch_bytes, uint64_t *out_sub_chunk);
+int vdb_flat_knn_vote(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint32_t column, uint64_t c, int mode,
+                      float eps, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint32_t *out_code, float *out_score,
+                      uint32_t *out_votes, uint64_t *out_count, uint64_t *out_voters);
+int vdb_flat_knn_vote_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, uint32_t column, uint64_t c,
+                             int mode, float eps, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, void *d_out_code,
+                             void *d_out_score, void *d_out_votes, void *d_out_count, void *d_out_voters, void *stream);
+int vdb_vote_lists_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld,
+                          uint32_t column, uint64_t c, int mode, float eps, void *d_out_code, void *d_out_score, void *d_out_votes,
+                          void *d_out_count, void *d_out_voters, void *stream);
 /* ---- diversified Flat k-NN: maximal marginal relevance (MMR) over the fetch_k nearest allowed rows -------------------------------------
  * "The k results that are close to the query and not near-copies of each other": the max_marginal_relevance_search(query, k, fetch_k,
  * lambda_mult) of the common retrieval stacks, with the library's bit-exact distances and nothing dragged to the host.  Grouping needs

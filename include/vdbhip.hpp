@@ -311,6 +311,32 @@ public:
             for (uint64_t j = 0; j < cnt[q]; j++) out[q].push_back({idx[q * k + j], d[q * k + j]});
         return out;
     }
+    // k-NN label vote (vdb_flat_knn_vote): per query the top c values of label column `column` among its k nearest rows, best first, as
+    // {code, score, votes}; mode VDB_VOTE_UNIFORM or VDB_VOTE_INVERSE (weight 1 / (d + eps)).  voters (may be null): per query the
+    // voting hits.  masks empty: over all rows; otherwise query q under *masks[mask_of[q]]
+    struct Vote {
+        uint32_t code;
+        float score;
+        uint32_t votes;
+    };
+    std::vector<std::vector<Vote>> knn_vote_batch(const float *queries, uint64_t nq, uint64_t k, uint32_t column, uint64_t c = 1,
+                                                  int mode = VDB_VOTE_UNIFORM, float eps = 1e-6f, const std::vector<const Mask *> &masks = {},
+                                                  const std::vector<uint32_t> &mask_of = {}, std::vector<uint64_t> *voters = nullptr) const {
+        if (!masks.empty() && mask_of.size() != nq) throw std::runtime_error("mask_of: one entry per query is needed");
+        std::vector<const vdb_mask *> hs;
+        for (const Mask *m : masks) hs.push_back(m->handle());
+        const uint64_t cc = c ? c : 1;
+        std::vector<uint32_t> code(nq * cc), votes(nq * cc);
+        std::vector<float> score(nq * cc);
+        std::vector<uint64_t> cnt(nq), nv(nq);
+        check(vdb_flat_knn_vote(h_, queries, nq, dim_, k, column, c, mode, eps, hs.data(), hs.size(), mask_of.data(), code.data(), score.data(),
+                                votes.data(), cnt.data(), nv.data()));
+        std::vector<std::vector<Vote>> out(nq);
+        for (uint64_t q = 0; q < nq; q++)
+            for (uint64_t j = 0; j < cnt[q]; j++) out[q].push_back({code[q * cc + j], score[q * cc + j], votes[q * cc + j]});
+        if (voters) *voters = nv;
+        return out;
+    }
     // diversified k-NN, maximal marginal relevance (vdb_flat_knn_mmr): per query, from the first min(fetch_k, allowed rows) pairs of
     // knn_batch, the nearest and then greedily the pair with the smallest lambda * d(query, row) - (1 - lambda) * min over the selected rows
     // of d(row, selected); the pairs come in SELECTION order.  masks empty: over all rows; otherwise query q under *masks[mask_of[q]]

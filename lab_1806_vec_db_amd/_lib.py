@@ -95,6 +95,10 @@ SIGNATURES = {
     "vdb_flat_knn_grouped": [vp, f32p, u64, u64, u64, C.c_uint32, u64, C.POINTER(vp), u64, u32p, u64p, f32p, u64p],
     "vdb_flat_knn_grouped_device": [vp, vp, u64, u64, u64, C.c_uint32, u64, C.POINTER(vp), u64, u32p, vp, vp, vp, vp],
     "vdb_group_cap_device": [vp, vp, vp, vp, u64, u64, u64, C.c_uint32, u64, vp, vp, vp, vp],
+    "vdb_vote_plan": [u64, u64, C.c_int, C.c_float, C.c_uint32, u64, u64, intp, u32p, intp, u64p, u64p],
+    "vdb_flat_knn_vote": [vp, f32p, u64, u64, u64, C.c_uint32, u64, C.c_int, C.c_float, C.POINTER(vp), u64, u32p, u32p, f32p, u32p, u64p, u64p],
+    "vdb_flat_knn_vote_device": [vp, vp, u64, u64, u64, C.c_uint32, u64, C.c_int, C.c_float, C.POINTER(vp), u64, u32p, vp, vp, vp, vp, vp, vp],
+    "vdb_vote_lists_device": [vp, vp, vp, vp, u64, u64, C.c_uint32, u64, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp],
     "vdb_flat_knn_mmr": [vp, f32p, u64, u64, u64, u64, C.c_float, C.POINTER(vp), u64, u32p, u64p, f32p, u64p],
     "vdb_flat_knn_mmr_device": [vp, vp, u64, u64, u64, u64, C.c_float, C.POINTER(vp), u64, u32p, vp, vp, vp, vp],
     "vdb_mmr_select_device": [vp, vp, vp, vp, u64, u64, u64, C.c_float, vp, vp, vp, vp],

@@ -1368,6 +1368,130 @@ int vdb_group_cap_device(vdb_index *idx, const void *d_ids, const void *d_dists,
     VDB_API_END
 }
 
+// ---- k-NN label vote: the values of a label column among the k nearest allowed rows (Index::flat_knn_vote_device, k_vote.hip) -----------
+// everything that can be refused is refused here, before anything is computed or written; -> the masks as RowMask pointers (none: unfiltered)
+static std::vector<const RowMask *> vote_check(const Index &ix, uint64_t nq, uint64_t dim, uint64_t k, uint32_t column, uint64_t c, int mode, float eps,
+                                               const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, const void *queries,
+                                               const void *out_code, const void *out_score, const void *out_votes, const void *out_count,
+                                               const void *out_voters) {
+    VDB_REQUIRE(dim == ix.dim, "query dimension mismatch: index dim " + std::to_string(ix.dim) + ", got " + std::to_string(dim));
+    const char *bad = vote_bad_text(vote_check_args(k, c, mode, eps, column));
+    VDB_REQUIRE(bad == nullptr, bad);
+    VDB_REQUIRE(nq == 0 || (queries && out_code && out_score && out_votes && out_count && out_voters), "null argument");
+    if (n_masks == 0) return {};  // (either element type: the unfiltered list call serves both)
+    require_f32_rows(ix);
+    return filtered_multi_check(ix, nq, masks, n_masks, mask_of);
+}
+
+// the outputs of nb queries of the host form: ONE device block [codes | scores | votes | counts | voters] in ws.out_idx
+struct VoteBlock {
+    size_t off_s, off_v, off_c, off_n, bytes;
+    char *d;
+    VoteBlock(Workspace &ws, uint64_t nb, uint64_t c) {
+        off_s = nb * c * sizeof(uint32_t);
+        off_v = 2 * off_s;
+        off_c = (3 * off_s + 7) & ~size_t(7);
+        off_n = off_c + nb * sizeof(uint64_t);
+        bytes = off_n + nb * sizeof(uint64_t);
+        ws.out_idx.reserve(bytes);
+        d = ws.out_idx.as<char>();
+    }
+    uint32_t *code() const { return reinterpret_cast<uint32_t *>(d); }
+    float *score() const { return reinterpret_cast<float *>(d + off_s); }
+    uint32_t *votes() const { return reinterpret_cast<uint32_t *>(d + off_v); }
+    uint64_t *cnt() const { return reinterpret_cast<uint64_t *>(d + off_c); }
+    uint64_t *voters() const { return reinterpret_cast<uint64_t *>(d + off_n); }
+};
+
+int vdb_vote_plan(uint64_t k, uint64_t c, int mode, float eps, uint32_t column, uint64_t nq, uint64_t budget, int *out_code, uint32_t *out_table_lg,
+                  int *out_in_lds, uint64_t *out_scratch_bytes, uint64_t *out_sub_chunk) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(out_code, "vote_plan: null out_code");
+    *out_code = vote_check_args(k, c, mode, eps, column);
+    if (*out_code != VOTE_OK) return VDB_OK;
+    const uint32_t lg = vote_table_lg(k);
+    if (out_table_lg) *out_table_lg = lg;
+    if (out_in_lds) *out_in_lds = vote_in_lds(lg) ? 1 : 0;
+    if (out_scratch_bytes) *out_scratch_bytes = vote_scratch_bytes(1, lg);
+    if (out_sub_chunk) *out_sub_chunk = vote_sub_chunk(nq, k, true, budget ? budget : LIST_BUDGET);
+    VDB_API_END
+}
+
+int vdb_flat_knn_vote(vdb_index *idx, const float *queries, uint64_t nq, uint64_t dim, uint64_t k, uint32_t column, uint64_t c, int mode, float eps,
+                      const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint32_t *out_code, float *out_score,
+                      uint32_t *out_votes, uint64_t *out_count, uint64_t *out_voters) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const std::vector<const RowMask *> rm =
+        vote_check(ix, nq, dim, k, column, c, mode, eps, masks, n_masks, mask_of, queries, out_code, out_score, out_votes, out_count, out_voters);
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    hipStream_t s = ws->stream;
+    // blocks of queries whose outputs pass through the pinned block in one copy
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(16384, OutBlock::STAGE_MAX / (c * 12 + 16)));
+    run_synced(ix, *ws, [&] {
+        for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
+            const uint64_t nb = std::min(chunk, nq - q0);
+            const size_t qb = nb * ix.dim * sizeof(float);
+            ws->q.reserve(qb);
+            const VoteBlock out(*ws, nb, c);
+            VDB_HIP(hipMemcpyAsync(ws->q.p, queries + q0 * ix.dim, qb, hipMemcpyHostToDevice, s));
+            ix.flat_knn_vote_device(*ws, ws->q.as<float>(), nb, k, column, c, mode, eps, rm.data(), n_masks, n_masks ? mask_of + q0 : nullptr, out.code(),
+                                    out.score(), out.votes(), out.cnt(), out.voters());
+            // (the search has synchronised after its own use of the pinned block: it is free again)
+            char *h = static_cast<char *>(ws->pinned(out.bytes));
+            VDB_HIP(hipMemcpyAsync(h, out.d, out.bytes, hipMemcpyDeviceToHost, s));
+            VDB_SYNC(s);
+            std::memcpy(out_code + q0 * c, h, nb * c * sizeof(uint32_t));
+            std::memcpy(out_score + q0 * c, h + out.off_s, nb * c * sizeof(float));
+            std::memcpy(out_votes + q0 * c, h + out.off_v, nb * c * sizeof(uint32_t));
+            std::memcpy(out_count + q0, h + out.off_c, nb * sizeof(uint64_t));
+            std::memcpy(out_voters + q0, h + out.off_n, nb * sizeof(uint64_t));
+        }
+    });
+    VDB_API_END
+}
+
+int vdb_flat_knn_vote_device(vdb_index *idx, const void *d_queries, uint64_t nq, uint64_t dim, uint64_t k, uint32_t column, uint64_t c, int mode,
+                             float eps, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, void *d_out_code, void *d_out_score,
+                             void *d_out_votes, void *d_out_count, void *d_out_voters, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const std::vector<const RowMask *> rm = vote_check(ix, nq, dim, k, column, c, mode, eps, masks, n_masks, mask_of, d_queries, d_out_code, d_out_score,
+                                                       d_out_votes, d_out_count, d_out_voters);
+    VDB_REQUIRE(nq <= 32768, "at most 32768 queries per device call");
+    if (nq == 0) return VDB_OK;
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries on the caller's stream
+    run_synced(ix, *ws, [&] {
+        ix.flat_knn_vote_device(*ws, static_cast<const float *>(d_queries), nq, k, column, c, mode, eps, rm.data(), n_masks, mask_of,
+                                static_cast<uint32_t *>(d_out_code), static_cast<float *>(d_out_score), static_cast<uint32_t *>(d_out_votes),
+                                static_cast<uint64_t *>(d_out_count), static_cast<uint64_t *>(d_out_voters));
+    });
+    VDB_API_END
+}
+
+int vdb_vote_lists_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, uint64_t nq, uint64_t ld, uint32_t column,
+                          uint64_t c, int mode, float eps, void *d_out_code, void *d_out_score, void *d_out_votes, void *d_out_count,
+                          void *d_out_voters, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const char *bad = vote_bad_text(vote_check_args(ld, c, mode, eps, column));
+    VDB_REQUIRE(bad == nullptr, bad);
+    VDB_REQUIRE(nq == 0 || (d_ids && d_dists && d_counts && d_out_code && d_out_score && d_out_votes && d_out_count && d_out_voters), "null argument");
+    list_form_run(ix, stream, nq, [&](Workspace &ws) {
+        ix.vote_lists_device(ws, static_cast<const uint64_t *>(d_ids), static_cast<const float *>(d_dists), static_cast<const uint64_t *>(d_counts), nq, ld,
+                             column, c, mode, eps, static_cast<uint32_t *>(d_out_code), static_cast<float *>(d_out_score),
+                             static_cast<uint32_t *>(d_out_votes), static_cast<uint64_t *>(d_out_count), static_cast<uint64_t *>(d_out_voters));
+    });
+    VDB_API_END
+}
+
 // ---- diversified k-NN: maximal marginal relevance over the fetch_k nearest allowed rows (Index::flat_knn_mmr_device, k_mmr.hip) ---------
 // everything that can be refused is refused here, before anything is computed or written; -> the masks as RowMask pointers (none: unfiltered)
 static std::vector<const RowMask *> mmr_check(const Index &ix, uint64_t nq, uint64_t k, uint64_t fetch_k, float lambda, const vdb_mask *const *masks,
@@ -2252,6 +2376,10 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.grouped_rounds.load();
     else if (n == "flat_grouped_exhausted_queries")
         *out = idx->ix.grouped_exhausted.load();
+    else if (n == "flat_vote_queries")  // k-NN label vote: queries voted for (both forms) | of those, the ones whose table left LDS
+        *out = idx->ix.vote_queries.load();
+    else if (n == "flat_vote_scratch")
+        *out = idx->ix.vote_scratch.load();
     else if (n == "flat_mmr_calls")  // diversified k-NN: calls | queries
         *out = idx->ix.mmr_calls.load();
     else if (n == "flat_mmr_queries")

@@ -471,4 +471,59 @@ void Index::fuse_groups_device(Workspace &ws, const uint64_t *d_ids, const float
     end_call(*this, ws);
 }
 
+// ---- Flat: k-NN label vote, the values of a label column among the k nearest allowed rows (k_vote.hip, vote_plan.hpp; 4.1ag) -------------
+// The voters of a query are a PREFIX of its order of fixed length, so one round is the whole call: the exact sorted list of
+// kp = min(k, longest allowed set) rows per query, then the vote.  The kernel's scratch lives in grp_table, the flag of the list form's id
+// check in grp_aux -- none of which the list calls touch.  The element type of the rows plays no part without masks.
+void Index::flat_knn_vote_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint32_t column, uint64_t c, int mode, float eps,
+                                 const RowMask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint32_t *d_code, float *d_score,
+                                 uint32_t *d_votes, uint64_t *d_cnt, uint64_t *d_voters) {
+    hipStream_t s = ws.stream;
+    VDB_REQUIRE(vote_check_args(k, c, mode, eps, column) == VOTE_OK, "vote: bad k, c, mode, eps or column");
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 31), "flat knn: too many queries");
+    const Allowed all{masks, n_masks, mask_of};
+    const uint64_t kp = list_len(k, max_allowed(*this, all, nq));
+    const uint32_t lg = vote_table_lg(kp);
+    const uint64_t sub = vote_sub_chunk(nq, kp);
+    const Lists l = reserve_lists(*this, ws, sub, kp, n_masks);
+    if (const size_t tb = vote_scratch_bytes(sub, lg)) ws.grp_table.reserve(tb);
+    const uint32_t *col = label_col(column);
+    sub_chunk_loop(
+        *this, ws, nq, sub, nullptr, "vote_lists", [&](const Chunk &ch) { fetch_lists(*this, ws, d_q + ch.c0 * dim, ch.nb, all, ch.c0, l); },
+        [&](const Chunk &ch) { return double(ch.nb) * kp * (LIST_PAIR_BYTES + sizeof(uint32_t)); },
+        [&](const Chunk &ch) {
+            launch_vote_lists(l.ids, l.dist, l.cnt, ch.nb, kp, col, n, id_offset, mode, eps, (uint32_t)c, ws.grp_table.as<uint32_t>(), d_code + ch.c0 * c,
+                              d_score + ch.c0 * c, d_votes + ch.c0 * c, d_cnt + ch.c0, d_voters + ch.c0, s);
+        });
+    end_call(*this, ws);
+    vote_queries += nq;
+    if (!vote_in_lds(lg)) vote_scratch += nq;
+}
+
+void Index::vote_lists_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld,
+                              uint32_t column, uint64_t c, int mode, float eps, uint32_t *d_code, float *d_score, uint32_t *d_votes, uint64_t *d_cnt,
+                              uint64_t *d_voters) {
+    hipStream_t s = ws.stream;
+    VDB_REQUIRE(vote_check_args(ld, c, mode, eps, column) == VOTE_OK, "vote lists: bad ld, c, mode, eps or column");
+    if (nq == 0) return;
+    VDB_REQUIRE(nq < (1ull << 31), "vote lists: too many queries");
+    const uint32_t lg = vote_table_lg(ld);
+    const uint64_t sub = vote_sub_chunk(nq, ld, false);
+    ws.grp_aux.reserve(sizeof(uint32_t));
+    if (const size_t tb = vote_scratch_bytes(sub, lg)) ws.grp_table.reserve(tb);
+    ids_ok(ws, s, ws.grp_aux.as<uint32_t>(), "vote lists: a list holds an id that is no row of this index (id - id_offset must be below len)",
+           [&](uint32_t *d_flag) { launch_list_check(d_ids, d_counts, nq, ld, n, id_offset, d_flag, s); });
+    const uint32_t *col = label_col(column);
+    sub_chunk_loop(
+        *this, ws, nq, sub, nullptr, "vote_lists", no_fetch, [&](const Chunk &ch) { return double(ch.nb) * ld * (LIST_PAIR_BYTES + sizeof(uint32_t)); },
+        [&](const Chunk &ch) {
+            launch_vote_lists(d_ids + ch.c0 * ld, d_dists + ch.c0 * ld, d_counts + ch.c0, ch.nb, ld, col, n, id_offset, mode, eps, (uint32_t)c,
+                              ws.grp_table.as<uint32_t>(), d_code + ch.c0 * c, d_score + ch.c0 * c, d_votes + ch.c0 * c, d_cnt + ch.c0, d_voters + ch.c0, s);
+        });
+    end_call(*this, ws);
+    vote_queries += nq;
+    if (!vote_in_lds(lg)) vote_scratch += nq;
+}
+
 }  // namespace vdb

@@ -775,6 +775,22 @@ struct Index {
                             uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, uint32_t column, uint64_t trunc_len, uint64_t *d_idx,
                             float *d_dist, uint64_t *d_cnt, uint8_t *d_exact);
     std::atomic<uint64_t> fused_groups_calls{0}, fused_groups_queries{0}, fused_groups_lists{0};
+    // k-NN label vote (k_vote.hip, vote_plan.hpp -- which states the limits; docs/DESIGN_flat.md 4.1ag): per query the values of label column
+    // `column` among the first min(k, m) rows of FlatIndex::knn's order over its allowed rows, ranked by (score descending, first voter
+    // ascending), the top c of them.  ONE round: the exact sorted list of min(k, longest allowed set) rows per query -- flat_knn_device
+    // without masks (either element type), flat_knn_masked_multi_device over the call's masks, whose counters advance as for those calls --
+    // then k_vote_lists, in sub-chunks of queries (vote_sub_chunk).  Outputs on the device: d_code / d_score / d_votes [nq][c], d_cnt
+    // [nq] values written, d_voters [nq] voting hits.  n_masks == 0: unfiltered (masks / mask_of not read).  The caller has checked the
+    // arguments (vote_check_args), the masks and mask_of; returns synchronised.
+    void flat_knn_vote_device(Workspace &ws, const float *d_q, uint64_t nq, uint64_t k, uint32_t column, uint64_t c, int mode, float eps,
+                              const RowMask *const *masks, uint64_t n_masks, const uint32_t *mask_of, uint32_t *d_code, float *d_score,
+                              uint32_t *d_votes, uint64_t *d_cnt, uint64_t *d_voters);
+    // k_vote_lists alone over caller-supplied lists [nq][ld] (device), walked as given: every id of the counted ranges is checked on the
+    // device first (one flag read back; a bad one throws before an output or a counter is written).  Returns synchronised.
+    void vote_lists_device(Workspace &ws, const uint64_t *d_ids, const float *d_dists, const uint64_t *d_counts, uint64_t nq, uint64_t ld,
+                           uint32_t column, uint64_t c, int mode, float eps, uint32_t *d_code, float *d_score, uint32_t *d_votes, uint64_t *d_cnt,
+                           uint64_t *d_voters);
+    std::atomic<uint64_t> vote_queries{0}, vote_scratch{0};  // queries voted for (both forms) / of those, the ones whose table left LDS
     // Near-duplicate grouping (flat_dups.hip, k_components.hip, dup_plan.hpp; docs/DESIGN_flat.md 4.1ab): the connected components of the
     // allowed rows (mask == nullptr: all rows) under the edges {i, j}, j != i on the list flat_range_device returns for query = row i at
     // `radius` under `limit` and the mask -- SINGLE LINKAGE at the radius.  d_group [n] u64 on the device: the lowest row of row i's

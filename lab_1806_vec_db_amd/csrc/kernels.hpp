@@ -17,6 +17,7 @@
 #include "mask_partition.hpp"
 #include "mask_sets.hpp"
 #include "mmr_plan.hpp"
+#include "vote_plan.hpp"
 
 namespace vdb {
 
@@ -388,6 +389,7 @@ void launch_mask_dense_nan(float *dist, uint64_t ld, uint64_t n, uint32_t nq, co
 constexpr uint32_t LABEL_COLUMNS = 16;       // VDB_LABEL_COLUMNS
 constexpr uint32_t LABEL_NONE = 0xFFFFFFFFu;  // VDB_LABEL_NONE: a row without a value in that column
 constexpr uint32_t MASK_MAX_TERMS = 8;        // VDB_MASK_MAX_TERMS
+static_assert(VOTE_LABEL_COLUMNS == LABEL_COLUMNS, "vote_plan.hpp and kernels.hpp agree");
 static_assert(SETS_LABEL_COLUMNS == LABEL_COLUMNS && SETS_LABEL_NONE == LABEL_NONE && SETS_MAX_TERMS == MASK_MAX_TERMS, "mask_sets.hpp and kernels.hpp agree");
 struct LabelCols {  // the allocated columns of an index (kernel argument, by value)
     uint32_t *col[LABEL_COLUMNS];
@@ -589,6 +591,17 @@ void launch_fuse_groups(const uint64_t *ids, const float *dists, const uint64_t 
                         uint64_t list_base, const float *weights, const uint32_t *labels, uint64_t n, int mode, float c, uint64_t id_offset,
                         uint64_t trunc_len, uint32_t k, uint32_t lg, uint32_t *scratch, uint64_t *out_idx, float *out_dist, uint64_t *out_cnt,
                         uint8_t *out_exact, hipStream_t s);
+// The label vote of the k-NN classifier (k_vote.hip, vote_plan.hpp): query b's list ids / dists [b][0 .. min(counts[b], ld)), 1 <= ld <=
+// VOTE_MAX_K, walked in the order given.  An entry votes iff its row carries a value in `labels` (u32 per LOCAL row = id - id_offset;
+// nullptr: a column never written; an id that is no row of the index is not gathered and does not vote) with the weight 1.0f
+// (VOTE_UNIFORM) or 1.0f / (d + eps), 0.0f for a NaN d (VOTE_INVERSE).  Per value: score = the strict left fold in f32 of its voters'
+// weights in list order from +0.0f, votes = their number, first = the position of the first.  The first min(c, values) by (score
+// descending, first ascending) go to out_code / out_score / out_votes [b][c] with LABEL_NONE, 0.0f, 0 behind them, their number to
+// out_cnt[b], the number of voting entries to out_voters[b].  scratch: vote_scratch_bytes(nq, vote_table_lg(ld)) bytes, unused while
+// the table fits LDS.
+void launch_vote_lists(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nq, uint64_t ld, const uint32_t *labels, uint64_t n,
+                       uint64_t id_offset, int mode, float eps, uint32_t c, uint32_t *scratch, uint32_t *out_code, float *out_score,
+                       uint32_t *out_votes, uint64_t *out_cnt, uint64_t *out_voters, hipStream_t s);
 // ---- k_pq.hip: product quantisation -- lookup tables, the ADC scans and their exact stages, encoder, re-sort, shard merge ----------
 // The argument structs are filled by the search drivers (pq.hip); every launcher works out its own grid and dynamic LDS bytes.  Where a
 // driver has to ASK whether a scan's LDS image fits before it chooses that scan, the same *_lds_bytes() the launcher uses answers.

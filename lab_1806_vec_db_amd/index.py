@@ -87,6 +87,8 @@ MASK_OP_AND, MASK_OP_OR = 0, 1  # VDB_MASK_OP_AND / VDB_MASK_OP_OR
 LIKE_MAX_EXAMPLES = 1024   # examples of one query of flat_knn_like, positives plus negatives (LIKE_MAX_EXAMPLES of csrc/like_plan.hpp)
 FUSE_MODES = {"rrf": 0, "min": 1}  # VDB_FUSE_RRF / VDB_FUSE_MIN
 FUSE_GROUP_MODES = {"rrf": 0, "min": 1, "sum": 2}  # ... and VDB_FUSE_SUM, which only the document-level fusion has
+VOTE_MODES = {"uniform": 0, "inverse": 1}  # VDB_VOTE_UNIFORM / VDB_VOTE_INVERSE
+VOTE_MAX_K = 4096          # longest list of flat_knn_vote / vote_lists_device (VOTE_MAX_K of csrc/vote_plan.hpp)
 FUSE_MAX_FETCH = 4096      # longest list of flat_knn_fused / fuse_lists_device (FUSE_MAX_FETCH of csrc/fuse_plan.hpp)
 MMR_MAX_FETCH = 4096       # longest candidate list of flat_knn_mmr / mmr_select_device (MMR_MAX_FETCH of csrc/mmr_plan.hpp)
 FETCH_CHUNK_BYTES_DEFAULT = 128 << 20  # what "fetch_chunk_bytes" is until set_param changes it (Index::FETCH_CHUNK_BYTES_DEFAULT)
@@ -884,6 +886,57 @@ class GpuIndex:
         given (vdb_group_cap_device); an id that is no row of this index raises and leaves the outputs untouched"""
         L.check(self._lib.vdb_group_cap_device(self._h, L.vp(ids_ptr), L.vp(dists_ptr), L.vp(counts_ptr), int(nq), int(ld), int(k), int(column),
                                                int(group_size), L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
+
+    @staticmethod
+    def _vote_mode(mode) -> int:
+        return VOTE_MODES.get(mode, -1) if isinstance(mode, str) else int(mode)
+
+    @staticmethod
+    def vote_plan(k: int, c: int = 1, mode="uniform", eps: float = 1e-6, column: int = 0, nq: int = 1, budget: int = 0):
+        """vdb_vote_plan, no GPU needed -> (code, table_lg, in_lds, scratch bytes per query, sub-chunk); code 0: the search forms accept
+        the call, and only then are the others meaningful (they are None otherwise)"""
+        rc, in_lds, lg = C.c_int(-1), C.c_int(-1), C.c_uint32(0)
+        scratch, sub = C.c_uint64(0), C.c_uint64(0)
+        L.check(L.load().vdb_vote_plan(int(k), int(c), GpuIndex._vote_mode(mode), float(eps), int(column), int(nq), int(budget), C.byref(rc),
+                                       C.byref(lg), C.byref(in_lds), C.byref(scratch), C.byref(sub)))
+        if rc.value:
+            return rc.value, None, None, None, None
+        return 0, lg.value, in_lds.value, scratch.value, sub.value
+
+    def flat_knn_vote(self, queries, k: int, column: int, c: int = 1, mode="uniform", eps: float = 1e-6, masks=None, mask_of=None):
+        """k-NN label vote (vdb_flat_knn_vote): per query the values of label column `column` among its k nearest rows -- flat_knn's list,
+        or flat_knn_filtered_multi's under masks / mask_of as in flat_knn_grouped; rows without a label do not vote.  A value's score is the
+        f32 left fold, in list order, of its voters' weights -- mode "uniform": 1; "inverse": 1 / (distance + eps), 0 for a NaN distance --
+        and the values are ranked by score descending, ties to the value whose first voter is nearer.  1 <= c <= k <= 4096.
+        -> (code u32 [nq][c], score f32 [nq][c], votes u32 [nq][c], count [nq] of values written -- the rest of a row is LABEL_NONE, 0, 0 --,
+        voters [nq]: the voting hits of the query)."""
+        q = _f32(queries)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        nq, cc = q.shape[0], max(int(c), 1)
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, nq)
+        code, score = np.full((nq, cc), LABEL_NONE, dtype=np.uint32), np.zeros((nq, cc), dtype=np.float32)
+        votes, cnt, voters = np.zeros((nq, cc), dtype=np.uint32), np.zeros(nq, dtype=np.uint64), np.zeros(nq, dtype=np.uint64)
+        L.check(self._lib.vdb_flat_knn_vote(self._h, _ptr(q, L.f32p), nq, q.shape[1], int(k), int(column), int(c), self._vote_mode(mode), float(eps),
+                                            arr, n_masks, mo_p, _ptr(code, L.u32p), _ptr(score, L.f32p), _ptr(votes, L.u32p), _ptr(cnt, L.u64p),
+                                            _ptr(voters, L.u64p)))
+        return code, score, votes, cnt, voters
+
+    def flat_knn_vote_device(self, q_ptr: int, nq: int, k: int, column: int, c: int, out_code_ptr: int, out_score_ptr: int, out_votes_ptr: int,
+                             out_cnt_ptr: int, out_voters_ptr: int, mode="uniform", eps: float = 1e-6, masks=None, mask_of=None, stream: int = 0):
+        """Device form (vdb_flat_knn_vote_device): the queries and the five outputs on this GPU, at most 32768 queries"""
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, int(nq))
+        L.check(self._lib.vdb_flat_knn_vote_device(self._h, L.vp(q_ptr), int(nq), self.dim, int(k), int(column), int(c), self._vote_mode(mode),
+                                                   float(eps), arr, n_masks, mo_p, L.vp(out_code_ptr), L.vp(out_score_ptr), L.vp(out_votes_ptr),
+                                                   L.vp(out_cnt_ptr), L.vp(out_voters_ptr), L.vp(stream)))
+
+    def vote_lists_device(self, ids_ptr: int, dists_ptr: int, counts_ptr: int, nq: int, ld: int, column: int, c: int, out_code_ptr: int,
+                          out_score_ptr: int, out_votes_ptr: int, out_cnt_ptr: int, out_voters_ptr: int, mode="uniform", eps: float = 1e-6,
+                          stream: int = 0):
+        """the vote alone over caller-supplied device lists [nq][ld] (u64 ids, f32 distances; 1 <= c <= ld <= 4096) and u64 counts, walked
+        in the order given (vdb_vote_lists_device); an id that is no row of this index raises and leaves the outputs untouched"""
+        L.check(self._lib.vdb_vote_lists_device(self._h, L.vp(ids_ptr), L.vp(dists_ptr), L.vp(counts_ptr), int(nq), int(ld), int(column), int(c),
+                                                self._vote_mode(mode), float(eps), L.vp(out_code_ptr), L.vp(out_score_ptr), L.vp(out_votes_ptr),
+                                                L.vp(out_cnt_ptr), L.vp(out_voters_ptr), L.vp(stream)))
 
     def flat_knn_mmr(self, queries, k: int, fetch_k: int, lambda_mult: float = 0.5, masks=None, mask_of=None):
         """Diversified exact k-NN, maximal marginal relevance (vdb_flat_knn_mmr): per query, from the first min(fetch_k, allowed rows)

@@ -412,6 +412,32 @@ def _f32_order_key(d) -> int:
     return (~u & 0xFFFFFFFF) if u & 0x80000000 else (u | 0x80000000)
 
 
+def vote_values(values_in_order, dists, top: int, mode: str = "uniform", eps: float = 1e-6):
+    """THE host statement of the k-NN label vote (GpuIndex.flat_knn_vote, k_vote_lists) over one hit list in the query's order: a
+    position votes iff its value is not None / LABEL_NONE, with the weight 1 ("uniform") or 1 / (distance + eps) in f32, 0 for a NaN
+    distance ("inverse"); a value's score is the f32 left fold of its voters' weights in list order; values rank by score descending,
+    then by the position of their first voter.  -> ([(value, score, votes)] of the first `top` values, voters).  Any hashable values."""
+    if mode not in ("uniform", "inverse"):
+        raise ValueError(f"weights {mode!r}: 'uniform' or 'inverse'")
+    e = np.float32(eps)
+    tally: dict[object, list] = {}  # value -> [score, votes, first]
+    voters = 0
+    with np.errstate(all="ignore"):
+        for pos, (v, d) in enumerate(zip(values_in_order, dists)):
+            if isinstance(v, np.integer):
+                v = int(v)
+            if v is None or v == LABEL_NONE:
+                continue
+            voters += 1
+            d = np.float32(d)
+            w = np.float32(1.0) if mode == "uniform" else (np.float32(0.0) if np.isnan(d) else np.float32(1.0) / np.float32(d + e))
+            s = tally.setdefault(v, [np.float32(0.0), 0, pos])
+            s[0] = np.float32(s[0] + w)
+            s[1] += 1
+    ranked = sorted(tally.items(), key=lambda it: (-_f32_order_key(it[1][0]), it[1][2]))
+    return [(v, float(s[0]), s[1]) for v, s in ranked[:max(int(top), 0)]], voters
+
+
 def fuse_groups(lists, k: int, mode: str = "rrf", weights=None, c: float = 60.0, trunc_len=None):
     """THE host statement of the document-level fusion (GpuIndex.flat_knn_fused_groups, k_fuse_groups), for keys without a label column.
     `lists`: per sub-query (ids, distances, values) in rank order -- values[i] is the group of entry i, any hashable; None: the row is a

@@ -57,8 +57,8 @@ from contextlib import contextmanager
 import numpy as np
 
 from ._lib import VdbError
-from .index import FUSE_MAX_FETCH, LIKE_MAX_EXAMPLES, MMR_MAX_FETCH, ROW_NONE, GpuIndex, RowMask, parse_dist
-from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, fuse_groups, filter_patterns, has_predicates, is_expression, stale_filters
+from .index import FUSE_MAX_FETCH, LIKE_MAX_EXAMPLES, MMR_MAX_FETCH, ROW_NONE, VOTE_MAX_K, VOTE_MODES, GpuIndex, RowMask, parse_dist
+from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, fuse_groups, filter_patterns, has_predicates, is_expression, stale_filters, vote_values
 from .labels import matches as value_matches
 
 _DIST_STR = {0: "l2sqr", 1: "cosine"}
@@ -1154,6 +1154,80 @@ class VecDB:
             if not short:
                 return o_idx[:, :k], o_dist[:, :k], o_cnt
             kk = min(kk * 4, n)
+
+    def classify(self, key: str, query, k: int, field: str, top: int = 1, weights: str = "uniform", filter=None):
+        """batch_classify for one query: the list of (value, score, votes) of its `top` best values of `field`"""
+        return self.batch_classify(key, [query], k, field, top, weights, None if filter is None else [filter])[0]
+
+    def batch_classify(self, key: str, queries, k: int, field: str, top: int = 1, weights: str = "uniform", filters=None, eps: float = 1e-6):
+        """Nearest-neighbour classification for a batch of queries in ONE library call (GpuIndex.flat_knn_vote): which values of the
+        metadata key `field` do the k nearest matching rows of each query carry, and how strongly?  Entry q is the list of (value, score,
+        votes) of the query's `top` best values (fewer when its neighbours carry fewer), best first.  Always exact, from the table's Flat
+        rows.  A row without the key does not vote.  weights="uniform": a value's score is its number of votes; "inverse": the f32 sum, in
+        order of distance, of 1 / (distance + eps) over its voters.  Values rank by score, ties to the value whose nearest voter is nearer.
+        1 <= top <= k <= 4096.  `filters` as in batch_search, through the mask cache.  `field` gets a label column on first use, as
+        count_by's field does -- so a field written by cluster, cluster_density or mark_duplicates assigns a new vector to a cluster or
+        a duplicate group; a key that cannot have a column (a 17th key) or whose values a dictionary cannot keep apart takes the host
+        fallback: the same rule (labels.vote_values) over the lists of the plain search at k.  One read guard covers the batch."""
+        if weights not in VOTE_MODES:
+            raise ValueError(f"weights {weights!r}: 'uniform' or 'inverse'")
+        if not 1 <= int(k) <= VOTE_MAX_K or not 1 <= int(top) <= int(k):
+            raise ValueError(f"classify: 1 <= top <= k <= {VOTE_MAX_K} is needed, got k = {k}, top = {top}")
+        t = self._t(key)
+        ix = t.index
+        q = np.asarray(queries, dtype=np.float32)
+        if q.size == 0 and q.ndim == 1:
+            return []  # (an empty batch has no shape to check)
+        if q.ndim != 2 or q.shape[1] != ix.dim:
+            raise RuntimeError(f"Dimension mismatch: table dim {ix.dim}, got {q.shape}")
+        nq = q.shape[0]
+        if filters is not None and not isinstance(filters, dict) and not is_expression(filters):
+            filters = list(filters)
+            if len(filters) != nq:
+                raise RuntimeError(f"filters: one pattern per query is needed ({nq}), got {len(filters)}")
+        if nq == 0:
+            return []
+        pats = None
+        if filters is not None:
+            pats = [filters] * nq if isinstance(filters, dict) or is_expression(filters) else filters
+            t.prepare(pats)
+        t.prepare([{field: None}])  # (the key's column, as count_by makes it)
+        with t.lock.read():  # one read guard for the whole batch, mask building and decoding included
+            masks = mask_of = None
+            if pats is not None:
+                slot: dict[object, int] = {}
+                distinct, mask_of = [], np.zeros(nq, dtype=np.uint32)
+                for i, p in enumerate(pats):
+                    pk = filter_key(p)
+                    if pk not in slot:
+                        slot[pk] = len(distinct)
+                        distinct.append(p)
+                    mask_of[i] = slot[pk]
+                masks = t.masks_for(distinct)  # the ones not cached yet: one library call
+            vc = t.codec.value_codes(field)
+            if vc is not None:
+                value_of = dict(zip(vc[1], vc[0]))
+                code, score, votes, cnt, _voters = ix.flat_knn_vote(q, k, t.codec.column_of(field), top, weights, eps, masks, mask_of)
+                return [[(value_of[int(c)], float(s), int(v)) for c, s, v in zip(code[j, :int(cnt[j])], score[j], votes[j])] for j in range(nq)]
+            if masks is None:
+                idx, dist, hits = ix.flat_knn(q, k)
+            else:
+                idx, dist, hits = ix.flat_knn_filtered_multi(q, k, masks, mask_of)
+            out = []
+            for j in range(nq):
+                odd, values = [], []
+                for i in idx[j, :int(hits[j])]:
+                    v = t.metadata[int(i)].get(field)
+                    try:
+                        hash(v)
+                    except TypeError:
+                        if v not in odd:
+                            odd.append(v)
+                        v = ("unhashable", odd.index(v), id(odd))
+                    values.append(v)
+                ranked, _ = vote_values(values, dist[j, :int(hits[j])], top, weights, eps)
+                out.append([(odd[v[1]] if isinstance(v, tuple) and v[::2] == ("unhashable", id(odd)) else v, s, n) for v, s, n in ranked])
+            return out
 
     def search_within(self, key: str, query, upper_bound: float, limit: int | None = None, filter: dict[str, str] | None = None,
                       with_vectors: bool = False):
