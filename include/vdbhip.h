@@ -619,6 +619,57 @@ int vdb_flat_dbscan_device(vdb_index *idx, float eps, uint64_t min_samples, cons
                            uint64_t *out_stats, void *stream);
 int vdb_dbscan_pairs_device(vdb_index *idx, const void *d_src, const void *d_lims, const void *d_ids, const void *d_dists, uint64_t nq,
                             uint64_t min_samples, void *d_out_label, void *d_out_kind, uint64_t *out_stats, void *stream);
+/* ---- the k-NN self-join of a table's rows, and outlier scores on its graph: k-distance, local reachability density, LOF -------------------
+ * "Which rows do not belong here?"  DBSCAN's noise needs one global radius and gives no ranking; these scores rank every row against its own
+ * neighbourhood.  (csrc/outlier_plan.hpp, csrc/flat_outliers.hip, csrc/k_outlier.hip; docs/DESIGN_flat.md 4.1ah.)  The reference has no
+ * counterpart; this is THE RULE.
+ * Let A be the allowed rows: all rows, or the rows of one mask.  Let m = |A|.  For p in A:
+ *   N(p)         the first kk = min(k, m - 1) rows of A \ {p} in the (distance, index) order of the exact f32 pair distance -- the order
+ *                vdb_flat_knn lists rows in for query = row p --, NaN greatest.  Exactly kk members, no tie extension (what
+ *                sklearn.neighbors.LocalOutlierFactor does).
+ *   kdist(p)     the distance of the last member of N(p).
+ *   reach(p, o)  max(kdist(o), d(p, o)).
+ *   lrd(p)       1 / (mean over o in N(p) of reach(p, o) + 1e-10).
+ *   lof(p)       (mean over o in N(p) of lrd(o)) / lrd(p).
+ *   m = 1 gives kk = 0: the count is 0 and all three values are NaN.  A NaN anywhere propagates, through the max as well.
+ *   Arithmetic.  Means, reciprocals and the quotient are computed in f64 from the f32 distances the search returned; each output is rounded
+ *     to f32 once.  No float atomics and a fixed summation order: two calls give the same bits.
+ *   Self-exclusion is by ID, not by position: the min(k + 1, m) nearest allowed rows are fetched; p is dropped where it stands, and the last
+ *     entry when p is not among them.  p is not always first, nor always present: a duplicate of p with a lower index precedes it at
+ *     distance 0, a NaN row's distance to itself is NaN, a zero row under Cosine is at distance 1 from itself.
+ * vdb_flat_knn_graph: out_ids [m][k] u64 (row + id_offset) and out_dists [m][k] f32, list p the N of the p-th allowed row in ascending row
+ *   order, zeros behind out_counts[p] = kk entries.  vdb_flat_outliers: out_kdist / out_lrd / out_lof [m] f32 in the same order; any of the
+ *   three may be NULL.
+ * How: the allowed rows are the queries, chunk by chunk in ascending row order ("flat_dup_chunk" queries, clipped so that a chunk's lists
+ * stay under 256 MiB), where they lie or gathered under a mask.  Per chunk ONE call of the existing search at min(k + 1, m) -- vdb_flat_knn's
+ * path, or vdb_flat_knn_filtered's under the mask, whose counters advance as for that call -- and one k_knn_self_pack launch: a wave per
+ * list, tiles of 64, a ballot finds the row's own id and a prefix popcount closes the gap.  The graph (4 B local row + 4 B distance per
+ * slot: 8 B x m x k, 160 MB at 1M x 20) stays on the device for the two score launches; kdist and the f64 lrd are kept per ROW (12 B per row
+ * of the table) so that their gathers need no row-to-position map under a mask.  k_lof_lrd / k_lof_score give pow2ceil(k) lanes to a source
+ * row while k <= 64 (64 / pow2ceil(k) rows per wave, one lane per neighbour, a fixed butterfly inside the lane group) and a wave to a row,
+ * striding, beyond.  They are two launches because lrd of EVERY row must exist before any lof.
+ * Refused, outputs and the two counters below untouched: k outside 1 .. 1023, a VecSet<u8> index (VDB_ERR_INVALID), a mask of another index
+ * (VDB_ERR_INVALID) or a stale one (VDB_ERR_STATE), a NULL graph output.  An empty index and an empty mask succeed.  Read-side, re-entrant;
+ * all forms return synchronised; the _device forms write device arrays of the same shapes (u64: 8-byte aligned) after waiting for `stream`.
+ * vdb_lof_lists_device: the two score stages alone over a caller-supplied graph on the index's GPU -- d_nbr u32 / d_nd f32 [m][k], d_cnt u32
+ *   [m]; list p belongs to item p and names items below m (the index lends its device and stream; its rows are not looked at); kdist(p) is
+ *   the distance of list p's last counted slot.  A count above k or an id at or above m is found on the device first and refused before
+ *   any output is written.  Any of the three outputs (f32 [m]) may be NULL.
+ * vdb_outlier_plan: host utility, works without a GPU: the argument check (also: an index of 2^32 rows or more, a chunk outside 1 .. 2^20,
+ *   an allowed count that does not fit the index) and the number of search calls, the last chunk's length, kk, the lane-group width (0: a
+ *   wave per row), the graph's bytes and the scratch bytes of an outliers call.  Any output may be NULL; on an error nothing is written.
+ * vdb_get_stat: "flat_knn_graph_calls" (graph walks that succeeded, from either entry), "flat_knn_graph_chunks" (their search calls).
+ * vdb_prof_get "knn_self_pack" / "lof_stages" time the kernels. */
+int vdb_outlier_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m_allowed, uint64_t k, uint64_t chunk, uint64_t *out_chunks,
+                     uint64_t *out_last, uint64_t *out_kk, uint32_t *out_group, uint64_t *out_graph_bytes, uint64_t *out_scratch_bytes);
+int vdb_flat_knn_graph(vdb_index *idx, uint64_t k, const vdb_mask *mask /* NULL: all rows */, uint64_t *out_ids /* [m][k] */,
+                       float *out_dists /* [m][k] */, uint64_t *out_counts /* [m] */);
+int vdb_flat_knn_graph_device(vdb_index *idx, uint64_t k, const vdb_mask *mask, void *d_out_ids, void *d_out_dists, void *d_out_counts, void *stream);
+int vdb_flat_outliers(vdb_index *idx, uint64_t k, const vdb_mask *mask /* NULL: all rows */, float *out_kdist /* [m] or NULL */,
+                      float *out_lrd /* [m] or NULL */, float *out_lof /* [m] or NULL */);
+int vdb_flat_outliers_device(vdb_index *idx, uint64_t k, const vdb_mask *mask, void *d_out_kdist, void *d_out_lrd, void *d_out_lof, void *stream);
+int vdb_lof_lists_device(vdb_index *idx, const void *d_nbr, const void *d_nd, const void *d_cnt, uint64_t m, uint64_t k, void *d_out_kdist,
+                         void *d_out_lrd, void *d_out_lof, void *stream);
 /* ---- grouped Flat k-NN: at most group_size hits per value of one label column -----------------------------------------------------------
  * "The 10 nearest chunks, at most 2 per document": the label columns so far restrict WHICH rows may be found; this call shapes the answer.
  * For one query let L be its allowed rows in FlatIndex::knn's order -- ascending by (distance, id), NaN distances last; all rows, or
@@ -1119,6 +1170,8 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *                        "flat_dup_pairs": the non-self pairs they saw,
  *   "flat_dbscan_calls"  vdb_flat_dbscan / _device calls that succeeded; "flat_dbscan_chunks": the range calls under them;
  *                        "flat_dbscan_pairs": the non-self pairs they saw,
+ *   "flat_knn_graph_calls"  vdb_flat_knn_graph / vdb_flat_outliers (+ _device) calls that succeeded; "flat_knn_graph_chunks": the search
+ *                        calls under them,
  *   "update_calls"       vdb_index_update_rows / _device calls that changed rows (m > 0, not refused); "update_rows": the rows they rewrote,
  *   "fetch_calls"        vdb_index_get_rows* calls that fetched rows (m > 0, not refused); "fetch_rows": the rows they returned;
  *                        "fetch_chunks": their gather launches; "fetch_direct": the calls answered by one plain copy,

@@ -337,6 +337,46 @@ public:
         if (voters) *voters = nv;
         return out;
     }
+    // the k-NN self-join (vdb_flat_knn_graph): per allowed row (mask null: every row), ascending, its min(k, m - 1) nearest OTHER allowed
+    // rows, best first
+    std::vector<std::vector<CandidatePair>> knn_graph(uint64_t k, const Mask *mask = nullptr) const {
+        const uint64_t m = mask ? mask->count() : len(), kk = k ? k : 1;
+        std::vector<uint64_t> idx(m * kk + 1), cnt(m + 1);
+        std::vector<float> d(m * kk + 1);
+        check(vdb_flat_knn_graph(h_, k, mask ? mask->handle() : nullptr, idx.data(), d.data(), cnt.data()));
+        std::vector<std::vector<CandidatePair>> out(m);
+        for (uint64_t p = 0; p < m; p++)
+            for (uint64_t j = 0; j < cnt[p]; j++) out[p].push_back({idx[p * k + j], d[p * k + j]});
+        return out;
+    }
+    // outlier scores on that graph (vdb_flat_outliers): k-distance, local reachability density and LOF of every allowed row, ascending
+    struct OutlierScores {
+        std::vector<float> kdist, lrd, lof;
+    };
+    OutlierScores outliers(uint64_t k, const Mask *mask = nullptr) const {
+        const uint64_t m = mask ? mask->count() : len();
+        OutlierScores s{std::vector<float>(m + 1), std::vector<float>(m + 1), std::vector<float>(m + 1)};
+        check(vdb_flat_outliers(h_, k, mask ? mask->handle() : nullptr, s.kdist.data(), s.lrd.data(), s.lof.data()));
+        s.kdist.resize(m), s.lrd.resize(m), s.lof.resize(m);
+        return s;
+    }
+    // the two score stages alone over a graph on the index's GPU (vdb_lof_lists_device): u32 nbr / f32 nd [m][k], u32 cnt [m] -> f32 [m] each
+    void lof_lists_device(const void *d_nbr, const void *d_nd, const void *d_cnt, uint64_t m, uint64_t k, void *d_kdist, void *d_lrd, void *d_lof,
+                          void *stream = nullptr) const {
+        check(vdb_lof_lists_device(h_, d_nbr, d_nd, d_cnt, m, k, d_kdist, d_lrd, d_lof, stream));
+    }
+    // (chunks, last, kk, group, graph_bytes, scratch_bytes) of such a call (vdb_outlier_plan; host only)
+    struct OutlierPlanInfo {
+        uint64_t chunks, last, kk;
+        uint32_t group;
+        uint64_t graph_bytes, scratch_bytes;
+    };
+    static OutlierPlanInfo outlier_plan(uint64_t n_rows, uint64_t dim, uint64_t k, bool masked = false, uint64_t m_allowed = 0, uint64_t chunk = 16384) {
+        OutlierPlanInfo p{};
+        check(vdb_outlier_plan(n_rows, dim, 0, masked ? 1 : 0, masked ? m_allowed : n_rows, k, chunk, &p.chunks, &p.last, &p.kk, &p.group, &p.graph_bytes,
+                               &p.scratch_bytes));
+        return p;
+    }
     // diversified k-NN, maximal marginal relevance (vdb_flat_knn_mmr): per query, from the first min(fetch_k, allowed rows) pairs of
     // knn_batch, the nearest and then greedily the pair with the smallest lambda * d(query, row) - (1 - lambda) * min over the selected rows
     // of d(row, selected); the pairs come in SELECTION order.  masks empty: over all rows; otherwise query q under *masks[mask_of[q]]

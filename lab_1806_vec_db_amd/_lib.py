@@ -81,6 +81,12 @@ SIGNATURES = {
     "vdb_flat_dbscan": [vp, C.c_float, u64, vp, u64p, u8p, u64p],
     "vdb_flat_dbscan_device": [vp, C.c_float, u64, vp, vp, vp, u64p, vp],
     "vdb_dbscan_pairs_device": [vp, vp, vp, vp, vp, u64, u64, vp, vp, u64p, vp],
+    "vdb_outlier_plan": [u64, u64, C.c_int, C.c_int, u64, u64, u64, u64p, u64p, u64p, u32p, u64p, u64p],
+    "vdb_flat_knn_graph": [vp, u64, vp, u64p, f32p, u64p],
+    "vdb_flat_knn_graph_device": [vp, u64, vp, vp, vp, vp, vp],
+    "vdb_flat_outliers": [vp, u64, vp, f32p, f32p, f32p],
+    "vdb_flat_outliers_device": [vp, u64, vp, vp, vp, vp, vp],
+    "vdb_lof_lists_device": [vp, vp, vp, vp, u64, u64, vp, vp, vp, vp],
     "vdb_kmeans_plan": [u64, u64, C.c_int, C.c_int, u64, u64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, u64p, u64p, u64p, u64p, u64p, f32p],
     "vdb_kmeans_segment": [u64, u64, u64p, u64p],
     "vdb_flat_kmeans": [vp, u64, u64, C.c_float, u64, f32p, u64, vp, f32p, u32p, u64p, u64p, f64p],

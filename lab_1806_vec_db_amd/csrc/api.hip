@@ -1070,6 +1070,130 @@ int vdb_dbscan_pairs_device(vdb_index *idx, const void *d_src, const void *d_lim
     std::memcpy(out_stats, stats, sizeof(stats));
     VDB_API_END
 }
+// the k-NN self-join and the outlier scores on its graph (Index::flat_knn_graph_device / flat_outliers_device / lof_lists_device,
+// outlier_plan.hpp, flat_outliers.hip)
+int vdb_outlier_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m_allowed, uint64_t k, uint64_t chunk, uint64_t *out_chunks,
+                     uint64_t *out_last, uint64_t *out_kk, uint32_t *out_group, uint64_t *out_graph_bytes, uint64_t *out_scratch_bytes) {
+    VDB_API_BEGIN
+    const std::string bad = outlier_check_args(n_rows, m_allowed, masked != 0, elem_u8 != 0, k, chunk);
+    VDB_REQUIRE(bad.empty(), bad);
+    const OutlierPlan p = outlier_plan(n_rows, dim, masked != 0, m_allowed, k, chunk);
+    if (out_chunks) *out_chunks = p.n_chunks;
+    if (out_last) *out_last = p.last_len;
+    if (out_kk) *out_kk = p.kk;
+    if (out_group) *out_group = p.group;
+    if (out_graph_bytes) *out_graph_bytes = p.graph_bytes;
+    if (out_scratch_bytes) *out_scratch_bytes = p.scratch_bytes;
+    VDB_API_END
+}
+// what the four forms refuse before a workspace is taken -> the mask as a RowMask (nullptr: all rows); *m = the allowed rows
+static const RowMask *outlier_check(const Index &ix, uint64_t k, const vdb_mask *mask, uint64_t *m) {
+    if (mask) ix.check_mask(mask->m);
+    *m = mask ? mask->m.m : ix.n;
+    const std::string bad = outlier_check_args(ix.n, *m, mask != nullptr, ix.elem_u8, k, ix.dup_chunk);
+    VDB_REQUIRE(bad.empty(), bad);
+    return mask ? &mask->m : nullptr;
+}
+int vdb_flat_knn_graph(vdb_index *idx, uint64_t k, const vdb_mask *mask, uint64_t *out_ids, float *out_dists, uint64_t *out_counts) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    uint64_t m = 0;
+    const RowMask *rm = outlier_check(ix, k, mask, &m);
+    VDB_REQUIRE(m == 0 || (out_ids && out_dists && out_counts), "knn graph: null argument");
+    ix.use_device();
+    WsLease ws(ix);
+    DevBuf d_ids, d_dists, d_counts;
+    d_ids.reserve(std::max<uint64_t>(m * k, 1) * sizeof(uint64_t));
+    d_dists.reserve(std::max<uint64_t>(m * k, 1) * sizeof(float));
+    d_counts.reserve(std::max<uint64_t>(m, 1) * sizeof(uint64_t));
+    run_synced(ix, *ws, [&] {
+        ix.flat_knn_graph_device(*ws, k, rm, d_ids.as<uint64_t>(), d_dists.as<float>(), d_counts.as<uint64_t>());
+        if (m) {
+            VDB_HIP(hipMemcpyAsync(out_ids, d_ids.p, m * k * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+            VDB_HIP(hipMemcpyAsync(out_dists, d_dists.p, m * k * sizeof(float), hipMemcpyDeviceToHost, ws->stream));
+            VDB_HIP(hipMemcpyAsync(out_counts, d_counts.p, m * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+        }
+        VDB_SYNC(ws->stream);
+    });
+    VDB_API_END
+}
+int vdb_flat_knn_graph_device(vdb_index *idx, uint64_t k, const vdb_mask *mask, void *d_out_ids, void *d_out_dists, void *d_out_counts, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    uint64_t m = 0;
+    const RowMask *rm = outlier_check(ix, k, mask, &m);
+    VDB_REQUIRE(m == 0 || (d_out_ids && d_out_dists && d_out_counts), "knn graph: null argument");
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_out_ids) % 8 == 0 && reinterpret_cast<uintptr_t>(d_out_dists) % 4 == 0 &&
+                    reinterpret_cast<uintptr_t>(d_out_counts) % 8 == 0,
+                "knn graph: the device outputs must be 8-byte aligned (the distances: 4)");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever last used the outputs on the caller's stream
+    run_synced(ix, *ws, [&] {
+        ix.flat_knn_graph_device(*ws, k, rm, static_cast<uint64_t *>(d_out_ids), static_cast<float *>(d_out_dists), static_cast<uint64_t *>(d_out_counts));
+    });
+    VDB_API_END
+}
+int vdb_flat_outliers(vdb_index *idx, uint64_t k, const vdb_mask *mask, float *out_kdist, float *out_lrd, float *out_lof) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    uint64_t m = 0;
+    const RowMask *rm = outlier_check(ix, k, mask, &m);
+    ix.use_device();
+    WsLease ws(ix);
+    float *const outs[3] = {out_kdist, out_lrd, out_lof};
+    DevBuf d_out;  // [kdist | lrd | lof], only the wanted ones used
+    d_out.reserve(std::max<uint64_t>(3 * m, 1) * sizeof(float));
+    float *d[3];
+    for (int i = 0; i < 3; i++) d[i] = outs[i] ? d_out.as<float>() + i * m : nullptr;
+    run_synced(ix, *ws, [&] {
+        ix.flat_outliers_device(*ws, k, rm, d[0], d[1], d[2]);
+        for (int i = 0; i < 3; i++)
+            if (m && outs[i]) VDB_HIP(hipMemcpyAsync(outs[i], d[i], m * sizeof(float), hipMemcpyDeviceToHost, ws->stream));
+        VDB_SYNC(ws->stream);
+    });
+    VDB_API_END
+}
+int vdb_flat_outliers_device(vdb_index *idx, uint64_t k, const vdb_mask *mask, void *d_out_kdist, void *d_out_lrd, void *d_out_lof, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    uint64_t m = 0;
+    const RowMask *rm = outlier_check(ix, k, mask, &m);
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_out_kdist) % 4 == 0 && reinterpret_cast<uintptr_t>(d_out_lrd) % 4 == 0 &&
+                    reinterpret_cast<uintptr_t>(d_out_lof) % 4 == 0,
+                "outliers: the device outputs must be 4-byte aligned");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever last used the outputs on the caller's stream
+    run_synced(ix, *ws, [&] {
+        ix.flat_outliers_device(*ws, k, rm, static_cast<float *>(d_out_kdist), static_cast<float *>(d_out_lrd), static_cast<float *>(d_out_lof));
+    });
+    VDB_API_END
+}
+int vdb_lof_lists_device(vdb_index *idx, const void *d_nbr, const void *d_nd, const void *d_cnt, uint64_t m, uint64_t k, void *d_out_kdist,
+                         void *d_out_lrd, void *d_out_lof, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    VDB_REQUIRE(m == 0 || (d_nbr && d_nd && d_cnt), "lof lists: null argument");
+    const std::string bad = outlier_check_k(k);
+    VDB_REQUIRE(bad.empty(), bad);
+    VDB_REQUIRE(m < (1ull << 32), "lof lists: too many lists for one call");
+    for (const void *p : {d_nbr, d_nd, d_cnt, (const void *)d_out_kdist, (const void *)d_out_lrd, (const void *)d_out_lof})
+        VDB_REQUIRE(reinterpret_cast<uintptr_t>(p) % 4 == 0, "lof lists: the device arrays must be 4-byte aligned");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the lists on the caller's stream
+    run_synced(ix, *ws, [&] {
+        ix.lof_lists_device(*ws, static_cast<const uint32_t *>(d_nbr), static_cast<const float *>(d_nd), static_cast<const uint32_t *>(d_cnt), m, k,
+                            static_cast<float *>(d_out_kdist), static_cast<float *>(d_out_lrd), static_cast<float *>(d_out_lof));
+    });
+    VDB_API_END
+}
 // k-means over the rows (Index::flat_kmeans_device / kmeans_assign_device, kmeans_plan.hpp, flat_kmeans.hip)
 int vdb_kmeans_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m, uint64_t c, int lloyd, int cosine, float xn, float cn,
                     float d_best, uint64_t *out_row_tiles, uint64_t *out_cent_tiles, uint64_t *out_k_blocks, uint64_t *out_order_passes,
@@ -2368,6 +2492,10 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.dbscan_chunks.load();
     else if (n == "flat_dbscan_pairs")
         *out = idx->ix.dbscan_pairs.load();
+    else if (n == "flat_knn_graph_calls")  // vdb_flat_knn_graph / vdb_flat_outliers (+ _device): graph walks that succeeded | search calls (chunks) under them
+        *out = idx->ix.knn_graph_calls.load();
+    else if (n == "flat_knn_graph_chunks")
+        *out = idx->ix.knn_graph_chunks.load();
     else if (n == "flat_grouped_calls")  // grouped k-NN: calls | queries | rounds run, summed over calls | queries whose last list was their whole allowed set
         *out = idx->ix.grouped_calls.load();
     else if (n == "flat_grouped_queries")

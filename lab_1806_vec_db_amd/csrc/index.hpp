@@ -823,6 +823,22 @@ struct Index {
     void dbscan_pairs_device(Workspace &ws, const uint64_t *d_src, const uint64_t *d_lims, const uint64_t *d_ids, const float *d_dists, uint64_t nq,
                              uint64_t min_samples, uint64_t *d_label, uint8_t *d_kind, uint64_t *stats);
     std::atomic<uint64_t> dbscan_calls{0}, dbscan_chunks{0}, dbscan_pairs{0};  // flat_dbscan calls that succeeded / their range calls / non-self pairs they saw
+    // The k-NN self-join and the outlier scores on its graph (flat_outliers.hip, k_outlier.hip, outlier_plan.hpp -- which states the rule;
+    // docs/DESIGN_flat.md 4.1ah).  Every allowed row (mask == nullptr: all rows) is a query of the existing search at min(k + 1, m), itself
+    // taken out of its list BY ID: N(p) = the first min(k, m - 1) other allowed rows in the (distance, index) order.  Outputs on the device,
+    // by POSITION among the allowed rows, ascending: flat_knn_graph_device d_ids u64 / d_dists f32 [m][k] (row + id_offset; zeros behind
+    // the count) and d_counts u64 [m]; flat_outliers_device d_kdist / d_lrd / d_lof f32 [m], each may be nullptr.  The allowed rows are
+    // walked in chunks of dup_chunk queries clipped to LIST_BUDGET, ONE flat_knn_device / flat_knn_masked_device call per chunk, whose
+    // counters advance as for that call.  Read-side, re-entrant; the arguments and the mask are checked here before anything is written.
+    // Return synchronised.
+    void flat_knn_graph_device(Workspace &ws, uint64_t k, const RowMask *mask, uint64_t *d_ids, float *d_dists, uint64_t *d_counts);
+    void flat_outliers_device(Workspace &ws, uint64_t k, const RowMask *mask, float *d_kdist, float *d_lrd, float *d_lof);
+    // The two score stages alone over a caller-supplied graph on the device: d_nbr u32 / d_nd f32 [m][k], d_cnt u32 [m]; list p belongs to
+    // item p and names items below m; kdist of an item is the distance of its last counted slot.  Counts and ids are checked on the device
+    // first (one flag read back; a bad one throws before an output is written).  Returns synchronised.
+    void lof_lists_device(Workspace &ws, const uint32_t *d_nbr, const float *d_nd, const uint32_t *d_cnt, uint64_t m, uint64_t k, float *d_kdist,
+                          float *d_lrd, float *d_lof);
+    std::atomic<uint64_t> knn_graph_calls{0}, knn_graph_chunks{0};  // graph walks that succeeded (either entry) / the search calls under them
     // k-means over the rows (flat_kmeans.hip, k_kmeans.hip, kmeans_plan.hpp; docs/DESIGN_flat.md 4.1ad).  The rows clustered are the mask's
     // allowed rows (nullptr: all); d_assign [n] u32 and d_best [n] f32 are indexed by row, KM_LABEL_NONE / NaN for a row outside the mask.
     // kmeans_assign_device: the assignment step alone against d_cent [c][dim] on the device -- row i to the centroid with the smallest

@@ -17,6 +17,7 @@
 #include "mask_partition.hpp"
 #include "mask_sets.hpp"
 #include "mmr_plan.hpp"
+#include "outlier_plan.hpp"
 #include "vote_plan.hpp"
 
 namespace vdb {
@@ -602,6 +603,21 @@ void launch_fuse_groups(const uint64_t *ids, const float *dists, const uint64_t 
 void launch_vote_lists(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nq, uint64_t ld, const uint32_t *labels, uint64_t n,
                        uint64_t id_offset, int mode, float eps, uint32_t c, uint32_t *scratch, uint32_t *out_code, float *out_score,
                        uint32_t *out_votes, uint64_t *out_cnt, uint64_t *out_voters, hipStream_t s);
+// The k-NN self-join's graph and the outlier scores on it (k_outlier.hip, outlier_plan.hpp).  launch_knn_self_pack: list b < nb of a chunk
+// (ids / dists [b][0 .. min(counts[b], ld)), sorted, ids = row + id_offset) belongs to position base + b and row src32 ? src32[b] : base +
+// b; the first kk entries other than the row itself go to slot [base + b][0 .. k) of nbr (u32 LOCAL row) / out_ids (u64 as listed) / nd,
+// zeros behind them, their number to cnt32 / cnt64 [base + b], the distance of the last one (NaN: none) to kdist[row].  nullptr: not
+// wanted (nd always is).  launch_lof_check: *flag = 1 (zeroed by the caller) when a cnt[p] passes k or a counted nbr[p][j] is not below
+// n.  launch_lof_kdist: kdist[p] = nd[p][cnt[p] - 1], NaN for an empty list.  launch_lof_stages: k_lof_lrd, then k_lof_score unless
+// out_lof == nullptr, at the lane-group width outlier_group(k); kdist / lrd64 are indexed by ROW (src32 ? src32[p] : p), the outputs
+// (f32 [m], nullptr: not wanted) by position.
+void launch_knn_self_pack(const uint64_t *ids, const float *dists, const uint64_t *counts, uint64_t nb, uint64_t ld, const uint32_t *src32, uint64_t base,
+                          uint64_t id_offset, uint32_t k, uint32_t kk, uint32_t *nbr, uint64_t *out_ids, float *nd, uint32_t *cnt32, uint64_t *cnt64,
+                          float *kdist, int num_cu, hipStream_t s);
+void launch_lof_check(const uint32_t *nbr, const uint32_t *cnt, uint64_t m, uint32_t k, uint64_t n, uint32_t *flag, int num_cu, hipStream_t s);
+void launch_lof_kdist(const float *nd, const uint32_t *cnt, uint64_t m, uint32_t k, float *kdist, int num_cu, hipStream_t s);
+void launch_lof_stages(const uint32_t *nbr, const float *nd, const uint32_t *cnt, const uint32_t *src32, uint64_t m, uint32_t k, const float *kdist,
+                       double *lrd64, float *out_kdist, float *out_lrd, float *out_lof, int num_cu, hipStream_t s);
 // ---- k_pq.hip: product quantisation -- lookup tables, the ADC scans and their exact stages, encoder, re-sort, shard merge ----------
 // The argument structs are filled by the search drivers (pq.hip); every launcher works out its own grid and dynamic LDS bytes.  Where a
 // driver has to ASK whether a scan's LDS image fits before it chooses that scan, the same *_lds_bytes() the launcher uses answers.

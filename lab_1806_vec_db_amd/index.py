@@ -692,6 +692,72 @@ class GpuIndex:
                                          C.byref(scratch)))
         return int(chunks.value), int(last.value), bool(gather.value), int(scratch.value)
 
+    @staticmethod
+    def _graph_k(k) -> int:
+        """as the C ABI's u64: what does not fit one becomes 0, which the library refuses with its own message"""
+        return int(k) if 0 <= int(k) < 2 ** 64 else 0
+
+    def knn_graph(self, k: int, mask: RowMask | None = None):
+        """The k-NN self-join of the index's own rows, or the mask's (vdb_flat_knn_graph): (ids, dists, counts).  With A the allowed rows,
+        m = |A|, list p is N of the p-th allowed row in ascending row order: the first kk = min(k, m - 1) rows of A without the row
+        itself, in the (distance, index) order of the exact f32 pair distance (the order search lists them in), NaN greatest, exactly
+        kk members.  The row is taken out BY ID: a lower-index duplicate precedes it, and a NaN row or a zero row under cosine is not
+        among its own nearest.  ids: uint64 [m][k] (row + id_offset), dists: float32 [m][k], zeros behind counts[p] = kk entries.
+        k outside 1 .. 1023, a u8 index and a stale or foreign mask raise VdbError."""
+        m, k = len(self) if mask is None else len(mask), self._graph_k(k)
+        ids, dists = np.zeros((m, max(k, 1)), dtype=np.uint64), np.zeros((m, max(k, 1)), dtype=np.float32)
+        counts = np.zeros(m, dtype=np.uint64)
+        L.check(self._lib.vdb_flat_knn_graph(self._h, k, None if mask is None else mask._h, _ptr(ids, L.u64p), _ptr(dists, L.f32p), _ptr(counts, L.u64p)))
+        return ids, dists, counts
+
+    def knn_graph_device(self, k: int, out_ids_ptr: int, out_dists_ptr: int, out_counts_ptr: int, mask: RowMask | None = None, stream: int = 0):
+        """the same with ids (u64 [m][k]), dists (f32 [m][k]) and counts (u64 [m]) written to device memory (vdb_flat_knn_graph_device);
+        returns synchronised"""
+        L.check(self._lib.vdb_flat_knn_graph_device(self._h, self._graph_k(k), None if mask is None else mask._h, L.vp(out_ids_ptr), L.vp(out_dists_ptr),
+                                                    L.vp(out_counts_ptr), L.vp(stream)))
+
+    def outliers(self, k: int = 20, mask: RowMask | None = None):
+        """Outlier scores of the index's rows, or the mask's, on knn_graph's lists N(p) (vdb_flat_outliers): (kdist, lrd, lof), float32 [m]
+        each, in ascending row order.
+          kdist(p)     the distance of the last member of N(p).
+          reach(p, o)  max(kdist(o), d(p, o)).
+          lrd(p)       1 / (mean over o in N(p) of reach(p, o) + 1e-10).
+          lof(p)       (mean over o in N(p) of lrd(o)) / lrd(p): about 1 inside a region of even density, well above 1 for a row whose
+                       neighbours are denser than it is.
+        m = 1: all three are NaN.  A NaN anywhere propagates.  Means, reciprocals and the quotient are f64 over the f32 distances, each
+        output rounded once; the summation order is fixed, so two calls give the same bits.  Raises what knn_graph raises."""
+        m = len(self) if mask is None else len(mask)
+        out = [np.full(m, np.nan, dtype=np.float32) for _ in range(3)]
+        L.check(self._lib.vdb_flat_outliers(self._h, self._graph_k(k), None if mask is None else mask._h, *(_ptr(o, L.f32p) for o in out)))
+        return tuple(out)
+
+    def outliers_device(self, k: int, out_kdist_ptr: int, out_lrd_ptr: int, out_lof_ptr: int, mask: RowMask | None = None, stream: int = 0):
+        """the same with the scores written to device memory (f32 [m] each, 0: not wanted; vdb_flat_outliers_device); returns synchronised"""
+        L.check(self._lib.vdb_flat_outliers_device(self._h, self._graph_k(k), None if mask is None else mask._h, L.vp(out_kdist_ptr), L.vp(out_lrd_ptr),
+                                                   L.vp(out_lof_ptr), L.vp(stream)))
+
+    def lof_lists_device(self, nbr_ptr: int, nd_ptr: int, cnt_ptr: int, m: int, k: int, out_kdist_ptr: int, out_lrd_ptr: int, out_lof_ptr: int,
+                         stream: int = 0):
+        """the two score stages alone over a caller-supplied graph on the device (vdb_lof_lists_device): nbr u32 / nd f32 [m][k], cnt u32
+        [m]; list p belongs to item p and names items below m (the index's rows are not looked at); kdist(p) is the distance of list p's
+        last counted slot.  Outputs f32 [m] each, 0: not wanted.  A count above k or an id at or above m raises and leaves the outputs
+        untouched."""
+        L.check(self._lib.vdb_lof_lists_device(self._h, L.vp(nbr_ptr), L.vp(nd_ptr), L.vp(cnt_ptr), int(m), self._graph_k(k), L.vp(out_kdist_ptr),
+                                               L.vp(out_lrd_ptr), L.vp(out_lof_ptr), L.vp(stream)))
+
+    @staticmethod
+    def outlier_plan(n_rows: int, dim: int, k: int, m_allowed: int | None = None, chunk: int = 16384, elem_u8: bool = False):
+        """(chunks, last, kk, group, graph_bytes, scratch_bytes) of an outliers call (vdb_outlier_plan; host only, no GPU): the search calls
+        it makes, the queries of the last one, kk = min(k, m - 1), the lanes that share a source row in the score stages (0: a wave per
+        row), the bytes of the resident graph (8 x m x k) and all device bytes held besides the search's own.  Raises VdbError for what
+        outliers refuses by its arguments."""
+        masked = m_allowed is not None
+        chunks, last, kk, group, graph, scratch = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+        L.check(L.load().vdb_outlier_plan(int(n_rows), int(dim), int(bool(elem_u8)), int(masked), int(m_allowed if masked else n_rows),
+                                          GpuIndex._graph_k(k), int(chunk), C.byref(chunks), C.byref(last), C.byref(kk), C.byref(group),
+                                          C.byref(graph), C.byref(scratch)))
+        return int(chunks.value), int(last.value), int(kk.value), int(group.value), int(graph.value), int(scratch.value)
+
     def kmeans(self, c: int, max_iter: int = 20, tol: float = 1e-4, seed: int = 0, init=None, mask: RowMask | None = None):
         """k-means over the index's rows, or the mask's (vdb_flat_kmeans): (centroids f32 [c][dim], assign uint32 [len], sizes uint64 [c],
         iters, inertia).  Rows go to the centroid with the smallest (pair distance as the re-rank reports it, centroid id); a centroid becomes

@@ -1419,6 +1419,61 @@ class VecDB:
             return {"clusters": stats["clusters"], "core": stats["core"], "border": stats["border"], "noise": stats["noise"],
                     "sizes": np.bincount(ordinal, minlength=len(names)).astype(np.int64)}
 
+    def knn_graph(self, key: str, k: int, filter=None):
+        """The k-NN self-join of the rows that match `filter` (every row without one): (rows, ids, dists, counts).  rows: the matching
+        rows, ascending; ids / dists [len(rows)][k]: per row its min(k, matching rows - 1) nearest OTHER matching rows (row numbers, as
+        search reports them) and their distances, nearest first, zeros behind counts[p] entries.  The row itself is taken out by id, so
+        an identical row with a lower number stays.  ONE GpuIndex.knn_graph call under the read lock and the filter's cached mask."""
+        t = self._t(key)
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.read():
+            mk = None if filter is None else t.mask_for(filter)
+            ids, dists, counts = t.index.knn_graph(k, mk)
+            rows = np.arange(len(t.index), dtype=np.int64) if mk is None else np.asarray(mk.rows()[1], dtype=np.int64)
+            return rows, ids, dists, counts
+
+    @staticmethod
+    def _outlier_rows(t: _Table, k: int, method: str, filter):
+        """UNDER THE READ LOCK: (rows, scores) of outlier_scores"""
+        if method not in ("lof", "kdist"):
+            raise ValueError('method must be "lof" or "kdist"')
+        mk = None if filter is None else t.mask_for(filter)
+        kdist, _, lof = t.index.outliers(k, mk)
+        rows = np.arange(len(t.index), dtype=np.int64) if mk is None else np.asarray(mk.rows()[1], dtype=np.int64)
+        return rows, lof if method == "lof" else kdist
+
+    def outlier_scores(self, key: str, k: int = 20, method: str = "lof", filter=None):
+        """(rows, scores): "which rows do not belong here?" as a number per row that matches `filter` (every row without one).  rows: the
+        matching rows, ascending; scores: float32, by `method` over each row's k nearest OTHER matching rows (GpuIndex.outliers states
+        the definitions):
+          "lof"    the Local Outlier Factor: the mean local reachability density of the row's neighbours over its own.  About 1 inside
+                   a region of even density, well above 1 for a row that is sparser than its neighbours; it needs no global radius.
+          "kdist"  the distance to the k-th neighbour.
+        A single matching row scores NaN.  ONE GpuIndex.outliers call under the read lock and the filter's cached mask."""
+        t = self._t(key)
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.read():
+            return self._outlier_rows(t, k, method, filter)
+
+    def find_outliers(self, key: str, k: int = 20, top: int = 10, method: str = "lof", filter=None, with_vectors: bool = False):
+        """The `top` rows of outlier_scores as records: (metadata, score), or (metadata, score, vector) with_vectors, ordered by (score
+        descending, row ascending), rows with a NaN score last.  The vectors come from one GpuIndex.get_rows call, as get's do."""
+        if int(top) < 0:
+            raise ValueError("top must be at least 0")
+        t = self._t(key)
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.read():
+            rows, scores = self._outlier_rows(t, k, method, filter)
+            nan = np.isnan(scores)
+            order = np.lexsort((rows, -np.where(nan, -np.inf, scores).astype(np.float64), nan))[:int(top)]  # (selecting top of m floats: plumbing)
+            picked = rows[order]
+            vecs = t.index.get_rows(picked.astype(np.uint64)) if with_vectors and picked.size else None
+            return [(dict(t.metadata[int(r)]), float(scores[o])) + ((vecs[j].copy(),) if vecs is not None else ())
+                    for j, (r, o) in enumerate(zip(picked.tolist(), order.tolist()))]
+
     def delete_duplicates(self, key: str, radius: float, filter=None, limit: int | None = None) -> int:
         """Removes every row of a find_duplicates group except its representative (the lowest row); returns the number removed.  ONE
         GpuIndex.remove_rows call; the metadata follow the moves it reports, and the HNSW index and the PQ table are cleared, as delete
