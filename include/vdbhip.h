@@ -523,6 +523,45 @@ int vdb_kmeans_assign(vdb_index *idx, const float *centroids, uint64_t c, uint64
                       float *out_best /* [len] or NULL */, uint64_t *out_unsure); /* the host form of the call below */
 int vdb_kmeans_assign_device(vdb_index *idx, const void *d_centroids, uint64_t c, uint64_t dim, const vdb_mask *mask, void *d_out_assign,
                              void *d_out_best, uint64_t *out_unsure, void *stream);
+/* ---- PCA of a table's rows (csrc/pca_plan.hpp, csrc/flat_pca.hip, csrc/k_pca.hip; docs/DESIGN_flat.md 4.1ai) -------------------------------
+ * "Along which directions do these rows vary, and what do they look like in few dimensions?"  The column means and the covariance matrix of
+ * the rows of an f32 index, or of the rows a mask allows, in f64 on the matrix pipe (v_mfma_f64_16x16x4_f64), and the projection of rows or
+ * of a caller's vectors onto a set of components.  The eigen-decomposition of the dim x dim matrix is left to the caller (its cost does not
+ * depend on the row count).  THE RULE, with m the number of allowed rows, taken in ascending row order:
+ *   Mean.  center = 1: mean[j] = (the f64 sum of double(x[j]) over the allowed rows) / m.  The sum is taken in 1024 segments of ceil(m / 1024)
+ *   rows each (the last ones short or empty), ascending inside a segment, the segments added in ascending order.  center = 0: mean[j] = 0.
+ *   Covariance.  cov[i][j] = (sum over the allowed rows of (double(x[i]) - mean[i]) * (double(x[j]) - mean[j])) / (m - center), all in f64.
+ *   The rows are split into R segments of seg_rows rows (vdb_pca_plan: a function of (m, dim) alone).  A segment's partial sum is
+ *   accumulated by the f64 matrix instruction in ascending row order, four rows per instruction; the R partial sums are added in ascending
+ *   segment order by a separate reduction; no float atomics.  Only the 64 x 64 blocks on or above the diagonal are computed, and cov[j][i] is
+ *   a copy of cov[i][j]: the matrix is symmetric bit for bit.  Two calls on the same (table, mask) return the same bits.  NaN and infinite
+ *   elements propagate by IEEE arithmetic; nothing more is promised about them.
+ *   Projection.  out[r][c] = f32(sum over j of (double(x_r[j]) - mean[j]) * double(W[c][j])): an f64 accumulation in ascending j, four
+ *   dimensions per instruction, rounded once.  W [n_comp][dim] is f32, mean [dim] is f64 or NULL for zeros.  The source is the allowed rows
+ *   of an index (with a mask the output is compact, in ascending allowed-row order) or a caller's array of n f32 vectors
+ *   (vdb_project_vectors: queries go through the same kernel as the table).
+ * Refused, with outputs and counters untouched: a u8 index; m < 2 for the covariance with center = 1, m < 1 with center = 0; dim > 2048; a
+ * stale or foreign mask; n_comp = 0, n_comp > dim, n_comp > 1024; w_dim != dim.  A projection of no rows succeeds and writes nothing.
+ * Outputs: out_mean [dim] f64, out_cov [dim][dim] f64, *out_m = m; out [m][n_comp] f32.  _device: the arrays in device memory on the index's
+ * GPU (f64 arrays 8-byte, f32 arrays 4-byte aligned); `stream` is synchronised first and the call returns synchronised.
+ * vdb_project_vectors / _device take no index: `device` names the GPU.
+ * vdb_pca_plan (host only): the argument check (project = 0: of a covariance; 1: of a projection onto n_comp x w_dim components) and the
+ * layout -- dim padded to blocks of 64, b (b + 1) / 2 blocks, R segments of seg_rows rows, scratch bytes.  vdb_pca_segment: the positions
+ * [first, first + len) of covariance segment s < R.
+ * vdb_get_stat: "pca_cov_calls", "pca_cov_rows", "pca_project_calls", "pca_project_rows" (calls that succeeded / the rows they read).
+ * vdb_prof_get: "pca_mean", "pca_cov" (the matrix kernel), "pca_cov_reduce", "pca_project". */
+int vdb_pca_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m, int center, int project, uint64_t n_comp, uint64_t w_dim,
+                 uint64_t *out_dim_pad, uint64_t *out_blocks, uint64_t *out_segments, uint64_t *out_seg_rows, uint64_t *out_scratch_bytes);
+int vdb_pca_segment(uint64_t m, uint64_t dim, uint64_t s, uint64_t *out_first, uint64_t *out_len);
+int vdb_flat_covariance(vdb_index *idx, int center, const vdb_mask *mask /* NULL: all rows */, double *out_mean, double *out_cov, uint64_t *out_m);
+int vdb_flat_covariance_device(vdb_index *idx, int center, const vdb_mask *mask, void *d_out_mean, void *d_out_cov, uint64_t *out_m, void *stream);
+int vdb_flat_project(vdb_index *idx, const vdb_mask *mask, const float *W, uint64_t n_comp, uint64_t w_dim, const double *mean /* NULL: zeros */,
+                     float *out);
+int vdb_flat_project_device(vdb_index *idx, const vdb_mask *mask, const void *d_W, uint64_t n_comp, uint64_t w_dim, const void *d_mean, void *d_out,
+                            void *stream);
+int vdb_project_vectors(const float *vecs, uint64_t n, uint64_t dim, const float *W, uint64_t n_comp, const double *mean, float *out, int device);
+int vdb_project_vectors_device(const void *d_vecs, uint64_t n, uint64_t dim, const void *d_W, uint64_t n_comp, const void *d_mean, void *d_out, int device,
+                               void *stream);
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids);
 /* ---- near-duplicate grouping: a range self-join over the table's own rows and the connected components of its pairs ---------------------
  * "Which rows are copies, or near copies, of each other?"  (csrc/dup_plan.hpp, csrc/flat_dups.hip, csrc/k_components.hip;
@@ -1172,6 +1211,8 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *                        "flat_dbscan_pairs": the non-self pairs they saw,
  *   "flat_knn_graph_calls"  vdb_flat_knn_graph / vdb_flat_outliers (+ _device) calls that succeeded; "flat_knn_graph_chunks": the search
  *                        calls under them,
+ *   "pca_cov_calls"      vdb_flat_covariance / _device calls that succeeded; "pca_cov_rows": the rows they read; "pca_project_calls" /
+ *                        "pca_project_rows": the same of vdb_flat_project / _device,
  *   "update_calls"       vdb_index_update_rows / _device calls that changed rows (m > 0, not refused); "update_rows": the rows they rewrote,
  *   "fetch_calls"        vdb_index_get_rows* calls that fetched rows (m > 0, not refused); "fetch_rows": the rows they returned;
  *                        "fetch_chunks": their gather launches; "fetch_direct": the calls answered by one plain copy,

@@ -377,6 +377,24 @@ public:
                                &p.scratch_bytes));
         return p;
     }
+    // PCA of the rows (vdb_flat_covariance): the f64 column means [dim] (zeros when !center) and covariance matrix [dim][dim] of the
+    // allowed rows (mask null: every row), and their number
+    struct Covariance {
+        std::vector<double> mean, cov;
+        uint64_t rows;
+    };
+    Covariance covariance(bool center = true, const Mask *mask = nullptr) const {
+        Covariance c{std::vector<double>(dim()), std::vector<double>(dim() * dim()), 0};
+        check(vdb_flat_covariance(h_, center ? 1 : 0, mask ? mask->handle() : nullptr, c.mean.data(), c.cov.data(), &c.rows));
+        return c;
+    }
+    // the allowed rows, ascending, less `mean` (null: zeros) projected onto W [n_comp][dim] (vdb_flat_project): f32 [rows][n_comp]
+    std::vector<float> project(const float *W, uint64_t n_comp, const double *mean = nullptr, const Mask *mask = nullptr) const {
+        std::vector<float> out((mask ? mask->count() : len()) * n_comp + 1);
+        check(vdb_flat_project(h_, mask ? mask->handle() : nullptr, W, n_comp, dim(), mean, out.data()));
+        out.pop_back();
+        return out;
+    }
     // diversified k-NN, maximal marginal relevance (vdb_flat_knn_mmr): per query, from the first min(fetch_k, allowed rows) pairs of
     // knn_batch, the nearest and then greedily the pair with the smallest lambda * d(query, row) - (1 - lambda) * min over the selected rows
     // of d(row, selected); the pairs come in SELECTION order.  masks empty: over all rows; otherwise query q under *masks[mask_of[q]]

@@ -1194,6 +1194,159 @@ int vdb_lof_lists_device(vdb_index *idx, const void *d_nbr, const void *d_nd, co
     });
     VDB_API_END
 }
+// PCA of the rows: mean and covariance in f64, projection (Index::flat_covariance_device / flat_project_device, pca_plan.hpp, flat_pca.hip)
+int vdb_pca_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m, int center, int project, uint64_t n_comp, uint64_t w_dim,
+                 uint64_t *out_dim_pad, uint64_t *out_blocks, uint64_t *out_segments, uint64_t *out_seg_rows, uint64_t *out_scratch_bytes) {
+    VDB_API_BEGIN
+    const std::string bad = project ? pca_check_project(dim, elem_u8 != 0, n_comp, w_dim) : pca_check_cov(n_rows, dim, elem_u8 != 0, masked != 0, m, center != 0);
+    VDB_REQUIRE(bad.empty(), bad);
+    const PcaPlan p = pca_plan(std::max<uint64_t>(m, 1), dim);
+    if (out_dim_pad) *out_dim_pad = p.dim_pad;
+    if (out_blocks) *out_blocks = p.blocks;
+    if (out_segments) *out_segments = p.segments;
+    if (out_seg_rows) *out_seg_rows = p.seg_rows;
+    if (out_scratch_bytes) *out_scratch_bytes = p.scratch_bytes;
+    VDB_API_END
+}
+int vdb_pca_segment(uint64_t m, uint64_t dim, uint64_t s, uint64_t *out_first, uint64_t *out_len) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(m >= 1 && m < (1ull << 32) && dim >= 1 && dim <= PCA_MAX_DIM, "pca segment: m must be in 1 .. 2^32 - 1, dim in 1 .. 2048");
+    const PcaPlan p = pca_plan(m, dim);
+    VDB_REQUIRE(s < p.segments, "pca segment: s must be below " + std::to_string(p.segments));
+    uint64_t first, len;
+    pca_segment(p, m, s, first, len);
+    if (out_first) *out_first = first;
+    if (out_len) *out_len = len;
+    VDB_API_END
+}
+// what the forms refuse before a workspace is taken -> the mask as a RowMask (nullptr: all rows); *m = the allowed rows
+static const RowMask *pca_check(const Index &ix, const vdb_mask *mask, uint64_t *m, bool cov, bool center, uint64_t n_comp, uint64_t w_dim) {
+    if (mask) ix.check_mask(mask->m);
+    *m = mask ? mask->m.m : ix.n;
+    const std::string bad = cov ? pca_check_cov(ix.n, ix.dim, ix.elem_u8, mask != nullptr, *m, center) : pca_check_project(ix.dim, ix.elem_u8, n_comp, w_dim);
+    VDB_REQUIRE(bad.empty(), bad);
+    return mask ? &mask->m : nullptr;
+}
+int vdb_flat_covariance(vdb_index *idx, int center, const vdb_mask *mask, double *out_mean, double *out_cov, uint64_t *out_m) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    uint64_t m = 0;
+    const RowMask *rm = pca_check(ix, mask, &m, true, center != 0, 0, 0);
+    VDB_REQUIRE(out_mean && out_cov && out_m, "covariance: null argument");
+    ix.use_device();
+    WsLease ws(ix);
+    DevBuf d_mean, d_cov;
+    d_mean.reserve(ix.dim * sizeof(double));
+    d_cov.reserve(ix.dim * ix.dim * sizeof(double));
+    run_synced(ix, *ws, [&] {
+        ix.flat_covariance_device(*ws, center != 0, rm, d_mean.as<double>(), d_cov.as<double>(), &m);
+        VDB_HIP(hipMemcpyAsync(out_mean, d_mean.p, ix.dim * sizeof(double), hipMemcpyDeviceToHost, ws->stream));
+        VDB_HIP(hipMemcpyAsync(out_cov, d_cov.p, ix.dim * ix.dim * sizeof(double), hipMemcpyDeviceToHost, ws->stream));
+        VDB_SYNC(ws->stream);
+    });
+    *out_m = m;
+    VDB_API_END
+}
+int vdb_flat_covariance_device(vdb_index *idx, int center, const vdb_mask *mask, void *d_out_mean, void *d_out_cov, uint64_t *out_m, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    uint64_t m = 0;
+    const RowMask *rm = pca_check(ix, mask, &m, true, center != 0, 0, 0);
+    VDB_REQUIRE(d_out_mean && d_out_cov && out_m, "covariance: null argument");
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_out_mean) % 8 == 0 && reinterpret_cast<uintptr_t>(d_out_cov) % 8 == 0,
+                "covariance: the device outputs must be 8-byte aligned");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever last used the outputs on the caller's stream
+    run_synced(ix, *ws, [&] { ix.flat_covariance_device(*ws, center != 0, rm, static_cast<double *>(d_out_mean), static_cast<double *>(d_out_cov), &m); });
+    *out_m = m;
+    VDB_API_END
+}
+int vdb_flat_project(vdb_index *idx, const vdb_mask *mask, const float *W, uint64_t n_comp, uint64_t w_dim, const double *mean, float *out) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    uint64_t m = 0;
+    const RowMask *rm = pca_check(ix, mask, &m, false, false, n_comp, w_dim);
+    VDB_REQUIRE(W && (m == 0 || out), "project: null argument");
+    ix.use_device();
+    WsLease ws(ix);
+    DevBuf d_W, d_mean, d_out;
+    d_W.reserve(n_comp * ix.dim * sizeof(float));
+    d_mean.reserve(ix.dim * sizeof(double));
+    d_out.reserve(std::max<uint64_t>(m * n_comp, 1) * sizeof(float));
+    run_synced(ix, *ws, [&] {
+        VDB_HIP(hipMemcpyAsync(d_W.p, W, n_comp * ix.dim * sizeof(float), hipMemcpyHostToDevice, ws->stream));
+        if (mean) VDB_HIP(hipMemcpyAsync(d_mean.p, mean, ix.dim * sizeof(double), hipMemcpyHostToDevice, ws->stream));
+        ix.flat_project_device(*ws, rm, d_W.as<float>(), n_comp, mean ? d_mean.as<double>() : nullptr, d_out.as<float>());
+        if (m) VDB_HIP(hipMemcpyAsync(out, d_out.p, m * n_comp * sizeof(float), hipMemcpyDeviceToHost, ws->stream));
+        VDB_SYNC(ws->stream);
+    });
+    VDB_API_END
+}
+int vdb_flat_project_device(vdb_index *idx, const vdb_mask *mask, const void *d_W, uint64_t n_comp, uint64_t w_dim, const void *d_mean, void *d_out,
+                            void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    uint64_t m = 0;
+    const RowMask *rm = pca_check(ix, mask, &m, false, false, n_comp, w_dim);
+    VDB_REQUIRE(d_W && (m == 0 || d_out), "project: null argument");
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_W) % 4 == 0 && reinterpret_cast<uintptr_t>(d_out) % 4 == 0 && reinterpret_cast<uintptr_t>(d_mean) % 8 == 0,
+                "project: the device arrays must be 4-byte aligned (the mean: 8)");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the components on the caller's stream
+    run_synced(ix, *ws, [&] {
+        ix.flat_project_device(*ws, rm, static_cast<const float *>(d_W), n_comp, static_cast<const double *>(d_mean), static_cast<float *>(d_out));
+    });
+    VDB_API_END
+}
+// a caller's vectors through the projection kernel: no index, the device named
+static void project_vectors_check(const void *vecs, uint64_t n, uint64_t dim, const void *W, uint64_t n_comp, const void *out) {
+    const std::string bad = pca_check_project(dim, false, n_comp, dim);
+    VDB_REQUIRE(bad.empty(), bad);
+    VDB_REQUIRE(n < (1ull << 32), "project vectors: too many vectors for one call");
+    VDB_REQUIRE(W && (n == 0 || (vecs && out)), "project vectors: null argument");
+    require_gpu();
+}
+int vdb_project_vectors(const float *vecs, uint64_t n, uint64_t dim, const float *W, uint64_t n_comp, const double *mean, float *out, int device) {
+    VDB_API_BEGIN
+    project_vectors_check(vecs, n, dim, W, n_comp, out);
+    VDB_HIP(hipSetDevice(device));
+    if (n) {
+        DevBuf d_vecs, d_W, d_mean, d_out;
+        d_vecs.reserve(n * dim * sizeof(float));
+        d_W.reserve(n_comp * dim * sizeof(float));
+        d_mean.reserve(dim * sizeof(double));
+        d_out.reserve(n * n_comp * sizeof(float));
+        VDB_HIP(hipMemcpy(d_vecs.p, vecs, n * dim * sizeof(float), hipMemcpyHostToDevice));
+        VDB_HIP(hipMemcpy(d_W.p, W, n_comp * dim * sizeof(float), hipMemcpyHostToDevice));
+        if (mean) VDB_HIP(hipMemcpy(d_mean.p, mean, dim * sizeof(double), hipMemcpyHostToDevice));
+        launch_pca_project(d_vecs.as<float>(), nullptr, n, (uint32_t)dim, d_W.as<float>(), (uint32_t)n_comp, mean ? d_mean.as<double>() : nullptr,
+                           d_out.as<float>(), nullptr);
+        VDB_SYNC(nullptr);
+        VDB_HIP(hipMemcpy(out, d_out.p, n * n_comp * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    VDB_API_END
+}
+int vdb_project_vectors_device(const void *d_vecs, uint64_t n, uint64_t dim, const void *d_W, uint64_t n_comp, const void *d_mean, void *d_out, int device,
+                               void *stream) {
+    VDB_API_BEGIN
+    project_vectors_check(d_vecs, n, dim, d_W, n_comp, d_out);
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_vecs) % 4 == 0 && reinterpret_cast<uintptr_t>(d_W) % 4 == 0 && reinterpret_cast<uintptr_t>(d_out) % 4 == 0 &&
+                    reinterpret_cast<uintptr_t>(d_mean) % 8 == 0,
+                "project vectors: the device arrays must be 4-byte aligned (the mean: 8)");
+    VDB_HIP(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n)
+        launch_pca_project(static_cast<const float *>(d_vecs), nullptr, n, (uint32_t)dim, static_cast<const float *>(d_W), (uint32_t)n_comp,
+                           static_cast<const double *>(d_mean), static_cast<float *>(d_out), s);
+    VDB_SYNC(s);
+    VDB_API_END
+}
 // k-means over the rows (Index::flat_kmeans_device / kmeans_assign_device, kmeans_plan.hpp, flat_kmeans.hip)
 int vdb_kmeans_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m, uint64_t c, int lloyd, int cosine, float xn, float cn,
                     float d_best, uint64_t *out_row_tiles, uint64_t *out_cent_tiles, uint64_t *out_k_blocks, uint64_t *out_order_passes,
@@ -2496,6 +2649,14 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.knn_graph_calls.load();
     else if (n == "flat_knn_graph_chunks")
         *out = idx->ix.knn_graph_chunks.load();
+    else if (n == "pca_cov_calls")  // vdb_flat_covariance / vdb_flat_project (+ _device): calls that succeeded | the rows they read
+        *out = idx->ix.pca_cov_calls.load();
+    else if (n == "pca_cov_rows")
+        *out = idx->ix.pca_cov_rows.load();
+    else if (n == "pca_project_calls")
+        *out = idx->ix.pca_project_calls.load();
+    else if (n == "pca_project_rows")
+        *out = idx->ix.pca_project_rows.load();
     else if (n == "flat_grouped_calls")  // grouped k-NN: calls | queries | rounds run, summed over calls | queries whose last list was their whole allowed set
         *out = idx->ix.grouped_calls.load();
     else if (n == "flat_grouped_queries")

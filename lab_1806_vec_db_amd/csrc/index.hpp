@@ -839,6 +839,14 @@ struct Index {
     void lof_lists_device(Workspace &ws, const uint32_t *d_nbr, const float *d_nd, const uint32_t *d_cnt, uint64_t m, uint64_t k, float *d_kdist,
                           float *d_lrd, float *d_lof);
     std::atomic<uint64_t> knn_graph_calls{0}, knn_graph_chunks{0};  // graph walks that succeeded (either entry) / the search calls under them
+    // PCA of the rows (flat_pca.hip, k_pca.hip, pca_plan.hpp -- the rule is stated in include/vdbhip.h; docs/DESIGN_flat.md 4.1ai).  The rows
+    // are the mask's allowed rows in ascending order (nullptr: all), m of them.  flat_covariance_device: d_mean f64 [dim] (zeros when
+    // !center), d_cov f64 [dim][dim], *out_m = m.  flat_project_device: d_out f32 [m][n_comp] = the rows, less d_mean f64 [dim] (nullptr:
+    // zeros), times d_W f32 [n_comp][dim] transposed.  Both on the device, read-side and re-entrant; arguments and mask are checked here
+    // before anything is written; counters advance on success; return synchronised.
+    void flat_covariance_device(Workspace &ws, bool center, const RowMask *mask, double *d_mean, double *d_cov, uint64_t *out_m);
+    void flat_project_device(Workspace &ws, const RowMask *mask, const float *d_W, uint64_t n_comp, const double *d_mean, float *d_out);
+    std::atomic<uint64_t> pca_cov_calls{0}, pca_cov_rows{0}, pca_project_calls{0}, pca_project_rows{0};
     // k-means over the rows (flat_kmeans.hip, k_kmeans.hip, kmeans_plan.hpp; docs/DESIGN_flat.md 4.1ad).  The rows clustered are the mask's
     // allowed rows (nullptr: all); d_assign [n] u32 and d_best [n] f32 are indexed by row, KM_LABEL_NONE / NaN for a row outside the mask.
     // kmeans_assign_device: the assignment step alone against d_cent [c][dim] on the device -- row i to the centroid with the smallest

@@ -18,6 +18,7 @@
 #include "mask_sets.hpp"
 #include "mmr_plan.hpp"
 #include "outlier_plan.hpp"
+#include "pca_plan.hpp"
 #include "vote_plan.hpp"
 
 namespace vdb {
@@ -537,6 +538,18 @@ void launch_kmeans_update(const float *X, const uint32_t *ids, uint32_t dim, uin
                           hipStream_t s);
 void launch_kmeans_reduce(const uint32_t *assign, const uint32_t *prev, const float *best, const uint32_t *ids, uint64_t m, double *partial,
                           uint64_t *changed, double *inertia, hipStream_t s);
+// The PCA of the rows X [..][dim] of an f32 index, all sums in f64 (k_pca.hip, pca_plan.hpp; p = pca_plan(m, dim)).  Positions 0 .. m are the
+// rows ids[0 .. m) (nullptr: position = row).  mean: partial [1024][dim_pad] = the column sums per mean segment, mean [dim_pad] = their sum in
+// segment order / m (zero past dim).  syrk: partial [R][blocks][64][64] = per row segment and block with bi <= bj the sum of
+// (x[i] - mean[i]) (x[j] - mean[j]) on the f64 matrix pipe (tiles below the diagonal of a diagonal block are not written).  cov_reduce:
+// cov [dim][dim] = the partials added in segment order / denom, cov[j][i] copied from cov[i][j].  project: out [n][n_comp] =
+// f32(sum over j of (x[j] - mean[j]) W[c][j]) for the n positions of X (mean nullptr: zeros); W [n_comp][dim].
+void launch_pca_mean(const float *X, const uint32_t *ids, uint64_t m, uint32_t dim, const PcaPlan &p, double *partial, double *mean, hipStream_t s);
+void launch_pca_syrk(const float *X, const uint32_t *ids, uint64_t m, uint32_t dim, const PcaPlan &p, const double *mean, double *partial,
+                     hipStream_t s);
+void launch_pca_cov_reduce(const double *partial, uint32_t dim, const PcaPlan &p, double denom, double *cov, hipStream_t s);
+void launch_pca_project(const float *X, const uint32_t *ids, uint64_t n, uint32_t dim, const float *W, uint32_t n_comp, const double *mean, float *out,
+                        hipStream_t s);
 // The capped walk of the grouped k-NN (k_group.hip, grouped_plan.hpp): query b's list ids / dists [b][0 .. min(counts[b], ld)) walked in the order
 // given, at most g rows kept per value of `labels` (u32 per LOCAL row = id - id_offset; nullptr: a column never written; a row without a
 // label is always kept), the first k kept pairs to row slot_q[b] (nullptr: b) of out_idx / out_dist [..][k] with zeros behind them, their

@@ -40,6 +40,20 @@ def _ptr(a, t):
     return a.ctypes.data_as(t) if a is not None else None
 
 
+def project_vectors(vecs, W, mean=None, device: int = 0) -> np.ndarray:
+    """vectors [n][dim] projected onto the components W [n_comp][dim] on GPU `device` (vdb_project_vectors; GpuIndex.project states the
+    arithmetic): float32 [n][n_comp].  `mean`: float64 [dim] or None for zeros."""
+    W, mean = GpuIndex._components(W, mean)
+    v = np.ascontiguousarray(vecs, dtype=np.float32)
+    v = v.reshape(1, -1) if v.ndim == 1 else v
+    if v.shape[1] != W.shape[1]:
+        raise L.VdbError(f"project: component dimension mismatch: vectors have dim {v.shape[1]}, got {W.shape[1]}")
+    out = np.zeros((v.shape[0], W.shape[0]), dtype=np.float32)
+    L.check(L.load().vdb_project_vectors(_ptr(v, L.f32p), v.shape[0], v.shape[1], _ptr(W, L.f32p), W.shape[0], _ptr(mean, L.f64p), _ptr(out, L.f32p),
+                                         int(device)))
+    return out
+
+
 def read_range(lib, h, nq: int):
     """(lims, idx, dist) of a vdb_range result object on the host; releases the object"""
     try:
@@ -757,6 +771,84 @@ class GpuIndex:
                                           GpuIndex._graph_k(k), int(chunk), C.byref(chunks), C.byref(last), C.byref(kk), C.byref(group),
                                           C.byref(graph), C.byref(scratch)))
         return int(chunks.value), int(last.value), int(kk.value), int(group.value), int(graph.value), int(scratch.value)
+
+    def covariance(self, center: bool = True, mask: RowMask | None = None):
+        """Column means and covariance matrix of the index's rows, or the mask's (vdb_flat_covariance): (mean float64 [dim], cov float64
+        [dim, dim], m).  mean[j] is the f64 sum of the column over the m rows / m (zeros when not `center`); cov[i][j] the f64 sum of
+        (x[i] - mean[i]) (x[j] - mean[j]) / (m - center).  An f32 widens exactly and the f64 matrix pipe multiplies and adds in f64, so only
+        the summation order rounds, and that order is a function of (m, dim): two calls return the same bits, and cov equals cov.T bit
+        for bit.  A u8 index, fewer than 2 rows (1 without centring), dim > 2048 and a stale or foreign mask raise VdbError."""
+        d = self.dim
+        mean = np.zeros(d, dtype=np.float64)
+        cov = np.zeros((d, d), dtype=np.float64)
+        m = C.c_uint64()
+        L.check(self._lib.vdb_flat_covariance(self._h, int(bool(center)), None if mask is None else mask._h, _ptr(mean, L.f64p), _ptr(cov, L.f64p),
+                                              C.byref(m)))
+        return mean, cov, int(m.value)
+
+    def covariance_device(self, out_mean_ptr: int, out_cov_ptr: int, center: bool = True, mask: RowMask | None = None, stream: int = 0) -> int:
+        """the same with mean f64 [dim] and cov f64 [dim][dim] written to device memory, 8-byte aligned (vdb_flat_covariance_device);
+        returns m, synchronised"""
+        m = C.c_uint64()
+        L.check(self._lib.vdb_flat_covariance_device(self._h, int(bool(center)), None if mask is None else mask._h, L.vp(out_mean_ptr),
+                                                     L.vp(out_cov_ptr), C.byref(m), L.vp(stream)))
+        return int(m.value)
+
+    @staticmethod
+    def _components(W, mean, dim=None):
+        """(W float32 [n_comp][w_dim], mean float64 [w_dim] or None) as the projection calls take them"""
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        W = W.reshape(1, -1) if W.ndim == 1 else W
+        if mean is not None:
+            mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+            if mean.size != (W.shape[1] if dim is None else dim):
+                raise L.VdbError(f"project: the mean has {mean.size} entries, the vectors {W.shape[1] if dim is None else dim}")
+        return W, mean
+
+    def project(self, W, mean=None, mask: RowMask | None = None) -> np.ndarray:
+        """The index's rows, or the mask's in ascending row order, projected onto the components W [n_comp][dim] (vdb_flat_project): float32
+        [m][n_comp], out[r][c] = f32(sum over j of (x_r[j] - mean[j]) W[c][j]), accumulated in f64 in ascending j and rounded once.
+        `mean`: float64 [dim] or None for zeros.  A u8 index, no components, more than min(dim, 1024) of them, components of another dim
+        and a stale or foreign mask raise VdbError."""
+        W, mean = self._components(W, mean, self.dim)
+        m = len(self) if mask is None else len(mask)
+        out = np.zeros((m, W.shape[0]), dtype=np.float32)
+        L.check(self._lib.vdb_flat_project(self._h, None if mask is None else mask._h, _ptr(W, L.f32p), W.shape[0], W.shape[1], _ptr(mean, L.f64p),
+                                           _ptr(out, L.f32p)))
+        return out
+
+    def project_device(self, W_ptr: int, n_comp: int, out_ptr: int, mean_ptr: int = 0, mask: RowMask | None = None, stream: int = 0):
+        """the same on device memory (vdb_flat_project_device): W f32 [n_comp][dim] and mean f64 [dim] (0: zeros) in, out f32 [m][n_comp],
+        4-byte aligned (the mean: 8); returns synchronised"""
+        L.check(self._lib.vdb_flat_project_device(self._h, None if mask is None else mask._h, L.vp(W_ptr), int(n_comp), self.dim,
+                                                  L.vp(mean_ptr) if mean_ptr else None, L.vp(out_ptr), L.vp(stream)))
+
+    def project_vectors(self, vecs, W, mean=None) -> np.ndarray:
+        """A caller's vectors [n][dim] through the same kernel on the index's GPU (vdb_project_vectors): float32 [n][n_comp], the same bits
+        `project` gives for the same vectors stored as rows.  What queries need before they search a table made by VecDB.reduce."""
+        return project_vectors(vecs, W, mean, self.device)
+
+    @staticmethod
+    def pca_plan(n_rows: int, dim: int, m_allowed: int | None = None, elem_u8: bool = False, center: bool = True, n_comp: int | None = None,
+                 w_dim: int | None = None):
+        """(dim_pad, blocks, segments, seg_rows, scratch_bytes) of a covariance call -- or, with n_comp, the check of a projection onto
+        n_comp x w_dim components (w_dim None: dim) -- (vdb_pca_plan; host only, no GPU): dim padded to blocks of 64, the b (b + 1) / 2
+        blocks on or above the diagonal, the R row segments whose partial sums are added in order, the rows of each, and the device bytes
+        held besides the outputs.  Raises VdbError for what the call refuses by its arguments."""
+        masked = m_allowed is not None
+        project = n_comp is not None
+        o = [C.c_uint64() for _ in range(5)]
+        L.check(L.load().vdb_pca_plan(int(n_rows), int(dim), int(bool(elem_u8)), int(masked), int(m_allowed if masked else n_rows), int(bool(center)),
+                                      int(project), int(n_comp or 0), int(dim if w_dim is None else w_dim), *(C.byref(x) for x in o)))
+        return tuple(int(x.value) for x in o)
+
+    @staticmethod
+    def pca_segment(m: int, dim: int, s: int):
+        """(first, len): covariance segment s of a call over m rows of `dim` dimensions covers positions [first, first + len) of the
+        ascending allowed rows (vdb_pca_segment; host only)"""
+        first, ln = C.c_uint64(), C.c_uint64()
+        L.check(L.load().vdb_pca_segment(int(m), int(dim), int(s), C.byref(first), C.byref(ln)))
+        return int(first.value), int(ln.value)
 
     def kmeans(self, c: int, max_iter: int = 20, tol: float = 1e-4, seed: int = 0, init=None, mask: RowMask | None = None):
         """k-means over the index's rows, or the mask's (vdb_flat_kmeans): (centroids f32 [c][dim], assign uint32 [len], sizes uint64 [c],

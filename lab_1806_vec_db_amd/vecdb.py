@@ -51,13 +51,14 @@ their rows with ONE pass over the field's label column whatever the number of va
 from __future__ import annotations
 
 import collections
+import dataclasses
 import threading
 from contextlib import contextmanager
 
 import numpy as np
 
 from ._lib import VdbError
-from .index import FUSE_MAX_FETCH, LIKE_MAX_EXAMPLES, MMR_MAX_FETCH, ROW_NONE, VOTE_MAX_K, VOTE_MODES, GpuIndex, RowMask, parse_dist
+from .index import FUSE_MAX_FETCH, LIKE_MAX_EXAMPLES, MMR_MAX_FETCH, ROW_NONE, VOTE_MAX_K, VOTE_MODES, GpuIndex, RowMask, parse_dist, project_vectors
 from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, fuse_groups, filter_patterns, has_predicates, is_expression, stale_filters, vote_values
 from .labels import matches as value_matches
 
@@ -77,6 +78,33 @@ PARTITION_MIN: int | None = 64
 # (profiles/label_lookup_1M.json; docs/DESIGN_flat.md 4.1aa), the lookup won at every group size from 2 to 4096, by 4.5 x to 43 x, so the
 # value is that floor.
 LOOKUP_MIN: int | None = 64
+
+
+@dataclasses.dataclass
+class PcaModel:
+    """What VecDB.fit_pca learns from a table's rows and VecDB.transform / reduce apply"""
+    mean: np.ndarray                      # float64 [dim]: the column means (zeros when not centred)
+    components: np.ndarray                # float32 [n_components][dim]: unit eigenvectors of the covariance, largest eigenvalue first
+    explained_variance: np.ndarray        # float64 [n_components]: their eigenvalues
+    explained_variance_ratio: np.ndarray  # float64 [n_components]: the same over the trace of the covariance
+    n_rows: int                           # rows the model was fitted on
+    center: bool
+
+
+def pca_from_covariance(mean, cov, n_rows: int, n_components: int, center: bool = True) -> PcaModel:
+    """The PcaModel of a covariance matrix (GpuIndex.covariance's outputs): numpy.linalg.eigh on the dim x dim float64 matrix, on the
+    host -- O(dim^3), whatever the row count --, eigenvalues descending, every component's sign fixed so that its entry of largest
+    magnitude is positive (ties: the lowest index), components rounded to float32."""
+    dim = cov.shape[0]
+    n = int(n_components)
+    if not 1 <= n <= min(dim, 1024):
+        raise ValueError(f"n_components must be in 1 .. min(dim, 1024) = {min(dim, 1024)}")
+    w, v = np.linalg.eigh(cov)
+    w, comp = w[::-1], v[:, ::-1].T  # ascending -> descending; components as rows
+    comp = comp[:n].copy()
+    big = np.argmax(np.abs(comp), axis=1)  # (the first maximum: the lowest index)
+    comp[comp[np.arange(n), big] < 0] *= -1.0
+    return PcaModel(np.asarray(mean, dtype=np.float64), comp.astype(np.float32), w[:n].copy(), w[:n] / w.sum(), int(n_rows), bool(center))
 
 
 def _differ(a, b) -> bool:
@@ -1473,6 +1501,57 @@ class VecDB:
             vecs = t.index.get_rows(picked.astype(np.uint64)) if with_vectors and picked.size else None
             return [(dict(t.metadata[int(r)]), float(scores[o])) + ((vecs[j].copy(),) if vecs is not None else ())
                     for j, (r, o) in enumerate(zip(picked.tolist(), order.tolist()))]
+
+    @staticmethod
+    def _fit_pca_rows(t: _Table, n_components: int, mk, center: bool) -> PcaModel:
+        """UNDER THE READ LOCK: the model of the rows of `mk` (None: every row)"""
+        mean, cov, m = t.index.covariance(center, mk)
+        return pca_from_covariance(mean, cov, m, n_components, center)
+
+    def fit_pca(self, key: str, n_components: int, filter=None, center: bool = True) -> PcaModel:
+        """Principal component analysis of the rows that match `filter` (every row without one): the PcaModel of their first
+        `n_components` principal axes.  ONE GpuIndex.covariance call under the read lock and the filter's cached mask -- means and the
+        dim x dim covariance matrix in f64 on the device, one read of the rows per block column --, then numpy.linalg.eigh on that matrix
+        on the host: O(dim^3), independent of the row count (the covariance itself costs rows x dim^2).
+        Eigenvalues descending; a component's entry of largest magnitude is positive (ties: the lowest index); components are float32.
+        `center=False` analyses the second moments about the origin instead (the mean of the model is zero)."""
+        t = self._t(key)
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.read():
+            return self._fit_pca_rows(t, n_components, None if filter is None else t.mask_for(filter), center)
+
+    def transform(self, model: PcaModel, vectors) -> np.ndarray:
+        """`vectors` [n][dim] (or one vector) in the coordinates of `model`: float32 [n][n_components] = (vectors - model.mean) times the
+        components, by the kernel that projects a table's rows (GpuIndex.project_vectors), so a query and a stored row with the same
+        values get the same bits.  What a query needs before it searches a table made by reduce."""
+        return project_vectors(vectors, model.components, model.mean if model.center else None, self.device)
+
+    def reduce(self, key: str, new_key: str, model_or_n, filter=None, center: bool = True) -> PcaModel:
+        """Creates the table `new_key` -- dim n_components, the metric of `key` -- from the rows of `key` that match `filter` (every row
+        without one), projected onto a PcaModel: `model_or_n` is a model (of fit_pca) or the number of components to fit on those rows
+        first.  The rows are projected on the device (ONE GpuIndex.project call under the filter's mask) and added with copies of their
+        metadata dicts, in ascending row order; the model is returned.  An existing `new_key` is refused.
+        CENTRING CHANGES COSINE GEOMETRY: the angle between two centred rows is not the angle between the rows.  On a cosine table
+        pass center=False (or a model fitted with it): the projection is then a linear map that keeps dot products as well as a map of
+        rank n_components can.  L2Sqr distances do not depend on the centre."""
+        t = self._t(key)
+        if self.contains_key(new_key):
+            raise RuntimeError(f"Table {new_key} already exists")
+        if filter is not None:
+            t.prepare([filter])
+        with t.lock.read():
+            mk = None if filter is None else t.mask_for(filter)
+            model = model_or_n if isinstance(model_or_n, PcaModel) else self._fit_pca_rows(t, int(model_or_n), mk, center)
+            out = t.index.project(model.components, model.mean if model.center else None, mk)
+            rows = range(len(t.metadata)) if mk is None else np.asarray(mk.rows()[1], dtype=np.int64).tolist()
+            meta = [dict(t.metadata[r]) for r in rows]
+            dist = _DIST_STR[t.index.dist]
+        if not self.create_table_if_not_exists(new_key, out.shape[1], dist):
+            raise RuntimeError(f"Table {new_key} already exists")
+        if out.shape[0]:
+            self.batch_add(new_key, out, meta)
+        return model
 
     def delete_duplicates(self, key: str, radius: float, filter=None, limit: int | None = None) -> int:
         """Removes every row of a find_duplicates group except its representative (the lowest row); returns the number removed.  ONE
