@@ -562,6 +562,46 @@ int vdb_flat_project_device(vdb_index *idx, const vdb_mask *mask, const void *d_
 int vdb_project_vectors(const float *vecs, uint64_t n, uint64_t dim, const float *W, uint64_t n_comp, const double *mean, float *out, int device);
 int vdb_project_vectors_device(const void *d_vecs, uint64_t n, uint64_t dim, const void *d_W, uint64_t n_comp, const void *d_mean, void *d_out, int device,
                                void *stream);
+/* ---- silhouette scoring of a labelled table (csrc/silhouette_plan.hpp, csrc/flat_silhouette.hip, csrc/k_silhouette.hip; docs/DESIGN_flat.md
+ * 4.1aj) ------------------------------------------------------------------------------------------------------------------------------------
+ * "How good is this clustering?"  The silhouette coefficient of every labelled row and its mean (scikit-learn's silhouette_samples /
+ * silhouette_score), from every pairwise distance among the scored rows in f64 on the matrix pipe (v_mfma_f64_16x16x4_f64).
+ * COST: m^2 * dim f64 multiply-adds for m scored rows; restrict the rows with a mask when the table is large.  THE RULE:
+ *   Inputs.  An f32 index, a label column `col`, an optional row mask, `flags`.
+ *   Scored rows.  A row is scored when the mask allows it (no mask: every row), it has a code in `col` (not VDB_LABEL_NONE) and it is
+ *   usable: every element is finite and, under Cosine, its norm is not zero.  m = the scored rows, C = the distinct codes among them.
+ *   Every other row is in no cluster: it contributes to no sum and its output is NaN.
+ *   Distance.  L2Sqr table: D = (|x_i|^2 + |x_j|^2) - 2 x_i.x_j, clamped at 0; d = sqrt(D) with VDB_SIL_EUCLIDEAN, d = D (the table's own
+ *   distance) without.  Cosine table: d = 1 - x_i.x_j / (|x_i| |x_j|), clamped at 0; the flag is refused.  All in f64 from the f32 elements:
+ *   widening is exact, so only summation rounds.  |x|^2: lane l of 64 adds the squares of elements l, l + 64, .. in ascending order, the 64
+ *   partial sums are added by a fixed butterfly.  x_i.x_j: the f64 matrix instruction, four dimensions per instruction, ascending.
+ *   Per row.  a(i) = the mean of d(i, j) over the OTHER scored rows of i's cluster; the pair (i, i) is excluded by position, not by value.
+ *   b(i) = the minimum over the other clusters c of the mean of d(i, j) over c.  s(i) = (b - a) / max(a, b); s(i) = 0 when i's cluster
+ *   has one member or max(a, b) = 0.  Each s(i) is rounded to f32 once.
+ *   Mean.  The f64 mean of the f64 s(i) over the scored rows in ascending (code, row) order: 256 segments of ceil(padded / 256) ordered
+ *   slots each, ascending inside a segment, the segments added by a fixed tree.
+ *   Determinism.  The rows are taken in ascending (code, row) order, every cluster's span padded to whole tiles of 64 slots; the sums of a
+ *   row run over a tile's 64 columns in a fixed order (a lane's four columns ascending, 16 lanes by a fixed butterfly) and over a cluster's
+ *   tiles in ascending order.  Tiling and segmenting depend on the cluster sizes and dim alone.  No float atomics.  Two calls on the same
+ *   table, column and mask return the same bits.
+ * Refused, with outputs and counters untouched: a u8 index; dim > 2048; 2^32 rows or more; flags other than VDB_SIL_EUCLIDEAN; the flag on a
+ * Cosine table; col > 15 or a column never written; a stale or foreign mask; C < 2 or C > m - 1 (scikit-learn's condition; the clusters
+ * are counted before any output is written).
+ * Outputs: out_s f32 [len] by row, NaN where the row is not scored; *out_mean f64; *out_m = m; *out_clusters = C.  _device: out_s and
+ * out_mean in device memory on the index's GPU (4- / 8-byte aligned); `stream` is synchronised first and the call returns synchronised.
+ * vdb_silhouette_plan (host only): the argument check -- the refusal texts of the calls -- and, for cluster sizes in ascending code
+ * order, the layout: padded slots, tiles of 64 (= row blocks = workgroups of the pair kernel), slices of 16 dimensions per tile pair,
+ * slots per mean segment, device scratch bytes, and out_first_tile [n_clusters + 1] (or NULL): cluster c owns tiles [first[c], first[c + 1]).
+ * vdb_get_stat: "silhouette_calls", "silhouette_rows" (calls that succeeded / the rows they scored).
+ * vdb_prof_get: "sil_prepare" (two brackets per call: norms and codes; gather and NaN fill), "sil_pairs" (the matrix kernel), "sil_finish". */
+#define VDB_SIL_EUCLIDEAN 1u
+int vdb_silhouette_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int cosine, uint32_t flags, uint64_t col, int col_live, int masked, uint64_t m_allowed,
+                        const uint64_t *sizes, uint64_t n_clusters, uint64_t *out_padded, uint64_t *out_tiles, uint64_t *out_slices,
+                        uint64_t *out_mean_slots, uint64_t *out_scratch_bytes, uint64_t *out_first_tile);
+int vdb_flat_silhouette(vdb_index *idx, uint64_t col, const vdb_mask *mask /* NULL: all rows */, uint32_t flags, float *out_s /* [len] */,
+                        double *out_mean, uint64_t *out_m, uint64_t *out_clusters);
+int vdb_flat_silhouette_device(vdb_index *idx, uint64_t col, const vdb_mask *mask, uint32_t flags, void *d_out_s, void *d_out_mean, uint64_t *out_m,
+                               uint64_t *out_clusters, void *stream);
 int vdb_mask_rows(const vdb_mask *m, uint64_t *out_bits, uint32_t *out_ids);
 /* ---- near-duplicate grouping: a range self-join over the table's own rows and the connected components of its pairs ---------------------
  * "Which rows are copies, or near copies, of each other?"  (csrc/dup_plan.hpp, csrc/flat_dups.hip, csrc/k_components.hip;
@@ -1213,6 +1253,7 @@ int vdb_flat_fallback_count(const vdb_index *idx, uint64_t *out);
  *                        calls under them,
  *   "pca_cov_calls"      vdb_flat_covariance / _device calls that succeeded; "pca_cov_rows": the rows they read; "pca_project_calls" /
  *                        "pca_project_rows": the same of vdb_flat_project / _device,
+ *   "silhouette_calls"   vdb_flat_silhouette / _device calls that succeeded; "silhouette_rows": the rows they scored,
  *   "update_calls"       vdb_index_update_rows / _device calls that changed rows (m > 0, not refused); "update_rows": the rows they rewrote,
  *   "fetch_calls"        vdb_index_get_rows* calls that fetched rows (m > 0, not refused); "fetch_rows": the rows they returned;
  *                        "fetch_chunks": their gather launches; "fetch_direct": the calls answered by one plain copy,

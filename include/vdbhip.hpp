@@ -395,6 +395,19 @@ public:
         out.pop_back();
         return out;
     }
+    // silhouette scoring of the rows labelled in column `col` (vdb_flat_silhouette): s f32 [len] by row (NaN: not scored), their f64 mean,
+    // the scored rows and their clusters; euclidean: the root of the L2Sqr distance (refused on a Cosine table).  Costs rows^2 x dim.
+    struct Silhouette {
+        std::vector<float> s;
+        double mean;
+        uint64_t rows, clusters;
+    };
+    Silhouette silhouette(uint64_t col, const Mask *mask = nullptr, bool euclidean = false) const {
+        Silhouette r{std::vector<float>(len() + 1), 0.0, 0, 0};
+        check(vdb_flat_silhouette(h_, col, mask ? mask->handle() : nullptr, euclidean ? VDB_SIL_EUCLIDEAN : 0u, r.s.data(), &r.mean, &r.rows, &r.clusters));
+        r.s.pop_back();
+        return r;
+    }
     // diversified k-NN, maximal marginal relevance (vdb_flat_knn_mmr): per query, from the first min(fetch_k, allowed rows) pairs of
     // knn_batch, the nearest and then greedily the pair with the smallest lambda * d(query, row) - (1 - lambda) * min over the selected rows
     // of d(row, selected); the pairs come in SELECTION order.  masks empty: over all rows; otherwise query q under *masks[mask_of[q]]

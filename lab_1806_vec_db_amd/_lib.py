@@ -97,6 +97,9 @@ SIGNATURES = {
     "vdb_flat_project_device": [vp, vp, vp, u64, u64, vp, vp, vp],
     "vdb_project_vectors": [f32p, u64, u64, f32p, u64, f64p, f32p, C.c_int],
     "vdb_project_vectors_device": [vp, u64, u64, vp, u64, vp, vp, C.c_int, vp],
+    "vdb_silhouette_plan": [u64, u64, C.c_int, C.c_int, C.c_uint32, u64, C.c_int, C.c_int, u64, u64p, u64, u64p, u64p, u64p, u64p, u64p, u64p],
+    "vdb_flat_silhouette": [vp, u64, vp, C.c_uint32, f32p, f64p, u64p, u64p],
+    "vdb_flat_silhouette_device": [vp, u64, vp, C.c_uint32, vp, vp, u64p, u64p, vp],
     "vdb_flat_kmeans": [vp, u64, u64, C.c_float, u64, f32p, u64, vp, f32p, u32p, u64p, u64p, f64p],
     "vdb_flat_kmeans_device": [vp, u64, u64, C.c_float, u64, f32p, u64, vp, vp, vp, vp, u64p, f64p, vp],
     "vdb_kmeans_assign": [vp, f32p, u64, u64, vp, u32p, f32p, u64p],

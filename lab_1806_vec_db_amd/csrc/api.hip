@@ -1347,6 +1347,82 @@ int vdb_project_vectors_device(const void *d_vecs, uint64_t n, uint64_t dim, con
     VDB_SYNC(s);
     VDB_API_END
 }
+// silhouette scoring of the labelled rows (Index::flat_silhouette_device, silhouette_plan.hpp, flat_silhouette.hip)
+static_assert(SIL_EUCLIDEAN == VDB_SIL_EUCLIDEAN, "vdbhip.h and silhouette_plan.hpp agree");
+int vdb_silhouette_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int cosine, uint32_t flags, uint64_t col, int col_live, int masked, uint64_t m_allowed,
+                        const uint64_t *sizes, uint64_t n_clusters, uint64_t *out_padded, uint64_t *out_tiles, uint64_t *out_slices,
+                        uint64_t *out_mean_slots, uint64_t *out_scratch_bytes, uint64_t *out_first_tile) {
+    VDB_API_BEGIN
+    std::string bad = sil_check_args(n_rows, dim, elem_u8 != 0, cosine != 0, flags, col, col_live != 0, masked != 0, m_allowed);
+    VDB_REQUIRE(bad.empty(), bad);
+    VDB_REQUIRE(sizes || n_clusters == 0, "silhouette plan: null argument");
+    uint64_t m = 0;
+    for (uint64_t c = 0; c < n_clusters; c++) {
+        VDB_REQUIRE(sizes[c] >= 1 && sizes[c] <= m_allowed - m, "silhouette plan: a cluster size must be in 1 .. the rows left");
+        m += sizes[c];
+    }
+    bad = sil_check_clusters(m, n_clusters);
+    VDB_REQUIRE(bad.empty(), bad);
+    const SilPlan p = sil_plan(sizes, n_clusters, dim, m_allowed);
+    if (out_padded) *out_padded = p.padded;
+    if (out_tiles) *out_tiles = p.tiles;
+    if (out_slices) *out_slices = p.slices;
+    if (out_mean_slots) *out_mean_slots = p.mean_slots;
+    if (out_scratch_bytes) *out_scratch_bytes = p.scratch_bytes;
+    if (out_first_tile) std::copy(p.first_tile.begin(), p.first_tile.end(), out_first_tile);
+    VDB_API_END
+}
+// what both forms refuse before a workspace is taken -> the mask as a RowMask (nullptr: all rows)
+static const RowMask *sil_check(const Index &ix, uint64_t col, const vdb_mask *mask, uint32_t flags) {
+    if (mask) ix.check_mask(mask->m);
+    const std::string bad = sil_check_args(ix.n, ix.dim, ix.elem_u8, ix.dist != 0, flags, col, col < LABEL_COLUMNS && ix.label_live[col], mask != nullptr,
+                                           mask ? mask->m.m : ix.n);
+    VDB_REQUIRE(bad.empty(), bad);
+    return mask ? &mask->m : nullptr;
+}
+int vdb_flat_silhouette(vdb_index *idx, uint64_t col, const vdb_mask *mask, uint32_t flags, float *out_s, double *out_mean, uint64_t *out_m,
+                        uint64_t *out_clusters) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const RowMask *rm = sil_check(ix, col, mask, flags);
+    VDB_REQUIRE(out_s && out_mean && out_m && out_clusters, "silhouette: null argument");
+    ix.use_device();
+    WsLease ws(ix);
+    DevBuf d_s, d_mean;
+    d_s.reserve(std::max<uint64_t>(ix.n, 1) * sizeof(float));
+    d_mean.reserve(sizeof(double));
+    uint64_t m = 0, clusters = 0;
+    run_synced(ix, *ws, [&] {
+        ix.flat_silhouette_device(*ws, (uint32_t)col, rm, flags, d_s.as<float>(), d_mean.as<double>(), &m, &clusters);
+        VDB_HIP(hipMemcpyAsync(out_s, d_s.p, ix.n * sizeof(float), hipMemcpyDeviceToHost, ws->stream));
+        VDB_HIP(hipMemcpyAsync(out_mean, d_mean.p, sizeof(double), hipMemcpyDeviceToHost, ws->stream));
+        VDB_SYNC(ws->stream);
+    });
+    *out_m = m;
+    *out_clusters = clusters;
+    VDB_API_END
+}
+int vdb_flat_silhouette_device(vdb_index *idx, uint64_t col, const vdb_mask *mask, uint32_t flags, void *d_out_s, void *d_out_mean, uint64_t *out_m,
+                               uint64_t *out_clusters, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const RowMask *rm = sil_check(ix, col, mask, flags);
+    VDB_REQUIRE(d_out_s && d_out_mean && out_m && out_clusters, "silhouette: null argument");
+    VDB_REQUIRE(reinterpret_cast<uintptr_t>(d_out_s) % 4 == 0 && reinterpret_cast<uintptr_t>(d_out_mean) % 8 == 0,
+                "silhouette: the device outputs must be 4-byte aligned (the mean: 8)");
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever last used the outputs on the caller's stream
+    uint64_t m = 0, clusters = 0;
+    run_synced(ix, *ws, [&] {
+        ix.flat_silhouette_device(*ws, (uint32_t)col, rm, flags, static_cast<float *>(d_out_s), static_cast<double *>(d_out_mean), &m, &clusters);
+    });
+    *out_m = m;
+    *out_clusters = clusters;
+    VDB_API_END
+}
 // k-means over the rows (Index::flat_kmeans_device / kmeans_assign_device, kmeans_plan.hpp, flat_kmeans.hip)
 int vdb_kmeans_plan(uint64_t n_rows, uint64_t dim, int elem_u8, int masked, uint64_t m, uint64_t c, int lloyd, int cosine, float xn, float cn,
                     float d_best, uint64_t *out_row_tiles, uint64_t *out_cent_tiles, uint64_t *out_k_blocks, uint64_t *out_order_passes,
@@ -2657,6 +2733,10 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.pca_project_calls.load();
     else if (n == "pca_project_rows")
         *out = idx->ix.pca_project_rows.load();
+    else if (n == "silhouette_calls")  // vdb_flat_silhouette (+ _device): calls that succeeded | the rows they scored
+        *out = idx->ix.silhouette_calls.load();
+    else if (n == "silhouette_rows")
+        *out = idx->ix.silhouette_rows.load();
     else if (n == "flat_grouped_calls")  // grouped k-NN: calls | queries | rounds run, summed over calls | queries whose last list was their whole allowed set
         *out = idx->ix.grouped_calls.load();
     else if (n == "flat_grouped_queries")

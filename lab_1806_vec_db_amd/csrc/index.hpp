@@ -847,6 +847,15 @@ struct Index {
     void flat_covariance_device(Workspace &ws, bool center, const RowMask *mask, double *d_mean, double *d_cov, uint64_t *out_m);
     void flat_project_device(Workspace &ws, const RowMask *mask, const float *d_W, uint64_t n_comp, const double *d_mean, float *d_out);
     std::atomic<uint64_t> pca_cov_calls{0}, pca_cov_rows{0}, pca_project_calls{0}, pca_project_rows{0};
+    // Silhouette scoring of the rows labelled in column `col` (flat_silhouette.hip, k_silhouette.hip, silhouette_plan.hpp -- the rule is
+    // stated in include/vdbhip.h; docs/DESIGN_flat.md 4.1aj).  The candidates are the mask's allowed rows (nullptr: all); d_out_s f32 [n]
+    // by row, NaN where the row is not scored; d_out_mean one f64; *out_m / *out_clusters = the scored rows and their distinct codes.
+    // On the device but for one read-back of the candidates' codes, from which the host makes the (code, row) order; read-side and
+    // re-entrant; everything is checked -- the cluster count too -- before an output is written; counters advance on success; returns
+    // synchronised.
+    void flat_silhouette_device(Workspace &ws, uint32_t col, const RowMask *mask, uint32_t flags, float *d_out_s, double *d_out_mean, uint64_t *out_m,
+                                uint64_t *out_clusters);
+    std::atomic<uint64_t> silhouette_calls{0}, silhouette_rows{0};
     // k-means over the rows (flat_kmeans.hip, k_kmeans.hip, kmeans_plan.hpp; docs/DESIGN_flat.md 4.1ad).  The rows clustered are the mask's
     // allowed rows (nullptr: all); d_assign [n] u32 and d_best [n] f32 are indexed by row, KM_LABEL_NONE / NaN for a row outside the mask.
     // kmeans_assign_device: the assignment step alone against d_cent [c][dim] on the device -- row i to the centroid with the smallest

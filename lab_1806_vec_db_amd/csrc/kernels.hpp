@@ -19,6 +19,7 @@
 #include "mmr_plan.hpp"
 #include "outlier_plan.hpp"
 #include "pca_plan.hpp"
+#include "silhouette_plan.hpp"
 #include "vote_plan.hpp"
 
 namespace vdb {
@@ -392,6 +393,7 @@ constexpr uint32_t LABEL_COLUMNS = 16;       // VDB_LABEL_COLUMNS
 constexpr uint32_t LABEL_NONE = 0xFFFFFFFFu;  // VDB_LABEL_NONE: a row without a value in that column
 constexpr uint32_t MASK_MAX_TERMS = 8;        // VDB_MASK_MAX_TERMS
 static_assert(VOTE_LABEL_COLUMNS == LABEL_COLUMNS, "vote_plan.hpp and kernels.hpp agree");
+static_assert(SIL_LABEL_COLUMNS == LABEL_COLUMNS && SIL_LABEL_NONE == LABEL_NONE, "silhouette_plan.hpp and kernels.hpp agree");
 static_assert(SETS_LABEL_COLUMNS == LABEL_COLUMNS && SETS_LABEL_NONE == LABEL_NONE && SETS_MAX_TERMS == MASK_MAX_TERMS, "mask_sets.hpp and kernels.hpp agree");
 struct LabelCols {  // the allocated columns of an index (kernel argument, by value)
     uint32_t *col[LABEL_COLUMNS];
@@ -550,6 +552,21 @@ void launch_pca_syrk(const float *X, const uint32_t *ids, uint64_t m, uint32_t d
 void launch_pca_cov_reduce(const double *partial, uint32_t dim, const PcaPlan &p, double denom, double *cov, hipStream_t s);
 void launch_pca_project(const float *X, const uint32_t *ids, uint64_t n, uint32_t dim, const float *W, uint32_t n_comp, const double *mean, float *out,
                         hipStream_t s);
+// The silhouette scoring of the labelled rows X [..][dim] of an f32 index, all sums in f64 (k_silhouette.hip, silhouette_plan.hpp).
+// prepare: per candidate p < cand (row ids[p]; nullptr: row p) key[p] = col[row], or LABEL_NONE when an element is not finite or, under
+// Cosine, the norm is zero; nrm[p] = |x|^2 (Cosine: |x|).  gather: per ordered slot < p.padded, through ord (candidate positions in
+// ascending (code, row) order, LABEL_NONE: padding), orow = the row and onorm = the norm (LABEL_NONE / -1 for padding); NaN to out_s [n].
+// pairs: a workgroup per 64 ordered slots walks every tile of 64 slots on the f64 matrix pipe; sum_a [padded] = the sum of d over the other
+// rows of the slot's cluster, min_b [padded] = the least mean of d over another cluster; tile_cl [tiles], cl_size [clusters].  finish:
+// out_s[row] = f32(s), s64 [padded] = s (0 for padding), *out_mean = their sum in 256 segments of p.mean_slots slots / p.m.
+void launch_sil_prepare(const float *X, const uint32_t *ids, const uint32_t *col, uint64_t cand, uint32_t dim, bool cosine, uint32_t *key, double *nrm,
+                        hipStream_t s);
+void launch_sil_gather(const uint32_t *ord, const uint32_t *ids, const double *nrm, uint64_t padded, uint32_t *orow, double *onorm, float *out_s,
+                       uint64_t n, hipStream_t s);
+void launch_sil_pairs(const float *X, uint32_t dim, bool cosine, bool root, const SilPlan &p, const uint32_t *orow, const double *onorm,
+                      const uint32_t *tile_cl, const uint32_t *cl_size, double *sum_a, double *min_b, hipStream_t s);
+void launch_sil_finish(const SilPlan &p, const uint32_t *orow, const uint32_t *tile_cl, const uint32_t *cl_size, const double *sum_a,
+                       const double *min_b, float *out_s, double *s64, double *out_mean, hipStream_t s);
 // The capped walk of the grouped k-NN (k_group.hip, grouped_plan.hpp): query b's list ids / dists [b][0 .. min(counts[b], ld)) walked in the order
 // given, at most g rows kept per value of `labels` (u32 per LOCAL row = id - id_offset; nullptr: a column never written; a row without a
 // label is always kept), the first k kept pairs to row slot_q[b] (nullptr: b) of out_idx / out_dist [..][k] with zeros behind them, their

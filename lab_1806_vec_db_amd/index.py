@@ -850,6 +850,45 @@ class GpuIndex:
         L.check(L.load().vdb_pca_segment(int(m), int(dim), int(s), C.byref(first), C.byref(ln)))
         return int(first.value), int(ln.value)
 
+    def silhouette(self, col: int, mask: RowMask | None = None, euclidean: bool = False):
+        """Silhouette coefficients of the rows labelled in column `col` (vdb_flat_silhouette): (s float32 [len], mean, m, clusters).  A row
+        is scored when the mask allows it (None: every row), it has a code in `col` and it is usable (every element finite; under Cosine
+        a non-zero norm); every other row reads NaN and enters no sum.  d(i, j) is the table's distance in f64 -- with `euclidean` the
+        root of the L2Sqr distance, scikit-learn's default; refused on a Cosine table --, a(i) the mean of d over the other rows of i's
+        cluster, b(i) the least mean over another cluster, s = (b - a) / max(a, b), 0 for a cluster of one; `mean` is the f64 mean of
+        the s(i).  COST: m^2 x dim f64 multiply-adds on the matrix pipe for m scored rows.  The summation order is a function of the
+        cluster sizes and dim: two calls return the same bits.  A u8 index, dim > 2048, a column never written, a stale or foreign mask
+        and fewer than 2 or more than m - 1 clusters raise VdbError."""
+        s = np.full(len(self), np.nan, dtype=np.float32)
+        mean, m, c = C.c_double(), C.c_uint64(), C.c_uint64()
+        L.check(self._lib.vdb_flat_silhouette(self._h, int(col), None if mask is None else mask._h, 1 if euclidean else 0, _ptr(s, L.f32p),
+                                              C.byref(mean), C.byref(m), C.byref(c)))
+        return s, float(mean.value), int(m.value), int(c.value)
+
+    def silhouette_device(self, col: int, out_s_ptr: int, out_mean_ptr: int, mask: RowMask | None = None, euclidean: bool = False, stream: int = 0):
+        """the same with s f32 [len] and the f64 mean written to device memory, 4- / 8-byte aligned (vdb_flat_silhouette_device); returns
+        (m, clusters), synchronised"""
+        m, c = C.c_uint64(), C.c_uint64()
+        L.check(self._lib.vdb_flat_silhouette_device(self._h, int(col), None if mask is None else mask._h, 1 if euclidean else 0, L.vp(out_s_ptr),
+                                                     L.vp(out_mean_ptr), C.byref(m), C.byref(c), L.vp(stream)))
+        return int(m.value), int(c.value)
+
+    @staticmethod
+    def silhouette_plan(n_rows: int, dim: int, sizes, m_allowed: int | None = None, elem_u8: bool = False, cosine: bool = False, flags: int = 0,
+                        col: int = 0, col_live: bool = True):
+        """(padded, tiles, slices, mean_slots, scratch_bytes, first_tile) of a silhouette call over clusters of `sizes` rows, in ascending
+        code order (vdb_silhouette_plan; host only, no GPU): the ordered slots with every cluster padded to whole tiles of 64, the tiles
+        (= row blocks = workgroups of the pair kernel), the slices of 16 dimensions per tile pair, the slots per mean segment, the device
+        bytes held besides the outputs, and first_tile [len(sizes) + 1].  Raises VdbError with the text the call refuses by."""
+        masked = m_allowed is not None
+        sz = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+        o = [C.c_uint64() for _ in range(5)]
+        first = np.zeros(sz.size + 1, dtype=np.uint64)
+        L.check(L.load().vdb_silhouette_plan(int(n_rows), int(dim), int(bool(elem_u8)), int(bool(cosine)), int(flags), int(col), int(bool(col_live)),
+                                             int(masked), int(m_allowed if masked else n_rows), _ptr(sz, L.u64p), sz.size, *(C.byref(x) for x in o),
+                                             _ptr(first, L.u64p)))
+        return tuple(int(x.value) for x in o) + (first,)
+
     def kmeans(self, c: int, max_iter: int = 20, tol: float = 1e-4, seed: int = 0, init=None, mask: RowMask | None = None):
         """k-means over the index's rows, or the mask's (vdb_flat_kmeans): (centroids f32 [c][dim], assign uint32 [len], sizes uint64 [c],
         iters, inertia).  Rows go to the centroid with the smallest (pair distance as the re-rank reports it, centroid id); a centroid becomes

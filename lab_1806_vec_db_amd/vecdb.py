@@ -1553,6 +1553,63 @@ class VecDB:
             self.batch_add(new_key, out, meta)
         return model
 
+    @staticmethod
+    def _silhouette_rows(t: _Table, field: str, filter, euclidean, sample, seed):
+        """UNDER THE READ LOCK: (rows, scores, mean, m) of silhouette_samples -- the candidate rows, ascending, and ONE GpuIndex.silhouette
+        call under the filter's cached mask, or under a host-made mask of the drawn rows"""
+        col = t.codec.column_of(field)
+        if col is None:
+            raise ValueError(f"silhouette: the field {field!r} has no label column and cannot get one (there is no host route)")
+        mk = None if filter is None else t.mask_for(filter)
+        rows = np.arange(len(t.index), dtype=np.int64) if mk is None else np.asarray(mk.rows()[1], dtype=np.int64)
+        euclid = (t.index.dist == 0) if euclidean is None else bool(euclidean)
+        drawn = None
+        if sample is not None:
+            if int(sample) < 0:
+                raise ValueError("sample must be at least 0")
+            if int(sample) < rows.size:
+                rows = np.sort(np.random.default_rng(seed).choice(rows, int(sample), replace=False))
+                mk = drawn = t.index.make_mask(rows)
+        try:
+            s, mean, m, _ = t.index.silhouette(col, mk, euclid)
+        finally:
+            if drawn is not None:
+                drawn.close()
+        return rows, s[rows], mean, m
+
+    def silhouette(self, key: str, field: str, filter=None, euclidean: bool | None = None, sample: int | None = None, seed: int = 0) -> dict:
+        """"How good is this clustering?"  The silhouette coefficient of the rows that match `filter` (every row without one) under the
+        labelling the metadata key `field` gives them -- the cluster ids written by cluster, cluster_density or mark_duplicates, or any
+        other field: {"mean", "rows", "by_value": {value: (mean, size)}}.  A matching row is scored when it carries `field` and is
+        usable (every element finite; on a cosine table a non-zero norm); "rows" counts those, "mean" is the mean of their s(i), near 1
+        for compact well-separated clusters, near 0 for overlapping ones, negative for rows that sit in the wrong cluster; "by_value"
+        gives every value's own mean and size (averaged on the host from the per-row scores: O(rows)).  GpuIndex.silhouette states the
+        rule.  `euclidean`: the root of the L2Sqr distance, as scikit-learn's default metric; None: True on an L2Sqr table, False on a
+        cosine table (where it is refused).
+        COST: rows^2 x dim f64 multiply-adds on the device.  For a large table pass `sample=n`: the scored rows are restricted to
+        numpy.random.default_rng(seed).choice(matching rows ascending, n, replace=False) through a host-made mask (every matching row
+        when there are at most n).
+        `field` gets a label column on first use, as in count_by; there is no host fallback: a field that cannot have one (a 17th key)
+        raises ValueError.  Fewer than 2 values among the scored rows, or as many values as rows, raise VdbError.  ONE GpuIndex.silhouette
+        call under the read lock and the filter's cached mask."""
+        t = self._t(key)
+        t.prepare(([] if filter is None else [filter]) + [{field: None}])
+        with t.lock.read():
+            rows, s, mean, m = self._silhouette_rows(t, field, filter, euclidean, sample, seed)
+            groups: dict = {}
+            for r, v in zip(rows.tolist(), s.astype(np.float64).tolist()):
+                if v == v:
+                    groups.setdefault(t.metadata[r].get(field), []).append(v)
+            return {"mean": mean, "rows": m, "by_value": {k: (float(np.mean(v)), len(v)) for k, v in groups.items()}}
+
+    def silhouette_samples(self, key: str, field: str, filter=None, euclidean: bool | None = None, sample: int | None = None, seed: int = 0):
+        """(rows, scores) of silhouette: the matching rows (the drawn ones with `sample`), ascending, and the float32 s(i) of each, NaN for
+        a row that is not scored (no value of `field`, a NaN element, a zero row on a cosine table)."""
+        t = self._t(key)
+        t.prepare(([] if filter is None else [filter]) + [{field: None}])
+        with t.lock.read():
+            return self._silhouette_rows(t, field, filter, euclidean, sample, seed)[:2]
+
     def delete_duplicates(self, key: str, radius: float, filter=None, limit: int | None = None) -> int:
         """Removes every row of a find_duplicates group except its representative (the lowest row); returns the number removed.  ONE
         GpuIndex.remove_rows call; the metadata follow the moves it reports, and the HNSW index and the PQ table are cleared, as delete
