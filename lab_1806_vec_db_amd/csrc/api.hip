@@ -2517,6 +2517,10 @@ int vdb_set_param(vdb_index *idx, const char *name, int64_t value) {
     }
     else if (n == "debug_alloc_fail_over")  // (testing aid, process-wide) device allocations of at least this many bytes fail; 0 = off
         devbuf_fail_over() = (size_t)value;
+    else if (n == "debug_scratch_poison") {  // (testing aid, process-wide) new device allocations and the pooled workspace's scratch are filled with this 32-bit word; 0 = off
+        VDB_REQUIRE(value >= 0 && value <= 0xFFFFFFFFll, "debug_scratch_poison must be a 32-bit pattern");
+        devbuf_poison() = (uint32_t)value;
+    }
     else if (n == "flat_i8_unit_min")  // threshold sample of the 8-bit pass: one value per sampled unit when the units are many (0 auto, 1 off, 2 on from 2 x rank units: tests)
         idx->ix.flat_i8_unit_min = (int)value;
     else if (n == "flat_i8_full")  // second 8-bit attempt of a handful of queries: all candidates at once (0 on, 1 off: rounds of 63 rows)

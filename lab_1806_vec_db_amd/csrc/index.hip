@@ -25,15 +25,22 @@ Index::Index(int dev, uint64_t d, int ds, bool u8) : device(dev), dim(d), dist(d
 
 std::unique_ptr<Workspace> Index::acquire_ws() {
     use_device();
+    std::unique_ptr<Workspace> ws;
     {
         std::lock_guard<std::mutex> g(ws_mu);
         if (!ws_free.empty()) {
-            auto ws = std::move(ws_free.back());
+            ws = std::move(ws_free.back());
             ws_free.pop_back();
-            return ws;
         }
     }
-    return std::make_unique<Workspace>();
+    if (!ws) return std::make_unique<Workspace>();
+#ifndef VDB_HOST_SANITIZER_BUILD  // (the host-only build has no device: its workspaces have neither a stream nor buffers)
+    if (const uint32_t word = devbuf_poison().load(std::memory_order_relaxed))  // (testing aid) the last call's leftovers overwritten, ahead of this call's work
+        ws->for_each_scratch([&](DevBuf &b) {
+            if (b.cap) devbuf_fill(b.p, b.cap, word, ws->stream);
+        });
+#endif
+    return ws;
 }
 void Index::release_ws(std::unique_ptr<Workspace> ws) {
     if (!ws) return;

@@ -33,6 +33,21 @@ inline std::atomic<size_t> &devbuf_fail_over() {
     static std::atomic<size_t> v{0};
     return v;
 }
+// (testing aid, "debug_scratch_poison") a 32-bit word that every new DevBuf allocation is filled with before it is handed out, and that
+// Index::acquire_ws refills the pooled workspace's scratch with before every call; 0 = off.  Fresh device memory is very often all zeros and
+// a single-threaded caller gets the same workspace for every call, so a kernel that reads a word nobody wrote in THIS call gets a
+// plausible value either way; under a pattern the answer or a route counter changes (tests/test_scratch_poison_gpu.py).
+inline std::atomic<uint32_t> &devbuf_poison() {
+    static std::atomic<uint32_t> v{0};
+    return v;
+}
+// `bytes` bytes at p <- the word repeated (a ragged tail gets the word's leading bytes), enqueued on s
+inline void devbuf_fill(void *p, size_t bytes, uint32_t word, hipStream_t s) {
+    const size_t words = bytes / sizeof(uint32_t);
+    if (words) VDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), (int)word, words, s));
+    for (size_t b = words * sizeof(uint32_t); b < bytes; b++)
+        VDB_HIP(hipMemsetAsync(static_cast<char *>(p) + b, int((word >> (8 * (b & 3))) & 0xFF), 1, s));
+}
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
@@ -54,6 +69,11 @@ struct DevBuf {
             throw AllocError("device allocation of " + std::to_string(bytes) + " bytes failed: out of memory");
         }
         VDB_HIP(e);
+        if (const uint32_t word = devbuf_poison().load(std::memory_order_relaxed)) {
+            // the streams of the workspaces do not wait for the null stream: the fill is complete before anybody sees the pointer
+            devbuf_fill(*out, bytes, word, nullptr);
+            VDB_HIP(hipDeviceSynchronize());
+        }
     }
     static void alloc(size_t want, void **base_out, void **p_out) {
         if (!devbuf_efence()) {
@@ -121,6 +141,10 @@ struct ProfEntry {
 };
 
 // per-call scratch: one per concurrent reader (read-side calls are re-entrant, see vdbhip.h)
+// What a buffer holds when a call takes the workspace is whatever the last call left there -- another feature's, at other sizes -- and
+// no call may depend on it: "debug_scratch_poison" (devbuf_poison) overwrites all of it before every call.  The buffers with a contract
+// ACROSS calls are listed here and nowhere else; for_each_scratch() visits every buffer but these:
+//   small_cnt -- k_flat_small's arrival counters: zeroed once when allocated, left zero by every launch (Index::flat_small_device)
 struct Workspace {
     hipStream_t stream = nullptr;
     DevBuf q, qsq, qfrag, qfrag_g, qaux, dense, lists, keys_a, keys_b, keys_c, flags, out_idx, out_dist, out_cnt, lut, misc;
@@ -130,6 +154,13 @@ struct Workspace {
     // counts), [slot map | done bytes | flag], the walk's table beyond LDS -- buffers of their own, because the list calls use the others.
     // The diversified k-NN (Index::flat_knn_mmr_device) keeps its candidate lists and its flag in the same ones.
     DevBuf grp_q, grp_ids, grp_dist, grp_cnt, grp_aux, grp_table;
+    // fn(buffer) for every buffer whose contents no call may rely on: all but the contract buffers of the comment above
+    template <class F>
+    void for_each_scratch(F fn) {
+        for (DevBuf *b : {&q, &qsq, &qfrag, &qfrag_g, &qaux, &dense, &lists, &keys_a, &keys_b, &keys_c, &flags, &out_idx, &out_dist, &out_cnt, &lut,
+                          &misc, &pq_img16, &pq_aux16, &small_part, &grp_q, &grp_ids, &grp_dist, &grp_cnt, &grp_aux, &grp_table})
+            fn(*b);
+    }
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     struct Pending {
         std::string name;
