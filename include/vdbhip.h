@@ -1075,8 +1075,9 @@ int vdb_fuse_lists_device(vdb_index *idx, const void *d_ids, const void *d_dists
  * VecSet<u8> index, every mask / mask_of error of vdb_flat_knn_filtered_multi (a stale mask: VDB_ERR_STATE), trunc_len == 0.
  * vdb_get_stat "flat_fused_groups_calls", "flat_fused_groups_queries", "flat_fused_groups_lists" count the two search forms (the list
  * call under them advances its own counters); vdb_prof_get "fuse_groups" times k_fuse_groups.
- * Not covered: rounds that grow fetch_k until MIN is exact (out_exact tells the caller), exact rescoring of candidate documents over
- * all their rows, weighted SUM, sharded contexts, VecSet<u8> indexes, lists from PQ / HNSW / IVF beyond feeding them to the list form. */
+ * Not covered: rounds that grow fetch_k until MIN is exact (out_exact tells the caller), weighted SUM, sharded contexts, VecSet<u8>
+ * indexes, lists from PQ / HNSW / IVF beyond feeding them to the list form.  (Exact rescoring of candidate documents over all their
+ * rows: vdb_flat_rescore_groups below.) */
 #define VDB_FUSE_SUM 2
 int vdb_fuse_groups_plan(int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t fetch_k, const float *weights, float rrf_c,
                          uint32_t column, uint64_t budget, int *out_code, uint64_t *out_s_max, uint32_t *out_table_lg, int *out_in_lds,
@@ -1092,6 +1093,63 @@ int vdb_flat_knn_fused_groups_device(vdb_index *idx, const void *d_queries, cons
 int vdb_fuse_groups_device(vdb_index *idx, const void *d_ids, const void *d_dists, const void *d_counts, const uint64_t *lims, uint64_t nq,
                            uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, uint32_t column, uint64_t trunc_len,
                            void *d_out_idx, void *d_out_dist, void *d_out_count, void *d_out_exact, void *stream);
+/* ---- exact late-interaction rescoring of candidate documents: their groups scored over ALL their rows ---------------------------------
+ * The second stage behind vdb_flat_knn_fused_groups: that call's SUM is a lower bound while a list is cut at fetch_k; this one takes
+ * candidate rows (its representatives, usually) and returns the TRUE scores of their groups -- nothing here depends on a fetch_k.
+ *   Inputs: an f32 index, a label `column`, nq questions with their sub-query vectors queries [lims[nq]][dim] and HOST lims [nq + 1]
+ *   (lims[0] == 0, 1 <= S_q <= 32, as vdb_fuse_plan), per question a candidate list cand_ids [nq][ld] of u64 row ids (id_offset added)
+ *   of which the first cand_count[q] <= ld count, ld <= 4096, a mode VDB_FUSE_SUM or VDB_FUSE_MIN, k <= ld, and masks / n_masks / mask_of,
+ *   one mask index per SUB-query, exactly as vdb_flat_knn_fused_groups takes them (n_masks == 0: unfiltered, they are not read).
+ *   A candidate is a row; the candidate GROUP is that row's group under the rules of vdb_flat_knn_fused_groups: all rows of the table with
+ *   the row's code when that is not VDB_LABEL_NONE; an unlabelled row, or any row of a column never written, is a group of its own.  Two
+ *   candidates of one group count once, at the first.
+ *   Distance: for sub-query s and group g, d_s(g) is the smallest D(q_s, row) over the rows of g that s's mask allows (no mask: all), the
+ *   smallest under the knn order -- ascending by (distance, row), -0 == +0, every NaN equal and last -- and r_s(g) is that row.  D is the
+ *   pair distance the re-rank reports: the strict ascending f32 fold, no FMA, bit for bit.  If g has no allowed row for s then
+ *   d_s(g) = +inf and s cannot supply the representative.
+ *   Score: VDB_FUSE_SUM: acc = +0.0f; for every s ascending acc = acc + d_s(g), one rounding per add.  VDB_FUSE_MIN: the smallest
+ *   d_s(g) under the knn order, of the first s that attains it.  A NaN score is reported as 0x7FC00000 (either mode).
+ *   Representative: r_s*(g) for the s that minimises (order key of d_s(g), s), as in the sibling call; if no sub-query has an allowed
+ *   row, the candidate row itself.
+ *   Order: ascending by (order key of the score, representative id), NaN last.
+ *   Outputs: out_idx [nq][k] the representatives (id_offset added), out_dist [nq][k] the scores, slots behind the count zero;
+ *   out_count[q] = min(k, distinct candidate groups).  k == 0 or no candidates: counts are zero and no pair is evaluated.
+ *   Determinism: no float atomic.  A per-(group, sub-query) minimum is an integer atomic min on the packed (order key, row) pair, which
+ *   does not depend on the order of arrival; the sum is a separate strict fold over those minima.  Two calls return the same bits.
+ *   How (csrc/flat_rescore.hip, csrc/k_rescore.hip): collect -- a workgroup per question dedupes the candidates' groups into slots and
+ *   enters the wanted codes into one hash table of the call; ONE pass over the label column finds every row that carries a wanted code
+ *   (run once to count, so that the host can size whole tiles of 64 rows from 8 B per question, and once to append: a wave ballot and one
+ *   integer atomic per wave and question); pairs -- k_rescore_pairs, a workgroup of 4 waves per (question, tile): the tile's rows and the
+ *   question's vectors staged through double-buffered LDS panels in slices of 32 dimensions, lane l folding row l, wave w the sub-queries
+ *   w, w + 4, ..; finish -- a thread per group folds its S minima, the workgroup sorts (score, representative) and writes k entries.
+ *   Questions go in sub-chunks whose entries and minima stay under 256 MiB.
+ * vdb_rescore_groups_plan: host utility, works without a GPU: *out_code = 0 when (mode, lims, nq, k, ld, column, cand_count) is a call the
+ *   forms accept, otherwise which refusal: 1 mode, 2 column >= VDB_LABEL_COLUMNS, 3 NULL lims, 4 lims[0] != 0, 5 a descent, 6 a question
+ *   without a sub-query, 7 more than 32, 8 ld > 4096, 9 k > ld, 10 a cand_count[q] > ld (cand_count may be NULL: not looked at) -- the
+ *   first that applies, in this order; nothing else is written then.  Accepted, and `rows` [nq] (the rows of each question's candidate
+ *   groups together) not NULL: *out_tiles = the work items, sum of ceil(rows[q] / 64); *out_sub_chunk = questions per sub-chunk, as many
+ *   as keep sub_chunk x the largest question's scratch (64 x tiles x 8 B of entries + slots[q] x S_q x 8 B of minima; slots NULL:
+ *   cand_count, that NULL too: ld) under `budget` bytes (0: 256 MiB), at least 1; *out_scratch_bytes = the scratch of the largest
+ *   sub-chunk.  Any output but out_code may be NULL.
+ * vdb_flat_rescore_groups: host arrays.  vdb_flat_rescore_groups_device: queries, candidates, counts and outputs on the index's GPU,
+ *   lims on the host; the counts are read back (8 B per question) to size the layout; returns synchronised.
+ * Refused before anything is computed or written, counters unchanged (VDB_ERR_INVALID): everything vdb_rescore_groups_plan reports, a
+ * VecSet<u8> index, a dim mismatch, 2^32 rows or more, every mask / mask_of error of vdb_flat_knn_filtered_multi (a stale mask:
+ * VDB_ERR_STATE), and a candidate id that is no row of the index -- checked on the device first, as vdb_fuse_groups_device does.
+ * vdb_get_stat "flat_rescore_calls", "flat_rescore_questions", "flat_rescore_rows" (candidate rows evaluated: the rows of the candidate
+ * groups; not advanced by k == 0); vdb_prof_get "rescore_collect", "rescore_pairs", "rescore_finish".
+ * Not covered: weighted SUM, RRF over rescored lists, VecSet<u8> indexes, sharded contexts, rounds that grow fetch_k until the answer
+ * is certified (VecDB.batch_search_fused(rescore=) reports the certificate). */
+int vdb_rescore_groups_plan(int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t ld, uint32_t column, const uint64_t *cand_count,
+                            const uint64_t *rows, const uint64_t *slots, uint64_t budget, int *out_code, uint64_t *out_tiles,
+                            uint64_t *out_sub_chunk, uint64_t *out_scratch_bytes);
+int vdb_flat_rescore_groups(vdb_index *idx, const float *queries, const uint64_t *lims, uint64_t nq, uint64_t dim, const uint64_t *cand_ids,
+                            const uint64_t *cand_count, uint64_t ld, uint64_t k, int mode, uint32_t column, const vdb_mask *const *masks,
+                            uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx, float *out_dist, uint64_t *out_count);
+int vdb_flat_rescore_groups_device(vdb_index *idx, const void *d_queries, const uint64_t *lims, uint64_t nq, uint64_t dim,
+                                   const void *d_cand_ids, const void *d_cand_count, uint64_t ld, uint64_t k, int mode, uint32_t column,
+                                   const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of, void *d_out_idx,
+                                   void *d_out_dist, void *d_out_count, void *stream);
 /* ---- bulk row fetch: the vectors of many rows as ONE call (no counterpart in the reference) ----------------------------------------
  * vdb_index_row reads one row with one blocking copy.  These calls return the vectors of a LIST of rows: out[j] = row rows[j].  The
  * list only names what is read, so its order is free and repeats are allowed (m may exceed len); every rows[j] must be below len, and a

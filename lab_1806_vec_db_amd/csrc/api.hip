@@ -2300,6 +2300,97 @@ int vdb_fuse_groups_device(vdb_index *idx, const void *d_ids, const void *d_dist
     VDB_API_END
 }
 
+// ---- exact rescoring of candidate documents over all their rows (Index::rescore_groups_device, k_rescore.hip) -----------------------------
+// everything the host can refuse is refused here, before anything is computed or written; -> the masks as RowMask pointers (none: unfiltered)
+static std::vector<const RowMask *> rescore_check(const Index &ix, const void *queries, const uint64_t *lims, uint64_t nq, uint64_t dim,
+                                                  const void *cand_ids, const void *cand_count, uint64_t ld, uint64_t k, int mode, uint32_t column,
+                                                  const uint64_t *h_count, const vdb_mask *const *masks, uint64_t n_masks, const uint32_t *mask_of,
+                                                  const void *out_idx, const void *out_dist, const void *out_count) {
+    const char *bad = rescore_bad_text(rescore_check_args(mode, lims, nq, k, ld, column, h_count));
+    VDB_REQUIRE(bad == nullptr, bad);
+    check_query_args(ix, queries, nq, dim, out_idx, out_dist);
+    VDB_REQUIRE(nq == 0 || (cand_count && out_count && (ld == 0 || cand_ids)), "null argument");
+    std::vector<const RowMask *> rm = optional_masks_check(ix, lims[nq], masks, n_masks, mask_of);
+    VDB_REQUIRE(ix.n < (1ull << 32) && nq < (1ull << 31), "rescore groups: too many rows or questions");
+    return rm;
+}
+
+int vdb_rescore_groups_plan(int mode, const uint64_t *lims, uint64_t nq, uint64_t k, uint64_t ld, uint32_t column, const uint64_t *cand_count,
+                            const uint64_t *rows, const uint64_t *slots, uint64_t budget, int *out_code, uint64_t *out_tiles, uint64_t *out_sub_chunk,
+                            uint64_t *out_scratch_bytes) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(out_code, "rescore_groups_plan: null out_code");
+    *out_code = rescore_check_args(mode, lims, nq, k, ld, column, cand_count);
+    if (*out_code != RESCORE_OK || !rows) return VDB_OK;
+    const RescoreLayout l = rescore_layout(lims, nq, rows, slots ? slots : cand_count, ld, budget);
+    if (out_tiles) *out_tiles = l.tiles;
+    if (out_sub_chunk) *out_sub_chunk = l.sub_chunk;
+    if (out_scratch_bytes) *out_scratch_bytes = l.scratch_bytes;
+    VDB_API_END
+}
+
+int vdb_flat_rescore_groups(vdb_index *idx, const float *queries, const uint64_t *lims, uint64_t nq, uint64_t dim, const uint64_t *cand_ids,
+                            const uint64_t *cand_count, uint64_t ld, uint64_t k, int mode, uint32_t column, const vdb_mask *const *masks,
+                            uint64_t n_masks, const uint32_t *mask_of, uint64_t *out_idx, float *out_dist, uint64_t *out_count) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const std::vector<const RowMask *> rm =
+        rescore_check(ix, queries, lims, nq, dim, cand_ids, cand_count, ld, k, mode, column, cand_count, masks, n_masks, mask_of, out_idx, out_dist, out_count);
+    if (nq == 0) {
+        ix.rescore_calls++;
+        return VDB_OK;
+    }
+    ix.use_device();
+    WsLease ws(ix);
+    hipStream_t s = ws->stream;
+    run_synced(ix, *ws, [&] {
+        const size_t qb = lims[nq] * ix.dim * sizeof(float), cb = nq * ld * sizeof(uint64_t), nb = nq * sizeof(uint64_t);
+        ws->q.reserve(qb);
+        ws->keys_a.reserve(std::max<size_t>(cb, 8));
+        ws->keys_b.reserve(nb);
+        const OutBlock out(*ws, nq, k);
+        VDB_HIP(hipMemcpyAsync(ws->q.p, queries, qb, hipMemcpyHostToDevice, s));
+        if (cb) VDB_HIP(hipMemcpyAsync(ws->keys_a.p, cand_ids, cb, hipMemcpyHostToDevice, s));
+        VDB_HIP(hipMemcpyAsync(ws->keys_b.p, cand_count, nb, hipMemcpyHostToDevice, s));
+        // (a refused candidate id throws in here, before the download: the caller's outputs stay as they are)
+        ix.rescore_groups_device(*ws, ws->q.as<float>(), lims, nq, ws->keys_a.as<uint64_t>(), ws->keys_b.as<uint64_t>(), cand_count, ld, k, mode, column,
+                                 rm.data(), n_masks, mask_of, out.idx(), out.dist(), out.cnt());
+        out.download(*ws, out.bytes <= OutBlock::STAGE_MAX, 0, 0, out_idx, out_dist, out_count);
+    });
+    VDB_API_END
+}
+
+int vdb_flat_rescore_groups_device(vdb_index *idx, const void *d_queries, const uint64_t *lims, uint64_t nq, uint64_t dim, const void *d_cand_ids,
+                                   const void *d_cand_count, uint64_t ld, uint64_t k, int mode, uint32_t column, const vdb_mask *const *masks,
+                                   uint64_t n_masks, const uint32_t *mask_of, void *d_out_idx, void *d_out_dist, void *d_out_count, void *stream) {
+    VDB_API_BEGIN
+    VDB_REQUIRE(idx, "null index");
+    Index &ix = idx->ix;
+    const std::vector<const RowMask *> rm = rescore_check(ix, d_queries, lims, nq, dim, d_cand_ids, d_cand_count, ld, k, mode, column, nullptr, masks,
+                                                          n_masks, mask_of, d_out_idx, d_out_dist, d_out_count);
+    if (nq == 0) {
+        ix.rescore_calls++;
+        return VDB_OK;
+    }
+    ix.use_device();
+    WsLease ws(ix);
+    VDB_SYNC(static_cast<hipStream_t>(stream));  // order after whatever produced the queries and the candidates on the caller's stream
+    run_synced(ix, *ws, [&] {
+        // the counts size the layout: 8 B per question come back, and a count above ld is refused like the host form's
+        std::vector<uint64_t> h_count(nq);
+        uint64_t *h = static_cast<uint64_t *>(ws->pinned(nq * sizeof(uint64_t)));
+        VDB_HIP(hipMemcpyAsync(h, d_cand_count, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+        VDB_SYNC(ws->stream);
+        std::memcpy(h_count.data(), h, nq * sizeof(uint64_t));
+        for (uint64_t q = 0; q < nq; q++) VDB_REQUIRE(h_count[q] <= ld, rescore_bad_text(RESCORE_BAD_COUNT));
+        ix.rescore_groups_device(*ws, static_cast<const float *>(d_queries), lims, nq, static_cast<const uint64_t *>(d_cand_ids),
+                                 static_cast<const uint64_t *>(d_cand_count), h_count.data(), ld, k, mode, column, rm.data(), n_masks, mask_of,
+                                 static_cast<uint64_t *>(d_out_idx), static_cast<float *>(d_out_dist), static_cast<uint64_t *>(d_out_count));
+    });
+    VDB_API_END
+}
+
 // ---- bulk row fetch (Index::get_rows*) ----------------------------------------------------------------------------------------------
 int vdb_index_get_rows(vdb_index *idx, const uint64_t *rows, uint64_t m, float *out) {
     VDB_API_BEGIN
@@ -2775,6 +2866,12 @@ int vdb_get_stat(const vdb_index *idx, const char *name, uint64_t *out) {
         *out = idx->ix.fused_groups_queries.load();
     else if (n == "flat_fused_groups_lists")
         *out = idx->ix.fused_groups_lists.load();
+    else if (n == "flat_rescore_calls")  // exact rescoring of candidate documents: calls | questions | candidate rows evaluated
+        *out = idx->ix.rescore_calls.load();
+    else if (n == "flat_rescore_questions")
+        *out = idx->ix.rescore_questions.load();
+    else if (n == "flat_rescore_rows")
+        *out = idx->ix.rescore_rows.load();
     else if (n == "update_calls")  // vdb_index_update_rows* calls that changed rows | rows they rewrote
         *out = idx->ix.update_calls.load();
     else if (n == "update_rows")

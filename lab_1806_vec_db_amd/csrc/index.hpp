@@ -806,6 +806,17 @@ struct Index {
                             uint64_t ld, uint64_t k, int mode, const float *weights, float rrf_c, uint32_t column, uint64_t trunc_len, uint64_t *d_idx,
                             float *d_dist, uint64_t *d_cnt, uint8_t *d_exact);
     std::atomic<uint64_t> fused_groups_calls{0}, fused_groups_queries{0}, fused_groups_lists{0};
+    // Exact late-interaction rescoring of candidate documents (flat_rescore.hip, k_rescore.hip, rescore_plan.hpp; docs/DESIGN_flat.md
+    // 4.1ak): per question the GROUPS of its candidate rows d_cand [nq][ld] (u64 ids, d_cand_cnt [nq] counted; h_cand_cnt: the same counts
+    // on the host, each <= ld) scored over ALL their allowed rows -- per sub-query the group's nearest row, the scores folded over the
+    // sub-queries (FUSE_SUM) or their minimum (FUSE_MIN) -- and the first min(k, groups) written ascending.  Three stages: collect (group
+    // slots, the rows that carry a wanted code), pairs (k_rescore_pairs) and finish, the questions in sub-chunks under LIST_BUDGET.  Every
+    // candidate id is checked on the device first (a bad one throws before an output is written or a counter moves).  The caller has
+    // checked the arguments (rescore_check_args), the masks and mask_of (indexed by SUB-query); returns synchronised.
+    void rescore_groups_device(Workspace &ws, const float *d_q, const uint64_t *lims, uint64_t nq, const uint64_t *d_cand, const uint64_t *d_cand_cnt,
+                               const uint64_t *h_cand_cnt, uint64_t ld, uint64_t k, int mode, uint32_t column, const RowMask *const *masks,
+                               uint64_t n_masks, const uint32_t *mask_of, uint64_t *d_idx, float *d_dist, uint64_t *d_cnt);
+    std::atomic<uint64_t> rescore_calls{0}, rescore_questions{0}, rescore_rows{0};
     // k-NN label vote (k_vote.hip, vote_plan.hpp -- which states the limits; docs/DESIGN_flat.md 4.1ag): per query the values of label column
     // `column` among the first min(k, m) rows of FlatIndex::knn's order over its allowed rows, ranked by (score descending, first voter
     // ascending), the top c of them.  ONE round: the exact sorted list of min(k, longest allowed set) rows per query -- flat_knn_device

@@ -7,6 +7,7 @@
 #include "dbscan_plan.hpp"
 #include "dup_plan.hpp"
 #include "fuse_groups_plan.hpp"
+#include "rescore_plan.hpp"
 #include "fuse_plan.hpp"
 #include "grouped_plan.hpp"
 #include "kmeans_plan.hpp"
@@ -622,6 +623,38 @@ void launch_fuse_groups(const uint64_t *ids, const float *dists, const uint64_t 
                         uint64_t list_base, const float *weights, const uint32_t *labels, uint64_t n, int mode, float c, uint64_t id_offset,
                         uint64_t trunc_len, uint32_t k, uint32_t lg, uint32_t *scratch, uint64_t *out_idx, float *out_dist, uint64_t *out_cnt,
                         uint8_t *out_exact, hipStream_t s);
+// The kernels of the exact rescoring of candidate documents (k_rescore.hip, rescore_plan.hpp; Index::rescore_groups_device states the
+// call).  Questions are numbered over the whole call; a launch covers the questions q0 .. q0 + nb.  All arrays on the device.
+//   slots    per question: its candidates ids [q][0 .. min(counts[q], ld)) (checked: rows of the index) resolved to groups -- the code
+//            of `labels` (nullptr: a column never written), or RS_ROW_TAG | row for a row without one --, deduped in first-occurrence
+//            order into slot_key / slot_row [coff[q] + slot] (the group, its first candidate row), n_slots[q]; rows_cnt[q] = its
+//            unlabelled groups; every labelled group enters the table tkey / tslot (2^glg entries, cleared by launch_rescore_fill64) as
+//            ((q << 32) | code) -> slot, probing from the hash of the CODE, so that one walk finds every question that wants a code.
+//   match    ONE pass over `labels`: a row whose code is in the table is counted into rows_cnt[q] (fill == false), or appended as
+//            (slot << 32) | row to entries + ent_off[q] at the cursor cur[q] (fill == true; questions q0 .. q0 + nb only, never past
+//            rows_cnt[q]), for every question that wants the code: a wave ballot and one integer atomic per wave and question.
+//   prepare  per question: its [n_slots][S] minima set empty, its whole tiles set to RESCORE_ENTRY_PAD (what stays is the padding of the
+//            last tile), its unlabelled groups appended as entries, cur[q] = the entries so far.
+//   pairs    work item (question, tile of 64 entries): every (row, sub-query) distance in the reference's fold order, then an integer
+//            min of (order key << 32 | row) into mins + tab_off[q] at [slot][s] for the pairs the sub-query's mask (bits[l], nullptr:
+//            none; `bits` itself nullptr: no masks) allows.  metric: MET_L2_DIRECT or MET_COSINE (xsq / qsq: the squared norms).
+//   finish   per question: score and representative of every slot, the sort by (score, representative), min(k, n_slots) entries out
+//            (id_offset added, zeros behind them) and the count.
+void launch_rescore_fill64(uint64_t *p, uint64_t count, uint64_t value, hipStream_t s);
+void launch_rescore_slots(const uint64_t *ids, const uint64_t *counts, uint64_t nq, uint64_t ld, const uint64_t *coff, const uint32_t *labels,
+                          uint64_t id_offset, uint64_t *slot_key, uint32_t *slot_row, uint32_t *n_slots, uint32_t *rows_cnt, uint64_t *tkey,
+                          uint32_t *tslot, uint32_t glg, hipStream_t s);
+void launch_rescore_match(const uint32_t *labels, uint64_t n, const uint64_t *tkey, const uint32_t *tslot, uint32_t glg, bool fill, uint64_t q0,
+                          uint64_t nb, uint32_t *rows_cnt, uint32_t *cur, const uint64_t *ent_off, uint64_t *entries, hipStream_t s);
+void launch_rescore_prepare(uint64_t q0, uint64_t nb, const uint64_t *lims, const uint64_t *coff, const uint64_t *slot_key, const uint32_t *slot_row,
+                            const uint32_t *n_slots, const uint32_t *rows_cnt, const uint64_t *ent_off, const uint64_t *tab_off, uint64_t *entries,
+                            uint64_t *mins, uint32_t *cur, hipStream_t s);
+void launch_rescore_pairs(const float *X, uint32_t dim, const float *Q, const uint64_t *lims, const uint2 *items, uint64_t n_items,
+                          const uint64_t *entries, const uint64_t *ent_off, uint64_t *mins, const uint64_t *tab_off, int metric, const float *xsq,
+                          const float *qsq, const uint64_t *const *bits, hipStream_t s);
+void launch_rescore_finish(uint64_t q0, uint64_t nb, const uint64_t *lims, const uint64_t *coff, const uint32_t *slot_row, const uint32_t *n_slots,
+                           const uint64_t *mins, const uint64_t *tab_off, int mode, uint64_t id_offset, uint32_t k, uint64_t *out_idx, float *out_dist,
+                           uint64_t *out_cnt, hipStream_t s);
 // The label vote of the k-NN classifier (k_vote.hip, vote_plan.hpp): query b's list ids / dists [b][0 .. min(counts[b], ld)), 1 <= ld <=
 // VOTE_MAX_K, walked in the order given.  An entry votes iff its row carries a value in `labels` (u32 per LOCAL row = id - id_offset;
 // nullptr: a column never written; an id that is no row of the index is not gathered and does not vote) with the weight 1.0f

@@ -1278,6 +1278,61 @@ class GpuIndex:
                                                  L.vp(out_cnt_ptr), L.vp(out_exact_ptr), L.vp(stream)))
 
     @staticmethod
+    def rescore_groups_plan(lims, k: int, ld: int, mode="sum", column: int = 0, cand_count=None, rows=None, slots=None, budget: int = 0):
+        """vdb_rescore_groups_plan, no GPU needed -> (code, tiles, sub-chunk, scratch bytes); code 0: the forms accept the call.  The layout
+        (None without `rows`, the rows of each question's candidate groups together, or after a refusal): work items of 64 rows, questions
+        per sub-chunk under `budget` bytes (0: 256 MiB), scratch of the largest sub-chunk; `slots`: the distinct groups per question
+        (None: cand_count, or ld)."""
+        lm = np.ascontiguousarray(lims, dtype=np.uint64).ravel()
+        code = FUSE_GROUP_MODES.get(mode, -1) if isinstance(mode, str) else int(mode)
+        u64a = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint64).ravel()  # noqa: E731
+        cc, rw, sl = u64a(cand_count), u64a(rows), u64a(slots)
+        rc = C.c_int(-1)
+        tiles, sub, scratch = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.check(L.load().vdb_rescore_groups_plan(code, _ptr(lm, L.u64p) if lm.size else None, max(lm.size, 1) - 1, int(k), int(ld), int(column),
+                                                 _ptr(cc, L.u64p), _ptr(rw, L.u64p), _ptr(sl, L.u64p), int(budget), C.byref(rc), C.byref(tiles),
+                                                 C.byref(sub), C.byref(scratch)))
+        if rc.value or rw is None:
+            return rc.value, None, None, None
+        return 0, tiles.value, sub.value, scratch.value
+
+    def rescore_groups(self, queries, lims, cand_ids, cand_count, k: int, column: int, mode="sum", masks=None, mask_of=None):
+        """Exact late-interaction rescoring (vdb_flat_rescore_groups): question q owns the sub-queries lims[q] .. lims[q + 1] - 1 of
+        `queries` (1 to 32 each) and the first cand_count[q] ids of cand_ids [nq][ld] (ld <= 4096).  A candidate stands for its GROUP --
+        the rows that share its value of label column `column`; a row without one is a group of its own -- and every distinct group is
+        scored over ALL its rows: per sub-query the nearest row its mask allows (+inf: none), mode="sum" the f32 left fold of those
+        distances over the sub-queries, "min" their smallest.  Nothing depends on a fetch_k: these are the true scores.  `idx` carries each
+        group's representative (its nearest row over the sub-queries), ascending by (score, representative).  masks / mask_of as in
+        flat_knn_fused_groups, indexed by SUB-query.  k <= ld.
+        -> (idx [nq][k], dist [nq][k], count [nq]); slots past a count are zero."""
+        lm, code, _w = self._fuse_args(lims, mode, None, FUSE_GROUP_MODES)
+        q = _f32(queries)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        if q.shape[0] != int(lm[-1]):
+            raise ValueError(f"{q.shape[0]} query vectors for {int(lm[-1])} sub-queries")
+        nq = lm.size - 1
+        ci = np.ascontiguousarray(cand_ids, dtype=np.uint64)
+        ci = ci.reshape(nq, ci.size // nq) if nq else ci.reshape(0, 0)
+        cc = np.ascontiguousarray(cand_count, dtype=np.uint64).ravel()
+        if cc.size != nq:
+            raise ValueError(f"{cc.size} candidate counts for {nq} questions")
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, q.shape[0])
+        out, ptrs = self._knn_outputs(nq, k)
+        L.check(self._lib.vdb_flat_rescore_groups(self._h, _ptr(q, L.f32p), _ptr(lm, L.u64p), nq, q.shape[1], _ptr(ci, L.u64p) if ci.size else None,
+                                                  _ptr(cc, L.u64p) if nq else None, ci.shape[1], int(k), code, int(column), arr, n_masks, mo_p, *ptrs))
+        return self._knn_cut(out, k)
+
+    def rescore_groups_device(self, q_ptr: int, lims, cand_ids_ptr: int, cand_count_ptr: int, ld: int, k: int, column: int, out_idx_ptr: int,
+                              out_dist_ptr: int, out_cnt_ptr: int, mode="sum", masks=None, mask_of=None, stream: int = 0):
+        """Device form (vdb_flat_rescore_groups_device): lims on the host; the sub-queries' vectors, the candidates [nq][ld] (u64), their
+        u64 counts and the outputs on this GPU; a candidate id that is no row of this index raises and leaves the outputs untouched"""
+        lm, code, _w = self._fuse_args(lims, mode, None, FUSE_GROUP_MODES)
+        arr, n_masks, mo_p, _keep = self._grouped_mask_args(masks, mask_of, int(lm[-1]))
+        L.check(self._lib.vdb_flat_rescore_groups_device(self._h, L.vp(q_ptr), _ptr(lm, L.u64p), lm.size - 1, self.dim, L.vp(cand_ids_ptr),
+                                                         L.vp(cand_count_ptr), int(ld), int(k), code, int(column), arr, n_masks, mo_p,
+                                                         L.vp(out_idx_ptr), L.vp(out_dist_ptr), L.vp(out_cnt_ptr), L.vp(stream)))
+
+    @staticmethod
     def _like_lists(lists, nq=None):
         """(lims, ids) of a list of id lists as u64 arrays: query q's ids are ids[lims[q]:lims[q + 1]]; None -> (None, None)"""
         if lists is None:

@@ -38,7 +38,9 @@ matches, the examples left out of the answer -- the query vector is made on the 
 search_fused / batch_search_fused join SEVERAL searches of one question -- several query vectors, or one vector under several filters --
 into one ranked answer on the device, by reciprocal rank fusion or by the smallest distance; the batch is one library call
 (GpuIndex.flat_knn_fused).  With `group_by` they rank DOCUMENTS, the rows that share a value of a metadata key -- also by the
-late-interaction sum, fusion="sum" -- still one library call (GpuIndex.flat_knn_fused_groups).
+late-interaction sum, fusion="sum" -- still one library call (GpuIndex.flat_knn_fused_groups).  That sum is a lower bound while a
+list is cut at fetch_k; `rescore=r` adds the second stage: the r best candidate documents scored over ALL their matching rows
+(GpuIndex.rescore_groups), the top k by true score, and with return_exact a certificate that no other document can enter it.
 get(key, filter, limit) returns the vectors and metadata of the matching rows, and every search takes `with_vectors`: the hits' vectors
 ride along, all of a call's from one bulk fetch (GpuIndex.get_rows / get_rows_mask); extract_data reads the table with one such call.
 update_metadata(key, pattern, changes) / batch_update_metadata change the METADATA of the matching rows in place: row ids, vectors, the
@@ -59,7 +61,7 @@ import numpy as np
 
 from ._lib import VdbError
 from .index import FUSE_MAX_FETCH, LIKE_MAX_EXAMPLES, MMR_MAX_FETCH, ROW_NONE, VOTE_MAX_K, VOTE_MODES, GpuIndex, RowMask, parse_dist, project_vectors
-from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, cap_groups, filter_key, fuse_groups, filter_patterns, has_predicates, is_expression, stale_filters, vote_values
+from .labels import LABEL_NONE, MASK_MAX_SET_BITS, AnyOf, LabelCodec, LabelTerm, Not, _f32_order_key, cap_groups, filter_key, fuse_groups, filter_patterns, has_predicates, is_expression, stale_filters, vote_values
 from .labels import matches as value_matches
 
 _DIST_STR = {0: "l2sqr", 1: "cosine"}
@@ -990,17 +992,17 @@ class VecDB:
 
     def search_fused(self, key: str, queries, k: int, fusion: str = "rrf", weights=None, filters=None, fetch_k: int | None = None,
                      rrf_c: float = 60.0, upper_bound: float | None = None, with_vectors: bool = False, group_by: str | None = None,
-                     return_exact: bool = False):
+                     return_exact: bool = False, rescore: int | None = None):
         """Several searches of ONE question joined into one ranked answer: batch_search_fused for one question (it states the rule).
         `queries`: the vectors of the question; `weights`: None or one per vector; `filters`: None, one filter for every vector, or one
         per vector.  Entries are (metadata, score[, vector]); with return_exact the result is (entries, exact)."""
         res = self.batch_search_fused(key, [queries], k, fusion, None if weights is None else [weights], None if filters is None else [filters],
-                                      fetch_k, rrf_c, upper_bound, with_vectors, group_by, return_exact)
+                                      fetch_k, rrf_c, upper_bound, with_vectors, group_by, return_exact, rescore)
         return (res[0][0], res[1][0]) if return_exact else res[0]
 
     def batch_search_fused(self, key: str, query_groups, k: int, fusion: str = "rrf", weights=None, filters=None, fetch_k: int | None = None,
                            rrf_c: float = 60.0, upper_bound: float | None = None, with_vectors: bool = False, group_by: str | None = None,
-                           return_exact: bool = False):
+                           return_exact: bool = False, rescore: int | None = None):
         """Fused multi-query search for a batch of questions in ONE library call (GpuIndex.flat_knn_fused).  `query_groups`: per
         question its 1 to 32 query vectors (paraphrases, a HyDE passage, sub-questions -- or one vector repeated under several filters).
         Every vector is searched exactly, from the table's Flat rows, for its `fetch_k` nearest matching rows (default 4 k, raised to k,
@@ -1023,7 +1025,19 @@ class VecDB:
         batch_search(group_by=) gives it one, and a key that cannot have a column (a 17th key) or whose values a dictionary cannot keep
         apart takes the host fallback: batch_search's lists at fetch_k, joined by labels.fuse_groups over the metadata values.
         `return_exact` (group_by only): the result becomes (answers, exact) -- exact[q] is True when the whole table would give this
-        answer ("rrf", "sum": no list was cut at fetch_k; "min": that, or the k-th score lies strictly before every cut)."""
+        answer ("rrf", "sum": no list was cut at fetch_k; "min": that, or the k-th score lies strictly before every cut).
+        `rescore` (group_by with "sum" or "min" only; an integer r >= k): the second stage of late interaction.  The fused call runs at
+        k' = min(r, fetch_k) candidate groups and GpuIndex.rescore_groups scores those groups over ALL their matching rows -- the entries
+        are the top k by TRUE score (no list's last distance stands in for a missing group), both calls under the one read guard.
+        exact[q] is then True when the fused call's own flag is set, or when it returned exactly k' groups, the answer has k entries and the
+        k-th rescored score lies STRICTLY before the last candidate's fused score: every group that was no candidate has a fused lower
+        bound at or beyond that score, and f32 addition is monotone, so none of them can enter the top k.  A key without a usable label
+        column has no device path here: ValueError."""
+        if rescore is not None:
+            if group_by is None or fusion not in ("sum", "min"):
+                raise ValueError("rescore needs group_by and fusion='sum' or 'min'")
+            if int(rescore) < int(k):
+                raise ValueError(f"rescore {int(rescore)} is below k = {int(k)}")
         if fusion not in ("rrf", "min") and not (fusion == "sum" and group_by is not None):
             raise ValueError(f"fusion {fusion!r}: 'rrf' or 'min'" + (", or 'sum'" if group_by is not None else " ('sum' needs group_by)"))
         if upper_bound is not None and fusion != "min":
@@ -1093,9 +1107,17 @@ class VecDB:
             exact = None
             if group_by is None:
                 idx, dist, cnt = ix.flat_knn_fused(q, lims, k, fk, fusion, w, rrf_c, masks, mask_of)
-            elif t.codec.value_codes(group_by) is not None:
+            elif t.codec.value_codes(group_by) is not None and rescore is None:
                 idx, dist, cnt, exact = ix.flat_knn_fused_groups(q, lims, k, fk, t.codec.column_of(group_by), fusion, w, rrf_c, masks, mask_of,
                                                                  return_exact=True)
+            elif t.codec.value_codes(group_by) is not None:
+                col, kc = t.codec.column_of(group_by), min(int(rescore), fk)
+                c_idx, c_dist, c_cnt, c_exact = ix.flat_knn_fused_groups(q, lims, kc, fk, col, fusion, None, rrf_c, masks, mask_of, return_exact=True)
+                idx, dist, cnt = ix.rescore_groups(q, lims, c_idx, c_cnt, k, col, fusion, masks, mask_of)
+                exact = [bool(c_exact[j]) or (int(k) > 0 and int(c_cnt[j]) == kc and int(cnt[j]) == int(k)
+                                              and _f32_order_key(dist[j, int(k) - 1]) < _f32_order_key(c_dist[j, kc - 1])) for j in range(nq)]
+            elif rescore is not None:
+                raise ValueError(f"rescore: the key {group_by!r} has no usable label column (a 17th key, or values a dictionary cannot keep apart)")
             else:
                 idx, dist, cnt, exact = self._fused_groups_on_host(t, q, lims, k, fk, group_by, fusion, w, rrf_c, masks, mask_of)
             ub = np.float32(np.inf) if upper_bound is None else np.float32(upper_bound)
