@@ -14,7 +14,8 @@ automatic state counts calls.
 Tables: f32 22 037 x 128 (= 16 * 1377 + 5 = 192 * 114 + 149: ragged last tiles, two 64-wide k blocks so that the 8-bit and fp16 filters can
 be forced) under L2Sqr and Cosine, f32 1003 x 128 (small-table paths; rows 900 .. 939 sit within 0.05 of row 7: the dense spot of the
 self-join rows), u8 20 003 x 128.  Two label columns on the f32 tables: 0 = row % 5 (row % 11 == 0: none), 1 = row // 4 % 50 (row % 13 == 0: none).
-Queries: rows of the table plus noise; query 5 of each set has a NaN coordinate (the hand-on / redo path)."""
+Queries: rows of the table plus noise; query 5 of each set has a NaN coordinate (the hand-on / redo path).  The rescoring rows take their
+candidates from the oracle's lists and score whole groups of label column 1 (tests/rescore_ref.py)."""
 import numpy as np
 
 import dbscan_ref
@@ -24,6 +25,7 @@ import fuse_ref
 import like_ref
 import lof_ref
 import mmr_ref
+import rescore_ref
 
 DIM, N_BIG, N_SMALL, N_U8 = 128, 22037, 1003, 20003
 NONE = 0xFFFFFFFF
@@ -43,6 +45,7 @@ COUNTERS = (
     "silhouette_calls", "silhouette_rows", "flat_grouped_calls", "flat_grouped_queries", "flat_grouped_rounds", "flat_grouped_exhausted_queries",
     "flat_vote_queries", "flat_vote_scratch", "flat_mmr_calls", "flat_mmr_queries", "flat_like_calls", "flat_like_queries", "like_example_rows",
     "flat_fused_calls", "flat_fused_queries", "flat_fused_lists", "flat_fused_groups_calls", "flat_fused_groups_queries", "flat_fused_groups_lists",
+    "flat_rescore_calls", "flat_rescore_questions", "flat_rescore_rows",
     "update_calls", "update_rows", "fetch_calls", "fetch_rows", "fetch_chunks", "fetch_direct", "labels_scatter_calls", "labels_scatter_rows",
 )
 ROUTE_DEFAULTS = {"flat_small": 0, "flat_half": 0, "flat_i8": 0, "flat_u8": 0, "flat_filtered_direct_max": 8192, "flat_i8_refine": 1,
@@ -313,6 +316,37 @@ def ref_fused_groups(q0, lims, k, fetch_k, column, mode):
     return check
 
 
+RESCORE_LD, RESCORE_MASK_OF = 16, [0, 1, 1, 0, 1, 0, 0, 1]
+
+
+def rescore_cands(env, q0, lims):
+    """the candidates of the rescoring rows: question q takes the oracle's first 5 rows of each of its sub-queries, list after list (so
+    10, 15 and 15 of ld = 16; neighbours share label codes and lists share rows: duplicates of both kinds) -> (ids [nq][16], counts)"""
+    oi = env.D.order(env.kind, q0, q0 + lims[-1], 12)[0]
+    cand, cnt = np.zeros((len(lims) - 1, RESCORE_LD), dtype=np.uint64), np.zeros(len(lims) - 1, dtype=np.uint64)
+    for q in range(len(lims) - 1):
+        ids = np.concatenate([oi[s][:5] for s in range(lims[q], lims[q + 1])])
+        cand[q, :len(ids)], cnt[q] = ids, len(ids)
+    return cand, cnt
+
+
+def ref_rescore(q0, lims, k, column, mode, masked=False):
+    def check(env, got):
+        nsub = lims[-1]
+        key = ("rescore-dm", env.kind, q0, nsub)
+        if key not in env.D._memo:  # the dense distance table of the sub-queries, from the oracle's order at k = n
+            oi, od = env.D.order(env.kind, q0, q0 + nsub, env.n)
+            dm = np.zeros((nsub, env.n), np.float32)
+            np.put_along_axis(dm, oi.astype(np.int64), od, axis=1)
+            env.D._memo[key] = dm
+        cand, cnt = rescore_cands(env, q0, lims)
+        allows = [env.D.allow_a[:env.n], env.D.allow_b[:env.n]] if masked else None
+        idx, bits, count, _rows = rescore_ref.expect(env.D._memo[key], (env.D.lab0, env.D.lab1)[column][:env.n], lims, cand, cnt, k, mode,
+                                                     allows=allows, mask_of=RESCORE_MASK_OF if masked else None)
+        assert np.array_equal(got[2], count) and np.array_equal(got[0], idx) and same(got[1], bits.view(np.float32)), "rescore"
+    return check
+
+
 def _self_lists(env, radius):
     oi, od = env.D.self_order()
     return [[(int(i), d) for i, d in zip(oi[r][od[r] <= radius], od[r][od[r] <= radius])] for r in range(N_SMALL)]
@@ -488,8 +522,24 @@ def _build_cases():
         ref_fused(8, LIMS, 5, 12, "rrf"), family="fused")
     add("fused-min", "big_l2", rerank(lambda e: e.ix.flat_knn_fused(e.q[8:16], LIMS, 5, 12, "min")), ("flat_fused_lists",),
         ref_fused(8, LIMS, 5, 12, "min"), family="fused")
+    # the exact rescoring borrows grp_aux, grp_ids, grp_dist, grp_cnt, grp_table, grp_q, lists, dense and qsq; it leaves tslot uncleared and
+    # its entry lists rely on a padding fill.  Over label column 1: 50 codes of about 400 rows, and unlabelled rows.  The rows stand on both
+    # sides of fused_groups, which fills the same grp_* buffers with another layout: test_call_history_gpu.py takes as a row's polluter the
+    # next row of another family, so rescore-sum and rescore-min run BEHIND fused_groups, and fused_groups behind rescore-masks
+    def rescore(mode, masked=False):
+        def fn(e):
+            e.route(2, flat_i8=2)
+            cand, cnt = rescore_cands(e, 8, LIMS)
+            kw = {"masks": [e.mask("a"), e.mask("b")], "mask_of": RESCORE_MASK_OF} if masked else {}
+            return e.ix.rescore_groups(e.q[8:16], LIMS, cand, cnt, 5, 1, mode, **kw)
+        return fn
+    for kind, tag in (("big_l2", ""), ("big_cos", "cos-")):
+        add(f"rescore-{tag}sum", kind, rescore("sum"), ("flat_rescore_rows",), ref_rescore(8, LIMS, 5, 1, "sum"))
+        add(f"rescore-{tag}min", kind, rescore("min"), ("flat_rescore_rows",), ref_rescore(8, LIMS, 5, 1, "min"))
     add("fused_groups", "big_l2", rerank(lambda e: e.ix.flat_knn_fused_groups(e.q[8:16], LIMS, 5, 12, 1, "sum", return_exact=True)),
         ("flat_fused_groups_lists",), ref_fused_groups(8, LIMS, 5, 12, 1, "sum"))
+    for kind, tag in (("big_l2", ""), ("big_cos", "cos-")):
+        add(f"rescore-{tag}masks", kind, rescore("sum", masked=True), ("flat_rescore_rows",), ref_rescore(8, LIMS, 5, 1, "sum", masked=True))
     add("fuse_lists_device", "big_l2", lambda e: fuse_lists_device(e, e.D.order(e.kind, 8, 16, 12)[0]), (), ref_fused(8, LIMS, 5, 12, "rrf"),
         family="fused")
     add("vote", "big_l2", rerank(lambda e: e.ix.flat_knn_vote(e.q[8:24], 9, 0, 3)), ("flat_vote_queries",))

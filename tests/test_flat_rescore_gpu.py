@@ -1,13 +1,13 @@
 """GPU: the exact late-interaction rescoring of candidate documents (GpuIndex.rescore_groups / rescore_groups_device,
 vdb_flat_rescore_groups*) on 575 rows whose label groups hold 1, 63, 64, 65 and 150 rows (a group ends at, starts at and spans a tile of 64
 entries), interleaved over the table, with unlabelled rows, identical rows, a NaN row inside a group and a group of NaN rows only.  The
-pair distances are the CPU oracle's (oracle.flat_knn_batch at k = n); the reference below takes per group and sub-query the smallest
-under (distance, row) with NaN last, folds a strict np.float32 sum over the sub-queries and sorts by (score, representative).  The
-criterion is equality of bits (NaN scores compare as NaN)."""
+pair distances are the CPU oracle's (oracle.flat_knn_batch at k = n); the reference (tests/rescore_ref.py) takes per group and sub-query
+the smallest under (distance, row) with NaN last, folds a strict np.float32 sum over the sub-queries and sorts by (score, representative).
+The criterion is equality of bits (NaN scores compare as NaN).  One shape only: tests/test_flat_rescore_shapes_gpu.py goes past it."""
 import numpy as np
 import pytest
 
-from fuse_groups_ref import order_key
+import rescore_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -53,35 +53,9 @@ class Data:
             np.put_along_axis(self.dm[kind], oi.astype(np.int64), od, axis=1)
 
     def expect(self, kind, k, mode, labels=LAB, allows=None, mask_of=None, off=0, counts=COUNTS):
-        """-> (idx, score bits, count, candidate rows evaluated)"""
-        nq, kk = len(SIZES), max(k, 1)
-        idx, bits, cnt, rows = np.zeros((nq, kk), np.uint64), np.zeros((nq, kk), np.uint32), np.zeros(nq, np.uint64), 0
-        for q, c in enumerate(counts):
-            seen, out = set(), []
-            for r in CANDS[:c].tolist():
-                g = ("row", r) if labels[r] == NONE else ("code", int(labels[r]))
-                if g in seen:
-                    continue
-                seen.add(g)
-                members = [r] if g[0] == "row" else np.flatnonzero(labels == labels[r]).tolist()
-                rows += len(members)
-                per = []  # per sub-query (order key, s, row, distance) of the group's nearest allowed row
-                acc = np.float32(0.0)
-                for s, j in enumerate(range(int(LIMS[q]), int(LIMS[q + 1]))):
-                    ok = [m for m in members if allows is None or allows[int(mask_of[j])][m]]
-                    best = min(((order_key(self.dm[kind][j, m]), m) for m in ok), default=None)
-                    with np.errstate(all="ignore"):
-                        acc = np.float32(acc + (np.float32(np.inf) if best is None else self.dm[kind][j, best[1]]))
-                    if best is not None:
-                        per.append((best[0], s, best[1]))
-                rep = min(per)[2] if per else r
-                score = acc if mode == "sum" else (self.dm[kind][int(LIMS[q]) + min(per)[1], rep] if per else np.float32(np.inf))
-                out.append((order_key(score), rep, score))
-            out.sort()
-            cnt[q] = min(k, len(out))
-            for i, (_, rep, score) in enumerate(out[:k]):
-                idx[q, i], bits[q, i] = rep + off, np.float32(score).view(np.uint32)
-        return idx[:, :k], bits[:, :k], cnt, rows
+        """-> (idx, score bits, count, candidate rows evaluated) of tests/rescore_ref.py"""
+        cand, cnt = _cands(off, counts)
+        return rescore_ref.expect(self.dm[kind], labels, LIMS, cand, cnt, k, mode, allows=allows, mask_of=mask_of, id_offset=off)
 
 
 @pytest.fixture(scope="module", params=(1, 3, 4, 33, 130))  # the element-wise tail, a 32-slice boundary, several slices with a tail
